@@ -38,6 +38,12 @@ The same line carries
   cpu_baseline  on rank 0: oracle/wc_oracle.c on this box's host cores - the reference's CPU algorithms restated (`kind: port`: OSQP
                 for the MPC, a dense active set for the IK) and, as `same_algorithm_qps`, the device kernels' OWN direct methods in
                 plain C, so that the record separates "a better algorithm" from "an MI355X".
+
+`--dump-outputs DIR` writes what the timed path returned in its LAST timed step as DIR/<name>.npy (rank 0's shard): the qp workload's
+QpStep outputs (u0, mpc_status, mpc_active, mpc_margin, dq, ik_status, active_lower, active_upper, iters), the tick workload's robot
+state after the last tick, the kin workload's Jacobians and poses.  Rows are robots in instance order; every file is float64 (integer
+outputs and bit masks converted exactly); over 64 MB in all, a fixed seeded sample of robots is kept and rows.npy names them.  The
+inputs depend on the arguments only, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -93,7 +99,32 @@ def parse_args(argv=None):
     ap.add_argument("--tick-batch", type=int, default=8192, help="`tick` object: robots per GPU (BASELINE configs[3]/[4]: 65536 over 8 GPUs)")
     ap.add_argument("--tick-ticks", type=int, default=1000, help="`tick` object: ticks of the timed wcqp_tick_run call")
     ap.add_argument("--exchange-steps", type=int, default=10, help="N > 1: steps of the second pass that measures the exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
     return ap.parse_args(argv)
+
+
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: bytes of .npy files in all, headers included
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: one DIR/<name>.npy per array (leading axis = robot), float32 / float64 as they are and every other dtype
+    converted to float64 (exact for the int32 / uint32 outputs).  When the files would exceed `budget` bytes, every array keeps the
+    same fixed, seeded sample of robots (sorted) and rows.npy holds their indices.  Returns what was written."""
+    out = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for k, a in ((k, np.asarray(v)) for k, v in arrays.items())}
+    n = len(next(iter(out.values())))
+    hdr = 256 * (len(out) + 1)                     # an .npy header of these shapes is 128 bytes
+    data = sum(a.nbytes for a in out.values())
+    if data + hdr > budget:
+        keep = int((budget - hdr) // (data / n + 8))
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        out = {k: a[rows] for k, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    if "rows" not in out and os.path.exists(os.path.join(dirname, "rows.npy")):
+        os.remove(os.path.join(dirname, "rows.npy"))      # a sample index left by an earlier, larger run
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------- launching the ranks
@@ -403,6 +434,24 @@ def bench_qp(c):
     for st_ in streams:
         if st_ is not cur:
             cur.wait_stream(st_)
+
+    # ---- --dump-outputs: the last timed step's outputs, copied out before the kernel passes below reuse the buffers
+    if args.dump_outputs and rank == 0:
+        last = W + R * S - 1
+        if exch_value:
+            got, inst = slabs.out_views(), np.arange(B)
+        else:
+            o = outs[last % P]
+            got = dict(u0=o["u0"], mpc_status=o["mstat"], mpc_active=o["mact"], mpc_margin=o["mmar"], dq=o["dq"], ik_status=o["istat"],
+                       active_lower=o["ilo"], active_upper=o["iup"], iters=o["iit"])
+            inst = (np.arange(B) - (last % K) * max(1, B // K)) % B        # output row r of a step that read set k is instance (r - k B / K) mod B
+        host = {}
+        for k, v in got.items():
+            a = v.cpu().numpy()
+            a = a.view(np.uint32) if k in ("mpc_active", "active_lower", "active_upper") else a
+            host[k] = np.empty_like(a)
+            host[k][inst] = a
+        dump_outputs(args.dump_outputs, host)
 
     # ---- sanity + goldens: the timed work really solved the problems, and solved them right (every way's LAST batch of the last repeat)
     if exch_value:
@@ -769,7 +818,7 @@ def tick_measure(c, B, T, W, kin_mode, first=0, handoff="fused", ticks_per_launc
     state_rw = 2 * 8 * (16 + 10 + 23 * 2) + 87 * 8 + 23 * 8 + 16 + 8       # mst + hand + q_des/dq_prev r/w, pose block, dq out, one reference stage, words
     jac_bytes = 4464 if not kin_mode else {"fused": 0, "compact": 2 * 1440 + 288, "dense": 2 * 4464 + 288}[handoff]
     res = {"dev_ms": dev_ms, "ik_fail": ik_fail, "mpc_fail": mpc_fail, "hot_try": hot_try, "hot_hit": hot_hit, "stopped": stopped,
-           "tick": min(x["tick"] for x in states), "own_bytes_model": state_rw + jac_bytes, "check": check, "n_groups": len(pipes)}
+           "tick": min(x["tick"] for x in states), "own_bytes_model": state_rw + jac_bytes, "check": check, "n_groups": len(pipes), "states": states}
     return res, elapsed
 
 
@@ -840,6 +889,10 @@ def bench_tick(c):
     stopped_all = int(round(reduce_over_ranks(c, float(r["stopped"]), "sum")))
     value = (2 * B * world * args.steps - stopped_all) / elapsed
     dev_ms = r["dev_ms"]
+    if args.dump_outputs and c.rank == 0:
+        # the robots' state after the last timed tick, as wcqp_tick_download hands it back (robot groups are consecutive rows)
+        dump_outputs(args.dump_outputs, {k: np.concatenate([x[k] for x in r["states"]])
+                                         for k in ("q_des", "dcm", "com", "active_lower", "active_upper", "mpc_fail", "ik_fail", "hot_try", "hot_hit")})
     if kin_mode:
         launches = {"fused": "1 launch per run() call: ik4_kernel<TICK, fused kinematics> walks through the ticks (kinematics, MPC of the next tick, glue, IK, post step)",
                     "compact": "2 launches per tick: kin_jacobians_kernel<TICK, compact>, ik4_kernel<TICK>",
@@ -905,6 +958,8 @@ def bench_kin(c):
     barrier()
     elapsed = reduce_over_ranks(c, time.perf_counter() - t0)
     k_ms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs and c.rank == 0:
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in (("J_left", JL), ("J_right", JR), ("J_neck", JN), ("J_com", JC), ("state", state))})
     bytes_per = 12 * 8 + 23 * 8 + (6 + 6 + 3 + 3) * 29 * 8 + 36 * 8           # base + q in; Jacobians + actual poses out
     return {
         "metric": "robots/sec through the kinematics kernel (auxiliary; NOT the BASELINE metric)",
