@@ -40,6 +40,8 @@ struct wcqp_ik_s {
     IkDeviceParams hp{};
     IkDeviceParams* d_prm = nullptr;
     wcqp::DeviceScratch scratch;
+    wcqp::IkRoute route = wcqp::IkRoute::NULLSPACE_32;     // the kernel this handle runs (wcqp_ik_create)
+    bool list_pass = false;           // BASE_ELIM with jacobian_structure AUTO: the general kernel re-solves the flagged instances
 };
 
 namespace {
@@ -61,7 +63,7 @@ int ensure_device(wcqp_ik_s* h) {
 namespace wcqp {
 int ik_prepare(wcqp_ik_t h) { return h ? ensure_device(h) : WCQP_E_INVALID; }
 const void* ik_device_params(wcqp_ik_t h) { return h ? h->d_prm : nullptr; }
-bool ik_fast_ok(wcqp_ik_t h) { return h && h->hp.fast_ok != 0; }
+IkRoute ik_route(wcqp_ik_t h) { return h->route; }
 }  // namespace wcqp
 
 extern "C" {
@@ -135,6 +137,19 @@ int wcqp_ik_create(const wcqp_ik_params* params, wcqp_ik_t* out) {
             for (int c = 0; c < 3; ++c) d.Lt[3 * r + c] = pd ? L[3 * c + r] : 0.0;
         if (!pd) d.fast_ok = 0;
     }
+    // the one place that decides which kernel the handle runs (d.fast_ok implies use_com_as_constraint)
+    {
+        using wcqp::IkRoute;
+        const int alg = params->algorithm;
+        const bool dflt = alg == WCQP_IK_ALG_DEFAULT || alg == WCQP_IK_ALG_BASE_ELIM;
+        const bool com = params->use_com_as_constraint != 0;
+        if (dflt && d.fast_ok && params->jacobian_structure != WCQP_IK_JAC_GENERAL) h->route = IkRoute::BASE_ELIM;
+        else if ((dflt || alg == WCQP_IK_ALG_NULLSPACE_16L) && com) h->route = IkRoute::NULLSPACE_16L;
+        else if (alg == WCQP_IK_ALG_SWEEP) h->route = IkRoute::SWEEP;
+        else if (com && alg != WCQP_IK_ALG_NULLSPACE) h->route = IkRoute::NULLSPACE_32_MFMA;
+        else h->route = IkRoute::NULLSPACE_32;
+        h->list_pass = h->route == IkRoute::BASE_ELIM && params->jacobian_structure == WCQP_IK_JAC_AUTO;
+    }
     *out = h;
     return WCQP_OK;
 }
@@ -167,38 +182,34 @@ int wcqp_ik_solve_device(wcqp_ik_t h, int32_t batch,
     if (batch == 0) return WCQP_OK;
     const int rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
-    // default: base elimination + range space (ik4.hip) for MIXED-representation Jacobians, with the general 16-lane
-    // kernel behind it for instances (or handles) that do not qualify
-    const bool want4 = h->p.algorithm == WCQP_IK_ALG_BASE_ELIM || h->p.algorithm == WCQP_IK_ALG_DEFAULT;
-    if (want4 && h->hp.fast_ok && h->p.jacobian_structure != WCQP_IK_JAC_GENERAL) {
-        const int rc4 = wcqp_ik::ik4_launch(h->d_prm, batch, J_left, J_right, J_neck, J_com, q, state, dq, status,
-                                            active_lower, active_upper, foot_err, iters, (hipStream_t)stream);
-        if (rc4 != WCQP_OK || h->p.jacobian_structure == WCQP_IK_JAC_MIXED) return rc4;
-        return wcqp_ik::ik3_launch_list(h->d_prm, batch, J_left, J_right, J_neck, J_com, q, state, dq, status,
-                                        active_lower, active_upper, foot_err, iters, (hipStream_t)stream);
+    const wcqp_ik::IkIo io{J_left, J_right, J_neck, J_com, q, state, dq, status, active_lower, active_upper, foot_err, iters};
+    const hipStream_t s = (hipStream_t)stream;
+    switch (h->route) {
+    case wcqp::IkRoute::BASE_ELIM: {
+        // base elimination + range space (ik4.hip) for MIXED-representation Jacobians, with the general 16-lane kernel behind
+        // it for the instances that do not qualify
+        const int rc4 = wcqp_ik::ik4_launch(h->d_prm, batch, io, s);
+        return rc4 != WCQP_OK || !h->list_pass ? rc4 : wcqp_ik::ik3_launch_list(h->d_prm, batch, io, s);
     }
-    const bool use16 = want4 || h->p.algorithm == WCQP_IK_ALG_NULLSPACE_16L;
-    if (use16 && h->p.use_com_as_constraint)
-        return wcqp_ik::ik3_launch(h->d_prm, batch, J_left, J_right, J_neck, J_com, q, state, dq, status,
-                                   active_lower, active_upper, foot_err, iters, (hipStream_t)stream);
-    if (h->p.algorithm != WCQP_IK_ALG_SWEEP)
-        return wcqp_ik::ik2_launch(h->d_prm, h->p.use_com_as_constraint != 0, h->p.algorithm != WCQP_IK_ALG_NULLSPACE, batch, J_left, J_right, J_neck, J_com,
-                                   q, state, dq, status, active_lower, active_upper, foot_err, iters, (hipStream_t)stream);
+    case wcqp::IkRoute::NULLSPACE_16L: return wcqp_ik::ik3_launch(h->d_prm, batch, io, s);
+    case wcqp::IkRoute::NULLSPACE_32:
+    case wcqp::IkRoute::NULLSPACE_32_MFMA:
+        return wcqp_ik::ik2_launch(h->d_prm, h->p.use_com_as_constraint != 0, h->route == wcqp::IkRoute::NULLSPACE_32_MFMA, batch, io, s);
+    case wcqp::IkRoute::SWEEP:
 #ifdef WCQP_DIAG_KERNELS
-    const unsigned grid = (unsigned)((batch + 1) / 2);
-    if (h->p.use_com_as_constraint)
-        hipLaunchKernelGGL(ik_kernel<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream,
-                           h->d_prm, batch, J_left, J_right, J_neck, J_com, q, state,
-                           dq, status, active_lower, active_upper, foot_err, iters);
-    else
-        hipLaunchKernelGGL(ik_kernel<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream,
-                           h->d_prm, batch, J_left, J_right, J_neck, J_com, q, state,
-                           dq, status, active_lower, active_upper, foot_err, iters);
-    WCQP_HIP_TRY(hipGetLastError());
-    return WCQP_OK;
+        if (h->p.use_com_as_constraint)
+            hipLaunchKernelGGL(ik_kernel<true>, dim3((unsigned)((batch + 1) / 2)), dim3(64), 0, s, h->d_prm, batch,
+                               J_left, J_right, J_neck, J_com, q, state, dq, status, active_lower, active_upper, foot_err, iters);
+        else
+            hipLaunchKernelGGL(ik_kernel<false>, dim3((unsigned)((batch + 1) / 2)), dim3(64), 0, s, h->d_prm, batch,
+                               J_left, J_right, J_neck, J_com, q, state, dq, status, active_lower, active_upper, foot_err, iters);
+        WCQP_HIP_TRY(hipGetLastError());
+        return WCQP_OK;
 #else
-    return WCQP_E_UNSUPPORTED;            // refused at create already
+        return WCQP_E_UNSUPPORTED;            // refused at create already
 #endif
+    }
+    return WCQP_E_INVALID;
 }
 
 }  // extern "C"
@@ -208,8 +219,7 @@ namespace wcqp {
 // base-eliminated kernel; WCQP_E_UNSUPPORTED = "make the two calls" (not an error)
 int qp_pair_enqueue(wcqp_mpc_t mpc, wcqp_ik_t h, int batch, const wcqp_qp_step& s) {
     if (!mpc || !h || batch < 1 || !s.x0 || !s.J_left || s.mpc_stream != s.ik_stream) return WCQP_E_UNSUPPORTED;
-    const bool want4 = h->p.algorithm == WCQP_IK_ALG_BASE_ELIM || h->p.algorithm == WCQP_IK_ALG_DEFAULT;
-    if (!(want4 && h->hp.fast_ok && h->p.jacobian_structure != WCQP_IK_JAC_GENERAL)) return WCQP_E_UNSUPPORTED;
+    if (h->route != IkRoute::BASE_ELIM) return WCQP_E_UNSUPPORTED;
     if (s.ref_len < 1 || !s.ref || !s.u_prev || !s.hull_A || !s.hull_b || !s.hull_nc || !s.u0 || !s.mpc_status) return WCQP_E_INVALID;
     if (!s.J_right || !s.J_neck || !s.J_com || !s.q || !s.state || !s.dq || !s.ik_status) return WCQP_E_INVALID;
     int rc = ensure_device(h);
@@ -218,13 +228,11 @@ int qp_pair_enqueue(wcqp_mpc_t mpc, wcqp_ik_t h, int batch, const wcqp_qp_step& 
     if (rc != WCQP_OK) return rc;
     wcqp_mpc::MpcDeviceConsts c;
     mpc_device_consts(mpc, &c);
-    rc = wcqp_ik::ik4_launch_pair(h->d_prm, batch, s.J_left, s.J_right, s.J_neck, s.J_com, s.q, s.state, s.dq, s.ik_status,
-                                  s.active_lower, s.active_upper, s.foot_err, s.iters,
-                                  c, s.x0, s.ref, s.ref_len, s.u_prev, s.hull_A, s.hull_b, s.hull_nc, s.u0, s.mpc_status, s.mpc_active, s.mpc_margin,
-                                  (hipStream_t)s.ik_stream);
-    if (rc != WCQP_OK || h->p.jacobian_structure == WCQP_IK_JAC_MIXED) return rc;
-    return wcqp_ik::ik3_launch_list(h->d_prm, batch, s.J_left, s.J_right, s.J_neck, s.J_com, s.q, s.state, s.dq, s.ik_status,
-                                    s.active_lower, s.active_upper, s.foot_err, s.iters, (hipStream_t)s.ik_stream);
+    const wcqp_ik::IkIo io{s.J_left, s.J_right, s.J_neck, s.J_com, s.q, s.state, s.dq, s.ik_status, s.active_lower, s.active_upper, s.foot_err, s.iters};
+    const hipStream_t st = (hipStream_t)s.ik_stream;
+    rc = wcqp_ik::ik4_launch_pair(h->d_prm, batch, io, c, s.x0, s.ref, s.ref_len, s.u_prev, s.hull_A, s.hull_b, s.hull_nc,
+                                  s.u0, s.mpc_status, s.mpc_active, s.mpc_margin, st);
+    return rc != WCQP_OK || !h->list_pass ? rc : wcqp_ik::ik3_launch_list(h->d_prm, batch, io, st);
 }
 }  // namespace wcqp
 
@@ -266,31 +274,20 @@ int wcqp_qp_plan_create(wcqp_mpc_t mpc, wcqp_ik_t ik, int32_t batch, int32_t n_s
         if (!ik_only && (!s.x0 || !s.ref || s.ref_len < 1 || !s.u_prev || !s.hull_A || !s.hull_b || !s.hull_nc || !s.u0 || !s.mpc_status)) return WCQP_E_INVALID;
         if (!mpc_only && (!s.J_left || !s.J_right || !s.J_neck || !s.J_com || !s.q || !s.state || !s.dq || !s.ik_status)) return WCQP_E_INVALID;
     }
-    if (mpc_only) {
-        if (ways < 1) return WCQP_E_UNSUPPORTED;        // the work-queue form belongs to the IK + MPC kernel
-        int rc0 = wcqp::mpc_prepare(mpc);
-        if (rc0 != WCQP_OK) return rc0;
-        wcqp_qp_plan_s* p = new (std::nothrow) wcqp_qp_plan_s();
-        if (!p) return WCQP_E_NOMEM;
-        p->mpc = mpc; p->batch = batch; p->n_steps = n_steps; p->ways = ways < n_steps ? ways : n_steps; p->mpc_only = true;
-        if (hipMalloc(reinterpret_cast<void**>(&p->d_recs), (size_t)n_steps * sizeof(wcqp_qp_step)) != hipSuccess) { delete p; return WCQP_E_NOMEM; }
-        if (hipMemcpy(p->d_recs, steps, (size_t)n_steps * sizeof(wcqp_qp_step), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(p->d_recs); delete p; return WCQP_E_HIP;
-        }
-        *out = p;
-        return WCQP_OK;
+    if (mpc_only && ways < 1) return WCQP_E_UNSUPPORTED;        // the work-queue form belongs to the IK + MPC kernel
+    if (!mpc_only) {
+        // one launch walks through the records: that is the base-eliminated kernel on Jacobians the caller declares MIXED (no
+        // fall-back launch behind it), with the MPC on the IK's lanes
+        if (!ik) return WCQP_E_INVALID;
+        if (ik->route != wcqp::IkRoute::BASE_ELIM || ik->p.jacobian_structure != WCQP_IK_JAC_MIXED) return WCQP_E_UNSUPPORTED;
     }
-    if (!ik) return WCQP_E_INVALID;
-    // one launch walks through the records: that is the base-eliminated kernel on Jacobians the caller declares MIXED (no
-    // fall-back launch behind it), with the MPC on the IK's lanes
-    const bool want4 = ik->p.algorithm == WCQP_IK_ALG_BASE_ELIM || ik->p.algorithm == WCQP_IK_ALG_DEFAULT;
-    if (!(want4 && ik->hp.fast_ok && ik->p.jacobian_structure == WCQP_IK_JAC_MIXED)) return WCQP_E_UNSUPPORTED;
-    int rc = ensure_device(ik);
+    int rc = mpc_only ? WCQP_OK : ensure_device(ik);
     if (rc == WCQP_OK && mpc) rc = wcqp::mpc_prepare(mpc);
     if (rc != WCQP_OK) return rc;
     wcqp_qp_plan_s* p = new (std::nothrow) wcqp_qp_plan_s();
     if (!p) return WCQP_E_NOMEM;
-    p->mpc = mpc; p->ik = ik; p->batch = batch; p->n_steps = n_steps; p->ways = ways < n_steps ? ways : n_steps; p->ik_only = ik_only;
+    p->mpc = mpc; p->ik = mpc_only ? nullptr : ik; p->batch = batch; p->n_steps = n_steps; p->ways = ways < n_steps ? ways : n_steps;
+    p->mpc_only = mpc_only; p->ik_only = ik_only;
     if (hipMalloc(reinterpret_cast<void**>(&p->d_recs), (size_t)n_steps * sizeof(wcqp_qp_step)) != hipSuccess) { delete p; return WCQP_E_NOMEM; }
     if (hipMemcpy(p->d_recs, steps, (size_t)n_steps * sizeof(wcqp_qp_step), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(p->d_recs); delete p; return WCQP_E_HIP;

@@ -574,20 +574,16 @@ void ik2_kernel(const IkDeviceParams* __restrict__ prm, int batch,
 
 namespace wcqp_ik {
 
-int ik2_launch(const IkDeviceParams* d_prm, bool use_com, bool use_mfma, int batch,
-               const double* JL, const double* JR, const double* JN, const double* JC,
-               const double* q, const double* state, double* dq, int* status,
-               unsigned* alo, unsigned* aup, double* ferr, int* iters, hipStream_t stream) {
-    const unsigned grid = (unsigned)((batch + 1) / 2);
-    if (use_com && use_mfma)
-        hipLaunchKernelGGL((ik2_kernel<true, true>), dim3(grid), dim3(64), 0, stream, d_prm, batch, JL, JR, JN, JC, q, state,
-                           dq, status, alo, aup, ferr, iters);
-    else if (use_com)
-        hipLaunchKernelGGL((ik2_kernel<true, false>), dim3(grid), dim3(64), 0, stream, d_prm, batch, JL, JR, JN, JC, q, state,
-                           dq, status, alo, aup, ferr, iters);
-    else
-        hipLaunchKernelGGL((ik2_kernel<false, false>), dim3(grid), dim3(64), 0, stream, d_prm, batch, JL, JR, JN, JC, q, state,
-                           dq, status, alo, aup, ferr, iters);
+template <bool USE_COM, bool USE_MFMA>
+static void ik2_launch_as(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream_t stream) {
+    hipLaunchKernelGGL((ik2_kernel<USE_COM, USE_MFMA>), dim3((unsigned)((batch + 1) / 2)), dim3(64), 0, stream, d_prm, batch,
+                       io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters);
+}
+
+int ik2_launch(const IkDeviceParams* d_prm, bool use_com, bool use_mfma, int batch, const IkIo& io, hipStream_t stream) {
+    if (use_com && use_mfma) ik2_launch_as<true, true>(d_prm, batch, io, stream);
+    else if (use_com) ik2_launch_as<true, false>(d_prm, batch, io, stream);
+    else ik2_launch_as<false, false>(d_prm, batch, io, stream);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }

@@ -975,37 +975,25 @@ void ik3_kernel(const IkDeviceParams* __restrict__ prm, int batch,
 
 namespace wcqp_ik {
 
-int ik3_launch(const IkDeviceParams* d_prm, int batch,
-               const double* JL, const double* JR, const double* JN, const double* JC,
-               const double* q, const double* state, double* dq, int* status,
-               unsigned* alo, unsigned* aup, double* ferr, int* iters, hipStream_t stream) {
-    const unsigned grid = (unsigned)((batch + 3) / 4);
-    hipLaunchKernelGGL((ik3_kernel<false, false>), dim3(grid), dim3(64), 0, stream, d_prm, batch, JL, JR, JN, JC, q, state,
-                       dq, status, alo, aup, ferr, iters, wcqp_tick::TickDev{});
+template <bool TICK, bool LIST>
+static int ik3_launch_as(unsigned grid, const IkDeviceParams* d_prm, int batch, const IkIo& io, const wcqp_tick::TickDev& td, hipStream_t stream) {
+    hipLaunchKernelGGL((ik3_kernel<TICK, LIST>), dim3(grid), dim3(64), 0, stream, d_prm, batch,
+                       io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters, td);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
 
-int ik3_launch_list(const IkDeviceParams* d_prm, int batch,
-                    const double* JL, const double* JR, const double* JN, const double* JC,
-                    const double* q, const double* state, double* dq, int* status,
-                    unsigned* alo, unsigned* aup, double* ferr, int* iters, hipStream_t stream) {
-    const unsigned grid = (unsigned)((batch + 63) / 64);
-    hipLaunchKernelGGL((ik3_kernel<false, true>), dim3(grid), dim3(64), 0, stream, d_prm, batch, JL, JR, JN, JC, q, state,
-                       dq, status, alo, aup, ferr, iters, wcqp_tick::TickDev{});
-    WCQP_HIP_TRY(hipGetLastError());
-    return WCQP_OK;
+int ik3_launch(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream_t stream) {
+    return ik3_launch_as<false, false>((unsigned)((batch + 3) / 4), d_prm, batch, io, wcqp_tick::TickDev{}, stream);
 }
 
-int ik3_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td,
-                    const double* JL, const double* JR, const double* JN, const double* JC,
-                    unsigned* alo, unsigned* aup, hipStream_t stream) {
+int ik3_launch_list(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream_t stream) {
+    return ik3_launch_as<false, true>((unsigned)((batch + 63) / 64), d_prm, batch, io, wcqp_tick::TickDev{}, stream);
+}
+
+int ik3_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const IkIo& io, hipStream_t stream) {
     if (!d_prm) return WCQP_E_INVALID;
-    const unsigned grid = (unsigned)((td.batch + 3) / 4);
-    hipLaunchKernelGGL((ik3_kernel<true, false>), dim3(grid), dim3(64), 0, stream, static_cast<const IkDeviceParams*>(d_prm), td.batch,
-                       JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, nullptr, nullptr, td);
-    WCQP_HIP_TRY(hipGetLastError());
-    return WCQP_OK;
+    return ik3_launch_as<true, false>((unsigned)((td.batch + 3) / 4), static_cast<const IkDeviceParams*>(d_prm), td.batch, io, td, stream);
 }
 
 }  // namespace wcqp_ik

@@ -1853,78 +1853,58 @@ int ik4_launch_plan(const IkDeviceParams* d_prm, int batch, const wcqp_qp_step* 
     return WCQP_OK;
 }
 
-int ik4_launch_pair(const IkDeviceParams* d_prm, int batch,
-                    const double* JL, const double* JR, const double* JN, const double* JC,
-                    const double* q, const double* state, double* dq, int* status,
-                    unsigned* alo, unsigned* aup, double* ferr, int* iters,
+int ik4_launch_pair(const IkDeviceParams* d_prm, int batch, const IkIo& io,
                     const wcqp_mpc::MpcDeviceConsts& c, const double* x0, const double* ref, int ref_len, const double* u_prev,
                     const double* hull_A, const double* hull_b, const int* hull_nc,
                     double* u0, int* mstatus, unsigned* mactive, double* mmargin, hipStream_t stream) {
     const int ik_blocks = (batch + 3) / 4;
     const int mpc_blocks = (batch + wcqp_mpc::kInstPerWave - 1) / wcqp_mpc::kInstPerWave;
     MpcPairArgs m{c, x0, ref, ref_len, u_prev, hull_A, hull_b, hull_nc, u0, mstatus, mactive, mmargin};
-    hipLaunchKernelGGL(qp_pair_kernel, dim3((unsigned)(ik_blocks + mpc_blocks)), dim3(64), 0, stream, d_prm, batch, JL, JR, JN, JC, q, state,
-                       dq, status, alo, aup, ferr, iters, ik_blocks, m);
+    hipLaunchKernelGGL(qp_pair_kernel, dim3((unsigned)(ik_blocks + mpc_blocks)), dim3(64), 0, stream, d_prm, batch,
+                       io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters, ik_blocks, m);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
 
-int ik4_launch(const IkDeviceParams* d_prm, int batch,
-               const double* JL, const double* JR, const double* JN, const double* JC,
-               const double* q, const double* state, double* dq, int* status,
-               unsigned* alo, unsigned* aup, double* ferr, int* iters, hipStream_t stream) {
-    const unsigned grid = (unsigned)((batch + 3) / 4);
-    hipLaunchKernelGGL((ik4_kernel<false, 0>), dim3(grid), dim3(64), 0, stream, d_prm, batch, JL, JR, JN, JC, q, state,
-                       dq, status, alo, aup, ferr, iters, nullptr, 0, 1, 0);
+// one launch of ik4_kernel: the stand-alone solve (td_dev = NULL) or a tick form
+template <bool TICK, int JSRC, bool LOG = false, bool EXT = false>
+static void ik4_launch_as(const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
+                          int n_inner, int skip_last_mpc, hipStream_t stream) {
+    hipLaunchKernelGGL((ik4_kernel<TICK, JSRC, LOG, EXT>), dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, stream, prm, batch,
+                       io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters,
+                       td_dev, phase, n_inner, skip_last_mpc);
+}
+
+int ik4_launch(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream_t stream) {
+    ik4_launch_as<false, 0>(d_prm, batch, io, nullptr, 0, 1, 0, stream);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
 
-int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev,
-                    const double* JL, const double* JR, const double* JN, const double* JC,
-                    unsigned* alo, unsigned* aup, int n_inner, int skip_last_mpc, hipStream_t stream, double* log_ferr) {
-    if (n_inner < 1 || (n_inner > 1 && td.kin_mode && !td.kin_fused)) return WCQP_E_INVALID;      // kinematics in a launch of their own: the Jacobians of tick t + 1 come from another launch
+int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                    int n_inner, int skip_last_mpc, hipStream_t stream) {
+    if (n_inner < 1) return WCQP_E_INVALID;       // (whether a handle may run several ticks per launch is decided at wcqp_tick_create)
     if (!d_prm || !td_dev || !td.skew || !td.mst || !td.hand || !td.live_A || !td.live_b || !td.live_nc || !td.sel_built) return WCQP_E_INVALID;
     if (td.compact && (!td.jcomp || td.cstride < 1)) return WCQP_E_INVALID;
     if (td.kin_fused && (!td.kin_tab || !td.kin_mode || td.kin_rounds < 0 || td.kin_rounds > 3 || td.horizon >= wcqp_tick::kGainsLdsStages)) return WCQP_E_INVALID;
-    const unsigned grid = (unsigned)((td.batch + 3) / 4);
     const IkDeviceParams* prm = static_cast<const IkDeviceParams*>(d_prm);
+    const int B = td.batch, ph = td.phase;
     if (td.logger_ticks > 0) {
         // the logging kernels (a debugging aid like the reference's dumpData): dense Jacobians also produce the foot errors
         if (!td.log_rows) return WCQP_E_INVALID;
-        if (td.kin_fused)
-            hipLaunchKernelGGL((ik4_kernel<true, 2, true>), dim3(grid), dim3(64), 0, stream, prm, td.batch,
-                               JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, nullptr, nullptr, td_dev, td.phase, n_inner, skip_last_mpc);
-        else if (td.compact)
-            hipLaunchKernelGGL((ik4_kernel<true, 1, true>), dim3(grid), dim3(64), 0, stream, prm, td.batch,
-                               JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, nullptr, nullptr, td_dev, td.phase, n_inner, skip_last_mpc);
-        else
-            hipLaunchKernelGGL((ik4_kernel<true, 0, true>), dim3(grid), dim3(64), 0, stream, prm, td.batch,
-                               JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, log_ferr, nullptr, td_dev, td.phase, n_inner, skip_last_mpc);
-        WCQP_HIP_TRY(hipGetLastError());
-        return WCQP_OK;
-    }
-    if (td.q_meas) {
+        if (td.kin_fused) ik4_launch_as<true, 2, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else if (td.compact) ik4_launch_as<true, 1, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else ik4_launch_as<true, 0, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+    } else if (td.q_meas) {
         // external feedback (wcqp_tick_params.plant = EXTERNAL): measured joints in the IK's regularisation; one tick per launch
         if (n_inner != 1 || td.compact) return WCQP_E_INVALID;
-        if (td.kin_fused)
-            hipLaunchKernelGGL((ik4_kernel<true, 2, false, true>), dim3(grid), dim3(64), 0, stream, prm, td.batch,
-                               JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, nullptr, nullptr, td_dev, td.phase, n_inner, skip_last_mpc);
-        else
-            hipLaunchKernelGGL((ik4_kernel<true, 0, false, true>), dim3(grid), dim3(64), 0, stream, prm, td.batch,
-                               JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, nullptr, nullptr, td_dev, td.phase, n_inner, skip_last_mpc);
-        WCQP_HIP_TRY(hipGetLastError());
-        return WCQP_OK;
+        if (td.kin_fused) ik4_launch_as<true, 2, false, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else ik4_launch_as<true, 0, false, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+    } else {
+        if (td.kin_fused) ik4_launch_as<true, 2>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else if (td.compact) ik4_launch_as<true, 1>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else ik4_launch_as<true, 0>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
     }
-    if (td.kin_fused)
-        hipLaunchKernelGGL((ik4_kernel<true, 2>), dim3(grid), dim3(64), 0, stream, prm, td.batch,
-                           JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, nullptr, nullptr, td_dev, td.phase, n_inner, skip_last_mpc);
-    else if (td.compact)
-        hipLaunchKernelGGL((ik4_kernel<true, 1>), dim3(grid), dim3(64), 0, stream, prm, td.batch,
-                           JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, nullptr, nullptr, td_dev, td.phase, n_inner, skip_last_mpc);
-    else
-        hipLaunchKernelGGL((ik4_kernel<true, 0>), dim3(grid), dim3(64), 0, stream, prm, td.batch,
-                           JL, JR, JN, JC, td.q_des, td.state, td.dq, td.ik_status, alo, aup, nullptr, nullptr, td_dev, td.phase, n_inner, skip_last_mpc);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }

@@ -351,52 +351,41 @@ __device__ __forceinline__ void gi_active_set(const GiScratch& w, int i, int hal
     }
 }
 
+// the per-call arrays of an IK solve (include/wcqp.h: wcqp_ik_solve_device), as every launcher below takes them
+struct IkIo {
+    const double *JL, *JR, *JN, *JC, *q, *state;
+    double* dq; int* status; unsigned *alo, *aup; double* ferr; int* iters;
+};
+
 // launch of the null-space kernel (ik2.hip)
-int ik2_launch(const IkDeviceParams* d_prm, bool use_com, bool use_mfma, int batch,
-               const double* JL, const double* JR, const double* JN, const double* JC,
-               const double* q, const double* state, double* dq, int* status,
-               unsigned* alo, unsigned* aup, double* ferr, int* iters, hipStream_t stream);
+int ik2_launch(const IkDeviceParams* d_prm, bool use_com, bool use_mfma, int batch, const IkIo& io, hipStream_t stream);
 
 // launch of the 16-lanes-per-instance null-space kernel (ik3.hip; CoM-as-constraint form only)
-int ik3_launch(const IkDeviceParams* d_prm, int batch,
-               const double* JL, const double* JR, const double* JN, const double* JC,
-               const double* q, const double* state, double* dq, int* status,
-               unsigned* alo, unsigned* aup, double* ferr, int* iters, hipStream_t stream);
+int ik3_launch(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream_t stream);
 
 // launch of the base-eliminated range-space kernel (ik4.hip; MIXED free-floating Jacobians, CoM as constraint).
 // Instances whose base blocks do not have the MIXED pattern come back with status WCQP_STATUS_STRUCTURE and dq = 0.
-int ik4_launch(const IkDeviceParams* d_prm, int batch,
-               const double* JL, const double* JR, const double* JN, const double* JC,
-               const double* q, const double* state, double* dq, int* status,
-               unsigned* alo, unsigned* aup, double* ferr, int* iters, hipStream_t stream);
+int ik4_launch(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream_t stream);
 // the general 16-lane kernel over the instances whose status reads WCQP_STATUS_STRUCTURE
-int ik3_launch_list(const IkDeviceParams* d_prm, int batch,
-                    const double* JL, const double* JR, const double* JN, const double* JC,
-                    const double* q, const double* state, double* dq, int* status,
-                    unsigned* alo, unsigned* aup, double* ferr, int* iters, hipStream_t stream);
+int ik3_launch_list(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream_t stream);
 
 }  // namespace wcqp_ik
 
 namespace wcqp_tick { struct TickDev; }
 namespace wcqp_ik {
 // the 16-lane kernel with the tick pipeline's glue and post steps fused in (tick.hip)
-int ik3_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td,
-                    const double* JL, const double* JR, const double* JN, const double* JC,
-                    unsigned* alo, unsigned* aup, hipStream_t stream);
-int ik4_launch_pair(const IkDeviceParams* d_prm, int batch,
-                    const double* JL, const double* JR, const double* JN, const double* JC,
-                    const double* q, const double* state, double* dq, int* status,
-                    unsigned* alo, unsigned* aup, double* ferr, int* iters,
+// io: the tick's Jacobians, q_des, state, dq, ik_status and previous active sets (ferr: the logger's foot errors, or NULL)
+int ik3_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const IkIo& io, hipStream_t stream);
+int ik4_launch_pair(const IkDeviceParams* d_prm, int batch, const IkIo& io,
                     const wcqp_mpc::MpcDeviceConsts& c, const double* x0, const double* ref, int ref_len, const double* u_prev,
                     const double* hull_A, const double* hull_b, const int* hull_nc,
                     double* u0, int* mstatus, unsigned* mactive, double* mmargin, hipStream_t stream);
 // the base-eliminated kernel with the SKEWED tick fused in: IK(t) + post step of tick t and the MPC chain of tick t + 1
 // (tick_device.h); dense Jacobians, or the compact per-joint records of the tick's own kinematics kernel (td.compact)
-// n_inner: ticks per launch (> 1 only without per-tick kinematics); td_dev: the same TickDev in device memory (td.phase is
+// n_inner: ticks per launch (> 1 only where the tick handle allows it); td_dev: the same TickDev in device memory (td.phase is
 // passed as a kernel argument, the copy's is not read)
-int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev,
-                    const double* JL, const double* JR, const double* JN, const double* JC,
-                    unsigned* alo, unsigned* aup, int n_inner, int skip_last_mpc, hipStream_t stream, double* log_ferr = nullptr);
+int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                    int n_inner, int skip_last_mpc, hipStream_t stream);
 // a plan of steps in ONE launch (wcqp_qp_plan_*): d_recs = the records in device memory
 int ik4_launch_plan(const IkDeviceParams* d_prm, int batch, const wcqp_qp_step* d_recs, int n_steps, int ways,
                     const wcqp_mpc::MpcDeviceConsts& c, hipStream_t stream, unsigned* d_queue, int queue_grid, bool ik_only);

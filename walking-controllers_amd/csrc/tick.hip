@@ -66,6 +66,10 @@ __global__ void tick_feedback_kernel(TickDev d, const double* __restrict__ dcm, 
 
 }  // namespace
 
+// how a tick is launched: the skewed base-eliminated kernel (ONE launch), MPC + the 16-lane kernel with glue and post fused in
+// (two), or MPC, glue, IK and post (four; any other IK kernel, and what the fused forms are tested against)
+enum class TickForm { SKEWED, MPC_IK16, FOUR_LAUNCH };
+
 struct wcqp_tick_s {
     wcqp_tick_params p{};
     wcqp_mpc_t mpc = nullptr;
@@ -82,12 +86,11 @@ struct wcqp_tick_s {
     bool uploaded = false;
     int ticks_enqueued = 0;  // since the last upload; its parity is the `phase` of the next tick
     double* log_ferr = nullptr;   // logger rows with dense Jacobians: where the IK kernel forms the foot errors
-    bool fused = false;      // glue + post inside the 16-lane IK kernel: 2 launches per tick instead of 4
-    bool base_elim = false;  // the fused kernel is the base-eliminated one (ik4.hip)
+    TickForm form = TickForm::FOUR_LAUNCH;   // from the IK handle's route (wcqp_tick_create)
     wcqp_kin_t kin = nullptr;     // use_kinematics: Jacobians, actual poses and hull rows are rebuilt every tick
     KinTick kt{};
     int phase = 0;                // which copy of the tick index the next launch reads (TickDev::tick2): toggles per LAUNCH
-    int ticks_per_launch = 1;     // > 1: the fused kernel walks through that many ticks per launch (no per-tick kinematics)
+    int ticks_per_launch = 1;     // > 1 only for the skewed tick without a kinematics launch: the ticks one launch walks through
     // wcqp_tick_splice_reference: the caller's host rows are staged HERE at call time (a copy stream of the handle's own, waited
     // for before the call returns), the strided device-to-device copy then runs in the caller's stream order
     double* splice_stage = nullptr; size_t splice_cap = 0;
@@ -113,33 +116,31 @@ int dev_alloc(wcqp_tick_s* h, T** out, size_t count) {
 template <typename T>
 int dev_alloc(wcqp_tick_s* h, wcqp::GPtr<T>* out, size_t count) { return dev_alloc(h, &out->p, count); }
 
-// one launch sequence of n_inner ticks (n_inner > 1: the fused base-eliminated kernel without per-tick kinematics only) with
+// one launch sequence of n_inner ticks (n_inner <= ticks_per_launch, which is 1 unless the handle may run several) with
 // the given phase (which copy of the tick index it reads: see TickDev::tick2)
 int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int skip_last_mpc = 0) {
     TickDev d = h->d;
     d.phase = phase & 1;
     const int B = d.batch;
     const int N = wcqp::mpc_horizon(h->mpc);
-    if (n_inner > 1 && !(h->fused && h->base_elim && (!h->kin || d.kin_fused))) return WCQP_E_INVALID;
+    if (n_inner > h->ticks_per_launch) return WCQP_E_INVALID;
     if (h->kin && !d.kin_fused) {
         h->kt.phase = d.phase;
         const int rck = wcqp::kin_enqueue_tick(h->kin, B, h->kt, d.q_des, h->J_left, h->J_right, h->J_neck, h->J_com, d.state, s);
         if (rck != WCQP_OK) return rck;
     }
+    const wcqp_ik::IkIo io{h->J_left, h->J_right, h->J_neck, h->J_com, d.q_des, d.state, d.dq, d.ik_status, h->ik_lo, h->ik_up,
+                           h->log_ferr, nullptr};
     // base-eliminated IK kernel: IK + post step of this tick and MPC + glue + plant of the NEXT one in ONE launch (skewed tick)
-    if (h->fused && h->base_elim)
-        return wcqp_ik::ik4_launch_tick(wcqp::ik_device_params(h->ik), d, h->d_dev, h->J_left, h->J_right, h->J_neck, h->J_com,
-                                        h->ik_lo, h->ik_up, n_inner, skip_last_mpc, s, h->log_ferr);
+    if (h->form == TickForm::SKEWED)
+        return wcqp_ik::ik4_launch_tick(wcqp::ik_device_params(h->ik), d, h->d_dev, io, n_inner, skip_last_mpc, s);
     int rc = wcqp::mpc_enqueue(h->mpc, B, d.dcm, d.ref_traj, N + 1, d.traj_len, d.tick2 + d.phase, d.u_prev,
                                d.hull_tab_A, d.hull_tab_b, d.hull_tab_nc, d.hull_sets, d.hull_sets > 1 ? d.sel : nullptr,
                                d.u0, d.mpc_status, h->mpc_active, h->mpc_margin, s);
     if (rc != WCQP_OK) return rc;
-    if (h->fused)
-        return wcqp_ik::ik3_launch_tick(wcqp::ik_device_params(h->ik), d, h->J_left, h->J_right, h->J_neck, h->J_com,
-                                        h->ik_lo, h->ik_up, s);
+    if (h->form == TickForm::MPC_IK16) return wcqp_ik::ik3_launch_tick(wcqp::ik_device_params(h->ik), d, io, s);
     hipLaunchKernelGGL(tick_glue_kernel, dim3((B + 127) / 128), dim3(128), 0, s, d);
-    rc = wcqp_ik_solve_device(h->ik, B, h->J_left, h->J_right, h->J_neck, h->J_com, d.q_des, d.state,
-                              d.dq, d.ik_status, h->ik_lo, h->ik_up, nullptr, nullptr, s);
+    rc = wcqp_ik_solve_device(h->ik, B, io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, nullptr, nullptr, s);
     if (rc != WCQP_OK) return rc;
     hipLaunchKernelGGL(tick_post_kernel, dim3((B * kDof + 255) / 256), dim3(256), 0, s, d);
     WCQP_HIP_TRY(hipGetLastError());
@@ -162,11 +163,6 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     wcqp_tick_s* h = new (std::nothrow) wcqp_tick_s();
     if (!h) return WCQP_E_NOMEM;
     h->p = *params;
-    // the fused form exists for the 16-lane kernel only (CoM as constraint); an explicit 32-lane / sweep
-    // algorithm keeps the four-launch form, which is also what the fused one is tested against
-    h->fused = params->ik.use_com_as_constraint &&
-               (params->ik.algorithm == WCQP_IK_ALG_DEFAULT || params->ik.algorithm == WCQP_IK_ALG_NULLSPACE_16L ||
-                params->ik.algorithm == WCQP_IK_ALG_BASE_ELIM);
     int rc = wcqp_mpc_create(&params->mpc, &h->mpc);
     if (rc == WCQP_OK) rc = wcqp_ik_create(&params->ik, &h->ik);
     if (rc == WCQP_OK && params->use_kinematics) {
@@ -183,8 +179,8 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (params->ticks_per_launch < 0 || params->logger_ticks < 0) { wcqp_tick_destroy(h); return WCQP_E_INVALID; }
     if (params->plant != WCQP_TICK_PLANT_INTERNAL && params->plant != WCQP_TICK_PLANT_EXTERNAL) { wcqp_tick_destroy(h); return WCQP_E_INVALID; }
     h->external = params->plant == WCQP_TICK_PLANT_EXTERNAL;
-    h->base_elim = h->fused && params->ik.algorithm != WCQP_IK_ALG_NULLSPACE_16L &&
-                   params->ik.jacobian_structure != WCQP_IK_JAC_GENERAL && wcqp::ik_fast_ok(h->ik);
+    const wcqp::IkRoute route = wcqp::ik_route(h->ik);
+    h->form = route == wcqp::IkRoute::BASE_ELIM ? TickForm::SKEWED : route == wcqp::IkRoute::NULLSPACE_16L ? TickForm::MPC_IK16 : TickForm::FOUR_LAUNCH;
     const size_t B = (size_t)params->batch;
     const int N = params->mpc.horizon;
     TickDev& d = h->d;
@@ -212,7 +208,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     A_(h->J_left, B * 6 * 29); A_(h->J_right, B * 6 * 29); A_(h->J_neck, B * 3 * 29); A_(h->J_com, B * 3 * 29);
     A_(h->mpc_active, B); A_(h->mpc_margin, B); A_(h->ik_lo, B); A_(h->ik_up, B);
     // skewed tick (base-eliminated fused kernel): state of the MPC chain, MPC -> IK hand-off, one live hull row set per robot
-    d.skew = (h->fused && h->base_elim) ? 1 : 0;
+    d.skew = h->form == TickForm::SKEWED ? 1 : 0;
 
     double* jcomp = nullptr;
     unsigned cm[3] = {0u, 0u, 0u};
@@ -230,7 +226,8 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (d.skew) {
         A_(d.mst, B * 16); A_(d.hand, 2 * B * kHandLen); A_(d.live_A, B * 16); A_(d.live_b, B * 8); A_(d.live_nc, B); A_(d.sel_built, B);
         if (compact) A_(jcomp, B * (size_t)cstride);
-        if (params->logger_ticks > 0) { A_(d.log_rows, (size_t)params->logger_ticks * B * kLoggerCols); A_(h->log_ferr, B * 12); d.logger_ticks = params->logger_ticks; }
+        if (params->logger_ticks > 0) { A_(d.log_rows, (size_t)params->logger_ticks * B * kLoggerCols); d.logger_ticks = params->logger_ticks; }
+        if (params->logger_ticks > 0 && !compact && !fusedk) A_(h->log_ferr, B * 12);      // (records: the kernel forms no foot errors)
         if (fusedk) {
             double* kt = nullptr;
             A_(kt, ktab.size());
@@ -244,9 +241,10 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     d.horizon = N; d.hull_sets = (int)hsets;
     if (compact) { d.compact = 1; d.jcomp = jcomp; d.cmaskL = cm[0]; d.cmaskR = cm[1]; d.cmaskN = cm[2]; d.cstride = cstride; d.coff_d = coff_d; }
     if (fusedk) { d.kin_fused = 1; d.cmaskL = cm[0]; d.cmaskR = cm[1]; d.cmaskN = cm[2]; }
-    // several ticks per launch: whenever a tick is ONE launch of the fused kernel (no kinematics launch in between)
-    h->ticks_per_launch = (d.skew && (!h->kin || fusedk)) ? (params->ticks_per_launch > 0 ? params->ticks_per_launch : (1 << 20)) : 1;
-    if (h->external) h->ticks_per_launch = 1;            // a tick cannot run ahead of its feedback
+    // several ticks per launch: whenever a tick is ONE launch of the fused kernel (no kinematics launch in between), and not
+    // with external feedback (a tick cannot run ahead of its feedback)
+    const bool multi_tick = d.skew && (!h->kin || fusedk) && !h->external;
+    h->ticks_per_launch = multi_tick ? (params->ticks_per_launch > 0 ? params->ticks_per_launch : (1 << 20)) : 1;
     if (h->kin) {
         double* h0 = nullptr;
         if (dev_alloc(h, &h0, B) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
@@ -390,7 +388,6 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     // Everything that can be refused on the host is refused BEFORE anything is enqueued (the prime launch below already advances
     // the MPC chain); an enqueue that fails after that leaves device state nobody can name - the handle then wants a new upload.
     struct NeedsUpload { wcqp_tick_s* h; bool armed = true; ~NeedsUpload() { if (armed) h->uploaded = false; } } guard{h};
-    if (h->ticks_per_launch > 1 && !(h->fused && h->base_elim && (!h->kin || h->d.kin_fused))) { guard.armed = false; return WCQP_E_INVALID; }
     if (h->d.skew && (!h->d_dev || !h->d.mst || !h->d.hand)) { guard.armed = false; return WCQP_E_INVALID; }
     if (h->d.skew) {
         // the fused launch of tick t carries IK(t) and MPC(t+1): the MPC of the call's first tick goes first, on its own, and

@@ -43,7 +43,10 @@ int mpc_launch_plan(wcqp_mpc_t h, int batch, const wcqp_qp_step* d_recs, int n_s
 int ik_prepare(wcqp_ik_t h);
 const void* ik_device_params(wcqp_ik_t h);     // IkDeviceParams* in HBM (after ik_prepare)
 int qp_pair_enqueue(wcqp_mpc_t mpc, wcqp_ik_t ik, int batch, const wcqp_qp_step& s);   // WCQP_E_UNSUPPORTED: make the two calls instead
-bool ik_fast_ok(wcqp_ik_t h);                  // the handle qualifies for the base-eliminated kernel (ik4.hip)
+// the IK kernel a handle runs, resolved once by wcqp_ik_create: base-eliminated (ik4.hip), the 16-lane null-space kernel (ik3.hip),
+// the 32-lane one without / with MFMA (ik2.hip), or the diagnostic sweep kernel
+enum class IkRoute { BASE_ELIM, NULLSPACE_16L, NULLSPACE_32, NULLSPACE_32_MFMA, SWEEP };
+IkRoute ik_route(wcqp_ik_t h);
 void mpc_dynamics(wcqp_mpc_t h, double* a, double* b);
 int kin_prepare(wcqp_kin_t h);
 // hull.hip: the three support-polygon row sets (left, right, both feet in contact) of every robot from the desired foot poses of its pose block
