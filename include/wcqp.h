@@ -483,9 +483,29 @@ typedef struct wcqp_tick_params {
      * measured joint positions of WalkingQPIK::setRobotState :373.  A tick then cannot run ahead of its feedback: wcqp_tick_run takes
      * exactly ONE tick per call, in order (MPC(t), then IK(t): 2 launches + the feedback copy).  Default IK kernel only. */
     int32_t plant;
+    /* The DCM controller of the tick (WCQP_TICK_DCM_*).  MPC (0, default): the DCM-MPC above (WalkingModule.cpp:604-636, the
+     * reference's `use_mpc 1`).  REACTIVE (1): WalkingDCMReactiveController (WM/src/WalkingDCMReactiveController.cpp:63-82, the
+     * reference's default `use_mpc 0`, WalkingModule.cpp:124, 188-211, 638-656), closed form per axis:
+     *     zmp_des = dcm_des - dcm_des_dot / omega - k_dcm (dcm_des - dcm_measured),   omega = sqrt(gravity / com_height)
+     * with dcm_des the reference stage of the tick and dcm_des_dot wcqp_tick_inputs.dcm_vel_traj (NULL: the forward difference
+     * (ref[t+1] - ref[t]) / dT).  Everything after it is what the MPC tick does: ZMP-CoM law, IK, joint integration, plant.
+     * With REACTIVE:
+     *   - the MPC's Q, R and hull inputs are ignored; the hull tables may be NULL when there are no kinematics;
+     *   - mpc.horizon still sets the length of the trajectory buffers (max_ticks + horizon + 1 stages), and sampling_time,
+     *     com_height and gravity keep their meaning;
+     *   - mpc_fail stays 0;
+     *   - u0_log and logger columns 8-9 hold the reactive output zmp_des; logger columns 4-5 the velocity actually used;
+     *   - the fused kinematics hand-off is taken at any horizon (the MPC's needs horizon < 55);
+     *   - wcqp_tick_splice_reference on a handle uploaded with an explicit dcm_vel_traj returns WCQP_E_UNSUPPORTED (the splice
+     *     has no velocity tail); with NULL velocities it works as with the MPC.
+     * wcqp_tick_create returns WCQP_E_INVALID for an unknown controller, and for REACTIVE with a k_dcm that is not finite. */
+    int32_t dcm_controller;
+    double k_dcm;               /* kDCM of DCM_REACTIVE_CONTROLLER (app/robots/<robot>/dcmReactiveControllerParams.ini:1) */
 } wcqp_tick_params;
 #define WCQP_TICK_PLANT_INTERNAL 0
 #define WCQP_TICK_PLANT_EXTERNAL 1
+#define WCQP_TICK_DCM_MPC        0
+#define WCQP_TICK_DCM_REACTIVE   1
 
 typedef struct wcqp_tick_inputs {   /* HOST pointers, copied at upload */
     const double* ref_traj;     /* [B][max_ticks+N+1][2]                                      */
@@ -498,6 +518,8 @@ typedef struct wcqp_tick_inputs {   /* HOST pointers, copied at upload */
     const double* swing_twist;  /* [B][6] desired twist of whichever foot is in the air        */
     const double* q0;           /* [B][dof]                                                    */
     const double* dcm0; const double* com0; const double* u_init;   /* [B][2] each             */
+    const double* dcm_vel_traj; /* [B][max_ticks+N+1][2] or NULL: the planner's DCM velocity (WalkingModule.cpp:641-642), read by
+                                 * the REACTIVE controller only (NULL: the forward difference of ref_traj); MPC handles ignore it */
 } wcqp_tick_inputs;
 
 typedef struct wcqp_tick_outputs {  /* HOST pointers, any may be NULL */
@@ -552,6 +574,16 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
  * caller orders the copy kernel's stream before the stream of the run call (the same stream does). */
 int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const double* com_meas, const double* zmp_meas, const double* q_meas);
 int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out);             /* synchronises     */
+
+/* The form a tick handle actually took at wcqp_tick_create (the route follows the IK algorithm, the kinematics hand-off and the
+ * controller: the fused kinematics hand-off of an MPC handle falls back to COMPACT at horizons of 55 and more, for example). */
+typedef struct wcqp_tick_info {
+    int32_t kin_handoff;        /* WCQP_KIN_HANDOFF_* taken; -1 without per-tick kinematics (constant Jacobians)            */
+    int32_t ticks_per_launch;   /* effective ticks one launch walks through (1 << 20: all the ticks of a wcqp_tick_run call) */
+    int32_t dcm_controller;     /* WCQP_TICK_DCM_*                                                                          */
+    int32_t launches_per_tick;  /* kernel launches of a tick that runs alone (the skewed fused kernel: 1)                   */
+} wcqp_tick_info;
+int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
 
 #ifdef __cplusplus
 }

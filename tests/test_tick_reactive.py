@@ -1,0 +1,353 @@
+"""
+The closed-loop tick with the REACTIVE DCM controller (wcqp_tick_params.dcm_controller = REACTIVE): the reference's default
+configuration (WM/src/WalkingModule.cpp:124 `use_mpc` defaults to false; :188-211, :638-656), and that of two of the three robots it ships.
+Checked against tests/helpers/reactive_tick.py: oracle/tick_spec.run_ticks with its MPC solve replaced by the closed-form law of
+WM/src/WalkingDCMReactiveController.cpp:63-82.
+"""
+import ctypes as C
+import importlib.util
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import robots
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("reactive_tick", os.path.join(ROOT, "tests", "helpers", "reactive_tick.py"))
+rt = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(rt)
+
+# kDCM of DCM_REACTIVE_CONTROLLER, app/robots/<robot>/dcmReactiveControllerParams.ini:1
+K_DCM = {
+    "iCubGazeboV2_5": 1.2,      # app/robots/iCubGazeboV2_5/dcmReactiveControllerParams.ini:1
+    "iCubGenova04": 1.1,        # app/robots/iCubGenova04/dcmReactiveControllerParams.ini:1
+    "icubGazeboSim": 1.2,       # app/robots/icubGazeboSim/dcmReactiveControllerParams.ini:1
+}
+VMAX = 0.45
+WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
+KEYS = ("u0_log", "dq_log", "q_des", "dcm", "com")
+
+
+def _close(out, ref, tol=1e-9):
+    for k in KEYS:
+        err = np.abs(out[k] - ref[k]).max()
+        assert err <= tol, (k, err)
+    assert out["mpc_fail"].sum() == 0
+    assert np.array_equal(out["ik_fail"], ref["ik_fail"])
+
+
+def _same(a, b, keys=KEYS + ("ik_fail", "mpc_fail", "hot_try", "hot_hit", "active_lower", "active_upper")):
+    for k in keys:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def _walk_scenario(wca, B, T, horizon=50):
+    kin = wca.KinModel(wca.synth.icub_like_model())
+    kb = wca.synth.synth_walk_kin_batch(B)
+    poses = kin.jacobians_host(kb["base"], kb["q"], state=np.zeros((B, 87)))["state"]
+    return kin, wca.synth.synth_walk_batch(B, T, poses, kb, horizon=horizon)
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU
+
+def test_restatement_law_and_patch_hygiene():
+    """The helper's law is WalkingDCMReactiveController.cpp:75-78 term by term; the patch of tick_spec.qs.mpc_exact is undone on exit,
+    an exception included."""
+    from oracle import tick_spec as ts
+    rng = np.random.default_rng(7)
+    p = ts.TickParams()
+    omega = np.sqrt(p.gravity / p.com_height)
+    r, rd, x = rng.normal(size=(3, 100, 2))
+    k = 1.1
+    expect = np.empty((100, 2))
+    for i in range(100):
+        for ax in range(2):
+            # zmp = dcm_des - dcm_des_dot / omega - kDCM * (dcm_des - dcm_measured)
+            expect[i, ax] = r[i, ax] - rd[i, ax] / omega - k * (r[i, ax] - x[i, ax])
+    assert np.abs(rt.reactive_law(r, rd, x, omega, k) - expect).max() <= 1e-15
+    orig = ts.qs.mpc_exact
+    with rt.reactive_solve(p, k, 1) as st:
+        assert ts.qs.mpc_exact is not orig
+        w = np.stack([r[0], r[1]])
+        u = ts.qs.mpc_exact(None, x[0], w, None, None, None, 0)["u0"]
+        assert np.abs(u - rt.reactive_law(r[0], (r[1] - r[0]) / p.dT, x[0], omega, k)).max() <= 1e-15 and st["calls"] == 1
+    assert ts.qs.mpc_exact is orig
+    with pytest.raises(RuntimeError):
+        with rt.reactive_solve(p, k, 1):
+            raise RuntimeError("inside")
+    assert ts.qs.mpc_exact is orig
+
+
+def test_new_struct_fields_match_the_ctypes_mirror(wca, tmp_path):
+    """wcqp_tick_params.dcm_controller / k_dcm, wcqp_tick_inputs.dcm_vel_traj and wcqp_tick_info: offsets in the C header == capi's."""
+    src = tmp_path / "layout.c"
+    src.write_text(r'''
+#include <stddef.h>
+#include <stdio.h>
+#include "wcqp.h"
+int main(void) {
+    printf("%zu %zu %zu %zu %zu\n", sizeof(wcqp_tick_params), offsetof(wcqp_tick_params, plant), offsetof(wcqp_tick_params, dcm_controller),
+           offsetof(wcqp_tick_params, k_dcm), (size_t)WCQP_TICK_DCM_REACTIVE);
+    printf("%zu %zu %zu\n", sizeof(wcqp_tick_inputs), offsetof(wcqp_tick_inputs, u_init), offsetof(wcqp_tick_inputs, dcm_vel_traj));
+    printf("%zu %zu %zu %zu %zu\n", sizeof(wcqp_tick_info), offsetof(wcqp_tick_info, kin_handoff), offsetof(wcqp_tick_info, ticks_per_launch),
+           offsetof(wcqp_tick_info, dcm_controller), offsetof(wcqp_tick_info, launches_per_tick));
+    return 0;
+}
+''')
+    exe = tmp_path / "layout"
+    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    lines = [[int(x) for x in ln.split()] for ln in subprocess.check_output([str(exe)], text=True).splitlines()]
+    P, I, N = wca.capi.TickParams, wca.capi.TickInputs, wca.capi.TickInfo
+    assert lines[0] == [C.sizeof(P), P.plant.offset, P.dcm_controller.offset, P.k_dcm.offset, wca.capi.TICK_DCM_REACTIVE]
+    assert lines[1] == [C.sizeof(I), I.u_init.offset, I.dcm_vel_traj.offset]
+    assert lines[2] == [C.sizeof(N), N.kin_handoff.offset, N.ticks_per_launch.offset, N.dcm_controller.offset, N.launches_per_tick.offset]
+
+
+def test_reactive_pipeline_needs_k_dcm(wca):
+    with pytest.raises(ValueError):
+        wca.TickPipeline(4, 10, wca.MpcSolver(), wca.IkSolver(), dcm_controller="reactive")
+    with pytest.raises(ValueError):
+        wca.TickPipeline(4, 10, wca.MpcSolver(), wca.IkSolver(), dcm_controller="lqr")
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+
+@pytest.fixture(scope="module")
+def tick_batch(wca):
+    return wca.synth.synth_tick_batch(24, 150)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot", robots.NAMES)
+def test_reactive_tick_with_constant_jacobians(wca, qs, tick_batch, robot):
+    """Each robot's kDCM and ZMP-CoM gains; the skewed single-launch tick (algorithm 0) and the in-order forms of algorithms 4 (2 launches
+    per tick) and 3 (4 launches); several ticks per launch, one per launch, and one per launch replayed from a graph."""
+    from oracle import tick_spec as ts
+    R = robots.ROBOTS[robot]
+    B, T = 24, 150
+    p = ts.TickParams(k_com=R["k_com"], k_zmp=R["k_zmp"])
+    d = tick_batch
+    ref = rt.run_ticks_reactive(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23)), K_DCM[robot])
+    assert ref["ik_fail"].sum() == 0
+    for alg in (0, 4, 3):
+        runs = []
+        for tpl, graph in ((0, False), (1, True)):
+            pipe = wca.TickPipeline(B, T, wca.MpcSolver(), wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=VMAX, algorithm=alg), log_ticks=T,
+                                    k_com=R["k_com"], k_zmp=R["k_zmp"], ticks_per_launch=tpl, dcm_controller="reactive", k_dcm=K_DCM[robot])
+            info = pipe.info()
+            assert info["dcm_controller"] == "reactive" and info["kin_handoff"] is None
+            assert info["launches_per_tick"] == {0: 1, 4: 2, 3: 4}[alg]
+            pipe.upload(d)
+            pipe.run(T, use_graph=graph)
+            out = pipe.download()
+            assert out["tick"] == T
+            _close(out, ref)
+            runs.append(out)
+        _same(runs[0], runs[1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("horizon", [50, 200])
+def test_reactive_tick_with_fused_kinematics_at_any_horizon(wca, qs, horizon):
+    """The reactive chain reads no gains: the FUSED kinematics hand-off (many ticks per launch) is taken at N = 200 too, where the MPC
+    handle still falls back to COMPACT."""
+    from oracle import tick_spec as ts
+    B, T = 12, 150
+    p = ts.TickParams(horizon=horizon)
+    kin, d = _walk_scenario(wca, B, T, horizon)
+    vmax = wca.synth.WALK_VMAX.copy()
+    mk = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=vmax, joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG))
+    ref = rt.run_ticks_reactive(p, d, T, qs.IKParams(v_max=vmax.copy(), joint_reg_deg=wca.synth.WALK_POSTURE_DEG.copy()), K_DCM["iCubGazeboV2_5"],
+                                kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT)
+    assert ref["ik_fail"].sum() == 0 and np.abs(ref["q_des"] - d["q0"]).max() > 0.05
+    pipe = wca.TickPipeline(B, T, wca.MpcSolver(horizon=horizon), mk(), log_ticks=T, kin=kin, dcm_controller="reactive", k_dcm=K_DCM["iCubGazeboV2_5"])
+    info = pipe.info()
+    assert info["kin_handoff"] == "fused" and info["ticks_per_launch"] > 1 and info["launches_per_tick"] == 1
+    pipe.upload(d)
+    pipe.run(T)
+    _close(pipe.download(), ref)
+    mpc = wca.TickPipeline(B, T, wca.MpcSolver(horizon=horizon), mk(), kin=kin).info()
+    assert mpc["dcm_controller"] == "mpc"
+    assert mpc["kin_handoff"] == ("fused" if horizon == 50 else "compact")
+
+
+@pytest.mark.gpu
+def test_explicit_dcm_velocity(wca, qs, tick_batch):
+    """The planner's DCM velocity: omega (ref - zmp_ref), the LIPM's exact one, follows the restatement; the forward difference passed
+    explicitly is what NULL means, bit for bit."""
+    from oracle import tick_spec as ts
+    B, T = 24, 150
+    p = ts.TickParams()
+    d = tick_batch
+    k = K_DCM["iCubGenova04"]
+    omega = np.sqrt(p.gravity / p.com_height)
+    vel = omega * (d["ref_traj"] - d["zmp_ref"])
+    fd = np.zeros_like(d["ref_traj"])
+    fd[:, :-1] = (d["ref_traj"][:, 1:] - d["ref_traj"][:, :-1]) / p.dT
+    assert np.abs(vel - fd)[:, :T].max() > 1e-4          # it is another velocity
+    ipar = qs.IKParams(v_max=VMAX * np.ones(23))
+
+    def run(v, tpl=0):
+        pipe = wca.TickPipeline(B, T, wca.MpcSolver(), wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=VMAX), log_ticks=T, ticks_per_launch=tpl,
+                                dcm_controller="reactive", k_dcm=k)
+        pipe.upload(d, dcm_vel_traj=v)
+        pipe.run(T)
+        return pipe.download()
+    ref = rt.run_ticks_reactive(p, d, T, ipar, k, dcm_vel=vel)
+    out = run(vel)
+    _close(out, ref)
+    assert np.abs(ref["u0_log"] - rt.run_ticks_reactive(p, d, T, ipar, k)["u0_log"]).max() > 1e-5
+    _same(run(fd), run(None))
+    _same(run(vel, 1), out)
+
+
+@pytest.mark.gpu
+def test_ticks_per_launch_and_shards_are_bit_identical(wca, tick_batch):
+    B, T = 24, 150
+    d = tick_batch
+    k = K_DCM["iCubGazeboV2_5"]
+    mk = lambda n, first=0, tpl=0: wca.TickPipeline(n, T, wca.MpcSolver(), wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=VMAX), first=first,
+                                                    log_ticks=T, ticks_per_launch=tpl, dcm_controller="reactive", k_dcm=k)
+    outs = []
+    for tpl, graph in ((0, False), (1, True), (3, False)):
+        pipe = mk(B, tpl=tpl)
+        pipe.upload(d)
+        pipe.run(61, use_graph=graph); pipe.run(T - 61, use_graph=graph)
+        outs.append(pipe.download())
+    _same(outs[0], outs[1]); _same(outs[0], outs[2])
+    half = wca.synth.synth_tick_batch(B // 2, T, first=B // 2)
+    pipe = mk(B // 2, first=B // 2)
+    pipe.upload(half)
+    pipe.run(61); pipe.run(T - 61)          # (the same calls: a call boundary moves the first chain of a call into the prime kernel)
+    part = pipe.download()
+    full = outs[0]
+    for key in ("u0_log", "dq_log"):
+        assert np.array_equal(part[key], full[key][:, B // 2:]), key
+    for key in ("q_des", "dcm", "com", "ik_fail", "active_lower", "active_upper"):
+        assert np.array_equal(part[key], full[key][B // 2:]), key
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kin_mode", [False, True], ids=["constant_jacobians", "fused_kinematics"])
+def test_reactive_external_plant(wca, qs, kin_mode):
+    """Fed its own logged plant state, the external-plant handle reproduces the internal run; fed a disturbed DCM (and other measurements),
+    it follows run_ticks(external=...) under the reactive restatement."""
+    from oracle import tick_spec as ts
+    B, T = 10, 60
+    p = ts.TickParams()
+    k = K_DCM["iCubGazeboV2_5"]
+    if kin_mode:
+        kin, d = _walk_scenario(wca, B, T)
+        vmax = wca.synth.WALK_VMAX.copy()
+        ipar = qs.IKParams(v_max=vmax, joint_reg_deg=wca.synth.WALK_POSTURE_DEG.copy())
+        okw = dict(kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT)
+        mk_ik = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=vmax, joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG))
+    else:
+        kin, d = None, wca.synth.synth_tick_batch(B, T)
+        ipar, okw = qs.IKParams(v_max=VMAX * np.ones(23)), {}
+        mk_ik = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=VMAX)
+    internal = rt.run_ticks_reactive(p, d, T, ipar, k, **okw)
+
+    def run_external(ext):
+        pipe = wca.TickPipeline(B, T, wca.MpcSolver(), mk_ik(), log_ticks=T, kin=kin, external_feedback=True, dcm_controller="reactive", k_dcm=k)
+        pipe.upload(d)
+        for t in range(T):
+            pipe.set_feedback_host(ext["dcm"][t], ext["com"][t], ext["zmp"][t], ext["q"][t] if ext.get("q") is not None else None)
+            pipe.run(1)
+        return pipe.download()
+    same = run_external(dict(dcm=internal["dcm_log"], com=internal["com_log"], zmp=internal["zmp_log"]))
+    _close(same, internal)
+    pipe = wca.TickPipeline(B, T, wca.MpcSolver(), mk_ik(), log_ticks=T, kin=kin, dcm_controller="reactive", k_dcm=k)
+    pipe.upload(d); pipe.run(T)
+    own = pipe.download()
+    for key in ("u0_log", "dq_log", "q_des"):
+        assert np.abs(same[key] - own[key]).max() <= 1e-9, key
+    rng = np.random.default_rng(4)
+    ext = dict(dcm=internal["dcm_log"] + 1e-3 * rng.normal(size=(T, B, 2)), com=internal["com_log"] + 5e-4 * rng.normal(size=(T, B, 2)),
+               zmp=internal["zmp_log"] + 2e-3 * rng.normal(size=(T, B, 2)), q=internal["q_log"] + 0.01 * rng.normal(size=(T, B, 23)))
+    ref = rt.run_ticks_reactive(p, d, T, ipar, k, external=ext, **okw)
+    out = run_external(ext)
+    for key in ("u0_log", "dq_log", "q_des"):
+        assert np.abs(out[key] - ref[key]).max() <= 1e-9, key
+    assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and out["mpc_fail"].sum() == 0
+    assert np.abs(ref["u0_log"] - internal["u0_log"]).max() > 1e-4
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kin_mode", [False, True], ids=["constant_jacobians", "fused_kinematics"])
+@pytest.mark.parametrize("explicit_vel", [False, True], ids=["forward_difference", "explicit_velocity"])
+def test_reactive_logger_rows(wca, qs, kin_mode, explicit_vel):
+    """Logger rows of a reactive run: columns 8-9 the reactive output, 4-5 the velocity the law used."""
+    from oracle import tick_spec as ts
+    B, T, L = 6, 40, 40
+    p = ts.TickParams()
+    k = K_DCM["icubGazeboSim"]
+    if kin_mode:
+        kin, d = _walk_scenario(wca, B, T)
+        vmax = wca.synth.WALK_VMAX
+        mk = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=vmax, joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG))
+        ipar = qs.IKParams(v_max=vmax.copy(), joint_reg_deg=wca.synth.WALK_POSTURE_DEG.copy())
+        okw = dict(kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT)
+    else:
+        kin, d = None, wca.synth.synth_tick_batch(B, T)
+        mk = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=VMAX)
+        ipar, okw = qs.IKParams(v_max=VMAX * np.ones(23)), {}
+    vel = np.sqrt(p.gravity / p.com_height) * (d["ref_traj"] - d["zmp_ref"]) if explicit_vel else None
+    ref = rt.run_ticks_reactive(p, d, T, ipar, k, dcm_vel=vel, logger_ticks=L, **okw)
+    outs = []
+    for lt in (L, 0):
+        pipe = wca.TickPipeline(B, T, wca.MpcSolver(), mk(), log_ticks=T, kin=kin, logger_ticks=lt, dcm_controller="reactive", k_dcm=k)
+        pipe.upload(d, dcm_vel_traj=vel); pipe.run(17); pipe.run(T - 17)
+        outs.append(pipe.download())
+    logged, plain = outs
+    assert np.array_equal(logged["dq_log"], plain["dq_log"]) and np.array_equal(logged["u0_log"], plain["u0_log"])
+    assert ref["ik_fail"].sum() == 0 and logged["ik_fail"].sum() == 0
+    err = np.abs(logged["logger"] - ref["logger"])
+    assert err.max() <= 1e-9, np.unravel_index(err.argmax(), err.shape)
+    assert np.array_equal(logged["logger"][:, :, 8:10], logged["u0_log"][:L])
+    if explicit_vel:
+        assert np.array_equal(logged["logger"][:, :, 4:6], np.transpose(vel[:, :L], (1, 0, 2)))
+
+
+@pytest.mark.gpu
+def test_reactive_refusals_and_hull_free_upload(wca, qs):
+    from oracle import tick_spec as ts
+    B, T = 8, 30
+    d = wca.synth.synth_tick_batch(B, T)
+    mk = lambda **kw: wca.TickPipeline(B, T, wca.MpcSolver(), wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=VMAX), log_ticks=T, **kw)
+    # the C entry point refuses an unknown controller and a k_dcm that is not finite
+    for ctrl, kd in ((2, 1.2), (wca.capi.TICK_DCM_REACTIVE, float("nan")), (wca.capi.TICK_DCM_REACTIVE, float("inf"))):
+        pipe = mk()
+        prm = wca.capi.TickParams.from_buffer_copy(pipe.params)
+        prm.dcm_controller, prm.k_dcm = ctrl, kd
+        h = C.c_void_p()
+        assert wca.capi.lib().wcqp_tick_create(C.byref(prm), C.byref(h)) == WCQP_E_INVALID and not h
+    # a splice with uploaded velocities: no velocity tail
+    pipe = mk(dcm_controller="reactive", k_dcm=1.2)
+    vel = np.zeros_like(d["ref_traj"])
+    pipe.upload(d, dcm_vel_traj=vel)
+    pipe.run(5)
+    prm_tail = np.ascontiguousarray(d["ref_traj"][:, 10:14])
+    rc = wca.capi.lib().wcqp_tick_splice_reference(pipe._h, 10, 4, prm_tail.ctypes.data_as(C.c_void_p), None)
+    assert rc == WCQP_E_UNSUPPORTED
+    # ... with the forward difference the splice works, and the velocity follows the new stages
+    p = ts.TickParams()
+    pipe.upload(d)
+    pipe.run(5)
+    tail = d["ref_traj"][:, 10:14] + 0.01
+    pipe.splice_reference(10, tail)
+    pipe.run(T - 5)
+    out = pipe.download()
+    d2 = dict(d); d2["ref_traj"] = d["ref_traj"].copy(); d2["ref_traj"][:, 10:14] = tail
+    ref = rt.run_ticks_reactive(p, d2, T, qs.IKParams(v_max=VMAX * np.ones(23)), 1.2)
+    _close(out, ref)
+    # a reactive handle with constant Jacobians takes an upload without hull tables; an MPC handle does not
+    bare = {k_: v for k_, v in d.items() if not k_.startswith("hull_tab")}
+    pipe = mk(dcm_controller="reactive", k_dcm=1.2)
+    pipe.upload(bare)
+    pipe.run(T)
+    _close(pipe.download(), rt.run_ticks_reactive(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23)), 1.2))
+    with pytest.raises(KeyError):
+        mk().upload(bare)

@@ -36,7 +36,7 @@ ABI_SYMBOLS = (
     "wcqp_hull_from_feet_device", "wcqp_hull_from_feet_host",
     "wcqp_kin_create", "wcqp_kin_destroy", "wcqp_kin_jacobians_device", "wcqp_kin_jacobians_host",
     "wcqp_tick_create", "wcqp_tick_destroy", "wcqp_tick_upload", "wcqp_tick_run", "wcqp_tick_download", "wcqp_tick_splice_reference",
-    "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host",
+    "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
 )
@@ -165,13 +165,22 @@ class TickParams(C.Structure):
                 ("k_com", C.c_double), ("k_zmp", C.c_double), ("noise", C.c_double), ("seed", C.c_uint64),
                 ("mpc", MpcParams), ("ik", IkParams),
                 ("ik_cold_start_only", C.c_int32), ("use_kinematics", C.c_int32), ("kin", KinParams), ("foot_rect", C.c_double * 8),
-                ("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("logger_ticks", C.c_int32), ("plant", C.c_int32)]
+                ("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("logger_ticks", C.c_int32), ("plant", C.c_int32),
+                ("dcm_controller", C.c_int32), ("k_dcm", C.c_double)]
+
+
+TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
+KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1, 0, 1, 2
+
+
+class TickInfo(C.Structure):
+    _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32)]
 
 
 class TickInputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("ref_traj", "hull_tab_A", "hull_tab_b", "hull_tab_nc", "phase0",
                                           "J_left", "J_right", "J_neck", "J_com", "state0", "swing_twist",
-                                          "q0", "dcm0", "com0", "u_init")]
+                                          "q0", "dcm0", "com0", "u_init", "dcm_vel_traj")]
 
 
 class TickOutputs(C.Structure):
@@ -221,6 +230,7 @@ def lib() -> C.CDLL:
         L.wcqp_tick_splice_reference.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.wcqp_tick_set_feedback_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wcqp_tick_set_feedback_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wcqp_tick_get_info.argtypes = [C.c_void_p, C.POINTER(TickInfo)]
         L.wcqp_qp_enqueue_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.POINTER(C.c_int32)]
         L.wcqp_qp_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.c_int32, C.POINTER(C.c_void_p)]
         L.wcqp_qp_plan_enqueue.argtypes = [C.c_void_p, C.c_void_p]
@@ -439,9 +449,17 @@ class TickPipeline:
     def __init__(self, batch, max_ticks, mpc: MpcSolver, ik: IkSolver, first=0, log_ticks=0,
                  step_ticks=180, ds_ticks=110, k_com=9.0, k_zmp=3.0, noise=1e-4, seed=99,
                  kin: "Optional[KinModel]" = None, foot_rect=None, ik_hot_start: bool = True, kin_handoff: int = 0,
-                 ticks_per_launch: int = 0, logger_ticks: int = 0, external_feedback: bool = False):
+                 ticks_per_launch: int = 0, logger_ticks: int = 0, external_feedback: bool = False,
+                 dcm_controller: str = "mpc", k_dcm: Optional[float] = None):
         """kin: a KinModel -> per-tick kinematics (Jacobians, actual poses and hull rows rebuilt every tick from the
-        integrated joint state with the base anchored at the stance foot; upload() then ignores J_* / hull_tab_*)."""
+        integrated joint state with the base anchored at the stance foot; upload() then ignores J_* / hull_tab_*).
+        dcm_controller: "mpc" (the DCM-MPC, the reference's use_mpc 1) or "reactive" (WalkingDCMReactiveController, the
+        reference's default use_mpc 0), which needs k_dcm (kDCM of the robot's dcmReactiveControllerParams.ini)."""
+        if dcm_controller not in ("mpc", "reactive"):
+            raise ValueError(f"dcm_controller must be 'mpc' or 'reactive', not {dcm_controller!r}")
+        self.reactive = dcm_controller == "reactive"
+        if self.reactive and k_dcm is None:
+            raise ValueError("the reactive DCM controller needs k_dcm")
         self.batch, self.max_ticks, self.log_ticks, self.dof = batch, max_ticks, log_ticks, ik.dof
         self.logger_ticks = int(logger_ticks)
         self.use_kin = kin is not None
@@ -451,7 +469,8 @@ class TickPipeline:
         self.params = TickParams(batch, first, max_ticks, log_ticks, step_ticks, ds_ticks, k_com, k_zmp, noise, seed,
                                  mpc.params, ik.params, int(not ik_hot_start), int(self.use_kin), kin.params if kin is not None else KinParams(),
                                  (C.c_double * 8)(*np.asarray(foot_rect, float).reshape(8)), int(kin_handoff), int(ticks_per_launch), int(logger_ticks),
-                                 int(bool(external_feedback)))
+                                 int(bool(external_feedback)), TICK_DCM_REACTIVE if self.reactive else TICK_DCM_MPC,
+                                 float(k_dcm) if k_dcm is not None else 0.0)
         self._h = C.c_void_p()
         check(lib().wcqp_tick_create(C.byref(self.params), C.byref(self._h)), "wcqp_tick_create")
         self._keep = None
@@ -467,16 +486,33 @@ class TickPipeline:
         except Exception:
             pass
 
-    def upload(self, data: dict):
+    def upload(self, data: dict, dcm_vel_traj=None):
+        """dcm_vel_traj: [B][max_ticks + N + 1][2], the planner's DCM velocity for the reactive controller (None: the forward
+        difference of ref_traj); MPC handles ignore it.  A reactive handle takes data without hull tables."""
         f64 = ("ref_traj", "state0", "swing_twist", "q0", "dcm0", "com0", "u_init")
-        f64 += () if self.use_kin else ("hull_tab_A", "hull_tab_b", "J_left", "J_right", "J_neck", "J_com")
+        f64 += () if self.use_kin else ("J_left", "J_right", "J_neck", "J_com")
+        if not self.use_kin and (not self.reactive or "hull_tab_A" in data):
+            f64 += ("hull_tab_A", "hull_tab_b")
         keep = {k: _f64(data[k]) for k in f64}
-        if not self.use_kin:
+        if "hull_tab_A" in keep:
             keep["hull_tab_nc"] = np.ascontiguousarray(data["hull_tab_nc"], dtype=np.int32)
         keep["phase0"] = np.ascontiguousarray(data["phase0"], dtype=np.int32)
         assert keep["ref_traj"].shape == (self.batch, self.max_ticks + self.params.mpc.horizon + 1, 2), keep["ref_traj"].shape
+        if dcm_vel_traj is not None:
+            keep["dcm_vel_traj"] = _f64(dcm_vel_traj)
+            assert keep["dcm_vel_traj"].shape == keep["ref_traj"].shape, keep["dcm_vel_traj"].shape
         ins = TickInputs(**{k: (keep[k].ctypes.data if k in keep else None) for k, _ in TickInputs._fields_})
         check(lib().wcqp_tick_upload(self._h, C.byref(ins)), "wcqp_tick_upload")
+
+    def info(self) -> dict:
+        """The form the handle took (wcqp_tick_get_info): kin_handoff ("fused", "compact", "dense" or None without kinematics),
+        ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick."""
+        i = TickInfo()
+        check(lib().wcqp_tick_get_info(self._h, C.byref(i)), "wcqp_tick_get_info")
+        return dict(kin_handoff={KIN_HANDOFF_NONE: None, KIN_HANDOFF_FUSED: "fused", KIN_HANDOFF_DENSE: "dense",
+                                 KIN_HANDOFF_COMPACT: "compact"}[i.kin_handoff],
+                    ticks_per_launch=int(i.ticks_per_launch), dcm_controller="reactive" if i.dcm_controller == TICK_DCM_REACTIVE else "mpc",
+                    launches_per_tick=int(i.launches_per_tick))
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")

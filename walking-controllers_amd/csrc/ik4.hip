@@ -164,7 +164,9 @@ struct MpcPairArgs {
 // EXT (tick kernel, wcqp_tick_params.plant = EXTERNAL): the IK regularises towards the caller's MEASURED joint positions
 // (TickDev::q_meas) instead of the desired ones - a kernel of its own: the two registers it holds across the kinematics phase
 // cost the fused-kinematics kernel 28 B of scratch, which the product kernel does not pay
-template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false>
+// REACT (tick kernel, wcqp_tick_params.dcm_controller = REACTIVE): the chain of tick t + 1 runs the reactive DCM controller
+// (tick_device.h: tick_react_*) in the MPC's place - ik4_tick_reactive_kernel
+template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false, bool REACT = false>
 __device__ __forceinline__
 void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 const double* __restrict__ JL, const double* __restrict__ JR,
@@ -177,6 +179,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 MpcPairArgs* pm = nullptr, double* carry = nullptr, int* gait = nullptr, const unsigned long long* noise_base = nullptr)
 {
     static_assert(!(TICK && PAIR), "the tick kernel carries its own MPC chain");
+    static_assert(TICK || !REACT, "the reactive controller is a tick form");
     constexpr bool COMPACT = JSRC == 1;
     constexpr bool KINF = JSRC == 2;
     int lane_id = threadIdx.x;
@@ -245,11 +248,13 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
         }
         }
     }
-    if constexpr (TICK) { if (do_mpc) wcqp_tick::tick_mpc_issue<KINF>(td, j, inst, tick_now + 1, mreg); else mreg.phase0 = td.phase0[inst]; }
+    if constexpr (TICK && !REACT) { if (do_mpc) wcqp_tick::tick_mpc_issue<KINF>(td, j, inst, tick_now + 1, mreg); else mreg.phase0 = td.phase0[inst]; }
     double2 cr0[5], cr1[5], cdv[5];        // COMPACT: the two joint records and the three vectors p_frame - p_base, as loaded
     int ckind0 = 0, ckind1 = 0;
-    double m_ux = 0.0, m_uy = 0.0;         // ... the MPC chain's partial sums, reduced early
+    double m_ux = 0.0, m_uy = 0.0;         // ... the MPC chain's partial sums, reduced early (REACT: m_ux = this lane's desired ZMP)
     double2 m_r0 = make_double2(0.0, 0.0);
+    double2 m_rd = make_double2(0.0, 0.0); // REACT: the reference DCM velocity of tick t + 1 (m_r0: its reference DCM)
+    if constexpr (TICK && REACT) { if (do_mpc) wcqp_tick::tick_react_issue(td, j, inst, tick_now + 1, mreg, m_r0, m_rd); else mreg.phase0 = td.phase0[inst]; }
     {
         // the state block first: vmcnt retires in order, and the rhs phase only needs the state, so the 36
         // Jacobian loads stay in flight underneath it
@@ -298,13 +303,17 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
             // of u0_unc now (its loads were issued first: they have landed when the pose block below has) and its per-axis records
             // and hull row wait in LDS; the pose block is re-read behind the kinematics (L2) instead of being held
             if (do_mpc) {
-                wcqp_tick::tick_mpc_partial<true>(td, j, inst, tick_now + 1, mreg, gr_lds, m_ux, m_uy);
-                m_r0 = mreg.L.r[0];
+                if constexpr (REACT) {
+                    m_ux = wcqp_tick::tick_react_law(td, j, mreg, m_r0, m_rd);       // (the reactive law needs nothing else: its output is all that waits)
+                } else {
+                    wcqp_tick::tick_mpc_partial<true>(td, j, inst, tick_now + 1, mreg, gr_lds, m_ux, m_uy);
+                    m_r0 = mreg.L.r[0];
+                }
                 if (j < 2) {
                     double* ms = S + K_MS + j * 8;
                     st2(ms, mreg.s01.x, mreg.s01.y); st2(ms + 2, mreg.s23.x, mreg.s23.y); st2(ms + 4, mreg.s45.x, mreg.s45.y); st2(ms + 6, mreg.s67.x, mreg.s67.y);
                 }
-                if (j < 8) { double* mh = S + K_MH + j * 3; mh[0] = mreg.ha.x; mh[1] = mreg.ha.y; mh[2] = mreg.hb; }
+                if (!REACT && j < 8) { double* mh = S + K_MH + j * 3; mh[0] = mreg.ha.x; mh[1] = mreg.ha.y; mh[2] = mreg.hb; }
             }
             WCQP_KSTAMP(1);          // MPC loads landed, partial sums stashed
             const int side = *gait >= td.step_ticks ? 1 : 0;          // (gait: this robot's cycle index (tick + phase0) % (2 step_ticks), carried from tick to tick) 0: left is the stance foot
@@ -564,7 +573,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                     const double* ms = S + K_MS + j * 8;
                     mreg.s01 = ld2(ms); mreg.s23 = ld2(ms + 2); mreg.s45 = ld2(ms + 4); mreg.s67 = ld2(ms + 6);
                 }
-                if (j < 8) { const double* mh = S + K_MH + j * 3; mreg.ha.x = mh[0]; mreg.ha.y = mh[1]; mreg.hb = mh[2]; }
+                if (!REACT && j < 8) { const double* mh = S + K_MH + j * 3; mreg.ha.x = mh[0]; mreg.ha.y = mh[1]; mreg.hb = mh[2]; }
             }
         } else if constexpr (COMPACT) {
             // compact kinematics -> IK hand-off (tick_device.h): one record per joint, [C lin3 | X ...], X = the joint's column of
@@ -621,7 +630,12 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
         }
         if constexpr (TICK) {
             // MPC(t+1), ZMP-CoM law and plant of tick t + 1 for the same four robots, while the Jacobians are on their way
-            if (do_mpc) {
+            if constexpr (REACT) {
+                if (do_mpc) {
+                    if constexpr (!KINF) m_ux = wcqp_tick::tick_react_law(td, j, mreg, m_r0, m_rd);
+                    wcqp_tick::tick_react_finish<EXT>(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, noise_base);
+                }
+            } else if (do_mpc) {
                 // (hull rows in the MPC stash's place, just read back: the attached frames at 312..347 are still needed)
                 const int cyc1 = *gait + 1 == 2 * td.step_ticks ? 0 : *gait + 1;
                 const int code1 = wcqp_tick::contact_code_cyc(cyc1, td.step_ticks, td.ds_ticks);
@@ -676,6 +690,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 const double r0 = td.ref_traj[((size_t)inst * td.traj_len + tick_now) * 2 + j];
                 const double r1 = td.ref_traj[((size_t)inst * td.traj_len + tick_now + 1) * 2 + j];
                 row[j] = hd[6 + j]; row[2 + j] = r0; row[4 + j] = (r1 - r0) / td.dT;        // the planner's DCM velocity: finite difference of the reference
+                if constexpr (REACT) row[4 + j] = td.dcm_vel[((size_t)inst * td.traj_len + tick_now) * 2 + j];     // ... the one the reactive law used
                 row[6 + j] = hd[10 + j]; row[8 + j] = hd[12 + j];
                 row[13 + j] = hd[j]; row[15 + j] = hd[2 + j];
             }
@@ -1604,28 +1619,30 @@ __device__ __forceinline__ int xcd_group(int b, int groups) {
 // memory for tick t + 1 (joint state, hand-off record, previous active set, live hull rows) is written and read by the
 // same wave, ordered by a workgroup-scope fence per tick.  No per-tick launch, no ramp-up / tail per tick, and a wave
 // whose robots walk a long active set on one tick catches up on the next instead of holding the whole launch.
-template <bool TICK, int JSRC, bool LOG = false, bool EXT = false>
-__global__ __launch_bounds__(64, WCQP_IK4_WAVES)
-void ik4_kernel(const IkDeviceParams* __restrict__ prm, int batch,
-                const double* __restrict__ JL, const double* __restrict__ JR,
-                const double* __restrict__ JN, const double* __restrict__ JC,
-                const double* qpos, const double* __restrict__ state,
-                double* __restrict__ dq_out, int* __restrict__ status_out,
-                unsigned* __restrict__ alo_out, unsigned* __restrict__ aup_out,
-                double* __restrict__ ferr_out, int* __restrict__ iters_out, const wcqp_tick::TickDev* __restrict__ tdp, int phase, int n_inner, int skip_last_mpc)
+// the tick kernels' walk through n_inner ticks (ik4_kernel<true, ...> with the MPC, ik4_tick_reactive_kernel with the reactive controller).
+// kmodel / kgains: the LDS the kernel declares for the kinematic model and (MPC, fused kinematics) the MPC's gain blocks.
+// (No __restrict__ on these parameters: the kernel's own carry it, and repeating it here changes the MPC kernels' code - their
+// SGPR spills grow by 10 to 18.)
+template <int JSRC, bool LOG, bool EXT, bool REACT>
+__device__ __forceinline__
+void ik4_tick_walk(const IkDeviceParams* prm, int batch,
+                   const double* JL, const double* JR,
+                   const double* JN, const double* JC,
+                   const double* qpos, const double* state,
+                   double* dq_out, int* status_out,
+                   unsigned* alo_out, unsigned* aup_out,
+                   double* ferr_out, int* iters_out, const wcqp_tick::TickDev* tdp, int phase, int n_inner, int skip_last_mpc,
+                   double (*smem)[PER_INST], double* kmodel, double* kgains)
 {
-    __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
-    if constexpr (TICK) {
+    {
         // TickDev lives in device memory, not in the kernel arguments: hipcc hoists kernel-argument loads out of the loop over
         // ticks as invariant (a hundred SGPRs live across the whole body, spilled to VGPR lanes); loads through this pointer
         // stay where they are used (memory clobber at the top of an iteration)
         const wcqp_tick::TickDev& td = *tdp;
-        __shared__ __attribute__((aligned(16))) double kmodel[JSRC == 2 ? wcqp_tick::kKinTabSize : 2];
-        __shared__ __attribute__((aligned(16))) double kgains[JSRC == 2 ? 4 * wcqp_tick::kGainsLdsStages : 2];
         if constexpr (JSRC == 2) {
             // the kinematic model and the MPC's gain blocks, once per launch: every tick of every robot of this wave reads them from LDS
             for (int k = threadIdx.x; k < wcqp_tick::kKinTabSize; k += 64) kmodel[k] = td.kin_tab[k];
-            for (int k = threadIdx.x; k < 4 * (td.horizon + 1); k += 64) kgains[k] = td.mpc.Gr[k];
+            if constexpr (!REACT) for (int k = threadIdx.x; k < 4 * (td.horizon + 1); k += 64) kgains[k] = td.mpc.Gr[k];
             wcqp::wave_lds_fence();
         }
         const int t0 = td.tick2[phase];
@@ -1645,7 +1662,7 @@ void ik4_kernel(const IkDeviceParams* __restrict__ prm, int batch,
 #pragma unroll 1
         for (int k = 0; k < n_inner; ++k) {
             __asm__ volatile("" ::: "memory");        // nothing of the body is hoisted out of the loop (its registers are all spoken for)
-            ik4_body<TICK, JSRC, false, LOG, EXT>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out, td, smem,
+            ik4_body<true, JSRC, false, LOG, EXT, REACT>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out, td, smem,
                                              (int)blockIdx.x, t0 + k, !(skip_last_mpc && k == n_inner - 1), kmodel, kgains, nullptr, carry, &gait, &nbase);
             gait = gait + 1 == 2 * td.step_ticks ? 0 : gait + 1;
             // tick t + 1 of this wave reads what tick t wrote (other lanes of the same wave): visible before it starts
@@ -1662,11 +1679,52 @@ void ik4_kernel(const IkDeviceParams* __restrict__ prm, int batch,
         }
         // advanceReferenceSignals (WalkingModule.cpp:816): the next launch reads the other copy of the tick index
         if (blockIdx.x == 0 && threadIdx.x == 0) td.tick2[1 - phase] = t0 + n_inner;
+    }
+}
+
+#ifndef WCQP_IK4_REACTIVE_TU
+template <bool TICK, int JSRC, bool LOG = false, bool EXT = false>
+__global__ __launch_bounds__(64, WCQP_IK4_WAVES)
+void ik4_kernel(const IkDeviceParams* __restrict__ prm, int batch,
+                const double* __restrict__ JL, const double* __restrict__ JR,
+                const double* __restrict__ JN, const double* __restrict__ JC,
+                const double* qpos, const double* __restrict__ state,
+                double* __restrict__ dq_out, int* __restrict__ status_out,
+                unsigned* __restrict__ alo_out, unsigned* __restrict__ aup_out,
+                double* __restrict__ ferr_out, int* __restrict__ iters_out, const wcqp_tick::TickDev* __restrict__ tdp, int phase, int n_inner, int skip_last_mpc)
+{
+    __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
+    if constexpr (TICK) {
+        __shared__ __attribute__((aligned(16))) double kmodel[JSRC == 2 ? wcqp_tick::kKinTabSize : 2];
+        __shared__ __attribute__((aligned(16))) double kgains[JSRC == 2 ? 4 * wcqp_tick::kGainsLdsStages : 2];
+        ik4_tick_walk<JSRC, LOG, EXT, false>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out,
+                                             tdp, phase, n_inner, skip_last_mpc, smem, kmodel, kgains);
     } else {
         ik4_body<TICK, JSRC>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out, wcqp_tick::TickDev{}, smem, xcd_group((int)blockIdx.x, (int)gridDim.x));
     }
 }
 
+#else
+// The tick kernel with the REACTIVE DCM controller (wcqp_tick_params.dcm_controller): the walk of ik4_kernel<true, JSRC, LOG, EXT>, the
+// chain of tick t + 1 the closed-form law instead of the MPC - no gain blocks in LDS (with fused kinematics at any horizon), no hull rows
+template <int JSRC, bool LOG = false, bool EXT = false>
+__global__ __launch_bounds__(64, WCQP_IK4_WAVES)
+void ik4_tick_reactive_kernel(const IkDeviceParams* __restrict__ prm, int batch,
+                              const double* __restrict__ JL, const double* __restrict__ JR,
+                              const double* __restrict__ JN, const double* __restrict__ JC,
+                              const double* qpos, const double* __restrict__ state,
+                              double* __restrict__ dq_out, int* __restrict__ status_out,
+                              unsigned* __restrict__ alo_out, unsigned* __restrict__ aup_out,
+                              double* __restrict__ ferr_out, int* __restrict__ iters_out, const wcqp_tick::TickDev* __restrict__ tdp, int phase, int n_inner, int skip_last_mpc)
+{
+    __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
+    __shared__ __attribute__((aligned(16))) double kmodel[JSRC == 2 ? wcqp_tick::kKinTabSize : 2];
+    ik4_tick_walk<JSRC, LOG, EXT, true>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out,
+                                        tdp, phase, n_inner, skip_last_mpc, smem, kmodel, nullptr);
+}
+#endif
+
+#ifndef WCQP_IK4_REACTIVE_TU
 // The MPC chain of ONE tick for every robot, on its own: primes the skewed tick after an upload (MPC(0) has to have run
 // before the first fused launch, which carries IK(0) and MPC(1)).
 template <bool EXT>
@@ -1682,6 +1740,24 @@ void tick_mpc_prime_kernel(wcqp_tick::TickDev td, int t)
     wcqp_tick::tick_mpc_issue(td, j, inst, t, mreg);
     wcqp_tick::tick_mpc_finish<false, EXT>(td, j, inst, live, t, mreg, s_hull[grp]);
 }
+#else
+// The chain of one tick with the reactive controller for every robot, on its own (primes ik4_tick_reactive_kernel)
+template <bool EXT>
+__global__ __launch_bounds__(64)
+void tick_reactive_prime_kernel(wcqp_tick::TickDev td, int t)
+{
+    const int lane = threadIdx.x, j = lane & 15;
+    const long inst_raw = (long)blockIdx.x * 4 + (lane >> 4);
+    const bool live = inst_raw < td.batch;
+    const long inst = live ? inst_raw : (long)td.batch - 1;
+    wcqp_tick::TickMpcRegs mreg;
+    double2 r0, rd;
+    wcqp_tick::tick_react_issue(td, j, inst, t, mreg, r0, rd);
+    wcqp_tick::tick_react_finish<EXT>(td, j, inst, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd));
+}
+#endif
+
+#ifndef WCQP_IK4_REACTIVE_TU
 
 // Both QPs of a batch of robot-ticks in ONE launch (wcqp_qp_enqueue_steps, a record whose two calls go to the same
 // stream): workgroups 0 .. ik_blocks-1 are the IK kernel above, the rest the DCM-MPC kernel of mpc.hip (same device
@@ -1829,10 +1905,12 @@ void ik_plan_kernel(const IkDeviceParams* __restrict__ prm, int batch, const wcq
     __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
     plan_walk<false>(prm, batch, recs, n_steps, ways, groups, c, queue, smem);
 }
+#endif  // WCQP_IK4_REACTIVE_TU
 
 }  // namespace
 
 namespace wcqp_ik {
+#ifndef WCQP_IK4_REACTIVE_TU
 
 int ik4_plan_queue_grid(int batch, int n_steps) {
     int dev = 0, cus = 0;
@@ -1881,42 +1959,87 @@ int ik4_launch(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream
     return WCQP_OK;
 }
 
-int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
-                    int n_inner, int skip_last_mpc, hipStream_t stream) {
-    if (n_inner < 1) return WCQP_E_INVALID;       // (whether a handle may run several ticks per launch is decided at wcqp_tick_create)
-    if (!d_prm || !td_dev || !td.skew || !td.mst || !td.hand || !td.live_A || !td.live_b || !td.live_nc || !td.sel_built) return WCQP_E_INVALID;
-    if (td.compact && (!td.jcomp || td.cstride < 1)) return WCQP_E_INVALID;
-    if (td.kin_fused && (!td.kin_tab || !td.kin_mode || td.kin_rounds < 0 || td.kin_rounds > 3 || td.horizon >= wcqp_tick::kGainsLdsStages)) return WCQP_E_INVALID;
-    const IkDeviceParams* prm = static_cast<const IkDeviceParams*>(d_prm);
+// the tick kernel of this translation unit's controller: ik4_kernel<true, ...> (the MPC) ...
+template <int JSRC, bool LOG = false, bool EXT = false>
+static void tick_kernel_launch(const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
+                               int n_inner, int skip_last_mpc, hipStream_t stream) {
+    ik4_launch_as<true, JSRC, LOG, EXT>(prm, batch, io, td_dev, phase, n_inner, skip_last_mpc, stream);
+}
+#else
+// ... or ik4_tick_reactive_kernel (ik4_reactive.hip: the reactive controller's kernels are a code object of their own, so that adding
+// them moves none of the kernels above - their addresses included)
+template <int JSRC, bool LOG = false, bool EXT = false>
+static void tick_kernel_launch(const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
+                               int n_inner, int skip_last_mpc, hipStream_t stream) {
+    hipLaunchKernelGGL((ik4_tick_reactive_kernel<JSRC, LOG, EXT>), dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, stream, prm, batch,
+                       io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters,
+                       td_dev, phase, n_inner, skip_last_mpc);
+}
+#endif
+
+// the tick kernel of a handle's form (checked by ik4_launch_tick)
+static int ik4_launch_tick_forms(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                                 int n_inner, int skip_last_mpc, hipStream_t stream) {
     const int B = td.batch, ph = td.phase;
     if (td.logger_ticks > 0) {
         // the logging kernels (a debugging aid like the reference's dumpData): dense Jacobians also produce the foot errors
         if (!td.log_rows) return WCQP_E_INVALID;
-        if (td.kin_fused) ik4_launch_as<true, 2, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else if (td.compact) ik4_launch_as<true, 1, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else ik4_launch_as<true, 0, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        if (td.kin_fused) tick_kernel_launch<2, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else if (td.compact) tick_kernel_launch<1, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else tick_kernel_launch<0, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
     } else if (td.q_meas) {
         // external feedback (wcqp_tick_params.plant = EXTERNAL): measured joints in the IK's regularisation; one tick per launch
         if (n_inner != 1 || td.compact) return WCQP_E_INVALID;
-        if (td.kin_fused) ik4_launch_as<true, 2, false, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else ik4_launch_as<true, 0, false, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        if (td.kin_fused) tick_kernel_launch<2, false, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else tick_kernel_launch<0, false, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
     } else {
-        if (td.kin_fused) ik4_launch_as<true, 2>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else if (td.compact) ik4_launch_as<true, 1>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else ik4_launch_as<true, 0>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        if (td.kin_fused) tick_kernel_launch<2>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else if (td.compact) tick_kernel_launch<1>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else tick_kernel_launch<0>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
     }
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
 
+#ifndef WCQP_IK4_REACTIVE_TU
+int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                    int n_inner, int skip_last_mpc, hipStream_t stream) {
+    if (n_inner < 1) return WCQP_E_INVALID;       // (whether a handle may run several ticks per launch is decided at wcqp_tick_create)
+    if (!d_prm || !td_dev || !td.skew || !td.mst || !td.hand || !td.live_A || !td.live_b || !td.live_nc || !td.sel_built) return WCQP_E_INVALID;
+    if (td.compact && (!td.jcomp || td.cstride < 1)) return WCQP_E_INVALID;
+    // (the MPC's gain blocks sit in LDS beside the model: a horizon limit the reactive controller, which reads no gains, does not have)
+    if (td.kin_fused && (!td.kin_tab || !td.kin_mode || td.kin_rounds < 0 || td.kin_rounds > 3 || (!td.reactive && td.horizon >= wcqp_tick::kGainsLdsStages))) return WCQP_E_INVALID;
+    if (td.reactive && !td.dcm_vel) return WCQP_E_INVALID;
+    const IkDeviceParams* prm = static_cast<const IkDeviceParams*>(d_prm);
+    return td.reactive ? ik4_launch_tick_reactive(prm, td, td_dev, io, n_inner, skip_last_mpc, stream)
+                       : ik4_launch_tick_forms(prm, td, td_dev, io, n_inner, skip_last_mpc, stream);
+}
+
 // MPC chain of tick t alone (see tick_mpc_prime_kernel)
 int ik4_launch_tick_prime(const wcqp_tick::TickDev& td, int t, hipStream_t stream) {
     if (!td.skew || !td.mst || !td.hand) return WCQP_E_INVALID;
+    if (td.reactive) return ik4_launch_tick_prime_reactive(td, t, stream);
     const unsigned grid = (unsigned)((td.batch + 3) / 4);
     if (td.q_meas) hipLaunchKernelGGL(tick_mpc_prime_kernel<true>, dim3(grid), dim3(64), 0, stream, td, t);      // external feedback: the caller's measured ZMP
     else hipLaunchKernelGGL(tick_mpc_prime_kernel<false>, dim3(grid), dim3(64), 0, stream, td, t);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
+#else
+int ik4_launch_tick_reactive(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                             int n_inner, int skip_last_mpc, hipStream_t stream) {
+    return ik4_launch_tick_forms(prm, td, td_dev, io, n_inner, skip_last_mpc, stream);
+}
+
+// the reactive chain of tick t alone (see tick_reactive_prime_kernel)
+int ik4_launch_tick_prime_reactive(const wcqp_tick::TickDev& td, int t, hipStream_t stream) {
+    if (!td.dcm_vel) return WCQP_E_INVALID;
+    const unsigned grid = (unsigned)((td.batch + 3) / 4);
+    if (td.q_meas) hipLaunchKernelGGL(tick_reactive_prime_kernel<true>, dim3(grid), dim3(64), 0, stream, td, t);
+    else hipLaunchKernelGGL(tick_reactive_prime_kernel<false>, dim3(grid), dim3(64), 0, stream, td, t);
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+#endif
 
 }  // namespace wcqp_ik

@@ -395,4 +395,8 @@ constexpr unsigned kPlanQueues = 32, kPlanQueueStride = 4352;
 constexpr size_t kPlanQueueBytes = (size_t)(kPlanQueues + 1) * kPlanQueueStride;
 // the MPC chain of tick t alone: primes the skewed tick after an upload
 int ik4_launch_tick_prime(const wcqp_tick::TickDev& td, int t, hipStream_t stream);
+// the same two with the REACTIVE DCM controller (ik4_reactive.hip; ik4_launch_tick / ik4_launch_tick_prime hand a reactive handle over)
+int ik4_launch_tick_reactive(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                             int n_inner, int skip_last_mpc, hipStream_t stream);
+int ik4_launch_tick_prime_reactive(const wcqp_tick::TickDev& td, int t, hipStream_t stream);
 }  // namespace wcqp_ik

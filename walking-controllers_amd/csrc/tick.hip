@@ -5,10 +5,12 @@
 // Reference call order reproduced (citations relative to /root/reference/modules/Walking_module):
 //   src/WalkingModule.cpp:578-597   StableDCMModel::integrateModel        -> tick_glue_kernel (consumer)
 //   src/WalkingModule.cpp:604-636   MPC bracket                           -> mpc_condensed_kernel
+//   src/WalkingModule.cpp:638-656   reactive DCM controller (use_mpc 0)   -> tick_reactive_kernel (in-order forms), tick_react_* (skewed)
 //   src/WalkingModule.cpp:657-695   WalkingZMPController + desired CoM    -> tick_glue_kernel
 //   src/WalkingModule.cpp:709-740   IK bracket                            -> ik_kernel
 //   src/WalkingModule.cpp:741-744   velocity integration                  -> tick_post_kernel
 //   src/WalkingModule.cpp:816       advanceReferenceSignals               -> tick counter in HBM
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -48,6 +50,29 @@ __global__ void tick_post_kernel(TickDev d) {
     tick_post_joint(d, i, t, g % kDof, ok, d.dq[g]);
     if (g % kDof == 0) tick_post_instance(d, i, t, ok);
     if (g == 0) d.tick2[1 - d.phase] = t + 1;      // advanceReferenceSignals (WalkingModule.cpp:816)
+}
+
+// the reactive DCM controller in the MPC launch's place (the in-order forms: the glue reads u0 / mpc_status as it does the MPC's):
+// WalkingDCMReactiveController::evaluateControl (WM/src/WalkingDCMReactiveController.cpp:63-82) at the plant's DCM
+__global__ void tick_reactive_kernel(TickDev d) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.batch * 2) return;
+    const int i = g >> 1, ax = g & 1;
+    const size_t w = ((size_t)i * d.traj_len + d.tick2[d.phase]) * 2 + ax;
+    d.u0[g] = reactive_zmp(d, d.ref_traj[w], d.dcm_vel[w], d.dcm[g]);
+    if (ax == 0) d.mpc_status[i] = WCQP_STATUS_SOLVED;
+}
+
+// the forward difference (ref[s + 1] - ref[s]) / dT of the stages [from, to) of every robot's reference: the reactive controller's DCM
+// velocity when none was uploaded, kept in step with wcqp_tick_splice_reference (stream order, behind the strided copy)
+__global__ void tick_vel_diff_kernel(TickDev d, int from, int to) {
+    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = to - from;
+    if (g >= (long)d.batch * n * 2) return;
+    const long i = g / (2 * n);
+    const int s = from + (int)((g / 2) % n), ax = (int)(g & 1);
+    const size_t w = ((size_t)i * d.traj_len + s) * 2 + ax;
+    const_cast<double*>(d.dcm_vel.get())[w] = (d.ref_traj[w + 2] - d.ref_traj[w]) / d.dT;
 }
 
 // external feedback: the caller's measured state into the places the next tick reads its plant state from - the skewed
@@ -96,6 +121,7 @@ struct wcqp_tick_s {
     double* splice_stage = nullptr; size_t splice_cap = 0;
     hipStream_t copy_stream = nullptr;
     hipEvent_t splice_done = nullptr; bool splice_pending = false;
+    bool vel_explicit = false;    // uploaded with an explicit dcm_vel_traj (reactive controller): the splice has no velocity tail
     bool external = false, feedback_set = false;     // wcqp_tick_params.plant = EXTERNAL: one tick per run call, each behind a set_feedback
     double* q_meas = nullptr;
     double* fb_stage = nullptr;   // wcqp_tick_set_feedback_host: [B][2 + 2 + 2 + dof]
@@ -134,13 +160,17 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
     // base-eliminated IK kernel: IK + post step of this tick and MPC + glue + plant of the NEXT one in ONE launch (skewed tick)
     if (h->form == TickForm::SKEWED)
         return wcqp_ik::ik4_launch_tick(wcqp::ik_device_params(h->ik), d, h->d_dev, io, n_inner, skip_last_mpc, s);
-    int rc = wcqp::mpc_enqueue(h->mpc, B, d.dcm, d.ref_traj, N + 1, d.traj_len, d.tick2 + d.phase, d.u_prev,
-                               d.hull_tab_A, d.hull_tab_b, d.hull_tab_nc, d.hull_sets, d.hull_sets > 1 ? d.sel : nullptr,
-                               d.u0, d.mpc_status, h->mpc_active, h->mpc_margin, s);
-    if (rc != WCQP_OK) return rc;
+    if (d.reactive) {
+        hipLaunchKernelGGL(tick_reactive_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, s, d);
+    } else {
+        const int rc = wcqp::mpc_enqueue(h->mpc, B, d.dcm, d.ref_traj, N + 1, d.traj_len, d.tick2 + d.phase, d.u_prev,
+                                         d.hull_tab_A, d.hull_tab_b, d.hull_tab_nc, d.hull_sets, d.hull_sets > 1 ? d.sel : nullptr,
+                                         d.u0, d.mpc_status, h->mpc_active, h->mpc_margin, s);
+        if (rc != WCQP_OK) return rc;
+    }
     if (h->form == TickForm::MPC_IK16) return wcqp_ik::ik3_launch_tick(wcqp::ik_device_params(h->ik), d, io, s);
     hipLaunchKernelGGL(tick_glue_kernel, dim3((B + 127) / 128), dim3(128), 0, s, d);
-    rc = wcqp_ik_solve_device(h->ik, B, io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, nullptr, nullptr, s);
+    const int rc = wcqp_ik_solve_device(h->ik, B, io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, nullptr, nullptr, s);
     if (rc != WCQP_OK) return rc;
     hipLaunchKernelGGL(tick_post_kernel, dim3((B * kDof + 255) / 256), dim3(256), 0, s, d);
     WCQP_HIP_TRY(hipGetLastError());
@@ -163,6 +193,9 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     wcqp_tick_s* h = new (std::nothrow) wcqp_tick_s();
     if (!h) return WCQP_E_NOMEM;
     h->p = *params;
+    const bool reactive = params->dcm_controller == WCQP_TICK_DCM_REACTIVE;
+    if ((params->dcm_controller != WCQP_TICK_DCM_MPC && !reactive) || (reactive && !std::isfinite(params->k_dcm))) { delete h; return WCQP_E_INVALID; }
+    // (a reactive handle keeps the MPC handle for the horizon and the LIPM's discretisation, without its condensed gains)
     int rc = wcqp_mpc_create(&params->mpc, &h->mpc);
     if (rc == WCQP_OK) rc = wcqp_ik_create(&params->ik, &h->ik);
     if (rc == WCQP_OK && params->use_kinematics) {
@@ -170,7 +203,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
         if (rc == WCQP_OK) rc = wcqp_kin_create(&params->kin, &h->kin);
         if (rc == WCQP_OK) rc = wcqp::kin_prepare(h->kin);
     }
-    if (rc == WCQP_OK) rc = wcqp::mpc_prepare(h->mpc);
+    if (rc == WCQP_OK && !reactive) rc = wcqp::mpc_prepare(h->mpc);
     if (rc == WCQP_OK) rc = wcqp::ik_prepare(h->ik);
     if (rc != WCQP_OK) { wcqp_tick_destroy(h); return rc; }
     // the tick's Jacobians are MIXED free-floating ones (uploaded or from wcqp_kin_*): an instance that is not comes
@@ -217,12 +250,13 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     const bool masks_ok = d.skew && h->kin && wcqp::kin_compact_layout(h->kin, cm, &cstride, &coff_d);
     // kinematics fused into the solve kernel (default), or a kinematics launch per tick handing over compact records / dense Jacobians
     std::vector<double> ktab;
-    const bool fusedk = masks_ok && params->kin_handoff == WCQP_KIN_HANDOFF_FUSED && N < kGainsLdsStages &&
+    const bool fusedk = masks_ok && params->kin_handoff == WCQP_KIN_HANDOFF_FUSED && (reactive || N < kGainsLdsStages) &&
                         wcqp::kin_fused_tables(h->kin, ktab, &d.kin_rounds);
     const bool compact = masks_ok && !fusedk && params->kin_handoff != WCQP_KIN_HANDOFF_DENSE;
     // external feedback: the default (base-eliminated) kernel with constant Jacobians or fused kinematics, without logger rows
     if (h->external && (!d.skew || params->logger_ticks > 0 || (h->kin && !fusedk))) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }
     if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); }
+    if (reactive) { double* vel = nullptr; A_(vel, B * d.traj_len * 2); d.dcm_vel = vel; d.reactive = 1; d.k_dcm = params->k_dcm; }
     if (d.skew) {
         A_(d.mst, B * 16); A_(d.hand, 2 * B * kHandLen); A_(d.live_A, B * 16); A_(d.live_b, B * 8); A_(d.live_nc, B); A_(d.sel_built, B);
         if (compact) A_(jcomp, B * (size_t)cstride);
@@ -282,13 +316,30 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
 int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     if (!h || !in) return WCQP_E_INVALID;
     if (!in->ref_traj || !in->phase0 || !in->state0 || !in->swing_twist || !in->q0 || !in->dcm0 || !in->com0 || !in->u_init) return WCQP_E_INVALID;
-    if (!h->kin && (!in->hull_tab_A || !in->hull_tab_b || !in->hull_tab_nc || !in->J_left || !in->J_right || !in->J_neck || !in->J_com))
-        return WCQP_E_INVALID;
+    if (!h->kin && (!in->J_left || !in->J_right || !in->J_neck || !in->J_com)) return WCQP_E_INVALID;
+    // (the reactive controller reads no hull rows)
+    if (!h->kin && !h->d.reactive && (!in->hull_tab_A || !in->hull_tab_b || !in->hull_tab_nc)) return WCQP_E_INVALID;
     TickDev& d = h->d;
     const size_t B = (size_t)d.batch;
     WCQP_HIP_TRY(hipDeviceSynchronize());
 #define UP_(dst, src, n) WCQP_HIP_TRY(hipMemcpy(const_cast<void*>(static_cast<const void*>(dst)), (src), (n), hipMemcpyHostToDevice))
     UP_(d.ref_traj, in->ref_traj, B * d.traj_len * 16);
+    if (d.reactive) {
+        // the planner's DCM velocity, or the forward difference (ref[t + 1] - ref[t]) / dT (the last stage, which no tick reads: 0)
+        h->vel_explicit = in->dcm_vel_traj != nullptr;
+        if (h->vel_explicit) {
+            UP_(d.dcm_vel, in->dcm_vel_traj, B * d.traj_len * 16);
+        } else {
+            std::vector<double> vel(B * d.traj_len * 2, 0.0);
+            for (size_t i = 0; i < B; ++i)
+                for (size_t k = 0; k + 1 < (size_t)d.traj_len; ++k)
+                    for (int ax = 0; ax < 2; ++ax) {
+                        const size_t w = (i * d.traj_len + k) * 2 + ax;
+                        vel[w] = (in->ref_traj[w + 2] - in->ref_traj[w]) / d.dT;
+                    }
+            UP_(d.dcm_vel, vel.data(), B * d.traj_len * 16);
+        }
+    }
     UP_(d.phase0, in->phase0, B * 4); UP_(d.swing_twist, in->swing_twist, B * 48);
     if (d.skew) {
         // state of the MPC chain per axis: c_ref, v_ref_prev, com, u_prev (= measured ZMP), p_star, v_star_prev, dcm, spare
@@ -308,7 +359,9 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
         for (size_t i = 0; i < B; ++i) h0[i] = in->state0[i * kStateLen + 68];       // desired CoM height = the initial one
         WCQP_HIP_TRY(hipMemcpy(const_cast<double*>(d.com_h0.get()), h0.data(), B * 8, hipMemcpyHostToDevice));
     } else {
-        UP_(d.hull_tab_A, in->hull_tab_A, B * 3 * 128); UP_(d.hull_tab_b, in->hull_tab_b, B * 3 * 64); UP_(d.hull_tab_nc, in->hull_tab_nc, B * 3 * 4);
+        if (in->hull_tab_A && in->hull_tab_b && in->hull_tab_nc) {
+            UP_(d.hull_tab_A, in->hull_tab_A, B * 3 * 128); UP_(d.hull_tab_b, in->hull_tab_b, B * 3 * 64); UP_(d.hull_tab_nc, in->hull_tab_nc, B * 3 * 4);
+        }
         UP_(h->J_left, in->J_left, B * 6 * 29 * 8); UP_(h->J_right, in->J_right, B * 6 * 29 * 8);
         UP_(h->J_neck, in->J_neck, B * 3 * 29 * 8); UP_(h->J_com, in->J_com, B * 3 * 29 * 8);
     }
@@ -452,6 +505,7 @@ int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stage
     // stages the ticks already enqueued have consumed as their own reference DCM stay as they are; everything a later
     // tick's window can see may change
     if (from_tick < h->ticks_enqueued || (long)from_tick + n_stages > (long)d.traj_len) return WCQP_E_INVALID;
+    if (h->vel_explicit) return WCQP_E_UNSUPPORTED;      // (the reactive controller's uploaded velocities: the splice has no tail for them)
     // `ref_tail` is the caller's HOST memory and the copy below is ordered behind ticks that may still run for a long time: the
     // rows are therefore taken NOW - staged into device memory of the handle on a copy stream of its own, waited for before
     // this call returns - and the caller may release `ref_tail` as soon as it has.
@@ -471,6 +525,15 @@ int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stage
     // behind the ticks already enqueued (the trajectory pointer the kernels - and any captured graph - hold does not change)
     WCQP_HIP_TRY(hipMemcpy2DAsync(const_cast<double*>(d.ref_traj.get()) + (size_t)from_tick * 2, (size_t)d.traj_len * 16, h->splice_stage, (size_t)n_stages * 16,
                                   (size_t)n_stages * 16, (size_t)d.batch, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d.reactive) {
+        // the forward difference of the stages the new ones touch: [from_tick - 1, from_tick + n_stages), the last stage excepted
+        const int lo = from_tick > 0 ? from_tick - 1 : 0, hi = from_tick + n_stages < d.traj_len ? from_tick + n_stages : d.traj_len - 1;
+        if (hi > lo) {
+            const long n = (long)d.batch * (hi - lo) * 2;
+            hipLaunchKernelGGL(tick_vel_diff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d, lo, hi);
+            WCQP_HIP_TRY(hipGetLastError());
+        }
+    }
     WCQP_HIP_TRY(hipEventRecord(h->splice_done, (hipStream_t)stream));
     h->splice_pending = true;
     return WCQP_OK;
@@ -485,6 +548,17 @@ int wcqp_tick_debug_stamps(wcqp_tick_t h, unsigned long long* out, int32_t n) {
     return WCQP_OK;
 }
 #endif
+
+int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
+    if (!h || !out) return WCQP_E_INVALID;
+    const TickDev& d = h->d;
+    out->kin_handoff = !h->kin ? -1 : d.kin_fused ? WCQP_KIN_HANDOFF_FUSED : d.compact ? WCQP_KIN_HANDOFF_COMPACT : WCQP_KIN_HANDOFF_DENSE;
+    out->ticks_per_launch = h->ticks_per_launch;
+    out->dcm_controller = d.reactive ? WCQP_TICK_DCM_REACTIVE : WCQP_TICK_DCM_MPC;
+    // a kinematics launch unless fused; then the skewed kernel (1), MPC / reactive + the 16-lane kernel (2) or controller, glue, IK, post (4)
+    out->launches_per_tick = (h->kin && !d.kin_fused ? 1 : 0) + (h->form == TickForm::SKEWED ? 1 : h->form == TickForm::MPC_IK16 ? 2 : 4);
+    return WCQP_OK;
+}
 
 int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out) {
     if (!h || !out) return WCQP_E_INVALID;

@@ -81,6 +81,11 @@ struct TickDev {
     // (WalkingModule.cpp:373: setRobotState gets the measured joints while the kinematics run at the desired ones, Appendix B-18);
     // NULL with the internal plant (measured = desired).  Measured DCM / CoM / ZMP go straight into the chain's state records.
     wcqp::GPtr<const double> q_meas;           // [B][dof], written by wcqp_tick_set_feedback_device
+    // ---- the REACTIVE DCM controller (wcqp_tick_params.dcm_controller, WalkingDCMReactiveController.cpp:63-82) in the MPC's place:
+    // no window, no hull rows, no gains - the reference stage of the tick, its velocity and the measured DCM
+    int reactive;
+    double k_dcm;
+    wcqp::GPtr<const double> dcm_vel;          // [B][traj_len][2] the planner's DCM velocity: uploaded, or the forward difference of ref_traj
 };
 constexpr int kHandLen = 14;
 constexpr int kLoggerCols = 53;
@@ -249,6 +254,61 @@ __device__ __forceinline__ void tick_mpc_issue(const TickDev& d, int j, long ins
     R.ha = *wcqp::at32(reinterpret_cast<const double2*>(d.live_A.get()), (iu * WCQP_HULL_ROWS + jr) * 16u);
     R.hb = *wcqp::at32(d.live_b.get(), (iu * WCQP_HULL_ROWS + jr) * 8u);
 }
+// What follows the DCM controller of tick t on the lane of axis `ax`, whichever controller it is (MPC or reactive): the LIPM reference
+// integrator, the ZMP-CoM law, the synthetic plant, the chain's state record, the hand-off to IK(t) and the u0 log.  rr: the reference
+// DCM of tick t; u: the controller's desired ZMP (the MPC's: the held command on failure); mpc_ok: what the hand-off reports.
+template <bool EXT>
+__device__ __forceinline__ void tick_chain_step(const TickDev& d, int ax, long inst, int t, const TickMpcRegs& R, double rr, double u, bool mpc_ok,
+                                                const unsigned long long* noise_base) {
+    const double c_ref0 = R.s01.x, v_ref_prev = R.s01.y, com = R.s23.x, u_prev = R.s23.y;
+    const double p_star0 = R.s45.x, v_star_prev = R.s45.y, xi = R.s67.x;
+    const double zmp_meas = EXT ? R.s67.y : u_prev;
+    // StableDCMModel::integrateModel (StableDCMModel.cpp:63-90), Tustin integrator
+    const double vr = -d.omega * (c_ref0 - rr);
+    const double c_ref = c_ref0 + 0.5 * d.dT * (vr + v_ref_prev);
+    // WalkingZMPController::evaluateControl (WalkingZMPController.cpp:146-173); the measured ZMP: with the internal plant the
+    // previous command (the same number as u_prev), with external feedback what the caller measured
+    const double v = d.k_com * (c_ref - com) - d.k_zmp * (u - zmp_meas) + vr;
+    const double p_star = p_star0 + 0.5 * d.dT * (v + v_star_prev);
+    // synthetic plant: LIPM with a bounded disturbance
+    const double com1 = com + d.dT * (-d.omega * (com - xi));
+    const double w_ = noise_base ? disturbance_from(*noise_base, t, ax) : disturbance(d.seed, (unsigned long long)(d.first + inst), t, ax);
+    const double xi1 = d.a * xi + d.b * u + d.noise * w_;
+    double2* sp = reinterpret_cast<double2*>(d.mst.get() + (inst * 2 + ax) * 8);
+    sp[0] = make_double2(c_ref, vr); sp[1] = make_double2(com1, u); sp[2] = make_double2(p_star, v); sp[3] = make_double2(xi1, EXT ? u : 0.0);
+    // hand-off to the IK of tick t (desired CoM position / velocity, WalkingModule.cpp:686-695) + the plant state at the start of tick t
+    double* hd = d.hand + ((size_t)(t & 1) * d.batch + inst) * kHandLen;
+    hd[ax] = p_star; hd[2 + ax] = v; hd[4 + ax] = com; hd[6 + ax] = xi;
+    if (ax == 0) hd[8] = mpc_ok ? 1.0 : 0.0;
+    hd[10 + ax] = zmp_meas; hd[12 + ax] = u;
+    if (t < d.log_ticks) d.u0_log[((size_t)t * d.batch + inst) * 2 + ax] = u;
+}
+// ---- the REACTIVE controller in the skewed tick: WalkingDCMReactiveController::evaluateControl (WM/src/WalkingDCMReactiveController.cpp:63-82)
+//     zmp_des = dcm_des - dcm_des_dot / omega - kDCM (dcm_des - dcm_measured)
+// tick_react_issue loads what it reads - the per-axis state record (the chain's, as above), the reference stage of tick t and its
+// velocity, both axes on every lane (one 16-byte load each) - tick_react_law evaluates it on the lane of axis j (j < 2), and
+// tick_chain_step does the rest.
+__device__ __forceinline__ void tick_react_issue(const TickDev& d, int j, long inst, int t, TickMpcRegs& R, double2& r0, double2& rd) {
+    const unsigned iu = (unsigned)inst;
+    const unsigned w0 = (iu * (unsigned)d.traj_len + (unsigned)t) * 16u;
+    R.phase0 = *wcqp::at32(d.phase0.get(), iu * 4u);
+    const double2* sp = reinterpret_cast<const double2*>(wcqp::at32(d.mst.get(), (iu * 2u + (unsigned)(j & 1)) * 64u));
+    R.s01 = sp[0]; R.s23 = sp[1]; R.s45 = sp[2]; R.s67 = sp[3];
+    r0 = *wcqp::at32(reinterpret_cast<const double2*>(d.ref_traj.get()), w0);
+    rd = *wcqp::at32(reinterpret_cast<const double2*>(d.dcm_vel.get()), w0);
+}
+__device__ __forceinline__ double reactive_zmp(const TickDev& d, double r, double rdot, double xi) {
+    return r - rdot / d.omega - d.k_dcm * (r - xi);
+}
+// the law on the lane of axis j & 1 (meaningful on lanes 0 / 1): its record's measured DCM is R.s67.x
+__device__ __forceinline__ double tick_react_law(const TickDev& d, int j, const TickMpcRegs& R, double2 r0, double2 rd) {
+    return (j & 1) ? reactive_zmp(d, r0.y, rd.y, R.s67.x) : reactive_zmp(d, r0.x, rd.x, R.s67.x);
+}
+template <bool EXT = false>
+__device__ __forceinline__ void tick_react_finish(const TickDev& d, int j, long inst, bool live, int t, const TickMpcRegs& R, double2 r0, double u,
+                                                  const unsigned long long* noise_base = nullptr) {
+    if (j < 2 && live) tick_chain_step<EXT>(d, j, inst, t, R, j == 0 ? r0.x : r0.y, u, true, noise_base);
+}
 // tick_mpc_finish = tick_mpc_partial (this lane's share of u0_unc from the loaded window: the window registers die here) +
 // tick_mpc_finish_from (everything else, from the per-axis state records, the hull row and the partial sums)
 template <bool GAINS_LDS = false>
@@ -306,30 +366,9 @@ __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, lo
     const double r_y = wcqp_mpc::row_move<0x111>(r0.y);          // lane 1 <- lane 0 (row_shr:1)
     if (j < 2 && live) {
         const int ax = j;
-        const double c_ref0 = R.s01.x, v_ref_prev = R.s01.y, com = R.s23.x, u_prev = R.s23.y;
-        const double p_star0 = R.s45.x, v_star_prev = R.s45.y, xi = R.s67.x;
-        const double zmp_meas = EXT ? R.s67.y : u_prev;
-        // StableDCMModel::integrateModel (StableDCMModel.cpp:63-90), Tustin integrator
         const double rr = ax == 0 ? r0.x : r_y;        // reference DCM of tick t: stage 0 of the window (lane 0 holds it)
-        const double vr = -d.omega * (c_ref0 - rr);
-        const double c_ref = c_ref0 + 0.5 * d.dT * (vr + v_ref_prev);
-        const double u = mpc_ok ? (ax == 0 ? u0x : u0y) : u_prev;        // hold the last command on failure
-        // WalkingZMPController::evaluateControl (WalkingZMPController.cpp:146-173); the measured ZMP: with the internal plant the
-        // previous command (the same number as u_prev), with external feedback what the caller measured
-        const double v = d.k_com * (c_ref - com) - d.k_zmp * (u - zmp_meas) + vr;
-        const double p_star = p_star0 + 0.5 * d.dT * (v + v_star_prev);
-        // synthetic plant: LIPM with a bounded disturbance
-        const double com1 = com + d.dT * (-d.omega * (com - xi));
-        const double w_ = noise_base ? disturbance_from(*noise_base, t, ax) : disturbance(d.seed, (unsigned long long)(d.first + inst), t, ax);
-        const double xi1 = d.a * xi + d.b * u + d.noise * w_;
-        double2* sp = reinterpret_cast<double2*>(d.mst.get() + (inst * 2 + ax) * 8);
-        sp[0] = make_double2(c_ref, vr); sp[1] = make_double2(com1, u); sp[2] = make_double2(p_star, v); sp[3] = make_double2(xi1, EXT ? u : 0.0);
-        // hand-off to the IK of tick t (desired CoM position / velocity, WalkingModule.cpp:686-695) + the plant state at the start of tick t
-        double* hd = d.hand + ((size_t)(t & 1) * d.batch + inst) * kHandLen;
-        hd[ax] = p_star; hd[2 + ax] = v; hd[4 + ax] = com; hd[6 + ax] = xi;
-        if (ax == 0) hd[8] = mpc_ok ? 1.0 : 0.0;
-        hd[10 + ax] = zmp_meas; hd[12 + ax] = u;
-        if (t < d.log_ticks) d.u0_log[((size_t)t * d.batch + inst) * 2 + ax] = u;
+        const double u = mpc_ok ? (ax == 0 ? u0x : u0y) : R.s23.y;       // hold the last command on failure
+        tick_chain_step<EXT>(d, ax, inst, t, R, rr, u, mpc_ok, noise_base);
     }
 }
 template <bool GAINS_LDS = false, bool EXT = false>
