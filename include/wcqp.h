@@ -501,6 +501,26 @@ typedef struct wcqp_tick_params {
      * wcqp_tick_create returns WCQP_E_INVALID for an unknown controller, and for REACTIVE with a k_dcm that is not finite. */
     int32_t dcm_controller;
     double k_dcm;               /* kDCM of DCM_REACTIVE_CONTROLLER (app/robots/<robot>/dcmReactiveControllerParams.ini:1) */
+    /* ZMP-CoM gain scheduling (0 = off: the fixed gains k_com / k_zmp on every tick).  On (the reference's `useGainScheduling 1`,
+     * app/robots/<robot>/zmpControllerParams.ini, set for all three shipped robots), k_com / k_zmp are the *_walking values and every
+     * tick t, before the ZMP-CoM law, does what WM/src/WalkingModule.cpp:657-662 and WM/src/WalkingZMPController.cpp:29-125 do:
+     *   - stance = sqrt(vx * vx + vy * vy) < 0.001, with (vx, vy) the DCM velocity of tick t: wcqp_tick_inputs.dcm_vel_traj, or (NULL)
+     *     the forward difference of ref_traj - MPC handles then read the velocity too;
+     *   - both gains' smoothers advance one step towards the stance gains (stance) or the walking ones; the gains of tick t are their
+     *     outputs after the step (tick 0 already uses the output after one step);
+     *   - wcqp_tick_upload puts both at rest at the stance gains (WalkingZMPController::initialize); their state carries across
+     *     wcqp_tick_run calls and splices;
+     *   - wcqp_tick_splice_reference on a handle uploaded with an explicit dcm_vel_traj returns WCQP_E_UNSUPPORTED, as with REACTIVE.
+     * The smoother (iCub::ctrl::minJerkTrajGen upstream, which is not part of the reference) is this project's restatement: the
+     * third-order minimum-jerk approximation H(s) = (150/T^3) / (s^3 + (9/T) s^2 + (60/T^2) s + 150/T^3), T = zmp_smoothing_time,
+     * discretised with the bilinear (Tustin) transform at mpc.sampling_time.  Both smoothers are this linear filter of unit DC gain,
+     * both start at rest at the stance gains, so the tick runs ONE filter s(t) of the 0 / 1 walking indicator per robot and uses
+     * k = k_stance + (k_walking - k_stance) s(t).
+     * wcqp_tick_create returns WCQP_E_INVALID with scheduling on when a stance gain is not finite or zmp_smoothing_time is not a
+     * finite number > 0. */
+    int32_t zmp_gain_scheduling;
+    double k_com_stance, k_zmp_stance;   /* kCoM_stance / kZMP_stance of zmpControllerParams.ini                                   */
+    double zmp_smoothing_time;           /* smoothingTime of zmpControllerParams.ini [s]                                           */
 } wcqp_tick_params;
 #define WCQP_TICK_PLANT_INTERNAL 0
 #define WCQP_TICK_PLANT_EXTERNAL 1
@@ -519,7 +539,8 @@ typedef struct wcqp_tick_inputs {   /* HOST pointers, copied at upload */
     const double* q0;           /* [B][dof]                                                    */
     const double* dcm0; const double* com0; const double* u_init;   /* [B][2] each             */
     const double* dcm_vel_traj; /* [B][max_ticks+N+1][2] or NULL: the planner's DCM velocity (WalkingModule.cpp:641-642), read by
-                                 * the REACTIVE controller only (NULL: the forward difference of ref_traj); MPC handles ignore it */
+                                 * the REACTIVE controller and by ZMP gain scheduling (NULL: the forward difference of ref_traj);
+                                 * MPC handles without gain scheduling ignore it */
 } wcqp_tick_inputs;
 
 typedef struct wcqp_tick_outputs {  /* HOST pointers, any may be NULL */
@@ -535,6 +556,8 @@ typedef struct wcqp_tick_outputs {  /* HOST pointers, any may be NULL */
     double* logger;             /* [logger_ticks][B][53] logger rows (wcqp_tick_params.logger_ticks)   */
     uint32_t* active_lower; uint32_t* active_upper;   /* [B] the IK's active joint-velocity bounds of the LAST tick (bit i = joint i):
                                                          what the next tick's hot start begins from                               */
+    double* zmp_gains;          /* [B][2] kCoM, kZMP the last executed tick used (zmp_gain_scheduling; without it k_com, k_zmp;
+                                   after an upload, before any tick: the stance gains)                                            */
 } wcqp_tick_outputs;
 
 typedef struct wcqp_tick_s* wcqp_tick_t;
@@ -582,6 +605,7 @@ typedef struct wcqp_tick_info {
     int32_t ticks_per_launch;   /* effective ticks one launch walks through (1 << 20: all the ticks of a wcqp_tick_run call) */
     int32_t dcm_controller;     /* WCQP_TICK_DCM_*                                                                          */
     int32_t launches_per_tick;  /* kernel launches of a tick that runs alone (the skewed fused kernel: 1)                   */
+    int32_t zmp_gain_scheduling;   /* wcqp_tick_params.zmp_gain_scheduling as taken (0 / 1)                                 */
 } wcqp_tick_info;
 int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
 

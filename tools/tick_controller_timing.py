@@ -3,6 +3,8 @@
 controller side by side, for constant Jacobians and fused kinematics at horizon 50, and the fused reactive tick at horizon 200.
 
     python tools/tick_controller_timing.py [--batch 8192] [--ticks 1000] [--reps 5] [--out profiles/r05_tick_reactive_timing.json]
+    python tools/tick_controller_timing.py --zmp-gain-scheduling [...]     (both controllers, constant Jacobians and fused kinematics at
+        N = 50, each with ZMP gain scheduling - iCubGazeboV2_5's zmpControllerParams.ini - and without, side by side)
 
 Per case: one pipeline of `batch` robots; every repetition re-uploads the inputs, runs `--warmup` ticks, then `--ticks` timed ticks in
 ONE wcqp_tick_run call (device events around it); the median over the repetitions is reported.  The first repetition logs its first
@@ -27,6 +29,10 @@ import walking_controllers_amd as wca  # noqa: E402
 _spec = importlib.util.spec_from_file_location("reactive_tick", os.path.join(ROOT, "tests", "helpers", "reactive_tick.py"))
 rt = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(rt)
+_spec = importlib.util.spec_from_file_location("zmp_gains", os.path.join(ROOT, "tests", "helpers", "zmp_gains.py"))
+zg = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(zg)
+GS = zg.ZMP_SCHEDULE["iCubGazeboV2_5"]       # smoothingTime 0.05, kCoM / kZMP stance 6.0 / 0.9 (walking: 9.0 / 3.0, the TickParams defaults)
 
 K_DCM = 1.2          # iCubGazeboV2_5, app/robots/iCubGazeboV2_5/dcmReactiveControllerParams.ini:1
 CHECK_TICKS = 16
@@ -43,7 +49,7 @@ def make_data(kin_mode, cnt, n, horizon, first, kin):
     return S.synth_tick_batch(cnt, n, first=first, horizon=horizon)
 
 
-def check_sample(kin_mode, ctrl, horizon, B, n, logged, kin):
+def check_sample(kin_mode, ctrl, horizon, B, n, logged, kin, gs=False):
     """the first CHECK_TICKS ticks of robots 0..3 and B-4..B-1 against the CPU restatement"""
     from oracle import qp_spec as qs, tick_spec as ts
     S = wca.synth
@@ -57,7 +63,13 @@ def check_sample(kin_mode, ctrl, horizon, B, n, logged, kin):
     fails = 0
     for f in (0, B - 4):
         one = make_data(kin_mode, 4, n, horizon, f, kin)
-        if ctrl == "reactive":
+        if gs:
+            if ctrl == "reactive":
+                with rt.reactive_solve(p, K_DCM, 4):
+                    ref = zg.run_ticks_scheduled(p, one, CHECK_TICKS, ipar, GS, **kw)
+            else:
+                ref = zg.run_ticks_scheduled(p, one, CHECK_TICKS, ipar, GS, **kw)
+        elif ctrl == "reactive":
             ref = rt.run_ticks_reactive(p, one, CHECK_TICKS, ipar, K_DCM, **kw)
         else:
             ref = ts.run_ticks(p, one, CHECK_TICKS, ipar, **kw)
@@ -68,7 +80,7 @@ def check_sample(kin_mode, ctrl, horizon, B, n, logged, kin):
             "oracle_ik_fail": fails, "ok": bool(eu <= 1e-9 and ed <= 1e-8)}
 
 
-def measure(kin_mode, ctrl, horizon, B, T, W, reps, check):
+def measure(kin_mode, ctrl, horizon, B, T, W, reps, check, gs=False):
     S = wca.synth
     dev = torch.device("cuda", 0)
     kin = wca.KinModel(S.icub_like_model()) if kin_mode else None
@@ -79,6 +91,8 @@ def measure(kin_mode, ctrl, horizon, B, T, W, reps, check):
     else:
         ik = wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=0.5)
     kw = dict(dcm_controller="reactive", k_dcm=K_DCM) if ctrl == "reactive" else {}
+    if gs:
+        kw.update(zmp_gain_scheduling=True, **GS)
     pipe = wca.TickPipeline(B, n, wca.MpcSolver(horizon=horizon), ik, kin=kin, log_ticks=CHECK_TICKS, **kw)
     info = pipe.info()
     stream = torch.cuda.current_stream(dev)
@@ -96,11 +110,11 @@ def measure(kin_mode, ctrl, horizon, B, T, W, reps, check):
         if r == 0:
             out0 = pipe.download()
     res = {"form": "fused_kinematics" if kin_mode else "constant_jacobians", "dcm_controller": ctrl, "horizon": horizon, "batch": B,
-           "timed_ticks": T, "warmup_ticks": W, "reps": reps, "us_per_tick_median": float(np.median(times)),
+           "zmp_gain_scheduling": bool(gs), "timed_ticks": T, "warmup_ticks": W, "reps": reps, "us_per_tick_median": float(np.median(times)),
            "us_per_tick_all": [round(x, 3) for x in times], "info": info,
            "ik_fail_robots": int((out0["ik_fail"] > 0).sum()), "mpc_fail": int(out0["mpc_fail"].sum())}
     if check:
-        res["oracle_check"] = check_sample(kin_mode, ctrl, horizon, B, n, out0, kin)
+        res["oracle_check"] = check_sample(kin_mode, ctrl, horizon, B, n, out0, kin, gs)
     pipe.close()
     return res
 
@@ -113,12 +127,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--zmp-gain-scheduling", action="store_true", help="the scheduled cases and their non-scheduled twins")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     rows = []
-    for form, ctrl, horizon in CASES:
+    cases = [(f, c, h, False) for f, c, h in CASES]
+    if a.zmp_gain_scheduling:
+        cases = [(f, c, 50, gs) for f in ("constant_jacobians", "fused_kinematics") for c in ("mpc", "reactive") for gs in (False, True)]
+    for form, ctrl, horizon, gs in cases:
         t0 = time.time()
-        r = measure(form == "fused_kinematics", ctrl, horizon, a.batch, a.ticks, max(a.warmup, CHECK_TICKS), a.reps, not a.no_check)
+        r = measure(form == "fused_kinematics", ctrl, horizon, a.batch, a.ticks, max(a.warmup, CHECK_TICKS), a.reps, not a.no_check, gs)
         r["wall_s"] = round(time.time() - t0, 1)
         print(json.dumps(r), flush=True)
         rows.append(r)

@@ -166,7 +166,8 @@ class TickParams(C.Structure):
                 ("mpc", MpcParams), ("ik", IkParams),
                 ("ik_cold_start_only", C.c_int32), ("use_kinematics", C.c_int32), ("kin", KinParams), ("foot_rect", C.c_double * 8),
                 ("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("logger_ticks", C.c_int32), ("plant", C.c_int32),
-                ("dcm_controller", C.c_int32), ("k_dcm", C.c_double)]
+                ("dcm_controller", C.c_int32), ("k_dcm", C.c_double),
+                ("zmp_gain_scheduling", C.c_int32), ("k_com_stance", C.c_double), ("k_zmp_stance", C.c_double), ("zmp_smoothing_time", C.c_double)]
 
 
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
@@ -174,7 +175,8 @@ KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1
 
 
 class TickInfo(C.Structure):
-    _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32)]
+    _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32),
+                ("zmp_gain_scheduling", C.c_int32)]
 
 
 class TickInputs(C.Structure):
@@ -184,7 +186,7 @@ class TickInputs(C.Structure):
 
 
 class TickOutputs(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("u0_log", "dq_log", "q_des", "dcm", "com", "mpc_fail", "ik_fail", "hot_try", "hot_hit", "tick", "logger", "active_lower", "active_upper")]
+    _fields_ = [(k, C.c_void_p) for k in ("u0_log", "dq_log", "q_des", "dcm", "com", "mpc_fail", "ik_fail", "hot_try", "hot_hit", "tick", "logger", "active_lower", "active_upper", "zmp_gains")]
 
 
 _lib: Optional[C.CDLL] = None
@@ -450,16 +452,24 @@ class TickPipeline:
                  step_ticks=180, ds_ticks=110, k_com=9.0, k_zmp=3.0, noise=1e-4, seed=99,
                  kin: "Optional[KinModel]" = None, foot_rect=None, ik_hot_start: bool = True, kin_handoff: int = 0,
                  ticks_per_launch: int = 0, logger_ticks: int = 0, external_feedback: bool = False,
-                 dcm_controller: str = "mpc", k_dcm: Optional[float] = None):
+                 dcm_controller: str = "mpc", k_dcm: Optional[float] = None, zmp_gain_scheduling: bool = False,
+                 k_com_stance: Optional[float] = None, k_zmp_stance: Optional[float] = None, zmp_smoothing_time: Optional[float] = None):
         """kin: a KinModel -> per-tick kinematics (Jacobians, actual poses and hull rows rebuilt every tick from the
         integrated joint state with the base anchored at the stance foot; upload() then ignores J_* / hull_tab_*).
         dcm_controller: "mpc" (the DCM-MPC, the reference's use_mpc 1) or "reactive" (WalkingDCMReactiveController, the
-        reference's default use_mpc 0), which needs k_dcm (kDCM of the robot's dcmReactiveControllerParams.ini)."""
+        reference's default use_mpc 0), which needs k_dcm (kDCM of the robot's dcmReactiveControllerParams.ini).
+        zmp_gain_scheduling: the reference's useGainScheduling 1 (zmpControllerParams.ini) - k_com / k_zmp are then the walking gains
+        and k_com_stance, k_zmp_stance and zmp_smoothing_time (kCoM_stance, kZMP_stance, smoothingTime) are needed."""
         if dcm_controller not in ("mpc", "reactive"):
             raise ValueError(f"dcm_controller must be 'mpc' or 'reactive', not {dcm_controller!r}")
         self.reactive = dcm_controller == "reactive"
         if self.reactive and k_dcm is None:
             raise ValueError("the reactive DCM controller needs k_dcm")
+        self.gain_sched = bool(zmp_gain_scheduling)
+        if self.gain_sched and (k_com_stance is None or k_zmp_stance is None or zmp_smoothing_time is None):
+            raise ValueError("ZMP gain scheduling needs k_com_stance, k_zmp_stance and zmp_smoothing_time")
+        if self.gain_sched and not (np.isfinite(k_com_stance) and np.isfinite(k_zmp_stance) and np.isfinite(zmp_smoothing_time) and zmp_smoothing_time > 0):
+            raise ValueError("ZMP gain scheduling needs finite stance gains and a finite zmp_smoothing_time > 0 (wcqp_tick_create: WCQP_E_INVALID)")
         self.batch, self.max_ticks, self.log_ticks, self.dof = batch, max_ticks, log_ticks, ik.dof
         self.logger_ticks = int(logger_ticks)
         self.use_kin = kin is not None
@@ -470,7 +480,9 @@ class TickPipeline:
                                  mpc.params, ik.params, int(not ik_hot_start), int(self.use_kin), kin.params if kin is not None else KinParams(),
                                  (C.c_double * 8)(*np.asarray(foot_rect, float).reshape(8)), int(kin_handoff), int(ticks_per_launch), int(logger_ticks),
                                  int(bool(external_feedback)), TICK_DCM_REACTIVE if self.reactive else TICK_DCM_MPC,
-                                 float(k_dcm) if k_dcm is not None else 0.0)
+                                 float(k_dcm) if k_dcm is not None else 0.0, int(self.gain_sched),
+                                 float(k_com_stance) if self.gain_sched else 0.0, float(k_zmp_stance) if self.gain_sched else 0.0,
+                                 float(zmp_smoothing_time) if self.gain_sched else 0.0)
         self._h = C.c_void_p()
         check(lib().wcqp_tick_create(C.byref(self.params), C.byref(self._h)), "wcqp_tick_create")
         self._keep = None
@@ -487,8 +499,9 @@ class TickPipeline:
             pass
 
     def upload(self, data: dict, dcm_vel_traj=None):
-        """dcm_vel_traj: [B][max_ticks + N + 1][2], the planner's DCM velocity for the reactive controller (None: the forward
-        difference of ref_traj); MPC handles ignore it.  A reactive handle takes data without hull tables."""
+        """dcm_vel_traj: [B][max_ticks + N + 1][2], the planner's DCM velocity for the reactive controller and for ZMP gain scheduling
+        (None: the forward difference of ref_traj); MPC handles without scheduling ignore it.  A reactive handle takes data without hull
+        tables."""
         f64 = ("ref_traj", "state0", "swing_twist", "q0", "dcm0", "com0", "u_init")
         f64 += () if self.use_kin else ("J_left", "J_right", "J_neck", "J_com")
         if not self.use_kin and (not self.reactive or "hull_tab_A" in data):
@@ -506,13 +519,13 @@ class TickPipeline:
 
     def info(self) -> dict:
         """The form the handle took (wcqp_tick_get_info): kin_handoff ("fused", "compact", "dense" or None without kinematics),
-        ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick."""
+        ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick, zmp_gain_scheduling (bool)."""
         i = TickInfo()
         check(lib().wcqp_tick_get_info(self._h, C.byref(i)), "wcqp_tick_get_info")
         return dict(kin_handoff={KIN_HANDOFF_NONE: None, KIN_HANDOFF_FUSED: "fused", KIN_HANDOFF_DENSE: "dense",
                                  KIN_HANDOFF_COMPACT: "compact"}[i.kin_handoff],
                     ticks_per_launch=int(i.ticks_per_launch), dcm_controller="reactive" if i.dcm_controller == TICK_DCM_REACTIVE else "mpc",
-                    launches_per_tick=int(i.launches_per_tick))
+                    launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling))
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")
@@ -541,7 +554,7 @@ class TickPipeline:
         o = dict(u0_log=np.zeros((L, B, 2)), dq_log=np.zeros((L, B, D)), q_des=np.zeros((B, D)), dcm=np.zeros((B, 2)),
                  com=np.zeros((B, 2)), mpc_fail=np.zeros(B, np.int64), ik_fail=np.zeros(B, np.int64),
                  hot_try=np.zeros(B, np.int64), hot_hit=np.zeros(B, np.int64), tick=np.zeros(1, np.int32),
-                 active_lower=np.zeros(B, np.uint32), active_upper=np.zeros(B, np.uint32))
+                 active_lower=np.zeros(B, np.uint32), active_upper=np.zeros(B, np.uint32), zmp_gains=np.zeros((B, 2)))
         if self.logger_ticks > 0:
             o["logger"] = np.zeros((self.logger_ticks, B, 53))
         outs = TickOutputs(**{k: (o[k].ctypes.data if k in o else None) for k, _ in TickOutputs._fields_})
@@ -551,12 +564,12 @@ class TickPipeline:
 
 
 def source_hash() -> str:
-    """sha256 over the kernel sources (csrc/*.hip, *.h, *.cpp): what a measurement that is kept in the repository
+    """sha256 over the kernel sources (csrc/*.hip, *.h, *.inc, *.cpp): what a measurement that is kept in the repository
     (profiles/traffic.json) is stamped with, so that it is not quoted for kernels that have changed since."""
     import glob
     import hashlib
     h = hashlib.sha256()
-    files = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + glob.glob(os.path.join(_HERE, "csrc", "*.h")) +
+    files = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + glob.glob(os.path.join(_HERE, "csrc", "*.h")) + glob.glob(os.path.join(_HERE, "csrc", "*.inc")) +
                    glob.glob(os.path.join(_HERE, "csrc", "*.cpp")))
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

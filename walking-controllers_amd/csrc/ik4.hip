@@ -40,6 +40,11 @@
 #include "tick_device.h"
 #include "kin_device.h"
 
+// ik4_reactive.hip / ik4_zmp_gs.hip: this file compiled for the tick kernels of the reactive controller / of ZMP gain scheduling only
+#if defined(WCQP_IK4_REACTIVE_TU) || defined(WCQP_IK4_GS_TU)
+#define WCQP_IK4_TICK_TU 1
+#endif
+
 namespace {
 
 using namespace wcqp_ik;
@@ -166,7 +171,9 @@ struct MpcPairArgs {
 // cost the fused-kinematics kernel 28 B of scratch, which the product kernel does not pay
 // REACT (tick kernel, wcqp_tick_params.dcm_controller = REACTIVE): the chain of tick t + 1 runs the reactive DCM controller
 // (tick_device.h: tick_react_*) in the MPC's place - ik4_tick_reactive_kernel
-template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false, bool REACT = false>
+// GS (tick kernel, wcqp_tick_params.zmp_gain_scheduling): the chain of tick t + 1 advances the robot's gain smoother (tick_device.h:
+// zmp_*) and runs the ZMP-CoM law with the gains of that tick - ik4_tick_gs_kernel; td is then a TickDevGS
+template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false, bool REACT = false, bool GS = false>
 __device__ __forceinline__
 void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 const double* __restrict__ JL, const double* __restrict__ JR,
@@ -180,6 +187,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
 {
     static_assert(!(TICK && PAIR), "the tick kernel carries its own MPC chain");
     static_assert(TICK || !REACT, "the reactive controller is a tick form");
+    static_assert(TICK || !GS, "gain scheduling is a tick form");
     constexpr bool COMPACT = JSRC == 1;
     constexpr bool KINF = JSRC == 2;
     int lane_id = threadIdx.x;
@@ -255,6 +263,18 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     double2 m_r0 = make_double2(0.0, 0.0);
     double2 m_rd = make_double2(0.0, 0.0); // REACT: the reference DCM velocity of tick t + 1 (m_r0: its reference DCM)
     if constexpr (TICK && REACT) { if (do_mpc) wcqp_tick::tick_react_issue(td, j, inst, tick_now + 1, mreg, m_r0, m_rd); else mreg.phase0 = td.phase0[inst]; }
+    // GS: the robot's smoother state and (MPC; the reactive issue has it) the velocity stage of tick t + 1, behind the chain's other loads
+    // and in front of the Jacobians'; consumed at the latest possible point - with fused kinematics before the kinematics phase, where
+    // only the smoother's output m_s waits across it
+    wcqp_tick::ZmpRegs zreg{};
+    double m_s = 0.0;
+    auto gsd = [&]() -> const wcqp_tick::TickDevGS& { return static_cast<const wcqp_tick::TickDevGS&>(td); };
+    if constexpr (TICK && GS) {
+        if (do_mpc) {
+            wcqp_tick::zmp_state_issue(gsd(), inst, zreg);
+            if constexpr (!REACT) m_rd = wcqp_tick::zmp_vel_issue(td, inst, tick_now + 1);
+        }
+    }
     {
         // the state block first: vmcnt retires in order, and the rhs phase only needs the state, so the 36
         // Jacobian loads stay in flight underneath it
@@ -303,6 +323,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
             // of u0_unc now (its loads were issued first: they have landed when the pose block below has) and its per-axis records
             // and hull row wait in LDS; the pose block is re-read behind the kinematics (L2) instead of being held
             if (do_mpc) {
+                if constexpr (GS) m_s = wcqp_tick::zmp_smoother_advance(gsd(), inst, j == 0 && live, m_rd, zreg);
                 if constexpr (REACT) {
                     m_ux = wcqp_tick::tick_react_law(td, j, mreg, m_r0, m_rd);       // (the reactive law needs nothing else: its output is all that waits)
                 } else {
@@ -630,17 +651,25 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
         }
         if constexpr (TICK) {
             // MPC(t+1), ZMP-CoM law and plant of tick t + 1 for the same four robots, while the Jacobians are on their way
+            // GS: setPhase of tick t + 1 (WalkingModule.cpp:657-662) ahead of the law - with fused kinematics done before the kinematics phase
+            double2 kg = make_double2(0.0, 0.0);
+            if constexpr (GS) {
+                if (do_mpc) {
+                    if constexpr (!KINF) m_s = wcqp_tick::zmp_smoother_advance(gsd(), inst, j == 0 && live, m_rd, zreg);
+                    kg = wcqp_tick::zmp_gains_at(td, gsd().zg, m_s);
+                }
+            }
             if constexpr (REACT) {
                 if (do_mpc) {
                     if constexpr (!KINF) m_ux = wcqp_tick::tick_react_law(td, j, mreg, m_r0, m_rd);
-                    wcqp_tick::tick_react_finish<EXT>(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, noise_base);
+                    wcqp_tick::tick_react_finish<EXT, GS>(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, noise_base, kg);
                 }
             } else if (do_mpc) {
                 // (hull rows in the MPC stash's place, just read back: the attached frames at 312..347 are still needed)
                 const int cyc1 = *gait + 1 == 2 * td.step_ticks ? 0 : *gait + 1;
                 const int code1 = wcqp_tick::contact_code_cyc(cyc1, td.step_ticks, td.ds_ticks);
-                if constexpr (KINF) wcqp_tick::tick_mpc_finish_from(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, m_uy, reinterpret_cast<double (*)[4]>(S + K_MS), code1, noise_base);
-                else wcqp_tick::tick_mpc_finish(td, j, inst, live, tick_now + 1, mreg, reinterpret_cast<double (*)[4]>(S + OFF_COL), nullptr, code1, noise_base);
+                if constexpr (KINF) wcqp_tick::tick_mpc_finish_from<false, GS>(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, m_uy, reinterpret_cast<double (*)[4]>(S + K_MS), code1, noise_base, kg);
+                else wcqp_tick::tick_mpc_finish<false, false, GS>(td, j, inst, live, tick_now + 1, mreg, reinterpret_cast<double (*)[4]>(S + OFF_COL), nullptr, code1, noise_base, kg);
             }
             if (j < 6) {
                 const int code = wcqp_tick::contact_code_cyc(*gait, td.step_ticks, td.ds_ticks);
@@ -1623,7 +1652,7 @@ __device__ __forceinline__ int xcd_group(int b, int groups) {
 // kmodel / kgains: the LDS the kernel declares for the kinematic model and (MPC, fused kinematics) the MPC's gain blocks.
 // (No __restrict__ on these parameters: the kernel's own carry it, and repeating it here changes the MPC kernels' code - their
 // SGPR spills grow by 10 to 18.)
-template <int JSRC, bool LOG, bool EXT, bool REACT>
+template <int JSRC, bool LOG, bool EXT, bool REACT, bool GS = false>
 __device__ __forceinline__
 void ik4_tick_walk(const IkDeviceParams* prm, int batch,
                    const double* JL, const double* JR,
@@ -1662,7 +1691,7 @@ void ik4_tick_walk(const IkDeviceParams* prm, int batch,
 #pragma unroll 1
         for (int k = 0; k < n_inner; ++k) {
             __asm__ volatile("" ::: "memory");        // nothing of the body is hoisted out of the loop (its registers are all spoken for)
-            ik4_body<true, JSRC, false, LOG, EXT, REACT>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out, td, smem,
+            ik4_body<true, JSRC, false, LOG, EXT, REACT, GS>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out, td, smem,
                                              (int)blockIdx.x, t0 + k, !(skip_last_mpc && k == n_inner - 1), kmodel, kgains, nullptr, carry, &gait, &nbase);
             gait = gait + 1 == 2 * td.step_ticks ? 0 : gait + 1;
             // tick t + 1 of this wave reads what tick t wrote (other lanes of the same wave): visible before it starts
@@ -1682,7 +1711,7 @@ void ik4_tick_walk(const IkDeviceParams* prm, int batch,
     }
 }
 
-#ifndef WCQP_IK4_REACTIVE_TU
+#ifndef WCQP_IK4_TICK_TU
 template <bool TICK, int JSRC, bool LOG = false, bool EXT = false>
 __global__ __launch_bounds__(64, WCQP_IK4_WAVES)
 void ik4_kernel(const IkDeviceParams* __restrict__ prm, int batch,
@@ -1704,7 +1733,7 @@ void ik4_kernel(const IkDeviceParams* __restrict__ prm, int batch,
     }
 }
 
-#else
+#elif defined(WCQP_IK4_REACTIVE_TU)
 // The tick kernel with the REACTIVE DCM controller (wcqp_tick_params.dcm_controller): the walk of ik4_kernel<true, JSRC, LOG, EXT>, the
 // chain of tick t + 1 the closed-form law instead of the MPC - no gain blocks in LDS (with fused kinematics at any horizon), no hull rows
 template <int JSRC, bool LOG = false, bool EXT = false>
@@ -1722,9 +1751,28 @@ void ik4_tick_reactive_kernel(const IkDeviceParams* __restrict__ prm, int batch,
     ik4_tick_walk<JSRC, LOG, EXT, true>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out,
                                         tdp, phase, n_inner, skip_last_mpc, smem, kmodel, nullptr);
 }
+#else
+// The tick kernels with ZMP-CoM gain scheduling (wcqp_tick_params.zmp_gain_scheduling), either controller: the walk of
+// ik4_kernel<true, JSRC, LOG, EXT> / ik4_tick_reactive_kernel<JSRC, LOG, EXT> with the smoother advanced in the chain of every tick
+template <int JSRC, bool LOG, bool EXT, bool REACT>
+__global__ __launch_bounds__(64, WCQP_IK4_WAVES)
+void ik4_tick_gs_kernel(const IkDeviceParams* __restrict__ prm, int batch,
+                        const double* __restrict__ JL, const double* __restrict__ JR,
+                        const double* __restrict__ JN, const double* __restrict__ JC,
+                        const double* qpos, const double* __restrict__ state,
+                        double* __restrict__ dq_out, int* __restrict__ status_out,
+                        unsigned* __restrict__ alo_out, unsigned* __restrict__ aup_out,
+                        double* __restrict__ ferr_out, int* __restrict__ iters_out, const wcqp_tick::TickDev* __restrict__ tdp, int phase, int n_inner, int skip_last_mpc)
+{
+    __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
+    __shared__ __attribute__((aligned(16))) double kmodel[JSRC == 2 ? wcqp_tick::kKinTabSize : 2];
+    __shared__ __attribute__((aligned(16))) double kgains[JSRC == 2 && !REACT ? 4 * wcqp_tick::kGainsLdsStages : 2];
+    ik4_tick_walk<JSRC, LOG, EXT, REACT, true>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out,
+                                               tdp, phase, n_inner, skip_last_mpc, smem, kmodel, REACT ? nullptr : kgains);
+}
 #endif
 
-#ifndef WCQP_IK4_REACTIVE_TU
+#ifndef WCQP_IK4_TICK_TU
 // The MPC chain of ONE tick for every robot, on its own: primes the skewed tick after an upload (MPC(0) has to have run
 // before the first fused launch, which carries IK(0) and MPC(1)).
 template <bool EXT>
@@ -1740,7 +1788,7 @@ void tick_mpc_prime_kernel(wcqp_tick::TickDev td, int t)
     wcqp_tick::tick_mpc_issue(td, j, inst, t, mreg);
     wcqp_tick::tick_mpc_finish<false, EXT>(td, j, inst, live, t, mreg, s_hull[grp]);
 }
-#else
+#elif defined(WCQP_IK4_REACTIVE_TU)
 // The chain of one tick with the reactive controller for every robot, on its own (primes ik4_tick_reactive_kernel)
 template <bool EXT>
 __global__ __launch_bounds__(64)
@@ -1755,9 +1803,31 @@ void tick_reactive_prime_kernel(wcqp_tick::TickDev td, int t)
     wcqp_tick::tick_react_issue(td, j, inst, t, mreg, r0, rd);
     wcqp_tick::tick_react_finish<EXT>(td, j, inst, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd));
 }
+#else
+// The chain of one tick with gain scheduling for every robot, on its own (primes ik4_tick_gs_kernel): the smoother state and the velocity
+// stage loaded with the chain's other loads, setPhase, then the controller's finish with the tick's gains
+template <bool EXT, bool REACT>
+__global__ __launch_bounds__(64)
+void tick_gs_prime_kernel(wcqp_tick::TickDevGS td, int t)
+{
+    __shared__ __attribute__((aligned(16))) double s_hull[4][WCQP_HULL_ROWS][4];
+    const int lane = threadIdx.x, grp = lane >> 4, j = lane & 15;
+    const long inst_raw = (long)blockIdx.x * 4 + grp;
+    const bool live = inst_raw < td.batch;
+    const long inst = live ? inst_raw : (long)td.batch - 1;
+    wcqp_tick::TickMpcRegs mreg;
+    wcqp_tick::ZmpRegs zreg;
+    double2 r0, rd;
+    if constexpr (REACT) wcqp_tick::tick_react_issue(td, j, inst, t, mreg, r0, rd);
+    else { wcqp_tick::tick_mpc_issue(td, j, inst, t, mreg); rd = wcqp_tick::zmp_vel_issue(td, inst, t); }
+    wcqp_tick::zmp_state_issue(td, inst, zreg);
+    const double2 kg = wcqp_tick::zmp_gains_at(td, td.zg, wcqp_tick::zmp_smoother_advance(td, inst, j == 0 && live, rd, zreg));
+    if constexpr (REACT) wcqp_tick::tick_react_finish<EXT, true>(td, j, inst, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd), nullptr, kg);
+    else wcqp_tick::tick_mpc_finish<false, EXT, true>(td, j, inst, live, t, mreg, s_hull[grp], nullptr, -1, nullptr, kg);
+}
 #endif
 
-#ifndef WCQP_IK4_REACTIVE_TU
+#ifndef WCQP_IK4_TICK_TU
 
 // Both QPs of a batch of robot-ticks in ONE launch (wcqp_qp_enqueue_steps, a record whose two calls go to the same
 // stream): workgroups 0 .. ik_blocks-1 are the IK kernel above, the rest the DCM-MPC kernel of mpc.hip (same device
@@ -1905,12 +1975,12 @@ void ik_plan_kernel(const IkDeviceParams* __restrict__ prm, int batch, const wcq
     __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
     plan_walk<false>(prm, batch, recs, n_steps, ways, groups, c, queue, smem);
 }
-#endif  // WCQP_IK4_REACTIVE_TU
+#endif  // WCQP_IK4_TICK_TU
 
 }  // namespace
 
 namespace wcqp_ik {
-#ifndef WCQP_IK4_REACTIVE_TU
+#ifndef WCQP_IK4_TICK_TU
 
 int ik4_plan_queue_grid(int batch, int n_steps) {
     int dev = 0, cus = 0;
@@ -1961,19 +2031,33 @@ int ik4_launch(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipStream
 
 // the tick kernel of this translation unit's controller: ik4_kernel<true, ...> (the MPC) ...
 template <int JSRC, bool LOG = false, bool EXT = false>
-static void tick_kernel_launch(const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
+static void tick_kernel_launch(bool /*react*/, const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
                                int n_inner, int skip_last_mpc, hipStream_t stream) {
     ik4_launch_as<true, JSRC, LOG, EXT>(prm, batch, io, td_dev, phase, n_inner, skip_last_mpc, stream);
 }
-#else
+#elif defined(WCQP_IK4_REACTIVE_TU)
 // ... or ik4_tick_reactive_kernel (ik4_reactive.hip: the reactive controller's kernels are a code object of their own, so that adding
 // them moves none of the kernels above - their addresses included)
 template <int JSRC, bool LOG = false, bool EXT = false>
-static void tick_kernel_launch(const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
+static void tick_kernel_launch(bool /*react*/, const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
                                int n_inner, int skip_last_mpc, hipStream_t stream) {
     hipLaunchKernelGGL((ik4_tick_reactive_kernel<JSRC, LOG, EXT>), dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, stream, prm, batch,
                        io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters,
                        td_dev, phase, n_inner, skip_last_mpc);
+}
+#else
+// ... or ik4_tick_gs_kernel of either controller (ik4_zmp_gs.hip: a code object of its own for the same reason)
+template <int JSRC, bool LOG = false, bool EXT = false>
+static void tick_kernel_launch(bool react, const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
+                               int n_inner, int skip_last_mpc, hipStream_t stream) {
+    if (react)
+        hipLaunchKernelGGL((ik4_tick_gs_kernel<JSRC, LOG, EXT, true>), dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, stream, prm, batch,
+                           io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters,
+                           td_dev, phase, n_inner, skip_last_mpc);
+    else
+        hipLaunchKernelGGL((ik4_tick_gs_kernel<JSRC, LOG, EXT, false>), dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, stream, prm, batch,
+                           io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters,
+                           td_dev, phase, n_inner, skip_last_mpc);
 }
 #endif
 
@@ -1984,24 +2068,24 @@ static int ik4_launch_tick_forms(const IkDeviceParams* prm, const wcqp_tick::Tic
     if (td.logger_ticks > 0) {
         // the logging kernels (a debugging aid like the reference's dumpData): dense Jacobians also produce the foot errors
         if (!td.log_rows) return WCQP_E_INVALID;
-        if (td.kin_fused) tick_kernel_launch<2, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else if (td.compact) tick_kernel_launch<1, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else tick_kernel_launch<0, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        if (td.kin_fused) tick_kernel_launch<2, true>(td.reactive, prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else if (td.compact) tick_kernel_launch<1, true>(td.reactive, prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else tick_kernel_launch<0, true>(td.reactive, prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
     } else if (td.q_meas) {
         // external feedback (wcqp_tick_params.plant = EXTERNAL): measured joints in the IK's regularisation; one tick per launch
         if (n_inner != 1 || td.compact) return WCQP_E_INVALID;
-        if (td.kin_fused) tick_kernel_launch<2, false, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else tick_kernel_launch<0, false, true>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        if (td.kin_fused) tick_kernel_launch<2, false, true>(td.reactive, prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else tick_kernel_launch<0, false, true>(td.reactive, prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
     } else {
-        if (td.kin_fused) tick_kernel_launch<2>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else if (td.compact) tick_kernel_launch<1>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
-        else tick_kernel_launch<0>(prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        if (td.kin_fused) tick_kernel_launch<2>(td.reactive, prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else if (td.compact) tick_kernel_launch<1>(td.reactive, prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
+        else tick_kernel_launch<0>(td.reactive, prm, B, io, td_dev, ph, n_inner, skip_last_mpc, stream);
     }
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
 
-#ifndef WCQP_IK4_REACTIVE_TU
+#ifndef WCQP_IK4_TICK_TU
 int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
                     int n_inner, int skip_last_mpc, hipStream_t stream) {
     if (n_inner < 1) return WCQP_E_INVALID;       // (whether a handle may run several ticks per launch is decided at wcqp_tick_create)
@@ -2009,8 +2093,9 @@ int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_
     if (td.compact && (!td.jcomp || td.cstride < 1)) return WCQP_E_INVALID;
     // (the MPC's gain blocks sit in LDS beside the model: a horizon limit the reactive controller, which reads no gains, does not have)
     if (td.kin_fused && (!td.kin_tab || !td.kin_mode || td.kin_rounds < 0 || td.kin_rounds > 3 || (!td.reactive && td.horizon >= wcqp_tick::kGainsLdsStages))) return WCQP_E_INVALID;
-    if (td.reactive && !td.dcm_vel) return WCQP_E_INVALID;
+    if ((td.reactive || td.gain_sched) && !td.dcm_vel) return WCQP_E_INVALID;
     const IkDeviceParams* prm = static_cast<const IkDeviceParams*>(d_prm);
+    if (td.gain_sched) return ik4_launch_tick_gs(prm, td, td_dev, io, n_inner, skip_last_mpc, stream);
     return td.reactive ? ik4_launch_tick_reactive(prm, td, td_dev, io, n_inner, skip_last_mpc, stream)
                        : ik4_launch_tick_forms(prm, td, td_dev, io, n_inner, skip_last_mpc, stream);
 }
@@ -2025,7 +2110,7 @@ int ik4_launch_tick_prime(const wcqp_tick::TickDev& td, int t, hipStream_t strea
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
-#else
+#elif defined(WCQP_IK4_REACTIVE_TU)
 int ik4_launch_tick_reactive(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
                              int n_inner, int skip_last_mpc, hipStream_t stream) {
     return ik4_launch_tick_forms(prm, td, td_dev, io, n_inner, skip_last_mpc, stream);
@@ -2037,6 +2122,26 @@ int ik4_launch_tick_prime_reactive(const wcqp_tick::TickDev& td, int t, hipStrea
     const unsigned grid = (unsigned)((td.batch + 3) / 4);
     if (td.q_meas) hipLaunchKernelGGL(tick_reactive_prime_kernel<true>, dim3(grid), dim3(64), 0, stream, td, t);
     else hipLaunchKernelGGL(tick_reactive_prime_kernel<false>, dim3(grid), dim3(64), 0, stream, td, t);
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+#else
+int ik4_launch_tick_gs(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                       int n_inner, int skip_last_mpc, hipStream_t stream) {
+    return ik4_launch_tick_forms(prm, td, td_dev, io, n_inner, skip_last_mpc, stream);
+}
+
+// the scheduled chain of tick t alone (see tick_gs_prime_kernel)
+int ik4_launch_tick_prime_gs(const wcqp_tick::TickDevGS& td, int t, hipStream_t stream) {
+    if (!td.skew || !td.mst || !td.hand || !td.gain_sched || !td.dcm_vel || !td.zg.zs) return WCQP_E_INVALID;
+    const unsigned grid = (unsigned)((td.batch + 3) / 4);
+    if (td.reactive) {
+        if (td.q_meas) hipLaunchKernelGGL((tick_gs_prime_kernel<true, true>), dim3(grid), dim3(64), 0, stream, td, t);
+        else hipLaunchKernelGGL((tick_gs_prime_kernel<false, true>), dim3(grid), dim3(64), 0, stream, td, t);
+    } else {
+        if (td.q_meas) hipLaunchKernelGGL((tick_gs_prime_kernel<true, false>), dim3(grid), dim3(64), 0, stream, td, t);
+        else hipLaunchKernelGGL((tick_gs_prime_kernel<false, false>), dim3(grid), dim3(64), 0, stream, td, t);
+    }
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }

@@ -6,6 +6,7 @@
 //   src/WalkingModule.cpp:578-597   StableDCMModel::integrateModel        -> tick_glue_kernel (consumer)
 //   src/WalkingModule.cpp:604-636   MPC bracket                           -> mpc_condensed_kernel
 //   src/WalkingModule.cpp:638-656   reactive DCM controller (use_mpc 0)   -> tick_reactive_kernel (in-order forms), tick_react_* (skewed)
+//   src/WalkingModule.cpp:657-662   ZMP gain scheduling (setPhase)        -> zmp_* (tick_device.h; zmp_gain_scheduling)
 //   src/WalkingModule.cpp:657-695   WalkingZMPController + desired CoM    -> tick_glue_kernel
 //   src/WalkingModule.cpp:709-740   IK bracket                            -> ik_kernel
 //   src/WalkingModule.cpp:741-744   velocity integration                  -> tick_post_kernel
@@ -23,7 +24,9 @@ namespace {
 
 using namespace wcqp_tick;
 
-__global__ void tick_glue_kernel(TickDev d) {
+// GS (zmp_gain_scheduling): setPhase of the tick first - one step of the robot's gain smoother - and the law with its gains; d is a TickDevGS
+template <bool GS>
+__device__ __forceinline__ void tick_glue_robot(const TickDev& d) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d.batch) return;
     const int t = d.tick2[d.phase];
@@ -31,15 +34,19 @@ __global__ void tick_glue_kernel(TickDev d) {
     const int st = d.mpc_status[i];
     const bool ok = st == WCQP_STATUS_SOLVED || st == WCQP_STATUS_OUTSIDE_HULL;
     if (!ok) d.mpc_fail[i] += 1;
+    double2 kg = make_double2(0.0, 0.0);
+    if constexpr (GS) kg = zmp_gains_tick(static_cast<const TickDevGS&>(d), i, t, true);
     double* s = d.state + (size_t)i * kStateLen;
     for (int ax = 0; ax < 2; ++ax) {
         double g_com;
-        tick_glue_axis(d, i, t, ax, ok, d.u0[2 * i + ax], g_com, s[69 + ax], s[72 + ax]);
+        tick_glue_axis<GS>(d, i, t, ax, ok, d.u0[2 * i + ax], g_com, s[69 + ax], s[72 + ax], kg);
         if (!d.kin_mode) s[66 + ax] = g_com;
     }
     tick_glue_height(d, i, s);
     for (int k = 0; k < 6; ++k) tick_glue_twist(d, i, code, k, t, s[75 + k], s[81 + k]);
 }
+__global__ void tick_glue_kernel(TickDev d) { tick_glue_robot<false>(d); }
+__global__ void tick_glue_gs_kernel(TickDevGS d) { tick_glue_robot<true>(d); }
 
 __global__ void tick_post_kernel(TickDev d) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,8 +70,8 @@ __global__ void tick_reactive_kernel(TickDev d) {
     if (ax == 0) d.mpc_status[i] = WCQP_STATUS_SOLVED;
 }
 
-// the forward difference (ref[s + 1] - ref[s]) / dT of the stages [from, to) of every robot's reference: the reactive controller's DCM
-// velocity when none was uploaded, kept in step with wcqp_tick_splice_reference (stream order, behind the strided copy)
+// the forward difference (ref[s + 1] - ref[s]) / dT of the stages [from, to) of every robot's reference: the DCM velocity of the
+// reactive controller and of gain scheduling when none was uploaded, kept in step with wcqp_tick_splice_reference (stream order, behind the strided copy)
 __global__ void tick_vel_diff_kernel(TickDev d, int from, int to) {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int n = to - from;
@@ -90,6 +97,26 @@ __global__ void tick_feedback_kernel(TickDev d, const double* __restrict__ dcm, 
 }
 
 }  // namespace
+
+namespace wcqp {
+// The gain smoother of zmp_gain_scheduling (include/wcqp.h): the third-order minimum-jerk approximation
+//     H(s) = w / (s^3 + a2 s^2 + a1 s + w),   w = 150 / T^3, a2 = 9 / T, a1 = 60 / T^2   (unit DC gain),
+// discretised with the bilinear (Tustin) transform s = K (1 - z^-1) / (1 + z^-1), K = 2 / dT.  The reference's smoother,
+// iCub::ctrl::minJerkTrajGen, is upstream code outside the reference: this is the project's restatement, and the one place that
+// defines it.  y[n] = sum_k nb[k] u[n - k] - sum_k na[k] y[n - 1 - k].
+void zmp_smoother_coeffs(double T, double dT, double nb[4], double na[3]) {
+    const double K = 2.0 / dT, K2 = K * K, K3 = K2 * K;
+    const double a2 = 9.0 / T, a1 = 60.0 / (T * T), w = 150.0 / (T * T * T);
+    // denominator K^3 (1 - z)^3 + a2 K^2 (1 - z)^2 (1 + z) + a1 K (1 - z)(1 + z)^2 + w (1 + z)^3, numerator w (1 + z)^3 (z = z^-1)
+    const double d0 = K3 + a2 * K2 + a1 * K + w;
+    const double d1 = -3.0 * K3 - a2 * K2 + a1 * K + 3.0 * w;
+    const double d2 = 3.0 * K3 - a2 * K2 - a1 * K + 3.0 * w;
+    const double d3 = -K3 + a2 * K2 - a1 * K + w;
+    const double g = w / d0;
+    nb[0] = g; nb[1] = 3.0 * g; nb[2] = 3.0 * g; nb[3] = g;
+    na[0] = d1 / d0; na[1] = d2 / d0; na[2] = d3 / d0;
+}
+}  // namespace wcqp
 
 // how a tick is launched: the skewed base-eliminated kernel (ONE launch), MPC + the 16-lane kernel with glue and post fused in
 // (two), or MPC, glue, IK and post (four; any other IK kernel, and what the fused forms are tested against)
@@ -125,6 +152,9 @@ struct wcqp_tick_s {
     bool external = false, feedback_set = false;     // wcqp_tick_params.plant = EXTERNAL: one tick per run call, each behind a set_feedback
     double* q_meas = nullptr;
     double* fb_stage = nullptr;   // wcqp_tick_set_feedback_host: [B][2 + 2 + 2 + dof]
+    ZmpSched zg{};                // zmp_gain_scheduling (d.gain_sched): the stance gains, the smoother, its per-robot state
+    // the handle's TickDev with the scheduling record behind it (what the scheduled kernels take)
+    TickDevGS dgs(const TickDev& base) const { TickDevGS g; static_cast<TickDev&>(g) = base; g.zg = zg; return g; }
 };
 
 namespace {
@@ -141,6 +171,13 @@ int dev_alloc(wcqp_tick_s* h, T** out, size_t count) {
 
 template <typename T>
 int dev_alloc(wcqp_tick_s* h, wcqp::GPtr<T>* out, size_t count) { return dev_alloc(h, &out->p, count); }
+
+// zmp_gains_at (tick_device.h) on the host, operation for operation
+void zmp_gains_host(const TickDev& d, const ZmpSched& z, double s, double* kg) {
+#pragma clang fp contract(off)
+    kg[0] = z.k_com_st + (d.k_com - z.k_com_st) * s;
+    kg[1] = z.k_zmp_st + (d.k_zmp - z.k_zmp_st) * s;
+}
 
 // one launch sequence of n_inner ticks (n_inner <= ticks_per_launch, which is 1 unless the handle may run several) with
 // the given phase (which copy of the tick index it reads: see TickDev::tick2)
@@ -160,6 +197,7 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
     // base-eliminated IK kernel: IK + post step of this tick and MPC + glue + plant of the NEXT one in ONE launch (skewed tick)
     if (h->form == TickForm::SKEWED)
         return wcqp_ik::ik4_launch_tick(wcqp::ik_device_params(h->ik), d, h->d_dev, io, n_inner, skip_last_mpc, s);
+    const bool gs = d.gain_sched != 0;
     if (d.reactive) {
         hipLaunchKernelGGL(tick_reactive_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, s, d);
     } else {
@@ -168,8 +206,10 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
                                          d.u0, d.mpc_status, h->mpc_active, h->mpc_margin, s);
         if (rc != WCQP_OK) return rc;
     }
-    if (h->form == TickForm::MPC_IK16) return wcqp_ik::ik3_launch_tick(wcqp::ik_device_params(h->ik), d, io, s);
-    hipLaunchKernelGGL(tick_glue_kernel, dim3((B + 127) / 128), dim3(128), 0, s, d);
+    if (h->form == TickForm::MPC_IK16)
+        return gs ? wcqp_ik::ik3_launch_tick_gs(wcqp::ik_device_params(h->ik), h->dgs(d), io, s) : wcqp_ik::ik3_launch_tick(wcqp::ik_device_params(h->ik), d, io, s);
+    if (gs) hipLaunchKernelGGL(tick_glue_gs_kernel, dim3((B + 127) / 128), dim3(128), 0, s, h->dgs(d));
+    else hipLaunchKernelGGL(tick_glue_kernel, dim3((B + 127) / 128), dim3(128), 0, s, d);
     const int rc = wcqp_ik_solve_device(h->ik, B, io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, nullptr, nullptr, s);
     if (rc != WCQP_OK) return rc;
     hipLaunchKernelGGL(tick_post_kernel, dim3((B * kDof + 255) / 256), dim3(256), 0, s, d);
@@ -185,6 +225,12 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (!params || !out || params->batch < 1 || params->max_ticks < 1) return WCQP_E_INVALID;
     if (params->step_ticks < 2 || params->ds_ticks < 0 || params->ds_ticks > params->step_ticks) return WCQP_E_INVALID;
     if (params->ik.dof != kDof) return WCQP_E_UNSUPPORTED;
+    // ZMP gain scheduling: finite stance gains, a finite smoothing time > 0 (refused before anything touches the device)
+    const bool gs = params->zmp_gain_scheduling != 0;
+    if (params->zmp_gain_scheduling != 0 && params->zmp_gain_scheduling != 1) return WCQP_E_INVALID;
+    if (gs && (!std::isfinite(params->k_com_stance) || !std::isfinite(params->k_zmp_stance) || !std::isfinite(params->zmp_smoothing_time) ||
+               !(params->zmp_smoothing_time > 0.0)))
+        return WCQP_E_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         std::fprintf(stderr, "[wcqp] no HIP device: the tick pipeline has no CPU fallback\n");
@@ -256,7 +302,15 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     // external feedback: the default (base-eliminated) kernel with constant Jacobians or fused kinematics, without logger rows
     if (h->external && (!d.skew || params->logger_ticks > 0 || (h->kin && !fusedk))) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }
     if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); }
-    if (reactive) { double* vel = nullptr; A_(vel, B * d.traj_len * 2); d.dcm_vel = vel; d.reactive = 1; d.k_dcm = params->k_dcm; }
+    if (reactive) { d.reactive = 1; d.k_dcm = params->k_dcm; }
+    // the DCM velocity: the reactive controller's input, and with gain scheduling the stance flag's (MPC handles then read it too)
+    if (reactive || gs) { double* vel = nullptr; A_(vel, B * d.traj_len * 2); d.dcm_vel = vel; }
+    if (gs) {
+        d.gain_sched = 1;
+        h->zg.k_com_st = params->k_com_stance; h->zg.k_zmp_st = params->k_zmp_stance;
+        wcqp::zmp_smoother_coeffs(params->zmp_smoothing_time, params->mpc.sampling_time, h->zg.nb, h->zg.na);
+        A_(h->zg.zs, B * 4);
+    }
     if (d.skew) {
         A_(d.mst, B * 16); A_(d.hand, 2 * B * kHandLen); A_(d.live_A, B * 16); A_(d.live_b, B * 8); A_(d.live_nc, B); A_(d.sel_built, B);
         if (compact) A_(jcomp, B * (size_t)cstride);
@@ -290,7 +344,14 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
 #ifdef WCQP_TICK_STAMPS
     if (d.skew && dev_alloc(h, &d.stamps, ((B + 3) / 4) * 16) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
 #endif
-    if (d.skew) {
+    if (d.skew && gs) {
+        // the scheduled kernels read the TickDevGS behind the pointer
+        TickDevGS* dg = nullptr;
+        if (dev_alloc(h, &dg, 1) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
+        const TickDevGS g = h->dgs(d);
+        if (hipMemcpy(dg, &g, sizeof(TickDevGS), hipMemcpyHostToDevice) != hipSuccess) { wcqp_tick_destroy(h); return WCQP_E_HIP; }
+        h->d_dev = dg;
+    } else if (d.skew) {
         if (dev_alloc(h, &h->d_dev, 1) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
         if (hipMemcpy(h->d_dev, &d, sizeof(TickDev), hipMemcpyHostToDevice) != hipSuccess) { wcqp_tick_destroy(h); return WCQP_E_HIP; }
     }
@@ -324,7 +385,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     WCQP_HIP_TRY(hipDeviceSynchronize());
 #define UP_(dst, src, n) WCQP_HIP_TRY(hipMemcpy(const_cast<void*>(static_cast<const void*>(dst)), (src), (n), hipMemcpyHostToDevice))
     UP_(d.ref_traj, in->ref_traj, B * d.traj_len * 16);
-    if (d.reactive) {
+    if (d.reactive || d.gain_sched) {
         // the planner's DCM velocity, or the forward difference (ref[t + 1] - ref[t]) / dT (the last stage, which no tick reads: 0)
         h->vel_explicit = in->dcm_vel_traj != nullptr;
         if (h->vel_explicit) {
@@ -378,6 +439,8 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     UP_(d.zmp_meas, in->u_init, B * 16); UP_(d.u_prev, in->u_init, B * 16);
 #undef UP_
     WCQP_HIP_TRY(hipMemset(d.v_ref_prev, 0, B * 16)); WCQP_HIP_TRY(hipMemset(d.v_star_prev, 0, B * 16));
+    // the gain smoothers at rest at the stance gains (WalkingZMPController::initialize): s = 0, state 0
+    if (d.gain_sched) WCQP_HIP_TRY(hipMemset(h->zg.zs, 0, B * 32));
     WCQP_HIP_TRY(hipMemset(d.dq_prev, 0, B * kDof * 8)); WCQP_HIP_TRY(hipMemset(d.tick2, 0, 8));
     {   // contact pair of tick 0 (later ticks: tick_post_kernel)
         std::vector<int> sel(B);
@@ -445,7 +508,8 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     if (h->d.skew) {
         // the fused launch of tick t carries IK(t) and MPC(t+1): the MPC of the call's first tick goes first, on its own, and
         // the call's LAST tick does not run the MPC of the tick after it - between calls nothing is ahead of anything
-        const int rc = wcqp_ik::ik4_launch_tick_prime(h->d, h->ticks_enqueued, s);
+        const int rc = h->d.gain_sched ? wcqp_ik::ik4_launch_tick_prime_gs(h->dgs(h->d), h->ticks_enqueued, s)
+                                       : wcqp_ik::ik4_launch_tick_prime(h->d, h->ticks_enqueued, s);
         if (rc != WCQP_OK) return rc;
     }
     // the fused kernel walks through several ticks per launch (the waves need no per-tick synchronisation): no graph needed
@@ -505,7 +569,7 @@ int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stage
     // stages the ticks already enqueued have consumed as their own reference DCM stay as they are; everything a later
     // tick's window can see may change
     if (from_tick < h->ticks_enqueued || (long)from_tick + n_stages > (long)d.traj_len) return WCQP_E_INVALID;
-    if (h->vel_explicit) return WCQP_E_UNSUPPORTED;      // (the reactive controller's uploaded velocities: the splice has no tail for them)
+    if (h->vel_explicit) return WCQP_E_UNSUPPORTED;      // (uploaded velocities - reactive controller, gain scheduling: the splice has no tail for them)
     // `ref_tail` is the caller's HOST memory and the copy below is ordered behind ticks that may still run for a long time: the
     // rows are therefore taken NOW - staged into device memory of the handle on a copy stream of its own, waited for before
     // this call returns - and the caller may release `ref_tail` as soon as it has.
@@ -525,7 +589,7 @@ int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stage
     // behind the ticks already enqueued (the trajectory pointer the kernels - and any captured graph - hold does not change)
     WCQP_HIP_TRY(hipMemcpy2DAsync(const_cast<double*>(d.ref_traj.get()) + (size_t)from_tick * 2, (size_t)d.traj_len * 16, h->splice_stage, (size_t)n_stages * 16,
                                   (size_t)n_stages * 16, (size_t)d.batch, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (d.reactive) {
+    if (d.reactive || d.gain_sched) {
         // the forward difference of the stages the new ones touch: [from_tick - 1, from_tick + n_stages), the last stage excepted
         const int lo = from_tick > 0 ? from_tick - 1 : 0, hi = from_tick + n_stages < d.traj_len ? from_tick + n_stages : d.traj_len - 1;
         if (hi > lo) {
@@ -555,6 +619,7 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
     out->kin_handoff = !h->kin ? -1 : d.kin_fused ? WCQP_KIN_HANDOFF_FUSED : d.compact ? WCQP_KIN_HANDOFF_COMPACT : WCQP_KIN_HANDOFF_DENSE;
     out->ticks_per_launch = h->ticks_per_launch;
     out->dcm_controller = d.reactive ? WCQP_TICK_DCM_REACTIVE : WCQP_TICK_DCM_MPC;
+    out->zmp_gain_scheduling = d.gain_sched ? 1 : 0;
     // a kinematics launch unless fused; then the skewed kernel (1), MPC / reactive + the 16-lane kernel (2) or controller, glue, IK, post (4)
     out->launches_per_tick = (h->kin && !d.kin_fused ? 1 : 0) + (h->form == TickForm::SKEWED ? 1 : h->form == TickForm::MPC_IK16 ? 2 : 4);
     return WCQP_OK;
@@ -590,6 +655,16 @@ int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out) {
     DN_(out->mpc_fail, d.mpc_fail, B * 8); DN_(out->ik_fail, d.ik_fail, B * 8);
     DN_(out->hot_try, d.hot_try, B * 8); DN_(out->hot_hit, d.hot_hit, B * 8); DN_(out->tick, d.tick2 + h->phase, 4);
 #undef DN_
+    if (out->zmp_gains) {
+        if (d.gain_sched) {
+            // the smoother output s of the last executed tick -> its gains (the two operations of zmp_gains_at, tick_device.h)
+            std::vector<double> zs(B * 4);
+            WCQP_HIP_TRY(hipMemcpy(zs.data(), h->zg.zs, B * 32, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < B; ++i) zmp_gains_host(d, h->zg, zs[i * 4 + 3], out->zmp_gains + 2 * i);
+        } else {
+            for (size_t i = 0; i < B; ++i) { out->zmp_gains[2 * i] = d.k_com; out->zmp_gains[2 * i + 1] = d.k_zmp; }
+        }
+    }
     return WCQP_OK;
 }
 

@@ -84,9 +84,28 @@ struct TickDev {
     // ---- the REACTIVE DCM controller (wcqp_tick_params.dcm_controller, WalkingDCMReactiveController.cpp:63-82) in the MPC's place:
     // no window, no hull rows, no gains - the reference stage of the tick, its velocity and the measured DCM
     int reactive;
+    // ZMP-CoM gain scheduling (wcqp_tick_params.zmp_gain_scheduling): the handle's TickDev is then a TickDevGS (below).  (This int
+    // sits in the padding in front of k_dcm: the size and layout of TickDev - the kernel arguments of every kernel that takes it by
+    // value - stay what they were.)
+    int gain_sched;
     double k_dcm;
     wcqp::GPtr<const double> dcm_vel;          // [B][traj_len][2] the planner's DCM velocity: uploaded, or the forward difference of ref_traj
+                                               // (read by the reactive controller, and with gain scheduling by either controller)
 };
+// ---- ZMP-CoM gain scheduling (wcqp_tick_params.zmp_gain_scheduling, include/wcqp.h): WalkingModule.cpp:657-662 calls
+// WalkingZMPController::setPhase(stance) before evaluateControl, and setPhase moves both gains through a minJerkTrajGen smoother
+// (WalkingZMPController.cpp:29-125).  Both smoothers are the same linear filter of unit DC gain at rest at the stance gains, so the
+// tick runs ONE filter s of the 0 / 1 walking indicator per robot: k = k_stance + (k_walking - k_stance) s.  The coefficients come from
+// wcqp::zmp_smoother_coeffs (tick.hip), the one place that defines the discretisation.
+struct ZmpSched {
+    double k_com_st, k_zmp_st;       // stance gains (TickDev::k_com / k_zmp are the walking ones)
+    double nb[4], na[3];             // y[n] = sum_k nb[k] u[n - k] - sum_k na[k] y[n - 1 - k]
+    wcqp::GPtr<double> zs;           // [B][4] per robot, one 32-byte record: the filter's state x0, x1, x2 (transposed direct form II)
+                                     // and its last output s (what the last executed tick used: wcqp_tick_outputs.zmp_gains)
+};
+// A scheduled handle's TickDev: the scheduled kernels that take it by value take this one, the skewed ones read it from device memory.
+// The kernels that know nothing of scheduling keep their TickDev (and their code).
+struct TickDevGS : TickDev { ZmpSched zg; };
 constexpr int kHandLen = 14;
 constexpr int kLoggerCols = 53;
 constexpr int kKinTabJoint = 22, kKinTabInts = 19, kKinTabFrames = kKinTabJoint * kDof, kKinTabRoot = kKinTabFrames + 36, kKinTabSize = kKinTabRoot + 6;
@@ -125,6 +144,8 @@ namespace wcqp {
 // the kinematics kernel in tick mode (kin.hip)
 int kin_enqueue_tick(wcqp_kin_t h, int batch, const wcqp_tick::KinTick& kt, const double* q,
                      double* J_left, double* J_right, double* J_neck, double* J_com, double* state, hipStream_t stream);
+// the discrete coefficients of the gain smoother of zmp_gain_scheduling (tick.hip): smoothing time T, sampling time dT
+void zmp_smoother_coeffs(double T, double dT, double nb[4], double na[3]);
 }  // namespace wcqp
 namespace wcqp_tick {
 
@@ -156,8 +177,10 @@ __device__ __forceinline__ int contact_code(int t, int phase0, int step_ticks, i
 
 // One horizontal axis of instance i at tick t: reference LIPM integrator, ZMP-CoM law, desired CoM
 // for the IK state block (returned: the caller stores it to HBM or LDS), synthetic plant.  `mpc_ok`: this tick's MPC ended usable.
+// GS (gain scheduling): the law's gains are kg (kCoM, kZMP of the tick: zmp_gains_tick), not d.k_com / d.k_zmp.
+template <bool GS = false>
 __device__ __forceinline__ void tick_glue_axis(const TickDev& d, int i, int t, int ax, bool mpc_ok, double u0_ax,
-                                               double& s_com, double& s_pstar, double& s_vel) {
+                                               double& s_com, double& s_pstar, double& s_vel, double2 kg = double2{}) {
     // StableDCMModel::integrateModel (StableDCMModel.cpp:63-90), Tustin integrator; it precedes the
     // MPC in the reference (WalkingModule.cpp:578-597) but only the ZMP-CoM law below consumes it
     const double r = d.ref_traj[((size_t)i * d.traj_len + t) * 2 + ax];
@@ -169,7 +192,7 @@ __device__ __forceinline__ void tick_glue_axis(const TickDev& d, int i, int t, i
     const double u = mpc_ok ? u0_ax : d.u_prev[2 * i + ax];     // hold the last command on failure
     // WalkingZMPController::evaluateControl (WalkingZMPController.cpp:146-173)
     const double com = d.com[2 * i + ax];
-    const double v = d.k_com * (c_ref - com) - d.k_zmp * (u - d.zmp_meas[2 * i + ax]) + vr;
+    const double v = (GS ? kg.x : d.k_com) * (c_ref - com) - (GS ? kg.y : d.k_zmp) * (u - d.zmp_meas[2 * i + ax]) + vr;
     const double p_star = d.p_star[2 * i + ax] + 0.5 * d.dT * (v + d.v_star_prev[2 * i + ax]);
     d.p_star[2 * i + ax] = p_star;
     d.v_star_prev[2 * i + ax] = v;
@@ -183,6 +206,52 @@ __device__ __forceinline__ void tick_glue_axis(const TickDev& d, int i, int t, i
     d.u_prev[2 * i + ax] = u;
     if (t < d.log_ticks) d.u0_log[((size_t)t * d.batch + i) * 2 + ax] = u;
 }
+// the stance flag of WalkingModule.cpp:657-658, evaluated as the reference does: the norm of the DCM velocity, compared with 0.001
+// (no squared form, and no FMA contraction, so that the device and a restatement in numpy agree at the threshold)
+__device__ __forceinline__ bool zmp_stance(double vx, double vy) {
+#pragma clang fp contract(off)
+    return sqrt(vx * vx + vy * vy) < 0.001;
+}
+// one step of the smoother towards u (1: walking, 0: stance) from the state (x0, x1, x2), which it advances: returns the output
+__device__ __forceinline__ double zmp_smoother_step(const ZmpSched& z, double u, double& x0, double& x1, double& x2) {
+    const double y = z.nb[0] * u + x0;
+    x0 = z.nb[1] * u - z.na[0] * y + x1;
+    x1 = z.nb[2] * u - z.na[1] * y + x2;
+    x2 = z.nb[3] * u - z.na[2] * y;
+    return y;
+}
+// the gains (kCoM, kZMP) at smoother output s (uncontracted: the host forms zmp_gains from s with the same two operations)
+__device__ __forceinline__ double2 zmp_gains_at(const TickDev& d, const ZmpSched& z, double s) {
+#pragma clang fp contract(off)
+    return make_double2(z.k_com_st + (d.k_com - z.k_com_st) * s, z.k_zmp_st + (d.k_zmp - z.k_zmp_st) * s);
+}
+// the robot's smoother state and the velocity stage of tick t (both axes), as loaded
+struct ZmpRegs { double2 x01; double x2; };
+__device__ __forceinline__ void zmp_state_issue(const TickDevGS& d, long inst, ZmpRegs& Z) {
+    const double* zp = wcqp::at32(d.zg.zs.get(), (unsigned)inst * 32u);
+    Z.x01 = *reinterpret_cast<const double2*>(zp); Z.x2 = zp[2];
+}
+__device__ __forceinline__ double2 zmp_vel_issue(const TickDev& d, long inst, int t) {
+    return *wcqp::at32(reinterpret_cast<const double2*>(d.dcm_vel.get()), ((unsigned)inst * (unsigned)d.traj_len + (unsigned)t) * 16u);
+}
+// setPhase of tick t: the stance flag from the velocity stage rd, one step of the smoother, the state stored back (by the lane that
+// passes `store`; every lane of the robot computes the same numbers); returns the smoother's output s of tick t (zmp_gains_at: the gains)
+__device__ __forceinline__ double zmp_smoother_advance(const TickDevGS& d, long inst, bool store, double2 rd, const ZmpRegs& Z) {
+    double x0 = Z.x01.x, x1 = Z.x01.y, x2 = Z.x2;
+    const double s = zmp_smoother_step(d.zg, zmp_stance(rd.x, rd.y) ? 0.0 : 1.0, x0, x1, x2);
+    if (store) {
+        double2* zp = reinterpret_cast<double2*>(d.zg.zs.get() + inst * 4);
+        zp[0] = make_double2(x0, x1); zp[1] = make_double2(x2, s);
+    }
+    return s;
+}
+// the same for robot i on its own (the in-order forms: the glue)
+__device__ __forceinline__ double2 zmp_gains_tick(const TickDevGS& d, int i, int t, bool store) {
+    ZmpRegs Z;
+    zmp_state_issue(d, i, Z);
+    return zmp_gains_at(d, d.zg, zmp_smoother_advance(d, i, store, zmp_vel_issue(d, i, t), Z));
+}
+
 // velocity profile of the swing foot over its single-support phase x in [0, 1): f(x) = 6 sqrt(3) x (1 - x)(1 - 2x), peak 1,
 // zero integral - the foot leaves its planted pose by at most 0.325 * amplitude * T_ss and is back at touch-down
 // (kinematics mode only: with real kinematics a twist held constant for the whole swing drags the foot out of the
@@ -257,9 +326,10 @@ __device__ __forceinline__ void tick_mpc_issue(const TickDev& d, int j, long ins
 // What follows the DCM controller of tick t on the lane of axis `ax`, whichever controller it is (MPC or reactive): the LIPM reference
 // integrator, the ZMP-CoM law, the synthetic plant, the chain's state record, the hand-off to IK(t) and the u0 log.  rr: the reference
 // DCM of tick t; u: the controller's desired ZMP (the MPC's: the held command on failure); mpc_ok: what the hand-off reports.
-template <bool EXT>
+// GS: the ZMP-CoM law's gains are kg (kCoM, kZMP of tick t: zmp_smoother_advance, then zmp_gains_at), not d.k_com / d.k_zmp.
+template <bool EXT, bool GS = false>
 __device__ __forceinline__ void tick_chain_step(const TickDev& d, int ax, long inst, int t, const TickMpcRegs& R, double rr, double u, bool mpc_ok,
-                                                const unsigned long long* noise_base) {
+                                                const unsigned long long* noise_base, double2 kg = double2{}) {
     const double c_ref0 = R.s01.x, v_ref_prev = R.s01.y, com = R.s23.x, u_prev = R.s23.y;
     const double p_star0 = R.s45.x, v_star_prev = R.s45.y, xi = R.s67.x;
     const double zmp_meas = EXT ? R.s67.y : u_prev;
@@ -268,7 +338,7 @@ __device__ __forceinline__ void tick_chain_step(const TickDev& d, int ax, long i
     const double c_ref = c_ref0 + 0.5 * d.dT * (vr + v_ref_prev);
     // WalkingZMPController::evaluateControl (WalkingZMPController.cpp:146-173); the measured ZMP: with the internal plant the
     // previous command (the same number as u_prev), with external feedback what the caller measured
-    const double v = d.k_com * (c_ref - com) - d.k_zmp * (u - zmp_meas) + vr;
+    const double v = (GS ? kg.x : d.k_com) * (c_ref - com) - (GS ? kg.y : d.k_zmp) * (u - zmp_meas) + vr;
     const double p_star = p_star0 + 0.5 * d.dT * (v + v_star_prev);
     // synthetic plant: LIPM with a bounded disturbance
     const double com1 = com + d.dT * (-d.omega * (com - xi));
@@ -304,10 +374,10 @@ __device__ __forceinline__ double reactive_zmp(const TickDev& d, double r, doubl
 __device__ __forceinline__ double tick_react_law(const TickDev& d, int j, const TickMpcRegs& R, double2 r0, double2 rd) {
     return (j & 1) ? reactive_zmp(d, r0.y, rd.y, R.s67.x) : reactive_zmp(d, r0.x, rd.x, R.s67.x);
 }
-template <bool EXT = false>
+template <bool EXT = false, bool GS = false>
 __device__ __forceinline__ void tick_react_finish(const TickDev& d, int j, long inst, bool live, int t, const TickMpcRegs& R, double2 r0, double u,
-                                                  const unsigned long long* noise_base = nullptr) {
-    if (j < 2 && live) tick_chain_step<EXT>(d, j, inst, t, R, j == 0 ? r0.x : r0.y, u, true, noise_base);
+                                                  const unsigned long long* noise_base = nullptr, double2 kg = double2{}) {
+    if (j < 2 && live) tick_chain_step<EXT, GS>(d, j, inst, t, R, j == 0 ? r0.x : r0.y, u, true, noise_base, kg);
 }
 // tick_mpc_finish = tick_mpc_partial (this lane's share of u0_unc from the loaded window: the window registers die here) +
 // tick_mpc_finish_from (everything else, from the per-axis state records, the hull row and the partial sums)
@@ -321,9 +391,10 @@ __device__ __forceinline__ void tick_mpc_partial(const TickDev& d, int j, long i
 // r0: stage 0 of the window (the reference DCM of tick t; meaningful on lane 0)
 // EXT (external feedback: only tick_mpc_prime_kernel<true> - with such a handle every tick's MPC runs there): the measured ZMP is the
 // caller's (record entry 7), not the previous command; the kernels of the internal plant keep entry 7 out of their registers
-template <bool EXT = false>
+template <bool EXT = false, bool GS = false>
 __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, long inst, bool live, int t, TickMpcRegs& R, double2 r0, double ux, double uy,
-                                                     double (*s_hull)[4], int code_known = -1, const unsigned long long* noise_base = nullptr) {
+                                                     double (*s_hull)[4], int code_known = -1, const unsigned long long* noise_base = nullptr,
+                                                     double2 kg = double2{}) {
     // contact pair of tick t; the live row set follows it (WalkingController::setConvexHullConstraint switches rows only
     // when the pair changes, ...PredictiveController.cpp:369-374)
     const int code = code_known >= 0 ? code_known : contact_code(t, R.phase0, d.step_ticks, d.ds_ticks);
@@ -368,15 +439,16 @@ __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, lo
         const int ax = j;
         const double rr = ax == 0 ? r0.x : r_y;        // reference DCM of tick t: stage 0 of the window (lane 0 holds it)
         const double u = mpc_ok ? (ax == 0 ? u0x : u0y) : R.s23.y;       // hold the last command on failure
-        tick_chain_step<EXT>(d, ax, inst, t, R, rr, u, mpc_ok, noise_base);
+        tick_chain_step<EXT, GS>(d, ax, inst, t, R, rr, u, mpc_ok, noise_base, kg);
     }
 }
-template <bool GAINS_LDS = false, bool EXT = false>
+template <bool GAINS_LDS = false, bool EXT = false, bool GS = false>
 __device__ __forceinline__ void tick_mpc_finish(const TickDev& d, int j, long inst, bool live, int t, TickMpcRegs& R, double (*s_hull)[4],
-                                                const double* gr_lds = nullptr, int code_known = -1, const unsigned long long* noise_base = nullptr) {
+                                                const double* gr_lds = nullptr, int code_known = -1, const unsigned long long* noise_base = nullptr,
+                                                double2 kg = double2{}) {
     double ux, uy;
     tick_mpc_partial<GAINS_LDS>(d, j, inst, t, R, gr_lds, ux, uy);
-    tick_mpc_finish_from<EXT>(d, j, inst, live, t, R, R.L.r[0], ux, uy, s_hull, code_known, noise_base);
+    tick_mpc_finish_from<EXT, GS>(d, j, inst, live, t, R, R.L.r[0], ux, uy, s_hull, code_known, noise_base, kg);
 }
 // the same two with the gait cycle index cyc = (t + phase0) % (2 step_ticks) at hand (the tick kernel carries it from tick to tick:
 // integer divisions by run-time values are ~35 instructions each, and a tick had four of them, on every lane)
