@@ -521,6 +521,24 @@ typedef struct wcqp_tick_params {
     int32_t zmp_gain_scheduling;
     double k_com_stance, k_zmp_stance;   /* kCoM_stance / kZMP_stance of zmpControllerParams.ini                                   */
     double zmp_smoothing_time;           /* smoothingTime of zmpControllerParams.ini [s]                                           */
+    /* Planned-trajectory mode (0 = off: the synthetic gait of step_ticks / ds_ticks / phase0 / swing_twist).  On, every tick t takes
+     * from stage t of the planner's trajectories (wcqp_tick_inputs.left_traj ... com_height_vel) what WalkingModule::updateTrajectories
+     * (WM/src/WalkingModule.cpp:1085-1145) pulls from TrajectoryGenerator:
+     *   - the IK's desired foot poses (state 24..47) and twists (75..86), the desired CoM height and its velocity (71, 74);
+     *   - the desired neck orientation (57..65) = RotZ(atan2(sin yL + sin yR, cos yL + cos yR)) * neck_additional_rotation, with each
+     *     foot's yaw atan2(R10, R00) (WalkingModule.cpp:697-707, :383; WalkingQPInverseKinematics.cpp:143-146);
+     *   - the floating-base anchor of the forward kinematics: the desired pose of the foot the fixed-frame bit names (:1147-1165);
+     *   - the contact pair; on a change of pair the MPC's support-polygon rows are rebuilt from that tick's desired foot poses and
+     *     foot_rect (...PredictiveController.cpp:364-435), with no change they stay.
+     * Everything else is what the tick does without it.  phase0, step_ticks (beyond the range check), ds_ticks, swing_twist, hull_tab_*
+     * and the desired-pose / Rd_neck entries of state0 are ignored.  Runs with per-tick kinematics and the FUSED hand-off in the skewed
+     * kernel of the default IK algorithm, either DCM controller, with or without gain scheduling, any ticks_per_launch and use_graph.
+     * wcqp_tick_create returns WCQP_E_UNSUPPORTED, before any device allocation, for the mode with constant Jacobians, with the DENSE or
+     * COMPACT hand-off (or wherever FUSED would not be taken: an MPC horizon of 56 or more, a tree FUSED cannot run), logger_ticks > 0,
+     * the EXTERNAL plant or an IK algorithm other than the default; wcqp_tick_splice_reference returns WCQP_E_UNSUPPORTED on such a
+     * handle (there is no tail for the feet).  WCQP_E_INVALID for a value other than 0 / 1 or a non-finite neck_additional_rotation. */
+    int32_t planned_trajectories;
+    double neck_additional_rotation[9];  /* additional_rotation of qpInverseKinematics.ini, row-major                              */
 } wcqp_tick_params;
 #define WCQP_TICK_PLANT_INTERNAL 0
 #define WCQP_TICK_PLANT_EXTERNAL 1
@@ -541,6 +559,18 @@ typedef struct wcqp_tick_inputs {   /* HOST pointers, copied at upload */
     const double* dcm_vel_traj; /* [B][max_ticks+N+1][2] or NULL: the planner's DCM velocity (WalkingModule.cpp:641-642), read by
                                  * the REACTIVE controller and by ZMP gain scheduling (NULL: the forward difference of ref_traj);
                                  * MPC handles without gain scheduling ignore it */
+    /* planned_trajectories only (ignored otherwise; required then, except the two CoM height arrays): T = max_ticks + N + 1 stages,
+     * stage t what the planner's deques hold at front() on tick t.  wcqp_tick_upload returns WCQP_E_INVALID when a required array is
+     * NULL, or when a stage a run can reach (0 .. max_ticks) has neither foot in contact, a fixed-frame foot that is not in contact or
+     * a non-finite value - checked before anything of the handle changes (a handle uploaded before keeps that upload).  The upload also
+     * builds the support-polygon rows of every change of contact pair from that stage's desired feet and foot_rect. */
+    const double* left_traj;    /* [B][T][12] left sole: position 3, rotation 9 row-major (m_leftTrajectory)                 */
+    const double* right_traj;   /* [B][T][12] right sole (m_rightTrajectory)                                                  */
+    const double* left_twist;   /* [B][T][6]  m_leftTwistTrajectory                                                           */
+    const double* right_twist;  /* [B][T][6]  m_rightTwistTrajectory                                                          */
+    const uint8_t* contact;     /* [B][T] bit 0 left in contact, bit 1 right in contact, bit 2 left is the fixed frame        */
+    const double* com_height_traj;  /* [B][T] or NULL: state0 entry 68 (m_comHeightTrajectory)                               */
+    const double* com_height_vel;   /* [B][T] or NULL: 0 (m_comHeightVelocity)                                               */
 } wcqp_tick_inputs;
 
 typedef struct wcqp_tick_outputs {  /* HOST pointers, any may be NULL */
@@ -606,6 +636,7 @@ typedef struct wcqp_tick_info {
     int32_t dcm_controller;     /* WCQP_TICK_DCM_*                                                                          */
     int32_t launches_per_tick;  /* kernel launches of a tick that runs alone (the skewed fused kernel: 1)                   */
     int32_t zmp_gain_scheduling;   /* wcqp_tick_params.zmp_gain_scheduling as taken (0 / 1)                                 */
+    int32_t planned_trajectories;  /* wcqp_tick_params.planned_trajectories as taken (0 / 1)                                */
 } wcqp_tick_info;
 int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
 

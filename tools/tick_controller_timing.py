@@ -10,7 +10,10 @@ Per case: one pipeline of `batch` robots; every repetition re-uploads the inputs
 ONE wcqp_tick_run call (device events around it); the median over the repetitions is reported.  The first repetition logs its first
 16 ticks, and a sample of robots is replayed through the CPU restatement (oracle/tick_spec.py; for the reactive controller with its
 MPC solve replaced by the reactive law, tests/helpers/reactive_tick.py).  Kernel statistics: run this under
-`rocprofv3 --kernel-trace --stats` in a run of its own (--no-check keeps the CPU replay out of it)."""
+`rocprofv3 --kernel-trace --stats` in a run of its own (--no-check keeps the CPU replay out of it).
+    python tools/tick_controller_timing.py --planned [...]     (fused kinematics at N = 50, both controllers: planned trajectories -
+        the synthetic gait written out as the planner's stages, the same work - against the synthetic gait, the two forms alternating
+        within every repetition; the first 16 ticks of both forms must agree to 1e-12)"""
 import argparse
 import importlib.util
 import json
@@ -29,6 +32,9 @@ import walking_controllers_amd as wca  # noqa: E402
 _spec = importlib.util.spec_from_file_location("reactive_tick", os.path.join(ROOT, "tests", "helpers", "reactive_tick.py"))
 rt = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(rt)
+_spec = importlib.util.spec_from_file_location("planned_tick", os.path.join(ROOT, "tests", "helpers", "planned_tick.py"))
+pt = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(pt)
 _spec = importlib.util.spec_from_file_location("zmp_gains", os.path.join(ROOT, "tests", "helpers", "zmp_gains.py"))
 zg = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(zg)
@@ -119,6 +125,55 @@ def measure(kin_mode, ctrl, horizon, B, T, W, reps, check, gs=False):
     return res
 
 
+ADD_ROT = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])      # iCubGazeboV2_5's additional_rotation (qpInverseKinematics.ini)
+
+
+def measure_planned(ctrl, B, T, W, reps):
+    """fused kinematics, N = 50: the synthetic gait and the same gait as planned trajectories, alternating within every repetition"""
+    S = wca.synth
+    dev = torch.device("cuda", 0)
+    kin = wca.KinModel(S.icub_like_model())
+    n = T + W
+    from oracle import tick_spec as ts
+    plan, data = pt.synthetic_as_planned(ts.TickParams(horizon=50), make_data(True, B, n, 50, 0, kin), n + 51, ADD_ROT)
+    kw = dict(dcm_controller="reactive", k_dcm=K_DCM) if ctrl == "reactive" else {}
+    pipes = {}
+    for form in ("synthetic", "planned"):
+        ik = wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=S.WALK_VMAX, joint_reg_rad=np.deg2rad(S.WALK_POSTURE_DEG))
+        pk = dict(planned_trajectories=True, neck_additional_rotation=ADD_ROT) if form == "planned" else {}
+        pipes[form] = wca.TickPipeline(B, n, wca.MpcSolver(horizon=50), ik, kin=kin, log_ticks=CHECK_TICKS, **kw, **pk)
+    stream = torch.cuda.current_stream(dev)
+    times = {f: [] for f in pipes}
+    outs = {}
+    for r in range(reps):
+        for form, pipe in pipes.items():
+            if form == "planned":
+                pipe.upload(data, **plan)
+            else:
+                pipe.upload(data)
+            pipe.run(W, stream=stream.cuda_stream)
+            torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            pipe.run(T, stream=stream.cuda_stream)
+            e1.record(stream)
+            torch.cuda.synchronize(dev)
+            times[form].append(e0.elapsed_time(e1) * 1e3 / T)
+            if r == 0:
+                outs[form] = pipe.download()
+    rows = []
+    for form in pipes:
+        rows.append({"form": "fused_kinematics", "trajectories": form, "dcm_controller": ctrl, "horizon": 50, "batch": B, "timed_ticks": T,
+                     "warmup_ticks": W, "reps": reps, "us_per_tick_median": float(np.median(times[form])),
+                     "us_per_tick_all": [round(x, 3) for x in times[form]], "info": pipes[form].info(),
+                     "ik_fail_robots": int((outs[form]["ik_fail"] > 0).sum()), "mpc_fail": int(outs[form]["mpc_fail"].sum())})
+    rows[1]["planned_over_synthetic"] = rows[1]["us_per_tick_median"] / rows[0]["us_per_tick_median"]
+    rows[1]["logged_ticks_max_abs_diff"] = {k: float(np.abs(outs["planned"][k] - outs["synthetic"][k]).max()) for k in ("u0_log", "dq_log")}
+    for p_ in pipes.values():
+        p_.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8192)
@@ -128,9 +183,20 @@ def main():
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--zmp-gain-scheduling", action="store_true", help="the scheduled cases and their non-scheduled twins")
+    ap.add_argument("--planned", action="store_true", help="planned trajectories against the synthetic gait (fused kinematics, N = 50)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     rows = []
+    if a.planned:
+        for ctrl in ("mpc", "reactive"):
+            for r in measure_planned(ctrl, a.batch, a.ticks, max(a.warmup, CHECK_TICKS), a.reps):
+                print(json.dumps(r), flush=True)
+                rows.append(r)
+        res = {"device": torch.cuda.get_device_name(0), "source_hash": wca.capi.source_hash(), "k_dcm": K_DCM, "cases": rows}
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     cases = [(f, c, h, False) for f, c, h in CASES]
     if a.zmp_gain_scheduling:
         cases = [(f, c, 50, gs) for f in ("constant_jacobians", "fused_kinematics") for c in ("mpc", "reactive") for gs in (False, True)]

@@ -167,7 +167,8 @@ class TickParams(C.Structure):
                 ("ik_cold_start_only", C.c_int32), ("use_kinematics", C.c_int32), ("kin", KinParams), ("foot_rect", C.c_double * 8),
                 ("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("logger_ticks", C.c_int32), ("plant", C.c_int32),
                 ("dcm_controller", C.c_int32), ("k_dcm", C.c_double),
-                ("zmp_gain_scheduling", C.c_int32), ("k_com_stance", C.c_double), ("k_zmp_stance", C.c_double), ("zmp_smoothing_time", C.c_double)]
+                ("zmp_gain_scheduling", C.c_int32), ("k_com_stance", C.c_double), ("k_zmp_stance", C.c_double), ("zmp_smoothing_time", C.c_double),
+                ("planned_trajectories", C.c_int32), ("neck_additional_rotation", C.c_double * 9)]
 
 
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
@@ -176,13 +177,14 @@ KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1
 
 class TickInfo(C.Structure):
     _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32),
-                ("zmp_gain_scheduling", C.c_int32)]
+                ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32)]
 
 
 class TickInputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("ref_traj", "hull_tab_A", "hull_tab_b", "hull_tab_nc", "phase0",
                                           "J_left", "J_right", "J_neck", "J_com", "state0", "swing_twist",
-                                          "q0", "dcm0", "com0", "u_init", "dcm_vel_traj")]
+                                          "q0", "dcm0", "com0", "u_init", "dcm_vel_traj",
+                                          "left_traj", "right_traj", "left_twist", "right_twist", "contact", "com_height_traj", "com_height_vel")]
 
 
 class TickOutputs(C.Structure):
@@ -453,13 +455,16 @@ class TickPipeline:
                  kin: "Optional[KinModel]" = None, foot_rect=None, ik_hot_start: bool = True, kin_handoff: int = 0,
                  ticks_per_launch: int = 0, logger_ticks: int = 0, external_feedback: bool = False,
                  dcm_controller: str = "mpc", k_dcm: Optional[float] = None, zmp_gain_scheduling: bool = False,
-                 k_com_stance: Optional[float] = None, k_zmp_stance: Optional[float] = None, zmp_smoothing_time: Optional[float] = None):
+                 k_com_stance: Optional[float] = None, k_zmp_stance: Optional[float] = None, zmp_smoothing_time: Optional[float] = None,
+                 planned_trajectories: bool = False, neck_additional_rotation=None):
         """kin: a KinModel -> per-tick kinematics (Jacobians, actual poses and hull rows rebuilt every tick from the
         integrated joint state with the base anchored at the stance foot; upload() then ignores J_* / hull_tab_*).
         dcm_controller: "mpc" (the DCM-MPC, the reference's use_mpc 1) or "reactive" (WalkingDCMReactiveController, the
         reference's default use_mpc 0), which needs k_dcm (kDCM of the robot's dcmReactiveControllerParams.ini).
         zmp_gain_scheduling: the reference's useGainScheduling 1 (zmpControllerParams.ini) - k_com / k_zmp are then the walking gains
-        and k_com_stance, k_zmp_stance and zmp_smoothing_time (kCoM_stance, kZMP_stance, smoothingTime) are needed."""
+        and k_com_stance, k_zmp_stance and zmp_smoothing_time (kCoM_stance, kZMP_stance, smoothingTime) are needed.
+        planned_trajectories: every tick follows the planner's feet, twists, contact flags and CoM height (upload(left_traj=...)) instead of
+        the synthetic gait; needs kin (the FUSED hand-off) and neck_additional_rotation (additional_rotation of qpInverseKinematics.ini, 3 x 3)."""
         if dcm_controller not in ("mpc", "reactive"):
             raise ValueError(f"dcm_controller must be 'mpc' or 'reactive', not {dcm_controller!r}")
         self.reactive = dcm_controller == "reactive"
@@ -470,6 +475,14 @@ class TickPipeline:
             raise ValueError("ZMP gain scheduling needs k_com_stance, k_zmp_stance and zmp_smoothing_time")
         if self.gain_sched and not (np.isfinite(k_com_stance) and np.isfinite(k_zmp_stance) and np.isfinite(zmp_smoothing_time) and zmp_smoothing_time > 0):
             raise ValueError("ZMP gain scheduling needs finite stance gains and a finite zmp_smoothing_time > 0 (wcqp_tick_create: WCQP_E_INVALID)")
+        self.planned = bool(planned_trajectories)
+        if self.planned and neck_additional_rotation is None:
+            raise ValueError("planned trajectories need neck_additional_rotation (additional_rotation of qpInverseKinematics.ini)")
+        if self.planned and kin is None:
+            raise ValueError("planned trajectories need per-tick kinematics (kin=KinModel(...)): with constant Jacobians the feet never move")
+        neck = np.asarray(neck_additional_rotation if self.planned else np.eye(3), float).reshape(-1)
+        if neck.shape != (9,) or not np.all(np.isfinite(neck)):
+            raise ValueError("neck_additional_rotation must be a finite 3 x 3 matrix")
         self.batch, self.max_ticks, self.log_ticks, self.dof = batch, max_ticks, log_ticks, ik.dof
         self.logger_ticks = int(logger_ticks)
         self.use_kin = kin is not None
@@ -482,7 +495,7 @@ class TickPipeline:
                                  int(bool(external_feedback)), TICK_DCM_REACTIVE if self.reactive else TICK_DCM_MPC,
                                  float(k_dcm) if k_dcm is not None else 0.0, int(self.gain_sched),
                                  float(k_com_stance) if self.gain_sched else 0.0, float(k_zmp_stance) if self.gain_sched else 0.0,
-                                 float(zmp_smoothing_time) if self.gain_sched else 0.0)
+                                 float(zmp_smoothing_time) if self.gain_sched else 0.0, int(self.planned), (C.c_double * 9)(*neck))
         self._h = C.c_void_p()
         check(lib().wcqp_tick_create(C.byref(self.params), C.byref(self._h)), "wcqp_tick_create")
         self._keep = None
@@ -498,34 +511,56 @@ class TickPipeline:
         except Exception:
             pass
 
-    def upload(self, data: dict, dcm_vel_traj=None):
+    def upload(self, data: dict, dcm_vel_traj=None, left_traj=None, right_traj=None, left_twist=None, right_twist=None, contact=None,
+               com_height_traj=None, com_height_vel=None):
         """dcm_vel_traj: [B][max_ticks + N + 1][2], the planner's DCM velocity for the reactive controller and for ZMP gain scheduling
         (None: the forward difference of ref_traj); MPC handles without scheduling ignore it.  A reactive handle takes data without hull
-        tables."""
-        f64 = ("ref_traj", "state0", "swing_twist", "q0", "dcm0", "com0", "u_init")
+        tables.
+        Planned handles: left_traj / right_traj [B][T][12] (sole position, row-major rotation), left_twist / right_twist [B][T][6], contact
+        [B][T] (bit 0 left, bit 1 right in contact, bit 2 left is the fixed frame), com_height_traj / com_height_vel [B][T] or None,
+        T = max_ticks + N + 1; data then needs no phase0 / swing_twist."""
+        plan = dict(left_traj=left_traj, right_traj=right_traj, left_twist=left_twist, right_twist=right_twist, contact=contact)
+        if self.planned and any(v is None for v in plan.values()):
+            raise ValueError("a planned handle's upload needs " + ", ".join(k for k, v in plan.items() if v is None))
+        if not self.planned and any(v is not None for v in list(plan.values()) + [com_height_traj, com_height_vel]):
+            raise ValueError("planned trajectories were given to a handle created without planned_trajectories=True")
+        f64 = ("ref_traj", "state0", "q0", "dcm0", "com0", "u_init") + (() if self.planned else ("swing_twist",))
         f64 += () if self.use_kin else ("J_left", "J_right", "J_neck", "J_com")
         if not self.use_kin and (not self.reactive or "hull_tab_A" in data):
             f64 += ("hull_tab_A", "hull_tab_b")
         keep = {k: _f64(data[k]) for k in f64}
         if "hull_tab_A" in keep:
             keep["hull_tab_nc"] = np.ascontiguousarray(data["hull_tab_nc"], dtype=np.int32)
-        keep["phase0"] = np.ascontiguousarray(data["phase0"], dtype=np.int32)
+        if not self.planned or "phase0" in data:
+            keep["phase0"] = np.ascontiguousarray(data["phase0"], dtype=np.int32)
         assert keep["ref_traj"].shape == (self.batch, self.max_ticks + self.params.mpc.horizon + 1, 2), keep["ref_traj"].shape
         if dcm_vel_traj is not None:
             keep["dcm_vel_traj"] = _f64(dcm_vel_traj)
             assert keep["dcm_vel_traj"].shape == keep["ref_traj"].shape, keep["dcm_vel_traj"].shape
+        if self.planned:
+            T = keep["ref_traj"].shape[1]
+            for k, w in (("left_traj", 12), ("right_traj", 12), ("left_twist", 6), ("right_twist", 6)):
+                keep[k] = _f64(plan[k])
+                assert keep[k].shape == (self.batch, T, w), (k, keep[k].shape)
+            keep["contact"] = np.ascontiguousarray(contact, dtype=np.uint8)
+            assert keep["contact"].shape == (self.batch, T), keep["contact"].shape
+            for k, v in (("com_height_traj", com_height_traj), ("com_height_vel", com_height_vel)):
+                if v is not None:
+                    keep[k] = _f64(v)
+                    assert keep[k].shape == (self.batch, T), (k, keep[k].shape)
         ins = TickInputs(**{k: (keep[k].ctypes.data if k in keep else None) for k, _ in TickInputs._fields_})
         check(lib().wcqp_tick_upload(self._h, C.byref(ins)), "wcqp_tick_upload")
 
     def info(self) -> dict:
         """The form the handle took (wcqp_tick_get_info): kin_handoff ("fused", "compact", "dense" or None without kinematics),
-        ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick, zmp_gain_scheduling (bool)."""
+        ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick, zmp_gain_scheduling (bool), planned_trajectories (bool)."""
         i = TickInfo()
         check(lib().wcqp_tick_get_info(self._h, C.byref(i)), "wcqp_tick_get_info")
         return dict(kin_handoff={KIN_HANDOFF_NONE: None, KIN_HANDOFF_FUSED: "fused", KIN_HANDOFF_DENSE: "dense",
                                  KIN_HANDOFF_COMPACT: "compact"}[i.kin_handoff],
                     ticks_per_launch=int(i.ticks_per_launch), dcm_controller="reactive" if i.dcm_controller == TICK_DCM_REACTIVE else "mpc",
-                    launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling))
+                    launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling),
+                    planned_trajectories=bool(i.planned_trajectories))
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")

@@ -40,8 +40,9 @@
 #include "tick_device.h"
 #include "kin_device.h"
 
-// ik4_reactive.hip / ik4_zmp_gs.hip: this file compiled for the tick kernels of the reactive controller / of ZMP gain scheduling only
-#if defined(WCQP_IK4_REACTIVE_TU) || defined(WCQP_IK4_GS_TU)
+// ik4_reactive.hip / ik4_zmp_gs.hip / ik4_planned.hip: this file compiled for the tick kernels of the reactive controller / of ZMP gain
+// scheduling / of planned trajectories only
+#if defined(WCQP_IK4_REACTIVE_TU) || defined(WCQP_IK4_GS_TU) || defined(WCQP_IK4_PLAN_TU)
 #define WCQP_IK4_TICK_TU 1
 #endif
 
@@ -86,7 +87,9 @@ constexpr int PER_INST = 440;         // = 24 mod 32: the four instances of a wa
 // kernel's LDS-active cycles as bank conflicts.  The two spare doubles behind frames 16..21 hold the anchor pose (k_sd).
 constexpr int K_FS = 14, K_TW = 0, K_FRB = 322, K_FR = 358;          // joint frames, attached frames in base / world coordinates [3][12] each
 constexpr int K_MS = 394, K_MH = 410;                               // stashes: the MPC chain's per-axis records [2][8], its hull rows [8][3]
+constexpr int K_PF = 434;                                           // stash: the planner's contact flags of tick t + 1 (planned trajectories)
 __host__ __device__ constexpr int k_sd(int m) { return K_TW + (16 + (m >> 1)) * K_FS + 12 + (m & 1); }      // anchor pose [12] / CoM [3]
+static_assert(K_MH + 24 <= K_PF && K_PF < PER_INST, "the flags stash is clear of the others");
 static_assert(kDof * K_FS <= K_FRB && K_FR + 36 <= K_MS && K_MH + 24 <= PER_INST && k_sd(11) < kDof * K_FS && k_sd(0) >= 32 * 4, "kinematics scratch fits; the prefix sums [32][4] stay clear of the anchor pose");
 static_assert(OFF_CT + 24 * LDC + 2 <= A_SIZE && OFF_DB + 18 <= A_SIZE && OFF_PB + 12 * 18 <= A_SIZE, "LDS overlays");
 static_assert(OFF_ROWB + 16 <= PER_INST && OFF_DV + 16 <= PER_INST && (PER_INST % 32 == 24 || PER_INST % 32 == 8), "instances 16 banks apart");
@@ -173,7 +176,10 @@ struct MpcPairArgs {
 // (tick_device.h: tick_react_*) in the MPC's place - ik4_tick_reactive_kernel
 // GS (tick kernel, wcqp_tick_params.zmp_gain_scheduling): the chain of tick t + 1 advances the robot's gain smoother (tick_device.h:
 // zmp_*) and runs the ZMP-CoM law with the gains of that tick - ik4_tick_gs_kernel; td is then a TickDevGS
-template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false, bool REACT = false, bool GS = false>
+// PL (tick kernel with fused kinematics, wcqp_tick_params.planned_trajectories): desired feet, twists, CoM height, neck orientation, the
+// base anchor and the contact pair come from the planner's per-stage records (tick_device.h: plan_*) - ik4_tick_plan_kernel; td is then
+// a TickDevPL, and *gait holds the contact flags of tick t instead of the gait cycle index
+template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false, bool REACT = false, bool GS = false, bool PL = false>
 __device__ __forceinline__
 void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 const double* __restrict__ JL, const double* __restrict__ JR,
@@ -188,6 +194,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     static_assert(!(TICK && PAIR), "the tick kernel carries its own MPC chain");
     static_assert(TICK || !REACT, "the reactive controller is a tick form");
     static_assert(TICK || !GS, "gain scheduling is a tick form");
+    static_assert(!PL || (TICK && JSRC == 2 && !LOG && !EXT), "planned trajectories: the fused-kinematics tick of the internal plant");
     constexpr bool COMPACT = JSRC == 1;
     constexpr bool KINF = JSRC == 2;
     int lane_id = threadIdx.x;
@@ -269,6 +276,11 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     wcqp_tick::ZmpRegs zreg{};
     double m_s = 0.0;
     auto gsd = [&]() -> const wcqp_tick::TickDevGS& { return static_cast<const wcqp_tick::TickDevGS&>(td); };
+    // PL: the flags word of stage t + 1 (and the touch of its other lines), behind the chain's loads; reduced to an int in LDS before the
+    // kinematics phase.  (The last tick of a launch loads nothing: the next launch reads the flags of its first tick itself.)
+    auto pld = [&]() -> const wcqp_tick::TickDevPL& { return static_cast<const wcqp_tick::TickDevPL&>(td); };
+    double m_pf = 0.0;
+    if constexpr (PL) { if (do_mpc) m_pf = wcqp_tick::plan_flags_issue(pld(), j, inst, tick_now + 1); }
     if constexpr (TICK && GS) {
         if (do_mpc) {
             wcqp_tick::zmp_state_issue(gsd(), inst, zreg);
@@ -282,6 +294,8 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
         const double* sp = at32(state, so + j8);                                         // entry m * 16 + j of the block: this lane's offset + an immediate
         const double* sp5 = at32(state, so + 640u + (j < kStateLen - 80 ? j8 : 0u));     // entries 80 .. 86
         double sreg[6];
+        double2 p_r01 = make_double2(0.0, 0.0);   // PL: record entries 2j, 2j + 1 and 32 + (j & 7) of stage t
+        double p_r2 = 0.0;
         if constexpr (!KINF) {
 #pragma unroll
             for (int m = 0; m < 5; ++m) sreg[m] = sp[m * 16];
@@ -305,8 +319,10 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
             const double* hb_ = at32(td.hand.get(), ((unsigned)(tick_now & 1) * (unsigned)td.batch + iu) * (unsigned)(wcqp_tick::kHandLen * 8));
             const double* hd = at32(hb_, (unsigned)(j & 1) * 8u);
             g_pstar = hd[0]; g_vel = hd[2]; g_com = hd[4]; g_ok = hb_[8];
-            g_sw = *at32(td.swing_twist.get(), iu * 48u + (j < 6 ? j8 : 0u));
-            g_h0 = td.kin_mode ? *at32(td.com_h0.get(), iu * 8u) : td.com_height;
+            if constexpr (!PL) {          // (planned: twists and height come with the stage's record)
+                g_sw = *at32(td.swing_twist.get(), iu * 48u + (j < 6 ? j8 : 0u));
+                g_h0 = td.kin_mode ? *at32(td.com_h0.get(), iu * 8u) : td.com_height;
+            }
         };
         if constexpr (TICK && !KINF) load_handoff();
         // the state / q loads above must ISSUE before the 36 column loads (vmcnt retires in order): hipcc otherwise sinks
@@ -335,10 +351,14 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                     st2(ms, mreg.s01.x, mreg.s01.y); st2(ms + 2, mreg.s23.x, mreg.s23.y); st2(ms + 4, mreg.s45.x, mreg.s45.y); st2(ms + 6, mreg.s67.x, mreg.s67.y);
                 }
                 if (!REACT && j < 8) { double* mh = S + K_MH + j * 3; mh[0] = mreg.ha.x; mh[1] = mreg.ha.y; mh[2] = mreg.hb; }
+                if constexpr (PL) { const int f1 = wcqp_tick::plan_flags_of(m_pf); if (j == 0) S[K_PF] = (double)f1; }
             }
             WCQP_KSTAMP(1);          // MPC loads landed, partial sums stashed
-            const int side = *gait >= td.step_ticks ? 1 : 0;          // (gait: this robot's cycle index (tick + phase0) % (2 step_ticks), carried from tick to tick) 0: left is the stance foot
-            if (j < 12) S[k_sd(j)] = *at32(state, iu * (unsigned)(kStateLen * 8) + (unsigned)(24 + side * 12) * 8u + j8);                // desired pose of the anchor sole: p (3), R (9)
+            // PL: the planner's fixed-frame foot of tick t (*gait: its flags, carried from the tick before) anchors the base at its desired pose
+            // of stage t - the record's lines are in L2 since that tick touched them
+            const int side = PL ? wcqp_tick::plan_side(*gait) : (*gait >= td.step_ticks ? 1 : 0);          // (gait: this robot's cycle index (tick + phase0) % (2 step_ticks), carried from tick to tick) 0: left is the stance foot
+            if constexpr (PL) { if (j < 12) S[k_sd(j)] = wcqp_tick::plan_rec(pld(), inst, tick_now)[wcqp_tick::kPlanLeft + side * 12 + j]; }
+            else if (j < 12) S[k_sd(j)] = *at32(state, iu * (unsigned)(kStateLen * 8) + (unsigned)(24 + side * 12) * 8u + j8);                // desired pose of the anchor sole: p (3), R (9)
             const int cs[2] = {j, var1 ? col1 : 0};
             double* TW = S + K_TW;
             int kup[2][3], ksub[2];                 // the joints' pointer-jumping links and subtree ends: from the model table in LDS
@@ -666,12 +686,16 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 }
             } else if (do_mpc) {
                 // (hull rows in the MPC stash's place, just read back: the attached frames at 312..347 are still needed)
-                const int cyc1 = *gait + 1 == 2 * td.step_ticks ? 0 : *gait + 1;
-                const int code1 = wcqp_tick::contact_code_cyc(cyc1, td.step_ticks, td.ds_ticks);
-                if constexpr (KINF) wcqp_tick::tick_mpc_finish_from<false, GS>(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, m_uy, reinterpret_cast<double (*)[4]>(S + K_MS), code1, noise_base, kg);
+                int code1;
+                if constexpr (PL) code1 = wcqp_tick::plan_code((int)S[K_PF]);
+                else {
+                    const int cyc1 = *gait + 1 == 2 * td.step_ticks ? 0 : *gait + 1;
+                    code1 = wcqp_tick::contact_code_cyc(cyc1, td.step_ticks, td.ds_ticks);
+                }
+                if constexpr (KINF) wcqp_tick::tick_mpc_finish_from<false, GS, PL>(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, m_uy, reinterpret_cast<double (*)[4]>(S + K_MS), code1, noise_base, kg);
                 else wcqp_tick::tick_mpc_finish<false, false, GS>(td, j, inst, live, tick_now + 1, mreg, reinterpret_cast<double (*)[4]>(S + OFF_COL), nullptr, code1, noise_base, kg);
             }
-            if (j < 6) {
+            if (!PL && j < 6) {
                 const int code = wcqp_tick::contact_code_cyc(*gait, td.step_ticks, td.ds_ticks);
                 const double tw = g_sw * wcqp_tick::swing_profile_cyc(td, *gait);
                 g_twl = (code == 0 || code == 2) ? 0.0 : tw;
@@ -686,6 +710,12 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
         k_pos_foot = prm->k_pos_foot; k_att_foot = prm->k_att_foot; k_pos_com = prm->k_pos_com;
         kap = prm->kappa * (-prm->k_neck);
         fast_ok = prm->fast_ok;
+        if constexpr (PL) {
+            // the record of stage t: one coalesced 320-byte load over the robot's 16 lanes (L2: the tick before touched its lines), issued
+            // behind the chain of tick t + 1 rather than with the pose block - held across the MPC's finish its three doubles cost spills
+            const double* rc = wcqp_tick::plan_rec(pld(), inst, tick_now);
+            p_r01 = ld2(rc + 2 * j); p_r2 = rc[32 + (j & 7)];
+        }
 #pragma unroll
         for (int m = 0; m < 5; ++m) st[m * 16 + j] = sreg[m];
         st[80 + j] = sreg[5];        // unconditional (slots 87..95 are spare): a predicated store makes hipcc sink the LOAD into the branch, behind the column loads
@@ -703,8 +733,19 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
         if constexpr (TICK) {
             wcqp::wave_lds_fence();
             if (j < 2) { if (!td.kin_mode) st[66 + j] = g_com; st[69 + j] = g_pstar; st[72 + j] = g_vel; }
+            if constexpr (PL) {
+                // the planner's stage t over the pose block: desired feet, twists, CoM height and its velocity (WalkingModule.cpp:1085-1145,
+                // 689, 695), then the desired neck orientation from the two desired rotations
+                const int k0 = wcqp_tick::plan_state_index(2 * j), k1 = wcqp_tick::plan_state_index(2 * j + 1), k2 = wcqp_tick::plan_state_index(32 + j);
+                if (k0 >= 0) st[k0] = p_r01.x;
+                if (k1 >= 0) st[k1] = p_r01.y;
+                if (j < 8 && k2 >= 0) st[k2] = p_r2;
+                wcqp::wave_lds_fence();
+                if (j < 9) st[57 + j] = wcqp_tick::plan_neck(pld().pl.neck_add, j, st[27], st[30], st[39], st[42]);
+            } else {
             if (j < 6) { st[75 + j] = g_twl; st[81 + j] = g_twr; }
             if (j == 0) { if (!td.kin_mode) st[68] = g_h0; st[71] = g_h0; st[74] = 0.0; }      // tick_glue_height
+            }
         }
     }
     wcqp::wave_lds_fence();
@@ -1575,6 +1616,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
             }
             if (j == 0 && (!ik_ok || stopped)) td.ik_fail[i_] += 1;       // tick_post_instance without the contact pair: the MPC part derives its own
         }
+        if constexpr (PL) { if (do_mpc) *gait = (int)S[K_PF]; }          // the flags of tick t + 1 for the next tick (the walk carries them)
         WCQP_STAMP(14);
     }
     if (ferr_out) {
@@ -1652,7 +1694,7 @@ __device__ __forceinline__ int xcd_group(int b, int groups) {
 // kmodel / kgains: the LDS the kernel declares for the kinematic model and (MPC, fused kinematics) the MPC's gain blocks.
 // (No __restrict__ on these parameters: the kernel's own carry it, and repeating it here changes the MPC kernels' code - their
 // SGPR spills grow by 10 to 18.)
-template <int JSRC, bool LOG, bool EXT, bool REACT, bool GS = false>
+template <int JSRC, bool LOG, bool EXT, bool REACT, bool GS = false, bool PL = false>
 __device__ __forceinline__
 void ik4_tick_walk(const IkDeviceParams* prm, int batch,
                    const double* JL, const double* JR,
@@ -1683,7 +1725,8 @@ void ik4_tick_walk(const IkDeviceParams* prm, int batch,
             const long ir = (long)blockIdx.x * 4 + (lane_ >> 4);
             const long i_ = ir < batch ? ir : (long)batch - 1;
             const bool v1_ = j_ < kDof - 16;
-            gait = (t0 + td.phase0[i_]) % (2 * td.step_ticks);
+            if constexpr (PL) gait = (int)wcqp_tick::plan_rec(static_cast<const wcqp_tick::TickDevPL&>(td), i_, t0)[wcqp_tick::kPlanFlags];      // the flags of the first tick
+            else gait = (t0 + td.phase0[i_]) % (2 * td.step_ticks);
             nbase = wcqp_tick::disturbance_base(td.seed, (unsigned long long)(td.first + i_));
             carry[0] = td.q_des[i_ * kDof + j_]; carry[1] = td.q_des[i_ * kDof + (v1_ ? j_ + 16 : 0)];
             carry[2] = td.dq_prev[i_ * kDof + j_]; carry[3] = td.dq_prev[i_ * kDof + (v1_ ? j_ + 16 : 0)];
@@ -1691,9 +1734,9 @@ void ik4_tick_walk(const IkDeviceParams* prm, int batch,
 #pragma unroll 1
         for (int k = 0; k < n_inner; ++k) {
             __asm__ volatile("" ::: "memory");        // nothing of the body is hoisted out of the loop (its registers are all spoken for)
-            ik4_body<true, JSRC, false, LOG, EXT, REACT, GS>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out, td, smem,
+            ik4_body<true, JSRC, false, LOG, EXT, REACT, GS, PL>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out, td, smem,
                                              (int)blockIdx.x, t0 + k, !(skip_last_mpc && k == n_inner - 1), kmodel, kgains, nullptr, carry, &gait, &nbase);
-            gait = gait + 1 == 2 * td.step_ticks ? 0 : gait + 1;
+            if constexpr (!PL) gait = gait + 1 == 2 * td.step_ticks ? 0 : gait + 1;
             // tick t + 1 of this wave reads what tick t wrote (other lanes of the same wave): visible before it starts
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
@@ -1751,7 +1794,7 @@ void ik4_tick_reactive_kernel(const IkDeviceParams* __restrict__ prm, int batch,
     ik4_tick_walk<JSRC, LOG, EXT, true>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out,
                                         tdp, phase, n_inner, skip_last_mpc, smem, kmodel, nullptr);
 }
-#else
+#elif defined(WCQP_IK4_GS_TU)
 // The tick kernels with ZMP-CoM gain scheduling (wcqp_tick_params.zmp_gain_scheduling), either controller: the walk of
 // ik4_kernel<true, JSRC, LOG, EXT> / ik4_tick_reactive_kernel<JSRC, LOG, EXT> with the smoother advanced in the chain of every tick
 template <int JSRC, bool LOG, bool EXT, bool REACT>
@@ -1769,6 +1812,25 @@ void ik4_tick_gs_kernel(const IkDeviceParams* __restrict__ prm, int batch,
     __shared__ __attribute__((aligned(16))) double kgains[JSRC == 2 && !REACT ? 4 * wcqp_tick::kGainsLdsStages : 2];
     ik4_tick_walk<JSRC, LOG, EXT, REACT, true>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out,
                                                tdp, phase, n_inner, skip_last_mpc, smem, kmodel, REACT ? nullptr : kgains);
+}
+#else
+// The tick kernels with planned trajectories (wcqp_tick_params.planned_trajectories): the fused-kinematics walk of ik4_kernel<true, 2> /
+// ik4_tick_reactive_kernel<2> / ik4_tick_gs_kernel<2, false, false, REACT> with the planner's records in the synthetic gait's place
+template <bool REACT, bool GS>
+__global__ __launch_bounds__(64, WCQP_IK4_WAVES)
+void ik4_tick_plan_kernel(const IkDeviceParams* __restrict__ prm, int batch,
+                          const double* __restrict__ JL, const double* __restrict__ JR,
+                          const double* __restrict__ JN, const double* __restrict__ JC,
+                          const double* qpos, const double* __restrict__ state,
+                          double* __restrict__ dq_out, int* __restrict__ status_out,
+                          unsigned* __restrict__ alo_out, unsigned* __restrict__ aup_out,
+                          double* __restrict__ ferr_out, int* __restrict__ iters_out, const wcqp_tick::TickDev* __restrict__ tdp, int phase, int n_inner, int skip_last_mpc)
+{
+    __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
+    __shared__ __attribute__((aligned(16))) double kmodel[wcqp_tick::kKinTabSize];
+    __shared__ __attribute__((aligned(16))) double kgains[!REACT ? 4 * wcqp_tick::kGainsLdsStages : 2];
+    ik4_tick_walk<2, false, false, REACT, GS, true>(prm, batch, JL, JR, JN, JC, qpos, state, dq_out, status_out, alo_out, aup_out, ferr_out, iters_out,
+                                                    tdp, phase, n_inner, skip_last_mpc, smem, kmodel, REACT ? nullptr : kgains);
 }
 #endif
 
@@ -1803,7 +1865,7 @@ void tick_reactive_prime_kernel(wcqp_tick::TickDev td, int t)
     wcqp_tick::tick_react_issue(td, j, inst, t, mreg, r0, rd);
     wcqp_tick::tick_react_finish<EXT>(td, j, inst, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd));
 }
-#else
+#elif defined(WCQP_IK4_GS_TU)
 // The chain of one tick with gain scheduling for every robot, on its own (primes ik4_tick_gs_kernel): the smoother state and the velocity
 // stage loaded with the chain's other loads, setPhase, then the controller's finish with the tick's gains
 template <bool EXT, bool REACT>
@@ -1824,6 +1886,35 @@ void tick_gs_prime_kernel(wcqp_tick::TickDevGS td, int t)
     const double2 kg = wcqp_tick::zmp_gains_at(td, td.zg, wcqp_tick::zmp_smoother_advance(td, inst, j == 0 && live, rd, zreg));
     if constexpr (REACT) wcqp_tick::tick_react_finish<EXT, true>(td, j, inst, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd), nullptr, kg);
     else wcqp_tick::tick_mpc_finish<false, EXT, true>(td, j, inst, live, t, mreg, s_hull[grp], nullptr, -1, nullptr, kg);
+}
+#else
+// The chain of one tick with planned trajectories for every robot, on its own (primes ik4_tick_plan_kernel): the contact pair from the
+// planner's flags of tick t (a change rebuilds the hull rows from its desired feet), with or without gain scheduling
+template <bool REACT, bool GS>
+__global__ __launch_bounds__(64)
+void tick_plan_prime_kernel(wcqp_tick::TickDevPL td, int t)
+{
+    __shared__ __attribute__((aligned(16))) double s_hull[4][WCQP_HULL_ROWS][4];
+    const int lane = threadIdx.x, grp = lane >> 4, j = lane & 15;
+    const long inst_raw = (long)blockIdx.x * 4 + grp;
+    const bool live = inst_raw < td.batch;
+    const long inst = live ? inst_raw : (long)td.batch - 1;
+    wcqp_tick::TickMpcRegs mreg;
+    wcqp_tick::ZmpRegs zreg;
+    double2 r0, rd = make_double2(0.0, 0.0);
+    if constexpr (REACT) wcqp_tick::tick_react_issue(td, j, inst, t, mreg, r0, rd);
+    else {
+        wcqp_tick::tick_mpc_issue(td, j, inst, t, mreg);
+        if constexpr (GS) rd = wcqp_tick::zmp_vel_issue(td, inst, t);
+    }
+    const int code = wcqp_tick::plan_code((int)wcqp_tick::plan_rec(td, inst, t)[wcqp_tick::kPlanFlags]);
+    double2 kg = make_double2(0.0, 0.0);
+    if constexpr (GS) {
+        wcqp_tick::zmp_state_issue(td, inst, zreg);
+        kg = wcqp_tick::zmp_gains_at(td, td.zg, wcqp_tick::zmp_smoother_advance(td, inst, j == 0 && live, rd, zreg));
+    }
+    if constexpr (REACT) wcqp_tick::tick_react_finish<false, GS>(td, j, inst, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd), nullptr, kg);
+    else wcqp_tick::tick_mpc_finish<false, false, GS, true>(td, j, inst, live, t, mreg, s_hull[grp], nullptr, code, nullptr, kg);
 }
 #endif
 
@@ -2045,7 +2136,7 @@ static void tick_kernel_launch(bool /*react*/, const IkDeviceParams* prm, int ba
                        io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters,
                        td_dev, phase, n_inner, skip_last_mpc);
 }
-#else
+#elif defined(WCQP_IK4_GS_TU)
 // ... or ik4_tick_gs_kernel of either controller (ik4_zmp_gs.hip: a code object of its own for the same reason)
 template <int JSRC, bool LOG = false, bool EXT = false>
 static void tick_kernel_launch(bool react, const IkDeviceParams* prm, int batch, const IkIo& io, const wcqp_tick::TickDev* td_dev, int phase,
@@ -2061,6 +2152,7 @@ static void tick_kernel_launch(bool react, const IkDeviceParams* prm, int batch,
 }
 #endif
 
+#if !defined(WCQP_IK4_PLAN_TU)
 // the tick kernel of a handle's form (checked by ik4_launch_tick)
 static int ik4_launch_tick_forms(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
                                  int n_inner, int skip_last_mpc, hipStream_t stream) {
@@ -2084,6 +2176,7 @@ static int ik4_launch_tick_forms(const IkDeviceParams* prm, const wcqp_tick::Tic
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
+#endif
 
 #ifndef WCQP_IK4_TICK_TU
 int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
@@ -2125,7 +2218,7 @@ int ik4_launch_tick_prime_reactive(const wcqp_tick::TickDev& td, int t, hipStrea
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }
-#else
+#elif defined(WCQP_IK4_GS_TU)
 int ik4_launch_tick_gs(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
                        int n_inner, int skip_last_mpc, hipStream_t stream) {
     return ik4_launch_tick_forms(prm, td, td_dev, io, n_inner, skip_last_mpc, stream);
@@ -2141,6 +2234,38 @@ int ik4_launch_tick_prime_gs(const wcqp_tick::TickDevGS& td, int t, hipStream_t 
     } else {
         if (td.q_meas) hipLaunchKernelGGL((tick_gs_prime_kernel<true, false>), dim3(grid), dim3(64), 0, stream, td, t);
         else hipLaunchKernelGGL((tick_gs_prime_kernel<false, false>), dim3(grid), dim3(64), 0, stream, td, t);
+    }
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+#else
+// planned trajectories (ik4_planned.hip: a code object of its own, so that the kernels of the other three keep their code and places):
+// the fused-kinematics skewed kernel of the handle's controller, with or without gain scheduling (td_dev: a TickDevPL)
+int ik4_launch_tick_plan(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                         int n_inner, int skip_last_mpc, hipStream_t stream) {
+    if (!prm || !td_dev || n_inner < 1 || !td.skew || !td.kin_fused || !td.kin_tab || !td.kin_mode || td.logger_ticks > 0 || td.q_meas) return WCQP_E_INVALID;
+    if (td.kin_rounds < 0 || td.kin_rounds > 3 || (!td.reactive && td.horizon >= wcqp_tick::kGainsLdsStages)) return WCQP_E_INVALID;
+    if ((td.reactive || td.gain_sched) && !td.dcm_vel) return WCQP_E_INVALID;
+    const dim3 grid((unsigned)((td.batch + 3) / 4));
+#define WCQP_PLAN_LAUNCH(R, G) hipLaunchKernelGGL((ik4_tick_plan_kernel<R, G>), grid, dim3(64), 0, stream, prm, td.batch, io.JL, io.JR, io.JN, io.JC, io.q, io.state, \
+                                                   io.dq, io.status, io.alo, io.aup, io.ferr, io.iters, td_dev, td.phase, n_inner, skip_last_mpc)
+    if (td.reactive) { if (td.gain_sched) WCQP_PLAN_LAUNCH(true, true); else WCQP_PLAN_LAUNCH(true, false); }
+    else { if (td.gain_sched) WCQP_PLAN_LAUNCH(false, true); else WCQP_PLAN_LAUNCH(false, false); }
+#undef WCQP_PLAN_LAUNCH
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+
+// the planned chain of tick t alone (see tick_plan_prime_kernel)
+int ik4_launch_tick_prime_plan(const wcqp_tick::TickDevPL& td, int t, hipStream_t stream) {
+    if (!td.skew || !td.mst || !td.hand || !td.pl.rec || ((td.reactive || td.gain_sched) && !td.dcm_vel) || (td.gain_sched && !td.zg.zs)) return WCQP_E_INVALID;
+    const unsigned grid = (unsigned)((td.batch + 3) / 4);
+    if (td.reactive) {
+        if (td.gain_sched) hipLaunchKernelGGL((tick_plan_prime_kernel<true, true>), dim3(grid), dim3(64), 0, stream, td, t);
+        else hipLaunchKernelGGL((tick_plan_prime_kernel<true, false>), dim3(grid), dim3(64), 0, stream, td, t);
+    } else {
+        if (td.gain_sched) hipLaunchKernelGGL((tick_plan_prime_kernel<false, true>), dim3(grid), dim3(64), 0, stream, td, t);
+        else hipLaunchKernelGGL((tick_plan_prime_kernel<false, false>), dim3(grid), dim3(64), 0, stream, td, t);
     }
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;

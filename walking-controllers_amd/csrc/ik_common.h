@@ -371,7 +371,7 @@ int ik3_launch_list(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipS
 
 }  // namespace wcqp_ik
 
-namespace wcqp_tick { struct TickDev; struct TickDevGS; }
+namespace wcqp_tick { struct TickDev; struct TickDevGS; struct TickDevPL; }
 namespace wcqp_ik {
 // the 16-lane kernel with the tick pipeline's glue and post steps fused in (tick.hip)
 // io: the tick's Jacobians, q_des, state, dq, ik_status and previous active sets (ferr: the logger's foot errors, or NULL)
@@ -404,6 +404,11 @@ int ik4_launch_tick_prime_reactive(const wcqp_tick::TickDev& td, int t, hipStrea
 int ik4_launch_tick_gs(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
                        int n_inner, int skip_last_mpc, hipStream_t stream);
 int ik4_launch_tick_prime_gs(const wcqp_tick::TickDevGS& td, int t, hipStream_t stream);
+// the same two with planned trajectories (ik4_planned.hip): the fused-kinematics skewed kernel of either controller, with or without gain
+// scheduling; td_dev then points to a TickDevPL (tick.hip calls these for a planned handle in place of the two above)
+int ik4_launch_tick_plan(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+                         int n_inner, int skip_last_mpc, hipStream_t stream);
+int ik4_launch_tick_prime_plan(const wcqp_tick::TickDevPL& td, int t, hipStream_t stream);
 // the 16-lane tick kernel with gain scheduling (ik3.hip: the glue advances the smoother)
 int ik3_launch_tick_gs(const void* d_prm, const wcqp_tick::TickDevGS& td, const IkIo& io, hipStream_t stream);
 }  // namespace wcqp_ik

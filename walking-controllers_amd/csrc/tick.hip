@@ -82,6 +82,21 @@ __global__ void tick_vel_diff_kernel(TickDev d, int from, int to) {
     const_cast<double*>(d.dcm_vel.get())[w] = (d.ref_traj[w + 2] - d.ref_traj[w]) / d.dT;
 }
 
+// planned trajectories: the support-polygon rows of every contact change (tick_device.h: PlanDev), one thread per set - the corners of
+// the feet in contact at the set's stage (its record's desired poses) hulled by the builder of hull.hip
+struct PlanRect { double v[8]; };
+__global__ void plan_hull_sets_kernel(int n, PlanRect rect, const double* __restrict__ rec, const long long* __restrict__ at,
+                                      const int* __restrict__ code, double* __restrict__ A, double* __restrict__ b, int* __restrict__ nc) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const double* r = rec + at[g];
+    double px[8], py[8];
+    int np = 0;
+    if (code[g] == 0 || code[g] == 2) wcqp_hull::foot_points(rect.v, r + kPlanLeft, px, py, np);
+    if (code[g] == 1 || code[g] == 2) wcqp_hull::foot_points(rect.v, r + kPlanRight, px, py, np);
+    nc[g] = wcqp_hull::hull_rows(px, py, np, A + (size_t)g * 16, b + (size_t)g * 8);
+}
+
 // external feedback: the caller's measured state into the places the next tick reads its plant state from - the skewed
 // chain's per-axis records (mst: com [2], dcm [6], measured ZMP [7]) - and the measured joints into q_meas (NULL: the desired ones)
 __global__ void tick_feedback_kernel(TickDev d, const double* __restrict__ dcm, const double* __restrict__ com, const double* __restrict__ zmp,
@@ -155,6 +170,11 @@ struct wcqp_tick_s {
     ZmpSched zg{};                // zmp_gain_scheduling (d.gain_sched): the stance gains, the smoother, its per-robot state
     // the handle's TickDev with the scheduling record behind it (what the scheduled kernels take)
     TickDevGS dgs(const TickDev& base) const { TickDevGS g; static_cast<TickDev&>(g) = base; g.zg = zg; return g; }
+    // planned_trajectories: the per-stage records and what the planned kernels take (the scheduling record behind it, used or not)
+    bool planned = false;
+    PlanDev pl{};
+    double* set_A = nullptr; double* set_b = nullptr; int* set_nc = nullptr;     // the row sets of the last upload (PlanDev::set_*)
+    TickDevPL dpl(const TickDev& base) const { TickDevPL g; static_cast<TickDevGS&>(g) = dgs(base); g.pl = pl; return g; }
 };
 
 namespace {
@@ -195,6 +215,8 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
     const wcqp_ik::IkIo io{h->J_left, h->J_right, h->J_neck, h->J_com, d.q_des, d.state, d.dq, d.ik_status, h->ik_lo, h->ik_up,
                            h->log_ferr, nullptr};
     // base-eliminated IK kernel: IK + post step of this tick and MPC + glue + plant of the NEXT one in ONE launch (skewed tick)
+    if (h->planned)
+        return wcqp_ik::ik4_launch_tick_plan(static_cast<const wcqp_ik::IkDeviceParams*>(wcqp::ik_device_params(h->ik)), d, h->d_dev, io, n_inner, skip_last_mpc, s);
     if (h->form == TickForm::SKEWED)
         return wcqp_ik::ik4_launch_tick(wcqp::ik_device_params(h->ik), d, h->d_dev, io, n_inner, skip_last_mpc, s);
     const bool gs = d.gain_sched != 0;
@@ -231,6 +253,19 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (gs && (!std::isfinite(params->k_com_stance) || !std::isfinite(params->k_zmp_stance) || !std::isfinite(params->zmp_smoothing_time) ||
                !(params->zmp_smoothing_time > 0.0)))
         return WCQP_E_INVALID;
+    // planned trajectories: the fused-kinematics skewed tick of the default IK kernel and the internal plant, without logger rows (what can
+    // be told from the parameters alone is refused here, before anything touches the device; the tree and the route below, before the
+    // tick's allocations)
+    const bool planned = params->planned_trajectories != 0;
+    if (params->planned_trajectories != 0 && params->planned_trajectories != 1) return WCQP_E_INVALID;
+    if (planned) {
+        for (int k = 0; k < 9; ++k) if (!std::isfinite(params->neck_additional_rotation[k])) return WCQP_E_INVALID;
+        const int alg = params->ik.algorithm;
+        if (!params->use_kinematics || params->kin_handoff != WCQP_KIN_HANDOFF_FUSED || params->logger_ticks > 0 ||
+            params->plant != WCQP_TICK_PLANT_INTERNAL || (alg != WCQP_IK_ALG_DEFAULT && alg != WCQP_IK_ALG_BASE_ELIM) ||
+            (params->dcm_controller == WCQP_TICK_DCM_MPC && params->mpc.horizon >= kGainsLdsStages))
+            return WCQP_E_UNSUPPORTED;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         std::fprintf(stderr, "[wcqp] no HIP device: the tick pipeline has no CPU fallback\n");
@@ -247,8 +282,18 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (rc == WCQP_OK && params->use_kinematics) {
         if (params->kin.dof != kDof) rc = WCQP_E_UNSUPPORTED;
         if (rc == WCQP_OK) rc = wcqp_kin_create(&params->kin, &h->kin);
-        if (rc == WCQP_OK) rc = wcqp::kin_prepare(h->kin);
     }
+    if (rc == WCQP_OK && planned) {
+        // planned trajectories where FUSED would not be taken - another IK route (CoM as a cost, say) or a tree the fused kernel cannot
+        // walk: refused from the handles' host state, before any device allocation (the prepare calls below are the first)
+        unsigned m3[3];
+        int cs_ = 0, cd_ = 0, rounds = 0;
+        std::vector<double> tab;
+        if (wcqp::ik_route(h->ik) != wcqp::IkRoute::BASE_ELIM || !h->kin || !wcqp::kin_compact_layout(h->kin, m3, &cs_, &cd_) ||
+            !wcqp::kin_fused_tables(h->kin, tab, &rounds))
+            rc = WCQP_E_UNSUPPORTED;
+    }
+    if (rc == WCQP_OK && h->kin) rc = wcqp::kin_prepare(h->kin);
     if (rc == WCQP_OK && !reactive) rc = wcqp::mpc_prepare(h->mpc);
     if (rc == WCQP_OK) rc = wcqp::ik_prepare(h->ik);
     if (rc != WCQP_OK) { wcqp_tick_destroy(h); return rc; }
@@ -301,6 +346,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     const bool compact = masks_ok && !fusedk && params->kin_handoff != WCQP_KIN_HANDOFF_DENSE;
     // external feedback: the default (base-eliminated) kernel with constant Jacobians or fused kinematics, without logger rows
     if (h->external && (!d.skew || params->logger_ticks > 0 || (h->kin && !fusedk))) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }
+    if (planned && (!d.skew || !fusedk)) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }      // (checked above, before any allocation)
     if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); }
     if (reactive) { d.reactive = 1; d.k_dcm = params->k_dcm; }
     // the DCM velocity: the reactive controller's input, and with gain scheduling the stance flag's (MPC handles then read it too)
@@ -310,6 +356,13 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
         h->zg.k_com_st = params->k_com_stance; h->zg.k_zmp_st = params->k_zmp_stance;
         wcqp::zmp_smoother_coeffs(params->zmp_smoothing_time, params->mpc.sampling_time, h->zg.nb, h->zg.na);
         A_(h->zg.zs, B * 4);
+    }
+    if (planned) {
+        // the records, [B][traj_len][kPlanRec] (64-bit sizes: 8192 robots x 1251 stages is 3.3 GB)
+        double* rec = nullptr;
+        A_(rec, B * (size_t)d.traj_len * kPlanRec);
+        h->planned = true; h->pl.rec = rec;
+        for (int k = 0; k < 9; ++k) h->pl.neck_add[k] = params->neck_additional_rotation[k];
     }
     if (d.skew) {
         A_(d.mst, B * 16); A_(d.hand, 2 * B * kHandLen); A_(d.live_A, B * 16); A_(d.live_b, B * 8); A_(d.live_nc, B); A_(d.sel_built, B);
@@ -344,7 +397,14 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
 #ifdef WCQP_TICK_STAMPS
     if (d.skew && dev_alloc(h, &d.stamps, ((B + 3) / 4) * 16) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
 #endif
-    if (d.skew && gs) {
+    if (h->planned) {
+        // the planned kernels read the TickDevPL behind the pointer
+        TickDevPL* dp = nullptr;
+        if (dev_alloc(h, &dp, 1) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
+        const TickDevPL g = h->dpl(d);
+        if (hipMemcpy(dp, &g, sizeof(TickDevPL), hipMemcpyHostToDevice) != hipSuccess) { wcqp_tick_destroy(h); return WCQP_E_HIP; }
+        h->d_dev = dp;
+    } else if (d.skew && gs) {
         // the scheduled kernels read the TickDevGS behind the pointer
         TickDevGS* dg = nullptr;
         if (dev_alloc(h, &dg, 1) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
@@ -364,6 +424,7 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     if (h->graph) (void)hipGraphDestroy(h->graph);
     for (void* p : h->allocs) (void)hipFree(p);
+    for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
     if (h->splice_stage) (void)hipFree(h->splice_stage);
     if (h->splice_done) (void)hipEventDestroy(h->splice_done);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -374,14 +435,109 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     return WCQP_OK;
 }
 
+// planned trajectories: the caller's per-stage arrays checked over the stages a run can reach (0 .. max_ticks), before anything of the
+// handle changes
+static int validate_plan(const wcqp_tick_s* h, const wcqp_tick_inputs* in) {
+    const TickDev& d = h->d;
+    const size_t B = (size_t)d.batch, T = (size_t)d.traj_len, reach = (size_t)h->p.max_ticks + 1;
+    if (!in->left_traj || !in->right_traj || !in->left_twist || !in->right_twist || !in->contact) return WCQP_E_INVALID;
+    for (size_t i = 0; i < B; ++i)
+        for (size_t t = 0; t < reach; ++t) {
+            const size_t w = i * T + t;
+            const unsigned f = in->contact[w];
+            if ((f & 3u) == 0u) return WCQP_E_INVALID;                          // neither foot in contact
+            if ((f & 4u) ? !(f & 1u) : !(f & 2u)) return WCQP_E_INVALID;        // the fixed-frame foot is not in contact
+            bool ok = true;
+            for (int k = 0; k < 12; ++k) ok = ok && std::isfinite(in->left_traj[w * 12 + k]) && std::isfinite(in->right_traj[w * 12 + k]);
+            for (int k = 0; k < 6; ++k) ok = ok && std::isfinite(in->left_twist[w * 6 + k]) && std::isfinite(in->right_twist[w * 6 + k]);
+            if (in->com_height_traj) ok = ok && std::isfinite(in->com_height_traj[w]);
+            if (in->com_height_vel) ok = ok && std::isfinite(in->com_height_vel[w]);
+            if (!ok) return WCQP_E_INVALID;
+        }
+    return WCQP_OK;
+}
+
+// ... repacked into the records (tick_device.h: kPlanRec), a slab of robots at a time, and the support-polygon row set of every change of
+// contact pair (and of stage 0) built from its stage's desired feet; the records name the set in force
+static int upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in) {
+    const TickDev& d = h->d;
+    const size_t B = (size_t)d.batch, T = (size_t)d.traj_len, reach = (size_t)h->p.max_ticks + 1;
+    std::vector<long long> set_at;       // record offset (doubles) of each set's stage
+    std::vector<int> set_code;           // its contact pair (0 left, 1 right, 2 both)
+    std::vector<double> set_of(B * T);   // the set in force at each stage
+    for (size_t i = 0; i < B; ++i) {
+        int prev = -1;
+        for (size_t t = 0; t < T; ++t) {
+            const int pair = (int)(in->contact[i * T + t] & 3u);
+            if (t < reach && pair != prev) {       // (beyond the reach no tick changes the pair: the last set stays)
+                set_at.push_back((long long)((i * T + t) * kPlanRec));
+                set_code.push_back(pair - 1);
+                prev = pair;
+            }
+            set_of[i * T + t] = (double)(set_at.size() - 1);
+        }
+    }
+    const size_t slab = 256;
+    std::vector<double> rec(slab * T * kPlanRec);
+    for (size_t i0 = 0; i0 < B; i0 += slab) {
+        const size_t n = B - i0 < slab ? B - i0 : slab;
+        for (size_t i = i0; i < i0 + n; ++i) {
+            const double h0 = in->state0[i * kStateLen + 68];
+            for (size_t t = 0; t < T; ++t) {
+                const size_t w = i * T + t;
+                double* r = &rec[((i - i0) * T + t) * kPlanRec];
+                r[kPlanFlags] = (double)in->contact[w];
+                r[kPlanHeight] = in->com_height_traj ? in->com_height_traj[w] : h0;
+                r[kPlanHeightVel] = in->com_height_vel ? in->com_height_vel[w] : 0.0;
+                std::memcpy(r + kPlanLeft, in->left_traj + w * 12, 96); std::memcpy(r + kPlanRight, in->right_traj + w * 12, 96);
+                std::memcpy(r + kPlanTwL, in->left_twist + w * 6, 48); std::memcpy(r + kPlanTwL + 6, in->right_twist + w * 6, 48);
+                r[kPlanHull] = set_of[w];
+            }
+        }
+        WCQP_HIP_TRY(hipMemcpy(const_cast<double*>(h->pl.rec.get()) + i0 * T * kPlanRec, rec.data(), n * T * kPlanRec * 8, hipMemcpyHostToDevice));
+    }
+    // the row sets: the previous upload's go, the new ones are built on the device from the records just copied
+    for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
+    h->set_A = nullptr; h->set_b = nullptr; h->set_nc = nullptr;
+    const size_t ns = set_at.size();
+    long long* d_at = nullptr; int* d_code = nullptr;
+    int rc = WCQP_OK;
+    if (hipMalloc(reinterpret_cast<void**>(&h->set_A), ns * 128) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&h->set_b), ns * 64) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&h->set_nc), ns * 4) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_at), ns * 8) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d_code), ns * 4) != hipSuccess)
+        rc = WCQP_E_NOMEM;
+    if (rc == WCQP_OK && (hipMemcpy(d_at, set_at.data(), ns * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(d_code, set_code.data(), ns * 4, hipMemcpyHostToDevice) != hipSuccess))
+        rc = WCQP_E_HIP;
+    if (rc == WCQP_OK) {
+        PlanRect r;
+        for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
+        hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((ns + 127) / 128)), dim3(128), 0, 0, (int)ns, r, h->pl.rec.get(), d_at, d_code,
+                           h->set_A, h->set_b, h->set_nc);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = WCQP_E_HIP;
+    }
+    (void)hipFree(d_at); (void)hipFree(d_code);
+    if (rc != WCQP_OK) return rc;
+    // the kernels read the sets through the handle's TickDevPL in device memory
+    h->pl.set_A = h->set_A; h->pl.set_b = h->set_b; h->pl.set_nc = h->set_nc;
+    const TickDevPL g = h->dpl(d);
+    WCQP_HIP_TRY(hipMemcpy(h->d_dev, &g, sizeof(TickDevPL), hipMemcpyHostToDevice));
+    return WCQP_OK;
+}
+
 int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     if (!h || !in) return WCQP_E_INVALID;
-    if (!in->ref_traj || !in->phase0 || !in->state0 || !in->swing_twist || !in->q0 || !in->dcm0 || !in->com0 || !in->u_init) return WCQP_E_INVALID;
+    // (planned trajectories: no synthetic gait - phase0 and swing_twist may be NULL)
+    if (!in->ref_traj || !in->state0 || !in->q0 || !in->dcm0 || !in->com0 || !in->u_init) return WCQP_E_INVALID;
+    if (!h->planned && (!in->phase0 || !in->swing_twist)) return WCQP_E_INVALID;
+    if (h->planned) { const int rcv = validate_plan(h, in); if (rcv != WCQP_OK) return rcv; }
     if (!h->kin && (!in->J_left || !in->J_right || !in->J_neck || !in->J_com)) return WCQP_E_INVALID;
     // (the reactive controller reads no hull rows)
     if (!h->kin && !h->d.reactive && (!in->hull_tab_A || !in->hull_tab_b || !in->hull_tab_nc)) return WCQP_E_INVALID;
     TickDev& d = h->d;
     const size_t B = (size_t)d.batch;
+    // from here on the device state changes: a call that fails on the way leaves the handle unrunnable until the next good upload
+    h->uploaded = false;
     WCQP_HIP_TRY(hipDeviceSynchronize());
 #define UP_(dst, src, n) WCQP_HIP_TRY(hipMemcpy(const_cast<void*>(static_cast<const void*>(dst)), (src), (n), hipMemcpyHostToDevice))
     UP_(d.ref_traj, in->ref_traj, B * d.traj_len * 16);
@@ -401,7 +557,14 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
             UP_(d.dcm_vel, vel.data(), B * d.traj_len * 16);
         }
     }
-    UP_(d.phase0, in->phase0, B * 4); UP_(d.swing_twist, in->swing_twist, B * 48);
+    if (h->planned) {
+        const int rcp = upload_plan(h, in);
+        if (rcp != WCQP_OK) return rcp;
+        WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
+        WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
+    } else {
+        UP_(d.phase0, in->phase0, B * 4); UP_(d.swing_twist, in->swing_twist, B * 48);
+    }
     if (d.skew) {
         // state of the MPC chain per axis: c_ref, v_ref_prev, com, u_prev (= measured ZMP), p_star, v_star_prev, dcm, spare
         std::vector<double> mst(B * 16, 0.0);
@@ -427,7 +590,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
         UP_(h->J_neck, in->J_neck, B * 3 * 29 * 8); UP_(h->J_com, in->J_com, B * 3 * 29 * 8);
     }
     UP_(d.state, in->state0, B * kStateLen * 8); UP_(d.q_des, in->q0, B * kDof * 8);
-    if (h->kin) {
+    if (h->kin && !h->planned) {     // (planned: the live rows are built from the records at the first tick - sel_built = -1)
         // setConvexHullConstraint (...PredictiveController.cpp:364-435) for the three contact pairs, from the DESIRED foot
         // poses just uploaded (the planned footsteps, WalkingModule.cpp:609-613): the MPC of a tick selects its rows by the pair
         const int rch = wcqp::hull_tables_from_state((int)B, h->p.foot_rect, d.state, kStateLen, const_cast<double*>(d.hull_tab_A.get()),
@@ -445,6 +608,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     {   // contact pair of tick 0 (later ticks: tick_post_kernel)
         std::vector<int> sel(B);
         for (size_t i = 0; i < B; ++i) {
+            if (h->planned) { sel[i] = (int)(in->contact[i * d.traj_len] & 3u) - 1; continue; }
             const int cyc = in->phase0[i] % (2 * d.step_ticks), sidx = cyc % d.step_ticks;
             sel[i] = sidx < d.ds_ticks ? 2 : cyc / d.step_ticks;
         }
@@ -508,7 +672,8 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     if (h->d.skew) {
         // the fused launch of tick t carries IK(t) and MPC(t+1): the MPC of the call's first tick goes first, on its own, and
         // the call's LAST tick does not run the MPC of the tick after it - between calls nothing is ahead of anything
-        const int rc = h->d.gain_sched ? wcqp_ik::ik4_launch_tick_prime_gs(h->dgs(h->d), h->ticks_enqueued, s)
+        const int rc = h->planned ? wcqp_ik::ik4_launch_tick_prime_plan(h->dpl(h->d), h->ticks_enqueued, s)
+                     : h->d.gain_sched ? wcqp_ik::ik4_launch_tick_prime_gs(h->dgs(h->d), h->ticks_enqueued, s)
                                        : wcqp_ik::ik4_launch_tick_prime(h->d, h->ticks_enqueued, s);
         if (rc != WCQP_OK) return rc;
     }
@@ -565,6 +730,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
 
 int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stages, const double* ref_tail, void* stream) {
     if (!h || !h->uploaded || !ref_tail || n_stages < 1) return WCQP_E_INVALID;
+    if (h->planned) return WCQP_E_UNSUPPORTED;           // (planned trajectories: the splice has no tail for the feet)
     const TickDev& d = h->d;
     // stages the ticks already enqueued have consumed as their own reference DCM stay as they are; everything a later
     // tick's window can see may change
@@ -620,6 +786,7 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
     out->ticks_per_launch = h->ticks_per_launch;
     out->dcm_controller = d.reactive ? WCQP_TICK_DCM_REACTIVE : WCQP_TICK_DCM_MPC;
     out->zmp_gain_scheduling = d.gain_sched ? 1 : 0;
+    out->planned_trajectories = h->planned ? 1 : 0;
     // a kinematics launch unless fused; then the skewed kernel (1), MPC / reactive + the 16-lane kernel (2) or controller, glue, IK, post (4)
     out->launches_per_tick = (h->kin && !d.kin_fused ? 1 : 0) + (h->form == TickForm::SKEWED ? 1 : h->form == TickForm::MPC_IK16 ? 2 : 4);
     return WCQP_OK;

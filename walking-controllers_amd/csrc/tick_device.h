@@ -106,6 +106,27 @@ struct ZmpSched {
 // A scheduled handle's TickDev: the scheduled kernels that take it by value take this one, the skewed ones read it from device memory.
 // The kernels that know nothing of scheduling keep their TickDev (and their code).
 struct TickDevGS : TickDev { ZmpSched zg; };
+// ---- planned-trajectory mode (wcqp_tick_params.planned_trajectories): what the planner's deques hold at front() on tick t, repacked at
+// upload (tick.hip) into ONE record of kPlanRec doubles per robot and stage - 320 bytes, five 64-byte lines:
+//   [0] contact flags (bit 0 left, bit 1 right in contact, bit 2 left is the fixed frame)   [1] desired CoM height   [2] its velocity
+//   [3..14] left sole pose (p 3 | R 9 row-major)   [15..26] right sole pose   [27..32] left twist   [33..38] right twist
+//   [39] the index of the support-polygon row set in force at this stage (PlanDev::set_*)
+// Records 3..38 are the pose block's entries 24..47 and 75..86 in order.  The desired neck orientation is not stored: the tick forms it
+// from the two rotations (plan_neck), three square roots, six divisions and a few multiply-adds against 9 more doubles (a sixth line) per robot and tick.
+constexpr int kPlanRec = 40;
+constexpr int kPlanFlags = 0, kPlanHeight = 1, kPlanHeightVel = 2, kPlanLeft = 3, kPlanRight = 15, kPlanTwL = 27, kPlanHull = 39;
+// The support polygons follow from the planner's data alone: the upload finds every stage whose contact pair differs from the stage before
+// (and stage 0), builds that stage's rows from its desired feet with the hull builder of hull_device.h (tick.hip: plan_hull_sets_kernel),
+// and writes the index of the set into every record.  A tick whose pair changes copies its set into the live rows, as the synthetic gait
+// copies one of its three - no hull builder inside the tick kernel.
+struct PlanDev {
+    wcqp::GPtr<const double> rec;    // [B][traj_len][kPlanRec], indexed with 64-bit offsets (8192 robots x 1251 stages: 3.3 GB)
+    double neck_add[9];              // wcqp_tick_params.neck_additional_rotation
+    wcqp::GPtr<const double> set_A; wcqp::GPtr<const double> set_b; wcqp::GPtr<const int> set_nc;   // [sets][8][2], [sets][8], [sets]
+};
+// A planned handle's TickDev (the scheduling record included, used or not): the planned kernels read it from device memory or take it
+// by value (the prime kernel); every other kernel keeps its TickDev.
+struct TickDevPL : TickDevGS { PlanDev pl; };
 constexpr int kHandLen = 14;
 constexpr int kLoggerCols = 53;
 constexpr int kKinTabJoint = 22, kKinTabInts = 19, kKinTabFrames = kKinTabJoint * kDof, kKinTabRoot = kKinTabFrames + 36, kKinTabSize = kKinTabRoot + 6;
@@ -169,6 +190,40 @@ __device__ __forceinline__ double disturbance_from(unsigned long long base, int 
     return (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
 }
 
+// ---- planned-trajectory mode (TickDevPL): the record of robot inst at stage t (64-bit offsets: no wcqp::at32 - the array passes 4 GB)
+__device__ __forceinline__ const double* plan_rec(const TickDevPL& d, long inst, int t) {
+    return d.pl.rec.get() + ((size_t)inst * (size_t)d.traj_len + (size_t)t) * (size_t)kPlanRec;
+}
+// The contact flags of stage t (lanes 0 and 5..15) - and, on lanes 1..4, the first word of the record's lines 1..4: the tick of stage
+// t - 1 issues this with the chain's loads, and all five lines of the record are in L2 when the tick of stage t reads it.  Every lane's
+// value is consumed (plan_flags_of: the row's broadcast reads all of them), so the extra words are not dropped as dead loads.
+__device__ __forceinline__ double plan_flags_issue(const TickDevPL& d, int j, long inst, int t) {
+    return plan_rec(d, inst, t)[(j >= 1 && j <= 4) ? 8 * j : kPlanFlags];
+}
+__device__ __forceinline__ int plan_flags_of(double v) {
+    return (int)__shfl(v, (int)(threadIdx.x & ~15u));
+}
+// contact pair code of the flags (0 left, 1 right, 2 both; the upload refuses a stage with neither foot in contact), and the side of
+// the fixed-frame foot (0: left anchors the floating base, WalkingModule::updateFKSolver, WM/src/WalkingModule.cpp:1147-1165)
+__device__ __forceinline__ int plan_code(int flags) { return (flags & 3) - 1; }
+__device__ __forceinline__ int plan_side(int flags) { return (flags & 4) ? 0 : 1; }
+// where record entry k goes in the pose block (-1: nowhere)
+__device__ __forceinline__ int plan_state_index(int k) {
+    return k == kPlanHeight ? 71 : (k == kPlanHeightVel ? 74 : (k < kPlanLeft ? -1 : (k < kPlanTwL ? k + 21 : (k < kPlanTwL + 12 ? k + 48 : -1))));
+}
+// Entry m < 9 of the desired neck orientation RotZ(atan2(sin yL + sin yR, cos yL + cos yR)) * neck_add with yaw_f = atan2(R10, R00) of
+// foot f's desired rotation (WalkingModule.cpp:697-707, :383; WalkingQPInverseKinematics.cpp:143-146) - without transcendentals:
+// cos / sin of atan2(y, x) are x / |(x, y)| and y / |(x, y)|, and (1, 0) where atan2 meets (0, 0)
+__device__ __forceinline__ double plan_neck(const double* neck_add, int m, double l00, double l10, double r00, double r10) {
+    const double hl = sqrt(l00 * l00 + l10 * l10), hr = sqrt(r00 * r00 + r10 * r10);
+    const double cl = hl > 0.0 ? l00 / hl : 1.0, sl = hl > 0.0 ? l10 / hl : 0.0;
+    const double cr = hr > 0.0 ? r00 / hr : 1.0, sr = hr > 0.0 ? r10 / hr : 0.0;
+    const double cs = cl + cr, ss = sl + sr, hh = sqrt(cs * cs + ss * ss);
+    const double cy = hh > 0.0 ? cs / hh : 1.0, sy = hh > 0.0 ? ss / hh : 0.0;
+    const int r = m / 3, c = m - 3 * r;
+    const double a0 = neck_add[c], a1 = neck_add[3 + c];
+    return r == 0 ? cy * a0 - sy * a1 : (r == 1 ? sy * a0 + cy * a1 : neck_add[6 + c]);
+}
 __device__ __forceinline__ int contact_code(int t, int phase0, int step_ticks, int ds_ticks) {
     const int cyc = (t + phase0) % (2 * step_ticks);
     const int s = cyc % step_ticks, side = cyc / step_ticks;
@@ -391,7 +446,9 @@ __device__ __forceinline__ void tick_mpc_partial(const TickDev& d, int j, long i
 // r0: stage 0 of the window (the reference DCM of tick t; meaningful on lane 0)
 // EXT (external feedback: only tick_mpc_prime_kernel<true> - with such a handle every tick's MPC runs there): the measured ZMP is the
 // caller's (record entry 7), not the previous command; the kernels of the internal plant keep entry 7 out of their registers
-template <bool EXT = false, bool GS = false>
+// PL (planned trajectories): code_known is the pair of the planner's flags, and a change of pair copies the row set the stage's record
+// names (PlanDev::set_*, built at upload from the stage's desired feet) instead of one of the three-set table; d is then a TickDevPL
+template <bool EXT = false, bool GS = false, bool PL = false>
 __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, long inst, bool live, int t, TickMpcRegs& R, double2 r0, double ux, double uy,
                                                      double (*s_hull)[4], int code_known = -1, const unsigned long long* noise_base = nullptr,
                                                      double2 kg = double2{}) {
@@ -400,7 +457,19 @@ __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, lo
     const int code = code_known >= 0 ? code_known : contact_code(t, R.phase0, d.step_ticks, d.ds_ticks);
     const bool stale = code != R.built;
     if (__ballot(stale) != 0ull) {
-        if (stale && live) {
+        if constexpr (PL) {
+            if (stale && live) {
+                const TickDevPL& dp = static_cast<const TickDevPL&>(d);
+                const long hset = (long)plan_rec(dp, inst, t)[kPlanHull];
+                double* lA = d.live_A + inst * (2 * WCQP_HULL_ROWS);
+                double* lb = d.live_b + inst * WCQP_HULL_ROWS;
+                if (j < WCQP_HULL_ROWS) {
+                    reinterpret_cast<double2*>(lA)[j] = reinterpret_cast<const double2*>(dp.pl.set_A.get())[hset * WCQP_HULL_ROWS + j];
+                    lb[j] = dp.pl.set_b[hset * WCQP_HULL_ROWS + j];
+                }
+                if (j == 0) { d.live_nc[inst] = dp.pl.set_nc[hset]; d.sel_built[inst] = code; }
+            }
+        } else if (stale && live) {
             double* lA = d.live_A + inst * (2 * WCQP_HULL_ROWS);
             double* lb = d.live_b + inst * WCQP_HULL_ROWS;
             const long hset = inst * 3 + code;
@@ -442,13 +511,13 @@ __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, lo
         tick_chain_step<EXT, GS>(d, ax, inst, t, R, rr, u, mpc_ok, noise_base, kg);
     }
 }
-template <bool GAINS_LDS = false, bool EXT = false, bool GS = false>
+template <bool GAINS_LDS = false, bool EXT = false, bool GS = false, bool PL = false>
 __device__ __forceinline__ void tick_mpc_finish(const TickDev& d, int j, long inst, bool live, int t, TickMpcRegs& R, double (*s_hull)[4],
                                                 const double* gr_lds = nullptr, int code_known = -1, const unsigned long long* noise_base = nullptr,
                                                 double2 kg = double2{}) {
     double ux, uy;
     tick_mpc_partial<GAINS_LDS>(d, j, inst, t, R, gr_lds, ux, uy);
-    tick_mpc_finish_from<EXT, GS>(d, j, inst, live, t, R, R.L.r[0], ux, uy, s_hull, code_known, noise_base, kg);
+    tick_mpc_finish_from<EXT, GS, PL>(d, j, inst, live, t, R, R.L.r[0], ux, uy, s_hull, code_known, noise_base, kg);
 }
 // the same two with the gait cycle index cyc = (t + phase0) % (2 step_ticks) at hand (the tick kernel carries it from tick to tick:
 // integer divisions by run-time values are ~35 instructions each, and a tick had four of them, on every lane)

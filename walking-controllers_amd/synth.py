@@ -467,3 +467,124 @@ def synth_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_batch: dic
                 dcm0=np.ascontiguousarray(dcm0),
                 # the plant's CoM starts where the robot's own (kinematic) CoM is
                 com0=np.ascontiguousarray(state0[:, o["com"]:o["com"] + 2].copy()), u_init=np.ascontiguousarray(zmp[:, 0].copy()))
+
+
+def _min_jerk(s):
+    """position, d/ds of the minimum-jerk profile 10 s^3 - 15 s^4 + 6 s^5 on [0, 1]"""
+    return s ** 3 * (10.0 - 15.0 * s + 6.0 * s * s), 30.0 * s * s * (1.0 - s) ** 2
+
+
+def synth_planned_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_batch: dict, seed: int = 4242, horizon: int = 50,
+                             first: int = 0, step_ticks: int = 180, ds_ticks: int = 110, n_steps: int = 4, step_length=(0.025, 0.035),
+                             yaw_step=(0.0, 0.0), lift: float = 0.02, dT: float = 0.01, com_height: float = 0.53, gravity: float = 9.81) -> dict:
+    """Inputs of the tick pipeline in planned-trajectory mode (`TickPipeline(planned_trajectories=True, kin=...)`): a seeded walk that goes
+    somewhere.  `kin_batch` / `poses` as for synth_walk_batch (the desired feet start at the actual ones).  After a first double support of
+    ds_ticks, n_steps steps of step_ticks each - single support (the swing foot lifted by `lift` and moved along a minimum-jerk profile),
+    then double support - carry the swing foot `step_length` [m] (drawn per robot) ahead of the stance foot along the walking direction,
+    which turns by `yaw_step` [rad] (drawn per robot) per step; the right foot swings first, and the robot stands for the rest.
+
+      left_traj / right_traj [B][T][12]   sole pose (position, row-major rotation), T = n_ticks + horizon + 1
+      left_twist / right_twist [B][T][6]  the analytic derivative of that pose (linear velocity, angular velocity about z)
+      contact [B][T]                      bit 0 / 1: left / right in contact; bit 2: the left foot is the fixed frame (the stance foot of the
+                                          last single support; the left one before the first)
+      ref_traj / dcm_vel_traj [B][T][2]   the DCM reference by the backward recursion of _dcm_reference from the footsteps' ZMP plan (on the
+                                          stance foot's ZMP point in single support, linear between the two in double support) and its
+                                          velocity omega (xi - zmp)
+    plus what synth_walk_batch returns (state0 with the desired neck orientation at the mean-yaw formula of the first stage, q0, dcm0,
+    com0, u_init, zmp_ref) and `goal` [B][2][12], the final planned poses, and `distance` [B], how far the feet's midpoint travels."""
+    rng = CounterRNG(seed ^ 0x57E95, first, count)
+    T = n_ticks + horizon + 1
+    o = IK_STATE_OFFSETS
+    ss = step_ticks - ds_ticks
+    L = step_length[0] + (step_length[1] - step_length[0]) * rng.uniform(1)[:, 0]
+    dyaw = yaw_step[0] + (yaw_step[1] - yaw_step[0]) * rng.uniform(1)[:, 0]
+    state0 = np.array(poses, dtype=np.float64, copy=True)
+    for src, dst, k in (("p_left", "pd_left", 3), ("R_left", "Rd_left", 9), ("p_right", "pd_right", 3), ("R_right", "Rd_right", 9)):
+        state0[:, o[dst]:o[dst] + k] = state0[:, o[src]:o[src] + k]
+    feet = np.zeros((count, 2, T, 12)); tw = np.zeros((count, 2, T, 6))
+    contact = np.zeros((count, T), np.uint8)
+    zmp_pt = np.zeros((count, 2, T, 2))        # each foot's ZMP point per stage (leftZMPDelta / rightZMPDelta in the foot frame)
+    delta = ((0.03, -0.005), (0.03, 0.005))
+    Tz = T + 4 * step_ticks
+    stance = np.zeros((count, Tz), np.int64)    # side of the ZMP plan: 0 left, 1 right, -1 double support towards `nxt`
+    for i in range(count):
+        p = [state0[i, o["pd_left"]:o["pd_left"] + 3].copy(), state0[i, o["pd_right"]:o["pd_right"] + 3].copy()]
+        R = [state0[i, o["Rd_left"]:o["Rd_left"] + 9].reshape(3, 3).copy(), state0[i, o["Rd_right"]:o["Rd_right"] + 9].reshape(3, 3).copy()]
+        heading = np.arctan2(R[0][1, 0] + R[1][1, 0], R[0][0, 0] + R[1][0, 0])
+        half_w = 0.5 * np.linalg.norm((p[0] - p[1])[:2])
+        mid = 0.5 * (p[0] + p[1])
+        fixed = 0
+        seq = []          # per stage: (pose of both feet, twists, flags)
+        for t in range(T):
+            k = (t - ds_ticks) // step_ticks if t >= ds_ticks else -1
+            s_in = (t - ds_ticks) % step_ticks if t >= ds_ticks else 0
+            pos = [p[0].copy(), p[1].copy()]; rot = [R[0].copy(), R[1].copy()]; twist = [np.zeros(6), np.zeros(6)]
+            flags = 3
+            if 0 <= k < n_steps and s_in < ss:
+                sw = 1 - (k % 2)                  # the right foot (1) swings first
+                st = 1 - sw
+                # the step's target: the swing foot step_length ahead of the stance foot, the heading turned by dyaw
+                h1 = heading + dyaw[i]
+                fwd = np.array([np.cos(h1), np.sin(h1), 0.0]); lat = np.array([-np.sin(h1), np.cos(h1), 0.0])
+                p_target = p[st] + L[i] * fwd + (2 * half_w) * lat * (1.0 if sw == 0 else -1.0)
+                p_target[2] = p[sw][2]
+                yaw0 = np.arctan2(R[sw][1, 0], R[sw][0, 0])
+                yaw1 = yaw0 + dyaw[i]
+                x = (s_in + 1) / float(ss)        # the foot lands on the last stage of the single support
+                m, dm = _min_jerk(x)
+                lz = 16.0 * x * x * (1.0 - x) ** 2; dlz = 32.0 * x * (1.0 - x) * (1.0 - 2.0 * x)
+                pos[sw] = p[sw] + (p_target - p[sw]) * m + np.array([0.0, 0.0, lift * lz])
+                rot[sw] = _rotz(np.array([(yaw1 - yaw0) * m]))[0] @ R[sw]
+                v = ((p_target - p[sw]) * dm + np.array([0.0, 0.0, lift * dlz])) / (ss * dT)
+                twist[sw] = np.concatenate([v, [0.0, 0.0, (yaw1 - yaw0) * dm / (ss * dT)]])
+                flags = 1 if sw == 1 else 2
+                fixed = st
+                if s_in == ss - 1:                # touch-down: the new footprint
+                    p[sw] = pos[sw].copy(); p[sw][2] = p_target[2]; R[sw] = rot[sw].copy()
+                    heading = h1
+                    mid = 0.5 * (p[0] + p[1])
+            flags |= 4 if fixed == 0 else 0
+            for f in range(2):
+                feet[i, f, t, :3] = pos[f]; feet[i, f, t, 3:] = rot[f].reshape(9); tw[i, f, t] = twist[f]
+                zmp_pt[i, f, t] = pos[f][:2] + rot[f][:2, :2] @ np.asarray(delta[f])
+            contact[i, t] = flags
+    # ZMP plan: single support on the stance foot's point, double support linear from the last stance foot to the next one
+    zmp = np.zeros((count, Tz, 2))
+    for i in range(count):
+        fl = np.concatenate([contact[i], np.full(Tz - T, contact[i, -1])])
+        zp = np.concatenate([zmp_pt[i], np.repeat(zmp_pt[i][:, -1:], Tz - T, axis=1)], axis=1)
+        t = 0
+        while t < Tz:
+            if fl[t] & 3 != 3:
+                side = 0 if fl[t] & 1 else 1
+                zmp[i, t] = zp[side, t]; t += 1
+                continue
+            t1 = t
+            while t1 < Tz and fl[t1] & 3 == 3:
+                t1 += 1
+            prev_side = (0 if fl[t - 1] & 1 else 1) if t > 0 else None
+            next_side = (0 if fl[t1] & 1 else 1) if t1 < Tz else None
+            for u in range(t, t1):
+                a = zp[prev_side, u] if prev_side is not None else 0.5 * (zp[0, u] + zp[1, u])
+                b = zp[next_side, u] if next_side is not None else 0.5 * (zp[0, u] + zp[1, u])
+                lam = (u - t + 1) / float(t1 - t + 1)
+                zmp[i, u] = a + lam * (b - a)
+            t = t1
+    omega = np.sqrt(gravity / com_height)
+    a = np.exp(omega * dT); b = 1.0 - a
+    xi = np.zeros((count, Tz, 2))
+    xi[:, -1] = zmp[:, -1]
+    for t in range(Tz - 2, -1, -1):
+        xi[:, t] = (xi[:, t + 1] - b * zmp[:, t]) / a
+    ref = np.ascontiguousarray(xi[:, :T]); zmp = np.ascontiguousarray(zmp[:, :T])
+    vel = np.ascontiguousarray(omega * (ref - zmp))
+    # the desired neck orientation of the first stage (planned mode recomputes it every tick; state0's copy is what the synthetic gait uses)
+    left = np.ascontiguousarray(feet[:, 0]); right = np.ascontiguousarray(feet[:, 1])
+    start_mid = 0.5 * (left[:, 0, :2] + right[:, 0, :2]); end_mid = 0.5 * (left[:, -1, :2] + right[:, -1, :2])
+    dcm0 = ref[:, 0, :] + rng.normal(2, 0.002)
+    return dict(first=first, ref_traj=ref, dcm_vel_traj=vel, zmp_ref=zmp, state0=np.ascontiguousarray(state0),
+                q0=np.ascontiguousarray(kin_batch["q"]), dcm0=np.ascontiguousarray(dcm0),
+                com0=np.ascontiguousarray(state0[:, o["com"]:o["com"] + 2].copy()), u_init=np.ascontiguousarray(zmp[:, 0].copy()),
+                left_traj=left, right_traj=right, left_twist=np.ascontiguousarray(tw[:, 0]), right_twist=np.ascontiguousarray(tw[:, 1]),
+                contact=np.ascontiguousarray(contact), goal=np.stack([left[:, -1], right[:, -1]], 1),
+                distance=np.linalg.norm(end_mid - start_mid, axis=1))
