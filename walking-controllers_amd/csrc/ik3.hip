@@ -138,16 +138,14 @@ int ik3_launch_list(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipS
     return ik3_launch_as<false, true>((unsigned)((batch + 63) / 64), d_prm, batch, io, wcqp_tick::TickDev{}, stream);
 }
 
-int ik3_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const IkIo& io, hipStream_t stream) {
+// the tick form: ik3_kernel<true, false>, or with gain scheduling ik3_tick_gs_kernel
+int ik3_launch_tick(const void* d_prm, const wcqp_tick::TickDevGS& td, const IkIo& io, hipStream_t stream) {
     if (!d_prm) return WCQP_E_INVALID;
-    return ik3_launch_as<true, false>((unsigned)((td.batch + 3) / 4), static_cast<const IkDeviceParams*>(d_prm), td.batch, io, td, stream);
-}
-
-int ik3_launch_tick_gs(const void* d_prm, const wcqp_tick::TickDevGS& td, const IkIo& io, hipStream_t stream) {
-    if (!d_prm || !td.gain_sched || !td.dcm_vel || !td.zg.zs) return WCQP_E_INVALID;
+    const IkDeviceParams* prm = static_cast<const IkDeviceParams*>(d_prm);
+    if (!td.gain_sched) return ik3_launch_as<true, false>((unsigned)((td.batch + 3) / 4), prm, td.batch, io, td, stream);
+    if (!td.dcm_vel || !td.zg.zs) return WCQP_E_INVALID;
     hipLaunchKernelGGL((ik3_tick_gs_kernel<true, false, true>), dim3((unsigned)((td.batch + 3) / 4)), dim3(64), 0, stream,
-                       static_cast<const IkDeviceParams*>(d_prm), td.batch, io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status,
-                       io.alo, io.aup, io.ferr, io.iters, td);
+                       prm, td.batch, io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, io.ferr, io.iters, td);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }

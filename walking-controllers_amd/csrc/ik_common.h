@@ -373,18 +373,28 @@ int ik3_launch_list(const IkDeviceParams* d_prm, int batch, const IkIo& io, hipS
 
 namespace wcqp_tick { struct TickDev; struct TickDevGS; struct TickDevPL; }
 namespace wcqp_ik {
-// the 16-lane kernel with the tick pipeline's glue and post steps fused in (tick.hip)
+// the 16-lane kernel with the tick pipeline's glue and post steps fused in (tick.hip); with ZMP-CoM gain scheduling (td.gain_sched) its
+// scheduled form, whose glue advances the smoother
 // io: the tick's Jacobians, q_des, state, dq, ik_status and previous active sets (ferr: the logger's foot errors, or NULL)
-int ik3_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const IkIo& io, hipStream_t stream);
+int ik3_launch_tick(const void* d_prm, const wcqp_tick::TickDevGS& td, const IkIo& io, hipStream_t stream);
 int ik4_launch_pair(const IkDeviceParams* d_prm, int batch, const IkIo& io,
                     const wcqp_mpc::MpcDeviceConsts& c, const double* x0, const double* ref, int ref_len, const double* u_prev,
                     const double* hull_A, const double* hull_b, const int* hull_nc,
                     double* u0, int* mstatus, unsigned* mactive, double* mmargin, hipStream_t stream);
-// the base-eliminated kernel with the SKEWED tick fused in: IK(t) + post step of tick t and the MPC chain of tick t + 1
-// (tick_device.h); dense Jacobians, or the compact per-joint records of the tick's own kinematics kernel (td.compact)
-// n_inner: ticks per launch (> 1 only where the tick handle allows it); td_dev: the same TickDev in device memory (td.phase is
-// passed as a kernel argument, the copy's is not read)
-int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
+// The skewed tick a handle runs, resolved once at wcqp_tick_create (as the IK's route is at wcqp_ik_create): where the Jacobians come
+// from (jsrc: 0 the dense arrays, 1 the compact records of the tick's kinematics kernel, 2 the kinematics fused into the kernel), the
+// logger rows, external feedback (ext: not with logger rows), and the chain's features - the reactive DCM controller, ZMP-CoM gain
+// scheduling, planned trajectories.  Without a feature the kernels are ik4.hip's, with any the variant kernels of ik4_tick.hip.
+struct TickVariant {
+    int jsrc = 0;
+    bool log = false, ext = false;
+    bool react = false, gs = false, pl = false;
+    bool plain() const { return !react && !gs && !pl; }
+};
+// the base-eliminated kernel with the SKEWED tick fused in: IK(t) + post step of tick t and the chain of tick t + 1 (tick_device.h).
+// n_inner: ticks per launch (> 1 only where the tick handle allows it); td_dev: the same record in device memory (td.phase is passed as a
+// kernel argument, the copy's is not read)
+int ik4_launch_tick(const void* d_prm, const wcqp_tick::TickDevPL& td, const wcqp_tick::TickDev* td_dev, const TickVariant& v, const IkIo& io,
                     int n_inner, int skip_last_mpc, hipStream_t stream);
 // a plan of steps in ONE launch (wcqp_qp_plan_*): d_recs = the records in device memory
 int ik4_launch_plan(const IkDeviceParams* d_prm, int batch, const wcqp_qp_step* d_recs, int n_steps, int ways,
@@ -393,22 +403,6 @@ int ik4_plan_queue_grid(int batch, int n_steps);      // work-queue form (ways =
 // its ticket counters: kPlanQueues of them + the count of finished waves, kPlanQueueStride bytes apart, all zero between launches
 constexpr unsigned kPlanQueues = 32, kPlanQueueStride = 4352;
 constexpr size_t kPlanQueueBytes = (size_t)(kPlanQueues + 1) * kPlanQueueStride;
-// the MPC chain of tick t alone: primes the skewed tick after an upload
-int ik4_launch_tick_prime(const wcqp_tick::TickDev& td, int t, hipStream_t stream);
-// the same two with the REACTIVE DCM controller (ik4_reactive.hip; ik4_launch_tick / ik4_launch_tick_prime hand a reactive handle over)
-int ik4_launch_tick_reactive(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
-                             int n_inner, int skip_last_mpc, hipStream_t stream);
-int ik4_launch_tick_prime_reactive(const wcqp_tick::TickDev& td, int t, hipStream_t stream);
-// the same two with ZMP-CoM gain scheduling, either controller (ik4_zmp_gs.hip; ik4_launch_tick hands a scheduled handle over, td_dev then
-// points to a TickDevGS; tick.hip primes a scheduled handle with ik4_launch_tick_prime_gs)
-int ik4_launch_tick_gs(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
-                       int n_inner, int skip_last_mpc, hipStream_t stream);
-int ik4_launch_tick_prime_gs(const wcqp_tick::TickDevGS& td, int t, hipStream_t stream);
-// the same two with planned trajectories (ik4_planned.hip): the fused-kinematics skewed kernel of either controller, with or without gain
-// scheduling; td_dev then points to a TickDevPL (tick.hip calls these for a planned handle in place of the two above)
-int ik4_launch_tick_plan(const IkDeviceParams* prm, const wcqp_tick::TickDev& td, const wcqp_tick::TickDev* td_dev, const IkIo& io,
-                         int n_inner, int skip_last_mpc, hipStream_t stream);
-int ik4_launch_tick_prime_plan(const wcqp_tick::TickDevPL& td, int t, hipStream_t stream);
-// the 16-lane tick kernel with gain scheduling (ik3.hip: the glue advances the smoother)
-int ik3_launch_tick_gs(const void* d_prm, const wcqp_tick::TickDevGS& td, const IkIo& io, hipStream_t stream);
+// the chain of tick t alone: primes the skewed tick after an upload (each kernel takes the slice of td its variant reads)
+int ik4_launch_tick_prime(const wcqp_tick::TickDevPL& td, const TickVariant& v, int t, hipStream_t stream);
 }  // namespace wcqp_ik

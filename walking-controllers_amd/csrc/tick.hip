@@ -142,7 +142,8 @@ struct wcqp_tick_s {
     wcqp_mpc_t mpc = nullptr;
     wcqp_ik_t ik = nullptr;
     TickDev d{};
-    TickDev* d_dev = nullptr;     // copy of `d` in device memory (the fused kernel reads it from there, see ik4.hip)
+    TickDev* d_dev = nullptr;     // skewed tick: a TickDevPL of `d` in device memory (the fused kernels read it from there, see ik4_device.h)
+    wcqp_ik::TickVariant variant{};   // skewed tick: the kernels this handle runs (wcqp_tick_create)
     std::vector<void*> allocs;
     double *J_left = nullptr, *J_right = nullptr, *J_neck = nullptr, *J_com = nullptr;
     unsigned* mpc_active = nullptr; double* mpc_margin = nullptr;
@@ -215,10 +216,8 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
     const wcqp_ik::IkIo io{h->J_left, h->J_right, h->J_neck, h->J_com, d.q_des, d.state, d.dq, d.ik_status, h->ik_lo, h->ik_up,
                            h->log_ferr, nullptr};
     // base-eliminated IK kernel: IK + post step of this tick and MPC + glue + plant of the NEXT one in ONE launch (skewed tick)
-    if (h->planned)
-        return wcqp_ik::ik4_launch_tick_plan(static_cast<const wcqp_ik::IkDeviceParams*>(wcqp::ik_device_params(h->ik)), d, h->d_dev, io, n_inner, skip_last_mpc, s);
     if (h->form == TickForm::SKEWED)
-        return wcqp_ik::ik4_launch_tick(wcqp::ik_device_params(h->ik), d, h->d_dev, io, n_inner, skip_last_mpc, s);
+        return wcqp_ik::ik4_launch_tick(wcqp::ik_device_params(h->ik), h->dpl(d), h->d_dev, h->variant, io, n_inner, skip_last_mpc, s);
     const bool gs = d.gain_sched != 0;
     if (d.reactive) {
         hipLaunchKernelGGL(tick_reactive_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, s, d);
@@ -229,7 +228,7 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
         if (rc != WCQP_OK) return rc;
     }
     if (h->form == TickForm::MPC_IK16)
-        return gs ? wcqp_ik::ik3_launch_tick_gs(wcqp::ik_device_params(h->ik), h->dgs(d), io, s) : wcqp_ik::ik3_launch_tick(wcqp::ik_device_params(h->ik), d, io, s);
+        return wcqp_ik::ik3_launch_tick(wcqp::ik_device_params(h->ik), h->dgs(d), io, s);
     if (gs) hipLaunchKernelGGL(tick_glue_gs_kernel, dim3((B + 127) / 128), dim3(128), 0, s, h->dgs(d));
     else hipLaunchKernelGGL(tick_glue_kernel, dim3((B + 127) / 128), dim3(128), 0, s, d);
     const int rc = wcqp_ik_solve_device(h->ik, B, io.JL, io.JR, io.JN, io.JC, io.q, io.state, io.dq, io.status, io.alo, io.aup, nullptr, nullptr, s);
@@ -397,23 +396,18 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
 #ifdef WCQP_TICK_STAMPS
     if (d.skew && dev_alloc(h, &d.stamps, ((B + 3) / 4) * 16) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
 #endif
-    if (h->planned) {
-        // the planned kernels read the TickDevPL behind the pointer
+    if (d.skew) {
+        // the skewed kernels read the handle's TickDevPL behind the pointer, whatever the variant: the plain and reactive ones its TickDev,
+        // the scheduled ones its TickDevGS
         TickDevPL* dp = nullptr;
         if (dev_alloc(h, &dp, 1) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
         const TickDevPL g = h->dpl(d);
         if (hipMemcpy(dp, &g, sizeof(TickDevPL), hipMemcpyHostToDevice) != hipSuccess) { wcqp_tick_destroy(h); return WCQP_E_HIP; }
         h->d_dev = dp;
-    } else if (d.skew && gs) {
-        // the scheduled kernels read the TickDevGS behind the pointer
-        TickDevGS* dg = nullptr;
-        if (dev_alloc(h, &dg, 1) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
-        const TickDevGS g = h->dgs(d);
-        if (hipMemcpy(dg, &g, sizeof(TickDevGS), hipMemcpyHostToDevice) != hipSuccess) { wcqp_tick_destroy(h); return WCQP_E_HIP; }
-        h->d_dev = dg;
-    } else if (d.skew) {
-        if (dev_alloc(h, &h->d_dev, 1) != WCQP_OK) { wcqp_tick_destroy(h); return WCQP_E_NOMEM; }
-        if (hipMemcpy(h->d_dev, &d, sizeof(TickDev), hipMemcpyHostToDevice) != hipSuccess) { wcqp_tick_destroy(h); return WCQP_E_HIP; }
+        h->variant.jsrc = d.kin_fused ? 2 : d.compact ? 1 : 0;
+        h->variant.log = d.logger_ticks > 0;
+        h->variant.ext = d.q_meas && !h->variant.log;
+        h->variant.react = d.reactive != 0; h->variant.gs = d.gain_sched != 0; h->variant.pl = h->planned;
     }
     *out = h;
     return WCQP_OK;
@@ -672,9 +666,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     if (h->d.skew) {
         // the fused launch of tick t carries IK(t) and MPC(t+1): the MPC of the call's first tick goes first, on its own, and
         // the call's LAST tick does not run the MPC of the tick after it - between calls nothing is ahead of anything
-        const int rc = h->planned ? wcqp_ik::ik4_launch_tick_prime_plan(h->dpl(h->d), h->ticks_enqueued, s)
-                     : h->d.gain_sched ? wcqp_ik::ik4_launch_tick_prime_gs(h->dgs(h->d), h->ticks_enqueued, s)
-                                       : wcqp_ik::ik4_launch_tick_prime(h->d, h->ticks_enqueued, s);
+        const int rc = wcqp_ik::ik4_launch_tick_prime(h->dpl(h->d), h->variant, h->ticks_enqueued, s);
         if (rc != WCQP_OK) return rc;
     }
     // the fused kernel walks through several ticks per launch (the waves need no per-tick synchronisation): no graph needed
