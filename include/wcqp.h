@@ -588,6 +588,11 @@ typedef struct wcqp_tick_outputs {  /* HOST pointers, any may be NULL */
                                                          what the next tick's hot start begins from                               */
     double* zmp_gains;          /* [B][2] kCoM, kZMP the last executed tick used (zmp_gain_scheduling; without it k_com, k_zmp;
                                    after an upload, before any tick: the stance gains)                                            */
+    double* measured;           /* [B][6] EXTERNAL plant only: dcm xy, com xy, ZMP xy the last executed tick used as its measured state,
+                                   whichever feedback form set it (after an upload, before any tick: dcm0, com0, u_init).  Any other
+                                   handle: WCQP_E_UNSUPPORTED when non-NULL                                                       */
+    int64_t* feedback_fail;     /* [B] EXTERNAL plant only: sensor ticks rejected by wcqp_tick_set_sensor_feedback_* since the last
+                                   upload (0 without kinematics).  Any other handle: WCQP_E_UNSUPPORTED when non-NULL               */
 } wcqp_tick_outputs;
 
 typedef struct wcqp_tick_s* wcqp_tick_t;
@@ -626,6 +631,34 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
  * arrays may be released at once, and the tick may then be run on any stream, a non-blocking one included).  With the device form the
  * caller orders the copy kernel's stream before the stream of the run call (the same stream does). */
 int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const double* com_meas, const double* zmp_meas, const double* q_meas);
+/* Sensor feedback (EXTERNAL plant with per-tick kinematics): the counterpart of wcqp_tick_set_feedback_* that takes what a robot
+ * reports - WalkingModule::getFeedbacks (WM/src/WalkingModule.cpp:547) - and evaluates the measured state on the device, for tick
+ * t = the ticks run since the last upload.  DEVICE pointers: q_meas, dq_meas [B][dof] (rad, rad/s); wrench_left, wrench_right [B][6]
+ * fx fy fz tx ty tz in that foot's sole frame (iDynTree's Wrench order, as wholeBodyDynamics reports it).  Per robot:
+ *   1. updateFKSolver (:1147-1165): forward kinematics at q_meas with the floating base anchored so that tick t's stance sole sits on its
+ *      desired pose, world_T_base = world_T_sole,desired * (base_T_sole(q_meas))^-1 - the stance side and desired pose tick t's own
+ *      kinematics take: side ((t + phase0) % (2 step_ticks)) / step_ticks, pose from state0.
+ *   2. evaluateCoM / evaluateDCM (:1167-1217; WM/src/WalkingForwardKinematics.cpp:258-337): com = the total CoM, v_com = the joint
+ *      columns of the MIXED CoM Jacobian times dq_meas (the base twist is zero, WalkingFK::setInternalRobotState),
+ *      dcm = com_xy + v_com_xy / omega, omega = sqrt(mpc.gravity / mpc.com_height).
+ *   3. evaluateZMP (:826-878): a foot is defined when fz >= 0.001; its ZMP (-ty / fz, tx / fz, 0) in the sole frame is mapped to world by
+ *      that sole's pose of step 1; totalZ = fz_left + fz_right; zmp = xy of sum_f (fz_f defined_f / totalZ) zmp_f.
+ *   4. com, dcm, zmp xy and q_meas go where wcqp_tick_set_feedback_device puts them: tick t then runs as a plain EXTERNAL tick fed them.
+ *   5. A robot with totalZ < 0.1 (updateModule returns false there) or with any input that is not finite is REJECTED: it keeps the
+ *      measured state of tick t - 1 (tick 0: the uploaded one, with the desired joints), wcqp_tick_outputs.feedback_fail counts it, and it
+ *      is stopped like a robot whose IK failed: dq = 0 from tick t on.  Its ik_fail then counts the rejection (when it was not stopped
+ *      yet) and every tick it runs stopped, tick t included.  The other robots are unaffected.
+ * The low-pass filters of the reference (use_filters, use_joint_velocity_filter, use_wrench_filter) are not applied.  Marks the
+ * feedback of tick t as set, as wcqp_tick_set_feedback_device does; either form may feed any tick of a handle.  The device form enqueues
+ * one kernel on `stream` and retains nothing.  WCQP_E_INVALID for a NULL pointer or a handle that has not been uploaded;
+ * WCQP_E_UNSUPPORTED with the internal plant or without per-tick kinematics (use_kinematics = 0). */
+int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
+                                         const double* wrench_right, void* stream);
+/* the same from HOST pointers: staged in device memory the handle allocated at create, and IN PLACE when the call returns - it first
+ * waits for the handle's last wcqp_tick_run, whatever stream that named (a non-blocking one included); the host arrays may be released
+ * at once and the tick may run on any stream. */
+int wcqp_tick_set_sensor_feedback_host(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
+                                       const double* wrench_right);
 int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out);             /* synchronises     */
 
 /* The form a tick handle actually took at wcqp_tick_create (the route follows the IK algorithm, the kinematics hand-off and the

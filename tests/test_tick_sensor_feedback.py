@@ -1,0 +1,408 @@
+"""
+Sensor feedback of the tick pipeline (include/wcqp.h: wcqp_tick_set_sensor_feedback_*): joint encoders and the two feet's wrenches in,
+the measured CoM, DCM and ZMP the EXTERNAL tick reads evaluated on the device - updateFKSolver, evaluateCoM / evaluateDCM and evaluateZMP
+of WM/src/WalkingModule.cpp (:1147-1217, :826-878).  Checked against the numpy restatement tests/helpers/sensor_feedback.py (built on
+oracle/kin_spec.py) and, in closed loop, against oracle/tick_spec.run_ticks(external=...) fed the restated measurements.
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from helpers import sensor_feedback as sf
+from helpers import reactive_tick as rt
+from helpers import zmp_gains as zg
+from oracle import kin_spec as ks
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
+OMEGA = np.sqrt(9.81 / 0.53)
+K_DCM = 1.2                                      # iCubGazeboV2_5/dcmReactiveControllerParams.ini:1
+
+
+def _rot_z(a):
+    c, s = np.cos(a), np.sin(a)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU: the restatement
+def test_zmp_restatement_on_hand_built_wrenches():
+    """evaluateZMP (WalkingModule.cpp:826-878): one foot, both feet, a foot below the 0.001 threshold, totalZ around 0.1, a sole that is
+    rotated and translated."""
+    I = (np.zeros(3), np.eye(3))
+    shifted = (np.array([0.0, 0.1, 0.0]), np.eye(3))
+    wl = np.array([0.0, 0.0, 200.0, 4.0, -6.0, 0.0])          # left ZMP in the sole frame: (-ty / fz, tx / fz) = (0.03, 0.02)
+    wr = np.array([0.0, 0.0, 100.0, -2.0, 1.0, 0.0])          # right: (-0.01, -0.02)
+    zero = np.zeros(6)
+    z, ok = sf.zmp_world(wl, zero, I, shifted)                 # left only
+    assert ok and np.allclose(z, [0.03, 0.02], atol=1e-15)
+    z, ok = sf.zmp_world(zero, wr, I, shifted)                 # right only, its sole 0.1 m to the left
+    assert ok and np.allclose(z, [-0.01, 0.08], atol=1e-15)
+    z, ok = sf.zmp_world(wl, wr, I, shifted)                   # both: weighted by fz / totalZ
+    assert ok and np.allclose(z, (200.0 * np.array([0.03, 0.02]) + 100.0 * np.array([-0.01, 0.08])) / 300.0, atol=1e-15)
+    # a foot below the threshold adds its force to totalZ, not its ZMP
+    weak = wr.copy(); weak[2] = 0.0009
+    z, ok = sf.zmp_world(wl, weak, I, shifted)
+    assert ok and np.allclose(z, 200.0 / 200.0009 * np.array([0.03, 0.02]), atol=1e-15)
+    # totalZ just below / just above 0.1
+    lo = wl.copy(); lo[2] = 0.0999
+    assert not sf.zmp_world(lo, zero, I, I)[1]
+    hi = wl.copy(); hi[2] = 0.1001; hi[3:5] = [1e-4, -2e-4]
+    z, ok = sf.zmp_world(hi, zero, I, I)
+    assert ok and np.allclose(z, [2e-4 / 0.1001, 1e-4 / 0.1001], atol=1e-15)
+    # a rotated and translated sole: R_z(90 deg) maps the sole's (0.03, 0.02) to (-0.02, 0.03), then the sole's position is added
+    pose = (np.array([0.5, -0.2, 0.01]), _rot_z(np.pi / 2))
+    z, ok = sf.zmp_world(wl, zero, pose, I)
+    assert ok and np.allclose(z, [0.5 - 0.02, -0.2 + 0.03], atol=1e-15)
+
+
+def _robot(seed=5):
+    from walking_controllers_amd import synth
+    model = synth.icub_like_model()
+    rng = np.random.default_rng(seed)
+    q = np.deg2rad(synth.WALK_POSTURE_DEG) + 0.1 * rng.normal(size=23)
+    return model, q, rng
+
+
+def test_v_com_is_the_derivative_of_the_com_along_dq(wca):
+    """v_com = J_com[:, joints] dq (zero base twist) is the central difference of kin_spec.forward's CoM along dq with the base held."""
+    model, q, rng = _robot()
+    dq = rng.normal(size=23)
+    sole = np.concatenate([[0.02, 0.07, 0.0], _rot_z(0.1).reshape(9)])
+    r = sf.evaluate(model, q, dq, *(w[0] for w in sf.wrenches(rng, 1)), sole, 0, OMEGA)
+    h = 1e-6
+    fd = (ks.forward(model, r["base"], q + h * dq)["com"] - ks.forward(model, r["base"], q - h * dq)["com"]) / (2 * h)
+    assert np.abs(r["v_com"] - fd).max() <= 1e-8 * max(1.0, np.abs(fd).max())
+    assert np.abs(r["v_com"]).max() > 1e-3
+    assert np.allclose(r["dcm"], r["com"] + r["v_com"][:2] / OMEGA, rtol=0, atol=1e-15)
+
+
+@pytest.mark.parametrize("side", [0, 1])
+def test_the_anchor_puts_the_stance_sole_on_its_desired_pose(side):
+    model, q, rng = _robot(7)
+    sole = np.concatenate([rng.normal(scale=0.1, size=3), (_rot_z(rng.uniform(-1, 1)) @ _rot_z(0.0)).reshape(9)])
+    base = sf.anchored_base(model, q, sole, side)
+    p, R = ks.forward(model, base, q)["frames"][side]
+    assert np.abs(p - sole[:3]).max() <= 1e-12 and np.abs(R.reshape(9) - sole[3:]).max() <= 1e-12
+
+
+def test_stance_side_follows_the_gait():
+    st = 180
+    assert list(sf.stance_side(np.arange(6), np.full(6, st - 3), st)) == [0, 0, 0, 1, 1, 1]
+    assert list(sf.stance_side(np.arange(6), np.full(6, 2 * st - 3), st)) == [1, 1, 1, 0, 0, 0]
+
+
+def test_outputs_layout_matches_the_ctypes_mirror(wca, tmp_path):
+    """wcqp_tick_outputs.measured / feedback_fail appended: header offsets and size == capi.TickOutputs'."""
+    O = wca.capi.TickOutputs
+    src = tmp_path / "sensor_layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "wcqp.h"\nint main(void) {\n'
+                   'printf("%zu %zu %zu %zu\\n", sizeof(wcqp_tick_outputs), offsetof(wcqp_tick_outputs, zmp_gains), '
+                   'offsetof(wcqp_tick_outputs, measured), offsetof(wcqp_tick_outputs, feedback_fail));\nreturn 0;\n}\n')
+    exe = tmp_path / "sensor_layout"
+    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert got == [C.sizeof(O), O.zmp_gains.offset, O.measured.offset, O.feedback_fail.offset]
+
+
+def test_the_entry_points_are_exported(wca):
+    for sym in ("wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host"):
+        assert sym in wca.capi.ABI_SYMBOLS
+        getattr(wca.capi.lib(), sym)
+
+
+def test_binding_checks_the_sensor_arrays_before_the_device(wca):
+    """Wrong shapes or dtypes raise ValueError before any library call; non-finite values pass to the library (here: a handle that does
+    not exist, so the library's own refusal comes back)."""
+    pipe = wca.TickPipeline.__new__(wca.TickPipeline)
+    pipe.batch, pipe.dof, pipe._h = 3, 23, C.c_void_p()
+    q, dq, w = np.zeros((3, 23)), np.zeros((3, 23)), np.zeros((3, 6))
+    for bad in ((q[:2], dq, w, w), (q, dq[:, :22], w, w), (q, dq, w[:, :5], w), (q, dq, w, np.zeros((3, 6, 1))),
+                (q.astype(np.float32), dq, w, w), (q, dq.astype(np.int64), w, w), (q, dq, w, w.astype(np.complex128))):
+        with pytest.raises(ValueError):
+            pipe.set_sensor_feedback_host(*bad)
+    nan = q.copy(); nan[1, 4] = np.nan
+    with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+        pipe.set_sensor_feedback_host(nan, dq, w, w)           # reached the library: a NULL handle is WCQP_E_INVALID
+    import torch
+    with pytest.raises(ValueError):
+        pipe.set_sensor_feedback_device(torch.zeros(3, 23, dtype=torch.float64), torch.zeros(3, 23, dtype=torch.float64),
+                                        torch.zeros(3, 6, dtype=torch.float64), torch.zeros(3, 6, dtype=torch.float64))   # host tensors
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+def _walk(wca, B, T, phase0=None):
+    kin = wca.KinModel(wca.synth.icub_like_model())
+    kb = wca.synth.synth_walk_kin_batch(B)
+    poses = kin.jacobians_host(kb["base"], kb["q"], state=np.zeros((B, 87)))["state"]
+    d = wca.synth.synth_walk_batch(B, T, poses, kb)
+    if phase0 is not None:
+        d = dict(d, phase0=np.asarray(phase0, np.int32))
+    return kin, d
+
+
+def _ik(wca):
+    return wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=wca.synth.WALK_VMAX.copy(), joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG))
+
+
+def _ik_params(wca, qs):
+    return qs.IKParams(v_max=wca.synth.WALK_VMAX.copy(), joint_reg_deg=wca.synth.WALK_POSTURE_DEG.copy())
+
+
+def _pipe(wca, B, T, kin, controller="mpc", gs=False, **kw):
+    if controller == "reactive":
+        kw.update(dcm_controller="reactive", k_dcm=K_DCM)
+    if gs:
+        kw.update(zmp_gain_scheduling=True, **zg.ZMP_SCHEDULE["iCubGazeboV2_5"])
+    return wca.TickPipeline(B, T, wca.MpcSolver(), _ik(wca), log_ticks=T, kin=kin, external_feedback=True, **kw)
+
+
+class Sensors:
+    """The sensors of tick t as a fixed function of what the robot did up to tick t - 1 (its desired joints and velocities) plus a seeded
+    perturbation drawn up front, so that two runs that agree on a robot's past feed it the same readings.  Feet: the normal force follows
+    the synthetic gait's contact pair (a foot in the air reads nothing)."""
+
+    def __init__(self, B, T, phase0, seed=11, q_sigma=0.01, dq_sigma=0.05):
+        from oracle import tick_spec as ts
+        rng = np.random.default_rng(seed)
+        self.B, self.phase0, self.p = B, np.asarray(phase0), ts.TickParams()
+        self.qn = q_sigma * rng.normal(size=(T, B, 23))
+        self.dqn = dq_sigma * rng.normal(size=(T, B, 23))
+        self.w = [sf.wrenches(rng, B) for _ in range(T)]
+        self.ts = ts
+
+    def at(self, t, q_des, dq_prev):
+        code = self.ts.contact_code(t, self.phase0, self.p)
+        wl, wr = (x.copy() for x in self.w[t])
+        wl[code == 1, 2] = 0.0                  # right foot only
+        wr[code == 0, 2] = 0.0                  # left foot only
+        return q_des + self.qn[t], dq_prev + self.dqn[t], wl, wr
+
+
+def _sensor_loop(wca, pipe, d, model, T, sensors, form=lambda t: "host", tamper=None, stream=0):
+    """Runs T sensor-fed ticks; returns the final download, the restated measurements [T][B][6], the readings and the per-tick measured
+    downloads.  form(t): "host" or "plain" (the plain form fed the restatement's values).  tamper(t, readings) may spoil them."""
+    B = d["q0"].shape[0]
+    q_des, dq_prev = d["q0"].copy(), np.zeros((B, 23))
+    restated, measured, readings = np.zeros((T, B, 6)), np.zeros((T, B, 6)), []
+    for t in range(T):
+        r = sensors.at(t, q_des, dq_prev)
+        if tamper is not None:
+            r = tamper(t, [x.copy() for x in r])
+        readings.append(r)
+        restated[t], _ = sf.evaluate_batch(model, t, d["phase0"], 180, d["state0"], *r, OMEGA)
+        if form(t) == "host":
+            pipe.set_sensor_feedback_host(*r)
+        else:
+            m = restated[t]
+            pipe.set_feedback_host(m[:, 0:2], m[:, 2:4], m[:, 4:6], r[0])
+        pipe.run(1, stream=stream)
+        o = pipe.download()
+        measured[t] = o["measured"]
+        q_des, dq_prev = o["q_des"], o["dq_log"][t]
+    return o, restated, readings, measured
+
+
+@pytest.mark.gpu
+def test_measured_state_matches_the_restatement_on_both_anchors(wca):
+    """B = 37 (not a multiple of 4 or 64), fused kinematics, 7 ticks around a step boundary at tick 3 for 20 robots (left -> right and
+    right -> left stance): random joints near the desired ones, random velocities, wrenches with both feet defined, one defined, and one
+    below the 0.001 threshold.  download()["measured"] == the restatement to 1e-12, tick by tick."""
+    B, T, st = 37, 7, 180
+    phase0 = np.array([st - 3] * 10 + [2 * st - 3] * 10 + [50] * 17, np.int32)
+    kin, d = _walk(wca, B, T, phase0)
+    model = wca.synth.icub_like_model()
+    pipe = _pipe(wca, B, T, kin)
+    pipe.upload(d)
+    o = pipe.download()
+    assert np.array_equal(o["measured"], np.concatenate([d["dcm0"], d["com0"], d["u_init"]], 1))   # before any tick: the uploaded state
+    rng = np.random.default_rng(3)
+    sides = set()
+    q_des = d["q0"].copy()
+    for t in range(T):
+        q = q_des + 0.05 * rng.normal(size=(B, 23))
+        dq = 0.3 * rng.normal(size=(B, 23))
+        wl, wr = sf.wrenches(rng, B)
+        wr[np.arange(B) % 3 == 1, 2] = 0.0                 # one foot defined
+        wr[np.arange(B) % 3 == 2, 2] = 0.0005              # one foot below the threshold (its force still counts in totalZ)
+        ref, rej = sf.evaluate_batch(model, t, phase0, st, d["state0"], q, dq, wl, wr, OMEGA)
+        assert not rej.any()
+        sides |= set(int(s) for s in sf.stance_side(t, phase0, st))
+        pipe.set_sensor_feedback_host(q, dq, wl, wr)
+        pipe.run(1)
+        o = pipe.download()
+        assert np.abs(o["measured"] - ref).max() <= 1e-12, (t, np.abs(o["measured"] - ref).max())
+        assert o["feedback_fail"].sum() == 0
+        q_des = o["q_des"]
+    assert sides == {0, 1}
+    # with q_meas = q_des (and no velocity) the CoM is the anchored kinematics' at the desired joints, what the tick's own kinematics see
+    pipe2 = _pipe(wca, B, T, kin)
+    pipe2.upload(d)
+    pipe2.set_sensor_feedback_host(d["q0"], np.zeros((B, 23)), *sf.wrenches(rng, B))
+    pipe2.run(1)
+    m = pipe2.download()["measured"]
+    assert np.array_equal(m[:, 0:2], m[:, 2:4])
+    for i in range(B):
+        side = int(sf.stance_side(0, phase0, st)[i])
+        base = sf.anchored_base(model, d["q0"][i], sf.desired_sole(d["state0"][i], side), side)
+        assert np.abs(m[i, 2:4] - ks.forward(model, base, d["q0"][i])["com"][:2]).max() <= 1e-12
+
+
+def _restated_run(wca, qs, d, T, controller, gs, ext):
+    from oracle import tick_spec as ts
+    p = ts.TickParams()
+    kw = dict(kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT, external=ext)
+    if gs:
+        sched = zg.ZMP_SCHEDULE["iCubGazeboV2_5"]
+        if controller == "reactive":
+            with rt.reactive_solve(p, K_DCM, d["q0"].shape[0]):
+                return zg.run_ticks_scheduled(p, d, T, _ik_params(wca, qs), sched, **kw)
+        return zg.run_ticks_scheduled(p, d, T, _ik_params(wca, qs), sched, **kw)
+    if controller == "reactive":
+        return rt.run_ticks_reactive(p, d, T, _ik_params(wca, qs), K_DCM, **kw)
+    return ts.run_ticks(p, d, T, _ik_params(wca, qs), **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("controller", ["mpc", "reactive"])
+@pytest.mark.parametrize("gs", [False, True], ids=["fixed_gains", "gain_scheduling"])
+def test_closed_loop_follows_the_restated_external_run(wca, qs, controller, gs):
+    """60 ticks whose sensors are a fixed function of the robot's previous desired state plus a seeded perturbation: the pipeline follows
+    tick_spec.run_ticks(external = the restated dcm / com / zmp and q_meas) - u0_log, q_des to 1e-9, dq_log to 1e-8, the same failures."""
+    B, T = 10, 60
+    kin, d = _walk(wca, B, T)
+    model = wca.synth.icub_like_model()
+    pipe = _pipe(wca, B, T, kin, controller, gs)
+    pipe.upload(d)
+    out, restated, readings, measured = _sensor_loop(wca, pipe, d, model, T, Sensors(B, T, d["phase0"]))
+    assert not np.isnan(restated).any() and out["feedback_fail"].sum() == 0
+    assert np.abs(measured - restated).max() <= 1e-12
+    ext = dict(dcm=restated[:, :, 0:2], com=restated[:, :, 2:4], zmp=restated[:, :, 4:6], q=np.stack([r[0] for r in readings]))
+    ref = _restated_run(wca, qs, d, T, controller, gs, ext)
+    assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
+    assert np.abs(out["u0_log"] - ref["u0_log"]).max() <= 1e-9
+    assert np.abs(out["dq_log"] - ref["dq_log"]).max() <= 1e-8
+    assert np.abs(out["q_des"] - ref["q_des"]).max() <= 1e-9
+    assert np.abs(ref["dq_log"]).max() > 1e-2                   # the robots move
+
+
+@pytest.mark.gpu
+def test_the_sensor_form_equals_the_plain_form_fed_its_values(wca):
+    """A plain EXTERNAL handle fed the sensor handle's measured values (and its q_meas) tick by tick gives identical logs; one handle that
+    switches between the sensor form and the plain form from tick to tick follows too.  The device form: a process of its own
+    (tests/helpers/sensor_device_check.py - torch has to initialise its HIP runtime before libwcqp's), fed from torch tensors on a
+    non-blocking stream, alone and alternating with the host form: bit for bit the host form's."""
+    B, T = 10, 24
+    kin, d = _walk(wca, B, T)
+    model = wca.synth.icub_like_model()
+    a = _pipe(wca, B, T, kin); a.upload(d)
+    oa, restated, readings, ma = _sensor_loop(wca, a, d, model, T, Sensors(B, T, d["phase0"]))
+    b = _pipe(wca, B, T, kin); b.upload(d)
+    for t in range(T):
+        b.set_feedback_host(ma[t, :, 0:2], ma[t, :, 2:4], ma[t, :, 4:6], readings[t][0])
+        b.run(1)
+    ob = b.download()
+    m = _pipe(wca, B, T, kin); m.upload(d)
+    om, _, _, mm = _sensor_loop(wca, m, d, model, T, Sensors(B, T, d["phase0"]), form=lambda t: ("host", "plain")[t % 2])
+    for k in ("u0_log", "dq_log", "q_des", "ik_fail", "mpc_fail", "measured"):
+        assert np.array_equal(oa[k], ob[k]), k
+    for k in ("u0_log", "dq_log", "q_des", "ik_fail", "mpc_fail"):
+        assert np.abs(oa[k] - om[k]).max() <= (1e-12 if k != "dq_log" else 1e-11), k
+    assert np.abs(ma - mm).max() <= 1e-12
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "sensor_device_check.py")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "sensor device ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["low_normal_force", "nan_velocity"])
+def test_a_rejected_robot_is_stopped_and_its_neighbours_are_not(wca, case):
+    """One robot's readings fail at tick k (totalZ < 0.1, or a NaN joint velocity): feedback_fail counts it, its measured state stays the
+    previous tick's, dq = 0 from tick k on, ik_fail counts the rejection and every stopped tick, and every other robot is bitwise what a run
+    without the failure gives."""
+    B, T, k, r = 10, 20, 7, 3
+    kin, d = _walk(wca, B, T)
+    model = wca.synth.icub_like_model()
+    sens = Sensors(B, T, d["phase0"])
+
+    def spoil(t, x):
+        if t == k:
+            if case == "low_normal_force":
+                x[2][r, 2] = 0.03; x[3][r, 2] = 0.05          # totalZ = 0.08
+            else:
+                x[1][r, 5] = np.nan
+        return x
+    base = _pipe(wca, B, T, kin); base.upload(d)
+    ob, _, _, _ = _sensor_loop(wca, base, d, model, T, sens)
+    bad = _pipe(wca, B, T, kin); bad.upload(d)
+    ox, _, _, mx = _sensor_loop(wca, bad, d, model, T, sens, tamper=spoil)
+    others = np.arange(B) != r
+    assert list(ox["feedback_fail"]) == [int(i == r) for i in range(B)] and ob["feedback_fail"].sum() == 0
+    assert ob["ik_fail"].sum() == 0
+    assert ox["ik_fail"][r] == T - k + 1 and (ox["ik_fail"][others] == 0).all()
+    assert (ox["dq_log"][k:, r] == 0).all() and np.abs(ox["dq_log"][k - 1, r]).max() > 0
+    assert np.array_equal(mx[k, r], mx[k - 1, r])                # the previous tick's measured state, kept
+    for key in ("u0_log", "dq_log"):
+        assert np.array_equal(ox[key][:, others], ob[key][:, others]), key
+    assert np.array_equal(ox["q_des"][others], ob["q_des"][others])
+    assert np.array_equal(ox["u0_log"][:k], ob["u0_log"][:k]) and np.array_equal(ox["dq_log"][:k], ob["dq_log"][:k])
+    # the trapezoid stops q_des half a step after the last velocity, as after an IK failure: q0 + dT sum_{t < k} dq_t
+    q_k = d["q0"][r] + 0.01 * ox["dq_log"][:k, r].sum(0)
+    assert np.abs(ox["q_des"][r] - q_k).max() <= 1e-12
+
+
+@pytest.mark.gpu
+def test_refusals_and_stream_order(wca):
+    """UNSUPPORTED without kinematics and with the internal plant, INVALID for NULL pointers, a run without feedback and two ticks in one
+    call; measured / feedback_fail refused on an internal-plant handle.  The host form followed by a run on a non-blocking stream
+    (wcqp_stream_create) gives what the NULL stream gives."""
+    B, T = 6, 8
+    kin, d = _walk(wca, B, T)
+    model = wca.synth.icub_like_model()
+    z23, z6 = np.zeros((B, 23)), np.zeros((B, 6))
+    # constant Jacobians: no model to evaluate
+    dc = wca.synth.synth_tick_batch(B, T)
+    nokin = wca.TickPipeline(B, T, wca.MpcSolver(), wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=0.45), log_ticks=T, external_feedback=True)
+    nokin.upload(dc)
+    with pytest.raises(wca.WcqpError, match=r"\(-2\)"):
+        nokin.set_sensor_feedback_host(z23, z23, z6, z6)
+    assert (nokin.download()["feedback_fail"] == 0).all()
+    # the internal plant
+    internal = wca.TickPipeline(B, T, wca.MpcSolver(), _ik(wca), log_ticks=T, kin=kin)
+    internal.upload(d)
+    with pytest.raises(wca.WcqpError, match=r"\(-2\)"):
+        internal.set_sensor_feedback_host(z23, z23, z6, z6)
+    for field in ("measured", "feedback_fail"):
+        buf = np.zeros(B * 6)
+        outs = wca.capi.TickOutputs(**{field: buf.ctypes.data})
+        assert wca.capi.lib().wcqp_tick_download(internal._h, C.byref(outs)) == WCQP_E_UNSUPPORTED
+    # NULL pointers (refused before anything reads the others), run without feedback, two ticks in one call
+    pipe = _pipe(wca, B, T, kin)
+    pipe.upload(d)
+    for args in ((0, 8, 8, 8), (8, 0, 8, 8), (8, 8, 0, 8), (8, 8, 8, 0)):
+        with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+            pipe.set_sensor_feedback_device(*args)
+    with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+        pipe.run(1)
+    sens = Sensors(B, T, d["phase0"])
+    pipe.set_sensor_feedback_host(*sens.at(0, d["q0"], np.zeros((B, 23))))
+    with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+        pipe.run(2)
+    pipe.run(1)
+    with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+        pipe.run(1)                                          # the feedback of tick 0 was consumed
+    # stream order: the host form, then the run on a non-blocking stream (wcqp_stream_create)
+    ref_pipe = _pipe(wca, B, T, kin); ref_pipe.upload(d)
+    oref, _, _, mref = _sensor_loop(wca, ref_pipe, d, model, T, sens)
+    s = wca.capi.stream_create()
+    try:
+        nb = _pipe(wca, B, T, kin); nb.upload(d)
+        onb, _, _, mnb = _sensor_loop(wca, nb, d, model, T, sens, stream=s)
+    finally:
+        wca.capi.stream_synchronize(s)
+        wca.capi.stream_destroy(s)
+    for k in ("u0_log", "dq_log", "q_des", "ik_fail", "mpc_fail", "measured"):
+        assert np.array_equal(onb[k], oref[k]), k
+    assert np.array_equal(mnb, mref)

@@ -37,6 +37,7 @@ ABI_SYMBOLS = (
     "wcqp_kin_create", "wcqp_kin_destroy", "wcqp_kin_jacobians_device", "wcqp_kin_jacobians_host",
     "wcqp_tick_create", "wcqp_tick_destroy", "wcqp_tick_upload", "wcqp_tick_run", "wcqp_tick_download", "wcqp_tick_splice_reference",
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
+    "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
 )
@@ -188,7 +189,8 @@ class TickInputs(C.Structure):
 
 
 class TickOutputs(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("u0_log", "dq_log", "q_des", "dcm", "com", "mpc_fail", "ik_fail", "hot_try", "hot_hit", "tick", "logger", "active_lower", "active_upper", "zmp_gains")]
+    _fields_ = [(k, C.c_void_p) for k in ("u0_log", "dq_log", "q_des", "dcm", "com", "mpc_fail", "ik_fail", "hot_try", "hot_hit", "tick", "logger", "active_lower", "active_upper", "zmp_gains",
+                                          "measured", "feedback_fail")]
 
 
 _lib: Optional[C.CDLL] = None
@@ -234,6 +236,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_splice_reference.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.wcqp_tick_set_feedback_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wcqp_tick_set_feedback_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wcqp_tick_set_sensor_feedback_device.argtypes = [C.c_void_p] * 6
+        L.wcqp_tick_set_sensor_feedback_host.argtypes = [C.c_void_p] * 5
         L.wcqp_tick_get_info.argtypes = [C.c_void_p, C.POINTER(TickInfo)]
         L.wcqp_qp_enqueue_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.POINTER(C.c_int32)]
         L.wcqp_qp_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.c_int32, C.POINTER(C.c_void_p)]
@@ -484,6 +488,7 @@ class TickPipeline:
         if neck.shape != (9,) or not np.all(np.isfinite(neck)):
             raise ValueError("neck_additional_rotation must be a finite 3 x 3 matrix")
         self.batch, self.max_ticks, self.log_ticks, self.dof = batch, max_ticks, log_ticks, ik.dof
+        self.external = bool(external_feedback)
         self.logger_ticks = int(logger_ticks)
         self.use_kin = kin is not None
         if foot_rect is None:
@@ -577,6 +582,42 @@ class TickPipeline:
         assert all(x.shape == (self.batch, 2) for x in a) and (q is None or q.shape == (self.batch, self.dof))
         check(lib().wcqp_tick_set_feedback_host(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(q)), "wcqp_tick_set_feedback_host")
 
+    def _sensor_arrays(self, q_meas, dq_meas, wrench_left, wrench_right):
+        """the four sensor arrays as contiguous float64, or ValueError - non-finite values pass (the device rejects that robot)"""
+        B, D = self.batch, self.dof
+        out = []
+        for name, x, shape in (("q_meas", q_meas, (B, D)), ("dq_meas", dq_meas, (B, D)), ("wrench_left", wrench_left, (B, 6)),
+                               ("wrench_right", wrench_right, (B, 6))):
+            a = np.asarray(x)
+            if a.dtype != np.float64:
+                raise ValueError(f"{name} must be float64, not {a.dtype}")
+            if a.shape != shape:
+                raise ValueError(f"{name} must have shape {shape}, not {a.shape}")
+            out.append(np.ascontiguousarray(a))
+        return out
+
+    def set_sensor_feedback_host(self, q_meas, dq_meas, wrench_left, wrench_right):
+        """Sensor feedback (plant = EXTERNAL with kinematics, wcqp_tick_set_sensor_feedback_host): measured joint positions / velocities
+        [B][dof] and the two sole wrenches [B][6] (fx fy fz tx ty tz in the sole frame) of the next tick; the device evaluates CoM, DCM and
+        ZMP from them.  In place when the call returns (the run may name any stream).  Shapes and dtypes are checked here, before any device
+        call; a robot with a non-finite value is rejected on the device (download()["feedback_fail"])."""
+        a = self._sensor_arrays(q_meas, dq_meas, wrench_left, wrench_right)
+        check(lib().wcqp_tick_set_sensor_feedback_host(self._h, *(_p(x) for x in a)), "wcqp_tick_set_sensor_feedback_host")
+
+    def set_sensor_feedback_device(self, q_meas, dq_meas, wrench_left, wrench_right, stream: int = 0):
+        """The same from DEVICE memory: raw addresses, or float64 torch tensors of the shapes above on the GPU (checked here); enqueue only."""
+        shapes = ((self.batch, self.dof), (self.batch, self.dof), (self.batch, 6), (self.batch, 6))
+        ptrs = []
+        for name, x, shape in zip(("q_meas", "dq_meas", "wrench_left", "wrench_right"), (q_meas, dq_meas, wrench_left, wrench_right), shapes):
+            if hasattr(x, "data_ptr"):
+                import torch
+                if x.dtype != torch.float64 or tuple(x.shape) != shape or not x.is_contiguous() or not x.is_cuda:
+                    raise ValueError(f"{name} must be a contiguous float64 device tensor of shape {shape}")
+                ptrs.append(x.data_ptr())
+            else:
+                ptrs.append(int(x))
+        check(lib().wcqp_tick_set_sensor_feedback_device(self._h, *[p or None for p in ptrs], stream or None), "wcqp_tick_set_sensor_feedback_device")
+
     def splice_reference(self, from_tick: int, ref_tail, stream: int = 0):
         """Trajectory merge: stages [from_tick, from_tick + n) of every instance's DCM reference <- ref_tail[B][n][2]."""
         tail = _f64(ref_tail)
@@ -592,6 +633,8 @@ class TickPipeline:
                  active_lower=np.zeros(B, np.uint32), active_upper=np.zeros(B, np.uint32), zmp_gains=np.zeros((B, 2)))
         if self.logger_ticks > 0:
             o["logger"] = np.zeros((self.logger_ticks, B, 53))
+        if getattr(self, "external", False):
+            o["measured"] = np.zeros((B, 6)); o["feedback_fail"] = np.zeros(B, np.int64)
         outs = TickOutputs(**{k: (o[k].ctypes.data if k in o else None) for k, _ in TickOutputs._fields_})
         check(lib().wcqp_tick_download(self._h, C.byref(outs)), "wcqp_tick_download")
         o["tick"] = int(o["tick"][0])

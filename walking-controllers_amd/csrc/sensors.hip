@@ -1,0 +1,291 @@
+// Sensor feedback of the tick pipeline (include/wcqp.h: wcqp_tick_set_sensor_feedback_*): what the reference evaluates from the robot's
+// joint encoders and foot wrenches every tick before its controllers run (citations relative to /root/reference/modules/Walking_module):
+//   src/WalkingModule.cpp:1147-1165           updateFKSolver: base anchored at the desired pose of the fixed-frame foot, measured joints
+//   src/WalkingForwardKinematics.cpp:258-337  setInternalRobotState (zero base twist), evaluateCoM, evaluateDCM
+//   src/WalkingModule.cpp:826-878             evaluateZMP
+// The kinematics are the fused tick kernel's (ik4_device.h, JSRC = 2) at the MEASURED joints: the model table in LDS, 16 lanes per robot
+// with lane j owning joints j and 16 + j, pointer jumping for the joint frames, a row scan for the subtree first moments - the same
+// operations in the same order, so that with q_meas = q_des the sole poses and the CoM agree with the tick's own to rounding.  No Jacobian
+// leaves the kernel: the CoM velocity is the joint block of the MIXED CoM Jacobian times dq_meas, reduced across the robot's row.
+#include "tick_device.h"
+#include "kin_device.h"
+#include "sensors.h"
+
+namespace {
+
+using namespace wcqp_tick;
+
+// LDS per robot (doubles): joint frames [23][S_FS] (the subtree prefix sums [32][4] overlay them once the joints are in world
+// coordinates), the two soles in base and in world coordinates [2][12] each, the anchor's desired pose [12], the CoM velocity [2]
+constexpr int S_FS = 14, S_TW = 0, S_FRB = 322, S_FR = 346, S_SD = 370, S_V = 382;
+constexpr int S_PER = 392;          // = 8 mod 32: the four robots of a wave sit apart in the banks
+static_assert(kDof * S_FS <= S_FRB && 32 * 4 <= S_FRB && S_V + 2 <= S_PER, "sensor kernel LDS layout");
+
+__device__ __forceinline__ void st2(double* p, double a, double b) { *reinterpret_cast<double2*>(p) = make_double2(a, b); }
+__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
+
+// One robot per 16 lanes, four per wave, one wave per workgroup.
+__global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
+    using namespace wcqp_kin;
+    __shared__ __attribute__((aligned(16))) double kmodel[kKinTabSize];
+    __shared__ __attribute__((aligned(16))) double smem[4][S_PER];
+    const int lane = threadIdx.x, grp = lane >> 4, j = lane & 15;
+    for (int k = lane; k < kKinTabSize; k += 64) kmodel[k] = a.kin_tab[k];
+    const long inst_raw = (long)blockIdx.x * 4 + grp;
+    const bool live = inst_raw < a.batch;
+    const size_t i = (size_t)(live ? inst_raw : (long)a.batch - 1);
+    double* S = smem[grp];
+    const bool var1 = j < kDof - 16;                 // slot 1 is joint 16 + j
+    const int cs[2] = {j, var1 ? 16 + j : 0};
+    // ---- inputs, and whether all of this robot's are finite
+    const double* qi = a.q + i * kDof;
+    const double* dqi = a.dq + i * kDof;
+    const double q0 = qi[j], q1 = var1 ? qi[16 + j] : 0.0;
+    const double dq0 = dqi[j], dq1 = var1 ? dqi[16 + j] : 0.0;
+    const double wv = j < 6 ? a.wl[i * 6 + j] : (j < 12 ? a.wr[i * 6 + j - 6] : 0.0);
+    const bool lane_bad = !(isfinite(q0) && isfinite(q1) && isfinite(dq0) && isfinite(dq1) && isfinite(wv));
+    const bool bad = ((__ballot(lane_bad) >> (grp * 16)) & 0xffffull) != 0ull;
+    // what the ZMP reads of the two wrenches - fz, tx, ty - on every lane, in flight with the rest (the same addresses across the row)
+    const double* wli = a.wl + i * 6;
+    const double* wri = a.wr + i * 6;
+    const double fzL = wli[2], txL = wli[3], tyL = wli[4], fzR = wri[2], txR = wri[3], tyR = wri[4];
+    // the stance side of tick t, as the tick kernel carries it: (t + phase0) % (2 step_ticks) >= step_ticks -> the right sole anchors
+    const int cyc = (a.t + a.phase0[i]) % (2 * a.step_ticks);
+    const int side = cyc >= a.step_ticks ? 1 : 0;
+    if (j < 12) S[S_SD + j] = a.state[i * kStateLen + 24 + side * 12 + j];     // its desired pose: p (3), R (9)
+    int kup[2][3], ksub[2];
+    __syncthreads();                                 // the model table is in LDS
+#pragma unroll
+    for (int s_ = 0; s_ < 2; ++s_) {
+        const int* ip = reinterpret_cast<const int*>(kmodel + cs[s_] * kKinTabJoint + kKinTabInts);
+        kup[s_][0] = ip[0]; kup[s_][1] = ip[1]; kup[s_][2] = ip[2]; ksub[s_] = ip[3];
+    }
+    const int kfj = reinterpret_cast<const int*>(kmodel + kKinTabRoot + 4)[j < 2 ? j : 0];
+    double* TW = S + S_TW;
+    {
+        double Ra[2][9], pa[2][3];
+#pragma unroll
+        for (int s_ = 0; s_ < 2; ++s_) {
+            const double* mt = kmodel + cs[s_] * kKinTabJoint;
+            double R0[9], axl[3];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) R0[k] = mt[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { pa[s_][k] = mt[9 + k]; axl[k] = mt[12 + k]; }
+            joint_rotation(R0, axl, s_ == 0 ? q0 : q1, Ra[s_]);
+        }
+        // the tree in base coordinates by pointer jumping: after round r a frame is relative to its 2^(r+1)-th ancestor
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            if (r >= a.kin_rounds) break;
+#pragma unroll
+            for (int s_ = 0; s_ < 2; ++s_) {
+                if (s_ == 0 || var1) {
+                    double* Tm = TW + cs[s_] * S_FS;
+#pragma unroll
+                    for (int k = 0; k < 8; k += 2) st2(Tm + k, Ra[s_][k], Ra[s_][k + 1]);
+                    st2(Tm + 8, Ra[s_][8], pa[s_][0]); st2(Tm + 10, pa[s_][1], pa[s_][2]);
+                }
+            }
+            wcqp::wave_lds_fence();
+#pragma unroll
+            for (int s_ = 0; s_ < 2; ++s_) {
+                const int u = kup[s_][r];
+                if (u >= 0 && (s_ == 0 || var1)) {
+                    const double* T = TW + u * S_FS;
+                    double Rp[9], pp[3], Rn[9], pn[3];
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) Rp[k] = T[k];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) pp[k] = T[9 + k];
+                    frame_mul(Rp, pp, Ra[s_], pa[s_], Rn, pn);
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) Ra[s_][k] = Rn[k];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) pa[s_][k] = pn[k];
+                }
+            }
+            wcqp::wave_lds_fence();
+        }
+#pragma unroll
+        for (int s_ = 0; s_ < 2; ++s_) {
+            if (s_ == 0 || var1) {
+                double* Tm = TW + cs[s_] * S_FS;
+#pragma unroll
+                for (int k = 0; k < 8; k += 2) st2(Tm + k, Ra[s_][k], Ra[s_][k + 1]);
+                st2(Tm + 8, Ra[s_][8], pa[s_][0]); st2(Tm + 10, pa[s_][1], pa[s_][2]);
+            }
+        }
+    }
+    wcqp::wave_lds_fence();
+    // the two soles in base coordinates: lanes 0 (left) and 1 (right)
+    double Rf[9], pf[3];
+    {
+        const double* T = TW + kfj * S_FS;
+        const double* ft = kmodel + kKinTabFrames + (j < 2 ? j : 0) * 12;
+        double Rj[9], pj[3], fR[9], fp[3];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { Rj[k] = T[k]; fR[k] = ft[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { pj[k] = T[9 + k]; fp[k] = ft[9 + k]; }
+        frame_mul(Rj, pj, fR, fp, Rf, pf);
+        if (j < 2) {
+            double* F = S + S_FRB + j * 12;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) F[k] = Rf[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) F[9 + k] = pf[k];
+        }
+    }
+    wcqp::wave_lds_fence();
+    // base pose from the anchor sole: world_T_base = world_T_sole,desired * (base_T_sole(q_meas))^-1
+    double pb[3], Rb[9];
+    {
+        const double* Fs = S + S_FRB + side * 12;
+        double Rs[9], ps[3], d3[3], sdp[3], sdR[9];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sdp[k] = S[S_SD + k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sdR[k] = S[S_SD + 3 + k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rs[k] = Fs[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ps[k] = Fs[9 + k];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Rb[3 * r + c] = sdR[3 * r] * Rs[3 * c] + sdR[3 * r + 1] * Rs[3 * c + 1] + sdR[3 * r + 2] * Rs[3 * c + 2];
+        mat3_vec(Rb, ps, d3);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pb[k] = sdp[k] - d3[k];
+    }
+    // the soles in world coordinates (the MEASURED poses the ZMP is mapped with)
+    if (j < 2) {
+        double Rg[9], pg[3];
+        frame_mul(Rb, pb, Rf, pf, Rg, pg);
+        double* F = S + S_FR + j * 12;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) F[k] = Rg[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) F[9 + k] = pg[k];
+    }
+    // own joints in world coordinates, their axes, link first moments {m c, m}
+    double pw[2][3], aw[2][3], e4[2][4];
+#pragma unroll
+    for (int s_ = 0; s_ < 2; ++s_) {
+        const double* mt = kmodel + cs[s_] * kKinTabJoint;
+        double Rw[9], cl[3], Rl[9], pl[3];
+        const double* Tm = TW + cs[s_] * S_FS;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rl[k] = Tm[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pl[k] = Tm[9 + k];
+        frame_mul(Rb, pb, Rl, pl, Rw, pw[s_]);
+        const double axl[3] = {mt[12], mt[13], mt[14]};
+        mat3_vec(Rw, axl, aw[s_]);
+        const double cj[3] = {mt[15], mt[16], mt[17]};
+        const double mj = (s_ == 0 || var1) ? mt[18] : 0.0;
+        mat3_vec(Rw, cj, cl);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e4[s_][k] = mj * (pw[s_][k] + cl[k]);
+        e4[s_][3] = mj;
+    }
+    wcqp::wave_lds_fence();          // the joint frames are dead: the prefix sums overlay them
+    // subtree first moments: the joint numbering is depth-first, a subtree is an index range; inclusive prefix sums over joints 0..15
+    // (slot 0, a DPP row scan) and 16.. (slot 1, offset by the row's total)
+    double* PS = S + S_TW;           // [32][4]
+    {
+        double p0s[4], p1s[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { p0s[k] = row_scan(e4[0][k]); p1s[k] = row_scan(e4[1][k]); }
+        st2(PS + j * 4, p0s[0], p0s[1]); st2(PS + j * 4 + 2, p0s[2], p0s[3]);
+        wcqp::wave_lds_fence();
+        const double2 t01 = ld2(PS + 15 * 4), t23 = ld2(PS + 15 * 4 + 2);
+        st2(PS + (16 + j) * 4, p1s[0] + t01.x, p1s[1] + t01.y); st2(PS + (16 + j) * 4 + 2, p1s[2] + t23.x, p1s[3] + t23.y);
+        wcqp::wave_lds_fence();
+    }
+    double tot[4], ctot[3];
+    {
+        const double* rt = kmodel + kKinTabRoot;
+        const double rootc[3] = {rt[0], rt[1], rt[2]};
+        const double root_mass = rt[3];
+        double cr[3];
+        mat3_vec(Rb, rootc, cr);
+        const double* Pt = PS + (kDof - 1) * 4;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tot[k] = Pt[k] + root_mass * (pb[k] + cr[k]);
+        tot[3] = Pt[3] + root_mass;
+    }
+    const double iM = 1.0 / tot[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ctot[k] = tot[k] * iM;
+    // v_com = J_com[:, joints] dq_meas (the base twist is zero, WalkingFK::setInternalRobotState): this lane's two CoM columns
+    // (a_c x (c_sub(c) - p_c) m_sub(c) / M, as the fused tick forms them) times its two joint velocities, summed over the row
+    double vx = 0.0, vy = 0.0;
+#pragma unroll
+    for (int s_ = 0; s_ < 2; ++s_) {
+        const int c = cs[s_];
+        const double* Pe = PS + ksub[s_] * 4;
+        const double* Pb = PS + (c > 0 ? c - 1 : 0) * 4;
+        const double z = c > 0 ? 1.0 : 0.0;
+        const double ms = Pe[3] - z * Pb[3];
+        const double d3[3] = {(Pe[0] - z * Pb[0] - ms * pw[s_][0]) * iM, (Pe[1] - z * Pb[1] - ms * pw[s_][1]) * iM, (Pe[2] - z * Pb[2] - ms * pw[s_][2]) * iM};
+        double lin[3];
+        cross3(aw[s_], d3, lin);
+        const double w = s_ == 0 ? dq0 : dq1;        // (0 on a lane without a second joint)
+        vx += lin[0] * w; vy += lin[1] * w;
+    }
+    vx = row_scan(vx); vy = row_scan(vy);
+    if (j == 15) st2(S + S_V, vx, vy);
+    wcqp::wave_lds_fence();
+    // ---- the rejection (every lane), lanes 0 / 1: axis j of the DCM and of the ZMP (WalkingModule::evaluateZMP), the write-back
+    if (!live) return;
+    const double totalZ = fzR + fzL;
+    const bool rejected = bad || !(totalZ >= 0.1);
+    double* qm = a.q_meas + i * kDof;
+    if (!rejected) {
+        qm[j] = q0;
+        if (var1) qm[16 + j] = q1;
+    } else if (a.t == 0) {
+        // rejected on tick 0: the desired joints, as the plain form without q_meas
+        qm[j] = a.q_des[i * kDof + j];
+        if (var1) qm[16 + j] = a.q_des[i * kDof + 16 + j];
+    }
+    if (j >= 2) return;
+    double* rec = a.mst + (i * 2 + j) * 8;
+    if (rejected) {
+        // updateModule returns false: the measured state of the previous tick stays - what its chain read, kept in the hand-off record of
+        // parity t - 1 (tick 0: the uploaded state) - and the robot is stopped like one whose IK failed
+        if (a.t > 0) {
+            const double* hd = a.hand + ((size_t)((a.t - 1) & 1) * a.batch + i) * kHandLen;
+            rec[2] = hd[4 + j]; rec[6] = hd[6 + j]; rec[7] = hd[10 + j];
+        }
+        if (j == 0) {
+            a.feedback_fail[i] += 1;
+            if (a.ik_fail[i] == 0) a.ik_fail[i] = 1;
+        }
+        return;
+    }
+    const double v = S[S_V + j];
+    const double dcm = ctot[j] + v / a.omega;
+    const double defL = fzL < 0.001 ? 0.0 : 1.0, defR = fzR < 0.001 ? 0.0 : 1.0;
+    // the foot's ZMP in its sole frame (-ty / fz, tx / fz, 0), mapped to world by the sole's measured pose (undefined: the sole origin)
+    const double zLx = defL != 0.0 ? -tyL / fzL : 0.0, zLy = defL != 0.0 ? txL / fzL : 0.0;
+    const double zRx = defR != 0.0 ? -tyR / fzR : 0.0, zRy = defR != 0.0 ? txR / fzR : 0.0;
+    const double* FL = S + S_FR;
+    const double* FR = S + S_FR + 12;
+    const double wL = FL[3 * j] * zLx + FL[3 * j + 1] * zLy + FL[9 + j];
+    const double wR = FR[3 * j] * zRx + FR[3 * j + 1] * zRy + FR[9 + j];
+    const double zmp = ((fzL * defL) / totalZ) * wL + ((fzR * defR) / totalZ) * wR;
+    rec[2] = ctot[j]; rec[6] = dcm; rec[7] = zmp;
+}
+
+}  // namespace
+
+namespace wcqp {
+int sensor_feedback_enqueue(const wcqp_tick::SensorDev& a, hipStream_t stream) {
+    hipLaunchKernelGGL(tick_sensor_kernel, dim3((unsigned)((a.batch + 3) / 4)), dim3(64), 0, stream, a);
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+}  // namespace wcqp

@@ -19,6 +19,7 @@
 
 #include "tick_device.h"
 #include "ik_common.h"
+#include "sensors.h"
 
 namespace {
 
@@ -168,6 +169,12 @@ struct wcqp_tick_s {
     bool external = false, feedback_set = false;     // wcqp_tick_params.plant = EXTERNAL: one tick per run call, each behind a set_feedback
     double* q_meas = nullptr;
     double* fb_stage = nullptr;   // wcqp_tick_set_feedback_host: [B][2 + 2 + 2 + dof]
+    // sensor feedback (EXTERNAL with kinematics, wcqp_tick_set_sensor_feedback_*): the host form's staging rows [B][dof + dof + 6 + 6],
+    // the rejection counter, and an event each run records on its stream (the host form waits for it before it stages)
+    double* sens_stage = nullptr;
+    long long* feedback_fail = nullptr;
+    hipEvent_t run_done = nullptr; bool run_pending = false;
+    std::vector<double> meas0;    // EXTERNAL: dcm0, com0, u_init of the last upload ([B][6]: wcqp_tick_outputs.measured before any tick)
     ZmpSched zg{};                // zmp_gain_scheduling (d.gain_sched): the stance gains, the smoother, its per-robot state
     // the handle's TickDev with the scheduling record behind it (what the scheduled kernels take)
     TickDevGS dgs(const TickDev& base) const { TickDevGS g; static_cast<TickDev&>(g) = base; g.zg = zg; return g; }
@@ -347,6 +354,10 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (h->external && (!d.skew || params->logger_ticks > 0 || (h->kin && !fusedk))) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }
     if (planned && (!d.skew || !fusedk)) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }      // (checked above, before any allocation)
     if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); }
+    if (h->external && h->kin) {
+        A_(h->sens_stage, B * (2 * kDof + 12)); A_(h->feedback_fail, B);
+        if (rc == WCQP_OK && hipEventCreateWithFlags(&h->run_done, hipEventDisableTiming) != hipSuccess) rc = WCQP_E_HIP;
+    }
     if (reactive) { d.reactive = 1; d.k_dcm = params->k_dcm; }
     // the DCM velocity: the reactive controller's input, and with gain scheduling the stance flag's (MPC handles then read it too)
     if (reactive || gs) { double* vel = nullptr; A_(vel, B * d.traj_len * 2); d.dcm_vel = vel; }
@@ -421,6 +432,7 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
     if (h->splice_stage) (void)hipFree(h->splice_stage);
     if (h->splice_done) (void)hipEventDestroy(h->splice_done);
+    if (h->run_done) (void)hipEventDestroy(h->run_done);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->kin) wcqp_kin_destroy(h->kin);
     if (h->mpc) wcqp_mpc_destroy(h->mpc);
@@ -611,6 +623,14 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     WCQP_HIP_TRY(hipMemset(d.mpc_fail, 0, B * 8)); WCQP_HIP_TRY(hipMemset(d.ik_fail, 0, B * 8));
     WCQP_HIP_TRY(hipMemset(d.hot_try, 0, B * 8)); WCQP_HIP_TRY(hipMemset(d.hot_hit, 0, B * 8));
     WCQP_HIP_TRY(hipMemset(h->ik_lo, 0, B * 4)); WCQP_HIP_TRY(hipMemset(h->ik_up, 0, B * 4));      // no previous active set at tick 0
+    if (h->feedback_fail) WCQP_HIP_TRY(hipMemset(h->feedback_fail, 0, B * 8));
+    if (h->external) {
+        h->meas0.resize(B * 6);
+        for (size_t i = 0; i < B; ++i)
+            for (int ax = 0; ax < 2; ++ax) {
+                h->meas0[i * 6 + ax] = in->dcm0[2 * i + ax]; h->meas0[i * 6 + 2 + ax] = in->com0[2 * i + ax]; h->meas0[i * 6 + 4 + ax] = in->u_init[2 * i + ax];
+            }
+    }
     // (hipMemset does not wait, and the copies / kernels above ran on the NULL stream: the run call that follows may name a non-blocking
     // stream - wcqp_stream_create makes such - which would not wait for them either)
     WCQP_HIP_TRY(hipDeviceSynchronize());
@@ -618,6 +638,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     h->ticks_enqueued = 0;
     h->phase = 0;
     h->feedback_set = false;
+    h->run_pending = false;
     return WCQP_OK;
 }
 
@@ -647,6 +668,43 @@ int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const dou
     if (rc != WCQP_OK) return rc;
     // the copy kernel ran on the NULL stream; the tick that consumes the feedback may be enqueued on ANY stream - a non-blocking one
     // (wcqp_stream_create) would not wait for it - so the feedback is in place when this call returns, and the staging rows are free
+    WCQP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return WCQP_OK;
+}
+
+int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
+                                         const double* wrench_right, void* stream) {
+    if (!h || !q_meas || !dq_meas || !wrench_left || !wrench_right) return WCQP_E_INVALID;
+    if (!h->external || !h->kin || !h->feedback_fail) return WCQP_E_UNSUPPORTED;
+    if (!h->uploaded) return WCQP_E_INVALID;
+    const TickDev& d = h->d;
+    SensorDev a{};
+    a.q = q_meas; a.dq = dq_meas; a.wl = wrench_left; a.wr = wrench_right;
+    a.q_des = d.q_des; a.state = d.state; a.phase0 = d.phase0; a.kin_tab = d.kin_tab;
+    a.mst = d.mst; a.hand = d.hand; a.q_meas = h->q_meas; a.ik_fail = d.ik_fail; a.feedback_fail = h->feedback_fail;
+    a.batch = d.batch; a.t = h->ticks_enqueued; a.step_ticks = d.step_ticks; a.kin_rounds = d.kin_rounds; a.omega = d.omega;
+    const int rc = wcqp::sensor_feedback_enqueue(a, (hipStream_t)stream);
+    if (rc != WCQP_OK) return rc;
+    h->feedback_set = true;
+    return WCQP_OK;
+}
+
+int wcqp_tick_set_sensor_feedback_host(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
+                                       const double* wrench_right) {
+    if (!h || !q_meas || !dq_meas || !wrench_left || !wrench_right) return WCQP_E_INVALID;
+    if (!h->external || !h->kin || !h->feedback_fail) return WCQP_E_UNSUPPORTED;
+    if (!h->uploaded) return WCQP_E_INVALID;
+    const size_t B = (size_t)h->d.batch;
+    // the last run may have been enqueued on a non-blocking stream, which the NULL stream below does not wait for: wait for its end
+    if (h->run_pending) { WCQP_HIP_TRY(hipEventSynchronize(h->run_done)); h->run_pending = false; }
+    double* st = h->sens_stage;
+    WCQP_HIP_TRY(hipMemcpy(st, q_meas, B * kDof * 8, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + B * kDof, dq_meas, B * kDof * 8, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 2 * B * kDof, wrench_left, B * 48, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 2 * B * kDof + 6 * B, wrench_right, B * 48, hipMemcpyHostToDevice));
+    const int rc = wcqp_tick_set_sensor_feedback_device(h, st, st + B * kDof, st + 2 * B * kDof, st + 2 * B * kDof + 6 * B, nullptr);
+    if (rc != WCQP_OK) return rc;
+    // in place when this call returns: the tick may be enqueued on any stream, and the staging rows are free for the next call
     WCQP_HIP_TRY(hipStreamSynchronize(nullptr));
     return WCQP_OK;
 }
@@ -715,6 +773,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
         if (rc != WCQP_OK) return rc;
         h->phase ^= 1; ++h->ticks_enqueued;
     }
+    if (h->run_done) { WCQP_HIP_TRY(hipEventRecord(h->run_done, s)); h->run_pending = true; }    // (sensor feedback: the host form waits for it)
     guard.armed = false;
     h->feedback_set = false;
     return WCQP_OK;
@@ -786,6 +845,7 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
 
 int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out) {
     if (!h || !out) return WCQP_E_INVALID;
+    if ((out->measured || out->feedback_fail) && !h->external) return WCQP_E_UNSUPPORTED;
     const TickDev& d = h->d;
     const size_t B = (size_t)d.batch;
     WCQP_HIP_TRY(hipDeviceSynchronize());
@@ -813,7 +873,28 @@ int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out) {
     }
     DN_(out->mpc_fail, d.mpc_fail, B * 8); DN_(out->ik_fail, d.ik_fail, B * 8);
     DN_(out->hot_try, d.hot_try, B * 8); DN_(out->hot_hit, d.hot_hit, B * 8); DN_(out->tick, d.tick2 + h->phase, 4);
+    if (out->feedback_fail) {
+        if (h->feedback_fail) WCQP_HIP_TRY(hipMemcpy(out->feedback_fail, h->feedback_fail, B * 8, hipMemcpyDeviceToHost));
+        else std::memset(out->feedback_fail, 0, B * 8);          // (no sensor form without kinematics: nothing was rejected)
+    }
 #undef DN_
+    if (out->measured) {
+        // what the chain of the last executed tick read as measured com / dcm / ZMP: the plant state at the start of tick t in its
+        // hand-off record (parity t & 1; no later tick has run, so no later chain step has overwritten it)
+        if (h->ticks_enqueued == 0) {
+            if (h->meas0.size() != B * 6) return WCQP_E_INVALID;
+            std::memcpy(out->measured, h->meas0.data(), B * 48);
+        } else {
+            std::vector<double> hd(B * kHandLen);
+            WCQP_HIP_TRY(hipMemcpy(hd.data(), d.hand + (size_t)((h->ticks_enqueued - 1) & 1) * B * kHandLen, B * kHandLen * 8, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < B; ++i)
+                for (int ax = 0; ax < 2; ++ax) {
+                    out->measured[i * 6 + ax] = hd[i * kHandLen + 6 + ax];
+                    out->measured[i * 6 + 2 + ax] = hd[i * kHandLen + 4 + ax];
+                    out->measured[i * 6 + 4 + ax] = hd[i * kHandLen + 10 + ax];
+                }
+        }
+    }
     if (out->zmp_gains) {
         if (d.gain_sched) {
             // the smoother output s of the last executed tick -> its gains (the two operations of zmp_gains_at, tick_device.h)
