@@ -539,6 +539,22 @@ typedef struct wcqp_tick_params {
      * handle (there is no tail for the feet).  WCQP_E_INVALID for a value other than 0 / 1 or a non-finite neck_additional_rotation. */
     int32_t planned_trajectories;
     double neck_additional_rotation[9];  /* additional_rotation of qpInverseKinematics.ini, row-major                              */
+    /* Streamed trajectories (0 = off: the handle behaves as before, bit for bit).  A capability of the EXTERNAL plant: on, every tick t
+     * takes its desired stage - the FRONT of the planner's deques, what WalkingModule::updateModule consumes per tick
+     * (WM/src/WalkingModule.cpp:509-511, 689-707, 1085-1165) - from the wcqp_tick_set_desired_* call that preceded it, instead of the
+     * synthetic gait.  The stage supplies what planned_trajectories lists above: the IK's desired feet (state 24..47) and twists (75..86),
+     * the CoM height and its velocity (71, 74), the desired neck orientation RotZ(meanYaw) * neck_additional_rotation (57..65), the
+     * floating-base anchor = the desired pose of the fixed-frame foot, the contact pair, and on a change of pair (and at tick 0) the MPC's
+     * support-polygon rows rebuilt from that stage's feet and foot_rect; with no change of pair the rows stay, whatever the feet do
+     * (...PredictiveController.cpp:364-435).  Nothing is uploaded per stage ([B][T] arrays do not exist), and replanning the feet needs no
+     * merge call: the caller hands over stages of the new plan from the next tick on (the DCM reference's tail still goes through
+     * wcqp_tick_splice_reference, which works on such a handle as on any EXTERNAL one).
+     * phase0, swing_twist, hull_tab_* (may be NULL) and the desired-pose / Rd_neck entries of state0 are ignored at upload.
+     * wcqp_tick_create returns WCQP_E_INVALID for a value other than 0 / 1 or a non-finite neck_additional_rotation, and
+     * WCQP_E_UNSUPPORTED, before anything touches the device, unless plant = EXTERNAL, use_kinematics with the FUSED hand-off actually
+     * taken (an MPC horizon below 56; REACTIVE any), the default / base-eliminated IK algorithm, logger_ticks = 0 and
+     * planned_trajectories = 0. */
+    int32_t streamed_trajectories;
 } wcqp_tick_params;
 #define WCQP_TICK_PLANT_INTERNAL 0
 #define WCQP_TICK_PLANT_EXTERNAL 1
@@ -659,6 +675,29 @@ int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, co
  * at once and the tick may run on any stream. */
 int wcqp_tick_set_sensor_feedback_host(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
                                        const double* wrench_right);
+/* Streamed trajectories (wcqp_tick_params.streamed_trajectories): the desired stage of tick t = the ticks run since the last upload, per
+ * robot - what the reference pops from the front of m_leftTrajectory, m_rightTrajectory, m_leftTwistTrajectory, m_rightTwistTrajectory,
+ * m_leftInContact / m_rightInContact, m_isLeftFixedFrame, m_comHeightTrajectory and m_comHeightVelocity on that tick
+ * (WM/src/WalkingModule.cpp:509-511, 689-707, 1085-1165). */
+typedef struct wcqp_tick_desired {
+    const double* left_pose;  const double* right_pose;    /* [B][12] sole: p 3 | R 9 row-major      */
+    const double* left_twist; const double* right_twist;   /* [B][6]                                 */
+    const uint8_t* contact;                                /* [B] bits as wcqp_tick_inputs.contact   */
+    const double* com_height; const double* com_height_vel;/* [B] or NULL: state0[68], 0             */
+} wcqp_tick_desired;
+/* DEVICE pointers; one kernel on `stream`, nothing retained (the arrays may be reused once it has run).  Order per tick:
+ * wcqp_tick_set_desired_* -> wcqp_tick_set_sensor_feedback_* (it anchors at this stage: WCQP_E_INVALID on a streamed handle whose stage of
+ * tick t has not been set) or wcqp_tick_set_feedback_* (before or after the stage) -> wcqp_tick_run(h, 1, ...), which returns
+ * WCQP_E_INVALID without a stage AND a feedback set since the last tick.  A second call before the run replaces the stage.
+ * WCQP_E_UNSUPPORTED on a handle without the mode; WCQP_E_INVALID before an upload or with a NULL required pointer.
+ * A robot whose stage is invalid - neither foot in contact, a fixed-frame foot that is not in contact, a non-finite value: the rules of
+ * the planned upload - is rejected by the kernel as a bad sensor reading is: it keeps its previous stage, is stopped like a robot whose
+ * IK failed (dq = 0 from tick t on), and wcqp_tick_outputs.feedback_fail counts it; the other robots are unaffected. */
+int wcqp_tick_set_desired_device(wcqp_tick_t h, const wcqp_tick_desired* desired, void* stream);
+/* the same from HOST pointers: checked on the host first (an invalid stage of any robot: WCQP_E_INVALID, the handle unchanged), staged in
+ * device memory the handle allocated at create, and IN PLACE when the call returns - it first waits for the handle's last wcqp_tick_run,
+ * whatever stream that named; the host arrays may be released at once and the tick may run on any stream. */
+int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* desired);
 int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out);             /* synchronises     */
 
 /* The form a tick handle actually took at wcqp_tick_create (the route follows the IK algorithm, the kinematics hand-off and the
@@ -670,6 +709,7 @@ typedef struct wcqp_tick_info {
     int32_t launches_per_tick;  /* kernel launches of a tick that runs alone (the skewed fused kernel: 1)                   */
     int32_t zmp_gain_scheduling;   /* wcqp_tick_params.zmp_gain_scheduling as taken (0 / 1)                                 */
     int32_t planned_trajectories;  /* wcqp_tick_params.planned_trajectories as taken (0 / 1)                                */
+    int32_t streamed_trajectories; /* wcqp_tick_params.streamed_trajectories as taken (0 / 1)                               */
 } wcqp_tick_info;
 int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
 

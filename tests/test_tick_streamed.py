@@ -1,0 +1,550 @@
+"""Streamed trajectories of the closed-loop tick (wcqp_tick_params.streamed_trajectories): an EXTERNAL handle takes the
+desired stage of every tick - feet, twists, contact flags, fixed frame, CoM height - from wcqp_tick_set_desired_*.  CPU: the restatement
+(tests/helpers/streamed_tick.py) against oracle/tick_spec.py and planned_tick, the ABI, the refusals.  GPU: the device against a planned
+INTERNAL handle on the same walk, against the restatement under disturbed feedback, the sensor form on moved feet, replanning, refusals."""
+import contextlib
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import robots
+from helpers import planned_tick as pt
+from helpers import reactive_tick as rt
+from helpers import sensor_feedback as sf
+from helpers import streamed_tick as stt
+from helpers import zmp_gains as zg
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
+K_DCM = {"iCubGazeboV2_5": 1.0, "iCubGenova04": 1.0, "icubGazeboSim": 1.5}
+KEYS = ("u0_log", "dq_log", "q_des", "dcm", "com")
+WALK_T = 880          # the generated walk: a double support of 110 ticks, four steps of 180, then standing
+ROBOT = "iCubGazeboV2_5"
+ADD_ROT = robots.ROBOTS[ROBOT]["additional_rotation"]
+OMEGA = np.sqrt(9.81 / 0.53)
+
+
+def _walk_cpu(wca, B, T, horizon=50, planned=False, **kw):
+    model = wca.synth.icub_like_model()
+    kb = wca.synth.synth_walk_kin_batch(B)
+    poses = pt.poses_host(model, kb)
+    if planned:
+        return model, wca.synth.synth_planned_walk_batch(B, T, poses, kb, horizon=horizon, **kw)
+    return model, wca.synth.synth_walk_batch(B, T, poses, kb, horizon=horizon)
+
+
+def _ik_params(wca, qs, robot):
+    ipar = robots.ik_params(qs, robot, v_max=wca.synth.WALK_VMAX.copy())
+    ipar.joint_reg_deg = wca.synth.WALK_POSTURE_DEG.copy()
+    return ipar
+
+
+def _ik_solver(wca, robot):
+    r = robots.ROBOTS[robot]
+    return wca.IkSolver(form=wca.IK_FORM_QPOASES, neck_weight=r["neck_weight"] * np.eye(3), joint_reg_weights=np.array(r["reg_w"], float),
+                        joint_reg_gains=np.array(r["reg_k"], float), joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG),
+                        v_max=wca.synth.WALK_VMAX.copy(), k_pos_com=r["k_pos_com"], k_pos_foot=r["k_pos_foot"], k_att_foot=r["k_att_foot"],
+                        k_neck=r["k_neck"])
+
+
+def _restate(qs, wca, robot, controller, gs, d, stages, T, horizon=50, external=None, splices=None, vel=None):
+    """run_ticks_streamed with the robot's parameters under the controller's and the schedule's patches"""
+    from oracle import tick_spec as ts
+    R = robots.ROBOTS[robot]
+    p = ts.TickParams(horizon=horizon, k_com=R["k_com"], k_zmp=R["k_zmp"])
+    B = d["q0"].shape[0]
+    with contextlib.ExitStack() as es:
+        if controller == "reactive":
+            es.enter_context(rt.reactive_solve(p, K_DCM[robot], B, vel))
+        if gs:
+            es.enter_context(zg.scheduled_gains(p, B, zg.ZMP_SCHEDULE[robot], vel))
+        return stt.run_ticks_streamed(p, d, stages, T, _ik_params(wca, qs, robot), wca.synth.icub_like_model(), wca.synth.FOOT_RECT,
+                                      R["additional_rotation"], external=external, splices=splices)
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU
+
+def test_restatement_equals_the_external_run_of_tick_spec(wca, qs):
+    """(1) The synthetic gait written out as stages and an `external` dict (a disturbed copy of the internal plant's states, measured
+    joints off the desired ones): the restatement equals tick_spec.run_ticks(kin_model=..., external=...) to 1e-12."""
+    from oracle import tick_spec as ts
+    B, T = 2, 130
+    p = ts.TickParams()
+    model, d = _walk_cpu(wca, B, T)
+    ipar = _ik_params(wca, qs, ROBOT)
+    plan, d2 = pt.synthetic_as_planned(p, d, T + p.horizon + 1, ADD_ROT)
+    stages = stt.stages_of(plan, T)
+    inner = ts.run_ticks(p, d2, T, ipar, kin_model=model, foot_rect=wca.synth.FOOT_RECT)
+    rng = np.random.default_rng(5)
+    ext = dict(dcm=inner["dcm_log"] + 1e-3 * rng.normal(size=(T, B, 2)), com=inner["com_log"] + 1e-4 * rng.normal(size=(T, B, 2)),
+               zmp=inner["zmp_log"] + 1e-3 * rng.normal(size=(T, B, 2)), q=inner["q_log"] + 0.005 * rng.normal(size=(T, B, 23)))
+    ref = ts.run_ticks(p, d2, T, ipar, kin_model=model, foot_rect=wca.synth.FOOT_RECT, external=ext)
+    out = stt.run_ticks_streamed(p, d2, stages, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT, external=ext)
+    for k in KEYS:
+        assert np.abs(out[k] - ref[k]).max() <= 1e-12, k
+    assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
+    assert np.abs(ref["dq_log"]).max() > 1e-3 and np.abs(ref["u0_log"] - inner["u0_log"]).max() > 1e-5
+
+
+def test_restatement_fed_the_internal_plant_equals_the_planned_one(wca, qs):
+    """(2) Run with the internal plant it equals run_ticks_planned; fed that run's own per-tick plant states as `external` it still does."""
+    from oracle import tick_spec as ts
+    B, T = 2, 150
+    model, d = _walk_cpu(wca, B, T, planned=True, yaw_step=(0.03, 0.08))
+    ipar = _ik_params(wca, qs, ROBOT)
+    p = ts.TickParams()
+    ref = pt.run_ticks_planned(p, d, d, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT)
+    stages = stt.stages_of(d, T)
+    a = stt.run_ticks_streamed(p, d, stages, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT)
+    b = stt.run_ticks_streamed(p, d, stages, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT, external=stt.external_of(a))
+    for out in (a, b):
+        for k in KEYS:
+            assert np.abs(out[k] - ref[k]).max() <= 1e-12, k
+        assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
+    assert len({int(x) & 3 for x in d["contact"][0, :T]}) >= 2 and np.abs(ref["dq_log"]).max() > 1e-3
+
+
+def test_robot_in_the_loop_run_is_reproduced_by_its_recording(wca, qs):
+    """The restatement with `sensors` (readings that depend on the run's own past) equals the restatement fed the recorded measured states
+    and joints as fixed `external` arrays: what the device tests of the sensor form rely on."""
+    from oracle import tick_spec as ts
+    B, T = 2, 40
+    model, d = _walk_cpu(wca, B, T, planned=True, yaw_step=(0.03, 0.08))
+    stages = stt.stages_of(d, T)
+    rng = np.random.default_rng(2)
+    noise = 1e-3 * rng.normal(size=(T, B, 23))
+    w = np.zeros((B, 6)); w[:, 2] = 150.0
+
+    def sensors(t, q_des, dq_prev, u_prev):
+        return q_des + noise[t], dq_prev, w, w
+    args = (ts.TickParams(), d, stages, T, _ik_params(wca, qs, ROBOT), model, wca.synth.FOOT_RECT, ADD_ROT)
+    a = stt.run_ticks_streamed(*args, sensors=sensors)
+    b = stt.run_ticks_streamed(*args, external=stt.external_of_sensors(a))
+    for k in KEYS[:3]:
+        assert np.array_equal(a[k], b[k]), k
+    m, _ = stt.sensor_measured(model, stages, 0, d["q0"] + noise[0], np.zeros((B, 23)), w, w, OMEGA)
+    assert np.array_equal(a["measured_log"][0], m) and (a["ik_fail"] == 0).all() and np.abs(a["dq_log"]).max() > 1e-4
+
+
+def test_new_fields_match_the_ctypes_mirror(wca, tmp_path):
+    """(3) Offsets of every new field and struct in include/wcqp.h equal the ctypes mirror's."""
+    capi = wca.capi
+    src = tmp_path / "off.c"
+    fields = [("wcqp_tick_params", "streamed_trajectories", capi.TickParams), ("wcqp_tick_info", "streamed_trajectories", capi.TickInfo)]
+    fields += [("wcqp_tick_desired", k, capi.TickDesired) for k, _ in capi.TickDesired._fields_]
+    structs = (("wcqp_tick_params", capi.TickParams), ("wcqp_tick_info", capi.TickInfo), ("wcqp_tick_desired", capi.TickDesired))
+    body = "".join(f'printf("%zu\\n", offsetof({s}, {f}));\n' for s, f, _ in fields)
+    body += "".join(f'printf("%zu\\n", sizeof({s}));\n' for s, _ in structs)
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "wcqp.h"\nint main(void) {\n' + body + "return 0;\n}\n")
+    exe = tmp_path / "off"
+    subprocess.check_call(["cc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert got == [getattr(cls, f).offset for _, f, cls in fields] + [C.sizeof(cls) for _, cls in structs]
+    for sym in ("wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host"):
+        assert sym in capi.ABI_SYMBOLS and getattr(capi.lib(), sym)
+
+
+def _params(wca, **kw):
+    prm = wca.capi.TickParams()
+    prm.batch, prm.max_ticks, prm.step_ticks, prm.ds_ticks = 4, 10, 180, 110
+    prm.mpc.horizon, prm.mpc.sampling_time, prm.mpc.com_height, prm.mpc.gravity = 50, 0.01, 0.53, 9.81
+    prm.ik.dof, prm.use_kinematics, prm.kin_handoff, prm.streamed_trajectories, prm.plant = 23, 1, 0, 1, 1
+    for k in range(9):
+        prm.neck_additional_rotation[k] = float(k % 4 == 0)
+    for k, v in kw.items():
+        if "." in k:
+            a, b = k.split(".")
+            setattr(getattr(prm, a), b, v)
+        else:
+            setattr(prm, k, v)
+    return prm
+
+
+@pytest.mark.parametrize("bad", [dict(plant=0), dict(use_kinematics=0), dict(kin_handoff=1), dict(kin_handoff=2), dict(logger_ticks=5),
+                                 dict(planned_trajectories=1, plant=0), dict(planned_trajectories=1), {"ik.algorithm": 4}, {"ik.algorithm": 2},
+                                 {"mpc.horizon": 200}, {"mpc.horizon": 56}])
+def test_create_refuses_before_the_device(wca, bad):
+    """(4) Every refused combination is WCQP_E_UNSUPPORTED before anything touches the device (so with or without a GPU)."""
+    h = C.c_void_p()
+    assert wca.capi.lib().wcqp_tick_create(C.byref(_params(wca, **bad)), C.byref(h)) == WCQP_E_UNSUPPORTED and not h
+
+
+def test_create_refuses_bad_values(wca):
+    h = C.c_void_p()
+    assert wca.capi.lib().wcqp_tick_create(C.byref(_params(wca, streamed_trajectories=2)), C.byref(h)) == WCQP_E_INVALID and not h
+    assert wca.capi.lib().wcqp_tick_create(C.byref(_params(wca, streamed_trajectories=-1)), C.byref(h)) == WCQP_E_INVALID and not h
+    prm = _params(wca)
+    prm.neck_additional_rotation[4] = float("nan")
+    assert wca.capi.lib().wcqp_tick_create(C.byref(prm), C.byref(h)) == WCQP_E_INVALID and not h
+
+
+def test_binding_refuses_bad_arguments(wca):
+    mpc, ik = wca.MpcSolver.__new__(wca.MpcSolver), wca.IkSolver.__new__(wca.IkSolver)
+    mpc.params = wca.capi.MpcParams(); ik.params = wca.capi.IkParams(); ik.dof = 23
+    with pytest.raises(ValueError, match="external"):
+        wca.TickPipeline(4, 10, mpc, ik, streamed_trajectories=True, neck_additional_rotation=np.eye(3))
+    with pytest.raises(ValueError, match="neck_additional_rotation"):
+        wca.TickPipeline(4, 10, mpc, ik, streamed_trajectories=True, external_feedback=True)
+    with pytest.raises(ValueError, match="kinematics"):
+        wca.TickPipeline(4, 10, mpc, ik, streamed_trajectories=True, external_feedback=True, neck_additional_rotation=np.eye(3))
+    with pytest.raises(ValueError, match="exclude"):
+        wca.TickPipeline(4, 10, mpc, ik, streamed_trajectories=True, planned_trajectories=True, external_feedback=True,
+                         neck_additional_rotation=np.eye(3))
+    pipe = wca.TickPipeline.__new__(wca.TickPipeline)
+    pipe.batch, pipe._h = 4, None
+    good = [np.zeros((4, 12)), np.zeros((4, 12)), np.zeros((4, 6)), np.zeros((4, 6)), np.full(4, 7, np.uint8)]
+    for k, bad, what in ((0, np.zeros((4, 11)), "left_pose"), (2, np.zeros((4, 6), np.float32), "left_twist"), (4, np.full(4, 7, np.int32), "contact"),
+                         (3, np.zeros((3, 6)), "right_twist")):
+        x = list(good)
+        x[k] = bad
+        with pytest.raises(ValueError, match=what):
+            pipe.set_desired_host(*x)
+    with pytest.raises(ValueError, match="com_height"):
+        pipe.set_desired_host(*good, com_height=np.zeros(3))
+    with pytest.raises(ValueError, match="right_pose"):
+        pipe.set_desired_device(8, 0, 8, 8, 8)
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+
+def _kin(wca):
+    return wca.KinModel(wca.synth.icub_like_model())
+
+
+def _pipe(wca, B, T, robot, controller, gs, horizon=50, mode="streamed", **kw):
+    R = robots.ROBOTS[robot]
+    ctl = dict(dcm_controller="reactive", k_dcm=K_DCM[robot]) if controller == "reactive" else {}
+    sch = dict(zmp_gain_scheduling=True, **zg.ZMP_SCHEDULE[robot]) if gs else {}
+    neck = np.array(R["additional_rotation"])
+    md = dict(streamed=dict(streamed_trajectories=True, external_feedback=True, neck_additional_rotation=neck),
+              planned=dict(planned_trajectories=True, neck_additional_rotation=neck), external=dict(external_feedback=True))[mode]
+    return wca.TickPipeline(B, T, wca.MpcSolver(horizon=horizon), _ik_solver(wca, robot), log_ticks=T, k_com=R["k_com"], k_zmp=R["k_zmp"],
+                            kin=_kin(wca), **ctl, **sch, **md, **kw)
+
+
+def _stage(stages, t):
+    return tuple(stages[k][t] for k in ("left_pose", "right_pose", "left_twist", "right_twist", "contact")) + \
+           (stages["com_height"][t] if "com_height" in stages else None, stages["com_height_vel"][t] if "com_height_vel" in stages else None)
+
+
+def _upload_streamed(pipe, d, vel=True):
+    pipe.upload({k: d[k] for k in ("ref_traj", "state0", "q0", "dcm0", "com0", "u_init")}, dcm_vel_traj=d.get("dcm_vel_traj") if vel else None)
+
+
+def _run_streamed(pipe, stages, ext, T, t0=0, stream=0):
+    """ticks t0 .. T - 1: the stage, the plain feedback of `ext`, one tick"""
+    for t in range(t0, T):
+        pipe.set_desired_host(*_stage(stages, t))
+        pipe.set_feedback_host(ext["dcm"][t], ext["com"][t], ext["zmp"][t], ext["q"][t] if ext.get("q") is not None else None)
+        pipe.run(1, stream=stream)
+
+
+def _close(out, ref, dq_tol=1e-9):
+    assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
+    for k, tol in (("u0_log", 1e-9), ("dq_log", dq_tol), ("q_des", 1e-9)):
+        err = np.abs(out[k] - ref[k]).max()
+        print(k, err)
+        assert err <= tol, (k, err)
+
+
+@pytest.fixture(scope="module")
+def walks(wca):
+    """the 4-step forward-and-turning walk of three robots per MPC horizon"""
+    cache = {}
+
+    def get(horizon):
+        if horizon not in cache:
+            cache[horizon] = _walk_cpu(wca, 3, WALK_T, horizon=horizon, planned=True, yaw_step=(0.03, 0.08))[1]
+        return cache[horizon]
+    return get
+
+
+@pytest.fixture(scope="module")
+def internal_run(wca, qs, walks):
+    """the restatement of the walk with the internal plant, per configuration: its per-tick plant states are what the streamed handles are fed"""
+    cache = {}
+
+    def get(robot, controller, horizon, gs):
+        key = (robot, controller, horizon, gs)
+        if key not in cache:
+            d = walks(horizon)
+            cache[key] = _restate(qs, wca, robot, controller, gs, d, stt.stages_of(d, WALK_T), WALK_T, horizon, vel=d["dcm_vel_traj"])
+            assert (cache[key]["ik_fail"] == 0).all() and (cache[key]["mpc_fail"] == 0).all()
+        return cache[key]
+    return get
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("gs", [False, True], ids=["fixed_gains", "gain_scheduling"])
+@pytest.mark.parametrize("controller,horizon", [("mpc", 50), ("reactive", 50), ("reactive", 200)])
+@pytest.mark.parametrize("robot", robots.NAMES)
+def test_same_walk_two_handles(wca, walks, internal_run, robot, controller, horizon, gs):
+    """(5) The walk streamed tick by tick into an EXTERNAL handle, fed the internal plant's states (q_meas = NULL), against a planned
+    INTERNAL handle running the same walk on the device: u0_log, dq_log, q_des within 1e-9, equal fail counts."""
+    d = walks(horizon)
+    B, T = d["q0"].shape[0], WALK_T
+    stages = stt.stages_of(d, T)
+    flags = stages["contact"].astype(int)
+    for i in range(B):
+        assert (np.diff(flags[:, i] & 3) != 0).sum() >= 3 and set(flags[:, i] & 4) == {0, 4}
+    for f in ("left_pose", "right_pose"):
+        assert (np.linalg.norm(stages[f][T - 1, :, :2] - stages[f][0, :, :2], axis=1) > 0.05).all()
+    ext = stt.external_of(internal_run(robot, controller, horizon, gs))
+    a = _pipe(wca, B, T, robot, controller, gs, horizon, mode="planned")
+    a.upload(d, dcm_vel_traj=d["dcm_vel_traj"], **{k: d[k] for k in ("left_traj", "right_traj", "left_twist", "right_twist", "contact")})
+    a.run(T)
+    oa = a.download()
+    b = _pipe(wca, B, T, robot, controller, gs, horizon)
+    info = b.info()
+    assert info["streamed_trajectories"] and not info["planned_trajectories"] and info["kin_handoff"] == "fused" and info["ticks_per_launch"] == 1
+    assert not a.info()["streamed_trajectories"]
+    _upload_streamed(b, d)
+    _run_streamed(b, stages, ext, T)
+    ob = b.download()
+    _close(ob, oa)
+    assert (oa["ik_fail"] == 0).all() and (oa["mpc_fail"] == 0).all() and ob["feedback_fail"].sum() == 0
+    assert np.abs(oa["dq_log"]).max() > 1e-2
+
+
+DIST_T, DIST_B = 330, 5          # through the first double support, the first step and into the second (a switch of the fixed frame)
+
+
+def _disturbed(qs, wca, controller, gs, d, stages, T):
+    """a disturbed DCM, a ZMP that is not the previous command, measured joints off the desired ones - fixed arrays, seeded"""
+    inner = _restate(qs, wca, ROBOT, controller, gs, d, stages, T, vel=d["dcm_vel_traj"])
+    B = d["q0"].shape[0]
+    rng = np.random.default_rng(17)
+    tt = np.arange(T)[:, None, None]
+    ext = dict(dcm=inner["dcm_log"] + 1.5e-3 * np.sin(0.05 * tt + rng.uniform(0, 6, size=(1, B, 2))),
+               com=inner["com_log"] + 2e-4 * rng.normal(size=(T, B, 2)),
+               zmp=inner["zmp_log"] + 1e-3 * rng.normal(size=(T, B, 2)),
+               q=inner["q_log"] + 0.004 * rng.normal(size=(T, B, 23)))
+    ref = _restate(qs, wca, ROBOT, controller, gs, d, stages, T, external=ext, vel=d["dcm_vel_traj"])
+    return ext, ref
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("gs", [False, True], ids=["fixed_gains", "gain_scheduling"])
+@pytest.mark.parametrize("controller", ["mpc", "reactive"])
+def test_disturbed_feedback_follows_the_restatement(wca, qs, controller, gs):
+    """(6) B = 5: u0_log / q_des to 1e-9, dq_log to 1e-8, identical failure counts, and the robots move."""
+    B, T = DIST_B, DIST_T
+    _, d = _walk_cpu(wca, B, T, planned=True, yaw_step=(0.03, 0.08))
+    stages = stt.stages_of(d, T)
+    ext, ref = _disturbed(qs, wca, controller, gs, d, stages, T)
+    assert (ref["ik_fail"] == 0).all() and (ref["mpc_fail"] == 0).all()
+    pipe = _pipe(wca, B, T, ROBOT, controller, gs)
+    _upload_streamed(pipe, d)
+    _run_streamed(pipe, stages, ext, T)
+    out = pipe.download()
+    _close(out, ref, dq_tol=1e-8)
+    assert out["feedback_fail"].sum() == 0
+    assert np.abs(out["dq_log"]).max() > 1e-2
+    assert np.abs(out["measured"] - np.concatenate([ext["dcm"][T - 1], ext["com"][T - 1], ext["zmp"][T - 1]], 1)).max() == 0.0
+
+
+def _sensor_case(wca, qs, d):
+    """The run of test 7, restated with the robot in the loop: the walk up to three ticks past the second switch of the fixed-frame foot that
+    follows the first step, every tick sensor-fed.  The readings are what a robot that tracks its commands reports, plus seeded noise: the
+    desired joints and the previous joint velocities of the run itself, wrenches that load the feet in contact and put each loaded foot's
+    ZMP where the previous command is (through the stage's desired soles).  (Feeding a tick of such a run the synthetic LIPM plant's state
+    instead is no option: its CoM lies 4 to 9 cm from the kinematic one, a step the IK cannot follow.)  Returns T, the stages, the ticks
+    within two of either switch, and the restated run with its readings and measured states."""
+    from oracle import tick_spec as ts
+    B = d["q0"].shape[0]
+    stages = stt.stages_of(d, WALK_T)
+    side = stt.stage_side(stages["contact"])                       # [T][B]
+    sw = [t for t in range(1, WALK_T) if (side[t] != side[t - 1]).any()]
+    moved = [t for t in sw if np.abs(stages["left_pose"][t] - stages["left_pose"][0]).max() > 1e-3
+             or np.abs(stages["right_pose"][t] - stages["right_pose"][0]).max() > 1e-3]
+    assert len(moved) >= 2
+    s1, s2 = moved[0], moved[1]
+    assert (side[s1 - 1] != side[s1]).all() and (side[s2 - 1] != side[s2]).all() and (side[s1] != side[s2]).all()      # both directions
+    T = s2 + 3
+    check_ticks = sorted(set(range(s1 - 2, s1 + 3)) | set(range(s2 - 2, s2 + 3)))
+    rng = np.random.default_rng(23)
+    qn, dqn = 1e-3 * rng.normal(size=(T, B, 23)), 2e-3 * rng.normal(size=(T, B, 23))
+    wn = rng.normal(size=(T, 2, B, 6)) * np.array([5.0, 5.0, 2.0, 0.05, 0.05, 0.5])
+
+    def sensors(t, q_des, dq_prev, u_prev):
+        code = (stages["contact"][t].astype(int) & 3) - 1
+        w = []
+        for f, pose in enumerate((stages["left_pose"][t], stages["right_pose"][t])):
+            loaded = code != 1 - f
+            fz = np.where(loaded, np.where(code == 2, 150.0, 300.0) + wn[t, f, :, 2], 0.0)
+            R = pose[:, 3:].reshape(B, 3, 3)
+            z = np.einsum("bji,bj->bi", R, np.concatenate([u_prev, np.zeros((B, 1))], 1) - pose[:, :3])      # the command in the sole frame
+            wf = wn[t, f].copy()
+            wf[:, 2] = fz; wf[:, 3] += z[:, 1] * fz; wf[:, 4] += -z[:, 0] * fz
+            w.append(wf)
+        return q_des + qn[t], dq_prev + dqn[t], w[0], w[1]
+    R = robots.ROBOTS[ROBOT]
+    p = ts.TickParams(horizon=50, k_com=R["k_com"], k_zmp=R["k_zmp"])
+    ref = stt.run_ticks_streamed(p, d, stages, T, _ik_params(wca, qs, ROBOT), wca.synth.icub_like_model(), wca.synth.FOOT_RECT,
+                                 R["additional_rotation"], sensors=sensors)
+    return T, stages, check_ticks, ref
+
+
+@pytest.mark.gpu
+def test_sensor_form_on_moved_feet(wca, qs, walks):
+    """(7) A sensor-fed walk across the two switches of the fixed-frame foot that follow the first step - the desired soles are no longer the
+    uploaded ones there: on the ticks around both switches download()["measured"] equals sensor_feedback.evaluate with the stage's sole
+    and side to 1e-12, and a handle fed those values through the plain form on those ticks is bit for bit the sensor-fed one.  The restated
+    run ends without a failure, and the device follows it (bars of 6)."""
+    d = walks(50)
+    B = d["q0"].shape[0]
+    T, stages, check_ticks, ref = _sensor_case(wca, qs, d)
+    assert (ref["ik_fail"] == 0).all() and (ref["mpc_fail"] == 0).all() and np.abs(ref["dq_log"]).max() > 1e-2
+    readings, restated = ref["readings"], ref["measured_log"]
+    side = stt.stage_side(stages["contact"][check_ticks])
+    assert set(side[:, 0]) == {0, 1} and max(np.abs(stages[f][check_ticks[0]] - stages[f][0]).max() for f in ("left_pose", "right_pose")) > 1e-3
+    a = _pipe(wca, B, WALK_T, ROBOT, "mpc", False)          # (the walk's arrays are WALK_T ticks long; T of them run)
+    _upload_streamed(a, d, vel=False)
+    measured = {}
+    for t in range(T):
+        a.set_desired_host(*_stage(stages, t))
+        a.set_sensor_feedback_host(*readings[t])
+        a.run(1)
+        if t in check_ticks:
+            measured[t] = a.download()["measured"]
+            err = np.abs(measured[t] - restated[t]).max()
+            print("tick", t, "measured error", err)
+            assert err <= 1e-12, (t, err)
+    oa = a.download()
+    assert oa["feedback_fail"].sum() == 0
+    _close({k: (oa[k][:T] if k.endswith("_log") else oa[k]) for k in oa}, ref, dq_tol=1e-8)
+    b = _pipe(wca, B, WALK_T, ROBOT, "mpc", False)
+    _upload_streamed(b, d, vel=False)
+    for t in range(T):
+        b.set_desired_host(*_stage(stages, t))
+        m = measured.get(t)
+        if m is not None:
+            b.set_feedback_host(m[:, 0:2], m[:, 2:4], m[:, 4:6], readings[t][0])       # the plain form, fed what the sensor form evaluated
+        else:
+            b.set_sensor_feedback_host(*readings[t])
+        b.run(1)
+    ob = b.download()
+    for k in ("u0_log", "dq_log", "q_des", "ik_fail", "mpc_fail", "measured"):
+        assert np.array_equal(oa[k], ob[k]), k
+
+
+@pytest.mark.gpu
+def test_replanning(wca, qs):
+    """(8) Two walks that differ in step length and turning rate.  At tick k of the first double support the caller splices the second
+    walk's DCM reference and hands over the second walk's stages from then on: the run equals the restatement (bars of 6) and ends at the
+    second walk's goal, not the first's."""
+    B, T, k = 3, WALK_T, 60
+    model, d1 = _walk_cpu(wca, B, T, planned=True, step_length=(0.025, 0.035), yaw_step=(0.03, 0.08))
+    _, d2 = _walk_cpu(wca, B, T, planned=True, step_length=(0.04, 0.045), yaw_step=(-0.06, -0.02))
+    s1, s2 = stt.stages_of(d1, T), stt.stages_of(d2, T)
+    for key in ("left_pose", "right_pose", "contact"):
+        assert np.array_equal(s1[key][:k + 1], s2[key][:k + 1])          # both still hold the starting feet at tick k
+    assert (s1["contact"][:k + 1] & 3 == 3).all()
+    stages = stt.concat_stages(s1, s2, k)
+    tail = np.ascontiguousarray(d2["ref_traj"][:, k:])
+    splices = {k: (k, tail)}
+    inner = _restate(qs, wca, ROBOT, "mpc", False, d1, stages, T, splices=splices)
+    ext = stt.external_of(inner)
+    ref = _restate(qs, wca, ROBOT, "mpc", False, d1, stages, T, external=ext, splices=splices)
+    assert (ref["ik_fail"] == 0).all() and (ref["mpc_fail"] == 0).all()
+    pipe = _pipe(wca, B, T, ROBOT, "mpc", False)
+    _upload_streamed(pipe, d1, vel=False)
+    _run_streamed(pipe, stages, ext, k)
+    pipe.splice_reference(k, tail)
+    _run_streamed(pipe, stages, ext, T, t0=k)
+    out = pipe.download()
+    _close(out, ref, dq_tol=1e-8)
+    assert out["feedback_fail"].sum() == 0 and np.abs(out["dq_log"]).max() > 1e-2
+    P, Rw = pt.sole_poses(model, out["q_des"], d2, T - 1)
+    for f in range(2):
+        assert np.abs(P[:, f] - d2["goal"][:, f, :3]).max() <= 1e-5
+        assert (np.abs(P[:, f] - d1["goal"][:, f, :3]).max(axis=1) > 1e-2).all()
+
+
+def _clean_run(wca, d, stages, ext, T, stream=0):
+    pipe = _pipe(wca, d["q0"].shape[0], T, ROBOT, "mpc", False)
+    _upload_streamed(pipe, d)
+    _run_streamed(pipe, stages, ext, T, stream=stream)
+    return pipe.download()
+
+
+@pytest.mark.gpu
+def test_refusals_order_and_stream(wca, qs):
+    """(9, 10) Run without a stage; sensor feedback before the stage; set_desired on a plain EXTERNAL handle, on a planned one and before an
+    upload; NULL pointers; an invalid stage through the host form leaves the handle unchanged (the valid stage set next gives the
+    un-tampered run bit for bit); the device form (a process of its own, tests/helpers/streamed_device_check.py): equal to the host form,
+    one robot's invalid stage stops and counts that robot alone.  The host form followed by a run on a wcqp_stream_create stream equals the
+    NULL-stream run."""
+    B, T = 6, 24
+    _, d = _walk_cpu(wca, B, T, planned=True, yaw_step=(0.03, 0.08))
+    stages = stt.stages_of(d, T)
+    ext = stt.external_of(_restate(qs, wca, ROBOT, "mpc", False, d, stages, T))
+    z23, z6 = np.zeros((B, 23)), np.zeros((B, 6))
+    pipe = _pipe(wca, B, T, ROBOT, "mpc", False)
+    with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+        pipe.set_desired_host(*_stage(stages, 0))                       # before an upload
+    _upload_streamed(pipe, d)
+    pipe.set_feedback_host(ext["dcm"][0], ext["com"][0], ext["zmp"][0])
+    with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+        pipe.run(1)                                                     # feedback, but no stage
+    _upload_streamed(pipe, d)
+    with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+        pipe.set_sensor_feedback_host(d["q0"], z23, *sf.wrenches(np.random.default_rng(1), B))      # the anchor's stage is not there yet
+    pipe.set_desired_host(*_stage(stages, 0))
+    with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+        pipe.run(1)                                                     # a stage, but no feedback
+    for k in (0, 1, 2, 3, 4):
+        ptrs = [8] * 5
+        ptrs[k] = 0
+        des = wca.capi.TickDesired(*[p or None for p in ptrs])
+        assert wca.capi.lib().wcqp_tick_set_desired_device(pipe._h, C.byref(des), None) == WCQP_E_INVALID
+        assert wca.capi.lib().wcqp_tick_set_desired_host(pipe._h, C.byref(des)) == WCQP_E_INVALID
+    plain = _pipe(wca, B, T, ROBOT, "mpc", False, mode="external")
+    planned = _pipe(wca, B, T, ROBOT, "mpc", False, mode="planned")
+    for other in (plain, planned):
+        with pytest.raises(wca.WcqpError, match=r"\(-2\)"):
+            other.set_desired_host(*_stage(stages, 0))
+    # the splice works on a streamed handle as on any EXTERNAL one
+    pipe.splice_reference(5, d["ref_traj"][:, 5:15])
+    # an invalid stage through the host form: refused, the handle unchanged
+    clean = _clean_run(wca, d, stages, ext, T)
+    assert clean["feedback_fail"].sum() == 0
+    tam = _pipe(wca, B, T, ROBOT, "mpc", False)
+    _upload_streamed(tam, d)
+    for t in range(T):
+        good = _stage(stages, t)
+        for mutate in ("no_contact", "fixed_in_air", "nan", "nan_height"):
+            bad = [np.array(x, copy=True) if x is not None else None for x in good]
+            if mutate == "no_contact":
+                bad[4][2] = 4
+            elif mutate == "fixed_in_air":
+                bad[4][1] = 2 | 4
+            elif mutate == "nan":
+                bad[2][3, 1] = np.nan
+            else:
+                bad[5] = np.full(B, np.inf)
+            if t in (0, 7, T - 1):
+                with pytest.raises(wca.WcqpError, match=r"\(-1\)"):
+                    tam.set_desired_host(*bad)
+        tam.set_desired_host(*good)
+        tam.set_feedback_host(ext["dcm"][t], ext["com"][t], ext["zmp"][t])
+        tam.run(1)
+    ot = tam.download()
+    for k in ("u0_log", "dq_log", "q_des", "ik_fail", "mpc_fail", "measured", "feedback_fail"):
+        assert np.array_equal(ot[k], clean[k]), k
+    # (10) the host form, then the run on a non-blocking stream
+    s = wca.capi.stream_create()
+    try:
+        onb = _clean_run(wca, d, stages, ext, T, stream=s)
+    finally:
+        wca.capi.stream_synchronize(s)
+        wca.capi.stream_destroy(s)
+    for k in ("u0_log", "dq_log", "q_des", "ik_fail", "mpc_fail", "measured"):
+        assert np.array_equal(onb[k], clean[k]), k
+    # the device form
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "streamed_device_check.py")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "streamed device ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_create", "wcqp_tick_destroy", "wcqp_tick_upload", "wcqp_tick_run", "wcqp_tick_download", "wcqp_tick_splice_reference",
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
+    "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
 )
@@ -169,7 +170,8 @@ class TickParams(C.Structure):
                 ("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("logger_ticks", C.c_int32), ("plant", C.c_int32),
                 ("dcm_controller", C.c_int32), ("k_dcm", C.c_double),
                 ("zmp_gain_scheduling", C.c_int32), ("k_com_stance", C.c_double), ("k_zmp_stance", C.c_double), ("zmp_smoothing_time", C.c_double),
-                ("planned_trajectories", C.c_int32), ("neck_additional_rotation", C.c_double * 9)]
+                ("planned_trajectories", C.c_int32), ("neck_additional_rotation", C.c_double * 9),
+                ("streamed_trajectories", C.c_int32)]
 
 
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
@@ -178,7 +180,12 @@ KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1
 
 class TickInfo(C.Structure):
     _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32),
-                ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32)]
+                ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32), ("streamed_trajectories", C.c_int32)]
+
+
+class TickDesired(C.Structure):
+    """wcqp_tick_desired: the desired stage of one tick (streamed trajectories)."""
+    _fields_ = [(k, C.c_void_p) for k in ("left_pose", "right_pose", "left_twist", "right_twist", "contact", "com_height", "com_height_vel")]
 
 
 class TickInputs(C.Structure):
@@ -238,6 +245,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_set_feedback_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wcqp_tick_set_sensor_feedback_device.argtypes = [C.c_void_p] * 6
         L.wcqp_tick_set_sensor_feedback_host.argtypes = [C.c_void_p] * 5
+        L.wcqp_tick_set_desired_device.argtypes = [C.c_void_p, C.POINTER(TickDesired), C.c_void_p]
+        L.wcqp_tick_set_desired_host.argtypes = [C.c_void_p, C.POINTER(TickDesired)]
         L.wcqp_tick_get_info.argtypes = [C.c_void_p, C.POINTER(TickInfo)]
         L.wcqp_qp_enqueue_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.POINTER(C.c_int32)]
         L.wcqp_qp_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.c_int32, C.POINTER(C.c_void_p)]
@@ -460,7 +469,7 @@ class TickPipeline:
                  ticks_per_launch: int = 0, logger_ticks: int = 0, external_feedback: bool = False,
                  dcm_controller: str = "mpc", k_dcm: Optional[float] = None, zmp_gain_scheduling: bool = False,
                  k_com_stance: Optional[float] = None, k_zmp_stance: Optional[float] = None, zmp_smoothing_time: Optional[float] = None,
-                 planned_trajectories: bool = False, neck_additional_rotation=None):
+                 planned_trajectories: bool = False, neck_additional_rotation=None, streamed_trajectories: bool = False):
         """kin: a KinModel -> per-tick kinematics (Jacobians, actual poses and hull rows rebuilt every tick from the
         integrated joint state with the base anchored at the stance foot; upload() then ignores J_* / hull_tab_*).
         dcm_controller: "mpc" (the DCM-MPC, the reference's use_mpc 1) or "reactive" (WalkingDCMReactiveController, the
@@ -468,7 +477,9 @@ class TickPipeline:
         zmp_gain_scheduling: the reference's useGainScheduling 1 (zmpControllerParams.ini) - k_com / k_zmp are then the walking gains
         and k_com_stance, k_zmp_stance and zmp_smoothing_time (kCoM_stance, kZMP_stance, smoothingTime) are needed.
         planned_trajectories: every tick follows the planner's feet, twists, contact flags and CoM height (upload(left_traj=...)) instead of
-        the synthetic gait; needs kin (the FUSED hand-off) and neck_additional_rotation (additional_rotation of qpInverseKinematics.ini, 3 x 3)."""
+        the synthetic gait; needs kin (the FUSED hand-off) and neck_additional_rotation (additional_rotation of qpInverseKinematics.ini, 3 x 3).
+        streamed_trajectories (with external_feedback): every tick takes its desired stage from the set_desired_host / set_desired_device call
+        in front of it - per tick set_desired -> set_sensor_feedback (or set_feedback) -> run(1); needs kin and neck_additional_rotation too."""
         if dcm_controller not in ("mpc", "reactive"):
             raise ValueError(f"dcm_controller must be 'mpc' or 'reactive', not {dcm_controller!r}")
         self.reactive = dcm_controller == "reactive"
@@ -480,11 +491,20 @@ class TickPipeline:
         if self.gain_sched and not (np.isfinite(k_com_stance) and np.isfinite(k_zmp_stance) and np.isfinite(zmp_smoothing_time) and zmp_smoothing_time > 0):
             raise ValueError("ZMP gain scheduling needs finite stance gains and a finite zmp_smoothing_time > 0 (wcqp_tick_create: WCQP_E_INVALID)")
         self.planned = bool(planned_trajectories)
+        if self.planned and streamed_trajectories:
+            raise ValueError("streamed_trajectories and planned_trajectories exclude each other")
         if self.planned and neck_additional_rotation is None:
             raise ValueError("planned trajectories need neck_additional_rotation (additional_rotation of qpInverseKinematics.ini)")
         if self.planned and kin is None:
             raise ValueError("planned trajectories need per-tick kinematics (kin=KinModel(...)): with constant Jacobians the feet never move")
-        neck = np.asarray(neck_additional_rotation if self.planned else np.eye(3), float).reshape(-1)
+        self.streamed = bool(streamed_trajectories)
+        if self.streamed and not external_feedback:
+            raise ValueError("streamed trajectories are a mode of the external plant (external_feedback=True)")
+        if self.streamed and neck_additional_rotation is None:
+            raise ValueError("streamed trajectories need neck_additional_rotation (additional_rotation of qpInverseKinematics.ini)")
+        if self.streamed and kin is None:
+            raise ValueError("streamed trajectories need per-tick kinematics (kin=KinModel(...)): with constant Jacobians the feet never move")
+        neck = np.asarray(neck_additional_rotation if (self.planned or self.streamed) else np.eye(3), float).reshape(-1)
         if neck.shape != (9,) or not np.all(np.isfinite(neck)):
             raise ValueError("neck_additional_rotation must be a finite 3 x 3 matrix")
         self.batch, self.max_ticks, self.log_ticks, self.dof = batch, max_ticks, log_ticks, ik.dof
@@ -500,7 +520,8 @@ class TickPipeline:
                                  int(bool(external_feedback)), TICK_DCM_REACTIVE if self.reactive else TICK_DCM_MPC,
                                  float(k_dcm) if k_dcm is not None else 0.0, int(self.gain_sched),
                                  float(k_com_stance) if self.gain_sched else 0.0, float(k_zmp_stance) if self.gain_sched else 0.0,
-                                 float(zmp_smoothing_time) if self.gain_sched else 0.0, int(self.planned), (C.c_double * 9)(*neck))
+                                 float(zmp_smoothing_time) if self.gain_sched else 0.0, int(self.planned), (C.c_double * 9)(*neck),
+                                 int(self.streamed))
         self._h = C.c_void_p()
         check(lib().wcqp_tick_create(C.byref(self.params), C.byref(self._h)), "wcqp_tick_create")
         self._keep = None
@@ -529,14 +550,15 @@ class TickPipeline:
             raise ValueError("a planned handle's upload needs " + ", ".join(k for k, v in plan.items() if v is None))
         if not self.planned and any(v is not None for v in list(plan.values()) + [com_height_traj, com_height_vel]):
             raise ValueError("planned trajectories were given to a handle created without planned_trajectories=True")
-        f64 = ("ref_traj", "state0", "q0", "dcm0", "com0", "u_init") + (() if self.planned else ("swing_twist",))
+        nogait = self.planned or getattr(self, "streamed", False)      # (no synthetic gait: phase0 / swing_twist are optional)
+        f64 = ("ref_traj", "state0", "q0", "dcm0", "com0", "u_init") + (() if nogait else ("swing_twist",))
         f64 += () if self.use_kin else ("J_left", "J_right", "J_neck", "J_com")
         if not self.use_kin and (not self.reactive or "hull_tab_A" in data):
             f64 += ("hull_tab_A", "hull_tab_b")
         keep = {k: _f64(data[k]) for k in f64}
         if "hull_tab_A" in keep:
             keep["hull_tab_nc"] = np.ascontiguousarray(data["hull_tab_nc"], dtype=np.int32)
-        if not self.planned or "phase0" in data:
+        if not nogait or "phase0" in data:
             keep["phase0"] = np.ascontiguousarray(data["phase0"], dtype=np.int32)
         assert keep["ref_traj"].shape == (self.batch, self.max_ticks + self.params.mpc.horizon + 1, 2), keep["ref_traj"].shape
         if dcm_vel_traj is not None:
@@ -565,7 +587,7 @@ class TickPipeline:
                                  KIN_HANDOFF_COMPACT: "compact"}[i.kin_handoff],
                     ticks_per_launch=int(i.ticks_per_launch), dcm_controller="reactive" if i.dcm_controller == TICK_DCM_REACTIVE else "mpc",
                     launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling),
-                    planned_trajectories=bool(i.planned_trajectories))
+                    planned_trajectories=bool(i.planned_trajectories), streamed_trajectories=bool(i.streamed_trajectories))
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")
@@ -617,6 +639,57 @@ class TickPipeline:
             else:
                 ptrs.append(int(x))
         check(lib().wcqp_tick_set_sensor_feedback_device(self._h, *[p or None for p in ptrs], stream or None), "wcqp_tick_set_sensor_feedback_device")
+
+    _DESIRED = (("left_pose", 12), ("right_pose", 12), ("left_twist", 6), ("right_twist", 6))
+
+    def set_desired_host(self, left_pose, right_pose, left_twist, right_twist, contact, com_height=None, com_height_vel=None):
+        """Streamed trajectories (wcqp_tick_set_desired_host): the desired stage of the next tick - sole poses [B][12] (p 3 | R 9 row-major),
+        twists [B][6], contact [B] uint8 (bit 0 left, bit 1 right in contact, bit 2 left is the fixed frame), CoM height / velocity [B] or
+        None (state0[68], 0).  Shapes and dtypes are checked here; an invalid stage (no foot in contact, a fixed-frame foot in the air, a
+        non-finite value) is refused by the library with the handle unchanged.  In place when the call returns."""
+        B = self.batch
+        keep = []
+        for (name, w), x in zip(self._DESIRED, (left_pose, right_pose, left_twist, right_twist)):
+            a = np.asarray(x)
+            if a.dtype != np.float64 or a.shape != (B, w):
+                raise ValueError(f"{name} must be float64 of shape {(B, w)}, not {a.dtype} {a.shape}")
+            keep.append(np.ascontiguousarray(a))
+        c = np.asarray(contact)
+        if c.dtype != np.uint8 or c.shape != (B,):
+            raise ValueError(f"contact must be uint8 of shape {(B,)}, not {c.dtype} {c.shape}")
+        keep.append(np.ascontiguousarray(c))
+        for name, x in (("com_height", com_height), ("com_height_vel", com_height_vel)):
+            if x is None:
+                keep.append(None)
+                continue
+            a = np.asarray(x)
+            if a.dtype != np.float64 or a.shape != (B,):
+                raise ValueError(f"{name} must be float64 of shape {(B,)}, not {a.dtype} {a.shape}")
+            keep.append(np.ascontiguousarray(a))
+        des = TickDesired(*[None if a is None else a.ctypes.data for a in keep])
+        check(lib().wcqp_tick_set_desired_host(self._h, C.byref(des)), "wcqp_tick_set_desired_host")
+
+    def set_desired_device(self, left_pose, right_pose, left_twist, right_twist, contact, com_height=None, com_height_vel=None, stream: int = 0):
+        """The same from DEVICE memory: raw addresses, or contiguous torch tensors on the GPU of the shapes above (float64; contact uint8),
+        checked here; enqueue only.  A robot with an invalid stage is rejected on the device (download()["feedback_fail"])."""
+        B = self.batch
+        spec = tuple((n, (B, w), "float64") for n, w in self._DESIRED) + (("contact", (B,), "uint8"), ("com_height", (B,), "float64"),
+                                                                           ("com_height_vel", (B,), "float64"))
+        ptrs = []
+        for (name, shape, dt), x in zip(spec, (left_pose, right_pose, left_twist, right_twist, contact, com_height, com_height_vel)):
+            if x is None or (isinstance(x, int) and x == 0):
+                if name not in ("com_height", "com_height_vel"):
+                    raise ValueError(f"{name} is required")
+                ptrs.append(None)
+            elif hasattr(x, "data_ptr"):
+                import torch
+                if x.dtype != getattr(torch, dt) or tuple(x.shape) != shape or not x.is_contiguous() or not x.is_cuda:
+                    raise ValueError(f"{name} must be a contiguous {dt} device tensor of shape {shape}")
+                ptrs.append(x.data_ptr())
+            else:
+                ptrs.append(int(x))
+        des = TickDesired(*ptrs)
+        check(lib().wcqp_tick_set_desired_device(self._h, C.byref(des), stream or None), "wcqp_tick_set_desired_device")
 
     def splice_reference(self, from_tick: int, ref_tail, stream: int = 0):
         """Trajectory merge: stages [from_tick, from_tick + n) of every instance's DCM reference <- ref_tail[B][n][2]."""

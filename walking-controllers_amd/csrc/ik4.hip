@@ -254,8 +254,8 @@ static int tick_check(const wcqp_tick::TickDevPL& td, const TickVariant& v) {
     if (v.ext && v.jsrc == 1) return WCQP_E_INVALID;          // external feedback: dense Jacobians or fused kinematics
     if ((v.react || v.gs) && !td.dcm_vel) return WCQP_E_INVALID;
     if (v.gs && !td.zg.zs) return WCQP_E_INVALID;
-    // planned trajectories: fused kinematics, no logger rows, the internal plant
-    if (v.pl && (!td.pl.rec || v.jsrc != 2 || v.log || v.ext)) return WCQP_E_INVALID;
+    // planned trajectories (the internal plant) and streamed ones (EXTERNAL): fused kinematics, no logger rows
+    if (v.pl && (!td.pl.rec || v.jsrc != 2 || v.log)) return WCQP_E_INVALID;
     return WCQP_OK;
 }
 

@@ -177,6 +177,9 @@ struct MpcPairArgs {
 // PL (tick kernel with fused kinematics, wcqp_tick_params.planned_trajectories): desired feet, twists, CoM height, neck orientation, the
 // base anchor and the contact pair come from the planner's per-stage records (tick_device.h: plan_*); td is then
 // a TickDevPL, and *gait holds the contact flags of tick t instead of the gait cycle index
+// PL with EXT (wcqp_tick_params.streamed_trajectories): the record is the ONE the caller handed over for this tick (plan_rec<true>); such a
+// launch runs one tick without the chain of the next (do_mpc false: there is no stage t + 1 to read ahead), the prime kernel ran this tick's
+// chain from the same record
 template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false, bool REACT = false, bool GS = false, bool PL = false>
 __device__ __forceinline__
 void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
@@ -192,7 +195,8 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     static_assert(!(TICK && PAIR), "the tick kernel carries its own MPC chain");
     static_assert(TICK || !REACT, "the reactive controller is a tick form");
     static_assert(TICK || !GS, "gain scheduling is a tick form");
-    static_assert(!PL || (TICK && JSRC == 2 && !LOG && !EXT), "planned trajectories: the fused-kinematics tick of the internal plant");
+    static_assert(!PL || (TICK && JSRC == 2 && !LOG), "planned / streamed trajectories: the fused-kinematics tick without logger rows");
+    constexpr bool ST = PL && EXT;          // streamed trajectories: one record per robot (tick_device.h: plan_rec<true>)
     constexpr bool COMPACT = JSRC == 1;
     constexpr bool KINF = JSRC == 2;
     int lane_id = threadIdx.x;
@@ -278,7 +282,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     // kinematics phase.  (The last tick of a launch loads nothing: the next launch reads the flags of its first tick itself.)
     auto pld = [&]() -> const wcqp_tick::TickDevPL& { return static_cast<const wcqp_tick::TickDevPL&>(td); };
     double m_pf = 0.0;
-    if constexpr (PL) { if (do_mpc) m_pf = wcqp_tick::plan_flags_issue(pld(), j, inst, tick_now + 1); }
+    if constexpr (PL) { if (do_mpc) m_pf = wcqp_tick::plan_flags_issue<ST>(pld(), j, inst, tick_now + 1); }
     if constexpr (TICK && GS) {
         if (do_mpc) {
             wcqp_tick::zmp_state_issue(gsd(), inst, zreg);
@@ -355,7 +359,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
             // PL: the planner's fixed-frame foot of tick t (*gait: its flags, carried from the tick before) anchors the base at its desired pose
             // of stage t - the record's lines are in L2 since that tick touched them
             const int side = PL ? wcqp_tick::plan_side(*gait) : (*gait >= td.step_ticks ? 1 : 0);          // (gait: this robot's cycle index (tick + phase0) % (2 step_ticks), carried from tick to tick) 0: left is the stance foot
-            if constexpr (PL) { if (j < 12) S[k_sd(j)] = wcqp_tick::plan_rec(pld(), inst, tick_now)[wcqp_tick::kPlanLeft + side * 12 + j]; }
+            if constexpr (PL) { if (j < 12) S[k_sd(j)] = wcqp_tick::plan_rec<ST>(pld(), inst, tick_now)[wcqp_tick::kPlanLeft + side * 12 + j]; }
             else if (j < 12) S[k_sd(j)] = *at32(state, iu * (unsigned)(kStateLen * 8) + (unsigned)(24 + side * 12) * 8u + j8);                // desired pose of the anchor sole: p (3), R (9)
             const int cs[2] = {j, var1 ? col1 : 0};
             double* TW = S + K_TW;
@@ -690,7 +694,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                     const int cyc1 = *gait + 1 == 2 * td.step_ticks ? 0 : *gait + 1;
                     code1 = wcqp_tick::contact_code_cyc(cyc1, td.step_ticks, td.ds_ticks);
                 }
-                if constexpr (KINF) wcqp_tick::tick_mpc_finish_from<false, GS, PL>(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, m_uy, reinterpret_cast<double (*)[4]>(S + K_MS), code1, noise_base, kg);
+                if constexpr (KINF) wcqp_tick::tick_mpc_finish_from<false, GS, PL, ST>(td, j, inst, live, tick_now + 1, mreg, m_r0, m_ux, m_uy, reinterpret_cast<double (*)[4]>(S + K_MS), code1, noise_base, kg);
                 else wcqp_tick::tick_mpc_finish<false, false, GS>(td, j, inst, live, tick_now + 1, mreg, reinterpret_cast<double (*)[4]>(S + OFF_COL), nullptr, code1, noise_base, kg);
             }
             if (!PL && j < 6) {
@@ -711,7 +715,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
         if constexpr (PL) {
             // the record of stage t: one coalesced 320-byte load over the robot's 16 lanes (L2: the tick before touched its lines), issued
             // behind the chain of tick t + 1 rather than with the pose block - held across the MPC's finish its three doubles cost spills
-            const double* rc = wcqp_tick::plan_rec(pld(), inst, tick_now);
+            const double* rc = wcqp_tick::plan_rec<ST>(pld(), inst, tick_now);
             p_r01 = ld2(rc + 2 * j); p_r2 = rc[32 + (j & 7)];
         }
 #pragma unroll
@@ -1723,7 +1727,7 @@ void ik4_tick_walk(const IkDeviceParams* prm, int batch,
             const long ir = (long)blockIdx.x * 4 + (lane_ >> 4);
             const long i_ = ir < batch ? ir : (long)batch - 1;
             const bool v1_ = j_ < kDof - 16;
-            if constexpr (PL) gait = (int)wcqp_tick::plan_rec(static_cast<const wcqp_tick::TickDevPL&>(td), i_, t0)[wcqp_tick::kPlanFlags];      // the flags of the first tick
+            if constexpr (PL) gait = (int)wcqp_tick::plan_rec<PL && EXT>(static_cast<const wcqp_tick::TickDevPL&>(td), i_, t0)[wcqp_tick::kPlanFlags];      // the flags of the first tick
             else gait = (t0 + td.phase0[i_]) % (2 * td.step_ticks);
             nbase = wcqp_tick::disturbance_base(td.seed, (unsigned long long)(td.first + i_));
             carry[0] = td.q_des[i_ * kDof + j_]; carry[1] = td.q_des[i_ * kDof + (v1_ ? j_ + 16 : 0)];
@@ -1781,7 +1785,10 @@ void tick_variant_visit(const TickVariant& v, F&& f) {
             else f(JsrcC<0>{}, N{}, N{}, r, g, N{});
         }
     };
-    if (v.pl) {       // planned trajectories: fused kinematics, no logger, the internal plant
+    if (v.pl && v.ext) {       // streamed trajectories: fused kinematics, no logger, the EXTERNAL plant
+        if (v.react) { if (v.gs) f(JsrcC<2>{}, N{}, Y{}, Y{}, Y{}, Y{}); else f(JsrcC<2>{}, N{}, Y{}, Y{}, N{}, Y{}); }
+        else { if (v.gs) f(JsrcC<2>{}, N{}, Y{}, N{}, Y{}, Y{}); else f(JsrcC<2>{}, N{}, Y{}, N{}, N{}, Y{}); }
+    } else if (v.pl) {       // planned trajectories: fused kinematics, no logger, the internal plant
         if (v.react) { if (v.gs) f(JsrcC<2>{}, N{}, N{}, Y{}, Y{}, Y{}); else f(JsrcC<2>{}, N{}, N{}, Y{}, N{}, Y{}); }
         else { if (v.gs) f(JsrcC<2>{}, N{}, N{}, N{}, Y{}, Y{}); else f(JsrcC<2>{}, N{}, N{}, N{}, N{}, Y{}); }
     } else if (v.gs) {

@@ -50,14 +50,14 @@ void tick_variant_prime_kernel(TickPrimeRecord<GS, PL> td, int t)
         if constexpr (GS) rd = wcqp_tick::zmp_vel_issue(td, inst, t);
     }
     int code = -1;
-    if constexpr (PL) code = wcqp_tick::plan_code((int)wcqp_tick::plan_rec(td, inst, t)[wcqp_tick::kPlanFlags]);
+    if constexpr (PL) code = wcqp_tick::plan_code((int)wcqp_tick::plan_rec<PL && EXT>(td, inst, t)[wcqp_tick::kPlanFlags]);
     double2 kg = make_double2(0.0, 0.0);
     if constexpr (GS) {
         wcqp_tick::zmp_state_issue(td, inst, zreg);
         kg = wcqp_tick::zmp_gains_at(td, td.zg, wcqp_tick::zmp_smoother_advance(td, inst, j == 0 && live, rd, zreg));
     }
     if constexpr (REACT) wcqp_tick::tick_react_finish<EXT, GS>(td, j, inst, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd), nullptr, kg);
-    else wcqp_tick::tick_mpc_finish<false, EXT, GS, PL>(td, j, inst, live, t, mreg, s_hull[grp], nullptr, code, nullptr, kg);
+    else wcqp_tick::tick_mpc_finish<false, EXT, GS, PL, PL && EXT>(td, j, inst, live, t, mreg, s_hull[grp], nullptr, code, nullptr, kg);
 }
 
 }  // namespace

@@ -22,6 +22,7 @@ struct SensorDev {
     long long* feedback_fail;     // [B] rejected sensor ticks
     int batch, t, step_ticks, kin_rounds;
     double omega;                 // sqrt(gravity / com_height)
+    const double* rec;            // streamed trajectories: [B][kPlanRec] the stage of tick t (stance side and anchor pose); else NULL
 };
 
 }  // namespace wcqp_tick

@@ -25,6 +25,9 @@ __device__ __forceinline__ void st2(double* p, double a, double b) { *reinterpre
 __device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
 
 // One robot per 16 lanes, four per wave, one wave per workgroup.
+// PL (streamed trajectories, wcqp_tick_set_desired_*): the stance side is the fixed-frame bit of the stage the caller handed over for tick t
+// and the anchor that stage's desired sole pose (the robot's record, tick_device.h: kPlanRec) - what tick t's own kinematics take
+template <bool PL>
 __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
     using namespace wcqp_kin;
     __shared__ __attribute__((aligned(16))) double kmodel[kKinTabSize];
@@ -50,9 +53,16 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
     const double* wri = a.wr + i * 6;
     const double fzL = wli[2], txL = wli[3], tyL = wli[4], fzR = wri[2], txR = wri[3], tyR = wri[4];
     // the stance side of tick t, as the tick kernel carries it: (t + phase0) % (2 step_ticks) >= step_ticks -> the right sole anchors
-    const int cyc = (a.t + a.phase0[i]) % (2 * a.step_ticks);
-    const int side = cyc >= a.step_ticks ? 1 : 0;
-    if (j < 12) S[S_SD + j] = a.state[i * kStateLen + 24 + side * 12 + j];     // its desired pose: p (3), R (9)
+    int side;
+    if constexpr (PL) {
+        const double* rc = a.rec + i * kPlanRec;
+        side = plan_side((int)rc[kPlanFlags]);
+        if (j < 12) S[S_SD + j] = rc[kPlanLeft + side * 12 + j];
+    } else {
+        const int cyc = (a.t + a.phase0[i]) % (2 * a.step_ticks);
+        side = cyc >= a.step_ticks ? 1 : 0;
+        if (j < 12) S[S_SD + j] = a.state[i * kStateLen + 24 + side * 12 + j];     // its desired pose: p (3), R (9)
+    }
     int kup[2][3], ksub[2];
     __syncthreads();                                 // the model table is in LDS
 #pragma unroll
@@ -284,7 +294,8 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
 
 namespace wcqp {
 int sensor_feedback_enqueue(const wcqp_tick::SensorDev& a, hipStream_t stream) {
-    hipLaunchKernelGGL(tick_sensor_kernel, dim3((unsigned)((a.batch + 3) / 4)), dim3(64), 0, stream, a);
+    if (a.rec) hipLaunchKernelGGL(tick_sensor_kernel<true>, dim3((unsigned)((a.batch + 3) / 4)), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(tick_sensor_kernel<false>, dim3((unsigned)((a.batch + 3) / 4)), dim3(64), 0, stream, a);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }

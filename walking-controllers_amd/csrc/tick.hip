@@ -98,6 +98,71 @@ __global__ void plan_hull_sets_kernel(int n, PlanRect rect, const double* __rest
     nc[g] = wcqp_hull::hull_rows(px, py, np, A + (size_t)g * 16, b + (size_t)g * 8);
 }
 
+// streamed trajectories (wcqp_tick_set_desired_*): the stage of the next tick - what WalkingModule::updateModule pops from the front of the
+// planner's deques (WM/src/WalkingModule.cpp:509-511, 689-707, 1085-1165) - packed into the robot's record (tick_device.h: kPlanRec, ONE
+// per robot) and validated by the rules of the planned upload.  16 lanes per robot: lane j carries entries j, 16 + j and 32 + j.
+// A robot whose stage is invalid keeps its previous record and is stopped and counted like one whose sensor reading was rejected
+// (sensors.hip).  pair: per robot the contact pair of the last stage a tick consumed and of the stage in hand (-1 after an upload); `first`:
+// this is the first stage handed over since the last tick, so the pair in hand has been consumed.  When the new pair differs from the
+// consumed one, lane 0 builds the robot's support-polygon rows from this stage's feet with the builder of hull_device.h - here, not in the
+// tick kernel - into set i, which entry 39 names: the chain of tick t copies them into the live rows on seeing the change
+// (tick_mpc_finish_from, ...PredictiveController.cpp:364-435); with no change the rows stay, whatever the feet do.
+struct DesiredDev {
+    const double *left_pose, *right_pose, *left_twist, *right_twist, *com_height, *com_height_vel;
+    const unsigned char* contact;
+    const double* h0;               // [B] TickDev::com_h0: the height of a stage without one
+    double* rec; double* set_A; double* set_b; int* set_nc; int* pair;
+    long long *ik_fail, *feedback_fail;
+    int batch, first, build;        // build: the handle's controller reads hull rows (the MPC)
+};
+__global__ __launch_bounds__(64) void tick_desired_kernel(DesiredDev a, PlanRect rect) {
+    const int lane = threadIdx.x, grp = lane >> 4, j = lane & 15;
+    const long inst_raw = (long)blockIdx.x * 4 + grp;
+    const bool live = inst_raw < a.batch;
+    const size_t i = (size_t)(live ? inst_raw : (long)a.batch - 1);
+    const unsigned f = a.contact[i];
+    // entries j (flags, height, its velocity, the left pose and the first of the right), 16 + j, 32 + j (< 40: the twists' tail, the set)
+    double v0, v1, v2 = 0.0;
+    if (j == kPlanFlags) v0 = (double)f;
+    else if (j == kPlanHeight) v0 = a.com_height ? a.com_height[i] : a.h0[i];
+    else if (j == kPlanHeightVel) v0 = a.com_height_vel ? a.com_height_vel[i] : 0.0;
+    else if (j < kPlanRight) v0 = a.left_pose[i * 12 + (j - kPlanLeft)];
+    else v0 = a.right_pose[i * 12 + (j - kPlanRight)];
+    const int k1 = 16 + j;
+    v1 = k1 < kPlanTwL ? a.right_pose[i * 12 + (k1 - kPlanRight)] : a.left_twist[i * 6 + (k1 - kPlanTwL)];
+    const int k2 = 32 + j;
+    if (k2 < kPlanTwL + 6) v2 = a.left_twist[i * 6 + (k2 - kPlanTwL)];
+    else if (k2 < kPlanHull) v2 = a.right_twist[i * 6 + (k2 - kPlanTwL - 6)];
+    else if (k2 == kPlanHull) v2 = (double)i;
+    const bool flags_bad = (f & 3u) == 0u || ((f & 4u) ? !(f & 1u) : !(f & 2u));       // no foot in contact / the fixed-frame foot is not
+    const bool lane_bad = flags_bad || !(isfinite(v0) && isfinite(v1) && isfinite(v2));
+    const bool bad = ((__ballot(lane_bad) >> (grp * 16)) & 0xffffull) != 0ull;
+    if (!live) return;
+    int* pr = a.pair + i * 2;
+    const int consumed = a.first ? pr[1] : pr[0];
+    if (bad) {
+        if (j == 0) {
+            pr[0] = consumed;
+            a.feedback_fail[i] += 1;
+            if (a.ik_fail[i] == 0) a.ik_fail[i] = 1;
+        }
+        return;
+    }
+    double* r = a.rec + i * kPlanRec;
+    r[j] = v0; r[k1] = v1;
+    if (k2 <= kPlanHull) r[k2] = v2;
+    if (j != 0) return;
+    const int code = (int)(f & 3u) - 1;
+    pr[0] = consumed; pr[1] = code;
+    if (a.build && code != consumed) {
+        double px[8], py[8];
+        int np = 0;
+        if (code == 0 || code == 2) wcqp_hull::foot_points(rect.v, a.left_pose + i * 12, px, py, np);
+        if (code == 1 || code == 2) wcqp_hull::foot_points(rect.v, a.right_pose + i * 12, px, py, np);
+        a.set_nc[i] = wcqp_hull::hull_rows(px, py, np, a.set_A + i * 16, a.set_b + i * 8);
+    }
+}
+
 // external feedback: the caller's measured state into the places the next tick reads its plant state from - the skewed
 // chain's per-axis records (mst: com [2], dcm [6], measured ZMP [7]) - and the measured joints into q_meas (NULL: the desired ones)
 __global__ void tick_feedback_kernel(TickDev d, const double* __restrict__ dcm, const double* __restrict__ com, const double* __restrict__ zmp,
@@ -182,6 +247,12 @@ struct wcqp_tick_s {
     bool planned = false;
     PlanDev pl{};
     double* set_A = nullptr; double* set_b = nullptr; int* set_nc = nullptr;     // the row sets of the last upload (PlanDev::set_*)
+    // streamed_trajectories (an EXTERNAL handle): pl.rec holds ONE record per robot, the stage wcqp_tick_set_desired_* handed over for the next
+    // tick, pl.set_* one row set per robot; `planned` stays false (the splice of the DCM reference keeps working)
+    bool streamed = false, desired_set = false;
+    double* st_rec = nullptr; double* st_set_A = nullptr; double* st_set_b = nullptr; int* st_set_nc = nullptr;
+    int* st_pair = nullptr;       // [B][2] contact pair of the last consumed stage / of the stage in hand (tick_desired_kernel)
+    double* des_stage = nullptr;  // wcqp_tick_set_desired_host: [B][12 + 12 + 6 + 6 + 1 + 1] doubles, then [B] bytes
     TickDevPL dpl(const TickDev& base) const { TickDevPL g; static_cast<TickDevGS&>(g) = dgs(base); g.pl = pl; return g; }
 };
 
@@ -272,6 +343,18 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
             (params->dcm_controller == WCQP_TICK_DCM_MPC && params->mpc.horizon >= kGainsLdsStages))
             return WCQP_E_UNSUPPORTED;
     }
+    // streamed trajectories: the EXTERNAL plant's per-tick hand-over of the desired stage - the fused-kinematics skewed tick of the default
+    // IK kernel without logger rows, and not a planned handle (refused here from the parameters, the tree and the route below)
+    const bool streamed = params->streamed_trajectories != 0;
+    if (params->streamed_trajectories != 0 && params->streamed_trajectories != 1) return WCQP_E_INVALID;
+    if (streamed) {
+        for (int k = 0; k < 9; ++k) if (!std::isfinite(params->neck_additional_rotation[k])) return WCQP_E_INVALID;
+        const int alg = params->ik.algorithm;
+        if (!params->use_kinematics || params->kin_handoff != WCQP_KIN_HANDOFF_FUSED || params->logger_ticks > 0 || planned ||
+            params->plant != WCQP_TICK_PLANT_EXTERNAL || (alg != WCQP_IK_ALG_DEFAULT && alg != WCQP_IK_ALG_BASE_ELIM) ||
+            (params->dcm_controller == WCQP_TICK_DCM_MPC && params->mpc.horizon >= kGainsLdsStages))
+            return WCQP_E_UNSUPPORTED;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         std::fprintf(stderr, "[wcqp] no HIP device: the tick pipeline has no CPU fallback\n");
@@ -289,8 +372,8 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
         if (params->kin.dof != kDof) rc = WCQP_E_UNSUPPORTED;
         if (rc == WCQP_OK) rc = wcqp_kin_create(&params->kin, &h->kin);
     }
-    if (rc == WCQP_OK && planned) {
-        // planned trajectories where FUSED would not be taken - another IK route (CoM as a cost, say) or a tree the fused kernel cannot
+    if (rc == WCQP_OK && (planned || streamed)) {
+        // planned / streamed trajectories where FUSED would not be taken - another IK route (CoM as a cost, say) or a tree the fused kernel cannot
         // walk: refused from the handles' host state, before any device allocation (the prepare calls below are the first)
         unsigned m3[3];
         int cs_ = 0, cd_ = 0, rounds = 0;
@@ -352,7 +435,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     const bool compact = masks_ok && !fusedk && params->kin_handoff != WCQP_KIN_HANDOFF_DENSE;
     // external feedback: the default (base-eliminated) kernel with constant Jacobians or fused kinematics, without logger rows
     if (h->external && (!d.skew || params->logger_ticks > 0 || (h->kin && !fusedk))) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }
-    if (planned && (!d.skew || !fusedk)) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }      // (checked above, before any allocation)
+    if ((planned || streamed) && (!d.skew || !fusedk)) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }      // (checked above, before any allocation)
     if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); }
     if (h->external && h->kin) {
         A_(h->sens_stage, B * (2 * kDof + 12)); A_(h->feedback_fail, B);
@@ -372,6 +455,14 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
         double* rec = nullptr;
         A_(rec, B * (size_t)d.traj_len * kPlanRec);
         h->planned = true; h->pl.rec = rec;
+        for (int k = 0; k < 9; ++k) h->pl.neck_add[k] = params->neck_additional_rotation[k];
+    }
+    if (streamed) {
+        // one record and one row set per robot, the pairs, the host form's staging rows
+        A_(h->st_rec, B * kPlanRec); A_(h->st_set_A, B * 16); A_(h->st_set_b, B * 8); A_(h->st_set_nc, B); A_(h->st_pair, B * 2);
+        A_(h->des_stage, B * 38 + (B + 7) / 8);
+        h->streamed = true;
+        h->pl.rec = h->st_rec; h->pl.set_A = h->st_set_A; h->pl.set_b = h->st_set_b; h->pl.set_nc = h->st_set_nc;
         for (int k = 0; k < 9; ++k) h->pl.neck_add[k] = params->neck_additional_rotation[k];
     }
     if (d.skew) {
@@ -418,7 +509,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
         h->variant.jsrc = d.kin_fused ? 2 : d.compact ? 1 : 0;
         h->variant.log = d.logger_ticks > 0;
         h->variant.ext = d.q_meas && !h->variant.log;
-        h->variant.react = d.reactive != 0; h->variant.gs = d.gain_sched != 0; h->variant.pl = h->planned;
+        h->variant.react = d.reactive != 0; h->variant.gs = d.gain_sched != 0; h->variant.pl = h->planned || h->streamed;
     }
     *out = h;
     return WCQP_OK;
@@ -535,7 +626,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     if (!h || !in) return WCQP_E_INVALID;
     // (planned trajectories: no synthetic gait - phase0 and swing_twist may be NULL)
     if (!in->ref_traj || !in->state0 || !in->q0 || !in->dcm0 || !in->com0 || !in->u_init) return WCQP_E_INVALID;
-    if (!h->planned && (!in->phase0 || !in->swing_twist)) return WCQP_E_INVALID;
+    if (!h->planned && !h->streamed && (!in->phase0 || !in->swing_twist)) return WCQP_E_INVALID;
     if (h->planned) { const int rcv = validate_plan(h, in); if (rcv != WCQP_OK) return rcv; }
     if (!h->kin && (!in->J_left || !in->J_right || !in->J_neck || !in->J_com)) return WCQP_E_INVALID;
     // (the reactive controller reads no hull rows)
@@ -568,6 +659,13 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
         if (rcp != WCQP_OK) return rcp;
         WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
         WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
+    } else if (h->streamed) {
+        // no stage yet (every tick's comes through wcqp_tick_set_desired_*): zero records, no rows, no pair - a robot whose very first
+        // stage is rejected runs stopped on a record that holds nothing
+        WCQP_HIP_TRY(hipMemset(h->st_rec, 0, B * kPlanRec * 8)); WCQP_HIP_TRY(hipMemset(h->st_set_nc, 0, B * 4));
+        WCQP_HIP_TRY(hipMemset(h->st_pair, 0xff, B * 8));
+        WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
+        WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
     } else {
         UP_(d.phase0, in->phase0, B * 4); UP_(d.swing_twist, in->swing_twist, B * 48);
     }
@@ -596,7 +694,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
         UP_(h->J_neck, in->J_neck, B * 3 * 29 * 8); UP_(h->J_com, in->J_com, B * 3 * 29 * 8);
     }
     UP_(d.state, in->state0, B * kStateLen * 8); UP_(d.q_des, in->q0, B * kDof * 8);
-    if (h->kin && !h->planned) {     // (planned: the live rows are built from the records at the first tick - sel_built = -1)
+    if (h->kin && !h->planned && !h->streamed) {     // (planned / streamed: the live rows are built from the records at the first tick - sel_built = -1)
         // setConvexHullConstraint (...PredictiveController.cpp:364-435) for the three contact pairs, from the DESIRED foot
         // poses just uploaded (the planned footsteps, WalkingModule.cpp:609-613): the MPC of a tick selects its rows by the pair
         const int rch = wcqp::hull_tables_from_state((int)B, h->p.foot_rect, d.state, kStateLen, const_cast<double*>(d.hull_tab_A.get()),
@@ -615,6 +713,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
         std::vector<int> sel(B);
         for (size_t i = 0; i < B; ++i) {
             if (h->planned) { sel[i] = (int)(in->contact[i * d.traj_len] & 3u) - 1; continue; }
+            if (h->streamed) { sel[i] = 2; continue; }      // (the skewed kernels take the pair from the stage's record)
             const int cyc = in->phase0[i] % (2 * d.step_ticks), sidx = cyc % d.step_ticks;
             sel[i] = sidx < d.ds_ticks ? 2 : cyc / d.step_ticks;
         }
@@ -638,7 +737,65 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     h->ticks_enqueued = 0;
     h->phase = 0;
     h->feedback_set = false;
+    h->desired_set = false;
     h->run_pending = false;
+    return WCQP_OK;
+}
+
+int wcqp_tick_set_desired_device(wcqp_tick_t h, const wcqp_tick_desired* des, void* stream) {
+    if (!h || !des) return WCQP_E_INVALID;
+    if (!h->streamed) return WCQP_E_UNSUPPORTED;
+    if (!h->uploaded || !des->left_pose || !des->right_pose || !des->left_twist || !des->right_twist || !des->contact) return WCQP_E_INVALID;
+    const TickDev& d = h->d;
+    DesiredDev a{};
+    a.left_pose = des->left_pose; a.right_pose = des->right_pose; a.left_twist = des->left_twist; a.right_twist = des->right_twist;
+    a.com_height = des->com_height; a.com_height_vel = des->com_height_vel; a.contact = des->contact; a.h0 = d.com_h0;
+    a.rec = h->st_rec; a.set_A = h->st_set_A; a.set_b = h->st_set_b; a.set_nc = h->st_set_nc; a.pair = h->st_pair;
+    a.ik_fail = d.ik_fail; a.feedback_fail = h->feedback_fail;
+    a.batch = d.batch; a.first = h->desired_set ? 0 : 1; a.build = d.reactive ? 0 : 1;
+    PlanRect r;
+    for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
+    hipLaunchKernelGGL(tick_desired_kernel, dim3((unsigned)((d.batch + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a, r);
+    WCQP_HIP_TRY(hipGetLastError());
+    h->desired_set = true;
+    return WCQP_OK;
+}
+
+int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* des) {
+    if (!h || !des) return WCQP_E_INVALID;
+    if (!h->streamed) return WCQP_E_UNSUPPORTED;
+    if (!h->uploaded || !des->left_pose || !des->right_pose || !des->left_twist || !des->right_twist || !des->contact) return WCQP_E_INVALID;
+    const size_t B = (size_t)h->d.batch;
+    // the rules of the planned upload (validate_plan), checked here: an invalid stage leaves the handle as it was
+    for (size_t i = 0; i < B; ++i) {
+        const unsigned f = des->contact[i];
+        if ((f & 3u) == 0u) return WCQP_E_INVALID;
+        if ((f & 4u) ? !(f & 1u) : !(f & 2u)) return WCQP_E_INVALID;
+        bool ok = true;
+        for (int k = 0; k < 12; ++k) ok = ok && std::isfinite(des->left_pose[i * 12 + k]) && std::isfinite(des->right_pose[i * 12 + k]);
+        for (int k = 0; k < 6; ++k) ok = ok && std::isfinite(des->left_twist[i * 6 + k]) && std::isfinite(des->right_twist[i * 6 + k]);
+        if (des->com_height) ok = ok && std::isfinite(des->com_height[i]);
+        if (des->com_height_vel) ok = ok && std::isfinite(des->com_height_vel[i]);
+        if (!ok) return WCQP_E_INVALID;
+    }
+    // the last run may have been enqueued on a non-blocking stream, which the NULL stream below does not wait for: wait for its end
+    if (h->run_pending) { WCQP_HIP_TRY(hipEventSynchronize(h->run_done)); h->run_pending = false; }
+    double* st = h->des_stage;
+    wcqp_tick_desired dv{};
+    dv.left_pose = st; dv.right_pose = st + 12 * B; dv.left_twist = st + 24 * B; dv.right_twist = st + 30 * B;
+    dv.com_height = des->com_height ? st + 36 * B : nullptr; dv.com_height_vel = des->com_height_vel ? st + 37 * B : nullptr;
+    dv.contact = reinterpret_cast<const uint8_t*>(st + 38 * B);
+    WCQP_HIP_TRY(hipMemcpy(st, des->left_pose, B * 96, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 12 * B, des->right_pose, B * 96, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 24 * B, des->left_twist, B * 48, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 30 * B, des->right_twist, B * 48, hipMemcpyHostToDevice));
+    if (des->com_height) WCQP_HIP_TRY(hipMemcpy(st + 36 * B, des->com_height, B * 8, hipMemcpyHostToDevice));
+    if (des->com_height_vel) WCQP_HIP_TRY(hipMemcpy(st + 37 * B, des->com_height_vel, B * 8, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 38 * B, des->contact, B, hipMemcpyHostToDevice));
+    const int rc = wcqp_tick_set_desired_device(h, &dv, nullptr);
+    if (rc != WCQP_OK) return rc;
+    // in place when this call returns: the tick may be enqueued on any stream, and the staging rows are free for the next call
+    WCQP_HIP_TRY(hipStreamSynchronize(nullptr));
     return WCQP_OK;
 }
 
@@ -677,12 +834,14 @@ int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, co
     if (!h || !q_meas || !dq_meas || !wrench_left || !wrench_right) return WCQP_E_INVALID;
     if (!h->external || !h->kin || !h->feedback_fail) return WCQP_E_UNSUPPORTED;
     if (!h->uploaded) return WCQP_E_INVALID;
+    if (h->streamed && !h->desired_set) return WCQP_E_INVALID;       // (the anchor is tick t's stage: wcqp_tick_set_desired_* goes first)
     const TickDev& d = h->d;
     SensorDev a{};
     a.q = q_meas; a.dq = dq_meas; a.wl = wrench_left; a.wr = wrench_right;
     a.q_des = d.q_des; a.state = d.state; a.phase0 = d.phase0; a.kin_tab = d.kin_tab;
     a.mst = d.mst; a.hand = d.hand; a.q_meas = h->q_meas; a.ik_fail = d.ik_fail; a.feedback_fail = h->feedback_fail;
     a.batch = d.batch; a.t = h->ticks_enqueued; a.step_ticks = d.step_ticks; a.kin_rounds = d.kin_rounds; a.omega = d.omega;
+    a.rec = h->streamed ? h->st_rec : nullptr;
     const int rc = wcqp::sensor_feedback_enqueue(a, (hipStream_t)stream);
     if (rc != WCQP_OK) return rc;
     h->feedback_set = true;
@@ -694,6 +853,7 @@ int wcqp_tick_set_sensor_feedback_host(wcqp_tick_t h, const double* q_meas, cons
     if (!h || !q_meas || !dq_meas || !wrench_left || !wrench_right) return WCQP_E_INVALID;
     if (!h->external || !h->kin || !h->feedback_fail) return WCQP_E_UNSUPPORTED;
     if (!h->uploaded) return WCQP_E_INVALID;
+    if (h->streamed && !h->desired_set) return WCQP_E_INVALID;
     const size_t B = (size_t)h->d.batch;
     // the last run may have been enqueued on a non-blocking stream, which the NULL stream below does not wait for: wait for its end
     if (h->run_pending) { WCQP_HIP_TRY(hipEventSynchronize(h->run_done)); h->run_pending = false; }
@@ -716,6 +876,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     hipStream_t s = (hipStream_t)stream;
     if (n_ticks == 0) return WCQP_OK;
     if (h->external && (n_ticks != 1 || !h->feedback_set)) return WCQP_E_INVALID;      // one tick per call, each behind its own feedback
+    if (h->streamed && !h->desired_set) return WCQP_E_INVALID;                          // ... and, streamed, behind its own desired stage
     int left = n_ticks;
     // Everything that can be refused on the host is refused BEFORE anything is enqueued (the prime launch below already advances
     // the MPC chain); an enqueue that fails after that leaves device state nobody can name - the handle then wants a new upload.
@@ -776,6 +937,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     if (h->run_done) { WCQP_HIP_TRY(hipEventRecord(h->run_done, s)); h->run_pending = true; }    // (sensor feedback: the host form waits for it)
     guard.armed = false;
     h->feedback_set = false;
+    h->desired_set = false;
     return WCQP_OK;
 }
 
@@ -838,6 +1000,7 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
     out->dcm_controller = d.reactive ? WCQP_TICK_DCM_REACTIVE : WCQP_TICK_DCM_MPC;
     out->zmp_gain_scheduling = d.gain_sched ? 1 : 0;
     out->planned_trajectories = h->planned ? 1 : 0;
+    out->streamed_trajectories = h->streamed ? 1 : 0;
     // a kinematics launch unless fused; then the skewed kernel (1), MPC / reactive + the 16-lane kernel (2) or controller, glue, IK, post (4)
     out->launches_per_tick = (h->kin && !d.kin_fused ? 1 : 0) + (h->form == TickForm::SKEWED ? 1 : h->form == TickForm::MPC_IK16 ? 2 : 4);
     return WCQP_OK;

@@ -124,6 +124,9 @@ struct PlanDev {
     double neck_add[9];              // wcqp_tick_params.neck_additional_rotation
     wcqp::GPtr<const double> set_A; wcqp::GPtr<const double> set_b; wcqp::GPtr<const int> set_nc;   // [sets][8][2], [sets][8], [sets]
 };
+// Streamed trajectories (wcqp_tick_params.streamed_trajectories, an EXTERNAL handle): the same record, ONE per robot - [B][kPlanRec], the
+// stage of the next tick as wcqp_tick_set_desired_* packed it (tick.hip: tick_desired_kernel) - and one row set per robot, [B] sets, entry
+// 39 of robot i's record naming set i; the kernels of such a handle address the record with plan_rec<true> (the ST flag below).
 // A planned handle's TickDev (the scheduling record included, used or not): the planned kernels read it from device memory or take it
 // by value (the prime kernel); every other kernel keeps its TickDev.
 struct TickDevPL : TickDevGS { PlanDev pl; };
@@ -191,14 +194,19 @@ __device__ __forceinline__ double disturbance_from(unsigned long long base, int 
 }
 
 // ---- planned-trajectory mode (TickDevPL): the record of robot inst at stage t (64-bit offsets: no wcqp::at32 - the array passes 4 GB)
+// ST (streamed trajectories, an EXTERNAL handle: wcqp_tick_set_desired_*): the array holds ONE record per robot, [B][kPlanRec] - the
+// stage of the tick the caller handed over last - whatever t is; a template flag, so that the planned kernels' addressing is what it was
+template <bool ST = false>
 __device__ __forceinline__ const double* plan_rec(const TickDevPL& d, long inst, int t) {
+    if constexpr (ST) return d.pl.rec.get() + (size_t)inst * (size_t)kPlanRec;
     return d.pl.rec.get() + ((size_t)inst * (size_t)d.traj_len + (size_t)t) * (size_t)kPlanRec;
 }
 // The contact flags of stage t (lanes 0 and 5..15) - and, on lanes 1..4, the first word of the record's lines 1..4: the tick of stage
 // t - 1 issues this with the chain's loads, and all five lines of the record are in L2 when the tick of stage t reads it.  Every lane's
 // value is consumed (plan_flags_of: the row's broadcast reads all of them), so the extra words are not dropped as dead loads.
+template <bool ST = false>
 __device__ __forceinline__ double plan_flags_issue(const TickDevPL& d, int j, long inst, int t) {
-    return plan_rec(d, inst, t)[(j >= 1 && j <= 4) ? 8 * j : kPlanFlags];
+    return plan_rec<ST>(d, inst, t)[(j >= 1 && j <= 4) ? 8 * j : kPlanFlags];
 }
 __device__ __forceinline__ int plan_flags_of(double v) {
     return (int)__shfl(v, (int)(threadIdx.x & ~15u));
@@ -448,7 +456,8 @@ __device__ __forceinline__ void tick_mpc_partial(const TickDev& d, int j, long i
 // caller's (record entry 7), not the previous command; the kernels of the internal plant keep entry 7 out of their registers
 // PL (planned trajectories): code_known is the pair of the planner's flags, and a change of pair copies the row set the stage's record
 // names (PlanDev::set_*, built at upload from the stage's desired feet) instead of one of the three-set table; d is then a TickDevPL
-template <bool EXT = false, bool GS = false, bool PL = false>
+// ST (streamed trajectories): the record is the robot's one (plan_rec<true>) and names the robot's own set, built by tick_desired_kernel
+template <bool EXT = false, bool GS = false, bool PL = false, bool ST = false>
 __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, long inst, bool live, int t, TickMpcRegs& R, double2 r0, double ux, double uy,
                                                      double (*s_hull)[4], int code_known = -1, const unsigned long long* noise_base = nullptr,
                                                      double2 kg = double2{}) {
@@ -460,7 +469,7 @@ __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, lo
         if constexpr (PL) {
             if (stale && live) {
                 const TickDevPL& dp = static_cast<const TickDevPL&>(d);
-                const long hset = (long)plan_rec(dp, inst, t)[kPlanHull];
+                const long hset = (long)plan_rec<ST>(dp, inst, t)[kPlanHull];
                 double* lA = d.live_A + inst * (2 * WCQP_HULL_ROWS);
                 double* lb = d.live_b + inst * WCQP_HULL_ROWS;
                 if (j < WCQP_HULL_ROWS) {
@@ -511,13 +520,13 @@ __device__ __forceinline__ void tick_mpc_finish_from(const TickDev& d, int j, lo
         tick_chain_step<EXT, GS>(d, ax, inst, t, R, rr, u, mpc_ok, noise_base, kg);
     }
 }
-template <bool GAINS_LDS = false, bool EXT = false, bool GS = false, bool PL = false>
+template <bool GAINS_LDS = false, bool EXT = false, bool GS = false, bool PL = false, bool ST = false>
 __device__ __forceinline__ void tick_mpc_finish(const TickDev& d, int j, long inst, bool live, int t, TickMpcRegs& R, double (*s_hull)[4],
                                                 const double* gr_lds = nullptr, int code_known = -1, const unsigned long long* noise_base = nullptr,
                                                 double2 kg = double2{}) {
     double ux, uy;
     tick_mpc_partial<GAINS_LDS>(d, j, inst, t, R, gr_lds, ux, uy);
-    tick_mpc_finish_from<EXT, GS, PL>(d, j, inst, live, t, R, R.L.r[0], ux, uy, s_hull, code_known, noise_base, kg);
+    tick_mpc_finish_from<EXT, GS, PL, ST>(d, j, inst, live, t, R, R.L.r[0], ux, uy, s_hull, code_known, noise_base, kg);
 }
 // the same two with the gait cycle index cyc = (t + phase0) % (2 step_ticks) at hand (the tick kernel carries it from tick to tick:
 // integer divisions by run-time values are ~35 instructions each, and a tick had four of them, on every lane)
