@@ -35,6 +35,29 @@
  *     the caller keeps their input / output arrays apart.  (wcqp_ik_set_posture and the
  *     `*_host` entry points synchronise the device first; a wcqp_tick_t owns its state and
  *     takes one stream at a time.)
+ *
+ * Non-finite inputs
+ *   A NaN or an Inf in one instance's inputs never aborts the batch, never comes back WCQP_STATUS_SOLVED and never reaches a documented
+ *   output; what the instance reports does not depend on the instances next to it, and they do not notice it (their results are bit for
+ *   bit those of a batch in which the value is finite).  Each entry point below says what it returns for such an instance.  (Finite inputs
+ *   so large that the arithmetic overflows are treated the same way.)
+ *
+ * Size limits (32-bit addressing)
+ *   The solve kernels reach row i of a per-instance array as base + a 32-bit BYTE offset, so every such array must end within 2^32 bytes
+ *   of its start: count x row_bytes <= 2^32, checked by every entry point from its arguments alone - before it looks for a device,
+ *   allocates or launches, and without reading the arrays - and answered with WCQP_E_UNSUPPORTED.  The rows, per entry point (the widest
+ *   one decides):
+ *     wcqp_mpc_solve_device / _host    ref: ref_len x 16 B (batch <= 2^32 / (16 ref_len) = 2^28 / ref_len); hull_A: 128 B; the rest narrower.
+ *                                      (The stand-alone kernel itself forms 64-bit addresses; the limit is kept so that a batch one route
+ *                                      takes is a batch every route takes.)
+ *     wcqp_ik_solve_device / _host     J_left, J_right: 6 x 29 x 8 = 1392 B (batch <= 3085465); J_neck, J_com, state: 696 B; q, dq: 184 B
+ *     wcqp_qp_enqueue_steps            both of the above, per record (the code of the first call that refuses)
+ *     wcqp_qp_plan_create              both of the above for every record that has the part
+ *     wcqp_qp_step_from_slabs          both of the above for the layout's batch and ref_len
+ *     wcqp_tick_create                 ref_traj, dcm_vel_traj: (max_ticks + horizon + 1) x 16 B; the two MPC -> IK hand-off records:
+ *                                      2 x batch rows of 112 B; the IK's arrays as above (1392 B).  From the parameters alone, before the
+ *                                      device is looked for.  The planned-trajectory records use 64-bit offsets and set no limit.
+ *     wcqp_kin_jacobians_*, wcqp_hull_from_feet_*   64-bit addresses throughout: no limit beyond int32 batch.
  */
 #ifndef WCQP_H
 #define WCQP_H
@@ -61,7 +84,8 @@ extern "C" {
 #define WCQP_STATUS_INFEASIBLE    2   /* constraints admit no point                       */
 #define WCQP_STATUS_OUTSIDE_HULL  3   /* MPC: margin(u0) < -convex_hull_tolerance
                                          (WM/src/WalkingDCMModelPredictiveController.cpp:513-517) */
-#define WCQP_STATUS_NUMERIC       4   /* non-positive pivot (KKT not regular)             */
+#define WCQP_STATUS_NUMERIC       4   /* non-positive pivot (KKT not regular), or a NaN / Inf
+                                         among the instance's inputs (see "Non-finite inputs") */
 #define WCQP_STATUS_STRUCTURE     5   /* IK: handle created with WCQP_IK_JAC_MIXED, but this instance's Jacobians do
                                          not have MIXED-representation base blocks          */
 
@@ -127,6 +151,11 @@ int wcqp_mpc_get_matrices(wcqp_mpc_t h, double* P, double* A_eq, double* grad_su
  *   status[B]     WCQP_STATUS_*                -> the bool of solve() (cpp:491-521)
  *   active[B]     bit e set <=> hull row e is in the optimal active set       (may be NULL)
  *   margin[B]     signed distance of u0 to the hull boundary, + inside         (may be NULL)
+ * Non-finite inputs: a NaN or +-Inf in x0, in u_prev, in a stage of ref the horizon reads (stages 0 .. min(N, ref_len - 1)) or in a hull
+ * row below hull_nc gives status = WCQP_STATUS_NUMERIC, u0 = (0, 0), active = 0, margin = -inf.  Hull rows at or above hull_nc and ref
+ * stages beyond the horizon are never looked at: a non-finite value there changes nothing.  The same holds for the MPC part of
+ * wcqp_qp_enqueue_steps and of a plan.  (The tick keeps such values out of its state: wcqp_tick_upload and wcqp_tick_splice_reference
+ * refuse them, wcqp_tick_set_feedback_* rejects the robot.)
  */
 int wcqp_mpc_solve_device(wcqp_mpc_t h, int32_t batch,
                           const double* x0, const double* ref, int32_t ref_len,
@@ -253,6 +282,14 @@ int wcqp_ik_set_posture(wcqp_ik_t h, const double* joint_reg_rad);
  *   foot_err[B][12]                     -> getLeftFootError | getRightFootError
  *                                          (osqp.cpp:430-454, qp.cpp:364-401)     (may be NULL)
  *   iters[B]                            active-set changes performed              (may be NULL)
+ * Non-finite inputs: a NaN or +-Inf in a joint column (6 .. n-1) of any of the four Jacobians, in q or in an entry of `state` the form
+ * reads gives status = WCQP_STATUS_NUMERIC, dq = 0, active_lower = active_upper = 0 and iters <= max_iter - whichever kernel the handle
+ * runs, and through wcqp_qp_enqueue_steps and the plans as well.  Both forms read every entry of `state`, with one exception: under
+ * WCQP_IK_FORM_OSQP a foot whose desired twist has twist[0] == twist[1] == 0 gets no pose correction (the zero-twist rule, osqp.cpp:286-306),
+ * so that foot's actual and desired pose entries (left 0..11, 24..35; right 12..23, 36..47) are not read and a non-finite value there
+ * changes nothing.  One in a base block (columns 0 .. 5) keeps the meaning given under
+ * jacobian_structure: WCQP_STATUS_STRUCTURE with WCQP_IK_JAC_MIXED; with WCQP_IK_JAC_AUTO the general kernel re-solves the instance, which
+ * then ends WCQP_STATUS_NUMERIC with dq = 0.  foot_err of such an instance is unspecified (it may hold NaN).
  */
 int wcqp_ik_solve_device(wcqp_ik_t h, int32_t batch,
                          const double* J_left, const double* J_right,
@@ -607,14 +644,18 @@ typedef struct wcqp_tick_outputs {  /* HOST pointers, any may be NULL */
     double* measured;           /* [B][6] EXTERNAL plant only: dcm xy, com xy, ZMP xy the last executed tick used as its measured state,
                                    whichever feedback form set it (after an upload, before any tick: dcm0, com0, u_init).  Any other
                                    handle: WCQP_E_UNSUPPORTED when non-NULL                                                       */
-    int64_t* feedback_fail;     /* [B] EXTERNAL plant only: sensor ticks rejected by wcqp_tick_set_sensor_feedback_* since the last
-                                   upload (0 without kinematics).  Any other handle: WCQP_E_UNSUPPORTED when non-NULL               */
+    int64_t* feedback_fail;     /* [B] EXTERNAL plant only: ticks whose feedback was rejected - by wcqp_tick_set_sensor_feedback_*, by
+                                   wcqp_tick_set_feedback_* (a non-finite value) or by wcqp_tick_set_desired_* - since the last
+                                   upload.  Any other handle: WCQP_E_UNSUPPORTED when non-NULL                                      */
 } wcqp_tick_outputs;
 
 typedef struct wcqp_tick_s* wcqp_tick_t;
 int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out);
 int wcqp_tick_destroy(wcqp_tick_t h);
-int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in);                 /* also rewinds to tick 0 */
+/* also rewinds to tick 0.  Non-finite inputs: WCQP_E_INVALID, before anything of the handle changes, for a NaN or an Inf in ref_traj,
+ * dcm_vel_traj (where it is read), dcm0, com0, u_init or q0 - of any robot: such a value would enter that robot's state on the first tick
+ * and never leave.  wcqp_tick_splice_reference refuses a non-finite ref_tail the same way. */
+int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in);
 /* enqueue only; use_graph: hipGraph replays of 8 ticks each, remainder as plain launches - IGNORED (no graph is built) whenever
  * the fused kernel runs several ticks per launch, i.e. for every wcqp_tick_params.ticks_per_launch != 1 including the default 0,
  * which makes a whole call ONE launch: a caller that needs the device back within a bound (another stream's work, a watchdog)
@@ -640,7 +681,13 @@ int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stage
  * retained.  Required before every wcqp_tick_run call of such a handle (which then takes n_ticks = 1: WCQP_E_INVALID otherwise,
  * or when no feedback has been set since the last tick); WCQP_E_UNSUPPORTED on a handle with the internal plant.
  * Replaces: WalkingController::setFeedback (:612), WalkingZMPController::setFeedback (:665), the joint part of
- * WalkingQPIK::setRobotState (:373) of WM/src/WalkingModule.cpp. */
+ * WalkingQPIK::setRobotState (:373) of WM/src/WalkingModule.cpp.
+ * Non-finite inputs: a robot with a NaN or an Inf in its dcm_meas, com_meas, zmp_meas or q_meas entries is REJECTED by rule 5 of the sensor
+ * form below: it keeps the measured state of tick t - 1 (tick 0: the uploaded one, with the desired joints), wcqp_tick_outputs.feedback_fail
+ * counts it, and it is stopped like a robot whose IK failed - dq = 0 from tick t on, ik_fail counting the rejection (when it was not stopped
+ * yet) and every tick it runs stopped, tick t included.  Nothing non-finite enters its state; the other robots are unaffected.  (A second
+ * call before the tick runs replaces the first; a robot the second call rejects keeps what the first gave it, and feedback_fail counts
+ * rejected calls.) */
 int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const double* com_meas, const double* zmp_meas,
                                   const double* q_meas, void* stream);
 /* the same from HOST pointers: staged through device memory of the handle and IN PLACE when the call returns (it synchronises: the host

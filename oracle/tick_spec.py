@@ -128,7 +128,8 @@ def run_ticks(p: TickParams, data: dict, n_ticks: int, ik_params: qs.IKParams, i
     p_star = data["com0"].copy(); v_star_prev = np.zeros((B, 2))
     q_des = data["q0"].copy(); dq_prev = np.zeros((B, 23))
     u0_log = np.zeros((n_ticks, B, 2)); dq_log = np.zeros((n_ticks, B, 23))
-    mpc_fail = np.zeros(B, np.int64); ik_fail = np.zeros(B, np.int64)
+    mpc_fail = np.zeros(B, np.int64); ik_fail = np.zeros(B, np.int64); feedback_fail = np.zeros(B, np.int64)
+    q_ik_prev = None
     use_kin = kin_model is not None
     state_now = data["state0"].copy()
     hull_cur = [None] * B; hull_code = -np.ones(B, np.int64)
@@ -147,8 +148,22 @@ def run_ticks(p: TickParams, data: dict, n_ticks: int, ik_params: qs.IKParams, i
             data["ref_traj"][:, frm:frm + tail.shape[1]] = tail
         code = contact_code(t, data["phase0"], p)
         if external is not None:
-            dcm = np.array(external["dcm"][t], float); com = np.array(external["com"][t], float); zmp_meas = np.array(external["zmp"][t], float)
-        q_ik = np.array(external["q"][t], float) if (external is not None and external.get("q") is not None) else q_des
+            # a robot whose feedback of tick t holds a NaN or an Inf (any of its dcm, com, zmp or q entries) is REJECTED, by the rule of the
+            # sensor form (include/wcqp.h, wcqp_tick_set_feedback_*): it keeps the measured state tick t - 1 used (tick 0: the uploaded
+            # one, with the desired joints), feedback_fail counts it, and it is stopped like a robot whose IK failed - ik_fail counts the
+            # rejection (when it was not stopped yet) and every tick it runs stopped, tick t included
+            new = [np.array(external[k][t], float) for k in ("dcm", "com", "zmp")]
+            q_new = np.array(external["q"][t], float) if external.get("q") is not None else None
+            bad = ~np.isfinite(np.concatenate(new + ([q_new] if q_new is not None else []), 1)).all(1)
+            held = (dcm_log[t - 1], com_log[t - 1], zmp_log[t - 1]) if t > 0 else (data["dcm0"], data["com0"], data["u_init"])
+            dcm, com, zmp_meas = (np.where(bad[:, None], h, n) for h, n in zip(held, new))
+            q_keep = q_ik_prev if t > 0 else q_des
+            q_ik = np.where(bad[:, None], q_keep, q_new if q_new is not None else q_des)
+            q_ik_prev = q_ik
+            feedback_fail += bad
+            ik_fail[bad & (ik_fail == 0)] = 1
+        else:
+            q_ik = q_des
         dcm_log[t] = dcm; com_log[t] = com; zmp_log[t] = zmp_meas; q_log[t] = q_des
         if use_kin:
             ident = np.concatenate([np.zeros(3), np.eye(3).reshape(9)])
@@ -240,6 +255,6 @@ def run_ticks(p: TickParams, data: dict, n_ticks: int, ik_params: qs.IKParams, i
         dcm = c.a * dcm + c.b * u0 + p.noise * w
         zmp_meas = u0.copy(); u_prev = u0.copy()
         u0_log[t] = u0; dq_log[t] = dq
-    return dict(u0_log=u0_log, dq_log=dq_log, q_des=q_des, dcm=dcm, com=com, mpc_fail=mpc_fail, ik_fail=ik_fail, logger=logger,
+    return dict(u0_log=u0_log, dq_log=dq_log, q_des=q_des, dcm=dcm, com=com, mpc_fail=mpc_fail, ik_fail=ik_fail, feedback_fail=feedback_fail, logger=logger,
                 dcm_log=dcm_log, com_log=com_log, zmp_log=zmp_log, q_log=q_log,
                 active_lower=act_lo[-1], active_upper=act_up[-1], active_lower_log=act_lo, active_upper_log=act_up)

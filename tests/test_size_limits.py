@@ -1,0 +1,145 @@
+"""
+The size guard behind the kernels' 32-bit addressing (include/wcqp.h, "Size limits"; csrc/wcqp_internal.h: wcqp::at32 / wcqp::fits32).
+
+The solve kernels reach row i of a per-robot array as base + a 32-bit byte offset.  Past 4 GB the offset wraps: nothing faults, the kernel
+reads another robot's rows and reports SOLVED.  So every entry point refuses, from its arguments alone, a batch whose arrays do not end
+within 2^32 bytes - and must not refuse one that does.
+
+CPU part: every entry point at the largest admitted size (anything but WCQP_E_UNSUPPORTED) and one past it (WCQP_E_UNSUPPORTED), with dummy
+pointers the guard must never dereference, in a child process that sees no device (tests/helpers/size_limit_probe.py).  The expected limits
+are computed HERE from the row sizes the header documents, not read back from the library.
+
+GPU part: just under the limit the kernels still address every robot correctly - the last 4096 robots of the largest admitted batch, solved
+again as a batch of their own, give the same bits, and 16 of them match the exact oracle to 1e-9.
+"""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_UNSUPPORTED, E_HIP = -2, -4
+SOL_TOL = 1e-9
+
+# bytes per robot of the arrays the kernels address with 32-bit offsets (include/wcqp.h)
+IK_ROWS = dict(J_left=6 * 29 * 8, J_right=6 * 29 * 8, J_neck=3 * 29 * 8, J_com=3 * 29 * 8, q=23 * 8, state=87 * 8, dq=23 * 8)
+HAND_ROW = 14 * 8            # one MPC -> IK hand-off record of the tick; there are 2 x batch of them in one array
+
+
+def mpc_rows(ref_len):
+    return dict(ref=ref_len * 2 * 8, hull_A=8 * 2 * 8, hull_b=8 * 8, x0=16, u_prev=16, u0=16, margin=8, status=4)
+
+
+def limit(rows, copies=1):
+    """largest count with copies x count x row <= 2^32 for the widest row"""
+    return (1 << 32) // (max(rows) * copies)
+
+
+def mpc_limit(ref_len):
+    return limit(mpc_rows(ref_len).values())
+
+
+IK_LIMIT = limit(IK_ROWS.values())
+
+
+def tick_limit(max_ticks, horizon):
+    traj = (max_ticks + horizon + 1) * 16
+    return min(limit([traj]), limit([HAND_ROW], copies=2), IK_LIMIT)
+
+
+def test_the_documented_rows_give_the_documented_limits():
+    assert IK_ROWS["J_left"] == 1392 and IK_ROWS["state"] == 696 and IK_LIMIT == 3085465
+    assert mpc_limit(51) == (1 << 28) // 51 and mpc_limit(201) == 1335499 and mpc_limit(4096) == 65536
+    assert mpc_limit(1) == 1 << 25                       # a window shorter than 8 stages: the hull rows (128 B) are the widest
+    assert tick_limit(4045, 50) == 65536 and tick_limit(10, 50) == IK_LIMIT
+
+
+def _cases():
+    out = []
+    for ref_len, horizon in ((1, 50), (51, 50), (201, 200), (4097, 50)):
+        out.append(dict(entry="mpc_solve_device", ref_len=ref_len, horizon=horizon, limit=mpc_limit(ref_len)))
+    out.append(dict(entry="ik_solve_device", limit=IK_LIMIT))
+    for entry in ("qp_enqueue_steps", "qp_plan_create", "qp_step_from_slabs"):
+        for ref_len in (51, 4097):
+            out.append(dict(entry=entry, ref_len=ref_len, limit=min(mpc_limit(ref_len), IK_LIMIT)))
+    out.append(dict(entry="qp_plan_create_mpc_only", ref_len=4097, limit=mpc_limit(4097)))
+    out.append(dict(entry="qp_plan_create_mpc_only", ref_len=8, limit=mpc_limit(8)))          # past the IK's limit: no IK part, no IK limit
+    out.append(dict(entry="qp_plan_create_ik_only", limit=IK_LIMIT))
+    for max_ticks, horizon, ext in ((4045, 50, False), (10, 50, False), (2000, 200, True), (4045, 50, True)):
+        out.append(dict(entry="tick_create", max_ticks=max_ticks, horizon=horizon, external=ext, limit=tick_limit(max_ticks, horizon)))
+    return out
+
+
+@pytest.fixture(scope="module")
+def probe(wca):
+    """every case at its limit and one past it, in ONE child process that sees no device"""
+    cases = []
+    for c in _cases():
+        cases.append(dict(c, batch=c["limit"], at="limit"))
+        cases.append(dict(c, batch=c["limit"] + 1, at="past"))
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "size_limit_probe.py"), json.dumps(cases)],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def _label(c):
+    return "%s ref_len=%s max_ticks=%s batch=%d" % (c["entry"], c.get("ref_len"), c.get("max_ticks"), c["batch"])
+
+
+def test_the_largest_admitted_size_passes_the_guard(probe):
+    """... and then fails for lack of a device (or, the slab arithmetic, succeeds): anything but WCQP_E_UNSUPPORTED"""
+    got = [c for c in probe if c["at"] == "limit"]
+    assert len(got) == len(_cases())
+    for c in got:
+        want = 0 if c["entry"] == "qp_step_from_slabs" else E_HIP
+        assert c["rc"] == want, (_label(c), c["rc"])
+
+
+def test_one_past_the_limit_is_refused(probe):
+    got = [c for c in probe if c["at"] == "past"]
+    assert len(got) == len(_cases())
+    for c in got:
+        assert c["rc"] == E_UNSUPPORTED, (_label(c), c["rc"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GPU: just under the limit (one process per case: tests/helpers/size_limit_gpu.py builds the batch on the device, solves it, solves
+# the last 4096 robots again as a batch of their own, compares bits and checks 16 robots against the exact oracle)
+def _run_gpu_case(name, timeout):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "size_limit_gpu.py"), name],
+                       capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    print(res)
+    return res
+
+
+@pytest.mark.gpu
+def test_mpc_horizon_200_at_the_largest_admitted_batch():
+    res = _run_gpu_case("mpc", 900)
+    assert res["batch"] == mpc_limit(201) and res["tail"] == 4096
+    assert res["tail_bit_identical"] and res["all_status_solved_or_hull"]
+    assert res["checked"] == 16 and res["max_err"] <= SOL_TOL
+
+
+@pytest.mark.gpu
+def test_ik_default_kernel_at_the_largest_admitted_batch():
+    res = _run_gpu_case("ik", 900)
+    assert res["batch"] == IK_LIMIT and res["tail"] == 4096
+    assert res["tail_bit_identical"] and res["tail_solved"] >= 16
+    assert res["checked"] == 16 and res["max_err"] <= SOL_TOL
+
+
+@pytest.mark.gpu
+def test_constant_jacobian_tick_with_trajectories_that_fill_the_32_bit_range():
+    """batch x traj_len = 2^28 stages (the largest wcqp_tick_create admits at traj_len = 1024), 3 ticks: the last 4096 robots - whose
+    trajectory offsets `(inst * traj_len + t) * 16` and hand-off records lie closest to 2^32 - run again as a handle of their own give the
+    same bits, and the last 16 match oracle/tick_spec.py at 1e-9"""
+    res = _run_gpu_case("tick", 900)
+    assert res["traj_len"] == 1024 and res["batch"] == tick_limit(973, 50) == (1 << 28) // 1024 and res["ticks"] == 3 and res["tail"] == 4096
+    assert res["tail_bit_identical"]
+    assert res["checked"] == 16 and res["max_err"] <= SOL_TOL

@@ -81,6 +81,10 @@ int wcqp_version(void) { return WCQP_VERSION; }
 int wcqp_qp_enqueue_steps(wcqp_mpc_t mpc, wcqp_ik_t ik, int32_t batch, int32_t n_steps, const wcqp_qp_step* steps, int32_t* n_done) {
     if (n_done) *n_done = 0;
     if (n_steps < 0 || (n_steps > 0 && !steps)) return WCQP_E_INVALID;
+    // the size limits of the two calls (wcqp::fits32), for every record before the first is enqueued
+    for (int32_t k = 0; k < n_steps; ++k)
+        if ((steps[k].x0 && steps[k].ref_len >= 1 && !wcqp::mpc_batch_fits32(batch, steps[k].ref_len)) || (steps[k].J_left && !wcqp::ik_batch_fits32(batch)))
+            return WCQP_E_UNSUPPORTED;
     for (int32_t k = 0; k < n_steps; ++k) {
         const wcqp_qp_step& s = steps[k];
         {
@@ -122,6 +126,8 @@ int wcqp_slab_layout_for(int32_t batch, int32_t ref_len, wcqp_slab_layout* out) 
 
 int wcqp_qp_step_from_slabs(const wcqp_slab_layout* L, const void* in_slab, void* out_slab, wcqp_qp_step* s) {
     if (!L || !in_slab || !out_slab || !s || L->batch < 1 || L->ref_len < 1) return WCQP_E_INVALID;
+    // a step over slabs goes to the solve kernels as it stands: the limits of wcqp_qp_enqueue_steps (wcqp::fits32)
+    if (!wcqp::mpc_batch_fits32(L->batch, L->ref_len) || !wcqp::ik_batch_fits32(L->batch)) return WCQP_E_UNSUPPORTED;
     if (((uintptr_t)in_slab | (uintptr_t)out_slab) & 15u) return WCQP_E_INVALID;        // 16-byte vector loads; the arrays inside sit on 256-byte offsets
     const char* in = static_cast<const char*>(in_slab);
     char* o = static_cast<char*>(out_slab);

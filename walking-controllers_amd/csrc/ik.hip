@@ -179,6 +179,7 @@ int wcqp_ik_solve_device(wcqp_ik_t h, int32_t batch,
                          double* foot_err, int32_t* iters, void* stream) {
     if (!h || batch < 0) return WCQP_E_INVALID;
     if (!J_left || !J_right || !J_neck || !J_com || !q || !state || !dq || !status) return WCQP_E_INVALID;
+    if (!wcqp::ik_batch_fits32(batch)) return WCQP_E_UNSUPPORTED;
     if (batch == 0) return WCQP_OK;
     const int rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
@@ -222,6 +223,7 @@ int qp_pair_enqueue(wcqp_mpc_t mpc, wcqp_ik_t h, int batch, const wcqp_qp_step& 
     if (h->route != IkRoute::BASE_ELIM) return WCQP_E_UNSUPPORTED;
     if (s.ref_len < 1 || !s.ref || !s.u_prev || !s.hull_A || !s.hull_b || !s.hull_nc || !s.u0 || !s.mpc_status) return WCQP_E_INVALID;
     if (!s.J_right || !s.J_neck || !s.J_com || !s.q || !s.state || !s.dq || !s.ik_status) return WCQP_E_INVALID;
+    // (the size limits of wcqp::fits32 were checked by the one caller, wcqp_qp_enqueue_steps, for every record)
     int rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     rc = mpc_prepare(mpc);
@@ -274,6 +276,9 @@ int wcqp_qp_plan_create(wcqp_mpc_t mpc, wcqp_ik_t ik, int32_t batch, int32_t n_s
         if (!ik_only && (!s.x0 || !s.ref || s.ref_len < 1 || !s.u_prev || !s.hull_A || !s.hull_b || !s.hull_nc || !s.u0 || !s.mpc_status)) return WCQP_E_INVALID;
         if (!mpc_only && (!s.J_left || !s.J_right || !s.J_neck || !s.J_com || !s.q || !s.state || !s.dq || !s.ik_status)) return WCQP_E_INVALID;
     }
+    // the plan kernels address every record's arrays with 32-bit offsets (wcqp::fits32)
+    for (int k = 0; k < n_steps; ++k)
+        if ((!ik_only && !wcqp::mpc_batch_fits32(batch, steps[k].ref_len)) || (!mpc_only && !wcqp::ik_batch_fits32(batch))) return WCQP_E_UNSUPPORTED;
     if (mpc_only && ways < 1) return WCQP_E_UNSUPPORTED;        // the work-queue form belongs to the IK + MPC kernel
     if (!mpc_only) {
         // one launch walks through the records: that is the base-eliminated kernel on Jacobians the caller declares MIXED (no
@@ -332,6 +337,7 @@ int wcqp_ik_solve_host(wcqp_ik_t h, int32_t batch,
                        double* foot_err, int32_t* iters) {
     if (!h || batch < 0) return WCQP_E_INVALID;
     if (!J_left || !J_right || !J_neck || !J_com || !q || !state || !dq || !status) return WCQP_E_INVALID;
+    if (!wcqp::ik_batch_fits32(batch)) return WCQP_E_UNSUPPORTED;
     if (batch == 0) return WCQP_OK;
     int rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;

@@ -526,6 +526,8 @@ void ik2_kernel(const IkDeviceParams* __restrict__ prm, int batch,
 
     WCQP_STAMP(8);
     // ---------------- outputs ---------------------------------------------------------------
+    // non-finite inputs (include/wcqp.h): no robot hands out a NaN - NUMERIC, dq = 0, empty active sets (ik4_device.h has the same)
+    if (((__ballot(i >= 6 && var && !isfinite(nu)) >> (32 * half)) & 0xffffffffull) != 0ull) { st_code = WCQP_STATUS_NUMERIC; nu = 0.0; in_w = false; }
     const unsigned long long bu = __ballot(in_w && my_sig > 0.0);
     const unsigned long long bl = __ballot(in_w && my_sig < 0.0);
     if (live) {

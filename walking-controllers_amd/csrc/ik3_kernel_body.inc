@@ -821,6 +821,11 @@
 
     WCQP_STAMP(8);
     // ---------------- outputs ------------------------------------------------------------------------
+    // non-finite inputs (include/wcqp.h): no robot hands out a NaN - NUMERIC, dq = 0, empty active sets (ik4_device.h has the same)
+    {
+        const bool nf_lane = (j >= 6 && !isfinite(nu0)) || (var1 && !isfinite(nu1));
+        if (row_max_u32(nf_lane ? 1u : 0u) != 0u) { st_code = WCQP_STATUS_NUMERIC; nu0 = 0.0; nu1 = 0.0; in_w0 = false; in_w1 = false; }
+    }
     const unsigned long long bu0 = __ballot(in_w0 && sig0 > 0.0), bu1 = __ballot(in_w1 && sig1 > 0.0);
     const unsigned long long bl0 = __ballot(in_w0 && sig0 < 0.0), bl1 = __ballot(in_w1 && sig1 < 0.0);
     if (live) {

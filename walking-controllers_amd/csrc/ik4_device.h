@@ -210,7 +210,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     const bool live = inst_raw < batch;
     const long inst = live ? inst_raw : (long)batch - 1;
     // 32-bit addressing (wcqp::at32): uniform array base + this lane's BYTE offset - the host entry points refuse batches whose
-    // arrays do not fit 4 GB
+    // arrays do not fit 4 GB (wcqp::fits32 / ik_batch_fits32, wcqp_internal.h)
     using wcqp::at32;
     const unsigned iu = (unsigned)inst, j8 = (unsigned)j * 8u;
     double* S = smem[grp];
@@ -1574,6 +1574,11 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     double dq0 = nu0 * sd0, dq1 = nu1 * sd1;
     if (st_code == WCQP_STATUS_SOLVED && in_w0) dq0 = sig0 > 0.0 ? prm->vhi[v0i] : prm->vlo[v0i];
     if (st_code == WCQP_STATUS_SOLVED && in_w1) dq1 = sig1 > 0.0 ? prm->vhi[v1i] : prm->vlo[v1i];
+    // Non-finite inputs (include/wcqp.h): a NaN or an Inf in a joint column, in q or in the pose block has reached the velocities by
+    // now - the QP couples every unknown - and the certificate above has already taken SOLVED away.  No robot hands out a NaN: the
+    // 16 lanes agree (one reduction), the status is NUMERIC, dq = 0 and the active sets are empty.
+    const bool nonfinite = row_max_u32((isfinite(dq0) && (!var1 || isfinite(dq1))) ? 0u : 1u) != 0u;
+    if (nonfinite) { st_code = WCQP_STATUS_NUMERIC; dq0 = 0.0; dq1 = 0.0; in_w0 = false; in_w1 = false; }
     const unsigned long long bu0 = __ballot(in_w0 && sig0 > 0.0), bu1 = __ballot(in_w1 && sig1 > 0.0);
     const unsigned long long bl0 = __ballot(in_w0 && sig0 < 0.0), bl1 = __ballot(in_w1 && sig1 < 0.0);
     if (!use) {

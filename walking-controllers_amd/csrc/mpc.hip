@@ -234,6 +234,9 @@ int mpc_enqueue(wcqp_mpc_t h, int batch, const double* x0, const double* ref, in
                 double* u0, int* status, unsigned* active, double* margin, hipStream_t stream) {
     if (!h || batch < 0 || ref_len < 1 || ref_stride < ref_len || hull_sets < 1) return WCQP_E_INVALID;
     if (!x0 || !ref || !u_prev || !hull_A || !hull_b || !hull_nc || !u0 || !status) return WCQP_E_INVALID;
+    // (this kernel forms its addresses in 64 bits; the limit is the one of the kernels that solve the same QP on the IK's lanes -
+    // wcqp_qp_enqueue_steps, the plans, the tick - so that a batch one route takes is a batch every route takes)
+    if (!fits32(batch, (long long)ref_stride * 16) || !fits32((long long)batch * hull_sets, WCQP_HULL_ROWS * 16)) return WCQP_E_UNSUPPORTED;
     if (batch == 0) return WCQP_OK;
     const int rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
@@ -331,6 +334,7 @@ int wcqp_mpc_solve_host(wcqp_mpc_t h, int32_t batch,
                         double* u0, int32_t* status, uint32_t* active, double* margin) {
     if (!h || batch < 0 || ref_len < 1) return WCQP_E_INVALID;
     if (!x0 || !ref || !u_prev || !hull_A || !hull_b || !hull_nc || !u0 || !status) return WCQP_E_INVALID;
+    if (!wcqp::mpc_batch_fits32(batch, ref_len)) return WCQP_E_UNSUPPORTED;
     if (batch == 0) return WCQP_OK;
     int rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;

@@ -195,6 +195,10 @@ __device__ __forceinline__ void mpc_row_finish(const MpcDeviceConsts& c, int t, 
                                                double& u0x, double& u0y, int& status, unsigned& active, double& margin_out)
 {
     nc = nc < 0 ? 0 : (nc > WCQP_HULL_ROWS ? WCQP_HULL_ROWS : nc);
+    // Non-finite inputs (include/wcqp.h: WCQP_STATUS_NUMERIC): a NaN or Inf in a reference stage of the window, in x0 or in u_prev is
+    // in this lane's partial sum already (0 x NaN = NaN: a zero gain does not hide it); one in a hull row the QP reads (lanes t < nc)
+    // is folded in here, so that the all-reduce below tells every lane of the row - no reduction of its own.  Rows >= nc are not looked at.
+    if (t < nc && !(isfinite(rax) && isfinite(ray) && isfinite(rb))) ux = std::numeric_limits<double>::quiet_NaN();
     // 1 / |a| of this lane's own hull row (lanes 0..7; 0 for a zero row): the margin below divides by the norm
     const double rn2 = fma(ray, ray, rax * rax);
     const double irn = (t < WCQP_HULL_ROWS && rn2 > 0.0) ? wcqp::fast_rsqrt(rn2) : 0.0;
@@ -202,6 +206,9 @@ __device__ __forceinline__ void mpc_row_finish(const MpcDeviceConsts& c, int t, 
 #define WCQP_SUM_STEP(C) ux += row_move<C>(ux); uy += row_move<C>(uy);
     WCQP_ROW_STEPS(WCQP_SUM_STEP)
 #undef WCQP_SUM_STEP
+    // the same on the 16 lanes of the row.  A poisoned robot takes no part in the wave's choice of path below and its result does not
+    // depend on the path: what its neighbours do cannot change what it reports.
+    const bool poisoned = !(isfinite(ux) && isfinite(uy));
 
     // ---- projection onto the polygon in the Sigma0^-1 metric --------------------------
     const double s00 = c.S0[0], s01 = c.S0[1], s10 = c.S0[2], s11 = c.S0[3];
@@ -213,7 +220,7 @@ __device__ __forceinline__ void mpc_row_finish(const MpcDeviceConsts& c, int t, 
     // already satisfies its hull rows, candidate 0 wins by construction (cost 0, lowest id) and the
     // 37-candidate enumeration is skipped.  Same feasibility test as the enumeration applies to
     // candidate 0, so the result is identical either way.
-    const bool row_violated = t < nc && row_res(rax, ray, rb, ux, uy) > c.feas_tol;
+    const bool row_violated = !poisoned && t < nc && row_res(rax, ray, rb, ux, uy) > c.feas_tol;
     const bool none_violated = __ballot(row_violated) == 0ull;        // wave-uniform
     if (none_violated) {
         best_cost = 0.0; best_id = 0;
@@ -285,6 +292,7 @@ __device__ __forceinline__ void mpc_row_finish(const MpcDeviceConsts& c, int t, 
     // WalkingController::solve: computeMargin(u0) < -tolerance => failure (cpp:513-517)
     if (st == WCQP_STATUS_SOLVED && margin < -c.hull_tol) st = WCQP_STATUS_OUTSIDE_HULL;
     u0x = best_x; u0y = best_y; status = st; active = best_mask; margin_out = margin;
+    if (poisoned) { u0x = 0.0; u0y = 0.0; status = WCQP_STATUS_NUMERIC; active = 0u; margin_out = -std::numeric_limits<double>::infinity(); }
     wcqp::wave_lds_fence();            // s_hull may be reused by the caller
 }
 #endif

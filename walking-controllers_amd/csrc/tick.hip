@@ -164,12 +164,33 @@ __global__ __launch_bounds__(64) void tick_desired_kernel(DesiredDev a, PlanRect
 }
 
 // external feedback: the caller's measured state into the places the next tick reads its plant state from - the skewed
-// chain's per-axis records (mst: com [2], dcm [6], measured ZMP [7]) - and the measured joints into q_meas (NULL: the desired ones)
+// chain's per-axis records (mst: com [2], dcm [6], measured ZMP [7]) - and the measured joints into q_meas (NULL: the desired ones).
+// A robot with a NaN or an Inf anywhere in its feedback is REJECTED by the rule of the sensor form (sensors.hip; include/wcqp.h): it keeps
+// the measured state tick t - 1 used (the hand-off record of parity t - 1; tick 0: the uploaded state, with the desired joints), is
+// counted in feedback_fail and stopped like a robot whose IK failed.  (A second call before the tick runs replaces the first: a robot it
+// rejects keeps what the first call gave it, and feedback_fail counts calls.)  One thread per (robot, joint): each looks at the robot's whole
+// feedback itself (29 values out of L2) - no exchange between threads that may sit in different workgroups.
 __global__ void tick_feedback_kernel(TickDev d, const double* __restrict__ dcm, const double* __restrict__ com, const double* __restrict__ zmp,
-                                     const double* __restrict__ q, double* __restrict__ q_meas) {
+                                     const double* __restrict__ q, double* __restrict__ q_meas, long long* __restrict__ feedback_fail, int t) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.batch * kDof) return;
     const int i = g / kDof, jj = g % kDof;
+    bool ok = true;
+    for (int k = 0; k < 2; ++k) ok = ok && isfinite(dcm[2 * i + k]) && isfinite(com[2 * i + k]) && isfinite(zmp[2 * i + k]);
+    if (q) for (int k = 0; k < kDof; ++k) ok = ok && isfinite(q[(size_t)i * kDof + k]);
+    if (!ok) {
+        if (t == 0) q_meas[g] = d.q_des[g];
+        if (jj < 2 && t > 0) {
+            double* r = d.mst + ((size_t)i * 2 + jj) * 8;
+            const double* hd = d.hand + ((size_t)((t - 1) & 1) * d.batch + i) * kHandLen;
+            r[2] = hd[4 + jj]; r[6] = hd[6 + jj]; r[7] = hd[10 + jj];
+        }
+        if (jj == 0) {
+            feedback_fail[i] += 1;
+            if (d.ik_fail[i] == 0) d.ik_fail[i] = 1;
+        }
+        return;
+    }
     q_meas[g] = q ? q[g] : d.q_des[g];
     if (jj < 2) {
         double* r = d.mst + ((size_t)i * 2 + jj) * 8;
@@ -355,6 +376,12 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
             (params->dcm_controller == WCQP_TICK_DCM_MPC && params->mpc.horizon >= kGainsLdsStages))
             return WCQP_E_UNSUPPORTED;
     }
+    // the tick kernels address the handle's per-robot arrays with 32-bit offsets (wcqp::fits32; from the parameters alone, before anything
+    // touches the device): the trajectories ref_traj / dcm_vel [B][max_ticks + N + 1][2], the two MPC -> IK hand-off records [2][B][kHandLen]
+    // and the IK's arrays, J_left / J_right [B][6][29] the widest.  (The planned-trajectory records use 64-bit offsets.)
+    if (!wcqp::fits32(params->batch, ((long long)params->max_ticks + (params->mpc.horizon > 0 ? params->mpc.horizon : 0) + 1) * 16) ||
+        !wcqp::fits32(2ll * params->batch, kHandLen * 8) || !wcqp::ik_batch_fits32(params->batch))
+        return WCQP_E_UNSUPPORTED;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         std::fprintf(stderr, "[wcqp] no HIP device: the tick pipeline has no CPU fallback\n");
@@ -436,9 +463,9 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     // external feedback: the default (base-eliminated) kernel with constant Jacobians or fused kinematics, without logger rows
     if (h->external && (!d.skew || params->logger_ticks > 0 || (h->kin && !fusedk))) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }
     if ((planned || streamed) && (!d.skew || !fusedk)) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }      // (checked above, before any allocation)
-    if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); }
+    if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); A_(h->feedback_fail, B); }
     if (h->external && h->kin) {
-        A_(h->sens_stage, B * (2 * kDof + 12)); A_(h->feedback_fail, B);
+        A_(h->sens_stage, B * (2 * kDof + 12));
         if (rc == WCQP_OK && hipEventCreateWithFlags(&h->run_done, hipEventDisableTiming) != hipSuccess) rc = WCQP_E_HIP;
     }
     if (reactive) { d.reactive = 1; d.k_dcm = params->k_dcm; }
@@ -633,6 +660,15 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     if (!h->kin && !h->d.reactive && (!in->hull_tab_A || !in->hull_tab_b || !in->hull_tab_nc)) return WCQP_E_INVALID;
     TickDev& d = h->d;
     const size_t B = (size_t)d.batch;
+    // Non-finite inputs (include/wcqp.h): a NaN or an Inf in the reference trajectory (and its velocity), the initial DCM / CoM / command or
+    // the initial joints would enter a robot's state on the first tick that reads it and never leave: refused here, before anything of
+    // the handle changes (a handle uploaded before keeps that upload)
+    {
+        auto finite = [](const double* a, size_t n) { bool ok = true; for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(a[k]); return ok; };
+        if (!finite(in->ref_traj, B * d.traj_len * 2) || !finite(in->dcm0, B * 2) || !finite(in->com0, B * 2) || !finite(in->u_init, B * 2) ||
+            !finite(in->q0, B * kDof) || ((d.reactive || d.gain_sched) && in->dcm_vel_traj && !finite(in->dcm_vel_traj, B * d.traj_len * 2)))
+            return WCQP_E_INVALID;
+    }
     // from here on the device state changes: a call that fails on the way leaves the handle unrunnable until the next good upload
     h->uploaded = false;
     WCQP_HIP_TRY(hipDeviceSynchronize());
@@ -804,7 +840,8 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
     if (!h->external) return WCQP_E_UNSUPPORTED;
     if (!h->uploaded) return WCQP_E_INVALID;
     const int n = h->d.batch * kDof;
-    hipLaunchKernelGGL(tick_feedback_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d, dcm_meas, com_meas, zmp_meas, q_meas, h->q_meas);
+    hipLaunchKernelGGL(tick_feedback_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d, dcm_meas, com_meas, zmp_meas, q_meas, h->q_meas,
+                       h->feedback_fail, h->ticks_enqueued);
     WCQP_HIP_TRY(hipGetLastError());
     h->feedback_set = true;
     return WCQP_OK;
@@ -949,6 +986,7 @@ int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stage
     // tick's window can see may change
     if (from_tick < h->ticks_enqueued || (long)from_tick + n_stages > (long)d.traj_len) return WCQP_E_INVALID;
     if (h->vel_explicit) return WCQP_E_UNSUPPORTED;      // (uploaded velocities - reactive controller, gain scheduling: the splice has no tail for them)
+    for (size_t k = 0; k < (size_t)d.batch * (size_t)n_stages * 2; ++k) if (!std::isfinite(ref_tail[k])) return WCQP_E_INVALID;      // (as the upload: no NaN / Inf into the reference)
     // `ref_tail` is the caller's HOST memory and the copy below is ordered behind ticks that may still run for a long time: the
     // rows are therefore taken NOW - staged into device memory of the handle on a copy stream of its own, waited for before
     // this call returns - and the caller may release `ref_tail` as soon as it has.

@@ -371,7 +371,7 @@ struct TickMpcRegs {
 // GAINS_LDS: the gain blocks Gr are read from a copy in LDS at the time of use (gr_lds), not loaded into registers here
 template <bool GAINS_LDS = false>
 __device__ __forceinline__ void tick_mpc_issue(const TickDev& d, int j, long inst, int t, TickMpcRegs& R) {
-    // (32-bit addressing, wcqp::at32: wcqp_tick_create refuses batches whose trajectories do not fit 4 GB)
+    // (32-bit addressing, wcqp::at32: wcqp_tick_create refuses batches whose trajectories do not fit 4 GB - wcqp::fits32)
     const unsigned iu = (unsigned)inst;
     const double2* ref = reinterpret_cast<const double2*>(d.ref_traj.get());
     const unsigned w0 = iu * (unsigned)d.traj_len + (unsigned)t;

@@ -18,6 +18,17 @@
 
 namespace wcqp_mpc { struct MpcDeviceConsts; }
 namespace wcqp {
+// The size guard behind wcqp::at32 (below): the kernels address a caller-sized array of `count` rows of `row_bytes` bytes each with
+// a 32-bit BYTE offset, so the array must end within 2^32 bytes of its base.  Every entry point that hands such an array to a kernel
+// calls this first - before it looks for a device, allocates or launches - and returns WCQP_E_UNSUPPORTED when it fails
+// (include/wcqp.h lists the rows per entry point).  Never touches the arrays themselves.
+inline bool fits32(long long count, long long row_bytes) {
+    return count >= 0 && row_bytes >= 0 && (row_bytes == 0 || count <= (1ll << 32) / row_bytes);
+}
+// the widest rows of the two solve calls (bytes per robot): the reference window ref[ref_len][2], and J_left / J_right [6][29]
+constexpr long long kRowBytesIkJacobian = 6 * 29 * 8;       // 1392; J_neck / J_com 696, state 696, q / dq 184
+inline bool mpc_batch_fits32(long long batch, long long ref_len) { return fits32(batch, ref_len * 16) && fits32(batch, WCQP_HULL_ROWS * 16); }
+inline bool ik_batch_fits32(long long batch) { return fits32(batch, kRowBytesIkJacobian); }
 void mpc_device_consts(wcqp_mpc_t h, wcqp_mpc::MpcDeviceConsts* c);   // kernel-argument copy of the condensed constants (after mpc_prepare)
 
 // Dense LU with partial pivoting, row-major, in place; returns false when singular.
@@ -93,7 +104,7 @@ __device__ __forceinline__ int dpp_dword(int v) {
 // gptr.h) and a zero-extended 32-bit per-lane offset the access is `global_load ... v_off, s[base:base+1] offset:imm` - no 64-bit
 // VALU arithmetic at all, and constant element offsets behind it fold into the immediate.  Written as `ptr + long_index * stride`
 // the same address costs a 64-bit multiply-add and a 64-bit add per array (~8 VALU instructions each, ~150 per robot-tick record
-// in the solve kernels' load phase).  The caller guarantees that the offset fits 32 bits (the host entry points check batch x stride).
+// in the solve kernels' load phase).  The caller guarantees that the offset fits 32 bits: the host entry points check count x row bytes with wcqp::fits32 (above).
 template <class T>
 __device__ __forceinline__ const T* at32(const T* base, unsigned byte_off) { return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off); }
 template <class T>
