@@ -1,12 +1,12 @@
 """
 ORACLE — TEST INFRASTRUCTURE ONLY.
 
-CPU restatement of the per-tick call order of WalkingModule::updateModule around the two
-solvers (WM/src/WalkingModule.cpp:578-745) for a batch of synthetic robots, using the exact
-solvers of oracle/qp_spec.py.  It is the checker of the device-resident tick pipeline
-(walking-controllers_amd/csrc/tick.hip, BASELINE configs 4 and 5).
+CPU restatement of the per-tick call order of WalkingModule::updateModule around the two solvers (WM/src/WalkingModule.cpp:578-745) for a
+batch of robots, using the exact solvers of oracle/qp_spec.py.  run_ticks is the ONE restatement of the tick loop and the checker of the
+device-resident tick pipeline (walking-controllers_amd/csrc/tick.hip, BASELINE configs 4 and 5): every mode the device has
+(include/wcqp.h: wcqp_tick_params; the keywords of TickPipeline) is an argument of it.
 
-What is restated from the reference (and where):
+What every run restates from the reference (and where):
   LIPM reference    v = -omega (c - dcm_des), c <- Integrator(v)      WM/src/StableDCMModel.cpp:63-90
   MPC               setConvexHullConstraint / setFeedback / setReferenceSignal / solve
                                                                       WM/src/WalkingModule.cpp:604-636
@@ -18,14 +18,35 @@ What is restated from the reference (and where):
   reference deque   advances one stage per tick                       WM/src/WalkingModule.cpp:35-96
   contact change    => new MPCSolver (cold start)                     …PredictiveController.cpp:415-420
 
+The modes, their arguments and where each is restated from:
+  per-tick kinematics   kin_model, foot_rect     forward kinematics at the integrated joints (:715), four fresh Jacobians and actual
+                        poses for the IK (:396-410), the base anchored at the fixed-frame foot (sensor_spec.anchored_base;
+                        WM/src/WalkingForwardKinematics.cpp:160-256), hull rows rebuilt from the DESIRED feet when the contact pair
+                        changes (…PredictiveController.cpp:364-435).  Without it: constant Jacobians and hull tables from `data`.
+  DCM controller        dcm_controller="reactive", k_dcm, dcm_vel     WalkingDCMReactiveController::evaluateControl
+                        (WM/src/WalkingDCMReactiveController.cpp:63-82; the reference's default, WalkingModule.cpp:124, :188-211, :638-656):
+                        zmp_des = dcm_des - dcm_des_dot / omega - kDCM (dcm_des - dcm_measured), reactive_law.  dcm_des_dot is
+                        dcm_vel[B][stages][2] (the planner's, :641-642) or the forward difference of the reference.
+  gain scheduling       zmp_gain_schedule        WalkingZMPController::setPhase(|dcm_des_dot| < 0.001) before the controller's solve
+                        (WalkingModule.cpp:657-662, WalkingZMPController.cpp:29-125): oracle/zmp_gains_spec.py.  Reads the same dcm_vel.
+  desired stage         stages, neck_additional_rotation     what WalkingModule::updateTrajectories (:1085-1145) pulls from
+                        TrajectoryGenerator, per tick: desired feet / twists (state 24..47, 75..86), CoM height and its velocity
+                        (71, 74; :689, :695), the neck orientation RotZ(mean yaw of the feet) @ additional rotation (57..65; :697-707,
+                        :383; neck_orientation), the fixed-frame foot (contact bit 2; :1147-1165) and the contact pair (bits 0-1).
+                        Without it: the synthetic gait of `data` (contact_code, constant desired feet, the swing profile).
+  trajectory merge      splices                  WM/src/WalkingModule.cpp:500-535, 1263-1308
+  logger rows           logger_ticks             WM/src/WalkingModule.cpp:800-810, columns :1231-1250
+  plant                 (default) the synthetic LIPM plant below; external: measured state from arrays (setFeedback :612, :665,
+                        setRobotState :373), a robot with a NaN / Inf reading rejected and stopped; sensors: a robot in the loop whose
+                        readings go through oracle/sensor_spec.py (updateFKSolver, evaluateCoM / DCM / ZMP :1147-1217, :826-878).
+
 Declared choices (SURVEY Appendix D-7): iCub::ctrl::Integrator is upstream; it is restated
 as the trapezoidal (Tustin) rule y += Ts/2 (x + x_prev), x_prev(0) = 0.  Gains are the
-"walking" gains of app/robots/iCubGazeboV2_5/zmpControllerParams.ini:7-8 (kZMP 3.0, kCoM 9.0,
-no gain scheduling).  The robot itself is synthetic (there is no simulator in scope): the
-measured DCM follows the LIPM  xi+ = a xi + b u0 + w  with a bounded uniform disturbance w
+"walking" gains of app/robots/iCubGazeboV2_5/zmpControllerParams.ini:7-8 (kZMP 3.0, kCoM 9.0) unless a schedule is given.  The synthetic
+plant (there is no simulator in scope): the measured DCM follows the LIPM  xi+ = a xi + b u0 + w  with a bounded uniform disturbance w
 drawn from the same counter-based mixer as the workloads, the measured CoM follows
 c+ = c + dT (-omega (c - xi)), the measured ZMP is the previous command, measured joint
-positions equal the desired ones, Jacobians are constant per instance.
+positions equal the desired ones; without kin_model the Jacobians are constant per instance.
 """
 from __future__ import annotations
 
@@ -36,6 +57,8 @@ import numpy as np
 from . import qp_spec as qs
 from . import kin_spec as ks
 from . import hull_spec as hs
+from . import sensor_spec as sn
+from . import zmp_gains_spec as zg
 
 _M1 = np.uint64(0x9E3779B97F4A7C15)
 _M2 = np.uint64(0xBF58476D1CE4E5B9)
@@ -83,17 +106,45 @@ def contact_code(t: int, phase0: np.ndarray, p: TickParams) -> np.ndarray:
     return np.where(s < p.ds_ticks, 2, side).astype(np.int32)
 
 
+def reactive_law(dcm_des, dcm_des_dot, dcm_meas, omega, k_dcm):
+    """WalkingDCMReactiveController.cpp:75-78, elementwise."""
+    return dcm_des - dcm_des_dot / omega - k_dcm * (dcm_des - dcm_meas)
+
+
+def neck_orientation(Rl, Rr, add_rot):
+    """RotZ(meanYaw) @ add_rot for desired foot rotations Rl, Rr (row-major 9 or 3 x 3); WalkingModule.cpp:697-707."""
+    Rl = np.asarray(Rl, float).reshape(3, 3); Rr = np.asarray(Rr, float).reshape(3, 3)
+    yl, yr = np.arctan2(Rl[1, 0], Rl[0, 0]), np.arctan2(Rr[1, 0], Rr[0, 0])       # the asRPY yaw of run_ticks' rpy helper
+    y = np.arctan2(np.sin(yl) + np.sin(yr), np.cos(yl) + np.cos(yr))
+    c, s = np.cos(y), np.sin(y)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]) @ np.asarray(add_rot, float).reshape(3, 3)
+
+
+@dataclasses.dataclass
+class Stage:
+    """What one robot's tick takes from the desired trajectories, whatever supplies them."""
+    left: np.ndarray            # desired sole poses (p 3 | R 9 row-major): state 24..35, 36..47
+    right: np.ndarray
+    twist_left: object          # desired sole twists (6, or 0.0): state 75..80, 81..86
+    twist_right: object
+    code: int                   # contact pair: 0 = left only, 1 = right only, 2 = both
+    side: int                   # the fixed-frame foot that anchors the base: 0 = left
+    height: float               # desired CoM height and its velocity: state 71, 74
+    height_vel: float
+    neck: object                # desired neck rotation (9), or None: leave state0's
+
+
 def run_ticks(p: TickParams, data: dict, n_ticks: int, ik_params: qs.IKParams, ik_form: str = "qpoases",
               kin_model: dict | None = None, foot_rect=None, splices: dict | None = None, logger_ticks: int = 0,
-              mpc_params: "qs.MPCParams | None" = None, external: dict | None = None):
-    """data: the arrays of walking-controllers_amd/synth.py::synth_tick_batch (or synth_walk_batch with
-    `kin_model`).  Returns the per-tick logs u0[T][B][2], dq[T][B][23] and the final states.
+              mpc_params: "qs.MPCParams | None" = None, external: dict | None = None, *, dcm_controller: str = "mpc", k_dcm: float | None = None,
+              dcm_vel=None, zmp_gain_schedule: dict | None = None, stages: dict | None = None, neck_additional_rotation=None, sensors=None):
+    """data: the arrays of walking-controllers_amd/synth.py::synth_tick_batch (or synth_walk_batch / synth_planned_walk_batch with
+    `kin_model`).  Returns the per-tick logs u0[T][B][2], dq[T][B][23], the final states and the fail counters.  `p` is never written to.
 
     kin_model (a table as in kin_spec): per-tick kinematics, the way the reference does it - forward kinematics at the
     integrated joint positions (WM/src/WalkingModule.cpp:715) and four fresh Jacobians / actual poses for the IK
-    (:396-410), with the floating base anchored at the stance foot of the current step: world_T_base = desired sole
-    pose x (sole pose in the base frame)^-1 (WalkingFK::evaluateWorldToBaseTransformation,
-    WM/src/WalkingForwardKinematics.cpp:160-256); the support-polygon rows are rebuilt from the DESIRED foot poses
+    (:396-410), with the floating base anchored at the fixed-frame foot of the tick: world_T_base = desired sole
+    pose x (sole pose in the base frame)^-1 (sensor_spec.anchored_base); the support-polygon rows are rebuilt from the DESIRED foot poses
     whenever the contact pair changes (...PredictiveController.cpp:364-435).
 
     splices {tick: (from_tick, tail[B][n][2])}: trajectory merges (WM/src/WalkingModule.cpp:500-535, 1263-1308) - before tick
@@ -109,8 +160,37 @@ def run_ticks(p: TickParams, data: dict, n_ticks: int, ik_params: qs.IKParams, i
     plant's state at the START of each tick (`dcm_log`, `com_log`, `zmp_log`, `q_log`): feeding an internal run's own logs back as
     `external` must reproduce it.
 
+    sensors(t, q_des, dq_prev, u_prev) -> (q_meas, dq_meas, wrench_left, wrench_right): a robot in the loop (needs kin_model; excludes
+    `external`) - tick t's measured state is what the sensor form evaluates from these readings (sensor_spec.evaluate_each with the
+    stage's fixed-frame sole), which may depend on what the run did up to tick t - 1.  The run then also returns the readings
+    (`readings`, a list of the four arrays per tick) and what was evaluated (`measured_log` [T][B][6]): fed back as fixed `external`
+    arrays they reproduce the run.  A rejected reading is an assertion error.
+
     logger_ticks > 0: also returns `logger` [logger_ticks][B][53], the row WalkingModule hands its logger per tick
-    (WM/src/WalkingModule.cpp:800-810, columns :1231-1250; include/wcqp.h: wcqp_tick_params.logger_ticks says which is which)."""
+    (WM/src/WalkingModule.cpp:800-810, columns :1231-1250; include/wcqp.h: wcqp_tick_params.logger_ticks says which is which).
+
+    dcm_controller "mpc" | "reactive" (with k_dcm): the reactive law at (i, t) in place of the MPC solve; it never fails.
+    dcm_vel [B][stages][2]: the DCM velocity the reactive law and the stance flag read; None: the forward difference of the reference
+    window, after any splice of that tick.  Logger columns 4-5 hold the velocity the reactive law used.
+
+    zmp_gain_schedule dict(zmp_smoothing_time, k_com_stance, k_zmp_stance): one zmp_gains_spec.GainSchedule per robot, advanced once per
+    tick BEFORE the controller's solve (a QPOracleError of the MPC still follows a setPhase); the ZMP-CoM law uses that tick's gains.
+    `zmp_gains` [T][B][2] returns them (the fixed gains of `p` without a schedule).
+
+    stages: the desired stage of every tick from per-tick arrays instead of the synthetic gait (needs kin_model and
+    neck_additional_rotation; no logger rows, as on the device) -
+      left_pose, right_pose [T][B][12]   left_twist, right_twist [T][B][6]   contact [T][B] uint8
+      com_height, com_height_vel [T][B] or absent (state0[68], 0)
+    stage-major: what a caller hands over tick by tick.  A planned upload [B][T][..] is the same data with the axes swapped, and two
+    walks' stages concatenated along the first axis are a replanned walk."""
+    reactive = dcm_controller == "reactive"
+    use_kin = kin_model is not None
+    if dcm_controller not in ("mpc", "reactive") or (reactive and k_dcm is None):
+        raise ValueError("dcm_controller is 'mpc' or 'reactive', the latter with k_dcm")
+    if stages is not None and (not use_kin or neck_additional_rotation is None or logger_ticks > 0):
+        raise ValueError("stages need kin_model and neck_additional_rotation, and exclude logger rows")
+    if sensors is not None and (not use_kin or external is not None):
+        raise ValueError("sensors need kin_model and exclude external")
     if splices:
         data = dict(data)
         data["ref_traj"] = np.array(data["ref_traj"], copy=True)
@@ -130,23 +210,60 @@ def run_ticks(p: TickParams, data: dict, n_ticks: int, ik_params: qs.IKParams, i
     u0_log = np.zeros((n_ticks, B, 2)); dq_log = np.zeros((n_ticks, B, 23))
     mpc_fail = np.zeros(B, np.int64); ik_fail = np.zeros(B, np.int64); feedback_fail = np.zeros(B, np.int64)
     q_ik_prev = None
-    use_kin = kin_model is not None
     state_now = data["state0"].copy()
     hull_cur = [None] * B; hull_code = -np.ones(B, np.int64)
     J_now = [None] * B
     act_lo = np.zeros((n_ticks, B), np.uint32); act_up = np.zeros((n_ticks, B), np.uint32)     # every tick's active bounds, bit i = joint i
     dcm_log = np.zeros((n_ticks, B, 2)); com_log = np.zeros((n_ticks, B, 2)); zmp_log = np.zeros((n_ticks, B, 2)); q_log = np.zeros((n_ticks, B, 23))
     logger = np.zeros((logger_ticks, B, 53))
+    readings, measured_log = [], np.zeros((n_ticks, B, 6))
+    schedule = [zg.GainSchedule(p.dT, float(p.k_com), float(p.k_zmp), **zmp_gain_schedule) for _ in range(B)] if zmp_gain_schedule else None
+    gains = np.tile([float(p.k_com), float(p.k_zmp)], (B, 1))          # this tick's (kCoM, kZMP) of every robot
+    zmp_gains = np.zeros((n_ticks, B, 2))
 
     def rpy(R9):
         R = np.asarray(R9).reshape(3, 3)         # iDynTree::Rotation::asRPY (upstream)
         return np.array([np.arctan2(R[2, 1], R[2, 2]), np.arcsin(np.clip(-R[2, 0], -1.0, 1.0)), np.arctan2(R[1, 0], R[0, 0])])
+
+    def synthetic_stage(t, i, k):
+        """the synthetic gait: the feet stay where state0 has them, the stance foot of the step anchors the base"""
+        cyc = (t + int(data["phase0"][i])) % (2 * p.step_ticks)
+        tw = data["swing_twist"][i]
+        if use_kin:
+            # the swing foot's velocity profile over its single-support phase: zero net displacement (tick_device.h)
+            sidx = cyc % p.step_ticks
+            ss = p.step_ticks - p.ds_ticks
+            x = (sidx - p.ds_ticks) / float(ss) if sidx >= p.ds_ticks else 0.0
+            tw = tw * (10.392304845413264 * x * (1.0 - x) * (1.0 - 2.0 * x) if sidx >= p.ds_ticks else 0.0)
+        s0 = data["state0"][i]
+        # a foot in contact has zero twist; with kinematics the desired height is the initial one
+        return Stage(left=s0[24:36], right=s0[36:48], twist_left=0.0 if k in (0, 2) else tw, twist_right=0.0 if k in (1, 2) else tw, code=k,
+                     side=int(cyc // p.step_ticks), height=s0[68] if use_kin else p.com_height, height_vel=0.0, neck=None)
+
+    def given_stage(t, i):
+        """stage t of `stages`: contact bits 0-1 the feet in contact, bit 2 the left sole as the fixed frame; the neck follows the feet"""
+        flags = int(stages["contact"][t, i])
+        left, right = stages["left_pose"][t, i], stages["right_pose"][t, i]
+        h, hv = stages.get("com_height"), stages.get("com_height_vel")
+        return Stage(left=left, right=right, twist_left=stages["left_twist"][t, i], twist_right=stages["right_twist"][t, i], code=(flags & 3) - 1,
+                     side=0 if flags & 4 else 1, height=h[t, i] if h is not None else data["state0"][i][68],
+                     height_vel=hv[t, i] if hv is not None else 0.0, neck=neck_orientation(left[3:12], right[3:12], neck_additional_rotation).reshape(9))
+
     for t in range(n_ticks):
         if splices and t in splices:
             frm, tail = splices[t]
             assert frm >= t
             data["ref_traj"][:, frm:frm + tail.shape[1]] = tail
-        code = contact_code(t, data["phase0"], p)
+        ref = data["ref_traj"]
+
+        # ---- the stage of tick t: the only block that knows where the desired trajectories come from
+        if stages is not None:
+            stage = [given_stage(t, i) for i in range(B)]
+        else:
+            code = contact_code(t, data["phase0"], p)
+            stage = [synthetic_stage(t, i, int(code[i])) for i in range(B)]
+
+        # ---- the measured state tick t reads: the synthetic plant's (advanced at the end of tick t - 1), external arrays, or sensors
         if external is not None:
             # a robot whose feedback of tick t holds a NaN or an Inf (any of its dcm, com, zmp or q entries) is REJECTED, by the rule of the
             # sensor form (include/wcqp.h, wcqp_tick_set_feedback_*): it keeps the measured state tick t - 1 used (tick 0: the uploaded
@@ -162,71 +279,76 @@ def run_ticks(p: TickParams, data: dict, n_ticks: int, ik_params: qs.IKParams, i
             q_ik_prev = q_ik
             feedback_fail += bad
             ik_fail[bad & (ik_fail == 0)] = 1
+        elif sensors is not None:
+            r = [np.array(x, float) for x in sensors(t, q_des.copy(), dq_prev.copy(), u_prev.copy())]
+            m, rej = sn.evaluate_each(kin_model, [st.right if st.side else st.left for st in stage], [st.side for st in stage], *r, omega)
+            assert not rej.any(), ("a rejected reading", t)
+            dcm, com, zmp_meas, q_ik = m[:, 0:2].copy(), m[:, 2:4].copy(), m[:, 4:6].copy(), r[0]
+            readings.append(r); measured_log[t] = m
         else:
             q_ik = q_des
         dcm_log[t] = dcm; com_log[t] = com; zmp_log[t] = zmp_meas; q_log[t] = q_des
+
+        # ---- kinematics at the desired joints, the base anchored at the stage's fixed-frame sole; hull rows on a change of contact pair
         if use_kin:
-            ident = np.concatenate([np.zeros(3), np.eye(3).reshape(9)])
-            for i in range(B):
-                side = int(((t + int(data["phase0"][i])) % (2 * p.step_ticks)) // p.step_ticks)   # 0: left is the stance foot
-                pa, Ra = ks.forward(kin_model, ident, q_des[i])["frames"][side]
-                sd = state_now[i][36:48] if side else state_now[i][24:36]
-                Rb = sd[3:12].reshape(3, 3) @ Ra.T
-                base = np.concatenate([sd[0:3] - Rb @ pa, Rb.reshape(9)])
+            for i, st in enumerate(stage):
+                s = state_now[i]
+                s[24:36] = st.left; s[36:48] = st.right
+                if st.neck is not None:
+                    s[57:66] = st.neck
+                base = sn.anchored_base(kin_model, q_des[i], s[36:48] if st.side else s[24:36], st.side)
                 K = ks.jacobians(kin_model, base, q_des[i])
                 J_now[i] = K
-                s = state_now[i]
                 s[0:3] = K["p_left"]; s[3:12] = K["R_left"].reshape(9); s[12:15] = K["p_right"]; s[15:24] = K["R_right"].reshape(9)
                 s[48:57] = K["R_neck"].reshape(9); s[66:69] = K["com"]
-                if int(code[i]) != hull_code[i]:
-                    k = int(code[i])
-                    hull_cur[i] = hs.hull_from_feet(foot_rect, s[24:36], s[36:48], {0: 1, 1: 2, 2: 3}[k])
-                    hull_code[i] = k
-        r_t = data["ref_traj"][:, t, :]
-        # LIPM reference (StableDCMModel.cpp:63-90)
+                if st.code != hull_code[i]:
+                    hull_cur[i] = hs.hull_from_feet(foot_rect, s[24:36], s[36:48], {0: 1, 1: 2, 2: 3}[st.code])
+                    hull_code[i] = st.code
+
+        # ---- LIPM reference (StableDCMModel.cpp:63-90)
+        r_t = ref[:, t, :]
         v_ref = -omega * (c_ref - r_t)
         c_ref = c_ref + 0.5 * p.dT * (v_ref + v_ref_prev); v_ref_prev = v_ref
+
+        # ---- the DCM command: setPhase (WalkingModule.cpp:657-662), then the MPC (:604-636) or the reactive law (:638-656)
+        vel_t = np.asarray(dcm_vel)[:, t] if dcm_vel is not None else (ref[:, t + 1, :] - r_t) / p.dT
         u0 = np.zeros((B, 2))
-        for i in range(B):
-            k = int(code[i])
+        for i, st in enumerate(stage):
+            if schedule:
+                gains[i] = schedule[i].set_phase(bool(zg.is_stance(vel_t[i])))
+            if reactive:
+                u0[i] = reactive_law(ref[i, t], vel_t[i], dcm[i], omega, k_dcm)
+                continue
             if use_kin:
                 hA, hb, nc = hull_cur[i]
             else:
-                hA, hb, nc = data["hull_tab_A"][i, k], data["hull_tab_b"][i, k], int(data["hull_tab_nc"][i, k])
+                hA, hb, nc = data["hull_tab_A"][i, st.code], data["hull_tab_b"][i, st.code], int(data["hull_tab_nc"][i, st.code])
             try:
-                r = qs.mpc_exact(c, dcm[i], data["ref_traj"][i, t:t + N + 1], u_prev[i], hA, hb, nc)
-                u0[i] = r["u0"]
+                u0[i] = qs.mpc_exact(c, dcm[i], ref[i, t:t + N + 1], u_prev[i], hA, hb, nc)["u0"]
             except qs.QPOracleError:
                 u0[i] = u_prev[i]; mpc_fail[i] += 1
-        # ZMP-CoM law (WalkingZMPController.cpp:146-173)
-        v_star = p.k_com * (c_ref - com) - p.k_zmp * (u0 - zmp_meas) + v_ref
+        zmp_gains[t] = gains
+
+        # ---- ZMP-CoM law (WalkingZMPController.cpp:146-173)
+        v_star = gains[:, 0:1] * (c_ref - com) - gains[:, 1:2] * (u0 - zmp_meas) + v_ref
         p_star = p_star + 0.5 * p.dT * (v_star + v_star_prev); v_star_prev = v_star
-        dq = np.zeros((B, 23))
         if t < logger_ticks:
             logger[t, :, 0:2] = dcm; logger[t, :, 2:4] = r_t
-            logger[t, :, 4:6] = (data["ref_traj"][:, t + 1, :] - r_t) / p.dT
+            logger[t, :, 4:6] = vel_t if reactive else (ref[:, t + 1, :] - r_t) / p.dT
             logger[t, :, 6:8] = zmp_meas; logger[t, :, 8:10] = u0
             logger[t, :, 13:15] = p_star; logger[t, :, 15:17] = v_star
-        for i in range(B):
+
+        # ---- IK (WalkingModule.cpp:686-695, 367-425)
+        dq = np.zeros((B, 23))
+        for i, st in enumerate(stage):
             s = state_now[i].copy()
-            if use_kin:
-                # the IK's "actual" CoM is the forward kinematics' at the desired joint state (WalkingModule.cpp:715,
-                # 373-376), not the plant's; the desired height is the initial one
-                s[69:71] = p_star[i]; s[71] = data["state0"][i][68]
-            else:
+            if not use_kin:
                 s[66:68] = com[i]; s[68] = p.com_height
-                s[69:71] = p_star[i]; s[71] = p.com_height
-            s[72:74] = v_star[i]; s[74] = 0.0
-            k = int(code[i])
-            tw = data["swing_twist"][i]
-            if use_kin:
-                # the swing foot's velocity profile over its single-support phase: zero net displacement (tick_device.h)
-                sidx = ((t + int(data["phase0"][i])) % (2 * p.step_ticks)) % p.step_ticks
-                ss = p.step_ticks - p.ds_ticks
-                x = (sidx - p.ds_ticks) / float(ss) if sidx >= p.ds_ticks else 0.0
-                tw = tw * (10.392304845413264 * x * (1.0 - x) * (1.0 - 2.0 * x) if sidx >= p.ds_ticks else 0.0)
-            s[75:81] = 0.0 if k in (0, 2) else tw      # left foot in contact -> zero twist
-            s[81:87] = 0.0 if k in (1, 2) else tw
+            # (with kinematics the IK's "actual" CoM is the forward kinematics' at the desired joint state, WalkingModule.cpp:715,
+            # 373-376; SURVEY Appendix B-18, not the plant's)
+            s[69:71] = p_star[i]; s[71] = st.height
+            s[72:74] = v_star[i]; s[74] = st.height_vel
+            s[75:81] = st.twist_left; s[81:87] = st.twist_right
             Jsrc = {n: J_now[i][n][None] for n in ("J_left", "J_right", "J_neck", "J_com")} if use_kin else \
                    {n: data[n][i:i + 1] for n in ("J_left", "J_right", "J_neck", "J_com")}
             one = dict(q=q_ik[i:i + 1], state=s[None, :], **Jsrc)
@@ -248,13 +370,16 @@ def run_ticks(p: TickParams, data: dict, n_ticks: int, ik_params: qs.IKParams, i
                     logger[t, i, 41:47] = res_ik["foot_err_left"]; logger[t, i, 47:53] = res_ik["foot_err_right"]
             except qs.QPOracleError:
                 ik_fail[i] += 1
-        q_des = q_des + 0.5 * p.dT * (dq + dq_prev); dq_prev = dq          # WalkingModule.cpp:741-744
-        # synthetic plant
+
+        # ---- joint integration (WalkingModule.cpp:741-744)
+        q_des = q_des + 0.5 * p.dT * (dq + dq_prev); dq_prev = dq
+
+        # ---- the synthetic plant
         w = np.stack([disturbance(p.seed, inst, t, 0), disturbance(p.seed, inst, t, 1)], 1)
         com = com + p.dT * (-omega * (com - dcm))
         dcm = c.a * dcm + c.b * u0 + p.noise * w
         zmp_meas = u0.copy(); u_prev = u0.copy()
         u0_log[t] = u0; dq_log[t] = dq
     return dict(u0_log=u0_log, dq_log=dq_log, q_des=q_des, dcm=dcm, com=com, mpc_fail=mpc_fail, ik_fail=ik_fail, feedback_fail=feedback_fail, logger=logger,
-                dcm_log=dcm_log, com_log=com_log, zmp_log=zmp_log, q_log=q_log,
+                dcm_log=dcm_log, com_log=com_log, zmp_log=zmp_log, q_log=q_log, zmp_gains=zmp_gains, readings=readings, measured_log=measured_log,
                 active_lower=act_lo[-1], active_upper=act_up[-1], active_lower_log=act_lo, active_upper_log=act_up)

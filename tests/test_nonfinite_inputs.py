@@ -251,11 +251,9 @@ def test_tick_external_feedback_with_a_non_finite_value_stops_that_robot_only(wc
     before, feedback_fail counts the rejection, ik_fail counts it and every tick the robot runs stopped (the counter the stop rule of the
     IK uses, test_a_robot_whose_ik_fails_is_stopped_like_the_oracle: a stopped robot is a stopped robot, whatever stopped it), dq = 0 from
     tick k on and nothing non-finite is in its state.  Every other robot is bit-identical to the clean run over all ticks, and the whole
-    run matches the restatement (oracle/tick_spec.py; the reactive law through tests/helpers/reactive_tick.py) at the tolerances of the
+    run matches the restatement (oracle/tick_spec.py, with either DCM controller) at the tolerances of the
     existing external-feedback tests (u0, q_des 1e-9; dq 1e-8)."""
     from oracle import tick_spec as ts
-    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
-    import reactive_tick as rt
     B, T, k_nan, k_inf, r_nan, r_inf = 10, 24, 5, 7, 6, 1
     p = ts.TickParams()
     if kin_mode:
@@ -272,8 +270,7 @@ def test_tick_external_feedback_with_a_non_finite_value_stops_that_robot_only(wc
         ipar, okw = qs.IKParams(v_max=0.45 * np.ones(23)), {}
         mk_ik = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=0.45)
     ckw = dict(dcm_controller="reactive", k_dcm=K_DCM) if controller == "reactive" else {}
-    spec = (lambda **kw: rt.run_ticks_reactive(p, d, T, ipar, K_DCM, **okw, **kw)) if controller == "reactive" else \
-           (lambda **kw: ts.run_ticks(p, d, T, ipar, **okw, **kw))
+    spec = lambda **kw: ts.run_ticks(p, d, T, ipar, dcm_controller=controller, k_dcm=K_DCM, **okw, **kw)
     internal = spec()
     rng = np.random.default_rng(4)
     ext = dict(dcm=internal["dcm_log"] + 1e-3 * rng.normal(size=(T, B, 2)), com=internal["com_log"] + 5e-4 * rng.normal(size=(T, B, 2)),

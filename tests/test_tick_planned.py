@@ -1,6 +1,6 @@
 """Planned-trajectory mode of the closed-loop tick (wcqp_tick_params.planned_trajectories): the desired feet, twists, contact
-flags, fixed frame and CoM height of every tick come from the planner's stage t.  CPU: the restatement (tests/helpers/planned_tick.py)
-against oracle/tick_spec.py, the ABI, the binding's and the library's refusals, the generator.  GPU: the device against the restatement."""
+flags, fixed frame and CoM height of every tick come from the planner's stage t.  CPU: the restatement's given-stages branch
+(oracle/tick_spec.py::run_ticks(stages=...)) against its synthetic gait, the ABI, the binding's and the library's refusals, the generator.  GPU: the device against the restatement."""
 import ctypes as C
 import os
 import subprocess
@@ -10,7 +10,7 @@ import pytest
 
 import robots
 from helpers import planned_tick as pt
-from helpers import reactive_tick as rt
+from helpers import streamed_tick as stt
 from helpers import zmp_gains as zg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,7 +48,7 @@ def _ik_solver(wca, robot):
 # ---------------------------------------------------------------------------------------------------------------- CPU
 
 def test_restatement_reproduces_the_synthetic_gait(wca, qs):
-    """The synthetic gait written out as planned trajectories: the restatement reproduces tick_spec.run_ticks(kin_model=...) to 1e-12."""
+    """The synthetic gait written out as stages: run_ticks(stages=...) reproduces its own synthetic branch to 1e-12."""
     from oracle import tick_spec as ts
     B, T = 2, 130
     p = ts.TickParams()
@@ -58,7 +58,7 @@ def test_restatement_reproduces_the_synthetic_gait(wca, qs):
     codes = np.array([ts.contact_code(t, d["phase0"], p) for t in range(T)])
     assert all(len(set(codes[:, i])) >= 2 for i in range(B)), "the run passes through a change of contact pair"
     ref = ts.run_ticks(p, d2, T, ipar, kin_model=model, foot_rect=wca.synth.FOOT_RECT)
-    out = pt.run_ticks_planned(p, d2, plan, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT)
+    out = ts.run_ticks(p, d2, T, ipar, kin_model=model, foot_rect=wca.synth.FOOT_RECT, stages=stt.stages_of(plan, T), neck_additional_rotation=ADD_ROT)
     for k in KEYS:
         assert np.abs(out[k] - ref[k]).max() <= 1e-12, k
     assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
@@ -183,23 +183,10 @@ def _ref(qs, wca, robot, controller, gs, d, plan, T, horizon=50):
     from oracle import tick_spec as ts
     R = robots.ROBOTS[robot]
     p = ts.TickParams(horizon=horizon, k_com=R["k_com"], k_zmp=R["k_zmp"])
-    ipar = _ik_params(wca, qs, robot)
-    B = d["q0"].shape[0]
-    vel = d.get("dcm_vel_traj")
-    args = (p, d, plan, T, ipar, wca.synth.icub_like_model(), wca.synth.FOOT_RECT, R["additional_rotation"])
-    import contextlib
-    with contextlib.ExitStack() as es:
-        if controller == "reactive":
-            es.enter_context(rt.reactive_solve(p, K_DCM[robot], B, vel))
-        st = es.enter_context(zg.scheduled_gains(p, B, zg.ZMP_SCHEDULE[robot], vel)) if gs else None
-        out = pt.run_ticks_planned(*args)
-    if gs:
-        g = np.zeros((T, B, 2))
-        for t, i, kc, kz in st["gains"]:
-            g[t, i] = (kc, kz)
-        out["zmp_gains"] = g[-1]
-    else:
-        out["zmp_gains"] = np.tile([R["k_com"], R["k_zmp"]], (B, 1))
+    out = ts.run_ticks(p, d, T, _ik_params(wca, qs, robot), kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT,
+                       stages=stt.stages_of(plan, T), neck_additional_rotation=R["additional_rotation"], dcm_controller=controller,
+                       k_dcm=K_DCM[robot], dcm_vel=d.get("dcm_vel_traj"), zmp_gain_schedule=zg.ZMP_SCHEDULE[robot] if gs else None)
+    out["zmp_gains"] = out["zmp_gains"][-1]
     return out
 
 

@@ -1,11 +1,11 @@
 """
 The closed-loop tick with the REACTIVE DCM controller (wcqp_tick_params.dcm_controller = REACTIVE): the reference's default
 configuration (WM/src/WalkingModule.cpp:124 `use_mpc` defaults to false; :188-211, :638-656), and that of two of the three robots it ships.
-Checked against tests/helpers/reactive_tick.py: oracle/tick_spec.run_ticks with its MPC solve replaced by the closed-form law of
-WM/src/WalkingDCMReactiveController.cpp:63-82.
+Checked against oracle/tick_spec.run_ticks(dcm_controller="reactive", k_dcm=...): the closed-form law of
+WM/src/WalkingDCMReactiveController.cpp:63-82 in place of the MPC solve.
 """
 import ctypes as C
-import importlib.util
+import dataclasses
 import os
 import subprocess
 
@@ -14,10 +14,9 @@ import pytest
 
 import robots
 
+from helpers import zmp_gains as zgh
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_spec = importlib.util.spec_from_file_location("reactive_tick", os.path.join(ROOT, "tests", "helpers", "reactive_tick.py"))
-rt = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(rt)
 
 # kDCM of DCM_REACTIVE_CONTROLLER, app/robots/<robot>/dcmReactiveControllerParams.ini:1
 K_DCM = {
@@ -53,9 +52,9 @@ def _walk_scenario(wca, B, T, horizon=50):
 # ---------------------------------------------------------------------------------------------------------------- CPU
 
 def test_restatement_law_and_patch_hygiene():
-    """The helper's law is WalkingDCMReactiveController.cpp:75-78 term by term; the patch of tick_spec.qs.mpc_exact is undone on exit,
-    an exception included."""
-    from oracle import tick_spec as ts
+    """The restated law is WalkingDCMReactiveController.cpp:75-78 term by term; a run with the reactive controller and a gain schedule
+    writes nothing to `p` and leaves oracle.qp_spec.mpc_exact the object it was, a run that raises included."""
+    from oracle import qp_spec, tick_spec as ts
     rng = np.random.default_rng(7)
     p = ts.TickParams()
     omega = np.sqrt(p.gravity / p.com_height)
@@ -66,18 +65,22 @@ def test_restatement_law_and_patch_hygiene():
         for ax in range(2):
             # zmp = dcm_des - dcm_des_dot / omega - kDCM * (dcm_des - dcm_measured)
             expect[i, ax] = r[i, ax] - rd[i, ax] / omega - k * (r[i, ax] - x[i, ax])
-    assert np.abs(rt.reactive_law(r, rd, x, omega, k) - expect).max() <= 1e-15
-    orig = ts.qs.mpc_exact
-    with rt.reactive_solve(p, k, 1) as st:
-        assert ts.qs.mpc_exact is not orig
-        w = np.stack([r[0], r[1]])
-        u = ts.qs.mpc_exact(None, x[0], w, None, None, None, 0)["u0"]
-        assert np.abs(u - rt.reactive_law(r[0], (r[1] - r[0]) / p.dT, x[0], omega, k)).max() <= 1e-15 and st["calls"] == 1
-    assert ts.qs.mpc_exact is orig
-    with pytest.raises(RuntimeError):
-        with rt.reactive_solve(p, k, 1):
-            raise RuntimeError("inside")
-    assert ts.qs.mpc_exact is orig
+    assert np.abs(ts.reactive_law(r, rd, x, omega, k) - expect).max() <= 1e-15
+    _no_side_effects(ts, qp_spec, p)
+
+
+def _no_side_effects(ts, qp_spec, p):
+    """run_ticks(reactive + gain schedule): `p` field for field what it was, qp_spec.mpc_exact the same object, also when the run raises"""
+    import walking_controllers_amd as wca
+    d = wca.synth.synth_tick_batch(2, 4)
+    ipar = qp_spec.IKParams(v_max=VMAX * np.ones(23))
+    before, orig = dataclasses.replace(p), qp_spec.mpc_exact
+    kw = dict(dcm_controller="reactive", k_dcm=1.1, zmp_gain_schedule=zgh.ZMP_SCHEDULE["iCubGazeboV2_5"])
+    out = ts.run_ticks(p, d, 4, ipar, **kw)
+    assert out["zmp_gains"].shape == (4, 2, 2) and dataclasses.asdict(p) == dataclasses.asdict(before) and qp_spec.mpc_exact is orig
+    with pytest.raises(IndexError):
+        ts.run_ticks(p, d, 4, ipar, dcm_vel=np.zeros((2, 2, 2)), **kw)          # the velocities run out on tick 2: the run raises half way
+    assert dataclasses.asdict(p) == dataclasses.asdict(before) and qp_spec.mpc_exact is orig and ts.qs.mpc_exact is orig
 
 
 def test_new_struct_fields_match_the_ctypes_mirror(wca, tmp_path):
@@ -129,7 +132,7 @@ def test_reactive_tick_with_constant_jacobians(wca, qs, tick_batch, robot):
     B, T = 24, 150
     p = ts.TickParams(k_com=R["k_com"], k_zmp=R["k_zmp"])
     d = tick_batch
-    ref = rt.run_ticks_reactive(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23)), K_DCM[robot])
+    ref = ts.run_ticks(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23)), dcm_controller="reactive", k_dcm=K_DCM[robot])
     assert ref["ik_fail"].sum() == 0
     for alg in (0, 4, 3):
         runs = []
@@ -159,7 +162,7 @@ def test_reactive_tick_with_fused_kinematics_at_any_horizon(wca, qs, horizon):
     kin, d = _walk_scenario(wca, B, T, horizon)
     vmax = wca.synth.WALK_VMAX.copy()
     mk = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=vmax, joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG))
-    ref = rt.run_ticks_reactive(p, d, T, qs.IKParams(v_max=vmax.copy(), joint_reg_deg=wca.synth.WALK_POSTURE_DEG.copy()), K_DCM["iCubGazeboV2_5"],
+    ref = ts.run_ticks(p, d, T, qs.IKParams(v_max=vmax.copy(), joint_reg_deg=wca.synth.WALK_POSTURE_DEG.copy()), dcm_controller="reactive", k_dcm=K_DCM["iCubGazeboV2_5"],
                                 kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT)
     assert ref["ik_fail"].sum() == 0 and np.abs(ref["q_des"] - d["q0"]).max() > 0.05
     pipe = wca.TickPipeline(B, T, wca.MpcSolver(horizon=horizon), mk(), log_ticks=T, kin=kin, dcm_controller="reactive", k_dcm=K_DCM["iCubGazeboV2_5"])
@@ -195,10 +198,10 @@ def test_explicit_dcm_velocity(wca, qs, tick_batch):
         pipe.upload(d, dcm_vel_traj=v)
         pipe.run(T)
         return pipe.download()
-    ref = rt.run_ticks_reactive(p, d, T, ipar, k, dcm_vel=vel)
+    ref = ts.run_ticks(p, d, T, ipar, dcm_controller="reactive", k_dcm=k, dcm_vel=vel)
     out = run(vel)
     _close(out, ref)
-    assert np.abs(ref["u0_log"] - rt.run_ticks_reactive(p, d, T, ipar, k)["u0_log"]).max() > 1e-5
+    assert np.abs(ref["u0_log"] - ts.run_ticks(p, d, T, ipar, dcm_controller="reactive", k_dcm=k)["u0_log"]).max() > 1e-5
     _same(run(fd), run(None))
     _same(run(vel, 1), out)
 
@@ -248,7 +251,7 @@ def test_reactive_external_plant(wca, qs, kin_mode):
         kin, d = None, wca.synth.synth_tick_batch(B, T)
         ipar, okw = qs.IKParams(v_max=VMAX * np.ones(23)), {}
         mk_ik = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=VMAX)
-    internal = rt.run_ticks_reactive(p, d, T, ipar, k, **okw)
+    internal = ts.run_ticks(p, d, T, ipar, dcm_controller="reactive", k_dcm=k, **okw)
 
     def run_external(ext):
         pipe = wca.TickPipeline(B, T, wca.MpcSolver(), mk_ik(), log_ticks=T, kin=kin, external_feedback=True, dcm_controller="reactive", k_dcm=k)
@@ -267,7 +270,7 @@ def test_reactive_external_plant(wca, qs, kin_mode):
     rng = np.random.default_rng(4)
     ext = dict(dcm=internal["dcm_log"] + 1e-3 * rng.normal(size=(T, B, 2)), com=internal["com_log"] + 5e-4 * rng.normal(size=(T, B, 2)),
                zmp=internal["zmp_log"] + 2e-3 * rng.normal(size=(T, B, 2)), q=internal["q_log"] + 0.01 * rng.normal(size=(T, B, 23)))
-    ref = rt.run_ticks_reactive(p, d, T, ipar, k, external=ext, **okw)
+    ref = ts.run_ticks(p, d, T, ipar, dcm_controller="reactive", k_dcm=k, external=ext, **okw)
     out = run_external(ext)
     for key in ("u0_log", "dq_log", "q_des"):
         assert np.abs(out[key] - ref[key]).max() <= 1e-9, key
@@ -295,7 +298,7 @@ def test_reactive_logger_rows(wca, qs, kin_mode, explicit_vel):
         mk = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=VMAX)
         ipar, okw = qs.IKParams(v_max=VMAX * np.ones(23)), {}
     vel = np.sqrt(p.gravity / p.com_height) * (d["ref_traj"] - d["zmp_ref"]) if explicit_vel else None
-    ref = rt.run_ticks_reactive(p, d, T, ipar, k, dcm_vel=vel, logger_ticks=L, **okw)
+    ref = ts.run_ticks(p, d, T, ipar, dcm_controller="reactive", k_dcm=k, dcm_vel=vel, logger_ticks=L, **okw)
     outs = []
     for lt in (L, 0):
         pipe = wca.TickPipeline(B, T, wca.MpcSolver(), mk(), log_ticks=T, kin=kin, logger_ticks=lt, dcm_controller="reactive", k_dcm=k)
@@ -341,13 +344,13 @@ def test_reactive_refusals_and_hull_free_upload(wca, qs):
     pipe.run(T - 5)
     out = pipe.download()
     d2 = dict(d); d2["ref_traj"] = d["ref_traj"].copy(); d2["ref_traj"][:, 10:14] = tail
-    ref = rt.run_ticks_reactive(p, d2, T, qs.IKParams(v_max=VMAX * np.ones(23)), 1.2)
+    ref = ts.run_ticks(p, d2, T, qs.IKParams(v_max=VMAX * np.ones(23)), dcm_controller="reactive", k_dcm=1.2)
     _close(out, ref)
     # a reactive handle with constant Jacobians takes an upload without hull tables; an MPC handle does not
     bare = {k_: v for k_, v in d.items() if not k_.startswith("hull_tab")}
     pipe = mk(dcm_controller="reactive", k_dcm=1.2)
     pipe.upload(bare)
     pipe.run(T)
-    _close(pipe.download(), rt.run_ticks_reactive(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23)), 1.2))
+    _close(pipe.download(), ts.run_ticks(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23)), dcm_controller="reactive", k_dcm=1.2))
     with pytest.raises(KeyError):
         mk().upload(bare)

@@ -1,7 +1,7 @@
 """
 Sensor feedback of the tick pipeline (include/wcqp.h: wcqp_tick_set_sensor_feedback_*): joint encoders and the two feet's wrenches in,
 the measured CoM, DCM and ZMP the EXTERNAL tick reads evaluated on the device - updateFKSolver, evaluateCoM / evaluateDCM and evaluateZMP
-of WM/src/WalkingModule.cpp (:1147-1217, :826-878).  Checked against the numpy restatement tests/helpers/sensor_feedback.py (built on
+of WM/src/WalkingModule.cpp (:1147-1217, :826-878).  Checked against the numpy restatement oracle/sensor_spec.py (built on
 oracle/kin_spec.py) and, in closed loop, against oracle/tick_spec.run_ticks(external=...) fed the restated measurements.
 """
 import ctypes as C
@@ -11,10 +11,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import sensor_feedback as sf
-from helpers import reactive_tick as rt
+from helpers import sensor_feedback as sfh
 from helpers import zmp_gains as zg
 from oracle import kin_spec as ks
+from oracle import sensor_spec as sf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
@@ -71,7 +71,7 @@ def test_v_com_is_the_derivative_of_the_com_along_dq(wca):
     model, q, rng = _robot()
     dq = rng.normal(size=23)
     sole = np.concatenate([[0.02, 0.07, 0.0], _rot_z(0.1).reshape(9)])
-    r = sf.evaluate(model, q, dq, *(w[0] for w in sf.wrenches(rng, 1)), sole, 0, OMEGA)
+    r = sf.evaluate(model, q, dq, *(w[0] for w in sfh.wrenches(rng, 1)), sole, 0, OMEGA)
     h = 1e-6
     fd = (ks.forward(model, r["base"], q + h * dq)["com"] - ks.forward(model, r["base"], q - h * dq)["com"]) / (2 * h)
     assert np.abs(r["v_com"] - fd).max() <= 1e-8 * max(1.0, np.abs(fd).max())
@@ -170,7 +170,7 @@ class Sensors:
         self.B, self.phase0, self.p = B, np.asarray(phase0), ts.TickParams()
         self.qn = q_sigma * rng.normal(size=(T, B, 23))
         self.dqn = dq_sigma * rng.normal(size=(T, B, 23))
-        self.w = [sf.wrenches(rng, B) for _ in range(T)]
+        self.w = [sfh.wrenches(rng, B) for _ in range(T)]
         self.ts = ts
 
     def at(self, t, q_des, dq_prev):
@@ -224,7 +224,7 @@ def test_measured_state_matches_the_restatement_on_both_anchors(wca):
     for t in range(T):
         q = q_des + 0.05 * rng.normal(size=(B, 23))
         dq = 0.3 * rng.normal(size=(B, 23))
-        wl, wr = sf.wrenches(rng, B)
+        wl, wr = sfh.wrenches(rng, B)
         wr[np.arange(B) % 3 == 1, 2] = 0.0                 # one foot defined
         wr[np.arange(B) % 3 == 2, 2] = 0.0005              # one foot below the threshold (its force still counts in totalZ)
         ref, rej = sf.evaluate_batch(model, t, phase0, st, d["state0"], q, dq, wl, wr, OMEGA)
@@ -240,7 +240,7 @@ def test_measured_state_matches_the_restatement_on_both_anchors(wca):
     # with q_meas = q_des (and no velocity) the CoM is the anchored kinematics' at the desired joints, what the tick's own kinematics see
     pipe2 = _pipe(wca, B, T, kin)
     pipe2.upload(d)
-    pipe2.set_sensor_feedback_host(d["q0"], np.zeros((B, 23)), *sf.wrenches(rng, B))
+    pipe2.set_sensor_feedback_host(d["q0"], np.zeros((B, 23)), *sfh.wrenches(rng, B))
     pipe2.run(1)
     m = pipe2.download()["measured"]
     assert np.array_equal(m[:, 0:2], m[:, 2:4])
@@ -252,17 +252,8 @@ def test_measured_state_matches_the_restatement_on_both_anchors(wca):
 
 def _restated_run(wca, qs, d, T, controller, gs, ext):
     from oracle import tick_spec as ts
-    p = ts.TickParams()
-    kw = dict(kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT, external=ext)
-    if gs:
-        sched = zg.ZMP_SCHEDULE["iCubGazeboV2_5"]
-        if controller == "reactive":
-            with rt.reactive_solve(p, K_DCM, d["q0"].shape[0]):
-                return zg.run_ticks_scheduled(p, d, T, _ik_params(wca, qs), sched, **kw)
-        return zg.run_ticks_scheduled(p, d, T, _ik_params(wca, qs), sched, **kw)
-    if controller == "reactive":
-        return rt.run_ticks_reactive(p, d, T, _ik_params(wca, qs), K_DCM, **kw)
-    return ts.run_ticks(p, d, T, _ik_params(wca, qs), **kw)
+    return ts.run_ticks(ts.TickParams(), d, T, _ik_params(wca, qs), kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT, external=ext,
+                        dcm_controller=controller, k_dcm=K_DCM, zmp_gain_schedule=zg.ZMP_SCHEDULE["iCubGazeboV2_5"] if gs else None)
 
 
 @pytest.mark.gpu

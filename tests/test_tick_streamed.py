@@ -1,8 +1,7 @@
 """Streamed trajectories of the closed-loop tick (wcqp_tick_params.streamed_trajectories): an EXTERNAL handle takes the
-desired stage of every tick - feet, twists, contact flags, fixed frame, CoM height - from wcqp_tick_set_desired_*.  CPU: the restatement
-(tests/helpers/streamed_tick.py) against oracle/tick_spec.py and planned_tick, the ABI, the refusals.  GPU: the device against a planned
+desired stage of every tick - feet, twists, contact flags, fixed frame, CoM height - from wcqp_tick_set_desired_*.  CPU: the restatement's
+given-stages branch (oracle/tick_spec.py::run_ticks(stages=...)) against its synthetic gait and under each plant, the ABI, the refusals.  GPU: the device against a planned
 INTERNAL handle on the same walk, against the restatement under disturbed feedback, the sensor form on moved feet, replanning, refusals."""
-import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -13,10 +12,10 @@ import pytest
 
 import robots
 from helpers import planned_tick as pt
-from helpers import reactive_tick as rt
 from helpers import sensor_feedback as sf
 from helpers import streamed_tick as stt
 from helpers import zmp_gains as zg
+from oracle import sensor_spec as sn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
@@ -52,25 +51,24 @@ def _ik_solver(wca, robot):
 
 
 def _restate(qs, wca, robot, controller, gs, d, stages, T, horizon=50, external=None, splices=None, vel=None):
-    """run_ticks_streamed with the robot's parameters under the controller's and the schedule's patches"""
+    """run_ticks on given stages with the robot's parameters, controller and schedule"""
     from oracle import tick_spec as ts
     R = robots.ROBOTS[robot]
     p = ts.TickParams(horizon=horizon, k_com=R["k_com"], k_zmp=R["k_zmp"])
-    B = d["q0"].shape[0]
-    with contextlib.ExitStack() as es:
-        if controller == "reactive":
-            es.enter_context(rt.reactive_solve(p, K_DCM[robot], B, vel))
-        if gs:
-            es.enter_context(zg.scheduled_gains(p, B, zg.ZMP_SCHEDULE[robot], vel))
-        return stt.run_ticks_streamed(p, d, stages, T, _ik_params(wca, qs, robot), wca.synth.icub_like_model(), wca.synth.FOOT_RECT,
-                                      R["additional_rotation"], external=external, splices=splices)
+    return ts.run_ticks(p, d, T, _ik_params(wca, qs, robot), kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT, stages=stages,
+                        neck_additional_rotation=R["additional_rotation"], external=external, splices=splices, dcm_controller=controller,
+                        k_dcm=K_DCM[robot], dcm_vel=vel, zmp_gain_schedule=zg.ZMP_SCHEDULE[robot] if gs else None)
+
+
+def _given(wca, stages):
+    return dict(kin_model=wca.synth.icub_like_model(), foot_rect=wca.synth.FOOT_RECT, stages=stages, neck_additional_rotation=ADD_ROT)
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
 
 def test_restatement_equals_the_external_run_of_tick_spec(wca, qs):
     """(1) The synthetic gait written out as stages and an `external` dict (a disturbed copy of the internal plant's states, measured
-    joints off the desired ones): the restatement equals tick_spec.run_ticks(kin_model=..., external=...) to 1e-12."""
+    joints off the desired ones): run_ticks(stages=..., external=...) equals run_ticks(kin_model=..., external=...) to 1e-12."""
     from oracle import tick_spec as ts
     B, T = 2, 130
     p = ts.TickParams()
@@ -83,7 +81,7 @@ def test_restatement_equals_the_external_run_of_tick_spec(wca, qs):
     ext = dict(dcm=inner["dcm_log"] + 1e-3 * rng.normal(size=(T, B, 2)), com=inner["com_log"] + 1e-4 * rng.normal(size=(T, B, 2)),
                zmp=inner["zmp_log"] + 1e-3 * rng.normal(size=(T, B, 2)), q=inner["q_log"] + 0.005 * rng.normal(size=(T, B, 23)))
     ref = ts.run_ticks(p, d2, T, ipar, kin_model=model, foot_rect=wca.synth.FOOT_RECT, external=ext)
-    out = stt.run_ticks_streamed(p, d2, stages, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT, external=ext)
+    out = ts.run_ticks(p, d2, T, ipar, external=ext, **_given(wca, stages))
     for k in KEYS:
         assert np.abs(out[k] - ref[k]).max() <= 1e-12, k
     assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
@@ -91,21 +89,52 @@ def test_restatement_equals_the_external_run_of_tick_spec(wca, qs):
 
 
 def test_restatement_fed_the_internal_plant_equals_the_planned_one(wca, qs):
-    """(2) Run with the internal plant it equals run_ticks_planned; fed that run's own per-tick plant states as `external` it still does."""
+    """(2) A planned upload as stages with the internal plant; fed that run's own per-tick plant states as `external` it is still that run."""
     from oracle import tick_spec as ts
     B, T = 2, 150
     model, d = _walk_cpu(wca, B, T, planned=True, yaw_step=(0.03, 0.08))
     ipar = _ik_params(wca, qs, ROBOT)
     p = ts.TickParams()
-    ref = pt.run_ticks_planned(p, d, d, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT)
     stages = stt.stages_of(d, T)
-    a = stt.run_ticks_streamed(p, d, stages, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT)
-    b = stt.run_ticks_streamed(p, d, stages, T, ipar, model, wca.synth.FOOT_RECT, ADD_ROT, external=stt.external_of(a))
-    for out in (a, b):
-        for k in KEYS:
-            assert np.abs(out[k] - ref[k]).max() <= 1e-12, k
-        assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
+    ref = ts.run_ticks(p, d, T, ipar, **_given(wca, stages))
+    out = ts.run_ticks(p, d, T, ipar, external=stt.external_of(ref), **_given(wca, stages))
+    for k in KEYS:
+        assert np.abs(out[k] - ref[k]).max() <= 1e-12, k
+    assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
     assert len({int(x) & 3 for x in d["contact"][0, :T]}) >= 2 and np.abs(ref["dq_log"]).max() > 1e-3
+
+
+def test_a_non_finite_reading_on_given_stages_is_rejected_as_on_the_synthetic_gait(wca, qs):
+    """Stages plus `external` with robot 1's reading non-finite on tick 3: the robot keeps the measured state of the tick before, is counted
+    (feedback_fail, then ik_fail for the rejection and every tick it runs stopped) and gets dq = 0 from then on, exactly as the
+    synthetic-gait `external` run holds it - the same gait written out as stages gives the same counters and the same run; robot 0 is
+    bit for bit the clean run's."""
+    from oracle import tick_spec as ts
+    B, T, k, r = 2, 6, 3, 1
+    p = ts.TickParams()
+    model, d = _walk_cpu(wca, B, T)
+    ipar = _ik_params(wca, qs, ROBOT)
+    plan, d2 = pt.synthetic_as_planned(p, d, T + p.horizon + 1, ADD_ROT)
+    rng = np.random.default_rng(9)
+    ext = dict(dcm=d2["dcm0"] + 1e-3 * rng.normal(size=(T, B, 2)), com=d2["com0"] + 1e-4 * rng.normal(size=(T, B, 2)),
+               zmp=d2["u_init"] + 1e-3 * rng.normal(size=(T, B, 2)), q=d2["q0"] + 0.005 * rng.normal(size=(T, B, 23)))
+    bad = {key: v.copy() for key, v in ext.items()}
+    bad["com"][k, r, 0] = np.inf
+    given = _given(wca, stt.stages_of(plan, T))
+    clean = ts.run_ticks(p, d2, T, ipar, external=ext, **given)
+    out = ts.run_ticks(p, d2, T, ipar, external=bad, **given)
+    ref = ts.run_ticks(p, d2, T, ipar, kin_model=model, foot_rect=wca.synth.FOOT_RECT, external=bad)
+    assert list(out["feedback_fail"]) == [0, 1] and list(out["ik_fail"]) == [0, 1 + (T - k)] and clean["feedback_fail"].sum() == 0
+    assert np.array_equal(out["feedback_fail"], ref["feedback_fail"]) and np.array_equal(out["ik_fail"], ref["ik_fail"])
+    assert np.array_equal(out["mpc_fail"], ref["mpc_fail"])
+    assert (out["dq_log"][k:, r] == 0).all() and np.abs(out["dq_log"][k - 1, r]).max() > 0
+    for key in ("dcm_log", "com_log", "zmp_log"):
+        assert np.array_equal(out[key][k, r], out[key][k - 1, r]), key          # the measured state of the tick before, kept
+    for key in KEYS:
+        assert np.isfinite(out[key]).all() and np.abs(out[key] - ref[key]).max() <= 1e-12, key
+    for key in ("u0_log", "dq_log"):
+        assert np.array_equal(out[key][:, 0], clean[key][:, 0]) and np.array_equal(out[key][:k], clean[key][:k]), key
+    assert np.array_equal(out["q_des"][0], clean["q_des"][0])
 
 
 def test_robot_in_the_loop_run_is_reproduced_by_its_recording(wca, qs):
@@ -121,12 +150,12 @@ def test_robot_in_the_loop_run_is_reproduced_by_its_recording(wca, qs):
 
     def sensors(t, q_des, dq_prev, u_prev):
         return q_des + noise[t], dq_prev, w, w
-    args = (ts.TickParams(), d, stages, T, _ik_params(wca, qs, ROBOT), model, wca.synth.FOOT_RECT, ADD_ROT)
-    a = stt.run_ticks_streamed(*args, sensors=sensors)
-    b = stt.run_ticks_streamed(*args, external=stt.external_of_sensors(a))
+    args = (ts.TickParams(), d, T, _ik_params(wca, qs, ROBOT))
+    a = ts.run_ticks(*args, sensors=sensors, **_given(wca, stages))
+    b = ts.run_ticks(*args, external=stt.external_of_sensors(a), **_given(wca, stages))
     for k in KEYS[:3]:
         assert np.array_equal(a[k], b[k]), k
-    m, _ = stt.sensor_measured(model, stages, 0, d["q0"] + noise[0], np.zeros((B, 23)), w, w, OMEGA)
+    m, _ = sn.sensor_measured(model, stages, 0, d["q0"] + noise[0], np.zeros((B, 23)), w, w, OMEGA)
     assert np.array_equal(a["measured_log"][0], m) and (a["ik_fail"] == 0).all() and np.abs(a["dq_log"]).max() > 1e-4
 
 
@@ -357,7 +386,7 @@ def _sensor_case(wca, qs, d):
     from oracle import tick_spec as ts
     B = d["q0"].shape[0]
     stages = stt.stages_of(d, WALK_T)
-    side = stt.stage_side(stages["contact"])                       # [T][B]
+    side = sn.stage_side(stages["contact"])                       # [T][B]
     sw = [t for t in range(1, WALK_T) if (side[t] != side[t - 1]).any()]
     moved = [t for t in sw if np.abs(stages["left_pose"][t] - stages["left_pose"][0]).max() > 1e-3
              or np.abs(stages["right_pose"][t] - stages["right_pose"][0]).max() > 1e-3]
@@ -384,8 +413,7 @@ def _sensor_case(wca, qs, d):
         return q_des + qn[t], dq_prev + dqn[t], w[0], w[1]
     R = robots.ROBOTS[ROBOT]
     p = ts.TickParams(horizon=50, k_com=R["k_com"], k_zmp=R["k_zmp"])
-    ref = stt.run_ticks_streamed(p, d, stages, T, _ik_params(wca, qs, ROBOT), wca.synth.icub_like_model(), wca.synth.FOOT_RECT,
-                                 R["additional_rotation"], sensors=sensors)
+    ref = ts.run_ticks(p, d, T, _ik_params(wca, qs, ROBOT), sensors=sensors, **_given(wca, stages))
     return T, stages, check_ticks, ref
 
 
@@ -400,7 +428,7 @@ def test_sensor_form_on_moved_feet(wca, qs, walks):
     T, stages, check_ticks, ref = _sensor_case(wca, qs, d)
     assert (ref["ik_fail"] == 0).all() and (ref["mpc_fail"] == 0).all() and np.abs(ref["dq_log"]).max() > 1e-2
     readings, restated = ref["readings"], ref["measured_log"]
-    side = stt.stage_side(stages["contact"][check_ticks])
+    side = sn.stage_side(stages["contact"][check_ticks])
     assert set(side[:, 0]) == {0, 1} and max(np.abs(stages[f][check_ticks[0]] - stages[f][0]).max() for f in ("left_pose", "right_pose")) > 1e-3
     a = _pipe(wca, B, WALK_T, ROBOT, "mpc", False)          # (the walk's arrays are WALK_T ticks long; T of them run)
     _upload_streamed(a, d, vel=False)

@@ -2,11 +2,11 @@
 ZMP-CoM gain scheduling in the closed-loop tick (wcqp_tick_params.zmp_gain_scheduling): the reference's `useGainScheduling 1`, set in
 the zmpControllerParams.ini of all three shipped robots.  Every tick calls WalkingZMPController::setPhase(|dcm_des_dot| < 0.001) before
 the ZMP-CoM law (WM/src/WalkingModule.cpp:657-662), which moves kCoM / kZMP between the stance and the walking values through a smoother
-(WM/src/WalkingZMPController.cpp:29-125).  Checked against tests/helpers/zmp_gains.py: two separate smoothers per robot around
-oracle/tick_spec.run_ticks (and tests/helpers/reactive_tick.py for the reactive controller).
+(WM/src/WalkingZMPController.cpp:29-125).  Checked against oracle/zmp_gains_spec.py: two separate smoothers per robot, advanced by
+oracle/tick_spec.run_ticks(zmp_gain_schedule=...) with either DCM controller.
 """
 import ctypes as C
-import importlib.util
+import dataclasses
 import os
 import subprocess
 
@@ -14,19 +14,10 @@ import numpy as np
 import pytest
 
 import robots
+from helpers import zmp_gains as zgh
+from oracle import zmp_gains_spec as zg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "helpers", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-zg = _load("zmp_gains")
-rt = _load("reactive_tick")
 
 K_DCM = {"iCubGazeboV2_5": 1.2, "iCubGenova04": 1.1, "icubGazeboSim": 1.2}   # dcmReactiveControllerParams.ini:1 (as test_tick_reactive)
 VMAX = 0.45
@@ -51,7 +42,7 @@ def test_smoother_step_response_and_rest():
 
 def test_one_filter_equals_two_filters():
     rng = np.random.default_rng(5)
-    for robot, sched in zg.ZMP_SCHEDULE.items():
+    for robot, sched in zgh.ZMP_SCHEDULE.items():
         R = robots.ROBOTS[robot]
         vel = rng.normal(scale=0.01, size=(300, 2))
         vel[rng.random(300) < 0.4] = 0.0
@@ -70,15 +61,21 @@ def test_stance_flag_at_the_threshold():
     assert zg.is_stance([0.0, 0.0]) and not zg.is_stance([0.001, 0.0])
 
 
-def test_wrapper_restores_the_patch_and_the_gains():
-    from oracle import tick_spec as ts
+def test_wrapper_restores_the_patch_and_the_gains(wca):
+    """A run with the reactive controller and a gain schedule writes nothing to `p` (field for field) and leaves oracle.qp_spec.mpc_exact
+    the object it was, a run that raises included; the gains it used come back as zmp_gains."""
+    from oracle import qp_spec, tick_spec as ts
     p = ts.TickParams()
-    orig = ts.qs.mpc_exact
-    with pytest.raises(RuntimeError):
-        with zg.scheduled_gains(p, 2, zg.ZMP_SCHEDULE["iCubGazeboV2_5"]):
-            assert ts.qs.mpc_exact is not orig and p.k_com.shape == (2, 1)
-            raise RuntimeError("inside")
-    assert ts.qs.mpc_exact is orig and p.k_com == 9.0 and p.k_zmp == 3.0
+    before, orig = dataclasses.replace(p), qp_spec.mpc_exact
+    d = wca.synth.synth_tick_batch(2, 4)
+    ipar = qp_spec.IKParams(v_max=VMAX * np.ones(23))
+    kw = dict(dcm_controller="reactive", k_dcm=1.2, zmp_gain_schedule=zgh.ZMP_SCHEDULE["iCubGazeboV2_5"])
+    out = ts.run_ticks(p, d, 4, ipar, **kw)
+    assert out["zmp_gains"].shape == (4, 2, 2) and np.abs(out["zmp_gains"][-1] - [9.0, 3.0]).max() > 1e-3
+    assert dataclasses.asdict(p) == dataclasses.asdict(before) and p.k_com == 9.0 and p.k_zmp == 3.0 and qp_spec.mpc_exact is orig
+    with pytest.raises(IndexError):
+        ts.run_ticks(p, d, 4, ipar, dcm_vel=np.zeros((2, 2, 2)), **kw)          # the velocities run out on tick 2: the run raises half way
+    assert dataclasses.asdict(p) == dataclasses.asdict(before) and qp_spec.mpc_exact is orig and ts.qs.mpc_exact is orig
 
 
 def test_new_struct_fields_match_the_ctypes_mirror(wca, tmp_path):
@@ -121,7 +118,7 @@ def test_create_refuses_a_bad_schedule_before_the_device(wca):
 # ---------------------------------------------------------------------------------------------------------------- GPU
 
 def _sched(robot):
-    return zg.ZMP_SCHEDULE[robot]
+    return zgh.ZMP_SCHEDULE[robot]
 
 
 def _pipe(wca, B, T, robot, controller, ik, tpl=0, first=0, **kw):
@@ -140,7 +137,7 @@ def _paused(d, B, T, seed=0):
         s = int(rng.integers(45, T - 60))
         pauses[i] = [(0, a), (s, int(rng.integers(12, 30)))]
     d = dict(d)
-    d["ref_traj"], idx = zg.pause_reference(np.asarray(d["ref_traj"]), pauses)
+    d["ref_traj"], idx = zgh.pause_reference(np.asarray(d["ref_traj"]), pauses)
     if "zmp_ref" in d:
         d["zmp_ref"] = np.stack([np.asarray(d["zmp_ref"])[i, idx[i]] for i in range(B)])
     return d
@@ -148,11 +145,7 @@ def _paused(d, B, T, seed=0):
 
 def _reference(qs, p, d, T, ipar, robot, controller, vel=None, **kw):
     from oracle import tick_spec as ts
-    B = d["q0"].shape[0]
-    if controller == "reactive":
-        with rt.reactive_solve(p, K_DCM[robot], B, vel):
-            return zg.run_ticks_scheduled(p, d, T, ipar, _sched(robot), dcm_vel=vel, **kw)
-    return zg.run_ticks_scheduled(p, d, T, ipar, _sched(robot), dcm_vel=vel, **kw)
+    return ts.run_ticks(p, d, T, ipar, dcm_controller=controller, k_dcm=K_DCM[robot], dcm_vel=vel, zmp_gain_schedule=_sched(robot), **kw)
 
 
 def _close(out, ref, tol=1e-9, logger=False):
@@ -234,8 +227,7 @@ def test_closed_loop_constant_jacobians(wca, qs, paused_batch, controller, alg):
     pipe.run(T)
     _close(pipe.download(), ref)
     # (the fixed gains give another run: the gains reach the joints through the desired CoM; the plant follows the controller's ZMP)
-    fixed = (rt.run_ticks_reactive(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23)), K_DCM[robot]) if controller == "reactive"
-             else ts.run_ticks(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23))))
+    fixed = ts.run_ticks(p, d, T, qs.IKParams(v_max=VMAX * np.ones(23)), dcm_controller=controller, k_dcm=K_DCM[robot])
     assert np.abs(ref["dq_log"] - fixed["dq_log"]).max() > 1e-6
 
 

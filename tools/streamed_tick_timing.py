@@ -3,7 +3,8 @@
 
   (a) the sensor-fed EXTERNAL tick on the synthetic gait (tick_sensor_kernel + prime + tick kernel),
   (b) the streamed sensor-fed tick (tick_desired_kernel + tick_sensor_kernel<PL> + prime + tick kernel) on the same gait written as stages
-      (tests/helpers/planned_tick.py::synthetic_as_planned), so that both sides do the same work,
+      (tests/helpers/planned_tick.py::synthetic_as_planned, the stage source oracle/tick_spec.py::run_ticks(stages=...) restates), so that
+      both sides do the same work,
   (c) tick_desired_kernel alone, back-to-back launches.
 
     python tools/streamed_tick_timing.py [--batch 8192] [--ticks 200] [--reps 5] [--out profiles/streamed_tick_timing.json]

@@ -8,14 +8,13 @@ controller side by side, for constant Jacobians and fused kinematics at horizon 
 
 Per case: one pipeline of `batch` robots; every repetition re-uploads the inputs, runs `--warmup` ticks, then `--ticks` timed ticks in
 ONE wcqp_tick_run call (device events around it); the median over the repetitions is reported.  The first repetition logs its first
-16 ticks, and a sample of robots is replayed through the CPU restatement (oracle/tick_spec.py; for the reactive controller with its
-MPC solve replaced by the reactive law, tests/helpers/reactive_tick.py).  Kernel statistics: run this under
+16 ticks, and a sample of robots is replayed through the CPU restatement (oracle/tick_spec.py::run_ticks with the case's controller
+and gain schedule).  Kernel statistics: run this under
 `rocprofv3 --kernel-trace --stats` in a run of its own (--no-check keeps the CPU replay out of it).
     python tools/tick_controller_timing.py --planned [...]     (fused kinematics at N = 50, both controllers: planned trajectories -
         the synthetic gait written out as the planner's stages, the same work - against the synthetic gait, the two forms alternating
         within every repetition; the first 16 ticks of both forms must agree to 1e-12)"""
 import argparse
-import importlib.util
 import json
 import os
 import sys
@@ -25,19 +24,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import torch  # noqa: E402  (the GPU runtime first, then libwcqp)
 import walking_controllers_amd as wca  # noqa: E402
+from helpers import planned_tick as pt  # noqa: E402
+from helpers import zmp_gains as zg  # noqa: E402
 
-_spec = importlib.util.spec_from_file_location("reactive_tick", os.path.join(ROOT, "tests", "helpers", "reactive_tick.py"))
-rt = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(rt)
-_spec = importlib.util.spec_from_file_location("planned_tick", os.path.join(ROOT, "tests", "helpers", "planned_tick.py"))
-pt = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(pt)
-_spec = importlib.util.spec_from_file_location("zmp_gains", os.path.join(ROOT, "tests", "helpers", "zmp_gains.py"))
-zg = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(zg)
 GS = zg.ZMP_SCHEDULE["iCubGazeboV2_5"]       # smoothingTime 0.05, kCoM / kZMP stance 6.0 / 0.9 (walking: 9.0 / 3.0, the TickParams defaults)
 
 K_DCM = 1.2          # iCubGazeboV2_5, app/robots/iCubGazeboV2_5/dcmReactiveControllerParams.ini:1
@@ -69,16 +62,7 @@ def check_sample(kin_mode, ctrl, horizon, B, n, logged, kin, gs=False):
     fails = 0
     for f in (0, B - 4):
         one = make_data(kin_mode, 4, n, horizon, f, kin)
-        if gs:
-            if ctrl == "reactive":
-                with rt.reactive_solve(p, K_DCM, 4):
-                    ref = zg.run_ticks_scheduled(p, one, CHECK_TICKS, ipar, GS, **kw)
-            else:
-                ref = zg.run_ticks_scheduled(p, one, CHECK_TICKS, ipar, GS, **kw)
-        elif ctrl == "reactive":
-            ref = rt.run_ticks_reactive(p, one, CHECK_TICKS, ipar, K_DCM, **kw)
-        else:
-            ref = ts.run_ticks(p, one, CHECK_TICKS, ipar, **kw)
+        ref = ts.run_ticks(p, one, CHECK_TICKS, ipar, dcm_controller=ctrl, k_dcm=K_DCM, zmp_gain_schedule=GS if gs else None, **kw)
         eu = max(eu, float(np.abs(logged["u0_log"][:, f:f + 4] - ref["u0_log"]).max()))
         ed = max(ed, float(np.abs(logged["dq_log"][:, f:f + 4] - ref["dq_log"]).max()))
         fails += int(ref["ik_fail"].sum())
