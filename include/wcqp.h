@@ -592,6 +592,16 @@ typedef struct wcqp_tick_params {
      * taken (an MPC horizon below 56; REACTIVE any), the default / base-eliminated IK algorithm, logger_ticks = 0 and
      * planned_trajectories = 0. */
     int32_t streamed_trajectories;
+    /* Low-pass filters of the sensor form (wcqp_tick_set_sensor_feedback_*, which says what they do), cut frequencies in Hz; 0 = that
+     * filter off (the reference's use_* 0; all three 0: the handle behaves as before, bit for bit):
+     *   joint_velocity_cut_frequency   use_joint_velocity_filter / joint_velocity_cut_frequency   (robotControl.ini)
+     *   wrench_cut_frequency           use_wrench_filter / wrench_cut_frequency                   (robotControl.ini)
+     *   com_cut_frequency              use_filters / cut_frequency                                (forwardKinematics.ini)
+     * wcqp_tick_create returns WCQP_E_INVALID for a negative or non-finite value and WCQP_E_UNSUPPORTED, before anything touches the
+     * device, for a value > 0 on a handle without a sensor form: the internal plant, or use_kinematics = 0. */
+    double joint_velocity_cut_frequency;
+    double wrench_cut_frequency;
+    double com_cut_frequency;
 } wcqp_tick_params;
 #define WCQP_TICK_PLANT_INTERNAL 0
 #define WCQP_TICK_PLANT_EXTERNAL 1
@@ -711,8 +721,28 @@ int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const dou
  *      measured state of tick t - 1 (tick 0: the uploaded one, with the desired joints), wcqp_tick_outputs.feedback_fail counts it, and it
  *      is stopped like a robot whose IK failed: dq = 0 from tick t on.  Its ik_fail then counts the rejection (when it was not stopped
  *      yet) and every tick it runs stopped, tick t included.  The other robots are unaffected.
- * The low-pass filters of the reference (use_filters, use_joint_velocity_filter, use_wrench_filter) are not applied.  Marks the
- * feedback of tick t as set, as wcqp_tick_set_feedback_device does; either form may feed any tick of a handle.  The device form enqueues
+ * Low-pass filters (wcqp_tick_params.joint_velocity_cut_frequency, wrench_cut_frequency, com_cut_frequency; each on when > 0): the
+ * reference's three first-order filters, RobotHelper::getFeedbacks (WM/src/RobotHelper.cpp:408-440) and WalkingFK::evaluateCoM /
+ * evaluateDCM / getCoMPosition (WM/src/WalkingForwardKinematics.cpp:138-162, 278-340, 354-394).  The filter is 1 / (1 + s tau),
+ * tau = 1 / (2 pi f_c), discretised with the bilinear transform at Ts = mpc.sampling_time:
+ *   y_k = (Ts (u_k + u_{k-1}) - (Ts - 2 tau) y_{k-1}) / (2 tau + Ts)        (unit DC gain; init(y0): u_{-1} = y_{-1} = y0)
+ * (the build's definition: iCub::ctrl::FirstOrderLowPassFilter is upstream).  Per robot, in this order:
+ *   a. Finiteness (rule 5) is judged on the RAW readings: nothing non-finite ever enters a filter's state.
+ *   b. dq_f = LP(dq_meas) per joint (positions are not filtered: the reference's position filter is commented out); LP of fz, tx, ty of
+ *      each wrench - what step 3 reads; the other components have no consumer and no state.
+ *   c. Step 1 at q_meas as above; step 2 with v_com formed from dq_f.  CoM filter: com = LP(com_xy), v = LP(v_com_xy),
+ *      dcm = com + v / omega; the filtered com is also the CoM the ZMP-CoM controller reads (getCoMPosition).
+ *   d. Step 3 on the filtered wrenches: the fz >= 0.001 test and the totalZ >= 0.1 test of rule 5 see filtered forces only.
+ *   wcqp_tick_outputs.measured reports what the tick used, so the filtered values.
+ * State, per robot, kept in the handle across ticks: wcqp_tick_upload resets it.  The joint-velocity and wrench filters start AT the
+ * first sensor reading the handle receives after an upload (RobotHelper::resetFilters), which is its own filtered value.  The CoM
+ * position filter starts at the uploaded com0 and the CoM velocity filter at 0 - DEVIATION: the reference starts them at
+ * (0, 0, com_height) and 0, once, at configure (WalkingForwardKinematics.cpp:153-160); the robots of a batch stand anywhere, and with
+ * com0 = 0 this is the reference's value.  A rejected robot's filters hold their state (it is stopped until the next upload anyway).
+ * "A second call before the tick runs replaces the first" holds for the filters too: every call starts from the state the last RUN
+ * tick left, and wcqp_tick_run commits the state of the call it consumes - two calls for one tick advance each filter once.  A tick
+ * fed by wcqp_tick_set_feedback_* supplies no sample: the filters hold (also when that call replaces a sensor call before the run).
+ * Marks the feedback of tick t as set, as wcqp_tick_set_feedback_device does; either form may feed any tick of a handle.  The device form enqueues
  * one kernel on `stream` and retains nothing.  WCQP_E_INVALID for a NULL pointer or a handle that has not been uploaded;
  * WCQP_E_UNSUPPORTED with the internal plant or without per-tick kinematics (use_kinematics = 0). */
 int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
@@ -757,6 +787,7 @@ typedef struct wcqp_tick_info {
     int32_t zmp_gain_scheduling;   /* wcqp_tick_params.zmp_gain_scheduling as taken (0 / 1)                                 */
     int32_t planned_trajectories;  /* wcqp_tick_params.planned_trajectories as taken (0 / 1)                                */
     int32_t streamed_trajectories; /* wcqp_tick_params.streamed_trajectories as taken (0 / 1)                               */
+    int32_t sensor_filters;        /* low-pass filters of the sensor form taken: bit 0 joint velocity, bit 1 wrench, bit 2 CoM      */
 } wcqp_tick_info;
 int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
 

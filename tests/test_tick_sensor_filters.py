@@ -1,0 +1,468 @@
+"""Low-pass filters of the sensor form (include/wcqp.h: wcqp_tick_params.joint_velocity_cut_frequency, wrench_cut_frequency,
+com_cut_frequency): the reference's three first-order filters on the joint velocities, the foot wrenches and the measured
+CoM, with their state in the handle.  Checked against tests/helpers/sensor_filters.py (scipy's bilinear transform, direct form I, around
+oracle/sensor_spec.py) - download()["measured"] to 1e-12, the bar of tests/test_tick_sensor_feedback.py - and in closed loop against
+oracle/tick_spec.run_ticks(external=...) fed the restated filtered states: u0_log, q_des 1e-9, dq_log 1e-8."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import robots
+from helpers import planned_tick as pt
+from helpers import sensor_feedback as sfh
+from helpers import sensor_filters as flt
+from helpers import streamed_tick as stt
+from oracle import sensor_spec as sn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
+OMEGA = np.sqrt(9.81 / 0.53)
+TS, ST = 0.01, 180                               # mpc.sampling_time, step_ticks
+ROBOT = "iCubGazeboV2_5"
+ADD_ROT = robots.ROBOTS[ROBOT]["additional_rotation"]
+K_DCM = 1.0
+ALL = dict(joint_velocity=10.0, wrench=10.0, com=10.0)
+CASES = {"joint_velocity": dict(joint_velocity=10.0), "wrench": dict(wrench=10.0), "com": dict(com=10.0), "all": ALL}
+MASK = {"joint_velocity": 1, "wrench": 2, "com": 4, "all": 7}
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU
+def test_new_fields_match_the_ctypes_mirror(wca, tmp_path):
+    """(1) sizeof / offsetof of the three cut frequencies and of wcqp_tick_info.sensor_filters: the C compiler's == the ctypes mirror's."""
+    capi = wca.capi
+    fields = [("wcqp_tick_params", k, capi.TickParams) for k in ("joint_velocity_cut_frequency", "wrench_cut_frequency", "com_cut_frequency")]
+    fields += [("wcqp_tick_info", "sensor_filters", capi.TickInfo)]
+    structs = (("wcqp_tick_params", capi.TickParams), ("wcqp_tick_info", capi.TickInfo))
+    body = "".join(f'printf("%zu\\n", offsetof({s}, {f}));\n' for s, f, _ in fields)
+    body += "".join(f'printf("%zu\\n", sizeof({s}));\n' for s, _ in structs)
+    src = tmp_path / "off.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "wcqp.h"\nint main(void) {\n' + body + "return 0;\n}\n")
+    exe = tmp_path / "off"
+    subprocess.check_call(["cc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert got == [getattr(cls, f).offset for _, f, cls in fields] + [C.sizeof(cls) for _, cls in structs]
+    # appended: every earlier field stays where it was
+    assert capi.TickParams.joint_velocity_cut_frequency.offset > capi.TickParams.streamed_trajectories.offset
+    assert capi.TickInfo.sensor_filters.offset == capi.TickInfo.streamed_trajectories.offset + 4
+
+
+@pytest.mark.parametrize("fc", [1.0, 10.0, 40.0])
+def test_restated_filter(fc):
+    """(2) scipy's bilinear coefficients equal the closed form of the header to 1e-15; a constant input returns itself; after init(y0) the
+    first output on u = y0 is y0; a unit step from rest is within 1e-3 of 1 after 10 tau / Ts samples."""
+    assert np.abs(np.array(flt.scipy_coeffs(fc, TS)) - np.array(flt.closed_form(fc, TS))).max() <= 1e-15
+    b0, b1, a1 = flt.scipy_coeffs(fc, TS)
+    assert abs(a1) < 1.0                                         # a contraction: rounding does not accumulate
+    f = flt.LowPass(fc, TS, (3,))
+    y0 = np.array([0.3, -2.0, 150.0])
+    f.init(y0)
+    assert np.abs(f.step(y0) - y0).max() <= 1e-15 * 150.0
+    for _ in range(50):
+        y = f.step(y0)
+    assert np.abs(y - y0).max() <= 1e-13
+    g = flt.LowPass(fc, TS, ())
+    tau = 1.0 / (2.0 * np.pi * fc)
+    for _ in range(int(np.ceil(10.0 * tau / TS))):
+        y = g.step(1.0)
+    assert abs(y - 1.0) <= 1e-3
+    off = flt.LowPass(0.0, TS, (2,))
+    assert np.array_equal(off.step(np.array([1.0, 2.0])), [1.0, 2.0])
+
+
+def test_binding_refuses_bad_filters_before_the_library(wca):
+    """(3) Unknown keys, negative and non-finite frequencies: ValueError before any library call (solvers that were never created: a call
+    that reached wcqp_tick_create would come back as a WcqpError)."""
+    mpc, ik = wca.MpcSolver.__new__(wca.MpcSolver), wca.IkSolver.__new__(wca.IkSolver)
+    mpc.params = wca.capi.MpcParams(); ik.params = wca.capi.IkParams(); ik.dof = 23
+    for bad, what in ((dict(velocity=10.0), "unknown key"), (dict(wrench=-1.0), "wrench"), (dict(com=float("nan")), "com"),
+                      (dict(joint_velocity=float("inf")), "joint_velocity")):
+        with pytest.raises(ValueError, match=what):
+            wca.TickPipeline(4, 10, mpc, ik, external_feedback=True, sensor_filters=bad)
+    with pytest.raises(wca.WcqpError):
+        wca.TickPipeline(4, 10, mpc, ik, external_feedback=True, sensor_filters=dict(com=10.0))      # reached the library: refused there
+
+
+def _params(wca, **kw):
+    prm = wca.capi.TickParams()
+    prm.batch, prm.max_ticks, prm.step_ticks, prm.ds_ticks = 4, 10, 180, 110
+    prm.mpc.horizon, prm.mpc.sampling_time, prm.mpc.com_height, prm.mpc.gravity = 50, 0.01, 0.53, 9.81
+    prm.ik.dof, prm.use_kinematics, prm.kin_handoff, prm.plant = 23, 1, 0, 1
+    for k, v in kw.items():
+        setattr(prm, k, v)
+    return prm
+
+
+@pytest.mark.parametrize("field", ["joint_velocity_cut_frequency", "wrench_cut_frequency", "com_cut_frequency"])
+def test_create_refuses_before_the_device(wca, field):
+    """(11, the part that needs no device) A frequency > 0 with the internal plant or with use_kinematics = 0: WCQP_E_UNSUPPORTED; a negative
+    or non-finite one: WCQP_E_INVALID - both before anything touches the device."""
+    h = C.c_void_p()
+    create = lambda **kw: wca.capi.lib().wcqp_tick_create(C.byref(_params(wca, **kw)), C.byref(h))
+    assert create(**{field: 10.0, "plant": 0}) == WCQP_E_UNSUPPORTED and not h
+    assert create(**{field: 10.0, "use_kinematics": 0}) == WCQP_E_UNSUPPORTED and not h
+    for bad in (-1.0, float("nan"), float("inf"), -float("inf")):
+        assert create(**{field: bad}) == WCQP_E_INVALID and not h
+        assert create(**{field: bad, "plant": 0}) == WCQP_E_INVALID and not h
+
+
+# ---------------------------------------------------------------------------------------------------------------- scenarios
+def _ik_solver(wca):
+    r = robots.ROBOTS[ROBOT]
+    return wca.IkSolver(form=wca.IK_FORM_QPOASES, neck_weight=r["neck_weight"] * np.eye(3), joint_reg_weights=np.array(r["reg_w"], float),
+                        joint_reg_gains=np.array(r["reg_k"], float), joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG),
+                        v_max=wca.synth.WALK_VMAX.copy(), k_pos_com=r["k_pos_com"], k_pos_foot=r["k_pos_foot"], k_att_foot=r["k_att_foot"],
+                        k_neck=r["k_neck"])
+
+
+def _ik_params(wca, qs):
+    ipar = robots.ik_params(qs, ROBOT, v_max=wca.synth.WALK_VMAX.copy())
+    ipar.joint_reg_deg = wca.synth.WALK_POSTURE_DEG.copy()
+    return ipar
+
+
+def _pipe(wca, B, T, filters, streamed=False, controller="mpc"):
+    R = robots.ROBOTS[ROBOT]
+    kw = dict(streamed_trajectories=True, neck_additional_rotation=np.array(ADD_ROT)) if streamed else {}
+    if controller == "reactive":
+        kw.update(dcm_controller="reactive", k_dcm=K_DCM)
+    if filters is not None:
+        kw.update(sensor_filters=filters)
+    return wca.TickPipeline(B, T, wca.MpcSolver(), _ik_solver(wca), log_ticks=T, k_com=R["k_com"], k_zmp=R["k_zmp"],
+                            kin=wca.KinModel(wca.synth.icub_like_model()), external_feedback=True, **kw)
+
+
+def _stage(stages, t):
+    return tuple(stages[k][t] for k in ("left_pose", "right_pose", "left_twist", "right_twist", "contact")) + \
+           (stages["com_height"][t], stages["com_height_vel"][t])
+
+
+class Scene:
+    """B robots on the synthetic gait, half of them four ticks before a stance switch, and T ticks of noisy readings that do not depend on
+    the run: joints near the initial ones (sigma 0.05), velocities of 0.3 rad/s, wrenches with both feet defined, one defined, one below
+    the 0.001 threshold.  streamed: the same gait written out as stages, handed over tick by tick."""
+
+    def __init__(self, wca, B, T, streamed, seed=3):
+        from oracle import tick_spec as ts
+        self.wca, self.B, self.T, self.streamed = wca, B, T, streamed
+        self.model = wca.synth.icub_like_model()
+        kb = wca.synth.synth_walk_kin_batch(B)
+        d = wca.synth.synth_walk_batch(B, T, pt.poses_host(self.model, kb), kb)
+        self.phase0 = np.array([ST - 4 if i % 2 == 0 else 50 for i in range(B)], np.int32)
+        d = dict(d, phase0=self.phase0)
+        self.stages = None
+        if streamed:
+            plan, d = pt.synthetic_as_planned(ts.TickParams(), d, T + 51, ADD_ROT)
+            self.stages = stt.stages_of(plan, T)
+        self.d = d
+        rng = np.random.default_rng(seed)
+        self.readings = []
+        for t in range(T):
+            wl, wr = sfh.wrenches(rng, B)
+            wr[np.arange(B) % 3 == 1, 2] = 0.0
+            wr[np.arange(B) % 3 == 2, 2] = 0.0005
+            self.readings.append((d["q0"] + 0.05 * rng.normal(size=(B, 23)), 0.3 * rng.normal(size=(B, 23)), wl, wr))
+
+    def pipe(self, filters):
+        p = _pipe(self.wca, self.B, self.T, filters, self.streamed)
+        self.upload(p)
+        return p
+
+    def upload(self, p):
+        if self.streamed:
+            p.upload({k: self.d[k] for k in ("ref_traj", "state0", "q0", "dcm0", "com0", "u_init")})
+        else:
+            p.upload(self.d)
+
+    def restatement(self, filters):
+        return flt.SensorFilters(self.B, TS, self.d["com0"], **(filters or {}))
+
+    def restate(self, f, t, r):
+        if self.streamed:
+            return f.step_stages(self.model, self.stages, t, *r, OMEGA)
+        return f.step_gait(self.model, t, self.phase0, ST, self.d["state0"], *r, OMEGA)
+
+    def tick(self, p, t, r, form="sensor", m=None):
+        """one tick of handle p: the stage (streamed), the feedback - the sensor form's readings r, or the plain form's measured m - and the
+        run; returns the download"""
+        if self.streamed:
+            p.set_desired_host(*_stage(self.stages, t))
+        if form == "sensor":
+            p.set_sensor_feedback_host(*r)
+        else:
+            p.set_feedback_host(m[:, 0:2], m[:, 2:4], m[:, 4:6], r[0])
+        p.run(1)
+        return p.download()
+
+
+BITS = ("measured", "u0_log", "dq_log", "q_des", "ik_fail", "mpc_fail", "feedback_fail")
+
+
+def _same_bits(a, b, rows=None):
+    for k in BITS:
+        x, y = a[k], b[k]
+        if rows is not None:
+            x, y = (x[:, rows], y[:, rows]) if k.endswith("_log") else (x[rows], y[rows])
+        assert np.array_equal(x, y), k
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,gait,B", [(c, g, 6) for c in CASES for g in ("synthetic", "streamed")] + [("all", "synthetic", 1), ("all", "streamed", 1)])
+def test_measured_state_tick_by_tick(wca, case, gait, B):
+    """(4) B = 6 (a full wave and a half-empty one, whose dead groups alias the last robot) and B = 1, 12 ticks around a stance switch:
+    download()["measured"] == the restatement to 1e-12 after every tick, nothing rejected, and the filters are seen to act."""
+    T = 12
+    sc = Scene(wca, B, T, gait == "streamed")
+    p, f, raw = sc.pipe(CASES[case]), sc.restatement(CASES[case]), sc.restatement(None)
+    assert p.info()["sensor_filters"] == MASK[case] == f.mask
+    sides, worst, moved = set(), 0.0, 0.0
+    for t in range(T):
+        ref, rej = sc.restate(f, t, sc.readings[t])
+        unf, _ = sc.restate(raw, t, sc.readings[t])
+        assert not rej.any()
+        o = sc.tick(p, t, sc.readings[t])
+        err = np.abs(o["measured"] - ref).max()
+        print("tick", t, "measured error", err)
+        worst, moved = max(worst, err), max(moved, np.abs(ref - unf).max())
+        assert err <= 1e-12, (t, err)
+        assert o["feedback_fail"].sum() == 0
+        sides |= set(int(s) for s in sn.stance_side(t, sc.phase0, ST))
+    assert (sides == {0, 1} or B == 1) and moved > 1e-4          # the filtered state is not the raw one: a mis-wired filter would show
+
+
+@pytest.mark.gpu
+def test_a_replaced_call_advances_the_filters_once(wca):
+    """(5) On ticks 2 and 5 the handle first gets different, finite readings and then the real ones: every download is bit for bit that
+    of a handle that only ever got the real ones."""
+    B, T = 6, 8
+    sc = Scene(wca, B, T, False)
+    a, b = sc.pipe(ALL), sc.pipe(ALL)
+    rng = np.random.default_rng(8)
+    for t in range(T):
+        oa = sc.tick(a, t, sc.readings[t])
+        if t in (2, 5):
+            q, dq, wl, wr = sc.readings[t]
+            b.set_sensor_feedback_host(q + 0.02, dq + rng.normal(size=dq.shape), 0.5 * wl, 1.5 * wr)
+        ob = sc.tick(b, t, sc.readings[t])
+        _same_bits(oa, ob)
+    assert ob["feedback_fail"].sum() == 0
+
+
+@pytest.mark.gpu
+def test_plain_form_ticks_hold_the_filters(wca):
+    """(6) Ticks 3 and 4 go through set_feedback_host (fed the unfiltered restatement of their readings), and on tick 6 a plain call
+    replaces a sensor call before the run: the sensor-fed ticks agree to 1e-12 with a restatement that never saw those three samples."""
+    B, T = 6, 9
+    sc = Scene(wca, B, T, False)
+    p, f = sc.pipe(ALL), sc.restatement(ALL)
+    for t in range(T):
+        r = sc.readings[t]
+        if t in (3, 4, 6):
+            m, _ = sn.evaluate_batch(sc.model, t, sc.phase0, ST, sc.d["state0"], *r, OMEGA)
+            if t == 6:
+                p.set_sensor_feedback_host(*r)               # computed, then replaced: nothing of it is committed
+            o = sc.tick(p, t, r, form="plain", m=m)
+            assert np.array_equal(o["measured"], m)
+            continue
+        ref, rej = sc.restate(f, t, r)
+        o = sc.tick(p, t, r)
+        err = np.abs(o["measured"] - ref).max()
+        print("tick", t, "measured error", err)
+        assert not rej.any() and err <= 1e-12, (t, err)
+    assert o["feedback_fail"].sum() == 0
+
+
+@pytest.mark.gpu
+def test_rejection_and_isolation(wca):
+    """(7) B = 6, all filters on, both feet at a steady ~150 N.
+    (a) robot 1: a NaN joint velocity on tick 2 - rejected and stopped, nothing of it in any state.
+    (b) robot 4: raw fz = 0 on both feet on tick 3.  The filtered total stays far above 0.1 (about 0.76 of the steady value after one zero
+        sample at 10 Hz / 10 ms): ACCEPTED, where a handle with the wrench filter off REJECTS the same readings.
+    (c) robot 5: a normal force of 0.049 N on both feet on every tick, a filtered total below 0.1 from tick 0: rejected on every call and
+        stopped from tick 0, its measured state the uploaded one throughout.  (The issue that asked for this test wrote fz = 0.05: in
+        binary64 0.05 + 0.05 == 0.1 exactly, which PASSES totalZ >= 0.1 - with or without filters.  0.049 is the value that does what
+        the case is there for.)
+    Every other robot is bit for bit what it is in a run where robots 1 and 5 had clean readings."""
+    B, T = 6, 6
+    sc = Scene(wca, B, T, False)
+    rng = np.random.default_rng(4)
+    clean = []
+    for t in range(T):
+        q, dq, _, _ = sc.readings[t]
+        wl, wr = sfh.wrenches(rng, B, left_fz=150.0 + rng.normal(size=B), right_fz=150.0 + rng.normal(size=B))
+        if t == 3:
+            wl[4, 2] = wr[4, 2] = 0.0
+        clean.append((q, dq, wl, wr))
+    spoiled = []
+    for t, (q, dq, wl, wr) in enumerate(clean):
+        dq, wl, wr = dq.copy(), wl.copy(), wr.copy()
+        if t == 2:
+            dq[1, 7] = np.nan
+        wl[5, 2] = wr[5, 2] = 0.049
+        spoiled.append((q, dq, wl, wr))
+    base, bad, nowf = sc.pipe(ALL), sc.pipe(ALL), sc.pipe(dict(joint_velocity=10.0, com=10.0))
+    f = sc.restatement(ALL)
+    others = np.array([0, 2, 3, 4])
+    m0 = np.concatenate([sc.d["dcm0"], sc.d["com0"], sc.d["u_init"]], 1)
+    for t in range(T):
+        ob, ox, on = sc.tick(base, t, clean[t]), sc.tick(bad, t, spoiled[t]), sc.tick(nowf, t, spoiled[t])
+        _same_bits(ob, ox, rows=others)
+        ref, rej = sc.restate(f, t, spoiled[t])
+        assert list(np.nonzero(rej)[0]) == ([1, 5] if t == 2 else [5])
+        ok = ~rej & (ox["ik_fail"] == 0)
+        assert np.abs(ox["measured"][ok] - ref[ok]).max() <= 1e-12
+        assert np.array_equal(ox["measured"][5], m0[5])
+        assert ox["feedback_fail"][5] == t + 1 and ox["ik_fail"][5] == t + 2
+        assert on["feedback_fail"][4] == (1 if t >= 3 else 0)                       # the unfiltered forces: rejected on tick 3
+    assert list(ox["feedback_fail"]) == [0, 1, 0, 0, 0, T] and ob["feedback_fail"].sum() == 0
+    assert list(ox["ik_fail"]) == [0, T - 2 + 1, 0, 0, 0, T + 1] and ob["ik_fail"].sum() == 0
+    assert (ox["dq_log"][2:, 1] == 0).all() and np.abs(ox["dq_log"][1, 1]).max() > 0 and (ox["dq_log"][:, 5] == 0).all()
+    assert on["ik_fail"][4] == T - 3 + 1 and (on["dq_log"][3:, 4] == 0).all() and np.abs(ox["dq_log"][3:, 4]).max() > 0
+    assert np.isfinite(ox["measured"]).all() and np.isfinite(ox["q_des"]).all()
+
+
+@pytest.mark.gpu
+def test_upload_resets_the_filters(wca):
+    """(8) The sequence of (4) with all filters, the same inputs uploaded again, the sequence again: identical bits."""
+    B, T = 6, 12
+    sc = Scene(wca, B, T, False)
+    p = sc.pipe(ALL)
+    runs = []
+    for k in range(2):
+        if k:
+            sc.upload(p)
+        runs.append([sc.tick(p, t, sc.readings[t]) for t in range(T)])
+    for t, (oa, ob) in enumerate(zip(*runs)):      # (an upload rewinds the tick, not the logs: rows beyond tick t are the first run's)
+        _same_bits({k: (v[:t + 1] if k.endswith("_log") else v) for k, v in oa.items()},
+                   {k: (v[:t + 1] if k.endswith("_log") else v) for k, v in ob.items()})
+    assert np.abs(runs[0][-1]["dq_log"]).max() > 1e-3
+
+
+@pytest.mark.gpu
+def test_device_form_equals_host_form(wca):
+    """(9) In a process of its own (torch initialises its HIP runtime first): 6 ticks fed from torch tensors on a non-blocking stream, and
+    alternating with the host form - bit for bit the host form's."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "sensor_filters_device_check.py")], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "sensor filters device ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+CL_B, CL_T = 4, 40
+_CL_CACHE = {}
+
+
+def _closed_loop_case(wca, qs, controller):
+    if controller not in _CL_CACHE:
+        _CL_CACHE[controller] = _closed_loop_case_build(wca, qs, controller)
+    return _CL_CACHE[controller]
+
+
+def _closed_loop_case_build(wca, qs, controller):
+    """The restated streamed walk of (10) with a robot in the loop and all three filters in front of it: readings = the run's own desired
+    joints and previous velocities plus seeded noise (q 0.01, dq 0.05), wrenches that load the feet in contact and put each loaded foot's
+    ZMP at the previous command.  Returns the walk, its stages and the restated run (with its readings and filtered measured states)."""
+    from oracle import tick_spec as ts
+    B, T = CL_B, CL_T
+    model = wca.synth.icub_like_model()
+    kb = wca.synth.synth_walk_kin_batch(B)
+    d = wca.synth.synth_planned_walk_batch(B, T, pt.poses_host(model, kb), kb, horizon=50, yaw_step=(0.03, 0.08))
+    stages = stt.stages_of(d, T)
+    rng = np.random.default_rng(29)
+    qn, dqn = 0.01 * rng.normal(size=(T, B, 23)), 0.05 * rng.normal(size=(T, B, 23))
+    wn = rng.normal(size=(T, 2, B, 6)) * np.array([5.0, 5.0, 2.0, 0.05, 0.05, 0.5])
+
+    def sensors(t, q_des, dq_prev, u_prev):
+        code = (stages["contact"][t].astype(int) & 3) - 1
+        w = []
+        for k, pose in enumerate((stages["left_pose"][t], stages["right_pose"][t])):
+            loaded = code != 1 - k
+            fz = np.where(loaded, np.where(code == 2, 150.0, 300.0) + wn[t, k, :, 2], 0.0)
+            Rm = pose[:, 3:].reshape(B, 3, 3)
+            z = np.einsum("bji,bj->bi", Rm, np.concatenate([u_prev, np.zeros((B, 1))], 1) - pose[:, :3])
+            wf = wn[t, k].copy()
+            wf[:, 2] = fz; wf[:, 3] += z[:, 1] * fz; wf[:, 4] += -z[:, 0] * fz
+            w.append(wf)
+        return q_des + qn[t], dq_prev + dqn[t], w[0], w[1]
+    R = robots.ROBOTS[ROBOT]
+    p = ts.TickParams(horizon=50, k_com=R["k_com"], k_zmp=R["k_zmp"])
+    given = dict(kin_model=model, foot_rect=wca.synth.FOOT_RECT, stages=stages, neck_additional_rotation=ADD_ROT, dcm_controller=controller,
+                 k_dcm=K_DCM)
+    with flt.robot_in_the_loop(flt.SensorFilters(B, TS, d["com0"], **ALL)):
+        loop = ts.run_ticks(p, d, T, _ik_params(wca, qs), sensors=sensors, **given)
+    return d, stages, loop, (p, given)
+
+
+@pytest.mark.parametrize("controller", ["mpc", "reactive"])
+def test_restated_closed_loop_keeps_walking(wca, qs, controller):
+    """(10, on the CPU) With these inputs - T = 40, noise q 0.01 / dq 0.05, all filters at 10 Hz - the restated run itself keeps every robot
+    walking, and the recording of it fed back as fixed `external` arrays reproduces it."""
+    from oracle import tick_spec as ts
+    d, stages, loop, (p, given) = _closed_loop_case(wca, qs, controller)
+    assert (loop["ik_fail"] == 0).all() and (loop["mpc_fail"] == 0).all() and np.isfinite(loop["measured_log"]).all()
+    ref = ts.run_ticks(p, d, CL_T, _ik_params(wca, qs), external=stt.external_of_sensors(loop), **given)
+    for k in ("u0_log", "dq_log", "q_des"):
+        assert np.array_equal(ref[k], loop[k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("controller", ["mpc", "reactive"])
+def test_closed_loop_follows_the_restated_filtered_run(wca, qs, controller):
+    """(10) B = 4, T = 40, a streamed sensor-fed walk with all filters on: fed the restated run's readings, the device's measured state is
+    the helper's filtered one (1e-12) on every tick and the run follows run_ticks(external = those states and the recorded q_meas):
+    u0_log, q_des 1e-9, dq_log 1e-8, the same failure counts, no robot stopped."""
+    from oracle import tick_spec as ts
+    B, T = CL_B, CL_T
+    d, stages, loop, (p, given) = _closed_loop_case(wca, qs, controller)
+    model = wca.synth.icub_like_model()
+    f = flt.SensorFilters(B, TS, d["com0"], **ALL)
+    restated = np.stack([f.step_stages(model, stages, t, *loop["readings"][t], OMEGA)[0] for t in range(T)])
+    ext = dict(dcm=restated[:, :, 0:2], com=restated[:, :, 2:4], zmp=restated[:, :, 4:6], q=np.stack([r[0] for r in loop["readings"]]))
+    ref = ts.run_ticks(p, d, T, _ik_params(wca, qs), external=ext, **given)
+    assert (ref["ik_fail"] == 0).all() and (ref["mpc_fail"] == 0).all()
+    pipe = _pipe(wca, B, T, ALL, streamed=True, controller=controller)
+    pipe.upload({k: d[k] for k in ("ref_traj", "state0", "q0", "dcm0", "com0", "u_init")})      # (the DCM velocity: the forward difference, as in run_ticks)
+    worst = 0.0
+    for t in range(T):
+        pipe.set_desired_host(*_stage_opt(stages, t))
+        pipe.set_sensor_feedback_host(*loop["readings"][t])
+        pipe.run(1)
+        worst = max(worst, np.abs(pipe.download()["measured"] - restated[t]).max())
+    print("measured error", worst)
+    assert worst <= 1e-12
+    out = pipe.download()
+    assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"]) and out["feedback_fail"].sum() == 0
+    for k, tol in (("u0_log", 1e-9), ("dq_log", 1e-8), ("q_des", 1e-9)):
+        err = np.abs(out[k] - ref[k]).max()
+        print(k, err)
+        assert err <= tol, (k, err)
+    assert (out["ik_fail"] == 0).all() and np.abs(out["dq_log"]).max() > 1e-3
+
+
+def _stage_opt(stages, t):
+    return tuple(stages[k][t] for k in ("left_pose", "right_pose", "left_twist", "right_twist", "contact")) + \
+           (stages["com_height"][t] if "com_height" in stages else None, stages["com_height_vel"][t] if "com_height_vel" in stages else None)
+
+
+@pytest.mark.gpu
+def test_info_reports_the_mask_and_zero_is_the_unfiltered_handle(wca):
+    """(11) info().sensor_filters is the mask of the filters taken; all three at 0 reports 0 and the handle is bit for bit one created
+    without the argument (the unfiltered kernel); the refusals of create through the binding."""
+    B, T = 6, 4
+    sc = Scene(wca, B, T, False)
+    for case, filters in CASES.items():
+        assert sc.pipe(filters).info()["sensor_filters"] == MASK[case]
+    assert sc.pipe(dict(joint_velocity=5.0, com=20.0)).info()["sensor_filters"] == 5
+    zero, none = sc.pipe(dict(joint_velocity=0.0, wrench=0.0, com=0.0)), sc.pipe(None)
+    assert zero.info()["sensor_filters"] == 0 and none.info()["sensor_filters"] == 0
+    for t in range(T):
+        _same_bits(sc.tick(zero, t, sc.readings[t]), sc.tick(none, t, sc.readings[t]))
+    kin = wca.KinModel(wca.synth.icub_like_model())
+    with pytest.raises(wca.WcqpError, match=r"\(-2\)"):          # the internal plant
+        wca.TickPipeline(B, T, wca.MpcSolver(), _ik_solver(wca), kin=kin, sensor_filters=dict(wrench=10.0))
+    with pytest.raises(wca.WcqpError, match=r"\(-2\)"):          # no per-tick kinematics
+        wca.TickPipeline(B, T, wca.MpcSolver(), wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=0.45), external_feedback=True,
+                         sensor_filters=dict(com=10.0))

@@ -171,7 +171,8 @@ class TickParams(C.Structure):
                 ("dcm_controller", C.c_int32), ("k_dcm", C.c_double),
                 ("zmp_gain_scheduling", C.c_int32), ("k_com_stance", C.c_double), ("k_zmp_stance", C.c_double), ("zmp_smoothing_time", C.c_double),
                 ("planned_trajectories", C.c_int32), ("neck_additional_rotation", C.c_double * 9),
-                ("streamed_trajectories", C.c_int32)]
+                ("streamed_trajectories", C.c_int32),
+                ("joint_velocity_cut_frequency", C.c_double), ("wrench_cut_frequency", C.c_double), ("com_cut_frequency", C.c_double)]
 
 
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
@@ -180,7 +181,11 @@ KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1
 
 class TickInfo(C.Structure):
     _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32),
-                ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32), ("streamed_trajectories", C.c_int32)]
+                ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32), ("streamed_trajectories", C.c_int32),
+                ("sensor_filters", C.c_int32)]
+
+
+SENSOR_FILTERS = ("joint_velocity", "wrench", "com")      # bit k of wcqp_tick_info.sensor_filters
 
 
 class TickDesired(C.Structure):
@@ -469,7 +474,8 @@ class TickPipeline:
                  ticks_per_launch: int = 0, logger_ticks: int = 0, external_feedback: bool = False,
                  dcm_controller: str = "mpc", k_dcm: Optional[float] = None, zmp_gain_scheduling: bool = False,
                  k_com_stance: Optional[float] = None, k_zmp_stance: Optional[float] = None, zmp_smoothing_time: Optional[float] = None,
-                 planned_trajectories: bool = False, neck_additional_rotation=None, streamed_trajectories: bool = False):
+                 planned_trajectories: bool = False, neck_additional_rotation=None, streamed_trajectories: bool = False,
+                 sensor_filters: Optional[dict] = None):
         """kin: a KinModel -> per-tick kinematics (Jacobians, actual poses and hull rows rebuilt every tick from the
         integrated joint state with the base anchored at the stance foot; upload() then ignores J_* / hull_tab_*).
         dcm_controller: "mpc" (the DCM-MPC, the reference's use_mpc 1) or "reactive" (WalkingDCMReactiveController, the
@@ -479,7 +485,18 @@ class TickPipeline:
         planned_trajectories: every tick follows the planner's feet, twists, contact flags and CoM height (upload(left_traj=...)) instead of
         the synthetic gait; needs kin (the FUSED hand-off) and neck_additional_rotation (additional_rotation of qpInverseKinematics.ini, 3 x 3).
         streamed_trajectories (with external_feedback): every tick takes its desired stage from the set_desired_host / set_desired_device call
-        in front of it - per tick set_desired -> set_sensor_feedback (or set_feedback) -> run(1); needs kin and neck_additional_rotation too."""
+        in front of it - per tick set_desired -> set_sensor_feedback (or set_feedback) -> run(1); needs kin and neck_additional_rotation too.
+        sensor_filters: dict(joint_velocity=, wrench=, com=) - cut frequencies in Hz of the low-pass filters set_sensor_feedback_* applies
+        (joint_velocity_cut_frequency / wrench_cut_frequency of robotControl.ini, cut_frequency of forwardKinematics.ini); a missing key or
+        0 leaves that filter off.  Needs external_feedback and kin."""
+        cuts = dict.fromkeys(SENSOR_FILTERS, 0.0)
+        for k, v in (sensor_filters or {}).items():
+            if k not in cuts:
+                raise ValueError(f"sensor_filters: unknown key {k!r} (one of {', '.join(SENSOR_FILTERS)})")
+            v = float(v)
+            if not np.isfinite(v) or v < 0.0:
+                raise ValueError(f"sensor_filters[{k!r}] must be a finite cut frequency >= 0 Hz, not {v!r}")
+            cuts[k] = v
         if dcm_controller not in ("mpc", "reactive"):
             raise ValueError(f"dcm_controller must be 'mpc' or 'reactive', not {dcm_controller!r}")
         self.reactive = dcm_controller == "reactive"
@@ -521,7 +538,7 @@ class TickPipeline:
                                  float(k_dcm) if k_dcm is not None else 0.0, int(self.gain_sched),
                                  float(k_com_stance) if self.gain_sched else 0.0, float(k_zmp_stance) if self.gain_sched else 0.0,
                                  float(zmp_smoothing_time) if self.gain_sched else 0.0, int(self.planned), (C.c_double * 9)(*neck),
-                                 int(self.streamed))
+                                 int(self.streamed), *(cuts[k] for k in SENSOR_FILTERS))
         self._h = C.c_void_p()
         check(lib().wcqp_tick_create(C.byref(self.params), C.byref(self._h)), "wcqp_tick_create")
         self._keep = None
@@ -580,14 +597,16 @@ class TickPipeline:
 
     def info(self) -> dict:
         """The form the handle took (wcqp_tick_get_info): kin_handoff ("fused", "compact", "dense" or None without kinematics),
-        ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick, zmp_gain_scheduling (bool), planned_trajectories (bool)."""
+        ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick, zmp_gain_scheduling (bool), planned_trajectories (bool),
+        streamed_trajectories (bool), sensor_filters (the mask: bit 0 joint velocity, bit 1 wrench, bit 2 CoM)."""
         i = TickInfo()
         check(lib().wcqp_tick_get_info(self._h, C.byref(i)), "wcqp_tick_get_info")
         return dict(kin_handoff={KIN_HANDOFF_NONE: None, KIN_HANDOFF_FUSED: "fused", KIN_HANDOFF_DENSE: "dense",
                                  KIN_HANDOFF_COMPACT: "compact"}[i.kin_handoff],
                     ticks_per_launch=int(i.ticks_per_launch), dcm_controller="reactive" if i.dcm_controller == TICK_DCM_REACTIVE else "mpc",
                     launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling),
-                    planned_trajectories=bool(i.planned_trajectories), streamed_trajectories=bool(i.streamed_trajectories))
+                    planned_trajectories=bool(i.planned_trajectories), streamed_trajectories=bool(i.streamed_trajectories),
+                    sensor_filters=int(i.sensor_filters))
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")

@@ -27,7 +27,14 @@ __device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_ca
 // One robot per 16 lanes, four per wave, one wave per workgroup.
 // PL (streamed trajectories, wcqp_tick_set_desired_*): the stance side is the fixed-frame bit of the stage the caller handed over for tick t
 // and the anchor that stage's desired sole pose (the robot's record, tick_device.h: kPlanRec) - what tick t's own kinematics take
-template <bool PL>
+// FILT (a cut frequency > 0, wcqp_tick_params): the reference's first-order low-pass filters on the joint velocities, on fz tx ty of both
+// wrenches and on the CoM position and velocity (sensors.h: lowpass_coeffs, the record layout).  The state of the last RUN tick is read
+// from a.filt_src with the sensor inputs - in flight under the kinematics - and this tick's goes to a.filt_dst, the handle's other slot: a
+// second call for the same tick starts from the same state.  Lane j owns the state of its joints j and 16 + j, lanes 0 .. 5 write one
+// wrench component each, lanes 0 / 1 their axis of the CoM.  The rejection is known before the kinematics (finiteness of the RAW readings,
+// the total of the FILTERED normal forces), so the joint and wrench records are stored there, while their previous values are still in
+// registers: a rejected robot's record is carried over unchanged - its filters hold - and nothing non-finite ever enters one.
+template <bool PL, bool FILT>
 __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
     using namespace wcqp_kin;
     __shared__ __attribute__((aligned(16))) double kmodel[kKinTabSize];
@@ -51,7 +58,41 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
     // what the ZMP reads of the two wrenches - fz, tx, ty - on every lane, in flight with the rest (the same addresses across the row)
     const double* wli = a.wl + i * 6;
     const double* wri = a.wr + i * 6;
-    const double fzL = wli[2], txL = wli[3], tyL = wli[4], fzR = wri[2], txR = wri[3], tyR = wri[4];
+    double fzL = wli[2], txL = wli[3], tyL = wli[4], fzR = wri[2], txR = wri[3], tyR = wri[4];
+    double dqf0 = dq0, dqf1 = dq1;                   // what v_com is formed with
+    double2 sc_p = make_double2(0.0, 0.0), sc_v = sc_p;      // FILT: {u_prev, y_prev} of this lane's axis of the CoM, position and velocity
+    bool rejected = bad;
+    if constexpr (FILT) {
+        const double* fs = a.filt_src + i * kFiltRec;
+        const double2 sd0 = ld2(fs + 2 * cs[0]), sd1 = ld2(fs + 2 * cs[1]);
+        double2 sw[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) sw[k] = ld2(fs + kFiltWrench + 2 * k);
+        sc_p = ld2(fs + kFiltCom + 4 * (j & 1)); sc_v = ld2(fs + kFiltCom + 4 * (j & 1) + 2);
+        const bool first = a.filt_first != 0;
+        if (a.filt_mask & 1) {
+            dqf0 = first ? dq0 : a.fb[0] * (dq0 + sd0.x) + a.fa[0] * sd0.y;
+            dqf1 = (first || !var1) ? dq1 : a.fb[0] * (dq1 + sd1.x) + a.fa[0] * sd1.y;     // (stays 0 on a lane without a second joint)
+        }
+        const double wu[6] = {fzL, txL, tyL, fzR, txR, tyR};
+        double wf[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) wf[k] = ((a.filt_mask & 2) && !first) ? a.fb[1] * (wu[k] + sw[k].x) + a.fa[1] * sw[k].y : wu[k];
+        fzL = wf[0]; txL = wf[1]; tyL = wf[2]; fzR = wf[3]; txR = wf[4]; tyR = wf[5];
+        rejected = bad || !(fzR + fzL >= 0.1);       // evaluateZMP sees the filtered forces only
+        if (live) {
+            double* fd = a.filt_dst + i * kFiltRec;
+            if (a.filt_mask & 1) {
+                st2(fd + 2 * j, rejected ? sd0.x : dq0, rejected ? sd0.y : dqf0);
+                if (var1) st2(fd + 2 * (16 + j), rejected ? sd1.x : dq1, rejected ? sd1.y : dqf1);
+            }
+            if (a.filt_mask & 2) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k)
+                    if (j == k) st2(fd + kFiltWrench + 2 * k, rejected ? sw[k].x : wu[k], rejected ? sw[k].y : wf[k]);
+            }
+        }
+    }
     // the stance side of tick t, as the tick kernel carries it: (t + phase0) % (2 step_ticks) >= step_ticks -> the right sole anchors
     int side;
     if constexpr (PL) {
@@ -242,7 +283,7 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
         const double d3[3] = {(Pe[0] - z * Pb[0] - ms * pw[s_][0]) * iM, (Pe[1] - z * Pb[1] - ms * pw[s_][1]) * iM, (Pe[2] - z * Pb[2] - ms * pw[s_][2]) * iM};
         double lin[3];
         cross3(aw[s_], d3, lin);
-        const double w = s_ == 0 ? dq0 : dq1;        // (0 on a lane without a second joint)
+        const double w = s_ == 0 ? dqf0 : dqf1;      // (0 on a lane without a second joint)
         vx += lin[0] * w; vy += lin[1] * w;
     }
     vx = row_scan(vx); vy = row_scan(vy);
@@ -251,7 +292,7 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
     // ---- the rejection (every lane), lanes 0 / 1: axis j of the DCM and of the ZMP (WalkingModule::evaluateZMP), the write-back
     if (!live) return;
     const double totalZ = fzR + fzL;
-    const bool rejected = bad || !(totalZ >= 0.1);
+    if constexpr (!FILT) rejected = bad || !(totalZ >= 0.1);
     double* qm = a.q_meas + i * kDof;
     if (!rejected) {
         qm[j] = q0;
@@ -270,14 +311,29 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
             const double* hd = a.hand + ((size_t)((a.t - 1) & 1) * a.batch + i) * kHandLen;
             rec[2] = hd[4 + j]; rec[6] = hd[6 + j]; rec[7] = hd[10 + j];
         }
+        if constexpr (FILT) {
+            if (a.filt_mask & 4) {
+                double* fd = a.filt_dst + i * kFiltRec + kFiltCom + 4 * j;
+                st2(fd, sc_p.x, sc_p.y); st2(fd + 2, sc_v.x, sc_v.y);
+            }
+        }
         if (j == 0) {
             a.feedback_fail[i] += 1;
             if (a.ik_fail[i] == 0) a.ik_fail[i] = 1;
         }
         return;
     }
-    const double v = S[S_V + j];
-    const double dcm = ctot[j] + v / a.omega;
+    double v = S[S_V + j], cm = ctot[j];
+    if constexpr (FILT) {
+        // evaluateCoM / evaluateDCM with use_filters: the filtered position goes to the ZMP-CoM controller too (getCoMPosition)
+        if (a.filt_mask & 4) {
+            const double cf = a.fb[2] * (cm + sc_p.x) + a.fa[2] * sc_p.y, vf = a.fb[2] * (v + sc_v.x) + a.fa[2] * sc_v.y;
+            double* fd = a.filt_dst + i * kFiltRec + kFiltCom + 4 * j;
+            st2(fd, cm, cf); st2(fd + 2, v, vf);
+            cm = cf; v = vf;
+        }
+    }
+    const double dcm = cm + v / a.omega;
     const double defL = fzL < 0.001 ? 0.0 : 1.0, defR = fzR < 0.001 ? 0.0 : 1.0;
     // the foot's ZMP in its sole frame (-ty / fz, tx / fz, 0), mapped to world by the sole's measured pose (undefined: the sole origin)
     const double zLx = defL != 0.0 ? -tyL / fzL : 0.0, zLy = defL != 0.0 ? txL / fzL : 0.0;
@@ -287,16 +343,30 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
     const double wL = FL[3 * j] * zLx + FL[3 * j + 1] * zLy + FL[9 + j];
     const double wR = FR[3 * j] * zRx + FR[3 * j + 1] * zRy + FR[9 + j];
     const double zmp = ((fzL * defL) / totalZ) * wL + ((fzR * defR) / totalZ) * wR;
-    rec[2] = ctot[j]; rec[6] = dcm; rec[7] = zmp;
+    rec[2] = cm; rec[6] = dcm; rec[7] = zmp;
 }
 
 }  // namespace
 
 namespace wcqp {
 int sensor_feedback_enqueue(const wcqp_tick::SensorDev& a, hipStream_t stream) {
-    if (a.rec) hipLaunchKernelGGL(tick_sensor_kernel<true>, dim3((unsigned)((a.batch + 3) / 4)), dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL(tick_sensor_kernel<false>, dim3((unsigned)((a.batch + 3) / 4)), dim3(64), 0, stream, a);
+    const dim3 grid((unsigned)((a.batch + 3) / 4));
+    if (a.filt_mask != 0) {
+        if (!a.filt_src || !a.filt_dst) return WCQP_E_INVALID;
+        if (a.rec) hipLaunchKernelGGL((tick_sensor_kernel<true, true>), grid, dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL((tick_sensor_kernel<false, true>), grid, dim3(64), 0, stream, a);
+    } else if (a.rec) {
+        hipLaunchKernelGGL((tick_sensor_kernel<true, false>), grid, dim3(64), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((tick_sensor_kernel<false, false>), grid, dim3(64), 0, stream, a);
+    }
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
+}
+
+void lowpass_coeffs(double cut_hz, double Ts, double* fb, double* fa) {
+    const double tau = 1.0 / (2.0 * M_PI * cut_hz);
+    *fb = Ts / (2.0 * tau + Ts);
+    *fa = (2.0 * tau - Ts) / (2.0 * tau + Ts);
 }
 }  // namespace wcqp

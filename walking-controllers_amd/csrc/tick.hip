@@ -260,6 +260,13 @@ struct wcqp_tick_s {
     double* sens_stage = nullptr;
     long long* feedback_fail = nullptr;
     hipEvent_t run_done = nullptr; bool run_pending = false;
+    // the sensor form's low-pass filters (wcqp_tick_params.*_cut_frequency; sensors.h): two slots of per-robot state [2][B][kFiltRec].  A
+    // sensor call reads slot filt_cur - what the last RUN tick left - and writes the other one; wcqp_tick_run commits it (filt_pending)
+    // when it consumes the tick, so a replaced call advances nothing and a tick fed by the plain form holds the state
+    double* filt_state = nullptr;
+    int filt_mask = 0, filt_cur = 0;
+    bool filt_started = false, filt_pending = false;
+    double filt_fb[3] = {0.0, 0.0, 0.0}, filt_fa[3] = {0.0, 0.0, 0.0};
     std::vector<double> meas0;    // EXTERNAL: dcm0, com0, u_init of the last upload ([B][6]: wcqp_tick_outputs.measured before any tick)
     ZmpSched zg{};                // zmp_gain_scheduling (d.gain_sched): the stance gains, the smoother, its per-robot state
     // the handle's TickDev with the scheduling record behind it (what the scheduled kernels take)
@@ -376,6 +383,14 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
             (params->dcm_controller == WCQP_TICK_DCM_MPC && params->mpc.horizon >= kGainsLdsStages))
             return WCQP_E_UNSUPPORTED;
     }
+    // the sensor form's low-pass filters: a cut frequency > 0 switches one on - where there is a sensor form at all
+    const double cuts[3] = {params->joint_velocity_cut_frequency, params->wrench_cut_frequency, params->com_cut_frequency};
+    int filt_mask = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(cuts[k]) || cuts[k] < 0.0) return WCQP_E_INVALID;
+        if (cuts[k] > 0.0) filt_mask |= 1 << k;
+    }
+    if (filt_mask && (params->plant != WCQP_TICK_PLANT_EXTERNAL || !params->use_kinematics)) return WCQP_E_UNSUPPORTED;
     // the tick kernels address the handle's per-robot arrays with 32-bit offsets (wcqp::fits32; from the parameters alone, before anything
     // touches the device): the trajectories ref_traj / dcm_vel [B][max_ticks + N + 1][2], the two MPC -> IK hand-off records [2][B][kHandLen]
     // and the IK's arrays, J_left / J_right [B][6][29] the widest.  (The planned-trajectory records use 64-bit offsets.)
@@ -467,6 +482,12 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (h->external && h->kin) {
         A_(h->sens_stage, B * (2 * kDof + 12));
         if (rc == WCQP_OK && hipEventCreateWithFlags(&h->run_done, hipEventDisableTiming) != hipSuccess) rc = WCQP_E_HIP;
+        if (filt_mask) {
+            A_(h->filt_state, 2 * B * kFiltRec);
+            h->filt_mask = filt_mask;
+            for (int k = 0; k < 3; ++k)
+                if (filt_mask & (1 << k)) wcqp::lowpass_coeffs(cuts[k], params->mpc.sampling_time, &h->filt_fb[k], &h->filt_fa[k]);
+        }
     }
     if (reactive) { d.reactive = 1; d.k_dcm = params->k_dcm; }
     // the DCM velocity: the reactive controller's input, and with gain scheduling the stance flag's (MPC handles then read it too)
@@ -759,6 +780,17 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     WCQP_HIP_TRY(hipMemset(d.hot_try, 0, B * 8)); WCQP_HIP_TRY(hipMemset(d.hot_hit, 0, B * 8));
     WCQP_HIP_TRY(hipMemset(h->ik_lo, 0, B * 4)); WCQP_HIP_TRY(hipMemset(h->ik_up, 0, B * 4));      // no previous active set at tick 0
     if (h->feedback_fail) WCQP_HIP_TRY(hipMemset(h->feedback_fail, 0, B * 8));
+    if (h->filt_state) {
+        // the filters at rest: the CoM position filter AT com0 and its velocity filter at 0 (the reference starts them at (0, 0, com_height)
+        // and 0 once, WM/src/WalkingForwardKinematics.cpp:153-160: its robot stands at the origin); the joint-velocity and wrench filters
+        // start at the first reading (RobotHelper::resetFilters), which the first sensor call is told
+        std::vector<double> fs(B * kFiltRec, 0.0);
+        for (size_t i = 0; i < B; ++i)
+            for (int ax = 0; ax < 2; ++ax) fs[i * kFiltRec + kFiltCom + 4 * ax] = fs[i * kFiltRec + kFiltCom + 4 * ax + 1] = in->com0[2 * i + ax];
+        WCQP_HIP_TRY(hipMemcpy(h->filt_state, fs.data(), B * kFiltRec * 8, hipMemcpyHostToDevice));
+        WCQP_HIP_TRY(hipMemset(h->filt_state + B * kFiltRec, 0, B * kFiltRec * 8));
+        h->filt_cur = 0; h->filt_started = false; h->filt_pending = false;
+    }
     if (h->external) {
         h->meas0.resize(B * 6);
         for (size_t i = 0; i < B; ++i)
@@ -844,6 +876,7 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
                        h->feedback_fail, h->ticks_enqueued);
     WCQP_HIP_TRY(hipGetLastError());
     h->feedback_set = true;
+    h->filt_pending = false;      // (this tick supplies the filters no sample: they hold, whatever a replaced sensor call computed)
     return WCQP_OK;
 }
 
@@ -879,9 +912,16 @@ int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, co
     a.mst = d.mst; a.hand = d.hand; a.q_meas = h->q_meas; a.ik_fail = d.ik_fail; a.feedback_fail = h->feedback_fail;
     a.batch = d.batch; a.t = h->ticks_enqueued; a.step_ticks = d.step_ticks; a.kin_rounds = d.kin_rounds; a.omega = d.omega;
     a.rec = h->streamed ? h->st_rec : nullptr;
+    if (h->filt_mask) {
+        const size_t slot = (size_t)d.batch * kFiltRec;
+        a.filt_src = h->filt_state + (size_t)h->filt_cur * slot; a.filt_dst = h->filt_state + (size_t)(h->filt_cur ^ 1) * slot;
+        a.filt_mask = h->filt_mask; a.filt_first = h->filt_started ? 0 : 1;
+        for (int k = 0; k < 3; ++k) { a.fb[k] = h->filt_fb[k]; a.fa[k] = h->filt_fa[k]; }
+    }
     const int rc = wcqp::sensor_feedback_enqueue(a, (hipStream_t)stream);
     if (rc != WCQP_OK) return rc;
     h->feedback_set = true;
+    h->filt_pending = h->filt_mask != 0;
     return WCQP_OK;
 }
 
@@ -975,6 +1015,8 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     guard.armed = false;
     h->feedback_set = false;
     h->desired_set = false;
+    // the tick consumed a sensor reading: what that call wrote is the filters' state from here on
+    if (h->filt_pending) { h->filt_cur ^= 1; h->filt_started = true; h->filt_pending = false; }
     return WCQP_OK;
 }
 
@@ -1039,6 +1081,7 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
     out->zmp_gain_scheduling = d.gain_sched ? 1 : 0;
     out->planned_trajectories = h->planned ? 1 : 0;
     out->streamed_trajectories = h->streamed ? 1 : 0;
+    out->sensor_filters = h->filt_mask;
     // a kinematics launch unless fused; then the skewed kernel (1), MPC / reactive + the 16-lane kernel (2) or controller, glue, IK, post (4)
     out->launches_per_tick = (h->kin && !d.kin_fused ? 1 : 0) + (h->form == TickForm::SKEWED ? 1 : h->form == TickForm::MPC_IK16 ? 2 : 4);
     return WCQP_OK;
