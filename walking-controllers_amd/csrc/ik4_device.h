@@ -145,8 +145,8 @@ __device__ __forceinline__ void swap16(double& a, double& b) {
     a = __hiloint2double((int)h[0], (int)l[0]); b = __hiloint2double((int)h[1], (int)l[1]);
 }
 
-__device__ __forceinline__ void st2(double* p, double a, double b) { *reinterpret_cast<double2*>(p) = make_double2(a, b); }
-__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
+using wcqp_kin::st2;
+using wcqp_kin::ld2;
 
 // the DCM-MPC of the same robots riding along with their IK (qp_pair_kernel: in workgroups of its own; PAIR: on the IK's lanes)
 struct MpcPairArgs {
@@ -334,8 +334,10 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
             // ================= kinematics phase (wcqp_tick_params.use_kinematics, fused): forward kinematics at the integrated
             // joint state with the base anchored at the stance foot (WalkingFK::evaluateWorldToBaseTransformation,
             // WM/src/WalkingForwardKinematics.cpp:160-256; WM/src/WalkingModule.cpp:715, 396-410) and this lane's two columns of
-            // the four MIXED Jacobians, straight into the registers the row operations read.  Same algebra as
-            // kin_jacobians_kernel (kin.hip), laid out for the IK's 16 lanes per robot: lane j owns joints j and 16 + j.
+            // the four MIXED Jacobians, straight into the registers the row operations read.  The walk itself is kin_device.h's
+            // (walk_*: 16 lanes per robot, lane j owns joints j and 16 + j - the functions the sensor kernel runs at the measured
+            // joints), called step by step on this kernel's LDS map (K_*); what is written out here is the tick's own: the MPC
+            // chain's stash, the anchor, the frame columns, the base-block vectors.
             using namespace wcqp_kin;
             // every register counts across this phase: what the MPC chain of tick t + 1 has loaded is reduced to this lane's share
             // of u0_unc now (its loads were issued first: they have landed when the pose block below has) and its per-axis records
@@ -364,148 +366,31 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
             const int cs[2] = {j, var1 ? col1 : 0};
             double* TW = S + K_TW;
             int kup[2][3], ksub[2];                 // the joints' pointer-jumping links and subtree ends: from the model table in LDS
-#pragma unroll
-            for (int s_ = 0; s_ < 2; ++s_) {
-                const int* ip = reinterpret_cast<const int*>(kmodel + cs[s_] * wcqp_tick::kKinTabJoint + wcqp_tick::kKinTabInts);
-                kup[s_][0] = ip[0]; kup[s_][1] = ip[1]; kup[s_][2] = ip[2]; ksub[s_] = ip[3];
-            }
-            const int kfj = reinterpret_cast<const int*>(kmodel + wcqp_tick::kKinTabRoot + 4)[j < 3 ? j : 0];
+            const int kfj = walk_links<3>(kmodel, j, cs, kup, ksub);
             {
             double Ra[2][9], pa[2][3];
-#pragma unroll
-            for (int s_ = 0; s_ < 2; ++s_) {
-                const double* mt = kmodel + cs[s_] * wcqp_tick::kKinTabJoint;
-                double R0[9], axl[3];
-#pragma unroll
-                for (int k = 0; k < 9; ++k) R0[k] = mt[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { pa[s_][k] = mt[9 + k]; axl[k] = mt[12 + k]; }
-                joint_rotation(R0, axl, s_ == 0 ? q0 : q1, Ra[s_]);
-            }
+            walk_local_frames(kmodel, cs, q0, q1, Ra, pa);
             WCQP_KSTAMP(2);          // joint rotations (sin / cos) done
-            // the tree in base coordinates by pointer jumping (kin.hip): after round r a frame is relative to its 2^(r+1)-th ancestor
-            const int n_rounds = td.kin_rounds;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                if (r >= n_rounds) break;
-#pragma unroll
-                for (int s_ = 0; s_ < 2; ++s_) {
-                    if (s_ == 0 || var1) {
-                        double* Tm = TW + cs[s_] * K_FS;
-#pragma unroll
-                        for (int k = 0; k < 8; k += 2) st2(Tm + k, Ra[s_][k], Ra[s_][k + 1]);
-                        st2(Tm + 8, Ra[s_][8], pa[s_][0]); st2(Tm + 10, pa[s_][1], pa[s_][2]);
-                    }
-                }
-                wcqp::wave_lds_fence();
-#pragma unroll
-                for (int s_ = 0; s_ < 2; ++s_) {
-                    const int u = kup[s_][r];
-                    if (u >= 0 && (s_ == 0 || var1)) {
-                        const double* T = TW + u * K_FS;
-                        double Rp[9], pp[3], Rn[9], pn[3];
-#pragma unroll
-                        for (int k = 0; k < 9; ++k) Rp[k] = T[k];
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) pp[k] = T[9 + k];
-                        frame_mul(Rp, pp, Ra[s_], pa[s_], Rn, pn);
-#pragma unroll
-                        for (int k = 0; k < 9; ++k) Ra[s_][k] = Rn[k];
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) pa[s_][k] = pn[k];
-                    }
-                }
-                wcqp::wave_lds_fence();
+            walk_tree_to_base<K_FS>(TW, cs, var1, kup, td.kin_rounds, Ra, pa);
             }
-#pragma unroll
-            for (int s_ = 0; s_ < 2; ++s_) {
-                if (s_ == 0 || var1) {
-                    double* Tm = TW + cs[s_] * K_FS;
-#pragma unroll
-                    for (int k = 0; k < 8; k += 2) st2(Tm + k, Ra[s_][k], Ra[s_][k + 1]);
-                    st2(Tm + 8, Ra[s_][8], pa[s_][0]); st2(Tm + 10, pa[s_][1], pa[s_][2]);
-                }
-            }
-            }
-            wcqp::wave_lds_fence();
             WCQP_KSTAMP(3);          // pointer jumping done, frames stored
             // attached frames (left sole, right sole, neck) in base coordinates: lanes 0..2
-            const int fi = j < 3 ? j : 0;
             double Rf[9], pf[3];
-            {
-                const double* T = TW + kfj * K_FS;
-                const double* ft = kmodel + wcqp_tick::kKinTabFrames + fi * 12;
-                double Rj[9], pj[3], fR[9], fp[3];
-#pragma unroll
-                for (int k = 0; k < 9; ++k) { Rj[k] = T[k]; fR[k] = ft[k]; }
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { pj[k] = T[9 + k]; fp[k] = ft[9 + k]; }
-                frame_mul(Rj, pj, fR, fp, Rf, pf);
-                if (j < 3) {
-                    double* F = S + K_FRB + j * 12;
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) F[k] = Rf[k];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) F[9 + k] = pf[k];
-                }
-            }
-            wcqp::wave_lds_fence();
+            walk_attached_frames<K_FS, 3>(kmodel, TW, S + K_FRB, j, kfj, Rf, pf);
             WCQP_KSTAMP(4);          // attached frames in base coordinates
-            // base pose from the anchor foot: world_T_base = world_T_sole,desired * (base_T_sole)^-1
             double pb[3], Rb[9];
             {
-                const double* Fs = S + K_FRB + side * 12;
-                double Rs[9], ps[3], d3[3], sdp[3], sdR[9];
+                double sdp[3], sdR[9];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) sdp[k] = S[k_sd(k)];
 #pragma unroll
                 for (int k = 0; k < 9; ++k) sdR[k] = S[k_sd(3 + k)];
-#pragma unroll
-                for (int k = 0; k < 9; ++k) Rs[k] = Fs[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) ps[k] = Fs[9 + k];
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) Rb[3 * r + c] = sdR[3 * r] * Rs[3 * c] + sdR[3 * r + 1] * Rs[3 * c + 1] + sdR[3 * r + 2] * Rs[3 * c + 2];
-                mat3_vec(Rb, ps, d3);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) pb[k] = sdp[k] - d3[k];
+                base_from_anchor(sdp, sdR, S + K_FRB + side * 12, Rb, pb);
             }
-            // attached frames in world coordinates
-            if (j < 3) {
-                double Rg[9], pg[3];
-                frame_mul(Rb, pb, Rf, pf, Rg, pg);
-                double* F = S + K_FR + j * 12;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) F[k] = Rg[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) F[9 + k] = pg[k];
-            }
+            if (j < 3) frame_to_world(Rb, pb, Rf, pf, S + K_FR + j * 12);
             WCQP_KSTAMP(5);          // base pose, attached frames in world coordinates
-            // own joints in world coordinates, their axes, link first moments {m c, m}
             double pw[2][3], aw[2][3], e4[2][4];
-#pragma unroll
-            for (int s_ = 0; s_ < 2; ++s_) {
-                const double* mt = kmodel + cs[s_] * wcqp_tick::kKinTabJoint;
-                double Rw[9], cl[3], Rl[9], pl[3];
-                {   // the joint's frame in base coordinates, back from LDS (not held in registers across the frames / base pose above)
-                    const double* Tm = TW + cs[s_] * K_FS;
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) Rl[k] = Tm[k];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) pl[k] = Tm[9 + k];
-                }
-                frame_mul(Rb, pb, Rl, pl, Rw, pw[s_]);
-                const double axl[3] = {mt[12], mt[13], mt[14]};
-                mat3_vec(Rw, axl, aw[s_]);
-                const double cj[3] = {mt[15], mt[16], mt[17]};
-                const double mj = (s_ == 0 || var1) ? mt[18] : 0.0;
-                mat3_vec(Rw, cj, cl);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) e4[s_][k] = mj * (pw[s_][k] + cl[k]);
-                e4[s_][3] = mj;
-            }
+            walk_joints_to_world<K_FS>(kmodel, TW, cs, var1, Rb, pb, pw, aw, e4);
             wcqp::wave_lds_fence();          // FR is complete; the joint frames are dead: the prefix sums overlay them
             WCQP_KSTAMP(6);          // own joints in world coordinates
             // ---- frame columns: joint c is on the path of at most one of the three frames (compact_offset: kind)
@@ -528,45 +413,15 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 }
             }
             WCQP_KSTAMP(7);          // frame columns
-            // ---- subtree first moments: the joint numbering is depth-first, a subtree is an index range; inclusive prefix sums
-            // over joints 0..15 (slot 0, a DPP row scan) and 16.. (slot 1, offset by the row's total)
-            double* PS = S + K_TW;               // [32][4]
-            {
-                double p0s[4], p1s[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { p0s[k] = row_scan(e4[0][k]); p1s[k] = row_scan(e4[1][k]); }
-                st2(PS + j * 4, p0s[0], p0s[1]); st2(PS + j * 4 + 2, p0s[2], p0s[3]);
-                wcqp::wave_lds_fence();
-                const double2 t01 = ld2(PS + 15 * 4), t23 = ld2(PS + 15 * 4 + 2);
-                st2(PS + (16 + j) * 4, p1s[0] + t01.x, p1s[1] + t01.y); st2(PS + (16 + j) * 4 + 2, p1s[2] + t23.x, p1s[3] + t23.y);
-                wcqp::wave_lds_fence();
-            }
+            double* PS = S + K_TW;               // [32][4]: the subtree prefix sums
+            walk_prefix_sums(PS, j, e4);
             WCQP_KSTAMP(8);          // prefix sums in LDS
-            double tot[4], ctot[3];
-            {
-                const double* rt = kmodel + wcqp_tick::kKinTabRoot;
-                const double rootc[3] = {rt[0], rt[1], rt[2]};
-                const double root_mass = rt[3];
-                double cr[3];
-                mat3_vec(Rb, rootc, cr);
-                const double* Pt = PS + (kDof - 1) * 4;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) tot[k] = Pt[k] + root_mass * (pb[k] + cr[k]);
-                tot[3] = Pt[3] + root_mass;
-            }
-            const double iM = 1.0 / tot[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ctot[k] = tot[k] * iM;
+            double tot[4], ctot[3], iM;
+            walk_com_total(kmodel, PS, Rb, pb, tot, ctot, iM);
 #pragma unroll
             for (int s_ = 0; s_ < 2; ++s_) {
-                const int c = cs[s_];
-                const double* Pe = PS + ksub[s_] * 4;
-                const double* Pb = PS + (c > 0 ? c - 1 : 0) * 4;
-                const double z = c > 0 ? 1.0 : 0.0;
-                const double ms = Pe[3] - z * Pb[3];
-                const double d3[3] = {(Pe[0] - z * Pb[0] - ms * pw[s_][0]) * iM, (Pe[1] - z * Pb[1] - ms * pw[s_][1]) * iM, (Pe[2] - z * Pb[2] - ms * pw[s_][2]) * iM};
                 double lin[3];
-                cross3(aw[s_], d3, lin);
+                walk_com_column(PS, cs[s_], ksub[s_], pw[s_], aw[s_], iM, lin);
                 double (&a)[NROWS_IN] = s_ == 0 ? a0 : a1;
                 const double mv = (s_ == 0 || var1) ? 1.0 : 0.0;
 #pragma unroll

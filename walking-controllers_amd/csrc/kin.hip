@@ -13,7 +13,9 @@
 // Layout: 32 lanes per instance (two per wave64); lane i owns COLUMN i of every Jacobian (0..5 base,
 // 6 + j joint j), so every output row is one coalesced 232-byte segment.  The tree is composed by pointer
 // jumping through LDS (ceil(log2 depth) rounds in which every joint lane works), subtree first moments are
-// differences of a prefix sum over the lanes when the joint numbering is depth-first.
+// differences of a prefix sum over the lanes when the joint numbering is depth-first.  What it does per slot - a frame in LDS,
+// a pointer-jumping composition, an attached frame, the base pose from the anchor sole - are the leaves of kin_device.h, which
+// the 16-lane walk of the tick and sensor kernels is built from as well.
 // HBM-bound by its output: 280 B in, 4464 B out per instance.
 #include <cmath>
 #include <cstring>
@@ -141,47 +143,19 @@ void kin_jacobians_kernel(const KinDev* __restrict__ md, KinShape shp, int batch
 #pragma unroll
     for (int r = 0; r < kMaxRounds; ++r) {
         if (r >= shp.n_rounds) break;
-        if (is_joint) {
-#pragma unroll
-            for (int k = 0; k < 8; k += 2) *reinterpret_cast<double2*>(Tm + k) = make_double2(Ra[k], Ra[k + 1]);
-            *reinterpret_cast<double2*>(Tm + 8) = make_double2(Ra[8], pa[0]);
-            *reinterpret_cast<double2*>(Tm + 10) = make_double2(pa[1], pa[2]);
-        }
+        if (is_joint) frame_store(Tm, Ra, pa);
         wcqp::wave_lds_fence();
         const int u = up[r];
-        if (is_joint && u >= 0) {
-            const double* T = S + OFF_TW + u * 12;
-            double Rp[9], pp[3], Rn[9], pn[3];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) Rp[k] = T[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pp[k] = T[9 + k];
-            frame_mul(Rp, pp, Ra, pa, Rn, pn);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) Ra[k] = Rn[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pa[k] = pn[k];
-        }
+        if (is_joint && u >= 0) frame_jump(S + OFF_TW + u * 12, Ra, pa);
         wcqp::wave_lds_fence();               // every lane has read: the frames may be overwritten
     }
-    if (is_joint) {
-#pragma unroll
-        for (int k = 0; k < 8; k += 2) *reinterpret_cast<double2*>(Tm + k) = make_double2(Ra[k], Ra[k + 1]);
-        *reinterpret_cast<double2*>(Tm + 8) = make_double2(Ra[8], pa[0]);
-        *reinterpret_cast<double2*>(Tm + 10) = make_double2(pa[1], pa[2]);
-    }
+    if (is_joint) frame_store(Tm, Ra, pa);
     wcqp::wave_lds_fence();
     // attached frames (lanes 0..2), base coordinates
     WCQP_KSTAMP(3);
     double Rf[9], pf[3];
     {
-        const double* T = S + OFF_TW + jfi * 12;
-        double Rj[9], pj[3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rj[k] = T[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) pj[k] = T[9 + k];
-        frame_mul(Rj, pj, fR, fp, Rf, pf);
+        attached_frame(S + OFF_TW + jfi * 12, fR, fp, Rf, pf);
         if (i < 3) {
             double* F = S + OFF_FRB + i * 12;
 #pragma unroll
@@ -194,7 +168,8 @@ void kin_jacobians_kernel(const KinDev* __restrict__ md, KinShape shp, int batch
     // base pose
     double pb[3], Rb[9];
     if constexpr (TICK) {
-        // anchor foot: world_T_base = world_T_sole,desired * (base_T_sole)^-1
+        // anchor foot: world_T_base = world_T_sole,desired * (base_T_sole)^-1   (kin_device.h: base_from_anchor, written out here: the call
+        // reads the desired pose first and moves the TICK kernels' VGPR figures)
         const double* sd = S + OFF_SD + side * 12;       // desired pose of the anchor sole: p (3), R (9)
         const double* Fs = S + OFF_FRB + side * 12;      // its frame in base coordinates: R (9), p (3)
         double Rd[9], Rs[9], ps[3], d[3];
@@ -221,15 +196,7 @@ void kin_jacobians_kernel(const KinDev* __restrict__ md, KinShape shp, int batch
     double Rw[9], pw[3];
     frame_mul(Rb, pb, Ra, pa, Rw, pw);
     // attached frames, world
-    if (i < 3) {
-        double Rg[9], pg[3];
-        frame_mul(Rb, pb, Rf, pf, Rg, pg);
-        double* F = S + OFF_FR + i * 12;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) F[k] = Rg[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) F[9 + k] = pg[k];
-    }
+    if (i < 3) frame_to_world(Rb, pb, Rf, pf, S + OFF_FR + i * 12);
     // joint axis in world (a rotation about the axis leaves it unchanged: R_w * axis)
     double aw[3];
     mat3_vec(Rw, ax, aw);
@@ -249,12 +216,12 @@ void kin_jacobians_kernel(const KinDev* __restrict__ md, KinShape shp, int batch
             cross3(aw, d, lin);
             if (ckind == 3) {                  // neck: the IK keeps the angular rows (setNeckJacobian)
                 crec[3] = aw[0];
-                *reinterpret_cast<double2*>(crec + 4) = make_double2(aw[1], aw[2]);
+                st2(crec + 4, aw[1], aw[2]);
             } else {
                 crec[3] = lin[0];
-                *reinterpret_cast<double2*>(crec + 4) = make_double2(lin[1], lin[2]);
-                *reinterpret_cast<double2*>(crec + 6) = make_double2(aw[0], aw[1]);
-                *reinterpret_cast<double2*>(crec + 8) = make_double2(aw[2], 0.0);
+                st2(crec + 4, lin[1], lin[2]);
+                st2(crec + 6, aw[0], aw[1]);
+                st2(crec + 8, aw[2], 0.0);
             }
         }
         if (live && i < 2) {                   // p_left - p_base, p_right - p_base
@@ -320,8 +287,8 @@ void kin_jacobians_kernel(const KinDev* __restrict__ md, KinShape shp, int batch
 #pragma unroll
         for (int k = 0; k < 4; ++k) ps4[k] = half_scan(e4[k]);
         double* P = S + OFF_PS + i * 4;
-        *reinterpret_cast<double2*>(P) = make_double2(ps4[0], ps4[1]);
-        *reinterpret_cast<double2*>(P + 2) = make_double2(ps4[2], ps4[3]);
+        st2(P, ps4[0], ps4[1]);
+        st2(P + 2, ps4[2], ps4[3]);
         wcqp::wave_lds_fence();
         const double* Pe = S + OFF_PS + (6 + sub_end) * 4;
         const double* Pb = S + OFF_PS + (i > 0 ? i - 1 : 0) * 4;
@@ -366,7 +333,7 @@ void kin_jacobians_kernel(const KinDev* __restrict__ md, KinShape shp, int batch
             const double d[3] = {(mcs[0] - ms * pw[0]) * iM, (mcs[1] - ms * pw[1]) * iM, (mcs[2] - ms * pw[2]) * iM};
             double lin[3];
             cross3(aw, d, lin);
-            *reinterpret_cast<double2*>(crec) = make_double2(lin[0], lin[1]);
+            st2(crec, lin[0], lin[1]);
             crec[2] = lin[2];
             if (ckind == 0) crec[3] = 0.0;
         }

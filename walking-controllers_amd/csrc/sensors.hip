@@ -3,9 +3,10 @@
 //   src/WalkingModule.cpp:1147-1165           updateFKSolver: base anchored at the desired pose of the fixed-frame foot, measured joints
 //   src/WalkingForwardKinematics.cpp:258-337  setInternalRobotState (zero base twist), evaluateCoM, evaluateDCM
 //   src/WalkingModule.cpp:826-878             evaluateZMP
-// The kinematics are the fused tick kernel's (ik4_device.h, JSRC = 2) at the MEASURED joints: the model table in LDS, 16 lanes per robot
-// with lane j owning joints j and 16 + j, pointer jumping for the joint frames, a row scan for the subtree first moments - the same
-// operations in the same order, so that with q_meas = q_des the sole poses and the CoM agree with the tick's own to rounding.  No Jacobian
+// The kinematics are the walk of kin_device.h (walk_*) at the MEASURED joints: the functions the fused tick kernel (ik4_device.h, JSRC = 2)
+// runs at the desired ones - the model table in LDS, 16 lanes per robot with lane j owning joints j and 16 + j, pointer jumping for the
+// joint frames, a row scan for the subtree first moments - here with this kernel's LDS map and two attached frames (the soles).  With
+// q_meas = q_des the sole poses and the CoM therefore agree with the tick's own to rounding: it is one text, not two kept in step.  No Jacobian
 // leaves the kernel: the CoM velocity is the joint block of the MIXED CoM Jacobian times dq_meas, reduced across the robot's row.
 #include "tick_device.h"
 #include "kin_device.h"
@@ -20,9 +21,6 @@ using namespace wcqp_tick;
 constexpr int S_FS = 14, S_TW = 0, S_FRB = 322, S_FR = 346, S_SD = 370, S_V = 382;
 constexpr int S_PER = 392;          // = 8 mod 32: the four robots of a wave sit apart in the banks
 static_assert(kDof * S_FS <= S_FRB && 32 * 4 <= S_FRB && S_V + 2 <= S_PER, "sensor kernel LDS layout");
-
-__device__ __forceinline__ void st2(double* p, double a, double b) { *reinterpret_cast<double2*>(p) = make_double2(a, b); }
-__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
 
 // One robot per 16 lanes, four per wave, one wave per workgroup.
 // PL (streamed trajectories, wcqp_tick_set_desired_*): the stance side is the fixed-frame bit of the stage the caller handed over for tick t
@@ -106,36 +104,21 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
     }
     int kup[2][3], ksub[2];
     __syncthreads();                                 // the model table is in LDS
-#pragma unroll
-    for (int s_ = 0; s_ < 2; ++s_) {
-        const int* ip = reinterpret_cast<const int*>(kmodel + cs[s_] * kKinTabJoint + kKinTabInts);
-        kup[s_][0] = ip[0]; kup[s_][1] = ip[1]; kup[s_][2] = ip[2]; ksub[s_] = ip[3];
-    }
-    const int kfj = reinterpret_cast<const int*>(kmodel + kKinTabRoot + 4)[j < 2 ? j : 0];
+    // the walk of kin_device.h - the fused tick kernel's (ik4_device.h, JSRC = 2) - at the measured joints, on this kernel's LDS map
+    const int kfj = walk_links<2>(kmodel, j, cs, kup, ksub);
     double* TW = S + S_TW;
     {
         double Ra[2][9], pa[2][3];
-#pragma unroll
-        for (int s_ = 0; s_ < 2; ++s_) {
-            const double* mt = kmodel + cs[s_] * kKinTabJoint;
-            double R0[9], axl[3];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) R0[k] = mt[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { pa[s_][k] = mt[9 + k]; axl[k] = mt[12 + k]; }
-            joint_rotation(R0, axl, s_ == 0 ? q0 : q1, Ra[s_]);
-        }
-        // the tree in base coordinates by pointer jumping: after round r a frame is relative to its 2^(r+1)-th ancestor
+        walk_local_frames(kmodel, cs, q0, q1, Ra, pa);
+        // walk_tree_to_base and (below) walk_prefix_sums, written out: called as functions they cost the FILT kernels' register figures
+        // (DESIGN.md 8.2); the rounds' stores are the shared leaf
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             if (r >= a.kin_rounds) break;
 #pragma unroll
             for (int s_ = 0; s_ < 2; ++s_) {
                 if (s_ == 0 || var1) {
-                    double* Tm = TW + cs[s_] * S_FS;
-#pragma unroll
-                    for (int k = 0; k < 8; k += 2) st2(Tm + k, Ra[s_][k], Ra[s_][k + 1]);
-                    st2(Tm + 8, Ra[s_][8], pa[s_][0]); st2(Tm + 10, pa[s_][1], pa[s_][2]);
+                    frame_store(TW + cs[s_] * S_FS, Ra[s_], pa[s_]);
                 }
             }
             wcqp::wave_lds_fence();
@@ -161,89 +144,29 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
 #pragma unroll
         for (int s_ = 0; s_ < 2; ++s_) {
             if (s_ == 0 || var1) {
-                double* Tm = TW + cs[s_] * S_FS;
-#pragma unroll
-                for (int k = 0; k < 8; k += 2) st2(Tm + k, Ra[s_][k], Ra[s_][k + 1]);
-                st2(Tm + 8, Ra[s_][8], pa[s_][0]); st2(Tm + 10, pa[s_][1], pa[s_][2]);
+                frame_store(TW + cs[s_] * S_FS, Ra[s_], pa[s_]);
             }
         }
     }
     wcqp::wave_lds_fence();
     // the two soles in base coordinates: lanes 0 (left) and 1 (right)
     double Rf[9], pf[3];
-    {
-        const double* T = TW + kfj * S_FS;
-        const double* ft = kmodel + kKinTabFrames + (j < 2 ? j : 0) * 12;
-        double Rj[9], pj[3], fR[9], fp[3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { Rj[k] = T[k]; fR[k] = ft[k]; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { pj[k] = T[9 + k]; fp[k] = ft[9 + k]; }
-        frame_mul(Rj, pj, fR, fp, Rf, pf);
-        if (j < 2) {
-            double* F = S + S_FRB + j * 12;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) F[k] = Rf[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) F[9 + k] = pf[k];
-        }
-    }
-    wcqp::wave_lds_fence();
-    // base pose from the anchor sole: world_T_base = world_T_sole,desired * (base_T_sole(q_meas))^-1
+    walk_attached_frames<S_FS, 2>(kmodel, TW, S + S_FRB, j, kfj, Rf, pf);
+    // base pose from the anchor sole's desired pose and its frame at q_meas
     double pb[3], Rb[9];
     {
-        const double* Fs = S + S_FRB + side * 12;
-        double Rs[9], ps[3], d3[3], sdp[3], sdR[9];
+        double sdp[3], sdR[9];
 #pragma unroll
         for (int k = 0; k < 3; ++k) sdp[k] = S[S_SD + k];
 #pragma unroll
         for (int k = 0; k < 9; ++k) sdR[k] = S[S_SD + 3 + k];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rs[k] = Fs[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) ps[k] = Fs[9 + k];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Rb[3 * r + c] = sdR[3 * r] * Rs[3 * c] + sdR[3 * r + 1] * Rs[3 * c + 1] + sdR[3 * r + 2] * Rs[3 * c + 2];
-        mat3_vec(Rb, ps, d3);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) pb[k] = sdp[k] - d3[k];
+        base_from_anchor(sdp, sdR, S + S_FRB + side * 12, Rb, pb);
     }
     // the soles in world coordinates (the MEASURED poses the ZMP is mapped with)
-    if (j < 2) {
-        double Rg[9], pg[3];
-        frame_mul(Rb, pb, Rf, pf, Rg, pg);
-        double* F = S + S_FR + j * 12;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) F[k] = Rg[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) F[9 + k] = pg[k];
-    }
-    // own joints in world coordinates, their axes, link first moments {m c, m}
+    if (j < 2) frame_to_world(Rb, pb, Rf, pf, S + S_FR + j * 12);
     double pw[2][3], aw[2][3], e4[2][4];
-#pragma unroll
-    for (int s_ = 0; s_ < 2; ++s_) {
-        const double* mt = kmodel + cs[s_] * kKinTabJoint;
-        double Rw[9], cl[3], Rl[9], pl[3];
-        const double* Tm = TW + cs[s_] * S_FS;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rl[k] = Tm[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) pl[k] = Tm[9 + k];
-        frame_mul(Rb, pb, Rl, pl, Rw, pw[s_]);
-        const double axl[3] = {mt[12], mt[13], mt[14]};
-        mat3_vec(Rw, axl, aw[s_]);
-        const double cj[3] = {mt[15], mt[16], mt[17]};
-        const double mj = (s_ == 0 || var1) ? mt[18] : 0.0;
-        mat3_vec(Rw, cj, cl);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) e4[s_][k] = mj * (pw[s_][k] + cl[k]);
-        e4[s_][3] = mj;
-    }
+    walk_joints_to_world<S_FS>(kmodel, TW, cs, var1, Rb, pb, pw, aw, e4);
     wcqp::wave_lds_fence();          // the joint frames are dead: the prefix sums overlay them
-    // subtree first moments: the joint numbering is depth-first, a subtree is an index range; inclusive prefix sums over joints 0..15
-    // (slot 0, a DPP row scan) and 16.. (slot 1, offset by the row's total)
     double* PS = S + S_TW;           // [32][4]
     {
         double p0s[4], p1s[4];
@@ -255,34 +178,15 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
         st2(PS + (16 + j) * 4, p1s[0] + t01.x, p1s[1] + t01.y); st2(PS + (16 + j) * 4 + 2, p1s[2] + t23.x, p1s[3] + t23.y);
         wcqp::wave_lds_fence();
     }
-    double tot[4], ctot[3];
-    {
-        const double* rt = kmodel + kKinTabRoot;
-        const double rootc[3] = {rt[0], rt[1], rt[2]};
-        const double root_mass = rt[3];
-        double cr[3];
-        mat3_vec(Rb, rootc, cr);
-        const double* Pt = PS + (kDof - 1) * 4;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) tot[k] = Pt[k] + root_mass * (pb[k] + cr[k]);
-        tot[3] = Pt[3] + root_mass;
-    }
-    const double iM = 1.0 / tot[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ctot[k] = tot[k] * iM;
+    double tot[4], ctot[3], iM;
+    walk_com_total(kmodel, PS, Rb, pb, tot, ctot, iM);
     // v_com = J_com[:, joints] dq_meas (the base twist is zero, WalkingFK::setInternalRobotState): this lane's two CoM columns
     // (a_c x (c_sub(c) - p_c) m_sub(c) / M, as the fused tick forms them) times its two joint velocities, summed over the row
     double vx = 0.0, vy = 0.0;
 #pragma unroll
     for (int s_ = 0; s_ < 2; ++s_) {
-        const int c = cs[s_];
-        const double* Pe = PS + ksub[s_] * 4;
-        const double* Pb = PS + (c > 0 ? c - 1 : 0) * 4;
-        const double z = c > 0 ? 1.0 : 0.0;
-        const double ms = Pe[3] - z * Pb[3];
-        const double d3[3] = {(Pe[0] - z * Pb[0] - ms * pw[s_][0]) * iM, (Pe[1] - z * Pb[1] - ms * pw[s_][1]) * iM, (Pe[2] - z * Pb[2] - ms * pw[s_][2]) * iM};
         double lin[3];
-        cross3(aw[s_], d3, lin);
+        walk_com_column(PS, cs[s_], ksub[s_], pw[s_], aw[s_], iM, lin);
         const double w = s_ == 0 ? dqf0 : dqf1;      // (0 on a lane without a second joint)
         vx += lin[0] * w; vy += lin[1] * w;
     }

@@ -9,10 +9,11 @@
 #include "wcqp_internal.h"
 #include "mpc_device.h"
 #include "hull_device.h"
+#include "kin_device.h"
 
 namespace wcqp_tick {
 
-constexpr int kDof = 23;
+constexpr int kDof = wcqp_kin::kWalkDof;       // 23
 constexpr int kStateLen = WCQP_IK_STATE_LEN;
 
 struct TickDev {
@@ -65,9 +66,7 @@ struct TickDev {
     // ---- kinematics FUSED into the tick kernel (ik4.hip, JSRC = 2): no kinematics launch, no Jacobian hand-off through memory
     // at all - the wave that solves a robot's IK first evaluates its forward kinematics and Jacobian columns, 16 lanes per
     // robot, two joints per lane - and the kernel can then walk through many ticks per launch, like the constant-Jacobian form.
-    // kin_tab: the model as one table of doubles (staged into LDS once per launch): [dof][22] = R0 9 | p0 3 | axis 3 | com 3 |
-    // mass | four ints: the joint's pointer-jumping links of rounds 0..2, the last joint of its subtree | pad; then [3][12]
-    // attached frames R 9 | p 3; then root_com 3, root_mass, three ints: the joints the frames are attached to.
+    // kin_tab: the model as one table of doubles (staged into LDS once per launch; layout: kin_device.h, kKinTab*).
     int kin_fused, kin_rounds;
     wcqp::GPtr<const double> kin_tab;
     // ---- logger rows (wcqp_tick_params.logger_ticks): the 53 values WalkingModule hands its logger per tick
@@ -132,7 +131,8 @@ struct PlanDev {
 struct TickDevPL : TickDevGS { PlanDev pl; };
 constexpr int kHandLen = 14;
 constexpr int kLoggerCols = 53;
-constexpr int kKinTabJoint = 22, kKinTabInts = 19, kKinTabFrames = kKinTabJoint * kDof, kKinTabRoot = kKinTabFrames + 36, kKinTabSize = kKinTabRoot + 6;
+// layout of TickDev::kin_tab: stated beside the walk that reads it (kin_device.h)
+using wcqp_kin::kKinTabJoint; using wcqp_kin::kKinTabInts; using wcqp_kin::kKinTabFrames; using wcqp_kin::kKinTabRoot; using wcqp_kin::kKinTabSize;
 constexpr int kGainsLdsStages = 56;        // fused kinematics: the MPC's gain blocks Gr ((N + 1) x 2 x 2, N <= 55) sit in LDS beside the model (56: what 8 workgroups per CU leave)
 
 // offset (doubles) of joint c's record inside a robot's compact Jacobian block, and the frame the joint belongs to
