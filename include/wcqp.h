@@ -666,6 +666,62 @@ int wcqp_tick_destroy(wcqp_tick_t h);
  * dcm_vel_traj (where it is read), dcm0, com0, u_init or q0 - of any robot: such a value would enter that robot's state on the first tick
  * and never leave.  wcqp_tick_splice_reference refuses a non-finite ref_tail the same way. */
 int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in);
+/* Planned trajectories generated on the device from footsteps.  wcqp_tick_upload_footsteps is wcqp_tick_upload for a handle with
+ * planned_trajectories whose stages the device expands itself, from a few footsteps per robot: it fills the arrays the classic upload
+ * fills (records, DCM reference and velocity, support-polygon sets), rewinds to tick 0 and resets what an upload resets.  The planner
+ * library upstream is not part of the reference: like the minimum-jerk smoother and the low-pass filters, THE PLAN IS THIS BUILD'S OWN
+ * DEFINITION, stated here (tests/helpers/footstep_plan.py restates it in numpy; synth.synth_planned_walk_batch is a special case).
+ *   dT = mpc.sampling_time, omega = sqrt(gravity / com_height), T = max_ticks + N + 1 stages.
+ *   Timeline  stages [0, first_ds) are double support; step k occupies the next ss + ds stages - ss of single support, then ds of double
+ *             support - the last step's double support lasting final_ds stages instead; after that the robot stands.
+ *   Swing     at stage s of the single support, x = (s + 1) / ss, m = 10 x^3 - 15 x^4 + 6 x^5, m' = 30 x^2 (1 - x)^2:
+ *             position = p + (target - p) m + lift 16 x^2 (1 - x)^2 z (the target's z is the foot's own), rotation = Rz(dyaw m) R,
+ *             twist = the analytic derivative / (ss dT), angular part about z only.  The foot lands on the last single-support stage;
+ *             its footprint from the next stage on is exactly the target with rotation Rz(dyaw) R.  A foot may swing twice in a row.
+ *   Flags     bits 0 / 1: left / right in contact; bit 2: the left foot is the fixed frame - the stance foot of the latest single
+ *             support, the left one before the first.
+ *   ZMP       single support: the stance foot's point p_xy + R_2x2 delta.  Double support of n stages, stage u (0-based):
+ *             a + (u + 1) / (n + 1) (b - a), a the previous stance foot's point (the midpoint of both feet's points before the first
+ *             step), b the next stance foot's (the midpoint after the last step).  Standing: the midpoint.
+ *   DCM       xi_t = (xi_{t+1} - (1 - a) zmp_t) / a, a = exp(omega dT), backwards from xi = zmp at the first standing stage - over the
+ *             whole plan, also where it ends past T (a plan cut off by T is simply truncated); dcm_vel = omega (xi - zmp).
+ *   Height    state0[68], velocity 0.  The desired neck orientation is derived per tick, as in every planned handle.
+ *   Sets      the support-polygon rows by the rule of the classic upload: one set at stage 0 and one at every change of contact pair at
+ *             a stage <= max_ticks, built from that stage's desired feet and foot_rect; later stages name the last set.
+ * From `in` it reads state0 (the initial footprints are its desired-foot entries 24..47, the CoM height entry 68), q0, com0 and -
+ * optionally - dcm0 and u_init (NULL: the generated DCM reference and ZMP of stage 0); every trajectory pointer is ignored and may be NULL.
+ * WCQP_E_UNSUPPORTED on a handle without planned_trajectories.  WCQP_E_INVALID, with the handle unchanged (a handle uploaded before keeps
+ * that upload), for a NULL required pointer, n_steps outside 0..K, a side other than 0 / 1, a non-finite value (of a step the robot
+ * takes, of the state0 entries read, q0, com0, dcm0, u_init, lift or the deltas), a tick count below 1 or final_ds_ticks below 0.
+ * Not offered, and refused by construction rather than silently ignored: regenerating from a tick > 0 (the call always rewinds), per-step
+ * timings, device-pointer footsteps. */
+typedef struct wcqp_tick_footsteps {      /* HOST pointers, copied at the call */
+    int32_t max_steps;                    /* K: row length of the per-step arrays, >= 0 */
+    const int32_t* n_steps;               /* [B] 0..K steps robot i takes */
+    const uint8_t* side;                  /* [B][K] foot that swings in step k: 0 left, 1 right */
+    const double*  target;                /* [B][K][3] x, y of the sole's new footprint (world), yaw INCREMENT of the foot [rad] */
+    int32_t first_ds_ticks, ss_ticks, ds_ticks, final_ds_ticks;   /* stages; final_ds_ticks 0 -> ds_ticks */
+    double  lift;                         /* apex height of the swing foot [m] */
+    double  zmp_delta_left[2], zmp_delta_right[2];   /* plannerParams.ini leftZMPDelta / rightZMPDelta, foot frame */
+} wcqp_tick_footsteps;
+int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps);
+/* The plan a planned handle holds, however it was uploaded: n robots from robot0, m stages from stage0, stage-major per robot.
+ * Synchronises.  Every pointer but two works on any planned handle, however it was uploaded.  The two: a non-NULL dcm_vel_traj makes
+ * the call return WCQP_E_UNSUPPORTED on a handle that keeps no velocity (neither the reactive controller nor gain scheduling), and a
+ * non-NULL u_init - this pointer alone - makes it return WCQP_E_UNSUPPORTED on a handle whose plan was uploaded with wcqp_tick_upload
+ * (wcqp_tick_info.plan_generated says which).  WCQP_E_UNSUPPORTED also on a handle without planned_trajectories; WCQP_E_INVALID before
+ * an upload and for a window outside the batch or the T stages.  Only what is asked for is copied: a call without a record-derived
+ * pointer (the feet, twists, contact, heights, hull rows) does not read the records. */
+typedef struct wcqp_tick_plan_window {    /* HOST pointers, any may be NULL */
+    double* left_traj; double* right_traj;     /* [n][m][12] */
+    double* left_twist; double* right_twist;   /* [n][m][6]  */
+    uint8_t* contact;                          /* [n][m]     */
+    double* com_height; double* com_height_vel;   /* [n][m]  */
+    double* ref_traj; double* dcm_vel_traj;    /* [n][m][2]  */
+    double* hull_A; double* hull_b; int32_t* hull_nc;   /* [n][m][8][2], [n][m][8], [n][m]: the support-polygon rows in force at each stage */
+    double* u_init;                            /* [n][2] a generated plan's ZMP of stage 0 (what a NULL u_init of wcqp_tick_upload_footsteps stands for) */
+} wcqp_tick_plan_window;
+int wcqp_tick_get_plan(wcqp_tick_t h, int32_t robot0, int32_t n, int32_t stage0, int32_t m, const wcqp_tick_plan_window* out);
 /* enqueue only; use_graph: hipGraph replays of 8 ticks each, remainder as plain launches - IGNORED (no graph is built) whenever
  * the fused kernel runs several ticks per launch, i.e. for every wcqp_tick_params.ticks_per_launch != 1 including the default 0,
  * which makes a whole call ONE launch: a caller that needs the device back within a bound (another stream's work, a watchdog)
@@ -788,6 +844,8 @@ typedef struct wcqp_tick_info {
     int32_t planned_trajectories;  /* wcqp_tick_params.planned_trajectories as taken (0 / 1)                                */
     int32_t streamed_trajectories; /* wcqp_tick_params.streamed_trajectories as taken (0 / 1)                               */
     int32_t sensor_filters;        /* low-pass filters of the sensor form taken: bit 0 joint velocity, bit 1 wrench, bit 2 CoM      */
+    int32_t plan_generated;        /* 1: the plan in place was generated by wcqp_tick_upload_footsteps; 0: uploaded, or none yet    */
+    double  plan_record_ms;        /* plan_generated: device time of that upload's record pass (events around it) [ms]; else 0      */
 } wcqp_tick_info;
 int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
 

@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host",
+    "wcqp_tick_upload_footsteps", "wcqp_tick_get_plan",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
 )
@@ -182,7 +183,7 @@ KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1
 class TickInfo(C.Structure):
     _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32),
                 ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32), ("streamed_trajectories", C.c_int32),
-                ("sensor_filters", C.c_int32)]
+                ("sensor_filters", C.c_int32), ("plan_generated", C.c_int32), ("plan_record_ms", C.c_double)]
 
 
 SENSOR_FILTERS = ("joint_velocity", "wrench", "com")      # bit k of wcqp_tick_info.sensor_filters
@@ -198,6 +199,24 @@ class TickInputs(C.Structure):
                                           "J_left", "J_right", "J_neck", "J_com", "state0", "swing_twist",
                                           "q0", "dcm0", "com0", "u_init", "dcm_vel_traj",
                                           "left_traj", "right_traj", "left_twist", "right_twist", "contact", "com_height_traj", "com_height_vel")]
+
+
+class TickFootsteps(C.Structure):
+    """wcqp_tick_footsteps: the footsteps wcqp_tick_upload_footsteps expands into a planned handle's stages on the device."""
+    _fields_ = [("max_steps", C.c_int32), ("n_steps", C.c_void_p), ("side", C.c_void_p), ("target", C.c_void_p),
+                ("first_ds_ticks", C.c_int32), ("ss_ticks", C.c_int32), ("ds_ticks", C.c_int32), ("final_ds_ticks", C.c_int32),
+                ("lift", C.c_double), ("zmp_delta_left", C.c_double * 2), ("zmp_delta_right", C.c_double * 2)]
+
+
+PLAN_WINDOW = (("left_traj", (12,), np.float64), ("right_traj", (12,), np.float64), ("left_twist", (6,), np.float64), ("right_twist", (6,), np.float64),
+               ("contact", (), np.uint8), ("com_height", (), np.float64), ("com_height_vel", (), np.float64),
+               ("ref_traj", (2,), np.float64), ("dcm_vel_traj", (2,), np.float64),
+               ("hull_A", (HULL_ROWS, 2), np.float64), ("hull_b", (HULL_ROWS,), np.float64), ("hull_nc", (), np.int32))
+
+
+class TickPlanWindow(C.Structure):
+    """wcqp_tick_plan_window: what wcqp_tick_get_plan fills (PLAN_WINDOW: the [n][m] arrays; u_init [n][2])."""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in PLAN_WINDOW] + [("u_init", C.c_void_p)]
 
 
 class TickOutputs(C.Structure):
@@ -253,6 +272,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_set_desired_device.argtypes = [C.c_void_p, C.POINTER(TickDesired), C.c_void_p]
         L.wcqp_tick_set_desired_host.argtypes = [C.c_void_p, C.POINTER(TickDesired)]
         L.wcqp_tick_get_info.argtypes = [C.c_void_p, C.POINTER(TickInfo)]
+        L.wcqp_tick_upload_footsteps.argtypes = [C.c_void_p, C.POINTER(TickInputs), C.POINTER(TickFootsteps)]
+        L.wcqp_tick_get_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TickPlanWindow)]
         L.wcqp_qp_enqueue_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.POINTER(C.c_int32)]
         L.wcqp_qp_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.c_int32, C.POINTER(C.c_void_p)]
         L.wcqp_qp_plan_enqueue.argtypes = [C.c_void_p, C.c_void_p]
@@ -595,10 +616,48 @@ class TickPipeline:
         ins = TickInputs(**{k: (keep[k].ctypes.data if k in keep else None) for k, _ in TickInputs._fields_})
         check(lib().wcqp_tick_upload(self._h, C.byref(ins)), "wcqp_tick_upload")
 
+    def upload_footsteps(self, data: dict, footsteps: dict):
+        """A planned handle's upload with the stages generated on the device (wcqp_tick_upload_footsteps, which defines the plan).
+        data: state0, q0, com0 and optionally dcm0 / u_init (missing or None: the generated DCM reference and ZMP of stage 0).
+        footsteps: n_steps [B], side [B][K] (0 left, 1 right), target [B][K][3] (x, y, yaw increment), first_ds_ticks, ss_ticks, ds_ticks,
+        final_ds_ticks (0 or missing: ds_ticks), lift, zmp_delta_left, zmp_delta_right - what synth.synth_footstep_walk_batch returns."""
+        if not self.planned:
+            raise ValueError("footsteps were given to a handle created without planned_trajectories=True")
+        keep = {k: _f64(data[k]) for k in ("state0", "q0", "com0")}
+        for k in ("dcm0", "u_init"):
+            if data.get(k) is not None:
+                keep[k] = _f64(data[k])
+        n_steps = np.ascontiguousarray(footsteps["n_steps"], dtype=np.int32)
+        side = np.ascontiguousarray(footsteps["side"], dtype=np.uint8)
+        target = _f64(footsteps["target"])
+        assert n_steps.shape == (self.batch,) and side.ndim == 2 and side.shape[0] == self.batch and target.shape == side.shape + (3,), \
+            (n_steps.shape, side.shape, target.shape)
+        fs = TickFootsteps(side.shape[1], n_steps.ctypes.data, side.ctypes.data if side.size else None, target.ctypes.data if target.size else None,
+                           int(footsteps["first_ds_ticks"]), int(footsteps["ss_ticks"]), int(footsteps["ds_ticks"]), int(footsteps.get("final_ds_ticks", 0)),
+                           float(footsteps["lift"]), (C.c_double * 2)(*footsteps["zmp_delta_left"]), (C.c_double * 2)(*footsteps["zmp_delta_right"]))
+        ins = TickInputs(**{k: (keep[k].ctypes.data if k in keep else None) for k, _ in TickInputs._fields_})
+        check(lib().wcqp_tick_upload_footsteps(self._h, C.byref(ins), C.byref(fs)), "wcqp_tick_upload_footsteps")
+
+    def plan_window(self, robot0: int = 0, n: Optional[int] = None, stage0: int = 0, m: Optional[int] = None) -> dict:
+        """The plan a planned handle holds (wcqp_tick_get_plan): n robots from robot0, m stages from stage0 (None: to the end) - left_traj,
+        right_traj, left_twist, right_twist, contact, com_height, com_height_vel, ref_traj, the support-polygon rows in force per stage
+        (hull_A, hull_b, hull_nc), dcm_vel_traj where the handle keeps it (reactive controller, gain scheduling) and, after
+        upload_footsteps, u_init [n][2], the generated ZMP of stage 0."""
+        T = self.max_ticks + self.params.mpc.horizon + 1
+        n = self.batch - robot0 if n is None else n
+        m = T - stage0 if m is None else m
+        out = {k: np.zeros((max(n, 0), max(m, 0)) + shp, dt) for k, shp, dt in PLAN_WINDOW if k != "dcm_vel_traj" or self.reactive or self.gain_sched}
+        if self.info()["plan_generated"]:
+            out["u_init"] = np.zeros((max(n, 0), 2))
+        win = TickPlanWindow(**{k: v.ctypes.data for k, v in out.items()})
+        check(lib().wcqp_tick_get_plan(self._h, int(robot0), int(n), int(stage0), int(m), C.byref(win)), "wcqp_tick_get_plan")
+        return out
+
     def info(self) -> dict:
         """The form the handle took (wcqp_tick_get_info): kin_handoff ("fused", "compact", "dense" or None without kinematics),
         ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick, zmp_gain_scheduling (bool), planned_trajectories (bool),
-        streamed_trajectories (bool), sensor_filters (the mask: bit 0 joint velocity, bit 1 wrench, bit 2 CoM)."""
+        streamed_trajectories (bool), sensor_filters (the mask: bit 0 joint velocity, bit 1 wrench, bit 2 CoM), plan_generated (bool: the plan
+        in place came from upload_footsteps) and plan_record_ms (the device time of that upload's record pass)."""
         i = TickInfo()
         check(lib().wcqp_tick_get_info(self._h, C.byref(i)), "wcqp_tick_get_info")
         return dict(kin_handoff={KIN_HANDOFF_NONE: None, KIN_HANDOFF_FUSED: "fused", KIN_HANDOFF_DENSE: "dense",
@@ -606,7 +665,7 @@ class TickPipeline:
                     ticks_per_launch=int(i.ticks_per_launch), dcm_controller="reactive" if i.dcm_controller == TICK_DCM_REACTIVE else "mpc",
                     launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling),
                     planned_trajectories=bool(i.planned_trajectories), streamed_trajectories=bool(i.streamed_trajectories),
-                    sensor_filters=int(i.sensor_filters))
+                    sensor_filters=int(i.sensor_filters), plan_generated=bool(i.plan_generated), plan_record_ms=float(i.plan_record_ms))
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")

@@ -1,0 +1,243 @@
+// Planned trajectories generated on the device from per-robot footstep lists (wcqp_tick_upload_footsteps).  include/wcqp.h defines the
+// plan - timeline, swing, flags, ZMP, DCM reference, support-polygon sets - and tests/helpers/footstep_plan.py restates it in numpy; the
+// record layout is tick_device.h's (kPlanRec).  Three kernels per upload, in stream order:
+//   plan_prologue_kernel   one thread per robot, O(K): the footprint chain (plan_gen.h: kFpRec), the ZMP points, the set table
+//   plan_dcm_kernel        one lane per (robot, axis), serial in the stage: the backward DCM recursion, tiles of stages through LDS
+//   plan_record_kernel     one wave per (robot, 64 stages), one lane per stage: the 320-byte records, through LDS, as whole lines
+#include <cmath>
+#include "plan_gen.h"
+
+namespace {
+
+using namespace wcqp_tick;
+
+__device__ __forceinline__ void zmp_point(const double* pose, const double* dl, double* out) {
+    out[0] = pose[0] + (pose[3] * dl[0] + pose[4] * dl[1]);
+    out[1] = pose[1] + (pose[6] * dl[0] + pose[7] * dl[1]);
+}
+
+__global__ void plan_prologue_kernel(PlanGenDev g) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.batch) return;
+    const int n = g.n_steps[i], per = g.ss + g.ds;
+    double fp[kFpPose];
+    for (int k = 0; k < kFpPose; ++k) fp[k] = g.state[(size_t)i * kStateLen + 24 + k];      // desired left sole, desired right sole
+    double* tab = g.table + (size_t)i * (size_t)(g.K + 1) * kFpRec;
+    const size_t rec0 = (size_t)i * (size_t)g.traj_len;
+    int set = g.set_base[i];
+    g.set_at[set] = (long long)(rec0 * kPlanRec); g.set_code[set] = 2; ++set;
+    for (int j = 0; j <= g.K; ++j) {
+        if (j >= 1 && j <= n) {
+            // step j - 1 lands: the swing foot's footprint becomes its target, rotated by the yaw increment about z
+            const int k = j - 1, sw = g.side[(size_t)i * g.K + k];
+            const double* tg = g.target + ((size_t)i * g.K + k) * 3;
+            double* f = fp + 12 * sw;
+            double sn, cs;
+            sincos(tg[2], &sn, &cs);
+            f[0] = tg[0]; f[1] = tg[1];
+            for (int c = 0; c < 3; ++c) {
+                const double r0 = f[3 + c], r1 = f[6 + c];
+                f[3 + c] = cs * r0 - sn * r1;
+                f[6 + c] = sn * r0 + cs * r1;
+            }
+            // its two changes of contact pair (the stance foot alone, both again), where a tick can reach them
+            const int s_k = g.first_ds + k * per;
+            if (s_k <= g.max_ticks) { g.set_at[set] = (long long)((rec0 + s_k) * kPlanRec); g.set_code[set] = 1 - sw; ++set; }
+            if (s_k + g.ss <= g.max_ticks) { g.set_at[set] = (long long)((rec0 + s_k + g.ss) * kPlanRec); g.set_code[set] = 2; ++set; }
+        }
+        double* t = tab + (size_t)j * kFpRec;
+        for (int k = 0; k < kFpPose; ++k) t[k] = fp[k];
+        zmp_point(fp, g.delta[0], t + 24);
+        zmp_point(fp + 12, g.delta[1], t + 26);
+    }
+}
+
+// ---- the DCM reference: xi_t = (xi_{t+1} - (1 - a) zmp_t) / a backwards from xi = zmp at the first standing stage
+constexpr int kDcmRobots = 32, kDcmTile = 32, kDcmRow = 2 * kDcmTile + 2;
+
+__global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) {
+    __shared__ double t_xi[kDcmRobots * kDcmRow];
+    __shared__ double t_vel[kDcmRobots * kDcmRow];
+    const int lane = threadIdx.x, r = lane >> 1, ax = lane & 1;
+    const int i_raw = blockIdx.x * kDcmRobots + r;
+    const bool live = i_raw < g.batch;
+    const int i = live ? i_raw : g.batch - 1;
+    const int n = g.n_steps[i], per = g.ss + g.ds, T = g.traj_len;
+    const int s_end = n > 0 ? g.first_ds + n * per - g.ds + g.final_ds : g.first_ds;      // the first standing stage
+    const double* tab = g.table + (size_t)i * (size_t)(g.K + 1) * kFpRec;
+    const unsigned char* side = g.side + (size_t)i * g.K;
+    const double mid0 = 0.5 * (tab[24 + ax] + tab[26 + ax]);
+    const double mid_n = 0.5 * (tab[(size_t)n * kFpRec + 24 + ax] + tab[(size_t)n * kFpRec + 26 + ax]);
+    int top = s_end > T ? s_end : T;
+    for (int m = 1; m < 64; m <<= 1) { const int o = __shfl_xor(top, m); top = o > top ? o : top; }
+    const double a = g.a, b1 = 1.0 - g.a;
+    double xi = mid_n;
+    int key = -2;                     // the segment za / zb belong to: -1 the first double support, 2 k single support of step k, 2 k + 1 the double support behind it
+    double za = 0.0, zb = 0.0;
+    for (int t = top - 1; t >= 0; --t) {
+        double z;
+        if (t >= s_end) {
+            z = mid_n; xi = mid_n;
+        } else {
+            if (t < g.first_ds) {
+                if (key != -1) { key = -1; za = mid0; zb = n > 0 ? tab[24 + 2 * (1 - side[0]) + ax] : mid0; }
+                z = za + ((double)(t + 1) / (double)(g.first_ds + 1)) * (zb - za);
+            } else {
+                const int rr = t - g.first_ds;
+                int k = rr / per;
+                k = k < n - 1 ? k : n - 1;
+                const int u = rr - k * per;
+                if (u < g.ss) {
+                    if (key != 2 * k) { key = 2 * k; za = tab[(size_t)k * kFpRec + 24 + 2 * (1 - side[k]) + ax]; }
+                    z = za;
+                } else {
+                    if (key != 2 * k + 1) {
+                        key = 2 * k + 1;
+                        const double* e = tab + (size_t)(k + 1) * kFpRec;
+                        za = e[24 + 2 * (1 - side[k]) + ax];
+                        zb = k < n - 1 ? e[24 + 2 * (1 - side[k + 1]) + ax] : 0.5 * (e[24 + ax] + e[26 + ax]);
+                    }
+                    const int nds = k == n - 1 ? g.final_ds : g.ds;
+                    z = za + ((double)(u - g.ss + 1) / (double)(nds + 1)) * (zb - za);
+                }
+            }
+            xi = (xi - b1 * z) / a;
+        }
+        if (t >= T) continue;
+        const int tt = t & (kDcmTile - 1);
+        t_xi[r * kDcmRow + 2 * tt + ax] = xi;
+        t_vel[r * kDcmRow + 2 * tt + ax] = g.omega * (xi - z);
+        if (t == 0 && live) g.zmp0[2 * (size_t)i + ax] = z;
+        if (tt != 0) continue;
+        // stages [t, hi) of the block's robots: each robot's tile is contiguous in HBM, 32 lanes write it 16 bytes each
+        __syncthreads();
+        const int hi = t + kDcmTile < T ? t + kDcmTile : T;
+        const int q = lane & 31;
+        for (int r0 = 0; r0 < kDcmRobots; r0 += 2) {
+            const int ro = r0 + (lane >> 5);
+            const long io = (long)blockIdx.x * kDcmRobots + ro;
+            if (io >= g.batch || t + q >= hi) continue;
+            const size_t w = ((size_t)io * (size_t)T + (size_t)(t + q)) * 2;
+            *reinterpret_cast<double2*>(g.ref + w) = make_double2(t_xi[ro * kDcmRow + 2 * q], t_xi[ro * kDcmRow + 2 * q + 1]);
+            if (g.vel) *reinterpret_cast<double2*>(g.vel + w) = make_double2(t_vel[ro * kDcmRow + 2 * q], t_vel[ro * kDcmRow + 2 * q + 1]);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the records.  A wave takes 64 consecutive stages of one robot - 20 KiB of records, contiguous in HBM and 64-byte aligned (a record
+// is five lines): lane l computes stage s0 + l into row l of an LDS tile (rows of 41 doubles: the 8-byte LDS stores of 16 lanes fall on
+// 16 different bank pairs), then the wave writes the tile out 16 bytes per lane, 1 KiB - sixteen whole lines - per store instruction.
+// The robot's footprints come from its table, the entries the tile's stages touch copied into LDS first: a step lasts two stages or more,
+// so 64 stages touch at most 34 entries.
+constexpr int kRecTile = 64, kRecRow = kPlanRec + 1, kTabMax = kRecTile / 2 + 2;
+
+__global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) {
+    __shared__ double tile[kRecTile * kRecRow];
+    __shared__ double fpt[kTabMax * kFpPose];
+    __shared__ double dyaw[kTabMax];
+    __shared__ int swing[kTabMax];
+    const int lane = threadIdx.x;
+    const size_t i = blockIdx.y;
+    const int T = g.traj_len, s0 = blockIdx.x * kRecTile;
+    const int nvalid = T - s0 < kRecTile ? T - s0 : kRecTile;
+    const int n = g.n_steps[i], per = g.ss + g.ds;
+    // entries j_lo .. j_hi: from the step the first stage lies in (the last step's, once standing: its stance foot is the fixed frame) to the
+    // footprints behind the step the last stage lies in
+    auto step_of = [&](int s) { return s < g.first_ds ? 0 : (s - g.first_ds) / per; };
+    const int last = n > 0 ? n - 1 : 0;
+    int j_lo = step_of(s0);
+    j_lo = j_lo < last ? j_lo : last;
+    int j_hi = step_of(s0 + nvalid - 1) + 1;
+    j_hi = j_hi < n ? j_hi : n;
+    int cnt = j_hi - j_lo + 1;
+    cnt = cnt < kTabMax ? cnt : kTabMax;
+    const double* tab = g.table + (i * (size_t)(g.K + 1) + (size_t)j_lo) * kFpRec;
+    for (int x = lane; x < cnt * kFpPose; x += kRecTile) fpt[x] = tab[(size_t)(x / kFpPose) * kFpRec + x % kFpPose];
+    if (lane < cnt && j_lo + lane < n) {
+        swing[lane] = g.side[i * g.K + j_lo + lane];
+        dyaw[lane] = g.target[(i * g.K + j_lo + lane) * 3 + 2];
+    }
+    __syncthreads();
+    const int s = s0 + lane;
+    if (lane < nvalid) {
+        double* o = tile + lane * kRecRow;
+        int k = -1, u = 0;
+        if (s >= g.first_ds) { k = (s - g.first_ds) / per; u = (s - g.first_ds) - k * per; }
+        const bool swinging = k >= 0 && k < n && u < g.ss;
+        // the footprints in force: after k + 1 landed steps, or - the swing foot still in the air - after k
+        int j = k < 0 ? 0 : (k < n ? k + (swinging ? 0 : 1) : n);
+        j = j - j_lo;
+        j = j < 0 ? 0 : (j < cnt ? j : cnt - 1);
+        const double* f = fpt + j * kFpPose;
+        for (int e = 0; e < kFpPose; ++e) o[kPlanLeft + e] = f[e];
+        for (int e = 0; e < 12; ++e) o[kPlanTwL + e] = 0.0;
+        int flags = 3, fixed = 0;
+        if (k >= 0 && n > 0) { const int kl = k < n ? k : n - 1; fixed = 1 - swing[kl - j_lo < cnt ? kl - j_lo : cnt - 1]; }
+        if (swinging) {
+            const int sw = swing[k - j_lo < cnt ? k - j_lo : cnt - 1];
+            const double dy = dyaw[k - j_lo < cnt ? k - j_lo : cnt - 1];
+            const double* p0 = f + 12 * sw;
+            const double* p1 = f + (j + 1 < cnt ? kFpPose : 0) + 12 * sw;       // the target: the same foot after this step
+            const double x = (double)(u + 1) / (double)g.ss, x1 = 1.0 - x;
+            const double m = x * x * x * (10.0 - 15.0 * x + 6.0 * x * x), dm = 30.0 * x * x * x1 * x1;
+            const double lz = 16.0 * x * x * x1 * x1, dlz = 32.0 * x * x1 * (1.0 - 2.0 * x);
+            const double inv = 1.0 / ((double)g.ss * g.dT);
+            double* op = o + kPlanLeft + 12 * sw;
+            double* ot = o + kPlanTwL + 6 * sw;
+            const double dx = p1[0] - p0[0], dyy = p1[1] - p0[1];
+            op[0] = p0[0] + dx * m; op[1] = p0[1] + dyy * m; op[2] = p0[2] + g.lift * lz;
+            double sn, cs;
+            sincos(dy * m, &sn, &cs);
+            for (int c = 0; c < 3; ++c) {
+                const double r0 = p0[3 + c], r1 = p0[6 + c];
+                op[3 + c] = cs * r0 - sn * r1;
+                op[6 + c] = sn * r0 + cs * r1;
+            }
+            ot[0] = dx * dm * inv; ot[1] = dyy * dm * inv; ot[2] = g.lift * dlz * inv; ot[5] = dy * dm * inv;
+            flags = sw == 1 ? 1 : 2;
+        }
+        o[kPlanFlags] = (double)(flags | (fixed == 0 ? 4 : 0));
+        o[kPlanHeight] = g.state[i * kStateLen + 68];
+        o[kPlanHeightVel] = 0.0;
+        // the support-polygon set in force: stage 0's, plus the changes of contact pair up to this stage that a tick can reach
+        const int se = s < g.max_ticks ? s : g.max_ticks;
+        int changes = 0;
+        if (se >= g.first_ds) {
+            const int ke = (se - g.first_ds) / per, ue = (se - g.first_ds) - ke * per;
+            changes = ke < n ? 2 * ke + 1 + (ue >= g.ss ? 1 : 0) : 2 * n;
+        }
+        o[kPlanHull] = (double)(g.set_base[i] + changes);
+    }
+    __syncthreads();
+    double* out = g.rec + (i * (size_t)T + (size_t)s0) * kPlanRec;
+    const int total = nvalid * kPlanRec;
+    for (int x = 2 * lane; x < total; x += 2 * kRecTile) {
+        const int st = x / kPlanRec, e = x - st * kPlanRec;
+        *reinterpret_cast<double2*>(out + x) = make_double2(tile[st * kRecRow + e], tile[st * kRecRow + e + 1]);
+    }
+}
+
+}  // namespace
+
+namespace wcqp {
+
+int plan_gen_enqueue(const PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) {
+    if (g.batch < 1 || g.traj_len < 1 || g.ss < 1 || g.ds < 1 || g.first_ds < 1 || g.final_ds < 1 || g.K < 0) return WCQP_E_INVALID;
+    hipLaunchKernelGGL(plan_prologue_kernel, dim3((unsigned)((g.batch + 63) / 64)), dim3(64), 0, stream, g);
+    hipLaunchKernelGGL(plan_dcm_kernel, dim3((unsigned)((g.batch + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, g);
+    if (rec0) WCQP_HIP_TRY(hipEventRecord(rec0, stream));
+    // (robots on grid.y: 65535 at most per launch)
+    for (int i0 = 0; i0 < g.batch; i0 += 65535) {
+        PlanGenDev p = g;
+        const int nb = g.batch - i0 < 65535 ? g.batch - i0 : 65535;
+        p.n_steps += i0; p.side += (size_t)i0 * g.K; p.target += (size_t)i0 * g.K * 3; p.state += (size_t)i0 * kStateLen;
+        p.set_base += i0; p.table += (size_t)i0 * (size_t)(g.K + 1) * kFpRec; p.rec += (size_t)i0 * (size_t)g.traj_len * kPlanRec;
+        hipLaunchKernelGGL(plan_record_kernel, dim3((unsigned)((g.traj_len + kRecTile - 1) / kRecTile), (unsigned)nb), dim3(kRecTile), 0, stream, p);
+    }
+    if (rec1) WCQP_HIP_TRY(hipEventRecord(rec1, stream));
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+
+}  // namespace wcqp

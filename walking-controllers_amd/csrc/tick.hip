@@ -20,6 +20,7 @@
 #include "tick_device.h"
 #include "ik_common.h"
 #include "sensors.h"
+#include "plan_gen.h"
 
 namespace {
 
@@ -275,6 +276,10 @@ struct wcqp_tick_s {
     bool planned = false;
     PlanDev pl{};
     double* set_A = nullptr; double* set_b = nullptr; int* set_nc = nullptr;     // the row sets of the last upload (PlanDev::set_*)
+    size_t n_sets = 0;            // how many (wcqp_tick_get_plan reads them back)
+    // wcqp_tick_upload_footsteps: the generated ZMP of stage 0 [B][2] (allocated by the first such upload), and whether the plan in place was generated
+    double* gen_zmp0 = nullptr; bool generated = false;
+    hipEvent_t gen_ev[2] = {nullptr, nullptr}; float gen_record_ms = 0.0f;     // the record pass of the last such upload, timed (wcqp_tick_info.plan_record_ms)
     // streamed_trajectories (an EXTERNAL handle): pl.rec holds ONE record per robot, the stage wcqp_tick_set_desired_* handed over for the next
     // tick, pl.set_* one row set per robot; `planned` stays false (the splice of the DCM reference keeps working)
     bool streamed = false, desired_set = false;
@@ -572,6 +577,7 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     if (h->splice_stage) (void)hipFree(h->splice_stage);
     if (h->splice_done) (void)hipEventDestroy(h->splice_done);
     if (h->run_done) (void)hipEventDestroy(h->run_done);
+    for (hipEvent_t e : h->gen_ev) if (e) (void)hipEventDestroy(e);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->kin) wcqp_kin_destroy(h->kin);
     if (h->mpc) wcqp_mpc_destroy(h->mpc);
@@ -599,6 +605,26 @@ static int validate_plan(const wcqp_tick_s* h, const wcqp_tick_inputs* in) {
             if (in->com_height_vel) ok = ok && std::isfinite(in->com_height_vel[w]);
             if (!ok) return WCQP_E_INVALID;
         }
+    return WCQP_OK;
+}
+
+// the support-polygon row sets of a plan whose records are in place (in NULL-stream order): the previous upload's go, `ns` new ones are built
+// on the device from the records of their stages (at: record offsets, code: contact pairs - device arrays), and the handle's kernels see them
+static int build_plan_sets(wcqp_tick_s* h, size_t ns, const long long* d_at, const int* d_code) {
+    for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
+    h->set_A = nullptr; h->set_b = nullptr; h->set_nc = nullptr; h->n_sets = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&h->set_A), ns * 128) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&h->set_b), ns * 64) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&h->set_nc), ns * 4) != hipSuccess)
+        return WCQP_E_NOMEM;
+    PlanRect r;
+    for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
+    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((ns + 127) / 128)), dim3(128), 0, 0, (int)ns, r, h->pl.rec.get(), d_at, d_code,
+                       h->set_A, h->set_b, h->set_nc);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return WCQP_E_HIP;
+    // the kernels read the sets through the handle's TickDevPL in device memory
+    h->pl.set_A = h->set_A; h->pl.set_b = h->set_b; h->pl.set_nc = h->set_nc; h->n_sets = ns;
+    const TickDevPL g = h->dpl(h->d);
+    WCQP_HIP_TRY(hipMemcpy(h->d_dev, &g, sizeof(TickDevPL), hipMemcpyHostToDevice));
     return WCQP_OK;
 }
 
@@ -641,34 +667,111 @@ static int upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in) {
         }
         WCQP_HIP_TRY(hipMemcpy(const_cast<double*>(h->pl.rec.get()) + i0 * T * kPlanRec, rec.data(), n * T * kPlanRec * 8, hipMemcpyHostToDevice));
     }
-    // the row sets: the previous upload's go, the new ones are built on the device from the records just copied
-    for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
-    h->set_A = nullptr; h->set_b = nullptr; h->set_nc = nullptr;
+    // the row sets, built on the device from the records just copied
     const size_t ns = set_at.size();
     long long* d_at = nullptr; int* d_code = nullptr;
     int rc = WCQP_OK;
-    if (hipMalloc(reinterpret_cast<void**>(&h->set_A), ns * 128) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&h->set_b), ns * 64) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&h->set_nc), ns * 4) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_at), ns * 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_code), ns * 4) != hipSuccess)
-        rc = WCQP_E_NOMEM;
+    if (hipMalloc(reinterpret_cast<void**>(&d_at), ns * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_code), ns * 4) != hipSuccess) rc = WCQP_E_NOMEM;
     if (rc == WCQP_OK && (hipMemcpy(d_at, set_at.data(), ns * 8, hipMemcpyHostToDevice) != hipSuccess ||
                           hipMemcpy(d_code, set_code.data(), ns * 4, hipMemcpyHostToDevice) != hipSuccess))
         rc = WCQP_E_HIP;
-    if (rc == WCQP_OK) {
-        PlanRect r;
-        for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
-        hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((ns + 127) / 128)), dim3(128), 0, 0, (int)ns, r, h->pl.rec.get(), d_at, d_code,
-                           h->set_A, h->set_b, h->set_nc);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = WCQP_E_HIP;
-    }
+    if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);
     (void)hipFree(d_at); (void)hipFree(d_code);
-    if (rc != WCQP_OK) return rc;
-    // the kernels read the sets through the handle's TickDevPL in device memory
-    h->pl.set_A = h->set_A; h->pl.set_b = h->set_b; h->pl.set_nc = h->set_nc;
-    const TickDevPL g = h->dpl(d);
-    WCQP_HIP_TRY(hipMemcpy(h->d_dev, &g, sizeof(TickDevPL), hipMemcpyHostToDevice));
-    return WCQP_OK;
+    return rc;
 }
+
+// The tail both uploads share (wcqp_tick_upload, wcqp_tick_upload_footsteps), once the trajectories are in place: the state records of the
+// chain, the pose block and joints, the initial DCM / CoM / command, the smoothers, filters and counters at rest, tick 0.  pair0 >= 0: the
+// contact pair of stage 0 where `in` holds no contact array.
+static int upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0) {
+    TickDev& d = h->d;
+    const size_t B = (size_t)d.batch;
+#define UP_(dst, src, n) WCQP_HIP_TRY(hipMemcpy(const_cast<void*>(static_cast<const void*>(dst)), (src), (n), hipMemcpyHostToDevice))
+    if (d.skew) {
+        // state of the MPC chain per axis: c_ref, v_ref_prev, com, u_prev (= measured ZMP), p_star, v_star_prev, dcm, spare
+        std::vector<double> mst(B * 16, 0.0);
+        for (size_t i = 0; i < B; ++i)
+            for (int ax = 0; ax < 2; ++ax) {
+                double* r = &mst[(i * 2 + ax) * 8];
+                r[0] = in->com0[2 * i + ax]; r[2] = in->com0[2 * i + ax]; r[3] = in->u_init[2 * i + ax];
+                r[4] = in->com0[2 * i + ax]; r[6] = in->dcm0[2 * i + ax]; r[7] = in->u_init[2 * i + ax];
+            }
+        WCQP_HIP_TRY(hipMemcpy(d.mst, mst.data(), B * 16 * 8, hipMemcpyHostToDevice));
+        WCQP_HIP_TRY(hipMemset(d.sel_built, 0xff, B * 4));           // -1: every robot builds / copies its live rows at tick 0
+        WCQP_HIP_TRY(hipMemset(d.live_nc, 0, B * 4));
+    }
+    if (h->kin) {
+        std::vector<double> h0(B);
+        for (size_t i = 0; i < B; ++i) h0[i] = in->state0[i * kStateLen + 68];       // desired CoM height = the initial one
+        WCQP_HIP_TRY(hipMemcpy(const_cast<double*>(d.com_h0.get()), h0.data(), B * 8, hipMemcpyHostToDevice));
+    } else {
+        if (in->hull_tab_A && in->hull_tab_b && in->hull_tab_nc) {
+            UP_(d.hull_tab_A, in->hull_tab_A, B * 3 * 128); UP_(d.hull_tab_b, in->hull_tab_b, B * 3 * 64); UP_(d.hull_tab_nc, in->hull_tab_nc, B * 3 * 4);
+        }
+        UP_(h->J_left, in->J_left, B * 6 * 29 * 8); UP_(h->J_right, in->J_right, B * 6 * 29 * 8);
+        UP_(h->J_neck, in->J_neck, B * 3 * 29 * 8); UP_(h->J_com, in->J_com, B * 3 * 29 * 8);
+    }
+    UP_(d.state, in->state0, B * kStateLen * 8); UP_(d.q_des, in->q0, B * kDof * 8);
+    if (h->kin && !h->planned && !h->streamed) {     // (planned / streamed: the live rows are built from the records at the first tick - sel_built = -1)
+        // setConvexHullConstraint (...PredictiveController.cpp:364-435) for the three contact pairs, from the DESIRED foot
+        // poses just uploaded (the planned footsteps, WalkingModule.cpp:609-613): the MPC of a tick selects its rows by the pair
+        const int rch = wcqp::hull_tables_from_state((int)B, h->p.foot_rect, d.state, kStateLen, const_cast<double*>(d.hull_tab_A.get()),
+                                                     const_cast<double*>(d.hull_tab_b.get()), const_cast<int*>(d.hull_tab_nc.get()), nullptr);
+        if (rch != WCQP_OK) return rch;
+        WCQP_HIP_TRY(hipDeviceSynchronize());
+    }
+    UP_(d.dcm, in->dcm0, B * 16); UP_(d.com, in->com0, B * 16); UP_(d.c_ref, in->com0, B * 16); UP_(d.p_star, in->com0, B * 16);
+    UP_(d.zmp_meas, in->u_init, B * 16); UP_(d.u_prev, in->u_init, B * 16);
+    WCQP_HIP_TRY(hipMemset(d.v_ref_prev, 0, B * 16)); WCQP_HIP_TRY(hipMemset(d.v_star_prev, 0, B * 16));
+    // the gain smoothers at rest at the stance gains (WalkingZMPController::initialize): s = 0, state 0
+    if (d.gain_sched) WCQP_HIP_TRY(hipMemset(h->zg.zs, 0, B * 32));
+    WCQP_HIP_TRY(hipMemset(d.dq_prev, 0, B * kDof * 8)); WCQP_HIP_TRY(hipMemset(d.tick2, 0, 8));
+    {   // contact pair of tick 0 (later ticks: tick_post_kernel)
+        std::vector<int> sel(B);
+        for (size_t i = 0; i < B; ++i) {
+            if (pair0 >= 0) { sel[i] = pair0; continue; }                 // (a generated plan: stage 0 is a double support)
+            if (h->planned) { sel[i] = (int)(in->contact[i * d.traj_len] & 3u) - 1; continue; }
+            if (h->streamed) { sel[i] = 2; continue; }      // (the skewed kernels take the pair from the stage's record)
+            const int cyc = in->phase0[i] % (2 * d.step_ticks), sidx = cyc % d.step_ticks;
+            sel[i] = sidx < d.ds_ticks ? 2 : cyc / d.step_ticks;
+        }
+        WCQP_HIP_TRY(hipMemcpy(d.sel, sel.data(), B * 4, hipMemcpyHostToDevice));
+    }
+    WCQP_HIP_TRY(hipMemset(d.mpc_fail, 0, B * 8)); WCQP_HIP_TRY(hipMemset(d.ik_fail, 0, B * 8));
+    WCQP_HIP_TRY(hipMemset(d.hot_try, 0, B * 8)); WCQP_HIP_TRY(hipMemset(d.hot_hit, 0, B * 8));
+    WCQP_HIP_TRY(hipMemset(h->ik_lo, 0, B * 4)); WCQP_HIP_TRY(hipMemset(h->ik_up, 0, B * 4));      // no previous active set at tick 0
+    if (h->feedback_fail) WCQP_HIP_TRY(hipMemset(h->feedback_fail, 0, B * 8));
+    if (h->filt_state) {
+        // the filters at rest: the CoM position filter AT com0 and its velocity filter at 0 (the reference starts them at (0, 0, com_height)
+        // and 0 once, WM/src/WalkingForwardKinematics.cpp:153-160: its robot stands at the origin); the joint-velocity and wrench filters
+        // start at the first reading (RobotHelper::resetFilters), which the first sensor call is told
+        std::vector<double> fs(B * kFiltRec, 0.0);
+        for (size_t i = 0; i < B; ++i)
+            for (int ax = 0; ax < 2; ++ax) fs[i * kFiltRec + kFiltCom + 4 * ax] = fs[i * kFiltRec + kFiltCom + 4 * ax + 1] = in->com0[2 * i + ax];
+        WCQP_HIP_TRY(hipMemcpy(h->filt_state, fs.data(), B * kFiltRec * 8, hipMemcpyHostToDevice));
+        WCQP_HIP_TRY(hipMemset(h->filt_state + B * kFiltRec, 0, B * kFiltRec * 8));
+        h->filt_cur = 0; h->filt_started = false; h->filt_pending = false;
+    }
+    if (h->external) {
+        h->meas0.resize(B * 6);
+        for (size_t i = 0; i < B; ++i)
+            for (int ax = 0; ax < 2; ++ax) {
+                h->meas0[i * 6 + ax] = in->dcm0[2 * i + ax]; h->meas0[i * 6 + 2 + ax] = in->com0[2 * i + ax]; h->meas0[i * 6 + 4 + ax] = in->u_init[2 * i + ax];
+            }
+    }
+    // (hipMemset does not wait, and the copies / kernels above ran on the NULL stream: the run call that follows may name a non-blocking
+    // stream - wcqp_stream_create makes such - which would not wait for them either)
+    WCQP_HIP_TRY(hipDeviceSynchronize());
+    h->uploaded = true;
+    h->ticks_enqueued = 0;
+    h->phase = 0;
+    h->feedback_set = false;
+    h->desired_set = false;
+    h->run_pending = false;
+    return WCQP_OK;
+#undef UP_
+}
+
 
 int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     if (!h || !in) return WCQP_E_INVALID;
@@ -714,6 +817,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     if (h->planned) {
         const int rcp = upload_plan(h, in);
         if (rcp != WCQP_OK) return rcp;
+        h->generated = false;
         WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
         WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
     } else if (h->streamed) {
@@ -726,87 +830,151 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     } else {
         UP_(d.phase0, in->phase0, B * 4); UP_(d.swing_twist, in->swing_twist, B * 48);
     }
-    if (d.skew) {
-        // state of the MPC chain per axis: c_ref, v_ref_prev, com, u_prev (= measured ZMP), p_star, v_star_prev, dcm, spare
-        std::vector<double> mst(B * 16, 0.0);
-        for (size_t i = 0; i < B; ++i)
-            for (int ax = 0; ax < 2; ++ax) {
-                double* r = &mst[(i * 2 + ax) * 8];
-                r[0] = in->com0[2 * i + ax]; r[2] = in->com0[2 * i + ax]; r[3] = in->u_init[2 * i + ax];
-                r[4] = in->com0[2 * i + ax]; r[6] = in->dcm0[2 * i + ax]; r[7] = in->u_init[2 * i + ax];
-            }
-        WCQP_HIP_TRY(hipMemcpy(d.mst, mst.data(), B * 16 * 8, hipMemcpyHostToDevice));
-        WCQP_HIP_TRY(hipMemset(d.sel_built, 0xff, B * 4));           // -1: every robot builds / copies its live rows at tick 0
-        WCQP_HIP_TRY(hipMemset(d.live_nc, 0, B * 4));
-    }
-    if (h->kin) {
-        std::vector<double> h0(B);
-        for (size_t i = 0; i < B; ++i) h0[i] = in->state0[i * kStateLen + 68];       // desired CoM height = the initial one
-        WCQP_HIP_TRY(hipMemcpy(const_cast<double*>(d.com_h0.get()), h0.data(), B * 8, hipMemcpyHostToDevice));
-    } else {
-        if (in->hull_tab_A && in->hull_tab_b && in->hull_tab_nc) {
-            UP_(d.hull_tab_A, in->hull_tab_A, B * 3 * 128); UP_(d.hull_tab_b, in->hull_tab_b, B * 3 * 64); UP_(d.hull_tab_nc, in->hull_tab_nc, B * 3 * 4);
-        }
-        UP_(h->J_left, in->J_left, B * 6 * 29 * 8); UP_(h->J_right, in->J_right, B * 6 * 29 * 8);
-        UP_(h->J_neck, in->J_neck, B * 3 * 29 * 8); UP_(h->J_com, in->J_com, B * 3 * 29 * 8);
-    }
-    UP_(d.state, in->state0, B * kStateLen * 8); UP_(d.q_des, in->q0, B * kDof * 8);
-    if (h->kin && !h->planned && !h->streamed) {     // (planned / streamed: the live rows are built from the records at the first tick - sel_built = -1)
-        // setConvexHullConstraint (...PredictiveController.cpp:364-435) for the three contact pairs, from the DESIRED foot
-        // poses just uploaded (the planned footsteps, WalkingModule.cpp:609-613): the MPC of a tick selects its rows by the pair
-        const int rch = wcqp::hull_tables_from_state((int)B, h->p.foot_rect, d.state, kStateLen, const_cast<double*>(d.hull_tab_A.get()),
-                                                     const_cast<double*>(d.hull_tab_b.get()), const_cast<int*>(d.hull_tab_nc.get()), nullptr);
-        if (rch != WCQP_OK) return rch;
-        WCQP_HIP_TRY(hipDeviceSynchronize());
-    }
-    UP_(d.dcm, in->dcm0, B * 16); UP_(d.com, in->com0, B * 16); UP_(d.c_ref, in->com0, B * 16); UP_(d.p_star, in->com0, B * 16);
-    UP_(d.zmp_meas, in->u_init, B * 16); UP_(d.u_prev, in->u_init, B * 16);
 #undef UP_
-    WCQP_HIP_TRY(hipMemset(d.v_ref_prev, 0, B * 16)); WCQP_HIP_TRY(hipMemset(d.v_star_prev, 0, B * 16));
-    // the gain smoothers at rest at the stance gains (WalkingZMPController::initialize): s = 0, state 0
-    if (d.gain_sched) WCQP_HIP_TRY(hipMemset(h->zg.zs, 0, B * 32));
-    WCQP_HIP_TRY(hipMemset(d.dq_prev, 0, B * kDof * 8)); WCQP_HIP_TRY(hipMemset(d.tick2, 0, 8));
-    {   // contact pair of tick 0 (later ticks: tick_post_kernel)
-        std::vector<int> sel(B);
-        for (size_t i = 0; i < B; ++i) {
-            if (h->planned) { sel[i] = (int)(in->contact[i * d.traj_len] & 3u) - 1; continue; }
-            if (h->streamed) { sel[i] = 2; continue; }      // (the skewed kernels take the pair from the stage's record)
-            const int cyc = in->phase0[i] % (2 * d.step_ticks), sidx = cyc % d.step_ticks;
-            sel[i] = sidx < d.ds_ticks ? 2 : cyc / d.step_ticks;
+    return upload_state(h, in, -1);
+}
+
+int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps) {
+    if (!h || !in || !steps) return WCQP_E_INVALID;
+    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    TickDev& d = h->d;
+    const size_t B = (size_t)d.batch;
+    const int K = steps->max_steps;
+    // everything is checked before anything of the handle changes (a handle uploaded before keeps that upload)
+    if (!in->state0 || !in->q0 || !in->com0 || !steps->n_steps || K < 0 || (K > 0 && (!steps->side || !steps->target))) return WCQP_E_INVALID;
+    if (steps->first_ds_ticks < 1 || steps->ss_ticks < 1 || steps->ds_ticks < 1 || steps->final_ds_ticks < 0) return WCQP_E_INVALID;
+    const int final_ds = steps->final_ds_ticks > 0 ? steps->final_ds_ticks : steps->ds_ticks;
+    const long long per = (long long)steps->ss_ticks + steps->ds_ticks;
+    if ((long long)steps->first_ds_ticks + (long long)K * per + final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    auto finite = [](const double* a, size_t n) { bool ok = true; for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(a[k]); return ok; };
+    if (!std::isfinite(steps->lift) || !finite(steps->zmp_delta_left, 2) || !finite(steps->zmp_delta_right, 2)) return WCQP_E_INVALID;
+    if (!finite(in->q0, B * kDof) || !finite(in->com0, B * 2) || (in->dcm0 && !finite(in->dcm0, B * 2)) || (in->u_init && !finite(in->u_init, B * 2)))
+        return WCQP_E_INVALID;
+    // the support-polygon sets, robot by robot: stage 0's, then two per step - the stance foot alone, both again - where a tick can reach them
+    std::vector<int> set_base(B);
+    size_t ns = 0;
+    for (size_t i = 0; i < B; ++i) {
+        const int n = steps->n_steps[i];
+        if (n < 0 || n > K) return WCQP_E_INVALID;
+        if (!finite(in->state0 + i * kStateLen + 24, 24) || !std::isfinite(in->state0[i * kStateLen + 68])) return WCQP_E_INVALID;
+        set_base[i] = (int)ns;
+        ns += 1;
+        for (int k = 0; k < n; ++k) {
+            if (steps->side[i * K + k] > 1 || !finite(steps->target + (i * K + k) * 3, 3)) return WCQP_E_INVALID;
+            const long long s_k = steps->first_ds_ticks + k * per;
+            ns += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + steps->ss_ticks <= h->p.max_ticks ? 1 : 0);
         }
-        WCQP_HIP_TRY(hipMemcpy(d.sel, sel.data(), B * 4, hipMemcpyHostToDevice));
     }
-    WCQP_HIP_TRY(hipMemset(d.mpc_fail, 0, B * 8)); WCQP_HIP_TRY(hipMemset(d.ik_fail, 0, B * 8));
-    WCQP_HIP_TRY(hipMemset(d.hot_try, 0, B * 8)); WCQP_HIP_TRY(hipMemset(d.hot_hit, 0, B * 8));
-    WCQP_HIP_TRY(hipMemset(h->ik_lo, 0, B * 4)); WCQP_HIP_TRY(hipMemset(h->ik_up, 0, B * 4));      // no previous active set at tick 0
-    if (h->feedback_fail) WCQP_HIP_TRY(hipMemset(h->feedback_fail, 0, B * 8));
-    if (h->filt_state) {
-        // the filters at rest: the CoM position filter AT com0 and its velocity filter at 0 (the reference starts them at (0, 0, com_height)
-        // and 0 once, WM/src/WalkingForwardKinematics.cpp:153-160: its robot stands at the origin); the joint-velocity and wrench filters
-        // start at the first reading (RobotHelper::resetFilters), which the first sensor call is told
-        std::vector<double> fs(B * kFiltRec, 0.0);
-        for (size_t i = 0; i < B; ++i)
-            for (int ax = 0; ax < 2; ++ax) fs[i * kFiltRec + kFiltCom + 4 * ax] = fs[i * kFiltRec + kFiltCom + 4 * ax + 1] = in->com0[2 * i + ax];
-        WCQP_HIP_TRY(hipMemcpy(h->filt_state, fs.data(), B * kFiltRec * 8, hipMemcpyHostToDevice));
-        WCQP_HIP_TRY(hipMemset(h->filt_state + B * kFiltRec, 0, B * kFiltRec * 8));
-        h->filt_cur = 0; h->filt_started = false; h->filt_pending = false;
-    }
-    if (h->external) {
-        h->meas0.resize(B * 6);
-        for (size_t i = 0; i < B; ++i)
-            for (int ax = 0; ax < 2; ++ax) {
-                h->meas0[i * 6 + ax] = in->dcm0[2 * i + ax]; h->meas0[i * 6 + 2 + ax] = in->com0[2 * i + ax]; h->meas0[i * 6 + 4 + ax] = in->u_init[2 * i + ax];
-            }
-    }
-    // (hipMemset does not wait, and the copies / kernels above ran on the NULL stream: the run call that follows may name a non-blocking
-    // stream - wcqp_stream_create makes such - which would not wait for them either)
+    if (ns > (size_t)1 << 30) return WCQP_E_UNSUPPORTED;
+    // from here on the device state changes: a call that fails on the way leaves the handle unrunnable until the next good upload
+    h->uploaded = false;
     WCQP_HIP_TRY(hipDeviceSynchronize());
-    h->uploaded = true;
-    h->ticks_enqueued = 0;
-    h->phase = 0;
-    h->feedback_set = false;
-    h->desired_set = false;
-    h->run_pending = false;
+    if (!h->gen_zmp0) { const int rca = dev_alloc(h, &h->gen_zmp0, B * 2); if (rca != WCQP_OK) return rca; }
+    // the footsteps, the table and the set table: device memory of this call
+    struct Scratch {
+        std::vector<void*> p;
+        ~Scratch() { for (void* q : p) (void)hipFree(q); }
+        void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes > 0 ? bytes : 1) != hipSuccess) return nullptr; p.push_back(q); return q; }
+    } scratch;
+    PlanGenDev g{};
+    const size_t BK = B * (size_t)K;
+    int* d_n = static_cast<int*>(scratch.get(B * 4)); int* d_base = static_cast<int*>(scratch.get(B * 4));
+    unsigned char* d_side = static_cast<unsigned char*>(scratch.get(BK)); double* d_tg = static_cast<double*>(scratch.get(BK * 24));
+    double* d_tab = static_cast<double*>(scratch.get(B * (size_t)(K + 1) * kFpRec * 8));
+    long long* d_at = static_cast<long long*>(scratch.get(ns * 8)); int* d_code = static_cast<int*>(scratch.get(ns * 4));
+    if (!d_n || !d_base || !d_side || !d_tg || !d_tab || !d_at || !d_code) return WCQP_E_NOMEM;
+    WCQP_HIP_TRY(hipMemcpy(d_n, steps->n_steps, B * 4, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(d_base, set_base.data(), B * 4, hipMemcpyHostToDevice));
+    if (BK > 0) {
+        WCQP_HIP_TRY(hipMemcpy(d_side, steps->side, BK, hipMemcpyHostToDevice));
+        WCQP_HIP_TRY(hipMemcpy(d_tg, steps->target, BK * 24, hipMemcpyHostToDevice));
+    }
+    WCQP_HIP_TRY(hipMemcpy(d.state, in->state0, B * kStateLen * 8, hipMemcpyHostToDevice));      // (the initial footprints and the CoM height)
+    g.n_steps = d_n; g.side = d_side; g.target = d_tg; g.state = d.state; g.set_base = d_base; g.table = d_tab; g.set_at = d_at; g.set_code = d_code;
+    g.rec = const_cast<double*>(h->pl.rec.get()); g.ref = const_cast<double*>(d.ref_traj.get());
+    g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
+    g.zmp0 = h->gen_zmp0;
+    g.batch = d.batch; g.K = K; g.traj_len = d.traj_len; g.max_ticks = h->p.max_ticks;
+    g.first_ds = steps->first_ds_ticks; g.ss = steps->ss_ticks; g.ds = steps->ds_ticks; g.final_ds = final_ds;
+    g.lift = steps->lift; g.dT = d.dT; g.omega = d.omega; g.a = std::exp(d.omega * d.dT);
+    for (int k = 0; k < 2; ++k) { g.delta[0][k] = steps->zmp_delta_left[k]; g.delta[1][k] = steps->zmp_delta_right[k]; }
+    for (hipEvent_t& e : h->gen_ev) if (!e) WCQP_HIP_TRY(hipEventCreate(&e));
+    int rc = wcqp::plan_gen_enqueue(g, nullptr, h->gen_ev[0], h->gen_ev[1]);
+    if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);      // (synchronises)
+    if (rc != WCQP_OK) return rc;
+    WCQP_HIP_TRY(hipEventElapsedTime(&h->gen_record_ms, h->gen_ev[0], h->gen_ev[1]));
+    h->vel_explicit = g.vel != nullptr;       // (the generated velocities, where the handle keeps any: the splice has no tail for them)
+    h->generated = true;
+    WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
+    WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
+    // dcm0 / u_init NULL: the generated DCM reference and ZMP of stage 0
+    std::vector<double> dcm0, u0;
+    wcqp_tick_inputs eff = *in;
+    if (!in->dcm0) {
+        dcm0.resize(B * 2);
+        WCQP_HIP_TRY(hipMemcpy2D(dcm0.data(), 16, d.ref_traj.get(), (size_t)d.traj_len * 16, 16, B, hipMemcpyDeviceToHost));
+        eff.dcm0 = dcm0.data();
+    }
+    if (!in->u_init) {
+        u0.resize(B * 2);
+        WCQP_HIP_TRY(hipMemcpy(u0.data(), h->gen_zmp0, B * 16, hipMemcpyDeviceToHost));
+        eff.u_init = u0.data();
+    }
+    return upload_state(h, &eff, 2);
+}
+
+int wcqp_tick_get_plan(wcqp_tick_t h, int32_t robot0, int32_t n, int32_t stage0, int32_t m, const wcqp_tick_plan_window* out) {
+    if (!h || !out) return WCQP_E_INVALID;
+    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    const TickDev& d = h->d;
+    if (!h->uploaded || robot0 < 0 || n < 1 || stage0 < 0 || m < 1 || (long long)robot0 + n > d.batch || (long long)stage0 + m > d.traj_len) return WCQP_E_INVALID;
+    const bool has_vel = d.reactive || d.gain_sched;
+    if ((out->dcm_vel_traj && !has_vel) || (out->u_init && !h->generated)) return WCQP_E_UNSUPPORTED;
+    WCQP_HIP_TRY(hipDeviceSynchronize());
+    const size_t N = (size_t)n, M = (size_t)m, T = (size_t)d.traj_len, R0 = (size_t)robot0, S0 = (size_t)stage0;
+    for (int which = 0; which < 2; ++which) {
+        double* dst = which ? out->dcm_vel_traj : out->ref_traj;
+        const double* src = which ? d.dcm_vel.get() : d.ref_traj.get();
+        if (dst) WCQP_HIP_TRY(hipMemcpy2D(dst, M * 16, src + (R0 * T + S0) * 2, T * 16, M * 16, N, hipMemcpyDeviceToHost));
+    }
+    if (out->u_init) WCQP_HIP_TRY(hipMemcpy(out->u_init, h->gen_zmp0 + R0 * 2, N * 16, hipMemcpyDeviceToHost));
+    const bool hull = out->hull_A || out->hull_b || out->hull_nc;
+    std::vector<double> sA, sb; std::vector<int> snc;
+    if (hull) {
+        sA.resize(h->n_sets * 16); sb.resize(h->n_sets * 8); snc.resize(h->n_sets);
+        WCQP_HIP_TRY(hipMemcpy(sA.data(), h->set_A, h->n_sets * 128, hipMemcpyDeviceToHost));
+        WCQP_HIP_TRY(hipMemcpy(sb.data(), h->set_b, h->n_sets * 64, hipMemcpyDeviceToHost));
+        WCQP_HIP_TRY(hipMemcpy(snc.data(), h->set_nc, h->n_sets * 4, hipMemcpyDeviceToHost));
+    }
+    if (!hull && !out->contact && !out->com_height && !out->com_height_vel && !out->left_traj && !out->right_traj && !out->left_twist && !out->right_twist)
+        return WCQP_OK;
+    // the records of the window, a slab of robots at a time (64 MiB of host memory at most, one robot at least), unpacked on the host
+    size_t slab = ((size_t)64 << 20) / (M * kPlanRec * 8);
+    slab = slab < 1 ? 1 : (slab > N ? N : slab);
+    std::vector<double> rec(slab * M * kPlanRec);
+    for (size_t i0 = 0; i0 < N; i0 += slab) {
+        const size_t nn = N - i0 < slab ? N - i0 : slab;
+        WCQP_HIP_TRY(hipMemcpy2D(rec.data(), M * kPlanRec * 8, h->pl.rec.get() + ((R0 + i0) * T + S0) * kPlanRec, T * kPlanRec * 8, M * kPlanRec * 8, nn,
+                                 hipMemcpyDeviceToHost));
+        for (size_t w0 = 0; w0 < nn * M; ++w0) {
+            const double* r = &rec[w0 * kPlanRec];
+            const size_t w = i0 * M + w0;
+            if (out->contact) out->contact[w] = (uint8_t)r[kPlanFlags];
+            if (out->com_height) out->com_height[w] = r[kPlanHeight];
+            if (out->com_height_vel) out->com_height_vel[w] = r[kPlanHeightVel];
+            if (out->left_traj) std::memcpy(out->left_traj + w * 12, r + kPlanLeft, 96);
+            if (out->right_traj) std::memcpy(out->right_traj + w * 12, r + kPlanRight, 96);
+            if (out->left_twist) std::memcpy(out->left_twist + w * 6, r + kPlanTwL, 48);
+            if (out->right_twist) std::memcpy(out->right_twist + w * 6, r + kPlanTwL + 6, 48);
+            if (hull) {
+                const size_t set = (size_t)r[kPlanHull];
+                if (set >= h->n_sets) return WCQP_E_HIP;
+                if (out->hull_A) std::memcpy(out->hull_A + w * 16, &sA[set * 16], 128);
+                if (out->hull_b) std::memcpy(out->hull_b + w * 8, &sb[set * 8], 64);
+                if (out->hull_nc) out->hull_nc[w] = snc[set];
+            }
+        }
+    }
     return WCQP_OK;
 }
 
@@ -1082,6 +1250,8 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
     out->planned_trajectories = h->planned ? 1 : 0;
     out->streamed_trajectories = h->streamed ? 1 : 0;
     out->sensor_filters = h->filt_mask;
+    out->plan_generated = h->planned && h->uploaded && h->generated ? 1 : 0;
+    out->plan_record_ms = out->plan_generated ? (double)h->gen_record_ms : 0.0;
     // a kinematics launch unless fused; then the skewed kernel (1), MPC / reactive + the 16-lane kernel (2) or controller, glue, IK, post (4)
     out->launches_per_tick = (h->kin && !d.kin_fused ? 1 : 0) + (h->form == TickForm::SKEWED ? 1 : h->form == TickForm::MPC_IK16 ? 2 : 4);
     return WCQP_OK;

@@ -588,3 +588,50 @@ def synth_planned_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_ba
                 left_traj=left, right_traj=right, left_twist=np.ascontiguousarray(tw[:, 0]), right_twist=np.ascontiguousarray(tw[:, 1]),
                 contact=np.ascontiguousarray(contact), goal=np.stack([left[:, -1], right[:, -1]], 1),
                 distance=np.linalg.norm(end_mid - start_mid, axis=1))
+
+
+ZMP_DELTA = ((0.03, -0.005), (0.03, 0.005))       # leftZMPDelta / rightZMPDelta (plannerParams.ini:39-40)
+
+
+def synth_footstep_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_batch: dict, seed: int = 4242, horizon: int = 50,
+                              first: int = 0, step_ticks: int = 180, ds_ticks: int = 110, n_steps: int = 4, step_length=(0.025, 0.035),
+                              yaw_step=(0.0, 0.0), lift: float = 0.02, dT: float = 0.01, com_height: float = 0.53, gravity: float = 9.81) -> dict:
+    """The walk of synth_planned_walk_batch (same arguments, seed and draws) as the footsteps that describe it - what
+    `TickPipeline.upload_footsteps` takes (wcqp_tick_footsteps): n_steps [B], side [B][K], target [B][K][3] (x, y of the new footprint, yaw
+    increment of the foot), first_ds_ticks, ss_ticks, ds_ticks, final_ds_ticks, lift, zmp_delta_left / zmp_delta_right - plus state0, q0,
+    com0.  final_ds_ticks is the rest of synth_planned_walk_batch's ZMP plan, which it runs 4 step_ticks past its T stages before it lets
+    the robot stand: (T + 4 step_ticks) - (the stage at which the last single support ends)."""
+    rng = CounterRNG(seed ^ 0x57E95, first, count)
+    T = n_ticks + horizon + 1
+    o = IK_STATE_OFFSETS
+    ss = step_ticks - ds_ticks
+    L = step_length[0] + (step_length[1] - step_length[0]) * rng.uniform(1)[:, 0]
+    dyaw = yaw_step[0] + (yaw_step[1] - yaw_step[0]) * rng.uniform(1)[:, 0]
+    state0 = np.array(poses, dtype=np.float64, copy=True)
+    for src, dst, k in (("p_left", "pd_left", 3), ("R_left", "Rd_left", 9), ("p_right", "pd_right", 3), ("R_right", "Rd_right", 9)):
+        state0[:, o[dst]:o[dst] + k] = state0[:, o[src]:o[src] + k]
+    side = np.zeros((count, n_steps), np.uint8)
+    target = np.zeros((count, n_steps, 3))
+    for i in range(count):
+        p = [state0[i, o["pd_left"]:o["pd_left"] + 3].copy(), state0[i, o["pd_right"]:o["pd_right"] + 3].copy()]
+        R = [state0[i, o["Rd_left"]:o["Rd_left"] + 9].reshape(3, 3).copy(), state0[i, o["Rd_right"]:o["Rd_right"] + 9].reshape(3, 3).copy()]
+        heading = np.arctan2(R[0][1, 0] + R[1][1, 0], R[0][0, 0] + R[1][0, 0])
+        half_w = 0.5 * np.linalg.norm((p[0] - p[1])[:2])
+        for k in range(n_steps):
+            sw = 1 - (k % 2)                      # the right foot (1) swings first
+            st = 1 - sw
+            h1 = heading + dyaw[i]
+            fwd = np.array([np.cos(h1), np.sin(h1), 0.0]); lat = np.array([-np.sin(h1), np.cos(h1), 0.0])
+            p_target = p[st] + L[i] * fwd + (2 * half_w) * lat * (1.0 if sw == 0 else -1.0)
+            yaw0 = np.arctan2(R[sw][1, 0], R[sw][0, 0])
+            inc = (yaw0 + dyaw[i]) - yaw0
+            side[i, k] = sw
+            target[i, k] = (p_target[0], p_target[1], inc)
+            p[sw] = np.array([p_target[0], p_target[1], p[sw][2]])
+            R[sw] = _rotz(np.array([inc]))[0] @ R[sw]
+            heading = h1
+    last_ss_end = ds_ticks + (n_steps - 1) * step_ticks + ss
+    return dict(first=first, n_steps=np.full(count, n_steps, np.int32), side=side, target=target, first_ds_ticks=ds_ticks, ss_ticks=ss,
+                ds_ticks=ds_ticks, final_ds_ticks=(T + 4 * step_ticks) - last_ss_end, lift=lift, zmp_delta_left=ZMP_DELTA[0],
+                zmp_delta_right=ZMP_DELTA[1], state0=np.ascontiguousarray(state0), q0=np.ascontiguousarray(kin_batch["q"]),
+                com0=np.ascontiguousarray(state0[:, o["com"]:o["com"] + 2].copy()))
