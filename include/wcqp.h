@@ -693,8 +693,8 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in);
  * WCQP_E_UNSUPPORTED on a handle without planned_trajectories.  WCQP_E_INVALID, with the handle unchanged (a handle uploaded before keeps
  * that upload), for a NULL required pointer, n_steps outside 0..K, a side other than 0 / 1, a non-finite value (of a step the robot
  * takes, of the state0 entries read, q0, com0, dcm0, u_init, lift or the deltas), a tick count below 1 or final_ds_ticks below 0.
- * Not offered, and refused by construction rather than silently ignored: regenerating from a tick > 0 (the call always rewinds), per-step
- * timings, device-pointer footsteps. */
+ * The call always rewinds to tick 0; wcqp_tick_replan_footsteps below regenerates a running plan from a later stage.  Not offered, and
+ * refused by construction rather than silently ignored: per-step timings, device-pointer footsteps. */
 typedef struct wcqp_tick_footsteps {      /* HOST pointers, copied at the call */
     int32_t max_steps;                    /* K: row length of the per-step arrays, >= 0 */
     const int32_t* n_steps;               /* [B] 0..K steps robot i takes */
@@ -705,6 +705,45 @@ typedef struct wcqp_tick_footsteps {      /* HOST pointers, copied at the call *
     double  zmp_delta_left[2], zmp_delta_right[2];   /* plannerParams.ini leftZMPDelta / rightZMPDelta, foot frame */
 } wcqp_tick_footsteps;
 int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps);
+/* A new goal for a walk that is running (WalkingModule::setPlannerInput / askNewTrajectories / updateTrajectories,
+ * WM/src/WalkingModule.cpp:1059-1145, 1263-1308: the planner restarts at a merge point inside a double support from the old trajectory's DCM
+ * there, and everything from the merge point on is replaced).  Robot i's generated plan is regenerated on the device from stage M_i =
+ * merge_stage[i] on, from new footsteps; a robot with merge_stage -1 keeps its plan, and none of its rows is read.  ss_ticks, ds_ticks,
+ * final_ds_ticks, lift and the ZMP deltas are those of the handle's last wcqp_tick_upload_footsteps (the reference's planner parameters
+ * are fixed for a run too).  THE REPLANNED PLAN, this build's own definition as the one above (tests/helpers/footstep_replan.py restates it):
+ *   Below M_i   every stage of robot i stays bit for bit: records, ref_traj, dcm_vel, and the support-polygon sets those stages name.
+ *   Footprints  the two desired sole poses of the current plan's record M_i - a stage with both feet in contact.
+ *   Timeline    stages [M_i, M_i + first_ds_ticks) are double support; from there on timeline, swing, flags, ZMP of single and double supports,
+ *               height and neck follow the rules above with stage 0 moved to M_i.
+ *   Fixed frame before the new plan's first single support (for n_steps = 0: everywhere) bit 2 keeps the value of stage M_i - 1.
+ *   DCM         the backward recursion above, from the new plan's first standing stage down to M_i + first_ds_ticks, where its value is X.
+ *               The first double support's ZMP is z_u = a + (u + 1) / (n + 1) (b - a), n = first_ds_ticks, b the first new stance foot's point
+ *               (n_steps = 0: the midpoint of both feet's points) and a - per axis - the point for which the recursion arrives at xi_{M_i} = the
+ *               old plan's ref_traj[M_i] (the reference's setDCMInitialState, for the position): with q = exp(-omega dT),
+ *               S0 = sum_{j=1..n} q^j, S1 = sum_{j=1..n} j q^j / (n + 1):   xi_{M_i} = X q^n + (exp(omega dT) - 1) (a (S0 - S1) + b S1).
+ *               dcm_vel = omega (xi - zmp) as above.  DEVIATION: the reference also hands the planner the old DCM VELOCITY at the merge
+ *               point; here the velocity at M_i follows from a and is not matched.
+ *   Sets        the classic rule on the stitched plan: stage M_i changes no contact pair, so the records from M_i to the next change name the
+ *               robot's last surviving set (the last one of a stage <= M_i); every later change of pair at a stage <= max_ticks gets a set
+ *               built from that stage's feet.
+ * Enqueue-only, like wcqp_tick_splice_reference: the HOST arrays are staged into device memory of the handle before the call returns, the
+ * kernels run on `stream` behind the ticks already enqueued; no counter, state record, filter or tick index changes, no pointer a tick or
+ * a captured graph holds moves, and no set a stage below M_i names is rewritten.  Valid between wcqp_tick_run calls.
+ * WCQP_E_UNSUPPORTED on a handle without planned_trajectories, or whose plan was not generated (wcqp_tick_info.plan_generated = 0: such a
+ * plan has no known timeline).  WCQP_E_INVALID - checked on the host before anything changes, the handle exactly as it was - for a handle
+ * that is not uploaded, a NULL pointer, first_ds_ticks < 1, and for a robot that replans: n_steps outside 0..K', a side above 1 or a
+ * non-finite target of a step it takes, M_i = 0 or < -1, M_i < the ticks enqueued so far (within one wcqp_tick_run call the kernel reads a
+ * stage ahead, between calls nothing is ahead), M_i >= T, M_i below the stage its current plan was generated from, or a stage M_i that
+ * lies in a single support of its current plan.  Not offered: replanning a classically uploaded plan, per-step timings, device pointers. */
+typedef struct wcqp_tick_replan {         /* HOST pointers, copied before the call returns */
+    const int32_t* merge_stage;           /* [B] M_i >= 1: robot i's plan is regenerated from stage M_i on; -1: robot i keeps its plan */
+    int32_t max_steps;                    /* K': row length of the per-step arrays, >= 0 */
+    const int32_t* n_steps;               /* [B] 0..K' (0 = come to a stop) */
+    const uint8_t* side;                  /* [B][K'] */
+    const double*  target;                /* [B][K'][3] x, y, yaw increment */
+    int32_t first_ds_ticks;               /* >= 1: stages of double support from M_i before the first new step */
+} wcqp_tick_replan;
+int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream);
 /* The plan a planned handle holds, however it was uploaded: n robots from robot0, m stages from stage0, stage-major per robot.
  * Synchronises.  Every pointer but two works on any planned handle, however it was uploaded.  The two: a non-NULL dcm_vel_traj makes
  * the call return WCQP_E_UNSUPPORTED on a handle that keeps no velocity (neither the reactive controller nor gain scheduling), and a

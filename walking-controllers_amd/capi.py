@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host",
-    "wcqp_tick_upload_footsteps", "wcqp_tick_get_plan",
+    "wcqp_tick_upload_footsteps", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
 )
@@ -208,6 +208,12 @@ class TickFootsteps(C.Structure):
                 ("lift", C.c_double), ("zmp_delta_left", C.c_double * 2), ("zmp_delta_right", C.c_double * 2)]
 
 
+class TickReplan(C.Structure):
+    """wcqp_tick_replan: per robot the merge stage (-1: the robot keeps its plan) and the footsteps its plan is regenerated from there."""
+    _fields_ = [("merge_stage", C.c_void_p), ("max_steps", C.c_int32), ("n_steps", C.c_void_p), ("side", C.c_void_p), ("target", C.c_void_p),
+                ("first_ds_ticks", C.c_int32)]
+
+
 PLAN_WINDOW = (("left_traj", (12,), np.float64), ("right_traj", (12,), np.float64), ("left_twist", (6,), np.float64), ("right_twist", (6,), np.float64),
                ("contact", (), np.uint8), ("com_height", (), np.float64), ("com_height_vel", (), np.float64),
                ("ref_traj", (2,), np.float64), ("dcm_vel_traj", (2,), np.float64),
@@ -274,6 +280,7 @@ def lib() -> C.CDLL:
         L.wcqp_tick_get_info.argtypes = [C.c_void_p, C.POINTER(TickInfo)]
         L.wcqp_tick_upload_footsteps.argtypes = [C.c_void_p, C.POINTER(TickInputs), C.POINTER(TickFootsteps)]
         L.wcqp_tick_get_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TickPlanWindow)]
+        L.wcqp_tick_replan_footsteps.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.c_void_p]
         L.wcqp_qp_enqueue_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.POINTER(C.c_int32)]
         L.wcqp_qp_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.c_int32, C.POINTER(C.c_void_p)]
         L.wcqp_qp_plan_enqueue.argtypes = [C.c_void_p, C.c_void_p]
@@ -637,6 +644,23 @@ class TickPipeline:
                            float(footsteps["lift"]), (C.c_double * 2)(*footsteps["zmp_delta_left"]), (C.c_double * 2)(*footsteps["zmp_delta_right"]))
         ins = TickInputs(**{k: (keep[k].ctypes.data if k in keep else None) for k, _ in TickInputs._fields_})
         check(lib().wcqp_tick_upload_footsteps(self._h, C.byref(ins), C.byref(fs)), "wcqp_tick_upload_footsteps")
+
+    def replan_footsteps(self, merge_stage, footsteps: dict, first_ds_ticks: int, stream: Optional[int] = None):
+        """A new goal for a generated walk that is running (wcqp_tick_replan_footsteps, which defines the replanned plan): robot i's plan is
+        regenerated from stage merge_stage[i] on (-1: the robot keeps its plan) from footsteps n_steps [B], side [B][K'], target [B][K'][3],
+        behind first_ds_ticks stages of double support; timings, lift and ZMP deltas stay those of upload_footsteps.  Enqueue-only on
+        `stream`, behind the ticks already enqueued there; the arrays are copied before the call returns."""
+        if not self.planned:
+            raise ValueError("footsteps were given to a handle created without planned_trajectories=True")
+        merge = np.ascontiguousarray(merge_stage, dtype=np.int32)
+        n_steps = np.ascontiguousarray(footsteps["n_steps"], dtype=np.int32)
+        side = np.ascontiguousarray(footsteps["side"], dtype=np.uint8)
+        target = _f64(footsteps["target"])
+        assert merge.shape == (self.batch,) and n_steps.shape == (self.batch,) and side.ndim == 2 and side.shape[0] == self.batch and \
+            target.shape == side.shape + (3,), (merge.shape, n_steps.shape, side.shape, target.shape)
+        rp = TickReplan(merge.ctypes.data, side.shape[1], n_steps.ctypes.data, side.ctypes.data if side.size else None,
+                        target.ctypes.data if target.size else None, int(first_ds_ticks))
+        check(lib().wcqp_tick_replan_footsteps(self._h, C.byref(rp), stream or None), "wcqp_tick_replan_footsteps")
 
     def plan_window(self, robot0: int = 0, n: Optional[int] = None, stage0: int = 0, m: Optional[int] = None) -> dict:
         """The plan a planned handle holds (wcqp_tick_get_plan): n robots from robot0, m stages from stage0 (None: to the end) - left_traj,

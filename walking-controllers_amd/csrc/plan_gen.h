@@ -17,7 +17,9 @@ struct PlanGenDev {
     const unsigned char* side;      // [B][K]
     const double* target;           // [B][K][3]
     const double* state;            // [B][kStateLen]
-    const int* set_base;            // [B] index of the robot's first support-polygon set (sets are numbered robot by robot, stage by stage)
+    const int* set_base;            // [B] index of the support-polygon set the plan's first stage names: an upload's stage-0 set, which the prologue
+                                    // enters, or - a replan - the robot's last surviving set; the plan's own sets follow it (tick.hip: a fixed range of
+                                    // slots per robot)
     double* table;                  // [B][K + 1][kFpRec], written by the prologue
     long long* set_at;              // [sets] record offset (doubles) of each set's stage
     int* set_code;                  // [sets] its contact pair (0 left, 1 right, 2 both)
@@ -29,6 +31,12 @@ struct PlanGenDev {
     int first_ds, ss, ds, final_ds; // stages (final_ds already resolved: never 0)
     double lift, dT, omega, a;      // a = exp(omega dT)
     double delta[2][2];             // zmp_delta_left / zmp_delta_right
+    // wcqp_tick_replan_footsteps only (plan_replan_enqueue; NULL / 0 in an upload): first_ds is then the double support from the merge stage
+    const int* origin;              // [B] the stage M_i robot i's plan is regenerated from (its timeline's stage 0); unread for a robot not listed
+    const int* robots;              // [n_robots] the robots regenerated
+    const int2* tiles;              // [n_tiles] (robot, 64-stage tile) of the record pass: the tiles at or above the robot's origin
+    const double* h0;               // [B] TickDev::com_h0, the CoM height of every stage
+    int n_robots, n_tiles;
 };
 
 }  // namespace wcqp_tick
@@ -36,4 +44,6 @@ struct PlanGenDev {
 namespace wcqp {
 // prologue, DCM pass and record pass of one upload, in stream order (plan_gen.hip); rec0 / rec1 (or NULL): events recorded around the record pass
 int plan_gen_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
+// the same three passes from per-robot origins, over the listed robots and tiles only (wcqp_tick_replan_footsteps); enqueue-only
+int plan_replan_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream);
 }  // namespace wcqp

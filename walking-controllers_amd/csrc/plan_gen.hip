@@ -4,6 +4,10 @@
 //   plan_prologue_kernel   one thread per robot, O(K): the footprint chain (plan_gen.h: kFpRec), the ZMP points, the set table
 //   plan_dcm_kernel        one lane per (robot, axis), serial in the stage: the backward DCM recursion, tiles of stages through LDS
 //   plan_record_kernel     one wave per (robot, 64 stages), one lane per stage: the 320-byte records, through LDS, as whole lines
+// wcqp_tick_replan_footsteps runs the same three bodies with an origin (RP = true): robot i's plan is regenerated from stage M_i =
+// origin[i] on - stage 0 of the rules moved to M_i, the start footprints taken from record M_i, the first double support's ZMP ramp started
+// where the recursion arrives at the old ref_traj[M_i] - over a host-compacted list of robots (prologue, DCM pass) and of (robot, tile)
+// pairs (record pass).  Nothing below M_i is stored: the DCM pass masks its tile write-out per stage, the record pass per 16-byte chunk.
 #include <cmath>
 #include "plan_gen.h"
 
@@ -16,16 +20,22 @@ __device__ __forceinline__ void zmp_point(const double* pose, const double* dl, 
     out[1] = pose[1] + (pose[6] * dl[0] + pose[7] * dl[1]);
 }
 
-__global__ void plan_prologue_kernel(PlanGenDev g) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= g.batch) return;
+template <bool RP>
+__device__ __forceinline__ void plan_prologue(const PlanGenDev& g) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= (RP ? g.n_robots : g.batch)) return;
+    const int i = RP ? g.robots[slot] : slot;
+    const int org = RP ? g.origin[i] : 0;
     const int n = g.n_steps[i], per = g.ss + g.ds;
-    double fp[kFpPose];
-    for (int k = 0; k < kFpPose; ++k) fp[k] = g.state[(size_t)i * kStateLen + 24 + k];      // desired left sole, desired right sole
-    double* tab = g.table + (size_t)i * (size_t)(g.K + 1) * kFpRec;
     const size_t rec0 = (size_t)i * (size_t)g.traj_len;
+    double fp[kFpPose];
+    // desired left sole, desired right sole: of state0, or - a replan - of the record of the merge stage (read here, before the record pass)
+    for (int k = 0; k < kFpPose; ++k) fp[k] = RP ? g.rec[(rec0 + (size_t)org) * kPlanRec + kPlanLeft + k] : g.state[(size_t)i * kStateLen + 24 + k];
+    double* tab = g.table + (size_t)i * (size_t)(g.K + 1) * kFpRec;
+    // set_base: the set the origin stage names - stage 0's own, built here, or the robot's last surviving one, which stays as it is
     int set = g.set_base[i];
-    g.set_at[set] = (long long)(rec0 * kPlanRec); g.set_code[set] = 2; ++set;
+    if (!RP) { g.set_at[set] = (long long)(rec0 * kPlanRec); g.set_code[set] = 2; }
+    ++set;
     for (int j = 0; j <= g.K; ++j) {
         if (j >= 1 && j <= n) {
             // step j - 1 lands: the swing foot's footprint becomes its target, rotated by the yaw increment about z
@@ -41,7 +51,7 @@ __global__ void plan_prologue_kernel(PlanGenDev g) {
                 f[6 + c] = sn * r0 + cs * r1;
             }
             // its two changes of contact pair (the stance foot alone, both again), where a tick can reach them
-            const int s_k = g.first_ds + k * per;
+            const int s_k = org + g.first_ds + k * per;
             if (s_k <= g.max_ticks) { g.set_at[set] = (long long)((rec0 + s_k) * kPlanRec); g.set_code[set] = 1 - sw; ++set; }
             if (s_k + g.ss <= g.max_ticks) { g.set_at[set] = (long long)((rec0 + s_k + g.ss) * kPlanRec); g.set_code[set] = 2; ++set; }
         }
@@ -52,38 +62,66 @@ __global__ void plan_prologue_kernel(PlanGenDev g) {
     }
 }
 
+__global__ void plan_prologue_kernel(PlanGenDev g) { plan_prologue<false>(g); }
+__global__ void plan_prologue_replan_kernel(PlanGenDev g) { plan_prologue<true>(g); }
+
 // ---- the DCM reference: xi_t = (xi_{t+1} - (1 - a) zmp_t) / a backwards from xi = zmp at the first standing stage
 constexpr int kDcmRobots = 32, kDcmTile = 32, kDcmRow = 2 * kDcmTile + 2;
 
-__global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) {
+// RP: lane r of block x carries robot robots[32 x + r]; a lane computes and stores only stages >= its robot's origin, and the serial pass
+// ends at the tile of the wave's lowest origin.  The first double support's ramp starts at the point that makes the recursion arrive at
+// the old ref_traj[origin] (read before the pass stores over it): xi_M = X q^n - (1 - a) (za (S0 - S1) + zb S1), q = 1 / a, n = first_ds,
+// S0 = sum_{j=1..n} q^j, S1 = sum_{j=1..n} j q^j / (n + 1), X the recursion's value at stage M + n - one division where the pass gets there.
+template <bool RP>
+__device__ __forceinline__ void plan_dcm(const PlanGenDev& g) {
     __shared__ double t_xi[kDcmRobots * kDcmRow];
     __shared__ double t_vel[kDcmRobots * kDcmRow];
     const int lane = threadIdx.x, r = lane >> 1, ax = lane & 1;
+    const int count = RP ? g.n_robots : g.batch;
     const int i_raw = blockIdx.x * kDcmRobots + r;
-    const bool live = i_raw < g.batch;
-    const int i = live ? i_raw : g.batch - 1;
+    const bool live = i_raw < count;
+    const int i = RP ? g.robots[live ? i_raw : count - 1] : (live ? i_raw : g.batch - 1);
+    const int org = RP ? g.origin[i] : 0;
     const int n = g.n_steps[i], per = g.ss + g.ds, T = g.traj_len;
-    const int s_end = n > 0 ? g.first_ds + n * per - g.ds + g.final_ds : g.first_ds;      // the first standing stage
+    const int s_end = org + (n > 0 ? g.first_ds + n * per - g.ds + g.final_ds : g.first_ds);      // the first standing stage
     const double* tab = g.table + (size_t)i * (size_t)(g.K + 1) * kFpRec;
     const unsigned char* side = g.side + (size_t)i * g.K;
     const double mid0 = 0.5 * (tab[24 + ax] + tab[26 + ax]);
     const double mid_n = 0.5 * (tab[(size_t)n * kFpRec + 24 + ax] + tab[(size_t)n * kFpRec + 26 + ax]);
+    const double xi_org = RP ? g.ref[((size_t)i * (size_t)T + (size_t)org) * 2 + ax] : 0.0;
     int top = s_end > T ? s_end : T;
     for (int m = 1; m < 64; m <<= 1) { const int o = __shfl_xor(top, m); top = o > top ? o : top; }
+    int bottom = 0;
+    if (RP) {
+        bottom = org;
+        for (int m = 1; m < 64; m <<= 1) { const int o = __shfl_xor(bottom, m); bottom = o < bottom ? o : bottom; }
+        bottom &= ~(kDcmTile - 1);
+    }
     const double a = g.a, b1 = 1.0 - g.a;
     double xi = mid_n;
     int key = -2;                     // the segment za / zb belong to: -1 the first double support, 2 k single support of step k, 2 k + 1 the double support behind it
     double za = 0.0, zb = 0.0;
-    for (int t = top - 1; t >= 0; --t) {
-        double z;
-        if (t >= s_end) {
+    for (int t = top - 1; t >= bottom; --t) {
+        double z = 0.0;
+        const int tr = t - org;       // the stage on the plan's own timeline
+        if (RP && tr < 0) {
+            // (below this lane's origin: nothing to compute, nothing of it is stored)
+        } else if (t >= s_end) {
             z = mid_n; xi = mid_n;
         } else {
-            if (t < g.first_ds) {
-                if (key != -1) { key = -1; za = mid0; zb = n > 0 ? tab[24 + 2 * (1 - side[0]) + ax] : mid0; }
-                z = za + ((double)(t + 1) / (double)(g.first_ds + 1)) * (zb - za);
+            if (tr < g.first_ds) {
+                if (key != -1) {
+                    key = -1; za = mid0; zb = n > 0 ? tab[24 + 2 * (1 - side[0]) + ax] : mid0;
+                    if (RP) {
+                        const double nn = (double)g.first_ds, q = 1.0 / a, qn = pow(q, nn);
+                        const double S0 = q * (1.0 - qn) / (1.0 - q);
+                        const double S1 = q * (1.0 - (nn + 1.0) * qn + nn * qn * q) / ((1.0 - q) * (1.0 - q) * (nn + 1.0));
+                        za = (xi * qn - b1 * zb * S1 - xi_org) / (b1 * (S0 - S1));
+                    }
+                }
+                z = za + ((double)(tr + 1) / (double)(g.first_ds + 1)) * (zb - za);
             } else {
-                const int rr = t - g.first_ds;
+                const int rr = tr - g.first_ds;
                 int k = rr / per;
                 k = k < n - 1 ? k : n - 1;
                 const int u = rr - k * per;
@@ -107,7 +145,7 @@ __global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) {
         const int tt = t & (kDcmTile - 1);
         t_xi[r * kDcmRow + 2 * tt + ax] = xi;
         t_vel[r * kDcmRow + 2 * tt + ax] = g.omega * (xi - z);
-        if (t == 0 && live) g.zmp0[2 * (size_t)i + ax] = z;
+        if (!RP && t == 0 && live) g.zmp0[2 * (size_t)i + ax] = z;
         if (tt != 0) continue;
         // stages [t, hi) of the block's robots: each robot's tile is contiguous in HBM, 32 lanes write it 16 bytes each
         __syncthreads();
@@ -115,8 +153,10 @@ __global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) {
         const int q = lane & 31;
         for (int r0 = 0; r0 < kDcmRobots; r0 += 2) {
             const int ro = r0 + (lane >> 5);
-            const long io = (long)blockIdx.x * kDcmRobots + ro;
-            if (io >= g.batch || t + q >= hi) continue;
+            const long so = (long)blockIdx.x * kDcmRobots + ro;
+            if (so >= count || t + q >= hi) continue;
+            const long io = RP ? (long)g.robots[so] : so;
+            if (RP && t + q < g.origin[io]) continue;       // (the tile that straddles the robot's origin: only stages >= it)
             const size_t w = ((size_t)io * (size_t)T + (size_t)(t + q)) * 2;
             *reinterpret_cast<double2*>(g.ref + w) = make_double2(t_xi[ro * kDcmRow + 2 * q], t_xi[ro * kDcmRow + 2 * q + 1]);
             if (g.vel) *reinterpret_cast<double2*>(g.vel + w) = make_double2(t_vel[ro * kDcmRow + 2 * q], t_vel[ro * kDcmRow + 2 * q + 1]);
@@ -125,6 +165,9 @@ __global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) {
     }
 }
 
+__global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) { plan_dcm<false>(g); }
+__global__ __launch_bounds__(64) void plan_dcm_replan_kernel(PlanGenDev g) { plan_dcm<true>(g); }
+
 // ---- the records.  A wave takes 64 consecutive stages of one robot - 20 KiB of records, contiguous in HBM and 64-byte aligned (a record
 // is five lines): lane l computes stage s0 + l into row l of an LDS tile (rows of 41 doubles: the 8-byte LDS stores of 16 lanes fall on
 // 16 different bank pairs), then the wave writes the tile out 16 bytes per lane, 1 KiB - sixteen whole lines - per store instruction.
@@ -132,23 +175,29 @@ __global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) {
 // so 64 stages touch at most 34 entries.
 constexpr int kRecTile = 64, kRecRow = kPlanRec + 1, kTabMax = kRecTile / 2 + 2;
 
-__global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) {
+// RP: block x takes entry x of the host's (robot, tile) list - the tiles at or above the robot's origin; in the tile that straddles it the
+// lanes below the origin compute nothing and the write-out skips their records (a record is twenty 16-byte chunks, none shared with a
+// neighbour).  Before the new plan's first single support the fixed-frame bit keeps the value of stage origin - 1, a record no replan
+// of this origin writes.
+template <bool RP>
+__device__ __forceinline__ void plan_record(const PlanGenDev& g) {
     __shared__ double tile[kRecTile * kRecRow];
     __shared__ double fpt[kTabMax * kFpPose];
     __shared__ double dyaw[kTabMax];
     __shared__ int swing[kTabMax];
     const int lane = threadIdx.x;
-    const size_t i = blockIdx.y;
-    const int T = g.traj_len, s0 = blockIdx.x * kRecTile;
+    const size_t i = RP ? (size_t)g.tiles[blockIdx.x].x : (size_t)blockIdx.y;
+    const int org = RP ? g.origin[i] : 0;
+    const int T = g.traj_len, s0 = (RP ? g.tiles[blockIdx.x].y : (int)blockIdx.x) * kRecTile;
     const int nvalid = T - s0 < kRecTile ? T - s0 : kRecTile;
     const int n = g.n_steps[i], per = g.ss + g.ds;
     // entries j_lo .. j_hi: from the step the first stage lies in (the last step's, once standing: its stance foot is the fixed frame) to the
-    // footprints behind the step the last stage lies in
+    // footprints behind the step the last stage lies in (stages on the plan's own timeline: the origin is its stage 0)
     auto step_of = [&](int s) { return s < g.first_ds ? 0 : (s - g.first_ds) / per; };
     const int last = n > 0 ? n - 1 : 0;
-    int j_lo = step_of(s0);
+    int j_lo = step_of((RP && s0 < org ? org : s0) - org);
     j_lo = j_lo < last ? j_lo : last;
-    int j_hi = step_of(s0 + nvalid - 1) + 1;
+    int j_hi = step_of(s0 + nvalid - 1 - org) + 1;
     j_hi = j_hi < n ? j_hi : n;
     int cnt = j_hi - j_lo + 1;
     cnt = cnt < kTabMax ? cnt : kTabMax;
@@ -158,12 +207,14 @@ __global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) {
         swing[lane] = g.side[i * g.K + j_lo + lane];
         dyaw[lane] = g.target[(i * g.K + j_lo + lane) * 3 + 2];
     }
+    int fixed0 = 0;
+    if (RP) fixed0 = ((int)g.rec[(i * (size_t)T + (size_t)(org - 1)) * kPlanRec + kPlanFlags] & 4) ? 0 : 1;
     __syncthreads();
-    const int s = s0 + lane;
-    if (lane < nvalid) {
+    const int s = s0 + lane, sr = s - org;
+    if (lane < nvalid && sr >= 0) {
         double* o = tile + lane * kRecRow;
         int k = -1, u = 0;
-        if (s >= g.first_ds) { k = (s - g.first_ds) / per; u = (s - g.first_ds) - k * per; }
+        if (sr >= g.first_ds) { k = (sr - g.first_ds) / per; u = (sr - g.first_ds) - k * per; }
         const bool swinging = k >= 0 && k < n && u < g.ss;
         // the footprints in force: after k + 1 landed steps, or - the swing foot still in the air - after k
         int j = k < 0 ? 0 : (k < n ? k + (swinging ? 0 : 1) : n);
@@ -172,7 +223,7 @@ __global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) {
         const double* f = fpt + j * kFpPose;
         for (int e = 0; e < kFpPose; ++e) o[kPlanLeft + e] = f[e];
         for (int e = 0; e < 12; ++e) o[kPlanTwL + e] = 0.0;
-        int flags = 3, fixed = 0;
+        int flags = 3, fixed = fixed0;
         if (k >= 0 && n > 0) { const int kl = k < n ? k : n - 1; fixed = 1 - swing[kl - j_lo < cnt ? kl - j_lo : cnt - 1]; }
         if (swinging) {
             const int sw = swing[k - j_lo < cnt ? k - j_lo : cnt - 1];
@@ -198,10 +249,10 @@ __global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) {
             flags = sw == 1 ? 1 : 2;
         }
         o[kPlanFlags] = (double)(flags | (fixed == 0 ? 4 : 0));
-        o[kPlanHeight] = g.state[i * kStateLen + 68];
+        o[kPlanHeight] = RP ? g.h0[i] : g.state[i * kStateLen + 68];
         o[kPlanHeightVel] = 0.0;
-        // the support-polygon set in force: stage 0's, plus the changes of contact pair up to this stage that a tick can reach
-        const int se = s < g.max_ticks ? s : g.max_ticks;
+        // the support-polygon set in force: the origin's, plus the changes of contact pair up to this stage that a tick can reach
+        const int se = (s < g.max_ticks ? s : g.max_ticks) - org;
         int changes = 0;
         if (se >= g.first_ds) {
             const int ke = (se - g.first_ds) / per, ue = (se - g.first_ds) - ke * per;
@@ -214,9 +265,13 @@ __global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) {
     const int total = nvalid * kPlanRec;
     for (int x = 2 * lane; x < total; x += 2 * kRecTile) {
         const int st = x / kPlanRec, e = x - st * kPlanRec;
+        if (RP && s0 + st < org) continue;
         *reinterpret_cast<double2*>(out + x) = make_double2(tile[st * kRecRow + e], tile[st * kRecRow + e + 1]);
     }
 }
+
+__global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) { plan_record<false>(g); }
+__global__ __launch_bounds__(kRecTile) void plan_record_replan_kernel(PlanGenDev g) { plan_record<true>(g); }
 
 }  // namespace
 
@@ -236,6 +291,18 @@ int plan_gen_enqueue(const PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, h
         hipLaunchKernelGGL(plan_record_kernel, dim3((unsigned)((g.traj_len + kRecTile - 1) / kRecTile), (unsigned)nb), dim3(kRecTile), 0, stream, p);
     }
     if (rec1) WCQP_HIP_TRY(hipEventRecord(rec1, stream));
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+
+
+int plan_replan_enqueue(const PlanGenDev& g, hipStream_t stream) {
+    if (g.batch < 1 || g.traj_len < 1 || g.ss < 1 || g.ds < 1 || g.first_ds < 1 || g.final_ds < 1 || g.K < 0) return WCQP_E_INVALID;
+    if (!g.origin || !g.robots || !g.tiles || !g.h0 || g.n_robots < 0 || g.n_tiles < 0) return WCQP_E_INVALID;
+    if (g.n_robots == 0) return WCQP_OK;
+    hipLaunchKernelGGL(plan_prologue_replan_kernel, dim3((unsigned)((g.n_robots + 63) / 64)), dim3(64), 0, stream, g);
+    hipLaunchKernelGGL(plan_dcm_replan_kernel, dim3((unsigned)((g.n_robots + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, g);
+    if (g.n_tiles > 0) hipLaunchKernelGGL(plan_record_replan_kernel, dim3((unsigned)g.n_tiles), dim3(kRecTile), 0, stream, g);
     WCQP_HIP_TRY(hipGetLastError());
     return WCQP_OK;
 }

@@ -91,6 +91,7 @@ __global__ void plan_hull_sets_kernel(int n, PlanRect rect, const double* __rest
                                       const int* __restrict__ code, double* __restrict__ A, double* __restrict__ b, int* __restrict__ nc) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
+    if (code[g] < 0) return;        // (a slot no set of this call occupies: generated plans keep a fixed range of slots per robot)
     const double* r = rec + at[g];
     double px[8], py[8];
     int np = 0;
@@ -280,6 +281,18 @@ struct wcqp_tick_s {
     // wcqp_tick_upload_footsteps: the generated ZMP of stage 0 [B][2] (allocated by the first such upload), and whether the plan in place was generated
     double* gen_zmp0 = nullptr; bool generated = false;
     hipEvent_t gen_ev[2] = {nullptr, nullptr}; float gen_record_ms = 0.0f;     // the record pass of the last such upload, timed (wcqp_tick_info.plan_record_ms)
+    // wcqp_tick_replan_footsteps: what the last wcqp_tick_upload_footsteps fixed for the handle - the timings, lift and deltas, and `cap`, the
+    // slots of the set arrays each robot owns (robot i: [i cap, (i + 1) cap)) - and per robot the plan in force: the stage it was generated
+    // from, its first double support and step count, and `keep`, the robot's slots in use by sets of stages <= that origin
+    struct GenPlan {
+        int ss = 0, ds = 0, final_ds = 0, cap = 0;
+        double lift = 0.0, delta[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        std::vector<int> origin, first_ds, n_steps, keep;
+    } gp;
+    // its per-call device memory (footsteps, robot and tile lists, footprint tables, set table): one block that only grows; rp_done, recorded
+    // behind the call's kernels, guards it as splice_done guards the staging rows
+    char* rp_buf = nullptr; size_t rp_cap = 0;
+    hipEvent_t rp_done = nullptr; bool rp_pending = false;
     // streamed_trajectories (an EXTERNAL handle): pl.rec holds ONE record per robot, the stage wcqp_tick_set_desired_* handed over for the next
     // tick, pl.set_* one row set per robot; `planned` stays false (the splice of the DCM reference keeps working)
     bool streamed = false, desired_set = false;
@@ -576,6 +589,8 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
     if (h->splice_stage) (void)hipFree(h->splice_stage);
     if (h->splice_done) (void)hipEventDestroy(h->splice_done);
+    if (h->rp_buf) (void)hipFree(h->rp_buf);
+    if (h->rp_done) (void)hipEventDestroy(h->rp_done);
     if (h->run_done) (void)hipEventDestroy(h->run_done);
     for (hipEvent_t e : h->gen_ev) if (e) (void)hipEventDestroy(e);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -850,20 +865,19 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     if (!std::isfinite(steps->lift) || !finite(steps->zmp_delta_left, 2) || !finite(steps->zmp_delta_right, 2)) return WCQP_E_INVALID;
     if (!finite(in->q0, B * kDof) || !finite(in->com0, B * 2) || (in->dcm0 && !finite(in->dcm0, B * 2)) || (in->u_init && !finite(in->u_init, B * 2)))
         return WCQP_E_INVALID;
-    // the support-polygon sets, robot by robot: stage 0's, then two per step - the stance foot alone, both again - where a tick can reach them
+    // the support-polygon sets: every robot owns `cap` slots - stage 0's set, then two per step (the stance foot alone, both again) where a
+    // tick can reach them.  A step occupies ss + 1 stages or more, so at most (max_ticks + 1) / (ss + 1) + 1 steps start at a stage
+    // <= max_ticks, whatever wcqp_tick_replan_footsteps later stitches together: the range never has to grow, and no set ever moves
+    const int cap = 1 + 2 * ((h->p.max_ticks + 1) / (steps->ss_ticks + 1) + 1);
     std::vector<int> set_base(B);
-    size_t ns = 0;
+    const size_t ns = B * (size_t)cap;
     for (size_t i = 0; i < B; ++i) {
         const int n = steps->n_steps[i];
         if (n < 0 || n > K) return WCQP_E_INVALID;
         if (!finite(in->state0 + i * kStateLen + 24, 24) || !std::isfinite(in->state0[i * kStateLen + 68])) return WCQP_E_INVALID;
-        set_base[i] = (int)ns;
-        ns += 1;
-        for (int k = 0; k < n; ++k) {
+        set_base[i] = (int)(i * (size_t)cap);
+        for (int k = 0; k < n; ++k)
             if (steps->side[i * K + k] > 1 || !finite(steps->target + (i * K + k) * 3, 3)) return WCQP_E_INVALID;
-            const long long s_k = steps->first_ds_ticks + k * per;
-            ns += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + steps->ss_ticks <= h->p.max_ticks ? 1 : 0);
-        }
     }
     if (ns > (size_t)1 << 30) return WCQP_E_UNSUPPORTED;
     // from here on the device state changes: a call that fails on the way leaves the handle unrunnable until the next good upload
@@ -883,6 +897,7 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     double* d_tab = static_cast<double*>(scratch.get(B * (size_t)(K + 1) * kFpRec * 8));
     long long* d_at = static_cast<long long*>(scratch.get(ns * 8)); int* d_code = static_cast<int*>(scratch.get(ns * 4));
     if (!d_n || !d_base || !d_side || !d_tg || !d_tab || !d_at || !d_code) return WCQP_E_NOMEM;
+    WCQP_HIP_TRY(hipMemset(d_code, 0xff, ns * 4));      // (-1: a slot without a set; the prologue enters the ones in use)
     WCQP_HIP_TRY(hipMemcpy(d_n, steps->n_steps, B * 4, hipMemcpyHostToDevice));
     WCQP_HIP_TRY(hipMemcpy(d_base, set_base.data(), B * 4, hipMemcpyHostToDevice));
     if (BK > 0) {
@@ -905,6 +920,14 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     WCQP_HIP_TRY(hipEventElapsedTime(&h->gen_record_ms, h->gen_ev[0], h->gen_ev[1]));
     h->vel_explicit = g.vel != nullptr;       // (the generated velocities, where the handle keeps any: the splice has no tail for them)
     h->generated = true;
+    {   // what a replan needs to know of this plan (wcqp_tick_replan_footsteps)
+        auto& gp = h->gp;
+        gp.ss = steps->ss_ticks; gp.ds = steps->ds_ticks; gp.final_ds = final_ds; gp.cap = cap; gp.lift = steps->lift;
+        for (int k = 0; k < 2; ++k) { gp.delta[0][k] = steps->zmp_delta_left[k]; gp.delta[1][k] = steps->zmp_delta_right[k]; }
+        gp.origin.assign(B, 0); gp.first_ds.assign(B, steps->first_ds_ticks); gp.keep.assign(B, 1);
+        gp.n_steps.assign(steps->n_steps, steps->n_steps + B);
+        h->rp_pending = false;      // (the device was synchronised above)
+    }
     WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
     WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
     // dcm0 / u_init NULL: the generated DCM reference and ZMP of stage 0
@@ -921,6 +944,116 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
         eff.u_init = u0.data();
     }
     return upload_state(h, &eff, 2);
+}
+
+int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) {
+    if (!h || !rp) return WCQP_E_INVALID;
+    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    if (!h->uploaded) return WCQP_E_INVALID;
+    if (!h->generated) return WCQP_E_UNSUPPORTED;        // (a classically uploaded plan has no known timeline)
+    const TickDev& d = h->d;
+    auto& gp = h->gp;
+    const size_t B = (size_t)d.batch;
+    const int K = rp->max_steps, T = d.traj_len, fd = rp->first_ds_ticks, per = gp.ss + gp.ds, cap = gp.cap;
+    // everything is checked here, in closed form, before anything changes: a refused call leaves the handle exactly as it was
+    if (!rp->merge_stage || !rp->n_steps || K < 0 || (K > 0 && (!rp->side || !rp->target)) || fd < 1) return WCQP_E_INVALID;
+    if ((long long)T + fd + (long long)K * per + gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    std::vector<int> robots, keep(B, 0);
+    std::vector<int> tiles;       // (robot, tile) pairs
+    const int n_tile = (T + 63) / 64;
+    for (size_t i = 0; i < B; ++i) {
+        const int M = rp->merge_stage[i];
+        if (M == -1) continue;                            // (the robot keeps its plan: nothing of its rows is read)
+        // stage 0 is the initial state's, stages the enqueued ticks have consumed stay (within one wcqp_tick_run call the kernel reads a stage
+        // ahead, between calls nothing is ahead: M >= ticks_enqueued is the condition), and a plan is cut only behind its own origin
+        if (M < 1 || M < h->ticks_enqueued || M >= T || M < gp.origin[i]) return WCQP_E_INVALID;
+        const int n = rp->n_steps[i];
+        if (n < 0 || n > K) return WCQP_E_INVALID;
+        for (int k = 0; k < n; ++k) {
+            if (rp->side[i * K + k] > 1) return WCQP_E_INVALID;
+            for (int c = 0; c < 3; ++c) if (!std::isfinite(rp->target[(i * K + k) * 3 + c])) return WCQP_E_INVALID;
+        }
+        // the merge stage has both feet in contact in the plan in force: not inside one of its single supports
+        const int O = gp.origin[i], fo = gp.first_ds[i], no = gp.n_steps[i], r = M - O;
+        if (r >= fo) { const int k = (r - fo) / per, u = (r - fo) - k * per; if (k < no && u < gp.ss) return WCQP_E_INVALID; }
+        // the sets that survive: those of stages <= M (a set of stage M itself is built from the feet the new plan starts from)
+        int c0 = gp.keep[i];
+        const int reach = M < h->p.max_ticks ? M : h->p.max_ticks;
+        for (int k = 0; k < no; ++k) {
+            const long long s_k = (long long)O + fo + (long long)k * per;
+            c0 += (s_k <= reach ? 1 : 0) + (s_k + gp.ss <= reach ? 1 : 0);
+        }
+        int fresh = 0;
+        for (int k = 0; k < n; ++k) {
+            const long long s_k = (long long)M + fd + (long long)k * per;
+            fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + gp.ss <= h->p.max_ticks ? 1 : 0);
+        }
+        if (c0 < 1 || c0 + fresh > cap) return WCQP_E_INVALID;      // (cannot happen: see cap in wcqp_tick_upload_footsteps)
+        keep[i] = c0;
+        robots.push_back((int)i);
+        for (int tl = M / 64; tl < n_tile; ++tl) { tiles.push_back((int)i); tiles.push_back(tl); }
+    }
+    if (robots.empty()) return WCQP_OK;
+    // the call's device memory: what the host hands over first (one copy), then what the kernels write for each other
+    const size_t BK = B * (size_t)K, nr = robots.size(), nt = tiles.size() / 2, nslots = B * (size_t)cap;
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_org = carve(B * 4), o_n = carve(B * 4), o_base = carve(B * 4), o_rob = carve(nr * 4), o_tile = carve(nt * 8), o_side = carve(BK),
+                 o_tg = carve(BK * 24), front = off, o_tab = carve(B * (size_t)(K + 1) * kFpRec * 8), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
+    std::vector<char> blob(front, 0);
+    {
+        int* org = reinterpret_cast<int*>(blob.data() + o_org); int* nn = reinterpret_cast<int*>(blob.data() + o_n);
+        int* base = reinterpret_cast<int*>(blob.data() + o_base);
+        for (size_t i = 0; i < B; ++i) {
+            const bool on = rp->merge_stage[i] != -1;
+            org[i] = on ? rp->merge_stage[i] : -1; nn[i] = on ? rp->n_steps[i] : 0;
+            base[i] = (int)(i * (size_t)cap) + (on ? keep[i] - 1 : 0);
+        }
+        std::memcpy(blob.data() + o_rob, robots.data(), nr * 4); std::memcpy(blob.data() + o_tile, tiles.data(), nt * 8);
+        if (BK > 0) { std::memcpy(blob.data() + o_side, rp->side, BK); std::memcpy(blob.data() + o_tg, rp->target, BK * 24); }
+    }
+    if (!h->copy_stream) WCQP_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    if (!h->rp_done) WCQP_HIP_TRY(hipEventCreateWithFlags(&h->rp_done, hipEventDisableTiming));
+    if (h->rp_pending) { WCQP_HIP_TRY(hipEventSynchronize(h->rp_done)); h->rp_pending = false; }      // the previous replan has left the block
+    if (off > h->rp_cap) {
+        if (h->rp_buf) { (void)hipFree(h->rp_buf); h->rp_buf = nullptr; h->rp_cap = 0; }
+        void* p = nullptr;
+        if (hipMalloc(&p, off) != hipSuccess) return WCQP_E_NOMEM;
+        h->rp_buf = static_cast<char*>(p); h->rp_cap = off;
+    }
+    char* buf = h->rp_buf;
+    // the caller's HOST arrays are taken NOW (a copy stream of the handle's own, waited for before this call returns)
+    WCQP_HIP_TRY(hipMemcpyAsync(buf, blob.data(), front, hipMemcpyHostToDevice, h->copy_stream));
+    WCQP_HIP_TRY(hipStreamSynchronize(h->copy_stream));
+    PlanGenDev g{};
+    g.origin = reinterpret_cast<const int*>(buf + o_org); g.n_steps = reinterpret_cast<const int*>(buf + o_n);
+    g.set_base = reinterpret_cast<const int*>(buf + o_base); g.robots = reinterpret_cast<const int*>(buf + o_rob);
+    g.tiles = reinterpret_cast<const int2*>(buf + o_tile); g.side = reinterpret_cast<const unsigned char*>(buf + o_side);
+    g.target = reinterpret_cast<const double*>(buf + o_tg); g.table = reinterpret_cast<double*>(buf + o_tab);
+    g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = reinterpret_cast<int*>(buf + o_code);
+    g.state = d.state; g.h0 = d.com_h0.get();
+    g.rec = const_cast<double*>(h->pl.rec.get()); g.ref = const_cast<double*>(d.ref_traj.get());
+    g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
+    g.zmp0 = h->gen_zmp0;
+    g.batch = d.batch; g.K = K; g.traj_len = T; g.max_ticks = h->p.max_ticks; g.n_robots = (int)nr; g.n_tiles = (int)nt;
+    g.first_ds = fd; g.ss = gp.ss; g.ds = gp.ds; g.final_ds = gp.final_ds;
+    g.lift = gp.lift; g.dT = d.dT; g.omega = d.omega; g.a = std::exp(d.omega * d.dT);
+    for (int k = 0; k < 2; ++k) { g.delta[0][k] = gp.delta[0][k]; g.delta[1][k] = gp.delta[1][k]; }
+    // in the caller's stream order, behind the ticks already enqueued: no pointer a tick or a captured graph holds changes, and the set
+    // slots written are those past each robot's surviving ones, which no stage below its merge stage names
+    hipStream_t st = (hipStream_t)stream;
+    WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
+    const int rc = wcqp::plan_replan_enqueue(g, st);
+    if (rc != WCQP_OK) return rc;
+    PlanRect r;
+    for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
+    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, r, h->pl.rec.get(), g.set_at, g.set_code,
+                       h->set_A, h->set_b, h->set_nc);
+    WCQP_HIP_TRY(hipGetLastError());
+    WCQP_HIP_TRY(hipEventRecord(h->rp_done, st));
+    h->rp_pending = true;
+    for (int i : robots) { gp.origin[i] = rp->merge_stage[i]; gp.first_ds[i] = fd; gp.n_steps[i] = rp->n_steps[i]; gp.keep[i] = keep[i]; }
+    return WCQP_OK;
 }
 
 int wcqp_tick_get_plan(wcqp_tick_t h, int32_t robot0, int32_t n, int32_t stage0, int32_t m, const wcqp_tick_plan_window* out) {

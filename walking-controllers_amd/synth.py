@@ -635,3 +635,40 @@ def synth_footstep_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_b
                 ds_ticks=ds_ticks, final_ds_ticks=(T + 4 * step_ticks) - last_ss_end, lift=lift, zmp_delta_left=ZMP_DELTA[0],
                 zmp_delta_right=ZMP_DELTA[1], state0=np.ascontiguousarray(state0), q0=np.ascontiguousarray(kin_batch["q"]),
                 com0=np.ascontiguousarray(state0[:, o["com"]:o["com"] + 2].copy()))
+
+
+def synth_footstep_replan_batch(fs: dict, after_step: int = 2, ds_offset: int = 0, n_steps: int = 3, seed: int = 777,
+                                step_length=(0.02, 0.03), yaw_step=(-0.04, 0.04)) -> dict:
+    """A new goal for the walk of synth_footstep_walk_batch (`fs`), merged in the double support behind its step `after_step` (1-based),
+    `ds_offset` stages into it - what `TickPipeline.replan_footsteps(merge_stage, footsteps, first_ds_ticks)` takes: merge_stage [B],
+    n_steps [B], side [B][n_steps], target [B][n_steps][3] and first_ds_ticks, the rest of that double support.  The feet go on alternating
+    from the footprints `after_step` landed steps leave, with a step length and a heading change per step drawn anew per robot."""
+    count, K = fs["side"].shape
+    ss, ds = int(fs["ss_ticks"]), int(fs["ds_ticks"])
+    assert 1 <= after_step <= K and 0 <= ds_offset < ds and np.all(np.asarray(fs["n_steps"]) > after_step - 1)
+    rng = CounterRNG(seed ^ 0x9E91A, int(fs.get("first", 0)), count)
+    L = step_length[0] + (step_length[1] - step_length[0]) * rng.uniform(1)[:, 0]
+    dyaw = yaw_step[0] + (yaw_step[1] - yaw_step[0]) * rng.uniform(1)[:, 0]
+    o = IK_STATE_OFFSETS
+    merge = np.full(count, int(fs["first_ds_ticks"]) + (after_step - 1) * (ss + ds) + ss + ds_offset, np.int32)
+    side = np.zeros((count, n_steps), np.uint8)
+    target = np.zeros((count, n_steps, 3))
+    for i in range(count):
+        st = fs["state0"][i]
+        p = [st[o["pd_left"]:o["pd_left"] + 2].copy(), st[o["pd_right"]:o["pd_right"] + 2].copy()]
+        yaw = [np.arctan2(st[o["Rd_left"] + 3], st[o["Rd_left"]]), np.arctan2(st[o["Rd_right"] + 3], st[o["Rd_right"]])]
+        for k in range(after_step):              # the footprints at the merge stage
+            sw = int(fs["side"][i, k])
+            p[sw] = np.array(fs["target"][i, k, :2]); yaw[sw] += fs["target"][i, k, 2]
+        sw = 1 - int(fs["side"][i, after_step - 1])
+        half_w = 0.5 * np.linalg.norm(p[0] - p[1])
+        heading = 0.5 * (yaw[0] + yaw[1])
+        for k in range(n_steps):
+            heading += dyaw[i]
+            fwd = np.array([np.cos(heading), np.sin(heading)]); lat = np.array([-np.sin(heading), np.cos(heading)])
+            pt = p[1 - sw] + L[i] * fwd + (2 * half_w) * lat * (1.0 if sw == 0 else -1.0)
+            side[i, k] = sw
+            target[i, k] = (pt[0], pt[1], heading - yaw[sw])
+            p[sw] = pt; yaw[sw] = heading
+            sw = 1 - sw
+    return dict(merge_stage=merge, n_steps=np.full(count, n_steps, np.int32), side=side, target=target, first_ds_ticks=ds - ds_offset)
