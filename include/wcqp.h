@@ -430,6 +430,86 @@ int wcqp_kin_jacobians_host(wcqp_kin_t h, int32_t batch, const double* base, con
                             double* J_left, double* J_right, double* J_neck, double* J_com, double* state);
 
 /* =====================================================================================
+ * Batched non-linear inverse kinematics (SURVEY.md component #11): the posture a robot's walk starts from - what
+ * WalkingModule::prepareRobot (WM/src/WalkingModule.cpp:880-1005; the targets and the neck rule :944-984) obtains from
+ * WalkingIK::computeIK (WM/src/WalkingInverseKinematics.cpp:239-305, 346-424), an iDynTree / IPOPT non-linear IK with the left sole as
+ * the fixed base, the right sole and the CoM as full constraints, a joint regularisation and a neck rotation target as costs and the
+ * model's joint limits as bounds.  iDynTree's InverseKinematics and IPOPT are upstream of the reference: THE PROBLEM AND THE ITERATION
+ * ARE THIS BUILD'S OWN DEFINITION, stated here (tests/helpers/prepare_spec.py restates them in numpy).
+ *
+ * The problem, per robot.  Unknowns: the joints q [dof].  The base is no unknown: the left sole is anchored at its desired pose T_L
+ * (world_T_base = T_L * (base_T_leftsole(q))^-1, as the tick's kinematics anchor the stance foot).
+ *     minimise    w_q/2 |q - q_reg|^2  +  w_n/2 |log(R_neck(q) Rd_neck^T)|^2
+ *     subject to  p_right(q) = pd_right,   log(R_right(q) Rd_right^T) = 0,   com(q) = com_d (x, y and height),   q_min <= q <= q_max
+ * log is the rotation vector of a rotation matrix.  The gradient of the neck term with respect to a world angular velocity is taken to
+ * be that vector itself (exact to first order in it), so the cost gradient is w_q (q - q_reg) + w_n Jn^T phi_n with Jn the anchored
+ * neck Jacobian (angular rows).  w_n = 0 switches the neck target off (no `additional_frame`); q_min / q_max NULL: no limits.
+ *
+ * The iteration (the contract is the optimum it stops at, not its path).  With the left sole anchored every MIXED Jacobian is reduced
+ * to the joints: J~ = J[:, 6:] - J[:, :6] (J_left[:, :6])^-1 J_left[:, 6:].  The guess is first clipped into the limits.  One
+ * iteration solves exactly this QP for dq:
+ *     minimise  1/2 dq^T H dq + g^T dq,   H = w_q I + w_n Jn~^T Jn~,   g = w_q (q - q_reg) + w_n Jn~^T phi_n
+ *     s. t.     [JR~; Jc~] dq = -c   (nine rows: c = p_right - pd_right | log(R_right Rd_right^T) | com - com_d)
+ *               q_min - q <= dq <= q_max - q
+ * and steps q += min(1, step_cap / max|dq|) dq.  The step cap is no part of the QP (far from the target it would make it infeasible).
+ * A robot stops WCQP_STATUS_SOLVED when max|dq| < tol_step and max|c| < tol_constraint; a QP whose equality rows and active bounds are
+ * dependent ends WCQP_STATUS_INFEASIBLE, one whose Hessian is not positive definite WCQP_STATUS_NUMERIC, max_iter iterations spent
+ * WCQP_STATUS_MAX_ITER.  For every status other than SOLVED q comes back as the CLIPPED GUESS, never a half-converged iterate.
+ * Non-finite inputs (the header's contract): a NaN or an Inf in a robot's targets or guess gives WCQP_STATUS_NUMERIC, q = the guess with
+ * every non-finite entry replaced by 0 and clipped, iters = 0, residual = +inf; the other robots do not notice.
+ *
+ * DEVIATIONS from the reference, all upstream of it and unpinned: iDynTree's roll-pitch-yaw parametrisation of the rotation targets,
+ * its internal cost scaling and IPOPT's path are not reproduced; the reference's 1e-4 tolerances are parameters here (1e-4 is a legal
+ * setting); the CoM weight 100 of setCOMTarget has no effect on a hard constraint and is not taken; the reference expresses everything in
+ * the left-sole frame, here the same problem is stated in the world frame with the sole anchored.
+ * ===================================================================================== */
+typedef struct wcqp_prepare_params {  /* every value is taken as given (no 0 -> default; capi.PrepareSolver holds the defaults) */
+    double  w_q;                         /* joint_regularization_weight (inverseKinematics.ini), reference 0.5; > 0                 */
+    double  w_n;                         /* weight of the neck rotation target, reference 1.0; 0 = off; >= 0                        */
+    double  step_cap;                    /* largest joint step of an iteration [rad], default 0.3; > 0                              */
+    double  tol_step;                    /* default 1e-12; >= 0                                                                     */
+    double  tol_constraint;              /* default 1e-10; >= 0                                                                     */
+    int32_t max_iter;                    /* default 100; >= 1                                                                       */
+    const double* q_reg;                 /* [dof] jointRegularization, rad; HOST pointer, copied at create                          */
+    const double* q_min;                 /* [dof] joint limits, HOST pointers copied at create; both NULL: no limits                */
+    const double* q_max;
+} wcqp_prepare_params;
+
+typedef struct wcqp_prepare_s* wcqp_prepare_t;
+
+/* WalkingIK::initialize (WM/src/WalkingInverseKinematics.cpp:25-237).  The handle copies the model out of `kin` (which may be destroyed
+ * afterwards).  WCQP_E_INVALID for a NULL kin, params, q_reg or out, a non-finite weight, tolerance or step cap or one outside the ranges
+ * above, a non-finite q_reg, only one of q_min / q_max, q_min > q_max or a NaN limit, max_iter < 1; WCQP_E_UNSUPPORTED for a tree the 16-lane walk of the tick's
+ * fused kinematics cannot run (wcqp_tick_params.kin_handoff: 23 joints, depth-first numbering, depth <= 8, every joint on the path of at
+ * most one attached frame).  Needs no device. */
+int wcqp_prepare_create(wcqp_kin_t kin, const wcqp_prepare_params* params, wcqp_prepare_t* out);
+int wcqp_prepare_destroy(wcqp_prepare_t h);
+/* WalkingIK::computeIK (WM/src/WalkingInverseKinematics.cpp:346-424) as WalkingModule::prepareRobot calls it (WM/src/WalkingModule.cpp:944-984),
+ * for `batch` robots, ALL ITERATIONS IN ONE LAUNCH.  DEVICE pointers; enqueue only (no allocation, no synchronisation):
+ *   left_d, right_d [B][12]   desired sole poses: p 3 | R 9 row-major (the left one is the anchor)
+ *   com_d [B][3]              desired CoM
+ *   Rd_neck [B][9] or NULL    desired neck orientation (already multiplied by additional_rotation); NULL: no neck target (as w_n = 0)
+ *   q_guess [B][dof]
+ * outputs
+ *   q [B][dof]                the optimum (SOLVED) or the clipped guess
+ *   base [B][12]              world pose of the root link at q: p 3 | R 9 (the `base` of wcqp_kin_jacobians_*)
+ *   state [B][87]             the packed pose block of wcqp_ik_solve_*, ready to be wcqp_tick_inputs.state0: the ACTUAL poses at q
+ *                             (0..23, 48..56, 66..68), the desired entries = the targets (24..47 the two soles, 57..65 Rd_neck - the
+ *                             actual neck orientation without a neck target -, 69..71 com_d), velocities and twists 0
+ *   status [B], iters [B]     WCQP_STATUS_*; iterations (QPs solved)
+ *   residual [B][2]           max |c| and max |stationarity| - the infinity norm of H-free g + [JR~; Jc~]^T lambda + mu, with lambda
+ *                             and mu the multipliers of the last QP - at the returned q of a SOLVED robot; +inf otherwise
+ * Any output pointer but q and status may be NULL.  Rows: state 696 B - a batch whose arrays pass the 4 GB rule above (batch x 696 > 2^32)
+ * gets WCQP_E_UNSUPPORTED before anything is looked for or allocated. */
+int wcqp_prepare_solve_device(wcqp_prepare_t h, int32_t batch, const double* left_d, const double* right_d, const double* com_d,
+                              const double* Rd_neck, const double* q_guess,
+                              double* q, double* base, double* state, int32_t* status, int32_t* iters, double* residual, void* stream);
+/* same with HOST pointers: staged through the handle's own device buffer, synchronises */
+int wcqp_prepare_solve_host(wcqp_prepare_t h, int32_t batch, const double* left_d, const double* right_d, const double* com_d,
+                            const double* Rd_neck, const double* q_guess,
+                            double* q, double* base, double* state, int32_t* status, int32_t* iters, double* residual);
+
+/* =====================================================================================
  * Device-resident tick pipeline — BASELINE configs 4/5 and SURVEY.md §8f-1/2: the call
  * order of WalkingModule::updateModule around the two solvers (WM/src/WalkingModule.cpp:
  * 578-745) for a batch of synthetic robots, kept entirely on the GPU:

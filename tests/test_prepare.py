@@ -1,0 +1,323 @@
+"""Batched non-linear IK: the posture each robot's walk starts from (wcqp_prepare_*).
+CPU: the numpy restatement (helpers/prepare_spec.py) against its own certificate, a second guess and joint limits; the ABI.  GPU: the
+kernel against the restatement and against the certificate computed here, its outputs as inputs of the kinematics and of the tick, the
+outcomes other than SOLVED, the launch forms, and a prepared batch walking 40 ticks.
+tests/robots.py holds parameter sets, not trees: the one tree of the repository, synth.icub_like_model(), is the one wcqp_kin is given."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import robots
+from helpers import footstep_plan as fp
+from helpers import prepare_spec as ps
+from helpers import streamed_tick as stt
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2
+B13 = 13                      # the last wave of four robots is partly empty
+ACTUAL = list(range(24)) + list(range(48, 57)) + [66, 67, 68]      # the entries of the pose block the kinematics write
+CONFIGS = ("free", "limits", "no_neck")
+
+
+def _targets(d, i, neck=True):
+    return dict(left_d=d["left_d"][i], right_d=d["right_d"][i], com_d=d["com_d"][i], Rd_neck=d["Rd_neck"][i] if neck else None)
+
+
+@pytest.fixture(scope="module")
+def scene(wca):
+    """13 robots of synth_prepare_batch and the restatement's optimum of each under the three configurations, computed once:
+    free, with limits that cut the two largest mean excursions from the posture to 0.6 of their free value (one or two bounds active per
+    robot), and without the neck target."""
+    model = wca.synth.icub_like_model()
+    d = wca.synth.synth_prepare_batch(B13)
+    q_reg = np.deg2rad(wca.synth.WALK_POSTURE_DEG)
+    par = {"free": ps.Params(q_reg=q_reg), "no_neck": ps.Params(q_reg=q_reg, w_n=0.0)}
+    sol = {k: [ps.solve(model, _targets(d, i), d["q_guess"][i], par[k]) for i in range(B13)] for k in ("free", "no_neck")}
+    mean = (np.stack([s["q"] for s in sol["free"]]) - q_reg).mean(0)
+    lo, hi = np.full(23, -3.0), np.full(23, 3.0)
+    for k in np.argsort(-np.abs(mean))[:2]:
+        (hi if mean[k] > 0 else lo)[k] = q_reg[k] + 0.6 * mean[k]
+    par["limits"] = ps.Params(q_reg=q_reg, q_min=lo, q_max=hi)
+    sol["limits"] = [ps.solve(model, _targets(d, i), d["q_guess"][i], par["limits"]) for i in range(B13)]
+    return dict(model=model, d=d, q_reg=q_reg, par=par, sol=sol)
+
+
+def _solver(wca, scene, cfg, **kw):
+    p = scene["par"][cfg]
+    return wca.PrepareSolver(wca.KinModel(scene["model"]), p.q_reg, w_q=p.w_q, w_n=p.w_n, q_min=p.q_min, q_max=p.q_max, **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU
+
+@pytest.mark.parametrize("cfg", CONFIGS)
+def test_restatement_optimum_passes_its_certificate(scene, cfg):
+    """every robot ends SOLVED within 40 iterations; at its q the constraints hold to 1e-10, the least-squares multipliers leave a
+    stationarity residual below 1e-9, the multipliers of the joints on a limit have the right sign and no joint is outside."""
+    for i, s in enumerate(scene["sol"][cfg]):
+        c = ps.certificate(scene["model"], s["q"], _targets(scene["d"], i), scene["par"][cfg])
+        print(cfg, i, s["iters"], c)
+        assert s["status"] == ps.SOLVED and s["iters"] <= 40
+        assert c["constraint"] <= 1e-10 and c["stationarity"] <= 1e-9 and c["mult_ok"] and c["inside"]
+        assert c["active"] == sorted(s["active"])
+    if cfg == "limits":
+        counts = {len(s["active"]) for s in scene["sol"][cfg]}
+        assert counts == {1, 2}, counts
+
+
+def test_restatement_reproduces_from_a_second_guess(scene):
+    """the optimum does not depend on the guess: posture + N(0, 0.05) arrives at the same q to 1e-11"""
+    rng = np.random.default_rng(3)
+    for i in range(0, B13, 3):
+        g2 = scene["q_reg"] + rng.normal(0.0, 0.05, 23)
+        s2 = ps.solve(scene["model"], _targets(scene["d"], i), g2, scene["par"]["free"])
+        err = np.abs(s2["q"] - scene["sol"]["free"][i]["q"]).max()
+        print(i, s2["iters"], err)
+        assert s2["status"] == ps.SOLVED and err <= 1e-11
+
+
+@pytest.mark.parametrize("n_cut", [1, 2])
+def test_restatement_respects_limits(scene, n_cut):
+    """robot 0 with its n_cut largest excursions cut to 0.6 of their free value: exactly those bounds are active, with multipliers of the
+    right sign, and the joints sit ON them"""
+    q_free, q_reg = scene["sol"]["free"][0]["q"], scene["q_reg"]
+    exc = q_free - q_reg
+    lo, hi = np.full(23, -3.0), np.full(23, 3.0)
+    cut = [int(k) for k in np.argsort(-np.abs(exc))[:n_cut]]
+    for k in cut:
+        (hi if exc[k] > 0 else lo)[k] = q_reg[k] + 0.6 * exc[k]
+    par = ps.Params(q_reg=q_reg, q_min=lo, q_max=hi)
+    s = ps.solve(scene["model"], _targets(scene["d"], 0), scene["d"]["q_guess"][0], par)
+    c = ps.certificate(scene["model"], s["q"], _targets(scene["d"], 0), par)
+    print(n_cut, s["iters"], c)
+    assert s["status"] == ps.SOLVED and s["iters"] <= 40
+    assert c["active"] == sorted(cut) and c["mult_ok"] and c["inside"] and c["constraint"] <= 1e-10 and c["stationarity"] <= 1e-9
+    for k in cut:
+        assert s["q"][k] == (hi if exc[k] > 0 else lo)[k]
+
+
+def test_abi_layout_and_symbols(wca, tmp_path):
+    """offsetof / sizeof of wcqp_prepare_params equal the ctypes mirror; the library exports the four entry points."""
+    exe = tmp_path / "prepare_layout"
+    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "prepare_layout.c"), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
+    cls = wca.capi.PrepareParams
+    assert got == [getattr(cls, k).offset for k, _ in cls._fields_] + [C.sizeof(cls)]
+    lib = wca.capi.lib()
+    for sym in ("wcqp_prepare_create", "wcqp_prepare_destroy", "wcqp_prepare_solve_device", "wcqp_prepare_solve_host"):
+        assert sym in wca.capi.ABI_SYMBOLS and getattr(lib, sym)
+
+
+def test_create_refusals(wca):
+    """every refusal that needs no device: NULL pointers, non-finite or out-of-range parameters, crossed limits, an iteration budget below
+    one, a tree the 16-lane walk cannot run; and the 4 GB rule of the solve calls, answered before anything is touched."""
+    lib = wca.capi.lib()
+    model = wca.synth.icub_like_model()
+    kin = wca.KinModel(model)
+    q_reg = np.zeros(23)
+    lo, hi = -np.ones(23), np.ones(23)
+
+    def create(kin_h=None, out=True, **kw):
+        v = dict(w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=100, q_reg=q_reg, q_min=None, q_max=None)
+        v.update(kw)
+        keep = [None if v[k] is None else np.ascontiguousarray(v[k], float) for k in ("q_reg", "q_min", "q_max")]
+        p = wca.capi.PrepareParams(v["w_q"], v["w_n"], v["step_cap"], v["tol_step"], v["tol_constraint"], v["max_iter"],
+                                   *(None if a is None else a.ctypes.data for a in keep))
+        h = C.c_void_p()
+        rc = lib.wcqp_prepare_create(kin._h if kin_h is None else kin_h, C.byref(p), C.byref(h) if out else None)
+        if rc == 0:
+            assert lib.wcqp_prepare_destroy(h) == 0
+        return rc
+
+    assert create() == 0 and create(q_min=lo, q_max=hi) == 0 and create(w_n=0.0) == 0
+    assert create(out=False) == WCQP_E_INVALID and create(kin_h=C.c_void_p()) == WCQP_E_INVALID and create(q_reg=None) == WCQP_E_INVALID
+    assert lib.wcqp_prepare_create(kin._h, None, C.byref(C.c_void_p())) == WCQP_E_INVALID
+    for bad in (np.nan, np.inf, -1.0):
+        assert create(w_q=bad) == WCQP_E_INVALID and create(w_n=bad) == WCQP_E_INVALID and create(step_cap=bad) == WCQP_E_INVALID
+        assert create(tol_step=bad) == WCQP_E_INVALID and create(tol_constraint=bad) == WCQP_E_INVALID
+    assert create(w_q=0.0) == WCQP_E_INVALID and create(step_cap=0.0) == WCQP_E_INVALID
+    assert create(max_iter=0) == WCQP_E_INVALID and create(max_iter=-3) == WCQP_E_INVALID
+    crossed = hi.copy(); crossed[7] = -2.0
+    assert create(q_min=lo, q_max=crossed) == WCQP_E_INVALID
+    nan_lim = hi.copy(); nan_lim[3] = np.nan
+    assert create(q_min=lo, q_max=nan_lim) == WCQP_E_INVALID
+    assert create(q_min=lo) == WCQP_E_INVALID and create(q_max=hi) == WCQP_E_INVALID
+    nan_reg = q_reg.copy(); nan_reg[22] = np.nan
+    assert create(q_reg=nan_reg) == WCQP_E_INVALID
+    assert lib.wcqp_prepare_destroy(None) == WCQP_E_INVALID
+    # a tree whose torso joint lies on the paths of two attached frames is not one the walk runs
+    two = dict(model, frame_joint=np.array([16, 22, 16], np.int32))
+    assert create(kin_h=wca.KinModel(two)._h) == WCQP_E_UNSUPPORTED
+    # the 4 GB rule: 696-byte rows, so 2^32 / 696 = 6170930 robots pass and one more does not; nothing is read or allocated
+    h = C.c_void_p()
+    p = wca.capi.PrepareParams(0.5, 1.0, 0.3, 1e-12, 1e-10, 100, q_reg.ctypes.data, None, None)
+    assert lib.wcqp_prepare_create(kin._h, C.byref(p), C.byref(h)) == 0
+    fake = C.c_void_p(4096)
+    for fn, extra in ((lib.wcqp_prepare_solve_device, (None,)), (lib.wcqp_prepare_solve_host, ())):
+        assert fn(h, 6170931, fake, fake, fake, None, fake, fake, None, None, fake, None, None, *extra) == WCQP_E_UNSUPPORTED
+        assert fn(h, -1, fake, fake, fake, None, fake, fake, None, None, fake, None, None, *extra) == WCQP_E_INVALID
+        assert fn(h, 4, None, fake, fake, None, fake, fake, None, None, fake, None, None, *extra) == WCQP_E_INVALID
+        assert fn(h, 0, fake, fake, fake, None, fake, fake, None, None, fake, None, None, *extra) == 0
+    assert lib.wcqp_prepare_destroy(h) == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+
+@pytest.fixture(scope="module")
+def device(wca, scene):
+    """the three configurations solved on the device, once"""
+    d = scene["d"]
+    out = {}
+    for cfg in CONFIGS:
+        sol = _solver(wca, scene, cfg)
+        out[cfg] = sol.solve_host(d["left_d"], d["right_d"], d["com_d"], d["q_guess"], d["Rd_neck"])
+        sol.close()
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg", CONFIGS)
+def test_parity_with_the_restatement(scene, device, cfg):
+    """q to 1e-9 (the project's parity bar; two guesses of the restatement itself agree to 6e-13), every robot SOLVED within the budget
+    of 100 iterations (the restatement stays at or below 40 on these inputs)"""
+    o = device[cfg]
+    ref = np.stack([s["q"] for s in scene["sol"][cfg]])
+    assert max(s["iters"] for s in scene["sol"][cfg]) <= 40
+    err = np.abs(o["q"] - ref).max()
+    print(cfg, "iters", o["iters"], "restatement", [s["iters"] for s in scene["sol"][cfg]], "err", err)
+    assert (o["status"] == 0).all() and (o["iters"] >= 1).all() and (o["iters"] <= 100).all()
+    assert err <= 1e-9
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg", CONFIGS)
+def test_certificate_at_the_device_solution(scene, device, cfg):
+    """the certificate, computed here at the device's q: constraints <= 1e-10, stationarity <= 1e-9, right multiplier signs, every joint
+    inside its limits exactly; the kernel's own `residual` agrees with it to 1e-12"""
+    o, par = device[cfg], scene["par"][cfg]
+    for i in range(B13):
+        c = ps.certificate(scene["model"], o["q"][i], _targets(scene["d"], i), par)
+        print(cfg, i, c, o["residual"][i])
+        assert c["constraint"] <= 1e-10 and c["stationarity"] <= 1e-9 and c["mult_ok"]
+        assert abs(o["residual"][i, 0] - c["constraint"]) <= 1e-12 and abs(o["residual"][i, 1] - c["stationarity"]) <= 1e-12
+    if par.q_min is not None:
+        assert (o["q"] >= par.q_min).all() and (o["q"] <= par.q_max).all()
+        assert ((o["q"] == par.q_min) | (o["q"] == par.q_max)).any(1).all()       # (every robot of this batch has a bound active)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg", CONFIGS)
+def test_outputs_plug_into_the_kinematics(wca, scene, device, cfg):
+    """base and state are what KinModel.jacobians_host computes at (base, q), bit for bit in the actual entries; the desired entries are
+    the targets, velocities and twists zero.
+    (The kernel spells out the fused multiply-adds of the joint rotation for this: left to the compiler, the 16-lane walk's second slot
+    and the stand-alone kernel differed in the last place of four entries of the right sole's rotation.)"""
+    o, d = device[cfg], scene["d"]
+    k = wca.KinModel(scene["model"]).jacobians_host(o["base"], o["q"], state=np.zeros((B13, 87)))
+    diff = np.abs(k["state"][:, ACTUAL] - o["state"][:, ACTUAL]).max()
+    print(cfg, "max difference of the actual entries", diff)
+    for i in range(B13):
+        assert np.abs(o["base"][i] - ps.anchored_base(scene["model"], d["left_d"][i], o["q"][i])).max() <= 1e-12
+    assert np.array_equal(o["state"][:, 24:36], d["left_d"]) and np.array_equal(o["state"][:, 36:48], d["right_d"])
+    assert np.array_equal(o["state"][:, 57:66], d["Rd_neck"]) and np.array_equal(o["state"][:, 69:72], d["com_d"])
+    assert not o["state"][:, 72:].any()
+    assert np.array_equal(k["state"][:, ACTUAL], o["state"][:, ACTUAL])
+
+
+@pytest.mark.gpu
+def test_a_guess_at_the_optimum_stops_at_once(wca, scene, device):
+    d, o = scene["d"], device["limits"]
+    sol = _solver(wca, scene, "limits")
+    again = sol.solve_host(d["left_d"], d["right_d"], d["com_d"], o["q"], d["Rd_neck"])
+    moved = np.abs(again["q"] - o["q"]).max()
+    print(again["iters"], moved)
+    assert (again["status"] == 0).all() and (again["iters"] <= 2).all() and moved < 1e-12
+
+
+@pytest.mark.gpu
+def test_not_solved(wca, scene, device):
+    """A CoM target 1 m above the soles ends MAX_ITER or INFEASIBLE with q = the clipped guess; a robot with a NaN in a target ends NUMERIC
+    while its 12 neighbours are bit for bit those of the batch without it - both in one batch, so that waves carry finished and unfinished
+    robots side by side."""
+    d, par = scene["d"], scene["par"]["limits"]
+    com = d["com_d"].copy(); left = d["left_d"].copy(); guess = d["q_guess"].copy()
+    high = [1, 6, 12]
+    com[high, 2] = 1.0
+    left[9, 4] = np.nan
+    k_lim = int(np.argmax(par.q_min > -3.0))
+    guess[:, k_lim] = par.q_min[k_lim] - 0.05     # outside the limits: the returned guess is the clipped one
+    sol = _solver(wca, scene, "limits")
+    clean = sol.solve_host(d["left_d"], d["right_d"], d["com_d"], guess, d["Rd_neck"])
+    o = sol.solve_host(left, d["right_d"], com, guess, d["Rd_neck"])
+    print(o["status"], o["iters"])
+    clipped = np.clip(guess, par.q_min, par.q_max)
+    for i in high:
+        assert o["status"][i] in (wca.STATUS_MAX_ITER, wca.STATUS_INFEASIBLE) and np.array_equal(o["q"][i], clipped[i])
+        assert o["iters"][i] <= 100 and np.isinf(o["residual"][i]).all()
+    assert o["status"][9] == wca.STATUS_NUMERIC and np.array_equal(o["q"][9], clipped[9]) and o["iters"][9] == 0
+    assert np.isfinite(o["q"]).all() and np.isfinite(o["base"]).all() and np.isfinite(o["state"]).all()
+    rest = [i for i in range(B13) if i not in high + [9]]
+    assert (clean["status"] == 0).all() and (o["status"][rest] == 0).all()
+    for k in ("q", "base", "state", "status", "iters", "residual"):
+        assert np.array_equal(o[k][rest], clean[k][rest]), k
+    # an iteration budget too small: MAX_ITER with the clipped guess, for everybody
+    short = _solver(wca, scene, "limits", max_iter=3).solve_host(d["left_d"], d["right_d"], d["com_d"], guess, d["Rd_neck"])
+    assert (short["status"] == wca.STATUS_MAX_ITER).all() and (short["iters"] == 3).all() and np.array_equal(short["q"], clipped)
+
+
+@pytest.mark.gpu
+def test_launch_forms_agree(wca):
+    """host and device entry points, the default and a non-default stream, batches of 1, 4 and 13, optional outputs left out: bit for
+    bit (tests/helpers/prepare_device_check.py, a process of its own: torch has to initialise its HIP runtime before libwcqp's)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "prepare_device_check.py")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "prepare device ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_prepared_robots_walk(wca, qs):
+    """prepare -> upload_footsteps replaces the synthetic start: 13 robots prepared with their CoM at 0.42 m, a generated walk planned at that
+    com_height, 40 ticks.  Every tick SOLVED; tick 0's actual sole poses are stage 0's desired ones to 1e-12; robot 0's closed loop matches
+    oracle/tick_spec.py to 1e-9."""
+    from oracle import tick_spec as ts
+    H, T, robot = 0.42, 40, "iCubGazeboV2_5"
+    R = robots.ROBOTS[robot]
+    model = wca.synth.icub_like_model()
+    d = wca.synth.synth_prepare_batch(B13, com_height=(H, H))
+    sol = wca.PrepareSolver(wca.KinModel(model), np.deg2rad(wca.synth.WALK_POSTURE_DEG))
+    o = sol.solve_host(d["left_d"], d["right_d"], d["com_d"], d["q_guess"], d["Rd_neck"])
+    assert (o["status"] == 0).all()
+    fs = wca.synth.synth_footstep_walk_batch(B13, T, o["state"], dict(q=o["q"]), step_ticks=50, ds_ticks=20, n_steps=2, com_height=H)
+    fs["state0"] = o["state"]                 # (the desired soles are the TARGETS, not copies of the actual ones)
+    ik = wca.IkSolver(form=wca.IK_FORM_QPOASES, neck_weight=R["neck_weight"] * np.eye(3), joint_reg_weights=np.array(R["reg_w"], float),
+                      joint_reg_gains=np.array(R["reg_k"], float), joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG),
+                      v_max=wca.synth.WALK_VMAX.copy(), k_pos_com=R["k_pos_com"], k_pos_foot=R["k_pos_foot"], k_att_foot=R["k_att_foot"], k_neck=R["k_neck"])
+    pipe = wca.TickPipeline(B13, T, wca.MpcSolver(horizon=50, com_height=H), ik, log_ticks=T, k_com=R["k_com"], k_zmp=R["k_zmp"],
+                            kin=wca.KinModel(model), planned_trajectories=True, neck_additional_rotation=np.eye(3))
+    pipe.upload_footsteps(fs, fs)
+    w = pipe.plan_window(stage0=0, m=1)
+    pipe.run(T)
+    out = pipe.download()
+    assert out["tick"] == T and not out["ik_fail"].any() and not out["mpc_fail"].any()
+    for des, act in ((w["left_traj"][:, 0], o["state"][:, 0:12]), (w["right_traj"][:, 0], o["state"][:, 12:24])):
+        assert np.abs(des - act).max() <= 1e-12
+    assert np.abs(o["state"][:, 68] - H).max() <= 1e-12 and np.abs(w["com_height"][:, 0] - H).max() <= 1e-12
+    # robot 0 against the restatement of the tick on the restatement of the plan
+    one = {k: (v[:1] if isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == B13 else v) for k, v in fs.items()}
+    plan = fp.footstep_plan(one, one["state0"], T + 51, T, com_height=H)
+    e = dict(one, ref_traj=plan["ref_traj"], dcm_vel_traj=plan["dcm_vel_traj"], dcm0=plan["ref_traj"][:, 0].copy(), u_init=plan["zmp_ref"][:, 0].copy())
+    ipar = robots.ik_params(qs, robot, v_max=wca.synth.WALK_VMAX.copy())
+    ipar.joint_reg_deg = wca.synth.WALK_POSTURE_DEG.copy()
+    ref = ts.run_ticks(ts.TickParams(horizon=50, com_height=H, k_com=R["k_com"], k_zmp=R["k_zmp"]), e, T, ipar, kin_model=model,
+                       foot_rect=wca.synth.FOOT_RECT, stages=stt.stages_of(plan, T), neck_additional_rotation=np.eye(3), dcm_vel=plan["dcm_vel_traj"])
+    assert (ref["ik_fail"] == 0).all()
+    for k in ("u0_log", "dq_log"):
+        err = np.abs(out[k][:, :1] - ref[k]).max()
+        print(k, err)
+        assert err <= 1e-9, (k, err)
+    for k in ("q_des", "dcm", "com"):
+        err = np.abs(out[k][:1] - ref[k]).max()
+        print(k, err)
+        assert err <= 1e-9, (k, err)

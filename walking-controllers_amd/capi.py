@@ -35,6 +35,7 @@ ABI_SYMBOLS = (
     "wcqp_ik_create", "wcqp_ik_destroy", "wcqp_ik_set_posture", "wcqp_ik_solve_device", "wcqp_ik_solve_host",
     "wcqp_hull_from_feet_device", "wcqp_hull_from_feet_host",
     "wcqp_kin_create", "wcqp_kin_destroy", "wcqp_kin_jacobians_device", "wcqp_kin_jacobians_host",
+    "wcqp_prepare_create", "wcqp_prepare_destroy", "wcqp_prepare_solve_device", "wcqp_prepare_solve_host",
     "wcqp_tick_create", "wcqp_tick_destroy", "wcqp_tick_upload", "wcqp_tick_run", "wcqp_tick_download", "wcqp_tick_splice_reference",
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
@@ -162,6 +163,13 @@ class KinParams(C.Structure):
                 ("frame_joint", C.c_int32 * 3), ("frame_R", (C.c_double * 9) * 3), ("frame_p", (C.c_double * 3) * 3)]
 
 
+class PrepareParams(C.Structure):
+    """wcqp_prepare_params: weights, step cap, tolerances and iteration budget of the non-linear IK; q_reg / q_min / q_max are HOST pointers
+    the library copies at create."""
+    _fields_ = [("w_q", C.c_double), ("w_n", C.c_double), ("step_cap", C.c_double), ("tol_step", C.c_double), ("tol_constraint", C.c_double),
+                ("max_iter", C.c_int32), ("q_reg", C.c_void_p), ("q_min", C.c_void_p), ("q_max", C.c_void_p)]
+
+
 class TickParams(C.Structure):
     _fields_ = [("batch", C.c_int32), ("first", C.c_int32), ("max_ticks", C.c_int32), ("log_ticks", C.c_int32),
                 ("step_ticks", C.c_int32), ("ds_ticks", C.c_int32),
@@ -265,6 +273,10 @@ def lib() -> C.CDLL:
         L.wcqp_kin_destroy.argtypes = [C.c_void_p]
         L.wcqp_kin_jacobians_device.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
         L.wcqp_kin_jacobians_host.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+        L.wcqp_prepare_create.argtypes = [C.c_void_p, C.POINTER(PrepareParams), C.POINTER(C.c_void_p)]
+        L.wcqp_prepare_destroy.argtypes = [C.c_void_p]
+        L.wcqp_prepare_solve_device.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 12
+        L.wcqp_prepare_solve_host.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 11
         L.wcqp_tick_create.argtypes = [C.POINTER(TickParams), C.POINTER(C.c_void_p)]
         L.wcqp_tick_destroy.argtypes = [C.c_void_p]
         L.wcqp_tick_upload.argtypes = [C.c_void_p, C.POINTER(TickInputs)]
@@ -491,6 +503,53 @@ class KinModel:
     def jacobians_device(self, batch, base, q, J_left, J_right, J_neck, J_com, state=0, stream=0):
         check(lib().wcqp_kin_jacobians_device(self._h, int(batch), base, q, J_left, J_right, J_neck, J_com, state or None, stream or None),
               "wcqp_kin_jacobians_device")
+
+
+class PrepareSolver:
+    """Handle over wcqp_prepare_* - the batched non-linear IK that gives every robot the posture its walk starts from
+    (WalkingModule::prepareRobot -> WalkingIK::computeIK; include/wcqp.h states the problem and the iteration).  kin: a KinModel;
+    q_reg: the regularisation posture [dof] in rad; q_min / q_max: joint limits [dof] or None (both).  Defaults follow the reference:
+    w_q = 0.5 (joint_regularization_weight), w_n = 1.0 (0: no neck target)."""
+
+    def __init__(self, kin: "KinModel", q_reg, w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=100,
+                 q_min=None, q_max=None):
+        self.dof = kin.dof
+        q_reg = _f64(np.asarray(q_reg, float).reshape(self.dof))
+        lim = [None if x is None else _f64(np.asarray(x, float).reshape(self.dof)) for x in (q_min, q_max)]
+        self.params = PrepareParams(float(w_q), float(w_n), float(step_cap), float(tol_step), float(tol_constraint), int(max_iter),
+                                    q_reg.ctypes.data, *(None if x is None else x.ctypes.data for x in lim))
+        self._h = C.c_void_p()
+        check(lib().wcqp_prepare_create(kin._h, C.byref(self.params), C.byref(self._h)), "wcqp_prepare_create")
+
+    def close(self):
+        if self._h:
+            lib().wcqp_prepare_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve_host(self, left_d, right_d, com_d, q_guess, Rd_neck=None) -> dict:
+        """left_d / right_d [B][12] desired sole poses (p 3 | R 9 row-major; the left one is the anchor), com_d [B][3], q_guess [B][dof],
+        Rd_neck [B][9] or None (no neck target).  -> q, base [B][12], state [B][87] (ready to be state0), status, iters, residual [B][2]."""
+        left_d, right_d, com_d, q_guess = map(_f64, (left_d, right_d, com_d, q_guess))
+        neck = None if Rd_neck is None else _f64(Rd_neck).reshape(-1, 9)
+        B = q_guess.shape[0]
+        assert left_d.shape == (B, 12) and right_d.shape == (B, 12) and com_d.shape == (B, 3) and q_guess.shape == (B, self.dof) and \
+            (neck is None or neck.shape == (B, 9)), (left_d.shape, right_d.shape, com_d.shape, q_guess.shape)
+        o = dict(q=np.zeros((B, self.dof)), base=np.zeros((B, 12)), state=np.zeros((B, IK_STATE_LEN)), status=np.full(B, -1, np.int32),
+                 iters=np.zeros(B, np.int32), residual=np.zeros((B, 2)))
+        check(lib().wcqp_prepare_solve_host(self._h, B, _p(left_d), _p(right_d), _p(com_d), _p(neck), _p(q_guess), _p(o["q"]), _p(o["base"]),
+                                            _p(o["state"]), _p(o["status"]), _p(o["iters"]), _p(o["residual"])), "wcqp_prepare_solve_host")
+        return o
+
+    def solve_device(self, batch, left_d, right_d, com_d, q_guess, q, status, Rd_neck=0, base=0, state=0, iters=0, residual=0, stream=0):
+        """All array arguments are raw device addresses (ints); enqueue only."""
+        check(lib().wcqp_prepare_solve_device(self._h, int(batch), left_d, right_d, com_d, Rd_neck or None, q_guess, q, base or None,
+                                              state or None, status, iters or None, residual or None, stream or None), "wcqp_prepare_solve_device")
 
 
 class TickPipeline:

@@ -672,3 +672,38 @@ def synth_footstep_replan_batch(fs: dict, after_step: int = 2, ds_offset: int = 
             p[sw] = pt; yaw[sw] = heading
             sw = 1 - sw
     return dict(merge_stage=merge, n_steps=np.full(count, n_steps, np.int32), side=side, target=target, first_ds_ticks=ds - ds_offset)
+
+
+def neck_target(left_d: np.ndarray, right_d: np.ndarray, additional_rotation=None) -> np.ndarray:
+    """Desired neck orientation [B][9] by the mean-yaw rule of WalkingModule::prepareRobot (WM/src/WalkingModule.cpp:957-970; the tick's
+    per-tick rule :697-707): RotZ(atan2(sin yL + sin yR, cos yL + cos yR)) * additional_rotation, each sole's yaw atan2(R10, R00) of its
+    desired pose [B][12] (p 3 | R 9 row-major)."""
+    left_d, right_d = np.asarray(left_d, float), np.asarray(right_d, float)
+    yl = np.arctan2(left_d[:, 6], left_d[:, 3]); yr = np.arctan2(right_d[:, 6], right_d[:, 3])
+    mean = np.arctan2(np.sin(yl) + np.sin(yr), np.cos(yl) + np.cos(yr))
+    add = np.eye(3) if additional_rotation is None else np.asarray(additional_rotation, float).reshape(3, 3)
+    return np.ascontiguousarray((_rotz(mean) @ add).reshape(-1, 9))
+
+
+def synth_prepare_batch(count: int, first: int = 0, seed: int = 88001, com_height=(0.39, 0.45), additional_rotation=None) -> dict:
+    """Targets of the batched non-linear IK (`PrepareSolver`, wcqp_prepare_*): "these robots stand with their soles here and their CoM
+    there".  Left sole anywhere on the floor within a metre of the origin with a yaw of +-0.4 rad; right sole 0.12-0.18 m beside it,
+    +-0.08 m fore-aft, +-0.2 rad of relative yaw; CoM between the two soles' ZMP points (ZMP_DELTA) at com_height above the floor - heights
+    this tree reaches with bent knees (its legs are straight near 0.5 m, where the iteration converges slowly or not at all); neck at the
+    mean yaw (neck_target).  q_guess: the joints of synth_walk_kin_batch.  Shard-invariant."""
+    rng = CounterRNG(seed, first, count)
+    u = rng.uniform(9)
+    yl = -0.4 + 0.8 * u[:, 0]
+    pl = np.stack([-1.0 + 2.0 * u[:, 1], -1.0 + 2.0 * u[:, 2], np.zeros(count)], -1)
+    Rl = _rotz(yl)
+    off = np.stack([-0.08 + 0.16 * u[:, 3], -(0.12 + 0.06 * u[:, 4]), np.zeros(count)], -1)
+    pr = pl + np.einsum("bij,bj->bi", Rl, off)
+    Rr = _rotz(yl + (-0.2 + 0.4 * u[:, 5]))
+    left_d = np.concatenate([pl, Rl.reshape(count, 9)], axis=1)
+    right_d = np.concatenate([pr, Rr.reshape(count, 9)], axis=1)
+    zl = pl[:, :2] + np.einsum("bij,j->bi", Rl[:, :2, :2], np.array(ZMP_DELTA[0]))
+    zr = pr[:, :2] + np.einsum("bij,j->bi", Rr[:, :2, :2], np.array(ZMP_DELTA[1]))
+    w = (0.35 + 0.3 * u[:, 6])[:, None]
+    com_d = np.concatenate([zl + w * (zr - zl), (com_height[0] + (com_height[1] - com_height[0]) * u[:, 7])[:, None]], axis=1)
+    return dict(first=first, left_d=np.ascontiguousarray(left_d), right_d=np.ascontiguousarray(right_d), com_d=np.ascontiguousarray(com_d),
+                Rd_neck=neck_target(left_d, right_d, additional_rotation), q_guess=synth_walk_kin_batch(count, first=first)["q"])
