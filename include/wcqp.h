@@ -682,11 +682,43 @@ typedef struct wcqp_tick_params {
     double joint_velocity_cut_frequency;
     double wrench_cut_frequency;
     double com_cut_frequency;
+    /* The inverse kinematics of the tick (WCQP_TICK_IK_*).  VELOCITY (0, default: the handle behaves as before, bit for bit): the Jacobian
+     * QP-IK gives joint velocities, which are integrated - the reference's `use_QP-IK 1` (WM/src/WalkingModule.cpp:709-744).  POSITION (1):
+     * the reference's `use_QP-IK 0` (:745-769) - WalkingIK::computeIK(m_leftTrajectory.front(), m_rightTrajectory.front(),
+     * desiredCoMPosition, m_qDesired) gives the joint POSITIONS of the tick directly: every tick's joints are an optimum of the position
+     * problem of wcqp_prepare_* above, so the soles sit on their planned poses to the solver's tolerance on every tick, with no drift from
+     * an integration.  A mode of a planned handle (planned_trajectories = 1).  Tick t of a POSITION handle:
+     *   1. The chain, exactly as the planned velocity tick runs it: the stage t record, the LIPM reference, the MPC or the reactive law, the
+     *      gain schedule where set, the ZMP-CoM law and its integrator, the internal plant.  It reads nothing the IK writes and keeps
+     *      running for a stopped robot.
+     *   2. The targets: left_d, right_d = the desired soles of record t; com_d = (p_star x, p_star y, the desired CoM height of record t);
+     *      Rd_neck = RotZ(meanYaw) * neck_additional_rotation, as the planned tick forms it.
+     *   3. The problem and the iteration of wcqp_prepare_*, unchanged: the left sole anchored at left_d, the right sole and the CoM as
+     *      equality rows, the joint regularisation and the neck target as costs, the joint limits as bounds.
+     *   4. The guess is q_des of tick t - 1 (tick 0: q0), clipped into the limits; the budget is position_ik.max_iter iterations PER TICK.
+     *   5. WCQP_STATUS_SOLVED: q_des takes the optimum.
+     *   6. Any other status: ik_fail counts the tick and the robot is stopped, as in the velocity tick - q_des keeps its value (at tick 0:
+     *      the clipped q0), no further IK is run for that robot and every later tick also counts.
+     * `position_ik` holds the problem's parameters: its HOST pointers are copied at create, every value is taken as given (no 0 -> default;
+     * capi.TickPipeline holds the defaults).  `ik` is ignored on such a handle apart from `dof` and the refusal of an `algorithm` below.
+     * DEVIATIONS from the reference: the fixed-frame bit of the record does not move the anchor - WalkingIK always uses the left foot as its
+     * base; the neck target is the planned tick's own, not yawRotation^-1 * inertial_R_world (WalkingModule.cpp:703-707); the upstream
+     * deviations listed for wcqp_prepare_* apply; the CoM velocity and the twists of the record are not read.
+     * wcqp_tick_create, before anything touches the device: WCQP_E_INVALID for an unknown ik_mode and, with POSITION, for any position_ik
+     * value wcqp_prepare_create refuses; WCQP_E_UNSUPPORTED for POSITION without planned_trajectories, and together with the EXTERNAL plant,
+     * streamed_trajectories, logger_ticks > 0 or an IK algorithm other than the default.  Every refusal of planned_trajectories applies
+     * unchanged (the FUSED hand-off actually taken, the tree).  On a POSITION handle wcqp_tick_upload, wcqp_tick_upload_footsteps,
+     * wcqp_tick_replan_footsteps, wcqp_tick_get_plan and wcqp_tick_run (any n_ticks, ticks_per_launch, use_graph, stream) work as on any
+     * planned handle; one launch of its kernel walks the ticks of a run call, and nothing runs ahead between ticks (no skew). */
+    int32_t ik_mode;
+    wcqp_prepare_params position_ik;
 } wcqp_tick_params;
 #define WCQP_TICK_PLANT_INTERNAL 0
 #define WCQP_TICK_PLANT_EXTERNAL 1
 #define WCQP_TICK_DCM_MPC        0
 #define WCQP_TICK_DCM_REACTIVE   1
+#define WCQP_TICK_IK_VELOCITY    0
+#define WCQP_TICK_IK_POSITION    1
 
 typedef struct wcqp_tick_inputs {   /* HOST pointers, copied at upload */
     const double* ref_traj;     /* [B][max_ticks+N+1][2]                                      */
@@ -737,6 +769,13 @@ typedef struct wcqp_tick_outputs {  /* HOST pointers, any may be NULL */
     int64_t* feedback_fail;     /* [B] EXTERNAL plant only: ticks whose feedback was rejected - by wcqp_tick_set_sensor_feedback_*, by
                                    wcqp_tick_set_feedback_* (a non-finite value) or by wcqp_tick_set_desired_* - since the last
                                    upload.  Any other handle: WCQP_E_UNSUPPORTED when non-NULL                                      */
+    double* q_log;              /* [log_ticks][B][dof] POSITION handles only (wcqp_tick_params.ik_mode): the joints tick t commanded.  On
+                                   such a handle dq_log must be NULL (WCQP_E_UNSUPPORTED otherwise: no velocity exists), hot_try and hot_hit
+                                   read 0, and active_lower / active_upper are the JOINT LIMITS active in the last QP of the last executed
+                                   tick (0 for a robot whose last tick did not end SOLVED).  Any other handle: WCQP_E_UNSUPPORTED when
+                                   non-NULL                                                                                         */
+    int64_t* ik_iters;          /* [B] POSITION handles only: Gauss-Newton iterations spent since the last upload.  Any other handle:
+                                   WCQP_E_UNSUPPORTED when non-NULL                                                                 */
 } wcqp_tick_outputs;
 
 typedef struct wcqp_tick_s* wcqp_tick_t;
@@ -965,6 +1004,7 @@ typedef struct wcqp_tick_info {
     int32_t sensor_filters;        /* low-pass filters of the sensor form taken: bit 0 joint velocity, bit 1 wrench, bit 2 CoM      */
     int32_t plan_generated;        /* 1: the plan in place was generated by wcqp_tick_upload_footsteps; 0: uploaded, or none yet    */
     double  plan_record_ms;        /* plan_generated: device time of that upload's record pass (events around it) [ms]; else 0      */
+    int32_t ik_mode;               /* wcqp_tick_params.ik_mode as taken (WCQP_TICK_IK_*)                                            */
 } wcqp_tick_info;
 int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
 

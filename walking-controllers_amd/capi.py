@@ -181,17 +181,20 @@ class TickParams(C.Structure):
                 ("zmp_gain_scheduling", C.c_int32), ("k_com_stance", C.c_double), ("k_zmp_stance", C.c_double), ("zmp_smoothing_time", C.c_double),
                 ("planned_trajectories", C.c_int32), ("neck_additional_rotation", C.c_double * 9),
                 ("streamed_trajectories", C.c_int32),
-                ("joint_velocity_cut_frequency", C.c_double), ("wrench_cut_frequency", C.c_double), ("com_cut_frequency", C.c_double)]
+                ("joint_velocity_cut_frequency", C.c_double), ("wrench_cut_frequency", C.c_double), ("com_cut_frequency", C.c_double),
+                ("ik_mode", C.c_int32), ("position_ik", PrepareParams)]
 
 
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
+TICK_IK_VELOCITY, TICK_IK_POSITION = 0, 1
+POSITION_IK_DEFAULTS = dict(q_reg=None, w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=30, q_min=None, q_max=None)
 KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1, 0, 1, 2
 
 
 class TickInfo(C.Structure):
     _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32),
                 ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32), ("streamed_trajectories", C.c_int32),
-                ("sensor_filters", C.c_int32), ("plan_generated", C.c_int32), ("plan_record_ms", C.c_double)]
+                ("sensor_filters", C.c_int32), ("plan_generated", C.c_int32), ("plan_record_ms", C.c_double), ("ik_mode", C.c_int32)]
 
 
 SENSOR_FILTERS = ("joint_velocity", "wrench", "com")      # bit k of wcqp_tick_info.sensor_filters
@@ -235,7 +238,7 @@ class TickPlanWindow(C.Structure):
 
 class TickOutputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("u0_log", "dq_log", "q_des", "dcm", "com", "mpc_fail", "ik_fail", "hot_try", "hot_hit", "tick", "logger", "active_lower", "active_upper", "zmp_gains",
-                                          "measured", "feedback_fail")]
+                                          "measured", "feedback_fail", "q_log", "ik_iters")]
 
 
 _lib: Optional[C.CDLL] = None
@@ -562,7 +565,7 @@ class TickPipeline:
                  dcm_controller: str = "mpc", k_dcm: Optional[float] = None, zmp_gain_scheduling: bool = False,
                  k_com_stance: Optional[float] = None, k_zmp_stance: Optional[float] = None, zmp_smoothing_time: Optional[float] = None,
                  planned_trajectories: bool = False, neck_additional_rotation=None, streamed_trajectories: bool = False,
-                 sensor_filters: Optional[dict] = None):
+                 sensor_filters: Optional[dict] = None, ik_mode: str = "velocity", position_ik: Optional[dict] = None):
         """kin: a KinModel -> per-tick kinematics (Jacobians, actual poses and hull rows rebuilt every tick from the
         integrated joint state with the base anchored at the stance foot; upload() then ignores J_* / hull_tab_*).
         dcm_controller: "mpc" (the DCM-MPC, the reference's use_mpc 1) or "reactive" (WalkingDCMReactiveController, the
@@ -575,7 +578,27 @@ class TickPipeline:
         in front of it - per tick set_desired -> set_sensor_feedback (or set_feedback) -> run(1); needs kin and neck_additional_rotation too.
         sensor_filters: dict(joint_velocity=, wrench=, com=) - cut frequencies in Hz of the low-pass filters set_sensor_feedback_* applies
         (joint_velocity_cut_frequency / wrench_cut_frequency of robotControl.ini, cut_frequency of forwardKinematics.ini); a missing key or
-        0 leaves that filter off.  Needs external_feedback and kin."""
+        0 leaves that filter off.  Needs external_feedback and kin.
+        ik_mode: "velocity" (the Jacobian QP-IK whose joint velocities are integrated, the reference's use_QP-IK 1) or "position" (the
+        reference's use_QP-IK 0: the non-linear IK of PrepareSolver every tick, hot-started at the previous tick's joints - a mode of a
+        planned handle).  position_ik: dict(q_reg=..., w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=30,
+        q_min=None, q_max=None) - the problem's parameters, max_iter the budget PER TICK; q_reg [dof] in rad is required.  `ik` then only
+        supplies dof.  download() of such a handle returns q_log [log_ticks][B][dof] and ik_iters [B], and no dq_log."""
+        if ik_mode not in ("velocity", "position"):
+            raise ValueError(f"ik_mode must be 'velocity' or 'position', not {ik_mode!r}")
+        self.position = ik_mode == "position"
+        if not self.position and position_ik is not None:
+            raise ValueError("position_ik was given to a handle created without ik_mode='position'")
+        pik = dict(POSITION_IK_DEFAULTS)
+        if self.position:
+            unknown = set(position_ik or {}) - set(pik)
+            if unknown:
+                raise ValueError(f"position_ik: unknown key(s) {sorted(unknown)} (known: {', '.join(pik)})")
+            pik.update(position_ik or {})
+            if pik["q_reg"] is None:
+                raise ValueError("ik_mode='position' needs position_ik['q_reg'], the regularisation posture [dof] in rad")
+            if not planned_trajectories:
+                raise ValueError("ik_mode='position' is a mode of a planned handle (planned_trajectories=True)")
         cuts = dict.fromkeys(SENSOR_FILTERS, 0.0)
         for k, v in (sensor_filters or {}).items():
             if k not in cuts:
@@ -626,6 +649,12 @@ class TickPipeline:
                                  float(k_com_stance) if self.gain_sched else 0.0, float(k_zmp_stance) if self.gain_sched else 0.0,
                                  float(zmp_smoothing_time) if self.gain_sched else 0.0, int(self.planned), (C.c_double * 9)(*neck),
                                  int(self.streamed), *(cuts[k] for k in SENSOR_FILTERS))
+        if self.position:
+            # (the library copies the three arrays at create)
+            arr = [None if pik[k] is None else _f64(np.asarray(pik[k], float).reshape(ik.dof)) for k in ("q_reg", "q_min", "q_max")]
+            self.params.ik_mode = TICK_IK_POSITION
+            self.params.position_ik = PrepareParams(float(pik["w_q"]), float(pik["w_n"]), float(pik["step_cap"]), float(pik["tol_step"]),
+                                                    float(pik["tol_constraint"]), int(pik["max_iter"]), *(None if a is None else a.ctypes.data for a in arr))
         self._h = C.c_void_p()
         check(lib().wcqp_tick_create(C.byref(self.params), C.byref(self._h)), "wcqp_tick_create")
         self._keep = None
@@ -740,7 +769,8 @@ class TickPipeline:
         """The form the handle took (wcqp_tick_get_info): kin_handoff ("fused", "compact", "dense" or None without kinematics),
         ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick, zmp_gain_scheduling (bool), planned_trajectories (bool),
         streamed_trajectories (bool), sensor_filters (the mask: bit 0 joint velocity, bit 1 wrench, bit 2 CoM), plan_generated (bool: the plan
-        in place came from upload_footsteps) and plan_record_ms (the device time of that upload's record pass)."""
+        in place came from upload_footsteps), plan_record_ms (the device time of that upload's record pass) and ik_mode ("velocity" /
+        "position")."""
         i = TickInfo()
         check(lib().wcqp_tick_get_info(self._h, C.byref(i)), "wcqp_tick_get_info")
         return dict(kin_handoff={KIN_HANDOFF_NONE: None, KIN_HANDOFF_FUSED: "fused", KIN_HANDOFF_DENSE: "dense",
@@ -748,7 +778,8 @@ class TickPipeline:
                     ticks_per_launch=int(i.ticks_per_launch), dcm_controller="reactive" if i.dcm_controller == TICK_DCM_REACTIVE else "mpc",
                     launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling),
                     planned_trajectories=bool(i.planned_trajectories), streamed_trajectories=bool(i.streamed_trajectories),
-                    sensor_filters=int(i.sensor_filters), plan_generated=bool(i.plan_generated), plan_record_ms=float(i.plan_record_ms))
+                    sensor_filters=int(i.sensor_filters), plan_generated=bool(i.plan_generated), plan_record_ms=float(i.plan_record_ms),
+                    ik_mode="position" if i.ik_mode == TICK_IK_POSITION else "velocity")
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")
@@ -865,6 +896,10 @@ class TickPipeline:
                  com=np.zeros((B, 2)), mpc_fail=np.zeros(B, np.int64), ik_fail=np.zeros(B, np.int64),
                  hot_try=np.zeros(B, np.int64), hot_hit=np.zeros(B, np.int64), tick=np.zeros(1, np.int32),
                  active_lower=np.zeros(B, np.uint32), active_upper=np.zeros(B, np.uint32), zmp_gains=np.zeros((B, 2)))
+        if getattr(self, "position", False):
+            # a POSITION handle forms no velocity: the joints every tick commanded, and the iterations spent
+            del o["dq_log"]
+            o["q_log"] = np.zeros((L, B, D)); o["ik_iters"] = np.zeros(B, np.int64)
         if self.logger_ticks > 0:
             o["logger"] = np.zeros((self.logger_ticks, B, 53))
         if getattr(self, "external", False):

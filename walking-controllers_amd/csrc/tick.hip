@@ -21,6 +21,7 @@
 #include "ik_common.h"
 #include "sensors.h"
 #include "plan_gen.h"
+#include "position_tick.h"
 
 namespace {
 
@@ -300,6 +301,11 @@ struct wcqp_tick_s {
     int* st_pair = nullptr;       // [B][2] contact pair of the last consumed stage / of the stage in hand (tick_desired_kernel)
     double* des_stage = nullptr;  // wcqp_tick_set_desired_host: [B][12 + 12 + 6 + 6 + 1 + 1] doubles, then [B] bytes
     TickDevPL dpl(const TickDev& base) const { TickDevPL g; static_cast<TickDevGS&>(g) = dgs(base); g.pl = pl; return g; }
+    // ik_mode = POSITION (a planned handle): the non-linear IK runs every tick in position_tick_kernel, which takes `pos` beside the
+    // handle's TickDevPL in device memory; the chain's state, hand-off rows and live hull rows are the skewed handle's, but nothing is
+    // skewed - no prime launch, no tick ahead
+    bool position = false;
+    wcqp::PosTickDev pos{};
 };
 
 namespace {
@@ -332,6 +338,8 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
     const int B = d.batch;
     const int N = wcqp::mpc_horizon(h->mpc);
     if (n_inner > h->ticks_per_launch) return WCQP_E_INVALID;
+    if (h->position)
+        return wcqp::position_tick_enqueue(static_cast<const TickDevPL*>(h->d_dev), h->pos, B, d.reactive != 0, d.gain_sched != 0, d.phase, n_inner, s);
     if (h->kin && !d.kin_fused) {
         h->kt.phase = d.phase;
         const int rck = wcqp::kin_enqueue_tick(h->kin, B, h->kt, d.q_des, h->J_left, h->J_right, h->J_neck, h->J_com, d.state, s);
@@ -401,6 +409,16 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
             (params->dcm_controller == WCQP_TICK_DCM_MPC && params->mpc.horizon >= kGainsLdsStages))
             return WCQP_E_UNSUPPORTED;
     }
+    // the POSITION mode: the problem's parameters by the rules of wcqp_prepare_create, then what the mode does not run with
+    if (params->ik_mode != WCQP_TICK_IK_VELOCITY && params->ik_mode != WCQP_TICK_IK_POSITION) return WCQP_E_INVALID;
+    const bool position = params->ik_mode == WCQP_TICK_IK_POSITION;
+    if (position) {
+        if (wcqp::prepare_check_scalars(&params->position_ik) != WCQP_OK || wcqp::prepare_check_arrays(&params->position_ik) != WCQP_OK) return WCQP_E_INVALID;
+        const int alg = params->ik.algorithm;
+        if (!planned || streamed || params->plant != WCQP_TICK_PLANT_INTERNAL || params->logger_ticks > 0 ||
+            (alg != WCQP_IK_ALG_DEFAULT && alg != WCQP_IK_ALG_BASE_ELIM))
+            return WCQP_E_UNSUPPORTED;
+    }
     // the sensor form's low-pass filters: a cut frequency > 0 switches one on - where there is a sensor form at all
     const double cuts[3] = {params->joint_velocity_cut_frequency, params->wrench_cut_frequency, params->com_cut_frequency};
     int filt_mask = 0;
@@ -427,7 +445,16 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if ((params->dcm_controller != WCQP_TICK_DCM_MPC && !reactive) || (reactive && !std::isfinite(params->k_dcm))) { delete h; return WCQP_E_INVALID; }
     // (a reactive handle keeps the MPC handle for the horizon and the LIPM's discretisation, without its condensed gains)
     int rc = wcqp_mpc_create(&params->mpc, &h->mpc);
-    if (rc == WCQP_OK) rc = wcqp_ik_create(&params->ik, &h->ik);
+    if (rc == WCQP_OK && position) {
+        // `ik` is not read: the handle's velocity IK is a neutral one of the default kernel (nothing launches it; it carries the route)
+        wcqp_ik_params neutral{};
+        neutral.dof = params->ik.dof; neutral.use_com_as_constraint = 1; neutral.form = WCQP_IK_FORM_QPOASES;
+        for (int k = 0; k < kDof; ++k) neutral.joint_reg_weights[k] = 1.0;      // (what the default route asks for: positive weights, W_neck > 0)
+        for (int k = 0; k < 3; ++k) neutral.neck_weight[4 * k] = 1.0;
+        rc = wcqp_ik_create(&neutral, &h->ik);
+    } else if (rc == WCQP_OK) {
+        rc = wcqp_ik_create(&params->ik, &h->ik);
+    }
     if (rc == WCQP_OK && params->use_kinematics) {
         if (params->kin.dof != kDof) rc = WCQP_E_UNSUPPORTED;
         if (rc == WCQP_OK) rc = wcqp_kin_create(&params->kin, &h->kin);
@@ -442,6 +469,8 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
             !wcqp::kin_fused_tables(h->kin, tab, &rounds))
             rc = WCQP_E_UNSUPPORTED;
     }
+    wcqp::PrepareHost ptab;
+    if (rc == WCQP_OK && position) rc = wcqp::prepare_host_tables(h->kin, &params->position_ik, &ptab);      // (the tree: refused above already)
     if (rc == WCQP_OK && h->kin) rc = wcqp::kin_prepare(h->kin);
     if (rc == WCQP_OK && !reactive) rc = wcqp::mpc_prepare(h->mpc);
     if (rc == WCQP_OK) rc = wcqp::ik_prepare(h->ik);
@@ -542,6 +571,22 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
             if (rc == WCQP_OK && hipMemcpy(kt, ktab.data(), ktab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) rc = WCQP_E_HIP;
             d.kin_tab = kt;
         }
+    }
+    if (position) {
+        // the model table and the parameter rows of the non-linear IK, the joint log and the iteration counters
+        double* ptd = nullptr;
+        const size_t nt = ptab.tab.size(), np = ptab.par.size();
+        A_(ptd, nt + np); A_(h->pos.q_log, (size_t)d.log_ticks * B * kDof); A_(h->pos.ik_iters, B);
+        if (rc == WCQP_OK && (hipMemcpy(ptd, ptab.tab.data(), nt * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                              hipMemcpy(ptd + nt, ptab.par.data(), np * 8, hipMemcpyHostToDevice) != hipSuccess))
+            rc = WCQP_E_HIP;
+        wcqp::PosTickDev& a = h->pos;
+        a.kin_tab = ptd; a.par = ptd + nt; a.kin_rounds = ptab.kin_rounds;
+        for (int k = 0; k < 3; ++k) a.pm[k] = ptab.pm[k];
+        a.w_q = ptab.w_q; a.w_n = ptab.w_n; a.step_cap = ptab.step_cap; a.tol_step = ptab.tol_step; a.tol_c = ptab.tol_c;
+        a.max_iter = ptab.max_iter; a.use_limits = ptab.use_limits;
+        a.alo = h->ik_lo; a.aup = h->ik_up;
+        h->position = true;
     }
 #undef A_
     if (rc != WCQP_OK) { wcqp_tick_destroy(h); return rc; }
@@ -756,6 +801,7 @@ static int upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0) {
     WCQP_HIP_TRY(hipMemset(d.hot_try, 0, B * 8)); WCQP_HIP_TRY(hipMemset(d.hot_hit, 0, B * 8));
     WCQP_HIP_TRY(hipMemset(h->ik_lo, 0, B * 4)); WCQP_HIP_TRY(hipMemset(h->ik_up, 0, B * 4));      // no previous active set at tick 0
     if (h->feedback_fail) WCQP_HIP_TRY(hipMemset(h->feedback_fail, 0, B * 8));
+    if (h->position) WCQP_HIP_TRY(hipMemset(h->pos.ik_iters, 0, B * 8));
     if (h->filt_state) {
         // the filters at rest: the CoM position filter AT com0 and its velocity filter at 0 (the reference starts them at (0, 0, com_height)
         // and 0 once, WM/src/WalkingForwardKinematics.cpp:153-160: its robot stands at the origin); the joint-velocity and wrench filters
@@ -1260,7 +1306,8 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     // the MPC chain); an enqueue that fails after that leaves device state nobody can name - the handle then wants a new upload.
     struct NeedsUpload { wcqp_tick_s* h; bool armed = true; ~NeedsUpload() { if (armed) h->uploaded = false; } } guard{h};
     if (h->d.skew && (!h->d_dev || !h->d.mst || !h->d.hand)) { guard.armed = false; return WCQP_E_INVALID; }
-    if (h->d.skew) {
+    const bool skewed = h->d.skew && !h->position;     // (a POSITION handle keeps the skewed handle's records, but runs every tick in order)
+    if (skewed) {
         // the fused launch of tick t carries IK(t) and MPC(t+1): the MPC of the call's first tick goes first, on its own, and
         // the call's LAST tick does not run the MPC of the tick after it - between calls nothing is ahead of anything
         const int rc = wcqp_ik::ik4_launch_tick_prime(h->dpl(h->d), h->variant, h->ticks_enqueued, s);
@@ -1277,7 +1324,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
         guard.armed = false;
         return WCQP_OK;
     }
-    if (h->d.skew) left -= 1;      // the last tick of the call is a plain launch of its own (below)
+    if (skewed) left -= 1;      // the last tick of the call is a plain launch of its own (below)
     // kGraphTicks ticks per graph (the tick index lives in HBM, so the graph is tick-invariant): one
     // hipGraphLaunch costs about as much as four plain launches.  The graph is captured with phases 0, 1, 0, ...
     // and therefore replayed only from phase 0; from phase 1 a plain tick goes first.
@@ -1307,7 +1354,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
         for (; left >= kGraphTicks; left -= kGraphTicks, h->ticks_enqueued += kGraphTicks) WCQP_HIP_TRY(hipGraphLaunch(h->graph_exec, s));
     }
     while (left > 0) { const int rc = plain(); if (rc != WCQP_OK) return rc; }
-    if (h->d.skew) {
+    if (skewed) {
         const int rc = enqueue_tick(h, h->phase, s, 1, 1);
         if (rc != WCQP_OK) return rc;
         h->phase ^= 1; ++h->ticks_enqueued;
@@ -1385,6 +1432,7 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
     out->sensor_filters = h->filt_mask;
     out->plan_generated = h->planned && h->uploaded && h->generated ? 1 : 0;
     out->plan_record_ms = out->plan_generated ? (double)h->gen_record_ms : 0.0;
+    out->ik_mode = h->position ? WCQP_TICK_IK_POSITION : WCQP_TICK_IK_VELOCITY;
     // a kinematics launch unless fused; then the skewed kernel (1), MPC / reactive + the 16-lane kernel (2) or controller, glue, IK, post (4)
     out->launches_per_tick = (h->kin && !d.kin_fused ? 1 : 0) + (h->form == TickForm::SKEWED ? 1 : h->form == TickForm::MPC_IK16 ? 2 : 4);
     return WCQP_OK;
@@ -1393,12 +1441,15 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
 int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out) {
     if (!h || !out) return WCQP_E_INVALID;
     if ((out->measured || out->feedback_fail) && !h->external) return WCQP_E_UNSUPPORTED;
+    if ((out->q_log || out->ik_iters) && !h->position) return WCQP_E_UNSUPPORTED;
+    if (out->dq_log && h->position) return WCQP_E_UNSUPPORTED;          // (a POSITION handle forms no velocity)
     const TickDev& d = h->d;
     const size_t B = (size_t)d.batch;
     WCQP_HIP_TRY(hipDeviceSynchronize());
 #define DN_(dst, src, n) if (dst) WCQP_HIP_TRY(hipMemcpy((dst), (src), (n), hipMemcpyDeviceToHost))
     DN_(out->u0_log, d.u0_log, (size_t)d.log_ticks * B * 16); DN_(out->dq_log, d.dq_log, (size_t)d.log_ticks * B * kDof * 8);
     DN_(out->q_des, d.q_des, B * kDof * 8);
+    if (h->position) { DN_(out->q_log, h->pos.q_log, (size_t)d.log_ticks * B * kDof * 8); DN_(out->ik_iters, h->pos.ik_iters, B * 8); }
     DN_(out->active_lower, h->ik_lo, B * 4); DN_(out->active_upper, h->ik_up, B * 4);
     if (out->logger) {
         if (!d.log_rows) return WCQP_E_UNSUPPORTED;          // logger_ticks = 0, or an IK algorithm without the fused tick kernel
