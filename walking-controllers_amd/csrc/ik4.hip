@@ -1,6 +1,8 @@
 // Jacobian QP-IK, fourth kernel (ik4_device.h: the algorithm): the base-eliminated kernel's code object - the stand-alone solve, the
-// plans of steps, the plain skewed tick and its MPC prime.  This code object is frozen for the headline: the skewed
-// tick with any of the chain's features runs the variant kernels of ik4_tick.hip, a code object of their own.
+// plans of steps, the plain skewed tick and its MPC prime.  This code object holds the headline's kernel, qp_plan_kernel, and what is put
+// beside it moves it: no new kernel goes in here - the skewed tick with any of the chain's features runs the variant
+// kernels of ik4_tick.hip, a code object of their own - and a change of the plan kernels themselves (the last: their launch-invariant
+// tables in LDS) is measured against the parent commit in the bench's forms; the other kernels keep their instructions.
 #include "ik4_device.h"
 
 namespace {
@@ -94,8 +96,9 @@ void qp_pair_kernel(const IkDeviceParams* __restrict__ prm, int batch,
 template <bool WITH_MPC>
 __device__ __forceinline__
 void plan_walk(const IkDeviceParams* __restrict__ prm, int batch, const wcqp_qp_step* __restrict__ recs, int n_steps, int ways, int groups,
-               const wcqp_mpc::MpcDeviceConsts& c, unsigned* queue, double (*smem)[PER_INST])
+               const wcqp_mpc::MpcDeviceConsts& c, unsigned* queue, double (*smem)[PER_INST], double* ptab)
 {
+    constexpr int TAB = WITH_MPC ? WCQP_PLAN_LDS : (WCQP_PLAN_LDS & 2);
     // ways > 0: workgroup (way, robot group) walks through records way, way + ways, ... of its group.
     // ways = 0, work queues: unit u = (robot group u / n_steps, record u % n_steps), GROUP-major: the resident waves then work inside a
     // window of a few dozen robot groups (record-major at 65536 robots every unit of a wave lies 11 MB further on in each of the
@@ -139,6 +142,10 @@ void plan_walk(const IkDeviceParams* __restrict__ prm, int batch, const wcqp_qp_
         r = k / n; blk = x * n + k % n;
     }
 #endif
+    // the launch-invariant tables on their way to LDS (ik4_device.h: PlanTables): the loads here, in front of the first record's (and of the first ticket's round trip); that
+    // record's body stores them behind its own loads.  (A wave without a record issues them for nothing: the registers are dead at once.)
+    PlanTables pt;
+    plan_tables_issue<TAB>(prm, c, WITH_MPC, ptab, pt);
     if (dynamic) {
         const unsigned u = draw();
         r = u < total ? (int)(u % (unsigned)n_steps) : n_steps; blk = u < total ? (int)(u / (unsigned)n_steps) : 0;
@@ -154,10 +161,12 @@ void plan_walk(const IkDeviceParams* __restrict__ prm, int batch, const wcqp_qp_
                       WITH_MPC ? as_global(s.u0) : nullptr, WITH_MPC ? as_global(s.mpc_status) : nullptr, WITH_MPC ? as_global(s.mpc_active) : nullptr,
                       WITH_MPC ? as_global(s.mpc_margin) : nullptr,
                       dynamic ? queue + home * QS + z : nullptr, 0u, WITH_MPC};
-        ik4_body<false, 0, true>(prm, batch, as_global(s.J_left), as_global(s.J_right), as_global(s.J_neck), as_global(s.J_com), as_global(s.q), as_global(s.state),
+        ik4_body<false, 0, true, false, false, false, false, false, TAB>(prm, batch, as_global(s.J_left), as_global(s.J_right), as_global(s.J_neck), as_global(s.J_com), as_global(s.q), as_global(s.state),
                                  as_global(s.dq), as_global(s.ik_status), as_global(s.active_lower), as_global(s.active_upper),
-                                 as_global(s.foot_err), as_global(s.iters), wcqp_tick::TickDev{}, smem, blk, 0, true, nullptr, nullptr, &m);
+                                 as_global(s.foot_err), as_global(s.iters), wcqp_tick::TickDev{}, smem, blk, 0, true, nullptr, nullptr, &m, nullptr, nullptr, nullptr, &pt);
         wcqp::wave_lds_fence();
+        // (the fill's registers are the first record's only: carried round the loop as zeros they are dead from here on)
+        pt.fill = false; pt.f_ik[0] = pt.f_ik[1] = pt.f_ik[2] = 0.0; pt.f_gr[0] = pt.f_gr[1] = make_double2(0.0, 0.0);
         if (dynamic) {
             unsigned u = (unsigned)__builtin_amdgcn_readfirstlane((int)m.ticket) * wcqp_ik::kPlanQueues + home;
             if (u >= total) { home = (home + 1u) % wcqp_ik::kPlanQueues; u = draw(); }
@@ -179,7 +188,8 @@ void qp_plan_kernel(const IkDeviceParams* __restrict__ prm, int batch, const wcq
                     wcqp_mpc::MpcDeviceConsts c, unsigned* queue)
 {
     __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
-    plan_walk<true>(prm, batch, recs, n_steps, ways, groups, c, queue, smem);
+    __shared__ __attribute__((aligned(16))) double ptab[PT_SIZE];
+    plan_walk<true>(prm, batch, recs, n_steps, ways, groups, c, queue, smem, ptab);
 }
 // an IK-only plan (no record has an MPC part: BASELINE config 3 on its own): the same walk without the MPC share, under a name of its
 // own so that profiles of the two do not mix
@@ -188,7 +198,8 @@ void ik_plan_kernel(const IkDeviceParams* __restrict__ prm, int batch, const wcq
                     wcqp_mpc::MpcDeviceConsts c, unsigned* queue)
 {
     __shared__ __attribute__((aligned(16))) double smem[4][PER_INST];
-    plan_walk<false>(prm, batch, recs, n_steps, ways, groups, c, queue, smem);
+    __shared__ __attribute__((aligned(16))) double ptab[PT_GR];          // (no MPC part: the IK's tables alone)
+    plan_walk<false>(prm, batch, recs, n_steps, ways, groups, c, queue, smem, ptab);
 }
 
 }  // namespace

@@ -38,6 +38,7 @@
 // Template parameter TICK: the tick pipeline's glue / post steps fused in (tick_device.h).
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <limits>
 #include <type_traits>
 #include "ik_common.h"
@@ -161,6 +162,66 @@ struct MpcPairArgs {
     bool has_mpc = true;       // false: ik_plan_kernel (an IK-only plan): the record has no MPC part
 };
 
+// The plan kernels' launch-invariant tables (TAB of ik4_body; plan_walk, ik4.hip): what every record of every robot of a launch reads
+// again - the MPC's gain blocks Gr and the IK's per-variable tables kq, qreg, vlo, vhi, sd, isd - sits in a block of LDS beside smem,
+// filled once per wave and read at the point of use: 20 loads per lane less in a record's vmcnt queue, and neither the 32 registers of
+// the gain blocks nor the 16 of the lane constants are held across the record's loads.
+// Gr has a capacity of ONE 64-stage pass of the window: a longer horizon (the shipped N = 200; its stages 64 .. N are read on the
+// spot from the global table anyway) takes the global path for the whole window, chosen per launch, wave-uniformly.
+#ifndef WCQP_PLAN_LDS
+#define WCQP_PLAN_LDS 3               // development switch: bit 0 the gain blocks, bit 1 the IK's tables
+#endif
+constexpr int kPlanGrStages = wcqp_mpc::kGrLdsStages;
+constexpr int PT_KQ = 0, PT_QREG = 32, PT_VLO = 64, PT_VHI = 96, PT_SD = 128, PT_ISD = 160;      // the tables as IkDeviceParams holds them: two runs
+constexpr int PT_GR = 192;                                                                      // [kPlanGrStages][2][2]
+constexpr int PT_SIZE = PT_GR + 4 * kPlanGrStages;
+static_assert(offsetof(IkDeviceParams, qreg) == offsetof(IkDeviceParams, kq) + 256 && offsetof(IkDeviceParams, vlo) == offsetof(IkDeviceParams, kq) + 512 &&
+              offsetof(IkDeviceParams, vhi) == offsetof(IkDeviceParams, kq) + 768 && offsetof(IkDeviceParams, isd) == offsetof(IkDeviceParams, sd) + 256,
+              "kq | qreg | vlo | vhi and sd | isd are copied as two runs");
+static_assert(PT_GR % 2 == 0 && (4 * PER_INST + PT_SIZE) * 8 <= 20480, "eight plan workgroups per CU: two waves per SIMD");
+struct PlanTables {
+    double* lds;               // [PT_SIZE] (an IK-only plan: [PT_GR])
+    bool gr_staged;            // this launch's horizon fits the Gr stage
+    bool fill;                 // the wave's first record: the block is still on its way, in the registers below
+    double f_ik[3];
+    double2 f_gr[2];
+};
+// The fill, first half: the loads, issued by plan_walk IN FRONT of the first record's.  The second half (plan_tables_land) sits in the
+// record body behind the record's own loads: vmcnt retires in order, so the wait is a counted one and nothing of the record is held back.
+template <int TAB>
+__device__ __forceinline__ void plan_tables_issue(const IkDeviceParams* prm, const wcqp_mpc::MpcDeviceConsts& c, bool with_mpc, double* lds, PlanTables& pt)
+{
+    const unsigned l8 = threadIdx.x * 8u;
+    pt.lds = lds; pt.fill = true;
+    pt.f_ik[0] = pt.f_ik[1] = pt.f_ik[2] = 0.0;
+    pt.f_gr[0] = pt.f_gr[1] = make_double2(0.0, 0.0);
+    if constexpr ((TAB & 2) != 0) {
+        const double* t4 = reinterpret_cast<const double*>(reinterpret_cast<const char*>(prm) + offsetof(IkDeviceParams, kq));
+        const double* t2 = reinterpret_cast<const double*>(reinterpret_cast<const char*>(prm) + offsetof(IkDeviceParams, sd));
+        pt.f_ik[0] = *wcqp::at32(t4, l8); pt.f_ik[1] = *wcqp::at32(t4, l8 + 512u); pt.f_ik[2] = *wcqp::at32(t2, l8);
+    }
+    pt.gr_staged = false;
+    if constexpr ((TAB & 1) != 0) {
+        pt.gr_staged = with_mpc && c.N < kPlanGrStages;
+        if (pt.gr_staged) {
+            // 2 (N + 1) double2 of gains, lane l takes entries l and 64 + l (clamped: what lies behind stage N is never read)
+            const double2* gp = reinterpret_cast<const double2*>(c.Gr.get());
+            const unsigned last = 2u * (unsigned)c.N + 1u, e0 = threadIdx.x, e1 = threadIdx.x + 64u;
+            pt.f_gr[0] = *wcqp::at32(gp, (e0 < last ? e0 : last) * 16u); pt.f_gr[1] = *wcqp::at32(gp, (e1 < last ? e1 : last) * 16u);
+        }
+    }
+}
+template <int TAB>
+__device__ __forceinline__ void plan_tables_land(const PlanTables& pt, int lane)
+{
+    double* T = pt.lds;
+    if constexpr ((TAB & 2) != 0) { T[lane] = pt.f_ik[0]; T[64 + lane] = pt.f_ik[1]; T[PT_SD + lane] = pt.f_ik[2]; }
+    if constexpr ((TAB & 1) != 0) {
+        if (pt.gr_staged) { st2(T + PT_GR + 2 * lane, pt.f_gr[0].x, pt.f_gr[0].y); st2(T + PT_GR + 128 + 2 * lane, pt.f_gr[1].x, pt.f_gr[1].y); }
+    }
+    wcqp::wave_lds_fence();
+}
+
 // PAIR (a plan of steps, wcqp_qp_plan_*): the wave also solves the DCM-MPC QP of its four robots, its loads issued in front
 // of the IK's and its arithmetic running while the Jacobians are in flight (what the tick kernel does with the MPC of the next tick).
 // JSRC: where the Jacobians come from - 0 the four dense arrays of the ABI, 1 the compact per-joint records of the tick's
@@ -180,7 +241,9 @@ struct MpcPairArgs {
 // PL with EXT (wcqp_tick_params.streamed_trajectories): the record is the ONE the caller handed over for this tick (plan_rec<true>); such a
 // launch runs one tick without the chain of the next (do_mpc false: there is no stage t + 1 to read ahead), the prime kernel ran this tick's
 // chain from the same record
-template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false, bool REACT = false, bool GS = false, bool PL = false>
+// TAB (the plan kernels only; PlanTables above): bit 0 - the MPC's gain blocks come from *pt's LDS block when the launch staged them,
+// bit 1 - the IK's per-variable tables come from it, read where they are used
+template <bool TICK, int JSRC = 0, bool PAIR = false, bool LOG = false, bool EXT = false, bool REACT = false, bool GS = false, bool PL = false, int TAB = 0>
 __device__ __forceinline__
 void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 const double* __restrict__ JL, const double* __restrict__ JR,
@@ -190,9 +253,14 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 unsigned* __restrict__ alo_out, unsigned* __restrict__ aup_out,
                 double* __restrict__ ferr_out, int* __restrict__ iters_out, const wcqp_tick::TickDev& td, double (*smem)[PER_INST], int blk,
                 const int tick_now = 0, const bool do_mpc = true, const double* kmodel = nullptr, const double* gr_lds = nullptr,
-                MpcPairArgs* pm = nullptr, double* carry = nullptr, int* gait = nullptr, const unsigned long long* noise_base = nullptr)
+                MpcPairArgs* pm = nullptr, double* carry = nullptr, int* gait = nullptr, const unsigned long long* noise_base = nullptr,
+                const PlanTables* pt = nullptr)
 {
     static_assert(!(TICK && PAIR), "the tick kernel carries its own MPC chain");
+    static_assert(TAB == 0 || (PAIR && JSRC == 0), "the LDS tables are the plan kernels'");
+    constexpr bool TAB_GR = (TAB & 1) != 0, TAB_IK = (TAB & 2) != 0;
+    const double* ptab = nullptr;
+    if constexpr (TAB != 0) ptab = pt->lds;
     static_assert(TICK || !REACT, "the reactive controller is a tick form");
     static_assert(TICK || !GS, "gain scheduling is a tick form");
     static_assert(!PL || (TICK && JSRC == 2 && !LOG), "planned / streamed trajectories: the fused-kinematics tick without logger rows");
@@ -240,7 +308,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
         sd0 = prm->sd[j]; sd1 = prm->sd[col1]; isd0 = prm->isd[j]; isd1 = prm->isd[col1];
         kq0 = prm->kq[v0i]; kq1 = prm->kq[v1i]; qreg0 = prm->qreg[v0i]; qreg1 = prm->qreg[v1i];
     };
-    if constexpr (!KINF) load_lane_constants();
+    if constexpr (!KINF && !TAB_IK) load_lane_constants();
     double a0[NROWS_IN], a1[NROWS_IN];     // columns of [J_left; J_right; J_com; J_neck]
     double q0, q1;
     double qm0, qm1;                       // the joint positions the IK's regularisation sees (tick with external feedback: measured ones)
@@ -255,6 +323,10 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     double2 p_xs = make_double2(0.0, 0.0), p_up = make_double2(0.0, 0.0);
     if constexpr (PAIR) {
         if (pm->has_mpc) {          // (an IK-only plan has no MPC part: a compile-time constant in either plan kernel)
+        if constexpr (TAB_GR) {          // (staged gains: only the window itself is loaded)
+            if (pt->gr_staged) wcqp_mpc::mpc_window_loads_ref_only(pm->c, j, reinterpret_cast<const double2*>(pm->ref), iu * (unsigned)pm->ref_len, pm->ref_len, mreg.L);
+            else wcqp_mpc::mpc_window_loads(pm->c, j, reinterpret_cast<const double2*>(pm->ref), iu * (unsigned)pm->ref_len, pm->ref_len, mreg.L);
+        } else
         wcqp_mpc::mpc_window_loads(pm->c, j, reinterpret_cast<const double2*>(pm->ref), iu * (unsigned)pm->ref_len, pm->ref_len, mreg.L);
         if (j == 0) { p_xs = *at32(reinterpret_cast<const double2*>(pm->x0), iu * 16u); p_up = *at32(reinterpret_cast<const double2*>(pm->u_prev), iu * 16u); }
         mreg.nc = *at32(pm->hull_nc, iu * 4u);
@@ -509,11 +581,19 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
             if (pm->ticket_from && threadIdx.x == 0) pm->ticket = __hip_atomic_fetch_add(pm->ticket_from, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __builtin_amdgcn_sched_barrier(0);
         }
+        if constexpr (TAB != 0) {
+            // the wave's first record: the table block lands in LDS here, behind the record's loads (a counted wait: the fill was issued first)
+            if (pt->fill) plan_tables_land<TAB>(*pt, lane);
+        }
         if constexpr (PAIR) if (pm->has_mpc) {
             // the DCM-MPC QP of the same four robots while the Jacobians are on their way: the operations of mpc_row_solve, in its order
             double ux, uy, u0x, u0y, margin;
             int mst_;
             unsigned mact;
+            if constexpr (TAB_GR) {
+                if (pt->gr_staged) wcqp_mpc::mpc_row_partial_lds(pm->c, j, mreg.L, ptab + PT_GR, ux, uy);
+                else wcqp_mpc::mpc_row_partial(pm->c, j, mreg.L, ux, uy);
+            } else
             wcqp_mpc::mpc_row_partial(pm->c, j, mreg.L, ux, uy);
             if (pm->c.N >= 4 * wcqp_mpc::kLanesPerInstance)          // a horizon beyond one 64-stage pass (the shipped N = 200): the rest of the window, loaded on the spot
                 wcqp_mpc::mpc_row_extra_passes(pm->c, j, reinterpret_cast<const double2*>(pm->ref) + inst * pm->ref_len, pm->ref_len, ux, uy);
@@ -689,6 +769,10 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     // gradient of the joint regularisation in the scaled variable: g~ = Lam^-1/2 (-w K (q_reg - q)); q = the MEASURED joint positions
     // (setRobotState, WalkingModule.cpp:373) - the desired ones unless the tick runs on external feedback
     if constexpr (!EXT) { qm0 = q0; qm1 = q1; }
+    if constexpr (TAB_IK) {
+        sd0 = ptab[PT_SD + j]; sd1 = ptab[PT_SD + col1]; kq0 = ptab[PT_KQ + v0i]; kq1 = ptab[PT_KQ + v1i];
+        qreg0 = ptab[PT_QREG + v0i]; qreg1 = ptab[PT_QREG + v1i];
+    }
     const double gt0 = -sd0 * kq0 * (qreg0 - qm0);
     const double gt1 = var1 ? -sd1 * kq1 * (qreg1 - qm1) : 0.0;
     wcqp::wave_lds_fence();
@@ -775,6 +859,7 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
                 }
                 c[6] = sc * (a[9] - w0); c[7] = sc * (a[10] - w1); c[8] = sc * (a[11] - w2);
             };
+            if constexpr (TAB_IK) { sd0 = ptab[PT_SD + j]; sd1 = ptab[PT_SD + col1]; }
             xf(a0, sd0, c0);
             xf(a1, var1 ? sd1 : 1.0, c1);
         }
@@ -852,7 +937,13 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
     // bounds and active-set settings: fetched here so that the latency hides under the sweep
     const double tol = prm->tol;
     const int max_iter = prm->max_iter;
-    double lo0 = prm->vlo[v0i] * isd0, hi0 = prm->vhi[v0i] * isd0, lo1 = prm->vlo[v1i] * isd1, hi1 = prm->vhi[v1i] * isd1;
+    double lo0, hi0, lo1, hi1;
+    if constexpr (TAB_IK) {
+        isd0 = ptab[PT_ISD + j]; isd1 = ptab[PT_ISD + col1];
+        lo0 = ptab[PT_VLO + v0i] * isd0; hi0 = ptab[PT_VHI + v0i] * isd0; lo1 = ptab[PT_VLO + v1i] * isd1; hi1 = ptab[PT_VHI + v1i] * isd1;
+    } else {
+        lo0 = prm->vlo[v0i] * isd0; hi0 = prm->vhi[v0i] * isd0; lo1 = prm->vlo[v1i] * isd1; hi1 = prm->vhi[v1i] * isd1;
+    }
     // ---------------- phase 5: sweep over the 12 pivots in 2 x 2 BLOCKS (no search: M is SPD), y, x~ ------------
     // A block step publishes two columns and applies the rank-2 update with the block's explicit inverse (computed
     // redundantly by every lane from the published entries): the same FMAs and LDS traffic as two single pivots, but
@@ -1426,9 +1517,17 @@ void ik4_body(const IkDeviceParams* __restrict__ prm, int batch,
 
     WCQP_STAMP(8);
     // ---------------- outputs (back in the unscaled variable) ----------------------------------------------
+    if constexpr (TAB_IK) { sd0 = ptab[PT_SD + j]; sd1 = ptab[PT_SD + col1]; }
     double dq0 = nu0 * sd0, dq1 = nu1 * sd1;
+    if constexpr (TAB_IK) {
+        // (the exact bounds: read in front of the branch, not inside it - DESIGN.md 4.2 on loads in rarely-taken branches)
+        const double bl0 = ptab[PT_VLO + v0i], bh0 = ptab[PT_VHI + v0i], bl1 = ptab[PT_VLO + v1i], bh1 = ptab[PT_VHI + v1i];
+        if (st_code == WCQP_STATUS_SOLVED && in_w0) dq0 = sig0 > 0.0 ? bh0 : bl0;
+        if (st_code == WCQP_STATUS_SOLVED && in_w1) dq1 = sig1 > 0.0 ? bh1 : bl1;
+    } else {
     if (st_code == WCQP_STATUS_SOLVED && in_w0) dq0 = sig0 > 0.0 ? prm->vhi[v0i] : prm->vlo[v0i];
     if (st_code == WCQP_STATUS_SOLVED && in_w1) dq1 = sig1 > 0.0 ? prm->vhi[v1i] : prm->vlo[v1i];
+    }
     // Non-finite inputs (include/wcqp.h): a NaN or an Inf in a joint column, in q or in the pose block has reached the velocities by
     // now - the QP couples every unknown - and the certificate above has already taken SOLVED away.  No robot hands out a NaN: the
     // 16 lanes agree (one reduction), the status is NUMERIC, dq = 0 and the active sets are empty.

@@ -72,12 +72,26 @@ void mpc_condensed_kernel(MpcDeviceConsts c, int batch,
 #ifdef WCQP_MPC_PLAN_VGPR_HALF
 __attribute__((amdgpu_num_vgpr(WCQP_MPC_PLAN_VGPR_HALF)))       // (half the unified register file's count: ik4.hip, WCQP_IK_PLAN_VGPR_HALF)
 #endif
-__global__ __launch_bounds__(kBlock)
+__global__ __launch_bounds__(kBlock, 6)          // (six waves per SIMD, as before the staging: left alone hipcc takes 87 registers, a wave less)
 void mpc_plan_kernel(MpcDeviceConsts c, int batch, const wcqp_qp_step* __restrict__ recs, int n_steps, int ways, int groups)
 {
     __shared__ __attribute__((aligned(16))) double s_hull[kInstPerWave][WCQP_HULL_ROWS][4];
+    __shared__ __attribute__((aligned(16))) double s_gr[4 * kGrLdsStages];
     using wcqp::as_global;
     const int way = (int)blockIdx.x / groups, blk = (int)blockIdx.x % groups;
+    // The gain blocks are the same for every record of the launch: a horizon of one 64-stage pass has them in LDS, copied once per wave,
+    // instead of 8 loads per lane and record (2048 B requested against the 1056 B of a robot's inputs).  A longer horizon reads the
+    // global table as before.  (The copy is a round trip in front of the first record: the card's other waves - six per SIMD - cover it;
+    // carried into the first record behind its loads, as qp_plan_kernel does it, its 8 registers cost this kernel a wave per SIMD.)
+    const bool staged = c.N < kGrLdsStages;
+    if (staged) {
+        const double2* gp = reinterpret_cast<const double2*>(c.Gr.get());
+        const unsigned last = 2u * (unsigned)c.N + 1u, e0 = threadIdx.x, e1 = threadIdx.x + 64u;      // (clamped: what lies behind stage N is never read)
+        const double2 f0 = gp[e0 < last ? e0 : last], f1 = gp[e1 < last ? e1 : last];
+        double* g = s_gr + 2 * threadIdx.x;
+        g[0] = f0.x; g[1] = f0.y; g[128] = f1.x; g[129] = f1.y;
+        wcqp::wave_lds_fence();
+    }
 #pragma unroll 1
     for (int r = way; r < n_steps; r += ways) {
         __asm__ volatile("" ::: "memory");
@@ -92,8 +106,32 @@ void mpc_plan_kernel(MpcDeviceConsts c, int batch, const wcqp_qp_step* __restric
         double ux, uy, margin;
         int st;
         unsigned mask;
-        mpc_row_solve(c, t, inst, as_global(s.x0), rp, s.ref_len, as_global(s.u_prev), as_global(s.hull_A), as_global(s.hull_b), as_global(s.hull_nc), inst,
-                      s_hull[sub], ux, uy, st, mask, margin);
+        if (staged) {
+            // the operations of mpc_row_solve in its order (bit-identical; what qp_plan_kernel does on the IK's lanes), every load of the
+            // record issued up front and the gain blocks out of LDS
+            MpcLoads L;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = t + k * kLanesPerInstance;
+                const int ic = i <= c.N ? i : c.N;
+                L.r[k] = rp[ic < s.ref_len ? ic : s.ref_len - 1];
+            }
+            double2 xs = make_double2(0.0, 0.0), up = xs, ha = xs;
+            double hb = 0.0;
+            if (t == 0) { xs = reinterpret_cast<const double2*>(as_global(s.x0))[inst]; up = reinterpret_cast<const double2*>(as_global(s.u_prev))[inst]; }
+            const int nc = as_global(s.hull_nc)[inst];
+            if (t < WCQP_HULL_ROWS) {
+                ha = reinterpret_cast<const double2*>(as_global(s.hull_A))[inst * WCQP_HULL_ROWS + t];
+                hb = as_global(s.hull_b)[inst * WCQP_HULL_ROWS + t];
+            }
+            double px, py;
+            mpc_row_partial_lds(c, t, L, s_gr, px, py);
+            if (t == 0) mpc_row_add_state(c, xs, up, px, py);
+            mpc_row_finish(c, t, px, py, nc, ha.x, ha.y, hb, s_hull[sub], ux, uy, st, mask, margin);
+        } else {
+            mpc_row_solve(c, t, inst, as_global(s.x0), rp, s.ref_len, as_global(s.u_prev), as_global(s.hull_A), as_global(s.hull_b), as_global(s.hull_nc), inst,
+                          s_hull[sub], ux, uy, st, mask, margin);
+        }
         if (t == 0 && live) {
             reinterpret_cast<double2*>(as_global(s.u0))[inst] = make_double2(ux, uy);
             as_global(s.mpc_status)[inst] = st;

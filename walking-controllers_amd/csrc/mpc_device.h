@@ -14,6 +14,9 @@ namespace wcqp_mpc {
 
 constexpr int kLanesPerInstance = 16;   // one DPP row per instance, 4 instances per wave
 constexpr int kInstPerWave = 64 / kLanesPerInstance;
+// the plan kernels (mpc_plan_kernel; qp_plan_kernel, ik4.hip) keep a copy of the gain blocks Gr in LDS, one 64-stage pass of the
+// window: a horizon of up to kGrLdsStages - 1 is read from it, a longer one from the global table as before
+constexpr int kGrLdsStages = 4 * kLanesPerInstance;
 
 struct MpcDeviceConsts {
     wcqp::GPtr<const double> Gr;     // (N+1) x 2 x 2   (GPtr: the struct also travels inside TickDev, which kernels read from device memory)
