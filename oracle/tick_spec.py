@@ -3,7 +3,7 @@ ORACLE — TEST INFRASTRUCTURE ONLY.
 
 CPU restatement of the per-tick call order of WalkingModule::updateModule around the two solvers (WM/src/WalkingModule.cpp:578-745) for a
 batch of robots, using the exact solvers of oracle/qp_spec.py.  run_ticks is the ONE restatement of the tick loop and the checker of the
-device-resident tick pipeline (walking-controllers_amd/csrc/tick.hip, BASELINE configs 4 and 5): every mode the device has
+device-resident tick pipeline (walking-controllers_amd/csrc/tick.hip and tick_plan.hip, BASELINE configs 4 and 5): every mode the device has
 (include/wcqp.h: wcqp_tick_params; the keywords of TickPipeline) is an argument of it.
 
 What every run restates from the reference (and where):

@@ -255,7 +255,7 @@ def test_kernels_hold_no_flat_memory_instructions(wca, tmp_path):
     llvm = "/opt/rocm/lib/llvm/bin"
     build = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "walking-controllers_amd", "csrc", "build")
     checked = 0
-    for name in ("mpc", "ik2", "ik3", "ik4", "ik4_tick", "tick", "hull", "kin"):
+    for name in ("mpc", "ik2", "ik3", "ik4", "ik4_tick", "tick", "tick_plan", "hull", "kin"):
         obj = os.path.join(build, name + ".hip.o")
         assert os.path.exists(obj), obj
         fat, dev = str(tmp_path / (name + ".fatbin")), str(tmp_path / (name + ".co"))
@@ -267,4 +267,4 @@ def test_kernels_hold_no_flat_memory_instructions(wca, tmp_path):
         flat = re.findall(r"\bflat_(?:load|store|atomic)\w*", asm)
         assert not flat, (name, len(flat), sorted(set(flat)))
         checked += 1
-    assert checked == 8
+    assert checked == 9

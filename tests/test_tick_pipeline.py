@@ -165,6 +165,14 @@ def test_tick_run_refuses_to_run_past_the_trajectories(wca, ticks_per_launch):
     assert np.array_equal(pipe.download()["dq_log"], want["dq_log"])
 
 
+def _bent_tail(base, t_m):
+    """a newly planned tail: `base` [B][n][2] bent away smoothly by up to 1.5 cm (per-instance direction), continuous at its first stage"""
+    B, n = base.shape[:2]
+    ramp = 1.0 - np.exp(-np.arange(n) / 40.0)
+    dirn = np.stack([np.cos(0.7 * np.arange(B) + t_m), np.sin(0.7 * np.arange(B) + t_m)], 1)
+    return np.ascontiguousarray(base + 0.015 * ramp[None, :, None] * dirn[:, None, :])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("ticks_per_launch", [0, 1], ids=["whole_call_per_launch", "one_tick_per_launch+graph"])
 def test_trajectory_merge_on_the_device(wca, qs, ticks_per_launch):
@@ -181,11 +189,9 @@ def test_trajectory_merge_on_the_device(wca, qs, ticks_per_launch):
     for t_m in (130, 280):
         frm = t_m + 20
         n = T + N + 1 - frm
-        # the new plan: the old one bent away smoothly by up to 1.5 cm (per-instance direction), continuous at the merge point
-        ramp = 1.0 - np.exp(-np.arange(n) / 40.0)
-        dirn = np.stack([np.cos(0.7 * np.arange(B) + t_m), np.sin(0.7 * np.arange(B) + t_m)], 1)
+        # the new plan: the old one bent away, continuous at the merge point
         base = merges[130][1][:, 150:] if t_m == 280 else d["ref_traj"][:, frm:]
-        merges[t_m] = (frm, np.ascontiguousarray(base[:, :n] + 0.015 * ramp[None, :, None] * dirn[:, None, :]))
+        merges[t_m] = (frm, _bent_tail(base[:, :n], t_m))
     ik = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=vmax)
     ref = ts.run_ticks(p, d, T, qs.IKParams(v_max=vmax * np.ones(23)), splices=merges)
     plain = ts.run_ticks(p, d, T, qs.IKParams(v_max=vmax * np.ones(23)))
@@ -206,6 +212,48 @@ def test_trajectory_merge_on_the_device(wca, qs, ticks_per_launch):
         pipe.splice_reference(T - 1, np.zeros((B, 4, 2)))
     with pytest.raises(wca.WcqpError):
         pipe.splice_reference(T + N, np.zeros((B, 4, 2)))
+
+
+@pytest.mark.gpu
+def test_trajectory_merge_into_growing_staging_rows(wca, qs):
+    """Two merges in a row on one non-blocking stream, nothing synchronised in between: a short tail (8 stages from tick 20) after 10
+    ticks, then, 10 ticks later, a long one (tick 35 to the end of the trajectory).  The second needs more staging rows than the first left
+    behind (B x 76 x 16 bytes after B x 8 x 16) while the first one's copy and the ticks behind it may still be running.  The rows are taken
+    at call time: the caller's array is overwritten with NaN as soon as each call returns.  Against oracle/tick_spec.py with the same two
+    merges (the tolerances of test_trajectory_merge_on_the_device), and really different from the run without them."""
+    from oracle import tick_spec as ts
+    B, T, vmax = 8, 60, 0.45
+    p = ts.TickParams()
+    d = wca.synth.synth_tick_batch(B, T)
+    L = T + p.horizon + 1
+    merges = {10: (20, _bent_tail(d["ref_traj"][:, 20:28], 10)), 20: (35, _bent_tail(d["ref_traj"][:, 35:L], 20))}
+    assert merges[10][1].shape == (B, 8, 2) and merges[20][1].shape == (B, L - 35, 2)
+    ref = ts.run_ticks(p, d, T, qs.IKParams(v_max=vmax * np.ones(23)), splices=merges)
+    plain = ts.run_ticks(p, d, T, qs.IKParams(v_max=vmax * np.ones(23)))
+    print("u0_log against the run without merges", np.abs(ref["u0_log"] - plain["u0_log"]).max())
+    assert np.abs(ref["u0_log"] - plain["u0_log"]).max() > 1e-3          # the merges matter
+    s = wca.capi.stream_create()
+    try:
+        pipe = wca.TickPipeline(B, T, wca.MpcSolver(), wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=vmax), log_ticks=T)
+        pipe.upload(d)
+        done = 0
+        for t_m in (10, 20):
+            pipe.run(t_m - done, stream=s); done = t_m
+            frm, tail = merges[t_m]
+            staged = tail.copy()                 # (distinct from the array the oracle was given)
+            pipe.splice_reference(frm, staged, stream=s)
+            staged[:] = np.nan
+        pipe.run(T - done, stream=s)
+        wca.capi.stream_synchronize(s)
+        out = pipe.download()
+    finally:
+        wca.capi.stream_destroy(s)
+    assert out["tick"] == T and out["mpc_fail"].sum() == 0 and np.array_equal(out["ik_fail"], ref["ik_fail"])
+    for k, tol in (("u0_log", 1e-9), ("dq_log", 1e-8), ("q_des", 1e-9), ("dcm", 1e-9)):
+        err = np.abs(out[k] - ref[k]).max()
+        print(k, err)
+        assert err <= tol, (k, err)
+    assert np.abs(out["u0_log"] - plain["u0_log"]).max() > 1e-3
 
 
 @pytest.mark.gpu

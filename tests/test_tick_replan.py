@@ -185,35 +185,75 @@ def replanned(wca, small):
     return w0, w1, pipe.plan_window()
 
 
+def _window_matches_the_restatement(wca, before, M, plan, w):
+    """the window `w` read after a replan at stages M of the plan read as `before`, against the restatement's stitched `plan`"""
+    from oracle import hull_spec as hs
+    assert np.array_equal(w["contact"], plan["contact"])
+    for k, kr in WINDOW:
+        err = np.abs(w[k] - plan[kr]).max()
+        print(k, err)
+        assert err <= 1e-12, (k, err)
+    assert np.array_equal(w["u_init"], before["u_init"])
+    for i in range(B13):
+        m = T if M[i] < 0 else int(M[i])
+        for k in w:
+            if k != "u_init":
+                assert np.array_equal(w[k][i, :m], before[k][i, :m]), (k, i)
+        # the rows in force at every stage: those of the last change of pair <= min(stage, max_ticks), built from THAT stage's feet
+        pair = plan["contact"][i] & 3
+        c = 0
+        for t in range(T):
+            if 0 < t <= MAXT and pair[t] != pair[t - 1]:
+                c = t
+            if t == c or t == T - 1 or t == m:
+                A, b, nc = hs.hull_from_feet(wca.synth.FOOT_RECT, plan["left_traj"][i, c], plan["right_traj"][i, c], int(pair[c]))
+                assert w["hull_nc"][i, t] == nc, (i, t)
+                assert np.abs(w["hull_A"][i, t] - A).max() < 1e-12 and np.abs(w["hull_b"][i, t, :nc] - b[:nc]).max() < 1e-12, (i, t)
+
+
 @pytest.mark.gpu
 def test_replanned_plan_matches_the_restatement(wca, small, replanned):
     """(5) plan_window() of the whole replanned plan against the restatement to 1e-12, hull rows by the classic rule on the stitched plan;
     stages below M_i and robots with -1 bit-identical to the window read before the call."""
-    from oracle import hull_spec as hs
     fs, plan0, (M1, rp1, plan1), (M2, rp2, plan2) = small
     w0, w1, w2 = replanned
     for before, M, plan, w in ((w0, M1, plan1, w1), (w1, M2, plan2, w2)):
-        assert np.array_equal(w["contact"], plan["contact"])
-        for k, kr in WINDOW:
-            err = np.abs(w[k] - plan[kr]).max()
-            print(k, err)
-            assert err <= 1e-12, (k, err)
-        assert np.array_equal(w["u_init"], before["u_init"])
-        for i in range(B13):
-            m = T if M[i] < 0 else int(M[i])
-            for k in w:
-                if k != "u_init":
-                    assert np.array_equal(w[k][i, :m], before[k][i, :m]), (k, i)
-            # the rows in force at every stage: those of the last change of pair <= min(stage, max_ticks), built from THAT stage's feet
-            pair = plan["contact"][i] & 3
-            c = 0
-            for t in range(T):
-                if 0 < t <= MAXT and pair[t] != pair[t - 1]:
-                    c = t
-                if t == c or t == T - 1 or t == m:
-                    A, b, nc = hs.hull_from_feet(wca.synth.FOOT_RECT, plan["left_traj"][i, c], plan["right_traj"][i, c], int(pair[c]))
-                    assert w["hull_nc"][i, t] == nc, (i, t)
-                    assert np.abs(w["hull_A"][i, t] - A).max() < 1e-12 and np.abs(w["hull_b"][i, t, :nc] - b[:nc]).max() < 1e-12, (i, t)
+        _window_matches_the_restatement(wca, before, M, plan, w)
+
+
+@pytest.mark.gpu
+def test_replan_into_a_growing_block(wca, small):
+    """The first replan of the small scenario in two calls on one non-blocking stream, the second right behind the first: robot 1 alone,
+    then every other robot the scenario replans.  The second call needs a larger block of device memory than the first left behind, while
+    the first one's kernels may still be reading it: more robots and tiles, and lists of up to 4 steps where the first call handed over
+    robot 1's two (the block's rows are padded to 256 bytes, so at 13 robots it is the wider lists and footprint tables that make it grow:
+    13 x 2 x 24 -> 768 and 13 x 3 x 224 -> 8960 bytes, then 13 x 4 x 24 -> 1280 and 13 x 5 x 224 -> 14592).  plan_window() against the
+    restatement of the same two calls by the comparison of test_replanned_plan_matches_the_restatement, robots neither call names
+    bit-identical to the window read before."""
+    fs, plan0, (M1, rp1, plan1), _ = small
+    one = 1
+    Ma = np.full(B13, -1, np.int32); Ma[one] = M1[one]
+    Mb = M1.copy(); Mb[one] = -1
+    Ka = int(rp1["n_steps"][one])
+    assert Ka < rp1["side"].shape[1] and (Mb >= 0).sum() > 1
+    rpa = dict(rp1, n_steps=np.where(Ma >= 0, rp1["n_steps"], 0).astype(np.int32), side=np.ascontiguousarray(rp1["side"][:, :Ka]),
+               target=np.ascontiguousarray(rp1["target"][:, :Ka]))
+    # CPU first: the restatement of the two calls is that of the one
+    plan = fr.footstep_replan(fr.footstep_replan(plan0, fs, Ma, rpa, T, MAXT), fs, Mb, rp1, T, MAXT)
+    for k in fr.PLAN_KEYS:
+        assert np.array_equal(plan[k], plan1[k]), k
+    s = wca.capi.stream_create()
+    try:
+        pipe = _pipe(wca, B13, MAXT, controller="reactive", gs=True)
+        pipe.upload_footsteps(fs, fs)
+        w0 = pipe.plan_window()
+        pipe.replan_footsteps(Ma, rpa, rpa["first_ds_ticks"], stream=s)
+        pipe.replan_footsteps(Mb, rp1, rp1["first_ds_ticks"], stream=s)
+        wca.capi.stream_synchronize(s)
+        w = pipe.plan_window()
+    finally:
+        wca.capi.stream_destroy(s)
+    _window_matches_the_restatement(wca, w0, M1, plan, w)
 
 
 @pytest.mark.gpu

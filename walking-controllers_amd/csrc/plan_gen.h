@@ -18,7 +18,7 @@ struct PlanGenDev {
     const double* target;           // [B][K][3]
     const double* state;            // [B][kStateLen]
     const int* set_base;            // [B] index of the support-polygon set the plan's first stage names: an upload's stage-0 set, which the prologue
-                                    // enters, or - a replan - the robot's last surviving set; the plan's own sets follow it (tick.hip: a fixed range of
+                                    // enters, or - a replan - the robot's last surviving set; the plan's own sets follow it (tick_plan.hip: a fixed range of
                                     // slots per robot)
     double* table;                  // [B][K + 1][kFpRec], written by the prologue
     long long* set_at;              // [sets] record offset (doubles) of each set's stage

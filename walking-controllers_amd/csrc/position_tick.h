@@ -1,5 +1,5 @@
 // The POSITION mode of the closed-loop tick (wcqp_tick_params.ik_mode = WCQP_TICK_IK_POSITION, include/wcqp.h): what the tick handle
-// (tick.hip) and the kernel (position_tick.hip) share, and the host code the two users of the non-linear IK - wcqp_prepare_create and
+// (tick_handle.h, tick.hip) and the kernel (position_tick.hip) share, and the host code the two users of the non-linear IK - wcqp_prepare_create and
 // wcqp_tick_create - build its tables with (prepare.hip).  Internal, not ABI.
 #pragma once
 #include <vector>

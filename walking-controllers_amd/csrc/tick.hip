@@ -1,6 +1,7 @@
 // Device-resident tick pipeline (BASELINE configs 4/5, SURVEY.md §8f-1 tick harness and
 // §8f-2 MPC->IK glue).  See include/wcqp.h for the contract and oracle/tick_spec.py for the
-// CPU restatement every number is checked against.
+// CPU restatement every number is checked against.  The handle is tick_handle.h's; what puts planned, generated, replanned or streamed
+// trajectories into it, or reads them back, is tick_plan.hip.
 //
 // Reference call order reproduced (citations relative to /root/reference/modules/Walking_module):
 //   src/WalkingModule.cpp:578-597   StableDCMModel::integrateModel        -> tick_glue_kernel (consumer)
@@ -15,13 +16,8 @@
 #include <cstring>
 #include <new>
 #include <vector>
-#include "wcqp_internal.h"
-
-#include "tick_device.h"
-#include "ik_common.h"
+#include "tick_handle.h"
 #include "sensors.h"
-#include "plan_gen.h"
-#include "position_tick.h"
 
 namespace {
 
@@ -85,87 +81,6 @@ __global__ void tick_vel_diff_kernel(TickDev d, int from, int to) {
     const_cast<double*>(d.dcm_vel.get())[w] = (d.ref_traj[w + 2] - d.ref_traj[w]) / d.dT;
 }
 
-// planned trajectories: the support-polygon rows of every contact change (tick_device.h: PlanDev), one thread per set - the corners of
-// the feet in contact at the set's stage (its record's desired poses) hulled by the builder of hull.hip
-struct PlanRect { double v[8]; };
-__global__ void plan_hull_sets_kernel(int n, PlanRect rect, const double* __restrict__ rec, const long long* __restrict__ at,
-                                      const int* __restrict__ code, double* __restrict__ A, double* __restrict__ b, int* __restrict__ nc) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    if (code[g] < 0) return;        // (a slot no set of this call occupies: generated plans keep a fixed range of slots per robot)
-    const double* r = rec + at[g];
-    double px[8], py[8];
-    int np = 0;
-    if (code[g] == 0 || code[g] == 2) wcqp_hull::foot_points(rect.v, r + kPlanLeft, px, py, np);
-    if (code[g] == 1 || code[g] == 2) wcqp_hull::foot_points(rect.v, r + kPlanRight, px, py, np);
-    nc[g] = wcqp_hull::hull_rows(px, py, np, A + (size_t)g * 16, b + (size_t)g * 8);
-}
-
-// streamed trajectories (wcqp_tick_set_desired_*): the stage of the next tick - what WalkingModule::updateModule pops from the front of the
-// planner's deques (WM/src/WalkingModule.cpp:509-511, 689-707, 1085-1165) - packed into the robot's record (tick_device.h: kPlanRec, ONE
-// per robot) and validated by the rules of the planned upload.  16 lanes per robot: lane j carries entries j, 16 + j and 32 + j.
-// A robot whose stage is invalid keeps its previous record and is stopped and counted like one whose sensor reading was rejected
-// (sensors.hip).  pair: per robot the contact pair of the last stage a tick consumed and of the stage in hand (-1 after an upload); `first`:
-// this is the first stage handed over since the last tick, so the pair in hand has been consumed.  When the new pair differs from the
-// consumed one, lane 0 builds the robot's support-polygon rows from this stage's feet with the builder of hull_device.h - here, not in the
-// tick kernel - into set i, which entry 39 names: the chain of tick t copies them into the live rows on seeing the change
-// (tick_mpc_finish_from, ...PredictiveController.cpp:364-435); with no change the rows stay, whatever the feet do.
-struct DesiredDev {
-    const double *left_pose, *right_pose, *left_twist, *right_twist, *com_height, *com_height_vel;
-    const unsigned char* contact;
-    const double* h0;               // [B] TickDev::com_h0: the height of a stage without one
-    double* rec; double* set_A; double* set_b; int* set_nc; int* pair;
-    long long *ik_fail, *feedback_fail;
-    int batch, first, build;        // build: the handle's controller reads hull rows (the MPC)
-};
-__global__ __launch_bounds__(64) void tick_desired_kernel(DesiredDev a, PlanRect rect) {
-    const int lane = threadIdx.x, grp = lane >> 4, j = lane & 15;
-    const long inst_raw = (long)blockIdx.x * 4 + grp;
-    const bool live = inst_raw < a.batch;
-    const size_t i = (size_t)(live ? inst_raw : (long)a.batch - 1);
-    const unsigned f = a.contact[i];
-    // entries j (flags, height, its velocity, the left pose and the first of the right), 16 + j, 32 + j (< 40: the twists' tail, the set)
-    double v0, v1, v2 = 0.0;
-    if (j == kPlanFlags) v0 = (double)f;
-    else if (j == kPlanHeight) v0 = a.com_height ? a.com_height[i] : a.h0[i];
-    else if (j == kPlanHeightVel) v0 = a.com_height_vel ? a.com_height_vel[i] : 0.0;
-    else if (j < kPlanRight) v0 = a.left_pose[i * 12 + (j - kPlanLeft)];
-    else v0 = a.right_pose[i * 12 + (j - kPlanRight)];
-    const int k1 = 16 + j;
-    v1 = k1 < kPlanTwL ? a.right_pose[i * 12 + (k1 - kPlanRight)] : a.left_twist[i * 6 + (k1 - kPlanTwL)];
-    const int k2 = 32 + j;
-    if (k2 < kPlanTwL + 6) v2 = a.left_twist[i * 6 + (k2 - kPlanTwL)];
-    else if (k2 < kPlanHull) v2 = a.right_twist[i * 6 + (k2 - kPlanTwL - 6)];
-    else if (k2 == kPlanHull) v2 = (double)i;
-    const bool flags_bad = (f & 3u) == 0u || ((f & 4u) ? !(f & 1u) : !(f & 2u));       // no foot in contact / the fixed-frame foot is not
-    const bool lane_bad = flags_bad || !(isfinite(v0) && isfinite(v1) && isfinite(v2));
-    const bool bad = ((__ballot(lane_bad) >> (grp * 16)) & 0xffffull) != 0ull;
-    if (!live) return;
-    int* pr = a.pair + i * 2;
-    const int consumed = a.first ? pr[1] : pr[0];
-    if (bad) {
-        if (j == 0) {
-            pr[0] = consumed;
-            a.feedback_fail[i] += 1;
-            if (a.ik_fail[i] == 0) a.ik_fail[i] = 1;
-        }
-        return;
-    }
-    double* r = a.rec + i * kPlanRec;
-    r[j] = v0; r[k1] = v1;
-    if (k2 <= kPlanHull) r[k2] = v2;
-    if (j != 0) return;
-    const int code = (int)(f & 3u) - 1;
-    pr[0] = consumed; pr[1] = code;
-    if (a.build && code != consumed) {
-        double px[8], py[8];
-        int np = 0;
-        if (code == 0 || code == 2) wcqp_hull::foot_points(rect.v, a.left_pose + i * 12, px, py, np);
-        if (code == 1 || code == 2) wcqp_hull::foot_points(rect.v, a.right_pose + i * 12, px, py, np);
-        a.set_nc[i] = wcqp_hull::hull_rows(px, py, np, a.set_A + i * 16, a.set_b + i * 8);
-    }
-}
-
 // external feedback: the caller's measured state into the places the next tick reads its plant state from - the skewed
 // chain's per-axis records (mst: com [2], dcm [6], measured ZMP [7]) - and the measured joints into q_meas (NULL: the desired ones).
 // A robot with a NaN or an Inf anywhere in its feedback is REJECTED by the rule of the sensor form (sensors.hip; include/wcqp.h): it keeps
@@ -223,105 +138,7 @@ void zmp_smoother_coeffs(double T, double dT, double nb[4], double na[3]) {
 }
 }  // namespace wcqp
 
-// how a tick is launched: the skewed base-eliminated kernel (ONE launch), MPC + the 16-lane kernel with glue and post fused in
-// (two), or MPC, glue, IK and post (four; any other IK kernel, and what the fused forms are tested against)
-enum class TickForm { SKEWED, MPC_IK16, FOUR_LAUNCH };
-
-struct wcqp_tick_s {
-    wcqp_tick_params p{};
-    wcqp_mpc_t mpc = nullptr;
-    wcqp_ik_t ik = nullptr;
-    TickDev d{};
-    TickDev* d_dev = nullptr;     // skewed tick: a TickDevPL of `d` in device memory (the fused kernels read it from there, see ik4_device.h)
-    wcqp_ik::TickVariant variant{};   // skewed tick: the kernels this handle runs (wcqp_tick_create)
-    std::vector<void*> allocs;
-    double *J_left = nullptr, *J_right = nullptr, *J_neck = nullptr, *J_com = nullptr;
-    unsigned* mpc_active = nullptr; double* mpc_margin = nullptr;
-    unsigned *ik_lo = nullptr, *ik_up = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    hipStream_t graph_stream = nullptr;
-    bool uploaded = false;
-    int ticks_enqueued = 0;  // since the last upload; its parity is the `phase` of the next tick
-    double* log_ferr = nullptr;   // logger rows with dense Jacobians: where the IK kernel forms the foot errors
-    TickForm form = TickForm::FOUR_LAUNCH;   // from the IK handle's route (wcqp_tick_create)
-    wcqp_kin_t kin = nullptr;     // use_kinematics: Jacobians, actual poses and hull rows are rebuilt every tick
-    KinTick kt{};
-    int phase = 0;                // which copy of the tick index the next launch reads (TickDev::tick2): toggles per LAUNCH
-    int ticks_per_launch = 1;     // > 1 only for the skewed tick without a kinematics launch: the ticks one launch walks through
-    // wcqp_tick_splice_reference: the caller's host rows are staged HERE at call time (a copy stream of the handle's own, waited
-    // for before the call returns), the strided device-to-device copy then runs in the caller's stream order
-    double* splice_stage = nullptr; size_t splice_cap = 0;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t splice_done = nullptr; bool splice_pending = false;
-    bool vel_explicit = false;    // uploaded with an explicit dcm_vel_traj (reactive controller): the splice has no velocity tail
-    bool external = false, feedback_set = false;     // wcqp_tick_params.plant = EXTERNAL: one tick per run call, each behind a set_feedback
-    double* q_meas = nullptr;
-    double* fb_stage = nullptr;   // wcqp_tick_set_feedback_host: [B][2 + 2 + 2 + dof]
-    // sensor feedback (EXTERNAL with kinematics, wcqp_tick_set_sensor_feedback_*): the host form's staging rows [B][dof + dof + 6 + 6],
-    // the rejection counter, and an event each run records on its stream (the host form waits for it before it stages)
-    double* sens_stage = nullptr;
-    long long* feedback_fail = nullptr;
-    hipEvent_t run_done = nullptr; bool run_pending = false;
-    // the sensor form's low-pass filters (wcqp_tick_params.*_cut_frequency; sensors.h): two slots of per-robot state [2][B][kFiltRec].  A
-    // sensor call reads slot filt_cur - what the last RUN tick left - and writes the other one; wcqp_tick_run commits it (filt_pending)
-    // when it consumes the tick, so a replaced call advances nothing and a tick fed by the plain form holds the state
-    double* filt_state = nullptr;
-    int filt_mask = 0, filt_cur = 0;
-    bool filt_started = false, filt_pending = false;
-    double filt_fb[3] = {0.0, 0.0, 0.0}, filt_fa[3] = {0.0, 0.0, 0.0};
-    std::vector<double> meas0;    // EXTERNAL: dcm0, com0, u_init of the last upload ([B][6]: wcqp_tick_outputs.measured before any tick)
-    ZmpSched zg{};                // zmp_gain_scheduling (d.gain_sched): the stance gains, the smoother, its per-robot state
-    // the handle's TickDev with the scheduling record behind it (what the scheduled kernels take)
-    TickDevGS dgs(const TickDev& base) const { TickDevGS g; static_cast<TickDev&>(g) = base; g.zg = zg; return g; }
-    // planned_trajectories: the per-stage records and what the planned kernels take (the scheduling record behind it, used or not)
-    bool planned = false;
-    PlanDev pl{};
-    double* set_A = nullptr; double* set_b = nullptr; int* set_nc = nullptr;     // the row sets of the last upload (PlanDev::set_*)
-    size_t n_sets = 0;            // how many (wcqp_tick_get_plan reads them back)
-    // wcqp_tick_upload_footsteps: the generated ZMP of stage 0 [B][2] (allocated by the first such upload), and whether the plan in place was generated
-    double* gen_zmp0 = nullptr; bool generated = false;
-    hipEvent_t gen_ev[2] = {nullptr, nullptr}; float gen_record_ms = 0.0f;     // the record pass of the last such upload, timed (wcqp_tick_info.plan_record_ms)
-    // wcqp_tick_replan_footsteps: what the last wcqp_tick_upload_footsteps fixed for the handle - the timings, lift and deltas, and `cap`, the
-    // slots of the set arrays each robot owns (robot i: [i cap, (i + 1) cap)) - and per robot the plan in force: the stage it was generated
-    // from, its first double support and step count, and `keep`, the robot's slots in use by sets of stages <= that origin
-    struct GenPlan {
-        int ss = 0, ds = 0, final_ds = 0, cap = 0;
-        double lift = 0.0, delta[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-        std::vector<int> origin, first_ds, n_steps, keep;
-    } gp;
-    // its per-call device memory (footsteps, robot and tile lists, footprint tables, set table): one block that only grows; rp_done, recorded
-    // behind the call's kernels, guards it as splice_done guards the staging rows
-    char* rp_buf = nullptr; size_t rp_cap = 0;
-    hipEvent_t rp_done = nullptr; bool rp_pending = false;
-    // streamed_trajectories (an EXTERNAL handle): pl.rec holds ONE record per robot, the stage wcqp_tick_set_desired_* handed over for the next
-    // tick, pl.set_* one row set per robot; `planned` stays false (the splice of the DCM reference keeps working)
-    bool streamed = false, desired_set = false;
-    double* st_rec = nullptr; double* st_set_A = nullptr; double* st_set_b = nullptr; int* st_set_nc = nullptr;
-    int* st_pair = nullptr;       // [B][2] contact pair of the last consumed stage / of the stage in hand (tick_desired_kernel)
-    double* des_stage = nullptr;  // wcqp_tick_set_desired_host: [B][12 + 12 + 6 + 6 + 1 + 1] doubles, then [B] bytes
-    TickDevPL dpl(const TickDev& base) const { TickDevPL g; static_cast<TickDevGS&>(g) = dgs(base); g.pl = pl; return g; }
-    // ik_mode = POSITION (a planned handle): the non-linear IK runs every tick in position_tick_kernel, which takes `pos` beside the
-    // handle's TickDevPL in device memory; the chain's state, hand-off rows and live hull rows are the skewed handle's, but nothing is
-    // skewed - no prime launch, no tick ahead
-    bool position = false;
-    wcqp::PosTickDev pos{};
-};
-
 namespace {
-
-template <typename T>
-int dev_alloc(wcqp_tick_s* h, T** out, size_t count) {
-    void* p = nullptr;
-    if (hipMalloc(&p, (count > 0 ? count : 1) * sizeof(T)) != hipSuccess) return WCQP_E_NOMEM;
-    h->allocs.push_back(p);              // owned from here on: wcqp_tick_destroy frees it whatever happens next
-    if (hipMemset(p, 0, (count > 0 ? count : 1) * sizeof(T)) != hipSuccess) return WCQP_E_HIP;
-    *out = static_cast<T*>(p);
-    return WCQP_OK;
-}
-
-template <typename T>
-int dev_alloc(wcqp_tick_s* h, wcqp::GPtr<T>* out, size_t count) { return dev_alloc(h, &out->p, count); }
 
 // zmp_gains_at (tick_device.h) on the host, operation for operation
 void zmp_gains_host(const TickDev& d, const ZmpSched& z, double s, double* kg) {
@@ -528,7 +345,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); A_(h->feedback_fail, B); }
     if (h->external && h->kin) {
         A_(h->sens_stage, B * (2 * kDof + 12));
-        if (rc == WCQP_OK && hipEventCreateWithFlags(&h->run_done, hipEventDisableTiming) != hipSuccess) rc = WCQP_E_HIP;
+        if (rc == WCQP_OK && hipEventCreateWithFlags(&h->run.done, hipEventDisableTiming) != hipSuccess) rc = WCQP_E_HIP;
         if (filt_mask) {
             A_(h->filt_state, 2 * B * kFiltRec);
             h->filt_mask = filt_mask;
@@ -632,11 +449,7 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     if (h->graph) (void)hipGraphDestroy(h->graph);
     for (void* p : h->allocs) (void)hipFree(p);
     for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
-    if (h->splice_stage) (void)hipFree(h->splice_stage);
-    if (h->splice_done) (void)hipEventDestroy(h->splice_done);
-    if (h->rp_buf) (void)hipFree(h->rp_buf);
-    if (h->rp_done) (void)hipEventDestroy(h->rp_done);
-    if (h->run_done) (void)hipEventDestroy(h->run_done);
+    for (StagedBlock* b : {&h->splice, &h->rp, &h->run}) b->release();
     for (hipEvent_t e : h->gen_ev) if (e) (void)hipEventDestroy(e);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->kin) wcqp_kin_destroy(h->kin);
@@ -646,107 +459,15 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     return WCQP_OK;
 }
 
-// planned trajectories: the caller's per-stage arrays checked over the stages a run can reach (0 .. max_ticks), before anything of the
-// handle changes
-static int validate_plan(const wcqp_tick_s* h, const wcqp_tick_inputs* in) {
-    const TickDev& d = h->d;
-    const size_t B = (size_t)d.batch, T = (size_t)d.traj_len, reach = (size_t)h->p.max_ticks + 1;
-    if (!in->left_traj || !in->right_traj || !in->left_twist || !in->right_twist || !in->contact) return WCQP_E_INVALID;
-    for (size_t i = 0; i < B; ++i)
-        for (size_t t = 0; t < reach; ++t) {
-            const size_t w = i * T + t;
-            const unsigned f = in->contact[w];
-            if ((f & 3u) == 0u) return WCQP_E_INVALID;                          // neither foot in contact
-            if ((f & 4u) ? !(f & 1u) : !(f & 2u)) return WCQP_E_INVALID;        // the fixed-frame foot is not in contact
-            bool ok = true;
-            for (int k = 0; k < 12; ++k) ok = ok && std::isfinite(in->left_traj[w * 12 + k]) && std::isfinite(in->right_traj[w * 12 + k]);
-            for (int k = 0; k < 6; ++k) ok = ok && std::isfinite(in->left_twist[w * 6 + k]) && std::isfinite(in->right_twist[w * 6 + k]);
-            if (in->com_height_traj) ok = ok && std::isfinite(in->com_height_traj[w]);
-            if (in->com_height_vel) ok = ok && std::isfinite(in->com_height_vel[w]);
-            if (!ok) return WCQP_E_INVALID;
-        }
-    return WCQP_OK;
-}
-
-// the support-polygon row sets of a plan whose records are in place (in NULL-stream order): the previous upload's go, `ns` new ones are built
-// on the device from the records of their stages (at: record offsets, code: contact pairs - device arrays), and the handle's kernels see them
-static int build_plan_sets(wcqp_tick_s* h, size_t ns, const long long* d_at, const int* d_code) {
-    for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
-    h->set_A = nullptr; h->set_b = nullptr; h->set_nc = nullptr; h->n_sets = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&h->set_A), ns * 128) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&h->set_b), ns * 64) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&h->set_nc), ns * 4) != hipSuccess)
-        return WCQP_E_NOMEM;
-    PlanRect r;
-    for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
-    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((ns + 127) / 128)), dim3(128), 0, 0, (int)ns, r, h->pl.rec.get(), d_at, d_code,
-                       h->set_A, h->set_b, h->set_nc);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return WCQP_E_HIP;
-    // the kernels read the sets through the handle's TickDevPL in device memory
-    h->pl.set_A = h->set_A; h->pl.set_b = h->set_b; h->pl.set_nc = h->set_nc; h->n_sets = ns;
-    const TickDevPL g = h->dpl(h->d);
-    WCQP_HIP_TRY(hipMemcpy(h->d_dev, &g, sizeof(TickDevPL), hipMemcpyHostToDevice));
-    return WCQP_OK;
-}
-
-// ... repacked into the records (tick_device.h: kPlanRec), a slab of robots at a time, and the support-polygon row set of every change of
-// contact pair (and of stage 0) built from its stage's desired feet; the records name the set in force
-static int upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in) {
-    const TickDev& d = h->d;
-    const size_t B = (size_t)d.batch, T = (size_t)d.traj_len, reach = (size_t)h->p.max_ticks + 1;
-    std::vector<long long> set_at;       // record offset (doubles) of each set's stage
-    std::vector<int> set_code;           // its contact pair (0 left, 1 right, 2 both)
-    std::vector<double> set_of(B * T);   // the set in force at each stage
-    for (size_t i = 0; i < B; ++i) {
-        int prev = -1;
-        for (size_t t = 0; t < T; ++t) {
-            const int pair = (int)(in->contact[i * T + t] & 3u);
-            if (t < reach && pair != prev) {       // (beyond the reach no tick changes the pair: the last set stays)
-                set_at.push_back((long long)((i * T + t) * kPlanRec));
-                set_code.push_back(pair - 1);
-                prev = pair;
-            }
-            set_of[i * T + t] = (double)(set_at.size() - 1);
-        }
-    }
-    const size_t slab = 256;
-    std::vector<double> rec(slab * T * kPlanRec);
-    for (size_t i0 = 0; i0 < B; i0 += slab) {
-        const size_t n = B - i0 < slab ? B - i0 : slab;
-        for (size_t i = i0; i < i0 + n; ++i) {
-            const double h0 = in->state0[i * kStateLen + 68];
-            for (size_t t = 0; t < T; ++t) {
-                const size_t w = i * T + t;
-                double* r = &rec[((i - i0) * T + t) * kPlanRec];
-                r[kPlanFlags] = (double)in->contact[w];
-                r[kPlanHeight] = in->com_height_traj ? in->com_height_traj[w] : h0;
-                r[kPlanHeightVel] = in->com_height_vel ? in->com_height_vel[w] : 0.0;
-                std::memcpy(r + kPlanLeft, in->left_traj + w * 12, 96); std::memcpy(r + kPlanRight, in->right_traj + w * 12, 96);
-                std::memcpy(r + kPlanTwL, in->left_twist + w * 6, 48); std::memcpy(r + kPlanTwL + 6, in->right_twist + w * 6, 48);
-                r[kPlanHull] = set_of[w];
-            }
-        }
-        WCQP_HIP_TRY(hipMemcpy(const_cast<double*>(h->pl.rec.get()) + i0 * T * kPlanRec, rec.data(), n * T * kPlanRec * 8, hipMemcpyHostToDevice));
-    }
-    // the row sets, built on the device from the records just copied
-    const size_t ns = set_at.size();
-    long long* d_at = nullptr; int* d_code = nullptr;
-    int rc = WCQP_OK;
-    if (hipMalloc(reinterpret_cast<void**>(&d_at), ns * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_code), ns * 4) != hipSuccess) rc = WCQP_E_NOMEM;
-    if (rc == WCQP_OK && (hipMemcpy(d_at, set_at.data(), ns * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemcpy(d_code, set_code.data(), ns * 4, hipMemcpyHostToDevice) != hipSuccess))
-        rc = WCQP_E_HIP;
-    if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);
-    (void)hipFree(d_at); (void)hipFree(d_code);
-    return rc;
-}
+}  // extern "C"
 
 // The tail both uploads share (wcqp_tick_upload, wcqp_tick_upload_footsteps), once the trajectories are in place: the state records of the
 // chain, the pose block and joints, the initial DCM / CoM / command, the smoothers, filters and counters at rest, tick 0.  pair0 >= 0: the
 // contact pair of stage 0 where `in` holds no contact array.
-static int upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0) {
+#define UP_(dst, src, n) WCQP_HIP_TRY(hipMemcpy(const_cast<void*>(static_cast<const void*>(dst)), (src), (n), hipMemcpyHostToDevice))
+int wcqp::upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0) {
     TickDev& d = h->d;
     const size_t B = (size_t)d.batch;
-#define UP_(dst, src, n) WCQP_HIP_TRY(hipMemcpy(const_cast<void*>(static_cast<const void*>(dst)), (src), (n), hipMemcpyHostToDevice))
     if (d.skew) {
         // state of the MPC chain per axis: c_ref, v_ref_prev, com, u_prev (= measured ZMP), p_star, v_star_prev, dcm, spare
         std::vector<double> mst(B * 16, 0.0);
@@ -828,10 +549,11 @@ static int upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0) {
     h->phase = 0;
     h->feedback_set = false;
     h->desired_set = false;
-    h->run_pending = false;
+    h->run.pending = false;
     return WCQP_OK;
-#undef UP_
 }
+
+extern "C" {
 
 
 int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
@@ -839,7 +561,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     // (planned trajectories: no synthetic gait - phase0 and swing_twist may be NULL)
     if (!in->ref_traj || !in->state0 || !in->q0 || !in->dcm0 || !in->com0 || !in->u_init) return WCQP_E_INVALID;
     if (!h->planned && !h->streamed && (!in->phase0 || !in->swing_twist)) return WCQP_E_INVALID;
-    if (h->planned) { const int rcv = validate_plan(h, in); if (rcv != WCQP_OK) return rcv; }
+    if (h->planned) { const int rcv = wcqp::validate_plan(h, in); if (rcv != WCQP_OK) return rcv; }
     if (!h->kin && (!in->J_left || !in->J_right || !in->J_neck || !in->J_com)) return WCQP_E_INVALID;
     // (the reactive controller reads no hull rows)
     if (!h->kin && !h->d.reactive && (!in->hull_tab_A || !in->hull_tab_b || !in->hull_tab_nc)) return WCQP_E_INVALID;
@@ -857,7 +579,6 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     // from here on the device state changes: a call that fails on the way leaves the handle unrunnable until the next good upload
     h->uploaded = false;
     WCQP_HIP_TRY(hipDeviceSynchronize());
-#define UP_(dst, src, n) WCQP_HIP_TRY(hipMemcpy(const_cast<void*>(static_cast<const void*>(dst)), (src), (n), hipMemcpyHostToDevice))
     UP_(d.ref_traj, in->ref_traj, B * d.traj_len * 16);
     if (d.reactive || d.gain_sched) {
         // the planner's DCM velocity, or the forward difference (ref[t + 1] - ref[t]) / dT (the last stage, which no tick reads: 0)
@@ -876,7 +597,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
         }
     }
     if (h->planned) {
-        const int rcp = upload_plan(h, in);
+        const int rcp = wcqp::upload_plan(h, in);
         if (rcp != WCQP_OK) return rcp;
         h->generated = false;
         WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
@@ -891,333 +612,20 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     } else {
         UP_(d.phase0, in->phase0, B * 4); UP_(d.swing_twist, in->swing_twist, B * 48);
     }
+    return wcqp::upload_state(h, in, -1);
+}
 #undef UP_
-    return upload_state(h, in, -1);
-}
 
-int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps) {
-    if (!h || !in || !steps) return WCQP_E_INVALID;
-    if (!h->planned) return WCQP_E_UNSUPPORTED;
-    TickDev& d = h->d;
-    const size_t B = (size_t)d.batch;
-    const int K = steps->max_steps;
-    // everything is checked before anything of the handle changes (a handle uploaded before keeps that upload)
-    if (!in->state0 || !in->q0 || !in->com0 || !steps->n_steps || K < 0 || (K > 0 && (!steps->side || !steps->target))) return WCQP_E_INVALID;
-    if (steps->first_ds_ticks < 1 || steps->ss_ticks < 1 || steps->ds_ticks < 1 || steps->final_ds_ticks < 0) return WCQP_E_INVALID;
-    const int final_ds = steps->final_ds_ticks > 0 ? steps->final_ds_ticks : steps->ds_ticks;
-    const long long per = (long long)steps->ss_ticks + steps->ds_ticks;
-    if ((long long)steps->first_ds_ticks + (long long)K * per + final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
-    auto finite = [](const double* a, size_t n) { bool ok = true; for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(a[k]); return ok; };
-    if (!std::isfinite(steps->lift) || !finite(steps->zmp_delta_left, 2) || !finite(steps->zmp_delta_right, 2)) return WCQP_E_INVALID;
-    if (!finite(in->q0, B * kDof) || !finite(in->com0, B * 2) || (in->dcm0 && !finite(in->dcm0, B * 2)) || (in->u_init && !finite(in->u_init, B * 2)))
-        return WCQP_E_INVALID;
-    // the support-polygon sets: every robot owns `cap` slots - stage 0's set, then two per step (the stance foot alone, both again) where a
-    // tick can reach them.  A step occupies ss + 1 stages or more, so at most (max_ticks + 1) / (ss + 1) + 1 steps start at a stage
-    // <= max_ticks, whatever wcqp_tick_replan_footsteps later stitches together: the range never has to grow, and no set ever moves
-    const int cap = 1 + 2 * ((h->p.max_ticks + 1) / (steps->ss_ticks + 1) + 1);
-    std::vector<int> set_base(B);
-    const size_t ns = B * (size_t)cap;
-    for (size_t i = 0; i < B; ++i) {
-        const int n = steps->n_steps[i];
-        if (n < 0 || n > K) return WCQP_E_INVALID;
-        if (!finite(in->state0 + i * kStateLen + 24, 24) || !std::isfinite(in->state0[i * kStateLen + 68])) return WCQP_E_INVALID;
-        set_base[i] = (int)(i * (size_t)cap);
-        for (int k = 0; k < n; ++k)
-            if (steps->side[i * K + k] > 1 || !finite(steps->target + (i * K + k) * 3, 3)) return WCQP_E_INVALID;
-    }
-    if (ns > (size_t)1 << 30) return WCQP_E_UNSUPPORTED;
-    // from here on the device state changes: a call that fails on the way leaves the handle unrunnable until the next good upload
-    h->uploaded = false;
-    WCQP_HIP_TRY(hipDeviceSynchronize());
-    if (!h->gen_zmp0) { const int rca = dev_alloc(h, &h->gen_zmp0, B * 2); if (rca != WCQP_OK) return rca; }
-    // the footsteps, the table and the set table: device memory of this call
-    struct Scratch {
-        std::vector<void*> p;
-        ~Scratch() { for (void* q : p) (void)hipFree(q); }
-        void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes > 0 ? bytes : 1) != hipSuccess) return nullptr; p.push_back(q); return q; }
-    } scratch;
-    PlanGenDev g{};
-    const size_t BK = B * (size_t)K;
-    int* d_n = static_cast<int*>(scratch.get(B * 4)); int* d_base = static_cast<int*>(scratch.get(B * 4));
-    unsigned char* d_side = static_cast<unsigned char*>(scratch.get(BK)); double* d_tg = static_cast<double*>(scratch.get(BK * 24));
-    double* d_tab = static_cast<double*>(scratch.get(B * (size_t)(K + 1) * kFpRec * 8));
-    long long* d_at = static_cast<long long*>(scratch.get(ns * 8)); int* d_code = static_cast<int*>(scratch.get(ns * 4));
-    if (!d_n || !d_base || !d_side || !d_tg || !d_tab || !d_at || !d_code) return WCQP_E_NOMEM;
-    WCQP_HIP_TRY(hipMemset(d_code, 0xff, ns * 4));      // (-1: a slot without a set; the prologue enters the ones in use)
-    WCQP_HIP_TRY(hipMemcpy(d_n, steps->n_steps, B * 4, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d_base, set_base.data(), B * 4, hipMemcpyHostToDevice));
-    if (BK > 0) {
-        WCQP_HIP_TRY(hipMemcpy(d_side, steps->side, BK, hipMemcpyHostToDevice));
-        WCQP_HIP_TRY(hipMemcpy(d_tg, steps->target, BK * 24, hipMemcpyHostToDevice));
-    }
-    WCQP_HIP_TRY(hipMemcpy(d.state, in->state0, B * kStateLen * 8, hipMemcpyHostToDevice));      // (the initial footprints and the CoM height)
-    g.n_steps = d_n; g.side = d_side; g.target = d_tg; g.state = d.state; g.set_base = d_base; g.table = d_tab; g.set_at = d_at; g.set_code = d_code;
-    g.rec = const_cast<double*>(h->pl.rec.get()); g.ref = const_cast<double*>(d.ref_traj.get());
-    g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
-    g.zmp0 = h->gen_zmp0;
-    g.batch = d.batch; g.K = K; g.traj_len = d.traj_len; g.max_ticks = h->p.max_ticks;
-    g.first_ds = steps->first_ds_ticks; g.ss = steps->ss_ticks; g.ds = steps->ds_ticks; g.final_ds = final_ds;
-    g.lift = steps->lift; g.dT = d.dT; g.omega = d.omega; g.a = std::exp(d.omega * d.dT);
-    for (int k = 0; k < 2; ++k) { g.delta[0][k] = steps->zmp_delta_left[k]; g.delta[1][k] = steps->zmp_delta_right[k]; }
-    for (hipEvent_t& e : h->gen_ev) if (!e) WCQP_HIP_TRY(hipEventCreate(&e));
-    int rc = wcqp::plan_gen_enqueue(g, nullptr, h->gen_ev[0], h->gen_ev[1]);
-    if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);      // (synchronises)
-    if (rc != WCQP_OK) return rc;
-    WCQP_HIP_TRY(hipEventElapsedTime(&h->gen_record_ms, h->gen_ev[0], h->gen_ev[1]));
-    h->vel_explicit = g.vel != nullptr;       // (the generated velocities, where the handle keeps any: the splice has no tail for them)
-    h->generated = true;
-    {   // what a replan needs to know of this plan (wcqp_tick_replan_footsteps)
-        auto& gp = h->gp;
-        gp.ss = steps->ss_ticks; gp.ds = steps->ds_ticks; gp.final_ds = final_ds; gp.cap = cap; gp.lift = steps->lift;
-        for (int k = 0; k < 2; ++k) { gp.delta[0][k] = steps->zmp_delta_left[k]; gp.delta[1][k] = steps->zmp_delta_right[k]; }
-        gp.origin.assign(B, 0); gp.first_ds.assign(B, steps->first_ds_ticks); gp.keep.assign(B, 1);
-        gp.n_steps.assign(steps->n_steps, steps->n_steps + B);
-        h->rp_pending = false;      // (the device was synchronised above)
-    }
-    WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
-    WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
-    // dcm0 / u_init NULL: the generated DCM reference and ZMP of stage 0
-    std::vector<double> dcm0, u0;
-    wcqp_tick_inputs eff = *in;
-    if (!in->dcm0) {
-        dcm0.resize(B * 2);
-        WCQP_HIP_TRY(hipMemcpy2D(dcm0.data(), 16, d.ref_traj.get(), (size_t)d.traj_len * 16, 16, B, hipMemcpyDeviceToHost));
-        eff.dcm0 = dcm0.data();
-    }
-    if (!in->u_init) {
-        u0.resize(B * 2);
-        WCQP_HIP_TRY(hipMemcpy(u0.data(), h->gen_zmp0, B * 16, hipMemcpyDeviceToHost));
-        eff.u_init = u0.data();
-    }
-    return upload_state(h, &eff, 2);
-}
-
-int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) {
-    if (!h || !rp) return WCQP_E_INVALID;
-    if (!h->planned) return WCQP_E_UNSUPPORTED;
+// what both forms of wcqp_tick_set_feedback_* ask before they touch anything
+static int feedback_ready(const wcqp_tick_s* h, const double* dcm_meas, const double* com_meas, const double* zmp_meas) {
+    if (!h || !dcm_meas || !com_meas || !zmp_meas) return WCQP_E_INVALID;
+    if (!h->external) return WCQP_E_UNSUPPORTED;
     if (!h->uploaded) return WCQP_E_INVALID;
-    if (!h->generated) return WCQP_E_UNSUPPORTED;        // (a classically uploaded plan has no known timeline)
-    const TickDev& d = h->d;
-    auto& gp = h->gp;
-    const size_t B = (size_t)d.batch;
-    const int K = rp->max_steps, T = d.traj_len, fd = rp->first_ds_ticks, per = gp.ss + gp.ds, cap = gp.cap;
-    // everything is checked here, in closed form, before anything changes: a refused call leaves the handle exactly as it was
-    if (!rp->merge_stage || !rp->n_steps || K < 0 || (K > 0 && (!rp->side || !rp->target)) || fd < 1) return WCQP_E_INVALID;
-    if ((long long)T + fd + (long long)K * per + gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
-    std::vector<int> robots, keep(B, 0);
-    std::vector<int> tiles;       // (robot, tile) pairs
-    const int n_tile = (T + 63) / 64;
-    for (size_t i = 0; i < B; ++i) {
-        const int M = rp->merge_stage[i];
-        if (M == -1) continue;                            // (the robot keeps its plan: nothing of its rows is read)
-        // stage 0 is the initial state's, stages the enqueued ticks have consumed stay (within one wcqp_tick_run call the kernel reads a stage
-        // ahead, between calls nothing is ahead: M >= ticks_enqueued is the condition), and a plan is cut only behind its own origin
-        if (M < 1 || M < h->ticks_enqueued || M >= T || M < gp.origin[i]) return WCQP_E_INVALID;
-        const int n = rp->n_steps[i];
-        if (n < 0 || n > K) return WCQP_E_INVALID;
-        for (int k = 0; k < n; ++k) {
-            if (rp->side[i * K + k] > 1) return WCQP_E_INVALID;
-            for (int c = 0; c < 3; ++c) if (!std::isfinite(rp->target[(i * K + k) * 3 + c])) return WCQP_E_INVALID;
-        }
-        // the merge stage has both feet in contact in the plan in force: not inside one of its single supports
-        const int O = gp.origin[i], fo = gp.first_ds[i], no = gp.n_steps[i], r = M - O;
-        if (r >= fo) { const int k = (r - fo) / per, u = (r - fo) - k * per; if (k < no && u < gp.ss) return WCQP_E_INVALID; }
-        // the sets that survive: those of stages <= M (a set of stage M itself is built from the feet the new plan starts from)
-        int c0 = gp.keep[i];
-        const int reach = M < h->p.max_ticks ? M : h->p.max_ticks;
-        for (int k = 0; k < no; ++k) {
-            const long long s_k = (long long)O + fo + (long long)k * per;
-            c0 += (s_k <= reach ? 1 : 0) + (s_k + gp.ss <= reach ? 1 : 0);
-        }
-        int fresh = 0;
-        for (int k = 0; k < n; ++k) {
-            const long long s_k = (long long)M + fd + (long long)k * per;
-            fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + gp.ss <= h->p.max_ticks ? 1 : 0);
-        }
-        if (c0 < 1 || c0 + fresh > cap) return WCQP_E_INVALID;      // (cannot happen: see cap in wcqp_tick_upload_footsteps)
-        keep[i] = c0;
-        robots.push_back((int)i);
-        for (int tl = M / 64; tl < n_tile; ++tl) { tiles.push_back((int)i); tiles.push_back(tl); }
-    }
-    if (robots.empty()) return WCQP_OK;
-    // the call's device memory: what the host hands over first (one copy), then what the kernels write for each other
-    const size_t BK = B * (size_t)K, nr = robots.size(), nt = tiles.size() / 2, nslots = B * (size_t)cap;
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_org = carve(B * 4), o_n = carve(B * 4), o_base = carve(B * 4), o_rob = carve(nr * 4), o_tile = carve(nt * 8), o_side = carve(BK),
-                 o_tg = carve(BK * 24), front = off, o_tab = carve(B * (size_t)(K + 1) * kFpRec * 8), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
-    std::vector<char> blob(front, 0);
-    {
-        int* org = reinterpret_cast<int*>(blob.data() + o_org); int* nn = reinterpret_cast<int*>(blob.data() + o_n);
-        int* base = reinterpret_cast<int*>(blob.data() + o_base);
-        for (size_t i = 0; i < B; ++i) {
-            const bool on = rp->merge_stage[i] != -1;
-            org[i] = on ? rp->merge_stage[i] : -1; nn[i] = on ? rp->n_steps[i] : 0;
-            base[i] = (int)(i * (size_t)cap) + (on ? keep[i] - 1 : 0);
-        }
-        std::memcpy(blob.data() + o_rob, robots.data(), nr * 4); std::memcpy(blob.data() + o_tile, tiles.data(), nt * 8);
-        if (BK > 0) { std::memcpy(blob.data() + o_side, rp->side, BK); std::memcpy(blob.data() + o_tg, rp->target, BK * 24); }
-    }
-    if (!h->copy_stream) WCQP_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    if (!h->rp_done) WCQP_HIP_TRY(hipEventCreateWithFlags(&h->rp_done, hipEventDisableTiming));
-    if (h->rp_pending) { WCQP_HIP_TRY(hipEventSynchronize(h->rp_done)); h->rp_pending = false; }      // the previous replan has left the block
-    if (off > h->rp_cap) {
-        if (h->rp_buf) { (void)hipFree(h->rp_buf); h->rp_buf = nullptr; h->rp_cap = 0; }
-        void* p = nullptr;
-        if (hipMalloc(&p, off) != hipSuccess) return WCQP_E_NOMEM;
-        h->rp_buf = static_cast<char*>(p); h->rp_cap = off;
-    }
-    char* buf = h->rp_buf;
-    // the caller's HOST arrays are taken NOW (a copy stream of the handle's own, waited for before this call returns)
-    WCQP_HIP_TRY(hipMemcpyAsync(buf, blob.data(), front, hipMemcpyHostToDevice, h->copy_stream));
-    WCQP_HIP_TRY(hipStreamSynchronize(h->copy_stream));
-    PlanGenDev g{};
-    g.origin = reinterpret_cast<const int*>(buf + o_org); g.n_steps = reinterpret_cast<const int*>(buf + o_n);
-    g.set_base = reinterpret_cast<const int*>(buf + o_base); g.robots = reinterpret_cast<const int*>(buf + o_rob);
-    g.tiles = reinterpret_cast<const int2*>(buf + o_tile); g.side = reinterpret_cast<const unsigned char*>(buf + o_side);
-    g.target = reinterpret_cast<const double*>(buf + o_tg); g.table = reinterpret_cast<double*>(buf + o_tab);
-    g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = reinterpret_cast<int*>(buf + o_code);
-    g.state = d.state; g.h0 = d.com_h0.get();
-    g.rec = const_cast<double*>(h->pl.rec.get()); g.ref = const_cast<double*>(d.ref_traj.get());
-    g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
-    g.zmp0 = h->gen_zmp0;
-    g.batch = d.batch; g.K = K; g.traj_len = T; g.max_ticks = h->p.max_ticks; g.n_robots = (int)nr; g.n_tiles = (int)nt;
-    g.first_ds = fd; g.ss = gp.ss; g.ds = gp.ds; g.final_ds = gp.final_ds;
-    g.lift = gp.lift; g.dT = d.dT; g.omega = d.omega; g.a = std::exp(d.omega * d.dT);
-    for (int k = 0; k < 2; ++k) { g.delta[0][k] = gp.delta[0][k]; g.delta[1][k] = gp.delta[1][k]; }
-    // in the caller's stream order, behind the ticks already enqueued: no pointer a tick or a captured graph holds changes, and the set
-    // slots written are those past each robot's surviving ones, which no stage below its merge stage names
-    hipStream_t st = (hipStream_t)stream;
-    WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
-    const int rc = wcqp::plan_replan_enqueue(g, st);
-    if (rc != WCQP_OK) return rc;
-    PlanRect r;
-    for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
-    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, r, h->pl.rec.get(), g.set_at, g.set_code,
-                       h->set_A, h->set_b, h->set_nc);
-    WCQP_HIP_TRY(hipGetLastError());
-    WCQP_HIP_TRY(hipEventRecord(h->rp_done, st));
-    h->rp_pending = true;
-    for (int i : robots) { gp.origin[i] = rp->merge_stage[i]; gp.first_ds[i] = fd; gp.n_steps[i] = rp->n_steps[i]; gp.keep[i] = keep[i]; }
-    return WCQP_OK;
-}
-
-int wcqp_tick_get_plan(wcqp_tick_t h, int32_t robot0, int32_t n, int32_t stage0, int32_t m, const wcqp_tick_plan_window* out) {
-    if (!h || !out) return WCQP_E_INVALID;
-    if (!h->planned) return WCQP_E_UNSUPPORTED;
-    const TickDev& d = h->d;
-    if (!h->uploaded || robot0 < 0 || n < 1 || stage0 < 0 || m < 1 || (long long)robot0 + n > d.batch || (long long)stage0 + m > d.traj_len) return WCQP_E_INVALID;
-    const bool has_vel = d.reactive || d.gain_sched;
-    if ((out->dcm_vel_traj && !has_vel) || (out->u_init && !h->generated)) return WCQP_E_UNSUPPORTED;
-    WCQP_HIP_TRY(hipDeviceSynchronize());
-    const size_t N = (size_t)n, M = (size_t)m, T = (size_t)d.traj_len, R0 = (size_t)robot0, S0 = (size_t)stage0;
-    for (int which = 0; which < 2; ++which) {
-        double* dst = which ? out->dcm_vel_traj : out->ref_traj;
-        const double* src = which ? d.dcm_vel.get() : d.ref_traj.get();
-        if (dst) WCQP_HIP_TRY(hipMemcpy2D(dst, M * 16, src + (R0 * T + S0) * 2, T * 16, M * 16, N, hipMemcpyDeviceToHost));
-    }
-    if (out->u_init) WCQP_HIP_TRY(hipMemcpy(out->u_init, h->gen_zmp0 + R0 * 2, N * 16, hipMemcpyDeviceToHost));
-    const bool hull = out->hull_A || out->hull_b || out->hull_nc;
-    std::vector<double> sA, sb; std::vector<int> snc;
-    if (hull) {
-        sA.resize(h->n_sets * 16); sb.resize(h->n_sets * 8); snc.resize(h->n_sets);
-        WCQP_HIP_TRY(hipMemcpy(sA.data(), h->set_A, h->n_sets * 128, hipMemcpyDeviceToHost));
-        WCQP_HIP_TRY(hipMemcpy(sb.data(), h->set_b, h->n_sets * 64, hipMemcpyDeviceToHost));
-        WCQP_HIP_TRY(hipMemcpy(snc.data(), h->set_nc, h->n_sets * 4, hipMemcpyDeviceToHost));
-    }
-    if (!hull && !out->contact && !out->com_height && !out->com_height_vel && !out->left_traj && !out->right_traj && !out->left_twist && !out->right_twist)
-        return WCQP_OK;
-    // the records of the window, a slab of robots at a time (64 MiB of host memory at most, one robot at least), unpacked on the host
-    size_t slab = ((size_t)64 << 20) / (M * kPlanRec * 8);
-    slab = slab < 1 ? 1 : (slab > N ? N : slab);
-    std::vector<double> rec(slab * M * kPlanRec);
-    for (size_t i0 = 0; i0 < N; i0 += slab) {
-        const size_t nn = N - i0 < slab ? N - i0 : slab;
-        WCQP_HIP_TRY(hipMemcpy2D(rec.data(), M * kPlanRec * 8, h->pl.rec.get() + ((R0 + i0) * T + S0) * kPlanRec, T * kPlanRec * 8, M * kPlanRec * 8, nn,
-                                 hipMemcpyDeviceToHost));
-        for (size_t w0 = 0; w0 < nn * M; ++w0) {
-            const double* r = &rec[w0 * kPlanRec];
-            const size_t w = i0 * M + w0;
-            if (out->contact) out->contact[w] = (uint8_t)r[kPlanFlags];
-            if (out->com_height) out->com_height[w] = r[kPlanHeight];
-            if (out->com_height_vel) out->com_height_vel[w] = r[kPlanHeightVel];
-            if (out->left_traj) std::memcpy(out->left_traj + w * 12, r + kPlanLeft, 96);
-            if (out->right_traj) std::memcpy(out->right_traj + w * 12, r + kPlanRight, 96);
-            if (out->left_twist) std::memcpy(out->left_twist + w * 6, r + kPlanTwL, 48);
-            if (out->right_twist) std::memcpy(out->right_twist + w * 6, r + kPlanTwL + 6, 48);
-            if (hull) {
-                const size_t set = (size_t)r[kPlanHull];
-                if (set >= h->n_sets) return WCQP_E_HIP;
-                if (out->hull_A) std::memcpy(out->hull_A + w * 16, &sA[set * 16], 128);
-                if (out->hull_b) std::memcpy(out->hull_b + w * 8, &sb[set * 8], 64);
-                if (out->hull_nc) out->hull_nc[w] = snc[set];
-            }
-        }
-    }
-    return WCQP_OK;
-}
-
-int wcqp_tick_set_desired_device(wcqp_tick_t h, const wcqp_tick_desired* des, void* stream) {
-    if (!h || !des) return WCQP_E_INVALID;
-    if (!h->streamed) return WCQP_E_UNSUPPORTED;
-    if (!h->uploaded || !des->left_pose || !des->right_pose || !des->left_twist || !des->right_twist || !des->contact) return WCQP_E_INVALID;
-    const TickDev& d = h->d;
-    DesiredDev a{};
-    a.left_pose = des->left_pose; a.right_pose = des->right_pose; a.left_twist = des->left_twist; a.right_twist = des->right_twist;
-    a.com_height = des->com_height; a.com_height_vel = des->com_height_vel; a.contact = des->contact; a.h0 = d.com_h0;
-    a.rec = h->st_rec; a.set_A = h->st_set_A; a.set_b = h->st_set_b; a.set_nc = h->st_set_nc; a.pair = h->st_pair;
-    a.ik_fail = d.ik_fail; a.feedback_fail = h->feedback_fail;
-    a.batch = d.batch; a.first = h->desired_set ? 0 : 1; a.build = d.reactive ? 0 : 1;
-    PlanRect r;
-    for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
-    hipLaunchKernelGGL(tick_desired_kernel, dim3((unsigned)((d.batch + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a, r);
-    WCQP_HIP_TRY(hipGetLastError());
-    h->desired_set = true;
-    return WCQP_OK;
-}
-
-int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* des) {
-    if (!h || !des) return WCQP_E_INVALID;
-    if (!h->streamed) return WCQP_E_UNSUPPORTED;
-    if (!h->uploaded || !des->left_pose || !des->right_pose || !des->left_twist || !des->right_twist || !des->contact) return WCQP_E_INVALID;
-    const size_t B = (size_t)h->d.batch;
-    // the rules of the planned upload (validate_plan), checked here: an invalid stage leaves the handle as it was
-    for (size_t i = 0; i < B; ++i) {
-        const unsigned f = des->contact[i];
-        if ((f & 3u) == 0u) return WCQP_E_INVALID;
-        if ((f & 4u) ? !(f & 1u) : !(f & 2u)) return WCQP_E_INVALID;
-        bool ok = true;
-        for (int k = 0; k < 12; ++k) ok = ok && std::isfinite(des->left_pose[i * 12 + k]) && std::isfinite(des->right_pose[i * 12 + k]);
-        for (int k = 0; k < 6; ++k) ok = ok && std::isfinite(des->left_twist[i * 6 + k]) && std::isfinite(des->right_twist[i * 6 + k]);
-        if (des->com_height) ok = ok && std::isfinite(des->com_height[i]);
-        if (des->com_height_vel) ok = ok && std::isfinite(des->com_height_vel[i]);
-        if (!ok) return WCQP_E_INVALID;
-    }
-    // the last run may have been enqueued on a non-blocking stream, which the NULL stream below does not wait for: wait for its end
-    if (h->run_pending) { WCQP_HIP_TRY(hipEventSynchronize(h->run_done)); h->run_pending = false; }
-    double* st = h->des_stage;
-    wcqp_tick_desired dv{};
-    dv.left_pose = st; dv.right_pose = st + 12 * B; dv.left_twist = st + 24 * B; dv.right_twist = st + 30 * B;
-    dv.com_height = des->com_height ? st + 36 * B : nullptr; dv.com_height_vel = des->com_height_vel ? st + 37 * B : nullptr;
-    dv.contact = reinterpret_cast<const uint8_t*>(st + 38 * B);
-    WCQP_HIP_TRY(hipMemcpy(st, des->left_pose, B * 96, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 12 * B, des->right_pose, B * 96, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 24 * B, des->left_twist, B * 48, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 30 * B, des->right_twist, B * 48, hipMemcpyHostToDevice));
-    if (des->com_height) WCQP_HIP_TRY(hipMemcpy(st + 36 * B, des->com_height, B * 8, hipMemcpyHostToDevice));
-    if (des->com_height_vel) WCQP_HIP_TRY(hipMemcpy(st + 37 * B, des->com_height_vel, B * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 38 * B, des->contact, B, hipMemcpyHostToDevice));
-    const int rc = wcqp_tick_set_desired_device(h, &dv, nullptr);
-    if (rc != WCQP_OK) return rc;
-    // in place when this call returns: the tick may be enqueued on any stream, and the staging rows are free for the next call
-    WCQP_HIP_TRY(hipStreamSynchronize(nullptr));
     return WCQP_OK;
 }
 
 int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const double* com_meas, const double* zmp_meas, const double* q_meas, void* stream) {
-    if (!h || !dcm_meas || !com_meas || !zmp_meas) return WCQP_E_INVALID;
-    if (!h->external) return WCQP_E_UNSUPPORTED;
-    if (!h->uploaded) return WCQP_E_INVALID;
+    if (const int rc = feedback_ready(h, dcm_meas, com_meas, zmp_meas); rc != WCQP_OK) return rc;
     const int n = h->d.batch * kDof;
     hipLaunchKernelGGL(tick_feedback_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d, dcm_meas, com_meas, zmp_meas, q_meas, h->q_meas,
                        h->feedback_fail, h->ticks_enqueued);
@@ -1228,8 +636,7 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
 }
 
 int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const double* com_meas, const double* zmp_meas, const double* q_meas) {
-    if (!h || !dcm_meas || !com_meas || !zmp_meas) return WCQP_E_INVALID;
-    if (!h->external) return WCQP_E_UNSUPPORTED;
+    if (const int rc = feedback_ready(h, dcm_meas, com_meas, zmp_meas); rc != WCQP_OK) return rc;
     const size_t B = (size_t)h->d.batch;
     double* st = h->fb_stage;
     // (synchronous copies on the NULL stream: they wait for what the handle's last tick left running on a blocking stream, and the
@@ -1246,12 +653,18 @@ int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const dou
     return WCQP_OK;
 }
 
-int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
-                                         const double* wrench_right, void* stream) {
+// ... and both forms of wcqp_tick_set_sensor_feedback_*
+static int sensor_feedback_ready(const wcqp_tick_s* h, const double* q_meas, const double* dq_meas, const double* wrench_left, const double* wrench_right) {
     if (!h || !q_meas || !dq_meas || !wrench_left || !wrench_right) return WCQP_E_INVALID;
     if (!h->external || !h->kin || !h->feedback_fail) return WCQP_E_UNSUPPORTED;
     if (!h->uploaded) return WCQP_E_INVALID;
     if (h->streamed && !h->desired_set) return WCQP_E_INVALID;       // (the anchor is tick t's stage: wcqp_tick_set_desired_* goes first)
+    return WCQP_OK;
+}
+
+int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
+                                         const double* wrench_right, void* stream) {
+    if (const int rc = sensor_feedback_ready(h, q_meas, dq_meas, wrench_left, wrench_right); rc != WCQP_OK) return rc;
     const TickDev& d = h->d;
     SensorDev a{};
     a.q = q_meas; a.dq = dq_meas; a.wl = wrench_left; a.wr = wrench_right;
@@ -1274,13 +687,10 @@ int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, co
 
 int wcqp_tick_set_sensor_feedback_host(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
                                        const double* wrench_right) {
-    if (!h || !q_meas || !dq_meas || !wrench_left || !wrench_right) return WCQP_E_INVALID;
-    if (!h->external || !h->kin || !h->feedback_fail) return WCQP_E_UNSUPPORTED;
-    if (!h->uploaded) return WCQP_E_INVALID;
-    if (h->streamed && !h->desired_set) return WCQP_E_INVALID;
+    if (const int rc = sensor_feedback_ready(h, q_meas, dq_meas, wrench_left, wrench_right); rc != WCQP_OK) return rc;
     const size_t B = (size_t)h->d.batch;
     // the last run may have been enqueued on a non-blocking stream, which the NULL stream below does not wait for: wait for its end
-    if (h->run_pending) { WCQP_HIP_TRY(hipEventSynchronize(h->run_done)); h->run_pending = false; }
+    if (const int rc = h->run.wait(); rc != WCQP_OK) return rc;
     double* st = h->sens_stage;
     WCQP_HIP_TRY(hipMemcpy(st, q_meas, B * kDof * 8, hipMemcpyHostToDevice));
     WCQP_HIP_TRY(hipMemcpy(st + B * kDof, dq_meas, B * kDof * 8, hipMemcpyHostToDevice));
@@ -1359,7 +769,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
         if (rc != WCQP_OK) return rc;
         h->phase ^= 1; ++h->ticks_enqueued;
     }
-    if (h->run_done) { WCQP_HIP_TRY(hipEventRecord(h->run_done, s)); h->run_pending = true; }    // (sensor feedback: the host form waits for it)
+    if (h->run.done) { if (const int rc = h->run.guard(s); rc != WCQP_OK) return rc; }    // (sensor feedback: the host form waits for it)
     guard.armed = false;
     h->feedback_set = false;
     h->desired_set = false;
@@ -1381,20 +791,10 @@ int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stage
     // rows are therefore taken NOW - staged into device memory of the handle on a copy stream of its own, waited for before
     // this call returns - and the caller may release `ref_tail` as soon as it has.
     const size_t bytes = (size_t)d.batch * (size_t)n_stages * 16;
-    if (!h->copy_stream) WCQP_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    if (!h->splice_done) WCQP_HIP_TRY(hipEventCreateWithFlags(&h->splice_done, hipEventDisableTiming));
-    if (h->splice_pending) { WCQP_HIP_TRY(hipEventSynchronize(h->splice_done)); h->splice_pending = false; }   // the previous merge has left the staging rows
-    if (bytes > h->splice_cap) {
-        if (h->splice_stage) { (void)hipFree(h->splice_stage); h->splice_stage = nullptr; h->splice_cap = 0; }
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) return WCQP_E_NOMEM;
-        h->splice_stage = static_cast<double*>(p); h->splice_cap = bytes;
-    }
-    WCQP_HIP_TRY(hipMemcpyAsync(h->splice_stage, ref_tail, bytes, hipMemcpyHostToDevice, h->copy_stream));
-    WCQP_HIP_TRY(hipStreamSynchronize(h->copy_stream));
+    if (const int rc = h->splice.take(h->copy_stream, ref_tail, bytes, bytes); rc != WCQP_OK) return rc;      // (waits until the previous merge has left the staging rows)
     // strided copy: row i of the tail goes to stages [from_tick, from_tick + n_stages) of instance i, in stream order
     // behind the ticks already enqueued (the trajectory pointer the kernels - and any captured graph - hold does not change)
-    WCQP_HIP_TRY(hipMemcpy2DAsync(const_cast<double*>(d.ref_traj.get()) + (size_t)from_tick * 2, (size_t)d.traj_len * 16, h->splice_stage, (size_t)n_stages * 16,
+    WCQP_HIP_TRY(hipMemcpy2DAsync(const_cast<double*>(d.ref_traj.get()) + (size_t)from_tick * 2, (size_t)d.traj_len * 16, h->splice.mem.ptr, (size_t)n_stages * 16,
                                   (size_t)n_stages * 16, (size_t)d.batch, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (d.reactive || d.gain_sched) {
         // the forward difference of the stages the new ones touch: [from_tick - 1, from_tick + n_stages), the last stage excepted
@@ -1405,9 +805,7 @@ int wcqp_tick_splice_reference(wcqp_tick_t h, int32_t from_tick, int32_t n_stage
             WCQP_HIP_TRY(hipGetLastError());
         }
     }
-    WCQP_HIP_TRY(hipEventRecord(h->splice_done, (hipStream_t)stream));
-    h->splice_pending = true;
-    return WCQP_OK;
+    return h->splice.guard((hipStream_t)stream);
 }
 
 #ifdef WCQP_TICK_STAMPS

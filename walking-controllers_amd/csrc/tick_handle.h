@@ -1,0 +1,150 @@
+// The tick handle (wcqp_tick_t) and what its two translation units share: tick.hip (create / destroy, upload, run, splice, feedback,
+// download) and tick_plan.hip (planned, generated, replanned and streamed trajectories).  Internal, not ABI.
+#pragma once
+#include <vector>
+#include "wcqp_internal.h"
+#include "tick_device.h"
+#include "ik_common.h"
+#include "position_tick.h"
+
+// how a tick is launched: the skewed base-eliminated kernel (ONE launch), MPC + the 16-lane kernel with glue and post fused in
+// (two), or MPC, glue, IK and post (four; any other IK kernel, and what the fused forms are tested against)
+enum class TickForm { SKEWED, MPC_IK16, FOUR_LAUNCH };
+
+// A device block that takes the caller's HOST arrays at call time and is then read in the caller's stream order, behind ticks that may
+// still run for a long time: it only grows, and an event recorded behind its consumer guards it for the next call.  Without a block
+// (`mem` unused) it is that guard alone.
+struct StagedBlock {
+    wcqp::DeviceScratch mem;
+    hipEvent_t done = nullptr;
+    bool pending = false;
+    // the previous consumer has left
+    int wait() {
+        if (pending) { WCQP_HIP_TRY(hipEventSynchronize(done)); pending = false; }
+        return WCQP_OK;
+    }
+    // a block of `bytes` whose first `n` are the caller's `host` rows, taken NOW: copied on a copy stream of the handle's own (made here
+    // when there is none yet) and waited for before this returns
+    int take(hipStream_t& copy_stream, const void* host, size_t n, size_t bytes) {
+        if (!copy_stream) WCQP_HIP_TRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+        if (!done) WCQP_HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        int rc = wait();
+        if (rc == WCQP_OK) rc = mem.reserve(bytes);
+        if (rc != WCQP_OK) return rc;
+        WCQP_HIP_TRY(hipMemcpyAsync(mem.ptr, host, n, hipMemcpyHostToDevice, copy_stream));
+        WCQP_HIP_TRY(hipStreamSynchronize(copy_stream));
+        return WCQP_OK;
+    }
+    // the consumer is everything enqueued on `s` so far
+    int guard(hipStream_t s) {
+        WCQP_HIP_TRY(hipEventRecord(done, s));
+        pending = true;
+        return WCQP_OK;
+    }
+    void release() {
+        mem.release();
+        if (done) (void)hipEventDestroy(done);
+        done = nullptr; pending = false;
+    }
+};
+
+struct wcqp_tick_s {
+    wcqp_tick_params p{};
+    wcqp_mpc_t mpc = nullptr;
+    wcqp_ik_t ik = nullptr;
+    wcqp_tick::TickDev d{};
+    wcqp_tick::TickDev* d_dev = nullptr;     // skewed tick: a TickDevPL of `d` in device memory (the fused kernels read it from there, see ik4_device.h)
+    wcqp_ik::TickVariant variant{};   // skewed tick: the kernels this handle runs (wcqp_tick_create)
+    std::vector<void*> allocs;
+    double *J_left = nullptr, *J_right = nullptr, *J_neck = nullptr, *J_com = nullptr;
+    unsigned* mpc_active = nullptr; double* mpc_margin = nullptr;
+    unsigned *ik_lo = nullptr, *ik_up = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+    hipStream_t graph_stream = nullptr;
+    bool uploaded = false;
+    int ticks_enqueued = 0;  // since the last upload; its parity is the `phase` of the next tick
+    double* log_ferr = nullptr;   // logger rows with dense Jacobians: where the IK kernel forms the foot errors
+    TickForm form = TickForm::FOUR_LAUNCH;   // from the IK handle's route (wcqp_tick_create)
+    wcqp_kin_t kin = nullptr;     // use_kinematics: Jacobians, actual poses and hull rows are rebuilt every tick
+    wcqp_tick::KinTick kt{};
+    int phase = 0;                // which copy of the tick index the next launch reads (TickDev::tick2): toggles per LAUNCH
+    int ticks_per_launch = 1;     // > 1 only for the skewed tick without a kinematics launch: the ticks one launch walks through
+    // wcqp_tick_splice_reference: the caller's host rows are staged HERE at call time (a copy stream of the handle's own, waited
+    // for before the call returns), the strided device-to-device copy then runs in the caller's stream order
+    StagedBlock splice;
+    hipStream_t copy_stream = nullptr;
+    bool vel_explicit = false;    // uploaded with an explicit dcm_vel_traj (reactive controller): the splice has no velocity tail
+    bool external = false, feedback_set = false;     // wcqp_tick_params.plant = EXTERNAL: one tick per run call, each behind a set_feedback
+    double* q_meas = nullptr;
+    double* fb_stage = nullptr;   // wcqp_tick_set_feedback_host: [B][2 + 2 + 2 + dof]
+    // sensor feedback (EXTERNAL with kinematics, wcqp_tick_set_sensor_feedback_*): the host form's staging rows [B][dof + dof + 6 + 6],
+    // the rejection counter, and the guard each run records on its stream (no block: the host forms wait for it before they stage)
+    double* sens_stage = nullptr;
+    long long* feedback_fail = nullptr;
+    StagedBlock run;
+    // the sensor form's low-pass filters (wcqp_tick_params.*_cut_frequency; sensors.h): two slots of per-robot state [2][B][kFiltRec].  A
+    // sensor call reads slot filt_cur - what the last RUN tick left - and writes the other one; wcqp_tick_run commits it (filt_pending)
+    // when it consumes the tick, so a replaced call advances nothing and a tick fed by the plain form holds the state
+    double* filt_state = nullptr;
+    int filt_mask = 0, filt_cur = 0;
+    bool filt_started = false, filt_pending = false;
+    double filt_fb[3] = {0.0, 0.0, 0.0}, filt_fa[3] = {0.0, 0.0, 0.0};
+    std::vector<double> meas0;    // EXTERNAL: dcm0, com0, u_init of the last upload ([B][6]: wcqp_tick_outputs.measured before any tick)
+    wcqp_tick::ZmpSched zg{};     // zmp_gain_scheduling (d.gain_sched): the stance gains, the smoother, its per-robot state
+    // the handle's TickDev with the scheduling record behind it (what the scheduled kernels take)
+    wcqp_tick::TickDevGS dgs(const wcqp_tick::TickDev& base) const { wcqp_tick::TickDevGS g; static_cast<wcqp_tick::TickDev&>(g) = base; g.zg = zg; return g; }
+    // planned_trajectories: the per-stage records and what the planned kernels take (the scheduling record behind it, used or not)
+    bool planned = false;
+    wcqp_tick::PlanDev pl{};
+    double* set_A = nullptr; double* set_b = nullptr; int* set_nc = nullptr;     // the row sets of the last upload (PlanDev::set_*)
+    size_t n_sets = 0;            // how many (wcqp_tick_get_plan reads them back)
+    // wcqp_tick_upload_footsteps: the generated ZMP of stage 0 [B][2] (allocated by the first such upload), and whether the plan in place was generated
+    double* gen_zmp0 = nullptr; bool generated = false;
+    hipEvent_t gen_ev[2] = {nullptr, nullptr}; float gen_record_ms = 0.0f;     // the record pass of the last such upload, timed (wcqp_tick_info.plan_record_ms)
+    // wcqp_tick_replan_footsteps: what the last wcqp_tick_upload_footsteps fixed for the handle - the timings, lift and deltas, and `cap`, the
+    // slots of the set arrays each robot owns (robot i: [i cap, (i + 1) cap)) - and per robot the plan in force: the stage it was generated
+    // from, its first double support and step count, and `keep`, the robot's slots in use by sets of stages <= that origin
+    struct GenPlan {
+        int ss = 0, ds = 0, final_ds = 0, cap = 0;
+        double lift = 0.0, delta[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        std::vector<int> origin, first_ds, n_steps, keep;
+    } gp;
+    // its per-call device memory (footsteps, robot and tile lists, footprint tables, set table), guarded behind the call's kernels
+    StagedBlock rp;
+    // streamed_trajectories (an EXTERNAL handle): pl.rec holds ONE record per robot, the stage wcqp_tick_set_desired_* handed over for the next
+    // tick, pl.set_* one row set per robot; `planned` stays false (the splice of the DCM reference keeps working)
+    bool streamed = false, desired_set = false;
+    double* st_rec = nullptr; double* st_set_A = nullptr; double* st_set_b = nullptr; int* st_set_nc = nullptr;
+    int* st_pair = nullptr;       // [B][2] contact pair of the last consumed stage / of the stage in hand (tick_desired_kernel)
+    double* des_stage = nullptr;  // wcqp_tick_set_desired_host: [B][12 + 12 + 6 + 6 + 1 + 1] doubles, then [B] bytes
+    wcqp_tick::TickDevPL dpl(const wcqp_tick::TickDev& base) const { wcqp_tick::TickDevPL g; static_cast<wcqp_tick::TickDevGS&>(g) = dgs(base); g.pl = pl; return g; }
+    // ik_mode = POSITION (a planned handle): the non-linear IK runs every tick in position_tick_kernel, which takes `pos` beside the
+    // handle's TickDevPL in device memory; the chain's state, hand-off rows and live hull rows are the skewed handle's, but nothing is
+    // skewed - no prime launch, no tick ahead
+    bool position = false;
+    wcqp::PosTickDev pos{};
+};
+
+template <typename T>
+int dev_alloc(wcqp_tick_s* h, T** out, size_t count) {
+    void* p = nullptr;
+    if (hipMalloc(&p, (count > 0 ? count : 1) * sizeof(T)) != hipSuccess) return WCQP_E_NOMEM;
+    h->allocs.push_back(p);              // owned from here on: wcqp_tick_destroy frees it whatever happens next
+    if (hipMemset(p, 0, (count > 0 ? count : 1) * sizeof(T)) != hipSuccess) return WCQP_E_HIP;
+    *out = static_cast<T*>(p);
+    return WCQP_OK;
+}
+
+template <typename T>
+int dev_alloc(wcqp_tick_s* h, wcqp::GPtr<T>* out, size_t count) { return dev_alloc(h, &out->p, count); }
+
+namespace wcqp {
+// tick_plan.hip, for wcqp_tick_upload of a planned handle: the caller's per-stage arrays checked before anything of the handle changes,
+// then repacked into the records with their support-polygon row sets
+int validate_plan(const wcqp_tick_s* h, const wcqp_tick_inputs* in);
+int upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in);
+// tick.hip, the tail wcqp_tick_upload and wcqp_tick_upload_footsteps share once the trajectories are in place (pair0 >= 0: the contact
+// pair of stage 0 where `in` holds no contact array)
+int upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0);
+}  // namespace wcqp

@@ -1,0 +1,516 @@
+// The trajectories of a tick handle (tick_handle.h; tick.hip holds the rest of it): planned ones uploaded per stage (wcqp_tick_upload of a
+// planned handle), walks generated from footsteps and replanned at a merge stage (plan_gen.hip holds those kernels), the streamed stage
+// of the next tick, and the plan read back.  See include/wcqp.h for the contract.
+#include <cmath>
+#include <cstring>
+#include <vector>
+#include "tick_handle.h"
+#include "plan_gen.h"
+
+namespace {
+
+using namespace wcqp_tick;
+
+// planned trajectories: the support-polygon rows of every contact change (tick_device.h: PlanDev), one thread per set - the corners of
+// the feet in contact at the set's stage (its record's desired poses) hulled by the builder of hull.hip
+struct PlanRect { double v[8]; };
+PlanRect plan_rect(const wcqp_tick_s* h) {
+    PlanRect r;
+    for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
+    return r;
+}
+__global__ void plan_hull_sets_kernel(int n, PlanRect rect, const double* __restrict__ rec, const long long* __restrict__ at,
+                                      const int* __restrict__ code, double* __restrict__ A, double* __restrict__ b, int* __restrict__ nc) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    if (code[g] < 0) return;        // (a slot no set of this call occupies: generated plans keep a fixed range of slots per robot)
+    const double* r = rec + at[g];
+    double px[8], py[8];
+    int np = 0;
+    if (code[g] == 0 || code[g] == 2) wcqp_hull::foot_points(rect.v, r + kPlanLeft, px, py, np);
+    if (code[g] == 1 || code[g] == 2) wcqp_hull::foot_points(rect.v, r + kPlanRight, px, py, np);
+    nc[g] = wcqp_hull::hull_rows(px, py, np, A + (size_t)g * 16, b + (size_t)g * 8);
+}
+
+// streamed trajectories (wcqp_tick_set_desired_*): the stage of the next tick - what WalkingModule::updateModule pops from the front of the
+// planner's deques (WM/src/WalkingModule.cpp:509-511, 689-707, 1085-1165) - packed into the robot's record (tick_device.h: kPlanRec, ONE
+// per robot) and validated by the rules of the planned upload.  16 lanes per robot: lane j carries entries j, 16 + j and 32 + j.
+// A robot whose stage is invalid keeps its previous record and is stopped and counted like one whose sensor reading was rejected
+// (sensors.hip).  pair: per robot the contact pair of the last stage a tick consumed and of the stage in hand (-1 after an upload); `first`:
+// this is the first stage handed over since the last tick, so the pair in hand has been consumed.  When the new pair differs from the
+// consumed one, lane 0 builds the robot's support-polygon rows from this stage's feet with the builder of hull_device.h - here, not in the
+// tick kernel - into set i, which entry 39 names: the chain of tick t copies them into the live rows on seeing the change
+// (tick_mpc_finish_from, ...PredictiveController.cpp:364-435); with no change the rows stay, whatever the feet do.
+struct DesiredDev {
+    const double *left_pose, *right_pose, *left_twist, *right_twist, *com_height, *com_height_vel;
+    const unsigned char* contact;
+    const double* h0;               // [B] TickDev::com_h0: the height of a stage without one
+    double* rec; double* set_A; double* set_b; int* set_nc; int* pair;
+    long long *ik_fail, *feedback_fail;
+    int batch, first, build;        // build: the handle's controller reads hull rows (the MPC)
+};
+__global__ __launch_bounds__(64) void tick_desired_kernel(DesiredDev a, PlanRect rect) {
+    const int lane = threadIdx.x, grp = lane >> 4, j = lane & 15;
+    const long inst_raw = (long)blockIdx.x * 4 + grp;
+    const bool live = inst_raw < a.batch;
+    const size_t i = (size_t)(live ? inst_raw : (long)a.batch - 1);
+    const unsigned f = a.contact[i];
+    // entries j (flags, height, its velocity, the left pose and the first of the right), 16 + j, 32 + j (< 40: the twists' tail, the set)
+    double v0, v1, v2 = 0.0;
+    if (j == kPlanFlags) v0 = (double)f;
+    else if (j == kPlanHeight) v0 = a.com_height ? a.com_height[i] : a.h0[i];
+    else if (j == kPlanHeightVel) v0 = a.com_height_vel ? a.com_height_vel[i] : 0.0;
+    else if (j < kPlanRight) v0 = a.left_pose[i * 12 + (j - kPlanLeft)];
+    else v0 = a.right_pose[i * 12 + (j - kPlanRight)];
+    const int k1 = 16 + j;
+    v1 = k1 < kPlanTwL ? a.right_pose[i * 12 + (k1 - kPlanRight)] : a.left_twist[i * 6 + (k1 - kPlanTwL)];
+    const int k2 = 32 + j;
+    if (k2 < kPlanTwL + 6) v2 = a.left_twist[i * 6 + (k2 - kPlanTwL)];
+    else if (k2 < kPlanHull) v2 = a.right_twist[i * 6 + (k2 - kPlanTwL - 6)];
+    else if (k2 == kPlanHull) v2 = (double)i;
+    const bool flags_bad = (f & 3u) == 0u || ((f & 4u) ? !(f & 1u) : !(f & 2u));       // no foot in contact / the fixed-frame foot is not
+    const bool lane_bad = flags_bad || !(isfinite(v0) && isfinite(v1) && isfinite(v2));
+    const bool bad = ((__ballot(lane_bad) >> (grp * 16)) & 0xffffull) != 0ull;
+    if (!live) return;
+    int* pr = a.pair + i * 2;
+    const int consumed = a.first ? pr[1] : pr[0];
+    if (bad) {
+        if (j == 0) {
+            pr[0] = consumed;
+            a.feedback_fail[i] += 1;
+            if (a.ik_fail[i] == 0) a.ik_fail[i] = 1;
+        }
+        return;
+    }
+    double* r = a.rec + i * kPlanRec;
+    r[j] = v0; r[k1] = v1;
+    if (k2 <= kPlanHull) r[k2] = v2;
+    if (j != 0) return;
+    const int code = (int)(f & 3u) - 1;
+    pr[0] = consumed; pr[1] = code;
+    if (a.build && code != consumed) {
+        double px[8], py[8];
+        int np = 0;
+        if (code == 0 || code == 2) wcqp_hull::foot_points(rect.v, a.left_pose + i * 12, px, py, np);
+        if (code == 1 || code == 2) wcqp_hull::foot_points(rect.v, a.right_pose + i * 12, px, py, np);
+        a.set_nc[i] = wcqp_hull::hull_rows(px, py, np, a.set_A + i * 16, a.set_b + i * 8);
+    }
+}
+
+// A valid stage of one robot, for the planned upload and the streamed host form alike: a foot in contact, the fixed-frame foot in contact,
+// finite poses [12], twists [6] and heights (height / height_vel: the stage's own entry, or NULL for none)
+bool stage_valid(unsigned f, const double* left_pose, const double* right_pose, const double* left_twist, const double* right_twist,
+                 const double* height, const double* height_vel) {
+    if ((f & 3u) == 0u) return false;                          // neither foot in contact
+    if ((f & 4u) ? !(f & 1u) : !(f & 2u)) return false;        // the fixed-frame foot is not in contact
+    bool ok = true;
+    for (int k = 0; k < 12; ++k) ok = ok && std::isfinite(left_pose[k]) && std::isfinite(right_pose[k]);
+    for (int k = 0; k < 6; ++k) ok = ok && std::isfinite(left_twist[k]) && std::isfinite(right_twist[k]);
+    if (height) ok = ok && std::isfinite(*height);
+    if (height_vel) ok = ok && std::isfinite(*height_vel);
+    return ok;
+}
+
+// A valid footstep list of robot i, for the upload and the replan alike: 0 <= n <= K steps, each with a side <= 1 and a finite target
+bool footsteps_valid(size_t i, int K, const int32_t* n_steps, const uint8_t* side, const double* target) {
+    const int n = n_steps[i];
+    if (n < 0 || n > K) return false;
+    for (int k = 0; k < n; ++k) {
+        if (side[i * K + k] > 1) return false;
+        for (int c = 0; c < 3; ++c) if (!std::isfinite(target[(i * K + k) * 3 + c])) return false;
+    }
+    return true;
+}
+
+// What every pass of plan_gen.hip takes of a handle whose GenPlan scalars are in place, for lists of at most K steps per robot; the caller
+// adds its own list pointers and first_ds (and a replan its origins, robots, tiles and h0)
+PlanGenDev plan_gen_of(const wcqp_tick_s* h, int K) {
+    const TickDev& d = h->d;
+    const auto& gp = h->gp;
+    PlanGenDev g{};
+    g.state = d.state;
+    g.rec = const_cast<double*>(h->pl.rec.get()); g.ref = const_cast<double*>(d.ref_traj.get());
+    g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
+    g.zmp0 = h->gen_zmp0;
+    g.batch = d.batch; g.K = K; g.traj_len = d.traj_len; g.max_ticks = h->p.max_ticks;
+    g.ss = gp.ss; g.ds = gp.ds; g.final_ds = gp.final_ds;
+    g.lift = gp.lift; g.dT = d.dT; g.omega = d.omega; g.a = std::exp(d.omega * d.dT);
+    for (int k = 0; k < 2; ++k) { g.delta[0][k] = gp.delta[0][k]; g.delta[1][k] = gp.delta[1][k]; }
+    return g;
+}
+
+// the support-polygon row sets of a plan whose records are in place (in NULL-stream order): the previous upload's go, `ns` new ones are built
+// on the device from the records of their stages (at: record offsets, code: contact pairs - device arrays), and the handle's kernels see them
+int build_plan_sets(wcqp_tick_s* h, size_t ns, const long long* d_at, const int* d_code) {
+    for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
+    h->set_A = nullptr; h->set_b = nullptr; h->set_nc = nullptr; h->n_sets = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&h->set_A), ns * 128) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&h->set_b), ns * 64) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&h->set_nc), ns * 4) != hipSuccess)
+        return WCQP_E_NOMEM;
+    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((ns + 127) / 128)), dim3(128), 0, 0, (int)ns, plan_rect(h), h->pl.rec.get(), d_at, d_code,
+                       h->set_A, h->set_b, h->set_nc);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return WCQP_E_HIP;
+    // the kernels read the sets through the handle's TickDevPL in device memory
+    h->pl.set_A = h->set_A; h->pl.set_b = h->set_b; h->pl.set_nc = h->set_nc; h->n_sets = ns;
+    const TickDevPL g = h->dpl(h->d);
+    WCQP_HIP_TRY(hipMemcpy(h->d_dev, &g, sizeof(TickDevPL), hipMemcpyHostToDevice));
+    return WCQP_OK;
+}
+}  // namespace
+
+
+// planned trajectories: the caller's per-stage arrays checked over the stages a run can reach (0 .. max_ticks), before anything of the
+// handle changes
+int wcqp::validate_plan(const wcqp_tick_s* h, const wcqp_tick_inputs* in) {
+    const TickDev& d = h->d;
+    const size_t B = (size_t)d.batch, T = (size_t)d.traj_len, reach = (size_t)h->p.max_ticks + 1;
+    if (!in->left_traj || !in->right_traj || !in->left_twist || !in->right_twist || !in->contact) return WCQP_E_INVALID;
+    for (size_t i = 0; i < B; ++i)
+        for (size_t t = 0; t < reach; ++t) {
+            const size_t w = i * T + t;
+            if (!stage_valid(in->contact[w], in->left_traj + w * 12, in->right_traj + w * 12, in->left_twist + w * 6, in->right_twist + w * 6,
+                             in->com_height_traj ? in->com_height_traj + w : nullptr, in->com_height_vel ? in->com_height_vel + w : nullptr))
+                return WCQP_E_INVALID;
+        }
+    return WCQP_OK;
+}
+
+// ... repacked into the records (tick_device.h: kPlanRec), a slab of robots at a time, and the support-polygon row set of every change of
+// contact pair (and of stage 0) built from its stage's desired feet; the records name the set in force
+int wcqp::upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in) {
+    const TickDev& d = h->d;
+    const size_t B = (size_t)d.batch, T = (size_t)d.traj_len, reach = (size_t)h->p.max_ticks + 1;
+    std::vector<long long> set_at;       // record offset (doubles) of each set's stage
+    std::vector<int> set_code;           // its contact pair (0 left, 1 right, 2 both)
+    std::vector<double> set_of(B * T);   // the set in force at each stage
+    for (size_t i = 0; i < B; ++i) {
+        int prev = -1;
+        for (size_t t = 0; t < T; ++t) {
+            const int pair = (int)(in->contact[i * T + t] & 3u);
+            if (t < reach && pair != prev) {       // (beyond the reach no tick changes the pair: the last set stays)
+                set_at.push_back((long long)((i * T + t) * kPlanRec));
+                set_code.push_back(pair - 1);
+                prev = pair;
+            }
+            set_of[i * T + t] = (double)(set_at.size() - 1);
+        }
+    }
+    const size_t slab = 256;
+    std::vector<double> rec(slab * T * kPlanRec);
+    for (size_t i0 = 0; i0 < B; i0 += slab) {
+        const size_t n = B - i0 < slab ? B - i0 : slab;
+        for (size_t i = i0; i < i0 + n; ++i) {
+            const double h0 = in->state0[i * kStateLen + 68];
+            for (size_t t = 0; t < T; ++t) {
+                const size_t w = i * T + t;
+                double* r = &rec[((i - i0) * T + t) * kPlanRec];
+                r[kPlanFlags] = (double)in->contact[w];
+                r[kPlanHeight] = in->com_height_traj ? in->com_height_traj[w] : h0;
+                r[kPlanHeightVel] = in->com_height_vel ? in->com_height_vel[w] : 0.0;
+                std::memcpy(r + kPlanLeft, in->left_traj + w * 12, 96); std::memcpy(r + kPlanRight, in->right_traj + w * 12, 96);
+                std::memcpy(r + kPlanTwL, in->left_twist + w * 6, 48); std::memcpy(r + kPlanTwL + 6, in->right_twist + w * 6, 48);
+                r[kPlanHull] = set_of[w];
+            }
+        }
+        WCQP_HIP_TRY(hipMemcpy(const_cast<double*>(h->pl.rec.get()) + i0 * T * kPlanRec, rec.data(), n * T * kPlanRec * 8, hipMemcpyHostToDevice));
+    }
+    // the row sets, built on the device from the records just copied
+    const size_t ns = set_at.size();
+    long long* d_at = nullptr; int* d_code = nullptr;
+    int rc = WCQP_OK;
+    if (hipMalloc(reinterpret_cast<void**>(&d_at), ns * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_code), ns * 4) != hipSuccess) rc = WCQP_E_NOMEM;
+    if (rc == WCQP_OK && (hipMemcpy(d_at, set_at.data(), ns * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(d_code, set_code.data(), ns * 4, hipMemcpyHostToDevice) != hipSuccess))
+        rc = WCQP_E_HIP;
+    if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);
+    (void)hipFree(d_at); (void)hipFree(d_code);
+    return rc;
+}
+
+extern "C" {
+
+int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps) {
+    if (!h || !in || !steps) return WCQP_E_INVALID;
+    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    TickDev& d = h->d;
+    const size_t B = (size_t)d.batch;
+    const int K = steps->max_steps;
+    // everything is checked before anything of the handle changes (a handle uploaded before keeps that upload)
+    if (!in->state0 || !in->q0 || !in->com0 || !steps->n_steps || K < 0 || (K > 0 && (!steps->side || !steps->target))) return WCQP_E_INVALID;
+    if (steps->first_ds_ticks < 1 || steps->ss_ticks < 1 || steps->ds_ticks < 1 || steps->final_ds_ticks < 0) return WCQP_E_INVALID;
+    const int final_ds = steps->final_ds_ticks > 0 ? steps->final_ds_ticks : steps->ds_ticks;
+    const long long per = (long long)steps->ss_ticks + steps->ds_ticks;
+    if ((long long)steps->first_ds_ticks + (long long)K * per + final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    auto finite = [](const double* a, size_t n) { bool ok = true; for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(a[k]); return ok; };
+    if (!std::isfinite(steps->lift) || !finite(steps->zmp_delta_left, 2) || !finite(steps->zmp_delta_right, 2)) return WCQP_E_INVALID;
+    if (!finite(in->q0, B * kDof) || !finite(in->com0, B * 2) || (in->dcm0 && !finite(in->dcm0, B * 2)) || (in->u_init && !finite(in->u_init, B * 2)))
+        return WCQP_E_INVALID;
+    // the support-polygon sets: every robot owns `cap` slots - stage 0's set, then two per step (the stance foot alone, both again) where a
+    // tick can reach them.  A step occupies ss + 1 stages or more, so at most (max_ticks + 1) / (ss + 1) + 1 steps start at a stage
+    // <= max_ticks, whatever wcqp_tick_replan_footsteps later stitches together: the range never has to grow, and no set ever moves
+    const int cap = 1 + 2 * ((h->p.max_ticks + 1) / (steps->ss_ticks + 1) + 1);
+    std::vector<int> set_base(B);
+    const size_t ns = B * (size_t)cap;
+    for (size_t i = 0; i < B; ++i) {
+        if (!footsteps_valid(i, K, steps->n_steps, steps->side, steps->target)) return WCQP_E_INVALID;
+        if (!finite(in->state0 + i * kStateLen + 24, 24) || !std::isfinite(in->state0[i * kStateLen + 68])) return WCQP_E_INVALID;
+        set_base[i] = (int)(i * (size_t)cap);
+    }
+    if (ns > (size_t)1 << 30) return WCQP_E_UNSUPPORTED;
+    // from here on the device state changes: a call that fails on the way leaves the handle unrunnable until the next good upload
+    h->uploaded = false;
+    WCQP_HIP_TRY(hipDeviceSynchronize());
+    if (!h->gen_zmp0) { const int rca = dev_alloc(h, &h->gen_zmp0, B * 2); if (rca != WCQP_OK) return rca; }
+    {   // what this plan fixes for the handle, and a replan needs to know of it (wcqp_tick_replan_footsteps)
+        auto& gp = h->gp;
+        gp.ss = steps->ss_ticks; gp.ds = steps->ds_ticks; gp.final_ds = final_ds; gp.cap = cap; gp.lift = steps->lift;
+        for (int k = 0; k < 2; ++k) { gp.delta[0][k] = steps->zmp_delta_left[k]; gp.delta[1][k] = steps->zmp_delta_right[k]; }
+    }
+    // the footsteps, the table and the set table: device memory of this call
+    struct Scratch {
+        std::vector<void*> p;
+        ~Scratch() { for (void* q : p) (void)hipFree(q); }
+        void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes > 0 ? bytes : 1) != hipSuccess) return nullptr; p.push_back(q); return q; }
+    } scratch;
+    PlanGenDev g = plan_gen_of(h, K);
+    const size_t BK = B * (size_t)K;
+    int* d_n = static_cast<int*>(scratch.get(B * 4)); int* d_base = static_cast<int*>(scratch.get(B * 4));
+    unsigned char* d_side = static_cast<unsigned char*>(scratch.get(BK)); double* d_tg = static_cast<double*>(scratch.get(BK * 24));
+    double* d_tab = static_cast<double*>(scratch.get(B * (size_t)(K + 1) * kFpRec * 8));
+    long long* d_at = static_cast<long long*>(scratch.get(ns * 8)); int* d_code = static_cast<int*>(scratch.get(ns * 4));
+    if (!d_n || !d_base || !d_side || !d_tg || !d_tab || !d_at || !d_code) return WCQP_E_NOMEM;
+    WCQP_HIP_TRY(hipMemset(d_code, 0xff, ns * 4));      // (-1: a slot without a set; the prologue enters the ones in use)
+    WCQP_HIP_TRY(hipMemcpy(d_n, steps->n_steps, B * 4, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(d_base, set_base.data(), B * 4, hipMemcpyHostToDevice));
+    if (BK > 0) {
+        WCQP_HIP_TRY(hipMemcpy(d_side, steps->side, BK, hipMemcpyHostToDevice));
+        WCQP_HIP_TRY(hipMemcpy(d_tg, steps->target, BK * 24, hipMemcpyHostToDevice));
+    }
+    WCQP_HIP_TRY(hipMemcpy(d.state, in->state0, B * kStateLen * 8, hipMemcpyHostToDevice));      // (the initial footprints and the CoM height)
+    g.n_steps = d_n; g.side = d_side; g.target = d_tg; g.set_base = d_base; g.table = d_tab; g.set_at = d_at; g.set_code = d_code;
+    g.first_ds = steps->first_ds_ticks;
+    for (hipEvent_t& e : h->gen_ev) if (!e) WCQP_HIP_TRY(hipEventCreate(&e));
+    int rc = wcqp::plan_gen_enqueue(g, nullptr, h->gen_ev[0], h->gen_ev[1]);
+    if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);      // (synchronises)
+    if (rc != WCQP_OK) return rc;
+    WCQP_HIP_TRY(hipEventElapsedTime(&h->gen_record_ms, h->gen_ev[0], h->gen_ev[1]));
+    h->vel_explicit = g.vel != nullptr;       // (the generated velocities, where the handle keeps any: the splice has no tail for them)
+    h->generated = true;
+    {   // per robot the plan in force
+        auto& gp = h->gp;
+        gp.origin.assign(B, 0); gp.first_ds.assign(B, steps->first_ds_ticks); gp.keep.assign(B, 1);
+        gp.n_steps.assign(steps->n_steps, steps->n_steps + B);
+        h->rp.pending = false;      // (the device was synchronised above)
+    }
+    WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
+    WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
+    // dcm0 / u_init NULL: the generated DCM reference and ZMP of stage 0
+    std::vector<double> dcm0, u0;
+    wcqp_tick_inputs eff = *in;
+    if (!in->dcm0) {
+        dcm0.resize(B * 2);
+        WCQP_HIP_TRY(hipMemcpy2D(dcm0.data(), 16, d.ref_traj.get(), (size_t)d.traj_len * 16, 16, B, hipMemcpyDeviceToHost));
+        eff.dcm0 = dcm0.data();
+    }
+    if (!in->u_init) {
+        u0.resize(B * 2);
+        WCQP_HIP_TRY(hipMemcpy(u0.data(), h->gen_zmp0, B * 16, hipMemcpyDeviceToHost));
+        eff.u_init = u0.data();
+    }
+    return wcqp::upload_state(h, &eff, 2);
+}
+
+int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) {
+    if (!h || !rp) return WCQP_E_INVALID;
+    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    if (!h->uploaded) return WCQP_E_INVALID;
+    if (!h->generated) return WCQP_E_UNSUPPORTED;        // (a classically uploaded plan has no known timeline)
+    const TickDev& d = h->d;
+    auto& gp = h->gp;
+    const size_t B = (size_t)d.batch;
+    const int K = rp->max_steps, T = d.traj_len, fd = rp->first_ds_ticks, per = gp.ss + gp.ds, cap = gp.cap;
+    // everything is checked here, in closed form, before anything changes: a refused call leaves the handle exactly as it was
+    if (!rp->merge_stage || !rp->n_steps || K < 0 || (K > 0 && (!rp->side || !rp->target)) || fd < 1) return WCQP_E_INVALID;
+    if ((long long)T + fd + (long long)K * per + gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    std::vector<int> robots, keep(B, 0);
+    std::vector<int> tiles;       // (robot, tile) pairs
+    const int n_tile = (T + 63) / 64;
+    for (size_t i = 0; i < B; ++i) {
+        const int M = rp->merge_stage[i];
+        if (M == -1) continue;                            // (the robot keeps its plan: nothing of its rows is read)
+        // stage 0 is the initial state's, stages the enqueued ticks have consumed stay (within one wcqp_tick_run call the kernel reads a stage
+        // ahead, between calls nothing is ahead: M >= ticks_enqueued is the condition), and a plan is cut only behind its own origin
+        if (M < 1 || M < h->ticks_enqueued || M >= T || M < gp.origin[i]) return WCQP_E_INVALID;
+        if (!footsteps_valid(i, K, rp->n_steps, rp->side, rp->target)) return WCQP_E_INVALID;
+        const int n = rp->n_steps[i];
+        // the merge stage has both feet in contact in the plan in force: not inside one of its single supports
+        const int O = gp.origin[i], fo = gp.first_ds[i], no = gp.n_steps[i], r = M - O;
+        if (r >= fo) { const int k = (r - fo) / per, u = (r - fo) - k * per; if (k < no && u < gp.ss) return WCQP_E_INVALID; }
+        // the sets that survive: those of stages <= M (a set of stage M itself is built from the feet the new plan starts from)
+        int c0 = gp.keep[i];
+        const int reach = M < h->p.max_ticks ? M : h->p.max_ticks;
+        for (int k = 0; k < no; ++k) {
+            const long long s_k = (long long)O + fo + (long long)k * per;
+            c0 += (s_k <= reach ? 1 : 0) + (s_k + gp.ss <= reach ? 1 : 0);
+        }
+        int fresh = 0;
+        for (int k = 0; k < n; ++k) {
+            const long long s_k = (long long)M + fd + (long long)k * per;
+            fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + gp.ss <= h->p.max_ticks ? 1 : 0);
+        }
+        if (c0 < 1 || c0 + fresh > cap) return WCQP_E_INVALID;      // (cannot happen: see cap in wcqp_tick_upload_footsteps)
+        keep[i] = c0;
+        robots.push_back((int)i);
+        for (int tl = M / 64; tl < n_tile; ++tl) { tiles.push_back((int)i); tiles.push_back(tl); }
+    }
+    if (robots.empty()) return WCQP_OK;
+    // the call's device memory: what the host hands over first (one copy), then what the kernels write for each other
+    const size_t BK = B * (size_t)K, nr = robots.size(), nt = tiles.size() / 2, nslots = B * (size_t)cap;
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_org = carve(B * 4), o_n = carve(B * 4), o_base = carve(B * 4), o_rob = carve(nr * 4), o_tile = carve(nt * 8), o_side = carve(BK),
+                 o_tg = carve(BK * 24), front = off, o_tab = carve(B * (size_t)(K + 1) * kFpRec * 8), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
+    std::vector<char> blob(front, 0);
+    {
+        int* org = reinterpret_cast<int*>(blob.data() + o_org); int* nn = reinterpret_cast<int*>(blob.data() + o_n);
+        int* base = reinterpret_cast<int*>(blob.data() + o_base);
+        for (size_t i = 0; i < B; ++i) {
+            const bool on = rp->merge_stage[i] != -1;
+            org[i] = on ? rp->merge_stage[i] : -1; nn[i] = on ? rp->n_steps[i] : 0;
+            base[i] = (int)(i * (size_t)cap) + (on ? keep[i] - 1 : 0);
+        }
+        std::memcpy(blob.data() + o_rob, robots.data(), nr * 4); std::memcpy(blob.data() + o_tile, tiles.data(), nt * 8);
+        if (BK > 0) { std::memcpy(blob.data() + o_side, rp->side, BK); std::memcpy(blob.data() + o_tg, rp->target, BK * 24); }
+    }
+    // the caller's HOST arrays are taken NOW, once the previous replan has left the block
+    if (const int rc = h->rp.take(h->copy_stream, blob.data(), front, off); rc != WCQP_OK) return rc;
+    char* buf = static_cast<char*>(h->rp.mem.ptr);
+    PlanGenDev g = plan_gen_of(h, K);
+    g.origin = reinterpret_cast<const int*>(buf + o_org); g.n_steps = reinterpret_cast<const int*>(buf + o_n);
+    g.set_base = reinterpret_cast<const int*>(buf + o_base); g.robots = reinterpret_cast<const int*>(buf + o_rob);
+    g.tiles = reinterpret_cast<const int2*>(buf + o_tile); g.side = reinterpret_cast<const unsigned char*>(buf + o_side);
+    g.target = reinterpret_cast<const double*>(buf + o_tg); g.table = reinterpret_cast<double*>(buf + o_tab);
+    g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = reinterpret_cast<int*>(buf + o_code);
+    g.h0 = d.com_h0.get(); g.n_robots = (int)nr; g.n_tiles = (int)nt; g.first_ds = fd;
+    // in the caller's stream order, behind the ticks already enqueued: no pointer a tick or a captured graph holds changes, and the set
+    // slots written are those past each robot's surviving ones, which no stage below its merge stage names
+    hipStream_t st = (hipStream_t)stream;
+    WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
+    const int rc = wcqp::plan_replan_enqueue(g, st);
+    if (rc != WCQP_OK) return rc;
+    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->pl.rec.get(), g.set_at, g.set_code,
+                       h->set_A, h->set_b, h->set_nc);
+    WCQP_HIP_TRY(hipGetLastError());
+    if (const int rc = h->rp.guard(st); rc != WCQP_OK) return rc;
+    for (int i : robots) { gp.origin[i] = rp->merge_stage[i]; gp.first_ds[i] = fd; gp.n_steps[i] = rp->n_steps[i]; gp.keep[i] = keep[i]; }
+    return WCQP_OK;
+}
+
+int wcqp_tick_get_plan(wcqp_tick_t h, int32_t robot0, int32_t n, int32_t stage0, int32_t m, const wcqp_tick_plan_window* out) {
+    if (!h || !out) return WCQP_E_INVALID;
+    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    const TickDev& d = h->d;
+    if (!h->uploaded || robot0 < 0 || n < 1 || stage0 < 0 || m < 1 || (long long)robot0 + n > d.batch || (long long)stage0 + m > d.traj_len) return WCQP_E_INVALID;
+    const bool has_vel = d.reactive || d.gain_sched;
+    if ((out->dcm_vel_traj && !has_vel) || (out->u_init && !h->generated)) return WCQP_E_UNSUPPORTED;
+    WCQP_HIP_TRY(hipDeviceSynchronize());
+    const size_t N = (size_t)n, M = (size_t)m, T = (size_t)d.traj_len, R0 = (size_t)robot0, S0 = (size_t)stage0;
+    for (int which = 0; which < 2; ++which) {
+        double* dst = which ? out->dcm_vel_traj : out->ref_traj;
+        const double* src = which ? d.dcm_vel.get() : d.ref_traj.get();
+        if (dst) WCQP_HIP_TRY(hipMemcpy2D(dst, M * 16, src + (R0 * T + S0) * 2, T * 16, M * 16, N, hipMemcpyDeviceToHost));
+    }
+    if (out->u_init) WCQP_HIP_TRY(hipMemcpy(out->u_init, h->gen_zmp0 + R0 * 2, N * 16, hipMemcpyDeviceToHost));
+    const bool hull = out->hull_A || out->hull_b || out->hull_nc;
+    std::vector<double> sA, sb; std::vector<int> snc;
+    if (hull) {
+        sA.resize(h->n_sets * 16); sb.resize(h->n_sets * 8); snc.resize(h->n_sets);
+        WCQP_HIP_TRY(hipMemcpy(sA.data(), h->set_A, h->n_sets * 128, hipMemcpyDeviceToHost));
+        WCQP_HIP_TRY(hipMemcpy(sb.data(), h->set_b, h->n_sets * 64, hipMemcpyDeviceToHost));
+        WCQP_HIP_TRY(hipMemcpy(snc.data(), h->set_nc, h->n_sets * 4, hipMemcpyDeviceToHost));
+    }
+    if (!hull && !out->contact && !out->com_height && !out->com_height_vel && !out->left_traj && !out->right_traj && !out->left_twist && !out->right_twist)
+        return WCQP_OK;
+    // the records of the window, a slab of robots at a time (64 MiB of host memory at most, one robot at least), unpacked on the host
+    size_t slab = ((size_t)64 << 20) / (M * kPlanRec * 8);
+    slab = slab < 1 ? 1 : (slab > N ? N : slab);
+    std::vector<double> rec(slab * M * kPlanRec);
+    for (size_t i0 = 0; i0 < N; i0 += slab) {
+        const size_t nn = N - i0 < slab ? N - i0 : slab;
+        WCQP_HIP_TRY(hipMemcpy2D(rec.data(), M * kPlanRec * 8, h->pl.rec.get() + ((R0 + i0) * T + S0) * kPlanRec, T * kPlanRec * 8, M * kPlanRec * 8, nn,
+                                 hipMemcpyDeviceToHost));
+        for (size_t w0 = 0; w0 < nn * M; ++w0) {
+            const double* r = &rec[w0 * kPlanRec];
+            const size_t w = i0 * M + w0;
+            if (out->contact) out->contact[w] = (uint8_t)r[kPlanFlags];
+            if (out->com_height) out->com_height[w] = r[kPlanHeight];
+            if (out->com_height_vel) out->com_height_vel[w] = r[kPlanHeightVel];
+            if (out->left_traj) std::memcpy(out->left_traj + w * 12, r + kPlanLeft, 96);
+            if (out->right_traj) std::memcpy(out->right_traj + w * 12, r + kPlanRight, 96);
+            if (out->left_twist) std::memcpy(out->left_twist + w * 6, r + kPlanTwL, 48);
+            if (out->right_twist) std::memcpy(out->right_twist + w * 6, r + kPlanTwL + 6, 48);
+            if (hull) {
+                const size_t set = (size_t)r[kPlanHull];
+                if (set >= h->n_sets) return WCQP_E_HIP;
+                if (out->hull_A) std::memcpy(out->hull_A + w * 16, &sA[set * 16], 128);
+                if (out->hull_b) std::memcpy(out->hull_b + w * 8, &sb[set * 8], 64);
+                if (out->hull_nc) out->hull_nc[w] = snc[set];
+            }
+        }
+    }
+    return WCQP_OK;
+}
+
+// what both forms of wcqp_tick_set_desired_* ask before they touch anything
+static int desired_ready(const wcqp_tick_s* h, const wcqp_tick_desired* des) {
+    if (!h || !des) return WCQP_E_INVALID;
+    if (!h->streamed) return WCQP_E_UNSUPPORTED;
+    if (!h->uploaded || !des->left_pose || !des->right_pose || !des->left_twist || !des->right_twist || !des->contact) return WCQP_E_INVALID;
+    return WCQP_OK;
+}
+
+int wcqp_tick_set_desired_device(wcqp_tick_t h, const wcqp_tick_desired* des, void* stream) {
+    if (const int rc = desired_ready(h, des); rc != WCQP_OK) return rc;
+    const TickDev& d = h->d;
+    DesiredDev a{};
+    a.left_pose = des->left_pose; a.right_pose = des->right_pose; a.left_twist = des->left_twist; a.right_twist = des->right_twist;
+    a.com_height = des->com_height; a.com_height_vel = des->com_height_vel; a.contact = des->contact; a.h0 = d.com_h0;
+    a.rec = h->st_rec; a.set_A = h->st_set_A; a.set_b = h->st_set_b; a.set_nc = h->st_set_nc; a.pair = h->st_pair;
+    a.ik_fail = d.ik_fail; a.feedback_fail = h->feedback_fail;
+    a.batch = d.batch; a.first = h->desired_set ? 0 : 1; a.build = d.reactive ? 0 : 1;
+    hipLaunchKernelGGL(tick_desired_kernel, dim3((unsigned)((d.batch + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a, plan_rect(h));
+    WCQP_HIP_TRY(hipGetLastError());
+    h->desired_set = true;
+    return WCQP_OK;
+}
+
+int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* des) {
+    if (const int rc = desired_ready(h, des); rc != WCQP_OK) return rc;
+    const size_t B = (size_t)h->d.batch;
+    // the stage rule of the planned upload: an invalid stage leaves the handle as it was
+    for (size_t i = 0; i < B; ++i)
+        if (!stage_valid(des->contact[i], des->left_pose + i * 12, des->right_pose + i * 12, des->left_twist + i * 6, des->right_twist + i * 6,
+                         des->com_height ? des->com_height + i : nullptr, des->com_height_vel ? des->com_height_vel + i : nullptr))
+            return WCQP_E_INVALID;
+    // the last run may have been enqueued on a non-blocking stream, which the NULL stream below does not wait for: wait for its end
+    if (const int rc = h->run.wait(); rc != WCQP_OK) return rc;
+    double* st = h->des_stage;
+    wcqp_tick_desired dv{};
+    dv.left_pose = st; dv.right_pose = st + 12 * B; dv.left_twist = st + 24 * B; dv.right_twist = st + 30 * B;
+    dv.com_height = des->com_height ? st + 36 * B : nullptr; dv.com_height_vel = des->com_height_vel ? st + 37 * B : nullptr;
+    dv.contact = reinterpret_cast<const uint8_t*>(st + 38 * B);
+    WCQP_HIP_TRY(hipMemcpy(st, des->left_pose, B * 96, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 12 * B, des->right_pose, B * 96, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 24 * B, des->left_twist, B * 48, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 30 * B, des->right_twist, B * 48, hipMemcpyHostToDevice));
+    if (des->com_height) WCQP_HIP_TRY(hipMemcpy(st + 36 * B, des->com_height, B * 8, hipMemcpyHostToDevice));
+    if (des->com_height_vel) WCQP_HIP_TRY(hipMemcpy(st + 37 * B, des->com_height_vel, B * 8, hipMemcpyHostToDevice));
+    WCQP_HIP_TRY(hipMemcpy(st + 38 * B, des->contact, B, hipMemcpyHostToDevice));
+    const int rc = wcqp_tick_set_desired_device(h, &dv, nullptr);
+    if (rc != WCQP_OK) return rc;
+    // in place when this call returns: the tick may be enqueued on any stream, and the staging rows are free for the next call
+    WCQP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return WCQP_OK;
+}
+
+}  // extern "C"
