@@ -1,6 +1,18 @@
 // DIAGNOSTIC ONLY - the round-1 IK kernel (sweep on M = H + rho A'A, 32 lanes per instance), kept as an A/B baseline.
 // Included by walking-controllers_amd/csrc/ik.hip when the library is built with -DWCQP_DIAG_KERNELS (tools/build_variant.sh);
-// the product library does not carry it (wcqp_ik_create refuses WCQP_IK_ALG_SWEEP there).  Algorithm: see the header of ik.hip.
+// the product library does not carry it (wcqp_ik_create refuses WCQP_IK_ALG_SWEEP there).
+//
+// One HIP kernel, 32 lanes per robot instance (two instances per wave64).  QP, nu = [v_base(6); dq(dof)], n = 29:
+// min 1/2 nu'H nu + g'nu  s.t.  A nu = b,  v_min <= dq <= v_max (qpOASES form only); H = Lambda + Jn'Wn Jn (+ Jc'Wc Jc) is only PSD
+// (rank 26/29), so it works on M = H + rho A'A (PD whenever the KKT matrix is regular; identical optimum and multipliers because
+// A nu = b holds at every iterate).  Lane i owns variable i: row i of the symmetric matrices in its REGISTERS (static indices), one
+// published column per elimination step through LDS, read back as a broadcast.
+//   1. M rows        M[i][:] = Lambda_i e_i + sum_r Cl[r][i] * Cr[r][:]     (18 stacked task rows)
+//   2. Minv          symmetric sweep operator over the 29 pivots
+//   3. G+ = Minv [A' g~],  S+ = [A; g~'] G+,  Sinv by a second sweep (15 pivots)
+//   4. equality optimum  lambda = -Sinv (A Minv g~ + b),  nu = -Minv g~ - G lambda
+//   5. bounds        Goldfarb-Idnani dual active set expressed through columns of the
+//                    projected inverse  P = Minv - G Sinv G'  (no refactorisation per change)
 #pragma once
 namespace {
 

@@ -1,34 +1,22 @@
-// Jacobian QP-IK: one HIP kernel, 32 lanes per robot instance (two instances per wave64).
+// Jacobian QP-IK, the host side: the IK handle (wcqp_ik_create / _set_posture / _destroy), the route - which kernel a handle runs,
+// resolved once in wcqp_ik_create (wcqp::IkRoute: BASE_ELIM ik4.hip, the default; NULLSPACE_16L ik3.hip, also the list pass over the
+// instances ik4 flags as not MIXED; NULLSPACE_32 / NULLSPACE_32_MFMA ik2.hip; SWEEP diagnostic builds only) -, the solve entry points
+// (wcqp_ik_solve_device / _host), the pair call (both QPs of a batch in one launch: qp_pair_kernel, ik4.hip) and the plan calls
+// (wcqp_qp_plan_*: one launch walks through a plan of steps: qp_plan_kernel / ik_plan_kernel, ik4.hip).  No product kernel is in this file.
 //
 // Reference path replaced (citations relative to /root/reference/modules/Walking_module):
 //   constants  WalkingQPIK::initializeMatrices          src/WalkingQPInverseKinematics.cpp:25-116
 //   per tick   WalkingQPIK_osqp::{setHessianMatrix,setGradientVector,setLinearConstraintMatrix,
 //              setBounds,solve,getSolution,get*FootError} src/WalkingQPInverseKinematics_osqp.cpp:135-454
 //              WalkingQPIK_qpOASES::{same}               src/WalkingQPInverseKinematics_qpOASES.cpp:135-401
-//
-// QP, nu = [v_base(6); dq(dof)], n = dof + 6 = 29:
-//      min 1/2 nu'H nu + g'nu   s.t.  A nu = b,   v_min <= dq <= v_max (qpOASES form only)
-//      H = Lambda + Jn'Wn Jn (+ Jc'Wc Jc)  is only PSD (rank 26/29), so the kernel works on
-//      M = H + rho A'A  (PD whenever the KKT matrix is regular; identical optimum and
-//      identical multipliers because A nu = b holds at every iterate).
-//
-// Layout: lane i of a 32-lane group owns variable i: row i of the symmetric matrices lives
-// in its REGISTERS (static indices, fully unrolled), and the only cross-lane traffic is one
-// published column per elimination step, written to LDS once and read back as a broadcast.
-//   1. M rows        M[i][:] = Lambda_i e_i + sum_r Cl[r][i] * Cr[r][:]     (18 stacked task rows)
-//   2. Minv          symmetric sweep operator over the 29 pivots
-//   3. G+ = Minv [A' g~],  S+ = [A; g~'] G+,  Sinv by a second sweep (15 pivots)
-//   4. equality optimum  lambda = -Sinv (A Minv g~ + b),  nu = -Minv g~ - G lambda
-//   5. bounds        Goldfarb-Idnani dual active set expressed through columns of the
-//                    projected inverse  P = Minv - G Sinv G'  (no refactorisation per change)
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <new>
 #include "ik_common.h"
 
-// The sweep kernel below is the round-1 A/B baseline: compiled only into diagnostic builds (-DWCQP_DIAG_KERNELS,
-// tools/build_variant.sh); the product library carries ik4 (default), ik3 (general fall-back) and ik2 (CoM as cost).
+// The round-1 sweep kernel (A/B baseline) is compiled only into diagnostic builds (-DWCQP_DIAG_KERNELS, tools/build_variant.sh);
+// the product library carries ik4 (default), ik3 (general fall-back) and ik2 (CoM as cost).
 using namespace wcqp_ik;
 #ifdef WCQP_DIAG_KERNELS
 #include "../../tools/diag/ik_sweep_kernel.h"      // ik_kernel<COM_AS_CONSTRAINT>: 380 lines that only diagnostic builds compile

@@ -1,8 +1,8 @@
-// Jacobian QP-IK, fourth kernel (ik4_device.h: the algorithm): the base-eliminated kernel's code object - the stand-alone solve, the
-// plans of steps, the plain skewed tick and its MPC prime.  This code object holds the headline's kernel, qp_plan_kernel, and what is put
-// beside it moves it: no new kernel goes in here - the skewed tick with any of the chain's features runs the variant
-// kernels of ik4_tick.hip, a code object of their own - and a change of the plan kernels themselves (the last: their launch-invariant
-// tables in LDS) is measured against the parent commit in the bench's forms; the other kernels keep their instructions.
+// Jacobian QP-IK, fourth kernel (ik4_device.h: the algorithm and the device code; ik4_layout.h: sizes, LDS map, knobs, stamps): the
+// base-eliminated kernel's code object - the stand-alone solve, the plans of steps, the plain skewed tick and its MPC prime.  It holds the
+// headline's kernel, qp_plan_kernel, and what is put beside it moves it: no new kernel goes in here - the skewed tick with any
+// of the chain's features runs the variant kernels of ik4_tick.hip, a code object of their own - and a change of the plan kernels themselves (the
+// last: their launch-invariant tables in LDS) is measured against the parent commit in the bench's forms; the other kernels keep their instructions.
 #include "ik4_device.h"
 
 namespace {

@@ -1,7 +1,8 @@
 // The skewed tick with any of the chain's features - the reactive DCM controller (wcqp_tick_params.dcm_controller), ZMP-CoM gain
 // scheduling (zmp_gain_scheduling), planned trajectories (planned_trajectories) - as ONE family of kernels in a code object of its own:
 // ik4.hip's code object carries the headline's kernels and stays as it is.  A new feature of the tick is one more flag of
-// these kernels and of TickVariant (ik_common.h).
+// these kernels and of TickVariant (ik_common.h).  The device code is ik4_device.h's (ik4_body, ik4_tick_walk, tick_variant_visit), its
+// sizes, LDS map, build knobs and stamps ik4_layout.h's.
 #include "ik4_device.h"
 
 namespace {
