@@ -58,6 +58,8 @@
  *                                      2 x batch rows of 112 B; the IK's arrays as above (1392 B).  From the parameters alone, before the
  *                                      device is looked for.  The planned-trajectory records use 64-bit offsets and set no limit.
  *     wcqp_kin_jacobians_*, wcqp_hull_from_feet_*   64-bit addresses throughout: no limit beyond int32 batch.
+ *     wcqp_unicycle_plan_device / _host   target: max_steps x 24 B; the soles: 96 B.  (The kernel forms 64-bit addresses; the limit is
+ *                                      kept for the reason given for the MPC.)
  */
 #ifndef WCQP_H
 #define WCQP_H
@@ -1007,6 +1009,101 @@ typedef struct wcqp_tick_info {
     int32_t ik_mode;               /* wcqp_tick_params.ik_mode as taken (WCQP_TICK_IK_*)                                            */
 } wcqp_tick_info;
 int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
+
+/* =====================================================================================
+ * Footsteps from per-robot goals: the unicycle planner.  "Robot i, go there" - the reference's setGoal(x, y):
+ * WalkingModule::setPlannerInput (WM/src/WalkingModule.cpp:1263-1308) stores the goal, TrajectoryGenerator::updateTrajectories
+ * (WM/src/TrajectoryGenerator.cpp:442-484) turns it into the unicycle's desired point, and the unicycle planner, configured at
+ * TrajectoryGenerator.cpp:114-132 from plannerParams.ini, turns that into footsteps.  The planner library is upstream of the reference:
+ * like the plan of wcqp_tick_upload_footsteps, THE PLANNER IS THIS BUILD'S OWN DEFINITION, stated here (tests/helpers/unicycle_plan.py
+ * restates it in numpy).  Its outputs have exactly the shapes wcqp_tick_footsteps / wcqp_tick_replan take.
+ *
+ * Inputs per robot: left0, right0 [12] the soles' poses in the layout of the desired-foot entries of state0 (position 3 | rotation 9
+ * row-major; only x, y and yaw = atan2(R10, R00) are read), goal [2] the argument of setGoal, in the unicycle's frame, and first_side,
+ * the foot that swings first (0 left, 1 right).  R(a) is the plane rotation by a, w = nominal_width, d = reference_position,
+ * wrap(a) = a - 2 pi rint(a / (2 pi)).
+ *   Start     (TrajectoryGenerator.cpp:445-466) the stance foot is the foot that does not swing first, at (p_s, th_s).  The unicycle
+ *             starts at p_s + R(th_s) (0, -w/2) for a left stance foot, (0, +w/2) for a right one, with heading th_s.  The desired point
+ *             y* = p_u + R(th) (d + goal) is fixed for the whole call, without a feed-forward velocity (the reference adds a single
+ *             trajectory point, :231-234).
+ *   Unicycle  reference point y = p + R(th) d; control (v, om) = -k B(th)^-1 (y - y*), B = [[cos th, -d_x sin th - d_y cos th],
+ *             [sin th, d_x cos th - d_y sin th]] (det B = d_x); then v and om are clamped to +-max_linear_velocity and
+ *             +-max_angular_velocity, then v <- v / (1 + g |om|).  Dynamics (x', y', th') = (v cos th, v sin th, om), integrated with
+ *             the classical RK4 at step dT, the control evaluated anew at every stage.  Sample n is the state after n steps; th is
+ *             never wrapped along the path.  (The heading loop's gain is k L / |d_x| with the desired point L away, and the explicit
+ *             RK4 integrates it stably only while k L dT / |d_x| < 2.785 - L < 2.78 m at the reference's values and dT = 0.01.  A
+ *             farther goal still yields feasible footsteps, but om chatters between its saturations on the way and the plan then
+ *             depends on the last bit of its inputs: send such a robot there through nearer goals.)
+ *   Steps     sides alternate from first_side.  Step k knows the swing foot's current footprint, the stance foot (p_st, th_st) and the
+ *             path index n_k, n_0 = 0.  Candidate m of 1..D is the unicycle at sample n_k + m: position c = p_u + R(th_u) (0, +-w/2)
+ *             (left +), yaw th_u.  With r = R(th_st)^T (c - p_st) it is feasible iff |r| <= max_step_length, the lateral component
+ *             of r towards the swing side (r_y for a left swing foot, -r_y for a right one) is >= min_width, and
+ *             |wrap(th_u - th_st)| <= max_angle_variation.  m* is the LARGEST feasible m; without one the robot's planning ends
+ *             WCQP_UNICYCLE_STUCK and keeps the steps so far.  If candidate m* lies less than min_step_length from the swing foot's
+ *             current footprint AND |wrap(th_u - th_swing)| < min_angle_variation the robot has arrived: no step, WCQP_UNICYCLE_DONE.
+ *             Otherwise step k is taken: side[k] = the swing foot, target[k] = (c_x, c_y, wrap(th_u - th_swing)) - the yaw INCREMENT
+ *             of wcqp_tick_footsteps.target -, the foot's footprint becomes (c, th_u), n_{k+1} = n_k + m*, and the feet swap roles.
+ *             K steps taken without arriving: WCQP_UNICYCLE_TRUNCATED.
+ *   Outputs   n_steps [B], side [B][K], target [B][K][3], status [B], desired_point [B][2] (y*), unicycle_end [B][3] (x, y, th at
+ *             sample n of the last step taken: the start pose without a step).  Entries of steps not taken are zero.
+ *   Non-finite inputs ("never report SOLVED for NaN / Inf inputs"): the device form gives a robot with a NaN or an Inf in an entry it
+ *             reads, a desired point that overflows or a first_side above 1 WCQP_UNICYCLE_INVALID_INPUT with n_steps = 0 and every output row zero; the other robots
+ *             do not notice.  The host form refuses the whole call with WCQP_E_INVALID before anything is copied.
+ * DEVIATIONS.  Step timings are common to a batch, as wcqp_tick_footsteps demands: minStepDuration, maxStepDuration, timeWeight and
+ * positionWeight are not read, and a step advances the PATH by at most D samples instead of choosing its duration.  plannerHorizon is
+ * not read: the tick handle's T cuts the plan.  addTerminalStep, startAlwaysSameFoot and pitchDelta are not offered: the feet of a DONE
+ * robot are aligned to within the two arrival thresholds, not exactly.  The two saturations are this build's own addition.
+ * ===================================================================================== */
+#define WCQP_UNICYCLE_DONE          0   /* arrived: the next candidate is no step                      */
+#define WCQP_UNICYCLE_TRUNCATED     1   /* max_steps steps taken without arriving                      */
+#define WCQP_UNICYCLE_STUCK         2   /* no feasible candidate within step_ticks samples             */
+#define WCQP_UNICYCLE_INVALID_INPUT 3   /* device form: a non-finite input, or first_side above 1      */
+typedef struct wcqp_unicycle_params {   /* every value is taken as given (capi.UnicyclePlanner holds the defaults) */
+    double  dT;                          /* sampling time of the unicycle's path [s]; > 0                                            */
+    double  reference_position[2];       /* d: referencePosition (plannerParams.ini), reference (0.1 0.0); d_x != 0 (det B = d_x)     */
+    double  unicycle_gain;               /* k: unicycleGain, reference 10; > 0                                                       */
+    double  slow_when_turning_gain;      /* g: slowWhenTurningGain, reference 5; >= 0                                                */
+    double  max_linear_velocity;         /* saturation of v [m/s], this build's own; > 0                                             */
+    double  max_angular_velocity;        /* saturation of om [rad/s], this build's own; > 0                                          */
+    double  max_step_length;             /* maxStepLength, reference 0.20; > min_step_length                                         */
+    double  min_step_length;             /* minStepLength, reference 0.05; > 0                                                       */
+    double  min_width;                   /* minWidth, reference 0.14; > 0, <= nominal_width                                          */
+    double  nominal_width;               /* w: nominalWidth, reference 0.16; > 0                                                     */
+    double  max_angle_variation;         /* maxAngleVariation, RADIANS here (reference 10 degrees); > 0                              */
+    double  min_angle_variation;         /* minAngleVariation, RADIANS here (reference 8 degrees); > 0                               */
+    int32_t step_ticks;                  /* D: unicycle samples per step, >= 1; callers pass ss_ticks + ds_ticks                      */
+    int32_t max_steps;                   /* K: row length of side / target, >= 0                                                     */
+} wcqp_unicycle_params;
+
+typedef struct wcqp_unicycle_inputs {    /* all required */
+    const double*  left0;                /* [B][12] */
+    const double*  right0;               /* [B][12] */
+    const double*  goal;                 /* [B][2]  */
+    const uint8_t* first_side;           /* [B]     */
+} wcqp_unicycle_inputs;
+
+typedef struct wcqp_unicycle_outputs {   /* n_steps, status and - for K > 0 - side and target are required */
+    int32_t* n_steps;                    /* [B]       */
+    uint8_t* side;                       /* [B][K]    */
+    double*  target;                     /* [B][K][3] */
+    int32_t* status;                     /* [B] WCQP_UNICYCLE_* */
+    double*  desired_point;              /* [B][2] or NULL */
+    double*  unicycle_end;               /* [B][3] or NULL */
+} wcqp_unicycle_outputs;
+
+typedef struct wcqp_unicycle_s* wcqp_unicycle_t;
+
+/* Refusals need no device: WCQP_E_INVALID for a NULL pointer, a non-finite scalar or one outside the ranges above (d_x = 0,
+ * min_width > nominal_width and min_step_length >= max_step_length among them), step_ticks < 1 or max_steps < 0. */
+int wcqp_unicycle_create(const wcqp_unicycle_params* params, wcqp_unicycle_t* out);
+int wcqp_unicycle_destroy(wcqp_unicycle_t h);
+/* DEVICE pointers; one launch on `stream`, enqueue only (no allocation, no synchronisation), nothing retained.  WCQP_E_INVALID for a
+ * NULL handle, struct or required pointer or batch < 0; WCQP_E_UNSUPPORTED for a batch whose widest array (target, batch x 24 K bytes,
+ * or the soles, batch x 96) passes 2^32 bytes; WCQP_E_HIP without a device. */
+int wcqp_unicycle_plan_device(wcqp_unicycle_t h, int32_t batch, const wcqp_unicycle_inputs* in, const wcqp_unicycle_outputs* out, void* stream);
+/* the same with HOST pointers: validated on the host first (a non-finite entry that is read, or a first_side above 1, of any robot:
+ * WCQP_E_INVALID, nothing copied or written), staged through the handle's own device buffer, and in place on return (it synchronises). */
+int wcqp_unicycle_plan_host(wcqp_unicycle_t h, int32_t batch, const wcqp_unicycle_inputs* in, const wcqp_unicycle_outputs* out);
 
 #ifdef __cplusplus
 }

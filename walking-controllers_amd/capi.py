@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_upload_footsteps", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
+    "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
 )
 
 
@@ -225,6 +226,27 @@ class TickReplan(C.Structure):
                 ("first_ds_ticks", C.c_int32)]
 
 
+UNICYCLE_DONE, UNICYCLE_TRUNCATED, UNICYCLE_STUCK, UNICYCLE_INVALID_INPUT = range(4)
+
+
+class UnicycleParams(C.Structure):
+    """wcqp_unicycle_params: the unicycle planner's parameters (plannerParams.ini keys in include/wcqp.h; angles in radians)."""
+    _fields_ = [("dT", C.c_double), ("reference_position", C.c_double * 2), ("unicycle_gain", C.c_double), ("slow_when_turning_gain", C.c_double),
+                ("max_linear_velocity", C.c_double), ("max_angular_velocity", C.c_double), ("max_step_length", C.c_double),
+                ("min_step_length", C.c_double), ("min_width", C.c_double), ("nominal_width", C.c_double),
+                ("max_angle_variation", C.c_double), ("min_angle_variation", C.c_double), ("step_ticks", C.c_int32), ("max_steps", C.c_int32)]
+
+
+class UnicycleInputs(C.Structure):
+    """wcqp_unicycle_inputs: left0 / right0 [B][12], goal [B][2], first_side [B] (uint8)."""
+    _fields_ = [(k, C.c_void_p) for k in ("left0", "right0", "goal", "first_side")]
+
+
+class UnicycleOutputs(C.Structure):
+    """wcqp_unicycle_outputs: n_steps [B], side [B][K], target [B][K][3], status [B], desired_point [B][2], unicycle_end [B][3]."""
+    _fields_ = [(k, C.c_void_p) for k in ("n_steps", "side", "target", "status", "desired_point", "unicycle_end")]
+
+
 PLAN_WINDOW = (("left_traj", (12,), np.float64), ("right_traj", (12,), np.float64), ("left_twist", (6,), np.float64), ("right_twist", (6,), np.float64),
                ("contact", (), np.uint8), ("com_height", (), np.float64), ("com_height_vel", (), np.float64),
                ("ref_traj", (2,), np.float64), ("dcm_vel_traj", (2,), np.float64),
@@ -296,6 +318,10 @@ def lib() -> C.CDLL:
         L.wcqp_tick_upload_footsteps.argtypes = [C.c_void_p, C.POINTER(TickInputs), C.POINTER(TickFootsteps)]
         L.wcqp_tick_get_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TickPlanWindow)]
         L.wcqp_tick_replan_footsteps.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.c_void_p]
+        L.wcqp_unicycle_create.argtypes = [C.POINTER(UnicycleParams), C.POINTER(C.c_void_p)]
+        L.wcqp_unicycle_destroy.argtypes = [C.c_void_p]
+        L.wcqp_unicycle_plan_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(UnicycleInputs), C.POINTER(UnicycleOutputs), C.c_void_p]
+        L.wcqp_unicycle_plan_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(UnicycleInputs), C.POINTER(UnicycleOutputs)]
         L.wcqp_qp_enqueue_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.POINTER(C.c_int32)]
         L.wcqp_qp_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.c_int32, C.POINTER(C.c_void_p)]
         L.wcqp_qp_plan_enqueue.argtypes = [C.c_void_p, C.c_void_p]
@@ -555,6 +581,82 @@ class PrepareSolver:
                                               state or None, status, iters or None, residual or None, stream or None), "wcqp_prepare_solve_device")
 
 
+class UnicyclePlanner:
+    """Handle over wcqp_unicycle_* - footsteps from per-robot goals, the reference's setGoal (include/wcqp.h states the planner).  Defaults
+    follow plannerParams.ini where it has the key (angles in radians here); the two saturations are this build's own.  step_ticks: unicycle
+    samples per step, ss_ticks + ds_ticks of the walk the footsteps are for; max_steps: K, the row length of side / target."""
+    DEFAULTS = dict(dT=0.01, reference_position=(0.1, 0.0), unicycle_gain=10.0, slow_when_turning_gain=5.0, max_linear_velocity=0.1,
+                    max_angular_velocity=0.5, max_step_length=0.20, min_step_length=0.05, min_width=0.14, nominal_width=0.16,
+                    max_angle_variation=np.deg2rad(10.0), min_angle_variation=np.deg2rad(8.0), step_ticks=90, max_steps=8)
+
+    def __init__(self, **params):
+        unknown = set(params) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown unicycle parameter(s): " + ", ".join(sorted(unknown)))
+        p = dict(self.DEFAULTS, **params)
+        self.values = p
+        self.max_steps, self.step_ticks = int(p["max_steps"]), int(p["step_ticks"])
+        scalars = [float(p[k]) for k, _ in UnicycleParams._fields_[2:12]]
+        self.params = UnicycleParams(float(p["dT"]), (C.c_double * 2)(*map(float, p["reference_position"])), *scalars, self.step_ticks, self.max_steps)
+        self._h = C.c_void_p()
+        check(lib().wcqp_unicycle_create(C.byref(self.params), C.byref(self._h)), "wcqp_unicycle_create")
+
+    @classmethod
+    def from_ini_values(cls, values: dict, **params):
+        """From the VALUES of a plannerParams.ini (a dict keyed as the file: unicycleGain, referencePosition, slowWhenTurningGain,
+        maxStepLength, minStepLength, minWidth, nominalWidth, maxAngleVariation / minAngleVariation in DEGREES); `params` adds or
+        overrides (dT, the saturations, step_ticks, max_steps)."""
+        key = dict(unicycleGain="unicycle_gain", referencePosition="reference_position", slowWhenTurningGain="slow_when_turning_gain",
+                   maxStepLength="max_step_length", minStepLength="min_step_length", minWidth="min_width", nominalWidth="nominal_width")
+        p = {v: values[k] for k, v in key.items() if k in values}
+        for k, v in (("maxAngleVariation", "max_angle_variation"), ("minAngleVariation", "min_angle_variation")):
+            if k in values:
+                p[v] = float(np.deg2rad(values[k]))
+        p.update(params)
+        return cls(**p)
+
+    def close(self):
+        if self._h:
+            lib().wcqp_unicycle_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def plan_host(self, left0, right0, goals, first_side) -> dict:
+        """left0 / right0 [B][12] sole poses (p 3 | R 9 row-major: the desired-foot entries of state0), goals [B][2] in the unicycle's frame,
+        first_side [B] or a scalar (0: the left foot swings first, 1: the right).  -> n_steps [B], side [B][K], target [B][K][3] - what
+        upload_footsteps / replan_footsteps take -, status [B] (UNICYCLE_*), desired_point [B][2], unicycle_end [B][3]."""
+        left0, right0, goals = _f64(left0), _f64(right0), _f64(goals)
+        B = goals.shape[0] if goals.ndim else -1
+        fs = np.asarray(first_side)
+        if fs.ndim == 0:
+            fs = np.full(max(B, 0), fs)
+        if fs.size and (fs.min() < 0 or fs.max() > 1):
+            raise ValueError("first_side is 0 (left) or 1 (right)")
+        fs = np.ascontiguousarray(fs, dtype=np.uint8)
+        if not (goals.shape == (B, 2) and left0.shape == (B, 12) and right0.shape == (B, 12) and fs.shape == (B,)):
+            raise ValueError("shapes: left0 %s right0 %s goals %s first_side %s" % (left0.shape, right0.shape, goals.shape, fs.shape))
+        K = self.max_steps
+        o = dict(n_steps=np.zeros(B, np.int32), side=np.zeros((B, K), np.uint8), target=np.zeros((B, K, 3)), status=np.full(B, -1, np.int32),
+                 desired_point=np.zeros((B, 2)), unicycle_end=np.zeros((B, 3)))
+        if B == 0:
+            return o
+        ins = UnicycleInputs(_p(left0), _p(right0), _p(goals), _p(fs))
+        outs = UnicycleOutputs(**{k: (v.ctypes.data if v.size else None) for k, v in o.items()})
+        check(lib().wcqp_unicycle_plan_host(self._h, B, C.byref(ins), C.byref(outs)), "wcqp_unicycle_plan_host")
+        return o
+
+    def plan_device(self, batch, left0, right0, goals, first_side, n_steps, side, target, status, desired_point=0, unicycle_end=0, stream=0):
+        """All array arguments are raw device addresses (ints); enqueue only."""
+        ins = UnicycleInputs(left0, right0, goals, first_side)
+        outs = UnicycleOutputs(n_steps, side or None, target or None, status, desired_point or None, unicycle_end or None)
+        check(lib().wcqp_unicycle_plan_device(self._h, int(batch), C.byref(ins), C.byref(outs), stream or None), "wcqp_unicycle_plan_device")
+
+
 class TickPipeline:
     """Handle over wcqp_tick_* — the device-resident MPC -> glue -> IK tick (configs 4/5)."""
 
@@ -750,17 +852,63 @@ class TickPipeline:
                         target.ctypes.data if target.size else None, int(first_ds_ticks))
         check(lib().wcqp_tick_replan_footsteps(self._h, C.byref(rp), stream or None), "wcqp_tick_replan_footsteps")
 
-    def plan_window(self, robot0: int = 0, n: Optional[int] = None, stage0: int = 0, m: Optional[int] = None) -> dict:
+    def upload_goal(self, data: dict, goals, planner: "UnicyclePlanner", first_side, first_ds_ticks: int, ss_ticks: int, ds_ticks: int,
+                    final_ds_ticks: int = 0, lift: float = 0.02, zmp_delta_left=(0.03, -0.005), zmp_delta_right=(0.03, 0.005)) -> dict:
+        """"Robot i, go there" from standing: plans footsteps on the device from the desired soles of data["state0"] (entries 24..47) towards
+        goals [B][2] (UnicyclePlanner.plan_host), then upload_footsteps with them.  planner.step_ticks is the path samples per step: callers
+        create it with ss_ticks + ds_ticks.  Returns the planner's output dict (status says how each robot's planning ended)."""
+        if not self.planned:
+            raise ValueError("a goal was given to a handle created without planned_trajectories=True")
+        st = _f64(data["state0"])
+        plan = planner.plan_host(st[:, 24:36], st[:, 36:48], goals, first_side)
+        self.upload_footsteps(data, dict(n_steps=plan["n_steps"], side=plan["side"], target=plan["target"], first_ds_ticks=first_ds_ticks,
+                                         ss_ticks=ss_ticks, ds_ticks=ds_ticks, final_ds_ticks=final_ds_ticks, lift=lift,
+                                         zmp_delta_left=zmp_delta_left, zmp_delta_right=zmp_delta_right))
+        return plan
+
+    def replan_goal(self, merge_stage, goals, planner: "UnicyclePlanner", first_side, first_ds_ticks: int, stream: Optional[int] = None) -> dict:
+        """A new goal for a generated walk that is running: for every robot with merge_stage[i] >= 1 plans footsteps from the two desired
+        soles of its plan's record merge_stage[i] towards goals[i], then replan_footsteps.  The soles are read through plan_window, one
+        one-stage window per distinct merge stage - it synchronises.  Rows of robots with merge_stage -1 are not read.  Returns the planner's
+        output dict over the whole batch: rows of robots that keep their plan are zero, with status -1."""
+        if not self.planned:
+            raise ValueError("a goal was given to a handle created without planned_trajectories=True")
+        merge = np.ascontiguousarray(merge_stage, dtype=np.int32)
+        goals = _f64(goals)
+        fs = np.asarray(first_side)
+        fs = np.full(self.batch, fs) if fs.ndim == 0 else fs
+        if not (merge.shape == (self.batch,) and goals.shape == (self.batch, 2) and fs.shape == (self.batch,)):
+            raise ValueError("shapes: merge_stage %s goals %s first_side %s" % (merge.shape, goals.shape, fs.shape))
+        K = planner.max_steps
+        out = dict(n_steps=np.zeros(self.batch, np.int32), side=np.zeros((self.batch, K), np.uint8), target=np.zeros((self.batch, K, 3)),
+                   status=np.full(self.batch, -1, np.int32), desired_point=np.zeros((self.batch, 2)), unicycle_end=np.zeros((self.batch, 3)))
+        sel = np.nonzero(merge >= 1)[0]
+        if sel.size:
+            left0, right0 = np.zeros((sel.size, 12)), np.zeros((sel.size, 12))
+            lo, n = int(sel.min()), int(sel.max() - sel.min() + 1)
+            for M in np.unique(merge[sel]):
+                w = self.plan_window(lo, n, int(M), 1, keys=("left_traj", "right_traj"))
+                rows = merge[sel] == M
+                left0[rows] = w["left_traj"][sel[rows] - lo, 0]; right0[rows] = w["right_traj"][sel[rows] - lo, 0]
+            plan = planner.plan_host(left0, right0, goals[sel], fs[sel])
+            for k in out:
+                out[k][sel] = plan[k]
+        self.replan_footsteps(merge, out, first_ds_ticks, stream=stream)
+        return out
+
+    def plan_window(self, robot0: int = 0, n: Optional[int] = None, stage0: int = 0, m: Optional[int] = None, keys=None) -> dict:
         """The plan a planned handle holds (wcqp_tick_get_plan): n robots from robot0, m stages from stage0 (None: to the end) - left_traj,
         right_traj, left_twist, right_twist, contact, com_height, com_height_vel, ref_traj, the support-polygon rows in force per stage
         (hull_A, hull_b, hull_nc), dcm_vel_traj where the handle keeps it (reactive controller, gain scheduling) and, after
-        upload_footsteps, u_init [n][2], the generated ZMP of stage 0."""
+        upload_footsteps, u_init [n][2], the generated ZMP of stage 0.  keys: only these arrays (None: all the handle offers)."""
         T = self.max_ticks + self.params.mpc.horizon + 1
         n = self.batch - robot0 if n is None else n
         m = T - stage0 if m is None else m
         out = {k: np.zeros((max(n, 0), max(m, 0)) + shp, dt) for k, shp, dt in PLAN_WINDOW if k != "dcm_vel_traj" or self.reactive or self.gain_sched}
         if self.info()["plan_generated"]:
             out["u_init"] = np.zeros((max(n, 0), 2))
+        if keys is not None:
+            out = {k: out[k] for k in keys}
         win = TickPlanWindow(**{k: v.ctypes.data for k, v in out.items()})
         check(lib().wcqp_tick_get_plan(self._h, int(robot0), int(n), int(stage0), int(m), C.byref(win)), "wcqp_tick_get_plan")
         return out

@@ -674,6 +674,48 @@ def synth_footstep_replan_batch(fs: dict, after_step: int = 2, ds_offset: int = 
     return dict(merge_stage=merge, n_steps=np.full(count, n_steps, np.int32), side=side, target=target, first_ds_ticks=ds - ds_offset)
 
 
+# the cases of synth_goal_batch's first robots: name, goal (x, y) in the unicycle's frame, the foot that swings first
+GOAL_CASES = (("origin", (0.0, 0.0), 1), ("straight", (0.2, 0.0), 1), ("straight_left_first", (0.1, 0.0), 0), ("turn_left", (0.15, 0.1), 1),
+              ("turn_right", (0.15, -0.1), 0), ("far", (2.5, 0.0), 1), ("far_turn", (2.0, 1.5), 0), ("behind", (-0.2, 0.0), 1),
+              ("behind_side", (-0.15, 0.1), 0), ("sideways", (0.0, 0.2), 1), ("below_a_step", (0.008, 0.0), 0), ("straight_long", (0.3, 0.0), 1),
+              ("turn_sharp", (0.1, 0.2), 0))
+
+
+def synth_goal_batch(count: int, seed: int = 6021, first: int = 0, state0=None, cases: bool = True, radius: float = 1.0,
+                     nominal_width: float = NOMINAL_WIDTH) -> dict:
+    """Goals for `UnicyclePlanner.plan_host` / `TickPipeline.upload_goal`: left0, right0 [B][12] (the desired soles of `state0` when it is
+    given; otherwise robots standing anywhere, heading anywhere, the feet nominal_width apart on the ground), goals [B][2], first_side [B]
+    and case [B] (names).  With `cases` robot i < 13 of the whole batch takes GOAL_CASES[i] - straight ahead, turns, the origin (no step), far goals
+    (they truncate at max_steps), goals behind and beside the robot; every other robot a goal drawn uniformly from the disc of `radius`
+    and either first side."""
+    rng = CounterRNG(seed ^ 0x60A15, first, count)
+    o = IK_STATE_OFFSETS
+    if state0 is not None:
+        state0 = np.asarray(state0, float)
+        left0 = np.ascontiguousarray(state0[:count, o["pd_left"]:o["pd_left"] + 12])
+        right0 = np.ascontiguousarray(state0[:count, o["pd_right"]:o["pd_right"] + 12])
+        rng.uniform(3)
+    else:
+        u = rng.uniform(3)
+        mid = 4.0 * u[:, :2] - 2.0
+        yaw = np.pi * (2.0 * u[:, 2] - 1.0)
+        lat = np.stack([-np.sin(yaw), np.cos(yaw)], axis=1)
+        R = _rotz(yaw).reshape(count, 9)
+        left0 = np.concatenate([mid + 0.5 * nominal_width * lat, np.zeros((count, 1)), R], axis=1)
+        right0 = np.concatenate([mid - 0.5 * nominal_width * lat, np.zeros((count, 1)), R], axis=1)
+    u = rng.uniform(3)
+    r, phi = radius * np.sqrt(u[:, 0]), 2.0 * np.pi * u[:, 1]
+    goals = np.stack([r * np.cos(phi), r * np.sin(phi)], axis=1)
+    first_side = (u[:, 2] < 0.5).astype(np.uint8)
+    case = ["random"] * count
+    if cases:
+        for i in range(count):
+            if first + i < len(GOAL_CASES):
+                case[i], goals[i], first_side[i] = GOAL_CASES[first + i]
+    return dict(first=first, left0=np.ascontiguousarray(left0), right0=np.ascontiguousarray(right0), goals=np.ascontiguousarray(goals),
+                first_side=first_side, case=case)
+
+
 def neck_target(left_d: np.ndarray, right_d: np.ndarray, additional_rotation=None) -> np.ndarray:
     """Desired neck orientation [B][9] by the mean-yaw rule of WalkingModule::prepareRobot (WM/src/WalkingModule.cpp:957-970; the tick's
     per-tick rule :697-707): RotZ(atan2(sin yL + sin yR, cos yL + cos yR)) * additional_rotation, each sole's yaw atan2(R10, R00) of its
