@@ -421,6 +421,10 @@ typedef struct wcqp_kin_params {
 
 typedef struct wcqp_kin_s* wcqp_kin_t;
 
+/* Needs no device.  Any tree with parent[j] < j is taken (whatever its numbering, depth or the joints its frames sit on).
+ * WCQP_E_UNSUPPORTED for a dof outside 1 .. 26; WCQP_E_INVALID for a NULL pointer, a parent[j] >= j or < -1, a negative or NaN mass or
+ * root_mass, a robot without mass, an axis of length zero or with a NaN, a frame_joint outside 0 .. dof - 1.  *out is written on
+ * success only. */
 int wcqp_kin_create(const wcqp_kin_params* params, wcqp_kin_t* out);
 int wcqp_kin_destroy(wcqp_kin_t h);
 /* base [B][12] = position, row-major rotation of the root link; q [B][dof].  DEVICE pointers. */

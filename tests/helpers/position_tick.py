@@ -13,6 +13,7 @@ import functools
 import numpy as np
 
 import robots
+import trees
 from helpers import footstep_plan as fp
 from helpers import prepare_spec as ps
 from helpers import streamed_tick as stt
@@ -37,13 +38,21 @@ def controller_kwargs(controller):
     return dict(dcm_controller="reactive", k_dcm=K_DCM, zmp_gain_scheduling=True, **zg.ZMP_SCHEDULE[ROBOT])
 
 
-@functools.lru_cache(maxsize=None)
-def scenario():
-    """model, q_reg, the footsteps (with state0, q0, com0: what upload_footsteps takes) and the plan of all 13 robots"""
+def tree_of(tree):
+    """(model, order) of a scenario's tree: "icub", the iCub-shaped one, or a variant of it in tests/trees.py whose joint k is joint order[k]"""
     from walking_controllers_amd import synth
-    model = synth.icub_like_model()
+    return (synth.icub_like_model(), list(range(23))) if tree == "icub" else (trees.named(tree), trees.ORDER[tree])
+
+
+@functools.lru_cache(maxsize=None)
+def scenario(tree="icub"):
+    """model, q_reg, the footsteps (with state0, q0, com0: what upload_footsteps takes) and the plan of all 13 robots; on another tree
+    than the iCub-shaped one everything per joint (guess, posture, v_max) is permuted with the joints"""
+    from walking_controllers_amd import synth
+    model, order = tree_of(tree)
     d = synth.synth_prepare_batch(B13, com_height=(H, H))
-    q_reg = np.deg2rad(synth.WALK_POSTURE_DEG)
+    d = dict(d, q_guess=trees.permute_joints(d["q_guess"], order))
+    q_reg = trees.permute_joints(np.deg2rad(synth.WALK_POSTURE_DEG), order)
     par = ps.Params(q_reg=q_reg)
     q0 = np.zeros((B13, 23)); state0 = np.zeros((B13, 87))
     for i in range(B13):
@@ -60,14 +69,14 @@ def scenario():
     fs = synth.synth_footstep_walk_batch(B13, T, state0, dict(q=q0), step_ticks=STEP_TICKS, ds_ticks=DS_TICKS, n_steps=N_STEPS, com_height=H)
     fs["state0"] = state0                # (the desired soles are the TARGETS, not copies of the actual ones)
     plan = fp.footstep_plan(fs, state0, T + N + 1, T, com_height=H)
-    return dict(model=model, q_reg=q_reg, fs=fs, plan=plan, foot_rect=synth.FOOT_RECT, v_max=synth.WALK_VMAX.copy(),
-                posture_deg=synth.WALK_POSTURE_DEG.copy())
+    return dict(model=model, order=order, q_reg=q_reg, fs=fs, plan=plan, foot_rect=synth.FOOT_RECT, v_max=trees.permute_joints(synth.WALK_VMAX, order),
+                posture_deg=trees.permute_joints(synth.WALK_POSTURE_DEG, order))
 
 
-def chain(controller, robot, plan=None, height=None):
+def chain(controller, robot, plan=None, height=None, tree="icub"):
     """The chain of one robot over T ticks on `plan` (default: the scenario's): run_ticks' u0_log, dcm, com, zmp_gains and p_star [T][2]."""
     from oracle import qp_spec as qs
-    sc = scenario()
+    sc = scenario(tree)
     plan = sc["plan"] if plan is None else plan
     R = robots.ROBOTS[ROBOT]
     i = robot
@@ -78,6 +87,8 @@ def chain(controller, robot, plan=None, height=None):
     e = dict(one, first=i, ref_traj=p1["ref_traj"], dcm_vel_traj=p1["dcm_vel_traj"], dcm0=p1["ref_traj"][:, 0].copy(), u_init=p1["zmp_ref"][:, 0].copy())
     ipar = robots.ik_params(qs, ROBOT, v_max=sc["v_max"])
     ipar.joint_reg_deg = sc["posture_deg"]
+    ipar.joint_reg_weights = trees.permute_joints(ipar.joint_reg_weights, sc["order"])
+    ipar.joint_reg_gains = trees.permute_joints(ipar.joint_reg_gains, sc["order"])
     tp = ts.TickParams(horizon=N, com_height=H, k_com=R["k_com"], k_zmp=R["k_zmp"])
     kw = {} if controller == "mpc" else dict(dcm_controller="reactive", k_dcm=K_DCM, zmp_gain_schedule=zg.ZMP_SCHEDULE[ROBOT])
     run = ts.run_ticks(tp, e, T, ipar, kin_model=sc["model"], foot_rect=sc["foot_rect"], stages=stt.stages_of(p1, T), neck_additional_rotation=ADD_ROT,
@@ -107,7 +118,7 @@ def targets(p1, p_star, t, height=None):
                 Rd_neck=ts.neck_orientation(left[3:12], right[3:12], ADD_ROT).reshape(9))
 
 
-def walk(ch, q0, par, n_ticks=T):
+def walk(ch, q0, par, n_ticks=T, tree="icub"):
     """The IK of the POSITION tick over the chain `ch` of one robot: prepare_spec.solve from the previous tick's joints (tick 0: q0), clipped
     into the limits; a tick that does not end SOLVED keeps the joints, stops the robot and counts, as every later tick does.
     -> q_log [T][23], iters [T], status [T], active (the joints on a limit in the last QP of each tick: {joint: side} or None), ik_fail."""
@@ -118,7 +129,7 @@ def walk(ch, q0, par, n_ticks=T):
     fail = 0
     for t in range(n_ticks):
         if fail == 0:
-            s = ps.solve(sc_model(), targets(ch["plan"], ch["p_star"], t), q, par)
+            s = ps.solve(sc_model(tree), targets(ch["plan"], ch["p_star"], t), q, par)
             iters[t] = s["iters"]; status[t] = s["status"]
             if s["status"] == ps.SOLVED:
                 q = s["q"]; active[t] = s["active"]
@@ -130,23 +141,23 @@ def walk(ch, q0, par, n_ticks=T):
     return dict(q_log=q_log, iters=iters, status=status, active=active, ik_fail=fail)
 
 
-def sc_model():
-    return scenario()["model"]
+def sc_model(tree="icub"):
+    return scenario(tree)["model"]
 
 
-def params(**kw):
+def params(tree="icub", **kw):
     """the IK's parameters of the scenario: the walk posture as regularisation, 30 iterations per tick, default tolerances"""
-    return ps.Params(q_reg=scenario()["q_reg"], max_iter=30, **kw)
+    return ps.Params(q_reg=scenario(tree)["q_reg"], max_iter=30, **kw)
 
 
 @functools.lru_cache(maxsize=None)
-def reference(controller):
-    """the restatement's walk of the robots SEL, without limits: {robot: dict(chain=..., walk=...)}"""
-    sc = scenario()
+def reference(controller, tree="icub", sel=SEL):
+    """the restatement's walk of the robots `sel`, without limits: {robot: dict(chain=..., walk=...)}"""
+    sc = scenario(tree)
     out = {}
-    for i in SEL:
-        ch = chain(controller, i)
-        out[i] = dict(chain=ch, walk=walk(ch, sc["fs"]["q0"][i], params()))
+    for i in sel:
+        ch = chain(controller, i, tree=tree)
+        out[i] = dict(chain=ch, walk=walk(ch, sc["fs"]["q0"][i], params(tree), tree=tree))
     return out
 
 

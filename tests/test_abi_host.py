@@ -245,6 +245,32 @@ def test_compact_jacobian_layout_of_the_icub_shaped_tree(wca):
         assert desc == list(range(j, j + len(desc)))
 
 
+@pytest.mark.parametrize("name", ["icub_gauged_legs_first", "icub_interleaved"])
+def test_compact_jacobian_layout_of_renumbered_trees(wca, name):
+    """The same restatement of compact_offset on the iCub-shaped robot numbered legs first and (not depth-first) with arms and legs
+    alternating: other path masks, the same robot - every joint keeps its record length, the records tile the block without gaps in the
+    new joint order and the block is 170 + 10 doubles again.  (The device side of these masks: the tick's automatic COMPACT hand-off on
+    icub_interleaved in test_tick_pipeline.py.)"""
+    import trees
+    m, order = trees.named(name), trees.ORDER[name]
+    f = trees.check_claims(name)
+    assert f["disjoint"]
+    mL, mR, mN = (sum(1 << j for j in p) for p in f["paths"])
+    assert [bin(x).count("1") for x in (mL, mR, mN)] == [6, 6, 3]
+    length = lambda masks, c: 10 if ((masks[0] | masks[1]) >> c) & 1 else (6 if (masks[2] >> c) & 1 else 4)
+    off = [4 * c + 6 * bin((mL | mR) & ((1 << c) - 1)).count("1") + 2 * bin(mN & ((1 << c) - 1)).count("1") for c in range(23)]
+    lens = [length((mL, mR, mN), c) for c in range(23)]
+    assert off[0] == 0 and all(off[c + 1] == off[c] + lens[c] for c in range(22)) and off[22] + lens[22] == 170
+    assert all(o % 2 == 0 for o in off)                      # 16-byte pieces
+    # the same joints carry the same records as in the iCub numbering
+    icub = trees.facts(wca.synth.icub_like_model())
+    iL, iR, iN = (sum(1 << j for j in p) for p in icub["paths"])
+    assert lens == [length((iL, iR, iN), order[c]) for c in range(23)]
+    if name == "icub_interleaved":
+        assert mL & 0x7ff == 0 and mR & 0x7ff == 0 and bin(mL).count("1") == 6 and mL & (mL >> 1) == 0      # every second joint of 11 .. 22
+        assert not f["dfs_contig"]
+
+
 def test_kernels_hold_no_flat_memory_instructions(wca, tmp_path):
     """Every global-memory access of the shipped kernels is a global_* instruction.  A pointer that a kernel reads out of a
     record in device memory (the tick's TickDev, the plan's step records) is generic unless it is marked (csrc/gptr.h), and an

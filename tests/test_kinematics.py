@@ -1,8 +1,12 @@
 """batched kinematics.  CPU: the oracle's analytic Jacobians against central differences of its own
 forward kinematics (the reference's model and iDynTree are absent: parity unpinned).  GPU: the kernel against the
 oracle, and the kernel's Jacobians driving the IK kernel against the exact IK optimum on the oracle's Jacobians."""
+import ctypes as C
+
 import numpy as np
 import pytest
+
+import trees
 
 
 def test_oracle_jacobians_match_finite_differences(wca):
@@ -78,3 +82,264 @@ def test_kinematics_feeds_the_ik_kernel(wca, qs):
         assert sol["status"][i] == 0 and np.abs(sol["dq"][i] - e["dq"]).max() <= 1e-8
         n_ok += 1
     assert n_ok > B // 2
+
+
+# ------------------------------------------------------------------------------------------------ trees other than the iCub-shaped one
+# (tests/trees.py: what each named tree is there for; every test asserts through trees.facts that its tree is of that kind)
+KIN_TOL = 1e-13          # the suite's kinematics tolerance: reach and base offset of every tree here are 1 m at most
+
+
+def _samples(name, count, seed=0, far=None):
+    """`count` base poses (any rotation) and joint angles uniform in +-2 pi for the named tree, seeded per tree"""
+    m = trees.named(name)
+    rng = np.random.default_rng([seed, trees.NAMES.index(name)])
+    return m, trees.random_base(rng, count, far=far), trees.random_q(rng, count, m["dof"])
+
+
+def _worst(a, b, keys=("J_left", "J_right", "J_neck", "J_com", "p_left", "R_left", "p_right", "R_right", "R_neck", "com")):
+    return max(np.abs(np.asarray(a[k]) - np.asarray(b[k])).max() for k in keys)
+
+
+@pytest.mark.parametrize("name", trees.NAMES)
+def test_oracle_jacobians_match_finite_differences_on_every_tree(name):
+    from oracle import kin_spec as ks
+    trees.check_claims(name)
+    m, base, q = _samples(name, 3)
+    assert trees.reach(m) <= 1.0
+    for i in range(3):
+        J, N = ks.jacobians(m, base[i], q[i]), ks.numeric_jacobians(m, base[i], q[i])
+        for k in N:
+            assert np.abs(J[k] - N[k]).max() < 5e-9, (k, i)
+
+
+def test_tree_twin_sees_what_the_trees_are_for():
+    """The CPU twin of wcqp_kin_create's derived facts on the named trees: pointer-jumping rounds 0, 3, 4 and 5, subtrees that are no index
+    ranges, shared frame paths, all three hand-offs - and on the iCub-shaped tree what the library's own comments say of it."""
+    f = {n: trees.check_claims(n) for n in trees.NAMES}
+    assert {f[n]["n_rounds"] for n in trees.NAMES} >= {0, 3, 4, 5}
+    assert not f["bushy26"]["dfs_contig"] and not f["icub_interleaved"]["dfs_contig"]
+    assert {f[n]["handoff"] for n in ("icub_gauged_legs_first", "icub_interleaved", "icub_waist")} == {"fused", "compact", "dense"}
+    assert f["star26"]["dof"] == 26 and f["one"]["dof"] == 1 and f["chain26"]["depth"] == 26
+    assert f["icub_waist"]["paths"][0] & f["icub_waist"]["paths"][1] & f["icub_waist"]["paths"][2] == {0}
+    from walking_controllers_amd import synth
+    g = trees.facts(synth.icub_like_model())
+    assert (g["depth"], g["n_rounds"], g["dfs_contig"], g["disjoint"], g["handoff"]) == (7, 3, True, True, "fused")
+    # legs first: the torso's subtree 12 .. 22 crosses the 16-joint boundary of the walk's two slots
+    lf = trees.named("icub_gauged_legs_first")
+    assert int(lf["parent"][12]) == -1 and all(12 in trees.path_to_root(lf, j) for j in range(12, 23))
+
+
+def test_oracle_is_invariant_under_regauging_and_renumbering(wca):
+    """The same physical robot in other numbers: every joint frame turned by a constant rotation, the joints numbered legs first or
+    (not depth-first) arms and legs alternately.  Jacobians (columns permuted back), poses and CoM of kin_spec agree to 1e-13."""
+    from oracle import kin_spec as ks
+    plain = wca.synth.icub_like_model()
+    b = wca.synth.synth_kin_batch(4, seed=77, joint_sigma=1.5, base_rot_sigma=1.0)
+    for name in ("icub_gauged", "icub_gauged_legs_first", "icub_interleaved"):
+        m, order = trees.named(name), trees.ORDER[name]
+        for i in range(4):
+            want = ks.jacobians(plain, b["base"][i], b["q"][i])
+            got = ks.jacobians(m, b["base"][i], trees.permute_joints(b["q"][i], order))
+            for k in ("J_left", "J_right", "J_neck", "J_com"):
+                got[k] = trees.unpermute_joints(got[k], order)
+            assert _worst(got, want) <= KIN_TOL, (name, i, _worst(got, want))
+    # and the helpers are each other's inverses
+    x = np.arange(29.0)
+    assert np.array_equal(trees.unpermute_joints(trees.permute_joints(x, trees.INTERLEAVED), trees.INTERLEAVED), x)
+    assert np.array_equal(trees.permute_joints(np.arange(23), trees.LEGS_FIRST), trees.LEGS_FIRST)
+    with pytest.raises(AssertionError):
+        trees.renumber(plain, [1, 0] + list(range(2, 23)))            # a child in front of its parent
+
+
+def _walk_inputs(wca, name, B, T):
+    """The walk scenario (synth_walk_batch) of the iCub-shaped robot in the named variant's numbering: (model, order, data, the keyword
+    arguments of qs.IKParams with posture, v_max and joint weights permuted with the joints).  The poses of tick 0 come from kin_spec."""
+    from helpers import planned_tick as pt
+    S = wca.synth
+    model, order = (S.icub_like_model(), list(range(23))) if name == "icub" else (trees.named(name), trees.ORDER[name])
+    kb = S.synth_walk_kin_batch(B)
+    kb = dict(base=kb["base"], q=trees.permute_joints(kb["q"], order))
+    d = S.synth_walk_batch(B, T, pt.poses_host(model, kb), kb)
+    w = trees.permute_joints(np.array([1.0] * 3 + [2.0] * 8 + [1.0] * 12), order)
+    vmax, posture = trees.permute_joints(S.WALK_VMAX, order), trees.permute_joints(S.WALK_POSTURE_DEG, order)
+    return model, order, d, dict(v_max=vmax.copy(), joint_reg_deg=posture.copy(), joint_reg_weights=w.copy())
+
+
+def test_restated_tick_is_invariant_under_renumbering(wca, qs):
+    """run_ticks on the interleaved numbering (posture, v_max and joint weights permuted with the joints) is the iCub-numbered run,
+    permuted: 120 closed-loop ticks, no failure, the joints travel."""
+    from oracle import tick_spec as ts
+    B, T = 3, 120
+    runs = {}
+    for name in ("icub", "icub_interleaved"):
+        model, order, d, ikw = _walk_inputs(wca, name, B, T)
+        runs[name] = ts.run_ticks(ts.TickParams(), d, T, qs.IKParams(**ikw), kin_model=model, foot_rect=wca.synth.FOOT_RECT)
+        assert runs[name]["ik_fail"].sum() == 0 and runs[name]["mpc_fail"].sum() == 0
+    a, b = runs["icub"], runs["icub_interleaved"]
+    assert np.abs(a["q_des"] - wca.synth.synth_walk_kin_batch(B)["q"]).max() > 0.05
+    assert np.abs(b["u0_log"] - a["u0_log"]).max() <= 1e-9 and np.abs(b["dcm"] - a["dcm"]).max() <= 1e-9
+    assert np.abs(b["com"] - a["com"]).max() <= 1e-9
+    assert np.abs(trees.unpermute_joints(b["q_des"], order) - a["q_des"]).max() <= 1e-9
+    assert np.abs(trees.unpermute_joints(b["dq_log"], order) - a["dq_log"]).max() <= 1e-8
+
+
+def _kin_params(wca, model):
+    """the wcqp_kin_params of a table, without creating a handle"""
+    n = int(model["dof"])
+    p = wca.capi.KinParams()
+    p.dof = n
+    for j in range(min(n, len(model["parent"]))):
+        p.parent[j] = int(model["parent"][j]); p.mass[j] = float(model["mass"][j])
+        for k in range(9):
+            p.R0[j][k] = float(np.asarray(model["R0"][j]).reshape(9)[k])
+        for k in range(3):
+            p.p0[j][k] = float(model["p0"][j][k]); p.axis[j][k] = float(model["axis"][j][k]); p.com[j][k] = float(model["com"][j][k])
+    p.root_mass = float(model["root_mass"])
+    for f in range(3):
+        p.frame_joint[f] = int(model["frame_joint"][f])
+        for k in range(9):
+            p.frame_R[f][k] = float(np.asarray(model["frame_R"][f]).reshape(9)[k])
+        for k in range(3):
+            p.frame_p[f][k] = float(model["frame_p"][f][k]); p.root_com[k] = float(model["root_com"][k])
+    return p
+
+
+def test_kin_create_refusals_need_no_device(wca):
+    """wcqp_kin_create refuses, with the code include/wcqp.h documents and `out` left NULL: a dof outside 1 .. 26 (UNSUPPORTED: one
+    column per lane of a 32-lane group), and with INVALID a parent that does not precede its joint or lies below -1, a negative or NaN
+    mass, a NaN root mass, a zero or NaN axis, a frame on a joint that is not there, a robot without mass.  26 joints, and 26 joints
+    all on the root link, are accepted."""
+    lib = wca.capi.lib()
+    INVALID, UNSUPPORTED = -1, -2
+
+    def create(name, edit=None):
+        m = trees.named(name)
+        if edit:
+            edit(m)
+        h = C.c_void_p()
+        rc = lib.wcqp_kin_create(C.byref(_kin_params(wca, m)), C.byref(h))
+        if rc == 0:
+            assert h.value and lib.wcqp_kin_destroy(h) == 0
+        else:
+            assert h.value is None, (rc, h.value)
+        return rc
+
+    def put(key, idx, val):
+        def edit(m):
+            if idx is None:
+                m[key] = val
+            else:
+                m[key][idx] = val
+        return edit
+    assert create("chain26") == 0 and create("star26") == 0 and create("one") == 0 and create("bushy26") == 0
+    assert create("one", put("dof", None, 0)) == UNSUPPORTED and create("chain26", put("dof", None, 27)) == UNSUPPORTED
+    nan = float("nan")
+    for key, idx, val in (("parent", 3, 3), ("parent", 3, 4), ("parent", 0, 0), ("parent", 5, -2), ("mass", 7, -0.5), ("mass", 25, nan),
+                          ("root_mass", None, nan), ("root_mass", None, -1.0), ("axis", 4, np.zeros(3)), ("axis", 25, np.array([0.0, nan, 1.0])),
+                          ("frame_joint", 0, -1), ("frame_joint", 2, 26), ("frame_joint", 1, 26)):
+        assert create("bushy26", put(key, idx, val)) == INVALID, (key, idx, val)
+    assert create("one", put("frame_joint", 1, 1)) == INVALID          # dof itself, on the smallest table
+
+    def massless(m):
+        m["mass"][:] = 0.0; m["root_mass"] = 0.0
+    assert create("star26", massless) == INVALID
+    assert lib.wcqp_kin_create(None, C.byref(C.c_void_p())) == INVALID and lib.wcqp_kin_create(C.byref(_kin_params(wca, trees.named("one"))), None) == INVALID
+
+
+# ---------------------------------------------------------------------------------------------------------------------- GPU
+def _against_oracle(out, state0, m, base, q, tol):
+    """the four Jacobians and the pose entries 0..23, 48..56, 66..68 against kin_spec; every other state entry bit-untouched"""
+    from oracle import kin_spec as ks
+    worst = 0.0
+    for i in range(q.shape[0]):
+        r = ks.jacobians(m, base[i], q[i])
+        s = out["state"][i]
+        got = dict(J_left=out["J_left"][i], J_right=out["J_right"][i], J_neck=out["J_neck"][i], J_com=out["J_com"][i], p_left=s[0:3],
+                   R_left=s[3:12].reshape(3, 3), p_right=s[12:15], R_right=s[15:24].reshape(3, 3), R_neck=s[48:57].reshape(3, 3), com=s[66:69])
+        for k in got:
+            err = np.abs(got[k] - r[k]).max()
+            worst = max(worst, err)
+            assert err <= tol, (k, i, err)
+        untouched = np.r_[24:48, 57:66, 69:87]
+        assert np.array_equal(s[untouched], state0[i][untouched])
+    return worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", trees.NAMES)
+def test_kinematics_kernel_matches_oracle_on_every_tree(wca, name):
+    """The stand-alone kernel on each named tree (B = 5: the last wave is half live; chain26 at B = 2), joint angles uniform in +-2 pi,
+    any base rotation, at the suite's 1e-13; without a state block the four Jacobians are the same bit for bit."""
+    f = trees.check_claims(name)
+    B = 2 if name == "chain26" else 5
+    m, base, q = _samples(name, B, seed=1)
+    assert q.shape == (B, f["dof"]) and np.abs(q).max() > np.pi and trees.reach(m) <= 1.0
+    state0 = np.arange(B * 87, dtype=float).reshape(B, 87) + 0.25
+    kin = wca.KinModel(m)
+    out = kin.jacobians_host(base, q, state0)
+    print(name, "worst deviation", _against_oracle(out, state0, m, base, q, KIN_TOL))
+    bare = kin.jacobians_host(base, q)
+    assert bare["state"] is None
+    for k in ("J_left", "J_right", "J_neck", "J_com"):
+        assert np.array_equal(bare[k], out[k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["icub_gauged", "bushy26"])
+def test_kinematics_kernel_far_from_the_origin(wca, name):
+    """The base about 100 m out: both sides round world coordinates at eps |p|, so the bound is 1e-13 max(1, |p_base|) - for the poses and
+    for every Jacobian column, the foot columns and the CoM columns whose subtree moments (prefix-sum differences on the depth-first
+    tree, the descendant loop on the other) are differences of world-frame first moments."""
+    f = trees.check_claims(name)
+    assert f["dfs_contig"] == (name == "icub_gauged")
+    B = 5
+    m, base, q = _samples(name, B, seed=2, far=(60.0, -70.0, 40.0))
+    scale = np.linalg.norm(base[:, :3], axis=1)
+    assert scale.min() > 95.0 and scale.max() < 105.0
+    state0 = np.zeros((B, 87))
+    out = wca.KinModel(m).jacobians_host(base, q, state0)
+    for i in range(B):
+        sl = slice(i, i + 1)
+        one = {k: (v[sl] if v is not None else None) for k, v in out.items()}
+        print(name, i, _against_oracle(one, state0[sl], m, base[sl], q[sl], KIN_TOL * max(1.0, scale[i])))
+
+
+@pytest.mark.gpu
+def test_kinematics_kernel_normalises_the_axes(wca):
+    """Axes 3.7 long: the library normalises them at create (kin_spec does not, it is given the unit ones).  On a tree with general axes
+    the kernel still meets the oracle at 1e-13; on one with coordinate axes - where x / sqrt(x x) is exactly 1 in IEEE arithmetic, so
+    that both tables hold the same numbers after create - it equals the unit-axis tree bit for bit.  (For a general unit axis u the two
+    inputs u and 3.7 u normalise to numbers that differ in the last bit: no bitwise claim can be made there.)"""
+    trees.check_claims("bushy26")
+    m, base, q = _samples("bushy26", 5, seed=3)
+    state0 = np.zeros((5, 87))
+    out = wca.KinModel(trees.scaled_axes(m)).jacobians_host(base, q, state0)
+    _against_oracle(out, state0, m, base, q, KIN_TOL)
+    trees.check_claims("icub_interleaved")
+    m, base, q = _samples("icub_interleaved", 5, seed=3)
+    long = trees.scaled_axes(m)
+    norm = lambda a: a / np.sqrt(a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1] + a[:, 2] * a[:, 2])[:, None]
+    assert np.array_equal(norm(long["axis"]), m["axis"]) and np.abs(long["axis"]).max() == 3.7
+    a, b = wca.KinModel(m).jacobians_host(base, q, state0), wca.KinModel(long).jacobians_host(base, q, state0)
+    _against_oracle(b, state0, m, base, q, KIN_TOL)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+@pytest.mark.gpu
+def test_kinematics_kernel_in_another_gauge_is_the_same_robot(wca):
+    """icub_gauged and the plain iCub-shaped tree, each within 1e-13 of its oracle, also agree with each other (2e-13), and so does the
+    legs-first numbering after its columns are permuted back."""
+    plain = wca.synth.icub_like_model()
+    b = wca.synth.synth_kin_batch(5, seed=78, joint_sigma=1.5, base_rot_sigma=1.0)
+    state0 = np.zeros((5, 87))
+    ref = wca.KinModel(plain).jacobians_host(b["base"], b["q"], state0)
+    _against_oracle(ref, state0, plain, b["base"], b["q"], KIN_TOL)
+    for name in ("icub_gauged", "icub_gauged_legs_first"):
+        m, order = trees.named(name), trees.ORDER[name]
+        q = trees.permute_joints(b["q"], order)
+        out = wca.KinModel(m).jacobians_host(b["base"], q, state0)
+        _against_oracle(out, state0, m, b["base"], q, KIN_TOL)
+        for k in ("J_left", "J_right", "J_neck", "J_com"):
+            assert np.abs(trees.unpermute_joints(out[k], order) - ref[k]).max() <= 2e-13, (name, k)
+        assert np.abs(out["state"] - ref["state"]).max() <= 2e-13

@@ -2,7 +2,8 @@
 CPU: the numpy restatement (helpers/prepare_spec.py) against its own certificate, a second guess and joint limits; the ABI.  GPU: the
 kernel against the restatement and against the certificate computed here, its outputs as inputs of the kinematics and of the tick, the
 outcomes other than SOLVED, the launch forms, and a prepared batch walking 40 ticks.
-tests/robots.py holds parameter sets, not trees: the one tree of the repository, synth.icub_like_model(), is the one wcqp_kin is given."""
+tests/robots.py holds parameter sets, not trees: wcqp_kin is given synth.icub_like_model(), and - one parity check, and the refusals - the
+variants of it in tests/trees.py (another gauge and numbering of the same robot; trees the 16-lane walk cannot run)."""
 import ctypes as C
 import os
 import subprocess
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 import robots
+import trees
 from helpers import footstep_plan as fp
 from helpers import prepare_spec as ps
 from helpers import streamed_tick as stt
@@ -27,23 +29,32 @@ def _targets(d, i, neck=True):
     return dict(left_d=d["left_d"][i], right_d=d["right_d"][i], com_d=d["com_d"][i], Rd_neck=d["Rd_neck"][i] if neck else None)
 
 
+def _scene(wca, model=None, order=None, configs=CONFIGS):
+    """the scene on a tree: by default the iCub-shaped one; model, order: the robot as another table (tests/trees.py) whose joint k is joint
+    order[k] of it - guess and posture are permuted with the joints, the restatement is given the same table"""
+    order = list(range(23)) if order is None else order
+    model = wca.synth.icub_like_model() if model is None else model
+    d = wca.synth.synth_prepare_batch(B13)
+    d = dict(d, q_guess=trees.permute_joints(d["q_guess"], order))
+    q_reg = trees.permute_joints(np.deg2rad(wca.synth.WALK_POSTURE_DEG), order)
+    par = {"free": ps.Params(q_reg=q_reg), "no_neck": ps.Params(q_reg=q_reg, w_n=0.0)}
+    sol = {k: [ps.solve(model, _targets(d, i), d["q_guess"][i], par[k]) for i in range(B13)] for k in ("free", "no_neck") if k in configs}
+    if "limits" in configs:
+        mean = (np.stack([s["q"] for s in sol["free"]]) - q_reg).mean(0)
+        lo, hi = np.full(23, -3.0), np.full(23, 3.0)
+        for k in np.argsort(-np.abs(mean))[:2]:
+            (hi if mean[k] > 0 else lo)[k] = q_reg[k] + 0.6 * mean[k]
+        par["limits"] = ps.Params(q_reg=q_reg, q_min=lo, q_max=hi)
+        sol["limits"] = [ps.solve(model, _targets(d, i), d["q_guess"][i], par["limits"]) for i in range(B13)]
+    return dict(model=model, d=d, q_reg=q_reg, par=par, sol=sol)
+
+
 @pytest.fixture(scope="module")
 def scene(wca):
     """13 robots of synth_prepare_batch and the restatement's optimum of each under the three configurations, computed once:
     free, with limits that cut the two largest mean excursions from the posture to 0.6 of their free value (one or two bounds active per
     robot), and without the neck target."""
-    model = wca.synth.icub_like_model()
-    d = wca.synth.synth_prepare_batch(B13)
-    q_reg = np.deg2rad(wca.synth.WALK_POSTURE_DEG)
-    par = {"free": ps.Params(q_reg=q_reg), "no_neck": ps.Params(q_reg=q_reg, w_n=0.0)}
-    sol = {k: [ps.solve(model, _targets(d, i), d["q_guess"][i], par[k]) for i in range(B13)] for k in ("free", "no_neck")}
-    mean = (np.stack([s["q"] for s in sol["free"]]) - q_reg).mean(0)
-    lo, hi = np.full(23, -3.0), np.full(23, 3.0)
-    for k in np.argsort(-np.abs(mean))[:2]:
-        (hi if mean[k] > 0 else lo)[k] = q_reg[k] + 0.6 * mean[k]
-    par["limits"] = ps.Params(q_reg=q_reg, q_min=lo, q_max=hi)
-    sol["limits"] = [ps.solve(model, _targets(d, i), d["q_guess"][i], par["limits"]) for i in range(B13)]
-    return dict(model=model, d=d, q_reg=q_reg, par=par, sol=sol)
+    return _scene(wca)
 
 
 def _solver(wca, scene, cfg, **kw):
@@ -151,6 +162,15 @@ def test_create_refusals(wca):
     # a tree whose torso joint lies on the paths of two attached frames is not one the walk runs
     two = dict(model, frame_joint=np.array([16, 22, 16], np.int32))
     assert create(kin_h=wca.KinModel(two)._h) == WCQP_E_UNSUPPORTED
+    # nor is one numbered not depth-first (COMPACT in the tick), nor one with a joint under all three frames (DENSE): `out` stays NULL
+    for name in ("icub_interleaved", "icub_waist"):
+        assert trees.check_claims(name)["handoff"] != "fused"
+        other = wca.KinModel(trees.named(name))
+        h = C.c_void_p()
+        p = wca.capi.PrepareParams(0.5, 1.0, 0.3, 1e-12, 1e-10, 100, q_reg.ctypes.data, None, None)
+        assert lib.wcqp_prepare_create(other._h, C.byref(p), C.byref(h)) == WCQP_E_UNSUPPORTED and h.value is None
+    for name in ("icub_gauged_legs_first", "icub_midframe"):
+        assert create(kin_h=wca.KinModel(trees.named(name))._h) == 0
     # the 4 GB rule: 696-byte rows, so 2^32 / 696 = 6170930 robots pass and one more does not; nothing is read or allocated
     h = C.c_void_p()
     p = wca.capi.PrepareParams(0.5, 1.0, 0.3, 1e-12, 1e-10, 100, q_reg.ctypes.data, None, None)
@@ -183,13 +203,31 @@ def device(wca, scene):
 def test_parity_with_the_restatement(scene, device, cfg):
     """q to 1e-9 (the project's parity bar; two guesses of the restatement itself agree to 6e-13), every robot SOLVED within the budget
     of 100 iterations (the restatement stays at or below 40 on these inputs)"""
-    o = device[cfg]
+    _parity(scene, device[cfg], cfg)
+
+
+def _parity(scene, o, cfg):
     ref = np.stack([s["q"] for s in scene["sol"][cfg]])
     assert max(s["iters"] for s in scene["sol"][cfg]) <= 40
     err = np.abs(o["q"] - ref).max()
     print(cfg, "iters", o["iters"], "restatement", [s["iters"] for s in scene["sol"][cfg]], "err", err)
     assert (o["status"] == 0).all() and (o["iters"] >= 1).all() and (o["iters"] <= 100).all()
     assert err <= 1e-9
+
+
+@pytest.mark.gpu
+def test_parity_with_the_restatement_on_a_regauged_tree_numbered_legs_first(wca):
+    """the same check on icub_gauged_legs_first (tests/trees.py): the same robot with general R0, axes and frame rotations and the torso's
+    subtree across the two slots of the 16-lane walk; the restatement is given the same table.  The free configuration."""
+    name = "icub_gauged_legs_first"
+    assert trees.check_claims(name)["handoff"] == "fused"
+    sc = _scene(wca, trees.named(name), trees.ORDER[name], configs=("free",))
+    d = sc["d"]
+    sol = _solver(wca, sc, "free")
+    o = sol.solve_host(d["left_d"], d["right_d"], d["com_d"], d["q_guess"], d["Rd_neck"])
+    sol.close()
+    _parity(sc, o, "free")
+    assert all(s["status"] == ps.SOLVED for s in sc["sol"]["free"])
 
 
 @pytest.mark.gpu

@@ -6,6 +6,8 @@ reference's per-tick call order (WalkingModule.cpp:578-745).
 import numpy as np
 import pytest
 
+import trees
+
 
 def test_contact_schedule_and_reference_are_consistent(wca):
     """CPU: the synthetic DCM reference satisfies xi_{t+1} = a xi_t + b zmp_t with the ZMP
@@ -291,27 +293,39 @@ def test_logger_rows_match_the_cpu_restatement(wca, qs, kin_mode):
     assert np.abs(ref["logger"][:, :, 20:23]).max() > 1e-3 and np.abs(ref["logger"][:, :, 8:10] - ref["logger"][:, :, 6:8]).max() > 1e-6
 
 
-def _walk_scenario(wca, B, T, first=0):
-    """A coherent synthetic robot marching in place (synth_walk_batch): poses from the device kinematics at tick 0."""
-    kin = wca.KinModel(wca.synth.icub_like_model())
+def _walk_scenario(wca, B, T, first=0, model=None, order=None):
+    """A coherent synthetic robot marching in place (synth_walk_batch): poses from the device kinematics at tick 0.  model, order: the
+    robot as another table (tests/trees.py) whose joint k is joint order[k] of the iCub-shaped one."""
+    kin = wca.KinModel(wca.synth.icub_like_model() if model is None else model)
     kb = wca.synth.synth_walk_kin_batch(B, first=first)
+    if order is not None:
+        kb = dict(kb, q=trees.permute_joints(kb["q"], order))
     poses = kin.jacobians_host(kb["base"], kb["q"], state=np.zeros((B, 87)))["state"]
     return kin, wca.synth.synth_walk_batch(B, T, poses, kb, first=first)
 
 
-def _kin_tick_against_oracle(wca, qs, B, T, vmax, ik_algorithm, handoff=0, graphs=(False, True), ticks_per_launch=0):
+def _kin_tick_against_oracle(wca, qs, B, T, vmax, ik_algorithm, handoff=0, graphs=(False, True), ticks_per_launch=0, model=None, order=None,
+                             expect_handoff=None):
+    """model, order: the tree the device and the restatement are both given (default: the iCub-shaped one) and its numbering - joint k is
+    joint order[k] of the iCub-shaped tree; posture, v_max and joint weights are permuted with the joints.  expect_handoff: what
+    info()["kin_handoff"] must say."""
     from oracle import tick_spec as ts
     p = ts.TickParams()
-    kin, d = _walk_scenario(wca, B, T)
-    model = wca.synth.icub_like_model()
-    vmax = np.broadcast_to(np.asarray(vmax, float), (23,)).copy()
-    ref = ts.run_ticks(p, d, T, qs.IKParams(v_max=vmax, joint_reg_deg=wca.synth.WALK_POSTURE_DEG.copy()),
+    order = list(range(23)) if order is None else order
+    model = wca.synth.icub_like_model() if model is None else model
+    kin, d = _walk_scenario(wca, B, T, model=model, order=order)
+    vmax = trees.permute_joints(np.broadcast_to(np.asarray(vmax, float), (23,)), order)
+    posture = trees.permute_joints(wca.synth.WALK_POSTURE_DEG, order)
+    weights = trees.permute_joints(qs.ICUB_JOINT_REG_WEIGHTS, order)
+    ref = ts.run_ticks(p, d, T, qs.IKParams(v_max=vmax, joint_reg_deg=posture.copy(), joint_reg_weights=weights.copy()),
                        kin_model=model, foot_rect=wca.synth.FOOT_RECT)
     assert ref["mpc_fail"].sum() == 0
     outs = []
     for use_graph in graphs:
-        ik = wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=vmax, algorithm=ik_algorithm, joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG))
+        ik = wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=vmax, algorithm=ik_algorithm, joint_reg_rad=np.deg2rad(posture), joint_reg_weights=weights)
         pipe = wca.TickPipeline(B, T, wca.MpcSolver(), ik, log_ticks=T, kin=kin, kin_handoff=handoff, ticks_per_launch=ticks_per_launch)
+        if expect_handoff is not None:
+            assert pipe.info()["kin_handoff"] == expect_handoff, pipe.info()
         pipe.upload(d)
         pipe.run(T, use_graph=use_graph)
         out = pipe.download()
@@ -533,3 +547,93 @@ def test_external_feedback_mode(wca, qs, kin_mode):
     # the internal-plant handle refuses feedback
     with pytest.raises(wca.WcqpError):
         pipe.set_feedback_device(1, 1, 1)
+
+
+# ---- the hand-off the tick takes by itself on other tables of the robot (tests/trees.py): COMPACT, DENSE, and FUSED in another gauge ----
+HANDOFF_B, HANDOFF_T = 12, 120
+
+
+def _auto_handoff_run(wca, qs, name):
+    """kin_handoff = 0 (nothing forced) on the named variant of the iCub-shaped robot, eager and graph, against the restatement run on
+    the same tree with the IK parameters permuted with the joints - the tolerances of _kin_tick_against_oracle."""
+    f = trees.check_claims(name)
+    model, order = trees.named(name), trees.ORDER[name]
+    d, ref, (eager, out), vmax = _kin_tick_against_oracle(wca, qs, HANDOFF_B, HANDOFF_T, wca.synth.WALK_VMAX, 0, handoff=0, model=model, order=order,
+                                                          expect_handoff=f["handoff"])
+    assert ref["ik_fail"].sum() == 0 and ref["mpc_fail"].sum() == 0          # the restatement walks on this tree
+    assert np.abs(ref["q_des"] - d["q0"]).max() > 0.05                       # and its joints travel
+    assert np.array_equal(out["u0_log"], eager["u0_log"]) and np.array_equal(out["dq_log"], eager["dq_log"])   # graph == eager, bitwise
+    return f, order, d, ref, out
+
+
+@pytest.mark.gpu
+def test_tick_falls_back_to_compact_records_on_a_numbering_that_is_not_depth_first(wca, qs):
+    """icub_interleaved: arms and legs numbered alternately, so no subtree is an index range and the fused walk does not apply; the frame
+    paths stay disjoint: the tick takes the COMPACT hand-off by itself (compact_offset on masks other than the iCub numbering's, the
+    kinematics kernel's descendant-mask CoM path).  Against the restatement on this tree, and - it is the same robot - against the device
+    run in the iCub numbering, permuted, at the tolerances test_kinematics_handoff_forms_agree uses between the compact and the fused form."""
+    f, order, d, ref, out = _auto_handoff_run(wca, qs, "icub_interleaved")
+    assert f["handoff"] == "compact" and not f["dfs_contig"] and f["disjoint"]
+    kin, d0 = _walk_scenario(wca, HANDOFF_B, HANDOFF_T)
+    ik = wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=wca.synth.WALK_VMAX, joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG))
+    pipe = wca.TickPipeline(HANDOFF_B, HANDOFF_T, wca.MpcSolver(), ik, log_ticks=HANDOFF_T, kin=kin)
+    assert pipe.info()["kin_handoff"] == "fused"
+    pipe.upload(d0); pipe.run(HANDOFF_T, use_graph=True)
+    icub = pipe.download()
+    assert icub["ik_fail"].sum() == 0 and out["ik_fail"].sum() == 0
+    e_dq = np.abs(trees.unpermute_joints(out["dq_log"], order) - icub["dq_log"]).max()
+    e_q = np.abs(trees.unpermute_joints(out["q_des"], order) - icub["q_des"]).max()
+    print("interleaved against the iCub numbering: dq", e_dq, "q_des", e_q, "u0", np.abs(out["u0_log"] - icub["u0_log"]).max())
+    assert np.array_equal(out["u0_log"], icub["u0_log"])
+    assert e_dq <= 1e-10 and e_q <= 1e-11
+
+
+@pytest.mark.gpu
+def test_tick_falls_back_to_dense_jacobians_when_frame_paths_share_a_joint(wca, qs):
+    """icub_waist: both legs hang under joint 0, which is then on the paths of both soles and the neck - a compact record holds ONE
+    frame's column, so the tick hands over the four dense Jacobians, by itself.  Another robot than the iCub-shaped one (the restatement's
+    q_des differ by 0.1 rad): compared with the restatement on this tree."""
+    f, order, d, ref, out = _auto_handoff_run(wca, qs, "icub_waist")
+    assert f["handoff"] == "dense" and not f["disjoint"] and f["dfs_contig"]
+
+
+@pytest.mark.gpu
+def test_fused_tick_on_a_regauged_tree_numbered_legs_first(wca, qs):
+    """icub_gauged_legs_first qualifies for the fused kinematics and is the iCub-shaped robot, with general R0, axes and frame rotations
+    and the torso's subtree 12 .. 22 across the two slots of the 16-lane walk."""
+    f, order, d, ref, out = _auto_handoff_run(wca, qs, "icub_gauged_legs_first")
+    assert f["handoff"] == "fused"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["icub_interleaved", "icub_waist"])
+def test_handles_that_need_the_fused_walk_refuse_other_trees(wca, name):
+    """Planned, streamed, external and position-IK handles run the fused kinematics only: on a tree the tick would give the COMPACT or the
+    DENSE hand-off they are refused at create with WCQP_E_UNSUPPORTED and `out` stays NULL.  (wcqp_tick_create looks for a device before it
+    looks at the tree; wcqp_prepare_create's refusal of the same trees needs none: test_prepare.py.)"""
+    import ctypes as C
+    assert trees.check_claims(name)["handoff"] != "fused"
+    lib = wca.capi.lib()
+    kin = wca.KinModel(trees.named(name))
+    B, T = 4, 8
+    q_reg = np.zeros(23)
+    ik = lambda: wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=1.0)
+    forms = dict(planned=dict(planned_trajectories=True, neck_additional_rotation=np.eye(3)),
+                 streamed=dict(streamed_trajectories=True, external_feedback=True, neck_additional_rotation=np.eye(3)),
+                 external=dict(external_feedback=True),
+                 position=dict(planned_trajectories=True, neck_additional_rotation=np.eye(3), ik_mode="position", position_ik=dict(q_reg=q_reg)))
+    for form, kw in forms.items():
+        with pytest.raises(wca.WcqpError, match=r"\(-2\)"):
+            wca.TickPipeline(B, T, wca.MpcSolver(), ik(), kin=kin, **kw)
+        # ... and straight through the ABI: the code, and the handle pointer as it was
+        good = wca.TickPipeline(B, T, wca.MpcSolver(), ik(), kin=wca.KinModel(wca.synth.icub_like_model()), **kw)
+        params = good.params
+        params.kin = kin.params
+        if form == "position":
+            params.position_ik.q_reg = q_reg.ctypes.data          # (the binding's own copy lived only through its create call)
+        h = C.c_void_p()
+        assert lib.wcqp_tick_create(C.byref(params), C.byref(h)) == -2 and h.value is None, form
+        good.close()
+    # the plain internal tick takes the same tree
+    pipe = wca.TickPipeline(B, T, wca.MpcSolver(), ik(), kin=kin)
+    assert pipe.info()["kin_handoff"] == trees.facts(trees.named(name))["handoff"]

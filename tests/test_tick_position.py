@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import robots
+import trees
 from helpers import footstep_replan as fr
 from helpers import position_tick as pk
 from helpers import prepare_spec as ps
@@ -28,11 +29,14 @@ def _ik(wca):
                         v_max=wca.synth.WALK_VMAX.copy(), k_pos_com=R["k_pos_com"], k_pos_foot=R["k_pos_foot"], k_att_foot=R["k_att_foot"], k_neck=R["k_neck"])
 
 
-def _pipe(wca, controller="mpc", position=True, tpl=0, B=B13, max_iter=30, **pik):
+def _pipe(wca, controller="mpc", position=True, tpl=0, B=B13, max_iter=30, tree="icub", **pik):
+    """tree: the scenario's tree (helpers/position_tick.tree_of); the velocity IK's parameters of _ik are in the iCub numbering - a POSITION
+    handle on another tree takes only its dof from them"""
+    assert position or tree == "icub"
     R = robots.ROBOTS[pk.ROBOT]
-    mode = dict(ik_mode="position", position_ik=dict(q_reg=pk.scenario()["q_reg"], max_iter=max_iter, **pik)) if position else {}
+    mode = dict(ik_mode="position", position_ik=dict(q_reg=pk.scenario(tree)["q_reg"], max_iter=max_iter, **pik)) if position else {}
     return wca.TickPipeline(B, T, wca.MpcSolver(horizon=pk.N, com_height=pk.H), _ik(wca), log_ticks=T, k_com=R["k_com"], k_zmp=R["k_zmp"],
-                            kin=wca.KinModel(pk.scenario()["model"]), planned_trajectories=True, neck_additional_rotation=pk.ADD_ROT,
+                            kin=wca.KinModel(pk.scenario(tree)["model"]), planned_trajectories=True, neck_additional_rotation=pk.ADD_ROT,
                             ticks_per_launch=tpl, **pk.controller_kwargs(controller), **mode)
 
 
@@ -244,12 +248,28 @@ def device(wca):
 def test_parity_with_the_restatement(device, controller):
     """(1) q_log of robots 0, 5 and 12 to 1e-9 on every tick; u0_log, dcm, com and zmp_gains to 1e-9; tick == T, no failure of either
     solver, between T and 30 T iterations per robot"""
-    o = device[controller]
-    assert device[controller + "/info"]["ik_mode"] == "position" and "dq_log" not in o
+    _parity(device[controller], device[controller + "/info"], controller, pk.reference(controller))
+
+
+@pytest.mark.gpu
+def test_parity_with_the_restatement_on_a_regauged_tree_numbered_legs_first(wca):
+    """the same check, MPC controller, on icub_gauged_legs_first (tests/trees.py): the same robot with general R0, axes and frame rotations
+    and the torso's subtree across the two slots of the 16-lane walk; the restatement walks the same table (two of its three robots)."""
+    tree = "icub_gauged_legs_first"
+    assert trees.check_claims(tree)["handoff"] == "fused"
+    pipe = _pipe(wca, "mpc", tree=tree)
+    o = _run(pipe, fs=pk.scenario(tree)["fs"])
+    info = pipe.info()
+    pipe.close()
+    _parity(o, info, "mpc", pk.reference("mpc", tree, sel=pk.SEL[1:]))        # a robot of the second wave and the last one
+
+
+def _parity(o, info, controller, reference):
+    assert info["ik_mode"] == "position" and "dq_log" not in o
     assert o["tick"] == T and not o["ik_fail"].any() and not o["mpc_fail"].any()
     assert (o["ik_iters"] >= T).all() and (o["ik_iters"] <= 30 * T).all()
     assert not o["hot_try"].any() and not o["hot_hit"].any()
-    for i, r in pk.reference(controller).items():
+    for i, r in reference.items():
         assert (r["walk"]["status"] == ps.SOLVED).all()
         err = np.abs(o["q_log"][:, i] - r["walk"]["q_log"]).max()
         print(controller, i, "q_log", err, "iters", int(o["ik_iters"][i]), "restatement", int(r["walk"]["iters"].sum()))

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import trees
 from helpers import sensor_feedback as sfh
 from helpers import zmp_gains as zg
 from oracle import kin_spec as ks
@@ -133,9 +134,12 @@ def test_binding_checks_the_sensor_arrays_before_the_device(wca):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
-def _walk(wca, B, T, phase0=None):
-    kin = wca.KinModel(wca.synth.icub_like_model())
+def _walk(wca, B, T, phase0=None, model=None, order=None):
+    """model, order: the robot as another table (tests/trees.py) whose joint k is joint order[k] of the iCub-shaped one"""
+    kin = wca.KinModel(wca.synth.icub_like_model() if model is None else model)
     kb = wca.synth.synth_walk_kin_batch(B)
+    if order is not None:
+        kb = dict(kb, q=trees.permute_joints(kb["q"], order))
     poses = kin.jacobians_host(kb["base"], kb["q"], state=np.zeros((B, 87)))["state"]
     d = wca.synth.synth_walk_batch(B, T, poses, kb)
     if phase0 is not None:
@@ -143,20 +147,23 @@ def _walk(wca, B, T, phase0=None):
     return kin, d
 
 
-def _ik(wca):
-    return wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=wca.synth.WALK_VMAX.copy(), joint_reg_rad=np.deg2rad(wca.synth.WALK_POSTURE_DEG))
+def _ik(wca, order=None):
+    order = list(range(23)) if order is None else order
+    return wca.IkSolver(form=wca.IK_FORM_QPOASES, v_max=trees.permute_joints(wca.synth.WALK_VMAX, order),
+                        joint_reg_rad=trees.permute_joints(np.deg2rad(wca.synth.WALK_POSTURE_DEG), order),
+                        joint_reg_weights=trees.permute_joints(np.array([1.0] * 3 + [2.0] * 8 + [1.0] * 12), order))
 
 
 def _ik_params(wca, qs):
     return qs.IKParams(v_max=wca.synth.WALK_VMAX.copy(), joint_reg_deg=wca.synth.WALK_POSTURE_DEG.copy())
 
 
-def _pipe(wca, B, T, kin, controller="mpc", gs=False, **kw):
+def _pipe(wca, B, T, kin, controller="mpc", gs=False, order=None, **kw):
     if controller == "reactive":
         kw.update(dcm_controller="reactive", k_dcm=K_DCM)
     if gs:
         kw.update(zmp_gain_scheduling=True, **zg.ZMP_SCHEDULE["iCubGazeboV2_5"])
-    return wca.TickPipeline(B, T, wca.MpcSolver(), _ik(wca), log_ticks=T, kin=kin, external_feedback=True, **kw)
+    return wca.TickPipeline(B, T, wca.MpcSolver(), _ik(wca, order), log_ticks=T, kin=kin, external_feedback=True, **kw)
 
 
 class Sensors:
@@ -210,11 +217,25 @@ def test_measured_state_matches_the_restatement_on_both_anchors(wca):
     """B = 37 (not a multiple of 4 or 64), fused kinematics, 7 ticks around a step boundary at tick 3 for 20 robots (left -> right and
     right -> left stance): random joints near the desired ones, random velocities, wrenches with both feet defined, one defined, and one
     below the 0.001 threshold.  download()["measured"] == the restatement to 1e-12, tick by tick."""
+    _measured_state_on_both_anchors(wca)
+
+
+@pytest.mark.gpu
+def test_measured_state_on_a_regauged_tree_numbered_legs_first(wca):
+    """the same check on icub_gauged_legs_first (tests/trees.py): the same robot with general R0, axes and frame rotations, the torso's
+    subtree across the two slots of the 16-lane walk; the restatement is given the same table."""
+    name = "icub_gauged_legs_first"
+    assert trees.check_claims(name)["handoff"] == "fused"
+    _measured_state_on_both_anchors(wca, trees.named(name), trees.ORDER[name])
+
+
+def _measured_state_on_both_anchors(wca, model=None, order=None):
     B, T, st = 37, 7, 180
     phase0 = np.array([st - 3] * 10 + [2 * st - 3] * 10 + [50] * 17, np.int32)
-    kin, d = _walk(wca, B, T, phase0)
-    model = wca.synth.icub_like_model()
-    pipe = _pipe(wca, B, T, kin)
+    model = wca.synth.icub_like_model() if model is None else model
+    kin, d = _walk(wca, B, T, phase0, model, order)
+    pipe = _pipe(wca, B, T, kin, order=order)
+    assert pipe.info()["kin_handoff"] == "fused"
     pipe.upload(d)
     o = pipe.download()
     assert np.array_equal(o["measured"], np.concatenate([d["dcm0"], d["com0"], d["u_init"]], 1))   # before any tick: the uploaded state
@@ -238,7 +259,7 @@ def test_measured_state_matches_the_restatement_on_both_anchors(wca):
         q_des = o["q_des"]
     assert sides == {0, 1}
     # with q_meas = q_des (and no velocity) the CoM is the anchored kinematics' at the desired joints, what the tick's own kinematics see
-    pipe2 = _pipe(wca, B, T, kin)
+    pipe2 = _pipe(wca, B, T, kin, order=order)
     pipe2.upload(d)
     pipe2.set_sensor_feedback_host(d["q0"], np.zeros((B, 23)), *sfh.wrenches(rng, B))
     pipe2.run(1)
