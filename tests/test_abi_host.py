@@ -294,3 +294,19 @@ def test_kernels_hold_no_flat_memory_instructions(wca, tmp_path):
         assert not flat, (name, len(flat), sorted(set(flat)))
         checked += 1
     assert checked == 9
+
+
+def test_host_staging_layout_under_sanitizers(tmp_path):
+    """csrc/host_stage.h - where a *_host entry point's arrays sit in its device block - built on its own (the header includes no HIP header)
+    with ASan + UBSan and run: tests/cpp/host_stage_check.cpp lays out the IK form's twelve arrays and the unicycle form's ten (K = 0 and 4)
+    for batches 1, 3, 5 and 67 and checks the offsets against the chains those entry points used to write by hand, no overlap, each
+    offset a multiple of its element size, absent NULL-when-absent arrays (no room, NULL), and that a seventeenth array or a fixed block
+    one byte too small is refused with nothing written."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "host_stage_check"
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
+                           "-I", os.path.join(root, "walking-controllers_amd", "csrc"), os.path.join(root, "tests", "cpp", "host_stage_check.cpp"),
+                           "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("host_stage ok"), r.stdout[-2000:] + r.stderr[-2000:]

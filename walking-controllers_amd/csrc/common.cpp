@@ -60,6 +60,38 @@ void DeviceScratch::release() {
     cap = 0;
 }
 
+int HostStage::upload(DeviceScratch& block) {
+    if (refused) return WCQP_E_INVALID;
+    const int rc = block.reserve(total);
+    return rc != WCQP_OK ? rc : upload(block.ptr, block.cap);
+}
+
+int HostStage::upload(void* block, size_t capacity) {
+    static_assert(kStageRefused == WCQP_E_INVALID, "a layout that does not fit is an invalid call");
+    // (synchronous copies on the NULL stream: the host arrays are consumed when they return)
+    return copy_in(block, capacity, [](void* dst, const void* src, size_t bytes) -> int {
+        WCQP_HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        return WCQP_OK;
+    });
+}
+
+int HostStage::download() const {
+    WCQP_HIP_TRY(hipDeviceSynchronize());
+    return copy_out([](void* dst, const void* src, size_t bytes) -> int {
+        WCQP_HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        return WCQP_OK;
+    });
+}
+
+int require_device(const char* what) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        std::fprintf(stderr, "[wcqp] no HIP device: the %s has no CPU fallback\n", what);
+        return WCQP_E_HIP;
+    }
+    return WCQP_OK;
+}
+
 }  // namespace wcqp
 
 extern "C" {

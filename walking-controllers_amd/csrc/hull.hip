@@ -59,10 +59,16 @@ int hull_tables_from_state(int batch, const double* foot_rect_host, const double
 
 extern "C" {
 
+// what both forms refuse before they look for a device
+static int check_call(int32_t batch, const double* foot_rect, const double* left_T, const double* right_T,
+                      const uint8_t* contact, const double* hull_A, const double* hull_b, const int32_t* hull_nc) {
+    return batch < 0 || !foot_rect || !left_T || !right_T || !contact || !hull_A || !hull_b || !hull_nc ? WCQP_E_INVALID : WCQP_OK;
+}
+
 int wcqp_hull_from_feet_device(int32_t batch, const double* foot_rect, const double* left_T, const double* right_T,
                                const uint8_t* contact, double* hull_A, double* hull_b, int32_t* hull_nc, void* stream) {
-    if (batch < 0 || !foot_rect || !left_T || !right_T || !contact || !hull_A || !hull_b || !hull_nc) return WCQP_E_INVALID;
-    if (batch == 0) return WCQP_OK;
+    const int rc = check_call(batch, foot_rect, left_T, right_T, contact, hull_A, hull_b, hull_nc);
+    if (rc != WCQP_OK || batch == 0) return rc;
     hipLaunchKernelGGL(hull_from_feet_kernel, dim3((batch + 127) / 128), dim3(128), 0, (hipStream_t)stream,
                        batch, foot_rect, left_T, right_T, contact, hull_A, hull_b, hull_nc);
     WCQP_HIP_TRY(hipGetLastError());
@@ -71,34 +77,22 @@ int wcqp_hull_from_feet_device(int32_t batch, const double* foot_rect, const dou
 
 int wcqp_hull_from_feet_host(int32_t batch, const double* foot_rect, const double* left_T, const double* right_T,
                              const uint8_t* contact, double* hull_A, double* hull_b, int32_t* hull_nc) {
-    if (batch < 0 || !foot_rect || !left_T || !right_T || !contact || !hull_A || !hull_b || !hull_nc) return WCQP_E_INVALID;
-    if (batch == 0) return WCQP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        std::fprintf(stderr, "[wcqp] no HIP device: the hull builder has no CPU fallback\n");
-        return WCQP_E_HIP;
-    }
+    int rc = check_call(batch, foot_rect, left_T, right_T, contact, hull_A, hull_b, hull_nc);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = wcqp::require_device("hull builder");
+    if (rc != WCQP_OK) return rc;
     const size_t B = (size_t)batch;
-    double *d_rect = nullptr, *d_l = nullptr, *d_r = nullptr, *d_A = nullptr, *d_b = nullptr;
-    unsigned char* d_c = nullptr; int* d_n = nullptr;
-    int rc = WCQP_OK;
-    if (hipMalloc(&d_rect, 64) != hipSuccess || hipMalloc(&d_l, B * 96) != hipSuccess || hipMalloc(&d_r, B * 96) != hipSuccess ||
-        hipMalloc(&d_A, B * 128) != hipSuccess || hipMalloc(&d_b, B * 64) != hipSuccess || hipMalloc(&d_c, B) != hipSuccess ||
-        hipMalloc(&d_n, B * 4) != hipSuccess) rc = WCQP_E_NOMEM;
-    if (rc == WCQP_OK) {
-        (void)hipMemcpy(d_rect, foot_rect, 64, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_l, left_T, B * 96, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_r, right_T, B * 96, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_c, contact, B, hipMemcpyHostToDevice);
-        rc = wcqp_hull_from_feet_device(batch, d_rect, d_l, d_r, d_c, d_A, d_b, d_n, nullptr);
-        if (rc == WCQP_OK && hipDeviceSynchronize() != hipSuccess) rc = WCQP_E_HIP;
-        if (rc == WCQP_OK) {
-            (void)hipMemcpy(hull_A, d_A, B * 128, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(hull_b, d_b, B * 64, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(hull_nc, d_n, B * 4, hipMemcpyDeviceToHost);
-        }
-    }
-    (void)hipFree(d_rect); (void)hipFree(d_l); (void)hipFree(d_r); (void)hipFree(d_A); (void)hipFree(d_b); (void)hipFree(d_c); (void)hipFree(d_n);
+    wcqp::HostStage st;
+    const auto d_rect = st.in(foot_rect, 8), d_l = st.in(left_T, B * 12), d_r = st.in(right_T, B * 12);
+    const auto d_A = st.out(hull_A, B * 16), d_b = st.out(hull_b, B * 8);
+    const auto d_n = st.out(hull_nc, B);
+    const auto d_c = st.in(contact, B);
+    // no handle: a block of the call's own, released on every way out; a copy that fails is WCQP_E_HIP
+    wcqp::DeviceScratch block;
+    rc = st.upload(block);
+    if (rc == WCQP_OK) rc = wcqp_hull_from_feet_device(batch, st[d_rect], st[d_l], st[d_r], st[d_c], st[d_A], st[d_b], st[d_n], nullptr);
+    if (rc == WCQP_OK) rc = st.download();
+    block.release();
     return rc;
 }
 

@@ -36,13 +36,18 @@ namespace {
 
 int ensure_device(wcqp_ik_s* h) {
     if (h->d_prm) return WCQP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        std::fprintf(stderr, "[wcqp] no HIP device: the IK solve path has no CPU fallback\n");
-        return WCQP_E_HIP;
-    }
+    if (const int rc = wcqp::require_device("IK solve path"); rc != WCQP_OK) return rc;
     WCQP_HIP_TRY(hipMalloc(&h->d_prm, sizeof(IkDeviceParams)));
     WCQP_HIP_TRY(hipMemcpy(h->d_prm, &h->hp, sizeof(IkDeviceParams), hipMemcpyHostToDevice));
+    return WCQP_OK;
+}
+
+// what both solve forms refuse before they look for a device
+int check_call(wcqp_ik_t h, int32_t batch, const double* J_left, const double* J_right, const double* J_neck, const double* J_com,
+               const double* q, const double* state, const double* dq, const int32_t* status) {
+    if (!h || batch < 0) return WCQP_E_INVALID;
+    if (!J_left || !J_right || !J_neck || !J_com || !q || !state || !dq || !status) return WCQP_E_INVALID;
+    if (!wcqp::ik_batch_fits32(batch)) return WCQP_E_UNSUPPORTED;
     return WCQP_OK;
 }
 
@@ -165,11 +170,9 @@ int wcqp_ik_solve_device(wcqp_ik_t h, int32_t batch,
                          const double* q, const double* state,
                          double* dq, int32_t* status, uint32_t* active_lower, uint32_t* active_upper,
                          double* foot_err, int32_t* iters, void* stream) {
-    if (!h || batch < 0) return WCQP_E_INVALID;
-    if (!J_left || !J_right || !J_neck || !J_com || !q || !state || !dq || !status) return WCQP_E_INVALID;
-    if (!wcqp::ik_batch_fits32(batch)) return WCQP_E_UNSUPPORTED;
-    if (batch == 0) return WCQP_OK;
-    const int rc = ensure_device(h);
+    int rc = check_call(h, batch, J_left, J_right, J_neck, J_com, q, state, dq, status);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     const wcqp_ik::IkIo io{J_left, J_right, J_neck, J_com, q, state, dq, status, active_lower, active_upper, foot_err, iters};
     const hipStream_t s = (hipStream_t)stream;
@@ -323,40 +326,23 @@ int wcqp_ik_solve_host(wcqp_ik_t h, int32_t batch,
                        const double* q, const double* state,
                        double* dq, int32_t* status, uint32_t* active_lower, uint32_t* active_upper,
                        double* foot_err, int32_t* iters) {
-    if (!h || batch < 0) return WCQP_E_INVALID;
-    if (!J_left || !J_right || !J_neck || !J_com || !q || !state || !dq || !status) return WCQP_E_INVALID;
-    if (!wcqp::ik_batch_fits32(batch)) return WCQP_E_UNSUPPORTED;
-    if (batch == 0) return WCQP_OK;
-    int rc = ensure_device(h);
+    int rc = check_call(h, batch, J_left, J_right, J_neck, J_com, q, state, dq, status);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     const size_t B = (size_t)batch;
-    const size_t o_jl = 0, o_jr = o_jl + B * 6 * kNV, o_jn = o_jr + B * 6 * kNV, o_jc = o_jn + B * 3 * kNV,
-                 o_q = o_jc + B * 3 * kNV, o_st = o_q + B * kDof, o_dq = o_st + B * kStateLen,
-                 o_fe = o_dq + B * kDof, n_dbl = o_fe + B * 12;
-    rc = h->scratch.reserve(n_dbl * 8 + B * 4 * 4);
+    wcqp::HostStage st;
+    const auto d_jl = st.in(J_left, B * 6 * kNV), d_jr = st.in(J_right, B * 6 * kNV), d_jn = st.in(J_neck, B * 3 * kNV), d_jc = st.in(J_com, B * 3 * kNV);
+    const auto d_q = st.in(q, B * kDof), d_s = st.in(state, B * kStateLen);
+    const auto d_dq = st.out(dq, B * kDof), d_fe = st.out(foot_err, B * 12, /*the kernel forms no foot errors without it*/ true);
+    const auto d_st = st.out(status, B);
+    const auto d_lo = st.out(active_lower, B), d_up = st.out(active_upper, B);
+    const auto d_it = st.out(iters, B);
+    rc = st.upload(h->scratch);
     if (rc != WCQP_OK) return rc;
-    double* d = static_cast<double*>(h->scratch.ptr);
-    int32_t* d_st = reinterpret_cast<int32_t*>(d + n_dbl);
-    uint32_t* d_lo = reinterpret_cast<uint32_t*>(d_st + B);
-    uint32_t* d_up = d_lo + B;
-    int32_t* d_it = reinterpret_cast<int32_t*>(d_up + B);
-    WCQP_HIP_TRY(hipMemcpy(d + o_jl, J_left, B * 6 * kNV * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_jr, J_right, B * 6 * kNV * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_jn, J_neck, B * 3 * kNV * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_jc, J_com, B * 3 * kNV * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_q, q, B * kDof * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_st, state, B * kStateLen * 8, hipMemcpyHostToDevice));
-    rc = wcqp_ik_solve_device(h, batch, d + o_jl, d + o_jr, d + o_jn, d + o_jc, d + o_q, d + o_st,
-                              d + o_dq, d_st, d_lo, d_up, foot_err ? d + o_fe : nullptr, d_it, nullptr);
-    if (rc != WCQP_OK) return rc;
-    WCQP_HIP_TRY(hipDeviceSynchronize());
-    WCQP_HIP_TRY(hipMemcpy(dq, d + o_dq, B * kDof * 8, hipMemcpyDeviceToHost));
-    WCQP_HIP_TRY(hipMemcpy(status, d_st, B * 4, hipMemcpyDeviceToHost));
-    if (active_lower) WCQP_HIP_TRY(hipMemcpy(active_lower, d_lo, B * 4, hipMemcpyDeviceToHost));
-    if (active_upper) WCQP_HIP_TRY(hipMemcpy(active_upper, d_up, B * 4, hipMemcpyDeviceToHost));
-    if (foot_err) WCQP_HIP_TRY(hipMemcpy(foot_err, d + o_fe, B * 12 * 8, hipMemcpyDeviceToHost));
-    if (iters) WCQP_HIP_TRY(hipMemcpy(iters, d_it, B * 4, hipMemcpyDeviceToHost));
-    return WCQP_OK;
+    rc = wcqp_ik_solve_device(h, batch, st[d_jl], st[d_jr], st[d_jn], st[d_jc], st[d_q], st[d_s],
+                              st[d_dq], st[d_st], st[d_lo], st[d_up], st[d_fe], st[d_it], nullptr);
+    return rc != WCQP_OK ? rc : st.download();
 }
 
 }  // extern "C"

@@ -387,13 +387,17 @@ namespace {
 
 int ensure_device(wcqp_kin_s* h) {
     if (h->d_model) return WCQP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        std::fprintf(stderr, "[wcqp] no HIP device: the kinematics kernel has no CPU fallback\n");
-        return WCQP_E_HIP;
-    }
+    if (const int rc = wcqp::require_device("kinematics kernel"); rc != WCQP_OK) return rc;
     WCQP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_model), sizeof(KinDev)));
     WCQP_HIP_TRY(hipMemcpy(h->d_model, &h->hd, sizeof(KinDev), hipMemcpyHostToDevice));
+    return WCQP_OK;
+}
+
+// what both forms of wcqp_kin_jacobians_* refuse before they look for a device
+int check_call(wcqp_kin_t h, int32_t batch, const double* base, const double* q,
+               const double* J_left, const double* J_right, const double* J_neck, const double* J_com) {
+    if (!h || batch < 0) return WCQP_E_INVALID;
+    if (!base || !q || !J_left || !J_right || !J_neck || !J_com) return WCQP_E_INVALID;
     return WCQP_OK;
 }
 
@@ -543,10 +547,9 @@ int wcqp_kin_destroy(wcqp_kin_t h) {
 
 int wcqp_kin_jacobians_device(wcqp_kin_t h, int32_t batch, const double* base, const double* q,
                               double* J_left, double* J_right, double* J_neck, double* J_com, double* state, void* stream) {
-    if (!h || batch < 0) return WCQP_E_INVALID;
-    if (!base || !q || !J_left || !J_right || !J_neck || !J_com) return WCQP_E_INVALID;
-    if (batch == 0) return WCQP_OK;
-    const int rc = ensure_device(h);
+    int rc = check_call(h, batch, base, q, J_left, J_right, J_neck, J_com);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     const unsigned grid = (unsigned)((batch + 1) / 2);
     wcqp_tick::KinTick kt{};
@@ -562,29 +565,19 @@ int wcqp_kin_jacobians_device(wcqp_kin_t h, int32_t batch, const double* base, c
 
 int wcqp_kin_jacobians_host(wcqp_kin_t h, int32_t batch, const double* base, const double* q,
                             double* J_left, double* J_right, double* J_neck, double* J_com, double* state) {
-    if (!h || batch < 0) return WCQP_E_INVALID;
-    if (!base || !q || !J_left || !J_right || !J_neck || !J_com) return WCQP_E_INVALID;
-    if (batch == 0) return WCQP_OK;
-    int rc = ensure_device(h);
+    int rc = check_call(h, batch, base, q, J_left, J_right, J_neck, J_com);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     const size_t B = (size_t)batch, n = (size_t)h->hd.dof, nc = 6 + n;
-    const size_t o_base = 0, o_q = o_base + B * 12, o_jl = o_q + B * n, o_jr = o_jl + B * 6 * nc, o_jn = o_jr + B * 6 * nc,
-                 o_jc = o_jn + B * 3 * nc, o_st = o_jc + B * 3 * nc, total = o_st + B * kStateLen;
-    rc = h->scratch.reserve(total * sizeof(double));
+    wcqp::HostStage st;
+    const auto d_base = st.in(base, B * 12), d_q = st.in(q, B * n);
+    const auto d_jl = st.out(J_left, B * 6 * nc), d_jr = st.out(J_right, B * 6 * nc), d_jn = st.out(J_neck, B * 3 * nc), d_jc = st.out(J_com, B * 3 * nc);
+    const auto d_st = st.inout(state, B * kStateLen, /*the kernel fills no pose block without it*/ true);     // (copied in AND out)
+    rc = st.upload(h->scratch);
     if (rc != WCQP_OK) return rc;
-    double* d = static_cast<double*>(h->scratch.ptr);
-    WCQP_HIP_TRY(hipMemcpy(d + o_base, base, B * 12 * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_q, q, B * n * 8, hipMemcpyHostToDevice));
-    if (state) WCQP_HIP_TRY(hipMemcpy(d + o_st, state, B * kStateLen * 8, hipMemcpyHostToDevice));
-    rc = wcqp_kin_jacobians_device(h, batch, d + o_base, d + o_q, d + o_jl, d + o_jr, d + o_jn, d + o_jc, state ? d + o_st : nullptr, nullptr);
-    if (rc != WCQP_OK) return rc;
-    WCQP_HIP_TRY(hipDeviceSynchronize());
-    WCQP_HIP_TRY(hipMemcpy(J_left, d + o_jl, B * 6 * nc * 8, hipMemcpyDeviceToHost));
-    WCQP_HIP_TRY(hipMemcpy(J_right, d + o_jr, B * 6 * nc * 8, hipMemcpyDeviceToHost));
-    WCQP_HIP_TRY(hipMemcpy(J_neck, d + o_jn, B * 3 * nc * 8, hipMemcpyDeviceToHost));
-    WCQP_HIP_TRY(hipMemcpy(J_com, d + o_jc, B * 3 * nc * 8, hipMemcpyDeviceToHost));
-    if (state) WCQP_HIP_TRY(hipMemcpy(state, d + o_st, B * kStateLen * 8, hipMemcpyDeviceToHost));
-    return WCQP_OK;
+    rc = wcqp_kin_jacobians_device(h, batch, st[d_base], st[d_q], st[d_jl], st[d_jr], st[d_jn], st[d_jc], st[d_st], nullptr);
+    return rc != WCQP_OK ? rc : st.download();
 }
 
 }  // extern "C"

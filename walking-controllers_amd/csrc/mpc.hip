@@ -251,14 +251,21 @@ int build_constants(wcqp_mpc_s& h) {
 
 int ensure_device(wcqp_mpc_s* h) {
     if (h->d_Gr) return WCQP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        std::fprintf(stderr, "[wcqp] no HIP device: the MPC solve path has no CPU fallback\n");
-        return WCQP_E_HIP;
-    }
+    if (const int rc = wcqp::require_device("MPC solve path"); rc != WCQP_OK) return rc;
     WCQP_HIP_TRY(hipGetDevice(&h->device));
     WCQP_HIP_TRY(hipMalloc(&h->d_Gr, h->Gr.size() * sizeof(double)));
     WCQP_HIP_TRY(hipMemcpy(h->d_Gr, h->Gr.data(), h->Gr.size() * sizeof(double), hipMemcpyHostToDevice));
+    return WCQP_OK;
+}
+
+// what the solve forms (and the tick's strided launch, mpc_enqueue) refuse before they look for a device
+int check_call(wcqp_mpc_t h, int batch, const double* x0, const double* ref, int ref_len, int ref_stride, const double* u_prev,
+               const double* hull_A, const double* hull_b, const int* hull_nc, int hull_sets, const double* u0, const int* status) {
+    if (!h || batch < 0 || ref_len < 1 || ref_stride < ref_len || hull_sets < 1) return WCQP_E_INVALID;
+    if (!x0 || !ref || !u_prev || !hull_A || !hull_b || !hull_nc || !u0 || !status) return WCQP_E_INVALID;
+    // (this kernel forms its addresses in 64 bits; the limit is the one of the kernels that solve the same QP on the IK's lanes -
+    // wcqp_qp_enqueue_steps, the plans, the tick - so that a batch one route takes is a batch every route takes)
+    if (!wcqp::fits32(batch, (long long)ref_stride * 16) || !wcqp::fits32((long long)batch * hull_sets, WCQP_HULL_ROWS * 16)) return WCQP_E_UNSUPPORTED;
     return WCQP_OK;
 }
 
@@ -270,13 +277,9 @@ int mpc_enqueue(wcqp_mpc_t h, int batch, const double* x0, const double* ref, in
                 const int* ref_start_dev, const double* u_prev,
                 const double* hull_A, const double* hull_b, const int* hull_nc, int hull_sets, const int* hull_sel,
                 double* u0, int* status, unsigned* active, double* margin, hipStream_t stream) {
-    if (!h || batch < 0 || ref_len < 1 || ref_stride < ref_len || hull_sets < 1) return WCQP_E_INVALID;
-    if (!x0 || !ref || !u_prev || !hull_A || !hull_b || !hull_nc || !u0 || !status) return WCQP_E_INVALID;
-    // (this kernel forms its addresses in 64 bits; the limit is the one of the kernels that solve the same QP on the IK's lanes -
-    // wcqp_qp_enqueue_steps, the plans, the tick - so that a batch one route takes is a batch every route takes)
-    if (!fits32(batch, (long long)ref_stride * 16) || !fits32((long long)batch * hull_sets, WCQP_HULL_ROWS * 16)) return WCQP_E_UNSUPPORTED;
-    if (batch == 0) return WCQP_OK;
-    const int rc = ensure_device(h);
+    int rc = check_call(h, batch, x0, ref, ref_len, ref_stride, u_prev, hull_A, hull_b, hull_nc, hull_sets, u0, status);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     MpcDeviceConsts c;
     mpc_device_consts(h, &c);
@@ -370,37 +373,22 @@ int wcqp_mpc_solve_host(wcqp_mpc_t h, int32_t batch,
                         const double* x0, const double* ref, int32_t ref_len, const double* u_prev,
                         const double* hull_A, const double* hull_b, const int32_t* hull_nc,
                         double* u0, int32_t* status, uint32_t* active, double* margin) {
-    if (!h || batch < 0 || ref_len < 1) return WCQP_E_INVALID;
-    if (!x0 || !ref || !u_prev || !hull_A || !hull_b || !hull_nc || !u0 || !status) return WCQP_E_INVALID;
-    if (!wcqp::mpc_batch_fits32(batch, ref_len)) return WCQP_E_UNSUPPORTED;
-    if (batch == 0) return WCQP_OK;
-    int rc = ensure_device(h);
+    int rc = check_call(h, batch, x0, ref, ref_len, ref_len, u_prev, hull_A, hull_b, hull_nc, 1, u0, status);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     const size_t B = (size_t)batch;
-    const size_t o_x0 = 0, o_ref = o_x0 + B * 2, o_up = o_ref + B * ref_len * 2, o_hA = o_up + B * 2,
-                 o_hb = o_hA + B * 16, o_u0 = o_hb + B * 8, o_mg = o_u0 + B * 2, n_dbl = o_mg + B;
-    const size_t bytes = n_dbl * 8 + B * 4 * 3;
-    rc = h->scratch.reserve(bytes);
+    wcqp::HostStage st;
+    const auto d_x0 = st.in(x0, B * 2), d_ref = st.in(ref, B * ref_len * 2), d_up = st.in(u_prev, B * 2), d_hA = st.in(hull_A, B * 16), d_hb = st.in(hull_b, B * 8);
+    const auto d_u0 = st.out(u0, B * 2), d_mg = st.out(margin, B);
+    const auto d_nc = st.in(hull_nc, B);
+    const auto d_st = st.out(status, B);
+    const auto d_ac = st.out(active, B);
+    rc = st.upload(h->scratch);
     if (rc != WCQP_OK) return rc;
-    double* d = static_cast<double*>(h->scratch.ptr);
-    int32_t* d_nc = reinterpret_cast<int32_t*>(d + n_dbl);
-    int32_t* d_st = d_nc + B;
-    uint32_t* d_ac = reinterpret_cast<uint32_t*>(d_st + B);
-    WCQP_HIP_TRY(hipMemcpy(d + o_x0, x0, B * 16, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_ref, ref, B * ref_len * 16, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_up, u_prev, B * 16, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_hA, hull_A, B * 128, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_hb, hull_b, B * 64, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d_nc, hull_nc, B * 4, hipMemcpyHostToDevice));
-    rc = wcqp_mpc_solve_device(h, batch, d + o_x0, d + o_ref, ref_len, d + o_up, d + o_hA, d + o_hb, d_nc,
-                               d + o_u0, d_st, d_ac, d + o_mg, nullptr);
-    if (rc != WCQP_OK) return rc;
-    WCQP_HIP_TRY(hipDeviceSynchronize());
-    WCQP_HIP_TRY(hipMemcpy(u0, d + o_u0, B * 16, hipMemcpyDeviceToHost));
-    WCQP_HIP_TRY(hipMemcpy(status, d_st, B * 4, hipMemcpyDeviceToHost));
-    if (active) WCQP_HIP_TRY(hipMemcpy(active, d_ac, B * 4, hipMemcpyDeviceToHost));
-    if (margin) WCQP_HIP_TRY(hipMemcpy(margin, d + o_mg, B * 8, hipMemcpyDeviceToHost));
-    return WCQP_OK;
+    rc = wcqp_mpc_solve_device(h, batch, st[d_x0], st[d_ref], ref_len, st[d_up], st[d_hA], st[d_hb], st[d_nc],
+                               st[d_u0], st[d_st], st[d_ac], st[d_mg], nullptr);
+    return rc != WCQP_OK ? rc : st.download();
 }
 
 }  // extern "C"

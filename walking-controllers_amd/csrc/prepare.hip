@@ -199,17 +199,22 @@ struct wcqp_prepare_s {
 namespace {
 int ensure_device(wcqp_prepare_s* h) {
     if (h->d_tab) return WCQP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        std::fprintf(stderr, "[wcqp] no HIP device: the prepare kernel has no CPU fallback\n");
-        return WCQP_E_HIP;
-    }
+    if (const int rc = wcqp::require_device("prepare kernel"); rc != WCQP_OK) return rc;
     const size_t nt = h->tab.size(), np = h->par.size();
     WCQP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_tab), (nt + np) * sizeof(double)));
     WCQP_HIP_TRY(hipMemcpy(h->d_tab, h->tab.data(), nt * sizeof(double), hipMemcpyHostToDevice));
     WCQP_HIP_TRY(hipMemcpy(h->d_tab + nt, h->par.data(), np * sizeof(double), hipMemcpyHostToDevice));
     h->dev.kin_tab = h->d_tab;
     h->dev.par = h->d_tab + nt;
+    return WCQP_OK;
+}
+
+// what both forms of wcqp_prepare_solve_* refuse before they look for a device
+int check_call(wcqp_prepare_t h, int32_t batch, const double* left_d, const double* right_d, const double* com_d, const double* q_guess,
+               const double* q, const int32_t* status) {
+    if (!h || batch < 0) return WCQP_E_INVALID;
+    if (!left_d || !right_d || !com_d || !q_guess || !q || !status) return WCQP_E_INVALID;
+    if (!wcqp::fits32(batch, kStateLen * 8)) return WCQP_E_UNSUPPORTED;
     return WCQP_OK;
 }
 }  // namespace
@@ -284,11 +289,9 @@ int wcqp_prepare_destroy(wcqp_prepare_t h) {
 int wcqp_prepare_solve_device(wcqp_prepare_t h, int32_t batch, const double* left_d, const double* right_d, const double* com_d,
                               const double* Rd_neck, const double* q_guess,
                               double* q, double* base, double* state, int32_t* status, int32_t* iters, double* residual, void* stream) {
-    if (!h || batch < 0) return WCQP_E_INVALID;
-    if (!left_d || !right_d || !com_d || !q_guess || !q || !status) return WCQP_E_INVALID;
-    if (!wcqp::fits32(batch, kStateLen * 8)) return WCQP_E_UNSUPPORTED;
-    if (batch == 0) return WCQP_OK;
-    const int rc = ensure_device(h);
+    int rc = check_call(h, batch, left_d, right_d, com_d, q_guess, q, status);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     PrepDev a = h->dev;
     a.batch = batch;
@@ -302,35 +305,21 @@ int wcqp_prepare_solve_device(wcqp_prepare_t h, int32_t batch, const double* lef
 int wcqp_prepare_solve_host(wcqp_prepare_t h, int32_t batch, const double* left_d, const double* right_d, const double* com_d,
                             const double* Rd_neck, const double* q_guess,
                             double* q, double* base, double* state, int32_t* status, int32_t* iters, double* residual) {
-    if (!h || batch < 0) return WCQP_E_INVALID;
-    if (!left_d || !right_d || !com_d || !q_guess || !q || !status) return WCQP_E_INVALID;
-    if (!wcqp::fits32(batch, kStateLen * 8)) return WCQP_E_UNSUPPORTED;
-    if (batch == 0) return WCQP_OK;
-    int rc = ensure_device(h);
+    int rc = check_call(h, batch, left_d, right_d, com_d, q_guess, q, status);
+    if (rc != WCQP_OK || batch == 0) return rc;
+    rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     const size_t B = (size_t)batch;
-    const size_t o_l = 0, o_r = o_l + B * 12, o_c = o_r + B * 12, o_n = o_c + B * 3, o_g = o_n + B * 9, o_q = o_g + B * kDof, o_b = o_q + B * kDof,
-                 o_s = o_b + B * 12, o_res = o_s + B * kStateLen, o_st = o_res + B * 2, total = o_st + B;     // status | iters: B ints each
-    rc = h->scratch.reserve(total * sizeof(double));
+    wcqp::HostStage st;
+    const auto d_l = st.in(left_d, B * 12), d_r = st.in(right_d, B * 12), d_c = st.in(com_d, B * 3);
+    const auto d_n = st.in(Rd_neck, B * 9, /*no neck task without it*/ true), d_g = st.in(q_guess, B * kDof);
+    const auto d_q = st.out(q, B * kDof), d_b = st.out(base, B * 12), d_s = st.out(state, B * kStateLen), d_res = st.out(residual, B * 2);
+    const auto d_st = st.out(status, B), d_it = st.out(iters, B);
+    rc = st.upload(h->scratch);
     if (rc != WCQP_OK) return rc;
-    double* d = static_cast<double*>(h->scratch.ptr);
-    int32_t* di = reinterpret_cast<int32_t*>(d + o_st);
-    WCQP_HIP_TRY(hipMemcpy(d + o_l, left_d, B * 12 * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_r, right_d, B * 12 * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_c, com_d, B * 3 * 8, hipMemcpyHostToDevice));
-    if (Rd_neck) WCQP_HIP_TRY(hipMemcpy(d + o_n, Rd_neck, B * 9 * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_g, q_guess, B * kDof * 8, hipMemcpyHostToDevice));
-    rc = wcqp_prepare_solve_device(h, batch, d + o_l, d + o_r, d + o_c, Rd_neck ? d + o_n : nullptr, d + o_g,
-                                   d + o_q, d + o_b, d + o_s, di, di + B, d + o_res, nullptr);
-    if (rc != WCQP_OK) return rc;
-    WCQP_HIP_TRY(hipDeviceSynchronize());
-    WCQP_HIP_TRY(hipMemcpy(q, d + o_q, B * kDof * 8, hipMemcpyDeviceToHost));
-    if (base) WCQP_HIP_TRY(hipMemcpy(base, d + o_b, B * 12 * 8, hipMemcpyDeviceToHost));
-    if (state) WCQP_HIP_TRY(hipMemcpy(state, d + o_s, B * kStateLen * 8, hipMemcpyDeviceToHost));
-    WCQP_HIP_TRY(hipMemcpy(status, di, B * 4, hipMemcpyDeviceToHost));
-    if (iters) WCQP_HIP_TRY(hipMemcpy(iters, di + B, B * 4, hipMemcpyDeviceToHost));
-    if (residual) WCQP_HIP_TRY(hipMemcpy(residual, d + o_res, B * 2 * 8, hipMemcpyDeviceToHost));
-    return WCQP_OK;
+    rc = wcqp_prepare_solve_device(h, batch, st[d_l], st[d_r], st[d_c], st[d_n], st[d_g],
+                                   st[d_q], st[d_b], st[d_s], st[d_st], st[d_it], st[d_res], nullptr);
+    return rc != WCQP_OK ? rc : st.download();
 }
 
 }  // extern "C"

@@ -187,6 +187,22 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
     return WCQP_OK;
 }
 
+// The staging rows of wcqp_tick_set_feedback_host and of wcqp_tick_set_sensor_feedback_host, each array named once: the call lays out
+// the caller's arrays, wcqp_tick_create the same rows with every array present (wcqp::stage_sizing) for the block's capacity
+struct FeedbackStage {
+    wcqp::HostStage st;
+    wcqp::StageSlot<double> dcm, com, zmp, q;
+    FeedbackStage(size_t B, const double* dcm_meas, const double* com_meas, const double* zmp_meas, const double* q_meas)
+        : dcm(st.in(dcm_meas, B * 2)), com(st.in(com_meas, B * 2)), zmp(st.in(zmp_meas, B * 2)),
+          q(st.in(q_meas, B * kDof, /*the joints are not fed back without it*/ true)) {}
+};
+struct SensorStage {
+    wcqp::HostStage st;
+    wcqp::StageSlot<double> q, dq, wl, wr;
+    SensorStage(size_t B, const double* q_meas, const double* dq_meas, const double* wrench_left, const double* wrench_right)
+        : q(st.in(q_meas, B * kDof)), dq(st.in(dq_meas, B * kDof)), wl(st.in(wrench_left, B * 6)), wr(st.in(wrench_right, B * 6)) {}
+};
+
 }  // namespace
 
 extern "C" {
@@ -250,11 +266,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (!wcqp::fits32(params->batch, ((long long)params->max_ticks + (params->mpc.horizon > 0 ? params->mpc.horizon : 0) + 1) * 16) ||
         !wcqp::fits32(2ll * params->batch, kHandLen * 8) || !wcqp::ik_batch_fits32(params->batch))
         return WCQP_E_UNSUPPORTED;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        std::fprintf(stderr, "[wcqp] no HIP device: the tick pipeline has no CPU fallback\n");
-        return WCQP_E_HIP;
-    }
+    if (const int rcd = wcqp::require_device("tick pipeline"); rcd != WCQP_OK) return rcd;
     wcqp_tick_s* h = new (std::nothrow) wcqp_tick_s();
     if (!h) return WCQP_E_NOMEM;
     h->p = *params;
@@ -315,6 +327,8 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     int *hn = nullptr, *ph = nullptr;
     rc = WCQP_OK;
 #define A_(ptr, n) if (rc == WCQP_OK) rc = dev_alloc(h, &(ptr), (n))
+#define STAGE_(blk, bytes) do { (blk).cap = (bytes); A_((blk).ptr, (blk).cap); } while (0)      // a host form's staging rows, sized by its layout
+    const double* const any = wcqp::stage_sizing<double>();
     const size_t hsets = 3;       // rows for {left, right, both} in contact: uploaded, or (kinematics mode) built at upload from the desired foot poses
     A_(ref, B * d.traj_len * 2); A_(hA, B * hsets * 16); A_(hb, B * hsets * 8); A_(hn, B * hsets); A_(ph, B); A_(sw, B * 6);
     A_(d.dcm, B * 2); A_(d.com, B * 2); A_(d.zmp_meas, B * 2); A_(d.u_prev, B * 2); A_(d.u0, B * 2);
@@ -342,9 +356,9 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     // external feedback: the default (base-eliminated) kernel with constant Jacobians or fused kinematics, without logger rows
     if (h->external && (!d.skew || params->logger_ticks > 0 || (h->kin && !fusedk))) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }
     if ((planned || streamed) && (!d.skew || !fusedk)) { wcqp_tick_destroy(h); return WCQP_E_UNSUPPORTED; }      // (checked above, before any allocation)
-    if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; A_(h->fb_stage, B * (6 + kDof)); A_(h->feedback_fail, B); }
+    if (h->external) { A_(h->q_meas, B * kDof); d.q_meas = h->q_meas; STAGE_(h->fb_stage, FeedbackStage(B, any, any, any, any).st.total); A_(h->feedback_fail, B); }
     if (h->external && h->kin) {
-        A_(h->sens_stage, B * (2 * kDof + 12));
+        STAGE_(h->sens_stage, SensorStage(B, any, any, any, any).st.total);
         if (rc == WCQP_OK && hipEventCreateWithFlags(&h->run.done, hipEventDisableTiming) != hipSuccess) rc = WCQP_E_HIP;
         if (filt_mask) {
             A_(h->filt_state, 2 * B * kFiltRec);
@@ -372,7 +386,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
     if (streamed) {
         // one record and one row set per robot, the pairs, the host form's staging rows
         A_(h->st_rec, B * kPlanRec); A_(h->st_set_A, B * 16); A_(h->st_set_b, B * 8); A_(h->st_set_nc, B); A_(h->st_pair, B * 2);
-        A_(h->des_stage, B * 38 + (B + 7) / 8);
+        STAGE_(h->des_stage, wcqp::desired_stage_bytes(B));
         h->streamed = true;
         h->pl.rec = h->st_rec; h->pl.set_A = h->st_set_A; h->pl.set_b = h->st_set_b; h->pl.set_nc = h->st_set_nc;
         for (int k = 0; k < 9; ++k) h->pl.neck_add[k] = params->neck_additional_rotation[k];
@@ -405,6 +419,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
         a.alo = h->ik_lo; a.aup = h->ik_up;
         h->position = true;
     }
+#undef STAGE_
 #undef A_
     if (rc != WCQP_OK) { wcqp_tick_destroy(h); return rc; }
     wcqp::mpc_device_consts(h->mpc, &d.mpc);
@@ -637,15 +652,11 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
 
 int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const double* com_meas, const double* zmp_meas, const double* q_meas) {
     if (const int rc = feedback_ready(h, dcm_meas, com_meas, zmp_meas); rc != WCQP_OK) return rc;
-    const size_t B = (size_t)h->d.batch;
-    double* st = h->fb_stage;
+    FeedbackStage s((size_t)h->d.batch, dcm_meas, com_meas, zmp_meas, q_meas);
     // (synchronous copies on the NULL stream: they wait for what the handle's last tick left running on a blocking stream, and the
     // host arrays are consumed when they return)
-    WCQP_HIP_TRY(hipMemcpy(st, dcm_meas, B * 16, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 2 * B, com_meas, B * 16, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 4 * B, zmp_meas, B * 16, hipMemcpyHostToDevice));
-    if (q_meas) WCQP_HIP_TRY(hipMemcpy(st + 6 * B, q_meas, B * kDof * 8, hipMemcpyHostToDevice));
-    const int rc = wcqp_tick_set_feedback_device(h, st, st + 2 * B, st + 4 * B, q_meas ? st + 6 * B : nullptr, nullptr);
+    int rc = s.st.upload(h->fb_stage.ptr, h->fb_stage.cap);
+    if (rc == WCQP_OK) rc = wcqp_tick_set_feedback_device(h, s.st[s.dcm], s.st[s.com], s.st[s.zmp], s.st[s.q], nullptr);
     if (rc != WCQP_OK) return rc;
     // the copy kernel ran on the NULL stream; the tick that consumes the feedback may be enqueued on ANY stream - a non-blocking one
     // (wcqp_stream_create) would not wait for it - so the feedback is in place when this call returns, and the staging rows are free
@@ -688,15 +699,11 @@ int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, co
 int wcqp_tick_set_sensor_feedback_host(wcqp_tick_t h, const double* q_meas, const double* dq_meas, const double* wrench_left,
                                        const double* wrench_right) {
     if (const int rc = sensor_feedback_ready(h, q_meas, dq_meas, wrench_left, wrench_right); rc != WCQP_OK) return rc;
-    const size_t B = (size_t)h->d.batch;
     // the last run may have been enqueued on a non-blocking stream, which the NULL stream below does not wait for: wait for its end
     if (const int rc = h->run.wait(); rc != WCQP_OK) return rc;
-    double* st = h->sens_stage;
-    WCQP_HIP_TRY(hipMemcpy(st, q_meas, B * kDof * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + B * kDof, dq_meas, B * kDof * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 2 * B * kDof, wrench_left, B * 48, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 2 * B * kDof + 6 * B, wrench_right, B * 48, hipMemcpyHostToDevice));
-    const int rc = wcqp_tick_set_sensor_feedback_device(h, st, st + B * kDof, st + 2 * B * kDof, st + 2 * B * kDof + 6 * B, nullptr);
+    SensorStage s((size_t)h->d.batch, q_meas, dq_meas, wrench_left, wrench_right);
+    int rc = s.st.upload(h->sens_stage.ptr, h->sens_stage.cap);
+    if (rc == WCQP_OK) rc = wcqp_tick_set_sensor_feedback_device(h, s.st[s.q], s.st[s.dq], s.st[s.wl], s.st[s.wr], nullptr);
     if (rc != WCQP_OK) return rc;
     // in place when this call returns: the tick may be enqueued on any stream, and the staging rows are free for the next call
     WCQP_HIP_TRY(hipStreamSynchronize(nullptr));

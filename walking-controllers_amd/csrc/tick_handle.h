@@ -48,6 +48,13 @@ struct StagedBlock {
     }
 };
 
+// A device block of fixed capacity that takes a host form's arrays (wcqp::HostStage::upload(ptr, cap)): wcqp_tick_create sizes it by the
+// stage's own layout with every optional array present, so a call's layout always fits - and one that did not would be refused, not written
+struct FixedStage {
+    char* ptr = nullptr;
+    size_t cap = 0;
+};
+
 struct wcqp_tick_s {
     wcqp_tick_params p{};
     wcqp_mpc_t mpc = nullptr;
@@ -77,10 +84,10 @@ struct wcqp_tick_s {
     bool vel_explicit = false;    // uploaded with an explicit dcm_vel_traj (reactive controller): the splice has no velocity tail
     bool external = false, feedback_set = false;     // wcqp_tick_params.plant = EXTERNAL: one tick per run call, each behind a set_feedback
     double* q_meas = nullptr;
-    double* fb_stage = nullptr;   // wcqp_tick_set_feedback_host: [B][2 + 2 + 2 + dof]
-    // sensor feedback (EXTERNAL with kinematics, wcqp_tick_set_sensor_feedback_*): the host form's staging rows [B][dof + dof + 6 + 6],
+    FixedStage fb_stage;          // wcqp_tick_set_feedback_host's staging rows (FeedbackStage, tick.hip)
+    // sensor feedback (EXTERNAL with kinematics, wcqp_tick_set_sensor_feedback_*): the host form's staging rows (SensorStage, tick.hip),
     // the rejection counter, and the guard each run records on its stream (no block: the host forms wait for it before they stage)
-    double* sens_stage = nullptr;
+    FixedStage sens_stage;
     long long* feedback_fail = nullptr;
     StagedBlock run;
     // the sensor form's low-pass filters (wcqp_tick_params.*_cut_frequency; sensors.h): two slots of per-robot state [2][B][kFiltRec].  A
@@ -117,7 +124,7 @@ struct wcqp_tick_s {
     bool streamed = false, desired_set = false;
     double* st_rec = nullptr; double* st_set_A = nullptr; double* st_set_b = nullptr; int* st_set_nc = nullptr;
     int* st_pair = nullptr;       // [B][2] contact pair of the last consumed stage / of the stage in hand (tick_desired_kernel)
-    double* des_stage = nullptr;  // wcqp_tick_set_desired_host: [B][12 + 12 + 6 + 6 + 1 + 1] doubles, then [B] bytes
+    FixedStage des_stage;         // wcqp_tick_set_desired_host's staging rows (DesiredStage, tick_plan.hip)
     wcqp_tick::TickDevPL dpl(const wcqp_tick::TickDev& base) const { wcqp_tick::TickDevPL g; static_cast<wcqp_tick::TickDevGS&>(g) = dgs(base); g.pl = pl; return g; }
     // ik_mode = POSITION (a planned handle): the non-linear IK runs every tick in position_tick_kernel, which takes `pos` beside the
     // handle's TickDevPL in device memory; the chain's state, hand-off rows and live hull rows are the skewed handle's, but nothing is
@@ -147,4 +154,6 @@ int upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in);
 // tick.hip, the tail wcqp_tick_upload and wcqp_tick_upload_footsteps share once the trajectories are in place (pair0 >= 0: the contact
 // pair of stage 0 where `in` holds no contact array)
 int upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0);
+// tick_plan.hip, for wcqp_tick_create: the bytes of wcqp_tick_set_desired_host's staging rows with every optional array present
+size_t desired_stage_bytes(size_t batch);
 }  // namespace wcqp

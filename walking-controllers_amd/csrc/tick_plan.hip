@@ -484,6 +484,17 @@ int wcqp_tick_set_desired_device(wcqp_tick_t h, const wcqp_tick_desired* des, vo
     return WCQP_OK;
 }
 
+// wcqp_tick_set_desired_host's staging rows, each array named once (the call's layout, and the capacity wcqp_tick_create gives the block)
+struct DesiredStage {
+    wcqp::HostStage st;
+    wcqp::StageSlot<double> lp, rp, lt, rt, ch, chv;
+    wcqp::StageSlot<uint8_t> contact;
+    DesiredStage(size_t B, const wcqp_tick_desired& des)
+        : lp(st.in(des.left_pose, B * 12)), rp(st.in(des.right_pose, B * 12)), lt(st.in(des.left_twist, B * 6)), rt(st.in(des.right_twist, B * 6)),
+          ch(st.in(des.com_height, B, /*the handle's constant height without it*/ true)), chv(st.in(des.com_height_vel, B, true)),
+          contact(st.in(des.contact, B)) {}
+};
+
 int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* des) {
     if (const int rc = desired_ready(h, des); rc != WCQP_OK) return rc;
     const size_t B = (size_t)h->d.batch;
@@ -494,19 +505,13 @@ int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* des) {
             return WCQP_E_INVALID;
     // the last run may have been enqueued on a non-blocking stream, which the NULL stream below does not wait for: wait for its end
     if (const int rc = h->run.wait(); rc != WCQP_OK) return rc;
-    double* st = h->des_stage;
+    DesiredStage s(B, *des);
+    int rc = s.st.upload(h->des_stage.ptr, h->des_stage.cap);
+    if (rc != WCQP_OK) return rc;
     wcqp_tick_desired dv{};
-    dv.left_pose = st; dv.right_pose = st + 12 * B; dv.left_twist = st + 24 * B; dv.right_twist = st + 30 * B;
-    dv.com_height = des->com_height ? st + 36 * B : nullptr; dv.com_height_vel = des->com_height_vel ? st + 37 * B : nullptr;
-    dv.contact = reinterpret_cast<const uint8_t*>(st + 38 * B);
-    WCQP_HIP_TRY(hipMemcpy(st, des->left_pose, B * 96, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 12 * B, des->right_pose, B * 96, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 24 * B, des->left_twist, B * 48, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 30 * B, des->right_twist, B * 48, hipMemcpyHostToDevice));
-    if (des->com_height) WCQP_HIP_TRY(hipMemcpy(st + 36 * B, des->com_height, B * 8, hipMemcpyHostToDevice));
-    if (des->com_height_vel) WCQP_HIP_TRY(hipMemcpy(st + 37 * B, des->com_height_vel, B * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(st + 38 * B, des->contact, B, hipMemcpyHostToDevice));
-    const int rc = wcqp_tick_set_desired_device(h, &dv, nullptr);
+    dv.left_pose = s.st[s.lp]; dv.right_pose = s.st[s.rp]; dv.left_twist = s.st[s.lt]; dv.right_twist = s.st[s.rt];
+    dv.com_height = s.st[s.ch]; dv.com_height_vel = s.st[s.chv]; dv.contact = s.st[s.contact];
+    rc = wcqp_tick_set_desired_device(h, &dv, nullptr);
     if (rc != WCQP_OK) return rc;
     // in place when this call returns: the tick may be enqueued on any stream, and the staging rows are free for the next call
     WCQP_HIP_TRY(hipStreamSynchronize(nullptr));
@@ -514,3 +519,11 @@ int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* des) {
 }
 
 }  // extern "C"
+
+namespace wcqp {
+size_t desired_stage_bytes(size_t batch) {
+    const double* const d = stage_sizing<double>();
+    const wcqp_tick_desired all{d, d, d, d, stage_sizing<uint8_t>(), d, d};
+    return DesiredStage(batch, all).st.total;
+}
+}  // namespace wcqp

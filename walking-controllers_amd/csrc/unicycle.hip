@@ -161,11 +161,7 @@ namespace {
 
 int ensure_device(wcqp_unicycle_s* h) {
     if (h->device_seen) return WCQP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        std::fprintf(stderr, "[wcqp] no HIP device: the unicycle planner has no CPU fallback\n");
-        return WCQP_E_HIP;
-    }
+    if (const int rc = wcqp::require_device("unicycle planner"); rc != WCQP_OK) return rc;
     h->device_seen = true;
     return WCQP_OK;
 }
@@ -247,32 +243,19 @@ int wcqp_unicycle_plan_host(wcqp_unicycle_t h, int32_t batch, const wcqp_unicycl
     if (batch == 0) return WCQP_OK;
     rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
-    // doubles first, then the 32-bit rows, then the bytes
-    const size_t o_l = 0, o_r = o_l + B * 12, o_g = o_r + B * 12, o_t = o_g + B * 2, o_dp = o_t + B * K * 3, o_ue = o_dp + B * 2, n_d = o_ue + B * 3;
-    const size_t bytes = n_d * 8 + 2 * B * 4 + B + B * K;
-    rc = h->scratch.reserve(bytes);
+    // doubles first, then the 32-bit rows, then the bytes; no step rows at all when the planner keeps none (K = 0)
+    wcqp::HostStage st;
+    const auto d_l = st.in(in->left0, B * 12), d_r = st.in(in->right0, B * 12), d_g = st.in(in->goal, B * 2);
+    const auto d_t = st.out(out->target, B * K * 3, true), d_dp = st.out(out->desired_point, B * 2), d_ue = st.out(out->unicycle_end, B * 3);
+    const auto d_n = st.out(out->n_steps, B), d_st = st.out(out->status, B);
+    const auto d_fs = st.in(in->first_side, B);
+    const auto d_sd = st.out(out->side, B * K, true);
+    rc = st.upload(h->scratch);
     if (rc != WCQP_OK) return rc;
-    double* d = static_cast<double*>(h->scratch.ptr);
-    int32_t* di = reinterpret_cast<int32_t*>(d + n_d);
-    uint8_t* db = reinterpret_cast<uint8_t*>(di + 2 * B);
-    WCQP_HIP_TRY(hipMemcpy(d + o_l, in->left0, B * 12 * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_r, in->right0, B * 12 * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(d + o_g, in->goal, B * 2 * 8, hipMemcpyHostToDevice));
-    WCQP_HIP_TRY(hipMemcpy(db, in->first_side, B, hipMemcpyHostToDevice));
-    wcqp_unicycle_inputs din{d + o_l, d + o_r, d + o_g, db};
-    wcqp_unicycle_outputs dout{di, K ? db + B : nullptr, K ? d + o_t : nullptr, di + B, d + o_dp, d + o_ue};
+    const wcqp_unicycle_inputs din{st[d_l], st[d_r], st[d_g], st[d_fs]};
+    const wcqp_unicycle_outputs dout{st[d_n], st[d_sd], st[d_t], st[d_st], st[d_dp], st[d_ue]};
     rc = wcqp_unicycle_plan_device(h, batch, &din, &dout, nullptr);
-    if (rc != WCQP_OK) return rc;
-    WCQP_HIP_TRY(hipDeviceSynchronize());
-    WCQP_HIP_TRY(hipMemcpy(out->n_steps, di, B * 4, hipMemcpyDeviceToHost));
-    WCQP_HIP_TRY(hipMemcpy(out->status, di + B, B * 4, hipMemcpyDeviceToHost));
-    if (K) {
-        WCQP_HIP_TRY(hipMemcpy(out->side, db + B, B * K, hipMemcpyDeviceToHost));
-        WCQP_HIP_TRY(hipMemcpy(out->target, d + o_t, B * K * 3 * 8, hipMemcpyDeviceToHost));
-    }
-    if (out->desired_point) WCQP_HIP_TRY(hipMemcpy(out->desired_point, d + o_dp, B * 2 * 8, hipMemcpyDeviceToHost));
-    if (out->unicycle_end) WCQP_HIP_TRY(hipMemcpy(out->unicycle_end, d + o_ue, B * 3 * 8, hipMemcpyDeviceToHost));
-    return WCQP_OK;
+    return rc != WCQP_OK ? rc : st.download();
 }
 
 }  // extern "C"

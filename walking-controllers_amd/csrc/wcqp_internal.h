@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <vector>
 #include "wcqp.h"
+#include "host_stage.h"
 
 #define WCQP_HIP_TRY(expr)                                                         \
     do {                                                                           \
@@ -42,6 +43,18 @@ struct DeviceScratch {
     int reserve(size_t bytes);
     void release();
 };
+
+// The arrays of a *_host entry point, each named once (host_stage.h), and their copies.  upload() takes the block - the handle's
+// growable one, or one of fixed capacity, which a layout that does not fit leaves untouched (WCQP_E_INVALID) - and copies every
+// input in; st[slot] is then the device pointer; download() waits for the device and copies out every output the caller wants.
+struct HostStage : StageLayout {
+    int upload(DeviceScratch& block);
+    int upload(void* block, size_t capacity);
+    int download() const;
+};
+
+// "[wcqp] no HIP device: the <what> has no CPU fallback" on stderr and WCQP_E_HIP, unless there is a device
+int require_device(const char* what);
 
 // internal launch of the MPC kernel with a strided / offset reference window (tick pipeline)
 int mpc_enqueue(wcqp_mpc_t h, int batch, const double* x0, const double* ref, int ref_len, int ref_stride,
