@@ -786,6 +786,29 @@ typedef struct wcqp_tick_outputs {  /* HOST pointers, any may be NULL */
 
 typedef struct wcqp_tick_s* wcqp_tick_t;
 int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out);
+/* Parameters added after wcqp_tick_params was closed (its layout, last fields included, is pinned): they travel in a struct of their own
+ * that only grows at its end, beside the unchanged wcqp_tick_params.  wcqp_tick_create(p, out) is wcqp_tick_create_ext(p, NULL, out).
+ *
+ * resident_plan (0 = off: every handle behaves as before, bit for bit).  A capability of a streamed handle (streamed_trajectories = 1,
+ * hence the EXTERNAL plant): the handle additionally HOLDS the plan arrays of a planned handle - the records [B][T][40] (320 B per robot
+ * and stage, T = max_ticks + horizon + 1), the plan's support-polygon row sets, and ref_traj / dcm_vel as it does already - and
+ * wcqp_tick_set_desired_from_plan stages tick t's stage out of them on the device, in the place of a wcqp_tick_set_desired_* call.  The
+ * tick, its prime launch and the sensor form run what they run on any streamed handle: they read the robot's one live record.
+ *   - wcqp_tick_upload_footsteps, wcqp_tick_upload WITH the planned arrays (left_traj ... com_height_vel; required on such a handle, by
+ *     the rules of a planned handle's upload), wcqp_tick_replan_footsteps and wcqp_tick_get_plan work as on a planned handle, through
+ *     the same code; without resident_plan they stay refused on a streamed handle (WCQP_E_UNSUPPORTED).
+ *   - Order per tick: wcqp_tick_set_desired_from_plan (it counts as a wcqp_tick_set_desired_*) -> wcqp_tick_set_sensor_feedback_* or
+ *     wcqp_tick_set_feedback_* -> wcqp_tick_run(h, 1, ...).  A later wcqp_tick_set_desired_* before the run replaces the stage, as a
+ *     second one does today; a second wcqp_tick_set_desired_from_plan restages it.
+ *   - Replan rule: a tick whose stage has been staged from the plan counts as enqueued - wcqp_tick_replan_footsteps after tick t was
+ *     staged needs merge_stage[i] >= t + 1 (WCQP_E_INVALID otherwise, the handle unchanged).
+ * wcqp_tick_create_ext returns WCQP_E_INVALID for a value other than 0 / 1 and WCQP_E_UNSUPPORTED, before anything touches the device, for
+ * resident_plan = 1 without streamed_trajectories; every refusal of a streamed handle stays (planned_trajectories = 1 with the EXTERNAL
+ * plant or together with streamed_trajectories among them). */
+typedef struct wcqp_tick_params_ext {
+    int32_t resident_plan;
+} wcqp_tick_params_ext;
+int wcqp_tick_create_ext(const wcqp_tick_params* params, const wcqp_tick_params_ext* ext, wcqp_tick_t* out);      /* ext NULL: all zero */
 int wcqp_tick_destroy(wcqp_tick_t h);
 /* also rewinds to tick 0.  Non-finite inputs: WCQP_E_INVALID, before anything of the handle changes, for a NaN or an Inf in ref_traj,
  * dcm_vel_traj (where it is read), dcm0, com0, u_init or q0 - of any robot: such a value would enter that robot's state on the first tick
@@ -995,6 +1018,13 @@ int wcqp_tick_set_desired_device(wcqp_tick_t h, const wcqp_tick_desired* desired
  * device memory the handle allocated at create, and IN PLACE when the call returns - it first waits for the handle's last wcqp_tick_run,
  * whatever stream that named; the host arrays may be released at once and the tick may run on any stream. */
 int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* desired);
+/* A resident plan (wcqp_tick_params_ext.resident_plan, which states the order and the replan rule): ONE kernel on `stream` that stages, for
+ * every robot, stage t of the plan the handle holds as the desired stage of the next tick - its record into the robot's live record, the
+ * row set the record names into the robot's own.  t = the ticks run since the last upload, read by the kernel from the handle's tick
+ * index in device memory: enqueue-only, in stream order behind the ticks already enqueued on `stream`.  Nothing is validated (the upload
+ * validated the plan) and no hull is built.  WCQP_E_UNSUPPORTED on a handle without resident_plan; WCQP_E_INVALID before a plan has
+ * been uploaded or when t has reached max_ticks. */
+int wcqp_tick_set_desired_from_plan(wcqp_tick_t h, void* stream);
 int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out);             /* synchronises     */
 
 /* The form a tick handle actually took at wcqp_tick_create (the route follows the IK algorithm, the kinematics hand-off and the
@@ -1013,6 +1043,11 @@ typedef struct wcqp_tick_info {
     int32_t ik_mode;               /* wcqp_tick_params.ik_mode as taken (WCQP_TICK_IK_*)                                            */
 } wcqp_tick_info;
 int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out);
+/* ... and what it took of wcqp_tick_params_ext - a struct of its own for the same reason: it only grows at its end */
+typedef struct wcqp_tick_info_ext {
+    int32_t resident_plan;         /* wcqp_tick_params_ext.resident_plan as taken (0 / 1)                                           */
+} wcqp_tick_info_ext;
+int wcqp_tick_get_info_ext(wcqp_tick_t h, wcqp_tick_info_ext* out);
 
 /* =====================================================================================
  * Footsteps from per-robot goals: the unicycle planner.  "Robot i, go there" - the reference's setGoal(x, y):

@@ -36,10 +36,10 @@ ABI_SYMBOLS = (
     "wcqp_hull_from_feet_device", "wcqp_hull_from_feet_host",
     "wcqp_kin_create", "wcqp_kin_destroy", "wcqp_kin_jacobians_device", "wcqp_kin_jacobians_host",
     "wcqp_prepare_create", "wcqp_prepare_destroy", "wcqp_prepare_solve_device", "wcqp_prepare_solve_host",
-    "wcqp_tick_create", "wcqp_tick_destroy", "wcqp_tick_upload", "wcqp_tick_run", "wcqp_tick_download", "wcqp_tick_splice_reference",
+    "wcqp_tick_create", "wcqp_tick_create_ext", "wcqp_tick_get_info_ext", "wcqp_tick_destroy", "wcqp_tick_upload", "wcqp_tick_run", "wcqp_tick_download", "wcqp_tick_splice_reference",
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
-    "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host",
+    "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
     "wcqp_tick_upload_footsteps", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
@@ -186,6 +186,11 @@ class TickParams(C.Structure):
                 ("ik_mode", C.c_int32), ("position_ik", PrepareParams)]
 
 
+class TickParamsExt(C.Structure):
+    """wcqp_tick_params_ext: the parameters added since wcqp_tick_params was closed (wcqp_tick_create_ext)."""
+    _fields_ = [("resident_plan", C.c_int32)]
+
+
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
 TICK_IK_VELOCITY, TICK_IK_POSITION = 0, 1
 POSITION_IK_DEFAULTS = dict(q_reg=None, w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=30, q_min=None, q_max=None)
@@ -196,6 +201,11 @@ class TickInfo(C.Structure):
     _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32),
                 ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32), ("streamed_trajectories", C.c_int32),
                 ("sensor_filters", C.c_int32), ("plan_generated", C.c_int32), ("plan_record_ms", C.c_double), ("ik_mode", C.c_int32)]
+
+
+class TickInfoExt(C.Structure):
+    """wcqp_tick_info_ext: what the handle took of wcqp_tick_params_ext (wcqp_tick_get_info_ext)."""
+    _fields_ = [("resident_plan", C.c_int32)]
 
 
 SENSOR_FILTERS = ("joint_velocity", "wrench", "com")      # bit k of wcqp_tick_info.sensor_filters
@@ -303,6 +313,8 @@ def lib() -> C.CDLL:
         L.wcqp_prepare_solve_device.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 12
         L.wcqp_prepare_solve_host.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 11
         L.wcqp_tick_create.argtypes = [C.POINTER(TickParams), C.POINTER(C.c_void_p)]
+        L.wcqp_tick_create_ext.argtypes = [C.POINTER(TickParams), C.POINTER(TickParamsExt), C.POINTER(C.c_void_p)]
+        L.wcqp_tick_get_info_ext.argtypes = [C.c_void_p, C.POINTER(TickInfoExt)]
         L.wcqp_tick_destroy.argtypes = [C.c_void_p]
         L.wcqp_tick_upload.argtypes = [C.c_void_p, C.POINTER(TickInputs)]
         L.wcqp_tick_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
@@ -314,6 +326,7 @@ def lib() -> C.CDLL:
         L.wcqp_tick_set_sensor_feedback_host.argtypes = [C.c_void_p] * 5
         L.wcqp_tick_set_desired_device.argtypes = [C.c_void_p, C.POINTER(TickDesired), C.c_void_p]
         L.wcqp_tick_set_desired_host.argtypes = [C.c_void_p, C.POINTER(TickDesired)]
+        L.wcqp_tick_set_desired_from_plan.argtypes = [C.c_void_p, C.c_void_p]
         L.wcqp_tick_get_info.argtypes = [C.c_void_p, C.POINTER(TickInfo)]
         L.wcqp_tick_upload_footsteps.argtypes = [C.c_void_p, C.POINTER(TickInputs), C.POINTER(TickFootsteps)]
         L.wcqp_tick_get_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TickPlanWindow)]
@@ -667,7 +680,8 @@ class TickPipeline:
                  dcm_controller: str = "mpc", k_dcm: Optional[float] = None, zmp_gain_scheduling: bool = False,
                  k_com_stance: Optional[float] = None, k_zmp_stance: Optional[float] = None, zmp_smoothing_time: Optional[float] = None,
                  planned_trajectories: bool = False, neck_additional_rotation=None, streamed_trajectories: bool = False,
-                 sensor_filters: Optional[dict] = None, ik_mode: str = "velocity", position_ik: Optional[dict] = None):
+                 sensor_filters: Optional[dict] = None, ik_mode: str = "velocity", position_ik: Optional[dict] = None,
+                 resident_plan: bool = False):
         """kin: a KinModel -> per-tick kinematics (Jacobians, actual poses and hull rows rebuilt every tick from the
         integrated joint state with the base anchored at the stance foot; upload() then ignores J_* / hull_tab_*).
         dcm_controller: "mpc" (the DCM-MPC, the reference's use_mpc 1) or "reactive" (WalkingDCMReactiveController, the
@@ -685,7 +699,13 @@ class TickPipeline:
         reference's use_QP-IK 0: the non-linear IK of PrepareSolver every tick, hot-started at the previous tick's joints - a mode of a
         planned handle).  position_ik: dict(q_reg=..., w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=30,
         q_min=None, q_max=None) - the problem's parameters, max_iter the budget PER TICK; q_reg [dof] in rad is required.  `ik` then only
-        supplies dof.  download() of such a handle returns q_log [log_ticks][B][dof] and ik_iters [B], and no dq_log."""
+        supplies dof.  download() of such a handle returns q_log [log_ticks][B][dof] and ik_iters [B], and no dq_log.
+        resident_plan (with streamed_trajectories): the handle also holds a plan, as a planned handle does - upload_footsteps, upload_goal,
+        upload(left_traj=...), replan_footsteps, replan_goal and plan_window work on it - and set_desired_from_plan() stages tick t's stage
+        out of it on the device: per tick set_desired_from_plan -> set_sensor_feedback (or set_feedback) -> run(1)."""
+        self.resident = bool(resident_plan)
+        if self.resident and not streamed_trajectories:
+            raise ValueError("resident_plan is a capability of a streamed handle (streamed_trajectories=True, external_feedback=True)")
         if ik_mode not in ("velocity", "position"):
             raise ValueError(f"ik_mode must be 'velocity' or 'position', not {ik_mode!r}")
         self.position = ik_mode == "position"
@@ -751,6 +771,7 @@ class TickPipeline:
                                  float(k_com_stance) if self.gain_sched else 0.0, float(k_zmp_stance) if self.gain_sched else 0.0,
                                  float(zmp_smoothing_time) if self.gain_sched else 0.0, int(self.planned), (C.c_double * 9)(*neck),
                                  int(self.streamed), *(cuts[k] for k in SENSOR_FILTERS))
+        self.params_ext = TickParamsExt(int(self.resident))
         if self.position:
             # (the library copies the three arrays at create)
             arr = [None if pik[k] is None else _f64(np.asarray(pik[k], float).reshape(ik.dof)) for k in ("q_reg", "q_min", "q_max")]
@@ -758,7 +779,7 @@ class TickPipeline:
             self.params.position_ik = PrepareParams(float(pik["w_q"]), float(pik["w_n"]), float(pik["step_cap"]), float(pik["tol_step"]),
                                                     float(pik["tol_constraint"]), int(pik["max_iter"]), *(None if a is None else a.ctypes.data for a in arr))
         self._h = C.c_void_p()
-        check(lib().wcqp_tick_create(C.byref(self.params), C.byref(self._h)), "wcqp_tick_create")
+        check(lib().wcqp_tick_create_ext(C.byref(self.params), C.byref(self.params_ext), C.byref(self._h)), "wcqp_tick_create_ext")
         self._keep = None
 
     def close(self):
@@ -772,6 +793,10 @@ class TickPipeline:
         except Exception:
             pass
 
+    def _holds_plan(self) -> bool:
+        """the handle holds a plan: a planned one, or a streamed one with resident_plan"""
+        return self.planned or getattr(self, "resident", False)
+
     def upload(self, data: dict, dcm_vel_traj=None, left_traj=None, right_traj=None, left_twist=None, right_twist=None, contact=None,
                com_height_traj=None, com_height_vel=None):
         """dcm_vel_traj: [B][max_ticks + N + 1][2], the planner's DCM velocity for the reactive controller and for ZMP gain scheduling
@@ -781,10 +806,11 @@ class TickPipeline:
         [B][T] (bit 0 left, bit 1 right in contact, bit 2 left is the fixed frame), com_height_traj / com_height_vel [B][T] or None,
         T = max_ticks + N + 1; data then needs no phase0 / swing_twist."""
         plan = dict(left_traj=left_traj, right_traj=right_traj, left_twist=left_twist, right_twist=right_twist, contact=contact)
-        if self.planned and any(v is None for v in plan.values()):
-            raise ValueError("a planned handle's upload needs " + ", ".join(k for k, v in plan.items() if v is None))
-        if not self.planned and any(v is not None for v in list(plan.values()) + [com_height_traj, com_height_vel]):
-            raise ValueError("planned trajectories were given to a handle created without planned_trajectories=True")
+        holds = self._holds_plan()
+        if holds and any(v is None for v in plan.values()):
+            raise ValueError("the upload of a handle that holds a plan needs " + ", ".join(k for k, v in plan.items() if v is None))
+        if not holds and any(v is not None for v in list(plan.values()) + [com_height_traj, com_height_vel]):
+            raise ValueError("planned trajectories were given to a handle created without planned_trajectories=True (or resident_plan=True)")
         nogait = self.planned or getattr(self, "streamed", False)      # (no synthetic gait: phase0 / swing_twist are optional)
         f64 = ("ref_traj", "state0", "q0", "dcm0", "com0", "u_init") + (() if nogait else ("swing_twist",))
         f64 += () if self.use_kin else ("J_left", "J_right", "J_neck", "J_com")
@@ -799,7 +825,7 @@ class TickPipeline:
         if dcm_vel_traj is not None:
             keep["dcm_vel_traj"] = _f64(dcm_vel_traj)
             assert keep["dcm_vel_traj"].shape == keep["ref_traj"].shape, keep["dcm_vel_traj"].shape
-        if self.planned:
+        if holds:
             T = keep["ref_traj"].shape[1]
             for k, w in (("left_traj", 12), ("right_traj", 12), ("left_twist", 6), ("right_twist", 6)):
                 keep[k] = _f64(plan[k])
@@ -818,8 +844,8 @@ class TickPipeline:
         data: state0, q0, com0 and optionally dcm0 / u_init (missing or None: the generated DCM reference and ZMP of stage 0).
         footsteps: n_steps [B], side [B][K] (0 left, 1 right), target [B][K][3] (x, y, yaw increment), first_ds_ticks, ss_ticks, ds_ticks,
         final_ds_ticks (0 or missing: ds_ticks), lift, zmp_delta_left, zmp_delta_right - what synth.synth_footstep_walk_batch returns."""
-        if not self.planned:
-            raise ValueError("footsteps were given to a handle created without planned_trajectories=True")
+        if not self._holds_plan():
+            raise ValueError("footsteps were given to a handle created without planned_trajectories=True (or resident_plan=True)")
         keep = {k: _f64(data[k]) for k in ("state0", "q0", "com0")}
         for k in ("dcm0", "u_init"):
             if data.get(k) is not None:
@@ -840,8 +866,8 @@ class TickPipeline:
         regenerated from stage merge_stage[i] on (-1: the robot keeps its plan) from footsteps n_steps [B], side [B][K'], target [B][K'][3],
         behind first_ds_ticks stages of double support; timings, lift and ZMP deltas stay those of upload_footsteps.  Enqueue-only on
         `stream`, behind the ticks already enqueued there; the arrays are copied before the call returns."""
-        if not self.planned:
-            raise ValueError("footsteps were given to a handle created without planned_trajectories=True")
+        if not self._holds_plan():
+            raise ValueError("footsteps were given to a handle created without planned_trajectories=True (or resident_plan=True)")
         merge = np.ascontiguousarray(merge_stage, dtype=np.int32)
         n_steps = np.ascontiguousarray(footsteps["n_steps"], dtype=np.int32)
         side = np.ascontiguousarray(footsteps["side"], dtype=np.uint8)
@@ -857,8 +883,8 @@ class TickPipeline:
         """"Robot i, go there" from standing: plans footsteps on the device from the desired soles of data["state0"] (entries 24..47) towards
         goals [B][2] (UnicyclePlanner.plan_host), then upload_footsteps with them.  planner.step_ticks is the path samples per step: callers
         create it with ss_ticks + ds_ticks.  Returns the planner's output dict (status says how each robot's planning ended)."""
-        if not self.planned:
-            raise ValueError("a goal was given to a handle created without planned_trajectories=True")
+        if not self._holds_plan():
+            raise ValueError("a goal was given to a handle created without planned_trajectories=True (or resident_plan=True)")
         st = _f64(data["state0"])
         plan = planner.plan_host(st[:, 24:36], st[:, 36:48], goals, first_side)
         self.upload_footsteps(data, dict(n_steps=plan["n_steps"], side=plan["side"], target=plan["target"], first_ds_ticks=first_ds_ticks,
@@ -871,8 +897,8 @@ class TickPipeline:
         soles of its plan's record merge_stage[i] towards goals[i], then replan_footsteps.  The soles are read through plan_window, one
         one-stage window per distinct merge stage - it synchronises.  Rows of robots with merge_stage -1 are not read.  Returns the planner's
         output dict over the whole batch: rows of robots that keep their plan are zero, with status -1."""
-        if not self.planned:
-            raise ValueError("a goal was given to a handle created without planned_trajectories=True")
+        if not self._holds_plan():
+            raise ValueError("a goal was given to a handle created without planned_trajectories=True (or resident_plan=True)")
         merge = np.ascontiguousarray(merge_stage, dtype=np.int32)
         goals = _f64(goals)
         fs = np.asarray(first_side)
@@ -919,7 +945,8 @@ class TickPipeline:
         streamed_trajectories (bool), sensor_filters (the mask: bit 0 joint velocity, bit 1 wrench, bit 2 CoM), plan_generated (bool: the plan
         in place came from upload_footsteps), plan_record_ms (the device time of that upload's record pass) and ik_mode ("velocity" /
         "position")."""
-        i = TickInfo()
+        i, x = TickInfo(), TickInfoExt()
+        check(lib().wcqp_tick_get_info_ext(self._h, C.byref(x)), "wcqp_tick_get_info_ext")
         check(lib().wcqp_tick_get_info(self._h, C.byref(i)), "wcqp_tick_get_info")
         return dict(kin_handoff={KIN_HANDOFF_NONE: None, KIN_HANDOFF_FUSED: "fused", KIN_HANDOFF_DENSE: "dense",
                                  KIN_HANDOFF_COMPACT: "compact"}[i.kin_handoff],
@@ -927,7 +954,7 @@ class TickPipeline:
                     launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling),
                     planned_trajectories=bool(i.planned_trajectories), streamed_trajectories=bool(i.streamed_trajectories),
                     sensor_filters=int(i.sensor_filters), plan_generated=bool(i.plan_generated), plan_record_ms=float(i.plan_record_ms),
-                    ik_mode="position" if i.ik_mode == TICK_IK_POSITION else "velocity")
+                    ik_mode="position" if i.ik_mode == TICK_IK_POSITION else "velocity", resident_plan=bool(x.resident_plan))
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")
@@ -1008,6 +1035,12 @@ class TickPipeline:
             keep.append(np.ascontiguousarray(a))
         des = TickDesired(*[None if a is None else a.ctypes.data for a in keep])
         check(lib().wcqp_tick_set_desired_host(self._h, C.byref(des)), "wcqp_tick_set_desired_host")
+
+    def set_desired_from_plan(self, stream: Optional[int] = None):
+        """A resident plan (wcqp_tick_set_desired_from_plan): stage t of the plan the handle holds becomes the desired stage of the next
+        tick, for every robot - one kernel on `stream`, enqueue only; t is read on the device.  It takes set_desired_*'s place in the
+        per-tick order; a set_desired_* call after it replaces the stage."""
+        check(lib().wcqp_tick_set_desired_from_plan(self._h, stream or None), "wcqp_tick_set_desired_from_plan")
 
     def set_desired_device(self, left_pose, right_pose, left_twist, right_twist, contact, com_height=None, com_height_vel=None, stream: int = 0):
         """The same from DEVICE memory: raw addresses, or contiguous torch tensors on the GPU of the shapes above (float64; contact uint8),

@@ -207,8 +207,11 @@ struct SensorStage {
 
 extern "C" {
 
-int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
+int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) { return wcqp_tick_create_ext(params, nullptr, out); }
+
+int wcqp_tick_create_ext(const wcqp_tick_params* params, const wcqp_tick_params_ext* ext, wcqp_tick_t* out) {
     if (!params || !out || params->batch < 1 || params->max_ticks < 1) return WCQP_E_INVALID;
+    const wcqp_tick_params_ext px = ext ? *ext : wcqp_tick_params_ext{};
     if (params->step_ticks < 2 || params->ds_ticks < 0 || params->ds_ticks > params->step_ticks) return WCQP_E_INVALID;
     if (params->ik.dof != kDof) return WCQP_E_UNSUPPORTED;
     // ZMP gain scheduling: finite stance gains, a finite smoothing time > 0 (refused before anything touches the device)
@@ -242,6 +245,10 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
             (params->dcm_controller == WCQP_TICK_DCM_MPC && params->mpc.horizon >= kGainsLdsStages))
             return WCQP_E_UNSUPPORTED;
     }
+    // a resident plan: a capability of a streamed handle
+    const bool resident = px.resident_plan != 0;
+    if (px.resident_plan != 0 && px.resident_plan != 1) return WCQP_E_INVALID;
+    if (resident && !streamed) return WCQP_E_UNSUPPORTED;
     // the POSITION mode: the problem's parameters by the rules of wcqp_prepare_create, then what the mode does not run with
     if (params->ik_mode != WCQP_TICK_IK_VELOCITY && params->ik_mode != WCQP_TICK_IK_POSITION) return WCQP_E_INVALID;
     const bool position = params->ik_mode == WCQP_TICK_IK_POSITION;
@@ -380,7 +387,7 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
         // the records, [B][traj_len][kPlanRec] (64-bit sizes: 8192 robots x 1251 stages is 3.3 GB)
         double* rec = nullptr;
         A_(rec, B * (size_t)d.traj_len * kPlanRec);
-        h->planned = true; h->pl.rec = rec;
+        h->planned = true; h->pl.rec = rec; h->plan_rec = rec;
         for (int k = 0; k < 9; ++k) h->pl.neck_add[k] = params->neck_additional_rotation[k];
     }
     if (streamed) {
@@ -390,6 +397,8 @@ int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) {
         h->streamed = true;
         h->pl.rec = h->st_rec; h->pl.set_A = h->st_set_A; h->pl.set_b = h->st_set_b; h->pl.set_nc = h->st_set_nc;
         for (int k = 0; k < 9; ++k) h->pl.neck_add[k] = params->neck_additional_rotation[k];
+        // a resident plan beside them: the records of a planned handle, which only the plan's own kernels and the staging kernel address
+        if (resident) { A_(h->plan_rec, B * (size_t)d.traj_len * kPlanRec); h->resident = true; }
     }
     if (d.skew) {
         A_(d.mst, B * 16); A_(d.hand, 2 * B * kHandLen); A_(d.live_A, B * 16); A_(d.live_b, B * 8); A_(d.live_nc, B); A_(d.sel_built, B);
@@ -563,7 +572,7 @@ int wcqp::upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0) {
     h->ticks_enqueued = 0;
     h->phase = 0;
     h->feedback_set = false;
-    h->desired_set = false;
+    h->desired_set = false; h->plan_staged = false;
     h->run.pending = false;
     return WCQP_OK;
 }
@@ -576,7 +585,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
     // (planned trajectories: no synthetic gait - phase0 and swing_twist may be NULL)
     if (!in->ref_traj || !in->state0 || !in->q0 || !in->dcm0 || !in->com0 || !in->u_init) return WCQP_E_INVALID;
     if (!h->planned && !h->streamed && (!in->phase0 || !in->swing_twist)) return WCQP_E_INVALID;
-    if (h->planned) { const int rcv = wcqp::validate_plan(h, in); if (rcv != WCQP_OK) return rcv; }
+    if (h->holds_plan()) { const int rcv = wcqp::validate_plan(h, in); if (rcv != WCQP_OK) return rcv; }
     if (!h->kin && (!in->J_left || !in->J_right || !in->J_neck || !in->J_com)) return WCQP_E_INVALID;
     // (the reactive controller reads no hull rows)
     if (!h->kin && !h->d.reactive && (!in->hull_tab_A || !in->hull_tab_b || !in->hull_tab_nc)) return WCQP_E_INVALID;
@@ -611,17 +620,13 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in) {
             UP_(d.dcm_vel, vel.data(), B * d.traj_len * 16);
         }
     }
-    if (h->planned) {
+    if (h->holds_plan()) {
         const int rcp = wcqp::upload_plan(h, in);
         if (rcp != WCQP_OK) return rcp;
         h->generated = false;
-        WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
-        WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
-    } else if (h->streamed) {
-        // no stage yet (every tick's comes through wcqp_tick_set_desired_*): zero records, no rows, no pair - a robot whose very first
-        // stage is rejected runs stopped on a record that holds nothing
-        WCQP_HIP_TRY(hipMemset(h->st_rec, 0, B * kPlanRec * 8)); WCQP_HIP_TRY(hipMemset(h->st_set_nc, 0, B * 4));
-        WCQP_HIP_TRY(hipMemset(h->st_pair, 0xff, B * 8));
+    }
+    if (h->streamed) { const int rcs = wcqp::reset_streamed_stage(h); if (rcs != WCQP_OK) return rcs; }
+    if (h->holds_plan() || h->streamed) {
         WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
         WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
     } else {
@@ -779,7 +784,7 @@ int wcqp_tick_run(wcqp_tick_t h, int32_t n_ticks, int32_t use_graph, void* strea
     if (h->run.done) { if (const int rc = h->run.guard(s); rc != WCQP_OK) return rc; }    // (sensor feedback: the host form waits for it)
     guard.armed = false;
     h->feedback_set = false;
-    h->desired_set = false;
+    h->desired_set = false; h->plan_staged = false;
     // the tick consumed a sensor reading: what that call wrote is the filters' state from here on
     if (h->filt_pending) { h->filt_cur ^= 1; h->filt_started = true; h->filt_pending = false; }
     return WCQP_OK;
@@ -835,11 +840,17 @@ int wcqp_tick_get_info(wcqp_tick_t h, wcqp_tick_info* out) {
     out->planned_trajectories = h->planned ? 1 : 0;
     out->streamed_trajectories = h->streamed ? 1 : 0;
     out->sensor_filters = h->filt_mask;
-    out->plan_generated = h->planned && h->uploaded && h->generated ? 1 : 0;
+    out->plan_generated = h->holds_plan() && h->uploaded && h->generated ? 1 : 0;
     out->plan_record_ms = out->plan_generated ? (double)h->gen_record_ms : 0.0;
     out->ik_mode = h->position ? WCQP_TICK_IK_POSITION : WCQP_TICK_IK_VELOCITY;
     // a kinematics launch unless fused; then the skewed kernel (1), MPC / reactive + the 16-lane kernel (2) or controller, glue, IK, post (4)
     out->launches_per_tick = (h->kin && !d.kin_fused ? 1 : 0) + (h->form == TickForm::SKEWED ? 1 : h->form == TickForm::MPC_IK16 ? 2 : 4);
+    return WCQP_OK;
+}
+
+int wcqp_tick_get_info_ext(wcqp_tick_t h, wcqp_tick_info_ext* out) {
+    if (!h || !out) return WCQP_E_INVALID;
+    out->resident_plan = h->resident ? 1 : 0;
     return WCQP_OK;
 }
 

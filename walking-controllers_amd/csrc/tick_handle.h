@@ -125,6 +125,13 @@ struct wcqp_tick_s {
     double* st_rec = nullptr; double* st_set_A = nullptr; double* st_set_b = nullptr; int* st_set_nc = nullptr;
     int* st_pair = nullptr;       // [B][2] contact pair of the last consumed stage / of the stage in hand (tick_desired_kernel)
     FixedStage des_stage;         // wcqp_tick_set_desired_host's staging rows (DesiredStage, tick_plan.hip)
+    // resident_plan (a streamed handle): it also holds a plan - records and row sets as a planned handle's - which the kernels of the tick never
+    // see (pl keeps pointing at the live record and the robots' own sets); wcqp_tick_set_desired_from_plan copies stage t out of it.
+    // plan_rec: the records [B][traj_len][kPlanRec] of whichever handle holds a plan (a planned handle: pl.rec), what the plan generator,
+    // the replan, the set builder and wcqp_tick_get_plan take.  plan_staged: the stage in hand came from the plan (the replan rule)
+    bool resident = false, plan_staged = false;
+    double* plan_rec = nullptr;
+    bool holds_plan() const { return planned || resident; }
     wcqp_tick::TickDevPL dpl(const wcqp_tick::TickDev& base) const { wcqp_tick::TickDevPL g; static_cast<wcqp_tick::TickDevGS&>(g) = dgs(base); g.pl = pl; return g; }
     // ik_mode = POSITION (a planned handle): the non-linear IK runs every tick in position_tick_kernel, which takes `pos` beside the
     // handle's TickDevPL in device memory; the chain's state, hand-off rows and live hull rows are the skewed handle's, but nothing is
@@ -151,6 +158,8 @@ namespace wcqp {
 // then repacked into the records with their support-polygon row sets
 int validate_plan(const wcqp_tick_s* h, const wcqp_tick_inputs* in);
 int upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in);
+// tick_plan.hip, for both uploads of a streamed handle: no stage in hand - zero records, no rows, no pair
+int reset_streamed_stage(wcqp_tick_s* h);
 // tick.hip, the tail wcqp_tick_upload and wcqp_tick_upload_footsteps share once the trajectories are in place (pair0 >= 0: the contact
 // pair of stage 0 where `in` holds no contact array)
 int upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0);

@@ -97,6 +97,50 @@ __global__ __launch_bounds__(64) void tick_desired_kernel(DesiredDev a, PlanRect
     }
 }
 
+// a resident plan (wcqp_tick_set_desired_from_plan): the stage of the next tick out of the plan the handle holds, in tick_desired_kernel's
+// place and layout - 16 lanes per robot, four robots per wave, the dead slots of the last wave repeat the last robot and store nothing.
+// t is the handle's tick index in device memory (TickDev::tick2, the copy the next launch reads).  Lane j copies entries j, 16 + j and
+// 32 + j of plan record (i, t) into the robot's live record, whose entry 39 names the robot's own set i; lanes 0..7 copy the row set the
+// plan's record names into that set, lane 0 its row count.  Nothing is validated (the upload did) and no hull is built: the rows exist,
+// and the chain of tick t copies them into the live rows on a change of pair, as for every streamed handle.  pair / first: as above.
+struct StageDev {
+    wcqp::GPtr<const double> plan, set_A, set_b; wcqp::GPtr<const int> set_nc;      // the resident plan: [B][traj_len][kPlanRec], its sets
+    wcqp::GPtr<const int> tick;
+    wcqp::GPtr<double> rec, st_A, st_b; wcqp::GPtr<int> st_nc, pair;                // the live record and set of every robot, the pairs
+    int batch, traj_len, first;
+};
+__global__ __launch_bounds__(64) void tick_stage_from_plan_kernel(StageDev a) {
+    const int lane = threadIdx.x, grp = lane >> 4, j = lane & 15;
+    const long inst_raw = (long)blockIdx.x * 4 + grp;
+    const bool live = inst_raw < a.batch;
+    const size_t i = (size_t)(live ? inst_raw : (long)a.batch - 1);
+    const int t = *a.tick.get();
+    const double* src = a.plan.get() + (i * (size_t)a.traj_len + (size_t)t) * (size_t)kPlanRec;       // (64-bit: the plan passes 4 GB)
+    const double v0 = src[j], v1 = src[16 + j], v2 = j < 8 ? src[32 + j] : 0.0;
+    const double flags = src[kPlanFlags];
+    const size_t set = (size_t)src[kPlanHull];
+    double2 rA = make_double2(0.0, 0.0);
+    double rb = 0.0;
+    if (j < WCQP_HULL_ROWS) {
+        rA = reinterpret_cast<const double2*>(a.set_A.get())[set * WCQP_HULL_ROWS + j];
+        rb = a.set_b.get()[set * WCQP_HULL_ROWS + j];
+    }
+    if (!live) return;
+    double* r = a.rec.get() + i * kPlanRec;
+    r[j] = v0; r[16 + j] = v1;
+    if (j < 7) r[32 + j] = v2;
+    if (j == 7) r[kPlanHull] = (double)i;
+    if (j < WCQP_HULL_ROWS) {
+        reinterpret_cast<double2*>(a.st_A.get())[i * WCQP_HULL_ROWS + j] = rA;
+        a.st_b.get()[i * WCQP_HULL_ROWS + j] = rb;
+    }
+    if (j != 0) return;
+    a.st_nc.get()[i] = a.set_nc.get()[set];
+    int* pr = a.pair.get() + i * 2;
+    const int consumed = a.first ? pr[1] : pr[0];
+    pr[0] = consumed; pr[1] = ((int)flags & 3) - 1;
+}
+
 // A valid stage of one robot, for the planned upload and the streamed host form alike: a foot in contact, the fixed-frame foot in contact,
 // finite poses [12], twists [6] and heights (height / height_vel: the stage's own entry, or NULL for none)
 bool stage_valid(unsigned f, const double* left_pose, const double* right_pose, const double* left_twist, const double* right_twist,
@@ -129,7 +173,7 @@ PlanGenDev plan_gen_of(const wcqp_tick_s* h, int K) {
     const auto& gp = h->gp;
     PlanGenDev g{};
     g.state = d.state;
-    g.rec = const_cast<double*>(h->pl.rec.get()); g.ref = const_cast<double*>(d.ref_traj.get());
+    g.rec = h->plan_rec; g.ref = const_cast<double*>(d.ref_traj.get());
     g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
     g.zmp0 = h->gen_zmp0;
     g.batch = d.batch; g.K = K; g.traj_len = d.traj_len; g.max_ticks = h->p.max_ticks;
@@ -147,11 +191,14 @@ int build_plan_sets(wcqp_tick_s* h, size_t ns, const long long* d_at, const int*
     if (hipMalloc(reinterpret_cast<void**>(&h->set_A), ns * 128) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&h->set_b), ns * 64) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&h->set_nc), ns * 4) != hipSuccess)
         return WCQP_E_NOMEM;
-    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((ns + 127) / 128)), dim3(128), 0, 0, (int)ns, plan_rect(h), h->pl.rec.get(), d_at, d_code,
+    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((ns + 127) / 128)), dim3(128), 0, 0, (int)ns, plan_rect(h), h->plan_rec, d_at, d_code,
                        h->set_A, h->set_b, h->set_nc);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return WCQP_E_HIP;
+    h->n_sets = ns;
+    // a resident plan's sets stay behind the staging kernel (a launch argument): the tick's kernels keep the robots' own
+    if (!h->planned) return WCQP_OK;
     // the kernels read the sets through the handle's TickDevPL in device memory
-    h->pl.set_A = h->set_A; h->pl.set_b = h->set_b; h->pl.set_nc = h->set_nc; h->n_sets = ns;
+    h->pl.set_A = h->set_A; h->pl.set_b = h->set_b; h->pl.set_nc = h->set_nc;
     const TickDevPL g = h->dpl(h->d);
     WCQP_HIP_TRY(hipMemcpy(h->d_dev, &g, sizeof(TickDevPL), hipMemcpyHostToDevice));
     return WCQP_OK;
@@ -212,7 +259,7 @@ int wcqp::upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in) {
                 r[kPlanHull] = set_of[w];
             }
         }
-        WCQP_HIP_TRY(hipMemcpy(const_cast<double*>(h->pl.rec.get()) + i0 * T * kPlanRec, rec.data(), n * T * kPlanRec * 8, hipMemcpyHostToDevice));
+        WCQP_HIP_TRY(hipMemcpy(h->plan_rec + i0 * T * kPlanRec, rec.data(), n * T * kPlanRec * 8, hipMemcpyHostToDevice));
     }
     // the row sets, built on the device from the records just copied
     const size_t ns = set_at.size();
@@ -231,7 +278,7 @@ extern "C" {
 
 int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps) {
     if (!h || !in || !steps) return WCQP_E_INVALID;
-    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
     TickDev& d = h->d;
     const size_t B = (size_t)d.batch;
     const int K = steps->max_steps;
@@ -304,6 +351,7 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     }
     WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
     WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
+    if (h->streamed) { const int rcs = wcqp::reset_streamed_stage(h); if (rcs != WCQP_OK) return rcs; }
     // dcm0 / u_init NULL: the generated DCM reference and ZMP of stage 0
     std::vector<double> dcm0, u0;
     wcqp_tick_inputs eff = *in;
@@ -322,7 +370,7 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
 
 int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) {
     if (!h || !rp) return WCQP_E_INVALID;
-    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
     if (!h->uploaded) return WCQP_E_INVALID;
     if (!h->generated) return WCQP_E_UNSUPPORTED;        // (a classically uploaded plan has no known timeline)
     const TickDev& d = h->d;
@@ -339,8 +387,9 @@ int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* 
         const int M = rp->merge_stage[i];
         if (M == -1) continue;                            // (the robot keeps its plan: nothing of its rows is read)
         // stage 0 is the initial state's, stages the enqueued ticks have consumed stay (within one wcqp_tick_run call the kernel reads a stage
-        // ahead, between calls nothing is ahead: M >= ticks_enqueued is the condition), and a plan is cut only behind its own origin
-        if (M < 1 || M < h->ticks_enqueued || M >= T || M < gp.origin[i]) return WCQP_E_INVALID;
+        // ahead, between calls nothing is ahead: M >= ticks_enqueued is the condition - a resident plan's tick whose stage has been staged
+        // counts as enqueued, its live record holds that stage), and a plan is cut only behind its own origin
+        if (M < 1 || M < h->ticks_enqueued + (h->plan_staged ? 1 : 0) || M >= T || M < gp.origin[i]) return WCQP_E_INVALID;
         if (!footsteps_valid(i, K, rp->n_steps, rp->side, rp->target)) return WCQP_E_INVALID;
         const int n = rp->n_steps[i];
         // the merge stage has both feet in contact in the plan in force: not inside one of its single supports
@@ -398,7 +447,7 @@ int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* 
     WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
     const int rc = wcqp::plan_replan_enqueue(g, st);
     if (rc != WCQP_OK) return rc;
-    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->pl.rec.get(), g.set_at, g.set_code,
+    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
                        h->set_A, h->set_b, h->set_nc);
     WCQP_HIP_TRY(hipGetLastError());
     if (const int rc = h->rp.guard(st); rc != WCQP_OK) return rc;
@@ -408,7 +457,7 @@ int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* 
 
 int wcqp_tick_get_plan(wcqp_tick_t h, int32_t robot0, int32_t n, int32_t stage0, int32_t m, const wcqp_tick_plan_window* out) {
     if (!h || !out) return WCQP_E_INVALID;
-    if (!h->planned) return WCQP_E_UNSUPPORTED;
+    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
     const TickDev& d = h->d;
     if (!h->uploaded || robot0 < 0 || n < 1 || stage0 < 0 || m < 1 || (long long)robot0 + n > d.batch || (long long)stage0 + m > d.traj_len) return WCQP_E_INVALID;
     const bool has_vel = d.reactive || d.gain_sched;
@@ -437,7 +486,7 @@ int wcqp_tick_get_plan(wcqp_tick_t h, int32_t robot0, int32_t n, int32_t stage0,
     std::vector<double> rec(slab * M * kPlanRec);
     for (size_t i0 = 0; i0 < N; i0 += slab) {
         const size_t nn = N - i0 < slab ? N - i0 : slab;
-        WCQP_HIP_TRY(hipMemcpy2D(rec.data(), M * kPlanRec * 8, h->pl.rec.get() + ((R0 + i0) * T + S0) * kPlanRec, T * kPlanRec * 8, M * kPlanRec * 8, nn,
+        WCQP_HIP_TRY(hipMemcpy2D(rec.data(), M * kPlanRec * 8, h->plan_rec + ((R0 + i0) * T + S0) * kPlanRec, T * kPlanRec * 8, M * kPlanRec * 8, nn,
                                  hipMemcpyDeviceToHost));
         for (size_t w0 = 0; w0 < nn * M; ++w0) {
             const double* r = &rec[w0 * kPlanRec];
@@ -480,7 +529,24 @@ int wcqp_tick_set_desired_device(wcqp_tick_t h, const wcqp_tick_desired* des, vo
     a.batch = d.batch; a.first = h->desired_set ? 0 : 1; a.build = d.reactive ? 0 : 1;
     hipLaunchKernelGGL(tick_desired_kernel, dim3((unsigned)((d.batch + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a, plan_rect(h));
     WCQP_HIP_TRY(hipGetLastError());
-    h->desired_set = true;
+    h->desired_set = true; h->plan_staged = false;
+    return WCQP_OK;
+}
+
+int wcqp_tick_set_desired_from_plan(wcqp_tick_t h, void* stream) {
+    if (!h) return WCQP_E_INVALID;
+    if (!h->resident) return WCQP_E_UNSUPPORTED;
+    // (every upload of such a handle brings a plan; stage t = ticks_enqueued is one a tick may run: within the records, and validated)
+    if (!h->uploaded || h->ticks_enqueued >= h->p.max_ticks) return WCQP_E_INVALID;
+    const TickDev& d = h->d;
+    StageDev a{};
+    a.plan = h->plan_rec; a.set_A = h->set_A; a.set_b = h->set_b; a.set_nc = h->set_nc;
+    a.tick = d.tick2.p + h->phase;
+    a.rec = h->st_rec; a.st_A = h->st_set_A; a.st_b = h->st_set_b; a.st_nc = h->st_set_nc; a.pair = h->st_pair;
+    a.batch = d.batch; a.traj_len = d.traj_len; a.first = h->desired_set ? 0 : 1;
+    hipLaunchKernelGGL(tick_stage_from_plan_kernel, dim3((unsigned)((d.batch + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a);
+    WCQP_HIP_TRY(hipGetLastError());
+    h->desired_set = true; h->plan_staged = true;
     return WCQP_OK;
 }
 
@@ -521,6 +587,14 @@ int wcqp_tick_set_desired_host(wcqp_tick_t h, const wcqp_tick_desired* des) {
 }  // extern "C"
 
 namespace wcqp {
+// no stage yet (every tick's comes through wcqp_tick_set_desired_*): zero records, no rows, no pair - a robot whose very first stage is
+// rejected runs stopped on a record that holds nothing
+int reset_streamed_stage(wcqp_tick_s* h) {
+    const size_t B = (size_t)h->d.batch;
+    WCQP_HIP_TRY(hipMemset(h->st_rec, 0, B * kPlanRec * 8)); WCQP_HIP_TRY(hipMemset(h->st_set_nc, 0, B * 4));
+    WCQP_HIP_TRY(hipMemset(h->st_pair, 0xff, B * 8));
+    return WCQP_OK;
+}
 size_t desired_stage_bytes(size_t batch) {
     const double* const d = stage_sizing<double>();
     const wcqp_tick_desired all{d, d, d, d, stage_sizing<uint8_t>(), d, d};
