@@ -104,23 +104,42 @@ def test_hull_rows_convention(wca):
     assert 5 <= nc2 <= 8 and ((A2[:nc2] @ two.T) <= b2[:nc2, None] + 1e-12).all()
 
 
-def test_qp_step_record_layout_matches_the_header(tmp_path):
-    """The ctypes mirror of wcqp_qp_step (an array of these crosses the FFI) has the header's size and field offsets."""
+def test_every_struct_and_constant_matches_the_header(wca, tmp_path):
+    """capi.ABI_STRUCTS and capi.ABI_CONSTANTS name every by-value struct and every integer macro of include/wcqp.h, and one C program
+    generated from the two tables says what the compiler makes of them: offset and size of every field in _fields_ order and the size of
+    every struct equal the ctypes mirror's (an array of wcqp_qp_step crosses the FFI), every macro its Python value.  The field count per
+    struct is compared too: a field missing from a mirror where padding hides it from sizeof.  A new field needs the header and the mirror,
+    a new struct or macro its table entry - and no test of its own."""
     import subprocess
-    import walking_controllers_amd as wca
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "abi_layout"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "abi_layout.c"), "-o", str(exe)])
-    lines = [ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines()]
-    out = lines[0]
-    S = wca.capi.QpStep
-    mine = [C.sizeof(S)] + [getattr(S, f).offset for f in ("x0", "ref_len", "u_prev", "hull_nc", "mpc_stream", "J_left", "ik_stream")]
-    assert out[0] == "wcqp_qp_step" and [int(x) for x in out[1:]] == mine
-    # wcqp_tick_params grew this round (kin_handoff, ticks_per_launch): the ctypes mirror follows the header field for field
-    out = lines[1]
-    T = wca.capi.TickParams
-    mine = [C.sizeof(T)] + [getattr(T, f).offset for f in ("seed", "mpc", "ik", "ik_cold_start_only", "kin", "foot_rect", "kin_handoff", "ticks_per_launch")]
-    assert out[0] == "wcqp_tick_params" and [int(x) for x in out[1:]] == mine
+    capi, inc = wca.capi, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(inc, "wcqp.h")).read(), flags=re.S)
+    bodies = {name: body for body, name in re.findall(r"\{([^{}]*)^\} (wcqp_\w+);", hdr, re.M)}
+    assert not set(bodies) ^ set(capi.ABI_STRUCTS), ("structs of the header and of ABI_STRUCTS differ", sorted(set(bodies) ^ set(capi.ABI_STRUCTS)))
+    not_integers = {"WCQP_H", "WCQP_IK_MIXED_TOL"}           # the include guard; the one floating value
+    macros = set(re.findall(r"^#define (WCQP_\w+)\b(?!\()", hdr, re.M)) - not_integers
+    assert not macros ^ set(capi.ABI_CONSTANTS), ("macros of the header and of ABI_CONSTANTS differ", sorted(macros ^ set(capi.ABI_CONSTANTS)))
+    for name, cls in capi.ABI_STRUCTS.items():
+        declared = sum(d.count(",") + 1 for d in bodies[name].split(";") if d.strip())
+        assert declared == len(cls._fields_), "%s: the header declares %d fields, %s has %d" % (name, declared, cls.__name__, len(cls._fields_))
+    src = ["#include <stddef.h>", "#include <stdio.h>", '#include "wcqp.h"', "int main(void) {"]
+    for name, cls in capi.ABI_STRUCTS.items():
+        src += ['printf("%%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (name, f, name, f) for f, _ in cls._fields_]
+        src.append('printf("%%zu\\n", sizeof(%s));' % name)
+    src += ['printf("%%lld\\n", (long long)%s);' % m for m in capi.ABI_CONSTANTS] + ["return 0; }"]
+    (tmp_path / "abi.c").write_text("\n".join(src) + "\n")
+    cc = subprocess.run(["cc", "-std=c99", "-I", inc, str(tmp_path / "abi.c"), "-o", str(tmp_path / "abi")], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr[-3000:]             # (a field of a mirror that the header does not have ends here, by name)
+    out = iter(subprocess.check_output([str(tmp_path / "abi")], text=True).splitlines())
+    for name, cls in capi.ABI_STRUCTS.items():
+        for f, _ in cls._fields_:
+            got, mine = [int(x) for x in next(out).split()], [getattr(cls, f).offset, getattr(cls, f).size]
+            assert got == mine, "%s.%s: offset, size %s in the header, %s in %s" % (name, f, got, mine, cls.__name__)
+        got = int(next(out))
+        assert got == C.sizeof(cls), "sizeof(%s) is %d in the header, %d in %s" % (name, got, C.sizeof(cls), cls.__name__)
+    for m, mine in capi.ABI_CONSTANTS.items():
+        got = int(next(out))
+        assert got == mine, "%s is %d in the header, %r in capi" % (m, got, mine)
+    assert next(out, None) is None
 
 
 def test_source_hash_follows_the_kernel_sources(wca, tmp_path, monkeypatch):

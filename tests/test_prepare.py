@@ -11,6 +11,7 @@ import sys
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED
 
 import robots
 import trees
@@ -19,7 +20,6 @@ from helpers import prepare_spec as ps
 from helpers import streamed_tick as stt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2
 B13 = 13                      # the last wave of four robots is partly empty
 ACTUAL = list(range(24)) + list(range(48, 57)) + [66, 67, 68]      # the entries of the pose block the kinematics write
 CONFIGS = ("free", "limits", "no_neck")
@@ -108,18 +108,6 @@ def test_restatement_respects_limits(scene, n_cut):
     assert c["active"] == sorted(cut) and c["mult_ok"] and c["inside"] and c["constraint"] <= 1e-10 and c["stationarity"] <= 1e-9
     for k in cut:
         assert s["q"][k] == (hi if exc[k] > 0 else lo)[k]
-
-
-def test_abi_layout_and_symbols(wca, tmp_path):
-    """offsetof / sizeof of wcqp_prepare_params equal the ctypes mirror; the library exports the four entry points."""
-    exe = tmp_path / "prepare_layout"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "prepare_layout.c"), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    cls = wca.capi.PrepareParams
-    assert got == [getattr(cls, k).offset for k, _ in cls._fields_] + [C.sizeof(cls)]
-    lib = wca.capi.lib()
-    for sym in ("wcqp_prepare_create", "wcqp_prepare_destroy", "wcqp_prepare_solve_device", "wcqp_prepare_solve_host"):
-        assert sym in wca.capi.ABI_SYMBOLS and getattr(lib, sym)
 
 
 def test_create_refusals(wca):

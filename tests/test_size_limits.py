@@ -18,9 +18,9 @@ import subprocess
 import sys
 
 import pytest
+from walking_controllers_amd.capi import E_HIP, E_UNSUPPORTED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E_UNSUPPORTED, E_HIP = -2, -4
 SOL_TOL = 1e-9
 
 # bytes per robot of the arrays the kernels address with 32-bit offsets (include/wcqp.h)

@@ -2,11 +2,10 @@
 CPU: the numpy restatement of the plan (helpers/footstep_plan.py) against synth_planned_walk_batch, the ABI.  GPU: the generated plan
 against the restatement, its own properties, the classic upload fed the same plan, the closed loop against oracle/tick_spec.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED
 
 import robots
 from helpers import footstep_plan as fp
@@ -14,8 +13,6 @@ from helpers import planned_tick as pt
 from helpers import streamed_tick as stt
 from helpers import zmp_gains as zg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2
 K_DCM = {"iCubGazeboV2_5": 1.0, "iCubGenova04": 1.0, "icubGazeboSim": 1.5}
 KEYS = ("u0_log", "dq_log", "q_des", "dcm", "com")
 SAME = KEYS + ("ik_fail", "mpc_fail", "hot_try", "hot_hit", "active_lower", "active_upper", "zmp_gains")
@@ -115,18 +112,6 @@ def test_restatement_reproduces_the_planned_walk(wca):
         print(k, err)
         assert err <= 1e-12, (k, err)
     assert np.exp(-np.sqrt(9.81 / 0.53) * 0.01 * 720) * 1e-4 < 1e-17
-
-
-def test_abi_layout_and_symbols(wca, tmp_path):
-    """offsetof / sizeof of wcqp_tick_footsteps and wcqp_tick_plan_window equal the ctypes mirrors; the library exports both entry points."""
-    exe = tmp_path / "footsteps_layout"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "footsteps_layout.c"), "-o", str(exe)])
-    lines = [[int(x) for x in ln.split()] for ln in subprocess.check_output([str(exe)], text=True).splitlines()]
-    for got, cls in zip(lines, (wca.capi.TickFootsteps, wca.capi.TickPlanWindow)):
-        assert got == [getattr(cls, k).offset for k, _ in cls._fields_] + [C.sizeof(cls)]
-    lib = wca.capi.lib()
-    for sym in ("wcqp_tick_upload_footsteps", "wcqp_tick_get_plan"):
-        assert sym in wca.capi.ABI_SYMBOLS and getattr(lib, sym)
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU

@@ -2,19 +2,16 @@
 flags, fixed frame and CoM height of every tick come from the planner's stage t.  CPU: the restatement's given-stages branch
 (oracle/tick_spec.py::run_ticks(stages=...)) against its synthetic gait, the ABI, the binding's and the library's refusals, the generator.  GPU: the device against the restatement."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED
 
 import robots
 from helpers import planned_tick as pt
 from helpers import streamed_tick as stt
 from helpers import zmp_gains as zg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
 K_DCM = {"iCubGazeboV2_5": 1.0, "iCubGenova04": 1.0, "icubGazeboSim": 1.5}
 KEYS = ("u0_log", "dq_log", "q_des", "dcm", "com")
 WALK_T = 880          # the generated walk: a double support of 110 ticks, four steps of 180, then standing
@@ -63,23 +60,6 @@ def test_restatement_reproduces_the_synthetic_gait(wca, qs):
         assert np.abs(out[k] - ref[k]).max() <= 1e-12, k
     assert np.array_equal(out["ik_fail"], ref["ik_fail"]) and np.array_equal(out["mpc_fail"], ref["mpc_fail"])
     assert np.abs(ref["dq_log"]).max() > 1e-3
-
-
-def test_new_fields_match_the_ctypes_mirror(wca, tmp_path):
-    """Offsets of the new fields in include/wcqp.h equal the ctypes mirror's."""
-    capi = wca.capi
-    src = tmp_path / "off.c"
-    fields = [("wcqp_tick_params", "planned_trajectories", capi.TickParams), ("wcqp_tick_params", "neck_additional_rotation", capi.TickParams)]
-    fields += [("wcqp_tick_inputs", k, capi.TickInputs) for k in ("left_traj", "right_traj", "left_twist", "right_twist", "contact", "com_height_traj", "com_height_vel")]
-    fields += [("wcqp_tick_info", "planned_trajectories", capi.TickInfo)]
-    body = "".join(f'printf("%zu\\n", offsetof({s}, {f}));\n' for s, f, _ in fields)
-    body += "".join(f'printf("%zu\\n", sizeof({s}));\n' for s in ("wcqp_tick_params", "wcqp_tick_inputs", "wcqp_tick_info"))
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "wcqp.h"\nint main(void) {\n' + body + "return 0;\n}\n")
-    exe = tmp_path / "off"
-    subprocess.check_call(["cc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [getattr(cls, f).offset for _, f, cls in fields] + [C.sizeof(capi.TickParams), C.sizeof(capi.TickInputs), C.sizeof(capi.TickInfo)]
-    assert got == want
 
 
 def test_binding_refuses_incomplete_arguments(wca):

@@ -6,17 +6,15 @@ WM/src/WalkingDCMReactiveController.cpp:63-82 in place of the MPC solve.
 """
 import ctypes as C
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED
 
 import robots
 
 from helpers import zmp_gains as zgh
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # kDCM of DCM_REACTIVE_CONTROLLER, app/robots/<robot>/dcmReactiveControllerParams.ini:1
 K_DCM = {
@@ -25,7 +23,6 @@ K_DCM = {
     "icubGazeboSim": 1.2,       # app/robots/icubGazeboSim/dcmReactiveControllerParams.ini:1
 }
 VMAX = 0.45
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
 KEYS = ("u0_log", "dq_log", "q_des", "dcm", "com")
 
 
@@ -81,31 +78,6 @@ def _no_side_effects(ts, qp_spec, p):
     with pytest.raises(IndexError):
         ts.run_ticks(p, d, 4, ipar, dcm_vel=np.zeros((2, 2, 2)), **kw)          # the velocities run out on tick 2: the run raises half way
     assert dataclasses.asdict(p) == dataclasses.asdict(before) and qp_spec.mpc_exact is orig and ts.qs.mpc_exact is orig
-
-
-def test_new_struct_fields_match_the_ctypes_mirror(wca, tmp_path):
-    """wcqp_tick_params.dcm_controller / k_dcm, wcqp_tick_inputs.dcm_vel_traj and wcqp_tick_info: offsets in the C header == capi's."""
-    src = tmp_path / "layout.c"
-    src.write_text(r'''
-#include <stddef.h>
-#include <stdio.h>
-#include "wcqp.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu\n", sizeof(wcqp_tick_params), offsetof(wcqp_tick_params, plant), offsetof(wcqp_tick_params, dcm_controller),
-           offsetof(wcqp_tick_params, k_dcm), (size_t)WCQP_TICK_DCM_REACTIVE);
-    printf("%zu %zu %zu\n", sizeof(wcqp_tick_inputs), offsetof(wcqp_tick_inputs, u_init), offsetof(wcqp_tick_inputs, dcm_vel_traj));
-    printf("%zu %zu %zu %zu %zu\n", sizeof(wcqp_tick_info), offsetof(wcqp_tick_info, kin_handoff), offsetof(wcqp_tick_info, ticks_per_launch),
-           offsetof(wcqp_tick_info, dcm_controller), offsetof(wcqp_tick_info, launches_per_tick));
-    return 0;
-}
-''')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    lines = [[int(x) for x in ln.split()] for ln in subprocess.check_output([str(exe)], text=True).splitlines()]
-    P, I, N = wca.capi.TickParams, wca.capi.TickInputs, wca.capi.TickInfo
-    assert lines[0] == [C.sizeof(P), P.plant.offset, P.dcm_controller.offset, P.k_dcm.offset, wca.capi.TICK_DCM_REACTIVE]
-    assert lines[1] == [C.sizeof(I), I.u_init.offset, I.dcm_vel_traj.offset]
-    assert lines[2] == [C.sizeof(N), N.kin_handoff.offset, N.ticks_per_launch.offset, N.dcm_controller.offset, N.launches_per_tick.offset]
 
 
 def test_reactive_pipeline_needs_k_dcm(wca):

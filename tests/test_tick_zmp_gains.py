@@ -7,21 +7,18 @@ oracle/tick_spec.run_ticks(zmp_gain_schedule=...) with either DCM controller.
 """
 import ctypes as C
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED
 
 import robots
 from helpers import zmp_gains as zgh
 from oracle import zmp_gains_spec as zg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 K_DCM = {"iCubGazeboV2_5": 1.2, "iCubGenova04": 1.1, "icubGazeboSim": 1.2}   # dcmReactiveControllerParams.ini:1 (as test_tick_reactive)
 VMAX = 0.45
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED = -1, -2      # include/wcqp.h
 KEYS = ("u0_log", "dq_log", "q_des", "dcm", "com")
 
 
@@ -76,18 +73,6 @@ def test_wrapper_restores_the_patch_and_the_gains(wca):
     with pytest.raises(IndexError):
         ts.run_ticks(p, d, 4, ipar, dcm_vel=np.zeros((2, 2, 2)), **kw)          # the velocities run out on tick 2: the run raises half way
     assert dataclasses.asdict(p) == dataclasses.asdict(before) and qp_spec.mpc_exact is orig and ts.qs.mpc_exact is orig
-
-
-def test_new_struct_fields_match_the_ctypes_mirror(wca, tmp_path):
-    """wcqp_tick_params' scheduling fields, wcqp_tick_outputs.zmp_gains, wcqp_tick_info.zmp_gain_scheduling: header offsets == capi's."""
-    exe = tmp_path / "zmp_gains_layout"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "zmp_gains_layout.c"), "-o", str(exe)])
-    lines = [[int(x) for x in ln.split()] for ln in subprocess.check_output([str(exe)], text=True).splitlines()]
-    Pm, O, N = wca.capi.TickParams, wca.capi.TickOutputs, wca.capi.TickInfo
-    assert lines[0] == [C.sizeof(Pm), Pm.k_dcm.offset, Pm.zmp_gain_scheduling.offset, Pm.k_com_stance.offset, Pm.k_zmp_stance.offset,
-                        Pm.zmp_smoothing_time.offset]
-    assert lines[1] == [C.sizeof(O), O.active_upper.offset, O.zmp_gains.offset]
-    assert lines[2] == [C.sizeof(N), N.launches_per_tick.offset, N.zmp_gain_scheduling.offset]
 
 
 def test_binding_needs_the_schedule(wca):

@@ -3,11 +3,10 @@
 kernel against the restatement, batch sizes, a stuck robot and a NaN goal next to healthy robots, the two forms, a fuzz batch, and
 upload_goal / replan_goal end to end against oracle/tick_spec.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
+from walking_controllers_amd.capi import E_INVALID as WCQP_E_INVALID, E_UNSUPPORTED as WCQP_E_UNSUPPORTED, E_HIP as WCQP_E_HIP
 
 import robots
 from helpers import footstep_plan as fp
@@ -17,8 +16,6 @@ from helpers import streamed_tick as stt
 from helpers import unicycle_plan as up
 from helpers import zmp_gains as zg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WCQP_E_INVALID, WCQP_E_UNSUPPORTED, WCQP_E_HIP = -1, -2, -4
 OUT = ("n_steps", "side", "target", "status", "desired_point", "unicycle_end")
 MARGIN = 1e-9           # a robot the restatement decided by less may be decided otherwise by the device: it is left out of a comparison
 # the scenario of the GPU tests: 13 robots (a wave with dead lanes), K = 8 steps of D = 25 samples.  The thresholds are set for steps of
@@ -210,18 +207,6 @@ def test_closed_loop_on_the_planned_footsteps(walk3):
     assert not np.array_equal(w["ref0"]["q_des"][2], w["ref1"]["q_des"][2])
 
 
-def test_abi_layout_and_symbols(wca, tmp_path):
-    """offsetof / sizeof of the three wcqp_unicycle_ structs equal the ctypes mirrors; the library exports the four entry points"""
-    exe = tmp_path / "unicycle_layout"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "unicycle_layout.c"), "-o", str(exe)])
-    lines = [[int(x) for x in ln.split()] for ln in subprocess.check_output([str(exe)], text=True).splitlines()]
-    for got, cls in zip(lines, (wca.capi.UnicycleParams, wca.capi.UnicycleInputs, wca.capi.UnicycleOutputs)):
-        assert got == [getattr(cls, k).offset for k, _ in cls._fields_] + [C.sizeof(cls)]
-    lib = wca.capi.lib()
-    for sym in ("wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host"):
-        assert sym in wca.capi.ABI_SYMBOLS and getattr(lib, sym)
-
-
 def test_create_refusals(wca):
     lib = wca.capi.lib()
 
@@ -260,20 +245,30 @@ def test_plan_refusals_without_a_device(wca, scen):
              desired_point=np.full((B, 2), 5.0), unicycle_end=np.full((B, 3), 5.0))
     base_in = dict(left0=g["left0"], right0=g["right0"], goal=g["goals"], first_side=g["first_side"])
 
-    def host(batch=B, drop=(), **kw):
+    def structs(drop=(), **kw):
         a = {k: np.ascontiguousarray(v) for k, v in dict(base_in, **kw).items()}
-        ins = wca.capi.UnicycleInputs(**{k: v.ctypes.data for k, v in a.items() if k not in drop})
-        outs = wca.capi.UnicycleOutputs(**{k: v.ctypes.data for k, v in o.items() if k not in drop})
+        return a, wca.capi.UnicycleInputs(**{k: v.ctypes.data for k, v in a.items() if k not in drop}), \
+            wca.capi.UnicycleOutputs(**{k: v.ctypes.data for k, v in o.items() if k not in drop})
+
+    def host(batch=B, **kw):
+        """the host form's code"""
+        _keep, ins, outs = structs(**kw)
+        return lib.wcqp_unicycle_plan_host(pl._h, batch, C.byref(ins), C.byref(outs))
+
+    def both(batch=B, drop=()):
+        """the codes of both forms - only for calls the device form refuses before it launches: the arrays are HOST memory, and with a
+        device present it would launch on them"""
+        _keep, ins, outs = structs(drop=drop)
         return lib.wcqp_unicycle_plan_host(pl._h, batch, C.byref(ins), C.byref(outs)), lib.wcqp_unicycle_plan_device(pl._h, batch, C.byref(ins), C.byref(outs), None)
 
     def arr(key, idx, val):
         a = np.array(base_in[key], copy=True); a[idx] = val
         return {key: a}
     for drop in ("left0", "right0", "goal", "first_side", "n_steps", "side", "target", "status"):
-        assert host(drop=(drop,)) == (WCQP_E_INVALID, WCQP_E_INVALID), drop
-    assert host(batch=-1) == (WCQP_E_INVALID, WCQP_E_INVALID) and host(batch=0) == (0, 0)
+        assert both(drop=(drop,)) == (WCQP_E_INVALID, WCQP_E_INVALID), drop
+    assert both(batch=-1) == (WCQP_E_INVALID, WCQP_E_INVALID) and both(batch=0) == (0, 0)
     # the 4 GB rule: target rows of 24 K = 192 bytes, so 2^32 / 192 = 22369621 robots pass and one more does not
-    assert host(batch=22369622) == (WCQP_E_UNSUPPORTED, WCQP_E_UNSUPPORTED)
+    assert both(batch=22369622) == (WCQP_E_UNSUPPORTED, WCQP_E_UNSUPPORTED)
     ins, outs = wca.capi.UnicycleInputs(), wca.capi.UnicycleOutputs()
     assert lib.wcqp_unicycle_plan_host(None, B, C.byref(ins), C.byref(outs)) == WCQP_E_INVALID
     assert lib.wcqp_unicycle_plan_host(pl._h, B, None, C.byref(outs)) == WCQP_E_INVALID and lib.wcqp_unicycle_plan_host(pl._h, B, C.byref(ins), None) == WCQP_E_INVALID
@@ -281,13 +276,13 @@ def test_plan_refusals_without_a_device(wca, scen):
     # the host form reads its arrays first: a non-finite entry that is read, a side above 1 - of any robot - and nothing is written
     for bad in (arr("goal", (12, 1), np.nan), arr("goal", (0, 0), np.inf), arr("left0", (3, 0), np.nan), arr("left0", (3, 6), np.inf),
                 arr("right0", (5, 1), -np.inf), arr("right0", (7, 3), np.nan), arr("first_side", 4, 2)):
-        assert host(**bad)[0] == WCQP_E_INVALID
+        assert host(**bad) == WCQP_E_INVALID
     assert (o["n_steps"] == 77).all() and (o["status"] == 77).all() and (o["side"] == 9).all() and (o["target"] == 5.0).all()
     # entries that are not read may hold anything: the sole's z, the rest of the rotation
     junk = np.array(g["left0"], copy=True); junk[:, [2, 4, 5, 7, 8, 9, 10, 11]] = np.nan
-    rc = host(left0=junk)[0]
+    rc = host(left0=junk)
     if wca.device_count() == 0:
-        assert rc == WCQP_E_HIP and host()[0] == WCQP_E_HIP          # no device: an error, never a plan from somewhere else
+        assert rc == WCQP_E_HIP and host() == WCQP_E_HIP          # no device: an error, never a plan from somewhere else
     else:
         assert rc == 0
 

@@ -17,14 +17,16 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WCQP_LIB_PATH") or os.path.join(_HERE, "libwcqp.so")   # override: diagnostic builds only
 
-WCQP_OK = 0
+VERSION = 400
+WCQP_OK = OK = 0
+E_INVALID, E_UNSUPPORTED, E_NUMERIC, E_HIP, E_NOMEM = -1, -2, -3, -4, -5
 STATUS_SOLVED, STATUS_MAX_ITER, STATUS_INFEASIBLE, STATUS_OUTSIDE_HULL, STATUS_NUMERIC, STATUS_STRUCTURE = range(6)
 IK_FORM_QPOASES, IK_FORM_OSQP = 0, 1
 IK_ALG_DEFAULT, IK_ALG_SWEEP, IK_ALG_NULLSPACE, IK_ALG_NULLSPACE_MFMA, IK_ALG_NULLSPACE_16L, IK_ALG_BASE_ELIM = 0, 1, 2, 3, 4, 5
 IK_JAC_AUTO, IK_JAC_MIXED, IK_JAC_GENERAL = 0, 1, 2
-KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = 0, 1, 2
+KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1, 0, 1, 2      # (NONE: get_info's answer without kinematics)
 HULL_ROWS = 8
-MAX_DOF = 32
+MAX_DOF = KIN_MAX_DOF = 32
 IK_STATE_LEN = 87
 
 # every symbol include/wcqp.h declares (tests check the library exports all of them)
@@ -84,6 +86,8 @@ class QpStep(C.Structure):
 
 SLAB_IN = ("x0", "ref", "u_prev", "hull_A", "hull_b", "hull_nc", "J_left", "J_right", "J_neck", "J_com", "q", "state")
 SLAB_OUT = ("u0", "mpc_margin", "dq", "mpc_status", "mpc_active", "ik_status", "active_lower", "active_upper", "iters")
+SLAB_IN_ARRAYS, SLAB_OUT_ARRAYS = 12, 9
+assert (SLAB_IN_ARRAYS, SLAB_OUT_ARRAYS) == (len(SLAB_IN), len(SLAB_OUT))
 
 
 class SlabLayout(C.Structure):
@@ -126,15 +130,31 @@ def qp_enqueue_steps(mpc, ik, batch, steps):
     return done.value
 
 
+class _Handle:
+    """What the handle classes share: close() calls the wcqp_*_destroy entry point `_destroy` names, once; __del__ closes."""
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # (also an object made with __new__ that never got _h)
+            pass
+
+
 PLAN_WAYS_AUTO = -1
 
 
-class QpPlan:
+class QpPlan(_Handle):
     """wcqp_qp_plan_*: the records of qp_enqueue_steps uploaded once, replayed as ONE launch that walks through them; `ways`
     wavefronts share a robot group (way w takes records w, w + ways, ...: records of different ways need their own outputs);
     ways = 0: a work queue over (record, robot group) units - every record needs outputs of its own.
     Records without an IK part (J_left = None in all of them; ik may be None): an MPC-only plan; without an MPC part (x0 = None; mpc may
     be None): an IK-only plan."""
+    _destroy = "wcqp_qp_plan_destroy"
 
     def __init__(self, mpc, ik, batch, steps, ways=1):
         self._h = C.c_void_p()
@@ -143,17 +163,6 @@ class QpPlan:
 
     def enqueue(self, stream=0):
         check(lib().wcqp_qp_plan_enqueue(self._h, stream or None), "wcqp_qp_plan_enqueue")
-
-    def close(self):
-        if self._h:
-            lib().wcqp_qp_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class KinParams(C.Structure):
@@ -191,10 +200,10 @@ class TickParamsExt(C.Structure):
     _fields_ = [("resident_plan", C.c_int32)]
 
 
+TICK_PLANT_INTERNAL, TICK_PLANT_EXTERNAL = 0, 1
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
 TICK_IK_VELOCITY, TICK_IK_POSITION = 0, 1
 POSITION_IK_DEFAULTS = dict(q_reg=None, w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=30, q_min=None, q_max=None)
-KIN_HANDOFF_NONE, KIN_HANDOFF_FUSED, KIN_HANDOFF_DENSE, KIN_HANDOFF_COMPACT = -1, 0, 1, 2
 
 
 class TickInfo(C.Structure):
@@ -272,6 +281,22 @@ class TickOutputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("u0_log", "dq_log", "q_des", "dcm", "com", "mpc_fail", "ik_fail", "hot_try", "hot_hit", "tick", "logger", "active_lower", "active_upper", "zmp_gains",
                                           "measured", "feedback_fail", "q_log", "ik_iters")]
 
+
+# every by-value struct and every integer macro of include/wcqp.h, by header name (tests check layout and values against the header)
+ABI_STRUCTS = {
+    "wcqp_mpc_params": MpcParams, "wcqp_ik_params": IkParams, "wcqp_qp_step": QpStep, "wcqp_slab_layout": SlabLayout, "wcqp_kin_params": KinParams,
+    "wcqp_prepare_params": PrepareParams, "wcqp_tick_params": TickParams, "wcqp_tick_params_ext": TickParamsExt,
+    "wcqp_tick_inputs": TickInputs, "wcqp_tick_outputs": TickOutputs, "wcqp_tick_info": TickInfo, "wcqp_tick_info_ext": TickInfoExt,
+    "wcqp_tick_desired": TickDesired, "wcqp_tick_footsteps": TickFootsteps, "wcqp_tick_replan": TickReplan, "wcqp_tick_plan_window": TickPlanWindow,
+    "wcqp_unicycle_params": UnicycleParams, "wcqp_unicycle_inputs": UnicycleInputs, "wcqp_unicycle_outputs": UnicycleOutputs,
+}
+ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
+    "VERSION OK E_INVALID E_UNSUPPORTED E_NUMERIC E_HIP E_NOMEM "
+    "STATUS_SOLVED STATUS_MAX_ITER STATUS_INFEASIBLE STATUS_OUTSIDE_HULL STATUS_NUMERIC STATUS_STRUCTURE HULL_ROWS MAX_DOF IK_STATE_LEN "
+    "IK_FORM_QPOASES IK_FORM_OSQP IK_ALG_DEFAULT IK_ALG_SWEEP IK_ALG_NULLSPACE IK_ALG_NULLSPACE_MFMA IK_ALG_NULLSPACE_16L IK_ALG_BASE_ELIM "
+    "IK_JAC_AUTO IK_JAC_MIXED IK_JAC_GENERAL PLAN_WAYS_AUTO SLAB_IN_ARRAYS SLAB_OUT_ARRAYS KIN_MAX_DOF "
+    "KIN_HANDOFF_FUSED KIN_HANDOFF_DENSE KIN_HANDOFF_COMPACT TICK_PLANT_INTERNAL TICK_PLANT_EXTERNAL TICK_DCM_MPC TICK_DCM_REACTIVE "
+    "TICK_IK_VELOCITY TICK_IK_POSITION UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT").split()}
 
 _lib: Optional[C.CDLL] = None
 
@@ -359,8 +384,9 @@ def _f64(a) -> np.ndarray:
 
 
 # --------------------------------------------------------------------------------------
-class MpcSolver:
+class MpcSolver(_Handle):
     """Handle over wcqp_mpc_* — the batched stand-in for WalkingController + MPCSolver."""
+    _destroy = "wcqp_mpc_destroy"
 
     def __init__(self, horizon=50, sampling_time=0.01, com_height=0.53, gravity=9.81,
                  Q=None, R=None, convex_hull_tolerance=0.05, feas_tol=0.0):
@@ -372,17 +398,6 @@ class MpcSolver:
         self.N = int(horizon)
         self._h = C.c_void_p()
         check(lib().wcqp_mpc_create(C.byref(self.params), C.byref(self._h)), "wcqp_mpc_create")
-
-    def close(self):
-        if self._h:
-            lib().wcqp_mpc_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def condensed(self):
         Gr = np.zeros((self.N + 1, 2, 2)); Gx = np.zeros((2, 2)); Gu = np.zeros((2, 2)); S0 = np.zeros((2, 2))
@@ -415,8 +430,9 @@ class MpcSolver:
               "wcqp_mpc_solve_device")
 
 
-class IkSolver:
+class IkSolver(_Handle):
     """Handle over wcqp_ik_* — the batched stand-in for WalkingQPIK_{osqp,qpOASES}."""
+    _destroy = "wcqp_ik_destroy"
 
     def __init__(self, form=IK_FORM_QPOASES, dof=23, use_com_as_constraint=True,
                  com_weight=None, neck_weight=None, joint_reg_weights=None, joint_reg_gains=None,
@@ -446,17 +462,6 @@ class IkSolver:
         self.dof = dof
         self._h = C.c_void_p()
         check(lib().wcqp_ik_create(C.byref(self.params), C.byref(self._h)), "wcqp_ik_create")
-
-    def close(self):
-        if self._h:
-            lib().wcqp_ik_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_posture(self, joint_reg_rad):
         """WalkingQPIK::setDesiredJointPosition: a new regularisation posture (rad) for every later solve."""
@@ -495,9 +500,10 @@ def hull_from_feet_host(foot_rect, left_T, right_T, contact):
     return A, b, nc
 
 
-class KinModel:
+class KinModel(_Handle):
     """Handle over wcqp_kin_* - batched forward kinematics + MIXED free-floating Jacobians.
     `model` is a table as returned by `synth.icub_like_model()`."""
+    _destroy = "wcqp_kin_destroy"
 
     def __init__(self, model: dict):
         n = int(model["dof"])
@@ -523,17 +529,6 @@ class KinModel:
         self._h = C.c_void_p()
         check(lib().wcqp_kin_create(C.byref(p), C.byref(self._h)), "wcqp_kin_create")
 
-    def close(self):
-        if self._h:
-            lib().wcqp_kin_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def jacobians_host(self, base, q, state=None):
         base, q = _f64(base), _f64(q)
         B, nc = q.shape[0], 6 + self.dof
@@ -547,11 +542,12 @@ class KinModel:
               "wcqp_kin_jacobians_device")
 
 
-class PrepareSolver:
+class PrepareSolver(_Handle):
     """Handle over wcqp_prepare_* - the batched non-linear IK that gives every robot the posture its walk starts from
     (WalkingModule::prepareRobot -> WalkingIK::computeIK; include/wcqp.h states the problem and the iteration).  kin: a KinModel;
     q_reg: the regularisation posture [dof] in rad; q_min / q_max: joint limits [dof] or None (both).  Defaults follow the reference:
     w_q = 0.5 (joint_regularization_weight), w_n = 1.0 (0: no neck target)."""
+    _destroy = "wcqp_prepare_destroy"
 
     def __init__(self, kin: "KinModel", q_reg, w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=100,
                  q_min=None, q_max=None):
@@ -562,17 +558,6 @@ class PrepareSolver:
                                     q_reg.ctypes.data, *(None if x is None else x.ctypes.data for x in lim))
         self._h = C.c_void_p()
         check(lib().wcqp_prepare_create(kin._h, C.byref(self.params), C.byref(self._h)), "wcqp_prepare_create")
-
-    def close(self):
-        if self._h:
-            lib().wcqp_prepare_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def solve_host(self, left_d, right_d, com_d, q_guess, Rd_neck=None) -> dict:
         """left_d / right_d [B][12] desired sole poses (p 3 | R 9 row-major; the left one is the anchor), com_d [B][3], q_guess [B][dof],
@@ -594,10 +579,11 @@ class PrepareSolver:
                                               state or None, status, iters or None, residual or None, stream or None), "wcqp_prepare_solve_device")
 
 
-class UnicyclePlanner:
+class UnicyclePlanner(_Handle):
     """Handle over wcqp_unicycle_* - footsteps from per-robot goals, the reference's setGoal (include/wcqp.h states the planner).  Defaults
     follow plannerParams.ini where it has the key (angles in radians here); the two saturations are this build's own.  step_ticks: unicycle
     samples per step, ss_ticks + ds_ticks of the walk the footsteps are for; max_steps: K, the row length of side / target."""
+    _destroy = "wcqp_unicycle_destroy"
     DEFAULTS = dict(dT=0.01, reference_position=(0.1, 0.0), unicycle_gain=10.0, slow_when_turning_gain=5.0, max_linear_velocity=0.1,
                     max_angular_velocity=0.5, max_step_length=0.20, min_step_length=0.05, min_width=0.14, nominal_width=0.16,
                     max_angle_variation=np.deg2rad(10.0), min_angle_variation=np.deg2rad(8.0), step_ticks=90, max_steps=8)
@@ -627,17 +613,6 @@ class UnicyclePlanner:
                 p[v] = float(np.deg2rad(values[k]))
         p.update(params)
         return cls(**p)
-
-    def close(self):
-        if self._h:
-            lib().wcqp_unicycle_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def plan_host(self, left0, right0, goals, first_side) -> dict:
         """left0 / right0 [B][12] sole poses (p 3 | R 9 row-major: the desired-foot entries of state0), goals [B][2] in the unicycle's frame,
@@ -670,8 +645,9 @@ class UnicyclePlanner:
         check(lib().wcqp_unicycle_plan_device(self._h, int(batch), C.byref(ins), C.byref(outs), stream or None), "wcqp_unicycle_plan_device")
 
 
-class TickPipeline:
+class TickPipeline(_Handle):
     """Handle over wcqp_tick_* — the device-resident MPC -> glue -> IK tick (configs 4/5)."""
+    _destroy = "wcqp_tick_destroy"
 
     def __init__(self, batch, max_ticks, mpc: MpcSolver, ik: IkSolver, first=0, log_ticks=0,
                  step_ticks=180, ds_ticks=110, k_com=9.0, k_zmp=3.0, noise=1e-4, seed=99,
@@ -781,17 +757,6 @@ class TickPipeline:
         self._h = C.c_void_p()
         check(lib().wcqp_tick_create_ext(C.byref(self.params), C.byref(self.params_ext), C.byref(self._h)), "wcqp_tick_create_ext")
         self._keep = None
-
-    def close(self):
-        if self._h:
-            lib().wcqp_tick_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _holds_plan(self) -> bool:
         """the handle holds a plan: a planned one, or a streamed one with resident_plan"""
