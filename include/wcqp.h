@@ -712,7 +712,8 @@ typedef struct wcqp_tick_params {
      * deviations listed for wcqp_prepare_* apply; the CoM velocity and the twists of the record are not read.
      * wcqp_tick_create, before anything touches the device: WCQP_E_INVALID for an unknown ik_mode and, with POSITION, for any position_ik
      * value wcqp_prepare_create refuses; WCQP_E_UNSUPPORTED for POSITION without planned_trajectories, and together with the EXTERNAL plant,
-     * streamed_trajectories, logger_ticks > 0 or an IK algorithm other than the default.  Every refusal of planned_trajectories applies
+     * streamed_trajectories (the last two unless WCQP_TICK_OPT_POSITION_STREAMED asks for them, wcqp_tick_create_opts below), logger_ticks > 0
+     * or an IK algorithm other than the default.  Every refusal of planned_trajectories applies
      * unchanged (the FUSED hand-off actually taken, the tree).  On a POSITION handle wcqp_tick_upload, wcqp_tick_upload_footsteps,
      * wcqp_tick_replan_footsteps, wcqp_tick_get_plan and wcqp_tick_run (any n_ticks, ticks_per_launch, use_graph, stream) work as on any
      * planned handle; one launch of its kernel walks the ticks of a run call, and nothing runs ahead between ticks (no skew). */
@@ -809,6 +810,46 @@ typedef struct wcqp_tick_params_ext {
     int32_t resident_plan;
 } wcqp_tick_params_ext;
 int wcqp_tick_create_ext(const wcqp_tick_params* params, const wcqp_tick_params_ext* ext, wcqp_tick_t* out);      /* ext NULL: all zero */
+/* Capabilities added after both structs were closed travel as an OPTION LIST: a later capability is one more key, not one more struct or
+ * field.  wcqp_tick_create_ext(p, ext, out) is wcqp_tick_create_opts with the one option {WCQP_TICK_OPT_RESIDENT_PLAN, ext->resident_plan}
+ * (ext NULL: 0), and the three entry points share one body: a parameter block gets the same answer through each of them.  A key that is
+ * absent is 0; every key so far is a switch.  wcqp_tick_create_opts returns WCQP_E_INVALID, before anything touches the device, for a NULL
+ * params or out, n_opts < 0, a NULL opts with n_opts > 0, an unknown key, a key given twice and a value other than 0 / 1.
+ * wcqp_tick_get_option reports the value the handle took (WCQP_E_INVALID for an unknown key or a NULL argument).
+ *
+ * WCQP_TICK_OPT_RESIDENT_PLAN: wcqp_tick_params_ext.resident_plan, above.
+ *
+ * WCQP_TICK_OPT_POSITION_STREAMED = 1: ik_mode = WCQP_TICK_IK_POSITION on a STREAMED handle - the position tick closed on the measured
+ * robot (the reference closes both of its IK paths on getFeedbacks / updateFKSolver / evaluateCoM, DCM, ZMP, WM/src/WalkingModule.cpp:546-575).
+ * The caller's order per tick is the streamed handle's: wcqp_tick_set_desired_* or wcqp_tick_set_desired_from_plan, then
+ * wcqp_tick_set_feedback_* or wcqp_tick_set_sensor_feedback_*, then wcqp_tick_run(h, 1, ...).  Tick t then
+ *   1. runs the chain exactly as the streamed velocity tick runs it, on the measured DCM, CoM and ZMP and on the robot's live record: the
+ *      MPC or the reactive law, gain scheduling where set, the ZMP-CoM law, the hull rows of the robot's own set on a change of contact pair;
+ *   2. forms the targets of the POSITION mode (wcqp_tick_params.ik_mode) from the live record: both soles, (p_star x, p_star y, the
+ *      record's CoM height), RotZ(meanYaw) * neck_additional_rotation;
+ *   3. solves the non-linear IK of wcqp_prepare_* from q_des of tick t - 1 (tick 0: the uploaded q0), clipped into the limits, within
+ *      position_ik.max_iter iterations;
+ *   4. WCQP_STATUS_SOLVED: q_des takes the optimum.  Any other status: ik_fail counts the tick, q_des keeps its value and the robot is
+ *      stopped, as on the planned POSITION handle.
+ * The hot start is the previous RESULT, not the encoders - the reference's own rule (m_guess = m_qResult,
+ * WM/src/WalkingInverseKinematics.cpp:389, 421); setFullModelFeedBack only places joints that are not optimised, and all dof joints are:
+ * q_meas is validated as on every EXTERNAL handle (a non-finite value rejects the robot) but the IK does not read it.  A robot rejected by
+ * either feedback form or by wcqp_tick_set_desired_device is stopped like a robot whose IK failed: its ik_fail and feedback_fail are those
+ * of a streamed VELOCITY handle given the same stages and the same feed.  The deviations of the POSITION mode carry over (the anchor foot,
+ * the neck target, the twists and the CoM-height velocity of the record are not read).  wcqp_tick_download gives q_log, ik_iters,
+ * measured and feedback_fail (dq_log: WCQP_E_UNSUPPORTED).
+ * The option needs, WCQP_E_UNSUPPORTED otherwise and before anything touches the device: ik_mode = POSITION; streamed_trajectories = 1
+ * (hence plant = EXTERNAL); use_kinematics with the FUSED hand-off; the default IK algorithm; logger_ticks = 0; with the MPC a horizon
+ * below 56, as on every streamed handle.  Every position_ik check applies unchanged.  It combines with WCQP_TICK_OPT_RESIDENT_PLAN = 1.
+ * WITHOUT the option POSITION with streamed_trajectories or the EXTERNAL plant stays WCQP_E_UNSUPPORTED through all three entry points. */
+typedef struct wcqp_tick_option {
+    int32_t key;                   /* WCQP_TICK_OPT_* */
+    int32_t value;
+} wcqp_tick_option;
+#define WCQP_TICK_OPT_RESIDENT_PLAN      1   /* = wcqp_tick_params_ext.resident_plan */
+#define WCQP_TICK_OPT_POSITION_STREAMED  2   /* 1: ik_mode POSITION on a streamed (EXTERNAL) handle */
+int wcqp_tick_create_opts(const wcqp_tick_params* params, const wcqp_tick_option* opts, int32_t n_opts, wcqp_tick_t* out);
+int wcqp_tick_get_option(wcqp_tick_t h, int32_t key, int32_t* value);
 int wcqp_tick_destroy(wcqp_tick_t h);
 /* also rewinds to tick 0.  Non-finite inputs: WCQP_E_INVALID, before anything of the handle changes, for a NaN or an Inf in ref_traj,
  * dcm_vel_traj (where it is read), dcm0, com0, u_init or q0 - of any robot: such a value would enter that robot's state on the first tick

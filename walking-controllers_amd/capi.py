@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "wcqp_hull_from_feet_device", "wcqp_hull_from_feet_host",
     "wcqp_kin_create", "wcqp_kin_destroy", "wcqp_kin_jacobians_device", "wcqp_kin_jacobians_host",
     "wcqp_prepare_create", "wcqp_prepare_destroy", "wcqp_prepare_solve_device", "wcqp_prepare_solve_host",
-    "wcqp_tick_create", "wcqp_tick_create_ext", "wcqp_tick_get_info_ext", "wcqp_tick_destroy", "wcqp_tick_upload", "wcqp_tick_run", "wcqp_tick_download", "wcqp_tick_splice_reference",
+    "wcqp_tick_create", "wcqp_tick_create_ext", "wcqp_tick_create_opts", "wcqp_tick_get_option", "wcqp_tick_get_info_ext", "wcqp_tick_destroy", "wcqp_tick_upload", "wcqp_tick_run", "wcqp_tick_download", "wcqp_tick_splice_reference",
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
@@ -200,6 +200,12 @@ class TickParamsExt(C.Structure):
     _fields_ = [("resident_plan", C.c_int32)]
 
 
+class TickOption(C.Structure):
+    """wcqp_tick_option: one (key, value) of the option list of wcqp_tick_create_opts - a capability added since both structs were closed."""
+    _fields_ = [("key", C.c_int32), ("value", C.c_int32)]
+
+
+TICK_OPT_RESIDENT_PLAN, TICK_OPT_POSITION_STREAMED = 1, 2
 TICK_PLANT_INTERNAL, TICK_PLANT_EXTERNAL = 0, 1
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
 TICK_IK_VELOCITY, TICK_IK_POSITION = 0, 1
@@ -285,7 +291,7 @@ class TickOutputs(C.Structure):
 # every by-value struct and every integer macro of include/wcqp.h, by header name (tests check layout and values against the header)
 ABI_STRUCTS = {
     "wcqp_mpc_params": MpcParams, "wcqp_ik_params": IkParams, "wcqp_qp_step": QpStep, "wcqp_slab_layout": SlabLayout, "wcqp_kin_params": KinParams,
-    "wcqp_prepare_params": PrepareParams, "wcqp_tick_params": TickParams, "wcqp_tick_params_ext": TickParamsExt,
+    "wcqp_prepare_params": PrepareParams, "wcqp_tick_params": TickParams, "wcqp_tick_params_ext": TickParamsExt, "wcqp_tick_option": TickOption,
     "wcqp_tick_inputs": TickInputs, "wcqp_tick_outputs": TickOutputs, "wcqp_tick_info": TickInfo, "wcqp_tick_info_ext": TickInfoExt,
     "wcqp_tick_desired": TickDesired, "wcqp_tick_footsteps": TickFootsteps, "wcqp_tick_replan": TickReplan, "wcqp_tick_plan_window": TickPlanWindow,
     "wcqp_unicycle_params": UnicycleParams, "wcqp_unicycle_inputs": UnicycleInputs, "wcqp_unicycle_outputs": UnicycleOutputs,
@@ -296,7 +302,7 @@ ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
     "IK_FORM_QPOASES IK_FORM_OSQP IK_ALG_DEFAULT IK_ALG_SWEEP IK_ALG_NULLSPACE IK_ALG_NULLSPACE_MFMA IK_ALG_NULLSPACE_16L IK_ALG_BASE_ELIM "
     "IK_JAC_AUTO IK_JAC_MIXED IK_JAC_GENERAL PLAN_WAYS_AUTO SLAB_IN_ARRAYS SLAB_OUT_ARRAYS KIN_MAX_DOF "
     "KIN_HANDOFF_FUSED KIN_HANDOFF_DENSE KIN_HANDOFF_COMPACT TICK_PLANT_INTERNAL TICK_PLANT_EXTERNAL TICK_DCM_MPC TICK_DCM_REACTIVE "
-    "TICK_IK_VELOCITY TICK_IK_POSITION UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT").split()}
+    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT").split()}
 
 _lib: Optional[C.CDLL] = None
 
@@ -339,6 +345,8 @@ def lib() -> C.CDLL:
         L.wcqp_prepare_solve_host.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 11
         L.wcqp_tick_create.argtypes = [C.POINTER(TickParams), C.POINTER(C.c_void_p)]
         L.wcqp_tick_create_ext.argtypes = [C.POINTER(TickParams), C.POINTER(TickParamsExt), C.POINTER(C.c_void_p)]
+        L.wcqp_tick_create_opts.argtypes = [C.POINTER(TickParams), C.POINTER(TickOption), C.c_int32, C.POINTER(C.c_void_p)]
+        L.wcqp_tick_get_option.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.wcqp_tick_get_info_ext.argtypes = [C.c_void_p, C.POINTER(TickInfoExt)]
         L.wcqp_tick_destroy.argtypes = [C.c_void_p]
         L.wcqp_tick_upload.argtypes = [C.c_void_p, C.POINTER(TickInputs)]
@@ -673,7 +681,8 @@ class TickPipeline(_Handle):
         0 leaves that filter off.  Needs external_feedback and kin.
         ik_mode: "velocity" (the Jacobian QP-IK whose joint velocities are integrated, the reference's use_QP-IK 1) or "position" (the
         reference's use_QP-IK 0: the non-linear IK of PrepareSolver every tick, hot-started at the previous tick's joints - a mode of a
-        planned handle).  position_ik: dict(q_reg=..., w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=30,
+        planned handle, or of a streamed one: with external_feedback and streamed_trajectories the tick runs its chain on the measured
+        state and the non-linear IK on the live stage, per tick set_desired -> set_feedback / set_sensor_feedback -> run(1)).  position_ik: dict(q_reg=..., w_q=0.5, w_n=1.0, step_cap=0.3, tol_step=1e-12, tol_constraint=1e-10, max_iter=30,
         q_min=None, q_max=None) - the problem's parameters, max_iter the budget PER TICK; q_reg [dof] in rad is required.  `ik` then only
         supplies dof.  download() of such a handle returns q_log [log_ticks][B][dof] and ik_iters [B], and no dq_log.
         resident_plan (with streamed_trajectories): the handle also holds a plan, as a planned handle does - upload_footsteps, upload_goal,
@@ -695,8 +704,9 @@ class TickPipeline(_Handle):
             pik.update(position_ik or {})
             if pik["q_reg"] is None:
                 raise ValueError("ik_mode='position' needs position_ik['q_reg'], the regularisation posture [dof] in rad")
-            if not planned_trajectories:
-                raise ValueError("ik_mode='position' is a mode of a planned handle (planned_trajectories=True)")
+            if not planned_trajectories and not streamed_trajectories:
+                raise ValueError("ik_mode='position' is a mode of a planned handle (planned_trajectories=True) or of a streamed one "
+                                 "(streamed_trajectories=True, external_feedback=True)")
         cuts = dict.fromkeys(SENSOR_FILTERS, 0.0)
         for k, v in (sensor_filters or {}).items():
             if k not in cuts:
@@ -747,16 +757,24 @@ class TickPipeline(_Handle):
                                  float(k_com_stance) if self.gain_sched else 0.0, float(k_zmp_stance) if self.gain_sched else 0.0,
                                  float(zmp_smoothing_time) if self.gain_sched else 0.0, int(self.planned), (C.c_double * 9)(*neck),
                                  int(self.streamed), *(cuts[k] for k in SENSOR_FILTERS))
-        self.params_ext = TickParamsExt(int(self.resident))
         if self.position:
             # (the library copies the three arrays at create)
             arr = [None if pik[k] is None else _f64(np.asarray(pik[k], float).reshape(ik.dof)) for k in ("q_reg", "q_min", "q_max")]
             self.params.ik_mode = TICK_IK_POSITION
             self.params.position_ik = PrepareParams(float(pik["w_q"]), float(pik["w_n"]), float(pik["step_cap"]), float(pik["tol_step"]),
                                                     float(pik["tol_constraint"]), int(pik["max_iter"]), *(None if a is None else a.ctypes.data for a in arr))
+        # the capabilities that travel as options (wcqp_tick_create_opts): a resident plan, POSITION on a streamed handle
+        opts = {TICK_OPT_RESIDENT_PLAN: int(self.resident), TICK_OPT_POSITION_STREAMED: int(self.position and self.streamed)}
+        self.options = (TickOption * len(opts))(*(TickOption(k, v) for k, v in opts.items()))
         self._h = C.c_void_p()
-        check(lib().wcqp_tick_create_ext(C.byref(self.params), C.byref(self.params_ext), C.byref(self._h)), "wcqp_tick_create_ext")
+        check(lib().wcqp_tick_create_opts(C.byref(self.params), self.options, len(opts), C.byref(self._h)), "wcqp_tick_create_opts")
         self._keep = None
+
+    def option(self, key: int) -> int:
+        """The value the handle took of option `key` (TICK_OPT_*; wcqp_tick_get_option)."""
+        v = C.c_int32(-1)
+        check(lib().wcqp_tick_get_option(self._h, int(key), C.byref(v)), "wcqp_tick_get_option")
+        return int(v.value)
 
     def _holds_plan(self) -> bool:
         """the handle holds a plan: a planned one, or a streamed one with resident_plan"""

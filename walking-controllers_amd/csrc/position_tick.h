@@ -32,8 +32,9 @@ struct PosTickDev {
     long long* ik_iters;                       // [B]
     unsigned *alo, *aup;                       // [B] the limits active in the last QP of the last tick (a tick that ends SOLVED; else 0)
 };
-// n_inner ticks from the tick index tick2[phase], one launch (td_dev: the handle's TickDevPL in device memory)
-int position_tick_enqueue(const wcqp_tick::TickDevPL* td_dev, const PosTickDev& a, int batch, bool reactive, bool gain_sched, int phase, int n_inner,
-                          hipStream_t stream);
+// n_inner ticks from the tick index tick2[phase], one launch (td_dev: the handle's TickDevPL in device memory).  external: a streamed
+// handle of the EXTERNAL plant - the chain on the measured state and the robot's live record, n_inner = 1 (WCQP_E_INVALID otherwise)
+int position_tick_enqueue(const wcqp_tick::TickDevPL* td_dev, const PosTickDev& a, int batch, bool external, bool reactive, bool gain_sched, int phase,
+                          int n_inner, hipStream_t stream);
 
 }  // namespace wcqp

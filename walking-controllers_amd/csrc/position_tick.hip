@@ -13,6 +13,8 @@
 //                  until the wave's four robots have stopped or spent the tick's budget
 //   the post step  q_des, q_log, ik_fail, ik_iters, the active limits; lane 0 of workgroup 0 advances the tick index at the end.
 // The handle is not skewed: nothing of tick t + 1 runs before tick t is done, there is no prime launch.  Plain vector loads and stores only.
+// On a streamed handle of the EXTERNAL plant (WCQP_TICK_OPT_POSITION_STREAMED) a launch carries ONE tick, whose chain runs on the measured
+// state and the live record the feedback and desired-stage kernels left: position_tick_external_kernel, the same body.
 #include "position_tick.h"
 #include "prepare_device.h"
 
@@ -21,11 +23,13 @@ namespace {
 using namespace wcqp_prep;
 using wcqp::PosTickDev;
 
-template <bool REACT, bool GS>
-__global__ __launch_bounds__(64) void position_tick_kernel(const wcqp_tick::TickDevPL* tdp, PosTickDev a, int phase, int n_inner) {
-    __shared__ __attribute__((aligned(16))) double kmodel[kKinTabSize];
-    __shared__ __attribute__((aligned(16))) double smem[4][P_PER];
-    __shared__ __attribute__((aligned(16))) double s_hull[4][WCQP_HULL_ROWS][4];      // the MPC's hull rows (1 KB)
+// The body of both kernels below.  EXT: the handle is a streamed one on the EXTERNAL plant (WCQP_TICK_OPT_POSITION_STREAMED, include/wcqp.h) -
+// the chain is the streamed velocity tick's (tick_variant_prime_kernel<true, REACT, GS, true>): the measured DCM, CoM and ZMP are what the
+// feedback or sensor kernel left in the per-axis records, the stage is the robot's ONE live record (plan_rec<true>), which also names the
+// robot's own hull set.  Everything behind the hand-off fence is the same text for both.
+template <bool EXT, bool REACT, bool GS>
+__device__ __forceinline__ void position_tick_body(const wcqp_tick::TickDevPL* tdp, const PosTickDev& a, int phase, int n_inner, double* kmodel,
+                                                   double (*smem)[P_PER], double (*s_hull)[WCQP_HULL_ROWS][4]) {
     // the handle's record stays in device memory (as in the skewed kernels, ik4_device.h: kernel-argument loads would be hoisted out of
     // the loop over ticks and held in registers across the whole body)
     const wcqp_tick::TickDevPL& td = *tdp;
@@ -58,12 +62,14 @@ __global__ __launch_bounds__(64) void position_tick_kernel(const wcqp_tick::Tick
         onL[s_] = (a.pm[0] >> cs[s_]) & 1u; onR[s_] = (a.pm[1] >> cs[s_]) & 1u; onN[s_] = use_neck ? (a.pm[2] >> cs[s_]) & 1u : 0u;
     }
     const int t0 = td.tick2[phase];
+    // (EXT: the feedback, sensor and desired-stage kernels stop a robot they reject by raising ik_fail; read here, at the start of the
+    // launch - which then carries that one tick - it is how the rejection reaches the IK)
     long long fails = td.ik_fail[i], spent = a.ik_iters[i];
 #pragma unroll 1
     for (int k = 0; k < n_inner; ++k) {
         __asm__ volatile("" ::: "memory");           // nothing of the body is hoisted out of the loop over ticks
         const int t = t0 + k;
-        // ================= the chain of tick t (tick_variant_prime_kernel<false, REACT, GS, true>)
+        // ================= the chain of tick t (tick_variant_prime_kernel<EXT, REACT, GS, true>)
         {
             wcqp_tick::TickMpcRegs mreg;
             wcqp_tick::ZmpRegs zreg;
@@ -73,14 +79,14 @@ __global__ __launch_bounds__(64) void position_tick_kernel(const wcqp_tick::Tick
                 wcqp_tick::tick_mpc_issue(td, j, i, t, mreg);
                 if constexpr (GS) rd = wcqp_tick::zmp_vel_issue(td, i, t);
             }
-            const int code = wcqp_tick::plan_code((int)wcqp_tick::plan_rec(td, i, t)[wcqp_tick::kPlanFlags]);
+            const int code = wcqp_tick::plan_code((int)wcqp_tick::plan_rec<EXT>(td, i, t)[wcqp_tick::kPlanFlags]);
             double2 kg = make_double2(0.0, 0.0);
             if constexpr (GS) {
                 wcqp_tick::zmp_state_issue(td, i, zreg);
                 kg = wcqp_tick::zmp_gains_at(td, td.zg, wcqp_tick::zmp_smoother_advance(td, i, j == 0 && live, rd, zreg));
             }
-            if constexpr (REACT) wcqp_tick::tick_react_finish<false, GS>(td, j, i, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd), nullptr, kg);
-            else wcqp_tick::tick_mpc_finish<false, false, GS, true, false>(td, j, i, live, t, mreg, s_hull[grp], nullptr, code, nullptr, kg);
+            if constexpr (REACT) wcqp_tick::tick_react_finish<EXT, GS>(td, j, i, live, t, mreg, r0, wcqp_tick::tick_react_law(td, j, mreg, r0, rd), nullptr, kg);
+            else wcqp_tick::tick_mpc_finish<false, EXT, GS, true, EXT>(td, j, i, live, t, mreg, s_hull[grp], nullptr, code, nullptr, kg);
         }
         // p_star of tick t is in the hand-off row of parity t & 1, written by lanes 0 / 1 of this robot: visible to its other lanes
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(64) void position_tick_kernel(const wcqp_tick::Tick
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         // ================= the targets: the record's soles, (p_star x, p_star y, the record's CoM height), RotZ(meanYaw) neck_add
         {
-            const double* rec = wcqp_tick::plan_rec(td, i, t);
+            const double* rec = wcqp_tick::plan_rec<EXT>(td, i, t);
             const double* hd = td.hand + ((size_t)(t & 1) * batch + i) * wcqp_tick::kHandLen;
             if (j < 12) { S[P_TG + j] = rec[wcqp_tick::kPlanLeft + j]; S[P_TG + TG_RIGHT + j] = rec[wcqp_tick::kPlanRight + j]; }
             if (j < 2) S[P_TG + TG_COM + j] = hd[j];
@@ -141,14 +147,40 @@ __global__ __launch_bounds__(64) void position_tick_kernel(const wcqp_tick::Tick
     if (blockIdx.x == 0 && threadIdx.x == 0) td.tick2[1 - phase] = t0 + n_inner;
 }
 
+// a planned handle with the internal plant: the ticks of a run call
+template <bool REACT, bool GS>
+__global__ __launch_bounds__(64) void position_tick_kernel(const wcqp_tick::TickDevPL* tdp, PosTickDev a, int phase, int n_inner) {
+    __shared__ __attribute__((aligned(16))) double kmodel[kKinTabSize];
+    __shared__ __attribute__((aligned(16))) double smem[4][P_PER];
+    __shared__ __attribute__((aligned(16))) double s_hull[4][WCQP_HULL_ROWS][4];      // the MPC's hull rows (1 KB)
+    position_tick_body<false, REACT, GS>(tdp, a, phase, n_inner, kmodel, smem, s_hull);
+}
+// a streamed handle on the EXTERNAL plant: ONE tick, behind its desired stage and its feedback
+template <bool REACT, bool GS>
+__global__ __launch_bounds__(64) void position_tick_external_kernel(const wcqp_tick::TickDevPL* tdp, PosTickDev a, int phase) {
+    __shared__ __attribute__((aligned(16))) double kmodel[kKinTabSize];
+    __shared__ __attribute__((aligned(16))) double smem[4][P_PER];
+    __shared__ __attribute__((aligned(16))) double s_hull[4][WCQP_HULL_ROWS][4];
+    position_tick_body<true, REACT, GS>(tdp, a, phase, 1, kmodel, smem, s_hull);
+}
+
 }  // namespace
 
 namespace wcqp {
 
-int position_tick_enqueue(const wcqp_tick::TickDevPL* td_dev, const PosTickDev& a, int batch, bool reactive, bool gain_sched, int phase, int n_inner,
-                          hipStream_t stream) {
+int position_tick_enqueue(const wcqp_tick::TickDevPL* td_dev, const PosTickDev& a, int batch, bool external, bool reactive, bool gain_sched, int phase,
+                          int n_inner, hipStream_t stream) {
     const dim3 grid((unsigned)((batch + 3) / 4)), block(64);
-    if (reactive) {
+    if (external) {
+        if (n_inner != 1) return WCQP_E_INVALID;
+        if (reactive) {
+            if (gain_sched) hipLaunchKernelGGL((position_tick_external_kernel<true, true>), grid, block, 0, stream, td_dev, a, phase);
+            else hipLaunchKernelGGL((position_tick_external_kernel<true, false>), grid, block, 0, stream, td_dev, a, phase);
+        } else {
+            if (gain_sched) hipLaunchKernelGGL((position_tick_external_kernel<false, true>), grid, block, 0, stream, td_dev, a, phase);
+            else hipLaunchKernelGGL((position_tick_external_kernel<false, false>), grid, block, 0, stream, td_dev, a, phase);
+        }
+    } else if (reactive) {
         if (gain_sched) hipLaunchKernelGGL((position_tick_kernel<true, true>), grid, block, 0, stream, td_dev, a, phase, n_inner);
         else hipLaunchKernelGGL((position_tick_kernel<true, false>), grid, block, 0, stream, td_dev, a, phase, n_inner);
     } else {

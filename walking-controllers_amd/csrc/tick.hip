@@ -156,7 +156,8 @@ int enqueue_tick(wcqp_tick_s* h, int phase, hipStream_t s, int n_inner = 1, int 
     const int N = wcqp::mpc_horizon(h->mpc);
     if (n_inner > h->ticks_per_launch) return WCQP_E_INVALID;
     if (h->position)
-        return wcqp::position_tick_enqueue(static_cast<const TickDevPL*>(h->d_dev), h->pos, B, d.reactive != 0, d.gain_sched != 0, d.phase, n_inner, s);
+        return wcqp::position_tick_enqueue(static_cast<const TickDevPL*>(h->d_dev), h->pos, B, h->external, d.reactive != 0, d.gain_sched != 0, d.phase,
+                                           n_inner, s);
     if (h->kin && !d.kin_fused) {
         h->kt.phase = d.phase;
         const int rck = wcqp::kin_enqueue_tick(h->kin, B, h->kt, d.q_des, h->J_left, h->J_right, h->J_neck, h->J_com, d.state, s);
@@ -205,13 +206,26 @@ struct SensorStage {
 
 }  // namespace
 
-extern "C" {
+// An option list as its values by key (0 where a key is absent).  What the list itself can be refused for - a negative count, a NULL list
+// with a count, an unknown key, a key given twice - is refused here; what a VALUE can be refused for, by the rule of its key in create_tick
+constexpr int kTickOptKeys = WCQP_TICK_OPT_POSITION_STREAMED;       // keys are 1 .. kTickOptKeys
+struct TickOptions { int32_t value[kTickOptKeys + 1] = {}; };
+static int parse_tick_options(const wcqp_tick_option* opts, int32_t n_opts, TickOptions* o) {
+    if (n_opts < 0 || (n_opts > 0 && !opts)) return WCQP_E_INVALID;
+    bool seen[kTickOptKeys + 1] = {};
+    for (int32_t k = 0; k < n_opts; ++k) {
+        const int32_t key = opts[k].key;
+        if (key < 1 || key > kTickOptKeys || seen[key]) return WCQP_E_INVALID;
+        seen[key] = true;
+        o->value[key] = opts[k].value;
+    }
+    return WCQP_OK;
+}
 
-int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) { return wcqp_tick_create_ext(params, nullptr, out); }
-
-int wcqp_tick_create_ext(const wcqp_tick_params* params, const wcqp_tick_params_ext* ext, wcqp_tick_t* out) {
-    if (!params || !out || params->batch < 1 || params->max_ticks < 1) return WCQP_E_INVALID;
-    const wcqp_tick_params_ext px = ext ? *ext : wcqp_tick_params_ext{};
+// the one body of wcqp_tick_create, wcqp_tick_create_ext and wcqp_tick_create_opts (which has refused a NULL params or out, and the list):
+// every other refusal is stated here, once
+static int create_tick(const wcqp_tick_params* params, const TickOptions& opt, wcqp_tick_t* out) {
+    if (params->batch < 1 || params->max_ticks < 1) return WCQP_E_INVALID;
     if (params->step_ticks < 2 || params->ds_ticks < 0 || params->ds_ticks > params->step_ticks) return WCQP_E_INVALID;
     if (params->ik.dof != kDof) return WCQP_E_UNSUPPORTED;
     // ZMP gain scheduling: finite stance gains, a finite smoothing time > 0 (refused before anything touches the device)
@@ -245,20 +259,24 @@ int wcqp_tick_create_ext(const wcqp_tick_params* params, const wcqp_tick_params_
             (params->dcm_controller == WCQP_TICK_DCM_MPC && params->mpc.horizon >= kGainsLdsStages))
             return WCQP_E_UNSUPPORTED;
     }
+    // the options: every key so far is a switch
+    for (int key = 1; key <= kTickOptKeys; ++key) if (opt.value[key] != 0 && opt.value[key] != 1) return WCQP_E_INVALID;
     // a resident plan: a capability of a streamed handle
-    const bool resident = px.resident_plan != 0;
-    if (px.resident_plan != 0 && px.resident_plan != 1) return WCQP_E_INVALID;
+    const bool resident = opt.value[WCQP_TICK_OPT_RESIDENT_PLAN] != 0;
     if (resident && !streamed) return WCQP_E_UNSUPPORTED;
-    // the POSITION mode: the problem's parameters by the rules of wcqp_prepare_create, then what the mode does not run with
+    // the POSITION mode: the problem's parameters by the rules of wcqp_prepare_create, then what the mode does not run with - a mode of a
+    // planned handle with the internal plant or, with WCQP_TICK_OPT_POSITION_STREAMED, of a streamed handle (which the block above has
+    // held to the EXTERNAL plant, the FUSED hand-off, no logger rows, the default IK algorithm and an MPC horizon below kGainsLdsStages)
     if (params->ik_mode != WCQP_TICK_IK_VELOCITY && params->ik_mode != WCQP_TICK_IK_POSITION) return WCQP_E_INVALID;
     const bool position = params->ik_mode == WCQP_TICK_IK_POSITION;
+    const bool position_streamed = opt.value[WCQP_TICK_OPT_POSITION_STREAMED] != 0;
     if (position) {
         if (wcqp::prepare_check_scalars(&params->position_ik) != WCQP_OK || wcqp::prepare_check_arrays(&params->position_ik) != WCQP_OK) return WCQP_E_INVALID;
         const int alg = params->ik.algorithm;
-        if (!planned || streamed || params->plant != WCQP_TICK_PLANT_INTERNAL || params->logger_ticks > 0 ||
-            (alg != WCQP_IK_ALG_DEFAULT && alg != WCQP_IK_ALG_BASE_ELIM))
-            return WCQP_E_UNSUPPORTED;
+        if (position_streamed ? !streamed : (!planned || streamed || params->plant != WCQP_TICK_PLANT_INTERNAL)) return WCQP_E_UNSUPPORTED;
+        if (params->logger_ticks > 0 || (alg != WCQP_IK_ALG_DEFAULT && alg != WCQP_IK_ALG_BASE_ELIM)) return WCQP_E_UNSUPPORTED;
     }
+    if (position_streamed && !position) return WCQP_E_UNSUPPORTED;
     // the sensor form's low-pass filters: a cut frequency > 0 switches one on - where there is a sensor form at all
     const double cuts[3] = {params->joint_velocity_cut_frequency, params->wrench_cut_frequency, params->com_cut_frequency};
     int filt_mask = 0;
@@ -464,6 +482,30 @@ int wcqp_tick_create_ext(const wcqp_tick_params* params, const wcqp_tick_params_
         h->variant.react = d.reactive != 0; h->variant.gs = d.gain_sched != 0; h->variant.pl = h->planned || h->streamed;
     }
     *out = h;
+    return WCQP_OK;
+}
+
+extern "C" {
+
+int wcqp_tick_create(const wcqp_tick_params* params, wcqp_tick_t* out) { return wcqp_tick_create_ext(params, nullptr, out); }
+
+int wcqp_tick_create_ext(const wcqp_tick_params* params, const wcqp_tick_params_ext* ext, wcqp_tick_t* out) {
+    const wcqp_tick_option one{WCQP_TICK_OPT_RESIDENT_PLAN, ext ? ext->resident_plan : 0};
+    return wcqp_tick_create_opts(params, &one, 1, out);
+}
+
+int wcqp_tick_create_opts(const wcqp_tick_params* params, const wcqp_tick_option* opts, int32_t n_opts, wcqp_tick_t* out) {
+    if (!params || !out) return WCQP_E_INVALID;
+    TickOptions opt;
+    if (const int rc = parse_tick_options(opts, n_opts, &opt); rc != WCQP_OK) return rc;
+    return create_tick(params, opt, out);
+}
+
+int wcqp_tick_get_option(wcqp_tick_t h, int32_t key, int32_t* value) {
+    if (!h || !value) return WCQP_E_INVALID;
+    if (key == WCQP_TICK_OPT_RESIDENT_PLAN) *value = h->resident ? 1 : 0;
+    else if (key == WCQP_TICK_OPT_POSITION_STREAMED) *value = h->position && h->streamed ? 1 : 0;
+    else return WCQP_E_INVALID;
     return WCQP_OK;
 }
 

@@ -135,7 +135,8 @@ struct wcqp_tick_s {
     wcqp_tick::TickDevPL dpl(const wcqp_tick::TickDev& base) const { wcqp_tick::TickDevPL g; static_cast<wcqp_tick::TickDevGS&>(g) = dgs(base); g.pl = pl; return g; }
     // ik_mode = POSITION (a planned handle): the non-linear IK runs every tick in position_tick_kernel, which takes `pos` beside the
     // handle's TickDevPL in device memory; the chain's state, hand-off rows and live hull rows are the skewed handle's, but nothing is
-    // skewed - no prime launch, no tick ahead
+    // skewed - no prime launch, no tick ahead.  With WCQP_TICK_OPT_POSITION_STREAMED the handle is a streamed one instead (`streamed`,
+    // `external`, perhaps `resident`, with everything such a handle allocates) and position_tick_external_kernel runs its one tick per call
     bool position = false;
     wcqp::PosTickDev pos{};
 };
