@@ -184,6 +184,17 @@ int wcqp_mpc_solve_host(wcqp_mpc_t h, int32_t batch,
  *   contact[B]              bit 0 = left foot in contact, bit 1 = right foot in contact
  * outputs hull_A[B][8][2], hull_b[B][8], hull_nc[B] (0 when no foot is in contact — the
  * reference refuses that case, cpp:406-410; the MPC kernel then reports the unconstrained u0).
+ * The rows are the polygon; their COUNT is not a function of the polygon alone.  When corners are
+ * collinear (parallel feet side by side or in tandem: four corners on one line) the builder's
+ * orientation test decides on rounding errors, a corner within an ulp of an edge may be kept as a
+ * vertex, and that edge is then delivered twice: consecutive rows that agree to ~1e-15.  Compare
+ * rows as sets, not index by index; the MPC takes such rows as they are.
+ * Coincident corners are merged: two feet at one pose give that foot's polygon.
+ * A set with no area: corners on one segment (a foot rolled by pi/2 projects on a line) give
+ * hull_nc = 2, the finite rows +-n.u <= +-n.a of the segment's line, which do not bound it along
+ * the segment (more than two distinct corners on a line: 2 to 8 such rows, by the rounding above,
+ * never more); corners that all coincide (a zero foot_rect) have no direction and give hull_nc = 2
+ * with both rows NaN, which the MPC answers with WCQP_STATUS_NUMERIC.
  * ===================================================================================== */
 int wcqp_hull_from_feet_device(int32_t batch, const double* foot_rect,
                                const double* left_T, const double* right_T, const uint8_t* contact,

@@ -17,8 +17,14 @@ HULL_PAD_B = 1e30
 
 
 def convex_hull_ccw(pts: np.ndarray) -> np.ndarray:
-    """Andrew monotone chain; CCW vertices without collinear points."""
+    """Andrew monotone chain; CCW vertices without collinear points (up to the rounding of the orientation test: a corner within an ulp of
+    an edge may stay, and its edge then appears twice).  Coincident points are one point: a point equal to its predecessor in the sorted
+    order is dropped - as a vertex it would end an edge of length 0, a NaN row.  When every point coincides there is no direction at all:
+    the point is returned twice, and hull_rows makes two NaN rows of it (the documented non-finite case of include/wcqp.h)."""
     P = sorted(map(tuple, np.asarray(pts, float)))
+    P = [p for i, p in enumerate(P) if i == 0 or p != P[i - 1]]
+    if len(P) == 1:
+        P = P * 2
     if len(P) <= 2:
         return np.array(P)
 
@@ -33,7 +39,10 @@ def convex_hull_ccw(pts: np.ndarray) -> np.ndarray:
         while len(up) >= 2 and cross(up[-2], up[-1], p) <= 0:
             up.pop()
         up.append(p)
-    return np.array(lo[:-1] + up[:-1])
+    V = lo[:-1] + up[:-1]
+    if len(V) > HULL_ROWS:      # only when every point lies on one line to rounding, where both passes may keep every point: the segment
+        V = [P[0], P[-1]]
+    return np.array(V)
 
 
 def hull_rows(pts: np.ndarray):

@@ -149,7 +149,8 @@ def test_mpc_properties_at_full_size(wca):
 
 def test_hull_rows_from_foot_poses(wca, qs):
     """§8f-3: device hull builder against the oracle's builder (oracle/hull_spec.py) and the
-    C++ host mirror's convention; then straight into the MPC kernel."""
+    C++ host mirror's convention; then straight into the MPC kernel.  General position only (independent random yaws, feet that never
+    touch), where rows compare index by index; parallel, coincident and tilted feet are in test_hull_stances.py."""
     from oracle import hull_spec as hs
     rng = np.random.default_rng(7)
     B = 300

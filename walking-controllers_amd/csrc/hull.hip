@@ -10,7 +10,7 @@
 
 namespace {
 
-__global__ void hull_from_feet_kernel(int batch, const double* __restrict__ rect,
+__global__ void __launch_bounds__(128) hull_from_feet_kernel(int batch, const double* __restrict__ rect,
                                       const double* __restrict__ left_T, const double* __restrict__ right_T,
                                       const unsigned char* __restrict__ contact,
                                       double* __restrict__ hull_A, double* __restrict__ hull_b, int* __restrict__ hull_nc) {
@@ -30,7 +30,7 @@ __global__ void hull_from_feet_kernel(int batch, const double* __restrict__ rect
 // The tick pipeline with per-tick kinematics: the three row sets (left foot, right foot, both in contact) of every robot
 // from the DESIRED foot poses in its pose block (entries 24..35 left, 36..47 right).  One thread per (robot, contact pair).
 struct RectArg { double v[8]; };
-__global__ void hull_tables_kernel(int batch, RectArg rect, const double* __restrict__ state, int state_len,
+__global__ void __launch_bounds__(128) hull_tables_kernel(int batch, RectArg rect, const double* __restrict__ state, int state_len,
                                    double* __restrict__ tab_A, double* __restrict__ tab_b, int* __restrict__ tab_nc) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= batch * 3) return;

@@ -19,7 +19,7 @@ PlanRect plan_rect(const wcqp_tick_s* h) {
     for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
     return r;
 }
-__global__ void plan_hull_sets_kernel(int n, PlanRect rect, const double* __restrict__ rec, const long long* __restrict__ at,
+__global__ void __launch_bounds__(128) plan_hull_sets_kernel(int n, PlanRect rect, const double* __restrict__ rec, const long long* __restrict__ at,
                                       const int* __restrict__ code, double* __restrict__ A, double* __restrict__ b, int* __restrict__ nc) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
