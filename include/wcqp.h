@@ -894,7 +894,8 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in);
  * that upload), for a NULL required pointer, n_steps outside 0..K, a side other than 0 / 1, a non-finite value (of a step the robot
  * takes, of the state0 entries read, q0, com0, dcm0, u_init, lift or the deltas), a tick count below 1 or final_ds_ticks below 0.
  * The call always rewinds to tick 0; wcqp_tick_replan_footsteps below regenerates a running plan from a later stage.  Not offered, and
- * refused by construction rather than silently ignored: per-step timings, device-pointer footsteps. */
+ * refused by construction rather than silently ignored: per-step timings, device-pointer footsteps (of a running walk,
+ * wcqp_tick_replan_goals plans the footsteps on the device and keeps them there). */
 typedef struct wcqp_tick_footsteps {      /* HOST pointers, copied at the call */
     int32_t max_steps;                    /* K: row length of the per-step arrays, >= 0 */
     const int32_t* n_steps;               /* [B] 0..K steps robot i takes */
@@ -934,7 +935,8 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
  * that is not uploaded, a NULL pointer, first_ds_ticks < 1, and for a robot that replans: n_steps outside 0..K', a side above 1 or a
  * non-finite target of a step it takes, M_i = 0 or < -1, M_i < the ticks enqueued so far (within one wcqp_tick_run call the kernel reads a
  * stage ahead, between calls nothing is ahead), M_i >= T, M_i below the stage its current plan was generated from, or a stage M_i that
- * lies in a single support of its current plan.  Not offered: replanning a classically uploaded plan, per-step timings, device pointers. */
+ * lies in a single support of its current plan.  Not offered: replanning a classically uploaded plan, per-step timings, device pointers
+ * (the goal form below, wcqp_tick_replan_goals, keeps the footsteps on the device: they are planned there and never visit the host). */
 typedef struct wcqp_tick_replan {         /* HOST pointers, copied before the call returns */
     const int32_t* merge_stage;           /* [B] M_i >= 1: robot i's plan is regenerated from stage M_i on; -1: robot i keeps its plan */
     int32_t max_steps;                    /* K': row length of the per-step arrays, >= 0 */
@@ -944,6 +946,69 @@ typedef struct wcqp_tick_replan {         /* HOST pointers, copied before the ca
     int32_t first_ds_ticks;               /* >= 1: stages of double support from M_i before the first new step */
 } wcqp_tick_replan;
 int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream);
+
+typedef struct wcqp_unicycle_s* wcqp_unicycle_t;       /* the unicycle planner's handle, stated at the end of this header */
+
+/* "Robot i, go there" for a walk that is running, on the device and enqueue-only: the reference's setGoal(x, y) -
+ * WalkingModule::setPlannerInput, askNewTrajectories and updateTrajectories (WM/src/WalkingModule.cpp:500-535, 1059-1145, 1263-1308).
+ * For every robot that replans, ONE kernel (goal_plan_kernel) plans footsteps with the unicycle planner stated below from the two
+ * desired soles of plan record M_i towards goal[i]; the three kernels of wcqp_tick_replan_footsteps then regenerate the plan from M_i
+ * from those footsteps - THE REPLANNED PLAN is the one defined above, with K' = the planner's max_steps -, the set builder follows, and
+ * one copy brings the result rows back into pinned memory of the handle, with an event behind it.  All of it is enqueued on `stream`
+ * behind the ticks already enqueued; the call synchronises with nothing but the previous replan's hold on the handle's staging block,
+ * and the footsteps never visit the host.  `planner` is read at the call only.  Valid between wcqp_tick_run calls, on every handle
+ * that holds a generated plan: planned handles, the POSITION tick, resident plans of streamed handles.
+ *   Merge stage  merge_stage[i] = WCQP_TICK_MERGE_KEEP: robot i keeps its plan, none of its rows is read (its goal may be a NaN).
+ *               M_i >= 1: taken as given and checked exactly as wcqp_tick_replan_footsteps checks it.  WCQP_TICK_MERGE_AUTO: with the plan in
+ *               force of robot i generated from stage O with a first double support of fo stages and n steps, per = ss + ds, step k's
+ *               single support starts at s_k = O + fo + k per; the plan's MERGE POINTS are s_k + ss for k = 0 .. n - 2 - the first stage of
+ *               each inner double support - and every stage >= L, L = s_{n-1} + ss (n = 0: L = O): the last double support and standing.
+ *               t0 = the ticks enqueued so far, plus 1 when a resident plan's stage has been staged (the term of the replan rule).
+ *               M_i = the smallest merge point >= max(t0 + min_lead_ticks, 1, O).  M_i >= T: the robot keeps its plan, status
+ *               WCQP_GOAL_TOO_LATE.  (csrc/goal_merge.h is the rule, tests/helpers/goal_merge.py restates it.)
+ *               This is the three-way rule of setPlannerInput (WalkingModule.cpp:1263-1308), whose merge points are the same stages
+ *               counted from the current tick, with a lead of 20: the front merge point if it is > 20 ticks away; with the front one <= 20
+ *               and more than one merge point, the second; otherwise 20 ticks on.  The two rules coincide while per > min_lead_ticks: the
+ *               second merge point is per stages behind the first and so beyond the lead, and "otherwise" is the last double support or
+ *               standing, where every stage is a merge point here.  They differ for per <= min_lead_ticks: the reference then takes the
+ *               second merge point although it is nearer than the lead, this rule goes on to the first one the lead allows.  They also
+ *               differ by one stage at the boundary (a merge point exactly min_lead_ticks away is taken here, passed over there).
+ *   First side   first_side[i] = 0 / 1: the foot that swings first.  WCQP_TICK_SIDE_AUTO: the fixed-frame foot of record M_i - 1 - bit 2 of its
+ *               flags set: the left foot, 0; clear: the right, 1 - and the feet keep alternating across the merge, the reference's
+ *               askNewTrajectories(..., !m_isLeftFixedFrame.front(), ...).  The host keeps no sides: the kernel reads the record.
+ *   Degenerate   a robot whose desired point overflows ends WCQP_UNICYCLE_INVALID_INPUT on the device (the host cannot see it: the soles
+ *               are there): it regenerates with n_steps = 0 and comes to a stop at M_i.  WCQP_UNICYCLE_STUCK and _TRUNCATED keep the steps
+ *               found so far, as the host composition of plan_host and wcqp_tick_replan_footsteps does.
+ * Refusals, all checked on the host before anything changes, the handle exactly as it was: WCQP_E_UNSUPPORTED as
+ * wcqp_tick_replan_footsteps (no planned_trajectories or resident plan, a plan that was not generated); WCQP_E_INVALID for a NULL handle,
+ * planner, struct or goal, a handle that is not uploaded, first_ds_ticks < 1, min_lead_ticks < 0, and for a robot that does not KEEP: a
+ * merge_stage below -2 or an explicit one that breaks the rules of wcqp_tick_replan_footsteps, a first_side other than 0, 1 or 255, a
+ * non-finite goal.  Every robot KEEP or TOO_LATE: WCQP_OK, nothing enqueued.
+ * The step count of a goal-replanned robot is known to the host only when the rows are back: every later call that needs it
+ * (wcqp_tick_replan_footsteps, wcqp_tick_replan_goals, wcqp_tick_get_goal_result) first waits for THAT call's event, nothing else. */
+#define WCQP_TICK_MERGE_KEEP  (-1)   /* robot keeps its plan; none of its rows is read */
+#define WCQP_TICK_MERGE_AUTO  (-2)   /* the rule above chooses M_i                      */
+#define WCQP_TICK_SIDE_AUTO   255    /* the fixed-frame foot of stage M_i - 1 swings first */
+#define WCQP_GOAL_KEPT        (-1)   /* status of a robot that was not asked to replan  */
+#define WCQP_GOAL_TOO_LATE    (-2)   /* AUTO found no merge stage below T: plan kept    */
+typedef struct wcqp_tick_goals {     /* HOST pointers, copied before the call returns */
+    const double*  goal;             /* [B][2], the argument of setGoal, unicycle frame   */
+    const int32_t* merge_stage;      /* [B] KEEP / AUTO / M_i >= 1; NULL = AUTO for all   */
+    const uint8_t* first_side;       /* [B] 0 / 1 / SIDE_AUTO;      NULL = SIDE_AUTO for all */
+    int32_t first_ds_ticks;          /* >= 1, as wcqp_tick_replan.first_ds_ticks          */
+    int32_t min_lead_ticks;          /* AUTO only, >= 0; the reference's 20               */
+} wcqp_tick_goals;
+int wcqp_tick_replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_tick_goals* g, void* stream);
+/* What the last wcqp_tick_replan_goals call decided and planned: waits for that call's event only (not for the stream, not for the
+ * device).  merge_stage, first_side and status are the values TAKEN; status is the planner's WCQP_UNICYCLE_* for a robot that
+ * replanned, WCQP_GOAL_KEPT / WCQP_GOAL_TOO_LATE for one that did not, and every row of such a robot is zero.  K' = the max_steps of
+ * the planner of that call.  WCQP_E_INVALID for a NULL handle or struct, or before any such call. */
+typedef struct wcqp_tick_goal_result { /* HOST pointers, any may be NULL; rows of KEPT / TOO_LATE robots zero */
+    int32_t* merge_stage; uint8_t* first_side; int32_t* status;    /* [B] the values TAKEN; status: WCQP_UNICYCLE_* or WCQP_GOAL_* */
+    int32_t* n_steps; uint8_t* side; double* target;               /* [B], [B][K'], [B][K'][3], K' = the planner's max_steps */
+    double* desired_point; double* unicycle_end;                   /* [B][2], [B][3] */
+} wcqp_tick_goal_result;
+int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out);   /* waits for the last replan_goals call only */
 /* The plan a planned handle holds, however it was uploaded: n robots from robot0, m stages from stage0, stage-major per robot.
  * Synchronises.  Every pointer but two works on any planned handle, however it was uploaded.  The two: a non-NULL dcm_vel_traj makes
  * the call return WCQP_E_UNSUPPORTED on a handle that keeps no velocity (neither the reactive controller nor gain scheduling), and a
@@ -1182,7 +1247,7 @@ typedef struct wcqp_unicycle_outputs {   /* n_steps, status and - for K > 0 - si
     double*  unicycle_end;               /* [B][3] or NULL */
 } wcqp_unicycle_outputs;
 
-typedef struct wcqp_unicycle_s* wcqp_unicycle_t;
+/* (wcqp_unicycle_t: declared above, ahead of wcqp_tick_replan_goals, which takes one) */
 
 /* Refusals need no device: WCQP_E_INVALID for a NULL pointer, a non-finite scalar or one outside the ranges above (d_x = 0,
  * min_width > nominal_width and min_step_length >= max_step_length among them), step_ticks < 1 or max_steps < 0. */

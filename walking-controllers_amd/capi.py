@@ -42,7 +42,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
-    "wcqp_tick_upload_footsteps", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps",
+    "wcqp_tick_upload_footsteps", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
     "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
@@ -251,6 +251,25 @@ class TickReplan(C.Structure):
                 ("first_ds_ticks", C.c_int32)]
 
 
+TICK_MERGE_KEEP, TICK_MERGE_AUTO, TICK_SIDE_AUTO = -1, -2, 255
+GOAL_KEPT, GOAL_TOO_LATE = -1, -2
+
+
+class TickGoals(C.Structure):
+    """wcqp_tick_goals: per robot the goal, the merge stage (KEEP / AUTO / M_i; NULL: AUTO) and the first swing foot (0 / 1 / SIDE_AUTO; NULL:
+    SIDE_AUTO) of wcqp_tick_replan_goals."""
+    _fields_ = [("goal", C.c_void_p), ("merge_stage", C.c_void_p), ("first_side", C.c_void_p), ("first_ds_ticks", C.c_int32), ("min_lead_ticks", C.c_int32)]
+
+
+GOAL_RESULT = (("merge_stage", (), np.int32), ("first_side", (), np.uint8), ("status", (), np.int32), ("n_steps", (), np.int32),
+               ("side", ("K",), np.uint8), ("target", ("K", 3), np.float64), ("desired_point", (2,), np.float64), ("unicycle_end", (3,), np.float64))
+
+
+class TickGoalResult(C.Structure):
+    """wcqp_tick_goal_result: what wcqp_tick_get_goal_result fills (GOAL_RESULT: [B] rows; K = the planner's max_steps)."""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in GOAL_RESULT]
+
+
 UNICYCLE_DONE, UNICYCLE_TRUNCATED, UNICYCLE_STUCK, UNICYCLE_INVALID_INPUT = range(4)
 
 
@@ -294,6 +313,7 @@ ABI_STRUCTS = {
     "wcqp_prepare_params": PrepareParams, "wcqp_tick_params": TickParams, "wcqp_tick_params_ext": TickParamsExt, "wcqp_tick_option": TickOption,
     "wcqp_tick_inputs": TickInputs, "wcqp_tick_outputs": TickOutputs, "wcqp_tick_info": TickInfo, "wcqp_tick_info_ext": TickInfoExt,
     "wcqp_tick_desired": TickDesired, "wcqp_tick_footsteps": TickFootsteps, "wcqp_tick_replan": TickReplan, "wcqp_tick_plan_window": TickPlanWindow,
+    "wcqp_tick_goals": TickGoals, "wcqp_tick_goal_result": TickGoalResult,
     "wcqp_unicycle_params": UnicycleParams, "wcqp_unicycle_inputs": UnicycleInputs, "wcqp_unicycle_outputs": UnicycleOutputs,
 }
 ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
@@ -302,7 +322,8 @@ ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
     "IK_FORM_QPOASES IK_FORM_OSQP IK_ALG_DEFAULT IK_ALG_SWEEP IK_ALG_NULLSPACE IK_ALG_NULLSPACE_MFMA IK_ALG_NULLSPACE_16L IK_ALG_BASE_ELIM "
     "IK_JAC_AUTO IK_JAC_MIXED IK_JAC_GENERAL PLAN_WAYS_AUTO SLAB_IN_ARRAYS SLAB_OUT_ARRAYS KIN_MAX_DOF "
     "KIN_HANDOFF_FUSED KIN_HANDOFF_DENSE KIN_HANDOFF_COMPACT TICK_PLANT_INTERNAL TICK_PLANT_EXTERNAL TICK_DCM_MPC TICK_DCM_REACTIVE "
-    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT").split()}
+    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
+    "TICK_MERGE_KEEP TICK_MERGE_AUTO TICK_SIDE_AUTO GOAL_KEPT GOAL_TOO_LATE").split()}
 
 _lib: Optional[C.CDLL] = None
 
@@ -364,6 +385,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_upload_footsteps.argtypes = [C.c_void_p, C.POINTER(TickInputs), C.POINTER(TickFootsteps)]
         L.wcqp_tick_get_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TickPlanWindow)]
         L.wcqp_tick_replan_footsteps.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.c_void_p]
+        L.wcqp_tick_replan_goals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickGoals), C.c_void_p]
+        L.wcqp_tick_get_goal_result.argtypes = [C.c_void_p, C.POINTER(TickGoalResult)]
         L.wcqp_unicycle_create.argtypes = [C.POINTER(UnicycleParams), C.POINTER(C.c_void_p)]
         L.wcqp_unicycle_destroy.argtypes = [C.c_void_p]
         L.wcqp_unicycle_plan_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(UnicycleInputs), C.POINTER(UnicycleOutputs), C.c_void_p]
@@ -903,6 +926,43 @@ class TickPipeline(_Handle):
             for k in out:
                 out[k][sel] = plan[k]
         self.replan_footsteps(merge, out, first_ds_ticks, stream=stream)
+        return out
+
+    def replan_goals(self, goals, planner: "UnicyclePlanner", first_ds_ticks: int, merge_stage=None, first_side=None, min_lead_ticks: int = 20,
+                     stream: Optional[int] = None) -> None:
+        """"Robot i, go there" for a generated walk that is running, on the device and enqueue-only (wcqp_tick_replan_goals, which states the
+        rules): goals [B][2]; merge_stage [B] of TICK_MERGE_KEEP / TICK_MERGE_AUTO / M_i >= 1 (None: AUTO for all - the first merge point of
+        the robot's plan at least min_lead_ticks ahead); first_side [B] or a scalar of 0 / 1 / TICK_SIDE_AUTO (None: AUTO for all - the feet
+        keep alternating).  The footsteps are planned and the plan regenerated on `stream` behind the ticks already enqueued; nothing is
+        waited for and nothing returned - goal_result() reads what was decided.  A goal row of a robot that keeps its plan is not read."""
+        if not self._holds_plan():
+            raise ValueError("a goal was given to a handle created without planned_trajectories=True (or resident_plan=True)")
+        goals = _f64(goals)
+        merge = None if merge_stage is None else np.ascontiguousarray(merge_stage, dtype=np.int32)
+        fs = None if first_side is None else np.asarray(first_side)
+        if fs is not None:
+            fs = np.full(self.batch, fs) if fs.ndim == 0 else fs
+            if ((fs < 0) | ((fs > 1) & (fs != TICK_SIDE_AUTO))).any():
+                raise ValueError("first_side is 0 (left), 1 (right) or TICK_SIDE_AUTO")
+            fs = np.ascontiguousarray(fs, dtype=np.uint8)
+        if goals.shape != (self.batch, 2) or (merge is not None and merge.shape != (self.batch,)) or (fs is not None and fs.shape != (self.batch,)):
+            raise ValueError("shapes: goals %s merge_stage %s first_side %s" % (goals.shape, None if merge is None else merge.shape, None if fs is None else fs.shape))
+        if int(min_lead_ticks) < 0 or int(first_ds_ticks) < 1:
+            raise ValueError("min_lead_ticks >= 0 and first_ds_ticks >= 1")
+        g = TickGoals(goals.ctypes.data, None if merge is None else merge.ctypes.data, None if fs is None else fs.ctypes.data, int(first_ds_ticks), int(min_lead_ticks))
+        check(lib().wcqp_tick_replan_goals(self._h, planner._h, C.byref(g), stream or None), "wcqp_tick_replan_goals")
+        self._goal_K = planner.max_steps
+
+    def goal_result(self) -> dict:
+        """What the last replan_goals call decided and planned (wcqp_tick_get_goal_result; waits for that call only): per robot the
+        merge_stage and first_side TAKEN, status (UNICYCLE_*, or GOAL_KEPT / GOAL_TOO_LATE with every other row zero), n_steps, side [B][K],
+        target [B][K][3], desired_point [B][2], unicycle_end [B][3]."""
+        K = getattr(self, "_goal_K", None)
+        if K is None:
+            raise ValueError("goal_result() before any replan_goals()")
+        out = {k: np.zeros((self.batch,) + tuple(K if d == "K" else d for d in shp), dt) for k, shp, dt in GOAL_RESULT}
+        res = TickGoalResult(**{k: (v.ctypes.data if v.size else None) for k, v in out.items()})
+        check(lib().wcqp_tick_get_goal_result(self._h, C.byref(res)), "wcqp_tick_get_goal_result")
         return out
 
     def plan_window(self, robot0: int = 0, n: Optional[int] = None, stage0: int = 0, m: Optional[int] = None, keys=None) -> dict:

@@ -516,6 +516,7 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     for (void* p : h->allocs) (void)hipFree(p);
     for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
     for (StagedBlock* b : {&h->splice, &h->rp, &h->run}) b->release();
+    h->goal.release();
     for (hipEvent_t e : h->gen_ev) if (e) (void)hipEventDestroy(e);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->kin) wcqp_kin_destroy(h->kin);

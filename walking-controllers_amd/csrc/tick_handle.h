@@ -119,6 +119,36 @@ struct wcqp_tick_s {
     } gp;
     // its per-call device memory (footsteps, robot and tile lists, footprint tables, set table), guarded behind the call's kernels
     StagedBlock rp;
+    // wcqp_tick_replan_goals: the footsteps are planned on the device, so a goal-replanned robot's gp.n_steps is known only once the
+    // call's result rows have come back into `host` (pinned; one copy behind the call's kernels, `ev` recorded behind it).  Until then the
+    // robot is `owed`: whatever reads gp.n_steps calls settle() first, which waits for that event alone and folds the values in.  The
+    // rows stay for wcqp_tick_get_goal_result, with what the host decided per robot at the call: the merge stage taken (0: none) and
+    // WCQP_GOAL_KEPT / WCQP_GOAL_TOO_LATE (0: the device's status row holds)
+    struct GoalCall {
+        char* host = nullptr; size_t host_cap = 0;
+        hipEvent_t ev = nullptr;
+        bool called = false, pending = false;
+        int K = 0;                                        // the planner's max_steps at the call
+        size_t o_target = 0, o_dp = 0, o_ue = 0, o_n = 0, o_status = 0, o_side = 0, o_fs = 0, bytes = 0;      // the rows' offsets in `host`
+        std::vector<int> owed, merge, decided;
+        int wait() {
+            if (pending) { WCQP_HIP_TRY(hipEventSynchronize(ev)); pending = false; }
+            return WCQP_OK;
+        }
+        void release() {
+            if (host) (void)hipHostFree(host);
+            if (ev) (void)hipEventDestroy(ev);
+            host = nullptr; host_cap = 0; ev = nullptr; pending = false; called = false; owed.clear();
+        }
+    } goal;
+    int settle() {
+        if (const int rc = goal.wait(); rc != WCQP_OK) return rc;
+        if (goal.owed.empty()) return WCQP_OK;
+        const int32_t* n = reinterpret_cast<const int32_t*>(goal.host + goal.o_n);
+        for (int i : goal.owed) gp.n_steps[i] = n[i];
+        goal.owed.clear();
+        return WCQP_OK;
+    }
     // streamed_trajectories (an EXTERNAL handle): pl.rec holds ONE record per robot, the stage wcqp_tick_set_desired_* handed over for the next
     // tick, pl.set_* one row set per robot; `planned` stays false (the splice of the DCM reference keeps working)
     bool streamed = false, desired_set = false;

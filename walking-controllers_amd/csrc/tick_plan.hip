@@ -1,11 +1,13 @@
 // The trajectories of a tick handle (tick_handle.h; tick.hip holds the rest of it): planned ones uploaded per stage (wcqp_tick_upload of a
-// planned handle), walks generated from footsteps and replanned at a merge stage (plan_gen.hip holds those kernels), the streamed stage
-// of the next tick, and the plan read back.  See include/wcqp.h for the contract.
+// planned handle), walks generated from footsteps and replanned at a merge stage - from the caller's footsteps or from goals, planned here
+// on the device (plan_gen.hip holds the plan kernels, unicycle_device.h the planner) -, the streamed stage of the next tick, and the plan read back.  See include/wcqp.h for the contract.
 #include <cmath>
 #include <cstring>
 #include <vector>
 #include "tick_handle.h"
 #include "plan_gen.h"
+#include "goal_merge.h"
+#include "unicycle_device.h"
 
 namespace {
 
@@ -274,6 +276,200 @@ int wcqp::upload_plan(wcqp_tick_s* h, const wcqp_tick_inputs* in) {
     return rc;
 }
 
+namespace {
+
+// Footsteps from goals for the robots a replan lists (wcqp_tick_replan_goals): one lane per listed robot, 64 per wave, one wave per
+// workgroup, as unicycle_kernel - the same per-robot body (unicycle_device.h), a latency chain of K x D RK4 steps that wants no more
+// than to stay clear of scratch.  Lane `slot` takes robot i = robots[slot]: the sole entries the planner reads of plan record M_i =
+// origin[i] (a stage with both feet down), the flag word of record M_i - 1 (M_i >= 1) for a first_side of WCQP_TICK_SIDE_AUTO - the
+// fixed-frame foot of that stage swings first: bit 2 set, the left one (0) -, and row i of the call's result rows, which the replan kernels
+// behind it read as their footstep lists.  A robot that keeps its plan has no lane; dead lanes of the last wave repeat the last listed
+// robot and store nothing.  Plain vector loads and stores, 64-bit offsets (the records pass 4 GB), no LDS.
+struct GoalPlanDev {
+    wcqp_unicycle::UniPar p;
+    const double* rec;              // the plan records [B][traj_len][kPlanRec]
+    const int* origin;              // [B] M_i of the listed robots
+    const int* robots;              // [n_robots]
+    const double* goal;             // [B][2]
+    const unsigned char* side_in;   // [B] 0 / 1 / WCQP_TICK_SIDE_AUTO
+    unsigned char* first_side;      // [B] the side taken
+    wcqp_unicycle::UniRows out;
+    int n_robots, traj_len;
+};
+__global__ __launch_bounds__(64) void goal_plan_kernel(GoalPlanDev a) {
+    const long raw = (long)blockIdx.x * 64 + threadIdx.x;
+    const bool live = raw < a.n_robots;
+    const size_t i = (size_t)a.robots[live ? raw : (long)a.n_robots - 1];
+    const double* r = a.rec + (i * (size_t)a.traj_len + (size_t)a.origin[i]) * (size_t)kPlanRec;
+    const unsigned flags = (unsigned)r[kPlanFlags - kPlanRec];
+    int sw = a.side_in[i];
+    if (sw == WCQP_TICK_SIDE_AUTO) sw = (flags & 4u) ? 0 : 1;
+    const double *l = r + kPlanLeft, *q = r + kPlanRight;
+    const wcqp_unicycle::UniStart in{l[0], l[1], l[3], l[6], q[0], q[1], q[3], q[6], a.goal[i * 2], a.goal[i * 2 + 1], sw};
+    if (live) a.first_side[i] = (unsigned char)sw;
+    wcqp_unicycle::plan_robot(a.p, in, a.out, i, live);
+}
+
+// the plan in force of robot i, and the stage below which the enqueued ticks have consumed it: a resident plan's tick whose stage has
+// been staged counts as enqueued, its live record holds that stage (gp.n_steps: settled by the caller)
+wcqp_goal::PlanInForce plan_in_force(const wcqp_tick_s* h, size_t i) {
+    const auto& gp = h->gp;
+    return {gp.origin[i], gp.first_ds[i], gp.n_steps[i], gp.ss, gp.ds};
+}
+int consumed_stages(const wcqp_tick_s* h) { return h->ticks_enqueued + (h->plan_staged ? 1 : 0); }
+
+// What a replan needs of the host per call, for footsteps from the caller's lists and from goals alike: per robot the merge stage (-1: it
+// keeps its plan), the compaction into robots and (robot, tile) pairs, and the sets that survive
+struct ReplanCall {
+    std::vector<int> merge, robots, keep, tiles;
+    explicit ReplanCall(size_t B) : merge(B, -1), keep(B, 0) {}
+};
+
+// Robot i joins the call at merge stage M (already found allowed: wcqp_goal::merge_allowed).  n_new: the steps of its new plan, or -1 where
+// the device plans them.  Its surviving sets are those of stages <= M (a set of stage M itself is built from the feet the new plan starts
+// from); the new plan's sets follow them in the robot's `cap` slots.  That they fit needs no n_new: cap (wcqp_tick_upload_footsteps)
+// bounds the steps that START at a stage <= max_ticks for ANY footstep list - a step occupies ss + 1 stages or more - and the stitched
+// plan is one such list, so the count below is a check of the arithmetic where n_new is known and is not evaluated where it is not.
+int replan_admit(const wcqp_tick_s* h, size_t i, int M, int fd, int n_new, ReplanCall& c) {
+    const auto& gp = h->gp;
+    const int per = gp.ss + gp.ds, O = gp.origin[i], fo = gp.first_ds[i], no = gp.n_steps[i];
+    int c0 = gp.keep[i];
+    const int reach = M < h->p.max_ticks ? M : h->p.max_ticks;
+    for (int k = 0; k < no; ++k) {
+        const long long s_k = (long long)O + fo + (long long)k * per;
+        c0 += (s_k <= reach ? 1 : 0) + (s_k + gp.ss <= reach ? 1 : 0);
+    }
+    int fresh = 0;
+    for (int k = 0; k < n_new; ++k) {
+        const long long s_k = (long long)M + fd + (long long)k * per;
+        fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + gp.ss <= h->p.max_ticks ? 1 : 0);
+    }
+    if (c0 < 1 || c0 + fresh > gp.cap) return WCQP_E_INVALID;      // (cannot happen: see cap in wcqp_tick_upload_footsteps)
+    c.merge[i] = M; c.keep[i] = c0;
+    c.robots.push_back((int)i);
+    const int n_tile = (h->d.traj_len + 63) / 64;
+    for (int tl = M / 64; tl < n_tile; ++tl) { c.tiles.push_back((int)i); c.tiles.push_back(tl); }
+    return WCQP_OK;
+}
+
+// where the footsteps of a replan come from: the caller's lists (wcqp_tick_replan_footsteps), or goals the device plans from
+// (wcqp_tick_replan_goals: goal [B][2], first_side [B] or NULL for WCQP_TICK_SIDE_AUTO everywhere, the planner's parameters)
+struct ReplanSource {
+    const wcqp_tick_replan* lists;
+    const double* goal; const uint8_t* first_side; const wcqp_unicycle::UniPar* par;
+};
+
+// Everything behind the checks, for a call that lists a robot at least: the call's device block - what the host hands over first (one
+// copy, taken NOW, once the previous replan has left the block), then what the kernels write for each other -, the kernels on `st` behind
+// the ticks already enqueued, the guard, and the plan in force of the listed robots.  From goals, goal_plan_kernel runs first and the
+// replan kernels' n_steps / side / target aim at the rows it writes; the result rows travel back in one copy, with an event behind it,
+// and gp.n_steps of the listed robots is owed until then (tick_handle.h: GoalCall).  Synchronises with nothing but the block's own wait.
+int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const ReplanSource& src, hipStream_t st) {
+    const TickDev& d = h->d;
+    auto& gp = h->gp;
+    auto& gc = h->goal;
+    const bool goals = src.lists == nullptr;
+    const int cap = gp.cap;
+    const size_t B = (size_t)d.batch, BK = B * (size_t)K, nr = c.robots.size(), nt = c.tiles.size() / 2, nslots = B * (size_t)cap;
+    // the result rows of a goal call, one contiguous run: doubles, then the 32-bit rows, then the bytes
+    const size_t r_target = 0, r_dp = r_target + BK * 24, r_ue = r_dp + B * 16, r_n = r_ue + B * 24, r_status = r_n + B * 4, r_side = r_status + B * 4,
+                 r_fs = r_side + BK, r_bytes = r_fs + B;
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_org = carve(B * 4), o_base = carve(B * 4), o_rob = carve(nr * 4), o_tile = carve(nt * 8);
+    const size_t o_n = goals ? 0 : carve(B * 4), o_side = goals ? 0 : carve(BK), o_tg = goals ? 0 : carve(BK * 24);
+    const size_t o_goal = goals ? carve(B * 16) : 0, o_fsin = goals ? carve(B) : 0;
+    const size_t front = off;
+    const size_t o_res = goals ? carve(r_bytes) : 0;
+    const size_t o_tab = carve(B * (size_t)(K + 1) * kFpRec * 8), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
+    std::vector<char> blob(front, 0);
+    {
+        int* org = reinterpret_cast<int*>(blob.data() + o_org); int* base = reinterpret_cast<int*>(blob.data() + o_base);
+        for (size_t i = 0; i < B; ++i) {
+            const bool on = c.merge[i] != -1;
+            org[i] = on ? c.merge[i] : -1;
+            base[i] = (int)(i * (size_t)cap) + (on ? c.keep[i] - 1 : 0);
+        }
+        std::memcpy(blob.data() + o_rob, c.robots.data(), nr * 4); std::memcpy(blob.data() + o_tile, c.tiles.data(), nt * 8);
+        if (!goals) {
+            int* nn = reinterpret_cast<int*>(blob.data() + o_n);
+            for (size_t i = 0; i < B; ++i) nn[i] = c.merge[i] != -1 ? src.lists->n_steps[i] : 0;
+            if (BK > 0) { std::memcpy(blob.data() + o_side, src.lists->side, BK); std::memcpy(blob.data() + o_tg, src.lists->target, BK * 24); }
+        } else {
+            // (a goal of a robot that keeps its plan may be anything, a NaN too: its row is zero here and no lane reads it)
+            double* gl = reinterpret_cast<double*>(blob.data() + o_goal);
+            for (int i : c.robots) { gl[(size_t)i * 2] = src.goal[(size_t)i * 2]; gl[(size_t)i * 2 + 1] = src.goal[(size_t)i * 2 + 1]; }
+            unsigned char* fs = reinterpret_cast<unsigned char*>(blob.data() + o_fsin);
+            for (size_t i = 0; i < B; ++i) fs[i] = src.first_side ? src.first_side[i] : (unsigned char)WCQP_TICK_SIDE_AUTO;
+        }
+    }
+    if (goals) {      // the pinned rows the results come back into (the previous call's have been folded in: the caller settled)
+        if (!gc.ev) WCQP_HIP_TRY(hipEventCreateWithFlags(&gc.ev, hipEventDisableTiming));
+        if (gc.host_cap < r_bytes) {
+            if (gc.host) (void)hipHostFree(gc.host);
+            gc.host = nullptr; gc.host_cap = 0;
+            if (hipHostMalloc(reinterpret_cast<void**>(&gc.host), r_bytes, hipHostMallocDefault) != hipSuccess) return WCQP_E_NOMEM;
+            gc.host_cap = r_bytes;
+        }
+    }
+    if (const int rc = h->rp.take(h->copy_stream, blob.data(), front, off); rc != WCQP_OK) return rc;
+    char* buf = static_cast<char*>(h->rp.mem.ptr);
+    char* res = buf + o_res;
+    PlanGenDev g = plan_gen_of(h, K);
+    g.origin = reinterpret_cast<const int*>(buf + o_org);
+    g.set_base = reinterpret_cast<const int*>(buf + o_base); g.robots = reinterpret_cast<const int*>(buf + o_rob);
+    g.tiles = reinterpret_cast<const int2*>(buf + o_tile);
+    g.n_steps = reinterpret_cast<const int*>(goals ? res + r_n : buf + o_n);
+    g.side = reinterpret_cast<const unsigned char*>(goals ? res + r_side : buf + o_side);
+    g.target = reinterpret_cast<const double*>(goals ? res + r_target : buf + o_tg);
+    g.table = reinterpret_cast<double*>(buf + o_tab);
+    g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = reinterpret_cast<int*>(buf + o_code);
+    g.h0 = d.com_h0.get(); g.n_robots = (int)nr; g.n_tiles = (int)nt; g.first_ds = fd;
+    // in the caller's stream order, behind the ticks already enqueued: no pointer a tick or a captured graph holds changes, and the set
+    // slots written are those past each robot's surviving ones, which no stage below its merge stage names
+    if (goals) {
+        WCQP_HIP_TRY(hipMemsetAsync(res, 0, r_bytes, st));      // (the rows of robots without a lane read back as zeros)
+        GoalPlanDev a{};
+        a.p = *src.par; a.rec = h->plan_rec; a.origin = g.origin; a.robots = g.robots;
+        a.goal = reinterpret_cast<const double*>(buf + o_goal); a.side_in = reinterpret_cast<const unsigned char*>(buf + o_fsin);
+        a.first_side = reinterpret_cast<unsigned char*>(res + r_fs);
+        a.out = wcqp_unicycle::UniRows{reinterpret_cast<int32_t*>(res + r_n), reinterpret_cast<int32_t*>(res + r_status), reinterpret_cast<uint8_t*>(res + r_side),
+                                       reinterpret_cast<double*>(res + r_target), reinterpret_cast<double*>(res + r_dp), reinterpret_cast<double*>(res + r_ue)};
+        a.n_robots = (int)nr; a.traj_len = d.traj_len;
+        hipLaunchKernelGGL(goal_plan_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, st, a);
+        WCQP_HIP_TRY(hipGetLastError());
+    }
+    WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
+    if (const int rc = wcqp::plan_replan_enqueue(g, st); rc != WCQP_OK) return rc;
+    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
+                       h->set_A, h->set_b, h->set_nc);
+    WCQP_HIP_TRY(hipGetLastError());
+    if (goals) {
+        WCQP_HIP_TRY(hipMemcpyAsync(gc.host, res, r_bytes, hipMemcpyDeviceToHost, st));
+        WCQP_HIP_TRY(hipEventRecord(gc.ev, st));
+    }
+    if (const int rc = h->rp.guard(st); rc != WCQP_OK) return rc;
+    for (int i : c.robots) {
+        gp.origin[i] = c.merge[i]; gp.first_ds[i] = fd; gp.keep[i] = c.keep[i];
+        if (!goals) gp.n_steps[i] = src.lists->n_steps[i];
+    }
+    if (goals) {
+        gc.pending = true; gc.owed = c.robots; gc.K = K;
+        gc.o_target = r_target; gc.o_dp = r_dp; gc.o_ue = r_ue; gc.o_n = r_n; gc.o_status = r_status; gc.o_side = r_side; gc.o_fs = r_fs; gc.bytes = r_bytes;
+    }
+    return WCQP_OK;
+}
+
+// what both replans ask of the handle before they look at a robot
+int replan_ready(const wcqp_tick_s* h) {
+    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
+    if (!h->uploaded) return WCQP_E_INVALID;
+    if (!h->generated) return WCQP_E_UNSUPPORTED;        // (a classically uploaded plan has no known timeline)
+    return WCQP_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps) {
@@ -347,7 +543,7 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
         auto& gp = h->gp;
         gp.origin.assign(B, 0); gp.first_ds.assign(B, steps->first_ds_ticks); gp.keep.assign(B, 1);
         gp.n_steps.assign(steps->n_steps, steps->n_steps + B);
-        h->rp.pending = false;      // (the device was synchronised above)
+        h->rp.pending = false; h->goal.pending = false; h->goal.owed.clear();      // (the device was synchronised above)
     }
     WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
     WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
@@ -370,88 +566,82 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
 
 int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) {
     if (!h || !rp) return WCQP_E_INVALID;
-    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
-    if (!h->uploaded) return WCQP_E_INVALID;
-    if (!h->generated) return WCQP_E_UNSUPPORTED;        // (a classically uploaded plan has no known timeline)
-    const TickDev& d = h->d;
-    auto& gp = h->gp;
-    const size_t B = (size_t)d.batch;
-    const int K = rp->max_steps, T = d.traj_len, fd = rp->first_ds_ticks, per = gp.ss + gp.ds, cap = gp.cap;
+    if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    const size_t B = (size_t)h->d.batch;
+    const int K = rp->max_steps, T = h->d.traj_len, fd = rp->first_ds_ticks, per = h->gp.ss + h->gp.ds;
     // everything is checked here, in closed form, before anything changes: a refused call leaves the handle exactly as it was
     if (!rp->merge_stage || !rp->n_steps || K < 0 || (K > 0 && (!rp->side || !rp->target)) || fd < 1) return WCQP_E_INVALID;
-    if ((long long)T + fd + (long long)K * per + gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
-    std::vector<int> robots, keep(B, 0);
-    std::vector<int> tiles;       // (robot, tile) pairs
-    const int n_tile = (T + 63) / 64;
+    if ((long long)T + fd + (long long)K * per + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (the step counts a goal call still owes)
+    ReplanCall c(B);
     for (size_t i = 0; i < B; ++i) {
         const int M = rp->merge_stage[i];
         if (M == -1) continue;                            // (the robot keeps its plan: nothing of its rows is read)
         // stage 0 is the initial state's, stages the enqueued ticks have consumed stay (within one wcqp_tick_run call the kernel reads a stage
-        // ahead, between calls nothing is ahead: M >= ticks_enqueued is the condition - a resident plan's tick whose stage has been staged
-        // counts as enqueued, its live record holds that stage), and a plan is cut only behind its own origin
-        if (M < 1 || M < h->ticks_enqueued + (h->plan_staged ? 1 : 0) || M >= T || M < gp.origin[i]) return WCQP_E_INVALID;
+        // ahead, between calls nothing is ahead), a plan is cut only behind its own origin, and the merge stage has both feet in contact in
+        // the plan in force: not inside one of its single supports
+        if (!wcqp_goal::merge_allowed(plan_in_force(h, i), M, consumed_stages(h), T)) return WCQP_E_INVALID;
         if (!footsteps_valid(i, K, rp->n_steps, rp->side, rp->target)) return WCQP_E_INVALID;
-        const int n = rp->n_steps[i];
-        // the merge stage has both feet in contact in the plan in force: not inside one of its single supports
-        const int O = gp.origin[i], fo = gp.first_ds[i], no = gp.n_steps[i], r = M - O;
-        if (r >= fo) { const int k = (r - fo) / per, u = (r - fo) - k * per; if (k < no && u < gp.ss) return WCQP_E_INVALID; }
-        // the sets that survive: those of stages <= M (a set of stage M itself is built from the feet the new plan starts from)
-        int c0 = gp.keep[i];
-        const int reach = M < h->p.max_ticks ? M : h->p.max_ticks;
-        for (int k = 0; k < no; ++k) {
-            const long long s_k = (long long)O + fo + (long long)k * per;
-            c0 += (s_k <= reach ? 1 : 0) + (s_k + gp.ss <= reach ? 1 : 0);
-        }
-        int fresh = 0;
-        for (int k = 0; k < n; ++k) {
-            const long long s_k = (long long)M + fd + (long long)k * per;
-            fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + gp.ss <= h->p.max_ticks ? 1 : 0);
-        }
-        if (c0 < 1 || c0 + fresh > cap) return WCQP_E_INVALID;      // (cannot happen: see cap in wcqp_tick_upload_footsteps)
-        keep[i] = c0;
-        robots.push_back((int)i);
-        for (int tl = M / 64; tl < n_tile; ++tl) { tiles.push_back((int)i); tiles.push_back(tl); }
+        if (const int rc = replan_admit(h, i, M, fd, rp->n_steps[i], c); rc != WCQP_OK) return rc;
     }
-    if (robots.empty()) return WCQP_OK;
-    // the call's device memory: what the host hands over first (one copy), then what the kernels write for each other
-    const size_t BK = B * (size_t)K, nr = robots.size(), nt = tiles.size() / 2, nslots = B * (size_t)cap;
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_org = carve(B * 4), o_n = carve(B * 4), o_base = carve(B * 4), o_rob = carve(nr * 4), o_tile = carve(nt * 8), o_side = carve(BK),
-                 o_tg = carve(BK * 24), front = off, o_tab = carve(B * (size_t)(K + 1) * kFpRec * 8), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
-    std::vector<char> blob(front, 0);
-    {
-        int* org = reinterpret_cast<int*>(blob.data() + o_org); int* nn = reinterpret_cast<int*>(blob.data() + o_n);
-        int* base = reinterpret_cast<int*>(blob.data() + o_base);
-        for (size_t i = 0; i < B; ++i) {
-            const bool on = rp->merge_stage[i] != -1;
-            org[i] = on ? rp->merge_stage[i] : -1; nn[i] = on ? rp->n_steps[i] : 0;
-            base[i] = (int)(i * (size_t)cap) + (on ? keep[i] - 1 : 0);
+    if (c.robots.empty()) return WCQP_OK;
+    return replan_enqueue(h, c, K, fd, ReplanSource{rp, nullptr, nullptr, nullptr}, (hipStream_t)stream);
+}
+
+int wcqp_tick_replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_tick_goals* gl, void* stream) {
+    if (!h || !planner || !gl || !gl->goal) return WCQP_E_INVALID;
+    if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    const wcqp_unicycle::UniPar* par = wcqp::unicycle_par(planner);
+    const size_t B = (size_t)h->d.batch;
+    const int K = par->K, T = h->d.traj_len, fd = gl->first_ds_ticks, per = h->gp.ss + h->gp.ds;
+    if (fd < 1 || gl->min_lead_ticks < 0) return WCQP_E_INVALID;
+    if ((long long)T + fd + (long long)K * per + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (AUTO and the checks read the step counts of the plans in force)
+    ReplanCall c(B);
+    std::vector<int> taken(B, 0), decided(B, 0);
+    const int t0 = consumed_stages(h);
+    for (size_t i = 0; i < B; ++i) {
+        int M = gl->merge_stage ? gl->merge_stage[i] : WCQP_TICK_MERGE_AUTO;
+        if (M == WCQP_TICK_MERGE_KEEP) { decided[i] = WCQP_GOAL_KEPT; continue; }      // (none of its rows is read)
+        if (M < WCQP_TICK_MERGE_AUTO || M == 0) return WCQP_E_INVALID;
+        const uint8_t fs = gl->first_side ? gl->first_side[i] : (uint8_t)WCQP_TICK_SIDE_AUTO;
+        if (fs > 1 && fs != WCQP_TICK_SIDE_AUTO) return WCQP_E_INVALID;
+        if (!std::isfinite(gl->goal[i * 2]) || !std::isfinite(gl->goal[i * 2 + 1])) return WCQP_E_INVALID;
+        const wcqp_goal::PlanInForce pf = plan_in_force(h, i);
+        if (M == WCQP_TICK_MERGE_AUTO) {
+            M = wcqp_goal::merge_auto(pf, t0, gl->min_lead_ticks, T);
+            if (M == wcqp_goal::kTooLate) { decided[i] = WCQP_GOAL_TOO_LATE; continue; }
+        } else if (!wcqp_goal::merge_allowed(pf, M, t0, T)) {
+            return WCQP_E_INVALID;
         }
-        std::memcpy(blob.data() + o_rob, robots.data(), nr * 4); std::memcpy(blob.data() + o_tile, tiles.data(), nt * 8);
-        if (BK > 0) { std::memcpy(blob.data() + o_side, rp->side, BK); std::memcpy(blob.data() + o_tg, rp->target, BK * 24); }
+        if (const int rc = replan_admit(h, i, M, fd, -1, c); rc != WCQP_OK) return rc;
+        taken[i] = M;
     }
-    // the caller's HOST arrays are taken NOW, once the previous replan has left the block
-    if (const int rc = h->rp.take(h->copy_stream, blob.data(), front, off); rc != WCQP_OK) return rc;
-    char* buf = static_cast<char*>(h->rp.mem.ptr);
-    PlanGenDev g = plan_gen_of(h, K);
-    g.origin = reinterpret_cast<const int*>(buf + o_org); g.n_steps = reinterpret_cast<const int*>(buf + o_n);
-    g.set_base = reinterpret_cast<const int*>(buf + o_base); g.robots = reinterpret_cast<const int*>(buf + o_rob);
-    g.tiles = reinterpret_cast<const int2*>(buf + o_tile); g.side = reinterpret_cast<const unsigned char*>(buf + o_side);
-    g.target = reinterpret_cast<const double*>(buf + o_tg); g.table = reinterpret_cast<double*>(buf + o_tab);
-    g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = reinterpret_cast<int*>(buf + o_code);
-    g.h0 = d.com_h0.get(); g.n_robots = (int)nr; g.n_tiles = (int)nt; g.first_ds = fd;
-    // in the caller's stream order, behind the ticks already enqueued: no pointer a tick or a captured graph holds changes, and the set
-    // slots written are those past each robot's surviving ones, which no stage below its merge stage names
-    hipStream_t st = (hipStream_t)stream;
-    WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
-    const int rc = wcqp::plan_replan_enqueue(g, st);
-    if (rc != WCQP_OK) return rc;
-    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
-                       h->set_A, h->set_b, h->set_nc);
-    WCQP_HIP_TRY(hipGetLastError());
-    if (const int rc = h->rp.guard(st); rc != WCQP_OK) return rc;
-    for (int i : robots) { gp.origin[i] = rp->merge_stage[i]; gp.first_ds[i] = fd; gp.n_steps[i] = rp->n_steps[i]; gp.keep[i] = keep[i]; }
+    if (!c.robots.empty())
+        if (const int rc = replan_enqueue(h, c, K, fd, ReplanSource{nullptr, gl->goal, gl->first_side, par}, (hipStream_t)stream); rc != WCQP_OK) return rc;
+    auto& gc = h->goal;
+    gc.called = true; gc.K = K; gc.merge.swap(taken); gc.decided.swap(decided);
+    return WCQP_OK;
+}
+
+int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out) {
+    if (!h || !out) return WCQP_E_INVALID;
+    auto& gc = h->goal;
+    if (!gc.called) return WCQP_E_INVALID;
+    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (waits for that call's own event, not for the stream or the device)
+    const size_t B = (size_t)h->d.batch, K = (size_t)gc.K;
+    for (size_t i = 0; i < B; ++i) {
+        const bool dev = gc.decided[i] == 0;              // (a robot that had a lane: its rows came back)
+        const char* r = gc.host;
+        if (out->merge_stage) out->merge_stage[i] = gc.merge[i];
+        if (out->first_side) out->first_side[i] = dev ? (uint8_t)r[gc.o_fs + i] : 0;
+        if (out->status) out->status[i] = dev ? reinterpret_cast<const int32_t*>(r + gc.o_status)[i] : gc.decided[i];
+        if (out->n_steps) out->n_steps[i] = dev ? reinterpret_cast<const int32_t*>(r + gc.o_n)[i] : 0;
+        if (out->side && K > 0) { if (dev) std::memcpy(out->side + i * K, r + gc.o_side + i * K, K); else std::memset(out->side + i * K, 0, K); }
+        if (out->target && K > 0) { if (dev) std::memcpy(out->target + i * K * 3, r + gc.o_target + i * K * 24, K * 24); else std::memset(out->target + i * K * 3, 0, K * 24); }
+        if (out->desired_point) { if (dev) std::memcpy(out->desired_point + i * 2, r + gc.o_dp + i * 16, 16); else std::memset(out->desired_point + i * 2, 0, 16); }
+        if (out->unicycle_end) { if (dev) std::memcpy(out->unicycle_end + i * 3, r + gc.o_ue + i * 24, 24); else std::memset(out->unicycle_end + i * 3, 0, 24); }
+    }
     return WCQP_OK;
 }
 

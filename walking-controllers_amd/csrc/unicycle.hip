@@ -3,26 +3,18 @@
 //   src/WalkingModule.cpp:1263-1308          setPlannerInput: the goal
 //   src/TrajectoryGenerator.cpp:442-484      updateTrajectories: the unicycle's start and its desired point
 //   src/TrajectoryGenerator.cpp:114-132      the planner's parameters (plannerParams.ini)
-// One lane per robot, 64 robots per wave, one wave per workgroup.  A robot's plan is one serial chain of at most K x D RK4 steps, and the
-// feasibility test rides on it: every sample is tested as it is reached, the state of the last feasible one stays in registers, and the
-// unicycle rewinds to it when the D samples of a step are through - nothing is integrated twice and no path array exists.  The cosine
-// and sine of a sample's heading serve its candidate, the first RK4 stage of the next sample and - when the candidate becomes a footprint
-// - the stance frame of the next step.  Every lane walks the same K x D trip counts (a robot that has ended idles behind a predicate); a
-// wave leaves the step loop when all of its robots have ended.  Dead lanes of the last wave repeat the last robot and store nothing.
+// One lane per robot, 64 robots per wave, one wave per workgroup; the per-robot body is unicycle_device.h's, which goal_plan_kernel
+// (tick_plan.hip) runs too.  Dead lanes of the last wave repeat the last robot and store nothing.
 // Plain vector loads and stores only; the parameters travel as the kernel argument.
 #include <cmath>
 #include <new>
 #include <vector>
 #include "wcqp_internal.h"
+#include "unicycle_device.h"
 
 namespace {
 
-struct UniPar {
-    double dT, dx, dy, kd;                     // kd = unicycle_gain / d_x
-    double g, vmax, wmax;
-    double len_max, len_min, width_min, half_w, ang_max, ang_min;
-    int D, K;
-};
+using namespace wcqp_unicycle;
 
 struct UniDev {
     UniPar p;
@@ -34,117 +26,14 @@ struct UniDev {
     double *target, *desired_point, *unicycle_end;
 };
 
-constexpr double kTwoPi = 6.283185307179586476925286766559;
-
-__device__ __forceinline__ double wrap_angle(double a) { return a - kTwoPi * rint(a / kTwoPi); }
-
-// the unicycle's velocity at (x, y) with heading cosine / sine (c, s), towards the desired point (px, py)
-__device__ __forceinline__ void uni_rate(const UniPar& p, double x, double y, double c, double s, double px, double py,
-                                         double& fx, double& fy, double& fw) {
-    const double ex = (x + (c * p.dx - s * p.dy)) - px;
-    const double ey = (y + (s * p.dx + c * p.dy)) - py;
-    double v = -p.kd * ((p.dx * c - p.dy * s) * ex + (p.dx * s + p.dy * c) * ey);
-    double w = -p.kd * (c * ey - s * ex);
-    v = fmin(fmax(v, -p.vmax), p.vmax);
-    w = fmin(fmax(w, -p.wmax), p.wmax);
-    v = v / (1.0 + p.g * fabs(w));
-    fx = v * c; fy = v * s; fw = w;
-}
-
 __global__ __launch_bounds__(64) void unicycle_kernel(UniDev a) {
-    const UniPar& p = a.p;
     const long raw = (long)blockIdx.x * 64 + threadIdx.x;
     const bool live = raw < a.batch;
     const size_t i = (size_t)(live ? raw : (long)a.batch - 1);
-    // ---- inputs, and whether all of this robot's are finite
-    double lx = a.left0[i * 12], ly = a.left0[i * 12 + 1], lc = a.left0[i * 12 + 3], ls = a.left0[i * 12 + 6];
-    double rx = a.right0[i * 12], ry = a.right0[i * 12 + 1], rc = a.right0[i * 12 + 3], rs = a.right0[i * 12 + 6];
-    double gx = a.goal[i * 2], gy = a.goal[i * 2 + 1];
-    int sw = a.first_side[i];                          // the swing foot: 0 left, 1 right
-    bool bad = !(isfinite(lx) && isfinite(ly) && isfinite(lc) && isfinite(ls) && isfinite(rx) && isfinite(ry) && isfinite(rc) && isfinite(rs) &&
-                 isfinite(gx) && isfinite(gy)) || sw > 1;
-    if (bad) { lx = ly = ls = rx = ry = rs = gx = gy = 0.0; lc = rc = 1.0; sw = 0; }     // (nothing non-finite enters the chain)
-    const double lth = atan2(ls, lc), rth = atan2(rs, rc);
-    // swing foot (sx, sy, sth), stance foot (tx, ty, tth) with its heading cosine / sine (tc, ts)
-    double sx = sw ? rx : lx, sy = sw ? ry : ly, sth = sw ? rth : lth;
-    double tx = sw ? lx : rx, ty = sw ? ly : ry, tth = sw ? lth : rth;
-    double tc, ts;
-    sincos(tth, &ts, &tc);
-    // the unicycle: (0, -w/2) from a left stance foot, (0, +w/2) from a right one
-    const double off = sw ? -p.half_w : p.half_w;
-    double ux = tx - ts * off, uy = ty + tc * off, uth = tth, uc = tc, us = ts;
-    const double ax = p.dx + gx, ay = p.dy + gy;
-    double px = ux + (tc * ax - ts * ay), py = uy + (ts * ax + tc * ay);
-    if (!(isfinite(px) && isfinite(py))) { bad = true; px = py = 0.0; }
-    int status = bad ? WCQP_UNICYCLE_INVALID_INPUT : -1;          // -1: planning
-    int n_steps = 0;
-    const double h2 = 0.5 * p.dT, h6 = p.dT / 6.0;
-    const unsigned K = (unsigned)p.K;
-#pragma unroll 1
-    for (unsigned k = 0; k < K; ++k) {
-        if (__ballot(status < 0) == 0ull) break;
-        const double sgn = sw ? -1.0 : 1.0, lat = sgn * p.half_w;
-        double x = ux, y = uy, th = uth, c = uc, s = us;
-        int best = 0;
-        double bx = 0.0, by = 0.0, bth = 0.0, bc = 1.0, bs = 0.0, bcx = 0.0, bcy = 0.0;
-#pragma unroll 1
-        for (int m = 1; m <= p.D; ++m) {
-            double f1x, f1y, f1w, f2x, f2y, f2w, f3x, f3y, f3w, f4x, f4y, f4w, cq, sq;
-            uni_rate(p, x, y, c, s, px, py, f1x, f1y, f1w);
-            sincos(th + h2 * f1w, &sq, &cq);
-            uni_rate(p, x + h2 * f1x, y + h2 * f1y, cq, sq, px, py, f2x, f2y, f2w);
-            sincos(th + h2 * f2w, &sq, &cq);
-            uni_rate(p, x + h2 * f2x, y + h2 * f2y, cq, sq, px, py, f3x, f3y, f3w);
-            sincos(th + p.dT * f3w, &sq, &cq);
-            uni_rate(p, x + p.dT * f3x, y + p.dT * f3y, cq, sq, px, py, f4x, f4y, f4w);
-            x = x + h6 * (f1x + 2.0 * f2x + 2.0 * f3x + f4x);
-            y = y + h6 * (f1y + 2.0 * f2y + 2.0 * f3y + f4y);
-            th = th + h6 * (f1w + 2.0 * f2w + 2.0 * f3w + f4w);
-            sincos(th, &s, &c);
-            // candidate m: the swing foot beside the unicycle, seen from the stance foot
-            const double cx = x - s * lat, cy = y + c * lat;
-            const double ex = cx - tx, ey = cy - ty;
-            const double rlon = tc * ex + ts * ey, rlat = tc * ey - ts * ex;
-            const bool feasible = sqrt(rlon * rlon + rlat * rlat) <= p.len_max && sgn * rlat >= p.width_min &&
-                                  fabs(wrap_angle(th - tth)) <= p.ang_max;
-            if (feasible) { best = m; bx = x; by = y; bth = th; bc = c; bs = s; bcx = cx; bcy = cy; }
-        }
-        if (status < 0) {
-            if (best == 0) {
-                status = WCQP_UNICYCLE_STUCK;
-            } else {
-                const double ex = bcx - sx, ey = bcy - sy, dyaw = wrap_angle(bth - sth);
-                if (sqrt(ex * ex + ey * ey) < p.len_min && fabs(dyaw) < p.ang_min) {
-                    status = WCQP_UNICYCLE_DONE;
-                } else {
-                    if (live) {
-                        a.side[i * K + k] = (uint8_t)sw;
-                        double* t = a.target + (i * K + k) * 3;
-                        t[0] = bcx; t[1] = bcy; t[2] = dyaw;
-                    }
-                    ++n_steps;
-                    // the foot that landed is the next stance foot; the unicycle rewinds to the sample it landed at
-                    sx = tx; sy = ty; sth = tth;
-                    tx = bcx; ty = bcy; tth = bth; tc = bc; ts = bs;
-                    ux = bx; uy = by; uth = bth; uc = bc; us = bs;
-                    sw = 1 - sw;
-                }
-            }
-        }
-    }
-    if (status < 0) status = WCQP_UNICYCLE_TRUNCATED;
-    if (!live) return;
-    for (unsigned k = (unsigned)n_steps; k < K; ++k) {
-        a.side[i * K + k] = 0;
-        double* t = a.target + (i * K + k) * 3;
-        t[0] = 0.0; t[1] = 0.0; t[2] = 0.0;
-    }
-    a.n_steps[i] = n_steps;
-    a.status[i] = status;
-    if (a.desired_point) { a.desired_point[i * 2] = bad ? 0.0 : px; a.desired_point[i * 2 + 1] = bad ? 0.0 : py; }
-    if (a.unicycle_end) {
-        a.unicycle_end[i * 3] = bad ? 0.0 : ux; a.unicycle_end[i * 3 + 1] = bad ? 0.0 : uy; a.unicycle_end[i * 3 + 2] = bad ? 0.0 : uth;
-    }
+    const UniStart in{a.left0[i * 12], a.left0[i * 12 + 1], a.left0[i * 12 + 3], a.left0[i * 12 + 6],
+                      a.right0[i * 12], a.right0[i * 12 + 1], a.right0[i * 12 + 3], a.right0[i * 12 + 6],
+                      a.goal[i * 2], a.goal[i * 2 + 1], (int)a.first_side[i]};
+    plan_robot(a.p, in, UniRows{a.n_steps, a.status, a.side, a.target, a.desired_point, a.unicycle_end}, i, live);
 }
 
 bool pos(double v) { return std::isfinite(v) && v > 0.0; }
@@ -259,3 +148,5 @@ int wcqp_unicycle_plan_host(wcqp_unicycle_t h, int32_t batch, const wcqp_unicycl
 }
 
 }  // extern "C"
+
+const wcqp_unicycle::UniPar* wcqp::unicycle_par(wcqp_unicycle_t h) { return h ? &h->par : nullptr; }
