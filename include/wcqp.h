@@ -59,7 +59,7 @@
  *                                      device is looked for.  The planned-trajectory records use 64-bit offsets and set no limit.
  *     wcqp_kin_jacobians_*, wcqp_hull_from_feet_*   64-bit addresses throughout: no limit beyond int32 batch.
  *     wcqp_unicycle_plan_device / _host   target: max_steps x 24 B; the soles: 96 B.  (The kernel forms 64-bit addresses; the limit is
- *                                      kept for the reason given for the MPC.)
+ *                                      kept for the reason given for the MPC.)  wcqp_unicycle_plan_timed_device / _host: the same.
  */
 #ifndef WCQP_H
 #define WCQP_H
@@ -859,6 +859,9 @@ typedef struct wcqp_tick_option {
 } wcqp_tick_option;
 #define WCQP_TICK_OPT_RESIDENT_PLAN      1   /* = wcqp_tick_params_ext.resident_plan */
 #define WCQP_TICK_OPT_POSITION_STREAMED  2   /* 1: ik_mode POSITION on a streamed (EXTERNAL) handle */
+#define WCQP_TICK_OPT_PLAN_TIMED         3   /* REPORTED ONLY (wcqp_tick_get_option; wcqp_tick_create_opts refuses it as an unknown key): 1 while the plan in
+                                              * place came from wcqp_tick_upload_footsteps_timed (per-step timings), 0 otherwise.  wcqp_tick_info_ext is
+                                              * closed like the structs before it, so the flag travels by key */
 int wcqp_tick_create_opts(const wcqp_tick_params* params, const wcqp_tick_option* opts, int32_t n_opts, wcqp_tick_t* out);
 int wcqp_tick_get_option(wcqp_tick_t h, int32_t key, int32_t* value);
 int wcqp_tick_destroy(wcqp_tick_t h);
@@ -893,9 +896,10 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in);
  * WCQP_E_UNSUPPORTED on a handle without planned_trajectories.  WCQP_E_INVALID, with the handle unchanged (a handle uploaded before keeps
  * that upload), for a NULL required pointer, n_steps outside 0..K, a side other than 0 / 1, a non-finite value (of a step the robot
  * takes, of the state0 entries read, q0, com0, dcm0, u_init, lift or the deltas), a tick count below 1 or final_ds_ticks below 0.
- * The call always rewinds to tick 0; wcqp_tick_replan_footsteps below regenerates a running plan from a later stage.  Not offered, and
- * refused by construction rather than silently ignored: per-step timings, device-pointer footsteps (of a running walk,
- * wcqp_tick_replan_goals plans the footsteps on the device and keeps them there). */
+ * The call always rewinds to tick 0; wcqp_tick_replan_footsteps below regenerates a running plan from a later stage.  In this call step
+ * timings are common to the batch and to all steps (per-step timings: wcqp_tick_upload_footsteps_timed, below).  Not offered, and
+ * refused by construction rather than silently ignored: device-pointer footsteps (of a running walk, wcqp_tick_replan_goals plans the
+ * footsteps on the device and keeps them there). */
 typedef struct wcqp_tick_footsteps {      /* HOST pointers, copied at the call */
     int32_t max_steps;                    /* K: row length of the per-step arrays, >= 0 */
     const int32_t* n_steps;               /* [B] 0..K steps robot i takes */
@@ -935,8 +939,9 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
  * that is not uploaded, a NULL pointer, first_ds_ticks < 1, and for a robot that replans: n_steps outside 0..K', a side above 1 or a
  * non-finite target of a step it takes, M_i = 0 or < -1, M_i < the ticks enqueued so far (within one wcqp_tick_run call the kernel reads a
  * stage ahead, between calls nothing is ahead), M_i >= T, M_i below the stage its current plan was generated from, or a stage M_i that
- * lies in a single support of its current plan.  Not offered: replanning a classically uploaded plan, per-step timings, device pointers
- * (the goal form below, wcqp_tick_replan_goals, keeps the footsteps on the device: they are planned there and never visit the host). */
+ * lies in a single support of its current plan.  WCQP_E_UNSUPPORTED on a TIMED plan (wcqp_tick_replan_footsteps_timed, below, replans
+ * those).  Not offered: replanning a classically uploaded plan, device pointers (the goal form below, wcqp_tick_replan_goals, keeps the
+ * footsteps on the device: they are planned there and never visit the host). */
 typedef struct wcqp_tick_replan {         /* HOST pointers, copied before the call returns */
     const int32_t* merge_stage;           /* [B] M_i >= 1: robot i's plan is regenerated from stage M_i on; -1: robot i keeps its plan */
     int32_t max_steps;                    /* K': row length of the per-step arrays, >= 0 */
@@ -946,6 +951,30 @@ typedef struct wcqp_tick_replan {         /* HOST pointers, copied before the ca
     int32_t first_ds_ticks;               /* >= 1: stages of double support from M_i before the first new step */
 } wcqp_tick_replan;
 int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream);
+/* Per-step timings: every footstep carries its own durations (the reference's planner gives every step its own, between minStepDuration
+ * and maxStepDuration; wcqp_unicycle_plan_timed_* below chooses them and fills exactly these two arrays).  THE TIMED PLAN is the plan
+ * wcqp_tick_upload_footsteps defines (tests/helpers/footstep_plan_timed.py restates it), with four changes:
+ *   - step k of robot i occupies ss[i][k] + ds[i][k] stages: ss of single support, then ds of double support;
+ *   - the last step's double support lasts steps->final_ds_ticks stages if that is > 0, else ds[i][n - 1];
+ *   - steps->ss_ticks / ds_ticks are ignored;
+ *   - the swing phase is x = (s + 1) / ss_k, the twist is divided by ss_k dT, and a double support's ZMP ramp uses that step's own n.
+ * Flags, fixed frame, ZMP points, the backward DCM recursion from the first standing stage, height and the set rule keep their wording.
+ * THE TIMED REPLAN is the replanned plan above on the per-step timeline: "a single support of its current plan" refers to the plan in
+ * force with its own durations, `tm` gives the NEW steps' durations, and the last step's double support again falls back to the
+ * final_ds_ticks of the upload, or to its own ds.
+ * A plan is timed or not from its upload on (wcqp_tick_get_option with WCQP_TICK_OPT_PLAN_TIMED): wcqp_tick_replan_footsteps on a timed plan and
+ * wcqp_tick_replan_footsteps_timed on an untimed one return WCQP_E_UNSUPPORTED, and so does wcqp_tick_replan_goals on a timed plan (it
+ * needs its merge-point rule over per-robot timelines and a timed planner kernel: not offered yet) - each before anything changes.
+ * wcqp_tick_get_plan, the POSITION tick and the resident plans of streamed handles take a timed plan as any other.
+ * Refusals, on the host, with the handle unchanged: every refusal of the untimed call (its ss_ticks / ds_ticks rule aside), and
+ * WCQP_E_INVALID for a NULL tm or a NULL pointer inside it (K > 0), ss < 1 or ds < 1 of a step the robot takes, or a timeline - of any
+ * robot, the first double support and, in a replan, the T stages in front included - that passes 2^30 stages. */
+typedef struct wcqp_tick_step_timing {   /* HOST pointers, copied at the call */
+    const int32_t* ss_ticks;             /* [B][K] single-support stages of step k, >= 1 for a step the robot takes */
+    const int32_t* ds_ticks;             /* [B][K] double-support stages behind step k, >= 1 */
+} wcqp_tick_step_timing;
+int wcqp_tick_upload_footsteps_timed(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps, const wcqp_tick_step_timing* tm);
+int wcqp_tick_replan_footsteps_timed(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_step_timing* tm, void* stream);
 
 typedef struct wcqp_unicycle_s* wcqp_unicycle_t;       /* the unicycle planner's handle, stated at the end of this header */
 
@@ -1205,8 +1234,9 @@ int wcqp_tick_get_info_ext(wcqp_tick_t h, wcqp_tick_info_ext* out);
  *   Non-finite inputs ("never report SOLVED for NaN / Inf inputs"): the device form gives a robot with a NaN or an Inf in an entry it
  *             reads, a desired point that overflows or a first_side above 1 WCQP_UNICYCLE_INVALID_INPUT with n_steps = 0 and every output row zero; the other robots
  *             do not notice.  The host form refuses the whole call with WCQP_E_INVALID before anything is copied.
- * DEVIATIONS.  Step timings are common to a batch, as wcqp_tick_footsteps demands: minStepDuration, maxStepDuration, timeWeight and
- * positionWeight are not read, and a step advances the PATH by at most D samples instead of choosing its duration.  plannerHorizon is
+ * DEVIATIONS.  In THIS form step timings are common to a batch, as wcqp_tick_footsteps demands: minStepDuration, maxStepDuration,
+ * nominalDuration, timeWeight, positionWeight and switchOverSwingRatio are not read, and a step advances the PATH by at most D samples
+ * instead of choosing its duration (wcqp_unicycle_plan_timed_*, below, reads them and chooses).  plannerHorizon is
  * not read: the tick handle's T cuts the plan.  addTerminalStep, startAlwaysSameFoot and pitchDelta are not offered: the feet of a DONE
  * robot are aligned to within the two arrival thresholds, not exactly.  The two saturations are this build's own addition.
  * ===================================================================================== */
@@ -1260,6 +1290,42 @@ int wcqp_unicycle_plan_device(wcqp_unicycle_t h, int32_t batch, const wcqp_unicy
 /* the same with HOST pointers: validated on the host first (a non-finite entry that is read, or a first_side above 1, of any robot:
  * WCQP_E_INVALID, nothing copied or written), staged through the handle's own device buffer, and in place on return (it synchronises). */
 int wcqp_unicycle_plan_host(wcqp_unicycle_t h, int32_t batch, const wcqp_unicycle_inputs* in, const wcqp_unicycle_outputs* out);
+
+/* =====================================================================================
+ * The planner chooses each step's duration.  The reference reads minStepDuration, maxStepDuration, nominalDuration, timeWeight,
+ * positionWeight and switchOverSwingRatio (TrajectoryGenerator.cpp:82-103) and hands them to its planner (setCostWeights,
+ * setStepTimings, setSwitchOverSwingRatio, :123-136).  The planner library is upstream of the reference, so - as above - THIS IS THIS
+ * BUILD'S OWN DEFINITION (tests/helpers/unicycle_plan_timed.py restates it).  Start, unicycle law, RK4, candidate geometry, the three
+ * feasibility constraints, the arrival test, the statuses and the treatment of non-finite inputs are those of wcqp_unicycle_plan_*;
+ * the handle's step_ticks is not read.  What differs:
+ *   Steps     Candidate m of min_step_ticks .. max_step_ticks is the unicycle at sample n_k + m (samples n_k + 1 .. n_k + min_step_ticks
+ *             - 1 are integrated and are no candidates).  A feasible candidate is scored
+ *                 c(m) = time_weight (1 / (m dT) - 1 / (nominal_step_ticks dT))^2 + position_weight |r_m - r_nom|^2,
+ *             r_m = R(th_st)^T (c - p_st) the candidate seen from the stance foot, as in the feasibility test, and r_nom = (0, +w) for
+ *             a left swing foot, (0, -w) for a right one.  m* is the feasible m with the SMALLEST c, the smallest such m on a tie;
+ *             without a feasible one the robot ends WCQP_UNICYCLE_STUCK.  The arrival test is applied to candidate m*; a step taken
+ *             continues the path from sample n_k + m*.
+ *   Durations With rho = r / (1 + r), r = switch_over_swing_ratio (double support over single support), computed once on the host:
+ *                 ds_k = min(max((int32) floor(m* rho + 0.5), 1), m* - 1),   ss_k = m* - ds_k,
+ *             so ss_k, ds_k >= 1 and ss_k + ds_k = m*.  ss_ticks / ds_ticks [B][K] are outputs, zero for steps not taken (and for
+ *             every step of a WCQP_UNICYCLE_INVALID_INPUT robot): a step's single-support stages and the double-support stages
+ *             behind it.
+ * DEVIATIONS that remain: plannerHorizon is not read, addTerminalStep, startAlwaysSameFoot and pitchDelta are not offered, and
+ * mergePointRatio is not read (a replan's merge stage is the caller's).  The two saturations stay this build's own addition.
+ * ===================================================================================== */
+typedef struct wcqp_unicycle_timing {
+    int32_t min_step_ticks, max_step_ticks, nominal_step_ticks;  /* minStepDuration, maxStepDuration, nominalDuration / dT; 2 <= min <= nominal <= max */
+    double  time_weight, position_weight;                        /* timeWeight, positionWeight; >= 0, finite */
+    double  switch_over_swing_ratio;                             /* switchOverSwingRatio (double support / single support); > 0, finite */
+} wcqp_unicycle_timing;
+/* As wcqp_unicycle_plan_device, with DEVICE ss_ticks / ds_ticks [B][K] (required for K > 0); `tm` is read at the call.  Refusals need no
+ * device and come before anything is launched: WCQP_E_INVALID for a NULL tm, a tick count or weight or ratio outside the ranges above,
+ * a NULL duration row with K > 0, and everything wcqp_unicycle_plan_device refuses. */
+int wcqp_unicycle_plan_timed_device(wcqp_unicycle_t h, const wcqp_unicycle_timing* tm, int32_t batch, const wcqp_unicycle_inputs* in,
+                                    const wcqp_unicycle_outputs* out, int32_t* ss_ticks, int32_t* ds_ticks, void* stream);
+/* the same with HOST pointers, validated, staged and synchronised as wcqp_unicycle_plan_host */
+int wcqp_unicycle_plan_timed_host(wcqp_unicycle_t h, const wcqp_unicycle_timing* tm, int32_t batch, const wcqp_unicycle_inputs* in,
+                                  const wcqp_unicycle_outputs* out, int32_t* ss_ticks, int32_t* ds_ticks);
 
 #ifdef __cplusplus
 }

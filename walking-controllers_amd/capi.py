@@ -42,10 +42,11 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_feedback_device", "wcqp_tick_set_feedback_host", "wcqp_tick_get_info",
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
-    "wcqp_tick_upload_footsteps", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
+    "wcqp_tick_upload_footsteps", "wcqp_tick_upload_footsteps_timed", "wcqp_tick_replan_footsteps_timed", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
     "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
+    "wcqp_unicycle_plan_timed_device", "wcqp_unicycle_plan_timed_host",
 )
 
 
@@ -206,6 +207,7 @@ class TickOption(C.Structure):
 
 
 TICK_OPT_RESIDENT_PLAN, TICK_OPT_POSITION_STREAMED = 1, 2
+TICK_OPT_PLAN_TIMED = 3        # reported only (TickPipeline.option / info()["plan_timed"]): the plan in place carries per-step timings
 TICK_PLANT_INTERNAL, TICK_PLANT_EXTERNAL = 0, 1
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
 TICK_IK_VELOCITY, TICK_IK_POSITION = 0, 1
@@ -216,6 +218,11 @@ class TickInfo(C.Structure):
     _fields_ = [("kin_handoff", C.c_int32), ("ticks_per_launch", C.c_int32), ("dcm_controller", C.c_int32), ("launches_per_tick", C.c_int32),
                 ("zmp_gain_scheduling", C.c_int32), ("planned_trajectories", C.c_int32), ("streamed_trajectories", C.c_int32),
                 ("sensor_filters", C.c_int32), ("plan_generated", C.c_int32), ("plan_record_ms", C.c_double), ("ik_mode", C.c_int32)]
+
+
+class TickStepTiming(C.Structure):
+    """wcqp_tick_step_timing: per-step durations ss_ticks / ds_ticks [B][K] (int32) of the timed footstep calls."""
+    _fields_ = [("ss_ticks", C.c_void_p), ("ds_ticks", C.c_void_p)]
 
 
 class TickInfoExt(C.Structure):
@@ -291,6 +298,13 @@ class UnicycleOutputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("n_steps", "side", "target", "status", "desired_point", "unicycle_end")]
 
 
+class UnicycleTiming(C.Structure):
+    """wcqp_unicycle_timing: the candidates' range and nominal duration in ticks, the two weights of a candidate's score and the
+    double-support / single-support ratio of wcqp_unicycle_plan_timed_*."""
+    _fields_ = [("min_step_ticks", C.c_int32), ("max_step_ticks", C.c_int32), ("nominal_step_ticks", C.c_int32),
+                ("time_weight", C.c_double), ("position_weight", C.c_double), ("switch_over_swing_ratio", C.c_double)]
+
+
 PLAN_WINDOW = (("left_traj", (12,), np.float64), ("right_traj", (12,), np.float64), ("left_twist", (6,), np.float64), ("right_twist", (6,), np.float64),
                ("contact", (), np.uint8), ("com_height", (), np.float64), ("com_height_vel", (), np.float64),
                ("ref_traj", (2,), np.float64), ("dcm_vel_traj", (2,), np.float64),
@@ -313,8 +327,9 @@ ABI_STRUCTS = {
     "wcqp_prepare_params": PrepareParams, "wcqp_tick_params": TickParams, "wcqp_tick_params_ext": TickParamsExt, "wcqp_tick_option": TickOption,
     "wcqp_tick_inputs": TickInputs, "wcqp_tick_outputs": TickOutputs, "wcqp_tick_info": TickInfo, "wcqp_tick_info_ext": TickInfoExt,
     "wcqp_tick_desired": TickDesired, "wcqp_tick_footsteps": TickFootsteps, "wcqp_tick_replan": TickReplan, "wcqp_tick_plan_window": TickPlanWindow,
-    "wcqp_tick_goals": TickGoals, "wcqp_tick_goal_result": TickGoalResult,
+    "wcqp_tick_goals": TickGoals, "wcqp_tick_goal_result": TickGoalResult, "wcqp_tick_step_timing": TickStepTiming,
     "wcqp_unicycle_params": UnicycleParams, "wcqp_unicycle_inputs": UnicycleInputs, "wcqp_unicycle_outputs": UnicycleOutputs,
+    "wcqp_unicycle_timing": UnicycleTiming,
 }
 ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
     "VERSION OK E_INVALID E_UNSUPPORTED E_NUMERIC E_HIP E_NOMEM "
@@ -322,7 +337,7 @@ ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
     "IK_FORM_QPOASES IK_FORM_OSQP IK_ALG_DEFAULT IK_ALG_SWEEP IK_ALG_NULLSPACE IK_ALG_NULLSPACE_MFMA IK_ALG_NULLSPACE_16L IK_ALG_BASE_ELIM "
     "IK_JAC_AUTO IK_JAC_MIXED IK_JAC_GENERAL PLAN_WAYS_AUTO SLAB_IN_ARRAYS SLAB_OUT_ARRAYS KIN_MAX_DOF "
     "KIN_HANDOFF_FUSED KIN_HANDOFF_DENSE KIN_HANDOFF_COMPACT TICK_PLANT_INTERNAL TICK_PLANT_EXTERNAL TICK_DCM_MPC TICK_DCM_REACTIVE "
-    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
+    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED TICK_OPT_PLAN_TIMED UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
     "TICK_MERGE_KEEP TICK_MERGE_AUTO TICK_SIDE_AUTO GOAL_KEPT GOAL_TOO_LATE").split()}
 
 _lib: Optional[C.CDLL] = None
@@ -383,6 +398,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_set_desired_from_plan.argtypes = [C.c_void_p, C.c_void_p]
         L.wcqp_tick_get_info.argtypes = [C.c_void_p, C.POINTER(TickInfo)]
         L.wcqp_tick_upload_footsteps.argtypes = [C.c_void_p, C.POINTER(TickInputs), C.POINTER(TickFootsteps)]
+        L.wcqp_tick_upload_footsteps_timed.argtypes = [C.c_void_p, C.POINTER(TickInputs), C.POINTER(TickFootsteps), C.POINTER(TickStepTiming)]
+        L.wcqp_tick_replan_footsteps_timed.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.POINTER(TickStepTiming), C.c_void_p]
         L.wcqp_tick_get_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TickPlanWindow)]
         L.wcqp_tick_replan_footsteps.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.c_void_p]
         L.wcqp_tick_replan_goals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickGoals), C.c_void_p]
@@ -391,6 +408,10 @@ def lib() -> C.CDLL:
         L.wcqp_unicycle_destroy.argtypes = [C.c_void_p]
         L.wcqp_unicycle_plan_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(UnicycleInputs), C.POINTER(UnicycleOutputs), C.c_void_p]
         L.wcqp_unicycle_plan_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(UnicycleInputs), C.POINTER(UnicycleOutputs)]
+        L.wcqp_unicycle_plan_timed_device.argtypes = [C.c_void_p, C.POINTER(UnicycleTiming), C.c_int32, C.POINTER(UnicycleInputs), C.POINTER(UnicycleOutputs),
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wcqp_unicycle_plan_timed_host.argtypes = [C.c_void_p, C.POINTER(UnicycleTiming), C.c_int32, C.POINTER(UnicycleInputs), C.POINTER(UnicycleOutputs),
+                                                    C.c_void_p, C.c_void_p]
         L.wcqp_qp_enqueue_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.POINTER(C.c_int32)]
         L.wcqp_qp_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QpStep), C.c_int32, C.POINTER(C.c_void_p)]
         L.wcqp_qp_plan_enqueue.argtypes = [C.c_void_p, C.c_void_p]
@@ -613,18 +634,26 @@ class PrepareSolver(_Handle):
 class UnicyclePlanner(_Handle):
     """Handle over wcqp_unicycle_* - footsteps from per-robot goals, the reference's setGoal (include/wcqp.h states the planner).  Defaults
     follow plannerParams.ini where it has the key (angles in radians here); the two saturations are this build's own.  step_ticks: unicycle
-    samples per step, ss_ticks + ds_ticks of the walk the footsteps are for; max_steps: K, the row length of side / target."""
+    samples per step, ss_ticks + ds_ticks of the walk the footsteps are for; max_steps: K, the row length of side / target.  timing (a
+    dict over TIMING_DEFAULTS, kept as `planner.timing`): what the timed form - plan_host / plan_device with `timing=` - chooses every
+    step's duration by; that form does not read step_ticks."""
     _destroy = "wcqp_unicycle_destroy"
     DEFAULTS = dict(dT=0.01, reference_position=(0.1, 0.0), unicycle_gain=10.0, slow_when_turning_gain=5.0, max_linear_velocity=0.1,
                     max_angular_velocity=0.5, max_step_length=0.20, min_step_length=0.05, min_width=0.14, nominal_width=0.16,
                     max_angle_variation=np.deg2rad(10.0), min_angle_variation=np.deg2rad(8.0), step_ticks=90, max_steps=8)
 
-    def __init__(self, **params):
+    # the reference's plannerParams.ini through dT = 0.01: minStepDuration 0.8, maxStepDuration 1.0, nominalDuration 0.9 [s], timeWeight 2.5,
+    # positionWeight 1.0, switchOverSwingRatio 0.7
+    TIMING_DEFAULTS = dict(min_step_ticks=80, max_step_ticks=100, nominal_step_ticks=90, time_weight=2.5, position_weight=1.0,
+                           switch_over_swing_ratio=0.7)
+
+    def __init__(self, timing=None, **params):
         unknown = set(params) - set(self.DEFAULTS)
         if unknown:
             raise TypeError("unknown unicycle parameter(s): " + ", ".join(sorted(unknown)))
         p = dict(self.DEFAULTS, **params)
         self.values = p
+        self.timing = None if timing is None else self.timing_values(timing)      # what plan_host(..., timing=planner.timing) takes
         self.max_steps, self.step_ticks = int(p["max_steps"]), int(p["step_ticks"])
         scalars = [float(p[k]) for k, _ in UnicycleParams._fields_[2:12]]
         self.params = UnicycleParams(float(p["dT"]), (C.c_double * 2)(*map(float, p["reference_position"])), *scalars, self.step_ticks, self.max_steps)
@@ -635,7 +664,9 @@ class UnicyclePlanner(_Handle):
     def from_ini_values(cls, values: dict, **params):
         """From the VALUES of a plannerParams.ini (a dict keyed as the file: unicycleGain, referencePosition, slowWhenTurningGain,
         maxStepLength, minStepLength, minWidth, nominalWidth, maxAngleVariation / minAngleVariation in DEGREES); `params` adds or
-        overrides (dT, the saturations, step_ticks, max_steps)."""
+        overrides (dT, the saturations, step_ticks, max_steps).  The step timings of the file - minStepDuration, maxStepDuration,
+        nominalDuration in SECONDS (ticks of dT here), timeWeight, positionWeight, switchOverSwingRatio - end up in `planner.timing`,
+        what plan_host(..., timing=planner.timing) takes; None when the file has none of them."""
         key = dict(unicycleGain="unicycle_gain", referencePosition="reference_position", slowWhenTurningGain="slow_when_turning_gain",
                    maxStepLength="max_step_length", minStepLength="min_step_length", minWidth="min_width", nominalWidth="nominal_width")
         p = {v: values[k] for k, v in key.items() if k in values}
@@ -643,12 +674,33 @@ class UnicyclePlanner(_Handle):
             if k in values:
                 p[v] = float(np.deg2rad(values[k]))
         p.update(params)
-        return cls(**p)
+        # the step timings, in seconds there and in ticks of dT here; held as planner.timing when the file has any of them
+        dT = float(p.get("dT", cls.DEFAULTS["dT"]))
+        tm = {v: int(round(float(values[k]) / dT)) for k, v in (("minStepDuration", "min_step_ticks"), ("maxStepDuration", "max_step_ticks"),
+                                                                 ("nominalDuration", "nominal_step_ticks")) if k in values}
+        tm.update({v: float(values[k]) for k, v in (("timeWeight", "time_weight"), ("positionWeight", "position_weight"),
+                                                    ("switchOverSwingRatio", "switch_over_swing_ratio")) if k in values})
+        return cls(timing=tm or None, **p)
 
-    def plan_host(self, left0, right0, goals, first_side) -> dict:
+    @classmethod
+    def timing_values(cls, timing: dict) -> dict:
+        """`timing` over TIMING_DEFAULTS (the keys of wcqp_unicycle_timing); an unknown key is a TypeError"""
+        unknown = set(timing) - set(cls.TIMING_DEFAULTS)
+        if unknown:
+            raise TypeError("unknown timing parameter(s): " + ", ".join(sorted(unknown)))
+        return dict(cls.TIMING_DEFAULTS, **timing)
+
+    def _timing_struct(self, timing: dict) -> "UnicycleTiming":
+        t = self.timing_values(timing)
+        return UnicycleTiming(int(t["min_step_ticks"]), int(t["max_step_ticks"]), int(t["nominal_step_ticks"]), float(t["time_weight"]),
+                              float(t["position_weight"]), float(t["switch_over_swing_ratio"]))
+
+    def plan_host(self, left0, right0, goals, first_side, timing: Optional[dict] = None) -> dict:
         """left0 / right0 [B][12] sole poses (p 3 | R 9 row-major: the desired-foot entries of state0), goals [B][2] in the unicycle's frame,
         first_side [B] or a scalar (0: the left foot swings first, 1: the right).  -> n_steps [B], side [B][K], target [B][K][3] - what
-        upload_footsteps / replan_footsteps take -, status [B] (UNICYCLE_*), desired_point [B][2], unicycle_end [B][3]."""
+        upload_footsteps / replan_footsteps take -, status [B] (UNICYCLE_*), desired_point [B][2], unicycle_end [B][3].
+        timing: a dict of wcqp_unicycle_timing's fields (over TIMING_DEFAULTS; planner.timing holds an ini file's) - the planner then
+        chooses every step's duration (wcqp_unicycle_plan_timed_host; step_ticks is not read) and ss_ticks, ds_ticks [B][K] come back too."""
         left0, right0, goals = _f64(left0), _f64(right0), _f64(goals)
         B = goals.shape[0] if goals.ndim else -1
         fs = np.asarray(first_side)
@@ -662,18 +714,31 @@ class UnicyclePlanner(_Handle):
         K = self.max_steps
         o = dict(n_steps=np.zeros(B, np.int32), side=np.zeros((B, K), np.uint8), target=np.zeros((B, K, 3)), status=np.full(B, -1, np.int32),
                  desired_point=np.zeros((B, 2)), unicycle_end=np.zeros((B, 3)))
+        tm = None if timing is None else self._timing_struct(timing)
+        dur = {} if tm is None else dict(ss_ticks=np.zeros((B, K), np.int32), ds_ticks=np.zeros((B, K), np.int32))
         if B == 0:
-            return o
+            return dict(o, **dur)
         ins = UnicycleInputs(_p(left0), _p(right0), _p(goals), _p(fs))
         outs = UnicycleOutputs(**{k: (v.ctypes.data if v.size else None) for k, v in o.items()})
-        check(lib().wcqp_unicycle_plan_host(self._h, B, C.byref(ins), C.byref(outs)), "wcqp_unicycle_plan_host")
-        return o
+        if tm is None:
+            check(lib().wcqp_unicycle_plan_host(self._h, B, C.byref(ins), C.byref(outs)), "wcqp_unicycle_plan_host")
+        else:
+            check(lib().wcqp_unicycle_plan_timed_host(self._h, C.byref(tm), B, C.byref(ins), C.byref(outs), *(v.ctypes.data if v.size else None for v in dur.values())),
+                  "wcqp_unicycle_plan_timed_host")
+        return dict(o, **dur)
 
-    def plan_device(self, batch, left0, right0, goals, first_side, n_steps, side, target, status, desired_point=0, unicycle_end=0, stream=0):
-        """All array arguments are raw device addresses (ints); enqueue only."""
+    def plan_device(self, batch, left0, right0, goals, first_side, n_steps, side, target, status, desired_point=0, unicycle_end=0, stream=0,
+                    timing: Optional[dict] = None, ss_ticks=0, ds_ticks=0):
+        """All array arguments are raw device addresses (ints); enqueue only.  With `timing` (plan_host's) the timed form fills ss_ticks and
+        ds_ticks [B][K] (int32) too."""
         ins = UnicycleInputs(left0, right0, goals, first_side)
         outs = UnicycleOutputs(n_steps, side or None, target or None, status, desired_point or None, unicycle_end or None)
-        check(lib().wcqp_unicycle_plan_device(self._h, int(batch), C.byref(ins), C.byref(outs), stream or None), "wcqp_unicycle_plan_device")
+        if timing is None:
+            check(lib().wcqp_unicycle_plan_device(self._h, int(batch), C.byref(ins), C.byref(outs), stream or None), "wcqp_unicycle_plan_device")
+        else:
+            tm = self._timing_struct(timing)
+            check(lib().wcqp_unicycle_plan_timed_device(self._h, C.byref(tm), int(batch), C.byref(ins), C.byref(outs), ss_ticks or None, ds_ticks or None,
+                                                        stream or None), "wcqp_unicycle_plan_timed_device")
 
 
 class TickPipeline(_Handle):
@@ -849,7 +914,9 @@ class TickPipeline(_Handle):
         """A planned handle's upload with the stages generated on the device (wcqp_tick_upload_footsteps, which defines the plan).
         data: state0, q0, com0 and optionally dcm0 / u_init (missing or None: the generated DCM reference and ZMP of stage 0).
         footsteps: n_steps [B], side [B][K] (0 left, 1 right), target [B][K][3] (x, y, yaw increment), first_ds_ticks, ss_ticks, ds_ticks,
-        final_ds_ticks (0 or missing: ds_ticks), lift, zmp_delta_left, zmp_delta_right - what synth.synth_footstep_walk_batch returns."""
+        final_ds_ticks (0 or missing: ds_ticks), lift, zmp_delta_left, zmp_delta_right - what synth.synth_footstep_walk_batch returns.
+        ss_ticks / ds_ticks as [B][K] arrays instead of two numbers: every step carries its own durations (wcqp_tick_upload_footsteps_timed;
+        final_ds_ticks 0 or missing: each robot's own last ds) - what synth.synth_timed_footstep_walk_batch and a timed plan_host return."""
         if not self._holds_plan():
             raise ValueError("footsteps were given to a handle created without planned_trajectories=True (or resident_plan=True)")
         keep = {k: _f64(data[k]) for k in ("state0", "q0", "com0")}
@@ -861,16 +928,34 @@ class TickPipeline(_Handle):
         target = _f64(footsteps["target"])
         assert n_steps.shape == (self.batch,) and side.ndim == 2 and side.shape[0] == self.batch and target.shape == side.shape + (3,), \
             (n_steps.shape, side.shape, target.shape)
+        dur = self._step_durations(footsteps, side.shape)
         fs = TickFootsteps(side.shape[1], n_steps.ctypes.data, side.ctypes.data if side.size else None, target.ctypes.data if target.size else None,
-                           int(footsteps["first_ds_ticks"]), int(footsteps["ss_ticks"]), int(footsteps["ds_ticks"]), int(footsteps.get("final_ds_ticks", 0)),
+                           int(footsteps["first_ds_ticks"]), 0 if dur else int(footsteps["ss_ticks"]), 0 if dur else int(footsteps["ds_ticks"]),
+                           int(footsteps.get("final_ds_ticks", 0)),
                            float(footsteps["lift"]), (C.c_double * 2)(*footsteps["zmp_delta_left"]), (C.c_double * 2)(*footsteps["zmp_delta_right"]))
         ins = TickInputs(**{k: (keep[k].ctypes.data if k in keep else None) for k, _ in TickInputs._fields_})
-        check(lib().wcqp_tick_upload_footsteps(self._h, C.byref(ins), C.byref(fs)), "wcqp_tick_upload_footsteps")
+        if dur:
+            tm = TickStepTiming(*(a.ctypes.data if a.size else None for a in dur))
+            check(lib().wcqp_tick_upload_footsteps_timed(self._h, C.byref(ins), C.byref(fs), C.byref(tm)), "wcqp_tick_upload_footsteps_timed")
+        else:
+            check(lib().wcqp_tick_upload_footsteps(self._h, C.byref(ins), C.byref(fs)), "wcqp_tick_upload_footsteps")
+
+    @staticmethod
+    def _step_durations(footsteps: dict, shape):
+        """(ss_ticks, ds_ticks) as int32 [B][K] arrays when `footsteps` carries per-step durations, else None"""
+        ss, ds = footsteps.get("ss_ticks"), footsteps.get("ds_ticks")
+        if ss is None or ds is None or (np.ndim(ss) == 0 and np.ndim(ds) == 0):
+            return None
+        ss, ds = np.ascontiguousarray(ss, dtype=np.int32), np.ascontiguousarray(ds, dtype=np.int32)
+        if ss.shape != tuple(shape) or ds.shape != tuple(shape):
+            raise ValueError("per-step ss_ticks %s / ds_ticks %s next to side %s" % (ss.shape, ds.shape, tuple(shape)))
+        return ss, ds
 
     def replan_footsteps(self, merge_stage, footsteps: dict, first_ds_ticks: int, stream: Optional[int] = None):
         """A new goal for a generated walk that is running (wcqp_tick_replan_footsteps, which defines the replanned plan): robot i's plan is
         regenerated from stage merge_stage[i] on (-1: the robot keeps its plan) from footsteps n_steps [B], side [B][K'], target [B][K'][3],
-        behind first_ds_ticks stages of double support; timings, lift and ZMP deltas stay those of upload_footsteps.  Enqueue-only on
+        behind first_ds_ticks stages of double support; timings, lift and ZMP deltas stay those of upload_footsteps.  On a timed plan
+        `footsteps` also carries the new steps' ss_ticks / ds_ticks [B][K'] (wcqp_tick_replan_footsteps_timed).  Enqueue-only on
         `stream`, behind the ticks already enqueued there; the arrays are copied before the call returns."""
         if not self._holds_plan():
             raise ValueError("footsteps were given to a handle created without planned_trajectories=True (or resident_plan=True)")
@@ -882,27 +967,38 @@ class TickPipeline(_Handle):
             target.shape == side.shape + (3,), (merge.shape, n_steps.shape, side.shape, target.shape)
         rp = TickReplan(merge.ctypes.data, side.shape[1], n_steps.ctypes.data, side.ctypes.data if side.size else None,
                         target.ctypes.data if target.size else None, int(first_ds_ticks))
-        check(lib().wcqp_tick_replan_footsteps(self._h, C.byref(rp), stream or None), "wcqp_tick_replan_footsteps")
+        dur = self._step_durations(footsteps, side.shape)
+        if dur:
+            tm = TickStepTiming(*(a.ctypes.data if a.size else None for a in dur))
+            check(lib().wcqp_tick_replan_footsteps_timed(self._h, C.byref(rp), C.byref(tm), stream or None), "wcqp_tick_replan_footsteps_timed")
+        else:
+            check(lib().wcqp_tick_replan_footsteps(self._h, C.byref(rp), stream or None), "wcqp_tick_replan_footsteps")
 
-    def upload_goal(self, data: dict, goals, planner: "UnicyclePlanner", first_side, first_ds_ticks: int, ss_ticks: int, ds_ticks: int,
-                    final_ds_ticks: int = 0, lift: float = 0.02, zmp_delta_left=(0.03, -0.005), zmp_delta_right=(0.03, 0.005)) -> dict:
+    def upload_goal(self, data: dict, goals, planner: "UnicyclePlanner", first_side, first_ds_ticks: int, ss_ticks: int = 0, ds_ticks: int = 0,
+                    final_ds_ticks: int = 0, lift: float = 0.02, zmp_delta_left=(0.03, -0.005), zmp_delta_right=(0.03, 0.005),
+                    timing: Optional[dict] = None) -> dict:
         """"Robot i, go there" from standing: plans footsteps on the device from the desired soles of data["state0"] (entries 24..47) towards
         goals [B][2] (UnicyclePlanner.plan_host), then upload_footsteps with them.  planner.step_ticks is the path samples per step: callers
-        create it with ss_ticks + ds_ticks.  Returns the planner's output dict (status says how each robot's planning ended)."""
+        create it with ss_ticks + ds_ticks.  With `timing` (plan_host's) the planner chooses every step's durations and the plan is a
+        timed one: ss_ticks / ds_ticks are not read.  Returns the planner's output dict (status says how each robot's planning ended)."""
         if not self._holds_plan():
             raise ValueError("a goal was given to a handle created without planned_trajectories=True (or resident_plan=True)")
         st = _f64(data["state0"])
-        plan = planner.plan_host(st[:, 24:36], st[:, 36:48], goals, first_side)
+        plan = planner.plan_host(st[:, 24:36], st[:, 36:48], goals, first_side, timing=timing)
+        if timing is not None:
+            ss_ticks, ds_ticks = plan["ss_ticks"], plan["ds_ticks"]
         self.upload_footsteps(data, dict(n_steps=plan["n_steps"], side=plan["side"], target=plan["target"], first_ds_ticks=first_ds_ticks,
                                          ss_ticks=ss_ticks, ds_ticks=ds_ticks, final_ds_ticks=final_ds_ticks, lift=lift,
                                          zmp_delta_left=zmp_delta_left, zmp_delta_right=zmp_delta_right))
         return plan
 
-    def replan_goal(self, merge_stage, goals, planner: "UnicyclePlanner", first_side, first_ds_ticks: int, stream: Optional[int] = None) -> dict:
+    def replan_goal(self, merge_stage, goals, planner: "UnicyclePlanner", first_side, first_ds_ticks: int, stream: Optional[int] = None,
+                    timing: Optional[dict] = None) -> dict:
         """A new goal for a generated walk that is running: for every robot with merge_stage[i] >= 1 plans footsteps from the two desired
         soles of its plan's record merge_stage[i] towards goals[i], then replan_footsteps.  The soles are read through plan_window, one
         one-stage window per distinct merge stage - it synchronises.  Rows of robots with merge_stage -1 are not read.  Returns the planner's
-        output dict over the whole batch: rows of robots that keep their plan are zero, with status -1."""
+        output dict over the whole batch: rows of robots that keep their plan are zero, with status -1.  With `timing`, on a timed plan, the
+        planner chooses the new steps' durations (ss_ticks, ds_ticks in the output too)."""
         if not self._holds_plan():
             raise ValueError("a goal was given to a handle created without planned_trajectories=True (or resident_plan=True)")
         merge = np.ascontiguousarray(merge_stage, dtype=np.int32)
@@ -914,6 +1010,8 @@ class TickPipeline(_Handle):
         K = planner.max_steps
         out = dict(n_steps=np.zeros(self.batch, np.int32), side=np.zeros((self.batch, K), np.uint8), target=np.zeros((self.batch, K, 3)),
                    status=np.full(self.batch, -1, np.int32), desired_point=np.zeros((self.batch, 2)), unicycle_end=np.zeros((self.batch, 3)))
+        if timing is not None:
+            out.update(ss_ticks=np.zeros((self.batch, K), np.int32), ds_ticks=np.zeros((self.batch, K), np.int32))
         sel = np.nonzero(merge >= 1)[0]
         if sel.size:
             left0, right0 = np.zeros((sel.size, 12)), np.zeros((sel.size, 12))
@@ -922,7 +1020,7 @@ class TickPipeline(_Handle):
                 w = self.plan_window(lo, n, int(M), 1, keys=("left_traj", "right_traj"))
                 rows = merge[sel] == M
                 left0[rows] = w["left_traj"][sel[rows] - lo, 0]; right0[rows] = w["right_traj"][sel[rows] - lo, 0]
-            plan = planner.plan_host(left0, right0, goals[sel], fs[sel])
+            plan = planner.plan_host(left0, right0, goals[sel], fs[sel], timing=timing)
             for k in out:
                 out[k][sel] = plan[k]
         self.replan_footsteps(merge, out, first_ds_ticks, stream=stream)
@@ -987,7 +1085,7 @@ class TickPipeline(_Handle):
         ticks_per_launch, dcm_controller ("mpc" / "reactive"), launches_per_tick, zmp_gain_scheduling (bool), planned_trajectories (bool),
         streamed_trajectories (bool), sensor_filters (the mask: bit 0 joint velocity, bit 1 wrench, bit 2 CoM), plan_generated (bool: the plan
         in place came from upload_footsteps), plan_record_ms (the device time of that upload's record pass) and ik_mode ("velocity" /
-        "position")."""
+        "position"), resident_plan (bool) and plan_timed (bool: the plan in place carries per-step timings)."""
         i, x = TickInfo(), TickInfoExt()
         check(lib().wcqp_tick_get_info_ext(self._h, C.byref(x)), "wcqp_tick_get_info_ext")
         check(lib().wcqp_tick_get_info(self._h, C.byref(i)), "wcqp_tick_get_info")
@@ -997,7 +1095,8 @@ class TickPipeline(_Handle):
                     launches_per_tick=int(i.launches_per_tick), zmp_gain_scheduling=bool(i.zmp_gain_scheduling),
                     planned_trajectories=bool(i.planned_trajectories), streamed_trajectories=bool(i.streamed_trajectories),
                     sensor_filters=int(i.sensor_filters), plan_generated=bool(i.plan_generated), plan_record_ms=float(i.plan_record_ms),
-                    ik_mode="position" if i.ik_mode == TICK_IK_POSITION else "velocity", resident_plan=bool(x.resident_plan))
+                    ik_mode="position" if i.ik_mode == TICK_IK_POSITION else "velocity", resident_plan=bool(x.resident_plan),
+                    plan_timed=bool(self.option(TICK_OPT_PLAN_TIMED)))
 
     def run(self, n_ticks: int, use_graph: bool = True, stream: int = 0):
         check(lib().wcqp_tick_run(self._h, int(n_ticks), int(bool(use_graph)), stream or None), "wcqp_tick_run")

@@ -12,7 +12,7 @@ struct StageSlot { int row = -1; };        // -1: the device sees NULL
 constexpr int kStageRefused = -1;           // (WCQP_E_INVALID)
 
 struct StageLayout {
-    static constexpr int kMaxRows = 16;   // the IK form stages 12 arrays, prepare 11, the unicycle planner 10
+    static constexpr int kMaxRows = 16;   // the IK form stages 12 arrays, prepare 11, the unicycle planner 10 (timed: 12)
     struct Row { const void* src; void* dst; size_t off, bytes; };     // src: copied in; dst: copied out (NULL: the caller does not want it back)
     Row rows[kMaxRows];
     int n = 0;

@@ -39,6 +39,20 @@ struct PlanGenDev {
     int n_robots, n_tiles;
 };
 
+// The timed calls' per-step durations (wcqp_tick_step_timing's device copies) and the start table the prologue writes from them
+struct PlanTimes {
+    const int* ss_k;                // [B][K] single-support stages of step k
+    const int* ds_k;                // [B][K] double-support stages behind step k (the last step's: see final_ds)
+    int* start;                     // [B][K + 1] entry k < n: the first stage s_k of step k's single support on the plan's own timeline (s_0 = first_ds);
+                                    // entries n .. K: the first standing stage
+    int final_ds;                   // the last step's double support, or 0 for its own ds_k
+};
+// what the timed kernels take: PlanGenDev as the untimed ones do (ss, ds and final_ds of it are not read), and the durations
+struct PlanGenTimedDev {
+    PlanGenDev g;
+    PlanTimes tm;
+};
+
 }  // namespace wcqp_tick
 
 namespace wcqp {
@@ -46,4 +60,7 @@ namespace wcqp {
 int plan_gen_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
 // the same three passes from per-robot origins, over the listed robots and tiles only (wcqp_tick_replan_footsteps); enqueue-only
 int plan_replan_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream);
+// the timed forms of the two (wcqp_tick_upload_footsteps_timed, wcqp_tick_replan_footsteps_timed)
+int plan_gen_timed_enqueue(const wcqp_tick::PlanGenTimedDev& t, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
+int plan_replan_timed_enqueue(const wcqp_tick::PlanGenTimedDev& t, hipStream_t stream);
 }  // namespace wcqp

@@ -8,6 +8,11 @@
 // origin[i] on - stage 0 of the rules moved to M_i, the start footprints taken from record M_i, the first double support's ZMP ramp started
 // where the recursion arrives at the old ref_traj[M_i] - over a host-compacted list of robots (prologue, DCM pass) and of (robot, tile)
 // pairs (record pass).  Nothing below M_i is stored: the DCM pass masks its tile write-out per stage, the record pass per 16-byte chunk.
+// The timed calls (wcqp_tick_upload_footsteps_timed, wcqp_tick_replan_footsteps_timed) run the same bodies with TIMED = true: step k of a
+// robot lasts its own ss_k + ds_k stages (plan_gen.h: PlanTimes), so no stage's step follows from a division.  The prologue writes the
+// robot's start table - entry k the first stage s_k of step k's single support on the plan's own timeline, entry n the first standing
+// stage -, the DCM pass walks a step index down it as its stage passes s_k, and the record pass copies the entries its tile touches into
+// LDS next to the footprints and finds each lane's step by a search there.  The untimed instantiations are the code they were.
 #include <cmath>
 #include "plan_gen.h"
 
@@ -20,8 +25,8 @@ __device__ __forceinline__ void zmp_point(const double* pose, const double* dl, 
     out[1] = pose[1] + (pose[6] * dl[0] + pose[7] * dl[1]);
 }
 
-template <bool RP>
-__device__ __forceinline__ void plan_prologue(const PlanGenDev& g) {
+template <bool RP, bool TIMED>
+__device__ __forceinline__ void plan_prologue(const PlanGenDev& g, const PlanTimes& tm) {
     const int slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= (RP ? g.n_robots : g.batch)) return;
     const int i = RP ? g.robots[slot] : slot;
@@ -36,6 +41,7 @@ __device__ __forceinline__ void plan_prologue(const PlanGenDev& g) {
     int set = g.set_base[i];
     if (!RP) { g.set_at[set] = (long long)(rec0 * kPlanRec); g.set_code[set] = 2; }
     ++set;
+    [[maybe_unused]] int s_next = g.first_ds;      // TIMED: s_k of the next step on the plan's own timeline, then the first standing stage
     for (int j = 0; j <= g.K; ++j) {
         if (j >= 1 && j <= n) {
             // step j - 1 lands: the swing foot's footprint becomes its target, rotated by the yaw increment about z
@@ -51,10 +57,20 @@ __device__ __forceinline__ void plan_prologue(const PlanGenDev& g) {
                 f[6 + c] = sn * r0 + cs * r1;
             }
             // its two changes of contact pair (the stance foot alone, both again), where a tick can reach them
-            const int s_k = org + g.first_ds + k * per;
+            int s_k, ss_k;
+            if constexpr (TIMED) {
+                ss_k = tm.ss_k[(size_t)i * g.K + k];
+                const int ds_k = k == n - 1 && tm.final_ds > 0 ? tm.final_ds : tm.ds_k[(size_t)i * g.K + k];
+                tm.start[(size_t)i * (g.K + 1) + k] = s_next;
+                s_k = org + s_next;
+                s_next += ss_k + ds_k;
+            } else {
+                s_k = org + g.first_ds + k * per; ss_k = g.ss;
+            }
             if (s_k <= g.max_ticks) { g.set_at[set] = (long long)((rec0 + s_k) * kPlanRec); g.set_code[set] = 1 - sw; ++set; }
-            if (s_k + g.ss <= g.max_ticks) { g.set_at[set] = (long long)((rec0 + s_k + g.ss) * kPlanRec); g.set_code[set] = 2; ++set; }
+            if (s_k + ss_k <= g.max_ticks) { g.set_at[set] = (long long)((rec0 + s_k + ss_k) * kPlanRec); g.set_code[set] = 2; ++set; }
         }
+        if constexpr (TIMED) { if (j >= n) tm.start[(size_t)i * (g.K + 1) + j] = s_next; }
         double* t = tab + (size_t)j * kFpRec;
         for (int k = 0; k < kFpPose; ++k) t[k] = fp[k];
         zmp_point(fp, g.delta[0], t + 24);
@@ -62,8 +78,10 @@ __device__ __forceinline__ void plan_prologue(const PlanGenDev& g) {
     }
 }
 
-__global__ void plan_prologue_kernel(PlanGenDev g) { plan_prologue<false>(g); }
-__global__ void plan_prologue_replan_kernel(PlanGenDev g) { plan_prologue<true>(g); }
+__global__ void plan_prologue_kernel(PlanGenDev g) { plan_prologue<false, false>(g, PlanTimes{}); }
+__global__ void plan_prologue_replan_kernel(PlanGenDev g) { plan_prologue<true, false>(g, PlanTimes{}); }
+__global__ void plan_prologue_timed_kernel(PlanGenTimedDev t) { plan_prologue<false, true>(t.g, t.tm); }
+__global__ void plan_prologue_replan_timed_kernel(PlanGenTimedDev t) { plan_prologue<true, true>(t.g, t.tm); }
 
 // ---- the DCM reference: xi_t = (xi_{t+1} - (1 - a) zmp_t) / a backwards from xi = zmp at the first standing stage
 constexpr int kDcmRobots = 32, kDcmTile = 32, kDcmRow = 2 * kDcmTile + 2;
@@ -72,8 +90,10 @@ constexpr int kDcmRobots = 32, kDcmTile = 32, kDcmRow = 2 * kDcmTile + 2;
 // ends at the tile of the wave's lowest origin.  The first double support's ramp starts at the point that makes the recursion arrive at
 // the old ref_traj[origin] (read before the pass stores over it): xi_M = X q^n - (1 - a) (za (S0 - S1) + zb S1), q = 1 / a, n = first_ds,
 // S0 = sum_{j=1..n} q^j, S1 = sum_{j=1..n} j q^j / (n + 1), X the recursion's value at stage M + n - one division where the pass gets there.
-template <bool RP>
-__device__ __forceinline__ void plan_dcm(const PlanGenDev& g) {
+// TIMED: the lane keeps the step its stage lies in (kc, from n - 1 down), that step's first stage and its two durations, and steps down
+// when the stage passes below the step's first one; the last step's double support lasts final_ds, or - 0 - its own ds.
+template <bool RP, bool TIMED>
+__device__ __forceinline__ void plan_dcm(const PlanGenDev& g, const PlanTimes& tm) {
     __shared__ double t_xi[kDcmRobots * kDcmRow];
     __shared__ double t_vel[kDcmRobots * kDcmRow];
     const int lane = threadIdx.x, r = lane >> 1, ax = lane & 1;
@@ -83,7 +103,17 @@ __device__ __forceinline__ void plan_dcm(const PlanGenDev& g) {
     const int i = RP ? g.robots[live ? i_raw : count - 1] : (live ? i_raw : g.batch - 1);
     const int org = RP ? g.origin[i] : 0;
     const int n = g.n_steps[i], per = g.ss + g.ds, T = g.traj_len;
-    const int s_end = org + (n > 0 ? g.first_ds + n * per - g.ds + g.final_ds : g.first_ds);      // the first standing stage
+    [[maybe_unused]] const int* start = TIMED ? tm.start + (size_t)i * (size_t)(g.K + 1) : nullptr;
+    int s_end;                                                                                    // the first standing stage
+    if constexpr (TIMED) s_end = org + start[n];
+    else s_end = org + (n > 0 ? g.first_ds + n * per - g.ds + g.final_ds : g.first_ds);
+    [[maybe_unused]] int kc = n - 1, kc_s = 0, kc_ss = 0, kc_ds = 0;
+    if constexpr (TIMED) {
+        if (n > 0) {
+            kc_s = start[kc]; kc_ss = tm.ss_k[(size_t)i * g.K + kc];
+            kc_ds = tm.final_ds > 0 ? tm.final_ds : tm.ds_k[(size_t)i * g.K + kc];
+        }
+    }
     const double* tab = g.table + (size_t)i * (size_t)(g.K + 1) * kFpRec;
     const unsigned char* side = g.side + (size_t)i * g.K;
     const double mid0 = 0.5 * (tab[24 + ax] + tab[26 + ax]);
@@ -121,11 +151,21 @@ __device__ __forceinline__ void plan_dcm(const PlanGenDev& g) {
                 }
                 z = za + ((double)(tr + 1) / (double)(g.first_ds + 1)) * (zb - za);
             } else {
-                const int rr = tr - g.first_ds;
-                int k = rr / per;
-                k = k < n - 1 ? k : n - 1;
-                const int u = rr - k * per;
-                if (u < g.ss) {
+                int k, u, ss_k;
+                if constexpr (TIMED) {
+                    while (kc > 0 && tr < kc_s) {
+                        --kc;
+                        kc_s = start[kc]; kc_ss = tm.ss_k[(size_t)i * g.K + kc]; kc_ds = tm.ds_k[(size_t)i * g.K + kc];
+                    }
+                    k = kc; u = tr - kc_s; ss_k = kc_ss;
+                } else {
+                    const int rr = tr - g.first_ds;
+                    k = rr / per;
+                    k = k < n - 1 ? k : n - 1;
+                    u = rr - k * per;
+                    ss_k = g.ss;
+                }
+                if (u < ss_k) {
                     if (key != 2 * k) { key = 2 * k; za = tab[(size_t)k * kFpRec + 24 + 2 * (1 - side[k]) + ax]; }
                     z = za;
                 } else {
@@ -135,8 +175,8 @@ __device__ __forceinline__ void plan_dcm(const PlanGenDev& g) {
                         za = e[24 + 2 * (1 - side[k]) + ax];
                         zb = k < n - 1 ? e[24 + 2 * (1 - side[k + 1]) + ax] : 0.5 * (e[24 + ax] + e[26 + ax]);
                     }
-                    const int nds = k == n - 1 ? g.final_ds : g.ds;
-                    z = za + ((double)(u - g.ss + 1) / (double)(nds + 1)) * (zb - za);
+                    const int nds = TIMED ? kc_ds : (k == n - 1 ? g.final_ds : g.ds);
+                    z = za + ((double)(u - ss_k + 1) / (double)(nds + 1)) * (zb - za);
                 }
             }
             xi = (xi - b1 * z) / a;
@@ -165,8 +205,10 @@ __device__ __forceinline__ void plan_dcm(const PlanGenDev& g) {
     }
 }
 
-__global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) { plan_dcm<false>(g); }
-__global__ __launch_bounds__(64) void plan_dcm_replan_kernel(PlanGenDev g) { plan_dcm<true>(g); }
+__global__ __launch_bounds__(64) void plan_dcm_kernel(PlanGenDev g) { plan_dcm<false, false>(g, PlanTimes{}); }
+__global__ __launch_bounds__(64) void plan_dcm_replan_kernel(PlanGenDev g) { plan_dcm<true, false>(g, PlanTimes{}); }
+__global__ __launch_bounds__(64) void plan_dcm_timed_kernel(PlanGenTimedDev t) { plan_dcm<false, true>(t.g, t.tm); }
+__global__ __launch_bounds__(64) void plan_dcm_replan_timed_kernel(PlanGenTimedDev t) { plan_dcm<true, true>(t.g, t.tm); }
 
 // ---- the records.  A wave takes 64 consecutive stages of one robot - 20 KiB of records, contiguous in HBM and 64-byte aligned (a record
 // is five lines): lane l computes stage s0 + l into row l of an LDS tile (rows of 41 doubles: the 8-byte LDS stores of 16 lanes fall on
@@ -179,8 +221,20 @@ constexpr int kRecTile = 64, kRecRow = kPlanRec + 1, kTabMax = kRecTile / 2 + 2;
 // lanes below the origin compute nothing and the write-out skips their records (a record is twenty 16-byte chunks, none shared with a
 // neighbour).  Before the new plan's first single support the fixed-frame bit keeps the value of stage origin - 1, a record no replan
 // of this origin writes.
-template <bool RP>
-__device__ __forceinline__ void plan_record(const PlanGenDev& g) {
+// TIMED: the largest k of 0 .. n - 1 whose first stage start[k] is <= s, or -1 (n = 0, or s lies in the first double support)
+__device__ __forceinline__ int step_at(const int* start, int n, int s) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (start[mid] <= s) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+
+// TIMED: the first stages and single-support lengths of steps j_lo .. j_hi - 1 sit in LDS next to the footprints (stl, ssl [kTabMax], the
+// timed kernels' own: a step lasts two stages or more), and a lane finds its step by counting the first stages at or below its own.
+template <bool RP, bool TIMED>
+__device__ __forceinline__ void plan_record(const PlanGenDev& g, const PlanTimes& tm, int* stl, int* ssl) {
     __shared__ double tile[kRecTile * kRecRow];
     __shared__ double fpt[kTabMax * kFpPose];
     __shared__ double dyaw[kTabMax];
@@ -193,7 +247,11 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g) {
     const int n = g.n_steps[i], per = g.ss + g.ds;
     // entries j_lo .. j_hi: from the step the first stage lies in (the last step's, once standing: its stance foot is the fixed frame) to the
     // footprints behind the step the last stage lies in (stages on the plan's own timeline: the origin is its stage 0)
-    auto step_of = [&](int s) { return s < g.first_ds ? 0 : (s - g.first_ds) / per; };
+    [[maybe_unused]] const int* start = TIMED ? tm.start + i * (size_t)(g.K + 1) : nullptr;
+    auto step_of = [&](int s) {
+        if constexpr (TIMED) { const int k = step_at(start, n, s); return k < 0 ? 0 : k; }
+        else return s < g.first_ds ? 0 : (s - g.first_ds) / per;
+    };
     const int last = n > 0 ? n - 1 : 0;
     int j_lo = step_of((RP && s0 < org ? org : s0) - org);
     j_lo = j_lo < last ? j_lo : last;
@@ -206,6 +264,7 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g) {
     if (lane < cnt && j_lo + lane < n) {
         swing[lane] = g.side[i * g.K + j_lo + lane];
         dyaw[lane] = g.target[(i * g.K + j_lo + lane) * 3 + 2];
+        if constexpr (TIMED) { stl[lane] = start[j_lo + lane]; ssl[lane] = tm.ss_k[i * g.K + j_lo + lane]; }
     }
     int fixed0 = 0;
     if (RP) fixed0 = ((int)g.rec[(i * (size_t)T + (size_t)(org - 1)) * kPlanRec + kPlanFlags] & 4) ? 0 : 1;
@@ -213,9 +272,19 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g) {
     const int s = s0 + lane, sr = s - org;
     if (lane < nvalid && sr >= 0) {
         double* o = tile + lane * kRecRow;
-        int k = -1, u = 0;
-        if (sr >= g.first_ds) { k = (sr - g.first_ds) / per; u = (sr - g.first_ds) - k * per; }
-        const bool swinging = k >= 0 && k < n && u < g.ss;
+        int k = -1, u = 0, ss_k = g.ss;
+        // the steps in LDS: j_lo .. j_lo + nst - 1
+        [[maybe_unused]] const int nst = (cnt < n - j_lo ? cnt : n - j_lo);
+        if constexpr (TIMED) {
+            if (sr >= g.first_ds && n > 0) {
+                int x = 0;
+                for (int y = 1; y < nst; ++y) x += stl[y] <= sr ? 1 : 0;
+                k = j_lo + x; u = sr - stl[x]; ss_k = ssl[x];
+            }
+        } else {
+            if (sr >= g.first_ds) { k = (sr - g.first_ds) / per; u = (sr - g.first_ds) - k * per; }
+        }
+        const bool swinging = k >= 0 && k < n && u < ss_k;
         // the footprints in force: after k + 1 landed steps, or - the swing foot still in the air - after k
         int j = k < 0 ? 0 : (k < n ? k + (swinging ? 0 : 1) : n);
         j = j - j_lo;
@@ -230,10 +299,10 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g) {
             const double dy = dyaw[k - j_lo < cnt ? k - j_lo : cnt - 1];
             const double* p0 = f + 12 * sw;
             const double* p1 = f + (j + 1 < cnt ? kFpPose : 0) + 12 * sw;       // the target: the same foot after this step
-            const double x = (double)(u + 1) / (double)g.ss, x1 = 1.0 - x;
+            const double x = (double)(u + 1) / (double)ss_k, x1 = 1.0 - x;
             const double m = x * x * x * (10.0 - 15.0 * x + 6.0 * x * x), dm = 30.0 * x * x * x1 * x1;
             const double lz = 16.0 * x * x * x1 * x1, dlz = 32.0 * x * x1 * (1.0 - 2.0 * x);
-            const double inv = 1.0 / ((double)g.ss * g.dT);
+            const double inv = 1.0 / ((double)ss_k * g.dT);
             double* op = o + kPlanLeft + 12 * sw;
             double* ot = o + kPlanTwL + 6 * sw;
             const double dx = p1[0] - p0[0], dyy = p1[1] - p0[1];
@@ -254,7 +323,20 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g) {
         // the support-polygon set in force: the origin's, plus the changes of contact pair up to this stage that a tick can reach
         const int se = (s < g.max_ticks ? s : g.max_ticks) - org;
         int changes = 0;
-        if (se >= g.first_ds) {
+        if constexpr (TIMED) {
+            // (se <= s: its step is the lane's own or an earlier one of the tile - or, below the tile, found in the robot's table)
+            if (se >= g.first_ds && n > 0) {
+                int ke, s_ke, ss_ke;
+                if (se >= stl[0]) {
+                    int x = 0;
+                    for (int y = 1; y < nst; ++y) x += stl[y] <= se ? 1 : 0;
+                    ke = j_lo + x; s_ke = stl[x]; ss_ke = ssl[x];
+                } else {
+                    ke = step_at(start, n, se); s_ke = start[ke]; ss_ke = tm.ss_k[i * g.K + ke];
+                }
+                changes = 2 * ke + 1 + (se - s_ke >= ss_ke ? 1 : 0);
+            }
+        } else if (se >= g.first_ds) {
             const int ke = (se - g.first_ds) / per, ue = (se - g.first_ds) - ke * per;
             changes = ke < n ? 2 * ke + 1 + (ue >= g.ss ? 1 : 0) : 2 * n;
         }
@@ -270,8 +352,16 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g) {
     }
 }
 
-__global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) { plan_record<false>(g); }
-__global__ __launch_bounds__(kRecTile) void plan_record_replan_kernel(PlanGenDev g) { plan_record<true>(g); }
+__global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) { plan_record<false, false>(g, PlanTimes{}, nullptr, nullptr); }
+__global__ __launch_bounds__(kRecTile) void plan_record_replan_kernel(PlanGenDev g) { plan_record<true, false>(g, PlanTimes{}, nullptr, nullptr); }
+__global__ __launch_bounds__(kRecTile) void plan_record_timed_kernel(PlanGenTimedDev t) {
+    __shared__ int stl[kTabMax], ssl[kTabMax];
+    plan_record<false, true>(t.g, t.tm, stl, ssl);
+}
+__global__ __launch_bounds__(kRecTile) void plan_record_replan_timed_kernel(PlanGenTimedDev t) {
+    __shared__ int stl[kTabMax], ssl[kTabMax];
+    plan_record<true, true>(t.g, t.tm, stl, ssl);
+}
 
 }  // namespace
 
@@ -295,6 +385,39 @@ int plan_gen_enqueue(const PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, h
     return WCQP_OK;
 }
 
+
+int plan_gen_timed_enqueue(const PlanGenTimedDev& t, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) {
+    const PlanGenDev& g = t.g;
+    if (g.batch < 1 || g.traj_len < 1 || g.first_ds < 1 || t.tm.final_ds < 0 || g.K < 0 || !t.tm.start || (g.K > 0 && (!t.tm.ss_k || !t.tm.ds_k))) return WCQP_E_INVALID;
+    hipLaunchKernelGGL(plan_prologue_timed_kernel, dim3((unsigned)((g.batch + 63) / 64)), dim3(64), 0, stream, t);
+    hipLaunchKernelGGL(plan_dcm_timed_kernel, dim3((unsigned)((g.batch + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, t);
+    if (rec0) WCQP_HIP_TRY(hipEventRecord(rec0, stream));
+    // (robots on grid.y: 65535 at most per launch)
+    for (int i0 = 0; i0 < g.batch; i0 += 65535) {
+        PlanGenTimedDev q = t;
+        PlanGenDev& p = q.g;
+        const int nb = g.batch - i0 < 65535 ? g.batch - i0 : 65535;
+        p.n_steps += i0; p.side += (size_t)i0 * g.K; p.target += (size_t)i0 * g.K * 3; p.state += (size_t)i0 * kStateLen;
+        p.set_base += i0; p.table += (size_t)i0 * (size_t)(g.K + 1) * kFpRec; p.rec += (size_t)i0 * (size_t)g.traj_len * kPlanRec;
+        q.tm.ss_k += (size_t)i0 * g.K; q.tm.ds_k += (size_t)i0 * g.K; q.tm.start += (size_t)i0 * (size_t)(g.K + 1);
+        hipLaunchKernelGGL(plan_record_timed_kernel, dim3((unsigned)((g.traj_len + kRecTile - 1) / kRecTile), (unsigned)nb), dim3(kRecTile), 0, stream, q);
+    }
+    if (rec1) WCQP_HIP_TRY(hipEventRecord(rec1, stream));
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+
+int plan_replan_timed_enqueue(const PlanGenTimedDev& t, hipStream_t stream) {
+    const PlanGenDev& g = t.g;
+    if (g.batch < 1 || g.traj_len < 1 || g.first_ds < 1 || t.tm.final_ds < 0 || g.K < 0 || !t.tm.start || (g.K > 0 && (!t.tm.ss_k || !t.tm.ds_k))) return WCQP_E_INVALID;
+    if (!g.origin || !g.robots || !g.tiles || !g.h0 || g.n_robots < 0 || g.n_tiles < 0) return WCQP_E_INVALID;
+    if (g.n_robots == 0) return WCQP_OK;
+    hipLaunchKernelGGL(plan_prologue_replan_timed_kernel, dim3((unsigned)((g.n_robots + 63) / 64)), dim3(64), 0, stream, t);
+    hipLaunchKernelGGL(plan_dcm_replan_timed_kernel, dim3((unsigned)((g.n_robots + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, t);
+    if (g.n_tiles > 0) hipLaunchKernelGGL(plan_record_replan_timed_kernel, dim3((unsigned)g.n_tiles), dim3(kRecTile), 0, stream, t);
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
 
 int plan_replan_enqueue(const PlanGenDev& g, hipStream_t stream) {
     if (g.batch < 1 || g.traj_len < 1 || g.ss < 1 || g.ds < 1 || g.first_ds < 1 || g.final_ds < 1 || g.K < 0) return WCQP_E_INVALID;

@@ -116,6 +116,10 @@ struct wcqp_tick_s {
         int ss = 0, ds = 0, final_ds = 0, cap = 0;
         double lift = 0.0, delta[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
         std::vector<int> origin, first_ds, n_steps, keep;
+        // a TIMED plan (wcqp_tick_upload_footsteps_timed): ss and ds are unused, final_ds is the upload's own value (0: a last step's own
+        // ds), cap counts a step as two stages, and dur[i] holds the durations of robot i's plan in force, ss_k then ds_k per step
+        bool timed = false;
+        std::vector<std::vector<int>> dur;
     } gp;
     // its per-call device memory (footsteps, robot and tile lists, footprint tables, set table), guarded behind the call's kernels
     StagedBlock rp;

@@ -168,6 +168,20 @@ bool footsteps_valid(size_t i, int K, const int32_t* n_steps, const uint8_t* sid
     return true;
 }
 
+// Valid durations of robot i's footsteps (the timed calls): ss >= 1 and ds >= 1 for every step it takes
+bool durations_valid(size_t i, int K, const int32_t* n_steps, const wcqp_tick_step_timing* tm) {
+    for (int k = 0; k < n_steps[i]; ++k)
+        if (tm->ss_ticks[i * K + k] < 1 || tm->ds_ticks[i * K + k] < 1) return false;
+    return true;
+}
+// ... and the stages they occupy behind the first double support, the last step's double support as the plan resolves it
+long long durations_span(size_t i, int K, const int32_t* n_steps, const wcqp_tick_step_timing* tm, int final_ds) {
+    long long sum = 0;
+    const int n = n_steps[i];
+    for (int k = 0; k < n; ++k) sum += (long long)tm->ss_ticks[i * K + k] + (k == n - 1 && final_ds > 0 ? final_ds : tm->ds_ticks[i * K + k]);
+    return sum;
+}
+
 // What every pass of plan_gen.hip takes of a handle whose GenPlan scalars are in place, for lists of at most K steps per robot; the caller
 // adds its own list pointers and first_ds (and a replan its origins, robots, tiles and h0)
 PlanGenDev plan_gen_of(const wcqp_tick_s* h, int K) {
@@ -316,6 +330,21 @@ wcqp_goal::PlanInForce plan_in_force(const wcqp_tick_s* h, size_t i) {
     const auto& gp = h->gp;
     return {gp.origin[i], gp.first_ds[i], gp.n_steps[i], gp.ss, gp.ds};
 }
+// a TIMED plan in force: M lies inside one of robot i's single supports, [s_k, s_k + ss_k) on its own timeline
+bool in_single_support_timed(const wcqp_tick_s* h, size_t i, int M) {
+    const auto& gp = h->gp;
+    const std::vector<int>& du = gp.dur[i];
+    long long s_k = (long long)gp.origin[i] + gp.first_ds[i];
+    for (int k = 0; k < gp.n_steps[i] && s_k <= M; ++k) {
+        if (M < s_k + du[2 * k]) return true;
+        s_k += (long long)du[2 * k] + du[2 * k + 1];
+    }
+    return false;
+}
+// wcqp_goal::merge_allowed on it
+bool merge_allowed_timed(const wcqp_tick_s* h, size_t i, int M, int t0, int T) {
+    return M >= 1 && M >= t0 && M < T && M >= h->gp.origin[i] && !in_single_support_timed(h, i, M);
+}
 int consumed_stages(const wcqp_tick_s* h) { return h->ticks_enqueued + (h->plan_staged ? 1 : 0); }
 
 // What a replan needs of the host per call, for footsteps from the caller's lists and from goals alike: per robot the merge stage (-1: it
@@ -330,19 +359,35 @@ struct ReplanCall {
 // from); the new plan's sets follow them in the robot's `cap` slots.  That they fit needs no n_new: cap (wcqp_tick_upload_footsteps)
 // bounds the steps that START at a stage <= max_ticks for ANY footstep list - a step occupies ss + 1 stages or more - and the stitched
 // plan is one such list, so the count below is a check of the arithmetic where n_new is known and is not evaluated where it is not.
-int replan_admit(const wcqp_tick_s* h, size_t i, int M, int fd, int n_new, ReplanCall& c) {
+// A timed plan (tm: the new steps' durations, [B][K]) counts both on the per-step timelines.
+int replan_admit(const wcqp_tick_s* h, size_t i, int M, int fd, int n_new, ReplanCall& c, const wcqp_tick_step_timing* tm = nullptr, int K = 0) {
     const auto& gp = h->gp;
     const int per = gp.ss + gp.ds, O = gp.origin[i], fo = gp.first_ds[i], no = gp.n_steps[i];
     int c0 = gp.keep[i];
     const int reach = M < h->p.max_ticks ? M : h->p.max_ticks;
-    for (int k = 0; k < no; ++k) {
-        const long long s_k = (long long)O + fo + (long long)k * per;
-        c0 += (s_k <= reach ? 1 : 0) + (s_k + gp.ss <= reach ? 1 : 0);
-    }
     int fresh = 0;
-    for (int k = 0; k < n_new; ++k) {
-        const long long s_k = (long long)M + fd + (long long)k * per;
-        fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + gp.ss <= h->p.max_ticks ? 1 : 0);
+    if (tm) {
+        long long s_k = (long long)O + fo;
+        for (int k = 0; k < no; ++k) {
+            const int ss = gp.dur[i][2 * k];
+            c0 += (s_k <= reach ? 1 : 0) + (s_k + ss <= reach ? 1 : 0);
+            s_k += (long long)ss + gp.dur[i][2 * k + 1];
+        }
+        s_k = (long long)M + fd;
+        for (int k = 0; k < n_new; ++k) {
+            const int ss = tm->ss_ticks[i * K + k];
+            fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + ss <= h->p.max_ticks ? 1 : 0);
+            s_k += (long long)ss + tm->ds_ticks[i * K + k];
+        }
+    } else {
+        for (int k = 0; k < no; ++k) {
+            const long long s_k = (long long)O + fo + (long long)k * per;
+            c0 += (s_k <= reach ? 1 : 0) + (s_k + gp.ss <= reach ? 1 : 0);
+        }
+        for (int k = 0; k < n_new; ++k) {
+            const long long s_k = (long long)M + fd + (long long)k * per;
+            fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + gp.ss <= h->p.max_ticks ? 1 : 0);
+        }
     }
     if (c0 < 1 || c0 + fresh > gp.cap) return WCQP_E_INVALID;      // (cannot happen: see cap in wcqp_tick_upload_footsteps)
     c.merge[i] = M; c.keep[i] = c0;
@@ -357,6 +402,7 @@ int replan_admit(const wcqp_tick_s* h, size_t i, int M, int fd, int n_new, Repla
 struct ReplanSource {
     const wcqp_tick_replan* lists;
     const double* goal; const uint8_t* first_side; const wcqp_unicycle::UniPar* par;
+    const wcqp_tick_step_timing* tm = nullptr;      // with lists, on a timed plan: the new steps' durations
 };
 
 // Everything behind the checks, for a call that lists a robot at least: the call's device block - what the host hands over first (one
@@ -379,9 +425,11 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
     const size_t o_org = carve(B * 4), o_base = carve(B * 4), o_rob = carve(nr * 4), o_tile = carve(nt * 8);
     const size_t o_n = goals ? 0 : carve(B * 4), o_side = goals ? 0 : carve(BK), o_tg = goals ? 0 : carve(BK * 24);
     const size_t o_goal = goals ? carve(B * 16) : 0, o_fsin = goals ? carve(B) : 0;
+    const size_t o_ssk = src.tm ? carve(BK * 4) : 0, o_dsk = src.tm ? carve(BK * 4) : 0;
     const size_t front = off;
     const size_t o_res = goals ? carve(r_bytes) : 0;
     const size_t o_tab = carve(B * (size_t)(K + 1) * kFpRec * 8), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
+    const size_t o_start = src.tm ? carve(B * (size_t)(K + 1) * 4) : 0;
     std::vector<char> blob(front, 0);
     {
         int* org = reinterpret_cast<int*>(blob.data() + o_org); int* base = reinterpret_cast<int*>(blob.data() + o_base);
@@ -395,6 +443,7 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
             int* nn = reinterpret_cast<int*>(blob.data() + o_n);
             for (size_t i = 0; i < B; ++i) nn[i] = c.merge[i] != -1 ? src.lists->n_steps[i] : 0;
             if (BK > 0) { std::memcpy(blob.data() + o_side, src.lists->side, BK); std::memcpy(blob.data() + o_tg, src.lists->target, BK * 24); }
+            if (src.tm && BK > 0) { std::memcpy(blob.data() + o_ssk, src.tm->ss_ticks, BK * 4); std::memcpy(blob.data() + o_dsk, src.tm->ds_ticks, BK * 4); }
         } else {
             // (a goal of a robot that keeps its plan may be anything, a NaN too: its row is zero here and no lane reads it)
             double* gl = reinterpret_cast<double*>(blob.data() + o_goal);
@@ -440,7 +489,11 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
         WCQP_HIP_TRY(hipGetLastError());
     }
     WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
-    if (const int rc = wcqp::plan_replan_enqueue(g, st); rc != WCQP_OK) return rc;
+    if (src.tm) {
+        const PlanGenTimedDev t{g, PlanTimes{reinterpret_cast<const int*>(buf + o_ssk), reinterpret_cast<const int*>(buf + o_dsk),
+                                             reinterpret_cast<int*>(buf + o_start), gp.final_ds}};
+        if (const int rc = wcqp::plan_replan_timed_enqueue(t, st); rc != WCQP_OK) return rc;
+    } else if (const int rc = wcqp::plan_replan_enqueue(g, st); rc != WCQP_OK) return rc;
     hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
                        h->set_A, h->set_b, h->set_nc);
     WCQP_HIP_TRY(hipGetLastError());
@@ -452,6 +505,12 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
     for (int i : c.robots) {
         gp.origin[i] = c.merge[i]; gp.first_ds[i] = fd; gp.keep[i] = c.keep[i];
         if (!goals) gp.n_steps[i] = src.lists->n_steps[i];
+        if (src.tm) {
+            gp.dur[i].resize(2 * (size_t)gp.n_steps[i]);
+            for (int k = 0; k < gp.n_steps[i]; ++k) {
+                gp.dur[i][2 * k] = src.tm->ss_ticks[(size_t)i * K + k]; gp.dur[i][2 * k + 1] = src.tm->ds_ticks[(size_t)i * K + k];
+            }
+        }
     }
     if (goals) {
         gc.pending = true; gc.owed = c.robots; gc.K = K;
@@ -468,11 +527,8 @@ int replan_ready(const wcqp_tick_s* h) {
     return WCQP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps) {
+// wcqp_tick_upload_footsteps (tm NULL) and wcqp_tick_upload_footsteps_timed
+int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps, const wcqp_tick_step_timing* tm) {
     if (!h || !in || !steps) return WCQP_E_INVALID;
     if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
     TickDev& d = h->d;
@@ -480,10 +536,12 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     const int K = steps->max_steps;
     // everything is checked before anything of the handle changes (a handle uploaded before keeps that upload)
     if (!in->state0 || !in->q0 || !in->com0 || !steps->n_steps || K < 0 || (K > 0 && (!steps->side || !steps->target))) return WCQP_E_INVALID;
-    if (steps->first_ds_ticks < 1 || steps->ss_ticks < 1 || steps->ds_ticks < 1 || steps->final_ds_ticks < 0) return WCQP_E_INVALID;
-    const int final_ds = steps->final_ds_ticks > 0 ? steps->final_ds_ticks : steps->ds_ticks;
+    if (steps->first_ds_ticks < 1 || (!tm && (steps->ss_ticks < 1 || steps->ds_ticks < 1)) || steps->final_ds_ticks < 0) return WCQP_E_INVALID;
+    if (tm && K > 0 && (!tm->ss_ticks || !tm->ds_ticks)) return WCQP_E_INVALID;
+    // (a timed plan keeps the caller's final_ds_ticks: 0 stands for every robot's own last ds)
+    const int final_ds = tm || steps->final_ds_ticks > 0 ? steps->final_ds_ticks : steps->ds_ticks;
     const long long per = (long long)steps->ss_ticks + steps->ds_ticks;
-    if ((long long)steps->first_ds_ticks + (long long)K * per + final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    if (!tm && (long long)steps->first_ds_ticks + (long long)K * per + final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
     auto finite = [](const double* a, size_t n) { bool ok = true; for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(a[k]); return ok; };
     if (!std::isfinite(steps->lift) || !finite(steps->zmp_delta_left, 2) || !finite(steps->zmp_delta_right, 2)) return WCQP_E_INVALID;
     if (!finite(in->q0, B * kDof) || !finite(in->com0, B * 2) || (in->dcm0 && !finite(in->dcm0, B * 2)) || (in->u_init && !finite(in->u_init, B * 2)))
@@ -491,11 +549,14 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     // the support-polygon sets: every robot owns `cap` slots - stage 0's set, then two per step (the stance foot alone, both again) where a
     // tick can reach them.  A step occupies ss + 1 stages or more, so at most (max_ticks + 1) / (ss + 1) + 1 steps start at a stage
     // <= max_ticks, whatever wcqp_tick_replan_footsteps later stitches together: the range never has to grow, and no set ever moves
-    const int cap = 1 + 2 * ((h->p.max_ticks + 1) / (steps->ss_ticks + 1) + 1);
+    // (a timed step: a stage of single and a stage of double support or more)
+    const int cap = 1 + 2 * ((h->p.max_ticks + 1) / (tm ? 2 : steps->ss_ticks + 1) + 1);
     std::vector<int> set_base(B);
     const size_t ns = B * (size_t)cap;
     for (size_t i = 0; i < B; ++i) {
         if (!footsteps_valid(i, K, steps->n_steps, steps->side, steps->target)) return WCQP_E_INVALID;
+        if (tm && (!durations_valid(i, K, steps->n_steps, tm) ||
+                   steps->first_ds_ticks + durations_span(i, K, steps->n_steps, tm, final_ds) > (1ll << 30))) return WCQP_E_INVALID;
         if (!finite(in->state0 + i * kStateLen + 24, 24) || !std::isfinite(in->state0[i * kStateLen + 68])) return WCQP_E_INVALID;
         set_base[i] = (int)(i * (size_t)cap);
     }
@@ -506,7 +567,11 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     if (!h->gen_zmp0) { const int rca = dev_alloc(h, &h->gen_zmp0, B * 2); if (rca != WCQP_OK) return rca; }
     {   // what this plan fixes for the handle, and a replan needs to know of it (wcqp_tick_replan_footsteps)
         auto& gp = h->gp;
-        gp.ss = steps->ss_ticks; gp.ds = steps->ds_ticks; gp.final_ds = final_ds; gp.cap = cap; gp.lift = steps->lift;
+        gp.ss = tm ? 0 : steps->ss_ticks; gp.ds = tm ? 0 : steps->ds_ticks; gp.final_ds = final_ds; gp.cap = cap; gp.lift = steps->lift;
+        gp.timed = tm != nullptr;
+        gp.dur.assign(tm ? B : 0, std::vector<int>());
+        for (size_t i = 0; tm && i < B; ++i)
+            for (int k = 0; k < steps->n_steps[i]; ++k) { gp.dur[i].push_back(tm->ss_ticks[i * K + k]); gp.dur[i].push_back(tm->ds_ticks[i * K + k]); }
         for (int k = 0; k < 2; ++k) { gp.delta[0][k] = steps->zmp_delta_left[k]; gp.delta[1][k] = steps->zmp_delta_right[k]; }
     }
     // the footsteps, the table and the set table: device memory of this call
@@ -522,6 +587,16 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     double* d_tab = static_cast<double*>(scratch.get(B * (size_t)(K + 1) * kFpRec * 8));
     long long* d_at = static_cast<long long*>(scratch.get(ns * 8)); int* d_code = static_cast<int*>(scratch.get(ns * 4));
     if (!d_n || !d_base || !d_side || !d_tg || !d_tab || !d_at || !d_code) return WCQP_E_NOMEM;
+    int *d_ssk = nullptr, *d_dsk = nullptr, *d_start = nullptr;
+    if (tm) {
+        d_ssk = static_cast<int*>(scratch.get(BK * 4)); d_dsk = static_cast<int*>(scratch.get(BK * 4));
+        d_start = static_cast<int*>(scratch.get(B * (size_t)(K + 1) * 4));
+        if (!d_ssk || !d_dsk || !d_start) return WCQP_E_NOMEM;
+        if (BK > 0) {
+            WCQP_HIP_TRY(hipMemcpy(d_ssk, tm->ss_ticks, BK * 4, hipMemcpyHostToDevice));
+            WCQP_HIP_TRY(hipMemcpy(d_dsk, tm->ds_ticks, BK * 4, hipMemcpyHostToDevice));
+        }
+    }
     WCQP_HIP_TRY(hipMemset(d_code, 0xff, ns * 4));      // (-1: a slot without a set; the prologue enters the ones in use)
     WCQP_HIP_TRY(hipMemcpy(d_n, steps->n_steps, B * 4, hipMemcpyHostToDevice));
     WCQP_HIP_TRY(hipMemcpy(d_base, set_base.data(), B * 4, hipMemcpyHostToDevice));
@@ -533,7 +608,8 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     g.n_steps = d_n; g.side = d_side; g.target = d_tg; g.set_base = d_base; g.table = d_tab; g.set_at = d_at; g.set_code = d_code;
     g.first_ds = steps->first_ds_ticks;
     for (hipEvent_t& e : h->gen_ev) if (!e) WCQP_HIP_TRY(hipEventCreate(&e));
-    int rc = wcqp::plan_gen_enqueue(g, nullptr, h->gen_ev[0], h->gen_ev[1]);
+    int rc = tm ? wcqp::plan_gen_timed_enqueue(PlanGenTimedDev{g, PlanTimes{d_ssk, d_dsk, d_start, final_ds}}, nullptr, h->gen_ev[0], h->gen_ev[1])
+                : wcqp::plan_gen_enqueue(g, nullptr, h->gen_ev[0], h->gen_ev[1]);
     if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);      // (synchronises)
     if (rc != WCQP_OK) return rc;
     WCQP_HIP_TRY(hipEventElapsedTime(&h->gen_record_ms, h->gen_ev[0], h->gen_ev[1]));
@@ -564,14 +640,17 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
     return wcqp::upload_state(h, &eff, 2);
 }
 
-int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) {
-    if (!h || !rp) return WCQP_E_INVALID;
+// wcqp_tick_replan_footsteps (tm NULL, an untimed plan) and wcqp_tick_replan_footsteps_timed (a timed one)
+int replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_step_timing* tm, bool timed, void* stream) {
+    if (!h || !rp || (timed && !tm)) return WCQP_E_INVALID;
     if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    if (h->gp.timed != timed) return WCQP_E_UNSUPPORTED;           // (a plan is timed or not from its upload on)
     const size_t B = (size_t)h->d.batch;
     const int K = rp->max_steps, T = h->d.traj_len, fd = rp->first_ds_ticks, per = h->gp.ss + h->gp.ds;
     // everything is checked here, in closed form, before anything changes: a refused call leaves the handle exactly as it was
     if (!rp->merge_stage || !rp->n_steps || K < 0 || (K > 0 && (!rp->side || !rp->target)) || fd < 1) return WCQP_E_INVALID;
-    if ((long long)T + fd + (long long)K * per + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    if (tm && K > 0 && (!tm->ss_ticks || !tm->ds_ticks)) return WCQP_E_INVALID;
+    if (!tm && (long long)T + fd + (long long)K * per + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
     if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (the step counts a goal call still owes)
     ReplanCall c(B);
     for (size_t i = 0; i < B; ++i) {
@@ -580,17 +659,40 @@ int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* 
         // stage 0 is the initial state's, stages the enqueued ticks have consumed stay (within one wcqp_tick_run call the kernel reads a stage
         // ahead, between calls nothing is ahead), a plan is cut only behind its own origin, and the merge stage has both feet in contact in
         // the plan in force: not inside one of its single supports
-        if (!wcqp_goal::merge_allowed(plan_in_force(h, i), M, consumed_stages(h), T)) return WCQP_E_INVALID;
+        if (!(tm ? merge_allowed_timed(h, i, M, consumed_stages(h), T) : wcqp_goal::merge_allowed(plan_in_force(h, i), M, consumed_stages(h), T)))
+            return WCQP_E_INVALID;
         if (!footsteps_valid(i, K, rp->n_steps, rp->side, rp->target)) return WCQP_E_INVALID;
-        if (const int rc = replan_admit(h, i, M, fd, rp->n_steps[i], c); rc != WCQP_OK) return rc;
+        if (tm && (!durations_valid(i, K, rp->n_steps, tm) || (long long)T + fd + durations_span(i, K, rp->n_steps, tm, h->gp.final_ds) > (1ll << 30)))
+            return WCQP_E_INVALID;
+        if (const int rc = replan_admit(h, i, M, fd, rp->n_steps[i], c, tm, K); rc != WCQP_OK) return rc;
     }
     if (c.robots.empty()) return WCQP_OK;
-    return replan_enqueue(h, c, K, fd, ReplanSource{rp, nullptr, nullptr, nullptr}, (hipStream_t)stream);
+    return replan_enqueue(h, c, K, fd, ReplanSource{rp, nullptr, nullptr, nullptr, tm}, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps) {
+    return upload_footsteps(h, in, steps, nullptr);
+}
+
+int wcqp_tick_upload_footsteps_timed(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps, const wcqp_tick_step_timing* tm) {
+    if (!tm) return WCQP_E_INVALID;
+    return upload_footsteps(h, in, steps, tm);
+}
+
+int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) { return replan_footsteps(h, rp, nullptr, false, stream); }
+
+int wcqp_tick_replan_footsteps_timed(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_step_timing* tm, void* stream) {
+    return replan_footsteps(h, rp, tm, true, stream);
 }
 
 int wcqp_tick_replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_tick_goals* gl, void* stream) {
     if (!h || !planner || !gl || !gl->goal) return WCQP_E_INVALID;
     if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    if (h->gp.timed) return WCQP_E_UNSUPPORTED;                    // (the merge-point rule and the planner kernel know one common timing)
     const wcqp_unicycle::UniPar* par = wcqp::unicycle_par(planner);
     const size_t B = (size_t)h->d.batch;
     const int K = par->K, T = h->d.traj_len, fd = gl->first_ds_ticks, per = h->gp.ss + h->gp.ds;

@@ -6,6 +6,9 @@
 // nothing is integrated twice and no path array exists.  The cosine and sine of a sample's heading serve its candidate, the first RK4 stage
 // of the next sample and - when the candidate becomes a footprint - the stance frame of the next step.  Every lane walks the same K x D trip
 // counts (a robot that has ended idles behind a predicate); a wave leaves the step loop when all of its robots have ended.
+// TIMED (wcqp_unicycle_plan_timed_*): the candidates of a step are the samples min_step_ticks .. max_step_ticks, every feasible one is
+// scored, and the state kept in registers is that of the best-scored feasible sample (the first of equals) instead of the last feasible
+// one; the step's two durations are stored next to its target.  The untimed instantiation is the code it was before the flag.
 #pragma once
 #include "wcqp_internal.h"
 
@@ -16,6 +19,13 @@ struct UniPar {
     double g, vmax, wmax;
     double len_max, len_min, width_min, half_w, ang_max, ang_min;
     int D, K;
+};
+
+// TIMED only: the candidates' range and score (include/wcqp.h: wcqp_unicycle_timing), rho = r / (1 + r) of the switch-over-swing ratio r
+struct UniTiming {
+    int m_min, m_max;
+    double inv_nom, time_w, pos_w, rho;        // inv_nom = 1 / (nominal_step_ticks dT)
+    int32_t *ss_ticks, *ds_ticks;              // [B][K], the durations' rows (results, next to UniRows')
 };
 
 // what one robot's planning starts from: the entries of the two soles that are read (x, y, R00, R10), the goal, the swing foot
@@ -50,7 +60,8 @@ __device__ __forceinline__ void uni_rate(const UniPar& p, double x, double y, do
 
 // One lane's robot, planned from `in` into row i of `o`.  Called by every lane of the wave (the step loop votes); a lane that is not
 // `live` repeats a live robot and stores nothing.
-__device__ __forceinline__ void plan_robot(const UniPar& p, const UniStart& in, const UniRows& o, size_t i, bool live) {
+template <bool TIMED>
+__device__ __forceinline__ void plan_robot_body(const UniPar& p, const UniTiming& tm, const UniStart& in, const UniRows& o, size_t i, bool live) {
     // ---- inputs, and whether all of this robot's are finite
     double lx = in.lx, ly = in.ly, lc = in.lc, ls = in.ls;
     double rx = in.rx, ry = in.ry, rc = in.rc, rs = in.rs;
@@ -82,8 +93,9 @@ __device__ __forceinline__ void plan_robot(const UniPar& p, const UniStart& in, 
         double x = ux, y = uy, th = uth, c = uc, s = us;
         int best = 0;
         double bx = 0.0, by = 0.0, bth = 0.0, bc = 1.0, bs = 0.0, bcx = 0.0, bcy = 0.0;
+        [[maybe_unused]] double bcost = 0.0;           // TIMED: the score of candidate `best`
 #pragma unroll 1
-        for (int m = 1; m <= p.D; ++m) {
+        for (int m = 1; m <= (TIMED ? tm.m_max : p.D); ++m) {
             double f1x, f1y, f1w, f2x, f2y, f2w, f3x, f3y, f3w, f4x, f4y, f4w, cq, sq;
             uni_rate(p, x, y, c, s, px, py, f1x, f1y, f1w);
             sincos(th + h2 * f1w, &sq, &cq);
@@ -102,7 +114,16 @@ __device__ __forceinline__ void plan_robot(const UniPar& p, const UniStart& in, 
             const double rlon = tc * ex + ts * ey, rlat = tc * ey - ts * ex;
             const bool feasible = sqrt(rlon * rlon + rlat * rlat) <= p.len_max && sgn * rlat >= p.width_min &&
                                   fabs(wrap_angle(th - tth)) <= p.ang_max;
-            if (feasible) { best = m; bx = x; by = y; bth = th; bc = c; bs = s; bcx = cx; bcy = cy; }
+            if constexpr (TIMED) {
+                // r_nom = (0, +-w): the lateral distance from it is rlat - sgn w
+                const double dt = 1.0 / ((double)m * p.dT) - tm.inv_nom, dl = rlat - 2.0 * lat;
+                const double cost = tm.time_w * (dt * dt) + tm.pos_w * (rlon * rlon + dl * dl);
+                if (feasible && m >= tm.m_min && (best == 0 || cost < bcost)) {
+                    best = m; bcost = cost; bx = x; by = y; bth = th; bc = c; bs = s; bcx = cx; bcy = cy;
+                }
+            } else {
+                if (feasible) { best = m; bx = x; by = y; bth = th; bc = c; bs = s; bcx = cx; bcy = cy; }
+            }
         }
         if (status < 0) {
             if (best == 0) {
@@ -116,6 +137,13 @@ __device__ __forceinline__ void plan_robot(const UniPar& p, const UniStart& in, 
                         o.side[i * K + k] = (uint8_t)sw;
                         double* t = o.target + (i * K + k) * 3;
                         t[0] = bcx; t[1] = bcy; t[2] = dyaw;
+                        if constexpr (TIMED) {
+                            int ds = (int)floor((double)best * tm.rho + 0.5);
+                            ds = ds > 1 ? ds : 1;
+                            ds = ds < best - 1 ? ds : best - 1;
+                            tm.ss_ticks[i * K + k] = best - ds;
+                            tm.ds_ticks[i * K + k] = ds;
+                        }
                     }
                     ++n_steps;
                     // the foot that landed is the next stance foot; the unicycle rewinds to the sample it landed at
@@ -133,6 +161,7 @@ __device__ __forceinline__ void plan_robot(const UniPar& p, const UniStart& in, 
         o.side[i * K + k] = 0;
         double* t = o.target + (i * K + k) * 3;
         t[0] = 0.0; t[1] = 0.0; t[2] = 0.0;
+        if constexpr (TIMED) { tm.ss_ticks[i * K + k] = 0; tm.ds_ticks[i * K + k] = 0; }
     }
     o.n_steps[i] = n_steps;
     o.status[i] = status;
@@ -140,6 +169,13 @@ __device__ __forceinline__ void plan_robot(const UniPar& p, const UniStart& in, 
     if (o.unicycle_end) {
         o.unicycle_end[i * 3] = bad ? 0.0 : ux; o.unicycle_end[i * 3 + 1] = bad ? 0.0 : uy; o.unicycle_end[i * 3 + 2] = bad ? 0.0 : uth;
     }
+}
+
+__device__ __forceinline__ void plan_robot(const UniPar& p, const UniStart& in, const UniRows& o, size_t i, bool live) {
+    plan_robot_body<false>(p, UniTiming{}, in, o, i, live);
+}
+__device__ __forceinline__ void plan_robot_timed(const UniPar& p, const UniTiming& tm, const UniStart& in, const UniRows& o, size_t i, bool live) {
+    plan_robot_body<true>(p, tm, in, o, i, live);
 }
 
 }  // namespace wcqp_unicycle

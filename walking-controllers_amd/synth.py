@@ -637,6 +637,21 @@ def synth_footstep_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_b
                 com0=np.ascontiguousarray(state0[:, o["com"]:o["com"] + 2].copy()))
 
 
+def synth_timed_footstep_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_batch: dict, spread: float = 0.2, **kw) -> dict:
+    """synth_footstep_walk_batch's walk (same arguments, seed and draws: the same footsteps) with durations that differ per robot and per
+    step - what `TickPipeline.upload_footsteps` routes to wcqp_tick_upload_footsteps_timed: ss_ticks / ds_ticks are [B][K] int32 arrays,
+    each step's single and double support stretched or shortened by up to `spread` of the common value (never below one stage), drawn
+    per (robot, step) from the robot's own counter stream; final_ds_ticks stays the common walk's."""
+    fs = synth_footstep_walk_batch(count, n_ticks, poses, kin_batch, **kw)
+    K = fs["side"].shape[1]
+    rng = CounterRNG(kw.get("seed", 4242) ^ 0x71AED, kw.get("first", 0), count)
+    u = rng.uniform(2 * K) if K else np.zeros((count, 0))
+    scale = 1.0 + spread * (2.0 * u - 1.0)
+    ss = np.maximum(np.rint(fs["ss_ticks"] * scale[:, :K]), 1).astype(np.int32)
+    ds = np.maximum(np.rint(fs["ds_ticks"] * scale[:, K:]), 1).astype(np.int32)
+    return dict(fs, ss_ticks=np.ascontiguousarray(ss), ds_ticks=np.ascontiguousarray(ds))
+
+
 def synth_footstep_replan_batch(fs: dict, after_step: int = 2, ds_offset: int = 0, n_steps: int = 3, seed: int = 777,
                                 step_length=(0.02, 0.03), yaw_step=(-0.04, 0.04)) -> dict:
     """A new goal for the walk of synth_footstep_walk_batch (`fs`), merged in the double support behind its step `after_step` (1-based),
