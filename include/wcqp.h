@@ -963,8 +963,9 @@ int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* 
  * force with its own durations, `tm` gives the NEW steps' durations, and the last step's double support again falls back to the
  * final_ds_ticks of the upload, or to its own ds.
  * A plan is timed or not from its upload on (wcqp_tick_get_option with WCQP_TICK_OPT_PLAN_TIMED): wcqp_tick_replan_footsteps on a timed plan and
- * wcqp_tick_replan_footsteps_timed on an untimed one return WCQP_E_UNSUPPORTED, and so does wcqp_tick_replan_goals on a timed plan (it
- * needs its merge-point rule over per-robot timelines and a timed planner kernel: not offered yet) - each before anything changes.
+ * wcqp_tick_replan_footsteps_timed on an untimed one return WCQP_E_UNSUPPORTED, and so does wcqp_tick_replan_goals on a timed plan (its
+ * merge-point rule and planner kernel know one common timing: wcqp_tick_replan_goals_timed below is the call for a timed plan) - each
+ * before anything changes.
  * wcqp_tick_get_plan, the POSITION tick and the resident plans of streamed handles take a timed plan as any other.
  * Refusals, on the host, with the handle unchanged: every refusal of the untimed call (its ss_ticks / ds_ticks rule aside), and
  * WCQP_E_INVALID for a NULL tm or a NULL pointer inside it (K > 0), ss < 1 or ds < 1 of a step the robot takes, or a timeline - of any
@@ -1038,6 +1039,35 @@ typedef struct wcqp_tick_goal_result { /* HOST pointers, any may be NULL; rows o
     double* desired_point; double* unicycle_end;                   /* [B][2], [B][3] */
 } wcqp_tick_goal_result;
 int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out);   /* waits for the last replan_goals call only */
+/* The same for a TIMED plan (wcqp_tick_upload_footsteps_timed): wcqp_tick_replan_goals on the per-step timeline, with the same
+ * wcqp_tick_goals - KEEP / AUTO / explicit M_i, first_side 0 / 1 / WCQP_TICK_SIDE_AUTO, first_ds_ticks, min_lead_ticks.  ONE kernel
+ * (goal_plan_timed_kernel) runs the timed planner of wcqp_unicycle_plan_timed_* (the same `tm`; the planner's step_ticks is not read) from
+ * the two desired soles of plan record M_i: it plans every listed robot's steps AND their durations; the three timed replan kernels then
+ * regenerate the plan from those rows - THE TIMED REPLAN as wcqp_tick_replan_footsteps_timed defines it, with K' = the planner's
+ * max_steps -, the set builder follows, and one copy brings the result rows, the two duration rows among them, back into the handle's
+ * pinned block with an event behind it.  Enqueued on `stream` behind the ticks already enqueued; nothing is waited for but the previous
+ * replan's hold on the staging block; neither footsteps nor durations visit the host.  Valid wherever the untimed call is.
+ *   Merge stage  as above on robot i's own timeline: s_0 = O + fo, s_{k+1} = s_k + ss_k + ds_k with the durations of its plan in force; the
+ *               MERGE POINTS are s_k + ss_k for k = 0 .. n - 2 and every stage >= L = s_{n-1} + ss_{n-1} (n = 0: L = O); M_i = the smallest
+ *               merge point >= max(t0 + min_lead_ticks, 1, O); M_i >= T: WCQP_GOAL_TOO_LATE.  With equal durations this is the untimed
+ *               rule.  An explicit M_i is checked exactly as wcqp_tick_replan_footsteps_timed checks it.  (csrc/goal_merge.h is the
+ *               rule, tests/helpers/goal_merge_timed.py restates it.)
+ *   Degenerate   as above: WCQP_UNICYCLE_INVALID_INPUT found on the device gives n_steps = 0 and a stop at M_i; WCQP_UNICYCLE_STUCK and
+ *               _TRUNCATED keep the steps found so far, with their durations.
+ * Refusals, all on the host before anything changes, the handle exactly as it was: every refusal of wcqp_tick_replan_goals;
+ * WCQP_E_UNSUPPORTED on an untimed plan (a plan is timed or not from its upload on); WCQP_E_INVALID for a NULL tm, for a tm that
+ * wcqp_unicycle_plan_timed_device refuses, and when T + first_ds_ticks + K' max_step_ticks + final_ds passes 2^30 stages (a step of m
+ * ticks has ds <= m - 1, so a final_ds of 0 is covered).  Every robot KEEP or TOO_LATE: WCQP_OK, nothing enqueued.
+ * Both the step count and the durations of a goal-replanned robot are known to the host only when the rows are back: every later call
+ * that needs them (the replans, the result getters) first waits for THAT call's event, nothing else.
+ * wcqp_tick_get_goal_result works after this call exactly as after the untimed one (wcqp_tick_goal_result keeps its fields: callers
+ * pass it with their own sizeof); the durations come through wcqp_tick_get_goal_timing: ss_ticks / ds_ticks [B][K'] (HOST pointers,
+ * either may be NULL), zero for KEPT / TOO_LATE robots and for steps not taken.  It waits for that call's event only, and returns
+ * WCQP_E_INVALID for a NULL handle, before any goal call, or when the last goal call was the untimed one. */
+struct wcqp_unicycle_timing;        /* the timed planner's candidates and score, stated at the end of this header */
+int wcqp_tick_replan_goals_timed(wcqp_tick_t h, wcqp_unicycle_t planner, const struct wcqp_unicycle_timing* tm,
+                                 const wcqp_tick_goals* g, void* stream);
+int wcqp_tick_get_goal_timing(wcqp_tick_t h, int32_t* ss_ticks, int32_t* ds_ticks);   /* [B][K'] each, either may be NULL */
 /* The plan a planned handle holds, however it was uploaded: n robots from robot0, m stages from stage0, stage-major per robot.
  * Synchronises.  Every pointer but two works on any planned handle, however it was uploaded.  The two: a non-NULL dcm_vel_traj makes
  * the call return WCQP_E_UNSUPPORTED on a handle that keeps no velocity (neither the reactive controller nor gain scheduling), and a

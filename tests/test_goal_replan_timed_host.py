@@ -1,0 +1,195 @@
+"""wcqp_tick_replan_goals_timed without a device: the merge rule over per-robot timelines three ways - csrc/goal_merge.h
+built into a stand-alone program, plain and under ASan + UBSan, its restatement helpers/goal_merge_timed.py, and on plans of equal
+durations the untimed rule -, the refusals that need no device, and the restated call on the two scenarios the GPU tests
+(test_goal_replan_timed.py) compare: their decisions, their decision margins, and oracle/tick_spec.py's walk over the stitched plans."""
+import ctypes as C
+import os
+import subprocess
+import types
+
+import numpy as np
+import pytest
+
+from helpers import goal_merge as gm
+from helpers import goal_merge_timed as gmt
+from helpers import goal_replan as gr
+from helpers import goal_replan_timed as gt
+from helpers import unicycle_plan as up
+from helpers import unicycle_plan_timed as ut
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T0S = LEADS = tuple(range(5))
+
+
+def _program(tmp_path, flags, name):
+    exe = tmp_path / name
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-I", os.path.join(ROOT, "walking-controllers_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "goal_merge_timed_check.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().splitlines()[-1].startswith("goal_merge_timed ok"), r.stdout[-2000:] + r.stderr[-2000:]
+    return r.stdout.strip().splitlines()
+
+
+def _bits(words):
+    return np.array([np.frombuffer(w.encode(), np.uint8) - 48 for w in words], bool)
+
+
+@pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]], ids=["plain", "sanitized"])
+def test_timed_merge_rule_three_ways(tmp_path, flags):
+    """tests/cpp/goal_merge_timed_check.cpp prints in_single_support, merge_allowed and merge_auto of a timed plan in force for n in 0..3,
+    every ss_k and ds_k in 1..3, O in {0, 2}, fo in 1..2, t0 and lead in 0..4 and every M and T up to the plan's end + 2: every value equals
+    the restatement's; where all steps have one ss and one ds, both equal the untimed goal_merge.py, and the program itself found the header's
+    timed and untimed functions equal there; the scalar restatement and its vectorised table agree on a sample."""
+    lines = _program(tmp_path, flags, "goal_merge_timed_check")
+    assert lines[-3] == "corner %d %d 0" % (gmt.TOO_LATE, 3 << 29)
+    n_uniform, n_bad = int(lines[-2].split()[1]), int(lines[-2].split()[3])
+    assert lines[-2].startswith("uniform") and n_uniform > 100000 and n_bad == 0
+    per = 1 + 1 + len(T0S) + len(T0S) * len(LEADS)
+    body = lines[:-3]
+    assert len(body) == per * int(lines[-1].split()[-1]) == per * 4 * (1 + 9 + 81 + 729)
+    seen, uniform_plans, late = set(), 0, 0
+    for at in range(0, len(body), per):
+        head = body[at].split()
+        assert head[0] == "P"
+        n, O, fo = int(head[1]), int(head[2]), int(head[3])
+        dur = [int(x) for x in head[4:]]
+        ss, ds = dur[0::2], dur[1::2]
+        assert len(ss) == n == len(ds)
+        seen.add((n, O, fo, tuple(dur)))
+        S = O + fo + sum(dur) + 3
+        single, allowed, auto = gmt.table(O, fo, ss, ds, T0S, LEADS, S)
+        assert body[at + 1][:2] == "S " and np.array_equal(_bits([body[at + 1][2:]])[0], single), body[at]
+        for j, t0 in enumerate(T0S):
+            w = body[at + 2 + j].split()
+            assert w[:2] == ["A", str(t0)] and np.array_equal(_bits(w[2:]), allowed[j]), (body[at], t0)
+        got = np.array([ln.split() for ln in body[at + 2 + len(T0S):at + per]])
+        assert (got[:, 0] == "U").all() and np.array_equal(got[:, 1:3].astype(int), [[a, b] for a in T0S for b in LEADS])
+        assert np.array_equal(got[:, 3:].astype(int).reshape(len(T0S), len(LEADS), S), auto), body[at]
+        late += int((auto == gmt.TOO_LATE).sum())
+        # plans of equal durations: the untimed rule, call by call
+        if len(set(ss)) <= 1 and len(set(ds)) <= 1:
+            uniform_plans += 1
+            a, b = (ss[0], ds[0]) if n else (1, 1)
+            assert [gm.in_single_support(O, fo, n, a, b, M) for M in range(S)] == single.tolist()
+            for j, t0 in enumerate(T0S):
+                for T in range(S):
+                    assert [gm.merge_allowed(O, fo, n, a, b, M, t0, T) for M in range(S)] == allowed[j, T].tolist()
+                    assert [gm.merge_auto(O, fo, n, a, b, t0, lead, T) for lead in LEADS] == auto[j, :, T].tolist()
+        # the table against the scalar restatement, on every 37th plan
+        if (at // per) % 37 == 0:
+            for M in range(S):
+                assert gmt.in_single_support(O, fo, ss, ds, M) == single[M]
+                assert [gmt.merge_allowed(O, fo, ss, ds, M, t0, S - 2) for t0 in T0S] == allowed[:, S - 2, M].tolist()
+            for T in range(S):
+                assert [[gmt.merge_auto(O, fo, ss, ds, t0, lead, T) for lead in LEADS] for t0 in T0S] == auto[:, :, T].tolist()
+    assert len(seen) == 4 * 820 and uniform_plans == 4 * (1 + 9 + 9 + 9) and late > 0
+
+
+def test_timed_merge_rule_properties():
+    """M is the FIRST merge point at or above the floor, lies in no single support of the robot's own timeline, passes the check an explicit
+    stage gets - and on a timeline that differs from the nominal one the two rules disagree (the reason the durations are owed)"""
+    O, fo, ss, ds, T = 105, 15, [29, 27, 35, 24], [21, 19, 25, 17], 10 ** 6
+    inner, L = gmt.merge_points(O, fo, ss, ds)
+    assert inner == [149, 197, 251] and L == 300
+    for t0 in range(0, 330):
+        for lead in (0, 20, 49):
+            M = gmt.merge_auto(O, fo, ss, ds, t0, lead, T)
+            lo = max(t0 + lead, 1, O)
+            assert M >= lo and (M in inner or M >= L) and not [x for x in inner if lo <= x < M] and not (lo >= L and M != lo)
+            assert gmt.merge_allowed(O, fo, ss, ds, M, t0, T) and not gmt.in_single_support(O, fo, ss, ds, M)
+    assert gmt.merge_auto(O, fo, ss, ds, 150, 0, T) == 197 != gm.merge_auto(O, fo, 4, 29, 21, 150, 0, T)
+    assert gmt.merge_auto(O, fo, ss, ds, 150, 0, 197) == gmt.TOO_LATE and gmt.merge_auto(O, fo, [], [], 0, 0, T) == O
+
+
+def test_refusals_that_need_no_device(wca):
+    """NULL handle, planner, timing, struct and goal at the C entry points; the getter on a NULL handle; through the binding a bad side, a
+    negative lead and shapes are refused before the library is called, with `timing` as without, and an unknown timing key is a TypeError"""
+    L = wca.capi.lib()
+    pl = wca.UnicyclePlanner(**gt.WALK)
+    goals = np.zeros((3, 2))
+    g = wca.capi.TickGoals(goals.ctypes.data, None, None, 15, 20)
+    tm = pl._timing_struct(gt.WALK_TIMING)
+    E = wca.capi.E_INVALID
+    assert L.wcqp_tick_replan_goals_timed(None, pl._h, C.byref(tm), C.byref(g), None) == E
+    assert L.wcqp_tick_replan_goals_timed(None, None, C.byref(tm), C.byref(g), None) == E
+    assert L.wcqp_tick_replan_goals_timed(None, pl._h, None, C.byref(g), None) == E
+    assert L.wcqp_tick_replan_goals_timed(None, pl._h, C.byref(tm), None, None) == E
+    ss = np.zeros((3, 6), np.int32)
+    assert L.wcqp_tick_get_goal_timing(None, ss.ctypes.data, None) == E and L.wcqp_tick_get_goal_timing(None, None, None) == E
+    stub = types.SimpleNamespace(batch=3, _h=None, _holds_plan=lambda: True)
+    call = wca.TickPipeline.replan_goals
+    with pytest.raises(ValueError, match="first_side"):
+        call(stub, goals, pl, 15, first_side=2, timing=gt.WALK_TIMING)
+    with pytest.raises(ValueError, match="min_lead_ticks"):
+        call(stub, goals, pl, 15, min_lead_ticks=-1, timing=gt.WALK_TIMING)
+    with pytest.raises(ValueError, match="shapes"):
+        call(stub, np.zeros((2, 2)), pl, 15, timing=gt.WALK_TIMING)
+    with pytest.raises(TypeError):
+        call(stub, goals, pl, 15, timing=dict(step_time=3))
+    with pytest.raises(wca.WcqpError, match="invalid|INVALID"):
+        call(stub, goals, pl, 15, timing=gt.WALK_TIMING)                       # (everything in order but the handle)
+    for name in ("wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing"):
+        assert name in wca.capi.ABI_SYMBOLS
+
+
+def test_walk_scenario_decisions_and_margins(wca):
+    """the restatement's values for the walk scenario: robot 2 merges at the first merge point of its own timeline at least 10 ticks behind
+    tick 90 - the end of a single support, whose fixed-frame foot decides the side -, the others keep.  Every decision margin of the upload
+    and of the call is >= 1e-9, the durations the call chooses differ from the nominal ones, and the new timeline has a single-support stage
+    that the nominal timeline has in a double support (what the GPU test of the owed durations needs)."""
+    sc = gt.walk_scenario(wca)
+    c = sc["c1"]
+    O, fo, ss, ds = gt.timeline(sc["force0"], 2)
+    want = next(m for m in gmt.merge_points(O, fo, ss, ds)[0] if m >= sc["t1"] + sc["lead1"])
+    assert c["M"].tolist() == [-1, -1, want] and c["decided"].tolist() == [gt.KEPT, gt.KEPT, 0]
+    assert c["fside"][2] == (0 if sc["plan0"]["contact"][2, want - 1] & 4 else 1)
+    assert (sc["plan0"]["contact"][2, want - 1] & 3) != 3 and (sc["plan0"]["contact"][2, want] & 3) == 3
+    print("margins", sc["r0"]["margin"].tolist(), c["r"]["margin"][2], "durations", (c["r"]["ss_ticks"] + c["r"]["ds_ticks"])[2].tolist())
+    assert (sc["r0"]["margin"] >= gt.MARGIN).all() and c["r"]["margin"][2] >= gt.MARGIN and not gr.left_out(sc, ("c1",)).any()
+    assert c["r"]["n_steps"][2] >= 2 and c["r"]["status"][2] == up.DONE
+    n = int(c["r"]["n_steps"][2])
+    m = (c["r"]["ss_ticks"] + c["r"]["ds_ticks"])[2, :n]
+    assert (m != gt.WALK_TIMING["nominal_step_ticks"]).any() and not c["r"]["ss_ticks"][:2].any() and not c["r"]["ds_ticks"][2, n:].any()
+    assert gt.single_support_probe(c["force"], 2, gt.WALK_TIMING["nominal_step_ticks"], gt.WALK_TIMING["switch_over_swing_ratio"], sc["t1"])
+
+
+def test_batch_scenario_margins_and_mix(wca):
+    """the 70 robots of the batch scenario, from the restatement alone: at most 2 % are decided by less than 1e-9 anywhere (the upload, the
+    two calls); the plans in force have durations that differ per robot and per step; the calls mix KEEP, AUTO and explicit stages, sides
+    0, 1 and AUTO; the second call's AUTO stages differ from the ones the nominal timeline would give - it reads what the first chose"""
+    sc = gt.batch_scenario(wca)
+    B = sc["B"]
+    out = gr.left_out(sc)
+    c1, c2 = sc["c1"], sc["c2"]
+    print("left out", int(out.sum()), "of", B, "smallest margins", np.sort(np.minimum(np.minimum(c1["r"]["margin"], c2["r"]["margin"]), sc["r0"]["margin"]))[:3])
+    assert out.mean() <= 0.02
+    m0 = sc["r0"]["ss_ticks"] + sc["r0"]["ds_ticks"]
+    assert len(set(map(tuple, m0.tolist()))) >= 3 and any(len(set(r[:n].tolist())) >= 2 for r, n in zip(m0, sc["r0"]["n_steps"]))
+    assert set(np.unique(np.sign(c1["M"]))) == {-1, 1} and len(np.unique(sc["merge1"][sc["merge1"] >= 1])) >= 2
+    assert set(np.unique(sc["side1"])) == {0, 1, gt.SIDE_AUTO} and set(np.unique(sc["merge2"])) == {gt.KEEP, gt.AUTO}
+    kinds = [(int(sc["merge1"][i]), int(sc["merge2"][i])) for i in gt.ORACLE_ROWS]
+    assert kinds[0] == (gt.KEEP, gt.AUTO) and kinds[1] == (gt.AUTO, gt.KEEP) and kinds[2][0] >= 1 and kinds[2][1] == gt.AUTO and kinds[3] == (gt.AUTO, gt.AUTO)
+    sel2 = c2["sel"]
+    f1 = c1["force"]
+    assert len(np.unique(f1["origin"][sel2])) >= 3 and len(np.unique(f1["n_steps"][sel2])) >= 3 and (c2["M"][sel2] >= gt.T2 + gt.LEAD2).all()
+    nss, nds = ut.durations(gt.BATCH_TIMING["nominal_step_ticks"], gt.BATCH_TIMING["switch_over_swing_ratio"])
+    nominal = gm.merge_auto_batch(f1["origin"], f1["first_ds"], f1["n_steps"], nss, nds, gt.T2, gt.LEAD2, gt.T)
+    assert (nominal[sel2] != c2["M"][sel2]).sum() >= 10
+    for c in (c1, c2):
+        r = c["r"]
+        taken = np.arange(gt.K_WALK)[None, :] < r["n_steps"][:, None]
+        m = (r["ss_ticks"] + r["ds_ticks"])
+        assert (m[taken] >= gt.BATCH_TIMING["min_step_ticks"]).all() and (m[taken] <= gt.BATCH_TIMING["max_step_ticks"]).all() and not m[~taken].any()
+        assert set(np.unique(r["status"][c["sel"]])) <= {up.DONE, up.TRUNCATED}
+
+
+def test_the_stitched_plans_walk_to_the_end(wca, qs):
+    """oracle/tick_spec.py (reactive controller, gain scheduling) walks all of the walk scenario and robots 0 to 3 of the batch - one per
+    kind of call pair - through MAXT ticks of the restated stitched plans with no IK or MPC failure, and the replanned robots' walks differ
+    from the ones they had"""
+    w_run, b_run = gt.oracle_runs(wca, qs)
+    for run in (w_run, b_run):
+        assert (run["ik_fail"] == 0).all() and (run["mpc_fail"] == 0).all()
+    w = gt.walk_scenario(wca)
+    assert not np.array_equal(w["plan0"]["ref_traj"][2], w["c1"]["plan"]["ref_traj"][2])
+    assert np.array_equal(w["plan0"]["ref_traj"][:2], w["c1"]["plan"]["ref_traj"][:2])

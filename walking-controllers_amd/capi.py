@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
     "wcqp_tick_upload_footsteps", "wcqp_tick_upload_footsteps_timed", "wcqp_tick_replan_footsteps_timed", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
+    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
     "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
@@ -404,6 +405,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_replan_footsteps.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.c_void_p]
         L.wcqp_tick_replan_goals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickGoals), C.c_void_p]
         L.wcqp_tick_get_goal_result.argtypes = [C.c_void_p, C.POINTER(TickGoalResult)]
+        L.wcqp_tick_replan_goals_timed.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(UnicycleTiming), C.POINTER(TickGoals), C.c_void_p]
+        L.wcqp_tick_get_goal_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.wcqp_unicycle_create.argtypes = [C.POINTER(UnicycleParams), C.POINTER(C.c_void_p)]
         L.wcqp_unicycle_destroy.argtypes = [C.c_void_p]
         L.wcqp_unicycle_plan_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(UnicycleInputs), C.POINTER(UnicycleOutputs), C.c_void_p]
@@ -1027,12 +1030,14 @@ class TickPipeline(_Handle):
         return out
 
     def replan_goals(self, goals, planner: "UnicyclePlanner", first_ds_ticks: int, merge_stage=None, first_side=None, min_lead_ticks: int = 20,
-                     stream: Optional[int] = None) -> None:
+                     stream: Optional[int] = None, timing: Optional[dict] = None) -> None:
         """"Robot i, go there" for a generated walk that is running, on the device and enqueue-only (wcqp_tick_replan_goals, which states the
         rules): goals [B][2]; merge_stage [B] of TICK_MERGE_KEEP / TICK_MERGE_AUTO / M_i >= 1 (None: AUTO for all - the first merge point of
         the robot's plan at least min_lead_ticks ahead); first_side [B] or a scalar of 0 / 1 / TICK_SIDE_AUTO (None: AUTO for all - the feet
         keep alternating).  The footsteps are planned and the plan regenerated on `stream` behind the ticks already enqueued; nothing is
-        waited for and nothing returned - goal_result() reads what was decided.  A goal row of a robot that keeps its plan is not read."""
+        waited for and nothing returned - goal_result() reads what was decided.  A goal row of a robot that keeps its plan is not read.
+        timing: on a timed plan, the dict plan_host / replan_goal take - the timed planner chooses every new step's durations on the device
+        (wcqp_tick_replan_goals_timed) and goal_result() returns them too.  Without it the untimed call is made, which a timed plan refuses."""
         if not self._holds_plan():
             raise ValueError("a goal was given to a handle created without planned_trajectories=True (or resident_plan=True)")
         goals = _f64(goals)
@@ -1048,19 +1053,29 @@ class TickPipeline(_Handle):
         if int(min_lead_ticks) < 0 or int(first_ds_ticks) < 1:
             raise ValueError("min_lead_ticks >= 0 and first_ds_ticks >= 1")
         g = TickGoals(goals.ctypes.data, None if merge is None else merge.ctypes.data, None if fs is None else fs.ctypes.data, int(first_ds_ticks), int(min_lead_ticks))
-        check(lib().wcqp_tick_replan_goals(self._h, planner._h, C.byref(g), stream or None), "wcqp_tick_replan_goals")
+        if timing is not None:
+            tm = planner._timing_struct(timing)
+            check(lib().wcqp_tick_replan_goals_timed(self._h, planner._h, C.byref(tm), C.byref(g), stream or None), "wcqp_tick_replan_goals_timed")
+        else:
+            check(lib().wcqp_tick_replan_goals(self._h, planner._h, C.byref(g), stream or None), "wcqp_tick_replan_goals")
         self._goal_K = planner.max_steps
+        self._goal_timed = timing is not None
 
     def goal_result(self) -> dict:
         """What the last replan_goals call decided and planned (wcqp_tick_get_goal_result; waits for that call only): per robot the
         merge_stage and first_side TAKEN, status (UNICYCLE_*, or GOAL_KEPT / GOAL_TOO_LATE with every other row zero), n_steps, side [B][K],
-        target [B][K][3], desired_point [B][2], unicycle_end [B][3]."""
+        target [B][K][3], desired_point [B][2], unicycle_end [B][3]; after a call with `timing` also ss_ticks, ds_ticks [B][K]
+        (wcqp_tick_get_goal_timing)."""
         K = getattr(self, "_goal_K", None)
         if K is None:
             raise ValueError("goal_result() before any replan_goals()")
         out = {k: np.zeros((self.batch,) + tuple(K if d == "K" else d for d in shp), dt) for k, shp, dt in GOAL_RESULT}
         res = TickGoalResult(**{k: (v.ctypes.data if v.size else None) for k, v in out.items()})
         check(lib().wcqp_tick_get_goal_result(self._h, C.byref(res)), "wcqp_tick_get_goal_result")
+        if getattr(self, "_goal_timed", False):
+            dur = dict(ss_ticks=np.zeros((self.batch, K), np.int32), ds_ticks=np.zeros((self.batch, K), np.int32))
+            check(lib().wcqp_tick_get_goal_timing(self._h, *(v.ctypes.data if v.size else None for v in dur.values())), "wcqp_tick_get_goal_timing")
+            out.update(dur)
         return out
 
     def plan_window(self, robot0: int = 0, n: Optional[int] = None, stage0: int = 0, m: Optional[int] = None, keys=None) -> dict:

@@ -43,4 +43,41 @@ inline int merge_auto(const PlanInForce& p, int t0, int min_lead, int T) {
     return M < T ? (int)M : kTooLate;
 }
 
+// Robot i's TIMED plan in force (wcqp_tick_upload_footsteps_timed): every step has its own durations, dur = ss_0, ds_0, ss_1, ds_1, ...
+// (2 n_steps entries; unread for n_steps = 0).  s_0 = origin + first_ds, s_{k+1} = s_k + ss_k + ds_k.  With all ss_k = ss and ds_k = ds the
+// three functions below are the three above (tests/helpers/goal_merge_timed.py restates them).
+struct TimedPlanInForce { int origin, first_ds, n_steps; const int* dur; };
+
+// M lies inside one of the plan's single supports: [s_k, s_k + ss_k) of a step k < n_steps
+inline bool in_single_support(const TimedPlanInForce& p, int M) {
+    long long s_k = (long long)p.origin + p.first_ds;
+    for (int k = 0; k < p.n_steps && s_k <= M; ++k) {
+        if (M < s_k + p.dur[2 * k]) return true;
+        s_k += (long long)p.dur[2 * k] + p.dur[2 * k + 1];
+    }
+    return false;
+}
+
+// An explicit merge stage, as wcqp_tick_replan_footsteps_timed takes it: the rule above on the per-step timeline
+inline bool merge_allowed(const TimedPlanInForce& p, int M, int t0, int T) {
+    return M >= 1 && M >= t0 && M < T && M >= p.origin && !in_single_support(p, M);
+}
+
+// AUTO: the merge points are s_k + ss_k for k = 0 .. n - 2 and every stage >= L = s_{n-1} + ss_{n-1} (n = 0: L = origin).  The smallest one
+// that is >= max(t0 + min_lead, 1, origin), or kTooLate when that is no stage below T.
+inline int merge_auto(const TimedPlanInForce& p, int t0, int min_lead, int T) {
+    long long lo = (long long)t0 + min_lead;
+    if (lo < 1) lo = 1;
+    if (lo < p.origin) lo = p.origin;
+    long long M = lo;
+    long long s_k = (long long)p.origin + p.first_ds;
+    for (int k = 0; k < p.n_steps; ++k) {
+        // the first s_k + ss_k at or above lo; the last one is L itself, and at or above L every stage is a merge point
+        const long long m_k = s_k + p.dur[2 * k];
+        if (m_k >= lo) { M = m_k; break; }
+        s_k = m_k + p.dur[2 * k + 1];
+    }
+    return M < T ? (int)M : kTooLate;
+}
+
 }  // namespace wcqp_goal

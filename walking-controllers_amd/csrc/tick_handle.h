@@ -127,13 +127,16 @@ struct wcqp_tick_s {
     // call's result rows have come back into `host` (pinned; one copy behind the call's kernels, `ev` recorded behind it).  Until then the
     // robot is `owed`: whatever reads gp.n_steps calls settle() first, which waits for that event alone and folds the values in.  The
     // rows stay for wcqp_tick_get_goal_result, with what the host decided per robot at the call: the merge stage taken (0: none) and
-    // WCQP_GOAL_KEPT / WCQP_GOAL_TOO_LATE (0: the device's status row holds)
+    // WCQP_GOAL_KEPT / WCQP_GOAL_TOO_LATE (0: the device's status row holds).  A TIMED goal call (wcqp_tick_replan_goals_timed) owes the
+    // robot's durations too: its rows hold ss_ticks / ds_ticks [B][K] at o_ss / o_ds, and settle() folds them into gp.dur next to the step
+    // counts - every reader of gp.dur (the timed merge rule, the timed replan_admit, AUTO of a later goal call) sits behind a settle()
     struct GoalCall {
         char* host = nullptr; size_t host_cap = 0;
         hipEvent_t ev = nullptr;
         bool called = false, pending = false;
         int K = 0;                                        // the planner's max_steps at the call
         size_t o_target = 0, o_dp = 0, o_ue = 0, o_n = 0, o_status = 0, o_side = 0, o_fs = 0, bytes = 0;      // the rows' offsets in `host`
+        size_t o_ss = 0, o_ds = 0; bool timed = false;    // the last call was a timed one: its two duration rows
         std::vector<int> owed, merge, decided;
         int wait() {
             if (pending) { WCQP_HIP_TRY(hipEventSynchronize(ev)); pending = false; }
@@ -150,6 +153,14 @@ struct wcqp_tick_s {
         if (goal.owed.empty()) return WCQP_OK;
         const int32_t* n = reinterpret_cast<const int32_t*>(goal.host + goal.o_n);
         for (int i : goal.owed) gp.n_steps[i] = n[i];
+        if (goal.timed) {
+            const int32_t* ss = reinterpret_cast<const int32_t*>(goal.host + goal.o_ss);
+            const int32_t* ds = reinterpret_cast<const int32_t*>(goal.host + goal.o_ds);
+            for (int i : goal.owed) {
+                gp.dur[i].resize(2 * (size_t)n[i]);
+                for (int k = 0; k < n[i]; ++k) { gp.dur[i][2 * k] = ss[(size_t)i * goal.K + k]; gp.dur[i][2 * k + 1] = ds[(size_t)i * goal.K + k]; }
+            }
+        }
         goal.owed.clear();
         return WCQP_OK;
     }

@@ -324,26 +324,38 @@ __global__ __launch_bounds__(64) void goal_plan_kernel(GoalPlanDev a) {
     wcqp_unicycle::plan_robot(a.p, in, a.out, i, live);
 }
 
+// Its timed sibling (wcqp_tick_replan_goals_timed): the same lanes, loads and side rule, the timed body of unicycle_timed_kernel - every
+// step's durations are chosen with its target and stored in rows i of tm.ss_ticks / tm.ds_ticks, which lie in the call's result rows next
+// to a.out's and are the PlanTimes::ss_k / ds_k of the timed replan kernels behind it.
+struct GoalPlanTimedDev {
+    GoalPlanDev a;
+    wcqp_unicycle::UniTiming tm;
+};
+__global__ __launch_bounds__(64) void goal_plan_timed_kernel(GoalPlanTimedDev t) {
+    const GoalPlanDev& a = t.a;
+    const long raw = (long)blockIdx.x * 64 + threadIdx.x;
+    const bool live = raw < a.n_robots;
+    const size_t i = (size_t)a.robots[live ? raw : (long)a.n_robots - 1];
+    const double* r = a.rec + (i * (size_t)a.traj_len + (size_t)a.origin[i]) * (size_t)kPlanRec;
+    const unsigned flags = (unsigned)r[kPlanFlags - kPlanRec];
+    int sw = a.side_in[i];
+    if (sw == WCQP_TICK_SIDE_AUTO) sw = (flags & 4u) ? 0 : 1;
+    const double *l = r + kPlanLeft, *q = r + kPlanRight;
+    const wcqp_unicycle::UniStart in{l[0], l[1], l[3], l[6], q[0], q[1], q[3], q[6], a.goal[i * 2], a.goal[i * 2 + 1], sw};
+    if (live) a.first_side[i] = (unsigned char)sw;
+    wcqp_unicycle::plan_robot_timed(a.p, t.tm, in, a.out, i, live);
+}
+
 // the plan in force of robot i, and the stage below which the enqueued ticks have consumed it: a resident plan's tick whose stage has
 // been staged counts as enqueued, its live record holds that stage (gp.n_steps: settled by the caller)
 wcqp_goal::PlanInForce plan_in_force(const wcqp_tick_s* h, size_t i) {
     const auto& gp = h->gp;
     return {gp.origin[i], gp.first_ds[i], gp.n_steps[i], gp.ss, gp.ds};
 }
-// a TIMED plan in force: M lies inside one of robot i's single supports, [s_k, s_k + ss_k) on its own timeline
-bool in_single_support_timed(const wcqp_tick_s* h, size_t i, int M) {
+// a TIMED plan in force, on robot i's own timeline (gp.n_steps and gp.dur: settled by the caller)
+wcqp_goal::TimedPlanInForce timed_plan_in_force(const wcqp_tick_s* h, size_t i) {
     const auto& gp = h->gp;
-    const std::vector<int>& du = gp.dur[i];
-    long long s_k = (long long)gp.origin[i] + gp.first_ds[i];
-    for (int k = 0; k < gp.n_steps[i] && s_k <= M; ++k) {
-        if (M < s_k + du[2 * k]) return true;
-        s_k += (long long)du[2 * k] + du[2 * k + 1];
-    }
-    return false;
-}
-// wcqp_goal::merge_allowed on it
-bool merge_allowed_timed(const wcqp_tick_s* h, size_t i, int M, int t0, int T) {
-    return M >= 1 && M >= t0 && M < T && M >= h->gp.origin[i] && !in_single_support_timed(h, i, M);
+    return {gp.origin[i], gp.first_ds[i], gp.n_steps[i], gp.dur[i].data()};
 }
 int consumed_stages(const wcqp_tick_s* h) { return h->ticks_enqueued + (h->plan_staged ? 1 : 0); }
 
@@ -359,14 +371,16 @@ struct ReplanCall {
 // from); the new plan's sets follow them in the robot's `cap` slots.  That they fit needs no n_new: cap (wcqp_tick_upload_footsteps)
 // bounds the steps that START at a stage <= max_ticks for ANY footstep list - a step occupies ss + 1 stages or more - and the stitched
 // plan is one such list, so the count below is a check of the arithmetic where n_new is known and is not evaluated where it is not.
-// A timed plan (tm: the new steps' durations, [B][K]) counts both on the per-step timelines.
+// A timed plan (tm: the new steps' durations, [B][K]; unread with n_new = -1) counts both on the per-step timelines, the surviving sets
+// from gp.dur; its cap (wcqp_tick_upload_footsteps_timed) already counts a step as two stages - one of single, one of double support -
+// for ANY footstep list, so the steps and durations the device chooses fit as well.
 int replan_admit(const wcqp_tick_s* h, size_t i, int M, int fd, int n_new, ReplanCall& c, const wcqp_tick_step_timing* tm = nullptr, int K = 0) {
     const auto& gp = h->gp;
     const int per = gp.ss + gp.ds, O = gp.origin[i], fo = gp.first_ds[i], no = gp.n_steps[i];
     int c0 = gp.keep[i];
     const int reach = M < h->p.max_ticks ? M : h->p.max_ticks;
     int fresh = 0;
-    if (tm) {
+    if (gp.timed) {
         long long s_k = (long long)O + fo;
         for (int k = 0; k < no; ++k) {
             const int ss = gp.dur[i][2 * k];
@@ -403,23 +417,26 @@ struct ReplanSource {
     const wcqp_tick_replan* lists;
     const double* goal; const uint8_t* first_side; const wcqp_unicycle::UniPar* par;
     const wcqp_tick_step_timing* tm = nullptr;      // with lists, on a timed plan: the new steps' durations
+    const wcqp_unicycle::UniTiming* utm = nullptr;  // with goals, on a timed plan: the timed planner's range and score (its rows: set here)
 };
 
 // Everything behind the checks, for a call that lists a robot at least: the call's device block - what the host hands over first (one
 // copy, taken NOW, once the previous replan has left the block), then what the kernels write for each other -, the kernels on `st` behind
 // the ticks already enqueued, the guard, and the plan in force of the listed robots.  From goals, goal_plan_kernel runs first and the
 // replan kernels' n_steps / side / target aim at the rows it writes; the result rows travel back in one copy, with an event behind it,
-// and gp.n_steps of the listed robots is owed until then (tick_handle.h: GoalCall).  Synchronises with nothing but the block's own wait.
+// and gp.n_steps of the listed robots is owed until then (tick_handle.h: GoalCall).  From goals on a timed plan, goal_plan_timed_kernel
+// also writes the two duration rows into the result rows, the timed replan kernels' PlanTimes aim at them, and gp.dur of the listed robots
+// is owed with gp.n_steps.  Synchronises with nothing but the block's own wait.
 int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const ReplanSource& src, hipStream_t st) {
     const TickDev& d = h->d;
     auto& gp = h->gp;
     auto& gc = h->goal;
-    const bool goals = src.lists == nullptr;
+    const bool goals = src.lists == nullptr, timed = src.tm || src.utm;
     const int cap = gp.cap;
     const size_t B = (size_t)d.batch, BK = B * (size_t)K, nr = c.robots.size(), nt = c.tiles.size() / 2, nslots = B * (size_t)cap;
     // the result rows of a goal call, one contiguous run: doubles, then the 32-bit rows, then the bytes
-    const size_t r_target = 0, r_dp = r_target + BK * 24, r_ue = r_dp + B * 16, r_n = r_ue + B * 24, r_status = r_n + B * 4, r_side = r_status + B * 4,
-                 r_fs = r_side + BK, r_bytes = r_fs + B;
+    const size_t r_target = 0, r_dp = r_target + BK * 24, r_ue = r_dp + B * 16, r_n = r_ue + B * 24, r_status = r_n + B * 4, r_ss = r_status + B * 4,
+                 r_ds = r_ss + (src.utm ? BK * 4 : 0), r_side = r_ds + (src.utm ? BK * 4 : 0), r_fs = r_side + BK, r_bytes = r_fs + B;
     size_t off = 0;
     auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
     const size_t o_org = carve(B * 4), o_base = carve(B * 4), o_rob = carve(nr * 4), o_tile = carve(nt * 8);
@@ -429,7 +446,7 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
     const size_t front = off;
     const size_t o_res = goals ? carve(r_bytes) : 0;
     const size_t o_tab = carve(B * (size_t)(K + 1) * kFpRec * 8), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
-    const size_t o_start = src.tm ? carve(B * (size_t)(K + 1) * 4) : 0;
+    const size_t o_start = timed ? carve(B * (size_t)(K + 1) * 4) : 0;
     std::vector<char> blob(front, 0);
     {
         int* org = reinterpret_cast<int*>(blob.data() + o_org); int* base = reinterpret_cast<int*>(blob.data() + o_base);
@@ -485,12 +502,18 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
         a.out = wcqp_unicycle::UniRows{reinterpret_cast<int32_t*>(res + r_n), reinterpret_cast<int32_t*>(res + r_status), reinterpret_cast<uint8_t*>(res + r_side),
                                        reinterpret_cast<double*>(res + r_target), reinterpret_cast<double*>(res + r_dp), reinterpret_cast<double*>(res + r_ue)};
         a.n_robots = (int)nr; a.traj_len = d.traj_len;
-        hipLaunchKernelGGL(goal_plan_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, st, a);
+        if (src.utm) {
+            GoalPlanTimedDev t{a, *src.utm};
+            t.tm.ss_ticks = reinterpret_cast<int32_t*>(res + r_ss); t.tm.ds_ticks = reinterpret_cast<int32_t*>(res + r_ds);
+            hipLaunchKernelGGL(goal_plan_timed_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, st, t);
+        } else {
+            hipLaunchKernelGGL(goal_plan_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, st, a);
+        }
         WCQP_HIP_TRY(hipGetLastError());
     }
     WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
-    if (src.tm) {
-        const PlanGenTimedDev t{g, PlanTimes{reinterpret_cast<const int*>(buf + o_ssk), reinterpret_cast<const int*>(buf + o_dsk),
+    if (timed) {
+        const PlanGenTimedDev t{g, PlanTimes{reinterpret_cast<const int*>(src.utm ? res + r_ss : buf + o_ssk), reinterpret_cast<const int*>(src.utm ? res + r_ds : buf + o_dsk),
                                              reinterpret_cast<int*>(buf + o_start), gp.final_ds}};
         if (const int rc = wcqp::plan_replan_timed_enqueue(t, st); rc != WCQP_OK) return rc;
     } else if (const int rc = wcqp::plan_replan_enqueue(g, st); rc != WCQP_OK) return rc;
@@ -515,6 +538,7 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
     if (goals) {
         gc.pending = true; gc.owed = c.robots; gc.K = K;
         gc.o_target = r_target; gc.o_dp = r_dp; gc.o_ue = r_ue; gc.o_n = r_n; gc.o_status = r_status; gc.o_side = r_side; gc.o_fs = r_fs; gc.bytes = r_bytes;
+        gc.o_ss = r_ss; gc.o_ds = r_ds; gc.timed = src.utm != nullptr;
     }
     return WCQP_OK;
 }
@@ -651,7 +675,7 @@ int replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_
     if (!rp->merge_stage || !rp->n_steps || K < 0 || (K > 0 && (!rp->side || !rp->target)) || fd < 1) return WCQP_E_INVALID;
     if (tm && K > 0 && (!tm->ss_ticks || !tm->ds_ticks)) return WCQP_E_INVALID;
     if (!tm && (long long)T + fd + (long long)K * per + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
-    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (the step counts a goal call still owes)
+    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (the step counts, and on a timed plan the durations, a goal call still owes)
     ReplanCall c(B);
     for (size_t i = 0; i < B; ++i) {
         const int M = rp->merge_stage[i];
@@ -659,7 +683,7 @@ int replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_
         // stage 0 is the initial state's, stages the enqueued ticks have consumed stay (within one wcqp_tick_run call the kernel reads a stage
         // ahead, between calls nothing is ahead), a plan is cut only behind its own origin, and the merge stage has both feet in contact in
         // the plan in force: not inside one of its single supports
-        if (!(tm ? merge_allowed_timed(h, i, M, consumed_stages(h), T) : wcqp_goal::merge_allowed(plan_in_force(h, i), M, consumed_stages(h), T)))
+        if (!(tm ? wcqp_goal::merge_allowed(timed_plan_in_force(h, i), M, consumed_stages(h), T) : wcqp_goal::merge_allowed(plan_in_force(h, i), M, consumed_stages(h), T)))
             return WCQP_E_INVALID;
         if (!footsteps_valid(i, K, rp->n_steps, rp->side, rp->target)) return WCQP_E_INVALID;
         if (tm && (!durations_valid(i, K, rp->n_steps, tm) || (long long)T + fd + durations_span(i, K, rp->n_steps, tm, h->gp.final_ds) > (1ll << 30)))
@@ -668,6 +692,53 @@ int replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_
     }
     if (c.robots.empty()) return WCQP_OK;
     return replan_enqueue(h, c, K, fd, ReplanSource{rp, nullptr, nullptr, nullptr, tm}, (hipStream_t)stream);
+}
+
+// wcqp_tick_replan_goals (tm NULL, an untimed plan) and wcqp_tick_replan_goals_timed (a timed one)
+int replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_timing* tm, bool timed, const wcqp_tick_goals* gl, void* stream) {
+    if (!h || !planner || !gl || !gl->goal || (timed && !tm)) return WCQP_E_INVALID;
+    if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    // (a plan is timed or not from its upload on: the untimed merge-point rule and planner kernel know one common timing, the timed ones none)
+    if (h->gp.timed != timed) return WCQP_E_UNSUPPORTED;
+    const wcqp_unicycle::UniPar* par = wcqp::unicycle_par(planner);
+    const size_t B = (size_t)h->d.batch;
+    const int K = par->K, T = h->d.traj_len, fd = gl->first_ds_ticks, per = h->gp.ss + h->gp.ds;
+    wcqp_unicycle::UniTiming utm{};
+    if (timed) {      // (the planner's own validation of tm; the duration rows are the call's, set where they are carved)
+        int32_t rows = 0;
+        if (const int rc = wcqp::unicycle_timing(planner, tm, &rows, &rows, &utm); rc != WCQP_OK) return rc;
+        utm.ss_ticks = nullptr; utm.ds_ticks = nullptr;
+    }
+    if (fd < 1 || gl->min_lead_ticks < 0) return WCQP_E_INVALID;
+    // (stage indices are 32-bit; a timed step lasts max_step_ticks at most, and its ds <= m - 1 covers a final_ds of 0)
+    if ((long long)T + fd + (long long)K * (timed ? tm->max_step_ticks : per) + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;
+    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (AUTO and the checks read the step counts - and durations - of the plans in force)
+    ReplanCall c(B);
+    std::vector<int> taken(B, 0), decided(B, 0);
+    const int t0 = consumed_stages(h);
+    for (size_t i = 0; i < B; ++i) {
+        int M = gl->merge_stage ? gl->merge_stage[i] : WCQP_TICK_MERGE_AUTO;
+        if (M == WCQP_TICK_MERGE_KEEP) { decided[i] = WCQP_GOAL_KEPT; continue; }      // (none of its rows is read)
+        if (M < WCQP_TICK_MERGE_AUTO || M == 0) return WCQP_E_INVALID;
+        const uint8_t fs = gl->first_side ? gl->first_side[i] : (uint8_t)WCQP_TICK_SIDE_AUTO;
+        if (fs > 1 && fs != WCQP_TICK_SIDE_AUTO) return WCQP_E_INVALID;
+        if (!std::isfinite(gl->goal[i * 2]) || !std::isfinite(gl->goal[i * 2 + 1])) return WCQP_E_INVALID;
+        if (M == WCQP_TICK_MERGE_AUTO) {
+            M = timed ? wcqp_goal::merge_auto(timed_plan_in_force(h, i), t0, gl->min_lead_ticks, T)
+                      : wcqp_goal::merge_auto(plan_in_force(h, i), t0, gl->min_lead_ticks, T);
+            if (M == wcqp_goal::kTooLate) { decided[i] = WCQP_GOAL_TOO_LATE; continue; }
+        } else if (!(timed ? wcqp_goal::merge_allowed(timed_plan_in_force(h, i), M, t0, T) : wcqp_goal::merge_allowed(plan_in_force(h, i), M, t0, T))) {
+            return WCQP_E_INVALID;
+        }
+        if (const int rc = replan_admit(h, i, M, fd, -1, c); rc != WCQP_OK) return rc;
+        taken[i] = M;
+    }
+    if (!c.robots.empty())
+        if (const int rc = replan_enqueue(h, c, K, fd, ReplanSource{nullptr, gl->goal, gl->first_side, par, nullptr, timed ? &utm : nullptr}, (hipStream_t)stream); rc != WCQP_OK)
+            return rc;
+    auto& gc = h->goal;
+    gc.called = true; gc.timed = timed; gc.K = K; gc.merge.swap(taken); gc.decided.swap(decided);
+    return WCQP_OK;
 }
 
 }  // namespace
@@ -690,40 +761,11 @@ int wcqp_tick_replan_footsteps_timed(wcqp_tick_t h, const wcqp_tick_replan* rp, 
 }
 
 int wcqp_tick_replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_tick_goals* gl, void* stream) {
-    if (!h || !planner || !gl || !gl->goal) return WCQP_E_INVALID;
-    if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
-    if (h->gp.timed) return WCQP_E_UNSUPPORTED;                    // (the merge-point rule and the planner kernel know one common timing)
-    const wcqp_unicycle::UniPar* par = wcqp::unicycle_par(planner);
-    const size_t B = (size_t)h->d.batch;
-    const int K = par->K, T = h->d.traj_len, fd = gl->first_ds_ticks, per = h->gp.ss + h->gp.ds;
-    if (fd < 1 || gl->min_lead_ticks < 0) return WCQP_E_INVALID;
-    if ((long long)T + fd + (long long)K * per + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
-    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (AUTO and the checks read the step counts of the plans in force)
-    ReplanCall c(B);
-    std::vector<int> taken(B, 0), decided(B, 0);
-    const int t0 = consumed_stages(h);
-    for (size_t i = 0; i < B; ++i) {
-        int M = gl->merge_stage ? gl->merge_stage[i] : WCQP_TICK_MERGE_AUTO;
-        if (M == WCQP_TICK_MERGE_KEEP) { decided[i] = WCQP_GOAL_KEPT; continue; }      // (none of its rows is read)
-        if (M < WCQP_TICK_MERGE_AUTO || M == 0) return WCQP_E_INVALID;
-        const uint8_t fs = gl->first_side ? gl->first_side[i] : (uint8_t)WCQP_TICK_SIDE_AUTO;
-        if (fs > 1 && fs != WCQP_TICK_SIDE_AUTO) return WCQP_E_INVALID;
-        if (!std::isfinite(gl->goal[i * 2]) || !std::isfinite(gl->goal[i * 2 + 1])) return WCQP_E_INVALID;
-        const wcqp_goal::PlanInForce pf = plan_in_force(h, i);
-        if (M == WCQP_TICK_MERGE_AUTO) {
-            M = wcqp_goal::merge_auto(pf, t0, gl->min_lead_ticks, T);
-            if (M == wcqp_goal::kTooLate) { decided[i] = WCQP_GOAL_TOO_LATE; continue; }
-        } else if (!wcqp_goal::merge_allowed(pf, M, t0, T)) {
-            return WCQP_E_INVALID;
-        }
-        if (const int rc = replan_admit(h, i, M, fd, -1, c); rc != WCQP_OK) return rc;
-        taken[i] = M;
-    }
-    if (!c.robots.empty())
-        if (const int rc = replan_enqueue(h, c, K, fd, ReplanSource{nullptr, gl->goal, gl->first_side, par}, (hipStream_t)stream); rc != WCQP_OK) return rc;
-    auto& gc = h->goal;
-    gc.called = true; gc.K = K; gc.merge.swap(taken); gc.decided.swap(decided);
-    return WCQP_OK;
+    return replan_goals(h, planner, nullptr, false, gl, stream);
+}
+
+int wcqp_tick_replan_goals_timed(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_timing* tm, const wcqp_tick_goals* gl, void* stream) {
+    return replan_goals(h, planner, tm, true, gl, stream);
 }
 
 int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out) {
@@ -743,6 +785,23 @@ int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out) {
         if (out->target && K > 0) { if (dev) std::memcpy(out->target + i * K * 3, r + gc.o_target + i * K * 24, K * 24); else std::memset(out->target + i * K * 3, 0, K * 24); }
         if (out->desired_point) { if (dev) std::memcpy(out->desired_point + i * 2, r + gc.o_dp + i * 16, 16); else std::memset(out->desired_point + i * 2, 0, 16); }
         if (out->unicycle_end) { if (dev) std::memcpy(out->unicycle_end + i * 3, r + gc.o_ue + i * 24, 24); else std::memset(out->unicycle_end + i * 3, 0, 24); }
+    }
+    return WCQP_OK;
+}
+
+int wcqp_tick_get_goal_timing(wcqp_tick_t h, int32_t* ss_ticks, int32_t* ds_ticks) {
+    if (!h) return WCQP_E_INVALID;
+    auto& gc = h->goal;
+    if (!gc.called || !gc.timed) return WCQP_E_INVALID;
+    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (waits for that call's own event, as wcqp_tick_get_goal_result)
+    const size_t B = (size_t)h->d.batch, K = (size_t)gc.K;
+    for (size_t i = 0; i < B && K > 0; ++i) {
+        const bool dev = gc.decided[i] == 0;
+        for (int which = 0; which < 2; ++which) {
+            int32_t* dst = which ? ds_ticks : ss_ticks;
+            if (!dst) continue;
+            if (dev) std::memcpy(dst + i * K, gc.host + (which ? gc.o_ds : gc.o_ss) + i * K * 4, K * 4); else std::memset(dst + i * K, 0, K * 4);
+        }
     }
     return WCQP_OK;
 }

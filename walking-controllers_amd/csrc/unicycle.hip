@@ -239,3 +239,6 @@ int wcqp_unicycle_plan_timed_host(wcqp_unicycle_t h, const wcqp_unicycle_timing*
 }  // extern "C"
 
 const wcqp_unicycle::UniPar* wcqp::unicycle_par(wcqp_unicycle_t h) { return h ? &h->par : nullptr; }
+int wcqp::unicycle_timing(wcqp_unicycle_t h, const wcqp_unicycle_timing* tm, int32_t* ss_ticks, int32_t* ds_ticks, wcqp_unicycle::UniTiming* out) {
+    return check_timing(h, tm, ss_ticks, ds_ticks, out);
+}

@@ -1,6 +1,7 @@
 // The unicycle planner's per-robot body (include/wcqp.h: wcqp_unicycle_*, which states the planner), shared by unicycle_kernel
 // (unicycle.hip: soles and goals from the caller's arrays) and goal_plan_kernel (tick_plan.hip: soles from a plan record of the tick
-// handle), as prepare_device.h is shared by prepare.hip and position_tick.hip.  Internal, not ABI.
+// handle) - and, in its timed form, by unicycle_timed_kernel and goal_plan_timed_kernel -, as prepare_device.h is shared by prepare.hip
+// and position_tick.hip.  Internal, not ABI.
 // A robot's plan is one serial chain of at most K x D RK4 steps, and the feasibility test rides on it: every sample is tested as it is
 // reached, the state of the last feasible one stays in registers, and the unicycle rewinds to it when the D samples of a step are through -
 // nothing is integrated twice and no path array exists.  The cosine and sine of a sample's heading serve its candidate, the first RK4 stage
@@ -183,4 +184,7 @@ __device__ __forceinline__ void plan_robot_timed(const UniPar& p, const UniTimin
 namespace wcqp {
 // unicycle.hip: the parameters a planner handle holds (NULL handle: NULL), for the kernels of other translation units
 const wcqp_unicycle::UniPar* unicycle_par(wcqp_unicycle_t h);
+// ... and the timed forms' validation of `tm` (what wcqp_unicycle_plan_timed_device refuses, it refuses), with the timing as a kernel takes
+// it: the candidates' range and score, and the two duration rows (NULL rows are refused for a planner with max_steps > 0)
+int unicycle_timing(wcqp_unicycle_t h, const wcqp_unicycle_timing* tm, int32_t* ss_ticks, int32_t* ds_ticks, wcqp_unicycle::UniTiming* out);
 }  // namespace wcqp
