@@ -252,7 +252,9 @@ typedef struct wcqp_ik_params {
     double  joint_reg_gains[WCQP_MAX_DOF];
     double  joint_reg_rad[WCQP_MAX_DOF]; /* jointRegularization already in rad (osqp.cpp:101-102) */
     double  v_min[WCQP_MAX_DOF];         /* joint velocity limits (WalkingModule.cpp:237-243)  */
-    double  v_max[WCQP_MAX_DOF];
+    double  v_max[WCQP_MAX_DOF];         /* any v_min[j] <= v_max[j] (else WCQP_E_INVALID): v_min need not be -v_max, an interval may
+                                            exclude zero, v_min[j] == v_max[j] pins joint j (dq[j] is that value exactly), +-1e30 leaves
+                                            a side open; an empty feasible set is WCQP_STATUS_INFEASIBLE per instance                 */
     double  k_pos_com, k_pos_foot, k_att_foot, k_neck;
     double  rho;                         /* weight of the A'A term that regularises H; 0 -> 1  */
     double  tol;                         /* bound-violation tolerance; 0 -> 1e-12              */

@@ -104,7 +104,7 @@ def _ik_params(ip, form):
                        (C.c_double * 9)(*np.asarray(ip.com_weight, float).reshape(-1)),
                        (C.c_double * 9)(*np.asarray(ip.neck_weight, float).reshape(-1)),
                        pad(ip.joint_reg_weights), pad(ip.joint_reg_gains), pad(ip.q_reg),
-                       pad(-np.asarray(ip.v_max)), pad(ip.v_max),
+                       pad(ip.v_lo), pad(ip.v_max),
                        ip.k_pos_com, ip.k_pos_foot, ip.k_att_foot, ip.k_neck)
 
 

@@ -402,11 +402,21 @@ class IKParams:
     k_att_foot: float = 2.0
     k_neck: float = 1.0
     v_max: np.ndarray = dataclasses.field(default_factory=lambda: np.ones(23))  # robot-supplied at run time (B-19)
+    # lower velocity bounds of their own (the C ABI's v_min[]); None = -v_max, which is all the reference's own
+    # back-ends ever pass.  Any v_min <= v_max is a QP: asymmetric, zero-excluding and pinned (v_min == v_max) intervals.
+    v_min: Optional[np.ndarray] = None
 
     @property
     def q_reg(self) -> np.ndarray:
         # deg -> rad: WM/src/WalkingQPInverseKinematics_osqp.cpp:101-102, _qpOASES.cpp:102-103
         return np.deg2rad(self.joint_reg_deg)
+
+    @property
+    def v_lo(self) -> np.ndarray:
+        """The lower bounds in force: v_min, or -v_max where none was given (bit for bit what -v_max always gave)."""
+        if self.v_min is None:
+            return -np.asarray(self.v_max, float)
+        return np.broadcast_to(np.asarray(self.v_min, float), (self.dof,)).copy()
 
 
 def rot_error(R: np.ndarray, Rd: np.ndarray) -> np.ndarray:
@@ -506,14 +516,16 @@ def ik_assemble_osqp(p: IKParams, x: IKInputs):
     """(P, q, A, l, u) handed to OSQP by WalkingQPIK_osqp: m = dof + 12 (+3).
     The joint-limit selector triplets are never populated (_osqp.hpp:18,
     _osqp.cpp:227-235), so the last `dof` rows of A are ZERO and the bounds
-    -v_max <= 0 <= v_max never bind."""
+    v_min <= 0 <= v_max never bind.  (An interval that excludes
+    zero would make OSQP's problem infeasible; ik_exact's osqp form, like the kernels',
+    has no such rows at all.)"""
     n = p.dof + 6
     At = ik_task_matrix(p, x)
     nt = At.shape[0]
     A = np.zeros((nt + p.dof, n))
     A[:nt] = At
     b = ik_task_rhs(p, x, "osqp")
-    l = np.concatenate([b, -p.v_max])       # _osqp.cpp:45-49
+    l = np.concatenate([b, p.v_lo])         # _osqp.cpp:45-49
     u = np.concatenate([b, +p.v_max])
     return ik_hessian(p, x), ik_gradient(p, x, "osqp"), A, l, u
 
@@ -523,7 +535,7 @@ def ik_assemble_qpoases(p: IKParams, x: IKInputs):
     (_qpOASES.cpp:284-339).  Base bounds are +-DBL_MAX (:39-43)."""
     b = ik_task_rhs(p, x, "qpoases")
     big = np.finfo(float).max
-    lb = np.concatenate([-big * np.ones(6), -p.v_max])
+    lb = np.concatenate([-big * np.ones(6), p.v_lo])
     ub = np.concatenate([+big * np.ones(6), +p.v_max])
     return ik_hessian(p, x), ik_gradient(p, x, "qpoases"), ik_task_matrix(p, x), lb, ub, b, b.copy()
 
@@ -541,7 +553,7 @@ def ik_exact(p: IKParams, x: IKInputs, form: str):
         E = np.zeros((p.dof, n))
         E[np.arange(p.dof), np.arange(6, n)] = 1.0
         Ain = np.vstack([E, -E])
-        bin_ = np.concatenate([p.v_max, p.v_max])
+        bin_ = np.concatenate([p.v_max, -p.v_lo])     # E dq <= v_max, -E dq <= -v_min
     else:
         Ain = np.zeros((0, n))
         bin_ = np.zeros(0)

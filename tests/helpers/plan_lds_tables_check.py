@@ -101,9 +101,11 @@ def run_plan(mpc, ik, B, sets, ways, ref, what):
 
 
 def per_joint_ik(form):
-    """an IK solver whose tables differ in every entry: bounds, weights (sd / isd per column), gains and posture per joint"""
+    """an IK solver whose tables differ in every entry: bounds, weights (sd / isd per column), gains and posture per joint, and a
+    neck weight with a full Cholesky factor (tests/ik_parameter_cases.py: W), so that the plan kernels see L01, L02, L12 != 0"""
     k = np.arange(23.0)
-    return wca.IkSolver(form=form, v_max=0.04 + 0.013 * k, v_min=-(0.05 + 0.011 * k[::-1]), joint_reg_weights=1.0 + 0.37 * k,
+    W = np.array([[3.6, 1.1, 1.0], [1.1, 8.2, 3.5], [1.0, 3.5, 3.2]])
+    return wca.IkSolver(form=form, v_max=0.04 + 0.013 * k, v_min=-(0.05 + 0.011 * k[::-1]), joint_reg_weights=1.0 + 0.37 * k, neck_weight=W,
                         joint_reg_gains=3.0 + 0.21 * k, joint_reg_rad=np.deg2rad(wca.synth.ICUB_JOINT_REG_DEG) + 0.02 * (k - 11.0),
                         jacobian_structure=wca.IK_JAC_MIXED)
 

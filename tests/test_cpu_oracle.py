@@ -314,3 +314,108 @@ def test_exact_oracle_against_scipy_slsqp_on_assembled_qps(qs, wca):
         assert np.abs(x[6:] - r["dq"]).max() < 1e-8, i
         n_active += len(r["lower"]) + len(r["upper"])
     assert n_active >= 6          # the comparison is on instances whose bounds bind
+
+
+# ---- IK parameter axes: full weight factors, lower bounds of their own (tests/ik_parameter_cases.py) --------------------------
+# The kernels are held to the numpy oracle on these cases in tests/test_ik_parameters.py.  Here: the oracle's two plain-C
+# restatements reach the same optimum (so the inputs are solvable and the reference is sound), and the inputs tell a transposed
+# weight factor and a mirrored lower bound from the right ones by orders more than the 1e-9 the kernels are held to.
+import ik_parameter_cases as ic
+
+
+def test_v_min_none_is_minus_v_max_bit_for_bit(qs, wca):
+    """IKParams.v_min = None is -v_max: the same arrays reach both back-end assemblies and the same optimum comes out, bit for bit."""
+    b = wca.synth.synth_ik_batch(6, seed=4321)
+    vmax = 0.3 * np.ones(23)
+    a, e = qs.IKParams(v_max=vmax), qs.IKParams(v_max=vmax, v_min=-vmax)
+    assert a.v_min is None and np.array_equal(a.v_lo, -vmax)
+    for i in range(6):
+        x = qs.ik_inputs_from_batch(b, i)
+        for u, v in zip(qs.ik_assemble_qpoases(a, x) + qs.ik_assemble_osqp(a, x), qs.ik_assemble_qpoases(e, x) + qs.ik_assemble_osqp(e, x)):
+            assert np.array_equal(u, v)
+        ra, re_ = qs.ik_exact(a, x, "qpoases"), qs.ik_exact(e, x, "qpoases")
+        assert np.array_equal(ra["dq"], re_["dq"]) and ra["lower"] == re_["lower"] and ra["upper"] == re_["upper"]
+    lo, hi = ic.CASES["asym"][:2]
+    H, g, A, lb, ub, lbA, ubA = qs.ik_assemble_qpoases(qs.IKParams(v_min=lo, v_max=hi), qs.ik_inputs_from_batch(b, 0))
+    assert np.array_equal(lb[6:], lo) and np.array_equal(ub[6:], hi)
+    P, q, A, l, u = qs.ik_assemble_osqp(qs.IKParams(v_min=lo, v_max=hi), qs.ik_inputs_from_batch(b, 0))
+    assert np.array_equal(l[15:], lo) and np.array_equal(u[15:], hi)
+
+
+@pytest.mark.parametrize("name", ic.NAMES)
+def test_c_solvers_on_ik_parameter_cases(qs, wca, name):
+    """co.ik_batch (dense active set) and, where it applies (CoM as constraint, positive definite neck weight, positive joint weights:
+    the range space divides by their roots, which is why wcqp_ik_create sets fast_ok = 0 without them), co.ik_batch_range_space
+    (the ik4 algorithm in plain C) against qs.ik_exact, at the tolerances this file already holds the two to."""
+    from oracle import c_oracle as co
+    b, p, ex = ic.batch(wca), ic.oracle_params(qs, name), ic.exact(qs, wca, name)
+    solved = np.array([r is not None for r in ex])
+    legs = [("dense", co.ik_batch, 1e-12)]
+    if p.use_com_as_constraint and np.linalg.eigvalsh(p.neck_weight).min() > 0 and p.joint_reg_weights.min() > 0:
+        legs.append(("range_space", co.ik_batch_range_space, 1e-10))
+    for leg, fn, tol in legs:
+        dq, st, lo, up, it = fn(p, b, "qpoases", nthreads=2)
+        assert np.array_equal(st == 0, solved) and (st[~solved] == 2).all(), (leg, st)
+        worst = 0.0
+        for i in np.flatnonzero(solved):
+            worst = max(worst, np.abs(dq[i] - ex[i]["dq"]).max())
+            if ic.clear_cut(ex[i]):
+                assert int(lo[i]) == ic.mask(ex[i]["lower"]) and int(up[i]) == ic.mask(ex[i]["upper"]), (leg, i)
+        print(name, leg, "worst |dq - dq_exact| %.2e" % worst)
+        assert worst < tol, leg
+    # what the issue measured on the oracle, so that the GPU tests' own conditions are known to hold before a GPU sees them
+    n_lo = sum(len(r["lower"]) for r in ex if r is not None); n_up = sum(len(r["upper"]) for r in ex if r is not None)
+    n_cc = sum(ic.clear_cut(r) for r in ex if r is not None)
+    print(name, "infeasible", int((~solved).sum()), "lower", n_lo, "upper", n_up, "clear-cut", n_cc)
+    assert (~solved).sum() == 0 or name == "tight_tables"
+    assert n_lo >= 1 and n_up >= 1
+    if name == "pinned":
+        assert n_cc == 0                    # the opposite bound of a pinned joint has slack 0
+        assert all(np.abs(r["dq"][[4, 15]] - 0.1).max() < 1e-15 for r in ex)
+    else:
+        assert n_cc >= (0.7 if name == "tight_tables" else 0.8) * ic.BATCH
+
+
+def _dq16(qs, wca, p):
+    b = ic.batch(wca)
+    return [qs.ik_exact(p, qs.ik_inputs_from_batch(b, i), "qpoases")["dq"] for i in range(16)]
+
+
+@pytest.mark.parametrize("name", ic.WITH_W)
+def test_ik_cases_tell_a_transposed_weight_factor(qs, wca, name):
+    """W = L L'.  A kernel that used L where it needs L' solves the QP of L'L: on every one of the first 16 instances that optimum
+    is more than 1e-6 (1e3 times the kernels' tolerance) from the right one.  A condition on the inputs, not on any kernel."""
+    ex = ic.exact(qs, wca, name)[:16]
+    assert all(r is not None for r in ex)
+    L = np.linalg.cholesky(ic.W)
+    assert min(abs(L[1, 0]), abs(L[2, 0]), abs(L[2, 1])) > 0.1
+    wrong = _dq16(qs, wca, ic.oracle_params(qs, name, neck_weight=L.T @ L))
+    d = [np.abs(w - r["dq"]).max() for w, r in zip(wrong, ex)]
+    print(name, "neck L'L for L L': min %.2e max %.2e" % (min(d), max(d)))
+    assert min(d) > 1e-6
+    if name == "com_cost_full":
+        Lc = np.linalg.cholesky(ic.CASES[name][2]["com_weight"])
+        wrong = _dq16(qs, wca, ic.oracle_params(qs, name, com_weight=Lc.T @ Lc))
+        d = [np.abs(w - r["dq"]).max() for w, r in zip(wrong, ex)]
+        print(name, "com L'L for L L': min %.2e max %.2e" % (min(d), max(d)))
+        assert min(d) > 1e-6
+
+
+@pytest.mark.parametrize("name", ic.ASYMMETRIC)
+def test_ik_cases_tell_a_mirrored_lower_bound(qs, wca, name):
+    """A kernel that read -v_max where it needs v_min solves another QP: on at least half of the solved instances that optimum (or
+    its infeasibility) is more than 1e-6 from the right one."""
+    b, ex = ic.batch(wca), ic.exact(qs, wca, name)
+    p = ic.oracle_params(qs, name)
+    p.v_min = None
+    differ = n = 0
+    for i, r in enumerate(ex):
+        if r is None:
+            continue
+        n += 1
+        try:
+            differ += np.abs(qs.ik_exact(p, qs.ik_inputs_from_batch(b, i), "qpoases")["dq"] - r["dq"]).max() > 1e-6
+        except qs.QPInfeasible:
+            differ += 1
+    print(name, "v_min := -v_max moves", differ, "of", n)
+    assert 2 * differ >= n

@@ -360,6 +360,65 @@ def test_tick_pipeline_with_per_tick_kinematics_matches_cpu_restatement(wca, qs,
     assert (np.abs(np.abs(ref["dq_log"]) - vmax) < 1e-12).any()        # velocity limits really bind
 
 
+def _bound_ticks(ref):
+    """robot-ticks of a restatement run on which a lower / an upper joint-velocity bound holds"""
+    return int((ref["active_lower_log"] != 0).sum()), int((ref["active_upper_log"] != 0).sum())
+
+
+@pytest.mark.gpu
+def test_tick_pipeline_with_a_full_neck_weight_and_bounds_of_their_own(wca, qs):
+    """The tick kernel's IK with the parameters tests/test_ik_parameters.py varies on the single calls: a neck weight whose Cholesky
+    factor is full, and lower bounds that are not the negated upper ones.  60 closed-loop ticks against oracle/tick_spec.py at the
+    bars of test_tick_pipeline_matches_cpu_restatement; the restatement holds a lower bound on 61 robot-ticks and an upper one on 22."""
+    from oracle import tick_spec as ts
+    import ik_parameter_cases as ic
+    B, T = 5, 60
+    k = np.arange(23.0)
+    v_min, v_max = -(0.25 + 0.01 * k[::-1]), 0.35 + 0.01 * k
+    d = wca.synth.synth_tick_batch(B, T)
+    ref = ts.run_ticks(ts.TickParams(), d, T, qs.IKParams(neck_weight=ic.W, v_min=v_min, v_max=v_max))
+    n_lo, n_up = _bound_ticks(ref)
+    print("robot-ticks with a lower bound active", n_lo, "with an upper one", n_up)
+    assert ref["mpc_fail"].sum() == 0 and ref["ik_fail"].sum() == 0 and n_lo >= 40 and n_up >= 15
+    pipe = wca.TickPipeline(B, T, wca.MpcSolver(), wca.IkSolver(form=wca.IK_FORM_QPOASES, neck_weight=ic.W, v_min=v_min, v_max=v_max), log_ticks=T)
+    pipe.upload(d)
+    pipe.run(T)
+    _tick_bars(pipe.download(), ref, T)
+
+
+def _tick_bars(out, ref, T):
+    assert out["tick"] == T and out["mpc_fail"].sum() == 0 and out["ik_fail"].sum() == 0
+    for key, tol in (("u0_log", 1e-9), ("dq_log", 1e-8), ("q_des", 1e-9), ("dcm", 1e-9), ("com", 1e-9)):
+        err = np.abs(out[key] - ref[key]).max()
+        print(key, "%.2e" % err)
+        assert err <= tol, (key, err)
+    assert np.array_equal(out["active_lower"], ref["active_lower"]) and np.array_equal(out["active_upper"], ref["active_upper"])
+
+
+@pytest.mark.gpu
+def test_tick_with_kinematics_a_full_neck_weight_and_bounds_of_their_own(wca, qs):
+    """The same with per-tick kinematics fused into the solve kernel (the pattern of _kin_tick_against_oracle): the walk scenario
+    with the neck weight W and v_min = -0.6 WALK_VMAX, v_max = 0.4 WALK_VMAX.  (The walk's joint velocities are lopsided - without bounds
+    they reach -1.8 WALK_VMAX but only +0.54 WALK_VMAX - so an upper bound at WALK_VMAX itself never holds; at 0.4 the restatement, on
+    kin_spec's poses, holds a lower bound on 175 robot-ticks and an upper one on 110, and no QP fails.)"""
+    from oracle import tick_spec as ts
+    import ik_parameter_cases as ic
+    B, T = 5, 60
+    S = wca.synth
+    v_min, v_max = -0.6 * S.WALK_VMAX, 0.4 * S.WALK_VMAX
+    kin, d = _walk_scenario(wca, B, T)
+    ref = ts.run_ticks(ts.TickParams(), d, T, qs.IKParams(neck_weight=ic.W, v_min=v_min, v_max=v_max, joint_reg_deg=S.WALK_POSTURE_DEG.copy()),
+                       kin_model=S.icub_like_model(), foot_rect=S.FOOT_RECT)
+    n_lo, n_up = _bound_ticks(ref)
+    print("robot-ticks with a lower bound active", n_lo, "with an upper one", n_up)
+    assert ref["mpc_fail"].sum() == 0 and ref["ik_fail"].sum() == 0 and n_lo >= 40 and n_up >= 15
+    ik = wca.IkSolver(form=wca.IK_FORM_QPOASES, neck_weight=ic.W, v_min=v_min, v_max=v_max, joint_reg_rad=np.deg2rad(S.WALK_POSTURE_DEG))
+    pipe = wca.TickPipeline(B, T, wca.MpcSolver(), ik, log_ticks=T, kin=kin, kin_handoff=wca.KIN_HANDOFF_FUSED)
+    pipe.upload(d)
+    pipe.run(T)
+    _tick_bars(pipe.download(), ref, T)
+
+
 @pytest.mark.gpu
 def test_kinematics_handoff_forms_agree(wca):
     """The compact kinematics -> IK hand-off carries exactly the non-zero entries of the four Jacobians, and the fused kinematics
