@@ -14,7 +14,7 @@ int main() {
         for (int O : origins)
             for (int lead : leads)
                 for (int T : Ts) {
-                    const wcqp_goal::PlanInForce p{O, fo, n, ss, ds};
+                    const wcqp_goal::Timeline p = wcqp_goal::Timeline::uniform(O, fo, n, ss, ds);
                     const int end = O + fo + n * (ss + ds) + ds;      // one stage past the plan's last double support
                     for (int t0 = 0; t0 <= end && t0 < T; ++t0) {
                         const int M = wcqp_goal::merge_auto(p, t0, lead, T);
@@ -24,7 +24,7 @@ int main() {
                     }
                 }
     // the far corners: nothing overflows
-    const wcqp_goal::PlanInForce big{1 << 29, 1 << 29, 1 << 20, 1 << 9, 1 << 9};
+    const wcqp_goal::Timeline big = wcqp_goal::Timeline::uniform(1 << 29, 1 << 29, 1 << 20, 1 << 9, 1 << 9);
     const int M = wcqp_goal::merge_auto(big, 2147483647, 2147483647, 2147483647);
     std::printf("corner %d\n", M);
     std::printf("goal_merge ok %ld\n", rows);

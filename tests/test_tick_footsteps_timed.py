@@ -1,8 +1,12 @@
 """Per-step timings: footsteps that carry their own durations (wcqp_tick_upload_footsteps_timed / wcqp_tick_replan_footsteps_timed,
 DESIGN §8.21).  CPU: the numpy restatement (helpers/footstep_plan_timed.py) with uniform durations against the untimed restatements, the
 NULL refusals.  GPU: uniform timed calls against the untimed ones bit for bit, the timed plan and replan against the restatement, the
-refusals that leave the handle unchanged."""
+refusals that leave the handle unchanged, and both uploads at a batch whose record pass takes a second launch."""
 import ctypes as C
+import json
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -394,3 +398,23 @@ def test_refusals_leave_the_plan_unchanged(wca, scen, timed, replans):
     pipe2.upload_footsteps(fs, fs)
     assert pipe2.info()["plan_timed"] is False
     pipe2.replan_footsteps(np.full(B35, -1, np.int32), {k: rp[k] for k in ("n_steps", "side", "target")}, 9)
+
+
+# seconds for the child process below.  Measured once on an MI355X: 1.2 s for the process, 0.44 s of it between the first import's end and
+# the last comparison (0.26 s to create the two handles).  Twice the process's time, and a margin for a cold start of the GPU runtime.
+SECOND_SLAB_LIMIT = 30
+
+
+@pytest.mark.gpu
+def test_uploads_past_65535_robots_take_the_second_record_launch():
+    """B = 65536, the smallest batch with a robot on the record pass's second launch (robots lie on grid.y), on the smallest handle
+    (max_ticks = 1, MPC horizon 1), K = 1, n_steps alternating 0 and 1, every robot at its own offset: robots 0, 65533, 65534 and 65535 of
+    the untimed and of the timed upload - whose durations differ for 65534 and 65535 - equal the restatements (flags and hull_nc exact,
+    the rest within 1e-9) and, bit for bit, a handle of those four robots alone.  tests/helpers/footstep_second_slab_check.py in a
+    process of its own, under a time limit."""
+    r = subprocess.run(["timeout", "-k", "10", str(SECOND_SLAB_LIMIT), sys.executable,
+                        os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", "footstep_second_slab_check.py")], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("footstep second slab ok"), r.stdout[-3000:] + r.stderr[-3000:]
+    res = json.loads(r.stdout.strip().splitlines()[-2])
+    print(res)
+    assert res["batch"] == 65536 and max(res["untimed"].values()) <= TOL and max(res["timed"].values()) <= TOL

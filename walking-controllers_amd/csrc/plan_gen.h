@@ -56,11 +56,11 @@ struct PlanGenTimedDev {
 }  // namespace wcqp_tick
 
 namespace wcqp {
-// prologue, DCM pass and record pass of one upload, in stream order (plan_gen.hip); rec0 / rec1 (or NULL): events recorded around the record pass
+// prologue, DCM pass and record pass of one upload, in stream order (plan_gen.hip); rec0 / rec1 (or NULL): events recorded around the record
+// pass.  An untimed plan (ss, ds, final_ds >= 1), or a timed one (wcqp_tick_upload_footsteps_timed: final_ds >= 0 and the three rows)
 int plan_gen_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
-// the same three passes from per-robot origins, over the listed robots and tiles only (wcqp_tick_replan_footsteps); enqueue-only
+int plan_gen_enqueue(const wcqp_tick::PlanGenTimedDev& t, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
+// the same three passes from per-robot origins, over the listed robots and tiles only (wcqp_tick_replan_footsteps*); enqueue-only
 int plan_replan_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream);
-// the timed forms of the two (wcqp_tick_upload_footsteps_timed, wcqp_tick_replan_footsteps_timed)
-int plan_gen_timed_enqueue(const wcqp_tick::PlanGenTimedDev& t, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
-int plan_replan_timed_enqueue(const wcqp_tick::PlanGenTimedDev& t, hipStream_t stream);
+int plan_replan_enqueue(const wcqp_tick::PlanGenTimedDev& t, hipStream_t stream);
 }  // namespace wcqp

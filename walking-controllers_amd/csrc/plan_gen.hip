@@ -13,6 +13,7 @@
 // robot's start table - entry k the first stage s_k of step k's single support on the plan's own timeline, entry n the first standing
 // stage -, the DCM pass walks a step index down it as its stage passes s_k, and the record pass copies the entries its tile touches into
 // LDS next to the footprints and finds each lane's step by a search there.  The untimed instantiations are the code they were.
+// The four forms - upload or replan, untimed or timed - are launched by one enqueue<RP, Arg> at the end of this file.
 #include <cmath>
 #include "plan_gen.h"
 
@@ -363,71 +364,67 @@ __global__ __launch_bounds__(kRecTile) void plan_record_replan_timed_kernel(Plan
     plan_record<true, true>(t.g, t.tm, stl, ssl);
 }
 
+// ---- the launch path: one implementation for the four forms - upload or replan (RP), untimed or timed (the argument's type)
+// what differs by the argument: the PlanGenDev in it, the kernels that take it, the checks of its durations, and the rows a slab advances
+const PlanGenDev& base(const PlanGenDev& g) { return g; }
+const PlanGenDev& base(const PlanGenTimedDev& t) { return t.g; }
+
+template <bool RP, class Arg> struct Passes;
+template <> struct Passes<false, PlanGenDev> { static constexpr auto prologue = plan_prologue_kernel, dcm = plan_dcm_kernel, record = plan_record_kernel; };
+template <> struct Passes<true, PlanGenDev> { static constexpr auto prologue = plan_prologue_replan_kernel, dcm = plan_dcm_replan_kernel, record = plan_record_replan_kernel; };
+template <> struct Passes<false, PlanGenTimedDev> { static constexpr auto prologue = plan_prologue_timed_kernel, dcm = plan_dcm_timed_kernel, record = plan_record_timed_kernel; };
+template <> struct Passes<true, PlanGenTimedDev> { static constexpr auto prologue = plan_prologue_replan_timed_kernel, dcm = plan_dcm_replan_timed_kernel, record = plan_record_replan_timed_kernel; };
+
+// an untimed plan has one (ss, ds) and a resolved final_ds; a timed one its three rows, and a final_ds of 0 for each last step's own ds
+bool durations_ok(const PlanGenDev& g) { return g.ss >= 1 && g.ds >= 1 && g.final_ds >= 1; }
+bool durations_ok(const PlanGenTimedDev& t) { return t.tm.final_ds >= 0 && t.tm.start && (t.g.K == 0 || (t.tm.ss_k && t.tm.ds_k)); }
+
+// the per-robot rows of the record pass moved on by i0 robots (its robot index is grid.y, which starts at 0 in every launch)
+void advance(PlanGenDev& p, int i0) {
+    p.n_steps += i0; p.side += (size_t)i0 * p.K; p.target += (size_t)i0 * p.K * 3; p.state += (size_t)i0 * kStateLen;
+    p.set_base += i0; p.table += (size_t)i0 * (size_t)(p.K + 1) * kFpRec; p.rec += (size_t)i0 * (size_t)p.traj_len * kPlanRec;
+}
+void advance(PlanGenTimedDev& t, int i0) {
+    advance(t.g, i0);
+    t.tm.ss_k += (size_t)i0 * t.g.K; t.tm.ds_k += (size_t)i0 * t.g.K; t.tm.start += (size_t)i0 * (size_t)(t.g.K + 1);
+}
+
+// prologue, DCM pass and record pass in stream order.  An upload runs every robot, its record pass one launch per 65535 robots (they lie
+// on grid.y) with rec0 / rec1 recorded around it; a replan runs the listed robots and tiles and records nothing.
+template <bool RP, class Arg>
+int enqueue(const Arg& a, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) {
+    using P = Passes<RP, Arg>;
+    const PlanGenDev& g = base(a);
+    if (g.batch < 1 || g.traj_len < 1 || g.first_ds < 1 || g.K < 0 || !durations_ok(a)) return WCQP_E_INVALID;
+    if (RP && (!g.origin || !g.robots || !g.tiles || !g.h0 || g.n_robots < 0 || g.n_tiles < 0)) return WCQP_E_INVALID;
+    const int robots = RP ? g.n_robots : g.batch;
+    if (robots == 0) return WCQP_OK;
+    hipLaunchKernelGGL(P::prologue, dim3((unsigned)((robots + 63) / 64)), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(P::dcm, dim3((unsigned)((robots + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, a);
+    if (rec0) WCQP_HIP_TRY(hipEventRecord(rec0, stream));
+    if (RP) {
+        if (g.n_tiles > 0) hipLaunchKernelGGL(P::record, dim3((unsigned)g.n_tiles), dim3(kRecTile), 0, stream, a);
+    } else {
+        constexpr int kSlab = 65535;
+        for (int i0 = 0; i0 < g.batch; i0 += kSlab) {
+            Arg slab = a;
+            advance(slab, i0);
+            const int nb = g.batch - i0 < kSlab ? g.batch - i0 : kSlab;
+            hipLaunchKernelGGL(P::record, dim3((unsigned)((g.traj_len + kRecTile - 1) / kRecTile), (unsigned)nb), dim3(kRecTile), 0, stream, slab);
+        }
+    }
+    if (rec1) WCQP_HIP_TRY(hipEventRecord(rec1, stream));
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+
 }  // namespace
 
 namespace wcqp {
 
-int plan_gen_enqueue(const PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) {
-    if (g.batch < 1 || g.traj_len < 1 || g.ss < 1 || g.ds < 1 || g.first_ds < 1 || g.final_ds < 1 || g.K < 0) return WCQP_E_INVALID;
-    hipLaunchKernelGGL(plan_prologue_kernel, dim3((unsigned)((g.batch + 63) / 64)), dim3(64), 0, stream, g);
-    hipLaunchKernelGGL(plan_dcm_kernel, dim3((unsigned)((g.batch + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, g);
-    if (rec0) WCQP_HIP_TRY(hipEventRecord(rec0, stream));
-    // (robots on grid.y: 65535 at most per launch)
-    for (int i0 = 0; i0 < g.batch; i0 += 65535) {
-        PlanGenDev p = g;
-        const int nb = g.batch - i0 < 65535 ? g.batch - i0 : 65535;
-        p.n_steps += i0; p.side += (size_t)i0 * g.K; p.target += (size_t)i0 * g.K * 3; p.state += (size_t)i0 * kStateLen;
-        p.set_base += i0; p.table += (size_t)i0 * (size_t)(g.K + 1) * kFpRec; p.rec += (size_t)i0 * (size_t)g.traj_len * kPlanRec;
-        hipLaunchKernelGGL(plan_record_kernel, dim3((unsigned)((g.traj_len + kRecTile - 1) / kRecTile), (unsigned)nb), dim3(kRecTile), 0, stream, p);
-    }
-    if (rec1) WCQP_HIP_TRY(hipEventRecord(rec1, stream));
-    WCQP_HIP_TRY(hipGetLastError());
-    return WCQP_OK;
-}
-
-
-int plan_gen_timed_enqueue(const PlanGenTimedDev& t, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) {
-    const PlanGenDev& g = t.g;
-    if (g.batch < 1 || g.traj_len < 1 || g.first_ds < 1 || t.tm.final_ds < 0 || g.K < 0 || !t.tm.start || (g.K > 0 && (!t.tm.ss_k || !t.tm.ds_k))) return WCQP_E_INVALID;
-    hipLaunchKernelGGL(plan_prologue_timed_kernel, dim3((unsigned)((g.batch + 63) / 64)), dim3(64), 0, stream, t);
-    hipLaunchKernelGGL(plan_dcm_timed_kernel, dim3((unsigned)((g.batch + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, t);
-    if (rec0) WCQP_HIP_TRY(hipEventRecord(rec0, stream));
-    // (robots on grid.y: 65535 at most per launch)
-    for (int i0 = 0; i0 < g.batch; i0 += 65535) {
-        PlanGenTimedDev q = t;
-        PlanGenDev& p = q.g;
-        const int nb = g.batch - i0 < 65535 ? g.batch - i0 : 65535;
-        p.n_steps += i0; p.side += (size_t)i0 * g.K; p.target += (size_t)i0 * g.K * 3; p.state += (size_t)i0 * kStateLen;
-        p.set_base += i0; p.table += (size_t)i0 * (size_t)(g.K + 1) * kFpRec; p.rec += (size_t)i0 * (size_t)g.traj_len * kPlanRec;
-        q.tm.ss_k += (size_t)i0 * g.K; q.tm.ds_k += (size_t)i0 * g.K; q.tm.start += (size_t)i0 * (size_t)(g.K + 1);
-        hipLaunchKernelGGL(plan_record_timed_kernel, dim3((unsigned)((g.traj_len + kRecTile - 1) / kRecTile), (unsigned)nb), dim3(kRecTile), 0, stream, q);
-    }
-    if (rec1) WCQP_HIP_TRY(hipEventRecord(rec1, stream));
-    WCQP_HIP_TRY(hipGetLastError());
-    return WCQP_OK;
-}
-
-int plan_replan_timed_enqueue(const PlanGenTimedDev& t, hipStream_t stream) {
-    const PlanGenDev& g = t.g;
-    if (g.batch < 1 || g.traj_len < 1 || g.first_ds < 1 || t.tm.final_ds < 0 || g.K < 0 || !t.tm.start || (g.K > 0 && (!t.tm.ss_k || !t.tm.ds_k))) return WCQP_E_INVALID;
-    if (!g.origin || !g.robots || !g.tiles || !g.h0 || g.n_robots < 0 || g.n_tiles < 0) return WCQP_E_INVALID;
-    if (g.n_robots == 0) return WCQP_OK;
-    hipLaunchKernelGGL(plan_prologue_replan_timed_kernel, dim3((unsigned)((g.n_robots + 63) / 64)), dim3(64), 0, stream, t);
-    hipLaunchKernelGGL(plan_dcm_replan_timed_kernel, dim3((unsigned)((g.n_robots + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, t);
-    if (g.n_tiles > 0) hipLaunchKernelGGL(plan_record_replan_timed_kernel, dim3((unsigned)g.n_tiles), dim3(kRecTile), 0, stream, t);
-    WCQP_HIP_TRY(hipGetLastError());
-    return WCQP_OK;
-}
-
-int plan_replan_enqueue(const PlanGenDev& g, hipStream_t stream) {
-    if (g.batch < 1 || g.traj_len < 1 || g.ss < 1 || g.ds < 1 || g.first_ds < 1 || g.final_ds < 1 || g.K < 0) return WCQP_E_INVALID;
-    if (!g.origin || !g.robots || !g.tiles || !g.h0 || g.n_robots < 0 || g.n_tiles < 0) return WCQP_E_INVALID;
-    if (g.n_robots == 0) return WCQP_OK;
-    hipLaunchKernelGGL(plan_prologue_replan_kernel, dim3((unsigned)((g.n_robots + 63) / 64)), dim3(64), 0, stream, g);
-    hipLaunchKernelGGL(plan_dcm_replan_kernel, dim3((unsigned)((g.n_robots + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, g);
-    if (g.n_tiles > 0) hipLaunchKernelGGL(plan_record_replan_kernel, dim3((unsigned)g.n_tiles), dim3(kRecTile), 0, stream, g);
-    WCQP_HIP_TRY(hipGetLastError());
-    return WCQP_OK;
-}
+int plan_gen_enqueue(const PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) { return enqueue<false>(g, stream, rec0, rec1); }
+int plan_gen_enqueue(const PlanGenTimedDev& t, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) { return enqueue<false>(t, stream, rec0, rec1); }
+int plan_replan_enqueue(const PlanGenDev& g, hipStream_t stream) { return enqueue<true>(g, stream, nullptr, nullptr); }
+int plan_replan_enqueue(const PlanGenTimedDev& t, hipStream_t stream) { return enqueue<true>(t, stream, nullptr, nullptr); }
 
 }  // namespace wcqp

@@ -6,6 +6,7 @@
 #include "tick_device.h"
 #include "ik_common.h"
 #include "position_tick.h"
+#include "goal_merge.h"
 
 // how a tick is launched: the skewed base-eliminated kernel (ONE launch), MPC + the 16-lane kernel with glue and post fused in
 // (two), or MPC, glue, IK and post (four; any other IK kernel, and what the fused forms are tested against)
@@ -120,23 +121,51 @@ struct wcqp_tick_s {
         // ds), cap counts a step as two stages, and dur[i] holds the durations of robot i's plan in force, ss_k then ds_k per step
         bool timed = false;
         std::vector<std::vector<int>> dur;
+        // robot i's plan in force on its own timeline (goal_merge.h) - the one place that knows which kind of plan the handle holds
+        wcqp_goal::Timeline timeline(size_t i) const {
+            return timed ? wcqp_goal::Timeline::per_step(origin[i], first_ds[i], n_steps[i], dur[i].data(), dur[i].data() + 1, 2)
+                         : wcqp_goal::Timeline::uniform(origin[i], first_ds[i], n_steps[i], ss, ds);
+        }
+        // robot i takes n steps from now on: on a timed plan with the durations ss_k / ds_k [n] (unread on an untimed one)
+        void set_steps(size_t i, int n, const int32_t* ss_k, const int32_t* ds_k) {
+            n_steps[i] = n;
+            if (!timed) return;
+            dur[i].resize(2 * (size_t)n);
+            for (int k = 0; k < n; ++k) { dur[i][2 * k] = ss_k[k]; dur[i][2 * k + 1] = ds_k[k]; }
+        }
     } gp;
     // its per-call device memory (footsteps, robot and tile lists, footprint tables, set table), guarded behind the call's kernels
     StagedBlock rp;
+    // The result rows of a goal call (wcqp_tick_replan_goals*), one contiguous run of B robots' rows for a planner of K steps - doubles,
+    // then the 32-bit rows, then the bytes -: the kernels write them in device memory, one copy brings them into GoalCall::host, and every
+    // reader finds a row at the offset stated HERE.  A timed call has the two duration rows [B][K]; an untimed one gives them no room.
+    struct GoalRows {
+        size_t K = 0; bool timed = false;
+        size_t target = 0, dp = 0, ue = 0, n = 0, status = 0, ss = 0, ds = 0, side = 0, fs = 0, bytes = 0;
+        static GoalRows of(size_t B, size_t K, bool timed) {
+            GoalRows r;
+            const size_t BK = B * K, dur = timed ? BK * 4 : 0;
+            r.K = K; r.timed = timed;
+            r.target = 0; r.dp = r.target + BK * 24; r.ue = r.dp + B * 16;
+            r.n = r.ue + B * 24; r.status = r.n + B * 4; r.ss = r.status + B * 4; r.ds = r.ss + dur;
+            r.side = r.ds + dur; r.fs = r.side + BK; r.bytes = r.fs + B;
+            return r;
+        }
+        template <class T> T* at(char* base, size_t off) const { return reinterpret_cast<T*>(base + off); }
+        template <class T> const T* at(const char* base, size_t off) const { return reinterpret_cast<const T*>(base + off); }
+    };
     // wcqp_tick_replan_goals: the footsteps are planned on the device, so a goal-replanned robot's gp.n_steps is known only once the
     // call's result rows have come back into `host` (pinned; one copy behind the call's kernels, `ev` recorded behind it).  Until then the
     // robot is `owed`: whatever reads gp.n_steps calls settle() first, which waits for that event alone and folds the values in.  The
     // rows stay for wcqp_tick_get_goal_result, with what the host decided per robot at the call: the merge stage taken (0: none) and
     // WCQP_GOAL_KEPT / WCQP_GOAL_TOO_LATE (0: the device's status row holds).  A TIMED goal call (wcqp_tick_replan_goals_timed) owes the
-    // robot's durations too: its rows hold ss_ticks / ds_ticks [B][K] at o_ss / o_ds, and settle() folds them into gp.dur next to the step
-    // counts - every reader of gp.dur (the timed merge rule, the timed replan_admit, AUTO of a later goal call) sits behind a settle()
+    // robot's durations too, and settle() folds them into gp.dur next to the step counts - every reader of a timeline (the merge rule,
+    // replan_admit, AUTO of a later goal call) sits behind a settle()
     struct GoalCall {
         char* host = nullptr; size_t host_cap = 0;
         hipEvent_t ev = nullptr;
         bool called = false, pending = false;
-        int K = 0;                                        // the planner's max_steps at the call
-        size_t o_target = 0, o_dp = 0, o_ue = 0, o_n = 0, o_status = 0, o_side = 0, o_fs = 0, bytes = 0;      // the rows' offsets in `host`
-        size_t o_ss = 0, o_ds = 0; bool timed = false;    // the last call was a timed one: its two duration rows
+        GoalRows rows;                                    // of the last call: the planner's max_steps, timed or not, where its rows lie in `host`
         std::vector<int> owed, merge, decided;
         int wait() {
             if (pending) { WCQP_HIP_TRY(hipEventSynchronize(ev)); pending = false; }
@@ -151,16 +180,9 @@ struct wcqp_tick_s {
     int settle() {
         if (const int rc = goal.wait(); rc != WCQP_OK) return rc;
         if (goal.owed.empty()) return WCQP_OK;
-        const int32_t* n = reinterpret_cast<const int32_t*>(goal.host + goal.o_n);
-        for (int i : goal.owed) gp.n_steps[i] = n[i];
-        if (goal.timed) {
-            const int32_t* ss = reinterpret_cast<const int32_t*>(goal.host + goal.o_ss);
-            const int32_t* ds = reinterpret_cast<const int32_t*>(goal.host + goal.o_ds);
-            for (int i : goal.owed) {
-                gp.dur[i].resize(2 * (size_t)n[i]);
-                for (int k = 0; k < n[i]; ++k) { gp.dur[i][2 * k] = ss[(size_t)i * goal.K + k]; gp.dur[i][2 * k + 1] = ds[(size_t)i * goal.K + k]; }
-            }
-        }
+        const GoalRows& r = goal.rows;
+        const int32_t* n = r.at<int32_t>(goal.host, r.n);
+        for (int i : goal.owed) gp.set_steps((size_t)i, n[i], r.at<int32_t>(goal.host, r.ss) + (size_t)i * r.K, r.at<int32_t>(goal.host, r.ds) + (size_t)i * r.K);
         goal.owed.clear();
         return WCQP_OK;
     }

@@ -1,6 +1,8 @@
 // The trajectories of a tick handle (tick_handle.h; tick.hip holds the rest of it): planned ones uploaded per stage (wcqp_tick_upload of a
 // planned handle), walks generated from footsteps and replanned at a merge stage - from the caller's footsteps or from goals, planned here
 // on the device (plan_gen.hip holds the plan kernels, unicycle_device.h the planner) -, the streamed stage of the next tick, and the plan read back.  See include/wcqp.h for the contract.
+// Timed and untimed generated plans take one path: what the host decides on a plan's timeline - merge stages, set counts, spans, the bound
+// on stage indices - is goal_merge.h's wcqp_goal::Timeline, built by GenPlan::timeline(i) (the plan in force) or list_timeline (a caller's list).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -21,6 +23,8 @@ PlanRect plan_rect(const wcqp_tick_s* h) {
     for (int k = 0; k < 8; ++k) r.v[k] = h->p.foot_rect[k];
     return r;
 }
+// (the hull build below - foot_points of the feet in contact, then hull_rows - stands again in tick_desired_kernel: as one device function
+// both kernels' instruction streams move - DESIGN §8.23)
 __global__ void __launch_bounds__(128) plan_hull_sets_kernel(int n, PlanRect rect, const double* __restrict__ rec, const long long* __restrict__ at,
                                       const int* __restrict__ code, double* __restrict__ A, double* __restrict__ b, int* __restrict__ nc) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -168,18 +172,11 @@ bool footsteps_valid(size_t i, int K, const int32_t* n_steps, const uint8_t* sid
     return true;
 }
 
-// Valid durations of robot i's footsteps (the timed calls): ss >= 1 and ds >= 1 for every step it takes
-bool durations_valid(size_t i, int K, const int32_t* n_steps, const wcqp_tick_step_timing* tm) {
-    for (int k = 0; k < n_steps[i]; ++k)
-        if (tm->ss_ticks[i * K + k] < 1 || tm->ds_ticks[i * K + k] < 1) return false;
-    return true;
-}
-// ... and the stages they occupy behind the first double support, the last step's double support as the plan resolves it
-long long durations_span(size_t i, int K, const int32_t* n_steps, const wcqp_tick_step_timing* tm, int final_ds) {
-    long long sum = 0;
-    const int n = n_steps[i];
-    for (int k = 0; k < n; ++k) sum += (long long)tm->ss_ticks[i * K + k] + (k == n - 1 && final_ds > 0 ? final_ds : tm->ds_ticks[i * K + k]);
-    return sum;
+// The timeline (goal_merge.h) of robot i's footstep list, n of at most K steps (a valid list: see above) from stage `origin` behind a first
+// double support of first_ds stages: on the caller's per-step rows tm [B][K] (the timed calls), or - tm NULL - on the common (ss, ds)
+wcqp_goal::Timeline list_timeline(size_t i, int K, int origin, int first_ds, int n, const wcqp_tick_step_timing* tm, int ss, int ds) {
+    if (!tm) return wcqp_goal::Timeline::uniform(origin, first_ds, n, ss, ds);
+    return wcqp_goal::Timeline::per_step(origin, first_ds, n, tm->ss_ticks + i * K, tm->ds_ticks + i * K, 1);
 }
 
 // What every pass of plan_gen.hip takes of a handle whose GenPlan scalars are in place, for lists of at most K steps per robot; the caller
@@ -310,17 +307,21 @@ struct GoalPlanDev {
     wcqp_unicycle::UniRows out;
     int n_robots, traj_len;
 };
-__global__ __launch_bounds__(64) void goal_plan_kernel(GoalPlanDev a) {
-    const long raw = (long)blockIdx.x * 64 + threadIdx.x;
-    const bool live = raw < a.n_robots;
-    const size_t i = (size_t)a.robots[live ? raw : (long)a.n_robots - 1];
+// robot i's start: the soles of plan record M_i, the goal, and the side that swings first
+__device__ __forceinline__ wcqp_unicycle::UniStart goal_start(const GoalPlanDev& a, size_t i) {
     const double* r = a.rec + (i * (size_t)a.traj_len + (size_t)a.origin[i]) * (size_t)kPlanRec;
     const unsigned flags = (unsigned)r[kPlanFlags - kPlanRec];
     int sw = a.side_in[i];
     if (sw == WCQP_TICK_SIDE_AUTO) sw = (flags & 4u) ? 0 : 1;
     const double *l = r + kPlanLeft, *q = r + kPlanRight;
-    const wcqp_unicycle::UniStart in{l[0], l[1], l[3], l[6], q[0], q[1], q[3], q[6], a.goal[i * 2], a.goal[i * 2 + 1], sw};
-    if (live) a.first_side[i] = (unsigned char)sw;
+    return {l[0], l[1], l[3], l[6], q[0], q[1], q[3], q[6], a.goal[i * 2], a.goal[i * 2 + 1], sw};
+}
+__global__ __launch_bounds__(64) void goal_plan_kernel(GoalPlanDev a) {
+    const long raw = (long)blockIdx.x * 64 + threadIdx.x;
+    const bool live = raw < a.n_robots;
+    const size_t i = (size_t)a.robots[live ? raw : (long)a.n_robots - 1];
+    const wcqp_unicycle::UniStart in = goal_start(a, i);
+    if (live) a.first_side[i] = (unsigned char)in.sw;
     wcqp_unicycle::plan_robot(a.p, in, a.out, i, live);
 }
 
@@ -336,27 +337,13 @@ __global__ __launch_bounds__(64) void goal_plan_timed_kernel(GoalPlanTimedDev t)
     const long raw = (long)blockIdx.x * 64 + threadIdx.x;
     const bool live = raw < a.n_robots;
     const size_t i = (size_t)a.robots[live ? raw : (long)a.n_robots - 1];
-    const double* r = a.rec + (i * (size_t)a.traj_len + (size_t)a.origin[i]) * (size_t)kPlanRec;
-    const unsigned flags = (unsigned)r[kPlanFlags - kPlanRec];
-    int sw = a.side_in[i];
-    if (sw == WCQP_TICK_SIDE_AUTO) sw = (flags & 4u) ? 0 : 1;
-    const double *l = r + kPlanLeft, *q = r + kPlanRight;
-    const wcqp_unicycle::UniStart in{l[0], l[1], l[3], l[6], q[0], q[1], q[3], q[6], a.goal[i * 2], a.goal[i * 2 + 1], sw};
-    if (live) a.first_side[i] = (unsigned char)sw;
+    const wcqp_unicycle::UniStart in = goal_start(a, i);
+    if (live) a.first_side[i] = (unsigned char)in.sw;
     wcqp_unicycle::plan_robot_timed(a.p, t.tm, in, a.out, i, live);
 }
 
-// the plan in force of robot i, and the stage below which the enqueued ticks have consumed it: a resident plan's tick whose stage has
-// been staged counts as enqueued, its live record holds that stage (gp.n_steps: settled by the caller)
-wcqp_goal::PlanInForce plan_in_force(const wcqp_tick_s* h, size_t i) {
-    const auto& gp = h->gp;
-    return {gp.origin[i], gp.first_ds[i], gp.n_steps[i], gp.ss, gp.ds};
-}
-// a TIMED plan in force, on robot i's own timeline (gp.n_steps and gp.dur: settled by the caller)
-wcqp_goal::TimedPlanInForce timed_plan_in_force(const wcqp_tick_s* h, size_t i) {
-    const auto& gp = h->gp;
-    return {gp.origin[i], gp.first_ds[i], gp.n_steps[i], gp.dur[i].data()};
-}
+// the stage below which the enqueued ticks have consumed the plans in force (gp.timeline(i): settled by the caller): a resident plan's tick
+// whose stage has been staged counts as enqueued, its live record holds that stage
 int consumed_stages(const wcqp_tick_s* h) { return h->ticks_enqueued + (h->plan_staged ? 1 : 0); }
 
 // What a replan needs of the host per call, for footsteps from the caller's lists and from goals alike: per robot the merge stage (-1: it
@@ -366,43 +353,16 @@ struct ReplanCall {
     explicit ReplanCall(size_t B) : merge(B, -1), keep(B, 0) {}
 };
 
-// Robot i joins the call at merge stage M (already found allowed: wcqp_goal::merge_allowed).  n_new: the steps of its new plan, or -1 where
-// the device plans them.  Its surviving sets are those of stages <= M (a set of stage M itself is built from the feet the new plan starts
-// from); the new plan's sets follow them in the robot's `cap` slots.  That they fit needs no n_new: cap (wcqp_tick_upload_footsteps)
-// bounds the steps that START at a stage <= max_ticks for ANY footstep list - a step occupies ss + 1 stages or more - and the stitched
-// plan is one such list, so the count below is a check of the arithmetic where n_new is known and is not evaluated where it is not.
-// A timed plan (tm: the new steps' durations, [B][K]; unread with n_new = -1) counts both on the per-step timelines, the surviving sets
-// from gp.dur; its cap (wcqp_tick_upload_footsteps_timed) already counts a step as two stages - one of single, one of double support -
-// for ANY footstep list, so the steps and durations the device chooses fit as well.
-int replan_admit(const wcqp_tick_s* h, size_t i, int M, int fd, int n_new, ReplanCall& c, const wcqp_tick_step_timing* tm = nullptr, int K = 0) {
+// Robot i joins the call at merge stage M (already found allowed: wcqp_goal::merge_allowed).  fresh: the timeline of its new plan, from M
+// on - without steps where the device plans them.  Its surviving sets are those of stages <= M (a set of stage M itself is built from
+// the feet the new plan starts from); the new plan's sets follow them in the robot's `cap` slots.  That they fit needs no new steps: cap
+// (upload_footsteps) bounds the steps that START at a stage <= max_ticks for ANY footstep list - an untimed step occupies ss + 1 stages or
+// more, a timed one a stage of single and a stage of double support - and the stitched plan is one such list, so the count below is a
+// check of the arithmetic where the new steps are known, and the steps and durations the device chooses fit as well.
+int replan_admit(const wcqp_tick_s* h, size_t i, int M, const wcqp_goal::Timeline& fresh_plan, ReplanCall& c) {
     const auto& gp = h->gp;
-    const int per = gp.ss + gp.ds, O = gp.origin[i], fo = gp.first_ds[i], no = gp.n_steps[i];
-    int c0 = gp.keep[i];
-    const int reach = M < h->p.max_ticks ? M : h->p.max_ticks;
-    int fresh = 0;
-    if (gp.timed) {
-        long long s_k = (long long)O + fo;
-        for (int k = 0; k < no; ++k) {
-            const int ss = gp.dur[i][2 * k];
-            c0 += (s_k <= reach ? 1 : 0) + (s_k + ss <= reach ? 1 : 0);
-            s_k += (long long)ss + gp.dur[i][2 * k + 1];
-        }
-        s_k = (long long)M + fd;
-        for (int k = 0; k < n_new; ++k) {
-            const int ss = tm->ss_ticks[i * K + k];
-            fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + ss <= h->p.max_ticks ? 1 : 0);
-            s_k += (long long)ss + tm->ds_ticks[i * K + k];
-        }
-    } else {
-        for (int k = 0; k < no; ++k) {
-            const long long s_k = (long long)O + fo + (long long)k * per;
-            c0 += (s_k <= reach ? 1 : 0) + (s_k + gp.ss <= reach ? 1 : 0);
-        }
-        for (int k = 0; k < n_new; ++k) {
-            const long long s_k = (long long)M + fd + (long long)k * per;
-            fresh += (s_k <= h->p.max_ticks ? 1 : 0) + (s_k + gp.ss <= h->p.max_ticks ? 1 : 0);
-        }
-    }
+    const int c0 = gp.keep[i] + gp.timeline(i).sets_up_to(M < h->p.max_ticks ? M : h->p.max_ticks);
+    const int fresh = fresh_plan.sets_up_to(h->p.max_ticks);
     if (c0 < 1 || c0 + fresh > gp.cap) return WCQP_E_INVALID;      // (cannot happen: see cap in wcqp_tick_upload_footsteps)
     c.merge[i] = M; c.keep[i] = c0;
     c.robots.push_back((int)i);
@@ -412,41 +372,44 @@ int replan_admit(const wcqp_tick_s* h, size_t i, int M, int fd, int n_new, Repla
 }
 
 // where the footsteps of a replan come from: the caller's lists (wcqp_tick_replan_footsteps), or goals the device plans from
-// (wcqp_tick_replan_goals: goal [B][2], first_side [B] or NULL for WCQP_TICK_SIDE_AUTO everywhere, the planner's parameters)
+// (wcqp_tick_replan_goals: goal [B][2], first_side [B] or NULL for WCQP_TICK_SIDE_AUTO everywhere, the planner's parameters, the layout
+// of the call's result rows)
 struct ReplanSource {
     const wcqp_tick_replan* lists;
     const double* goal; const uint8_t* first_side; const wcqp_unicycle::UniPar* par;
+    const wcqp_tick_s::GoalRows* rows;
     const wcqp_tick_step_timing* tm = nullptr;      // with lists, on a timed plan: the new steps' durations
     const wcqp_unicycle::UniTiming* utm = nullptr;  // with goals, on a timed plan: the timed planner's range and score (its rows: set here)
 };
 
 // Everything behind the checks, for a call that lists a robot at least: the call's device block - what the host hands over first (one
 // copy, taken NOW, once the previous replan has left the block), then what the kernels write for each other -, the kernels on `st` behind
-// the ticks already enqueued, the guard, and the plan in force of the listed robots.  From goals, goal_plan_kernel runs first and the
-// replan kernels' n_steps / side / target aim at the rows it writes; the result rows travel back in one copy, with an event behind it,
-// and gp.n_steps of the listed robots is owed until then (tick_handle.h: GoalCall).  From goals on a timed plan, goal_plan_timed_kernel
-// also writes the two duration rows into the result rows, the timed replan kernels' PlanTimes aim at them, and gp.dur of the listed robots
-// is owed with gp.n_steps.  Synchronises with nothing but the block's own wait.
+// the ticks already enqueued, the guard, and the plan in force of the listed robots.  The replan kernels read their footstep rows -
+// n_steps, side, target, on a timed plan ss_k and ds_k - at `steps`: the caller's, staged in the block's front, or the result rows
+// goal_plan_kernel (timed: goal_plan_timed_kernel) writes ahead of them.  Those travel back in one copy, with an event behind it, and
+// the listed robots' step counts - and durations - are owed until then (tick_handle.h: GoalCall).  Synchronises with nothing but the
+// block's own wait.
 int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const ReplanSource& src, hipStream_t st) {
     const TickDev& d = h->d;
     auto& gp = h->gp;
     auto& gc = h->goal;
-    const bool goals = src.lists == nullptr, timed = src.tm || src.utm;
+    const bool goals = src.lists == nullptr;
     const int cap = gp.cap;
     const size_t B = (size_t)d.batch, BK = B * (size_t)K, nr = c.robots.size(), nt = c.tiles.size() / 2, nslots = B * (size_t)cap;
-    // the result rows of a goal call, one contiguous run: doubles, then the 32-bit rows, then the bytes
-    const size_t r_target = 0, r_dp = r_target + BK * 24, r_ue = r_dp + B * 16, r_n = r_ue + B * 24, r_status = r_n + B * 4, r_ss = r_status + B * 4,
-                 r_ds = r_ss + (src.utm ? BK * 4 : 0), r_side = r_ds + (src.utm ? BK * 4 : 0), r_fs = r_side + BK, r_bytes = r_fs + B;
+    const wcqp_tick_s::GoalRows gr = goals ? *src.rows : wcqp_tick_s::GoalRows{};
     size_t off = 0;
     auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
     const size_t o_org = carve(B * 4), o_base = carve(B * 4), o_rob = carve(nr * 4), o_tile = carve(nt * 8);
-    const size_t o_n = goals ? 0 : carve(B * 4), o_side = goals ? 0 : carve(BK), o_tg = goals ? 0 : carve(BK * 24);
+    struct StepRows { size_t n, side, target, ss, ds; } steps{};
+    if (!goals) { steps.n = carve(B * 4); steps.side = carve(BK); steps.target = carve(BK * 24); }
     const size_t o_goal = goals ? carve(B * 16) : 0, o_fsin = goals ? carve(B) : 0;
-    const size_t o_ssk = src.tm ? carve(BK * 4) : 0, o_dsk = src.tm ? carve(BK * 4) : 0;
+    if (src.tm) { steps.ss = carve(BK * 4); steps.ds = carve(BK * 4); }
     const size_t front = off;
-    const size_t o_res = goals ? carve(r_bytes) : 0;
+    const size_t o_res = goals ? carve(gr.bytes) : 0;
+    if (goals) steps = StepRows{o_res + gr.n, o_res + gr.side, o_res + gr.target, o_res + gr.ss, o_res + gr.ds};
     const size_t o_tab = carve(B * (size_t)(K + 1) * kFpRec * 8), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
-    const size_t o_start = timed ? carve(B * (size_t)(K + 1) * 4) : 0;
+    size_t o_start = 0;
+    if (gp.timed) o_start = carve(B * (size_t)(K + 1) * 4);       // (PlanTimes::start)
     std::vector<char> blob(front, 0);
     {
         int* org = reinterpret_cast<int*>(blob.data() + o_org); int* base = reinterpret_cast<int*>(blob.data() + o_base);
@@ -457,10 +420,10 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
         }
         std::memcpy(blob.data() + o_rob, c.robots.data(), nr * 4); std::memcpy(blob.data() + o_tile, c.tiles.data(), nt * 8);
         if (!goals) {
-            int* nn = reinterpret_cast<int*>(blob.data() + o_n);
+            int* nn = reinterpret_cast<int*>(blob.data() + steps.n);
             for (size_t i = 0; i < B; ++i) nn[i] = c.merge[i] != -1 ? src.lists->n_steps[i] : 0;
-            if (BK > 0) { std::memcpy(blob.data() + o_side, src.lists->side, BK); std::memcpy(blob.data() + o_tg, src.lists->target, BK * 24); }
-            if (src.tm && BK > 0) { std::memcpy(blob.data() + o_ssk, src.tm->ss_ticks, BK * 4); std::memcpy(blob.data() + o_dsk, src.tm->ds_ticks, BK * 4); }
+            if (BK > 0) { std::memcpy(blob.data() + steps.side, src.lists->side, BK); std::memcpy(blob.data() + steps.target, src.lists->target, BK * 24); }
+            if (src.tm && BK > 0) { std::memcpy(blob.data() + steps.ss, src.tm->ss_ticks, BK * 4); std::memcpy(blob.data() + steps.ds, src.tm->ds_ticks, BK * 4); }
         } else {
             // (a goal of a robot that keeps its plan may be anything, a NaN too: its row is zero here and no lane reads it)
             double* gl = reinterpret_cast<double*>(blob.data() + o_goal);
@@ -471,11 +434,11 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
     }
     if (goals) {      // the pinned rows the results come back into (the previous call's have been folded in: the caller settled)
         if (!gc.ev) WCQP_HIP_TRY(hipEventCreateWithFlags(&gc.ev, hipEventDisableTiming));
-        if (gc.host_cap < r_bytes) {
+        if (gc.host_cap < gr.bytes) {
             if (gc.host) (void)hipHostFree(gc.host);
             gc.host = nullptr; gc.host_cap = 0;
-            if (hipHostMalloc(reinterpret_cast<void**>(&gc.host), r_bytes, hipHostMallocDefault) != hipSuccess) return WCQP_E_NOMEM;
-            gc.host_cap = r_bytes;
+            if (hipHostMalloc(reinterpret_cast<void**>(&gc.host), gr.bytes, hipHostMallocDefault) != hipSuccess) return WCQP_E_NOMEM;
+            gc.host_cap = gr.bytes;
         }
     }
     if (const int rc = h->rp.take(h->copy_stream, blob.data(), front, off); rc != WCQP_OK) return rc;
@@ -485,26 +448,26 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
     g.origin = reinterpret_cast<const int*>(buf + o_org);
     g.set_base = reinterpret_cast<const int*>(buf + o_base); g.robots = reinterpret_cast<const int*>(buf + o_rob);
     g.tiles = reinterpret_cast<const int2*>(buf + o_tile);
-    g.n_steps = reinterpret_cast<const int*>(goals ? res + r_n : buf + o_n);
-    g.side = reinterpret_cast<const unsigned char*>(goals ? res + r_side : buf + o_side);
-    g.target = reinterpret_cast<const double*>(goals ? res + r_target : buf + o_tg);
+    g.n_steps = reinterpret_cast<const int*>(buf + steps.n);
+    g.side = reinterpret_cast<const unsigned char*>(buf + steps.side);
+    g.target = reinterpret_cast<const double*>(buf + steps.target);
     g.table = reinterpret_cast<double*>(buf + o_tab);
     g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = reinterpret_cast<int*>(buf + o_code);
     g.h0 = d.com_h0.get(); g.n_robots = (int)nr; g.n_tiles = (int)nt; g.first_ds = fd;
     // in the caller's stream order, behind the ticks already enqueued: no pointer a tick or a captured graph holds changes, and the set
     // slots written are those past each robot's surviving ones, which no stage below its merge stage names
     if (goals) {
-        WCQP_HIP_TRY(hipMemsetAsync(res, 0, r_bytes, st));      // (the rows of robots without a lane read back as zeros)
+        WCQP_HIP_TRY(hipMemsetAsync(res, 0, gr.bytes, st));      // (the rows of robots without a lane read back as zeros)
         GoalPlanDev a{};
         a.p = *src.par; a.rec = h->plan_rec; a.origin = g.origin; a.robots = g.robots;
         a.goal = reinterpret_cast<const double*>(buf + o_goal); a.side_in = reinterpret_cast<const unsigned char*>(buf + o_fsin);
-        a.first_side = reinterpret_cast<unsigned char*>(res + r_fs);
-        a.out = wcqp_unicycle::UniRows{reinterpret_cast<int32_t*>(res + r_n), reinterpret_cast<int32_t*>(res + r_status), reinterpret_cast<uint8_t*>(res + r_side),
-                                       reinterpret_cast<double*>(res + r_target), reinterpret_cast<double*>(res + r_dp), reinterpret_cast<double*>(res + r_ue)};
+        a.first_side = gr.at<unsigned char>(res, gr.fs);
+        a.out = wcqp_unicycle::UniRows{gr.at<int32_t>(res, gr.n), gr.at<int32_t>(res, gr.status), gr.at<uint8_t>(res, gr.side),
+                                       gr.at<double>(res, gr.target), gr.at<double>(res, gr.dp), gr.at<double>(res, gr.ue)};
         a.n_robots = (int)nr; a.traj_len = d.traj_len;
         if (src.utm) {
             GoalPlanTimedDev t{a, *src.utm};
-            t.tm.ss_ticks = reinterpret_cast<int32_t*>(res + r_ss); t.tm.ds_ticks = reinterpret_cast<int32_t*>(res + r_ds);
+            t.tm.ss_ticks = gr.at<int32_t>(res, gr.ss); t.tm.ds_ticks = gr.at<int32_t>(res, gr.ds);
             hipLaunchKernelGGL(goal_plan_timed_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, st, t);
         } else {
             hipLaunchKernelGGL(goal_plan_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, st, a);
@@ -512,34 +475,24 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
         WCQP_HIP_TRY(hipGetLastError());
     }
     WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
-    if (timed) {
-        const PlanGenTimedDev t{g, PlanTimes{reinterpret_cast<const int*>(src.utm ? res + r_ss : buf + o_ssk), reinterpret_cast<const int*>(src.utm ? res + r_ds : buf + o_dsk),
+    if (gp.timed) {
+        const PlanGenTimedDev t{g, PlanTimes{reinterpret_cast<const int*>(buf + steps.ss), reinterpret_cast<const int*>(buf + steps.ds),
                                              reinterpret_cast<int*>(buf + o_start), gp.final_ds}};
-        if (const int rc = wcqp::plan_replan_timed_enqueue(t, st); rc != WCQP_OK) return rc;
+        if (const int rc = wcqp::plan_replan_enqueue(t, st); rc != WCQP_OK) return rc;
     } else if (const int rc = wcqp::plan_replan_enqueue(g, st); rc != WCQP_OK) return rc;
     hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
                        h->set_A, h->set_b, h->set_nc);
     WCQP_HIP_TRY(hipGetLastError());
     if (goals) {
-        WCQP_HIP_TRY(hipMemcpyAsync(gc.host, res, r_bytes, hipMemcpyDeviceToHost, st));
+        WCQP_HIP_TRY(hipMemcpyAsync(gc.host, res, gr.bytes, hipMemcpyDeviceToHost, st));
         WCQP_HIP_TRY(hipEventRecord(gc.ev, st));
     }
     if (const int rc = h->rp.guard(st); rc != WCQP_OK) return rc;
     for (int i : c.robots) {
         gp.origin[i] = c.merge[i]; gp.first_ds[i] = fd; gp.keep[i] = c.keep[i];
-        if (!goals) gp.n_steps[i] = src.lists->n_steps[i];
-        if (src.tm) {
-            gp.dur[i].resize(2 * (size_t)gp.n_steps[i]);
-            for (int k = 0; k < gp.n_steps[i]; ++k) {
-                gp.dur[i][2 * k] = src.tm->ss_ticks[(size_t)i * K + k]; gp.dur[i][2 * k + 1] = src.tm->ds_ticks[(size_t)i * K + k];
-            }
-        }
+        if (!goals) gp.set_steps((size_t)i, src.lists->n_steps[i], src.tm ? src.tm->ss_ticks + (size_t)i * K : nullptr, src.tm ? src.tm->ds_ticks + (size_t)i * K : nullptr);
     }
-    if (goals) {
-        gc.pending = true; gc.owed = c.robots; gc.K = K;
-        gc.o_target = r_target; gc.o_dp = r_dp; gc.o_ue = r_ue; gc.o_n = r_n; gc.o_status = r_status; gc.o_side = r_side; gc.o_fs = r_fs; gc.bytes = r_bytes;
-        gc.o_ss = r_ss; gc.o_ds = r_ds; gc.timed = src.utm != nullptr;
-    }
+    if (goals) { gc.pending = true; gc.owed = c.robots; gc.rows = gr; }
     return WCQP_OK;
 }
 
@@ -565,7 +518,7 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
     // (a timed plan keeps the caller's final_ds_ticks: 0 stands for every robot's own last ds)
     const int final_ds = tm || steps->final_ds_ticks > 0 ? steps->final_ds_ticks : steps->ds_ticks;
     const long long per = (long long)steps->ss_ticks + steps->ds_ticks;
-    if (!tm && (long long)steps->first_ds_ticks + (long long)K * per + final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    if (!tm && !wcqp_goal::stages_fit(steps->first_ds_ticks, wcqp_goal::span_bound(K, per, final_ds))) return WCQP_E_INVALID;
     auto finite = [](const double* a, size_t n) { bool ok = true; for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(a[k]); return ok; };
     if (!std::isfinite(steps->lift) || !finite(steps->zmp_delta_left, 2) || !finite(steps->zmp_delta_right, 2)) return WCQP_E_INVALID;
     if (!finite(in->q0, B * kDof) || !finite(in->com0, B * 2) || (in->dcm0 && !finite(in->dcm0, B * 2)) || (in->u_init && !finite(in->u_init, B * 2)))
@@ -579,8 +532,9 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
     const size_t ns = B * (size_t)cap;
     for (size_t i = 0; i < B; ++i) {
         if (!footsteps_valid(i, K, steps->n_steps, steps->side, steps->target)) return WCQP_E_INVALID;
-        if (tm && (!durations_valid(i, K, steps->n_steps, tm) ||
-                   steps->first_ds_ticks + durations_span(i, K, steps->n_steps, tm, final_ds) > (1ll << 30))) return WCQP_E_INVALID;
+        // (the timed plan's own durations and stage indices; an untimed plan's were bounded above, for any list of K steps)
+        const wcqp_goal::Timeline tl = list_timeline(i, K, 0, steps->first_ds_ticks, steps->n_steps[i], tm, steps->ss_ticks, steps->ds_ticks);
+        if (tm && (!tl.durations_valid() || !wcqp_goal::stages_fit(tl.first_step(), tl.span(final_ds)))) return WCQP_E_INVALID;
         if (!finite(in->state0 + i * kStateLen + 24, 24) || !std::isfinite(in->state0[i * kStateLen + 68])) return WCQP_E_INVALID;
         set_base[i] = (int)(i * (size_t)cap);
     }
@@ -593,9 +547,6 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
         auto& gp = h->gp;
         gp.ss = tm ? 0 : steps->ss_ticks; gp.ds = tm ? 0 : steps->ds_ticks; gp.final_ds = final_ds; gp.cap = cap; gp.lift = steps->lift;
         gp.timed = tm != nullptr;
-        gp.dur.assign(tm ? B : 0, std::vector<int>());
-        for (size_t i = 0; tm && i < B; ++i)
-            for (int k = 0; k < steps->n_steps[i]; ++k) { gp.dur[i].push_back(tm->ss_ticks[i * K + k]); gp.dur[i].push_back(tm->ds_ticks[i * K + k]); }
         for (int k = 0; k < 2; ++k) { gp.delta[0][k] = steps->zmp_delta_left[k]; gp.delta[1][k] = steps->zmp_delta_right[k]; }
     }
     // the footsteps, the table and the set table: device memory of this call
@@ -632,7 +583,7 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
     g.n_steps = d_n; g.side = d_side; g.target = d_tg; g.set_base = d_base; g.table = d_tab; g.set_at = d_at; g.set_code = d_code;
     g.first_ds = steps->first_ds_ticks;
     for (hipEvent_t& e : h->gen_ev) if (!e) WCQP_HIP_TRY(hipEventCreate(&e));
-    int rc = tm ? wcqp::plan_gen_timed_enqueue(PlanGenTimedDev{g, PlanTimes{d_ssk, d_dsk, d_start, final_ds}}, nullptr, h->gen_ev[0], h->gen_ev[1])
+    int rc = tm ? wcqp::plan_gen_enqueue(PlanGenTimedDev{g, PlanTimes{d_ssk, d_dsk, d_start, final_ds}}, nullptr, h->gen_ev[0], h->gen_ev[1])
                 : wcqp::plan_gen_enqueue(g, nullptr, h->gen_ev[0], h->gen_ev[1]);
     if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);      // (synchronises)
     if (rc != WCQP_OK) return rc;
@@ -642,7 +593,8 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
     {   // per robot the plan in force
         auto& gp = h->gp;
         gp.origin.assign(B, 0); gp.first_ds.assign(B, steps->first_ds_ticks); gp.keep.assign(B, 1);
-        gp.n_steps.assign(steps->n_steps, steps->n_steps + B);
+        gp.n_steps.assign(B, 0); gp.dur.assign(tm ? B : 0, std::vector<int>());
+        for (size_t i = 0; i < B; ++i) gp.set_steps(i, steps->n_steps[i], tm ? tm->ss_ticks + i * K : nullptr, tm ? tm->ds_ticks + i * K : nullptr);
         h->rp.pending = false; h->goal.pending = false; h->goal.owed.clear();      // (the device was synchronised above)
     }
     WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
@@ -664,17 +616,19 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
     return wcqp::upload_state(h, &eff, 2);
 }
 
-// wcqp_tick_replan_footsteps (tm NULL, an untimed plan) and wcqp_tick_replan_footsteps_timed (a timed one)
-int replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_step_timing* tm, bool timed, void* stream) {
-    if (!h || !rp || (timed && !tm)) return WCQP_E_INVALID;
+// wcqp_tick_replan_footsteps (tm NULL, an untimed plan) and wcqp_tick_replan_footsteps_timed (tm: the new steps' durations, a timed one)
+int replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_step_timing* tm, void* stream) {
+    if (!h || !rp) return WCQP_E_INVALID;
     if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
-    if (h->gp.timed != timed) return WCQP_E_UNSUPPORTED;           // (a plan is timed or not from its upload on)
+    const auto& gp = h->gp;
+    if (gp.timed != (tm != nullptr)) return WCQP_E_UNSUPPORTED;           // (a plan is timed or not from its upload on)
     const size_t B = (size_t)h->d.batch;
-    const int K = rp->max_steps, T = h->d.traj_len, fd = rp->first_ds_ticks, per = h->gp.ss + h->gp.ds;
-    // everything is checked here, in closed form, before anything changes: a refused call leaves the handle exactly as it was
+    const int K = rp->max_steps, T = h->d.traj_len, fd = rp->first_ds_ticks;
+    // everything is checked here, on the host, before anything changes: a refused call leaves the handle exactly as it was
     if (!rp->merge_stage || !rp->n_steps || K < 0 || (K > 0 && (!rp->side || !rp->target)) || fd < 1) return WCQP_E_INVALID;
     if (tm && K > 0 && (!tm->ss_ticks || !tm->ds_ticks)) return WCQP_E_INVALID;
-    if (!tm && (long long)T + fd + (long long)K * per + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;      // (stage indices are 32-bit)
+    const long long last = (long long)T + fd;       // (no new plan starts its steps later)
+    if (!tm && !wcqp_goal::stages_fit(last, wcqp_goal::span_bound(K, (long long)gp.ss + gp.ds, gp.final_ds))) return WCQP_E_INVALID;
     if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (the step counts, and on a timed plan the durations, a goal call still owes)
     ReplanCall c(B);
     for (size_t i = 0; i < B; ++i) {
@@ -683,35 +637,37 @@ int replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_
         // stage 0 is the initial state's, stages the enqueued ticks have consumed stay (within one wcqp_tick_run call the kernel reads a stage
         // ahead, between calls nothing is ahead), a plan is cut only behind its own origin, and the merge stage has both feet in contact in
         // the plan in force: not inside one of its single supports
-        if (!(tm ? wcqp_goal::merge_allowed(timed_plan_in_force(h, i), M, consumed_stages(h), T) : wcqp_goal::merge_allowed(plan_in_force(h, i), M, consumed_stages(h), T)))
-            return WCQP_E_INVALID;
+        if (!wcqp_goal::merge_allowed(gp.timeline(i), M, consumed_stages(h), T)) return WCQP_E_INVALID;
         if (!footsteps_valid(i, K, rp->n_steps, rp->side, rp->target)) return WCQP_E_INVALID;
-        if (tm && (!durations_valid(i, K, rp->n_steps, tm) || (long long)T + fd + durations_span(i, K, rp->n_steps, tm, h->gp.final_ds) > (1ll << 30)))
-            return WCQP_E_INVALID;
-        if (const int rc = replan_admit(h, i, M, fd, rp->n_steps[i], c, tm, K); rc != WCQP_OK) return rc;
+        const wcqp_goal::Timeline fresh = list_timeline(i, K, M, fd, rp->n_steps[i], tm, gp.ss, gp.ds);
+        if (tm && (!fresh.durations_valid() || !wcqp_goal::stages_fit(last, fresh.span(gp.final_ds)))) return WCQP_E_INVALID;
+        if (const int rc = replan_admit(h, i, M, fresh, c); rc != WCQP_OK) return rc;
     }
     if (c.robots.empty()) return WCQP_OK;
-    return replan_enqueue(h, c, K, fd, ReplanSource{rp, nullptr, nullptr, nullptr, tm}, (hipStream_t)stream);
+    return replan_enqueue(h, c, K, fd, ReplanSource{rp, nullptr, nullptr, nullptr, nullptr, tm}, (hipStream_t)stream);
 }
 
-// wcqp_tick_replan_goals (tm NULL, an untimed plan) and wcqp_tick_replan_goals_timed (a timed one)
-int replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_timing* tm, bool timed, const wcqp_tick_goals* gl, void* stream) {
-    if (!h || !planner || !gl || !gl->goal || (timed && !tm)) return WCQP_E_INVALID;
+// wcqp_tick_replan_goals (tm NULL, an untimed plan) and wcqp_tick_replan_goals_timed (tm: the timed planner's range and score, a timed one)
+int replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_timing* tm, const wcqp_tick_goals* gl, void* stream) {
+    if (!h || !planner || !gl || !gl->goal) return WCQP_E_INVALID;
     if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
-    // (a plan is timed or not from its upload on: the untimed merge-point rule and planner kernel know one common timing, the timed ones none)
-    if (h->gp.timed != timed) return WCQP_E_UNSUPPORTED;
+    const auto& gp = h->gp;
+    // (a plan is timed or not from its upload on: the untimed planner kernel knows one common timing, the timed one none)
+    if (gp.timed != (tm != nullptr)) return WCQP_E_UNSUPPORTED;
     const wcqp_unicycle::UniPar* par = wcqp::unicycle_par(planner);
     const size_t B = (size_t)h->d.batch;
-    const int K = par->K, T = h->d.traj_len, fd = gl->first_ds_ticks, per = h->gp.ss + h->gp.ds;
+    const int K = par->K, T = h->d.traj_len, fd = gl->first_ds_ticks;
     wcqp_unicycle::UniTiming utm{};
-    if (timed) {      // (the planner's own validation of tm; the duration rows are the call's, set where they are carved)
+    if (tm) {      // (the planner's own validation of tm; the duration rows are the call's, set where they are carved)
         int32_t rows = 0;
         if (const int rc = wcqp::unicycle_timing(planner, tm, &rows, &rows, &utm); rc != WCQP_OK) return rc;
         utm.ss_ticks = nullptr; utm.ds_ticks = nullptr;
     }
     if (fd < 1 || gl->min_lead_ticks < 0) return WCQP_E_INVALID;
-    // (stage indices are 32-bit; a timed step lasts max_step_ticks at most, and its ds <= m - 1 covers a final_ds of 0)
-    if ((long long)T + fd + (long long)K * (timed ? tm->max_step_ticks : per) + h->gp.final_ds > (1ll << 30)) return WCQP_E_INVALID;
+    // (the steps are the device's to choose: an untimed one lasts ss + ds stages, a timed one max_step_ticks at most, and its
+    // ds <= m - 1 covers a final_ds of 0)
+    const long long longest = tm ? (long long)tm->max_step_ticks : (long long)gp.ss + gp.ds;
+    if (!wcqp_goal::stages_fit((long long)T + fd, wcqp_goal::span_bound(K, longest, gp.final_ds))) return WCQP_E_INVALID;
     if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (AUTO and the checks read the step counts - and durations - of the plans in force)
     ReplanCall c(B);
     std::vector<int> taken(B, 0), decided(B, 0);
@@ -723,21 +679,23 @@ int replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_tim
         const uint8_t fs = gl->first_side ? gl->first_side[i] : (uint8_t)WCQP_TICK_SIDE_AUTO;
         if (fs > 1 && fs != WCQP_TICK_SIDE_AUTO) return WCQP_E_INVALID;
         if (!std::isfinite(gl->goal[i * 2]) || !std::isfinite(gl->goal[i * 2 + 1])) return WCQP_E_INVALID;
+        const wcqp_goal::Timeline in_force = gp.timeline(i);
         if (M == WCQP_TICK_MERGE_AUTO) {
-            M = timed ? wcqp_goal::merge_auto(timed_plan_in_force(h, i), t0, gl->min_lead_ticks, T)
-                      : wcqp_goal::merge_auto(plan_in_force(h, i), t0, gl->min_lead_ticks, T);
+            M = wcqp_goal::merge_auto(in_force, t0, gl->min_lead_ticks, T);
             if (M == wcqp_goal::kTooLate) { decided[i] = WCQP_GOAL_TOO_LATE; continue; }
-        } else if (!(timed ? wcqp_goal::merge_allowed(timed_plan_in_force(h, i), M, t0, T) : wcqp_goal::merge_allowed(plan_in_force(h, i), M, t0, T))) {
+        } else if (!wcqp_goal::merge_allowed(in_force, M, t0, T)) {
             return WCQP_E_INVALID;
         }
-        if (const int rc = replan_admit(h, i, M, fd, -1, c); rc != WCQP_OK) return rc;
+        // (the new plan's steps are the device's: none to count here)
+        if (const int rc = replan_admit(h, i, M, wcqp_goal::Timeline::uniform(M, fd, 0, 0, 0), c); rc != WCQP_OK) return rc;
         taken[i] = M;
     }
+    const auto rows = wcqp_tick_s::GoalRows::of(B, (size_t)K, tm != nullptr);
     if (!c.robots.empty())
-        if (const int rc = replan_enqueue(h, c, K, fd, ReplanSource{nullptr, gl->goal, gl->first_side, par, nullptr, timed ? &utm : nullptr}, (hipStream_t)stream); rc != WCQP_OK)
+        if (const int rc = replan_enqueue(h, c, K, fd, ReplanSource{nullptr, gl->goal, gl->first_side, par, &rows, nullptr, tm ? &utm : nullptr}, (hipStream_t)stream); rc != WCQP_OK)
             return rc;
     auto& gc = h->goal;
-    gc.called = true; gc.timed = timed; gc.K = K; gc.merge.swap(taken); gc.decided.swap(decided);
+    gc.called = true; gc.rows = rows; gc.merge.swap(taken); gc.decided.swap(decided);
     return WCQP_OK;
 }
 
@@ -754,18 +712,20 @@ int wcqp_tick_upload_footsteps_timed(wcqp_tick_t h, const wcqp_tick_inputs* in, 
     return upload_footsteps(h, in, steps, tm);
 }
 
-int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) { return replan_footsteps(h, rp, nullptr, false, stream); }
+int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream) { return replan_footsteps(h, rp, nullptr, stream); }
 
 int wcqp_tick_replan_footsteps_timed(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_step_timing* tm, void* stream) {
-    return replan_footsteps(h, rp, tm, true, stream);
+    if (!tm) return WCQP_E_INVALID;
+    return replan_footsteps(h, rp, tm, stream);
 }
 
 int wcqp_tick_replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_tick_goals* gl, void* stream) {
-    return replan_goals(h, planner, nullptr, false, gl, stream);
+    return replan_goals(h, planner, nullptr, gl, stream);
 }
 
 int wcqp_tick_replan_goals_timed(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_timing* tm, const wcqp_tick_goals* gl, void* stream) {
-    return replan_goals(h, planner, tm, true, gl, stream);
+    if (!tm) return WCQP_E_INVALID;
+    return replan_goals(h, planner, tm, gl, stream);
 }
 
 int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out) {
@@ -773,18 +733,19 @@ int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out) {
     auto& gc = h->goal;
     if (!gc.called) return WCQP_E_INVALID;
     if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (waits for that call's own event, not for the stream or the device)
-    const size_t B = (size_t)h->d.batch, K = (size_t)gc.K;
+    const auto& at = gc.rows;
+    const size_t B = (size_t)h->d.batch, K = at.K;
     for (size_t i = 0; i < B; ++i) {
         const bool dev = gc.decided[i] == 0;              // (a robot that had a lane: its rows came back)
         const char* r = gc.host;
         if (out->merge_stage) out->merge_stage[i] = gc.merge[i];
-        if (out->first_side) out->first_side[i] = dev ? (uint8_t)r[gc.o_fs + i] : 0;
-        if (out->status) out->status[i] = dev ? reinterpret_cast<const int32_t*>(r + gc.o_status)[i] : gc.decided[i];
-        if (out->n_steps) out->n_steps[i] = dev ? reinterpret_cast<const int32_t*>(r + gc.o_n)[i] : 0;
-        if (out->side && K > 0) { if (dev) std::memcpy(out->side + i * K, r + gc.o_side + i * K, K); else std::memset(out->side + i * K, 0, K); }
-        if (out->target && K > 0) { if (dev) std::memcpy(out->target + i * K * 3, r + gc.o_target + i * K * 24, K * 24); else std::memset(out->target + i * K * 3, 0, K * 24); }
-        if (out->desired_point) { if (dev) std::memcpy(out->desired_point + i * 2, r + gc.o_dp + i * 16, 16); else std::memset(out->desired_point + i * 2, 0, 16); }
-        if (out->unicycle_end) { if (dev) std::memcpy(out->unicycle_end + i * 3, r + gc.o_ue + i * 24, 24); else std::memset(out->unicycle_end + i * 3, 0, 24); }
+        if (out->first_side) out->first_side[i] = dev ? (uint8_t)r[at.fs + i] : 0;
+        if (out->status) out->status[i] = dev ? at.at<int32_t>(r, at.status)[i] : gc.decided[i];
+        if (out->n_steps) out->n_steps[i] = dev ? at.at<int32_t>(r, at.n)[i] : 0;
+        if (out->side && K > 0) { if (dev) std::memcpy(out->side + i * K, r + at.side + i * K, K); else std::memset(out->side + i * K, 0, K); }
+        if (out->target && K > 0) { if (dev) std::memcpy(out->target + i * K * 3, r + at.target + i * K * 24, K * 24); else std::memset(out->target + i * K * 3, 0, K * 24); }
+        if (out->desired_point) { if (dev) std::memcpy(out->desired_point + i * 2, r + at.dp + i * 16, 16); else std::memset(out->desired_point + i * 2, 0, 16); }
+        if (out->unicycle_end) { if (dev) std::memcpy(out->unicycle_end + i * 3, r + at.ue + i * 24, 24); else std::memset(out->unicycle_end + i * 3, 0, 24); }
     }
     return WCQP_OK;
 }
@@ -792,15 +753,16 @@ int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out) {
 int wcqp_tick_get_goal_timing(wcqp_tick_t h, int32_t* ss_ticks, int32_t* ds_ticks) {
     if (!h) return WCQP_E_INVALID;
     auto& gc = h->goal;
-    if (!gc.called || !gc.timed) return WCQP_E_INVALID;
+    if (!gc.called || !gc.rows.timed) return WCQP_E_INVALID;
     if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (waits for that call's own event, as wcqp_tick_get_goal_result)
-    const size_t B = (size_t)h->d.batch, K = (size_t)gc.K;
+    const auto& at = gc.rows;
+    const size_t B = (size_t)h->d.batch, K = at.K;
     for (size_t i = 0; i < B && K > 0; ++i) {
         const bool dev = gc.decided[i] == 0;
         for (int which = 0; which < 2; ++which) {
             int32_t* dst = which ? ds_ticks : ss_ticks;
             if (!dst) continue;
-            if (dev) std::memcpy(dst + i * K, gc.host + (which ? gc.o_ds : gc.o_ss) + i * K * 4, K * 4); else std::memset(dst + i * K, 0, K * 4);
+            if (dev) std::memcpy(dst + i * K, gc.host + (which ? at.ds : at.ss) + i * K * 4, K * 4); else std::memset(dst + i * K, 0, K * 4);
         }
     }
     return WCQP_OK;

@@ -1,11 +1,12 @@
 // Footsteps from per-robot goals (include/wcqp.h: wcqp_unicycle_*, which states the planner): the reference's setGoal path (citations
-// relative to /root/reference/modules/Walking_module):
+// relative to the reference's modules/Walking_module):
 //   src/WalkingModule.cpp:1263-1308          setPlannerInput: the goal
 //   src/TrajectoryGenerator.cpp:442-484      updateTrajectories: the unicycle's start and its desired point
 //   src/TrajectoryGenerator.cpp:114-132      the planner's parameters (plannerParams.ini)
 // One lane per robot, 64 robots per wave, one wave per workgroup; the per-robot body is unicycle_device.h's, which goal_plan_kernel
 // (tick_plan.hip) runs too.  Dead lanes of the last wave repeat the last robot and store nothing.
 // Plain vector loads and stores only; the parameters travel as the kernel argument.
+// The untimed and the timed host form share one body (plan_host): the duration rows are optional staged outputs.
 #include <cmath>
 #include <new>
 #include <vector>
@@ -32,6 +33,8 @@ struct UniTimedDev {
     UniTiming tm;
 };
 
+// (the two front ends load their robot's UniStart in the same written-out lines: as one device function the kernels' instruction streams
+// move - DESIGN §8.23)
 __global__ __launch_bounds__(64) void unicycle_kernel(UniDev a) {
     const long raw = (long)blockIdx.x * 64 + threadIdx.x;
     const bool live = raw < a.batch;
@@ -167,30 +170,6 @@ int wcqp_unicycle_plan_device(wcqp_unicycle_t h, int32_t batch, const wcqp_unicy
     return WCQP_OK;
 }
 
-int wcqp_unicycle_plan_host(wcqp_unicycle_t h, int32_t batch, const wcqp_unicycle_inputs* in, const wcqp_unicycle_outputs* out) {
-    int rc = check_call(h, batch, in, out);
-    if (rc != WCQP_OK) return rc;
-    const size_t B = (size_t)batch, K = (size_t)h->par.K;
-    rc = check_host_arrays(h->par, B, in);
-    if (rc != WCQP_OK) return rc;
-    if (batch == 0) return WCQP_OK;
-    rc = ensure_device(h);
-    if (rc != WCQP_OK) return rc;
-    // doubles first, then the 32-bit rows, then the bytes; no step rows at all when the planner keeps none (K = 0)
-    wcqp::HostStage st;
-    const auto d_l = st.in(in->left0, B * 12), d_r = st.in(in->right0, B * 12), d_g = st.in(in->goal, B * 2);
-    const auto d_t = st.out(out->target, B * K * 3, true), d_dp = st.out(out->desired_point, B * 2), d_ue = st.out(out->unicycle_end, B * 3);
-    const auto d_n = st.out(out->n_steps, B), d_st = st.out(out->status, B);
-    const auto d_fs = st.in(in->first_side, B);
-    const auto d_sd = st.out(out->side, B * K, true);
-    rc = st.upload(h->scratch);
-    if (rc != WCQP_OK) return rc;
-    const wcqp_unicycle_inputs din{st[d_l], st[d_r], st[d_g], st[d_fs]};
-    const wcqp_unicycle_outputs dout{st[d_n], st[d_sd], st[d_t], st[d_st], st[d_dp], st[d_ue]};
-    rc = wcqp_unicycle_plan_device(h, batch, &din, &dout, nullptr);
-    return rc != WCQP_OK ? rc : st.download();
-}
-
 int wcqp_unicycle_plan_timed_device(wcqp_unicycle_t h, const wcqp_unicycle_timing* tm, int32_t batch, const wcqp_unicycle_inputs* in,
                                     const wcqp_unicycle_outputs* out, int32_t* ss_ticks, int32_t* ds_ticks, void* stream) {
     int rc = check_call(h, batch, in, out);
@@ -207,12 +186,14 @@ int wcqp_unicycle_plan_timed_device(wcqp_unicycle_t h, const wcqp_unicycle_timin
     return WCQP_OK;
 }
 
-int wcqp_unicycle_plan_timed_host(wcqp_unicycle_t h, const wcqp_unicycle_timing* tm, int32_t batch, const wcqp_unicycle_inputs* in,
-                                  const wcqp_unicycle_outputs* out, int32_t* ss_ticks, int32_t* ds_ticks) {
+// Both host forms (timed or not: wcqp_unicycle_plan_host has no timing and no duration rows): the checks, the arrays staged in one block, the
+// device form
+static int plan_host(wcqp_unicycle_t h, bool timed, const wcqp_unicycle_timing* tm, int32_t batch, const wcqp_unicycle_inputs* in,
+                     const wcqp_unicycle_outputs* out, int32_t* ss_ticks, int32_t* ds_ticks) {
     int rc = check_call(h, batch, in, out);
     if (rc != WCQP_OK) return rc;
     UniTiming unused{};
-    rc = check_timing(h, tm, ss_ticks, ds_ticks, &unused);
+    if (timed) rc = check_timing(h, tm, ss_ticks, ds_ticks, &unused);
     if (rc != WCQP_OK) return rc;
     const size_t B = (size_t)batch, K = (size_t)h->par.K;
     rc = check_host_arrays(h->par, B, in);
@@ -220,20 +201,30 @@ int wcqp_unicycle_plan_timed_host(wcqp_unicycle_t h, const wcqp_unicycle_timing*
     if (batch == 0) return WCQP_OK;
     rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
-    // doubles first, then the 32-bit rows, then the bytes; no step rows at all when the planner keeps none (K = 0)
+    // doubles first, then the 32-bit rows (the timed form's duration rows last of them), then the bytes; no step rows at all when the
+    // planner keeps none (K = 0)
     wcqp::HostStage st;
     const auto d_l = st.in(in->left0, B * 12), d_r = st.in(in->right0, B * 12), d_g = st.in(in->goal, B * 2);
     const auto d_t = st.out(out->target, B * K * 3, true), d_dp = st.out(out->desired_point, B * 2), d_ue = st.out(out->unicycle_end, B * 3);
     const auto d_n = st.out(out->n_steps, B), d_st = st.out(out->status, B);
-    const auto d_ss = st.out(ss_ticks, B * K, true), d_ds = st.out(ds_ticks, B * K, true);
+    const auto d_ss = st.out(timed ? ss_ticks : nullptr, B * K, true), d_ds = st.out(timed ? ds_ticks : nullptr, B * K, true);
     const auto d_fs = st.in(in->first_side, B);
     const auto d_sd = st.out(out->side, B * K, true);
     rc = st.upload(h->scratch);
     if (rc != WCQP_OK) return rc;
     const wcqp_unicycle_inputs din{st[d_l], st[d_r], st[d_g], st[d_fs]};
     const wcqp_unicycle_outputs dout{st[d_n], st[d_sd], st[d_t], st[d_st], st[d_dp], st[d_ue]};
-    rc = wcqp_unicycle_plan_timed_device(h, tm, batch, &din, &dout, st[d_ss], st[d_ds], nullptr);
+    rc = timed ? wcqp_unicycle_plan_timed_device(h, tm, batch, &din, &dout, st[d_ss], st[d_ds], nullptr) : wcqp_unicycle_plan_device(h, batch, &din, &dout, nullptr);
     return rc != WCQP_OK ? rc : st.download();
+}
+
+int wcqp_unicycle_plan_host(wcqp_unicycle_t h, int32_t batch, const wcqp_unicycle_inputs* in, const wcqp_unicycle_outputs* out) {
+    return plan_host(h, false, nullptr, batch, in, out, nullptr, nullptr);
+}
+
+int wcqp_unicycle_plan_timed_host(wcqp_unicycle_t h, const wcqp_unicycle_timing* tm, int32_t batch, const wcqp_unicycle_inputs* in,
+                                  const wcqp_unicycle_outputs* out, int32_t* ss_ticks, int32_t* ds_ticks) {
+    return plan_host(h, true, tm, batch, in, out, ss_ticks, ds_ticks);
 }
 
 }  // extern "C"
