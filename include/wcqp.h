@@ -864,6 +864,8 @@ typedef struct wcqp_tick_option {
 #define WCQP_TICK_OPT_PLAN_TIMED         3   /* REPORTED ONLY (wcqp_tick_get_option; wcqp_tick_create_opts refuses it as an unknown key): 1 while the plan in
                                               * place came from wcqp_tick_upload_footsteps_timed (per-step timings), 0 otherwise.  wcqp_tick_info_ext is
                                               * closed like the structs before it, so the flag travels by key */
+#define WCQP_TICK_OPT_PLAN_SHIFT         4   /* REPORTED ONLY, like WCQP_TICK_OPT_PLAN_TIMED: the stages wcqp_tick_rebase_plan has taken since the last upload,
+                                              * summed (0 after every upload; saturates at INT32_MAX) */
 int wcqp_tick_create_opts(const wcqp_tick_params* params, const wcqp_tick_option* opts, int32_t n_opts, wcqp_tick_t* out);
 int wcqp_tick_get_option(wcqp_tick_t h, int32_t key, int32_t* value);
 int wcqp_tick_destroy(wcqp_tick_t h);
@@ -953,6 +955,46 @@ typedef struct wcqp_tick_replan {         /* HOST pointers, copied before the ca
     int32_t first_ds_ticks;               /* >= 1: stages of double support from M_i before the first new step */
 } wcqp_tick_replan;
 int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* stream);
+/* A walk that outlasts max_ticks (WalkingModule::advanceReferenceSignals, WM/src/WalkingModule.cpp:35-..., called at :816, pops the front of
+ * every trajectory deque and pushes the last element back, for as long as the module runs).  wcqp_tick_rebase_plan moves a GENERATED plan
+ * and everything indexed by its stages R = shift stages towards 0 on the device: stage R becomes stage 0, the tick index goes down by R,
+ * the robots' state is not touched, and ticks and replans go on as if nothing had happened - with R more ticks of room.
+ * shift = WCQP_TICK_REBASE_AUTO: the largest even shift <= the ticks enqueued.  THE REBASED PLAN, with T stages
+ * (tests/helpers/plan_rebase.py restates it on the windows wcqp_tick_get_plan returns):
+ *   Stages [0, T - R)  of every robot are the old stages [R, T), bit for bit: record entries 0..38, ref_traj, dcm_vel, and the support-polygon
+ *               rows a stage names, as wcqp_tick_get_plan returns them.
+ *   Stages [T - R, T)  are copies of the old stage T - 1 (the reference's push-back of the last element).  The admission rule makes that a
+ *               standing stage - twists 0, dcm_vel 0, ref_traj equal to its ZMP -, so the copy is what the generator would have produced there.
+ *   Tick index  both device copies go down by R, and so does the host's count of enqueued ticks: wcqp_tick_run has R more ticks of room,
+ *               merge stages and wcqp_tick_splice_reference's from_tick are stages of the REBASED plan.
+ *   Plan in force  every robot's plan keeps its first double support, steps and durations; the stage it was generated from goes down by R
+ *               and may become negative.  A pending wcqp_tick_replan_goals* is settled first (the rule below reads timelines).
+ *   State       no state record, counter, filter, gain smoother, live hull row, hand-off record or joint array is read or written.
+ *   Logs        u0_log, dq_log, q_log and the logger rows are indexed by the tick index, which this call rewinds: the ticks that follow
+ *               write over rows R stages back.  A caller who wants the rows of the ticks so far downloads before rebasing.
+ *   ZMP of stage 0  wcqp_tick_plan_window.u_init becomes the ZMP of the new stage 0, recovered from what the plan keeps of old stage R:
+ *               ref_traj[R] - dcm_vel[R] / omega on a handle that keeps the DCM velocity (reactive controller, gain scheduling), else the
+ *               recursion solved for it, (ref_traj[R + 1] - a ref_traj[R]) / (1 - a), a = exp(omega dT) - each operation rounded on its
+ *               own.  It agrees with the generator's value to rounding, not bit for bit.
+ *   Set slots   robot i owns slots [i cap, (i + 1) cap) of the row sets and entry 39 of a record names one.  With d_i = (entry 39 of the old
+ *               record R) - i cap, the robot's rows in slots >= i cap + d_i move down by d_i and entry 39 of every record of the robot goes
+ *               down by d_i: the sets of stages that are gone free their slots, so replans never run out of them.
+ * Enqueue-only: two kernels on `stream` behind the ticks already enqueued, and one 4-byte row per robot (d_i) that travels back behind
+ * an event of its own, which the next call that needs it waits for (as for the step counts of wcqp_tick_replan_goals).  No pointer a tick
+ * or a captured graph holds moves.  On a handle with resident_plan a stage in hand (wcqp_tick_set_desired_from_plan) stays in hand.
+ * Valid between wcqp_tick_run calls.  Everything is checked on the host before anything changes; a refused call leaves the handle as it was.
+ * WCQP_E_UNSUPPORTED: a handle that holds no plan, or whose plan was not generated (wcqp_tick_info.plan_generated = 0: no known timeline);
+ * plant = INTERNAL with noise != 0 (the disturbance is a hash of the tick index, and a rewound index would repeat its stream).
+ * WCQP_E_INVALID: not uploaded; shift odd (the MPC -> IK hand-off record is addressed by the tick's parity), shift < 2 - also AUTO with
+ * fewer than two ticks enqueued -, shift > the ticks enqueued; any robot whose plan in force does not STAND from a stage <= max_ticks
+ * on, that is first_ds_ticks + its steps' durations (the last double support as the plan resolves it), counted from the stage the plan
+ * was generated from, exceed max_ticks.  That rule guarantees that every change of contact pair of the plan has its row set - sets are
+ * built for stages <= max_ticks only - and that stage T - 1 stands.  A robot on a plan cut off by T is first replanned to one that ends.
+ * SIZING: max_ticks must hold the longest plan a robot is ever given from its merge stage to standing, plus the ticks between two
+ * rebases: with plans of at most P stages, merged at most L stages ahead, and a rebase every E ticks, max_ticks >= E + L + P.
+ * Not offered: rebasing a classically uploaded plan, per-robot shifts, a tick offset inside the kernels (noise, logs). */
+#define WCQP_TICK_REBASE_AUTO (-1)
+int wcqp_tick_rebase_plan(wcqp_tick_t h, int32_t shift, void* stream);
 /* Per-step timings: every footstep carries its own durations (the reference's planner gives every step its own, between minStepDuration
  * and maxStepDuration; wcqp_unicycle_plan_timed_* below chooses them and fills exactly these two arrays).  THE TIMED PLAN is the plan
  * wcqp_tick_upload_footsteps defines (tests/helpers/footstep_plan_timed.py restates it), with four changes:

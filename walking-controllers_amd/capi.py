@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
     "wcqp_tick_upload_footsteps", "wcqp_tick_upload_footsteps_timed", "wcqp_tick_replan_footsteps_timed", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
-    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing",
+    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
     "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
@@ -209,6 +209,8 @@ class TickOption(C.Structure):
 
 TICK_OPT_RESIDENT_PLAN, TICK_OPT_POSITION_STREAMED = 1, 2
 TICK_OPT_PLAN_TIMED = 3        # reported only (TickPipeline.option / info()["plan_timed"]): the plan in place carries per-step timings
+TICK_OPT_PLAN_SHIFT = 4        # reported only (TickPipeline.option): the stages rebase_plan has taken since the last upload, summed
+TICK_REBASE_AUTO = -1          # rebase_plan: the largest even shift <= the ticks enqueued
 TICK_PLANT_INTERNAL, TICK_PLANT_EXTERNAL = 0, 1
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
 TICK_IK_VELOCITY, TICK_IK_POSITION = 0, 1
@@ -338,7 +340,7 @@ ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
     "IK_FORM_QPOASES IK_FORM_OSQP IK_ALG_DEFAULT IK_ALG_SWEEP IK_ALG_NULLSPACE IK_ALG_NULLSPACE_MFMA IK_ALG_NULLSPACE_16L IK_ALG_BASE_ELIM "
     "IK_JAC_AUTO IK_JAC_MIXED IK_JAC_GENERAL PLAN_WAYS_AUTO SLAB_IN_ARRAYS SLAB_OUT_ARRAYS KIN_MAX_DOF "
     "KIN_HANDOFF_FUSED KIN_HANDOFF_DENSE KIN_HANDOFF_COMPACT TICK_PLANT_INTERNAL TICK_PLANT_EXTERNAL TICK_DCM_MPC TICK_DCM_REACTIVE "
-    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED TICK_OPT_PLAN_TIMED UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
+    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED TICK_OPT_PLAN_TIMED TICK_OPT_PLAN_SHIFT TICK_REBASE_AUTO UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
     "TICK_MERGE_KEEP TICK_MERGE_AUTO TICK_SIDE_AUTO GOAL_KEPT GOAL_TOO_LATE").split()}
 
 _lib: Optional[C.CDLL] = None
@@ -404,6 +406,7 @@ def lib() -> C.CDLL:
         L.wcqp_tick_get_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TickPlanWindow)]
         L.wcqp_tick_replan_footsteps.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.c_void_p]
         L.wcqp_tick_replan_goals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickGoals), C.c_void_p]
+        L.wcqp_tick_rebase_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.wcqp_tick_get_goal_result.argtypes = [C.c_void_p, C.POINTER(TickGoalResult)]
         L.wcqp_tick_replan_goals_timed.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(UnicycleTiming), C.POINTER(TickGoals), C.c_void_p]
         L.wcqp_tick_get_goal_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -976,6 +979,16 @@ class TickPipeline(_Handle):
             check(lib().wcqp_tick_replan_footsteps_timed(self._h, C.byref(rp), C.byref(tm), stream or None), "wcqp_tick_replan_footsteps_timed")
         else:
             check(lib().wcqp_tick_replan_footsteps(self._h, C.byref(rp), stream or None), "wcqp_tick_replan_footsteps")
+
+    def rebase_plan(self, shift: Optional[int] = None, stream: Optional[int] = None) -> int:
+        """Moves the generated plan `shift` stages towards 0 on the device (wcqp_tick_rebase_plan, which defines the rebased plan): stage
+        `shift` becomes stage 0, the tick index goes down by it, the robots' state stays, and run() has `shift` more ticks of room.
+        shift None: the largest even shift <= the ticks enqueued.  Merge stages given afterwards are stages of the rebased plan; the
+        logs are indexed by the rewound tick index, so download() first where the rows so far matter.  Enqueue-only on `stream`.
+        Returns the shift taken."""
+        before = self.option(TICK_OPT_PLAN_SHIFT)
+        check(lib().wcqp_tick_rebase_plan(self._h, TICK_REBASE_AUTO if shift is None else int(shift), stream or None), "wcqp_tick_rebase_plan")
+        return self.option(TICK_OPT_PLAN_SHIFT) - before
 
     def upload_goal(self, data: dict, goals, planner: "UnicyclePlanner", first_side, first_ds_ticks: int, ss_ticks: int = 0, ds_ticks: int = 0,
                     final_ds_ticks: int = 0, lift: float = 0.02, zmp_delta_left=(0.03, -0.005), zmp_delta_right=(0.03, 0.005),

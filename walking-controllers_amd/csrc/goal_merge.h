@@ -1,8 +1,8 @@
 // The timeline of a generated plan, stated once for timed and untimed plans alike, and what the host decides on it: where a running walk
 // may be cut for a new goal (wcqp_tick_replan_goals, include/wcqp.h, which states the rule; tests/helpers/goal_merge.py and
 // goal_merge_timed.py restate it), how many support-polygon sets a plan reaches, how many stages it spans, and whether its stage indices
-// fit.  Pure host arithmetic in long long.  No HIP header: tests/cpp/goal_merge_check.cpp, goal_merge_timed_check.cpp and
-// timeline_count_check.cpp build it alone.
+// fit - and whether a running plan may be rebased (wcqp_tick_rebase_plan).  Pure host arithmetic in long long.  No HIP header:
+// tests/cpp/goal_merge_check.cpp, goal_merge_timed_check.cpp, timeline_count_check.cpp and rebase_check.cpp build it alone.
 #pragma once
 
 namespace wcqp_goal {
@@ -92,5 +92,18 @@ inline int merge_auto(const Timeline& p, int t0, int min_lead, int T) {
     }
     return M < T ? (int)M : kTooLate;
 }
+
+// The plan stands - its steps are over, the last double support included - from a stage <= max_ticks on: every change of contact pair
+// it holds lies at a stage a tick can reach (so each has its support-polygon set), and stage T - 1 is a standing stage
+inline bool stands_within(const Timeline& p, int max_ticks, int final_ds) { return p.first_step() + p.span(final_ds) <= max_ticks; }
+
+// A rebase by `shift` stages (wcqp_tick_rebase_plan, include/wcqp.h, which states the rule; tests/helpers/plan_rebase.py restates it):
+// even - the MPC -> IK hand-off record is addressed by the tick's parity -, 2 at least, no more than the ticks enqueued, and on a plan
+// that stands within max_ticks.  The origin of `p` may be negative: a plan rebased before.
+inline bool rebase_allowed(const Timeline& p, int shift, int ticks_enqueued, int max_ticks, int final_ds) {
+    return shift >= 2 && (shift & 1) == 0 && shift <= ticks_enqueued && stands_within(p, max_ticks, final_ds);
+}
+// WCQP_TICK_REBASE_AUTO: the largest even shift <= the ticks enqueued (below 2: no rebase is allowed)
+inline int rebase_auto(int ticks_enqueued) { return ticks_enqueued > 0 ? ticks_enqueued & ~1 : 0; }
 
 }  // namespace wcqp_goal

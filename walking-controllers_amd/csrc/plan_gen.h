@@ -53,9 +53,24 @@ struct PlanGenTimedDev {
     PlanTimes tm;
 };
 
+// wcqp_tick_rebase_plan (plan_rebase.hip): a generated plan and everything indexed by its stages moved `shift` stages towards 0, in place
+struct PlanRebaseDev {
+    double* rec;                    // [B][traj_len][kPlanRec]
+    double* ref;                    // TickDev::ref_traj
+    double* vel;                    // TickDev::dcm_vel, or NULL on a handle that keeps none
+    double* zmp0;                   // [B][2] the generated ZMP of stage 0
+    double* set_A; double* set_b; int* set_nc;      // the row sets: robot i owns slots [i cap, (i + 1) cap)
+    int* tick2;                     // TickDev::tick2: both copies of the tick index go down by shift
+    int* d_out;                     // [B] d_i, the slots robot i's sets move down by: entry 39 of its old record `shift`, less i cap
+    int batch, traj_len, shift, cap;
+    double omega, a;                // a = exp(omega dT)
+};
+
 }  // namespace wcqp_tick
 
 namespace wcqp {
+// its two kernels in stream order: d_i, the ZMP of the new stage 0 and the tick index first, then the rows.  Enqueue-only
+int plan_rebase_enqueue(const wcqp_tick::PlanRebaseDev& g, hipStream_t stream);
 // prologue, DCM pass and record pass of one upload, in stream order (plan_gen.hip); rec0 / rec1 (or NULL): events recorded around the record
 // pass.  An untimed plan (ss, ds, final_ds >= 1), or a timed one (wcqp_tick_upload_footsteps_timed: final_ds >= 0 and the three rows)
 int plan_gen_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);

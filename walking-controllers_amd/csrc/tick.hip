@@ -505,6 +505,7 @@ int wcqp_tick_get_option(wcqp_tick_t h, int32_t key, int32_t* value) {
     if (!h || !value) return WCQP_E_INVALID;
     if (key == WCQP_TICK_OPT_RESIDENT_PLAN) *value = h->resident ? 1 : 0;
     else if (key == WCQP_TICK_OPT_POSITION_STREAMED) *value = h->position && h->streamed ? 1 : 0;
+    else if (key == WCQP_TICK_OPT_PLAN_SHIFT) *value = (int32_t)(h->plan_shift < INT32_MAX ? h->plan_shift : INT32_MAX);      // (reported only)
     else if (key == WCQP_TICK_OPT_PLAN_TIMED) *value = h->holds_plan() && h->uploaded && h->generated && h->gp.timed ? 1 : 0;      // (reported only)
     else return WCQP_E_INVALID;
     return WCQP_OK;
@@ -518,6 +519,7 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     for (void* p : {(void*)h->set_A, (void*)h->set_b, (void*)h->set_nc}) if (p) (void)hipFree(p);
     for (StagedBlock* b : {&h->splice, &h->rp, &h->run}) b->release();
     h->goal.release();
+    h->rebase.release();
     for (hipEvent_t e : h->gen_ev) if (e) (void)hipEventDestroy(e);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->kin) wcqp_kin_destroy(h->kin);
@@ -614,6 +616,7 @@ int wcqp::upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0) {
     WCQP_HIP_TRY(hipDeviceSynchronize());
     h->uploaded = true;
     h->ticks_enqueued = 0;
+    h->plan_shift = 0;
     h->phase = 0;
     h->feedback_set = false;
     h->desired_set = false; h->plan_staged = false;
@@ -692,7 +695,7 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
     if (const int rc = feedback_ready(h, dcm_meas, com_meas, zmp_meas); rc != WCQP_OK) return rc;
     const int n = h->d.batch * kDof;
     hipLaunchKernelGGL(tick_feedback_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d, dcm_meas, com_meas, zmp_meas, q_meas, h->q_meas,
-                       h->feedback_fail, h->ticks_enqueued);
+                       h->feedback_fail, h->ticks_for_handoff());
     WCQP_HIP_TRY(hipGetLastError());
     h->feedback_set = true;
     h->filt_pending = false;      // (this tick supplies the filters no sample: they hold, whatever a replaced sensor call computed)
@@ -730,7 +733,7 @@ int wcqp_tick_set_sensor_feedback_device(wcqp_tick_t h, const double* q_meas, co
     a.q = q_meas; a.dq = dq_meas; a.wl = wrench_left; a.wr = wrench_right;
     a.q_des = d.q_des; a.state = d.state; a.phase0 = d.phase0; a.kin_tab = d.kin_tab;
     a.mst = d.mst; a.hand = d.hand; a.q_meas = h->q_meas; a.ik_fail = d.ik_fail; a.feedback_fail = h->feedback_fail;
-    a.batch = d.batch; a.t = h->ticks_enqueued; a.step_ticks = d.step_ticks; a.kin_rounds = d.kin_rounds; a.omega = d.omega;
+    a.batch = d.batch; a.t = h->ticks_for_handoff(); a.step_ticks = d.step_ticks; a.kin_rounds = d.kin_rounds; a.omega = d.omega;
     a.rec = h->streamed ? h->st_rec : nullptr;
     if (h->filt_mask) {
         const size_t slot = (size_t)d.batch * kFiltRec;
@@ -939,12 +942,12 @@ int wcqp_tick_download(wcqp_tick_t h, const wcqp_tick_outputs* out) {
     if (out->measured) {
         // what the chain of the last executed tick read as measured com / dcm / ZMP: the plant state at the start of tick t in its
         // hand-off record (parity t & 1; no later tick has run, so no later chain step has overwritten it)
-        if (h->ticks_enqueued == 0) {
+        if (h->ticks_for_handoff() == 0) {
             if (h->meas0.size() != B * 6) return WCQP_E_INVALID;
             std::memcpy(out->measured, h->meas0.data(), B * 48);
         } else {
             std::vector<double> hd(B * kHandLen);
-            WCQP_HIP_TRY(hipMemcpy(hd.data(), d.hand + (size_t)((h->ticks_enqueued - 1) & 1) * B * kHandLen, B * kHandLen * 8, hipMemcpyDeviceToHost));
+            WCQP_HIP_TRY(hipMemcpy(hd.data(), d.hand + (size_t)((h->ticks_for_handoff() - 1) & 1) * B * kHandLen, B * kHandLen * 8, hipMemcpyDeviceToHost));
             for (size_t i = 0; i < B; ++i)
                 for (int ax = 0; ax < 2; ++ax) {
                     out->measured[i * 6 + ax] = hd[i * kHandLen + 6 + ax];

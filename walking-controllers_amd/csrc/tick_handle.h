@@ -71,7 +71,11 @@ struct wcqp_tick_s {
     hipGraphExec_t graph_exec = nullptr;
     hipStream_t graph_stream = nullptr;
     bool uploaded = false;
-    int ticks_enqueued = 0;  // since the last upload; its parity is the `phase` of the next tick
+    int ticks_enqueued = 0;  // since the last upload, less what wcqp_tick_rebase_plan took off (plan_shift): the stage of the next tick
+    long long plan_shift = 0;     // stages rebased since the last upload, summed (WCQP_TICK_OPT_PLAN_SHIFT)
+    // the tick count for what only asks whether a tick has run since the upload and for its parity (the hand-off record of the last tick,
+    // the feedback kernels' first-tick rule): a rebase takes an even count off ticks_enqueued, perhaps all of it, and no tick back
+    int ticks_for_handoff() const { return ticks_enqueued == 0 && plan_shift > 0 ? 2 : ticks_enqueued; }
     double* log_ferr = nullptr;   // logger rows with dense Jacobians: where the IK kernel forms the foot errors
     TickForm form = TickForm::FOUR_LAUNCH;   // from the IK handle's route (wcqp_tick_create)
     wcqp_kin_t kin = nullptr;     // use_kinematics: Jacobians, actual poses and hull rows are rebuilt every tick
@@ -177,13 +181,32 @@ struct wcqp_tick_s {
             host = nullptr; host_cap = 0; ev = nullptr; pending = false; called = false; owed.clear();
         }
     } goal;
+    // wcqp_tick_rebase_plan owes the same way: d_i, the slots robot i's sets moved down by, is read on the device (plan_rebase.hip) and
+    // comes back into `host` (pinned, [B]) behind `ev`; until then every gp.keep is owed d_i, and settle() takes it off.  A call settles
+    // before it enqueues, so one row is in flight at most.  dev / host: allocated by the first wcqp_tick_upload_footsteps*
+    struct RebaseCall {
+        int* dev = nullptr; int* host = nullptr;
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+        void release() {
+            if (host) (void)hipHostFree(host);
+            if (ev) (void)hipEventDestroy(ev);
+            host = nullptr; ev = nullptr; pending = false;
+        }
+    } rebase;
     int settle() {
         if (const int rc = goal.wait(); rc != WCQP_OK) return rc;
-        if (goal.owed.empty()) return WCQP_OK;
-        const GoalRows& r = goal.rows;
-        const int32_t* n = r.at<int32_t>(goal.host, r.n);
-        for (int i : goal.owed) gp.set_steps((size_t)i, n[i], r.at<int32_t>(goal.host, r.ss) + (size_t)i * r.K, r.at<int32_t>(goal.host, r.ds) + (size_t)i * r.K);
-        goal.owed.clear();
+        if (!goal.owed.empty()) {
+            const GoalRows& r = goal.rows;
+            const int32_t* n = r.at<int32_t>(goal.host, r.n);
+            for (int i : goal.owed) gp.set_steps((size_t)i, n[i], r.at<int32_t>(goal.host, r.ss) + (size_t)i * r.K, r.at<int32_t>(goal.host, r.ds) + (size_t)i * r.K);
+            goal.owed.clear();
+        }
+        if (rebase.pending) {
+            WCQP_HIP_TRY(hipEventSynchronize(rebase.ev));
+            rebase.pending = false;
+            for (size_t i = 0; i < gp.keep.size(); ++i) gp.keep[i] -= rebase.host[i];
+        }
         return WCQP_OK;
     }
     // streamed_trajectories (an EXTERNAL handle): pl.rec holds ONE record per robot, the stage wcqp_tick_set_desired_* handed over for the next

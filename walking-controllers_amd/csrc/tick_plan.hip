@@ -543,6 +543,12 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
     h->uploaded = false;
     WCQP_HIP_TRY(hipDeviceSynchronize());
     if (!h->gen_zmp0) { const int rca = dev_alloc(h, &h->gen_zmp0, B * 2); if (rca != WCQP_OK) return rca; }
+    {   // wcqp_tick_rebase_plan's row of d_i, on the device and pinned, and the event behind its copy
+        auto& rb = h->rebase;
+        if (!rb.dev) { const int rca = dev_alloc(h, &rb.dev, B); if (rca != WCQP_OK) return rca; }
+        if (!rb.host && hipHostMalloc(reinterpret_cast<void**>(&rb.host), B * 4, hipHostMallocDefault) != hipSuccess) return WCQP_E_NOMEM;
+        if (!rb.ev) WCQP_HIP_TRY(hipEventCreateWithFlags(&rb.ev, hipEventDisableTiming));
+    }
     {   // what this plan fixes for the handle, and a replan needs to know of it (wcqp_tick_replan_footsteps)
         auto& gp = h->gp;
         gp.ss = tm ? 0 : steps->ss_ticks; gp.ds = tm ? 0 : steps->ds_ticks; gp.final_ds = final_ds; gp.cap = cap; gp.lift = steps->lift;
@@ -595,7 +601,7 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
         gp.origin.assign(B, 0); gp.first_ds.assign(B, steps->first_ds_ticks); gp.keep.assign(B, 1);
         gp.n_steps.assign(B, 0); gp.dur.assign(tm ? B : 0, std::vector<int>());
         for (size_t i = 0; i < B; ++i) gp.set_steps(i, steps->n_steps[i], tm ? tm->ss_ticks + i * K : nullptr, tm ? tm->ds_ticks + i * K : nullptr);
-        h->rp.pending = false; h->goal.pending = false; h->goal.owed.clear();      // (the device was synchronised above)
+        h->rp.pending = false; h->goal.pending = false; h->goal.owed.clear(); h->rebase.pending = false;      // (the device was synchronised above)
     }
     WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
     WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
@@ -726,6 +732,42 @@ int wcqp_tick_replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_ti
 int wcqp_tick_replan_goals_timed(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_timing* tm, const wcqp_tick_goals* gl, void* stream) {
     if (!tm) return WCQP_E_INVALID;
     return replan_goals(h, planner, tm, gl, stream);
+}
+
+// THE REBASED PLAN (include/wcqp.h).  The host decides - on the timelines of the plans in force, settled first - and keeps its own
+// books: origins and the tick count go down by the shift at once, each robot's `keep` by d_i once the row has come back (RebaseCall)
+int wcqp_tick_rebase_plan(wcqp_tick_t h, int32_t shift, void* stream) {
+    if (!h) return WCQP_E_INVALID;
+    if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    // (the internal plant's disturbance is a hash of the tick index: a rewound index would repeat its stream)
+    if (!h->external && h->p.noise != 0.0) return WCQP_E_UNSUPPORTED;
+    const TickDev& d = h->d;
+    auto& gp = h->gp;
+    auto& rb = h->rebase;
+    const size_t B = (size_t)d.batch;
+    const int R = shift == WCQP_TICK_REBASE_AUTO ? wcqp_goal::rebase_auto(h->ticks_enqueued) : shift;
+    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (the rule reads timelines; and the previous rebase's row has come back)
+    for (size_t i = 0; i < B; ++i)
+        if (!wcqp_goal::rebase_allowed(gp.timeline(i), R, h->ticks_enqueued, h->p.max_ticks, gp.final_ds)) return WCQP_E_INVALID;
+    if (!rb.dev || !rb.host || !rb.ev) return WCQP_E_INVALID;       // (cannot happen: every generated upload allocates them)
+    PlanRebaseDev g{};
+    g.rec = h->plan_rec; g.ref = const_cast<double*>(d.ref_traj.get());
+    g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
+    g.zmp0 = h->gen_zmp0;
+    g.set_A = h->set_A; g.set_b = h->set_b; g.set_nc = h->set_nc;
+    g.tick2 = d.tick2.p; g.d_out = rb.dev;
+    g.batch = d.batch; g.traj_len = d.traj_len; g.shift = R; g.cap = gp.cap;
+    g.omega = d.omega; g.a = std::exp(d.omega * d.dT);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = wcqp::plan_rebase_enqueue(g, st); rc != WCQP_OK) return rc;
+    WCQP_HIP_TRY(hipMemcpyAsync(rb.host, rb.dev, B * 4, hipMemcpyDeviceToHost, st));
+    WCQP_HIP_TRY(hipEventRecord(rb.ev, st));
+    rb.pending = true;
+    // (an origin 2^30 stages back belongs to a plan that ended before stage 0 - stages_fit bounds its span -: it may stay there)
+    for (size_t i = 0; i < B; ++i) if (gp.origin[i] > -(1 << 30)) gp.origin[i] -= R;
+    h->ticks_enqueued -= R;
+    h->plan_shift += R;
+    return WCQP_OK;
 }
 
 int wcqp_tick_get_goal_result(wcqp_tick_t h, const wcqp_tick_goal_result* out) {
