@@ -866,6 +866,8 @@ typedef struct wcqp_tick_option {
                                               * closed like the structs before it, so the flag travels by key */
 #define WCQP_TICK_OPT_PLAN_SHIFT         4   /* REPORTED ONLY, like WCQP_TICK_OPT_PLAN_TIMED: the stages wcqp_tick_rebase_plan has taken since the last upload,
                                               * summed (0 after every upload; saturates at INT32_MAX) */
+#define WCQP_TICK_OPT_SWING_PROFILE      5   /* REPORTED ONLY, like WCQP_TICK_OPT_PLAN_TIMED: 1 while the plan in force was generated with a non-zero
+                                              * swing profile (wcqp_tick_set_swing_profile, below), 0 otherwise */
 int wcqp_tick_create_opts(const wcqp_tick_params* params, const wcqp_tick_option* opts, int32_t n_opts, wcqp_tick_t* out);
 int wcqp_tick_get_option(wcqp_tick_t h, int32_t key, int32_t* value);
 int wcqp_tick_destroy(wcqp_tick_t h);
@@ -892,7 +894,7 @@ int wcqp_tick_upload(wcqp_tick_t h, const wcqp_tick_inputs* in);
  *             step), b the next stance foot's (the midpoint after the last step).  Standing: the midpoint.
  *   DCM       xi_t = (xi_{t+1} - (1 - a) zmp_t) / a, a = exp(omega dT), backwards from xi = zmp at the first standing stage - over the
  *             whole plan, also where it ends past T (a plan cut off by T is simply truncated); dcm_vel = omega (xi - zmp).
- *   Height    state0[68], velocity 0.  The desired neck orientation is derived per tick, as in every planned handle.
+ *   Height    state0[68], velocity 0 (with a swing profile: THE SHAPED SWING, below, which also shapes the swing foot).  The desired neck orientation is derived per tick, as in every planned handle.
  *   Sets      the support-polygon rows by the rule of the classic upload: one set at stage 0 and one at every change of contact pair at
  *             a stage <= max_ticks, built from that stage's desired feet and foot_rect; later stages name the last set.
  * From `in` it reads state0 (the initial footprints are its desired-foot entries 24..47, the CoM height entry 68), q0, com0 and -
@@ -1020,6 +1022,46 @@ typedef struct wcqp_tick_step_timing {   /* HOST pointers, copied at the call */
 } wcqp_tick_step_timing;
 int wcqp_tick_upload_footsteps_timed(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_footsteps* steps, const wcqp_tick_step_timing* tm);
 int wcqp_tick_replan_footsteps_timed(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_step_timing* tm, void* stream);
+/* The shape of a step (plannerParams.ini footApexTime, stepLandingVelocity, pitchDelta, comHeightDelta, which the reference hands its
+ * planner at WM/src/TrajectoryGenerator.cpp:94-111; the shipped set is 0.8, 0.0, 0.0 - in DEGREES there, radians here - and 0.01).
+ * wcqp_tick_set_swing_profile stores a profile on the handle - host only, nothing is launched -; the next wcqp_tick_upload_footsteps or
+ * wcqp_tick_upload_footsteps_timed copies it into the plan it generates, next to lift and the ZMP deltas, and every replan of that plan
+ * (wcqp_tick_replan_footsteps*, wcqp_tick_replan_goals*) keeps it: the reference's planner parameters are fixed for a run too.  A later
+ * wcqp_tick_set_swing_profile does not touch a running plan, nor does wcqp_tick_rebase_plan touch the profile.  An all-zero profile - and
+ * a handle never given one - is THE PLAN above, bit for bit, by the same kernels.  THE SHAPED SWING, this build's own definition like
+ * THE PLAN (tests/helpers/swing_profile.py restates it): step k with ss_k single-support stages, at stage u; x = (u + 1) / ss_k; m, m' the
+ * plan's quintic; D = ss_k dT; r = apex_ratio; h(y) = 3 y^2 - 2 y^3.
+ *   Shape     c0(x) and its derivative in x:  r = 0: 16 x^2 (1 - x)^2, as in THE PLAN;  r > 0 and x <= r: h(x / r);  r > 0 and x > r:
+ *             1 - h(y), y = (x - r) / (1 - r).  C1 at x = r (both branches give 1 with slope 0 there).
+ *   Height of the swing foot   z = p_z + lift c0(x) + landing_velocity (1 - r) D (y^3 - y^2), the last term for r > 0 and x > r only.
+ *             Vertical twist = the analytic derivative in time, lift c0'(x) / D + landing_velocity (3 y^2 - 2 y).  At x = 1 - the landing
+ *             stage - z = p_z and the vertical twist is exactly landing_velocity.  The landing term is C1 at x = r as well (y = 0).
+ *             The descent is monotone if and only if |landing_velocity| (1 - r) D <= 3 lift.  That is NOT checked: durations chosen on
+ *             the device (wcqp_tick_replan_goals_timed) are not known to the host.
+ *   Pitch     theta = pitch_delta c0(x) about the foot's own y axis: rotation = Rz(dyaw m) R Ry(theta), angular twist (world frame) =
+ *             z dyaw m' / D + (Rz(dyaw m) R)[:, 1] pitch_delta c0'(x) / D.  theta = 0 at x = 1: the footprint from the next stage on is
+ *             still exactly the target.
+ *   CoM height  in a single-support stage: com_height = h0 + com_height_delta 16 x^2 (1 - x)^2, com_height_vel = its derivative / D; in
+ *             every other stage h0 and 0.  h0 = state0[68] in an upload, the handle's constant height in a replan; merge stages lie in
+ *             double supports, where the bump is 0, so a replanned plan stays continuous.
+ *   Unchanged   the swing foot's x, y and yaw increment, flags, ZMP, DCM reference and velocity, the timeline, the support-polygon sets (built
+ *             at changes of contact pair, where the landing foot has theta = 0 and z = p_z) and the rules of wcqp_tick_replan_* and
+ *             wcqp_tick_rebase_plan (the stage T - 1 it copies stands, so its height is h0).
+ * wcqp_tick_get_swing_profile returns the profile of the plan IN FORCE (all zero without a generated plan), not the pending one;
+ * wcqp_tick_get_option(WCQP_TICK_OPT_SWING_PROFILE) says whether it is non-zero.
+ * Refusals, on the host, the handle unchanged: WCQP_E_UNSUPPORTED on a handle that holds no plan (neither planned_trajectories nor
+ * resident_plan).  WCQP_E_INVALID for a NULL pointer, a non-finite value, apex_ratio < 0 or >= 1, landing_velocity > 0,
+ * landing_velocity != 0 with apex_ratio = 0 (the quartic has no landing branch), |pitch_delta| > pi / 4.
+ * Not offered: useMinimumJerkFootTrajectory (x and y already follow the quintic), per-robot profiles, changing the profile of a running
+ * plan, a natural frequency that follows the CoM height (the reference keeps omega constant too). */
+typedef struct wcqp_tick_swing_profile {
+    double apex_ratio;        /* footApexTime: 0 = the symmetric quartic of THE PLAN; else in (0, 1) */
+    double landing_velocity;  /* stepLandingVelocity [m/s]: <= 0; != 0 needs apex_ratio > 0 */
+    double pitch_delta;       /* pitchDelta, RADIANS here: |.| <= pi / 4 */
+    double com_height_delta;  /* comHeightDelta [m] */
+} wcqp_tick_swing_profile;
+int wcqp_tick_set_swing_profile(wcqp_tick_t h, const wcqp_tick_swing_profile* p);      /* host only, nothing launched */
+int wcqp_tick_get_swing_profile(wcqp_tick_t h, wcqp_tick_swing_profile* out);          /* the one of the plan in force */
 
 typedef struct wcqp_unicycle_s* wcqp_unicycle_t;       /* the unicycle planner's handle, stated at the end of this header */
 
@@ -1311,8 +1353,9 @@ int wcqp_tick_get_info_ext(wcqp_tick_t h, wcqp_tick_info_ext* out);
  * DEVIATIONS.  In THIS form step timings are common to a batch, as wcqp_tick_footsteps demands: minStepDuration, maxStepDuration,
  * nominalDuration, timeWeight, positionWeight and switchOverSwingRatio are not read, and a step advances the PATH by at most D samples
  * instead of choosing its duration (wcqp_unicycle_plan_timed_*, below, reads them and chooses).  plannerHorizon is
- * not read: the tick handle's T cuts the plan.  addTerminalStep, startAlwaysSameFoot and pitchDelta are not offered: the feet of a DONE
- * robot are aligned to within the two arrival thresholds, not exactly.  The two saturations are this build's own addition.
+ * not read: the tick handle's T cuts the plan.  addTerminalStep and startAlwaysSameFoot are not offered: the feet of a DONE
+ * robot are aligned to within the two arrival thresholds, not exactly (pitchDelta shapes the swing, not the footsteps:
+ * wcqp_tick_swing_profile).  The two saturations are this build's own addition.
  * ===================================================================================== */
 #define WCQP_UNICYCLE_DONE          0   /* arrived: the next candidate is no step                      */
 #define WCQP_UNICYCLE_TRUNCATED     1   /* max_steps steps taken without arriving                      */
@@ -1384,7 +1427,7 @@ int wcqp_unicycle_plan_host(wcqp_unicycle_t h, int32_t batch, const wcqp_unicycl
  *             so ss_k, ds_k >= 1 and ss_k + ds_k = m*.  ss_ticks / ds_ticks [B][K] are outputs, zero for steps not taken (and for
  *             every step of a WCQP_UNICYCLE_INVALID_INPUT robot): a step's single-support stages and the double-support stages
  *             behind it.
- * DEVIATIONS that remain: plannerHorizon is not read, addTerminalStep, startAlwaysSameFoot and pitchDelta are not offered, and
+ * DEVIATIONS that remain: plannerHorizon is not read, addTerminalStep and startAlwaysSameFoot are not offered, and
  * mergePointRatio is not read (a replan's merge stage is the caller's).  The two saturations stay this build's own addition.
  * ===================================================================================== */
 typedef struct wcqp_unicycle_timing {

@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
     "wcqp_tick_upload_footsteps", "wcqp_tick_upload_footsteps_timed", "wcqp_tick_replan_footsteps_timed", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
-    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan",
+    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan", "wcqp_tick_set_swing_profile", "wcqp_tick_get_swing_profile",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
     "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
@@ -210,6 +210,7 @@ class TickOption(C.Structure):
 TICK_OPT_RESIDENT_PLAN, TICK_OPT_POSITION_STREAMED = 1, 2
 TICK_OPT_PLAN_TIMED = 3        # reported only (TickPipeline.option / info()["plan_timed"]): the plan in place carries per-step timings
 TICK_OPT_PLAN_SHIFT = 4        # reported only (TickPipeline.option): the stages rebase_plan has taken since the last upload, summed
+TICK_OPT_SWING_PROFILE = 5     # reported only (TickPipeline.option): the plan in force was generated with a non-zero swing profile
 TICK_REBASE_AUTO = -1          # rebase_plan: the largest even shift <= the ticks enqueued
 TICK_PLANT_INTERNAL, TICK_PLANT_EXTERNAL = 0, 1
 TICK_DCM_MPC, TICK_DCM_REACTIVE = 0, 1
@@ -226,6 +227,11 @@ class TickInfo(C.Structure):
 class TickStepTiming(C.Structure):
     """wcqp_tick_step_timing: per-step durations ss_ticks / ds_ticks [B][K] (int32) of the timed footstep calls."""
     _fields_ = [("ss_ticks", C.c_void_p), ("ds_ticks", C.c_void_p)]
+
+
+class TickSwingProfile(C.Structure):
+    """wcqp_tick_swing_profile: the shape of a generated step (wcqp_tick_set_swing_profile, which defines the shaped swing)."""
+    _fields_ = [("apex_ratio", C.c_double), ("landing_velocity", C.c_double), ("pitch_delta", C.c_double), ("com_height_delta", C.c_double)]
 
 
 class TickInfoExt(C.Structure):
@@ -331,6 +337,7 @@ ABI_STRUCTS = {
     "wcqp_tick_inputs": TickInputs, "wcqp_tick_outputs": TickOutputs, "wcqp_tick_info": TickInfo, "wcqp_tick_info_ext": TickInfoExt,
     "wcqp_tick_desired": TickDesired, "wcqp_tick_footsteps": TickFootsteps, "wcqp_tick_replan": TickReplan, "wcqp_tick_plan_window": TickPlanWindow,
     "wcqp_tick_goals": TickGoals, "wcqp_tick_goal_result": TickGoalResult, "wcqp_tick_step_timing": TickStepTiming,
+    "wcqp_tick_swing_profile": TickSwingProfile,
     "wcqp_unicycle_params": UnicycleParams, "wcqp_unicycle_inputs": UnicycleInputs, "wcqp_unicycle_outputs": UnicycleOutputs,
     "wcqp_unicycle_timing": UnicycleTiming,
 }
@@ -340,7 +347,7 @@ ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
     "IK_FORM_QPOASES IK_FORM_OSQP IK_ALG_DEFAULT IK_ALG_SWEEP IK_ALG_NULLSPACE IK_ALG_NULLSPACE_MFMA IK_ALG_NULLSPACE_16L IK_ALG_BASE_ELIM "
     "IK_JAC_AUTO IK_JAC_MIXED IK_JAC_GENERAL PLAN_WAYS_AUTO SLAB_IN_ARRAYS SLAB_OUT_ARRAYS KIN_MAX_DOF "
     "KIN_HANDOFF_FUSED KIN_HANDOFF_DENSE KIN_HANDOFF_COMPACT TICK_PLANT_INTERNAL TICK_PLANT_EXTERNAL TICK_DCM_MPC TICK_DCM_REACTIVE "
-    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED TICK_OPT_PLAN_TIMED TICK_OPT_PLAN_SHIFT TICK_REBASE_AUTO UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
+    "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED TICK_OPT_PLAN_TIMED TICK_OPT_PLAN_SHIFT TICK_OPT_SWING_PROFILE TICK_REBASE_AUTO UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
     "TICK_MERGE_KEEP TICK_MERGE_AUTO TICK_SIDE_AUTO GOAL_KEPT GOAL_TOO_LATE").split()}
 
 _lib: Optional[C.CDLL] = None
@@ -407,6 +414,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_replan_footsteps.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.c_void_p]
         L.wcqp_tick_replan_goals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickGoals), C.c_void_p]
         L.wcqp_tick_rebase_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.wcqp_tick_set_swing_profile.argtypes = [C.c_void_p, C.POINTER(TickSwingProfile)]
+        L.wcqp_tick_get_swing_profile.argtypes = [C.c_void_p, C.POINTER(TickSwingProfile)]
         L.wcqp_tick_get_goal_result.argtypes = [C.c_void_p, C.POINTER(TickGoalResult)]
         L.wcqp_tick_replan_goals_timed.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(UnicycleTiming), C.POINTER(TickGoals), C.c_void_p]
         L.wcqp_tick_get_goal_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -989,6 +998,20 @@ class TickPipeline(_Handle):
         before = self.option(TICK_OPT_PLAN_SHIFT)
         check(lib().wcqp_tick_rebase_plan(self._h, TICK_REBASE_AUTO if shift is None else int(shift), stream or None), "wcqp_tick_rebase_plan")
         return self.option(TICK_OPT_PLAN_SHIFT) - before
+
+    def set_swing_profile(self, apex_ratio: float = 0.0, landing_velocity: float = 0.0, pitch_delta: float = 0.0, com_height_delta: float = 0.0):
+        """The shape of the steps the NEXT upload_footsteps / upload_goal generates (wcqp_tick_set_swing_profile, which defines the shaped
+        swing): apex_ratio (footApexTime; 0: the symmetric quartic), landing_velocity [m/s, <= 0], pitch_delta [rad] and com_height_delta
+        [m] - synth.shipped_swing_profile() holds plannerParams.ini's.  Host only; a running plan keeps the profile it was uploaded with,
+        through every replan.  All zero: the plain plan, bit for bit."""
+        p = TickSwingProfile(float(apex_ratio), float(landing_velocity), float(pitch_delta), float(com_height_delta))
+        check(lib().wcqp_tick_set_swing_profile(self._h, C.byref(p)), "wcqp_tick_set_swing_profile")
+
+    def swing_profile(self) -> dict:
+        """The swing profile of the plan in force (wcqp_tick_get_swing_profile) - not the one set_swing_profile left for the next upload."""
+        p = TickSwingProfile()
+        check(lib().wcqp_tick_get_swing_profile(self._h, C.byref(p)), "wcqp_tick_get_swing_profile")
+        return {k: float(getattr(p, k)) for k, _ in TickSwingProfile._fields_}
 
     def upload_goal(self, data: dict, goals, planner: "UnicyclePlanner", first_side, first_ds_ticks: int, ss_ticks: int = 0, ds_ticks: int = 0,
                     final_ds_ticks: int = 0, lift: float = 0.02, zmp_delta_left=(0.03, -0.005), zmp_delta_right=(0.03, 0.005),

@@ -39,6 +39,14 @@ struct PlanGenDev {
     int n_robots, n_tiles;
 };
 
+// THE SHAPED SWING (wcqp_tick_swing_profile, as the upload took it): a kernel argument of its own, behind PlanGenDev / PlanGenTimedDev, of
+// the shaped record kernels only - with every field zero the launch path takes the kernels that do not know it, with the arguments they
+// always took
+struct PlanSwing {
+    double apex, v_land, pitch, dh;
+    bool shaped() const { return apex != 0.0 || v_land != 0.0 || pitch != 0.0 || dh != 0.0; }
+};
+
 // The timed calls' per-step durations (wcqp_tick_step_timing's device copies) and the start table the prologue writes from them
 struct PlanTimes {
     const int* ss_k;                // [B][K] single-support stages of step k
@@ -72,10 +80,11 @@ namespace wcqp {
 // its two kernels in stream order: d_i, the ZMP of the new stage 0 and the tick index first, then the rows.  Enqueue-only
 int plan_rebase_enqueue(const wcqp_tick::PlanRebaseDev& g, hipStream_t stream);
 // prologue, DCM pass and record pass of one upload, in stream order (plan_gen.hip); rec0 / rec1 (or NULL): events recorded around the record
-// pass.  An untimed plan (ss, ds, final_ds >= 1), or a timed one (wcqp_tick_upload_footsteps_timed: final_ds >= 0 and the three rows)
-int plan_gen_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
-int plan_gen_enqueue(const wcqp_tick::PlanGenTimedDev& t, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
+// pass.  An untimed plan (ss, ds, final_ds >= 1), or a timed one (wcqp_tick_upload_footsteps_timed: final_ds >= 0 and the three rows).
+// sw: the plan's swing profile (all zero: none)
+int plan_gen_enqueue(const wcqp_tick::PlanGenDev& g, const wcqp_tick::PlanSwing& sw, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
+int plan_gen_enqueue(const wcqp_tick::PlanGenTimedDev& t, const wcqp_tick::PlanSwing& sw, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1);
 // the same three passes from per-robot origins, over the listed robots and tiles only (wcqp_tick_replan_footsteps*); enqueue-only
-int plan_replan_enqueue(const wcqp_tick::PlanGenDev& g, hipStream_t stream);
-int plan_replan_enqueue(const wcqp_tick::PlanGenTimedDev& t, hipStream_t stream);
+int plan_replan_enqueue(const wcqp_tick::PlanGenDev& g, const wcqp_tick::PlanSwing& sw, hipStream_t stream);
+int plan_replan_enqueue(const wcqp_tick::PlanGenTimedDev& t, const wcqp_tick::PlanSwing& sw, hipStream_t stream);
 }  // namespace wcqp

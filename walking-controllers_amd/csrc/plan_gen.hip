@@ -13,7 +13,8 @@
 // robot's start table - entry k the first stage s_k of step k's single support on the plan's own timeline, entry n the first standing
 // stage -, the DCM pass walks a step index down it as its stage passes s_k, and the record pass copies the entries its tile touches into
 // LDS next to the footprints and finds each lane's step by a search there.  The untimed instantiations are the code they were.
-// The four forms - upload or replan, untimed or timed - are launched by one enqueue<RP, Arg> at the end of this file.
+// The four forms - upload or replan, untimed or timed - are launched by one enqueue<RP, Arg> at the end of this file.  A plan uploaded with
+// a swing profile (wcqp_tick_set_swing_profile) runs the record pass's SHAPED instantiations; prologue and DCM pass do not know the profile.
 #include <cmath>
 #include "plan_gen.h"
 
@@ -234,8 +235,13 @@ __device__ __forceinline__ int step_at(const int* start, int n, int s) {
 
 // TIMED: the first stages and single-support lengths of steps j_lo .. j_hi - 1 sit in LDS next to the footprints (stl, ssl [kTabMax], the
 // timed kernels' own: a step lasts two stages or more), and a lane finds its step by counting the first stages at or below its own.
-template <bool RP, bool TIMED>
-__device__ __forceinline__ void plan_record(const PlanGenDev& g, const PlanTimes& tm, int* stl, int* ssl) {
+// SHAPED: THE SHAPED SWING (include/wcqp.h; tests/helpers/swing_profile.py restates it) - the swing block gives the foot's height the
+// two-branch smoothstep with its apex at x = apex and the landing term, pitches the foot about its own y axis (one more sincos per
+// swinging lane, the nine rotation entries instead of six, two more of the twist) and a single-support stage's CoM height the quartic bump.
+// Nothing else of the pass knows the profile (prof: the shaped kernels' second argument, unread otherwise): the tile, the tables in LDS and
+// the write-out are the unshaped kernels'.
+template <bool RP, bool TIMED, bool SHAPED>
+__device__ __forceinline__ void plan_record(const PlanGenDev& g, const PlanTimes& tm, const PlanSwing& prof, int* stl, int* ssl) {
     __shared__ double tile[kRecTile * kRecRow];
     __shared__ double fpt[kTabMax * kFpPose];
     __shared__ double dyaw[kTabMax];
@@ -294,6 +300,7 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g, const PlanTimes
         for (int e = 0; e < kFpPose; ++e) o[kPlanLeft + e] = f[e];
         for (int e = 0; e < 12; ++e) o[kPlanTwL + e] = 0.0;
         int flags = 3, fixed = fixed0;
+        [[maybe_unused]] double bump = 0.0, dbump = 0.0;      // SHAPED: a single-support stage's CoM height over h0, and its velocity
         if (k >= 0 && n > 0) { const int kl = k < n ? k : n - 1; fixed = 1 - swing[kl - j_lo < cnt ? kl - j_lo : cnt - 1]; }
         if (swinging) {
             const int sw = swing[k - j_lo < cnt ? k - j_lo : cnt - 1];
@@ -316,11 +323,40 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g, const PlanTimes
                 op[6 + c] = sn * r0 + cs * r1;
             }
             ot[0] = dx * dm * inv; ot[1] = dyy * dm * inv; ot[2] = g.lift * dlz * inv; ot[5] = dy * dm * inv;
+            if constexpr (SHAPED) {
+                // c0, its derivative in x, and the landing term with its derivative in TIME: v_land (3 y^2 - 2 y), exactly v_land at x = 1
+                double c0 = lz, dc0 = dlz, land = 0.0, vland = 0.0;
+                if (prof.apex > 0.0) {
+                    if (x <= prof.apex) {
+                        const double y = x / prof.apex;
+                        c0 = y * y * (3.0 - 2.0 * y); dc0 = 6.0 * y * (1.0 - y) / prof.apex;
+                    } else {
+                        const double w = 1.0 - prof.apex, y = (x - prof.apex) / w;
+                        c0 = 1.0 - y * y * (3.0 - 2.0 * y); dc0 = -6.0 * y * (1.0 - y) / w;
+                        land = prof.v_land * w * ((double)ss_k * g.dT) * (y * y * y - y * y);
+                        vland = prof.v_land * (3.0 * y * y - 2.0 * y);
+                    }
+                }
+                op[2] = p0[2] + g.lift * c0 + land;
+                ot[2] = g.lift * dc0 * inv + vland;
+                // Rz(dyaw m) R is in place (its third row the footprint's own): the pitch rate turns about its second column, then Ry(theta)
+                const double rate = prof.pitch * dc0 * inv;
+                ot[3] = op[4] * rate; ot[4] = op[7] * rate; ot[5] += op[10] * rate;
+                double sp, cp;
+                sincos(prof.pitch * c0, &sp, &cp);
+                for (int c = 3; c < 12; c += 3) {
+                    const double a0 = op[c], a2 = op[c + 2];
+                    op[c] = cp * a0 - sp * a2;
+                    op[c + 2] = sp * a0 + cp * a2;
+                }
+                bump = prof.dh * lz; dbump = prof.dh * dlz * inv;
+            }
             flags = sw == 1 ? 1 : 2;
         }
         o[kPlanFlags] = (double)(flags | (fixed == 0 ? 4 : 0));
-        o[kPlanHeight] = RP ? g.h0[i] : g.state[i * kStateLen + 68];
-        o[kPlanHeightVel] = 0.0;
+        const double h0 = RP ? g.h0[i] : g.state[i * kStateLen + 68];
+        o[kPlanHeight] = SHAPED ? h0 + bump : h0;
+        o[kPlanHeightVel] = SHAPED ? dbump : 0.0;
         // the support-polygon set in force: the origin's, plus the changes of contact pair up to this stage that a tick can reach
         const int se = (s < g.max_ticks ? s : g.max_ticks) - org;
         int changes = 0;
@@ -353,15 +389,26 @@ __device__ __forceinline__ void plan_record(const PlanGenDev& g, const PlanTimes
     }
 }
 
-__global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) { plan_record<false, false>(g, PlanTimes{}, nullptr, nullptr); }
-__global__ __launch_bounds__(kRecTile) void plan_record_replan_kernel(PlanGenDev g) { plan_record<true, false>(g, PlanTimes{}, nullptr, nullptr); }
+__global__ __launch_bounds__(kRecTile) void plan_record_kernel(PlanGenDev g) { plan_record<false, false, false>(g, PlanTimes{}, PlanSwing{}, nullptr, nullptr); }
+__global__ __launch_bounds__(kRecTile) void plan_record_replan_kernel(PlanGenDev g) { plan_record<true, false, false>(g, PlanTimes{}, PlanSwing{}, nullptr, nullptr); }
 __global__ __launch_bounds__(kRecTile) void plan_record_timed_kernel(PlanGenTimedDev t) {
     __shared__ int stl[kTabMax], ssl[kTabMax];
-    plan_record<false, true>(t.g, t.tm, stl, ssl);
+    plan_record<false, true, false>(t.g, t.tm, PlanSwing{}, stl, ssl);
 }
 __global__ __launch_bounds__(kRecTile) void plan_record_replan_timed_kernel(PlanGenTimedDev t) {
     __shared__ int stl[kTabMax], ssl[kTabMax];
-    plan_record<true, true>(t.g, t.tm, stl, ssl);
+    plan_record<true, true, false>(t.g, t.tm, PlanSwing{}, stl, ssl);
+}
+// their shaped siblings: what a plan uploaded with a non-zero swing profile runs (enqueue<> chooses), the profile a second argument
+__global__ __launch_bounds__(kRecTile) void plan_record_shaped_kernel(PlanGenDev g, PlanSwing sw) { plan_record<false, false, true>(g, PlanTimes{}, sw, nullptr, nullptr); }
+__global__ __launch_bounds__(kRecTile) void plan_record_replan_shaped_kernel(PlanGenDev g, PlanSwing sw) { plan_record<true, false, true>(g, PlanTimes{}, sw, nullptr, nullptr); }
+__global__ __launch_bounds__(kRecTile) void plan_record_timed_shaped_kernel(PlanGenTimedDev t, PlanSwing sw) {
+    __shared__ int stl[kTabMax], ssl[kTabMax];
+    plan_record<false, true, true>(t.g, t.tm, sw, stl, ssl);
+}
+__global__ __launch_bounds__(kRecTile) void plan_record_replan_timed_shaped_kernel(PlanGenTimedDev t, PlanSwing sw) {
+    __shared__ int stl[kTabMax], ssl[kTabMax];
+    plan_record<true, true, true>(t.g, t.tm, sw, stl, ssl);
 }
 
 // ---- the launch path: one implementation for the four forms - upload or replan (RP), untimed or timed (the argument's type)
@@ -370,10 +417,10 @@ const PlanGenDev& base(const PlanGenDev& g) { return g; }
 const PlanGenDev& base(const PlanGenTimedDev& t) { return t.g; }
 
 template <bool RP, class Arg> struct Passes;
-template <> struct Passes<false, PlanGenDev> { static constexpr auto prologue = plan_prologue_kernel, dcm = plan_dcm_kernel, record = plan_record_kernel; };
-template <> struct Passes<true, PlanGenDev> { static constexpr auto prologue = plan_prologue_replan_kernel, dcm = plan_dcm_replan_kernel, record = plan_record_replan_kernel; };
-template <> struct Passes<false, PlanGenTimedDev> { static constexpr auto prologue = plan_prologue_timed_kernel, dcm = plan_dcm_timed_kernel, record = plan_record_timed_kernel; };
-template <> struct Passes<true, PlanGenTimedDev> { static constexpr auto prologue = plan_prologue_replan_timed_kernel, dcm = plan_dcm_replan_timed_kernel, record = plan_record_replan_timed_kernel; };
+template <> struct Passes<false, PlanGenDev> { static constexpr auto prologue = plan_prologue_kernel, dcm = plan_dcm_kernel, record = plan_record_kernel; static constexpr auto shaped = plan_record_shaped_kernel; };
+template <> struct Passes<true, PlanGenDev> { static constexpr auto prologue = plan_prologue_replan_kernel, dcm = plan_dcm_replan_kernel, record = plan_record_replan_kernel; static constexpr auto shaped = plan_record_replan_shaped_kernel; };
+template <> struct Passes<false, PlanGenTimedDev> { static constexpr auto prologue = plan_prologue_timed_kernel, dcm = plan_dcm_timed_kernel, record = plan_record_timed_kernel; static constexpr auto shaped = plan_record_timed_shaped_kernel; };
+template <> struct Passes<true, PlanGenTimedDev> { static constexpr auto prologue = plan_prologue_replan_timed_kernel, dcm = plan_dcm_replan_timed_kernel, record = plan_record_replan_timed_kernel; static constexpr auto shaped = plan_record_replan_timed_shaped_kernel; };
 
 // an untimed plan has one (ss, ds) and a resolved final_ds; a timed one its three rows, and a final_ds of 0 for each last step's own ds
 bool durations_ok(const PlanGenDev& g) { return g.ss >= 1 && g.ds >= 1 && g.final_ds >= 1; }
@@ -392,25 +439,30 @@ void advance(PlanGenTimedDev& t, int i0) {
 // prologue, DCM pass and record pass in stream order.  An upload runs every robot, its record pass one launch per 65535 robots (they lie
 // on grid.y) with rec0 / rec1 recorded around it; a replan runs the listed robots and tiles and records nothing.
 template <bool RP, class Arg>
-int enqueue(const Arg& a, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) {
+int enqueue(const Arg& a, const PlanSwing& sw, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) {
     using P = Passes<RP, Arg>;
     const PlanGenDev& g = base(a);
     if (g.batch < 1 || g.traj_len < 1 || g.first_ds < 1 || g.K < 0 || !durations_ok(a)) return WCQP_E_INVALID;
     if (RP && (!g.origin || !g.robots || !g.tiles || !g.h0 || g.n_robots < 0 || g.n_tiles < 0)) return WCQP_E_INVALID;
     const int robots = RP ? g.n_robots : g.batch;
     if (robots == 0) return WCQP_OK;
+    // the record pass of one grid: an all-zero profile takes the kernels that know none, with the one argument they always took
+    auto record = [&](dim3 grid, const Arg& arg) {
+        if (sw.shaped()) hipLaunchKernelGGL(P::shaped, grid, dim3(kRecTile), 0, stream, arg, sw);
+        else hipLaunchKernelGGL(P::record, grid, dim3(kRecTile), 0, stream, arg);
+    };
     hipLaunchKernelGGL(P::prologue, dim3((unsigned)((robots + 63) / 64)), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(P::dcm, dim3((unsigned)((robots + kDcmRobots - 1) / kDcmRobots)), dim3(64), 0, stream, a);
     if (rec0) WCQP_HIP_TRY(hipEventRecord(rec0, stream));
     if (RP) {
-        if (g.n_tiles > 0) hipLaunchKernelGGL(P::record, dim3((unsigned)g.n_tiles), dim3(kRecTile), 0, stream, a);
+        if (g.n_tiles > 0) record(dim3((unsigned)g.n_tiles), a);
     } else {
         constexpr int kSlab = 65535;
         for (int i0 = 0; i0 < g.batch; i0 += kSlab) {
             Arg slab = a;
             advance(slab, i0);
             const int nb = g.batch - i0 < kSlab ? g.batch - i0 : kSlab;
-            hipLaunchKernelGGL(P::record, dim3((unsigned)((g.traj_len + kRecTile - 1) / kRecTile), (unsigned)nb), dim3(kRecTile), 0, stream, slab);
+            record(dim3((unsigned)((g.traj_len + kRecTile - 1) / kRecTile), (unsigned)nb), slab);
         }
     }
     if (rec1) WCQP_HIP_TRY(hipEventRecord(rec1, stream));
@@ -422,9 +474,9 @@ int enqueue(const Arg& a, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) 
 
 namespace wcqp {
 
-int plan_gen_enqueue(const PlanGenDev& g, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) { return enqueue<false>(g, stream, rec0, rec1); }
-int plan_gen_enqueue(const PlanGenTimedDev& t, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) { return enqueue<false>(t, stream, rec0, rec1); }
-int plan_replan_enqueue(const PlanGenDev& g, hipStream_t stream) { return enqueue<true>(g, stream, nullptr, nullptr); }
-int plan_replan_enqueue(const PlanGenTimedDev& t, hipStream_t stream) { return enqueue<true>(t, stream, nullptr, nullptr); }
+int plan_gen_enqueue(const PlanGenDev& g, const PlanSwing& sw, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) { return enqueue<false>(g, sw, stream, rec0, rec1); }
+int plan_gen_enqueue(const PlanGenTimedDev& t, const PlanSwing& sw, hipStream_t stream, hipEvent_t rec0, hipEvent_t rec1) { return enqueue<false>(t, sw, stream, rec0, rec1); }
+int plan_replan_enqueue(const PlanGenDev& g, const PlanSwing& sw, hipStream_t stream) { return enqueue<true>(g, sw, stream, nullptr, nullptr); }
+int plan_replan_enqueue(const PlanGenTimedDev& t, const PlanSwing& sw, hipStream_t stream) { return enqueue<true>(t, sw, stream, nullptr, nullptr); }
 
 }  // namespace wcqp

@@ -507,6 +507,7 @@ int wcqp_tick_get_option(wcqp_tick_t h, int32_t key, int32_t* value) {
     else if (key == WCQP_TICK_OPT_POSITION_STREAMED) *value = h->position && h->streamed ? 1 : 0;
     else if (key == WCQP_TICK_OPT_PLAN_SHIFT) *value = (int32_t)(h->plan_shift < INT32_MAX ? h->plan_shift : INT32_MAX);      // (reported only)
     else if (key == WCQP_TICK_OPT_PLAN_TIMED) *value = h->holds_plan() && h->uploaded && h->generated && h->gp.timed ? 1 : 0;      // (reported only)
+    else if (key == WCQP_TICK_OPT_SWING_PROFILE) *value = h->holds_plan() && h->uploaded && h->generated && h->gp.shaped() ? 1 : 0;      // (reported only)
     else return WCQP_E_INVALID;
     return WCQP_OK;
 }

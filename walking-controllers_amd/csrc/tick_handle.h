@@ -120,6 +120,9 @@ struct wcqp_tick_s {
     struct GenPlan {
         int ss = 0, ds = 0, final_ds = 0, cap = 0;
         double lift = 0.0, delta[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        // THE SHAPED SWING: the profile the upload took (the handle's swing_pending at that call); every replan of the plan keeps it
+        wcqp_tick_swing_profile swing{0.0, 0.0, 0.0, 0.0};
+        bool shaped() const { return swing.apex_ratio != 0.0 || swing.landing_velocity != 0.0 || swing.pitch_delta != 0.0 || swing.com_height_delta != 0.0; }
         std::vector<int> origin, first_ds, n_steps, keep;
         // a TIMED plan (wcqp_tick_upload_footsteps_timed): ss and ds are unused, final_ds is the upload's own value (0: a last step's own
         // ds), cap counts a step as two stages, and dur[i] holds the durations of robot i's plan in force, ss_k then ds_k per step
@@ -138,6 +141,8 @@ struct wcqp_tick_s {
             for (int k = 0; k < n; ++k) { dur[i][2 * k] = ss_k[k]; dur[i][2 * k + 1] = ds_k[k]; }
         }
     } gp;
+    // wcqp_tick_set_swing_profile: what the NEXT wcqp_tick_upload_footsteps* copies into gp.swing (a running plan never sees it)
+    wcqp_tick_swing_profile swing_pending{0.0, 0.0, 0.0, 0.0};
     // its per-call device memory (footsteps, robot and tile lists, footprint tables, set table), guarded behind the call's kernels
     StagedBlock rp;
     // The result rows of a goal call (wcqp_tick_replan_goals*), one contiguous run of B robots' rows for a planner of K steps - doubles,

@@ -195,6 +195,11 @@ PlanGenDev plan_gen_of(const wcqp_tick_s* h, int K) {
     for (int k = 0; k < 2; ++k) { g.delta[0][k] = gp.delta[0][k]; g.delta[1][k] = gp.delta[1][k]; }
     return g;
 }
+// ... and the swing profile of the plan in force, the shaped record kernels' second argument (all zero: the launch path takes the others)
+PlanSwing plan_swing_of(const wcqp_tick_s* h) {
+    const wcqp_tick_swing_profile& s = h->gp.swing;
+    return PlanSwing{s.apex_ratio, s.landing_velocity, s.pitch_delta, s.com_height_delta};
+}
 
 // the support-polygon row sets of a plan whose records are in place (in NULL-stream order): the previous upload's go, `ns` new ones are built
 // on the device from the records of their stages (at: record offsets, code: contact pairs - device arrays), and the handle's kernels see them
@@ -478,8 +483,8 @@ int replan_enqueue(wcqp_tick_s* h, const ReplanCall& c, int K, int fd, const Rep
     if (gp.timed) {
         const PlanGenTimedDev t{g, PlanTimes{reinterpret_cast<const int*>(buf + steps.ss), reinterpret_cast<const int*>(buf + steps.ds),
                                              reinterpret_cast<int*>(buf + o_start), gp.final_ds}};
-        if (const int rc = wcqp::plan_replan_enqueue(t, st); rc != WCQP_OK) return rc;
-    } else if (const int rc = wcqp::plan_replan_enqueue(g, st); rc != WCQP_OK) return rc;
+        if (const int rc = wcqp::plan_replan_enqueue(t, plan_swing_of(h), st); rc != WCQP_OK) return rc;
+    } else if (const int rc = wcqp::plan_replan_enqueue(g, plan_swing_of(h), st); rc != WCQP_OK) return rc;
     hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
                        h->set_A, h->set_b, h->set_nc);
     WCQP_HIP_TRY(hipGetLastError());
@@ -553,6 +558,7 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
         auto& gp = h->gp;
         gp.ss = tm ? 0 : steps->ss_ticks; gp.ds = tm ? 0 : steps->ds_ticks; gp.final_ds = final_ds; gp.cap = cap; gp.lift = steps->lift;
         gp.timed = tm != nullptr;
+        gp.swing = h->swing_pending;
         for (int k = 0; k < 2; ++k) { gp.delta[0][k] = steps->zmp_delta_left[k]; gp.delta[1][k] = steps->zmp_delta_right[k]; }
     }
     // the footsteps, the table and the set table: device memory of this call
@@ -589,8 +595,8 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
     g.n_steps = d_n; g.side = d_side; g.target = d_tg; g.set_base = d_base; g.table = d_tab; g.set_at = d_at; g.set_code = d_code;
     g.first_ds = steps->first_ds_ticks;
     for (hipEvent_t& e : h->gen_ev) if (!e) WCQP_HIP_TRY(hipEventCreate(&e));
-    int rc = tm ? wcqp::plan_gen_enqueue(PlanGenTimedDev{g, PlanTimes{d_ssk, d_dsk, d_start, final_ds}}, nullptr, h->gen_ev[0], h->gen_ev[1])
-                : wcqp::plan_gen_enqueue(g, nullptr, h->gen_ev[0], h->gen_ev[1]);
+    int rc = tm ? wcqp::plan_gen_enqueue(PlanGenTimedDev{g, PlanTimes{d_ssk, d_dsk, d_start, final_ds}}, plan_swing_of(h), nullptr, h->gen_ev[0], h->gen_ev[1])
+                : wcqp::plan_gen_enqueue(g, plan_swing_of(h), nullptr, h->gen_ev[0], h->gen_ev[1]);
     if (rc == WCQP_OK) rc = build_plan_sets(h, ns, d_at, d_code);      // (synchronises)
     if (rc != WCQP_OK) return rc;
     WCQP_HIP_TRY(hipEventElapsedTime(&h->gen_record_ms, h->gen_ev[0], h->gen_ev[1]));
@@ -732,6 +738,27 @@ int wcqp_tick_replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_ti
 int wcqp_tick_replan_goals_timed(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_timing* tm, const wcqp_tick_goals* gl, void* stream) {
     if (!tm) return WCQP_E_INVALID;
     return replan_goals(h, planner, tm, gl, stream);
+}
+
+// THE SHAPED SWING (include/wcqp.h): host only.  The profile waits on the handle for the next wcqp_tick_upload_footsteps*
+int wcqp_tick_set_swing_profile(wcqp_tick_t h, const wcqp_tick_swing_profile* p) {
+    if (!h || !p) return WCQP_E_INVALID;
+    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
+    if (!std::isfinite(p->apex_ratio) || !std::isfinite(p->landing_velocity) || !std::isfinite(p->pitch_delta) || !std::isfinite(p->com_height_delta))
+        return WCQP_E_INVALID;
+    if (p->apex_ratio < 0.0 || p->apex_ratio >= 1.0 || p->landing_velocity > 0.0) return WCQP_E_INVALID;
+    if (p->landing_velocity != 0.0 && p->apex_ratio == 0.0) return WCQP_E_INVALID;      // (the quartic has no landing branch)
+    if (std::fabs(p->pitch_delta) > 0.78539816339744830962) return WCQP_E_INVALID;
+    h->swing_pending = *p;
+    return WCQP_OK;
+}
+
+int wcqp_tick_get_swing_profile(wcqp_tick_t h, wcqp_tick_swing_profile* out) {
+    if (!h || !out) return WCQP_E_INVALID;
+    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
+    const bool in_force = h->uploaded && h->generated;      // (a classically uploaded plan has none)
+    *out = in_force ? h->gp.swing : wcqp_tick_swing_profile{0.0, 0.0, 0.0, 0.0};
+    return WCQP_OK;
 }
 
 // THE REBASED PLAN (include/wcqp.h).  The host decides - on the timelines of the plans in force, settled first - and keeps its own

@@ -593,6 +593,12 @@ def synth_planned_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_ba
 ZMP_DELTA = ((0.03, -0.005), (0.03, 0.005))       # leftZMPDelta / rightZMPDelta (plannerParams.ini:39-40)
 
 
+def shipped_swing_profile() -> dict:
+    """The swing profile plannerParams.ini ships (footApexTime :31, stepLandingVelocity :30, pitchDelta :46 - degrees there, radians
+    here -, comHeightDelta :32), as the keyword arguments of TickPipeline.set_swing_profile."""
+    return dict(apex_ratio=0.8, landing_velocity=0.0, pitch_delta=0.0, com_height_delta=0.01)
+
+
 def synth_footstep_walk_batch(count: int, n_ticks: int, poses: np.ndarray, kin_batch: dict, seed: int = 4242, horizon: int = 50,
                               first: int = 0, step_ticks: int = 180, ds_ticks: int = 110, n_steps: int = 4, step_length=(0.025, 0.035),
                               yaw_step=(0.0, 0.0), lift: float = 0.02, dT: float = 0.01, com_height: float = 0.53, gravity: float = 9.81) -> dict:
