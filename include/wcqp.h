@@ -945,7 +945,9 @@ int wcqp_tick_upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const 
  * that is not uploaded, a NULL pointer, first_ds_ticks < 1, and for a robot that replans: n_steps outside 0..K', a side above 1 or a
  * non-finite target of a step it takes, M_i = 0 or < -1, M_i < the ticks enqueued so far (within one wcqp_tick_run call the kernel reads a
  * stage ahead, between calls nothing is ahead), M_i >= T, M_i below the stage its current plan was generated from, or a stage M_i that
- * lies in a single support of its current plan.  WCQP_E_UNSUPPORTED on a TIMED plan (wcqp_tick_replan_footsteps_timed, below, replans
+ * lies in a single support of its current plan; also for a robot whose support-polygon set slots cannot take the new plan's sets - two
+ * per step that starts at a stage <= max_ticks -, which happens only after wcqp_tick_restart_robots calls (each takes a slot with no
+ * step behind it) and until wcqp_tick_rebase_plan frees the slots of past stages.  WCQP_E_UNSUPPORTED on a TIMED plan (wcqp_tick_replan_footsteps_timed, below, replans
  * those).  Not offered: replanning a classically uploaded plan, device pointers (the goal form below, wcqp_tick_replan_goals, keeps the
  * footsteps on the device: they are planned there and never visit the host). */
 typedef struct wcqp_tick_replan {         /* HOST pointers, copied before the call returns */
@@ -997,6 +999,62 @@ int wcqp_tick_replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, void* 
  * Not offered: rebasing a classically uploaded plan, per-robot shifts, a tick offset inside the kernels (noise, logs). */
 #define WCQP_TICK_REBASE_AUTO (-1)
 int wcqp_tick_rebase_plan(wcqp_tick_t h, int32_t shift, void* stream);
+/* Stopped robots of a running fleet restarted per robot (the reference leaves that state per robot: stopWalking -> prepareRobot ->
+ * startWalking, WM/src/WalkingModule.cpp).  A robot whose IK fails once is stopped for good - ik_fail[i] > 0, dq = 0 from then on - and
+ * wcqp_tick_upload* rewinds EVERY robot of the handle.  wcqp_tick_restart_robots applies the upload's rules to the listed robots alone, at
+ * the stage S the next tick will read (the ticks enqueued so far), on the device.  mode [B]: KEEP - the robot keeps state and plan, none
+ * of its rows is read (they may hold NaN) -, ALWAYS, or IF_STOPPED - the DEVICE decides: the robot restarts iff ik_fail[i] > 0 when the
+ * call's kernels run, behind the ticks already enqueued.  THE RESTARTED ROBOT (tests/helpers/plan_restart.py restates its plan on the
+ * windows wcqp_tick_get_plan returns):
+ *   Plan        stages below S stay bit for bit: records, ref_traj, dcm_vel and the row sets those stages name.  Every stage >= S is the
+ *               same STANDING stage: both feet in contact, the fixed-frame bit = left, the two soles of state0 (entries 24..47), twists 0,
+ *               CoM height state0[68] with velocity 0, ref_traj = the ZMP = the midpoint of the two feet's points p_xy + R_2x2 delta
+ *               (zmp_delta_* of the upload; each operation rounded on its own), dcm_vel 0, and entry 39 names ONE new support-polygon
+ *               set, built from these feet by the classic rule in the robot's next free slot.  A standing stage has no swing, so a swing
+ *               profile in force changes nothing of it; timed and untimed plans alike.
+ *   Plan in force  "generated from S, no steps": wcqp_tick_replan_footsteps* and wcqp_tick_replan_goals* with M_i >= S send the robot
+ *               walking again (they read the soles of record M_i, as always), and wcqp_tick_rebase_plan admits it, because it stands.
+ *   State       what wcqp_tick_upload_footsteps does for every robot, for this one: the MPC chain's records, the live hull rows marked
+ *               unbuilt (the first tick builds them), the contact pair "both", the desired CoM height, the pose block (= the row of
+ *               state0), q_des = q0, DCM = dcm0, CoM = com0 (and its references), measured ZMP and previous command = u_init, previous
+ *               velocities 0, the gain smoother at rest at the stance gains, and mpc_fail, ik_fail, hot_try, hot_hit, the previous
+ *               active set and (POSITION) ik_iters at 0.  dcm0 / u_init NULL: the standing stage's ZMP above, for every listed robot.
+ *               NOT touched: the tick index (the robot goes on at tick S with the fleet: u0_log, dq_log, q_log rows below S stay), the
+ *               logs, any other robot's row, any pointer a tick or a captured graph holds.  Between wcqp_tick_run calls nothing is ahead
+ *               of anything: the next call primes its own first tick and rewrites the whole MPC -> IK hand-off record of parity S & 1.
+ * Enqueue-only: the host rows of the LISTED robots are staged before the call returns (the block a replan stages through; a kept robot's
+ * rows are not even copied), three kernels run on `stream` behind the ticks already enqueued, and one small row per listed robot -
+ * restarted or not, and its ik_fail just before - travels back behind an event of its own.  With IF_STOPPED the host does not know who
+ * restarted until then: the robot's plan in force is OWED, as a goal call owes step counts, and the next call that reads a timeline or a
+ * slot count waits for THAT event first, nothing else.  A robot listed ALWAYS owes nothing.  Pending goal and rebase calls are settled
+ * first.  Valid between wcqp_tick_run calls.  A call that lists no robot returns WCQP_OK and enqueues nothing.
+ * Everything is checked on the host before anything changes; a refused call leaves the handle as it was.
+ * WCQP_E_UNSUPPORTED: a handle that holds no plan; plant = EXTERNAL or a resident plan (the caller's plant is the state there); a plan that
+ * was not generated (wcqp_tick_info.plan_generated = 0).  WCQP_E_INVALID: not uploaded; mode, state0, q0 or com0 NULL; a mode above 2; a
+ * non-finite value in state0, q0, com0, dcm0 or u_init of a robot whose mode is not KEEP; S > max_ticks; a listed robot whose set slots
+ * cannot take one more set (IF_STOPPED counts as if it restarted) - wcqp_tick_rebase_plan frees the slots of past stages.
+ * SLOTS: a restart takes one of the robot's set slots with no step behind it, so it also takes room from the replans that follow: a
+ * footstep or goal replan whose new sets would not fit returns WCQP_E_INVALID (see there) until a rebase.  cap has room for one step
+ * more than can start within max_ticks, so a robot restarted over and over without a rebase between runs out.
+ * Not offered: device-pointer inputs, a restart at a stage other than S, EXTERNAL and resident handles, a per-robot tick index. */
+#define WCQP_TICK_RESTART_KEEP        0
+#define WCQP_TICK_RESTART_ALWAYS      1
+#define WCQP_TICK_RESTART_IF_STOPPED  2
+typedef struct wcqp_tick_restart {        /* HOST pointers, staged before the call returns */
+    const uint8_t* mode;                  /* [B] WCQP_TICK_RESTART_* */
+    const double*  state0;                /* [B][87]: entries 24..47 (the two soles) and 68 (CoM height) make the plan, the row becomes the pose block */
+    const double*  q0;                    /* [B][dof] */
+    const double*  com0;                  /* [B][2] */
+    const double*  dcm0;                  /* [B][2] or NULL: the standing stage's ZMP */
+    const double*  u_init;                /* [B][2] or NULL: the same */
+} wcqp_tick_restart;
+int wcqp_tick_restart_robots(wcqp_tick_t h, const wcqp_tick_restart* r, void* stream);
+typedef struct wcqp_tick_restart_result { /* HOST pointers, any may be NULL */
+    uint8_t* restarted;                   /* [B] 1: the robot was restarted by the last call */
+    int64_t* stopped_ticks;               /* [B] its ik_fail just before (0 if not restarted) */
+    int32_t* stage;                       /* the stage S of the last call */
+} wcqp_tick_restart_result;
+int wcqp_tick_get_restart_result(wcqp_tick_t h, const wcqp_tick_restart_result* out);   /* waits for that call's event only */
 /* Per-step timings: every footstep carries its own durations (the reference's planner gives every step its own, between minStepDuration
  * and maxStepDuration; wcqp_unicycle_plan_timed_* below chooses them and fills exactly these two arrays).  THE TIMED PLAN is the plan
  * wcqp_tick_upload_footsteps defines (tests/helpers/footstep_plan_timed.py restates it), with four changes:
@@ -1099,7 +1157,10 @@ typedef struct wcqp_unicycle_s* wcqp_unicycle_t;       /* the unicycle planner's
  * wcqp_tick_replan_footsteps (no planned_trajectories or resident plan, a plan that was not generated); WCQP_E_INVALID for a NULL handle,
  * planner, struct or goal, a handle that is not uploaded, first_ds_ticks < 1, min_lead_ticks < 0, and for a robot that does not KEEP: a
  * merge_stage below -2 or an explicit one that breaks the rules of wcqp_tick_replan_footsteps, a first_side other than 0, 1 or 255, a
- * non-finite goal.  Every robot KEEP or TOO_LATE: WCQP_OK, nothing enqueued.
+ * non-finite goal; also for a robot whose set slots cannot take the sets of the steps the device MAY choose - two for each of at most K
+ * steps that can start at a stage <= max_ticks, the first at M_i + first_ds_ticks, the others ss + ds stages apart (a timed plan:
+ * min_step_ticks) - which, as for wcqp_tick_replan_footsteps, happens only to a robot that spent slots on wcqp_tick_restart_robots
+ * calls since the last rebase.  Every robot KEEP or TOO_LATE: WCQP_OK, nothing enqueued.
  * The step count of a goal-replanned robot is known to the host only when the rows are back: every later call that needs it
  * (wcqp_tick_replan_footsteps, wcqp_tick_replan_goals, wcqp_tick_get_goal_result) first waits for THAT call's event, nothing else. */
 #define WCQP_TICK_MERGE_KEEP  (-1)   /* robot keeps its plan; none of its rows is read */

@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
     "wcqp_tick_upload_footsteps", "wcqp_tick_upload_footsteps_timed", "wcqp_tick_replan_footsteps_timed", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
-    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan", "wcqp_tick_set_swing_profile", "wcqp_tick_get_swing_profile",
+    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan", "wcqp_tick_restart_robots", "wcqp_tick_get_restart_result", "wcqp_tick_set_swing_profile", "wcqp_tick_get_swing_profile",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
     "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
@@ -286,6 +286,20 @@ class TickGoalResult(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in GOAL_RESULT]
 
 
+TICK_RESTART_KEEP, TICK_RESTART_ALWAYS, TICK_RESTART_IF_STOPPED = 0, 1, 2
+
+
+class TickRestart(C.Structure):
+    """wcqp_tick_restart: per robot the mode (TICK_RESTART_*) and the rows a restarted robot starts from - state0 [B][87], q0 [B][dof],
+    com0 [B][2], dcm0 / u_init [B][2] or NULL (the standing stage's ZMP)."""
+    _fields_ = [(k, C.c_void_p) for k in ("mode", "state0", "q0", "com0", "dcm0", "u_init")]
+
+
+class TickRestartResult(C.Structure):
+    """wcqp_tick_restart_result: what wcqp_tick_get_restart_result fills - restarted [B] (uint8), stopped_ticks [B] (int64), stage (one int32)."""
+    _fields_ = [(k, C.c_void_p) for k in ("restarted", "stopped_ticks", "stage")]
+
+
 UNICYCLE_DONE, UNICYCLE_TRUNCATED, UNICYCLE_STUCK, UNICYCLE_INVALID_INPUT = range(4)
 
 
@@ -337,7 +351,7 @@ ABI_STRUCTS = {
     "wcqp_tick_inputs": TickInputs, "wcqp_tick_outputs": TickOutputs, "wcqp_tick_info": TickInfo, "wcqp_tick_info_ext": TickInfoExt,
     "wcqp_tick_desired": TickDesired, "wcqp_tick_footsteps": TickFootsteps, "wcqp_tick_replan": TickReplan, "wcqp_tick_plan_window": TickPlanWindow,
     "wcqp_tick_goals": TickGoals, "wcqp_tick_goal_result": TickGoalResult, "wcqp_tick_step_timing": TickStepTiming,
-    "wcqp_tick_swing_profile": TickSwingProfile,
+    "wcqp_tick_swing_profile": TickSwingProfile, "wcqp_tick_restart": TickRestart, "wcqp_tick_restart_result": TickRestartResult,
     "wcqp_unicycle_params": UnicycleParams, "wcqp_unicycle_inputs": UnicycleInputs, "wcqp_unicycle_outputs": UnicycleOutputs,
     "wcqp_unicycle_timing": UnicycleTiming,
 }
@@ -348,7 +362,7 @@ ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
     "IK_JAC_AUTO IK_JAC_MIXED IK_JAC_GENERAL PLAN_WAYS_AUTO SLAB_IN_ARRAYS SLAB_OUT_ARRAYS KIN_MAX_DOF "
     "KIN_HANDOFF_FUSED KIN_HANDOFF_DENSE KIN_HANDOFF_COMPACT TICK_PLANT_INTERNAL TICK_PLANT_EXTERNAL TICK_DCM_MPC TICK_DCM_REACTIVE "
     "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED TICK_OPT_PLAN_TIMED TICK_OPT_PLAN_SHIFT TICK_OPT_SWING_PROFILE TICK_REBASE_AUTO UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
-    "TICK_MERGE_KEEP TICK_MERGE_AUTO TICK_SIDE_AUTO GOAL_KEPT GOAL_TOO_LATE").split()}
+    "TICK_MERGE_KEEP TICK_MERGE_AUTO TICK_SIDE_AUTO GOAL_KEPT GOAL_TOO_LATE TICK_RESTART_KEEP TICK_RESTART_ALWAYS TICK_RESTART_IF_STOPPED").split()}
 
 _lib: Optional[C.CDLL] = None
 
@@ -414,6 +428,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_replan_footsteps.argtypes = [C.c_void_p, C.POINTER(TickReplan), C.c_void_p]
         L.wcqp_tick_replan_goals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickGoals), C.c_void_p]
         L.wcqp_tick_rebase_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.wcqp_tick_restart_robots.argtypes = [C.c_void_p, C.POINTER(TickRestart), C.c_void_p]
+        L.wcqp_tick_get_restart_result.argtypes = [C.c_void_p, C.POINTER(TickRestartResult)]
         L.wcqp_tick_set_swing_profile.argtypes = [C.c_void_p, C.POINTER(TickSwingProfile)]
         L.wcqp_tick_get_swing_profile.argtypes = [C.c_void_p, C.POINTER(TickSwingProfile)]
         L.wcqp_tick_get_goal_result.argtypes = [C.c_void_p, C.POINTER(TickGoalResult)]
@@ -998,6 +1014,35 @@ class TickPipeline(_Handle):
         before = self.option(TICK_OPT_PLAN_SHIFT)
         check(lib().wcqp_tick_rebase_plan(self._h, TICK_REBASE_AUTO if shift is None else int(shift), stream or None), "wcqp_tick_rebase_plan")
         return self.option(TICK_OPT_PLAN_SHIFT) - before
+
+    def restart_robots(self, mode, data: dict, stream: Optional[int] = None):
+        """Stopped robots restarted per robot, on the device (wcqp_tick_restart_robots, which defines the restarted robot): mode [B] of
+        TICK_RESTART_KEEP / TICK_RESTART_ALWAYS / TICK_RESTART_IF_STOPPED (the device decides: ik_fail > 0); data: state0 [B][87], q0 [B][dof],
+        com0 [B][2] and optionally dcm0 / u_init [B][2] (missing or None: the standing stage's ZMP).  A restarted robot has the state of an
+        upload and stands, from the stage the next tick reads, on the soles of state0; replan_footsteps / replan_goals send it walking
+        again.  Rows of KEEP robots are not read.  Enqueue-only on `stream`; the arrays are copied before the call returns.
+        The rows can come from the batched start posture: p = PrepareSolver(...).solve_host(left_d, right_d, com_d, q_guess) gives
+        restart_robots(mode, dict(state0=p["state"], q0=p["q"], com0=com_d[:, :2]))."""
+        if not self._holds_plan():
+            raise ValueError("restart_robots on a handle created without planned_trajectories=True (or resident_plan=True)")
+        m = np.ascontiguousarray(mode, dtype=np.uint8)
+        keep = {k: _f64(data[k]) for k in ("state0", "q0", "com0")}
+        for k in ("dcm0", "u_init"):
+            if data.get(k) is not None:
+                keep[k] = _f64(data[k])
+        assert m.shape == (self.batch,) and keep["state0"].shape == (self.batch, IK_STATE_LEN) and keep["q0"].ndim == 2 and \
+            keep["q0"].shape[0] == self.batch and all(keep[k].shape == (self.batch, 2) for k in keep if k not in ("state0", "q0")), \
+            (m.shape, {k: v.shape for k, v in keep.items()})
+        rs = TickRestart(m.ctypes.data, *(keep[k].ctypes.data if k in keep else None for k in ("state0", "q0", "com0", "dcm0", "u_init")))
+        check(lib().wcqp_tick_restart_robots(self._h, C.byref(rs), stream or None), "wcqp_tick_restart_robots")
+
+    def restart_result(self) -> dict:
+        """What the last restart_robots call did (wcqp_tick_get_restart_result; waits for that call only): restarted [B] (bool),
+        stopped_ticks [B] (the robot's ik_fail just before; 0 if it was not restarted) and stage, the stage S it restarted at."""
+        out = dict(restarted=np.zeros(self.batch, np.uint8), stopped_ticks=np.zeros(self.batch, np.int64), stage=np.zeros(1, np.int32))
+        res = TickRestartResult(**{k: v.ctypes.data for k, v in out.items()})
+        check(lib().wcqp_tick_get_restart_result(self._h, C.byref(res)), "wcqp_tick_get_restart_result")
+        return dict(restarted=out["restarted"].astype(bool), stopped_ticks=out["stopped_ticks"], stage=int(out["stage"][0]))
 
     def set_swing_profile(self, apex_ratio: float = 0.0, landing_velocity: float = 0.0, pitch_delta: float = 0.0, com_height_delta: float = 0.0):
         """The shape of the steps the NEXT upload_footsteps / upload_goal generates (wcqp_tick_set_swing_profile, which defines the shaped

@@ -74,9 +74,39 @@ struct PlanRebaseDev {
     double omega, a;                // a = exp(omega dT)
 };
 
+// wcqp_tick_restart_robots (plan_restart.hip): the listed robots - slot r of the call is robot robots[r] - decided on the device, and those
+// that restart reset to the staged rows and put on a standing plan from stage S on.  The staged rows are compact, one per SLOT
+struct PlanRestartDev {
+    const int* robots;              // [n_robots]
+    const unsigned char* mode;      // [n_robots] WCQP_TICK_RESTART_ALWAYS / _IF_STOPPED
+    const double* state0;           // [n_robots][kStateLen]
+    const double* q0;               // [n_robots][kDof]
+    const double* com0;             // [n_robots][2]
+    const double* dcm0;             // [n_robots][2], or NULL: the standing stage's ZMP
+    const double* u0;               // [n_robots][2], or NULL: the same
+    const int* set_slot;            // [n_robots] the robot's next free slot of the row sets: where its standing set goes
+    const int2* tiles;              // [n_tiles] (slot, 64-stage tile): the tiles at or above S / 64
+    // what the first kernel writes per slot for the second, and for the host
+    double* pattern;                // [n_robots][kPlanRec] the standing record
+    double* mid;                    // [n_robots][2] its ref_traj entry, the ZMP
+    int* restarted;                 // [n_robots] 1: the robot restarts
+    long long* stopped;             // [n_robots] its ik_fail just before (0 if it does not)
+    long long* set_at; int* set_code;               // plan_hull_sets_kernel's table, indexed by set slot (memset to -1 ahead of the kernels)
+    double* rec; double* ref; double* vel;          // the plan, as in PlanRebaseDev
+    // the state wcqp::upload_state sets (tick.hip), every array indexed by ROBOT; NULL where the handle keeps none
+    double *mst, *state, *q_des, *dq_prev, *dcm, *com, *c_ref, *p_star, *zmp_meas, *u_prev, *v_ref_prev, *v_star_prev, *zs, *com_h0;
+    int *sel_built, *live_nc, *sel;
+    long long *mpc_fail, *ik_fail, *hot_try, *hot_hit, *ik_iters;
+    unsigned *ik_lo, *ik_up;
+    int n_robots, n_tiles, traj_len, stage;         // stage: S
+    double delta[2][2];             // zmp_delta_left / zmp_delta_right
+};
+
 }  // namespace wcqp_tick
 
 namespace wcqp {
+// its two kernels in stream order: decide-and-reset over the slots, then the fill over the tiles.  Enqueue-only
+int plan_restart_enqueue(const wcqp_tick::PlanRestartDev& g, hipStream_t stream);
 // its two kernels in stream order: d_i, the ZMP of the new stage 0 and the tick index first, then the rows.  Enqueue-only
 int plan_rebase_enqueue(const wcqp_tick::PlanRebaseDev& g, hipStream_t stream);
 // prologue, DCM pass and record pass of one upload, in stream order (plan_gen.hip); rec0 / rec1 (or NULL): events recorded around the record

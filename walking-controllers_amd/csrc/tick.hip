@@ -521,6 +521,7 @@ int wcqp_tick_destroy(wcqp_tick_t h) {
     for (StagedBlock* b : {&h->splice, &h->rp, &h->run}) b->release();
     h->goal.release();
     h->rebase.release();
+    h->restart.release();
     for (hipEvent_t e : h->gen_ev) if (e) (void)hipEventDestroy(e);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->kin) wcqp_kin_destroy(h->kin);
@@ -622,6 +623,10 @@ int wcqp::upload_state(wcqp_tick_s* h, const wcqp_tick_inputs* in, int pair0) {
     h->feedback_set = false;
     h->desired_set = false; h->plan_staged = false;
     h->run.pending = false;
+    // (the device was synchronised above: nothing of a goal, rebase or restart call before this upload is owed or on its way any more,
+    // and wcqp_tick_get_restart_result has no call of this upload to report)
+    h->goal.pending = false; h->goal.owed.clear(); h->rebase.pending = false;
+    h->restart.pending = false; h->restart.owed.clear(); h->restart.called = false;
     return WCQP_OK;
 }
 

@@ -199,7 +199,40 @@ struct wcqp_tick_s {
             host = nullptr; ev = nullptr; pending = false;
         }
     } rebase;
+    // wcqp_tick_restart_robots: one row per LISTED robot (slot r of the call: robot robots[r]) comes back into `host` (pinned: the
+    // decisions [n] as int32 behind the ik_fail rows [n] as int64) behind `ev`.  A robot listed ALWAYS is on its standing plan in gp at
+    // once; one listed IF_STOPPED is `owed` - the device decides - and settle() puts it on the standing plan (origin `stage`, no steps,
+    // `keep_new` slots in use) if its row says it restarted.  The rows stay for wcqp_tick_get_restart_result
+    struct RestartCall {
+        char* host = nullptr; size_t host_cap = 0;
+        hipEvent_t ev = nullptr;
+        bool called = false, pending = false;           // pending: the rows are still on their way
+        int stage = 0;
+        std::vector<int> robots, keep_new, owed;        // by slot: the robot, its slot count if it restarts; the slots still owed
+        const long long* stopped() const { return reinterpret_cast<const long long*>(host); }
+        const int* restarted() const { return reinterpret_cast<const int*>(host + robots.size() * 8); }
+        int wait() {
+            if (pending) { WCQP_HIP_TRY(hipEventSynchronize(ev)); pending = false; }
+            return WCQP_OK;
+        }
+        void release() {
+            if (host) (void)hipHostFree(host);
+            if (ev) (void)hipEventDestroy(ev);
+            host = nullptr; host_cap = 0; ev = nullptr; pending = false; called = false; owed.clear();
+        }
+    } restart;
+    // robot i stands from stage S on: the plan in force wcqp_tick_restart_robots leaves
+    void stand_from(size_t i, int S, int keep_new) {
+        gp.origin[i] = S; gp.first_ds[i] = 0; gp.keep[i] = keep_new;
+        gp.set_steps(i, 0, nullptr, nullptr);
+    }
     int settle() {
+        if (!restart.owed.empty()) {
+            if (const int rc = restart.wait(); rc != WCQP_OK) return rc;
+            for (int r : restart.owed)
+                if (restart.restarted()[r]) stand_from((size_t)restart.robots[r], restart.stage, restart.keep_new[r]);
+            restart.owed.clear();
+        }
         if (const int rc = goal.wait(); rc != WCQP_OK) return rc;
         if (!goal.owed.empty()) {
             const GoalRows& r = goal.rows;

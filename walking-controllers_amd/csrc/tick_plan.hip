@@ -358,22 +358,34 @@ struct ReplanCall {
     explicit ReplanCall(size_t B) : merge(B, -1), keep(B, 0) {}
 };
 
-// Robot i joins the call at merge stage M (already found allowed: wcqp_goal::merge_allowed).  fresh: the timeline of its new plan, from M
-// on - without steps where the device plans them.  Its surviving sets are those of stages <= M (a set of stage M itself is built from
-// the feet the new plan starts from); the new plan's sets follow them in the robot's `cap` slots.  That they fit needs no new steps: cap
-// (upload_footsteps) bounds the steps that START at a stage <= max_ticks for ANY footstep list - an untimed step occupies ss + 1 stages or
-// more, a timed one a stage of single and a stage of double support - and the stitched plan is one such list, so the count below is a
-// check of the arithmetic where the new steps are known, and the steps and durations the device chooses fit as well.
-int replan_admit(const wcqp_tick_s* h, size_t i, int M, const wcqp_goal::Timeline& fresh_plan, ReplanCall& c) {
+// Robot i joins the call at merge stage M (already found allowed: wcqp_goal::merge_allowed).  fresh: the sets its new plan builds behind
+// M where a tick can reach them - counted on the caller's list, or, where the device plans the steps, bounded by goal_sets_bound below.
+// Its surviving sets are those of stages <= M (a set of stage M itself is built from the feet the new plan starts from); the new
+// plan's sets follow them in the robot's `cap` slots, and a call whose sets would pass them is refused: plan_prologue writes its set
+// table without a bound of its own.  cap (upload_footsteps) bounds the steps that START at a stage <= max_ticks for ANY stitched footstep
+// list - an untimed step occupies ss + 1 stages or more, a timed one a stage of single and a stage of double support -, so for a robot
+// that only ever walked the check never fires.  It fires for a robot that spent slots on restarts (wcqp_tick_restart_robots takes one
+// per call, with no step behind it) since the last rebase: that robot is refused here until wcqp_tick_rebase_plan has freed them.
+int replan_admit(const wcqp_tick_s* h, size_t i, int M, int fresh, ReplanCall& c) {
     const auto& gp = h->gp;
     const int c0 = gp.keep[i] + gp.timeline(i).sets_up_to(M < h->p.max_ticks ? M : h->p.max_ticks);
-    const int fresh = fresh_plan.sets_up_to(h->p.max_ticks);
-    if (c0 < 1 || c0 + fresh > gp.cap) return WCQP_E_INVALID;      // (cannot happen: see cap in wcqp_tick_upload_footsteps)
+    if (c0 < 1 || c0 + fresh > gp.cap) return WCQP_E_INVALID;
     c.merge[i] = M; c.keep[i] = c0;
     c.robots.push_back((int)i);
     const int n_tile = (h->d.traj_len + 63) / 64;
     for (int tl = M / 64; tl < n_tile; ++tl) { c.tiles.push_back((int)i); c.tiles.push_back(tl); }
     return WCQP_OK;
+}
+
+// The sets a goal call's new plan can build, whatever steps the device chooses: at most K steps, the first at stage M + fd, each `spacing`
+// stages or more behind the one before (an untimed plan: exactly ss + ds; a timed one: the planner's min_step_ticks, two at least), two
+// sets for each that starts at a stage <= max_ticks.  With floor(M / L) steps landed by M at most (L = ss + 1, or 2) this stays within
+// cap for every stitched list of steps: floor(M / L) + floor((max_ticks - M - 1) / L) + 1 <= (max_ticks + 1) / L + 1
+int goal_sets_bound(int K, int M, int fd, long long spacing, int max_ticks) {
+    const long long room = (long long)max_ticks - M - fd;
+    if (room < 0 || K < 1) return 0;
+    const long long n = room / (spacing < 2 ? 2 : spacing) + 1;
+    return 2 * (int)(n < K ? n : K);
 }
 
 // where the footsteps of a replan come from: the caller's lists (wcqp_tick_replan_footsteps), or goals the device plans from
@@ -608,6 +620,7 @@ int upload_footsteps(wcqp_tick_t h, const wcqp_tick_inputs* in, const wcqp_tick_
         gp.n_steps.assign(B, 0); gp.dur.assign(tm ? B : 0, std::vector<int>());
         for (size_t i = 0; i < B; ++i) gp.set_steps(i, steps->n_steps[i], tm ? tm->ss_ticks + i * K : nullptr, tm ? tm->ds_ticks + i * K : nullptr);
         h->rp.pending = false; h->goal.pending = false; h->goal.owed.clear(); h->rebase.pending = false;      // (the device was synchronised above)
+        h->restart.pending = false; h->restart.owed.clear(); h->restart.called = false;
     }
     WCQP_HIP_TRY(hipMemset(const_cast<int*>(d.phase0.get()), 0, B * 4));
     WCQP_HIP_TRY(hipMemset(const_cast<double*>(d.swing_twist.get()), 0, B * 48));
@@ -653,7 +666,7 @@ int replan_footsteps(wcqp_tick_t h, const wcqp_tick_replan* rp, const wcqp_tick_
         if (!footsteps_valid(i, K, rp->n_steps, rp->side, rp->target)) return WCQP_E_INVALID;
         const wcqp_goal::Timeline fresh = list_timeline(i, K, M, fd, rp->n_steps[i], tm, gp.ss, gp.ds);
         if (tm && (!fresh.durations_valid() || !wcqp_goal::stages_fit(last, fresh.span(gp.final_ds)))) return WCQP_E_INVALID;
-        if (const int rc = replan_admit(h, i, M, fresh, c); rc != WCQP_OK) return rc;
+        if (const int rc = replan_admit(h, i, M, fresh.sets_up_to(h->p.max_ticks), c); rc != WCQP_OK) return rc;
     }
     if (c.robots.empty()) return WCQP_OK;
     return replan_enqueue(h, c, K, fd, ReplanSource{rp, nullptr, nullptr, nullptr, nullptr, tm}, (hipStream_t)stream);
@@ -698,8 +711,9 @@ int replan_goals(wcqp_tick_t h, wcqp_unicycle_t planner, const wcqp_unicycle_tim
         } else if (!wcqp_goal::merge_allowed(in_force, M, t0, T)) {
             return WCQP_E_INVALID;
         }
-        // (the new plan's steps are the device's: none to count here)
-        if (const int rc = replan_admit(h, i, M, wcqp_goal::Timeline::uniform(M, fd, 0, 0, 0), c); rc != WCQP_OK) return rc;
+        // (the new plan's steps are the device's: their sets are bounded, not counted)
+        const int fresh = goal_sets_bound(K, M, fd, tm ? (long long)tm->min_step_ticks : (long long)gp.ss + gp.ds, h->p.max_ticks);
+        if (const int rc = replan_admit(h, i, M, fresh, c); rc != WCQP_OK) return rc;
         taken[i] = M;
     }
     const auto rows = wcqp_tick_s::GoalRows::of(B, (size_t)K, tm != nullptr);
@@ -794,6 +808,136 @@ int wcqp_tick_rebase_plan(wcqp_tick_t h, int32_t shift, void* stream) {
     for (size_t i = 0; i < B; ++i) if (gp.origin[i] > -(1 << 30)) gp.origin[i] -= R;
     h->ticks_enqueued -= R;
     h->plan_shift += R;
+    return WCQP_OK;
+}
+
+// THE RESTARTED ROBOT (include/wcqp.h).  The host checks everything and compacts the listed robots' rows into the call's block, one row per
+// SLOT, so a kept robot's rows are never read; the device decides IF_STOPPED.  The host's own books: a robot listed ALWAYS is on its
+// standing plan at once, one listed IF_STOPPED is owed until its row has come back (tick_handle.h: RestartCall)
+int wcqp_tick_restart_robots(wcqp_tick_t h, const wcqp_tick_restart* rs, void* stream) {
+    if (!h || !rs) return WCQP_E_INVALID;
+    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
+    // (the caller's plant is the state there: a reset of the handle's rows would restart nothing)
+    if (h->external || h->resident || h->streamed) return WCQP_E_UNSUPPORTED;
+    if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    if (!rs->mode || !rs->state0 || !rs->q0 || !rs->com0) return WCQP_E_INVALID;
+    const TickDev& d = h->d;
+    auto& gp = h->gp;
+    auto& rc_ = h->restart;
+    const size_t B = (size_t)d.batch;
+    const int T = d.traj_len, cap = gp.cap;
+    if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (the slot counts and timelines goal, rebase and restart calls still owe)
+    const int S = consumed_stages(h);
+    if (S > h->p.max_ticks) return WCQP_E_INVALID;
+    auto finite = [](const double* a, size_t n) { bool ok = true; for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(a[k]); return ok; };
+    std::vector<int> robots, keep_new;
+    for (size_t i = 0; i < B; ++i) {
+        const uint8_t m = rs->mode[i];
+        if (m == WCQP_TICK_RESTART_KEEP) continue;            // (none of its rows is read)
+        if (m > WCQP_TICK_RESTART_IF_STOPPED) return WCQP_E_INVALID;
+        if (!finite(rs->state0 + i * kStateLen, kStateLen) || !finite(rs->q0 + i * kDof, kDof) || !finite(rs->com0 + i * 2, 2) ||
+            (rs->dcm0 && !finite(rs->dcm0 + i * 2, 2)) || (rs->u_init && !finite(rs->u_init + i * 2, 2)))
+            return WCQP_E_INVALID;
+        // the robot's slots in use by sets of stages < S - no stage >= S keeps its record, so the sets they alone name are free -, and one
+        // more for the standing set (IF_STOPPED: counted as if it restarted)
+        const int used = gp.keep[i] + gp.timeline(i).sets_up_to((S - 1 < h->p.max_ticks ? S - 1 : h->p.max_ticks));
+        if (used < 1 || used + 1 > cap) return WCQP_E_INVALID;
+        robots.push_back((int)i); keep_new.push_back(used + 1);
+    }
+    if (robots.empty()) {      // (nothing is enqueued: the result is "nobody, at stage S")
+        if (const int rc = rc_.wait(); rc != WCQP_OK) return rc;
+        rc_.robots.clear(); rc_.keep_new.clear(); rc_.owed.clear();
+        rc_.called = true; rc_.stage = S;
+        return WCQP_OK;
+    }
+    const size_t nr = robots.size(), n_tile = (size_t)((T + 63) / 64), t0 = (size_t)(S / 64), nt = nr * (n_tile - t0), nslots = B * (size_t)cap;
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_rob = carve(nr * 4), o_mode = carve(nr), o_slot = carve(nr * 4), o_tile = carve(nt * 8), o_st = carve(nr * kStateLen * 8),
+                 o_q = carve(nr * kDof * 8), o_com = carve(nr * 16), o_dcm = carve(rs->dcm0 ? nr * 16 : 0), o_u = carve(rs->u_init ? nr * 16 : 0);
+    const size_t front = off;
+    const size_t o_pat = carve(nr * kPlanRec * 8), o_mid = carve(nr * 16), o_res = carve(nr * 12), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
+    std::vector<char> blob(front, 0);
+    {
+        std::memcpy(blob.data() + o_rob, robots.data(), nr * 4);
+        int* slot = reinterpret_cast<int*>(blob.data() + o_slot); int* tile = reinterpret_cast<int*>(blob.data() + o_tile);
+        for (size_t r = 0; r < nr; ++r) {
+            const size_t i = (size_t)robots[r];
+            blob[o_mode + r] = (char)rs->mode[i];
+            slot[r] = (int)(i * (size_t)cap) + keep_new[r] - 1;
+            for (size_t tl = t0; tl < n_tile; ++tl) { *tile++ = (int)r; *tile++ = (int)tl; }
+            std::memcpy(blob.data() + o_st + r * kStateLen * 8, rs->state0 + i * kStateLen, kStateLen * 8);
+            std::memcpy(blob.data() + o_q + r * kDof * 8, rs->q0 + i * kDof, kDof * 8);
+            std::memcpy(blob.data() + o_com + r * 16, rs->com0 + i * 2, 16);
+            if (rs->dcm0) std::memcpy(blob.data() + o_dcm + r * 16, rs->dcm0 + i * 2, 16);
+            if (rs->u_init) std::memcpy(blob.data() + o_u + r * 16, rs->u_init + i * 2, 16);
+        }
+    }
+    if (!rc_.ev) WCQP_HIP_TRY(hipEventCreateWithFlags(&rc_.ev, hipEventDisableTiming));
+    if (const int rc = rc_.wait(); rc != WCQP_OK) return rc;       // (the previous call's rows, before this one's take their place)
+    if (rc_.host_cap < nr * 12) {
+        if (rc_.host) (void)hipHostFree(rc_.host);
+        rc_.host = nullptr; rc_.host_cap = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&rc_.host), nr * 12, hipHostMallocDefault) != hipSuccess) return WCQP_E_NOMEM;
+        rc_.host_cap = nr * 12;
+    }
+    if (const int rc = h->rp.take(h->copy_stream, blob.data(), front, off); rc != WCQP_OK) return rc;
+    char* buf = static_cast<char*>(h->rp.mem.ptr);
+    PlanRestartDev g{};
+    g.robots = reinterpret_cast<const int*>(buf + o_rob); g.mode = reinterpret_cast<const unsigned char*>(buf + o_mode);
+    g.state0 = reinterpret_cast<const double*>(buf + o_st); g.q0 = reinterpret_cast<const double*>(buf + o_q);
+    g.com0 = reinterpret_cast<const double*>(buf + o_com);
+    g.dcm0 = rs->dcm0 ? reinterpret_cast<const double*>(buf + o_dcm) : nullptr; g.u0 = rs->u_init ? reinterpret_cast<const double*>(buf + o_u) : nullptr;
+    g.set_slot = reinterpret_cast<const int*>(buf + o_slot); g.tiles = reinterpret_cast<const int2*>(buf + o_tile);
+    g.pattern = reinterpret_cast<double*>(buf + o_pat); g.mid = reinterpret_cast<double*>(buf + o_mid);
+    g.stopped = reinterpret_cast<long long*>(buf + o_res); g.restarted = reinterpret_cast<int*>(buf + o_res + nr * 8);
+    g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = reinterpret_cast<int*>(buf + o_code);
+    g.rec = h->plan_rec; g.ref = const_cast<double*>(d.ref_traj.get());
+    g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
+    g.mst = d.skew ? d.mst.p : nullptr; g.state = d.state.p; g.q_des = d.q_des.p; g.dq_prev = d.dq_prev.p;
+    g.dcm = d.dcm.p; g.com = d.com.p; g.c_ref = d.c_ref.p; g.p_star = d.p_star.p; g.zmp_meas = d.zmp_meas.p; g.u_prev = d.u_prev.p;
+    g.v_ref_prev = d.v_ref_prev.p; g.v_star_prev = d.v_star_prev.p;
+    g.zs = d.gain_sched ? h->zg.zs.p : nullptr;
+    g.com_h0 = h->kin ? const_cast<double*>(d.com_h0.get()) : nullptr;
+    g.sel_built = d.skew ? d.sel_built.p : nullptr; g.live_nc = d.skew ? d.live_nc.p : nullptr; g.sel = d.sel.p;
+    g.mpc_fail = d.mpc_fail.p; g.ik_fail = d.ik_fail.p; g.hot_try = d.hot_try.p; g.hot_hit = d.hot_hit.p;
+    g.ik_iters = h->position ? h->pos.ik_iters : nullptr;
+    g.ik_lo = h->ik_lo; g.ik_up = h->ik_up;
+    g.n_robots = (int)nr; g.n_tiles = (int)nt; g.traj_len = T; g.stage = S;
+    for (int k = 0; k < 2; ++k) { g.delta[0][k] = gp.delta[0][k]; g.delta[1][k] = gp.delta[1][k]; }
+    // in the caller's stream order, behind the ticks already enqueued: no pointer a tick or a captured graph holds changes, and the set
+    // slot written is one no stage below S names
+    const hipStream_t st = (hipStream_t)stream;
+    WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
+    if (const int rc = wcqp::plan_restart_enqueue(g, st); rc != WCQP_OK) return rc;
+    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
+                       h->set_A, h->set_b, h->set_nc);
+    WCQP_HIP_TRY(hipGetLastError());
+    WCQP_HIP_TRY(hipMemcpyAsync(rc_.host, buf + o_res, nr * 12, hipMemcpyDeviceToHost, st));
+    WCQP_HIP_TRY(hipEventRecord(rc_.ev, st));
+    if (const int rc = h->rp.guard(st); rc != WCQP_OK) return rc;
+    rc_.called = true; rc_.stage = S; rc_.pending = true; rc_.owed.clear();
+    for (size_t r = 0; r < nr; ++r) {
+        if (rs->mode[robots[r]] == WCQP_TICK_RESTART_ALWAYS) h->stand_from((size_t)robots[r], S, keep_new[r]);
+        else rc_.owed.push_back((int)r);
+    }
+    rc_.robots.swap(robots); rc_.keep_new.swap(keep_new);
+    return WCQP_OK;
+}
+
+int wcqp_tick_get_restart_result(wcqp_tick_t h, const wcqp_tick_restart_result* out) {
+    if (!h || !out) return WCQP_E_INVALID;
+    auto& rc_ = h->restart;
+    if (!rc_.called) return WCQP_E_INVALID;
+    if (const int rc = rc_.wait(); rc != WCQP_OK) return rc;       // (that call's own event, not the stream or the device)
+    const size_t B = (size_t)h->d.batch;
+    if (out->restarted) std::memset(out->restarted, 0, B);
+    if (out->stopped_ticks) std::memset(out->stopped_ticks, 0, B * 8);
+    for (size_t r = 0; r < rc_.robots.size(); ++r) {
+        if (out->restarted) out->restarted[rc_.robots[r]] = (uint8_t)rc_.restarted()[r];
+        if (out->stopped_ticks) out->stopped_ticks[rc_.robots[r]] = rc_.stopped()[r];
+    }
+    if (out->stage) *out->stage = rc_.stage;
     return WCQP_OK;
 }
 
