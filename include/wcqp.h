@@ -1036,7 +1036,8 @@ int wcqp_tick_rebase_plan(wcqp_tick_t h, int32_t shift, void* stream);
  * SLOTS: a restart takes one of the robot's set slots with no step behind it, so it also takes room from the replans that follow: a
  * footstep or goal replan whose new sets would not fit returns WCQP_E_INVALID (see there) until a rebase.  cap has room for one step
  * more than can start within max_ticks, so a robot restarted over and over without a rebase between runs out.
- * Not offered: device-pointer inputs, a restart at a stage other than S, EXTERNAL and resident handles, a per-robot tick index. */
+ * Rows that never visit the host: wcqp_tick_recover_robots below runs the posture IK on the device and restarts from its result.
+ * Not offered: a restart at a stage other than S, EXTERNAL and resident handles, a per-robot tick index. */
 #define WCQP_TICK_RESTART_KEEP        0
 #define WCQP_TICK_RESTART_ALWAYS      1
 #define WCQP_TICK_RESTART_IF_STOPPED  2
@@ -1055,6 +1056,65 @@ typedef struct wcqp_tick_restart_result { /* HOST pointers, any may be NULL */
     int32_t* stage;                       /* the stage S of the last call */
 } wcqp_tick_restart_result;
 int wcqp_tick_get_restart_result(wcqp_tick_t h, const wcqp_tick_restart_result* out);   /* waits for that call's event only */
+/* Stopped robots stood up on the device: posture IK and restart in one enqueue-only call (the reference's Stopped -> prepareRobot ->
+ * startWalking, WM/src/WalkingModule.cpp:882, 944-984, 1223, whose IK starts from the measured joints, :944).  wcqp_tick_restart_robots
+ * takes the posture as host rows, so its caller downloads (to learn who stopped, and where their joints are), solves, and restarts: two
+ * synchronisations.  wcqp_tick_recover_robots does the three steps on the device, on `stream`, behind the ticks already enqueued; the
+ * posture never visits the host.  S is the stage the next tick reads, as for a restart.  THE RECOVERED ROBOT - a listed robot (mode is not
+ * KEEP; tests/helpers/plan_recover.py restates the targets and the host composition the call equals):
+ *   Decision    ALWAYS: the robot goes on.  IF_STOPPED: it goes on iff ik_fail[i] > 0 when the call's kernels run; otherwise its status is
+ *               WCQP_RECOVER_NOT_STOPPED.  With soles taken from the plan (left_d and right_d NULL) a robot that would go on does so only
+ *               if bits 0 and 1 of record S's flags are both set - a double support or standing: both soles lie on the ground at landed
+ *               poses -; otherwise its status is WCQP_RECOVER_NOT_STANDING.  A robot that does not go on is not touched and costs no IK
+ *               iteration.
+ *   Posture     the problem and iteration of wcqp_prepare_solve_* with `prepare`'s parameters.  left_d / right_d: the caller's rows, or
+ *               the left and right sole of record S.  com_d: the caller's row, or x, y = the midpoint of the two feet's ZMP points
+ *               p_xy + R_2x2 delta of THESE soles (zmp_delta_* of the upload, each operation rounded on its own: the ZMP of THE RESTARTED
+ *               ROBOT's standing stage) and z = the CoM height of record S.  Rd_neck: the caller's row, or no neck target.  q_guess: the
+ *               caller's row, or the robot's q_des as the device holds it when the kernels run - the joints it stopped at.  The rows q,
+ *               state, status, iters, residual are bit for bit what wcqp_prepare_solve_host returns for these inputs: the same kernel runs,
+ *               over the rows of the robots that go on alone.
+ *   Restart     a robot whose IK ended WCQP_STATUS_SOLVED is THE RESTARTED ROBOT of wcqp_tick_restart_robots, bit for bit, with
+ *               state0 = the pose block of the IK, q0 = its q, com0 = entries 66, 67 of that block (the CoM at the solved posture), and
+ *               dcm0 / u_init as given: the same kernels and the same set builder produce it.  Any other status leaves the robot exactly
+ *               as it was: state, plan, and an ik_fail that keeps counting.
+ * Every listed robot is decided by the device - ALWAYS too: the SOLVED gate applies to it -, so every listed robot's plan in force is OWED
+ * as an IF_STOPPED robot's of a restart call is: one result row per listed robot comes back behind an event of the call's own, and the
+ * next call that reads a timeline or a slot count waits for that event first.  Slots are counted as if every listed robot restarted.  A
+ * recover call is the handle's last restart call: wcqp_tick_get_restart_result reports its restarted / stopped_ticks / stage too.
+ * Pending goal, rebase and restart calls are settled first.  Valid between wcqp_tick_run calls.  A call that lists nobody returns WCQP_OK
+ * and enqueues nothing.  The host rows of the LISTED robots are staged before the call returns.  (The first solve of a wcqp_prepare_t,
+ * here or in wcqp_prepare_solve_*, copies its tables to the device and waits for that copy alone.)
+ * Everything is checked on the host before anything changes; a refused call leaves the handle and the last result as they were.
+ * WCQP_E_UNSUPPORTED: exactly where wcqp_tick_restart_robots returns it.  WCQP_E_INVALID: as for a restart - not uploaded, mode NULL, a
+ * mode above 2, S > max_ticks, a listed robot without a free set slot -, and: `prepare` or the struct NULL; exactly one of left_d /
+ * right_d NULL; a `prepare` whose model table is not byte for byte that of the handle's kinematics (or a handle without kinematics); a
+ * non-finite value in a given left_d, right_d, com_d, Rd_neck, q_guess, dcm0 or u_init row of a listed robot - rows of KEPT robots are
+ * never read and may hold NaN.
+ * wcqp_tick_get_recover_result: WCQP_E_INVALID before any recover call, and when the handle's last restart call was not one.
+ * Not offered: a restart at a stage other than S, EXTERNAL and resident handles, a per-robot tick index. */
+#define WCQP_RECOVER_KEPT          (-1)   /* mode KEEP: not listed                                          */
+#define WCQP_RECOVER_NOT_STOPPED   (-2)   /* IF_STOPPED and ik_fail == 0 when the call's kernels ran         */
+#define WCQP_RECOVER_NOT_STANDING  (-3)   /* soles from the plan, and record S is not a double support       */
+typedef struct wcqp_tick_recover {        /* HOST pointers, staged before the call returns */
+    const uint8_t* mode;      /* [B] WCQP_TICK_RESTART_KEEP / _ALWAYS / _IF_STOPPED, as wcqp_tick_restart.mode      */
+    const double*  left_d;    /* [B][12] p 3 | R 9, the anchor; NULL together with right_d: the soles of plan record S */
+    const double*  right_d;   /* [B][12]                                                                           */
+    const double*  com_d;     /* [B][3] or NULL: x, y = the standing ZMP of these soles, z = the CoM height of record S */
+    const double*  Rd_neck;   /* [B][9] or NULL: no neck target                                                    */
+    const double*  q_guess;   /* [B][dof] or NULL: the robot's own joints on the device (q_des), read by the call's kernels */
+    const double*  dcm0;      /* [B][2] or NULL, as wcqp_tick_restart.dcm0                                          */
+    const double*  u_init;    /* [B][2] or NULL, as wcqp_tick_restart.u_init                                        */
+} wcqp_tick_recover;
+int wcqp_tick_recover_robots(wcqp_tick_t h, wcqp_prepare_t prepare, const wcqp_tick_recover* r, void* stream);
+typedef struct wcqp_tick_recover_result { /* HOST pointers, any may be NULL */
+    uint8_t* restarted; int64_t* stopped_ticks;  /* [B], as wcqp_tick_restart_result                       */
+    int32_t* status;   /* [B] WCQP_STATUS_* of the robot's IK, or WCQP_RECOVER_*                            */
+    int32_t* iters;    /* [B] 0 for a robot whose IK did not run                                            */
+    double*  residual; /* [B][2] as wcqp_prepare_solve_*; 0 for a robot whose IK did not run                 */
+    int32_t* stage;
+} wcqp_tick_recover_result;
+int wcqp_tick_get_recover_result(wcqp_tick_t h, const wcqp_tick_recover_result* out);  /* waits for that call's event only */
 /* Per-step timings: every footstep carries its own durations (the reference's planner gives every step its own, between minStepDuration
  * and maxStepDuration; wcqp_unicycle_plan_timed_* below chooses them and fills exactly these two arrays).  THE TIMED PLAN is the plan
  * wcqp_tick_upload_footsteps defines (tests/helpers/footstep_plan_timed.py restates it), with four changes:

@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
     "wcqp_tick_upload_footsteps", "wcqp_tick_upload_footsteps_timed", "wcqp_tick_replan_footsteps_timed", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
-    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan", "wcqp_tick_restart_robots", "wcqp_tick_get_restart_result", "wcqp_tick_set_swing_profile", "wcqp_tick_get_swing_profile",
+    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan", "wcqp_tick_restart_robots", "wcqp_tick_get_restart_result", "wcqp_tick_recover_robots", "wcqp_tick_get_recover_result", "wcqp_tick_set_swing_profile", "wcqp_tick_get_swing_profile",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
     "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
@@ -300,6 +300,22 @@ class TickRestartResult(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("restarted", "stopped_ticks", "stage")]
 
 
+RECOVER_KEPT, RECOVER_NOT_STOPPED, RECOVER_NOT_STANDING = -1, -2, -3
+RECOVER_ROWS = ("left_d", "right_d", "com_d", "Rd_neck", "q_guess", "dcm0", "u_init")
+
+
+class TickRecover(C.Structure):
+    """wcqp_tick_recover: per robot the mode (TICK_RESTART_*) and the targets of its posture IK - left_d / right_d [B][12] (both NULL: the
+    soles of the plan's record S), com_d [B][3], Rd_neck [B][9], q_guess [B][dof], dcm0 / u_init [B][2], each or NULL."""
+    _fields_ = [(k, C.c_void_p) for k in ("mode",) + RECOVER_ROWS]
+
+
+class TickRecoverResult(C.Structure):
+    """wcqp_tick_recover_result: what wcqp_tick_get_recover_result fills - restarted [B] (uint8), stopped_ticks [B] (int64), status and
+    iters [B] (int32), residual [B][2], stage (one int32)."""
+    _fields_ = [(k, C.c_void_p) for k in ("restarted", "stopped_ticks", "status", "iters", "residual", "stage")]
+
+
 UNICYCLE_DONE, UNICYCLE_TRUNCATED, UNICYCLE_STUCK, UNICYCLE_INVALID_INPUT = range(4)
 
 
@@ -352,6 +368,7 @@ ABI_STRUCTS = {
     "wcqp_tick_desired": TickDesired, "wcqp_tick_footsteps": TickFootsteps, "wcqp_tick_replan": TickReplan, "wcqp_tick_plan_window": TickPlanWindow,
     "wcqp_tick_goals": TickGoals, "wcqp_tick_goal_result": TickGoalResult, "wcqp_tick_step_timing": TickStepTiming,
     "wcqp_tick_swing_profile": TickSwingProfile, "wcqp_tick_restart": TickRestart, "wcqp_tick_restart_result": TickRestartResult,
+    "wcqp_tick_recover": TickRecover, "wcqp_tick_recover_result": TickRecoverResult,
     "wcqp_unicycle_params": UnicycleParams, "wcqp_unicycle_inputs": UnicycleInputs, "wcqp_unicycle_outputs": UnicycleOutputs,
     "wcqp_unicycle_timing": UnicycleTiming,
 }
@@ -362,7 +379,8 @@ ABI_CONSTANTS = {"WCQP_" + k: globals()[k] for k in (
     "IK_JAC_AUTO IK_JAC_MIXED IK_JAC_GENERAL PLAN_WAYS_AUTO SLAB_IN_ARRAYS SLAB_OUT_ARRAYS KIN_MAX_DOF "
     "KIN_HANDOFF_FUSED KIN_HANDOFF_DENSE KIN_HANDOFF_COMPACT TICK_PLANT_INTERNAL TICK_PLANT_EXTERNAL TICK_DCM_MPC TICK_DCM_REACTIVE "
     "TICK_IK_VELOCITY TICK_IK_POSITION TICK_OPT_RESIDENT_PLAN TICK_OPT_POSITION_STREAMED TICK_OPT_PLAN_TIMED TICK_OPT_PLAN_SHIFT TICK_OPT_SWING_PROFILE TICK_REBASE_AUTO UNICYCLE_DONE UNICYCLE_TRUNCATED UNICYCLE_STUCK UNICYCLE_INVALID_INPUT "
-    "TICK_MERGE_KEEP TICK_MERGE_AUTO TICK_SIDE_AUTO GOAL_KEPT GOAL_TOO_LATE TICK_RESTART_KEEP TICK_RESTART_ALWAYS TICK_RESTART_IF_STOPPED").split()}
+    "TICK_MERGE_KEEP TICK_MERGE_AUTO TICK_SIDE_AUTO GOAL_KEPT GOAL_TOO_LATE TICK_RESTART_KEEP TICK_RESTART_ALWAYS TICK_RESTART_IF_STOPPED "
+    "RECOVER_KEPT RECOVER_NOT_STOPPED RECOVER_NOT_STANDING").split()}
 
 _lib: Optional[C.CDLL] = None
 
@@ -430,6 +448,8 @@ def lib() -> C.CDLL:
         L.wcqp_tick_rebase_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.wcqp_tick_restart_robots.argtypes = [C.c_void_p, C.POINTER(TickRestart), C.c_void_p]
         L.wcqp_tick_get_restart_result.argtypes = [C.c_void_p, C.POINTER(TickRestartResult)]
+        L.wcqp_tick_recover_robots.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickRecover), C.c_void_p]
+        L.wcqp_tick_get_recover_result.argtypes = [C.c_void_p, C.POINTER(TickRecoverResult)]
         L.wcqp_tick_set_swing_profile.argtypes = [C.c_void_p, C.POINTER(TickSwingProfile)]
         L.wcqp_tick_get_swing_profile.argtypes = [C.c_void_p, C.POINTER(TickSwingProfile)]
         L.wcqp_tick_get_goal_result.argtypes = [C.c_void_p, C.POINTER(TickGoalResult)]
@@ -1043,6 +1063,38 @@ class TickPipeline(_Handle):
         res = TickRestartResult(**{k: v.ctypes.data for k, v in out.items()})
         check(lib().wcqp_tick_get_restart_result(self._h, C.byref(res)), "wcqp_tick_get_restart_result")
         return dict(restarted=out["restarted"].astype(bool), stopped_ticks=out["stopped_ticks"], stage=int(out["stage"][0]))
+
+    def recover_robots(self, mode, prepare, left_d=None, right_d=None, com_d=None, Rd_neck=None, q_guess=None, dcm0=None, u_init=None,
+                       stream: Optional[int] = None):
+        """Stopped robots stood up on the device, posture IK and restart in one enqueue-only call (wcqp_tick_recover_robots, which defines
+        the recovered robot): mode [B] as for restart_robots; prepare: a PrepareSolver on the handle's kinematic model.  Per listed robot the
+        device decides whether it goes on (IF_STOPPED: ik_fail > 0), solves the start posture of those that do - towards left_d / right_d
+        [B][12] (both None: the soles of the plan's next stage, which must be a double support), com_d [B][3] (None: the standing ZMP of the
+        soles at the plan's CoM height), Rd_neck [B][9] (None: no neck target), from q_guess [B][dof] (None: the joints the robot stopped at) -
+        and restarts exactly those whose IK ended SOLVED, with dcm0 / u_init [B][2] as restart_robots takes them.  Rows of KEEP robots are
+        not read; the arrays are copied before the call returns."""
+        if not self._holds_plan():
+            raise ValueError("recover_robots on a handle created without planned_trajectories=True (or resident_plan=True)")
+        if not isinstance(prepare, PrepareSolver):
+            raise TypeError("recover_robots needs a PrepareSolver")
+        m = np.ascontiguousarray(mode, dtype=np.uint8)
+        given = dict(left_d=left_d, right_d=right_d, com_d=com_d, Rd_neck=Rd_neck, q_guess=q_guess, dcm0=dcm0, u_init=u_init)
+        keep = {k: _f64(v) for k, v in given.items() if v is not None}
+        width = dict(left_d=12, right_d=12, com_d=3, Rd_neck=9, dcm0=2, u_init=2)
+        assert m.shape == (self.batch,) and all(v.ndim == 2 and v.shape[0] == self.batch and v.shape[1] == width.get(k, v.shape[1])
+                                                for k, v in keep.items()), (m.shape, {k: v.shape for k, v in keep.items()})
+        rv = TickRecover(m.ctypes.data, *(keep[k].ctypes.data if k in keep else None for k in RECOVER_ROWS))
+        check(lib().wcqp_tick_recover_robots(self._h, prepare._h, C.byref(rv), stream or None), "wcqp_tick_recover_robots")
+
+    def recover_result(self) -> dict:
+        """What the last recover_robots call did (wcqp_tick_get_recover_result; waits for that call only): restarted [B] (bool),
+        stopped_ticks [B], status [B] (the STATUS_* of the robot's IK, or RECOVER_KEPT / RECOVER_NOT_STOPPED / RECOVER_NOT_STANDING), iters [B],
+        residual [B][2] and stage."""
+        out = dict(restarted=np.zeros(self.batch, np.uint8), stopped_ticks=np.zeros(self.batch, np.int64), status=np.zeros(self.batch, np.int32),
+                   iters=np.zeros(self.batch, np.int32), residual=np.zeros((self.batch, 2)), stage=np.zeros(1, np.int32))
+        res = TickRecoverResult(**{k: v.ctypes.data for k, v in out.items()})
+        check(lib().wcqp_tick_get_recover_result(self._h, C.byref(res)), "wcqp_tick_get_recover_result")
+        return dict(out, restarted=out["restarted"].astype(bool), stage=int(out["stage"][0]))
 
     def set_swing_profile(self, apex_ratio: float = 0.0, landing_velocity: float = 0.0, pitch_delta: float = 0.0, com_height_delta: float = 0.0):
         """The shape of the steps the NEXT upload_footsteps / upload_goal generates (wcqp_tick_set_swing_profile, which defines the shaped

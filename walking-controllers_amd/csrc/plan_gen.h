@@ -79,6 +79,7 @@ struct PlanRebaseDev {
 struct PlanRestartDev {
     const int* robots;              // [n_robots]
     const unsigned char* mode;      // [n_robots] WCQP_TICK_RESTART_ALWAYS / _IF_STOPPED
+    const int* decided;             // NULL, or [n_robots] the decision, made elsewhere on the device (plan_recover.hip: nonzero restarts); mode is then unread
     const double* state0;           // [n_robots][kStateLen]
     const double* q0;               // [n_robots][kDof]
     const double* com0;             // [n_robots][2]
@@ -102,9 +103,45 @@ struct PlanRestartDev {
     double delta[2][2];             // zmp_delta_left / zmp_delta_right
 };
 
+// a foot's ZMP point p_xy + R_2x2 delta of the sole `pose` (p 3 | R 9 row-major), every operation rounded on its own, as numpy does
+__device__ __forceinline__ double zmp_point_ax(const double* pose, const double* dl, int ax) {
+#pragma clang fp contract(off)
+    const double r = pose[3 + 3 * ax] * dl[0] + pose[4 + 3 * ax] * dl[1];
+    return pose[ax] + r;
+}
+
+// wcqp_tick_recover_robots (plan_recover.hip): around the non-linear IK of prepare.hip, the kernel that decides per slot and packs the rows
+// of the slots that go on, and the gate that turns the IK's status into PlanRestartDev::decided and hands its rows to the restart
+struct PlanRecoverDev {
+    const int* robots;              // [n_robots]
+    const unsigned char* mode;      // [n_robots] WCQP_TICK_RESTART_ALWAYS / _IF_STOPPED
+    // the caller's rows, one per SLOT; NULL: left / right the soles of record S (both or neither), com the standing ZMP of the soles and the
+    // height of record S, q the robot's q_des; neck: no neck target
+    const double *left_in, *right_in, *com_in, *neck_in, *q_in;
+    const long long* ik_fail;       // [B]
+    const double* q_des;            // [B][kDof]
+    const double* rec;              // the plan's records
+    // what the gather kernel writes: per slot its packed row (>= 0) or WCQP_RECOVER_NOT_STOPPED / _NOT_STANDING; the rows of the slots that
+    // go on, packed to the front in no particular order, as prepare_kernel reads them; and their number
+    int* pos;                       // [n_robots]
+    int* count;                     // zero when the kernel starts
+    double *p_left, *p_right, *p_com, *p_neck, *p_q;
+    // what the IK leaves per packed row, and what the gate makes of it per slot: the restart's rows and decision, the result rows
+    const double *o_q, *o_state, *o_res;
+    const int *o_status, *o_iters;
+    double *state0, *q0, *com0;     // PlanRestartDev's
+    int* decided;
+    int *status, *iters; double* residual;
+    int n_robots, traj_len, stage;
+    double delta[2][2];
+};
+
 }  // namespace wcqp_tick
 
 namespace wcqp {
+// plan_recover.hip: the two kernels either side of the IK, each enqueue-only
+int plan_recover_gather_enqueue(const wcqp_tick::PlanRecoverDev& g, hipStream_t stream);
+int plan_recover_gate_enqueue(const wcqp_tick::PlanRecoverDev& g, hipStream_t stream);
 // its two kernels in stream order: decide-and-reset over the slots, then the fill over the tiles.  Enqueue-only
 int plan_restart_enqueue(const wcqp_tick::PlanRestartDev& g, hipStream_t stream);
 // its two kernels in stream order: d_i, the ZMP of the new stage 0 and the tick index first, then the rows.  Enqueue-only

@@ -1,7 +1,8 @@
 // Stopped robots of a running fleet restarted on the device, per robot (wcqp_tick_restart_robots; include/wcqp.h states THE RESTARTED
 // ROBOT, tests/helpers/plan_restart.py restates its plan in numpy).  The call lists robots - slot r is robot robots[r] - and two kernels
 // run in stream order:
-//   plan_restart_reset_kernel   one wave per slot: reads the robot's ik_fail, decides (ALWAYS, or IF_STOPPED: ik_fail > 0), writes the
+//   plan_restart_reset_kernel   one wave per slot: reads the robot's ik_fail, decides (ALWAYS, or IF_STOPPED: ik_fail > 0; or takes the
+//                               decision a recover call's gate made, plan_recover.hip), writes the
 //                               decision and ik_fail into the slot's result row and - for a robot that restarts - resets the state
 //                               wcqp::upload_state sets (tick.hip: the one definition of "a robot at tick 0") from the slot's staged rows,
 //                               and writes the slot's standing record (kPlanRec doubles), its ref_traj entry and the robot's entry of the
@@ -24,18 +25,11 @@ constexpr int kTile = 64, kTilePieces = kTile * kRecPieces, kPerLane = kTilePiec
 static_assert(kPlanRec == 40 && kPlanLeft == 3 && kPlanTwL == 27 && kPlanHull == 39, "the standing record below is written by entry");
 static_assert(kPerLane == kRecPieces && (64 * 5) % kRecPieces == 0, "a lane's pieces repeat with period 5");
 
-// a foot's ZMP point p_xy + R_2x2 delta of the sole `pose` (p 3 | R 9 row-major), every operation rounded on its own, as numpy does
-__device__ __forceinline__ double zmp_point_ax(const double* pose, const double* dl, int ax) {
-#pragma clang fp contract(off)
-    const double r = pose[3 + 3 * ax] * dl[0] + pose[4 + 3 * ax] * dl[1];
-    return pose[ax] + r;
-}
-
 __global__ __launch_bounds__(64) void plan_restart_reset_kernel(PlanRestartDev g) {
     const int r = blockIdx.x, lane = threadIdx.x;
     const size_t i = (size_t)g.robots[r];
     const long long failed = g.ik_fail[i];            // (every lane: read before any lane resets it - the branch below waits for it)
-    const bool go = g.mode[r] == WCQP_TICK_RESTART_ALWAYS || failed > 0;
+    const bool go = g.decided ? g.decided[r] != 0 : (g.mode[r] == WCQP_TICK_RESTART_ALWAYS || failed > 0);
     __syncthreads();
     if (lane == 0) { g.restarted[r] = go ? 1 : 0; g.stopped[r] = go ? failed : 0; }
     if (!go) return;
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(64) void plan_restart_fill_kernel(PlanRestartDev g)
 namespace wcqp {
 
 int plan_restart_enqueue(const PlanRestartDev& g, hipStream_t stream) {
-    if (!g.robots || !g.mode || !g.state0 || !g.q0 || !g.com0 || !g.set_slot || !g.tiles || !g.pattern || !g.mid || !g.restarted || !g.stopped ||
+    if (!g.robots || (!g.mode && !g.decided) || !g.state0 || !g.q0 || !g.com0 || !g.set_slot || !g.tiles || !g.pattern || !g.mid || !g.restarted || !g.stopped ||
         !g.set_at || !g.set_code || !g.rec || !g.ref)
         return WCQP_E_INVALID;
     if (!g.state || !g.q_des || !g.dq_prev || !g.dcm || !g.com || !g.c_ref || !g.p_star || !g.zmp_meas || !g.u_prev || !g.v_ref_prev || !g.v_star_prev ||

@@ -24,6 +24,7 @@
 #include "kin_device.h"
 #include "prepare_device.h"
 #include "position_tick.h"
+#include "prepare_rows.h"
 
 namespace {
 
@@ -39,9 +40,12 @@ struct PrepDev {
     const double* par;                         // q_reg [23] | q_min [23] | q_max [23]
     double w_q, w_n, step_cap, tol_step, tol_c;
     int max_iter, use_limits;
+    const int* n_rows;                         // NULL (the public entry points), or the rows to solve, at most `batch`, counted on the device
 };
 
 __global__ __launch_bounds__(64) void prepare_kernel(PrepDev a) {
+    // (prepare_rows.h: the launch covers `batch` rows, a wave past the device's count leaves before it reads one)
+    if (a.n_rows) { a.batch = min(a.batch, *a.n_rows); if ((long)blockIdx.x * 4 >= a.batch) return; }
     __shared__ __attribute__((aligned(16))) double kmodel[kKinTabSize];
     __shared__ __attribute__((aligned(16))) double smem[4][P_PER];
     const int lane = threadIdx.x, grp = lane >> 4, j = lane & 15;
@@ -221,6 +225,22 @@ int check_call(wcqp_prepare_t h, int32_t batch, const double* left_d, const doub
 
 namespace wcqp {
 
+const std::vector<double>& prepare_model_table(wcqp_prepare_t h) { return h->tab; }
+
+int prepare_enqueue_rows(wcqp_prepare_t h, const PrepareRows& r, hipStream_t stream) {
+    if (!h || r.max_rows < 1 || !r.n_rows || !r.left_d || !r.right_d || !r.com_d || !r.q_guess || !r.q || !r.state || !r.status || !r.iters || !r.residual)
+        return WCQP_E_INVALID;
+    if (!fits32(r.max_rows, kStateLen * 8)) return WCQP_E_UNSUPPORTED;
+    if (const int rc = ensure_device(h); rc != WCQP_OK) return rc;
+    PrepDev a = h->dev;
+    a.batch = r.max_rows; a.n_rows = r.n_rows;
+    a.left_d = r.left_d; a.right_d = r.right_d; a.com_d = r.com_d; a.Rd_neck = r.Rd_neck; a.q_guess = r.q_guess;
+    a.q = r.q; a.base = nullptr; a.state = r.state; a.status = r.status; a.iters = r.iters; a.residual = r.residual;
+    hipLaunchKernelGGL(prepare_kernel, dim3((unsigned)((r.max_rows + 3) / 4)), dim3(64), 0, stream, a);
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+
 int prepare_check_scalars(const wcqp_prepare_params* p) {
     if (!std::isfinite(p->w_q) || !(p->w_q > 0.0) || !std::isfinite(p->w_n) || !(p->w_n >= 0.0)) return WCQP_E_INVALID;
     if (!std::isfinite(p->step_cap) || !(p->step_cap > 0.0)) return WCQP_E_INVALID;
@@ -294,7 +314,7 @@ int wcqp_prepare_solve_device(wcqp_prepare_t h, int32_t batch, const double* lef
     rc = ensure_device(h);
     if (rc != WCQP_OK) return rc;
     PrepDev a = h->dev;
-    a.batch = batch;
+    a.batch = batch; a.n_rows = nullptr;
     a.left_d = left_d; a.right_d = right_d; a.com_d = com_d; a.Rd_neck = Rd_neck; a.q_guess = q_guess;
     a.q = q; a.base = base; a.state = state; a.status = status; a.iters = iters; a.residual = residual;
     hipLaunchKernelGGL(prepare_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a);

@@ -199,18 +199,25 @@ struct wcqp_tick_s {
             host = nullptr; ev = nullptr; pending = false;
         }
     } rebase;
-    // wcqp_tick_restart_robots: one row per LISTED robot (slot r of the call: robot robots[r]) comes back into `host` (pinned: the
-    // decisions [n] as int32 behind the ik_fail rows [n] as int64) behind `ev`.  A robot listed ALWAYS is on its standing plan in gp at
-    // once; one listed IF_STOPPED is `owed` - the device decides - and settle() puts it on the standing plan (origin `stage`, no steps,
-    // `keep_new` slots in use) if its row says it restarted.  The rows stay for wcqp_tick_get_restart_result
+    // wcqp_tick_restart_robots and wcqp_tick_recover_robots: one row per LISTED robot (slot r of the call: robot robots[r]) comes back into
+    // `host` (pinned) behind `ev`: the ik_fail rows [n] as int64, a recover call's residual rows [n][2] as doubles, the decisions [n] as
+    // int32, a recover call's status and iters rows [n] as int32.  THE RULE, for both calls: a robot whose restart the HOST decides - one
+    // listed ALWAYS in a restart call - is on its standing plan in gp at once; a robot the DEVICE decides - IF_STOPPED, and every listed
+    // robot of a recover call, whose IK must end SOLVED - is `owed`, and settle() puts it on the standing plan (origin `stage`, no steps,
+    // `keep_new` slots in use) if its row says it restarted.  The rows stay for wcqp_tick_get_restart_result / _recover_result
     struct RestartCall {
         char* host = nullptr; size_t host_cap = 0;
         hipEvent_t ev = nullptr;
         bool called = false, pending = false;           // pending: the rows are still on their way
+        bool recover = false;                           // the last call was a recover call: the rows hold its three more columns
         int stage = 0;
         std::vector<int> robots, keep_new, owed;        // by slot: the robot, its slot count if it restarts; the slots still owed
+        static size_t row_bytes(bool recover) { return recover ? 36 : 12; }
         const long long* stopped() const { return reinterpret_cast<const long long*>(host); }
-        const int* restarted() const { return reinterpret_cast<const int*>(host + robots.size() * 8); }
+        const double* residual() const { return reinterpret_cast<const double*>(host + robots.size() * 8); }
+        const int* restarted() const { return reinterpret_cast<const int*>(host + robots.size() * (recover ? 24 : 8)); }
+        const int* status() const { return restarted() + robots.size(); }
+        const int* iters() const { return restarted() + 2 * robots.size(); }
         int wait() {
             if (pending) { WCQP_HIP_TRY(hipEventSynchronize(ev)); pending = false; }
             return WCQP_OK;
@@ -218,7 +225,7 @@ struct wcqp_tick_s {
         void release() {
             if (host) (void)hipHostFree(host);
             if (ev) (void)hipEventDestroy(ev);
-            host = nullptr; host_cap = 0; ev = nullptr; pending = false; called = false; owed.clear();
+            host = nullptr; host_cap = 0; ev = nullptr; pending = false; called = false; recover = false; owed.clear();
         }
     } restart;
     // robot i stands from stage S on: the plan in force wcqp_tick_restart_robots leaves

@@ -10,6 +10,7 @@
 #include "plan_gen.h"
 #include "goal_merge.h"
 #include "unicycle_device.h"
+#include "prepare_rows.h"
 
 namespace {
 
@@ -811,16 +812,30 @@ int wcqp_tick_rebase_plan(wcqp_tick_t h, int32_t shift, void* stream) {
     return WCQP_OK;
 }
 
-// THE RESTARTED ROBOT (include/wcqp.h).  The host checks everything and compacts the listed robots' rows into the call's block, one row per
-// SLOT, so a kept robot's rows are never read; the device decides IF_STOPPED.  The host's own books: a robot listed ALWAYS is on its
-// standing plan at once, one listed IF_STOPPED is owed until its row has come back (tick_handle.h: RestartCall)
-int wcqp_tick_restart_robots(wcqp_tick_t h, const wcqp_tick_restart* rs, void* stream) {
-    if (!h || !rs) return WCQP_E_INVALID;
+// THE RESTARTED ROBOT and THE RECOVERED ROBOT (include/wcqp.h), one path.  The host checks everything and compacts the listed robots' rows
+// into the call's block, one row per SLOT, so a kept robot's rows are never read.  A restart call (rs) brings the posture rows and the
+// device decides IF_STOPPED; a recover call (rv, prep) brings targets, and the device decides, solves the posture of the slots that go on
+// and restarts those that end SOLVED (plan_recover.hip around prepare.hip's kernel).  The host's own books: tick_handle.h, RestartCall
+static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare_t prep, const wcqp_tick_recover* rv, void* stream) {
+    const bool recover = rv != nullptr;
+    if (!h || (!rs && !rv)) return WCQP_E_INVALID;
     if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
     // (the caller's plant is the state there: a reset of the handle's rows would restart nothing)
     if (h->external || h->resident || h->streamed) return WCQP_E_UNSUPPORTED;
     if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
-    if (!rs->mode || !rs->state0 || !rs->q0 || !rs->com0) return WCQP_E_INVALID;
+    const uint8_t* mode = recover ? rv->mode : rs->mode;
+    const double* dcm0 = recover ? rv->dcm0 : rs->dcm0;
+    const double* u_init = recover ? rv->u_init : rs->u_init;
+    if (!mode) return WCQP_E_INVALID;
+    if (!recover && (!rs->state0 || !rs->q0 || !rs->com0)) return WCQP_E_INVALID;
+    if (recover) {
+        if (!prep || (rv->left_d == nullptr) != (rv->right_d == nullptr)) return WCQP_E_INVALID;
+        // the IK must walk the tree the handle's ticks walk: the joints it reads and writes are theirs
+        std::vector<double> tab; int rounds = 0;
+        if (!h->kin || !wcqp::kin_fused_tables(h->kin, tab, &rounds)) return WCQP_E_INVALID;
+        const std::vector<double>& mine = wcqp::prepare_model_table(prep);
+        if (mine.size() != tab.size() || std::memcmp(mine.data(), tab.data(), tab.size() * sizeof(double)) != 0) return WCQP_E_INVALID;
+    }
     const TickDev& d = h->d;
     auto& gp = h->gp;
     auto& rc_ = h->restart;
@@ -829,17 +844,21 @@ int wcqp_tick_restart_robots(wcqp_tick_t h, const wcqp_tick_restart* rs, void* s
     if (const int rc = h->settle(); rc != WCQP_OK) return rc;       // (the slot counts and timelines goal, rebase and restart calls still owe)
     const int S = consumed_stages(h);
     if (S > h->p.max_ticks) return WCQP_E_INVALID;
+    // the caller's rows by kind: where they lie, how long a robot's row is, and (below) where the slot rows go in the block
+    struct In { const double* host; size_t len; size_t at; };
+    In in[7] = {{recover ? rv->left_d : rs->state0, recover ? (size_t)12 : (size_t)kStateLen, 0}, {recover ? rv->right_d : rs->q0, recover ? (size_t)12 : (size_t)kDof, 0},
+                {recover ? rv->com_d : rs->com0, recover ? (size_t)3 : (size_t)2, 0}, {recover ? rv->Rd_neck : nullptr, 9, 0},
+                {recover ? rv->q_guess : nullptr, (size_t)kDof, 0}, {dcm0, 2, 0}, {u_init, 2, 0}};
     auto finite = [](const double* a, size_t n) { bool ok = true; for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(a[k]); return ok; };
     std::vector<int> robots, keep_new;
     for (size_t i = 0; i < B; ++i) {
-        const uint8_t m = rs->mode[i];
+        const uint8_t m = mode[i];
         if (m == WCQP_TICK_RESTART_KEEP) continue;            // (none of its rows is read)
         if (m > WCQP_TICK_RESTART_IF_STOPPED) return WCQP_E_INVALID;
-        if (!finite(rs->state0 + i * kStateLen, kStateLen) || !finite(rs->q0 + i * kDof, kDof) || !finite(rs->com0 + i * 2, 2) ||
-            (rs->dcm0 && !finite(rs->dcm0 + i * 2, 2)) || (rs->u_init && !finite(rs->u_init + i * 2, 2)))
-            return WCQP_E_INVALID;
+        for (const In& a : in)
+            if (a.host && !finite(a.host + i * a.len, a.len)) return WCQP_E_INVALID;
         // the robot's slots in use by sets of stages < S - no stage >= S keeps its record, so the sets they alone name are free -, and one
-        // more for the standing set (IF_STOPPED: counted as if it restarted)
+        // more for the standing set (a robot the device decides: counted as if it restarted)
         const int used = gp.keep[i] + gp.timeline(i).sets_up_to((S - 1 < h->p.max_ticks ? S - 1 : h->p.max_ticks));
         if (used < 1 || used + 1 > cap) return WCQP_E_INVALID;
         robots.push_back((int)i); keep_new.push_back(used + 1);
@@ -847,51 +866,59 @@ int wcqp_tick_restart_robots(wcqp_tick_t h, const wcqp_tick_restart* rs, void* s
     if (robots.empty()) {      // (nothing is enqueued: the result is "nobody, at stage S")
         if (const int rc = rc_.wait(); rc != WCQP_OK) return rc;
         rc_.robots.clear(); rc_.keep_new.clear(); rc_.owed.clear();
-        rc_.called = true; rc_.stage = S;
+        rc_.called = true; rc_.recover = recover; rc_.stage = S;
         return WCQP_OK;
     }
     const size_t nr = robots.size(), n_tile = (size_t)((T + 63) / 64), t0 = (size_t)(S / 64), nt = nr * (n_tile - t0), nslots = B * (size_t)cap;
+    const size_t res_bytes = nr * wcqp_tick_s::RestartCall::row_bytes(recover);
     size_t off = 0;
     auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_rob = carve(nr * 4), o_mode = carve(nr), o_slot = carve(nr * 4), o_tile = carve(nt * 8), o_st = carve(nr * kStateLen * 8),
-                 o_q = carve(nr * kDof * 8), o_com = carve(nr * 16), o_dcm = carve(rs->dcm0 ? nr * 16 : 0), o_u = carve(rs->u_init ? nr * 16 : 0);
+    const size_t o_rob = carve(nr * 4), o_mode = carve(nr), o_slot = carve(nr * 4), o_tile = carve(nt * 8), o_cnt = carve(recover ? 4 : 0);
+    for (In& a : in) a.at = carve(a.host ? nr * a.len * 8 : 0);
     const size_t front = off;
-    const size_t o_pat = carve(nr * kPlanRec * 8), o_mid = carve(nr * 16), o_res = carve(nr * 12), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
-    std::vector<char> blob(front, 0);
+    const size_t o_pat = carve(nr * kPlanRec * 8), o_mid = carve(nr * 16), o_res = carve(res_bytes), o_at = carve(nslots * 8), o_code = carve(nslots * 4);
+    // a recover call: the restart's rows, which its gate writes; the slots' packed rows; the packed rows the IK reads and writes
+    size_t o_st = in[0].at, o_q = in[1].at, o_com = in[2].at, o_dec = 0, o_pos = 0, o_pk[5] = {0, 0, 0, 0, 0}, o_ik[5] = {0, 0, 0, 0, 0};
+    if (recover) {
+        o_st = carve(nr * kStateLen * 8); o_q = carve(nr * kDof * 8); o_com = carve(nr * 16); o_dec = carve(nr * 4); o_pos = carve(nr * 4);
+        const size_t pk[5] = {12, 12, 3, 9, (size_t)kDof}, ik[5] = {(size_t)kDof * 8, (size_t)kStateLen * 8, 16, 4, 4};
+        for (int k = 0; k < 5; ++k) { o_pk[k] = carve(nr * pk[k] * 8); o_ik[k] = carve(nr * ik[k]); }
+    }
+    std::vector<char> blob(front, 0);       // (a recover call's counter starts at 0)
     {
         std::memcpy(blob.data() + o_rob, robots.data(), nr * 4);
         int* slot = reinterpret_cast<int*>(blob.data() + o_slot); int* tile = reinterpret_cast<int*>(blob.data() + o_tile);
         for (size_t r = 0; r < nr; ++r) {
             const size_t i = (size_t)robots[r];
-            blob[o_mode + r] = (char)rs->mode[i];
+            blob[o_mode + r] = (char)mode[i];
             slot[r] = (int)(i * (size_t)cap) + keep_new[r] - 1;
             for (size_t tl = t0; tl < n_tile; ++tl) { *tile++ = (int)r; *tile++ = (int)tl; }
-            std::memcpy(blob.data() + o_st + r * kStateLen * 8, rs->state0 + i * kStateLen, kStateLen * 8);
-            std::memcpy(blob.data() + o_q + r * kDof * 8, rs->q0 + i * kDof, kDof * 8);
-            std::memcpy(blob.data() + o_com + r * 16, rs->com0 + i * 2, 16);
-            if (rs->dcm0) std::memcpy(blob.data() + o_dcm + r * 16, rs->dcm0 + i * 2, 16);
-            if (rs->u_init) std::memcpy(blob.data() + o_u + r * 16, rs->u_init + i * 2, 16);
+            for (const In& a : in)
+                if (a.host) std::memcpy(blob.data() + a.at + r * a.len * 8, a.host + i * a.len, a.len * 8);
         }
     }
     if (!rc_.ev) WCQP_HIP_TRY(hipEventCreateWithFlags(&rc_.ev, hipEventDisableTiming));
     if (const int rc = rc_.wait(); rc != WCQP_OK) return rc;       // (the previous call's rows, before this one's take their place)
-    if (rc_.host_cap < nr * 12) {
+    if (rc_.host_cap < res_bytes) {
         if (rc_.host) (void)hipHostFree(rc_.host);
         rc_.host = nullptr; rc_.host_cap = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&rc_.host), nr * 12, hipHostMallocDefault) != hipSuccess) return WCQP_E_NOMEM;
-        rc_.host_cap = nr * 12;
+        if (hipHostMalloc(reinterpret_cast<void**>(&rc_.host), res_bytes, hipHostMallocDefault) != hipSuccess) return WCQP_E_NOMEM;
+        rc_.host_cap = res_bytes;
     }
     if (const int rc = h->rp.take(h->copy_stream, blob.data(), front, off); rc != WCQP_OK) return rc;
     char* buf = static_cast<char*>(h->rp.mem.ptr);
+    auto dbl = [buf](size_t at) { return reinterpret_cast<double*>(buf + at); };
+    auto i32 = [buf](size_t at) { return reinterpret_cast<int*>(buf + at); };
     PlanRestartDev g{};
-    g.robots = reinterpret_cast<const int*>(buf + o_rob); g.mode = reinterpret_cast<const unsigned char*>(buf + o_mode);
-    g.state0 = reinterpret_cast<const double*>(buf + o_st); g.q0 = reinterpret_cast<const double*>(buf + o_q);
-    g.com0 = reinterpret_cast<const double*>(buf + o_com);
-    g.dcm0 = rs->dcm0 ? reinterpret_cast<const double*>(buf + o_dcm) : nullptr; g.u0 = rs->u_init ? reinterpret_cast<const double*>(buf + o_u) : nullptr;
-    g.set_slot = reinterpret_cast<const int*>(buf + o_slot); g.tiles = reinterpret_cast<const int2*>(buf + o_tile);
-    g.pattern = reinterpret_cast<double*>(buf + o_pat); g.mid = reinterpret_cast<double*>(buf + o_mid);
-    g.stopped = reinterpret_cast<long long*>(buf + o_res); g.restarted = reinterpret_cast<int*>(buf + o_res + nr * 8);
-    g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = reinterpret_cast<int*>(buf + o_code);
+    g.robots = i32(o_rob); g.mode = reinterpret_cast<const unsigned char*>(buf + o_mode);
+    g.decided = recover ? i32(o_dec) : nullptr;
+    g.state0 = dbl(o_st); g.q0 = dbl(o_q); g.com0 = dbl(o_com);
+    g.dcm0 = dcm0 ? dbl(in[5].at) : nullptr; g.u0 = u_init ? dbl(in[6].at) : nullptr;
+    g.set_slot = i32(o_slot); g.tiles = reinterpret_cast<const int2*>(buf + o_tile);
+    g.pattern = dbl(o_pat); g.mid = dbl(o_mid);
+    // the result rows, in the order RestartCall reads them
+    g.stopped = reinterpret_cast<long long*>(buf + o_res); g.restarted = i32(o_res + nr * (recover ? 24 : 8));
+    g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = i32(o_code);
     g.rec = h->plan_rec; g.ref = const_cast<double*>(d.ref_traj.get());
     g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
     g.mst = d.skew ? d.mst.p : nullptr; g.state = d.state.p; g.q_des = d.q_des.p; g.dq_prev = d.dq_prev.p;
@@ -908,21 +935,52 @@ int wcqp_tick_restart_robots(wcqp_tick_t h, const wcqp_tick_restart* rs, void* s
     // in the caller's stream order, behind the ticks already enqueued: no pointer a tick or a captured graph holds changes, and the set
     // slot written is one no stage below S names
     const hipStream_t st = (hipStream_t)stream;
+    if (recover) {
+        PlanRecoverDev v{};
+        v.robots = g.robots; v.mode = g.mode;
+        v.left_in = rv->left_d ? dbl(in[0].at) : nullptr; v.right_in = rv->right_d ? dbl(in[1].at) : nullptr;
+        v.com_in = rv->com_d ? dbl(in[2].at) : nullptr; v.neck_in = rv->Rd_neck ? dbl(in[3].at) : nullptr; v.q_in = rv->q_guess ? dbl(in[4].at) : nullptr;
+        v.ik_fail = d.ik_fail.p; v.q_des = d.q_des.p; v.rec = h->plan_rec;
+        v.pos = i32(o_pos); v.count = i32(o_cnt);
+        v.p_left = dbl(o_pk[0]); v.p_right = dbl(o_pk[1]); v.p_com = dbl(o_pk[2]); v.p_neck = dbl(o_pk[3]); v.p_q = dbl(o_pk[4]);
+        v.o_q = dbl(o_ik[0]); v.o_state = dbl(o_ik[1]); v.o_res = dbl(o_ik[2]); v.o_status = i32(o_ik[3]); v.o_iters = i32(o_ik[4]);
+        v.state0 = dbl(o_st); v.q0 = dbl(o_q); v.com0 = dbl(o_com); v.decided = i32(o_dec);
+        v.residual = dbl(o_res + nr * 8); v.status = g.restarted + nr; v.iters = g.restarted + 2 * nr;
+        v.n_robots = (int)nr; v.traj_len = T; v.stage = S;
+        for (int k = 0; k < 2; ++k) { v.delta[0][k] = gp.delta[0][k]; v.delta[1][k] = gp.delta[1][k]; }
+        wcqp::PrepareRows pr{};
+        pr.max_rows = (int)nr; pr.n_rows = v.count;
+        pr.left_d = v.p_left; pr.right_d = v.p_right; pr.com_d = v.p_com; pr.Rd_neck = rv->Rd_neck ? v.p_neck : nullptr; pr.q_guess = v.p_q;
+        pr.q = dbl(o_ik[0]); pr.state = dbl(o_ik[1]); pr.residual = dbl(o_ik[2]); pr.status = i32(o_ik[3]); pr.iters = i32(o_ik[4]);
+        if (const int rc = wcqp::plan_recover_gather_enqueue(v, st); rc != WCQP_OK) return rc;
+        if (const int rc = wcqp::prepare_enqueue_rows(prep, pr, st); rc != WCQP_OK) return rc;
+        if (const int rc = wcqp::plan_recover_gate_enqueue(v, st); rc != WCQP_OK) return rc;
+    }
     WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
     if (const int rc = wcqp::plan_restart_enqueue(g, st); rc != WCQP_OK) return rc;
     hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
                        h->set_A, h->set_b, h->set_nc);
     WCQP_HIP_TRY(hipGetLastError());
-    WCQP_HIP_TRY(hipMemcpyAsync(rc_.host, buf + o_res, nr * 12, hipMemcpyDeviceToHost, st));
+    WCQP_HIP_TRY(hipMemcpyAsync(rc_.host, buf + o_res, res_bytes, hipMemcpyDeviceToHost, st));
     WCQP_HIP_TRY(hipEventRecord(rc_.ev, st));
     if (const int rc = h->rp.guard(st); rc != WCQP_OK) return rc;
-    rc_.called = true; rc_.stage = S; rc_.pending = true; rc_.owed.clear();
+    rc_.called = true; rc_.recover = recover; rc_.stage = S; rc_.pending = true; rc_.owed.clear();
     for (size_t r = 0; r < nr; ++r) {
-        if (rs->mode[robots[r]] == WCQP_TICK_RESTART_ALWAYS) h->stand_from((size_t)robots[r], S, keep_new[r]);
+        if (!recover && mode[robots[r]] == WCQP_TICK_RESTART_ALWAYS) h->stand_from((size_t)robots[r], S, keep_new[r]);
         else rc_.owed.push_back((int)r);
     }
     rc_.robots.swap(robots); rc_.keep_new.swap(keep_new);
     return WCQP_OK;
+}
+
+int wcqp_tick_restart_robots(wcqp_tick_t h, const wcqp_tick_restart* rs, void* stream) {
+    if (!rs) return WCQP_E_INVALID;
+    return restart_call(h, rs, nullptr, nullptr, stream);
+}
+
+int wcqp_tick_recover_robots(wcqp_tick_t h, wcqp_prepare_t prepare, const wcqp_tick_recover* rv, void* stream) {
+    if (!rv) return WCQP_E_INVALID;
+    return restart_call(h, nullptr, prepare, rv, stream);
 }
 
 int wcqp_tick_get_restart_result(wcqp_tick_t h, const wcqp_tick_restart_result* out) {
@@ -938,6 +996,27 @@ int wcqp_tick_get_restart_result(wcqp_tick_t h, const wcqp_tick_restart_result* 
         if (out->stopped_ticks) out->stopped_ticks[rc_.robots[r]] = rc_.stopped()[r];
     }
     if (out->stage) *out->stage = rc_.stage;
+    return WCQP_OK;
+}
+
+int wcqp_tick_get_recover_result(wcqp_tick_t h, const wcqp_tick_recover_result* out) {
+    if (!h || !out) return WCQP_E_INVALID;
+    auto& rc_ = h->restart;
+    if (!rc_.called || !rc_.recover) return WCQP_E_INVALID;
+    const wcqp_tick_restart_result shared{out->restarted, out->stopped_ticks, out->stage};
+    if (const int rc = wcqp_tick_get_restart_result(h, &shared); rc != WCQP_OK) return rc;
+    const size_t B = (size_t)h->d.batch;
+    for (size_t i = 0; i < B; ++i) {
+        if (out->status) out->status[i] = WCQP_RECOVER_KEPT;
+        if (out->iters) out->iters[i] = 0;
+        if (out->residual) { out->residual[2 * i] = 0.0; out->residual[2 * i + 1] = 0.0; }
+    }
+    for (size_t r = 0; r < rc_.robots.size(); ++r) {
+        const size_t i = (size_t)rc_.robots[r];
+        if (out->status) out->status[i] = rc_.status()[r];
+        if (out->iters) out->iters[i] = rc_.iters()[r];
+        if (out->residual) { out->residual[2 * i] = rc_.residual()[2 * r]; out->residual[2 * i + 1] = rc_.residual()[2 * r + 1]; }
+    }
     return WCQP_OK;
 }
 
