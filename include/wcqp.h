@@ -1037,7 +1037,7 @@ int wcqp_tick_rebase_plan(wcqp_tick_t h, int32_t shift, void* stream);
  * footstep or goal replan whose new sets would not fit returns WCQP_E_INVALID (see there) until a rebase.  cap has room for one step
  * more than can start within max_ticks, so a robot restarted over and over without a rebase between runs out.
  * Rows that never visit the host: wcqp_tick_recover_robots below runs the posture IK on the device and restarts from its result.
- * Not offered: a restart at a stage other than S, EXTERNAL and resident handles, a per-robot tick index. */
+ * Not offered: a restart at a stage other than S, a per-robot tick index.  EXTERNAL and resident handles: wcqp_tick_reset_robots below. */
 #define WCQP_TICK_RESTART_KEEP        0
 #define WCQP_TICK_RESTART_ALWAYS      1
 #define WCQP_TICK_RESTART_IF_STOPPED  2
@@ -1092,7 +1092,7 @@ int wcqp_tick_get_restart_result(wcqp_tick_t h, const wcqp_tick_restart_result* 
  * non-finite value in a given left_d, right_d, com_d, Rd_neck, q_guess, dcm0 or u_init row of a listed robot - rows of KEPT robots are
  * never read and may hold NaN.
  * wcqp_tick_get_recover_result: WCQP_E_INVALID before any recover call, and when the handle's last restart call was not one.
- * Not offered: a restart at a stage other than S, EXTERNAL and resident handles, a per-robot tick index. */
+ * Not offered: a restart at a stage other than S, a per-robot tick index.  EXTERNAL and resident handles: wcqp_tick_reset_robots below. */
 #define WCQP_RECOVER_KEPT          (-1)   /* mode KEEP: not listed                                          */
 #define WCQP_RECOVER_NOT_STOPPED   (-2)   /* IF_STOPPED and ik_fail == 0 when the call's kernels ran         */
 #define WCQP_RECOVER_NOT_STANDING  (-3)   /* soles from the plan, and record S is not a double support       */
@@ -1115,6 +1115,42 @@ typedef struct wcqp_tick_recover_result { /* HOST pointers, any may be NULL */
     int32_t* stage;
 } wcqp_tick_recover_result;
 int wcqp_tick_get_recover_result(wcqp_tick_t h, const wcqp_tick_recover_result* out);  /* waits for that call's event only */
+/* Robots of a sensor-fed fleet reset per robot: the caller's simulator put a robot back - it fell, or its episode ended -, and the
+ * controller follows.  On a streamed EXTERNAL handle a robot stops for good after one rejected reading or stage, and wcqp_tick_upload*
+ * rewinds every robot and synchronises the device.  wcqp_tick_reset_robots takes wcqp_tick_restart - mode, state0, q0, com0, dcm0, u_init,
+ * HOST rows, KEEP / ALWAYS / IF_STOPPED as there - at the stage S the next tick reads (the ticks enqueued so far).  THE RESET ROBOT - a
+ * listed robot that goes on (ALWAYS, or IF_STOPPED and ik_fail[i] > 0 when the call's kernels run; tests/helpers/tick_reset.py restates it):
+ *   State       THE RESTARTED ROBOT's, written by the same kernel from the call's rows.  dcm0 / u_init NULL: the standing ZMP of the two
+ *               soles of state0 with the restart's rounding rule (a handle without a resident plan knows no zmp_delta_*: the deltas are
+ *               0 there, the ZMP is the midpoint of the two sole origins).
+ *   EXTERNAL    the measured joints = q0; feedback_fail = 0; no stage and no contact pair in hand, as after an upload: the robot's next
+ *               stage rebuilds or copies its support-polygon rows.  A REJECTED READING at tick S: the robot keeps (com0, dcm0, u_init)
+ *               as its measured state and q0 as its measured joints, exactly as a robot rejected on tick 0 keeps the uploaded state, and
+ *               is stopped and counted again.  THE RULE stays one: a robot rejected at tick t > 0 keeps the hand-off record of parity
+ *               t - 1, and the call writes the three rows into that record (before any tick: into the rows wcqp_tick_download reports as
+ *               `measured`, which therefore shows the reset rows when S = 0).
+ *   Filters     (sensor filters on) the upload's rule for this robot: the CoM position filter at com0, its velocity filter at 0, and the
+ *               joint-velocity and wrench filters start AT the robot's next accepted reading - a per-robot FRESH mark in the filter
+ *               record, double-buffered with it: a second sensor call for the same tick starts from the same state, a rejected reading
+ *               leaves the robot fresh, an accepted one clears the mark.  Every upload clears every mark.
+ *   Plan        (resident_plan only) THE RESTARTED ROBOT's, word for word: stages below S bit for bit, every stage >= S the standing
+ *               stage of state0's soles with one new set in the robot's next free slot, plan in force "generated from S, no steps" -
+ *               the same fill kernel, set builder, slot accounting and owed bookkeeping.  Without a resident plan there is no plan
+ *               part: the caller's next wcqp_tick_set_desired_* is the robot's stage.
+ *   NOT touched the tick index, the logs below S, any other robot's row, any pointer a tick or a captured graph holds.
+ * ORDER: the call comes first in tick S's sequence, reset_robots -> set_desired_* / set_desired_from_plan -> set_*feedback_* -> run(1); with
+ * a stage or a feedback already in hand it returns WCQP_E_INVALID.  Enqueue-only on `stream`: the listed robots' rows are staged before it
+ * returns, a kept robot's rows are never read.  The HOST forms of the stage and the feedback wait for the call's kernels, whatever the
+ * stream.  Pending goal, rebase and restart calls are settled first; IF_STOPPED owes the plan in force as a restart does.  It is the
+ * handle's last restart call: wcqp_tick_get_restart_result reports it, wcqp_tick_get_recover_result returns WCQP_E_INVALID after it.  A
+ * call that lists nobody returns WCQP_OK and enqueues nothing.  Everything is checked on the host before anything changes.
+ * WCQP_E_UNSUPPORTED: a handle that is not streamed (internal plant, planned handles, the synthetic-gait EXTERNAL handle); a POSITION handle;
+ * a resident plan that was not generated.  WCQP_E_INVALID: not uploaded; the struct, mode, state0, q0 or com0 NULL; a mode above 2; a
+ * non-finite value in a listed robot's rows; S > max_ticks; a stage or a feedback in hand; on a resident handle a listed robot without a
+ * free set slot (wcqp_tick_rebase_plan frees the slots of past stages).
+ * Not offered: wcqp_tick_recover_robots on these handles (the caller's plant holds the posture), POSITION streamed handles, a reset at a
+ * stage other than S, soles taken from the measured feet. */
+int wcqp_tick_reset_robots(wcqp_tick_t h, const wcqp_tick_restart* r, void* stream);
 /* Per-step timings: every footstep carries its own durations (the reference's planner gives every step its own, between minStepDuration
  * and maxStepDuration; wcqp_unicycle_plan_timed_* below chooses them and fills exactly these two arrays).  THE TIMED PLAN is the plan
  * wcqp_tick_upload_footsteps defines (tests/helpers/footstep_plan_timed.py restates it), with four changes:
@@ -1328,7 +1364,10 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
                                   const double* q_meas, void* stream);
 /* the same from HOST pointers: staged through device memory of the handle and IN PLACE when the call returns (it synchronises: the host
  * arrays may be released at once, and the tick may then be run on any stream, a non-blocking one included).  With the device form the
- * caller orders the copy kernel's stream before the stream of the run call (the same stream does). */
+ * caller orders the copy kernel's stream before the stream of the run call (the same stream does).  On a handle with per-tick
+ * kinematics it first waits, on the host, for the event behind the handle's last wcqp_tick_run - and behind a wcqp_tick_reset_robots call
+ * since -, as wcqp_tick_set_sensor_feedback_host and wcqp_tick_set_desired_host do: new with wcqp_tick_reset_robots, and a host wait a
+ * caller whose ticks run on a non-blocking stream did not have before (the feedback of tick t is then never written under tick t - 1). */
 int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const double* com_meas, const double* zmp_meas, const double* q_meas);
 /* Sensor feedback (EXTERNAL plant with per-tick kinematics): the counterpart of wcqp_tick_set_feedback_* that takes what a robot
  * reports - WalkingModule::getFeedbacks (WM/src/WalkingModule.cpp:547) - and evaluates the measured state on the device, for tick

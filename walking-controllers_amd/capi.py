@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "wcqp_tick_set_sensor_feedback_device", "wcqp_tick_set_sensor_feedback_host",
     "wcqp_tick_set_desired_device", "wcqp_tick_set_desired_host", "wcqp_tick_set_desired_from_plan",
     "wcqp_tick_upload_footsteps", "wcqp_tick_upload_footsteps_timed", "wcqp_tick_replan_footsteps_timed", "wcqp_tick_get_plan", "wcqp_tick_replan_footsteps", "wcqp_tick_replan_goals", "wcqp_tick_get_goal_result",
-    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan", "wcqp_tick_restart_robots", "wcqp_tick_get_restart_result", "wcqp_tick_recover_robots", "wcqp_tick_get_recover_result", "wcqp_tick_set_swing_profile", "wcqp_tick_get_swing_profile",
+    "wcqp_tick_replan_goals_timed", "wcqp_tick_get_goal_timing", "wcqp_tick_rebase_plan", "wcqp_tick_restart_robots", "wcqp_tick_get_restart_result", "wcqp_tick_recover_robots", "wcqp_tick_get_recover_result", "wcqp_tick_reset_robots", "wcqp_tick_set_swing_profile", "wcqp_tick_get_swing_profile",
     "wcqp_qp_enqueue_steps", "wcqp_qp_plan_create", "wcqp_qp_plan_enqueue", "wcqp_qp_plan_destroy",
     "wcqp_slab_layout_for", "wcqp_qp_step_from_slabs",
     "wcqp_unicycle_create", "wcqp_unicycle_destroy", "wcqp_unicycle_plan_device", "wcqp_unicycle_plan_host",
@@ -447,6 +447,7 @@ def lib() -> C.CDLL:
         L.wcqp_tick_replan_goals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickGoals), C.c_void_p]
         L.wcqp_tick_rebase_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.wcqp_tick_restart_robots.argtypes = [C.c_void_p, C.POINTER(TickRestart), C.c_void_p]
+        L.wcqp_tick_reset_robots.argtypes = [C.c_void_p, C.POINTER(TickRestart), C.c_void_p]
         L.wcqp_tick_get_restart_result.argtypes = [C.c_void_p, C.POINTER(TickRestartResult)]
         L.wcqp_tick_recover_robots.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TickRecover), C.c_void_p]
         L.wcqp_tick_get_recover_result.argtypes = [C.c_void_p, C.POINTER(TickRecoverResult)]
@@ -1045,6 +1046,11 @@ class TickPipeline(_Handle):
         restart_robots(mode, dict(state0=p["state"], q0=p["q"], com0=com_d[:, :2]))."""
         if not self._holds_plan():
             raise ValueError("restart_robots on a handle created without planned_trajectories=True (or resident_plan=True)")
+        rs, _rows = self._restart_rows(mode, data)
+        check(lib().wcqp_tick_restart_robots(self._h, C.byref(rs), stream or None), "wcqp_tick_restart_robots")
+
+    def _restart_rows(self, mode, data: dict):
+        """wcqp_tick_restart from mode [B] and data (state0, q0, com0, optionally dcm0 / u_init), with the arrays it points into."""
         m = np.ascontiguousarray(mode, dtype=np.uint8)
         keep = {k: _f64(data[k]) for k in ("state0", "q0", "com0")}
         for k in ("dcm0", "u_init"):
@@ -1054,7 +1060,16 @@ class TickPipeline(_Handle):
             keep["q0"].shape[0] == self.batch and all(keep[k].shape == (self.batch, 2) for k in keep if k not in ("state0", "q0")), \
             (m.shape, {k: v.shape for k, v in keep.items()})
         rs = TickRestart(m.ctypes.data, *(keep[k].ctypes.data if k in keep else None for k in ("state0", "q0", "com0", "dcm0", "u_init")))
-        check(lib().wcqp_tick_restart_robots(self._h, C.byref(rs), stream or None), "wcqp_tick_restart_robots")
+        return rs, (m, keep)
+
+    def reset_robots(self, mode, data: dict, stream: Optional[int] = None):
+        """Robots of a sensor-fed fleet reset per robot, on the device (wcqp_tick_reset_robots, which defines the reset robot): a streamed
+        EXTERNAL handle, with or without resident_plan.  mode and data as restart_robots takes them.  A reset robot has the controller state
+        of an upload from the call's rows, measured joints q0, no rejected reading, no stage in hand, filters that start at its next
+        accepted reading and - on a resident plan - stands from the stage the next tick reads.  The call comes first in that tick's
+        sequence: reset_robots -> set_desired* -> set_*feedback* -> run(1).  Enqueue-only on `stream`; restart_result() reports it."""
+        rs, _rows = self._restart_rows(mode, data)
+        check(lib().wcqp_tick_reset_robots(self._h, C.byref(rs), stream or None), "wcqp_tick_reset_robots")
 
     def restart_result(self) -> dict:
         """What the last restart_robots call did (wcqp_tick_get_restart_result; waits for that call only): restarted [B] (bool),

@@ -3,6 +3,7 @@
 #pragma once
 #include "wcqp_internal.h"
 #include "tick_device.h"
+#include "sensors.h"
 
 namespace wcqp_tick {
 
@@ -103,6 +104,26 @@ struct PlanRestartDev {
     double delta[2][2];             // zmp_delta_left / zmp_delta_right
 };
 
+// wcqp_tick_reset_robots (plan_restart.hip): what only a streamed EXTERNAL handle keeps per robot, reset behind plan_restart_reset_kernel for
+// the slots it restarted - the rows of PlanRestartDev it reads are that call's.  Every array is indexed by ROBOT
+struct TickResetDev {
+    const int* robots;              // [n_robots] PlanRestartDev's
+    const int* restarted;           // [n_robots] written by plan_restart_reset_kernel ahead of this kernel
+    const double* q0;               // [n_robots][kDof]
+    const double* com0;             // [n_robots][2]
+    const double* dcm0;             // [n_robots][2], or NULL: `mid`
+    const double* u0;               // [n_robots][2], or NULL: `mid`
+    const double* mid;              // [n_robots][2] the standing ZMP plan_restart_reset_kernel wrote
+    double* q_meas;                 // [B][kDof]
+    long long* feedback_fail;       // [B]
+    int* pair;                      // [B][2] st_pair: -1, -1 as after an upload
+    double* st_rec; int* st_set_nc; // the live record [B][kPlanRec] and the row count of the robot's own set: 0 as after an upload
+    double* hand_prev;              // the hand-off records [B][kHandLen] of parity S - 1, where a reading rejected at tick S finds the measured
+                                    // state to keep; NULL at tick 0 (the host keeps the rows: wcqp_tick_s::meas0)
+    double* filt;                   // the filter slot the next sensor call reads [B][kFiltRec], or NULL on a handle without filters
+    int n_robots;
+};
+
 // a foot's ZMP point p_xy + R_2x2 delta of the sole `pose` (p 3 | R 9 row-major), every operation rounded on its own, as numpy does
 __device__ __forceinline__ double zmp_point_ax(const double* pose, const double* dl, int ax) {
 #pragma clang fp contract(off)
@@ -144,6 +165,9 @@ int plan_recover_gather_enqueue(const wcqp_tick::PlanRecoverDev& g, hipStream_t 
 int plan_recover_gate_enqueue(const wcqp_tick::PlanRecoverDev& g, hipStream_t stream);
 // its two kernels in stream order: decide-and-reset over the slots, then the fill over the tiles.  Enqueue-only
 int plan_restart_enqueue(const wcqp_tick::PlanRestartDev& g, hipStream_t stream);
+// wcqp_tick_reset_robots: plan_restart_reset_kernel, the reset of what only an EXTERNAL handle keeps, and - g.rec set: a resident plan - the
+// fill.  Enqueue-only
+int tick_reset_enqueue(const wcqp_tick::PlanRestartDev& g, const wcqp_tick::TickResetDev& e, hipStream_t stream);
 // its two kernels in stream order: d_i, the ZMP of the new stage 0 and the tick index first, then the rows.  Enqueue-only
 int plan_rebase_enqueue(const wcqp_tick::PlanRebaseDev& g, hipStream_t stream);
 // prologue, DCM pass and record pass of one upload, in stream order (plan_gen.hip); rec0 / rec1 (or NULL): events recorded around the record

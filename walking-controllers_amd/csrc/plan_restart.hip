@@ -14,6 +14,8 @@
 //                               dcm_vel entries, one 16-byte piece per lane.  Pieces of stages below S (the first tile) and at or above T
 //                               (the last) are skipped; a slot the first kernel did not restart leaves its tiles untouched.
 // Plain vector loads and stores, 64-bit row offsets (the records pass 4 GB), 32-bit piece indices inside a tile.
+// wcqp_tick_reset_robots (THE RESET ROBOT: a streamed EXTERNAL handle) runs the same two kernels with tick_reset_extern_kernel between
+// them, and without a resident plan the first of them alone with it (tick_reset_enqueue, below).
 #include "plan_gen.h"
 
 namespace {
@@ -104,19 +106,69 @@ __global__ __launch_bounds__(64) void plan_restart_fill_kernel(PlanRestartDev g)
     if (g.vel) reinterpret_cast<double2*>(g.vel)[w] = make_double2(0.0, 0.0);
 }
 
+// wcqp_tick_reset_robots (include/wcqp.h: THE RESET ROBOT): behind plan_restart_reset_kernel, one wave per slot, what only a streamed EXTERNAL
+// handle keeps of a robot that restarted - the measured joints at q0, no rejected reading, no stage and no pair in hand (the upload's:
+// wcqp::reset_streamed_stage), the measured state a reading rejected at tick S keeps - (com0, dcm0, u_init), in the hand-off record of parity
+// S - 1 where tick_feedback_kernel and tick_sensor_kernel read it -, and the filter record the next sensor call reads at rest by the
+// upload's rule, marked fresh (sensors.h).  Plain vector loads and stores, 64-bit row offsets.
+__global__ __launch_bounds__(64) void tick_reset_extern_kernel(TickResetDev e) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (!e.restarted[r]) return;
+    const size_t i = (size_t)e.robots[r];
+    for (int k = lane; k < kDof; k += 64) e.q_meas[i * kDof + k] = e.q0[(size_t)r * kDof + k];
+    for (int k = lane; k < kPlanRec; k += 64) e.st_rec[i * kPlanRec + k] = 0.0;
+    if (lane < 2) e.pair[i * 2 + lane] = -1;
+    if (lane == 2) { e.feedback_fail[i] = 0; e.st_set_nc[i] = 0; }
+    if (e.hand_prev && lane >= 4 && lane < 6) {
+        const int ax = lane - 4;
+        const size_t w = (size_t)r * 2 + ax;
+        double* hd = e.hand_prev + i * kHandLen;
+        hd[4 + ax] = e.com0[w]; hd[6 + ax] = e.dcm0 ? e.dcm0[w] : e.mid[w]; hd[10 + ax] = e.u0 ? e.u0[w] : e.mid[w];
+    }
+    if (e.filt) {
+        // {u_prev, y_prev} of the CoM position filter at com0, everything else 0 (wcqp::upload_state), the mark set
+        for (int k = lane; k < kFiltRec; k += 64) {
+            double v = 0.0;
+            if (k == kFiltCom || k == kFiltCom + 1) v = e.com0[(size_t)r * 2];
+            else if (k == kFiltCom + 4 || k == kFiltCom + 5) v = e.com0[(size_t)r * 2 + 1];
+            else if (k == kFiltFresh) v = 1.0;
+            e.filt[i * kFiltRec + k] = v;
+        }
+    }
+}
+
 }  // namespace
 
 namespace wcqp {
 
-int plan_restart_enqueue(const PlanRestartDev& g, hipStream_t stream) {
-    if (!g.robots || (!g.mode && !g.decided) || !g.state0 || !g.q0 || !g.com0 || !g.set_slot || !g.tiles || !g.pattern || !g.mid || !g.restarted || !g.stopped ||
-        !g.set_at || !g.set_code || !g.rec || !g.ref)
-        return WCQP_E_INVALID;
+// what both enqueue functions ask of the record: every array the reset kernel touches, and - plan: the handle holds a plan to stand the
+// robots on - the fill's arrays and bounds
+static bool restart_dev_valid(const PlanRestartDev& g, bool plan) {
+    if (!g.robots || (!g.mode && !g.decided) || !g.state0 || !g.q0 || !g.com0 || !g.set_slot || !g.pattern || !g.mid || !g.restarted || !g.stopped ||
+        !g.set_at || !g.set_code)
+        return false;
     if (!g.state || !g.q_des || !g.dq_prev || !g.dcm || !g.com || !g.c_ref || !g.p_star || !g.zmp_meas || !g.u_prev || !g.v_ref_prev || !g.v_star_prev ||
         !g.sel || !g.mpc_fail || !g.ik_fail || !g.hot_try || !g.hot_hit || !g.ik_lo || !g.ik_up)
-        return WCQP_E_INVALID;
+        return false;
+    if (g.n_robots < 1 || g.stage < 0) return false;
     // (stage S has a record, and every tile of the list lies within the T stages: the host builds it from S / 64 to (T - 1) / 64)
-    if (g.n_robots < 1 || g.n_tiles < 1 || g.traj_len < 1 || g.stage < 0 || g.stage >= g.traj_len) return WCQP_E_INVALID;
+    return !plan || (g.tiles && g.rec && g.ref && g.n_tiles >= 1 && g.traj_len >= 1 && g.stage < g.traj_len);
+}
+
+int tick_reset_enqueue(const PlanRestartDev& g, const TickResetDev& e, hipStream_t stream) {
+    if (!restart_dev_valid(g, g.rec != nullptr) || g.decided) return WCQP_E_INVALID;
+    if (e.robots != g.robots || e.restarted != g.restarted || e.mid != g.mid || !e.q0 || !e.com0 || !e.q_meas || !e.feedback_fail || !e.pair || !e.st_rec ||
+        !e.st_set_nc || e.n_robots != g.n_robots)
+        return WCQP_E_INVALID;
+    hipLaunchKernelGGL(plan_restart_reset_kernel, dim3((unsigned)g.n_robots), dim3(64), 0, stream, g);
+    hipLaunchKernelGGL(tick_reset_extern_kernel, dim3((unsigned)g.n_robots), dim3(64), 0, stream, e);
+    if (g.rec) hipLaunchKernelGGL(plan_restart_fill_kernel, dim3((unsigned)g.n_tiles), dim3(64), 0, stream, g);
+    WCQP_HIP_TRY(hipGetLastError());
+    return WCQP_OK;
+}
+
+int plan_restart_enqueue(const PlanRestartDev& g, hipStream_t stream) {
+    if (!restart_dev_valid(g, true)) return WCQP_E_INVALID;
     hipLaunchKernelGGL(plan_restart_reset_kernel, dim3((unsigned)g.n_robots), dim3(64), 0, stream, g);
     hipLaunchKernelGGL(plan_restart_fill_kernel, dim3((unsigned)g.n_tiles), dim3(64), 0, stream, g);
     WCQP_HIP_TRY(hipGetLastError());

@@ -34,9 +34,12 @@ struct SensorDev {
 };
 
 // One robot's filter record (doubles), {u_prev, y_prev} pairs: joint velocity j at 2 j; the wrench components the ZMP reads - fz tx ty of the
-// left sole, then of the right - at kFiltWrench + 2 c; axis a of the CoM at kFiltCom + 4 a (position pair, velocity pair).  528 bytes.
-constexpr int kFiltWrench = 46, kFiltCom = 58, kFiltRec = 66;
-static_assert(kFiltWrench == 2 * kDof && (kFiltRec * 8) % 16 == 0, "filter record layout");
+// left sole, then of the right - at kFiltWrench + 2 c; axis a of the CoM at kFiltCom + 4 a (position pair, velocity pair).  At kFiltFresh
+// the robot's FRESH mark (0.0 / 1.0; wcqp_tick_reset_robots sets it, every upload clears it): the joint-velocity and wrench filters start
+// AT the robot's next accepted reading, as every robot's do at the first reading after an upload (SensorDev::filt_first).  It lies in the
+// record, so it is double-buffered with it: a rejected reading carries it over, an accepted one clears it.  544 bytes.
+constexpr int kFiltWrench = 46, kFiltCom = 58, kFiltFresh = 66, kFiltRec = 68;
+static_assert(kFiltWrench == 2 * kDof && kFiltFresh == kFiltCom + 8 && (kFiltRec * 8) % 16 == 0, "filter record layout");
 
 }  // namespace wcqp_tick
 

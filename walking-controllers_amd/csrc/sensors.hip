@@ -31,7 +31,9 @@ static_assert(kDof * S_FS <= S_FRB && 32 * 4 <= S_FRB && S_V + 2 <= S_PER, "sens
 // second call for the same tick starts from the same state.  Lane j owns the state of its joints j and 16 + j, lanes 0 .. 5 write one
 // wrench component each, lanes 0 / 1 their axis of the CoM.  The rejection is known before the kinematics (finiteness of the RAW readings,
 // the total of the FILTERED normal forces), so the joint and wrench records are stored there, while their previous values are still in
-// registers: a rejected robot's record is carried over unchanged - its filters hold - and nothing non-finite ever enters one.
+// registers: a rejected robot's record is carried over unchanged - its filters hold - and nothing non-finite ever enters one.  The
+// robot's FRESH mark (sensors.h: kFiltFresh, set by wcqp_tick_reset_robots) is loaded with the record and makes this reading the robot's
+// first, as a.filt_first makes it everybody's; lane 6 stores it with the record: carried over when rejected, cleared when accepted.
 template <bool PL, bool FILT>
 __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
     using namespace wcqp_kin;
@@ -67,7 +69,8 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) sw[k] = ld2(fs + kFiltWrench + 2 * k);
         sc_p = ld2(fs + kFiltCom + 4 * (j & 1)); sc_v = ld2(fs + kFiltCom + 4 * (j & 1) + 2);
-        const bool first = a.filt_first != 0;
+        const double fresh = fs[kFiltFresh];         // (wcqp_tick_reset_robots: this robot's filters start at its next accepted reading)
+        const bool first = a.filt_first != 0 || fresh != 0.0;
         if (a.filt_mask & 1) {
             dqf0 = first ? dq0 : a.fb[0] * (dq0 + sd0.x) + a.fa[0] * sd0.y;
             dqf1 = (first || !var1) ? dq1 : a.fb[0] * (dq1 + sd1.x) + a.fa[0] * sd1.y;     // (stays 0 on a lane without a second joint)
@@ -89,6 +92,7 @@ __global__ __launch_bounds__(64) void tick_sensor_kernel(SensorDev a) {
                 for (int k = 0; k < 6; ++k)
                     if (j == k) st2(fd + kFiltWrench + 2 * k, rejected ? sw[k].x : wu[k], rejected ? sw[k].y : wf[k]);
             }
+            if (j == 6) fd[kFiltFresh] = rejected ? fresh : 0.0;
         }
     }
     // the stance side of tick t, as the tick kernel carries it: (t + phase0) % (2 step_ticks) >= step_ticks -> the right sole anchors

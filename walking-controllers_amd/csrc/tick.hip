@@ -710,6 +710,8 @@ int wcqp_tick_set_feedback_device(wcqp_tick_t h, const double* dcm_meas, const d
 
 int wcqp_tick_set_feedback_host(wcqp_tick_t h, const double* dcm_meas, const double* com_meas, const double* zmp_meas, const double* q_meas) {
     if (const int rc = feedback_ready(h, dcm_meas, com_meas, zmp_meas); rc != WCQP_OK) return rc;
+    // (a wcqp_tick_reset_robots call on a non-blocking stream re-records the run's event behind its kernels: wait for them, as the sensor form does)
+    if (const int rc = h->run.wait(); rc != WCQP_OK) return rc;
     FeedbackStage s((size_t)h->d.batch, dcm_meas, com_meas, zmp_meas, q_meas);
     // (synchronous copies on the NULL stream: they wait for what the handle's last tick left running on a blocking stream, and the
     // host arrays are consumed when they return)

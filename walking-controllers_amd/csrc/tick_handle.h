@@ -97,7 +97,8 @@ struct wcqp_tick_s {
     StagedBlock run;
     // the sensor form's low-pass filters (wcqp_tick_params.*_cut_frequency; sensors.h): two slots of per-robot state [2][B][kFiltRec].  A
     // sensor call reads slot filt_cur - what the last RUN tick left - and writes the other one; wcqp_tick_run commits it (filt_pending)
-    // when it consumes the tick, so a replaced call advances nothing and a tick fed by the plain form holds the state
+    // when it consumes the tick, so a replaced call advances nothing and a tick fed by the plain form holds the state.  A robot's FRESH mark
+    // (sensors.h: kFiltFresh; wcqp_tick_reset_robots writes it into slot filt_cur) lies in its record and is double-buffered with it
     double* filt_state = nullptr;
     int filt_mask = 0, filt_cur = 0;
     bool filt_started = false, filt_pending = false;
@@ -204,7 +205,8 @@ struct wcqp_tick_s {
     // int32, a recover call's status and iters rows [n] as int32.  THE RULE, for both calls: a robot whose restart the HOST decides - one
     // listed ALWAYS in a restart call - is on its standing plan in gp at once; a robot the DEVICE decides - IF_STOPPED, and every listed
     // robot of a recover call, whose IK must end SOLVED - is `owed`, and settle() puts it on the standing plan (origin `stage`, no steps,
-    // `keep_new` slots in use) if its row says it restarted.  The rows stay for wcqp_tick_get_restart_result / _recover_result
+    // `keep_new` slots in use) if its row says it restarted.  The rows stay for wcqp_tick_get_restart_result / _recover_result.
+    // wcqp_tick_reset_robots (a streamed EXTERNAL handle) is a restart call here; without a resident plan no robot is ever owed
     struct RestartCall {
         char* host = nullptr; size_t host_cap = 0;
         hipEvent_t ev = nullptr;

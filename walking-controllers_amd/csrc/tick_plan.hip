@@ -812,17 +812,38 @@ int wcqp_tick_rebase_plan(wcqp_tick_t h, int32_t shift, void* stream) {
     return WCQP_OK;
 }
 
+// the standing ZMP of the two soles of a state0 row on the host, operation for operation plan_restart_reset_kernel's (zmp_point_ax)
+static double standing_zmp_host(const double* st0, const double (*delta)[2], int ax) {
+#pragma clang fp contract(off)
+    const double* L = st0 + 24;
+    const double* R = st0 + 36;
+    const double rl = L[3 + 3 * ax] * delta[0][0] + L[4 + 3 * ax] * delta[0][1], rr = R[3 + 3 * ax] * delta[1][0] + R[4 + 3 * ax] * delta[1][1];
+    const double zl = L[ax] + rl, zr = R[ax] + rr;
+    return 0.5 * (zl + zr);
+}
+
 // THE RESTARTED ROBOT and THE RECOVERED ROBOT (include/wcqp.h), one path.  The host checks everything and compacts the listed robots' rows
 // into the call's block, one row per SLOT, so a kept robot's rows are never read.  A restart call (rs) brings the posture rows and the
 // device decides IF_STOPPED; a recover call (rv, prep) brings targets, and the device decides, solves the posture of the slots that go on
-// and restarts those that end SOLVED (plan_recover.hip around prepare.hip's kernel).  The host's own books: tick_handle.h, RestartCall
-static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare_t prep, const wcqp_tick_recover* rv, void* stream) {
+// and restarts those that end SOLVED (plan_recover.hip around prepare.hip's kernel).  The host's own books: tick_handle.h, RestartCall.
+// THE RESET ROBOT (`reset`: wcqp_tick_reset_robots, a restart call's rows on a streamed EXTERNAL handle) takes the same path: `plan` says
+// whether the handle holds a plan to stand the robot on - a resident one -, and what only such a handle keeps is reset behind the restart's
+// first kernel (plan_restart.hip)
+static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare_t prep, const wcqp_tick_recover* rv, void* stream, bool reset = false) {
     const bool recover = rv != nullptr;
     if (!h || (!rs && !rv)) return WCQP_E_INVALID;
-    if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
-    // (the caller's plant is the state there: a reset of the handle's rows would restart nothing)
-    if (h->external || h->resident || h->streamed) return WCQP_E_UNSUPPORTED;
-    if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    if (reset) {
+        // (a POSITION handle's non-linear IK keeps state of its own; the synthetic-gait EXTERNAL handle has no stage to start from)
+        if (!h->streamed || !h->external || h->position) return WCQP_E_UNSUPPORTED;
+        if (h->resident) { if (const int rc = replan_ready(h); rc != WCQP_OK) return rc; }
+        else if (!h->uploaded) return WCQP_E_INVALID;
+    } else {
+        if (!h->holds_plan()) return WCQP_E_UNSUPPORTED;
+        // (the caller's plant is the state there: wcqp_tick_reset_robots resets it with the handle's rows)
+        if (h->external || h->resident || h->streamed) return WCQP_E_UNSUPPORTED;
+        if (const int rc = replan_ready(h); rc != WCQP_OK) return rc;
+    }
+    const bool plan = !reset || h->resident;
     const uint8_t* mode = recover ? rv->mode : rs->mode;
     const double* dcm0 = recover ? rv->dcm0 : rs->dcm0;
     const double* u_init = recover ? rv->u_init : rs->u_init;
@@ -836,6 +857,8 @@ static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare
         const std::vector<double>& mine = wcqp::prepare_model_table(prep);
         if (mine.size() != tab.size() || std::memcmp(mine.data(), tab.data(), tab.size() * sizeof(double)) != 0) return WCQP_E_INVALID;
     }
+    // (the call comes first in tick S's sequence: a stage or a feedback in hand was made for the robot as it was)
+    if (reset && (h->desired_set || h->feedback_set)) return WCQP_E_INVALID;
     const TickDev& d = h->d;
     auto& gp = h->gp;
     auto& rc_ = h->restart;
@@ -859,8 +882,8 @@ static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare
             if (a.host && !finite(a.host + i * a.len, a.len)) return WCQP_E_INVALID;
         // the robot's slots in use by sets of stages < S - no stage >= S keeps its record, so the sets they alone name are free -, and one
         // more for the standing set (a robot the device decides: counted as if it restarted)
-        const int used = gp.keep[i] + gp.timeline(i).sets_up_to((S - 1 < h->p.max_ticks ? S - 1 : h->p.max_ticks));
-        if (used < 1 || used + 1 > cap) return WCQP_E_INVALID;
+        const int used = plan ? gp.keep[i] + gp.timeline(i).sets_up_to((S - 1 < h->p.max_ticks ? S - 1 : h->p.max_ticks)) : 0;
+        if (plan && (used < 1 || used + 1 > cap)) return WCQP_E_INVALID;
         robots.push_back((int)i); keep_new.push_back(used + 1);
     }
     if (robots.empty()) {      // (nothing is enqueued: the result is "nobody, at stage S")
@@ -869,7 +892,8 @@ static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare
         rc_.called = true; rc_.recover = recover; rc_.stage = S;
         return WCQP_OK;
     }
-    const size_t nr = robots.size(), n_tile = (size_t)((T + 63) / 64), t0 = (size_t)(S / 64), nt = nr * (n_tile - t0), nslots = B * (size_t)cap;
+    // (a handle without a plan: no tile, and the first kernel's set table has one entry per slot of the call, which nothing reads)
+    const size_t nr = robots.size(), n_tile = (size_t)((T + 63) / 64), t0 = (size_t)(S / 64), nt = plan ? nr * (n_tile - t0) : 0, nslots = plan ? B * (size_t)cap : nr;
     const size_t res_bytes = nr * wcqp_tick_s::RestartCall::row_bytes(recover);
     size_t off = 0;
     auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
@@ -891,8 +915,8 @@ static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare
         for (size_t r = 0; r < nr; ++r) {
             const size_t i = (size_t)robots[r];
             blob[o_mode + r] = (char)mode[i];
-            slot[r] = (int)(i * (size_t)cap) + keep_new[r] - 1;
-            for (size_t tl = t0; tl < n_tile; ++tl) { *tile++ = (int)r; *tile++ = (int)tl; }
+            slot[r] = plan ? (int)(i * (size_t)cap) + keep_new[r] - 1 : (int)r;
+            for (size_t tl = t0; plan && tl < n_tile; ++tl) { *tile++ = (int)r; *tile++ = (int)tl; }
             for (const In& a : in)
                 if (a.host) std::memcpy(blob.data() + a.at + r * a.len * 8, a.host + i * a.len, a.len * 8);
         }
@@ -919,8 +943,8 @@ static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare
     // the result rows, in the order RestartCall reads them
     g.stopped = reinterpret_cast<long long*>(buf + o_res); g.restarted = i32(o_res + nr * (recover ? 24 : 8));
     g.set_at = reinterpret_cast<long long*>(buf + o_at); g.set_code = i32(o_code);
-    g.rec = h->plan_rec; g.ref = const_cast<double*>(d.ref_traj.get());
-    g.vel = (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
+    g.rec = plan ? h->plan_rec : nullptr; g.ref = plan ? const_cast<double*>(d.ref_traj.get()) : nullptr;
+    g.vel = plan && (d.reactive || d.gain_sched) ? const_cast<double*>(d.dcm_vel.get()) : nullptr;
     g.mst = d.skew ? d.mst.p : nullptr; g.state = d.state.p; g.q_des = d.q_des.p; g.dq_prev = d.dq_prev.p;
     g.dcm = d.dcm.p; g.com = d.com.p; g.c_ref = d.c_ref.p; g.p_star = d.p_star.p; g.zmp_meas = d.zmp_meas.p; g.u_prev = d.u_prev.p;
     g.v_ref_prev = d.v_ref_prev.p; g.v_star_prev = d.v_star_prev.p;
@@ -957,17 +981,45 @@ static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare
         if (const int rc = wcqp::plan_recover_gate_enqueue(v, st); rc != WCQP_OK) return rc;
     }
     WCQP_HIP_TRY(hipMemsetAsync(g.set_code, 0xff, nslots * 4, st));
-    if (const int rc = wcqp::plan_restart_enqueue(g, st); rc != WCQP_OK) return rc;
-    hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
-                       h->set_A, h->set_b, h->set_nc);
-    WCQP_HIP_TRY(hipGetLastError());
+    const int t_hand = h->ticks_for_handoff();
+    if (reset) {
+        TickResetDev e{};
+        e.robots = g.robots; e.restarted = g.restarted; e.q0 = g.q0; e.com0 = g.com0; e.dcm0 = g.dcm0; e.u0 = g.u0; e.mid = g.mid;
+        e.q_meas = h->q_meas; e.feedback_fail = h->feedback_fail; e.pair = h->st_pair; e.st_rec = h->st_rec; e.st_set_nc = h->st_set_nc;
+        // THE RULE for a reading rejected at tick S: it keeps the hand-off record of parity S - 1 (tick.hip, sensors.hip), so the reset rows go there
+        e.hand_prev = t_hand > 0 ? d.hand.p + (size_t)((t_hand - 1) & 1) * B * kHandLen : nullptr;
+        // (no feedback is in hand, so no sensor call's write is pending: slot filt_cur is the one the next sensor call reads)
+        e.filt = h->filt_state ? h->filt_state + (size_t)h->filt_cur * B * kFiltRec : nullptr;
+        e.n_robots = (int)nr;
+        if (const int rc = wcqp::tick_reset_enqueue(g, e, st); rc != WCQP_OK) return rc;
+    } else if (const int rc = wcqp::plan_restart_enqueue(g, st); rc != WCQP_OK) return rc;
+    if (plan) {
+        hipLaunchKernelGGL(plan_hull_sets_kernel, dim3((unsigned)((nslots + 127) / 128)), dim3(128), 0, st, (int)nslots, plan_rect(h), h->plan_rec, g.set_at, g.set_code,
+                           h->set_A, h->set_b, h->set_nc);
+        WCQP_HIP_TRY(hipGetLastError());
+    }
     WCQP_HIP_TRY(hipMemcpyAsync(rc_.host, buf + o_res, res_bytes, hipMemcpyDeviceToHost, st));
     WCQP_HIP_TRY(hipEventRecord(rc_.ev, st));
     if (const int rc = h->rp.guard(st); rc != WCQP_OK) return rc;
     rc_.called = true; rc_.recover = recover; rc_.stage = S; rc_.pending = true; rc_.owed.clear();
-    for (size_t r = 0; r < nr; ++r) {
+    for (size_t r = 0; plan && r < nr; ++r) {
         if (!recover && mode[robots[r]] == WCQP_TICK_RESTART_ALWAYS) h->stand_from((size_t)robots[r], S, keep_new[r]);
         else rc_.owed.push_back((int)r);
+    }
+    if (reset) {
+        // the HOST forms of tick S's stage and feedback work on the NULL stream behind the last run's event: from here on behind this call
+        if (h->run.done) { if (const int rc = h->run.guard(st); rc != WCQP_OK) return rc; }
+        // before any tick wcqp_tick_download reports the uploaded measured state from the host's rows: the reset robots' are the call's
+        // (ALWAYS only: no robot is stopped there, so IF_STOPPED resets none)
+        for (size_t r = 0; t_hand == 0 && r < nr; ++r) {
+            const size_t i = (size_t)robots[r];
+            if (mode[i] != WCQP_TICK_RESTART_ALWAYS || h->meas0.size() != B * 6) continue;
+            for (int ax = 0; ax < 2; ++ax) {
+                const double mid = standing_zmp_host(rs->state0 + i * kStateLen, gp.delta, ax);
+                h->meas0[i * 6 + ax] = dcm0 ? dcm0[2 * i + ax] : mid; h->meas0[i * 6 + 2 + ax] = rs->com0[2 * i + ax];
+                h->meas0[i * 6 + 4 + ax] = u_init ? u_init[2 * i + ax] : mid;
+            }
+        }
     }
     rc_.robots.swap(robots); rc_.keep_new.swap(keep_new);
     return WCQP_OK;
@@ -976,6 +1028,11 @@ static int restart_call(wcqp_tick_t h, const wcqp_tick_restart* rs, wcqp_prepare
 int wcqp_tick_restart_robots(wcqp_tick_t h, const wcqp_tick_restart* rs, void* stream) {
     if (!rs) return WCQP_E_INVALID;
     return restart_call(h, rs, nullptr, nullptr, stream);
+}
+
+int wcqp_tick_reset_robots(wcqp_tick_t h, const wcqp_tick_restart* rs, void* stream) {
+    if (!rs) return WCQP_E_INVALID;
+    return restart_call(h, rs, nullptr, nullptr, stream, true);
 }
 
 int wcqp_tick_recover_robots(wcqp_tick_t h, wcqp_prepare_t prepare, const wcqp_tick_recover* rv, void* stream) {
